@@ -11,12 +11,15 @@ rank 0.  Started without a launcher (`python bench.py --gpus N`, WORLD_SIZE unse
 the GPU - starts the N ranks itself as child processes and relays rank 0's JSON line; started by torch.distributed.run
 it reads RANK / LOCAL_RANK / WORLD_SIZE / MASTER_* from the environment.
 
-Prints ONE JSON line on rank 0.  `roofline` is measured live with HIP events on the launch stream (each op replayed 20x
-between one event pair) for the kernel instantiation with the largest share of the step; `cpu_baseline` times the
-reference's fake-quant CPU op sequence (oracle/fakequant_torch.py) on the host cores (N=1 only).
-`--config w6a6|jasper` runs BASELINE.json's configurations 3 / 4 through the same loop (config 2 is the default and the
-headline).  At N = 1 the default run ALSO measures, after the headline region and never inside it, 20 steps each of config 3,
-config 4 and config 2 with log-probs written (`other_configs` in the JSON line; `--no-other-configs` skips them)."""
+Prints ONE JSON line on rank 0.  A plain run sets up, warms up, times exactly `--steps` steps and prints the headline
+(`value`, `ms_per_step`); `--dump-outputs DIR` then also writes what the last timed step returned as DIR/<name>.npy.
+`--full` adds, after the headline region and never inside it: every step in flight checked bit for bit against its serial
+result; `roofline`, measured live with HIP events on the launch stream (each op replayed 20x between one event pair) for
+the kernel instantiation with the largest share of the step; and at N = 1 the one-step-in-flight run, 20 steps each of
+config 3, config 4 and config 2 with log-probs written (`other_configs`; `--no-other-configs` skips them) and
+`cpu_baseline`, the reference's fake-quant CPU op sequence (oracle/fakequant_torch.py) on the host cores
+(`--no-cpu-baseline` skips it).  `--config w6a6|jasper` runs BASELINE.json's configurations 3 / 4 through the same loop
+(config 2 is the default and the headline)."""
 import argparse
 import json
 import os
@@ -62,7 +65,13 @@ def parse_args(argv=None):
     ap.add_argument('--warmup', type=int, default=5)
     ap.add_argument('--config', choices=sorted(CONFIGS), default='quartznet',
                     help='quartznet = BASELINE.json config 2 (headline); w6a6 = config 3; jasper = config 4')
-    ap.add_argument('--no-cpu-baseline', action='store_true')
+    ap.add_argument('--full', action='store_true',
+                    help='after the headline region also check the steps in flight against their serial results and measure '
+                         'the roofline, the one-step-in-flight run, the other configs and the CPU baseline')
+    ap.add_argument('--dump-outputs', metavar='DIR',
+                    help='write what the last timed step returned (tokens, encoded lengths; log-probs with --gather logits) '
+                         'as DIR/<name>.npy in float32')
+    ap.add_argument('--no-cpu-baseline', action='store_true', help='(--full) skip the CPU baseline')
     ap.add_argument('--tile', type=int, default=0, choices=[0, 32, 64, 128],
                     help='frames per work-group of the separable-layer kernels: 32 = lowest single-step latency; 64 / 128 = '
                          'less weight / halo / tap-row traffic per frame but 1/2, 1/4 of the work-groups (128: the plain '
@@ -71,7 +80,7 @@ def parse_args(argv=None):
     ap.add_argument('--streams', type=int, default=int(os.environ.get('QASR_BENCH_STREAMS', 0)),
                     help='independent steps in flight per GPU (each on its own HIP stream + engine arena); 0 = the config default')
     ap.add_argument('--no-other-configs', action='store_true',
-                    help='skip the extra measurements of BASELINE.json configs 3 / 4 and of config 2 with log-probs (N = 1 only)')
+                    help='(--full) skip the extra measurements of BASELINE.json configs 3 / 4 and of config 2 with log-probs (N = 1 only)')
     ap.add_argument('--gather', choices=['tokens', 'logits'], default='tokens',
                     help='what the per-step exchange sends to rank 0: int32 greedy tokens [B, T\'] (default; conv_asr.py:275 + '
                          'ctc_models.py:405) or the float32 CTC log-probs [B, T\', 29] (north_star\'s wording; the step then writes them)')
@@ -81,7 +90,20 @@ def parse_args(argv=None):
     ap.add_argument('--dry-run', action='store_true',
                     help='rank plumbing only (launcher, process group, blob broadcast, per-step token gather) on synthetic '
                          'payloads: no model, no engine, no GPU needed (gloo when no GPU is visible)')
-    return ap.parse_args(argv)
+    args = ap.parse_args(argv)
+    if args.steps < 1:
+        ap.error('--steps must be at least 1')
+    return args
+
+
+def dump_outputs(path, arrays):
+    """`--dump-outputs`: every array that is not None as path/<name>.npy in float32 (token ids and lengths are small
+    integers, exact in float32), for output-by-output comparison of two builds on the same seeded inputs."""
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    for name, t in arrays.items():
+        if t is not None:
+            np.save(os.path.join(path, name + '.npy'), t.detach().cpu().numpy().astype(np.float32))
 
 
 # ------------------------------------------------------------------------------------------------ launcher
@@ -557,17 +579,18 @@ class Workload:
 
     def timed(self, lane, steps, warmup, gathered=None):
         """One-time setup like the model build (each engine's first forward launches kernel by kernel, the second is captured
-        into its hipGraph; the serial results of that phase are the reference every later step must reproduce), `warmup`
-        untimed steps, then EXACTLY `steps` steps between barrier + synchronize pairs."""
+        into its hipGraph; with --full the serial results of that phase are the reference every later step must reproduce),
+        `warmup` untimed steps, then EXACTLY `steps` steps between barrier + synchronize pairs."""
         import torch
         env, step_trace = self.env, self.step_trace
         dist = env['dist'] if (env['use_dist'] and gathered is not False) else None
         S = lane['S']
+        check = self.args.full
         ref = []
         for i in range(2 * S):
             t_ = self.step(lane, i, gathered)
             torch.cuda.synchronize()
-            if i >= S:
+            if check and i >= S:
                 ref.append(t_.clone())
         for i in range(warmup):
             self.step(lane, i, gathered)
@@ -597,7 +620,7 @@ class Workload:
             dist.barrier()
         dt = time.perf_counter() - t0
         # every step in flight decodes its own batch: each must reproduce its serial result bit for bit
-        for k, t_ in last.items():
+        for k, t_ in (last.items() if check else ()):
             if not torch.equal(t_, ref[k]):
                 raise SystemExit(f'bench: stream {k} produced different tokens with other steps in flight')
         if dist is not None and env['rank'] == 0 and gathered is not None:
@@ -712,6 +735,10 @@ def run(args):
     gathered = ([[torch.empty(gshape, dtype=gdtype, device=comm_dev) for _ in range(world)] for _ in range(S)]
                 if rank == 0 else None)
     dt, t_enq, tokens = w.timed(lane, args.steps, args.warmup, gathered)
+    if args.dump_outputs and rank == 0:
+        # the caller-owned buffers of the last timed step's stream: nothing has run on them since that step (timed synchronises)
+        logp, _, enc_len = lane['bufs'][(args.steps - 1) % S]['out']
+        dump_outputs(args.dump_outputs, {'tokens': tokens, 'encoded_lengths': enc_len, 'log_probs': logp})
     if use_dist:
         tmax = torch.tensor([dt], dtype=torch.float64, device=comm_dev)
         dist.all_reduce(tmax, op=dist.ReduceOp.MAX)
@@ -751,7 +778,7 @@ def run(args):
             if rank == 0:
                 result['gather_checked_ranks'] = checked
 
-    if rank == 0:
+    if rank == 0 and args.full:
         # ---- roofline of the dominant kernel, HIP events on the launch stream ---------------------------------
         # every op is replayed 20x back to back between one HIP event pair on the launch stream
         # (qasr_engine_time_ops); buffers hold the real activations of the last timed step
@@ -776,7 +803,7 @@ def run(args):
     for e_ in lane['engs']:
         e_.close()
 
-    if world == 1 and rank == 0:
+    if world == 1 and rank == 0 and args.full:
         # ---- one step in flight (32-frame tiles): the latency view of the same workload ------------------------
         if S > 1:
             lane1 = w.make_lane(1, 32)

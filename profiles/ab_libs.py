@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """A/B of several builds of the native library in ONE gpurun call, interleaved (A B C A B C ...), each run a fresh process:
     python profiles/ab_libs.py out.txt hip tail pf both            # names = q-asr_amd/qasr/libqasr_<name>.so
-Per run: bench.py --no-cpu-baseline --no-other-configs at K = 200 and at the driver's K = 20; reported: ms/step with 4 steps in
+Per run: bench.py --full --no-cpu-baseline --no-other-configs at K = 200 and at K = 20; reported: ms/step with 4 steps in
 flight, one step in flight, and the dominant kernel alone (HIP events)."""
 import json
 import os
@@ -14,13 +14,13 @@ extra = os.environ.get('AB_EXTRA', '').split()
 rounds = int(os.environ.get('AB_ROUNDS', 2))
 rows = {n: [] for n in names}
 with open(out_path, 'w') as fh:
-    fh.write(f'# bench.py {" ".join(extra)} --no-cpu-baseline --no-other-configs, builds interleaved, {rounds} rounds; columns: K, ms/step (4 in flight), '
+    fh.write(f'# bench.py {" ".join(extra)} --full --no-cpu-baseline --no-other-configs, builds interleaved, {rounds} rounds; columns: K, ms/step (4 in flight), '
              'ms/step (1 in flight, 32-frame tiles), dominant kernel, its launch alone (us)\n')
     for r in range(rounds):
         for n in names:
             lib = os.path.join(ROOT, 'q-asr_amd', 'qasr', f'libqasr_{n}.so')
             for K, W in ((200, 10), (20, 5)):
-                p = subprocess.run([sys.executable, os.path.join(ROOT, 'bench.py'), '--steps', str(K), '--warmup', str(W), '--no-cpu-baseline',
+                p = subprocess.run([sys.executable, os.path.join(ROOT, 'bench.py'), '--steps', str(K), '--warmup', str(W), '--full', '--no-cpu-baseline',
                                     '--no-other-configs'] + extra, capture_output=True, text=True, env=dict(os.environ, QASR_LIB=lib))
                 if p.returncode:
                     fh.write(f'{n:8s} K={K}: FAILED rc={p.returncode}: {p.stderr[-400:]}\n')

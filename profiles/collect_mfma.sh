@@ -33,7 +33,7 @@ for G in A B C D E; do
   done
   [ -z "$USE" ] && continue
   echo "[collect_mfma] group $G:$USE"
-  rocprofv3 --kernel-trace --pmc $USE --output-format csv -d $OUT/pmcm_${TAG}_$G -o c -- python3 $R/bench.py --steps 8 --warmup 2 --no-cpu-baseline --no-other-configs --streams 1 --tile $TILE $EXTRA > $OUT/pmcm_${TAG}_$G.log 2>&1 \
+  rocprofv3 --kernel-trace --pmc $USE --output-format csv -d $OUT/pmcm_${TAG}_$G -o c -- python3 $R/bench.py --full --steps 8 --warmup 2 --no-cpu-baseline --no-other-configs --streams 1 --tile $TILE $EXTRA > $OUT/pmcm_${TAG}_$G.log 2>&1 \
     || echo "group $G failed (see pmcm_${TAG}_$G.log)" >> $OUT/${TAG}_pmc_MFMA.skipped
 done
 GRAFT_REPO_ROOT=$R python3 - "$TAG" "$OUT" "$EXTRA" "$TILE" <<'PY'
@@ -63,7 +63,7 @@ for k, cs in agg.items():
     if dur[k][0]:
         row['avg_us_under_pmc'] = round(dur[k][1] / dur[k][0], 2)
     kern[k] = row
-doc = {'tag': tag, 'command': f'bench.py --steps 8 --warmup 2 --no-cpu-baseline --no-other-configs --streams 1 --tile {tile} {extra}'.strip(),
+doc = {'tag': tag, 'command': f'bench.py --full --steps 8 --warmup 2 --no-cpu-baseline --no-other-configs --streams 1 --tile {tile} {extra}'.strip(),
        'note': '', 'kernels': kern}
 path = os.path.join(out, f'{tag}_pmc_MFMA.json')
 json.dump(doc, open(path, 'w'), indent=1)

@@ -369,7 +369,7 @@ def test_bench_exchange_steps_on_a_one_rank_rccl_communicator():
     for k in ('RANK', 'LOCAL_RANK', 'WORLD_SIZE'):
         env.pop(k, None)
     out = subprocess.run([sys.executable, os.path.join(ROOT, 'bench.py'), '--gpus', '1', '--steps', '8', '--warmup', '2',
-                          '--no-cpu-baseline'], capture_output=True, text=True, timeout=600, env=env)
+                          '--full', '--no-cpu-baseline'], capture_output=True, text=True, timeout=600, env=env)
     assert out.returncode == 0, out.stderr[-3000:]
     line = json.loads(out.stdout.strip().splitlines()[-1])
     assert line['n_gpus'] == 1 and line['n_ranks_seen'] == 1 and line['steps'] == 8
@@ -390,7 +390,7 @@ def test_bench_two_ranks_with_real_engines_gloo_rehearsal(gather):
         env.pop(k, None)
     out = subprocess.run([sys.executable, '-m', 'torch.distributed.run', '--nnodes=1', '--nproc-per-node', '2', '--master-addr',
                           '127.0.0.1', '--master-port', '29547' if gather == 'tokens' else '29549', os.path.join(ROOT, 'bench.py'),
-                          '--gpus', '2', '--steps', '8', '--warmup', '2', '--no-cpu-baseline', '--gather', gather, '--check-gather'],
+                          '--gpus', '2', '--steps', '8', '--warmup', '2', '--full', '--no-cpu-baseline', '--gather', gather, '--check-gather'],
                          capture_output=True, text=True, timeout=900, env=env)
     assert out.returncode == 0, out.stderr[-3000:]
     line = json.loads([l for l in out.stdout.strip().splitlines() if l.startswith('{')][-1])
@@ -400,6 +400,42 @@ def test_bench_two_ranks_with_real_engines_gloo_rehearsal(gather):
     assert line['config']['global_batch'] == 64 and line['config']['steps_in_flight'] == 4
     assert ('logits gather' if gather == 'logits' else 'token gather') in line['config']['parallelism']
     assert line['value'] > 0
+
+
+def test_bench_plain_run_dumps_the_last_timed_step(tmp_path):
+    """A plain bench run (no --full) times exactly --steps steps, prints the headline without the --full figures, and
+    --dump-outputs writes what the last timed step returned.  This process rebuilds the same model, runs the same seeded audio
+    batch (step K - 1 ran on stream (K - 1) % S) through a fresh engine and compares: tokens and encoded lengths bit for bit,
+    the log-probs (written with --gather logits) to float rounding."""
+    import bench
+    from qasr import engine
+    env = dict(os.environ)
+    for k in ('RANK', 'LOCAL_RANK', 'WORLD_SIZE', 'MASTER_ADDR', 'MASTER_PORT', 'QASR_BENCH_FORCE_DIST'):
+        env.pop(k, None)
+    steps, dump = 7, tmp_path / 'outputs'
+    out = subprocess.run([sys.executable, os.path.join(ROOT, 'bench.py'), '--gpus', '1', '--steps', str(steps), '--warmup', '2',
+                          '--gather', 'logits', '--dump-outputs', str(dump)], capture_output=True, text=True, timeout=600, env=env)
+    assert out.returncode == 0, out.stderr[-3000:]
+    line = json.loads(out.stdout.strip().splitlines()[-1])
+    assert line['steps'] == steps and line['ms_per_step'] > 0
+    assert abs(line['value'] - 32 * 5.0 / (line['ms_per_step'] * 1e-3)) / line['value'] < 1e-6
+    assert not {'roofline', 'cpu_baseline', 'other_configs', 'single_stream_ms_per_step'} & set(line), sorted(line)
+    got = {n: np.load(dump / f'{n}.npy') for n in ('tokens', 'encoded_lengths', 'log_probs')}
+    assert all(a.dtype == np.float32 for a in got.values())
+
+    dev = torch.device('cuda', 0)
+    blob, _, fb, window, _, _ = bench.build_model(dev, 'QuartzNet15x5Base-En', 8, 8)
+    fb, window = fb.to(dev), window.to(dev)
+    S = line['config']['steps_in_flight']
+    audio = torch.from_numpy(synth.make_audio(32, bench.SAMPLES, seed=100 + (steps - 1) % S)).to(dev)
+    alen = torch.full((32,), bench.SAMPLES, dtype=torch.int32, device=dev)
+    eng = engine.Engine(blob, 0, tile=128 if S > 1 else 32)
+    logp, tokens, enc_len = eng.forward_audio(audio, alen, fb, window, engine.frontend_plan(fb), 0.97, 16, want_logp=True)
+    torch.cuda.synchronize()
+    np.testing.assert_array_equal(got['tokens'], tokens.cpu().numpy())
+    np.testing.assert_array_equal(got['encoded_lengths'], enc_len.cpu().numpy())
+    np.testing.assert_allclose(got['log_probs'], logp.cpu().numpy(), rtol=1e-6, atol=1e-6)
+    eng.close()
 
 
 def test_legacy_create_keeps_normalised_feats_and_read_tensor_refuses_unstored(golden_dir):
