@@ -171,7 +171,8 @@ typedef struct qasr_engine_opts {
   int32_t sep_gen;             /* 0 / 2: k_sep2 where it has the shape; 1: round 1's k_sep everywhere */
   int32_t fuse_dw;             /* depthwise conv fused into the following 1x1 conv's launch */
   int32_t fuse_stem;           /* block 0 (lengths, first-layer QuantAct, strided depthwise, 1x1) as one launch */
-  int32_t fuse_decoder;        /* decoder conv + log-softmax + argmax + encoded lengths as one launch */
+  int32_t fuse_decoder;        /* decoder conv + log-softmax + argmax + encoded lengths fused: one launch (k_dec) up to 32
+                                  classes, two (k_decw) for 33 .. 8192; 0: the generic k_sep logits + k_logsoftmax */
   int32_t graph;               /* replay the forward as one hipGraph launch (second call with the same buffers captures) */
   int32_t retired_whole_utterance; /* round 1's k_utt kernels, removed in round 4: must be <= 0 */
   int32_t res_tile128;         /* block-end (residual) layers on 128-frame tiles too when tile_frames == 128 */
@@ -194,7 +195,13 @@ int qasr_engine_create_ex(const void* blob, size_t blob_bytes, int device, const
  * logp    device f32 [B][T'][n_classes] log-probabilities (may be NULL)
  * tokens  device i32 [B][T']           greedy argmax (may be NULL)
  * lens_out device i32 [B]              encoded lengths (may be NULL)
- * T' = qasr_engine_out_frames(e, T). */
+ * T' = qasr_engine_out_frames(e, T).
+ * Decoder kernels by width (fuse_decoder on, the default): up to 32 classes k_dec, one launch (decoder input channels a
+ * multiple of 256, at most 2048); 33 .. 8192 classes (e.g. QuartzNet15x5Base-Zh's 5207) with at most 2048 decoder input
+ * channels k_decw, two launches (per-group softmax statistics, then tokens / lengths and, when logp is
+ * not NULL, the log-probabilities), its workspace part of the plan; any other shape, or fuse_decoder = 0: k_sep logits + k_logsoftmax
+ * (qasr_engine_op_label names the kernel a plan uses).
+ * Tokens are the argmax of the same float32 logits on every path; log-probabilities agree to rounding. */
 int qasr_engine_forward(qasr_engine* e, void* stream, const float* feats, const int32_t* lens, int B, int T,
                         float* logp, int32_t* tokens, int32_t* lens_out);
 /* The same with the mel front-end in front (qasr_frontend_mel_planned into the caller's `feats` [B][n_mels][T_pad] /
@@ -220,7 +227,8 @@ int qasr_engine_num_launches(const qasr_engine* e);
 int qasr_engine_read_acc(qasr_engine* e, int op, int pane, int32_t* host_out, size_t n_elems);
 /* read_tensor also serves a production (non-debug) engine for a tensor whose arena slot no later tensor reused - e.g.
  * the decoder's input, the final encoder codes - and refuses the others.  Every engine refuses a tensor its launch plan
- * never stores (a depthwise output inside the fused layer's launch, k_stem's intermediates, the float logits inside k_dec). */
+ * never stores (a depthwise output inside the fused layer's launch, k_stem's intermediates, the float logits inside
+ * k_dec / k_decw). */
 int qasr_engine_read_tensor(qasr_engine* e, int tensor, void* host_out, size_t n_bytes, int* T_out, int* Tp_out);
 /* average device time (ms) per op kind over the last forward, measured with HIP events (debug engines) */
 int qasr_engine_last_op_ms(qasr_engine* e, float* ms_per_op, int n_ops);

@@ -104,6 +104,9 @@ struct qasr_engine {
   bool fuse_dec = true;                // decoder conv + log-softmax + argmax in one launch (QASR_NO_FUSE_DEC=1: two launches)
   std::vector<char> rq_skip;           // per op: REQUANT op served by the launch of an earlier REQUANT op of the same stored value
   std::vector<char> dec_skip;          // per op: LOGSOFTMAX op that ran inside the preceding decoder launch
+  std::vector<char> dec_wide;          // per op: decoder op that ran as k_decw (two launches)
+  void* decw_ws = nullptr;             // k_decw's per-(frame, class group) partials: part of the plan (no allocation in forward)
+  size_t decw_ws_bytes = 0;
   bool tile128 = true;                 // tile_frames == 128 (QASR_TILE128=0: k_sep2's plain layers stay on 64-frame tiles, A/B runs)
   bool res_tile128 = true;             // block-end layers on 128-frame tiles too (qasr_engine_opts.res_tile128)
   bool dense_tile128 = true;           // QASR_DENSE_TILE128=0 keeps Jasper's dense convs on 64-frame tiles (A/B runs)
@@ -150,6 +153,9 @@ static void free_plan(qasr_engine* e) {
   e->norm_stats = nullptr;
   e->norm_stats_bytes = 0;
   e->norm_tiles = e->norm_frames = 0;
+  if (e->decw_ws) (void)hipFree(e->decw_ws);
+  e->decw_ws = nullptr;
+  e->decw_ws_bytes = 0;
   for (auto& v : e->acc_dbg)
     for (auto p : v)
       if (p) (void)hipFree(p);
@@ -158,6 +164,8 @@ static void free_plan(qasr_engine* e) {
   e->B = e->T0 = 0;
   e->forwarded = false;
 }
+
+static void build_sep(qasr_engine* e, uint32_t oi, SepP& p);
 
 static int build_plan(qasr_engine* e, int B, int T0) {
   free_plan(e);
@@ -181,6 +189,7 @@ static int build_plan(qasr_engine* e, int B, int T0) {
   e->fused_dw.assign(h.n_ops, -1);
   e->skip.assign(h.n_ops, 0);
   e->dec_skip.assign(h.n_ops, 0);
+  e->dec_wide.assign(h.n_ops, 0);
   e->rq_skip.assign(h.n_ops, 0);
   if (e->fuse)
     for (uint32_t oi = 0; oi + 1 < h.n_ops; ++oi) {
@@ -193,6 +202,19 @@ static int build_plan(qasr_engine* e, int B, int T0) {
       if (e->tdesc[d.outs[0].tensor].last_use != (int)oi + 1 || (d.flags & QASR_F_EXACT_Z)) continue;
       e->fused_dw[oi + 1] = (int)oi;
       e->skip[oi] = 1;
+    }
+  // a production engine's fused wide decoder (k_decw) never stores the float logits [B][T][C] (167 MB at bs32 x 500
+  // frames x 5207 classes): that tensor gets no arena slot; launch_op takes the same decision from the same shapes
+  std::vector<char> no_slot(h.n_tensors, 0);
+  if (e->fuse_dec && !e->debug)
+    for (uint32_t oi = 0; oi + 1 < h.n_ops; ++oi) {
+      const qasr_op_desc& op = e->ops[oi];
+      if (op.kind != QASR_OP_PW || !(op.flags & QASR_F_LOGITS) || e->ops[oi + 1].kind != QASR_OP_LOGSOFTMAX ||
+          e->ops[oi + 1].in != op.outs[0].tensor)
+        continue;
+      SepP p{};
+      build_sep(e, oi, p);
+      if (!decoder_fusable(p) && decoder_wide_fusable(p)) no_slot[op.outs[0].tensor] = 1;
     }
   // greedy arena: a slot is reused once its tensor's last reader has been enqueued (stream order makes that safe)
   std::vector<int> free_slots;
@@ -220,7 +242,7 @@ static int build_plan(qasr_engine* e, int B, int T0) {
   };
   for (uint32_t oi = 0; oi < h.n_ops; ++oi) {
     for (uint32_t i = 1; i < h.n_tensors; ++i)      // tensor 0 is the caller's feature buffer
-      if (e->tens[i].d.producer == (int)oi && acquire(e->tens[i]) < 0) return fail(QASR_ERR_HIP, "hipMalloc failed (arena)");
+      if (e->tens[i].d.producer == (int)oi && !no_slot[i] && acquire(e->tens[i]) < 0) return fail(QASR_ERR_HIP, "hipMalloc failed (arena)");
     for (uint32_t i = 1; i < h.n_tensors; ++i) {
       TensorRT& t = e->tens[i];
       // a depthwise op fused into the next op's launch reads its input THERE: the input must outlive that launch,
@@ -232,6 +254,18 @@ static int build_plan(qasr_engine* e, int B, int T0) {
     }
   }
   HIPCHK(hipMalloc((void**)&e->lens_all, sizeof(int32_t) * h.n_domains * B));
+  for (uint32_t oi = 0; oi < h.n_ops; ++oi) {                // k_decw's workspace, for a decoder wider than k_dec's 32 classes
+    const qasr_op_desc& op = e->ops[oi];
+    if (op.kind != QASR_OP_PW || !(op.flags & QASR_F_LOGITS) || op.cout <= 32) continue;
+    const size_t need = decoder_wide_ws_bytes(B, e->tens[op.outs[0].tensor].Tp);
+    if (need > e->decw_ws_bytes) {
+      if (e->decw_ws) HIPCHK(hipFree(e->decw_ws));
+      e->decw_ws = nullptr;
+      e->decw_ws_bytes = 0;
+      HIPCHK(hipMalloc(&e->decw_ws, need));
+      e->decw_ws_bytes = need;
+    }
+  }
   HIPCHK(hipMalloc((void**)&e->time_tokens, sizeof(int32_t) * (size_t)B * (T0 + 64)));
   if (e->debug) {
     e->acc_dbg.resize(h.n_ops);
@@ -476,7 +510,7 @@ int qasr_engine_num_launches(const qasr_engine* e) {
   int n = (e->stem ? 0 : 1) + e->fe_launches;               // (k_lens, which the stem absorbs; front-end of forward_audio)
   for (uint32_t oi = 0; oi < e->h.n_ops; ++oi) {
     if (e->skip[oi] || e->dec_skip[oi] || e->rq_skip[oi] || (e->stem && oi >= 1 && oi <= 2)) continue;
-    n += 1;
+    n += e->dec_wide[oi] ? 2 : 1;                            // k_decw: statistics + output launches
   }
   return n;
 }
@@ -642,6 +676,14 @@ static int launch_op(qasr_engine* e, hipStream_t s, uint32_t oi, float* logp, in
         e->dec_skip[oi + 1] = 1;
         break;
       }
+      if (e->fuse_dec && (op.flags & QASR_F_LOGITS) && oi + 1 < e->h.n_ops && e->ops[oi + 1].kind == QASR_OP_LOGSOFTMAX &&
+          e->ops[oi + 1].in == op.outs[0].tensor && decoder_wide_fusable(p)) {
+        int rc = launch_decoder_wide(s, p, logp, tokens, lens_out, e->debug, e->decw_ws, e->decw_ws_bytes);
+        if (rc) return fail(rc, "op %u: wide decoder launch", oi);
+        e->dec_skip[oi + 1] = 1;
+        e->dec_wide[oi] = 1;
+        break;
+      }
       int rc = launch_sep(s, p);
       if (rc) return fail(rc, "op %u: no k_sep instantiation for K=%d dilation=%d (or bad launch shape)", oi, p.K, p.dilation);
       break;
@@ -701,7 +743,7 @@ static int launch_op(qasr_engine* e, hipStream_t s, uint32_t oi, float* logp, in
       break;
     }
     case QASR_OP_LOGSOFTMAX: {
-      if (e->dec_skip[oi]) break;                            // ran inside the decoder's launch (k_dec), lengths included
+      if (e->dec_skip[oi]) break;                            // ran inside the decoder's launch (k_dec / k_decw), lengths included
       launch_logsoftmax(s, (const float*)tin.ptr, logp, tokens, B * tin.T, (int)op.cin);
       if (lens_out)
         HIPCHK(hipMemcpyAsync(lens_out, e->lens_all + (size_t)tin.d.domain * B, sizeof(int32_t) * B,
@@ -904,7 +946,7 @@ int qasr_engine_op_label(qasr_engine* e, int op, char* buf, size_t cap) {
         SepP p{};
         build_sep(e, (uint32_t)op, p);
         if (e->fuse_dec && (d.flags & QASR_F_LOGITS) && op + 1 < (int)e->h.n_ops && e->dec_skip[op + 1]) {
-          name = "k_dec";
+          name = e->dec_wide[op] ? "k_decw" : "k_dec";
           break;
         }
         sep_kernel_label(p, buf, cap);
@@ -943,8 +985,8 @@ int qasr_engine_read_tensor(qasr_engine* e, int tensor, void* host_out, size_t n
     const bool in_launch = pr >= 0 && pr < (int)e->skip.size() && e->skip[pr];           // depthwise output inside the fused layer's launch
     const bool in_stem = e->stem && pr >= 0 && pr <= 1;                                    // k_stem's intermediates
     const bool in_dec = !e->debug && pr >= 0 && pr + 1 < (int)e->dec_skip.size() && e->dec_skip[pr + 1] &&
-                        (e->ops[pr].flags & QASR_F_LOGITS);                                // float logits inside k_dec
-    if (in_launch || in_stem || in_dec)
+                        (e->ops[pr].flags & QASR_F_LOGITS);                                // float logits inside k_dec / k_decw
+    if (in_launch || in_stem || in_dec || !t.ptr)
       return fail(QASR_ERR_ARG, "read_tensor: tensor %d is never materialised by this plan (its producer, op %d, runs fused inside another launch)", tensor, pr);
   }
   if (!e->debug) {                                           // production engines reuse arena slots: only a tensor nobody overwrote

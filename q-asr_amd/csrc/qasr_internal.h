@@ -135,6 +135,13 @@ int frontend_mel_stats(hipStream_t s, const float* audio, const int32_t* audio_l
 // qasr_decoder.hip: the decoder's 1x1 conv + log_softmax + argmax (+ the encoded lengths) as one launch
 bool decoder_fusable(const SepP& p);
 int launch_decoder(hipStream_t s, const SepP& p, float* logp, int32_t* tokens, int32_t* lens_out, bool keep_logits);
+// qasr_decoder_wide.hip: the same op for 32 < classes <= QASR_DECW_MAX_CLASSES (k_decw_stats + k_decw_out); `ws` is the plan's
+// partial-softmax workspace of decoder_wide_ws_bytes(B, Tp) bytes
+#define QASR_DECW_MAX_CLASSES 8192
+bool decoder_wide_fusable(const SepP& p);
+size_t decoder_wide_ws_bytes(int B, int Tp);
+int launch_decoder_wide(hipStream_t s, const SepP& p, float* logp, int32_t* tokens, int32_t* lens_out, bool keep_logits,
+                        void* ws, size_t ws_bytes);
 void launch_lens(hipStream_t s, const int32_t* lens_in, int32_t* lens_all, const qasr_domain_desc* doms,
                  int n_domains, int B);
 

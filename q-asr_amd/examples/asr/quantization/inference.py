@@ -39,7 +39,8 @@ def main():
     p.add_argument("--asr_model", type=str, default="QuartzNet15x5Base-En", required=True)
     p.add_argument("--dataset", type=str, required=True, help="path to evaluation data (JSON-lines manifest)")
     p.add_argument("--batch_size", type=int, default=8)
-    p.add_argument("--normalize_text", default=True, type=bool)
+    p.add_argument("--normalize_text", default=True, type=bool,
+                   help="English transcript normalisation; type=bool as in the reference: pass '' for False (non-English models)")
     p.add_argument("--shuffle", action='store_true')
     p.add_argument("--load", type=str, default=None, help="load path for the synthetic data")
     p.add_argument("--percentile", type=float, default=None)

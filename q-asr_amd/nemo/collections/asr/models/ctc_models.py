@@ -54,7 +54,7 @@ class EncDecCTCModel(nn.Module):
     # ------------------------------------------------------------------ construction / checkpoints
     @classmethod
     def list_available_models(cls):
-        return ['QuartzNet15x5Base-En', 'Jasper10x5Dr-En']
+        return ['QuartzNet15x5Base-En', 'QuartzNet15x5Base-Zh', 'Jasper10x5Dr-En']
 
     @classmethod
     def restore_from(cls, restore_path, map_location='cpu', strict=False):

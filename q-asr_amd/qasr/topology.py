@@ -53,6 +53,23 @@ def jasper10x5dr() -> ModelCfg:
     return ModelCfg('Jasper10x5Dr-En', 64, b)
 
 
+def zh_placeholder_vocabulary(n: int = 5206) -> List[str]:
+    """Stand-in label list of a Mandarin character model: ' ', "'", A-Z, then consecutive CJK code points from U+4E00 -
+    n distinct single characters.  A real .nemo brings its own vocabulary through its config."""
+    head = [' ', "'"] + [chr(ord('A') + i) for i in range(26)]
+    return (head + [chr(0x4E00 + i) for i in range(max(0, n - len(head)))])[:n]
+
+
+def quartznet15x5_zh() -> ModelCfg:
+    """QuartzNet15x5 with a 5206-label (+ blank) character decoder (examples/asr/conf/quartznet_15x5_zh.yaml): the
+    encoder of quartznet15x5(), only the decoder is wider."""
+    cfg = quartznet15x5()
+    cfg.name = 'QuartzNet15x5Base-Zh'
+    cfg.num_classes = 5206
+    cfg.vocabulary = zh_placeholder_vocabulary(5206)
+    return cfg
+
+
 def mini_quartznet(c0=32, c1=48) -> ModelCfg:
     """Small QuartzNet-shaped net (every block kind once) for parity tests."""
     b = [BlockCfg(c0, 11, 1, stride=2, separable=True),
@@ -75,6 +92,7 @@ def mini_jasper() -> ModelCfg:
 
 MODELS = {
     'QuartzNet15x5Base-En': quartznet15x5,
+    'QuartzNet15x5Base-Zh': quartznet15x5_zh,
     'Jasper10x5Dr-En': jasper10x5dr,
     'MiniQuartzNet': mini_quartznet,
     'MiniJasper': mini_jasper,
