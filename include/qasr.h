@@ -219,7 +219,7 @@ int qasr_engine_out_frames(const qasr_engine* e, int T);
 int qasr_engine_num_ops(const qasr_engine* e);
 /* kernel launches of the last forward with the current plan: encoder + decoder (80 for QuartzNet15x5 with the default
  * options) plus, after qasr_engine_forward_audio, the front-end's (k_mel; + k_norm when fuse_norm is
- * off: 81 / 82); -1 before the first forward */
+ * off: 81 / 82), plus one (k_ctc) while a qasr_ctc_out is attached; -1 before the first forward */
 int qasr_engine_num_launches(const qasr_engine* e);
 
 /* Parity hooks (debug engines only; synchronise the stream).  acc: int32 [B][cout][T_out] = the
@@ -252,6 +252,44 @@ int qasr_engine_run_op(qasr_engine* e, void* stream, int op);
 size_t qasr_quantile_workspace_bytes(void);
 int qasr_quantile2(void* stream, const float* x, size_t n, float q_lo, float q_hi, float* out2, void* workspace,
                    size_t workspace_bytes);
+
+/* ---- greedy CTC decoding on the device ---------------------------------------------------------------------------
+ * The loop of WER.ctc_decoder_predictions_tensor (nemo/collections/asr/metrics/wer.py: keep p when
+ * (p != previous or previous == blank) and p != blank) as one kernel, k_ctc, with what that loop throws away.
+ * Input: tokens i32 [B][T]; frame_score f32 [B][T] (optional): the log-probability of each frame's arg-max class; lens
+ * i32 [B] (optional).  Per utterance b, over the frames t < lim, lim = min(lens[b], T) (lens NULL: T, the padded row as
+ * the reference walks it): a run is a maximal stretch of equal tokens; every run of a non-blank token emits one label.
+ * Outputs (caller-owned device buffers, row pitch T):
+ *   labels    i32 [B][T]  the emitted ids in order; entries from n_labels[b] on are `blank`
+ *   n_labels  i32 [B]
+ *   start     i32 [B][T]  first frame of the run;  nframes i32 [B][T] its length;  tails 0        (each optional)
+ *   score     f32 [B][T]  the maximum of frame_score over the run's frames (exact); tail 0        (optional)
+ *   utt_score f32 [B]     log-probability of the greedy path = sum of frame_score[b][t], t < lim, in this fixed order:
+ *                         part[l] = float32 sum, in increasing t, of the frames with t % 64 == l (from 0.0f); result =
+ *                         float32 sum of part[0] .. part[63] in increasing l (from 0.0f).  lim == 0: 0.0f  (optional)
+ * score / utt_score need frame_score.  Score maxima are taken in the total order of float32 bit patterns (-0 < +0). */
+typedef struct qasr_ctc_out {
+  uint32_t struct_size;        /* sizeof(qasr_ctc_out) of the caller's header */
+  int32_t* labels;
+  int32_t* n_labels;
+  int32_t* start;
+  int32_t* nframes;
+  float* score;
+  float* utt_score;
+} qasr_ctc_out;
+/* Stand-alone operator on any token matrix (one launch on `stream`).  QASR_ERR_ARG (nothing launched): B < 1, T < 1, a
+ * NULL tokens / out / labels / n_labels, score or utt_score without frame_score, an unknown struct_size. */
+int qasr_ctc_collapse(void* stream, const int32_t* tokens, const float* frame_score, const int32_t* lens, int B, int T,
+                      int blank, const qasr_ctc_out* out);
+/* Sticky attachment: every later qasr_engine_forward / qasr_engine_forward_audio of this engine also writes
+ * `frame_score` (f32 [B][T'], if not NULL: one store per frame from the decoder kernel, bit-identical to
+ * logp[b][t][tokens[b][t]] of the same run, no extra launch) and, if `out` is not NULL, runs k_ctc on the call's own
+ * tokens after the decoder, on the same stream and inside the captured graph (one more launch; `tokens` must then be
+ * non-NULL).  blank = the decoder's last class.  use_lens = 1: stop at the encoded length; 0: walk the padded row like
+ * the reference.  The struct is copied; the buffers stay the caller's and must fit the B x T' of the forwards that follow.
+ * The attachment is part of the graph key: changing it re-captures, keeping it replays.  Both NULL detaches.
+ * QASR_ERR_ARG: a blob without a LOGSOFTMAX op, score / utt_score without frame_score, missing labels / n_labels. */
+int qasr_engine_attach_ctc(qasr_engine* e, float* frame_score, const qasr_ctc_out* out, int use_lens);
 
 /* ---- stand-alone operators (same kernels the engine launches; device pointers) -------------- */
 

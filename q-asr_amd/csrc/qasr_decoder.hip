@@ -26,6 +26,7 @@ struct DecP {
   float* logits;            // optional f32 [B][T][cout]
   float* logp;              // optional f32 [B][T][ncls]
   int32_t* tokens;          // optional i32 [B][T]
+  float* frame_score;       // optional f32 [B][T]: log-prob of the frame's argmax class, the bits of logp[b][t][tokens[b][t]]
   int cin, cin_pad, x_unsigned, B, T, Tp, ncls;
 };
 
@@ -111,6 +112,7 @@ __global__ void __launch_bounds__(DEC_NT) k_dec(DecP p) {
     if (p.logp)
       for (int c = 0; c < p.ncls; ++c) p.logp[row * p.ncls + c] = (x[c] - m) - ls;
     if (p.tokens) p.tokens[row] = am;
+    if (p.frame_score) p.frame_score[row] = 0.0f - ls;                    // x[am] == m: (x[am] - m) - ls, +0 for a one-hot frame
   }
 }
 
@@ -120,13 +122,14 @@ bool decoder_fusable(const SepP& p) {
          p.cin_pad <= 2048 && p.e.Tp % DEC_TT == 0;
 }
 
-int launch_decoder(hipStream_t s, const SepP& q, float* logp, int32_t* tokens, int32_t* lens_out, bool keep_logits) {
+int launch_decoder(hipStream_t s, const SepP& q, float* logp, int32_t* tokens, int32_t* lens_out, bool keep_logits,
+                   float* frame_score) {
   if (!decoder_fusable(q) || !q.x || !q.w || !q.bias || !q.e.sb || !q.e.lens || q.e.B < 1 || q.e.T > q.e.Tp) return QASR_ERR_ARG;
   DecP p{};
   p.x = q.x, p.w = q.w, p.bias = q.bias, p.sb = q.e.sb, p.lens = q.e.lens, p.lens_out = lens_out;
   p.acc_dbg = q.e.acc_dbg;
   p.logits = keep_logits ? q.e.logits : nullptr;
-  p.logp = logp, p.tokens = tokens;
+  p.logp = logp, p.tokens = tokens, p.frame_score = frame_score;
   p.cin = q.cin, p.cin_pad = q.cin_pad, p.x_unsigned = q.pw_unsigned;
   p.B = q.e.B, p.T = q.e.T, p.Tp = q.e.Tp, p.ncls = q.e.cout;
   const size_t smem = (size_t)p.cin_pad * 32 + sizeof(int) * 8 * 32 * 33 + sizeof(float) * 32 * 33;

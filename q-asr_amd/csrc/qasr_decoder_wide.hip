@@ -41,6 +41,7 @@ struct DecwP {
   float* logits;            // optional f32 [B][T][ncls]
   float* logp;              // optional f32 [B][T][ncls]
   int32_t* tokens;          // optional i32 [B][T]
+  float* frame_score;       // optional f32 [B][T]: log-prob of the frame's argmax class, the bits of logp[b][t][tokens[b][t]]
   float4* part;             // workspace [B][Tp][G] {max, sum exp, argmax (bits), 0}
   int cin, cin_pad, x_unsigned, B, T, Tp, ncls, G, n_ct;
 };
@@ -217,6 +218,8 @@ __global__ void __launch_bounds__(DECW_NT) k_decw_out(DecwP p) {
     Lf[tid] = logf(s.s);
     const int t = t0 + tid;
     if (g == 0 && t < p.T && p.tokens) p.tokens[(size_t)b * p.T + t] = s.a;
+    // z[argmax] == M bit for bit (the maximum is one of the z values): (z - M) - log S of that class
+    if (g == 0 && t < p.T && p.frame_score) p.frame_score[(size_t)b * p.T + t] = 0.0f - Lf[tid];
   }
   if (g == 0 && t0 == 0 && tid == 0 && p.lens_out) p.lens_out[b] = p.lens[b];
   if (!p.logp) return;
@@ -248,7 +251,7 @@ bool decoder_wide_fusable(const SepP& p) {
 size_t decoder_wide_ws_bytes(int B, int Tp) { return (size_t)B * Tp * DECW_G * sizeof(float4); }
 
 int launch_decoder_wide(hipStream_t s, const SepP& q, float* logp, int32_t* tokens, int32_t* lens_out, bool keep_logits,
-                        void* ws, size_t ws_bytes) {
+                        void* ws, size_t ws_bytes, float* frame_score) {
   if (!decoder_wide_fusable(q) || !q.x || !q.w || !q.bias || !q.e.sb || !q.e.lens || q.e.B < 1 || q.e.T > q.e.Tp || !ws ||
       ws_bytes < decoder_wide_ws_bytes(q.e.B, q.e.Tp))
     return QASR_ERR_ARG;
@@ -256,7 +259,7 @@ int launch_decoder_wide(hipStream_t s, const SepP& q, float* logp, int32_t* toke
   p.x = q.x, p.w = q.w, p.bias = q.bias, p.sb = q.e.sb, p.lens = q.e.lens, p.lens_out = lens_out;
   p.acc_dbg = q.e.acc_dbg;
   p.logits = keep_logits ? q.e.logits : nullptr;
-  p.logp = logp, p.tokens = tokens;
+  p.logp = logp, p.tokens = tokens, p.frame_score = frame_score;
   p.part = (float4*)ws;
   p.cin = q.cin, p.cin_pad = q.cin_pad, p.x_unsigned = q.pw_unsigned;
   p.B = q.e.B, p.T = q.e.T, p.Tp = q.e.Tp, p.ncls = q.e.cout;

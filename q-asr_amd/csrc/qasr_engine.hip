@@ -122,6 +122,12 @@ struct qasr_engine {
   // reuses its buffers with another S of equal T_pad, or swaps the filterbank, must not replay the old graph)
   uint64_t gfe[6] = {0, 0, 0, 0, 0, 0};
   int gcalls = 0;                      // forwards seen with the current key (1st: direct launches, 2nd: capture)
+  // qasr_engine_attach_ctc: per-frame best-path score from the decoder kernel and / or k_ctc behind it
+  float* ctc_fs = nullptr;
+  qasr_ctc_out ctc_out{};
+  bool ctc_on = false;                 // ctc_out is attached: one more launch
+  int ctc_use_lens = 0;
+  uint64_t gctc[8] = {0, 0, 0, 0, 0, 0, 0, 0};   // the attachment a captured graph bakes in
 };
 
 template <class T>
@@ -512,7 +518,7 @@ int qasr_engine_num_launches(const qasr_engine* e) {
     if (e->skip[oi] || e->dec_skip[oi] || e->rq_skip[oi] || (e->stem && oi >= 1 && oi <= 2)) continue;
     n += e->dec_wide[oi] ? 2 : 1;                            // k_decw: statistics + output launches
   }
-  return n;
+  return n + (e->ctc_on ? 1 : 0);                            // k_ctc behind the decoder
 }
 
 int qasr_engine_out_frames(const qasr_engine* e, int T) {
@@ -671,14 +677,14 @@ static int launch_op(qasr_engine* e, hipStream_t s, uint32_t oi, float* logp, in
       build_sep(e, oi, p);
       if (e->fuse_dec && (op.flags & QASR_F_LOGITS) && oi + 1 < e->h.n_ops && e->ops[oi + 1].kind == QASR_OP_LOGSOFTMAX &&
           e->ops[oi + 1].in == op.outs[0].tensor && decoder_fusable(p)) {
-        int rc = launch_decoder(s, p, logp, tokens, lens_out, e->debug);
+        int rc = launch_decoder(s, p, logp, tokens, lens_out, e->debug, e->ctc_fs);
         if (rc) return fail(rc, "op %u: decoder launch", oi);
         e->dec_skip[oi + 1] = 1;
         break;
       }
       if (e->fuse_dec && (op.flags & QASR_F_LOGITS) && oi + 1 < e->h.n_ops && e->ops[oi + 1].kind == QASR_OP_LOGSOFTMAX &&
           e->ops[oi + 1].in == op.outs[0].tensor && decoder_wide_fusable(p)) {
-        int rc = launch_decoder_wide(s, p, logp, tokens, lens_out, e->debug, e->decw_ws, e->decw_ws_bytes);
+        int rc = launch_decoder_wide(s, p, logp, tokens, lens_out, e->debug, e->decw_ws, e->decw_ws_bytes, e->ctc_fs);
         if (rc) return fail(rc, "op %u: wide decoder launch", oi);
         e->dec_skip[oi + 1] = 1;
         e->dec_wide[oi] = 1;
@@ -744,7 +750,7 @@ static int launch_op(qasr_engine* e, hipStream_t s, uint32_t oi, float* logp, in
     }
     case QASR_OP_LOGSOFTMAX: {
       if (e->dec_skip[oi]) break;                            // ran inside the decoder's launch (k_dec / k_decw), lengths included
-      launch_logsoftmax(s, (const float*)tin.ptr, logp, tokens, B * tin.T, (int)op.cin);
+      launch_logsoftmax(s, (const float*)tin.ptr, logp, tokens, e->ctc_fs, B * tin.T, (int)op.cin);
       if (lens_out)
         HIPCHK(hipMemcpyAsync(lens_out, e->lens_all + (size_t)tin.d.domain * B, sizeof(int32_t) * B,
                               hipMemcpyDeviceToDevice, s));
@@ -754,6 +760,13 @@ static int launch_op(qasr_engine* e, hipStream_t s, uint32_t oi, float* logp, in
       return fail(QASR_ERR_UNSUPPORTED, "op kind %u", op.kind);
   }
   return QASR_OK;
+}
+
+// index of the plan's LOGSOFTMAX op (the decoder's output stage), or -1
+static int logsoftmax_op(const qasr_engine* e) {
+  for (uint32_t oi = 0; oi < e->h.n_ops; ++oi)
+    if (e->ops[oi].kind == QASR_OP_LOGSOFTMAX) return (int)oi;
+  return -1;
 }
 
 // front-end of a forward_audio call (nullptr: the caller's features are the input)
@@ -779,6 +792,7 @@ static int forward_impl(qasr_engine* e, hipStream_t s, const FrontArgs* fe, floa
     e->gexec = nullptr;
     e->gkey[0] = nullptr;
   }
+  if (e->ctc_on && !tokens) return fail(QASR_ERR_ARG, "forward: a qasr_ctc_out is attached, tokens must not be NULL");
   const auto& h = e->h;
   e->tens[0].ptr = (void*)feats;
   e->cur_lens = lens;
@@ -820,6 +834,13 @@ static int forward_impl(qasr_engine* e, hipStream_t s, const FrontArgs* fe, floa
       int rc = launch_op(e, s, oi, logp, tokens, lens_out);
       if (rc) return rc;
     }
+    if (e->ctc_on) {                                         // greedy collapse of this call's tokens, behind the decoder
+      const qasr_op_desc& ls = e->ops[logsoftmax_op(e)];
+      const TensorRT& tl = e->tens[ls.in];
+      int rc = launch_ctc(s, tokens, e->ctc_fs, e->ctc_use_lens ? e->lens_all + (size_t)tl.d.domain * B : nullptr, B, tl.T,
+                          (int)ls.cin - 1, e->ctc_out);
+      if (rc) return fail(rc, "k_ctc launch");
+    }
     return QASR_OK;
   };
   e->forwarded = true;
@@ -836,12 +857,17 @@ static int forward_impl(qasr_engine* e, hipStream_t s, const FrontArgs* fe, floa
     bool same = true;
     for (int i = 0; i < 8; ++i) same = same && key[i] == e->gkey[i];
     for (int i = 0; i < 6; ++i) same = same && fkey[i] == e->gfe[i];
+    const uint64_t ckey[8] = {(uint64_t)(uintptr_t)e->ctc_fs, (uint64_t)(uintptr_t)e->ctc_out.labels, (uint64_t)(uintptr_t)e->ctc_out.n_labels,
+                              (uint64_t)(uintptr_t)e->ctc_out.start, (uint64_t)(uintptr_t)e->ctc_out.nframes, (uint64_t)(uintptr_t)e->ctc_out.score,
+                              (uint64_t)(uintptr_t)e->ctc_out.utt_score, (uint64_t)(e->ctc_on ? 1 : 0) | (uint64_t)(e->ctc_use_lens ? 2 : 0)};
+    for (int i = 0; i < 8; ++i) same = same && ckey[i] == e->gctc[i];
     if (!same) {                                             // new buffer set / front-end arguments: drop the old graph, start over
       if (e->gexec) (void)hipGraphExecDestroy(e->gexec);
       e->gexec = nullptr;
       e->gcalls = 0;
       for (int i = 0; i < 8; ++i) e->gkey[i] = key[i];
       for (int i = 0; i < 6; ++i) e->gfe[i] = fkey[i];
+      for (int i = 0; i < 8; ++i) e->gctc[i] = ckey[i];
     }
     if (e->gexec) {
       HIPCHK(hipGraphLaunch(e->gexec, s));
@@ -875,6 +901,41 @@ static int forward_impl(qasr_engine* e, hipStream_t s, const FrontArgs* fe, floa
     e->timed = true;
   }
   HIPCHK(hipGetLastError());
+  return QASR_OK;
+}
+
+// the caller's qasr_ctc_out, checked; an older (shorter) struct is not known yet: sizes must match
+static int ctc_out_check(const qasr_ctc_out* out, bool have_fs, const char* who) {
+  if (out->struct_size != sizeof(qasr_ctc_out)) return fail(QASR_ERR_ARG, "%s: qasr_ctc_out.struct_size %u is not %zu", who, out->struct_size, sizeof(qasr_ctc_out));
+  if (!out->labels || !out->n_labels) return fail(QASR_ERR_ARG, "%s: labels and n_labels are required", who);
+  if ((out->score || out->utt_score) && !have_fs) return fail(QASR_ERR_ARG, "%s: score / utt_score need frame_score", who);
+  return QASR_OK;
+}
+
+int qasr_ctc_collapse(void* stream, const int32_t* tokens, const float* frame_score, const int32_t* lens, int B, int T,
+                      int blank, const qasr_ctc_out* out) {
+  if (!tokens || !out || B < 1 || T < 1) return fail(QASR_ERR_ARG, "ctc_collapse: tokens / out NULL or B, T < 1");
+  int rc = ctc_out_check(out, frame_score != nullptr, "ctc_collapse");
+  if (rc) return rc;
+  rc = launch_ctc((hipStream_t)stream, tokens, frame_score, lens, B, T, blank, *out);
+  if (rc) return fail(rc, "ctc_collapse: launch");
+  HIPCHK(hipGetLastError());
+  return QASR_OK;
+}
+
+int qasr_engine_attach_ctc(qasr_engine* e, float* frame_score, const qasr_ctc_out* out, int use_lens) {
+  if (!e) return fail(QASR_ERR_ARG, "attach_ctc: engine is NULL");
+  if (frame_score || out) {
+    if (logsoftmax_op(e) < 0) return fail(QASR_ERR_ARG, "attach_ctc: the model has no LOGSOFTMAX op (no CTC decoder)");
+    if (out) {
+      int rc = ctc_out_check(out, frame_score != nullptr, "attach_ctc");
+      if (rc) return rc;
+    }
+  }
+  e->ctc_fs = frame_score;
+  e->ctc_on = out != nullptr;
+  e->ctc_out = out ? *out : qasr_ctc_out{};
+  e->ctc_use_lens = (out && use_lens) ? 1 : 0;
   return QASR_OK;
 }
 

@@ -120,7 +120,8 @@ int launch_sep(hipStream_t s, const SepP& p);      // QASR_OK, or QASR_ERR_UNSUP
 void sep_kernel_label(const SepP& p, char* buf, size_t cap);
 int sep_tile_for(const SepP& p);
 void launch_requant(hipStream_t s, const RequantP& p);
-void launch_logsoftmax(hipStream_t s, const float* logits, float* logp, int32_t* tokens, int rows, int ncls);
+// frame_score (optional, [rows]): the log-probability of each row's argmax class, bit-identical to logp[row][tokens[row]]
+void launch_logsoftmax(hipStream_t s, const float* logits, float* logp, int32_t* tokens, float* frame_score, int rows, int ncls);
 // qasr_stem.hip: lengths + first-layer QuantAct + strided depthwise conv + 1x1 conv of block 0 as one launch
 bool stem_supported(const QuantInP& qi, const DwP& dw, const SepP& pw);
 // stats != nullptr: x holds un-normalised log-mel and normalize_batch runs inside (per-tile sums from frontend_mel_stats)
@@ -134,14 +135,18 @@ int frontend_mel_stats(hipStream_t s, const float* audio, const int32_t* audio_l
                        const void* workspace, size_t workspace_bytes, double* stats, int* n_tiles, int* n_frames);
 // qasr_decoder.hip: the decoder's 1x1 conv + log_softmax + argmax (+ the encoded lengths) as one launch
 bool decoder_fusable(const SepP& p);
-int launch_decoder(hipStream_t s, const SepP& p, float* logp, int32_t* tokens, int32_t* lens_out, bool keep_logits);
+int launch_decoder(hipStream_t s, const SepP& p, float* logp, int32_t* tokens, int32_t* lens_out, bool keep_logits,
+                   float* frame_score = nullptr);
 // qasr_decoder_wide.hip: the same op for 32 < classes <= QASR_DECW_MAX_CLASSES (k_decw_stats + k_decw_out); `ws` is the plan's
 // partial-softmax workspace of decoder_wide_ws_bytes(B, Tp) bytes
 #define QASR_DECW_MAX_CLASSES 8192
 bool decoder_wide_fusable(const SepP& p);
 size_t decoder_wide_ws_bytes(int B, int Tp);
 int launch_decoder_wide(hipStream_t s, const SepP& p, float* logp, int32_t* tokens, int32_t* lens_out, bool keep_logits,
-                        void* ws, size_t ws_bytes);
+                        void* ws, size_t ws_bytes, float* frame_score = nullptr);
+// qasr_ctc.hip: greedy CTC collapse of a token matrix (k_ctc), one work-group per utterance
+int launch_ctc(hipStream_t s, const int32_t* tokens, const float* frame_score, const int32_t* lens, int B, int T, int blank,
+               const qasr_ctc_out& out);
 void launch_lens(hipStream_t s, const int32_t* lens_in, int32_t* lens_all, const qasr_domain_desc* doms,
                  int n_domains, int B);
 

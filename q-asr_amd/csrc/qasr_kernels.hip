@@ -468,7 +468,7 @@ void launch_requant(hipStream_t s, const RequantP& p) {
 
 // ------------------------------------------------------------------------------------------------ log-softmax + argmax
 // torch.nn.functional.log_softmax(dim=-1) + argmax (conv_asr.py:275, ctc_models.py:405); one lane per (b, t) row.
-__global__ void k_logsoftmax(const float* logits, float* logp, int32_t* tokens, int rows, int ncls) {
+__global__ void k_logsoftmax(const float* logits, float* logp, int32_t* tokens, float* frame_score, int rows, int ncls) {
   int r = blockIdx.x * blockDim.x + threadIdx.x;
   if (r >= rows) return;
   const float* x = logits + (size_t)r * ncls;
@@ -484,9 +484,10 @@ __global__ void k_logsoftmax(const float* logits, float* logp, int32_t* tokens, 
   if (logp)
     for (int c = 0; c < ncls; ++c) logp[(size_t)r * ncls + c] = (x[c] - m) - ls;
   if (tokens) tokens[r] = am;
+  if (frame_score) frame_score[r] = 0.0f - ls;   // x[am] == m: the bits of logp[r][am]; +0 for a one-hot row
 }
-void launch_logsoftmax(hipStream_t s, const float* logits, float* logp, int32_t* tokens, int rows, int ncls) {
-  hipLaunchKernelGGL(k_logsoftmax, dim3((rows + 127) / 128), dim3(128), 0, s, logits, logp, tokens, rows, ncls);
+void launch_logsoftmax(hipStream_t s, const float* logits, float* logp, int32_t* tokens, float* frame_score, int rows, int ncls) {
+  hipLaunchKernelGGL(k_logsoftmax, dim3((rows + 127) / 128), dim3(128), 0, s, logits, logp, tokens, frame_score, rows, ncls);
 }
 
 }  // namespace qasr

@@ -54,6 +54,9 @@ def main():
     p.add_argument("--synthetic_model", action='store_true', help="(extension) random-init weights of --asr_model")
     p.add_argument("--dither", type=float, default=None, help="(extension) override the preprocessor's dither (0: reproducible runs)")
     p.add_argument("--dump_hyps", type=str, default=None, help="(extension) write hypotheses, references and WER as JSON")
+    p.add_argument("--timestamps", action='store_true',
+                   help="(extension) also decode every batch with EncDecCTCModel.decode: word times and confidences "
+                        "(`words`, `utt_score` per utterance in the --dump_hyps JSON); hypotheses and WER are unchanged")
     args = p.parse_args()
     torch.set_grad_enabled(False)
 
@@ -106,7 +109,7 @@ def main():
     qm.set_dynamic(asr_model, args.dynamic)
     labels_map = dict(enumerate(asr_model.decoder.vocabulary))
     wer = WER(vocabulary=asr_model.decoder.vocabulary)
-    hyps, refs = [], []
+    hyps, refs, words, utt_scores = [], [], [], []
     audio_s, t0 = 0.0, time.time()
     for i, batch in enumerate(asr_model.test_dataloader()):
         if i == args.eval_early_stop:
@@ -114,6 +117,10 @@ def main():
         batch = [x.cuda() for x in batch]
         log_probs, enc_len, greedy = asr_model(input_signal=batch[0].float(), input_signal_length=batch[1])
         hyps += wer.ctc_decoder_predictions_tensor(greedy)
+        if args.timestamps:                                  # device-side collapse up to each utterance's encoded length
+            for h in asr_model.decode(input_signal=batch[0].float(), input_signal_length=batch[1]):
+                words.append([list(w) for w in h.words])
+                utt_scores.append(h.utt_score)
         for row in batch[2].cpu().numpy():
             refs.append(''.join(labels_map[c] for c in row))
         audio_s += float(batch[1].sum()) / 16000.0
@@ -127,7 +134,8 @@ def main():
     if args.dump_hyps:
         import json
         with open(args.dump_hyps, 'w') as f:
-            json.dump(dict(hypotheses=hyps, references=refs, wer=wer_value, path=served), f)
+            extra = dict(words=words, utt_score=utt_scores) if args.timestamps else {}
+            json.dump(dict(hypotheses=hyps, references=refs, wer=wer_value, path=served, **extra), f)
     print(f'RTFx (incl. host data loading): {audio_s / max(wall, 1e-9):.1f}  ({audio_s:.1f} s audio in {wall:.2f} s)')
 
 

@@ -148,11 +148,13 @@ class EncDecCTCModel(nn.Module):
         return self._test_dl
 
     @torch.no_grad()
-    def transcribe(self, paths2audio_files, batch_size=4, logprobs=False):
+    def transcribe(self, paths2audio_files, batch_size=4, logprobs=False, return_hypotheses=False):
         """Greedy transcripts (or per-file log-probabilities) of audio files, in input order - the reference's debugging /
         prototyping entry (ctc_models.py:148-212, 476-503): dither off and pad_to 0 for the duration of the call, evaluation
         mode, a temporary manifest with `duration` 100000 and text 'nothing', batch size min(batch_size, #files), silence
-        trimmed (`trim_silence: True`), everything restored afterwards.  A calibrated model runs on the HIP engine."""
+        trimmed (`trim_silence: True`), everything restored afterwards.  A calibrated model runs on the HIP engine.
+        return_hypotheses=True (an extension): qasr.ctc.Hypothesis objects - text, label and word times, confidences - from
+        decode() instead of strings."""
         if paths2audio_files is None or len(paths2audio_files) == 0:
             return {}
         import json
@@ -177,6 +179,10 @@ class EncDecCTCModel(nn.Module):
                                           'shuffle': False})
                 wer = WER(vocabulary=self.decoder.vocabulary)
                 for batch in loader:
+                    if return_hypotheses and not logprobs:
+                        hypotheses += self.decode(input_signal=batch[0].to(device).float(),
+                                                  input_signal_length=batch[1].to(device))
+                        continue
                     logits, logits_len, greedy = self.forward(input_signal=batch[0].to(device).float(),
                                                               input_signal_length=batch[1].to(device))
                     if logprobs:
@@ -317,6 +323,40 @@ class EncDecCTCModel(nn.Module):
     # ------------------------------------------------------------------ forward
     def forward(self, input_signal=None, input_signal_length=None, processed_signal=None,
                 processed_signal_length=None):
+        return self._forward(input_signal, input_signal_length, processed_signal, processed_signal_length)
+
+    def seconds_per_frame(self):
+        """Seconds per encoder output frame, from the model itself: featurizer hop x the encoder's strides (0.02 s for the
+        registered models)."""
+        from qasr import ctc as qctc
+        f = self.preprocessor.featurizer
+        return qctc.seconds_per_frame(qconfigs.topology_from_config(self.cfg), f.hop_length / float(self.preprocessor._sample_rate))
+
+    @torch.no_grad()
+    def decode(self, input_signal=None, input_signal_length=None, processed_signal=None, processed_signal_length=None):
+        """Greedy CTC hypotheses of one batch (an extension of the reference's API): List[qasr.ctc.Hypothesis] with the
+        text, every label's start / end time and confidence (best frame log-probability of its run), word groups and the
+        log-probability of the greedy path.  Decoding stops at each utterance's encoded length.  On the static engine the
+        collapse (k_ctc) and the per-frame scores ride inside the engine's call on persistent buffers - no log-prob tensor
+        is written; on the dynamic device path and the host modules the scores are log_probs gathered at the tokens,
+        collapsed by qasr_ctc_collapse (cuda) or qasr.ctc.collapse_host (cpu)."""
+        from qasr import ctc as qctc
+        res = self._forward(input_signal, input_signal_length, processed_signal, processed_signal_length, decode=True)
+        return qctc.to_hypotheses(res, self.decoder.vocabulary, self.seconds_per_frame())
+
+    def _collapse(self, log_probs, tokens, enc_len):
+        """decode() behind a path that returned log-probabilities: frame scores = log_probs at the tokens"""
+        from qasr import ctc as qctc
+        blank = len(self.decoder.vocabulary)
+        fs = log_probs.float().gather(2, tokens.long().unsqueeze(-1)).squeeze(-1)
+        if tokens.is_cuda:
+            from qasr import engine as qengine
+            return qengine.ctc_collapse(tokens.to(torch.int32), fs, enc_len.to(torch.int32), blank=blank)
+        return qctc.collapse_host(tokens.numpy(), fs.numpy(), enc_len.numpy(), blank=blank)
+
+    def _forward(self, input_signal=None, input_signal_length=None, processed_signal=None,
+                 processed_signal_length=None, decode=False):
+        """forward(); decode=True returns the CTC collapse of the batch (a qasr.ctc.CtcResult) instead of the triple"""
         has_in = input_signal is not None and input_signal_length is not None
         has_pr = processed_signal is not None and processed_signal_length is not None
         if has_in == has_pr:
@@ -336,12 +376,17 @@ class EncDecCTCModel(nn.Module):
                 if f.dither > 0:
                     sig = sig + f.dither * torch.randn_like(sig)
                 fb, plan = self._frontend_plan_for(ref.device)
-                log_probs, tokens, enc_len = eng.forward_audio(
-                    sig, input_signal_length.to(device=ref.device, dtype=torch.int32).contiguous(), fb,
-                    f.window.to(device=ref.device, dtype=torch.float32).contiguous(), plan, float(f.preemph), int(f.pad_to))
+                audio_lens = input_signal_length.to(device=ref.device, dtype=torch.int32).contiguous()
+                window = f.window.to(device=ref.device, dtype=torch.float32).contiguous()
+                if decode:                                       # tokens only: the scores come from the decoder kernel
+                    return eng.forward_audio(sig, audio_lens, fb, window, plan, float(f.preemph), int(f.pad_to),
+                                             want_logp=False, decode=True)[3]
+                log_probs, tokens, enc_len = eng.forward_audio(sig, audio_lens, fb, window, plan, float(f.preemph), int(f.pad_to))
                 return log_probs, enc_len.long(), tokens.long()
             if has_in:
                 processed_signal, processed_signal_length = self._frontend_hip(input_signal, input_signal_length)
+            if decode:
+                return eng.forward(processed_signal.float(), processed_signal_length, want_logp=False, decode=True)[3]
             log_probs, tokens, enc_len = eng.forward(processed_signal.float(), processed_signal_length)
             return log_probs, enc_len.long(), tokens.long()
         if ref.is_cuda and self.dynamic_ready():
@@ -350,10 +395,14 @@ class EncDecCTCModel(nn.Module):
                 if has_in:
                     processed_signal, processed_signal_length = self._frontend_hip(input_signal, input_signal_length)
                 out = runner.forward(processed_signal.float(), processed_signal_length)
+                if decode:
+                    return self._collapse(out['log_probs'], out['tokens'], out['enc_len'])
                 return out['log_probs'], out['enc_len'].long(), out['tokens'].long()
         if has_in:
             processed_signal, processed_signal_length = self.preprocessor(input_signal=input_signal,
                                                                           length=input_signal_length)
         encoded, encoded_len, encoded_sf = self.encoder(audio_signal=processed_signal, length=processed_signal_length)
         log_probs = self.decoder(encoder_output=encoded, encoder_output_scaling_factor=encoded_sf)
+        if decode:
+            return self._collapse(log_probs, log_probs.argmax(dim=-1, keepdim=False), encoded_len)
         return log_probs, encoded_len, log_probs.argmax(dim=-1, keepdim=False)

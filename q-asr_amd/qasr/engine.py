@@ -16,7 +16,7 @@ SYMBOLS = ['qasr_blob_check', 'qasr_engine_create', 'qasr_engine_create_ex', 'qa
            'qasr_frontend_workspace_bytes', 'qasr_pw_conv_acc',
            'qasr_dw_conv_acc', 'qasr_dense_conv_acc', 'qasr_requant', 'qasr_dyn_range', 'qasr_dyn_range_percentile', 'qasr_dyn_residue_codes', 'qasr_dyn_act_params', 'qasr_dyn_requant',
            'qasr_dyn_quant_in', 'qasr_dyn_conv_params', 'qasr_sep_layer', 'qasr_quantile2', 'qasr_quantile_workspace_bytes', 'qasr_debug_prof',
-           'qasr_debug_timeline',
+           'qasr_debug_timeline', 'qasr_ctc_collapse', 'qasr_engine_attach_ctc',
            'qasr_last_error', 'qasr_version']
 
 _lib = None
@@ -44,6 +44,12 @@ class EngineOpts(C.Structure):
                 [(n, C.c_int32) for n in ('tile_frames', 'sep_gen', 'fuse_dw', 'fuse_stem', 'fuse_decoder', 'graph',
                                           'retired_whole_utterance', 'res_tile128', 'dense_tile128', 'retired_legacy_pw', 'retired_persistent', 'fuse_norm')] +
                 [('reserved', C.c_int32 * 2)])
+
+
+class CtcOut(C.Structure):
+    """qasr_ctc_out (include/qasr.h): caller-owned device buffers of k_ctc, row pitch T."""
+    _fields_ = [('struct_size', C.c_uint32)] + [(n, C.c_void_p) for n in ('labels', 'n_labels', 'start', 'nframes', 'score',
+                                                                         'utt_score')]
 
 
 class QasrError(RuntimeError):
@@ -95,6 +101,9 @@ def load_library():
     lib.qasr_dyn_requant.argtypes = [vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, i32, vp]
     lib.qasr_dyn_quant_in.argtypes = [vp, vp, i32, vp, vp, i32, i32, i32, i32, i32, vp, vp]
     lib.qasr_dyn_conv_params.argtypes = [vp, vp, vp, vp, vp, i32, i32, vp, vp]
+    if hasattr(lib, 'qasr_ctc_collapse'):       # (a QASR_LIB A/B build of an older tree lacks them: calling them raises there)
+        lib.qasr_ctc_collapse.argtypes = [vp, vp, vp, vp, i32, i32, i32, C.POINTER(CtcOut)]
+        lib.qasr_engine_attach_ctc.argtypes = [vp, vp, C.POINTER(CtcOut), i32]
     lib.qasr_debug_prof.argtypes = [vp]
     lib.qasr_debug_timeline.argtypes = [vp, sz]
     lib.qasr_sep_layer.argtypes = [vp, C.POINTER(SepLayerArgs), C.c_char_p, sz]
@@ -127,6 +136,53 @@ def _stream_ptr(stream=None):
 
 def _ptr(t):
     return C.c_void_p(0 if t is None else t.data_ptr())
+
+
+def _ctc_out_struct(res):
+    o = CtcOut()
+    o.struct_size = C.sizeof(CtcOut)
+    for n in ('labels', 'n_labels', 'start', 'nframes', 'score', 'utt_score'):
+        t = getattr(res, n)
+        if t is not None:
+            assert t.is_cuda and t.is_contiguous() and t.dtype == (torch.float32 if 'score' in n else torch.int32), n
+            setattr(o, n, t.data_ptr())
+    return o
+
+
+def ctc_buffers(B, T, device, scores=True, blank=-1):
+    """Device buffers of one k_ctc call as a qasr.ctc.CtcResult of torch tensors (score / utt_score / frame_score only with
+    `scores`)."""
+    from .ctc import CtcResult
+    i32 = dict(device=device, dtype=torch.int32)
+    f32 = dict(device=device, dtype=torch.float32)
+    return CtcResult(labels=torch.empty(B, T, **i32), n_labels=torch.empty(B, **i32), start=torch.empty(B, T, **i32),
+                     nframes=torch.empty(B, T, **i32), score=torch.empty(B, T, **f32) if scores else None,
+                     utt_score=torch.empty(B, **f32) if scores else None, blank=blank,
+                     frame_score=torch.empty(B, T, **f32) if scores else None)
+
+
+def ctc_collapse(tokens, frame_score=None, lens=None, blank=None, out=None, stream=None):
+    """qasr_ctc_collapse: greedy CTC collapse of a cuda int32 token matrix [B, T] on the device (k_ctc, one launch on the
+    current stream).  frame_score f32 [B, T] / lens int32 [B] optional (lens None: the padded row).  Returns a
+    qasr.ctc.CtcResult of cuda tensors (`out`: caller-owned, any of its optional arrays may be None)."""
+    lib = load_library()
+    if blank is None:
+        raise ValueError('ctc_collapse: blank is required (the decoder\'s last class)')
+    assert tokens.is_cuda and tokens.dim() == 2, 'ctc_collapse: tokens must be a cuda tensor [B, T]'
+    dev = tokens.device
+    tok = tokens.to(torch.int32).contiguous()
+    fs = None if frame_score is None else frame_score.to(device=dev, dtype=torch.float32).contiguous()
+    ln = None if lens is None else lens.to(device=dev, dtype=torch.int32).contiguous()
+    B, T = tok.shape
+    if out is None:
+        out = ctc_buffers(B, T, dev, scores=fs is not None, blank=int(blank))
+        out.frame_score = fs
+    o = _ctc_out_struct(out)
+    with torch.cuda.device(dev):
+        _check(lib.qasr_ctc_collapse(_stream_ptr(stream), _ptr(tok), _ptr(fs), _ptr(ln), B, T, int(blank), C.byref(o)),
+               'qasr_ctc_collapse')
+    out._keep = (tok, fs, ln)               # inputs stay alive until the stream has consumed them
+    return out
 
 
 class Engine:
@@ -168,6 +224,9 @@ class Engine:
         hdr = np.frombuffer(blob[:40], dtype=np.uint32)
         self.feat_in, self.n_classes = int(hdr[4]), int(hdr[5])
         self.B = self.T = None
+        self._ctc = None                    # (frame_score, CtcResult, use_lens) attached to the engine
+        self._ctc_auto = False              # ... by a decode= call (dropped again by the next call without decode=)
+        self._ctc_cache = {}                # decode=True: persistent buffers of the current (B, T')
 
     def close(self):
         if getattr(self, '_h', None) and self._h.value:
@@ -187,8 +246,50 @@ class Engine:
         """kernel launches of one forward of the current plan (after a forward)"""
         return self.lib.qasr_engine_num_launches(self._h)
 
-    def forward(self, feats: torch.Tensor, lens: torch.Tensor, want_logp=True, stream=None, out=None):
-        """feats f32 [B, feat_in, T] (cuda, contiguous), lens [B] -> (log_probs [B,T',C], tokens [B,T'], enc_len [B])."""
+    # ---- greedy CTC decoding behind the decoder (qasr_engine_attach_ctc)
+    def attach_ctc(self, frame_score=None, out=None, use_lens=True):
+        """Sticky: every later forward / forward_audio also writes `frame_score` (f32 [B, T'] cuda: the log-probability of
+        each frame's arg-max class, from the decoder kernel itself) and, with `out` (a qasr.ctc.CtcResult of cuda tensors,
+        e.g. ctc_buffers), collapses its tokens with k_ctc inside the same stream / captured graph.  The buffers are the
+        caller's: keep them (and their pointers) for as long as they are attached."""
+        if frame_score is None and out is None:
+            return self.detach_ctc()
+        if frame_score is not None:
+            assert frame_score.is_cuda and frame_score.dtype == torch.float32 and frame_score.is_contiguous()
+        o = _ctc_out_struct(out) if out is not None else None
+        _check(self.lib.qasr_engine_attach_ctc(self._h, _ptr(frame_score), C.byref(o) if o is not None else None,
+                                               int(bool(use_lens))), 'qasr_engine_attach_ctc')
+        self._ctc = (frame_score, out, bool(use_lens))
+        self._ctc_auto = False
+
+    def detach_ctc(self):
+        _check(self.lib.qasr_engine_attach_ctc(self._h, None, None, 0), 'qasr_engine_attach_ctc')
+        self._ctc = None
+        self._ctc_auto = False
+
+    def _decode_begin(self, decode, B, To, device):
+        """decode=None: nothing (an attachment a decode= call made is dropped); True: the engine's persistent buffers for
+        this shape; a CtcResult: caller-owned buffers (its frame_score, if any, is attached too).  Returns the result."""
+        if decode is None or decode is False:
+            if self._ctc_auto:
+                self.detach_ctc()
+            return None
+        if decode is True:
+            res = self._ctc_cache.get((B, To))
+            if res is None:                                  # one buffer set, for the current shape (like the engine's plan)
+                res = ctc_buffers(B, To, device, scores=True, blank=self.n_classes - 1)
+                self._ctc_cache = {(B, To): res}
+        else:
+            res = decode
+        if self._ctc is None or self._ctc[1] is not res or self._ctc[0] is not res.frame_score or not self._ctc[2]:
+            self.attach_ctc(res.frame_score, res, use_lens=True)
+            self._ctc_auto = True
+        return res
+
+    def forward(self, feats: torch.Tensor, lens: torch.Tensor, want_logp=True, stream=None, out=None, decode=None):
+        """feats f32 [B, feat_in, T] (cuda, contiguous), lens [B] -> (log_probs [B,T',C], tokens [B,T'], enc_len [B]).
+        decode=True (or a qasr.ctc.CtcResult of caller-owned, pointer-stable cuda buffers): the greedy CTC collapse runs in
+        the same call, stopping at the encoded lengths, and the result is returned as a fourth element."""
         assert feats.is_cuda and feats.dtype == torch.float32 and feats.dim() == 3 and feats.shape[1] == self.feat_in
         feats = feats.contiguous()
         lens32 = lens.to(device=feats.device, dtype=torch.int32).contiguous()
@@ -200,14 +301,15 @@ class Engine:
             logp = torch.empty(B, To, self.n_classes, device=feats.device, dtype=torch.float32) if want_logp else None
             tokens = torch.empty(B, To, device=feats.device, dtype=torch.int32)
             enc_len = torch.empty(B, device=feats.device, dtype=torch.int32)
+        res = self._decode_begin(decode, B, To, feats.device)
         _check(self.lib.qasr_engine_forward(self._h, _stream_ptr(stream), _ptr(feats), _ptr(lens32), B, T,
                                             _ptr(logp), _ptr(tokens), _ptr(enc_len)), 'qasr_engine_forward')
         self.B, self.T = B, T
         self._keep = (feats, lens32)        # keep inputs alive until the stream has consumed them
-        return logp, tokens, enc_len
+        return (logp, tokens, enc_len) if res is None else (logp, tokens, enc_len, res)
 
     def forward_audio(self, audio, audio_lens, fb, window, plan, preemph=0.97, pad_to=16, want_logp=True, stream=None,
-                      feats=None, feat_lens=None, out=None):
+                      feats=None, feat_lens=None, out=None, decode=None):
         """qasr_engine_forward_audio: audio f32 [B, S] (cuda) -> (log_probs, tokens, enc_len) with the mel front-end inside the
         engine's call (one hipGraph launch per batch once the buffer set has been seen twice).  `plan` = frontend_plan(fb);
         `feats` / `feat_lens` / `out` = caller-owned buffers (stable pointers keep the captured graph)."""
@@ -228,13 +330,14 @@ class Engine:
             logp = torch.empty(B, To, self.n_classes, device=dev, dtype=torch.float32) if want_logp else None
             tokens = torch.empty(B, To, device=dev, dtype=torch.int32)
             enc_len = torch.empty(B, device=dev, dtype=torch.int32)
+        res = self._decode_begin(decode, B, To, dev)            # (see forward: the collapse rides in the same call)
         _check(self.lib.qasr_engine_forward_audio(self._h, _stream_ptr(stream), _ptr(audio), _ptr(audio_lens), B, S, _ptr(fb),
                                                   _ptr(window), n_mels, C.c_float(preemph), pad_to, _ptr(plan), plan.numel(),
                                                   _ptr(feats), _ptr(feat_lens), _ptr(logp), _ptr(tokens), _ptr(enc_len)),
                'qasr_engine_forward_audio')
         self.B, self.T = B, T
         self._keep = (audio, audio_lens, feats, feat_lens, fb, window, plan)
-        return logp, tokens, enc_len
+        return (logp, tokens, enc_len) if res is None else (logp, tokens, enc_len, res)
 
     # ---- parity hooks (debug engines)
     def read_acc(self, op, pane, cout, T_out):
