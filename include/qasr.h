@@ -182,7 +182,11 @@ typedef struct qasr_engine_opts {
                                   routes), removed in round 4: must be <= 0.  The three retired fields keep the struct layout */
   int32_t fuse_norm;           /* qasr_engine_forward_audio with the fused block 0: normalize_batch folded into k_stem from
                                   per-tile sums k_mel writes (no k_norm launch; `feats` then holds the UN-normalised log-mel) */
-  int32_t reserved[2];
+  int32_t mask_skip;           /* k_sep2's layers run as k_sep2s: a work-group whose frames all lie at or beyond its utterance's
+                                  length stores the zero codes and returns (the same bytes, no work).  Default (-1): on for a
+                                  reserved engine (qasr_engine_reserve), off otherwise - the never-taken branch costs the
+                                  full-length step 0.14 - 0.28 us per launch */
+  int32_t reserved[1];
 } qasr_engine_opts;
 /* fills `o` with struct_size and the defaults (-1 / 0) */
 void qasr_engine_default_opts(qasr_engine_opts* o);
@@ -291,6 +295,80 @@ int qasr_ctc_collapse(void* stream, const int32_t* tokens, const float* frame_sc
  * QASR_ERR_ARG: a blob without a LOGSOFTMAX op, score / utt_score without frame_score, missing labels / n_labels. */
 int qasr_engine_attach_ctc(qasr_engine* e, float* frame_score, const qasr_ctc_out* out, int use_lens);
 
+/* ---- reserved engines: ragged batches without allocation, with graph replay ------------------------------------------
+ * A data loader pads every batch to its own longest utterance (the reference's collate function), so (B, T) changes on
+ * almost every call; qasr_engine_forward[_audio] then rebuilds its plan (device-synchronising frees + allocations) and,
+ * with caller-allocated outputs, never replays a graph.  qasr_engine_reserve allocates ONCE for an envelope: the arena,
+ * the length tables, every workspace, staging buffers for the input and engine-owned output buffers.  Afterwards
+ * qasr_engine_forward_ragged[_audio] run any shape inside the envelope:
+ *   - the shape is rounded up to a bucket: all max_batch rows (the added rows have length 0) and
+ *     qasr_ragged_bucket_frames() frames; the outputs for rows < B and frames < T' are bit-identical to the exact-shape
+ *     forward of an unreserved engine (every conv masks its input with the lengths; the mel front-end reads the batch's
+ *     own sample count from a device-resident shape block, so torch.stft's reflect padding folds where it does at the
+ *     exact shape);
+ *   - one kernel (k_ragged_stage) copies input and lengths into the engine's staging buffers and writes the shape
+ *     block; it is launched directly, everything behind it belongs to the bucket's hipGraph: the first call that lands
+ *     in a bucket launches kernel by kernel, the second captures, later ones replay.  Graphs are kept per bucket and
+ *     share the one arena;
+ *   - a shape outside the envelope returns QASR_ERR_ARG (the message names the limit); nothing is reallocated.
+ * Debug / timing engines cannot be reserved.  A reserved engine refuses qasr_engine_forward[_audio] (they would rebuild
+ * the plan): use a second engine for those.  Graph capture needs a non-default stream, as for qasr_engine_opts.graph. */
+typedef struct qasr_reserve_opts {
+  uint32_t struct_size;        /* sizeof(qasr_reserve_opts) of the caller's header */
+  int32_t max_batch;           /* >= 1 */
+  int32_t max_samples;         /* audio entry: longest padded row S (0: audio entry not used) */
+  int32_t max_frames;          /* feature entry: most frames T (0: derived from max_samples); the envelope is the larger of
+                                  the two, rounded up to a multiple of 128 frames */
+  int32_t n_mels;              /* audio entry: rows of the filterbank (0: the blob's feat_in) */
+  int32_t pad_to;              /* audio entry: frames are padded to a multiple of it; must divide 128 (0: 16) */
+  int32_t want_logp;           /* keep a log-probability buffer [max_batch][T'max][n_classes] */
+  int32_t decode;              /* greedy CTC outputs and per-frame scores as qasr_engine_attach_ctc writes them: 1: use_lens = 1
+                                  (stop at the encoded lengths); 2: use_lens = 0 (the padded row as the reference walks it -
+                                  the batch's own T' frames, not the bucket's) */
+  int32_t max_graphs;          /* most buckets, one captured graph each (0: 16; at most 64) */
+  int32_t reserved[3];
+} qasr_reserve_opts;
+/* Engine-owned buffers of the last ragged forward (device pointers; valid until the next call on this engine).  Rows
+ * are `*_pitch` ELEMENTS apart; rows < B and frames < out_frames hold the result, the rest is unspecified. */
+typedef struct qasr_ragged_out {
+  uint32_t struct_size;        /* sizeof(qasr_ragged_out), set by the caller */
+  int32_t out_frames;          /* T' of the exact shape: qasr_engine_out_frames(e, T) */
+  int32_t bucket_frames;       /* the bucket edge this call ran at (input frames) */
+  int32_t row_pitch;           /* frames per row of tokens / frame_score / the CTC outputs */
+  int32_t n_classes;
+  int32_t* tokens;             /* i32 [max_batch][row_pitch] */
+  int32_t* lens_out;           /* i32 [max_batch] encoded lengths */
+  float* logp;                 /* f32 [max_batch][row_pitch][n_classes], NULL without want_logp */
+  float* frame_score;          /* f32 [max_batch][row_pitch], NULL without decode */
+  qasr_ctc_out ctc;            /* NULL members without decode */
+  float* feats;                /* audio entry: staging features f32 [max_batch][n_mels][bucket_frames] (see
+                                  qasr_engine_forward_audio for what they hold) */
+  int32_t* feat_lens;          /* i32 [max_batch] */
+} qasr_ragged_out;
+typedef struct qasr_ragged_stats {
+  uint32_t struct_size;        /* sizeof(qasr_ragged_stats), set by the caller */
+  int32_t n_buckets;           /* buckets with at least one call */
+  uint64_t device_allocs;      /* hipMalloc calls made by this engine since qasr_engine_create */
+  uint64_t device_frees;       /* hipFree calls */
+  uint64_t graphs_captured, graph_replays, eager_runs;
+  int32_t bucket_frames[64];   /* per bucket that was visited: its edge */
+  uint64_t bucket_calls[64];   /* ... and the calls that landed in it */
+} qasr_ragged_stats;
+int qasr_engine_reserve(qasr_engine* e, const qasr_reserve_opts* opts);
+/* As qasr_engine_forward / qasr_engine_forward_audio without the output (and feature) pointers; lens[b] <= T. */
+int qasr_engine_forward_ragged(qasr_engine* e, void* stream, const float* feats, const int32_t* lens, int B, int T,
+                               qasr_ragged_out* out);
+int qasr_engine_forward_ragged_audio(qasr_engine* e, void* stream, const float* audio, const int32_t* audio_lens, int B, int S,
+                                     const float* fb, const float* window, int n_mels, float preemph, int pad_to,
+                                     const void* frontend_plan, size_t plan_bytes, qasr_ragged_out* out);
+/* Works on every engine (an unreserved one reports its allocations and zero graphs). */
+int qasr_engine_ragged_stats(const qasr_engine* e, qasr_ragged_stats* out);
+/* The bucket policy, a pure function (no GPU): max_frames (a multiple of 128) is cut into at most max_graphs equal steps
+ * of whole 128-frame tiles; returns the smallest edge >= T, or -1 when T < 1, T > max_frames or an argument is bad.
+ * qasr_ragged_envelope_frames: the envelope a qasr_reserve_opts describes (-1: bad arguments). */
+int qasr_ragged_bucket_frames(int max_frames, int max_graphs, int T);
+int qasr_ragged_envelope_frames(int max_samples, int max_frames, int pad_to);
+
 /* ---- stand-alone operators (same kernels the engine launches; device pointers) -------------- */
 
 /* AudioToMelSpectrogramPreprocessor.forward / FilterbankFeatures.forward
@@ -392,7 +470,8 @@ int qasr_dyn_conv_params(void* stream, const float* s_x, const float* s_w, const
  * ReLU -> the consumers' QuantAct requant (jasper.py:569-600,664-687; quant_modules.py:186-190,301-309).  Every pointer
  * is a device pointer in the blob's layouts (see qasr_op_desc): the parity tests drive the production kernels through
  * this entry with operands of their own making (accumulators beyond 2^22, rounding ties, ragged lengths).
- * K == 0: no depthwise stage (`x` feeds the 1x1 conv).  gen: 2 = k_sep2 where it has the shape, 1 = k_sep.
+ * K == 0: no depthwise stage (`x` feeds the 1x1 conv).  gen: 2 = k_sep2 where it has the shape, 1 = k_sep, 3 = k_sep2s
+ * (k_sep2 with the mask-skip rule, see qasr_engine_opts.mask_skip).
  * tile: 32, 64 or 128 (k_sep2's plain layers; others fall back to 64) frames per work-group.  `label` (optional)
  * receives the kernel instantiation that ran. */
 typedef struct qasr_sep_layer_args {

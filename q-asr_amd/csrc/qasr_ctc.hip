@@ -34,6 +34,7 @@ struct CtcP {
   float* score;             // optional [B][T] (needs fs)
   float* utt_score;         // optional [B] (needs fs)
   int B, T, blank;
+  const int32_t* t_act;     // optional (device): frames of the batch inside rows of pitch T (reserved engines)
 };
 
 // float32 bits <-> an int that orders like the float (its own inverse)
@@ -44,7 +45,8 @@ __global__ void __launch_bounds__(CTC_NT) k_ctc(CtcP p) {
   __shared__ float sm_part[64];
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, nw = blockDim.x >> 6;
   const int b = blockIdx.x, T = p.T;
-  const int lim = p.lens ? min(max(p.lens[b], 0), T) : T;
+  const int Ta = p.t_act ? min(*p.t_act, T) : T;
+  const int lim = p.lens ? min(max(p.lens[b], 0), Ta) : Ta;
   const int32_t* const tok = p.tokens + (size_t)b * T;
   const float* const fs = p.fs ? p.fs + (size_t)b * T : nullptr;
   const size_t row = (size_t)b * T;
@@ -132,14 +134,14 @@ __global__ void __launch_bounds__(CTC_NT) k_ctc(CtcP p) {
 }
 
 int launch_ctc(hipStream_t s, const int32_t* tokens, const float* frame_score, const int32_t* lens, int B, int T, int blank,
-               const qasr_ctc_out& out) {
+               const qasr_ctc_out& out, const int32_t* t_act) {
   if (!tokens || !out.labels || !out.n_labels || B < 1 || T < 1) return QASR_ERR_ARG;
   if ((out.score || out.utt_score) && !frame_score) return QASR_ERR_ARG;
   CtcP p{};
   p.tokens = tokens, p.fs = frame_score, p.lens = lens;
   p.labels = out.labels, p.n_labels = out.n_labels, p.start = out.start, p.nframes = out.nframes;
   p.score = out.score, p.utt_score = out.utt_score;
-  p.B = B, p.T = T, p.blank = blank;
+  p.B = B, p.T = T, p.blank = blank, p.t_act = t_act;
   hipLaunchKernelGGL(k_ctc, dim3(B), dim3(CTC_NT), 0, s, p);
   return QASR_OK;
 }

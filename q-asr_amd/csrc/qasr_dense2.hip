@@ -114,6 +114,14 @@ __global__ void __launch_bounds__(DENSE2_NT, 2) k_dense2(SepP p) {
   for (int mt = 0; mt < MT; ++mt)
 #pragma unroll
     for (int r = 0; r < 16; ++r) acc[mt][r] = bias;
+  // mask-skip (work-group uniform, behind the per-lane parameter requests): every frame of this tile is masked - store the
+  // zero codes the epilogue would store for this work-group's 128 channels (frames below Tp only) and leave
+  if constexpr (!DBG) {
+    if ((flags & QASR_F_MASK_OUT) && t0 >= lim && !p.prof) {
+      store_masked_tile<DENSE2_NT>(e, b, t0, min(32 * MT, eTp - t0), 128 * (int)blockIdx.y, min(128, ecout - 128 * (int)blockIdx.y), tid);
+      return;
+    }
+  }
 
   // weight fragments of item i = (chunk, tap): the 4 K steps of the chunk, fragment order (pack.py:fragment_order), one
   // fragment-ordered [cout_pad][cin_pad] matrix per tap (QASR_F_TAPMAJOR); two register sets, loaded one item (32 MT / 8

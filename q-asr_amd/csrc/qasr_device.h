@@ -7,6 +7,25 @@ namespace qasr {
 typedef int v4i __attribute__((ext_vector_type(4)));
 typedef int v16i __attribute__((ext_vector_type(16)));
 
+// (always inlined: a call from these kernels costs them their register allocation - measured 3.5x slower)
+// Mask-skip rule: a QASR_F_MASK_OUT op's work-group whose frames [t0, t0 + TT) all lie at or beyond the
+// utterance's length writes exactly what the full path writes there - code 0 in every consumer's tensor (byte 0; int32 0
+// for a raw accumulator consumer, mode 3) - without staging, multiplying or requantising anything.  Channels
+// [c0, c0 + nc) of utterance b, 16 bytes per lane; every row start is 16-byte aligned (Tp % 64 == 0, t0 % 32 == 0).
+template <int NT>
+__device__ __forceinline__ void store_masked_tile(const EpiP& e, int b, int t0, int TT, int c0, int nc, int tid) {
+  const int n_outs = e.n_outs;
+  for (int j = 0; j < n_outs; ++j) {
+    const int esz = e.outs[j].mode == 3 ? 4 : 1;
+    const int gpr = TT * esz / 16, total = nc * gpr;         // 16-byte granules per row / in all
+    char* const base = (char*)e.outs[j].ptr + (((size_t)b * e.cout + c0) * e.Tp + t0) * esz;
+    for (int i = tid; i < total; i += NT) {
+      const int c = i / gpr, q = i - c * gpr;
+      *(v4i*)(base + (size_t)c * e.Tp * esz + 16 * q) = (v4i){0, 0, 0, 0};
+    }
+  }
+}
+
 #define MAGIC_RNE 6755399441055744.0 /* 1.5 * 2^52: fma(z, M, MAGIC) rounds z*M half-to-even into the low word */
 
 // clamp(rint(z * M), lo, hi): fixedpoint_mul.forward (quant_utils.py:196-198,213).  z*M is exact in fp64

@@ -7,6 +7,7 @@
 #include <cstdlib>
 #include <cstring>
 #include <string>
+#include <type_traits>
 #include <vector>
 
 #include "qasr_internal.h"
@@ -111,6 +112,7 @@ struct qasr_engine {
   bool res_tile128 = true;             // block-end layers on 128-frame tiles too (qasr_engine_opts.res_tile128)
   bool dense_tile128 = true;           // QASR_DENSE_TILE128=0 keeps Jasper's dense convs on 64-frame tiles (A/B runs)
   bool wide_tiles = false;             // k_sep with 64-frame tiles (throughput mode: bit 3 of `debug`, or QASR_WIDE_TILES=1)
+  int mask_skip = -1;                  // k_sep2s (mask-skip rule): -1 = when reserved, 0 = never, 1 = always (qasr_engine_opts.mask_skip)
   int sep_gen = 2;                     // 2: k_sep2 where it has the shape; 1 (QASR_SEP_GEN=1): k_sep everywhere (A/B runs)
   // hipGraph replay (bit 4 of `debug`): the whole forward of one (shape, buffer set) is captured once and re-launched
   // with one call; key = the caller's pointers, which a serving loop keeps stable
@@ -128,7 +130,49 @@ struct qasr_engine {
   bool ctc_on = false;                 // ctc_out is attached: one more launch
   int ctc_use_lens = 0;
   uint64_t gctc[8] = {0, 0, 0, 0, 0, 0, 0, 0};   // the attachment a captured graph bakes in
+  // qasr_engine_ragged_stats: every hipMalloc / hipFree this engine makes goes through dev_alloc / dev_free
+  uint64_t n_allocs = 0, n_frees = 0;
+  // qasr_engine_reserve: the plan, staging and output buffers are allocated once for the envelope max_batch x max_frames;
+  // qasr_engine_forward_ragged[_audio] re-derive the launch parameters for a bucket shape inside it and never allocate
+  struct Bucket {
+    int frames = 0;
+    uint64_t calls = 0;
+    hipGraphExec_t gexec = nullptr;
+    uint64_t key[8] = {0, 0, 0, 0, 0, 0, 0, 0};   // what the graph bakes in besides the engine's own buffers (front-end arguments)
+  };
+  struct Reserved {
+    bool on = false;
+    int max_batch = 0, max_samples = 0, max_frames = 0, n_mels = 0, pad_to = 16, max_graphs = 16;
+    int spitch = 0, out_frames = 0;      // staging pitch of an audio row; T' of max_frames
+    bool want_logp = false, decode = false;
+    int decode_use_lens = 1;
+    float* audio = nullptr;              // [max_batch][spitch]
+    int32_t* audio_lens = nullptr;       // [max_batch]
+    float* feats = nullptr;              // [max_batch][n_mels or feat_in][max_frames]
+    int32_t* feat_lens = nullptr;        // [max_batch]
+    int32_t* shp = nullptr;              // shape block, QASR_SHAPE_WORDS i32
+    int32_t* tokens = nullptr;
+    int32_t* lens_out = nullptr;
+    float* logp = nullptr;
+    float* fs = nullptr;
+    qasr_ctc_out ctc{};
+    std::vector<void*> owned;
+    std::vector<Bucket> buckets;
+    uint64_t captured = 0, replays = 0, eager = 0;
+  } rs;
+  const int32_t* ctc_t_act = nullptr;  // ragged forward being enqueued: k_ctc walks the batch's own T' (shape block)
 };
+
+static hipError_t dev_alloc(qasr_engine* e, void** p, size_t n) {
+  hipError_t rc = hipMalloc(p, n);
+  if (rc == hipSuccess) e->n_allocs++;
+  return rc;
+}
+static void dev_free(qasr_engine* e, void* p) {
+  if (!p) return;
+  (void)hipFree(p);
+  e->n_frees++;
+}
 
 template <class T>
 static const T* dev_at(const qasr_engine* e, uint64_t off) {
@@ -148,23 +192,23 @@ static int conv_out_len(int len, const qasr_domain_desc& d) {
 }
 
 static void free_plan(qasr_engine* e) {
-  for (void* p : e->slots) (void)hipFree(p);
+  for (void* p : e->slots) dev_free(e, p);
   e->slots.clear();
   e->slot_bytes.clear();
-  if (e->lens_all) (void)hipFree(e->lens_all);
+  dev_free(e, e->lens_all);
   e->lens_all = nullptr;
-  if (e->time_tokens) (void)hipFree(e->time_tokens);
+  dev_free(e, e->time_tokens);
   e->time_tokens = nullptr;
-  if (e->norm_stats) (void)hipFree(e->norm_stats);
+  dev_free(e, e->norm_stats);
   e->norm_stats = nullptr;
   e->norm_stats_bytes = 0;
   e->norm_tiles = e->norm_frames = 0;
-  if (e->decw_ws) (void)hipFree(e->decw_ws);
+  dev_free(e, e->decw_ws);
   e->decw_ws = nullptr;
   e->decw_ws_bytes = 0;
   for (auto& v : e->acc_dbg)
     for (auto p : v)
-      if (p) (void)hipFree(p);
+      dev_free(e, p);
   e->acc_dbg.clear();
   e->tens.clear();
   e->B = e->T0 = 0;
@@ -173,8 +217,9 @@ static void free_plan(qasr_engine* e) {
 
 static void build_sep(qasr_engine* e, uint32_t oi, SepP& p);
 
-static int build_plan(qasr_engine* e, int B, int T0) {
-  free_plan(e);
+// Launch parameters of a shape: frames per time domain, every tensor's frames / row pitch / bytes, the fusion plan.
+// Host only.  Arena slots and pointers a tensor already holds are kept: a reserved engine calls this per bucket.
+static int plan_shape(qasr_engine* e, int B, int T0) {
   const auto& h = e->h;
   e->domT.assign(h.n_domains, 0);
   e->domT[0] = T0;
@@ -209,6 +254,16 @@ static int build_plan(qasr_engine* e, int B, int T0) {
       e->fused_dw[oi + 1] = (int)oi;
       e->skip[oi] = 1;
     }
+  e->B = B;
+  e->T0 = T0;
+  return QASR_OK;
+}
+
+// Allocates for the shape plan_shape derived last: arena, length tables, workspaces.  A reserved engine calls it once,
+// for its maximum; every smaller shape fits the same slots (a tensor's bytes grow with B and T, its lifetime does not move).
+static int plan_alloc(qasr_engine* e) {
+  const auto& h = e->h;
+  const int B = e->B, T0 = e->T0;
   // a production engine's fused wide decoder (k_decw) never stores the float logits [B][T][C] (167 MB at bs32 x 500
   // frames x 5207 classes): that tensor gets no arena slot; launch_op takes the same decision from the same shapes
   std::vector<char> no_slot(h.n_tensors, 0);
@@ -237,7 +292,7 @@ static int build_plan(qasr_engine* e, int B, int T0) {
       free_slots.erase(free_slots.begin() + best);
     } else {
       void* p = nullptr;
-      if (hipMalloc(&p, t.bytes) != hipSuccess) return -1;
+      if (dev_alloc(e, &p, t.bytes) != hipSuccess) return -1;
       e->slots.push_back(p);
       e->slot_bytes.push_back(t.bytes);
       s = (int)e->slots.size() - 1;
@@ -259,20 +314,20 @@ static int build_plan(qasr_engine* e, int B, int T0) {
       if (dead_after && !e->debug) free_slots.push_back(t.slot);
     }
   }
-  HIPCHK(hipMalloc((void**)&e->lens_all, sizeof(int32_t) * h.n_domains * B));
+  HIPCHK(dev_alloc(e, (void**)&e->lens_all, sizeof(int32_t) * h.n_domains * B));
   for (uint32_t oi = 0; oi < h.n_ops; ++oi) {                // k_decw's workspace, for a decoder wider than k_dec's 32 classes
     const qasr_op_desc& op = e->ops[oi];
     if (op.kind != QASR_OP_PW || !(op.flags & QASR_F_LOGITS) || op.cout <= 32) continue;
     const size_t need = decoder_wide_ws_bytes(B, e->tens[op.outs[0].tensor].Tp);
     if (need > e->decw_ws_bytes) {
-      if (e->decw_ws) HIPCHK(hipFree(e->decw_ws));
+      dev_free(e, e->decw_ws);
       e->decw_ws = nullptr;
       e->decw_ws_bytes = 0;
-      HIPCHK(hipMalloc(&e->decw_ws, need));
+      HIPCHK(dev_alloc(e, &e->decw_ws, need));
       e->decw_ws_bytes = need;
     }
   }
-  HIPCHK(hipMalloc((void**)&e->time_tokens, sizeof(int32_t) * (size_t)B * (T0 + 64)));
+  HIPCHK(dev_alloc(e, (void**)&e->time_tokens, sizeof(int32_t) * (size_t)B * (T0 + 64)));
   if (e->debug) {
     e->acc_dbg.resize(h.n_ops);
     for (uint32_t oi = 0; oi < h.n_ops; ++oi) {
@@ -282,7 +337,7 @@ static int build_plan(qasr_engine* e, int B, int T0) {
       size_t n = (size_t)B * op.cout * rup(o.T, 64);
       for (uint32_t k = 0; k < 1 + op.n_panes; ++k) {
         int32_t* p = nullptr;
-        HIPCHK(hipMalloc((void**)&p, n * 4));
+        HIPCHK(dev_alloc(e, (void**)&p, n * 4));
         HIPCHK(hipMemset(p, 0, n * 4));
         e->acc_dbg[oi].push_back(p);
       }
@@ -292,9 +347,19 @@ static int build_plan(qasr_engine* e, int B, int T0) {
     e->ev.resize(h.n_ops + 1);
     for (auto& v : e->ev) HIPCHK(hipEventCreate(&v));
   }
-  e->B = B;
-  e->T0 = T0;
   return QASR_OK;
+}
+
+static int build_plan(qasr_engine* e, int B, int T0) {
+  free_plan(e);
+  int rc = plan_shape(e, B, T0);
+  if (rc) {
+    e->B = e->T0 = 0;
+    return rc;
+  }
+  rc = plan_alloc(e);
+  if (rc) e->B = e->T0 = 0;
+  return rc;
 }
 
 static void fill_out(const qasr_engine* e, const qasr_out& o, OutP& d) {
@@ -373,7 +438,7 @@ void qasr_engine_default_opts(qasr_engine_opts* o) {
   if (!o) return;
   memset(o, 0, sizeof *o);
   o->struct_size = (uint32_t)sizeof *o;
-  o->fuse_dw = o->fuse_stem = o->fuse_decoder = o->res_tile128 = o->dense_tile128 = o->fuse_norm = -1;
+  o->fuse_dw = o->fuse_stem = o->fuse_decoder = o->res_tile128 = o->dense_tile128 = o->fuse_norm = o->mask_skip = -1;
 }
 
 // the `debug` bits of round 1 / 2 callers, as options
@@ -424,6 +489,7 @@ int qasr_engine_create_ex(const void* blob, size_t n, int device, const qasr_eng
   e->res_tile128 = tri(o.res_tile128, true);
   e->dense_tile128 = tri(o.dense_tile128, true);
   e->sep_gen = o.sep_gen == 1 ? 1 : 2;
+  e->mask_skip = o.mask_skip < 0 ? -1 : (o.mask_skip != 0);
   e->use_graph = o.graph > 0;
   // environment: A/B overrides for profiling runs of an unmodified caller (include/qasr.h lists them), read per create call
   if (getenv("QASR_NO_FUSE")) e->fuse = false;
@@ -440,7 +506,7 @@ int qasr_engine_create_ex(const void* blob, size_t n, int device, const qasr_eng
   e->tdesc = (const qasr_tensor_desc*)(e->blob.data() + h.tensors_off);
   e->ops = (const qasr_op_desc*)(e->blob.data() + h.ops_off);
   e->doms = (const qasr_domain_desc*)(e->blob.data() + h.domains_off);
-  if (hipMalloc((void**)&e->dblob, n + 256) != hipSuccess ||      // slack: 16-byte granule copies may overrun an array's tail
+  if (dev_alloc(e, (void**)&e->dblob, n + 256) != hipSuccess ||      // slack: 16-byte granule copies may overrun an array's tail
       hipMemcpy(e->dblob, blob, n, hipMemcpyHostToDevice) != hipSuccess) {
     delete e;
     return fail(QASR_ERR_HIP, "blob upload failed");
@@ -466,7 +532,7 @@ int qasr_engine_create_ex(const void* blob, size_t n, int device, const qasr_eng
       for (uint32_t k = 0; k < op.n_panes; ++k) add(op.panes[k].w_off, cp * (size_t)rup((int)op.panes[k].cin, 128));
     }
     if (!jobs.empty()) {
-      if (hipMalloc((void**)&e->dexp, total) != hipSuccess) {
+      if (dev_alloc(e, (void**)&e->dexp, total) != hipSuccess) {
         qasr_engine_destroy(e);
         return fail(QASR_ERR_HIP, "weight expansion buffer (%zu bytes)", total);
       }
@@ -502,10 +568,13 @@ void qasr_engine_destroy(qasr_engine* e) {
   if (!e) return;
   (void)hipSetDevice(e->device);
   if (e->gexec) (void)hipGraphExecDestroy(e->gexec);
+  for (auto& bk : e->rs.buckets)
+    if (bk.gexec) (void)hipGraphExecDestroy(bk.gexec);
+  for (void* p : e->rs.owned) dev_free(e, p);
   free_plan(e);
   for (auto v : e->ev) (void)hipEventDestroy(v);
-  if (e->dblob) (void)hipFree(e->dblob);
-  if (e->dexp) (void)hipFree(e->dexp);
+  dev_free(e, e->dblob);
+  dev_free(e, e->dexp);
   delete e;
 }
 
@@ -543,6 +612,7 @@ static void build_sep(qasr_engine* e, uint32_t oi, SepP& p) {
   p.etile = p.tile;
   if (p.tile == 128 && !e->res_tile128 && (op.flags & QASR_F_RESADD)) p.tile = 64;
   p.gen = e->sep_gen;
+  p.mask_skip = e->mask_skip < 0 ? e->rs.on : e->mask_skip != 0;
   fill_panes(e, oi, op, p.panes);
   fill_epi(e, oi, op, p.e);
   const int di = e->fused_dw[oi];
@@ -781,10 +851,46 @@ struct FrontArgs {
   int pad_to;
   const void* plan;
   size_t plan_bytes;
+  const RaggedFront* rg;               // reserved engines: staging pitch, bucket frames, shape block (nullptr otherwise)
 };
+
+// every launch of one forward, in order: front-end, lengths, ops, k_ctc (directly, or inside a stream capture)
+static int enqueue_forward(qasr_engine* e, hipStream_t s, const FrontArgs* fe, bool norm_in_stem, float* feats, int32_t* lens,
+                           float* logp, int32_t* tokens, int32_t* lens_out) {
+  const auto& h = e->h;
+  const int B = e->B;
+  if (fe && norm_in_stem) {
+    int nt = 0, nf = 0;
+    int rc = frontend_mel_stats(s, fe->audio, fe->audio_lens, B, fe->S, fe->fb, fe->window, fe->n_mels, fe->preemph, fe->pad_to,
+                                feats, lens, fe->plan, fe->plan_bytes, e->norm_stats, &nt, &nf, fe->rg);
+    if (rc || nt != e->norm_tiles || nf != e->norm_frames) return fail(rc ? rc : QASR_ERR_ARG, "forward_audio: front-end (k_mel with statistics)");
+  } else if (fe) {                                           // mel front-end into the caller's feature / length buffers
+    int rc = fe->rg ? frontend_mel_planned_ragged(s, fe->audio, fe->audio_lens, B, fe->S, fe->fb, fe->window, fe->n_mels,
+                                                  fe->preemph, fe->pad_to, feats, lens, fe->plan, fe->plan_bytes, *fe->rg)
+                    : qasr_frontend_mel_planned(s, fe->audio, fe->audio_lens, B, fe->S, fe->fb, fe->window, fe->n_mels, fe->preemph,
+                                                fe->pad_to, feats, lens, fe->plan, fe->plan_bytes);
+    if (rc) return fail(rc, "forward_audio: front-end");
+  }
+  const qasr_domain_desc* ddoms = (const qasr_domain_desc*)(e->dblob + h.domains_off);
+  if (!e->stem) launch_lens(s, lens, e->lens_all, ddoms, (int)h.n_domains, B);   // (k_stem derives them itself)
+  for (uint32_t oi = 0; oi < h.n_ops; ++oi) {
+    if (e->timing) HIPCHK(hipEventRecord(e->ev[oi], s));
+    int rc = launch_op(e, s, oi, logp, tokens, lens_out);
+    if (rc) return rc;
+  }
+  if (e->ctc_on) {                                           // greedy collapse of this call's tokens, behind the decoder
+    const qasr_op_desc& ls = e->ops[logsoftmax_op(e)];
+    const TensorRT& tl = e->tens[ls.in];
+    int rc = launch_ctc(s, tokens, e->ctc_fs, e->ctc_use_lens ? e->lens_all + (size_t)tl.d.domain * B : nullptr, B, tl.T,
+                        (int)ls.cin - 1, e->ctc_out, e->ctc_t_act);
+    if (rc) return fail(rc, "k_ctc launch");
+  }
+  return QASR_OK;
+}
 
 static int forward_impl(qasr_engine* e, hipStream_t s, const FrontArgs* fe, float* feats, int32_t* lens, int B, int T,
                         float* logp, int32_t* tokens, int32_t* lens_out) {
+  if (e->rs.on) return fail(QASR_ERR_ARG, "forward: this engine is reserved (qasr_engine_reserve): use qasr_engine_forward_ragged[_audio], or a second engine");
   if (B != e->B || T != e->T0) {
     int rc = build_plan(e, B, T);
     if (rc) return rc;
@@ -809,40 +915,14 @@ static int forward_impl(qasr_engine* e, hipStream_t s, const FrontArgs* fe, floa
       if (e->gexec) (void)hipGraphExecDestroy(e->gexec);
       e->gexec = nullptr;
       e->gkey[0] = nullptr;
-      if (e->norm_stats) HIPCHK(hipFree(e->norm_stats));
+      dev_free(e, e->norm_stats);
       e->norm_stats = nullptr;
       e->norm_stats_bytes = 0;
-      HIPCHK(hipMalloc(&e->norm_stats, need));
+      HIPCHK(dev_alloc(e, (void**)&e->norm_stats, need));
       e->norm_stats_bytes = need;
     }
   }
-  auto enqueue = [&]() -> int {
-    if (fe && norm_in_stem) {
-      int nt = 0, nf = 0;
-      int rc = frontend_mel_stats(s, fe->audio, fe->audio_lens, B, fe->S, fe->fb, fe->window, fe->n_mels, fe->preemph, fe->pad_to,
-                                  feats, lens, fe->plan, fe->plan_bytes, e->norm_stats, &nt, &nf);
-      if (rc || nt != e->norm_tiles || nf != e->norm_frames) return fail(rc ? rc : QASR_ERR_ARG, "forward_audio: front-end (k_mel with statistics)");
-    } else if (fe) {                                         // mel front-end into the caller's feature / length buffers
-      int rc = qasr_frontend_mel_planned(s, fe->audio, fe->audio_lens, B, fe->S, fe->fb, fe->window, fe->n_mels, fe->preemph,
-                                         fe->pad_to, feats, lens, fe->plan, fe->plan_bytes);
-      if (rc) return fail(rc, "forward_audio: front-end");
-    }
-    const qasr_domain_desc* ddoms = (const qasr_domain_desc*)(e->dblob + h.domains_off);
-    if (!e->stem) launch_lens(s, lens, e->lens_all, ddoms, (int)h.n_domains, B);   // (k_stem derives them itself)
-    for (uint32_t oi = 0; oi < h.n_ops; ++oi) {
-      if (e->timing) HIPCHK(hipEventRecord(e->ev[oi], s));
-      int rc = launch_op(e, s, oi, logp, tokens, lens_out);
-      if (rc) return rc;
-    }
-    if (e->ctc_on) {                                         // greedy collapse of this call's tokens, behind the decoder
-      const qasr_op_desc& ls = e->ops[logsoftmax_op(e)];
-      const TensorRT& tl = e->tens[ls.in];
-      int rc = launch_ctc(s, tokens, e->ctc_fs, e->ctc_use_lens ? e->lens_all + (size_t)tl.d.domain * B : nullptr, B, tl.T,
-                          (int)ls.cin - 1, e->ctc_out);
-      if (rc) return fail(rc, "k_ctc launch");
-    }
-    return QASR_OK;
-  };
+  auto enqueue = [&]() -> int { return enqueue_forward(e, s, fe, norm_in_stem, feats, lens, logp, tokens, lens_out); };
   e->forwarded = true;
   if (e->use_graph && s != nullptr && !e->timing && !e->debug) {   // the legacy default stream cannot be captured
     const void* key[8] = {feats, lens, logp, tokens, lens_out, fe ? fe->audio : nullptr, fe ? fe->audio_lens : nullptr,
@@ -951,8 +1031,291 @@ int qasr_engine_forward_audio(qasr_engine* e, void* stream, const float* audio, 
                               int32_t* tokens, int32_t* lens_out) {
   if (!e || !audio || !audio_lens || !fb || !window || !frontend_plan || !feats || !feat_lens || B <= 0 || S <= 0)
     return fail(QASR_ERR_ARG, "bad forward_audio arguments");
-  FrontArgs fe{audio, audio_lens, S, fb, window, n_mels, preemph, pad_to, frontend_plan, plan_bytes};
+  FrontArgs fe{audio, audio_lens, S, fb, window, n_mels, preemph, pad_to, frontend_plan, plan_bytes, nullptr};
   return forward_impl(e, (hipStream_t)stream, &fe, feats, feat_lens, B, qasr_frontend_frames(S, pad_to), logp, tokens, lens_out);
+}
+
+// ---------------------------------------------------------------------------------- reserved engines (ragged batches)
+int qasr_ragged_bucket_frames(int max_frames, int max_graphs, int T) { return ragged_bucket(max_frames, max_graphs, T); }
+
+int qasr_ragged_envelope_frames(int max_samples, int max_frames, int pad_to) {
+  if (pad_to == 0) pad_to = 16;
+  if (pad_to < 1 || QASR_RAGGED_TILE % pad_to || max_samples < 0 || max_frames < 0 || (max_samples == 0 && max_frames == 0)) return -1;
+  if (max_samples > (1 << 28) || max_frames > (1 << 24)) return -1;
+  int m = max_frames;
+  if (max_samples > 0) m = std::max(m, qasr_frontend_frames(max_samples, pad_to));
+  return rup(m, QASR_RAGGED_TILE);
+}
+
+int qasr_engine_reserve(qasr_engine* e, const qasr_reserve_opts* opts) {
+  // the options first: refused without an engine and without touching the device
+  if (!opts) return fail(QASR_ERR_ARG, "reserve: opts is NULL");
+  if (opts->struct_size != sizeof(qasr_reserve_opts))
+    return fail(QASR_ERR_ARG, "reserve: qasr_reserve_opts.struct_size %u is not %zu", opts->struct_size, sizeof(qasr_reserve_opts));
+  const qasr_reserve_opts o = *opts;
+  if (o.max_batch < 1 || o.max_batch > 4096) return fail(QASR_ERR_ARG, "reserve: max_batch %d (1 .. 4096)", o.max_batch);
+  if (o.max_samples <= 0 && o.max_frames <= 0) return fail(QASR_ERR_ARG, "reserve: max_samples and max_frames are both 0: nothing to reserve");
+  if (o.max_samples > 0 && o.max_samples <= 256) return fail(QASR_ERR_ARG, "reserve: max_samples %d (the front-end needs more than 256 samples)", o.max_samples);
+  const int pad_to = o.pad_to ? o.pad_to : 16, max_graphs = o.max_graphs ? o.max_graphs : 16;
+  if (max_graphs < 1 || max_graphs > 64) return fail(QASR_ERR_ARG, "reserve: max_graphs %d (1 .. 64)", o.max_graphs);
+  if (o.decode < 0 || o.decode > 2) return fail(QASR_ERR_ARG, "reserve: decode %d (0, 1 or 2)", o.decode);
+  const int M = qasr_ragged_envelope_frames(std::max(o.max_samples, 0), std::max(o.max_frames, 0), pad_to);
+  if (M < 0) return fail(QASR_ERR_ARG, "reserve: pad_to %d must divide %d; max_samples / max_frames out of range", pad_to, QASR_RAGGED_TILE);
+  if (!e) return fail(QASR_ERR_ARG, "reserve: engine is NULL");
+  if (e->debug || e->timing) return fail(QASR_ERR_ARG, "reserve: debug / timing engines keep per-shape hook buffers and cannot be reserved");
+  if (e->rs.on) return fail(QASR_ERR_ARG, "reserve: this engine is reserved already");
+  if (e->h.n_domains > QASR_SHAPE_MAXDOM) return fail(QASR_ERR_UNSUPPORTED, "reserve: %u time domains (the shape block holds %d)", e->h.n_domains, QASR_SHAPE_MAXDOM);
+  const int ls = logsoftmax_op(e);
+  if (ls < 0) return fail(QASR_ERR_ARG, "reserve: the model has no LOGSOFTMAX op (no CTC decoder)");
+  HIPCHK(hipSetDevice(e->device));
+  if (e->gexec) (void)hipGraphExecDestroy(e->gexec);
+  e->gexec = nullptr;
+  e->gkey[0] = nullptr;
+  free_plan(e);
+  int rc = plan_shape(e, o.max_batch, M);
+  if (!rc) rc = plan_alloc(e);
+  if (rc) {
+    free_plan(e);
+    return rc;
+  }
+  auto& r = e->rs;
+  r.max_batch = o.max_batch;
+  r.max_samples = std::max(o.max_samples, 0);
+  r.max_frames = M;
+  r.n_mels = o.n_mels > 0 ? o.n_mels : (int)e->h.feat_in;
+  r.pad_to = pad_to;
+  r.max_graphs = max_graphs;
+  r.want_logp = o.want_logp != 0;
+  r.decode = o.decode != 0;
+  r.decode_use_lens = o.decode == 2 ? 0 : 1;
+  r.spitch = rup(std::max(r.max_samples, 4), 4);
+  r.out_frames = e->tens[e->ops[ls].in].T;
+  const int ncls = (int)e->ops[ls].cin;
+  const size_t Bm = (size_t)o.max_batch, rows = Bm * (size_t)r.out_frames;
+  bool ok = true;
+  auto take = [&](auto** p, size_t bytes) {
+    void* q = nullptr;
+    if (!ok || dev_alloc(e, &q, bytes) != hipSuccess || hipMemset(q, 0, bytes) != hipSuccess) {
+      ok = false;
+      if (q) r.owned.push_back(q);
+      return;
+    }
+    r.owned.push_back(q);
+    *p = reinterpret_cast<std::remove_reference_t<decltype(*p)>>(q);
+  };
+  take(&r.shp, sizeof(int32_t) * QASR_SHAPE_WORDS);
+  if (r.max_samples > 0) {
+    take(&r.audio, sizeof(float) * Bm * r.spitch);
+    take(&r.audio_lens, sizeof(int32_t) * Bm);
+    const size_t need = Bm * (size_t)(M / QASR_MEL_TILE) * r.n_mels * 2 * sizeof(double);   // k_mel's per-tile statistics
+    if (ok && dev_alloc(e, (void**)&e->norm_stats, need) == hipSuccess) e->norm_stats_bytes = need;
+    else ok = false;
+  }
+  take(&r.feats, sizeof(float) * Bm * std::max(r.n_mels, (int)e->h.feat_in) * M);
+  take(&r.feat_lens, sizeof(int32_t) * Bm);
+  take(&r.tokens, sizeof(int32_t) * rows);
+  take(&r.lens_out, sizeof(int32_t) * Bm);
+  if (r.want_logp) take(&r.logp, sizeof(float) * rows * ncls);
+  r.ctc = qasr_ctc_out{};
+  if (r.decode) {
+    r.ctc.struct_size = (uint32_t)sizeof(qasr_ctc_out);
+    take(&r.fs, sizeof(float) * rows);
+    take(&r.ctc.labels, sizeof(int32_t) * rows);
+    take(&r.ctc.n_labels, sizeof(int32_t) * Bm);
+    take(&r.ctc.start, sizeof(int32_t) * rows);
+    take(&r.ctc.nframes, sizeof(int32_t) * rows);
+    take(&r.ctc.score, sizeof(float) * rows);
+    take(&r.ctc.utt_score, sizeof(float) * Bm);
+  }
+  if (!ok || hipDeviceSynchronize() != hipSuccess) {
+    for (void* p : r.owned) dev_free(e, p);
+    r = qasr_engine::Reserved{};
+    free_plan(e);
+    return fail(QASR_ERR_HIP, "reserve: allocation for %d x %d frames failed", o.max_batch, M);
+  }
+  r.buckets.reserve((size_t)max_graphs);
+  r.on = true;
+  return QASR_OK;
+}
+
+// one ragged forward: fe == nullptr: `src` = features [B][feat_in][X]; else audio [B][X] samples
+static int ragged_impl(qasr_engine* e, hipStream_t s, const FrontArgs* fe, const float* src, const int32_t* lens, int B, int X,
+                       qasr_ragged_out* out) {
+  const char* who = fe ? "forward_ragged_audio" : "forward_ragged";
+  if (!e || !src || !lens || !out || B <= 0 || X <= 0) return fail(QASR_ERR_ARG, "%s: bad arguments", who);
+  if (out->struct_size != sizeof(qasr_ragged_out)) return fail(QASR_ERR_ARG, "%s: qasr_ragged_out.struct_size %u is not %zu", who, out->struct_size, sizeof(qasr_ragged_out));
+  auto& r = e->rs;
+  if (!r.on) return fail(QASR_ERR_ARG, "%s: call qasr_engine_reserve first", who);
+  if (B > r.max_batch) return fail(QASR_ERR_ARG, "%s: batch %d is outside the reserved envelope (max_batch %d)", who, B, r.max_batch);
+  if (fe) {
+    if (!r.audio) return fail(QASR_ERR_ARG, "%s: the engine was reserved without max_samples", who);
+    if (X > r.max_samples) return fail(QASR_ERR_ARG, "%s: %d samples are outside the reserved envelope (max_samples %d)", who, X, r.max_samples);
+    if (X <= 256) return fail(QASR_ERR_ARG, "%s: %d samples (the front-end needs more than 256)", who, X);
+    if (fe->n_mels != r.n_mels || fe->pad_to != r.pad_to)
+      return fail(QASR_ERR_ARG, "%s: n_mels %d / pad_to %d differ from the reservation (%d / %d)", who, fe->n_mels, fe->pad_to, r.n_mels, r.pad_to);
+  }
+  const int T = fe ? qasr_frontend_frames(X, r.pad_to) : X;
+  if (T > r.max_frames) return fail(QASR_ERR_ARG, "%s: %d frames are outside the reserved envelope (max_frames %d)", who, T, r.max_frames);
+  const auto& h = e->h;
+  RaggedStageP sp{};
+  sp.shape[QASR_SHAPE_B] = B;
+  sp.shape[QASR_SHAPE_S] = fe ? X : 0;
+  sp.shape[QASR_SHAPE_NF] = fe ? 1 + X / 160 : T;
+  sp.shape[QASR_SHAPE_DOM] = T;
+  for (uint32_t d = 1; d < h.n_domains; ++d)
+    sp.shape[QASR_SHAPE_DOM + d] = conv_out_len(sp.shape[QASR_SHAPE_DOM + e->doms[d].parent], e->doms[d]);
+  for (uint32_t d = 0; d < h.n_domains; ++d)
+    if (sp.shape[QASR_SHAPE_DOM + d] <= 0) return fail(QASR_ERR_ARG, "input of %d frames is too short for domain %u", T, d);
+  const int Tb = ragged_bucket(r.max_frames, r.max_graphs, T);
+  if (Tb < T) return fail(QASR_ERR_ARG, "%s: no bucket for %d frames", who, T);
+  qasr_engine::Bucket* bk = nullptr;
+  for (auto& q : r.buckets)
+    if (q.frames == Tb) bk = &q;
+  if (!bk) {
+    r.buckets.emplace_back();
+    bk = &r.buckets.back();
+    bk->frames = Tb;
+  }
+  HIPCHK(hipSetDevice(e->device));
+  if (e->T0 != Tb || e->B != r.max_batch) {                  // launch parameters of the bucket: host arithmetic only
+    int rc = plan_shape(e, r.max_batch, Tb);
+    if (rc) return rc;
+  }
+  const int ls = logsoftmax_op(e);
+  const TensorRT& tl = e->tens[e->ops[ls].in];
+  e->tens[0].ptr = (void*)r.feats;
+  e->cur_lens = r.feat_lens;
+  e->stem = e->fuse_stem && stem_shape(e);
+  const bool norm_in_stem = fe && e->stem && e->fuse_norm && fe->n_mels == (int)h.feat_in;
+  e->norm_tiles = e->norm_frames = 0;
+  e->fe_launches = fe ? (norm_in_stem ? 1 : 2) : 0;
+  if (norm_in_stem) {                                        // the grid covers the bucket; tiles beyond the batch's frames hold zeros
+    e->norm_frames = Tb;
+    e->norm_tiles = Tb / QASR_MEL_TILE;
+  }
+  // ---- the one eager launch: input + lengths into staging, shape block
+  sp.src = src;
+  sp.lens_in = lens;
+  sp.shp = r.shp;
+  sp.B = B;
+  sp.max_batch = r.max_batch;
+  if (fe) {
+    sp.dst = r.audio, sp.lens_out = r.audio_lens;
+    sp.row = X, sp.src_pitch = X, sp.dst_pitch = r.spitch, sp.n_rows = 1;
+  } else {
+    sp.dst = r.feats, sp.lens_out = r.feat_lens;
+    sp.row = T, sp.src_pitch = T, sp.dst_pitch = Tb, sp.n_rows = (int)h.feat_in;
+  }
+  {
+    int rc = launch_ragged_stage(s, sp);
+    if (rc) return fail(rc, "%s: k_ragged_stage launch", who);
+  }
+  // ---- everything else runs on the engine's own buffers: the bucket's graph
+  RaggedFront rg{r.spitch, Tb, r.shp};
+  FrontArgs f2{};
+  if (fe) {
+    f2 = *fe;
+    f2.audio = r.audio, f2.audio_lens = r.audio_lens, f2.S = X, f2.rg = &rg;
+  }
+  struct CtcSwap {                                           // the reservation's own CTC outputs for the duration of the call
+    qasr_engine* e;
+    float* fs; qasr_ctc_out out; bool on; int use_lens;
+    ~CtcSwap() { e->ctc_fs = fs, e->ctc_out = out, e->ctc_on = on, e->ctc_use_lens = use_lens, e->ctc_t_act = nullptr; }
+  } swap{e, e->ctc_fs, e->ctc_out, e->ctc_on, e->ctc_use_lens};
+  e->ctc_fs = r.decode ? r.fs : nullptr;
+  e->ctc_out = r.ctc;
+  e->ctc_on = r.decode;
+  e->ctc_use_lens = r.decode ? r.decode_use_lens : 0;
+  e->ctc_t_act = r.shp + QASR_SHAPE_DOM + tl.d.domain;
+  auto enqueue = [&]() -> int {
+    return enqueue_forward(e, s, fe ? &f2 : nullptr, norm_in_stem, r.feats, r.feat_lens, r.logp, r.tokens, r.lens_out);
+  };
+  out->out_frames = sp.shape[QASR_SHAPE_DOM + tl.d.domain];
+  out->bucket_frames = Tb;
+  out->row_pitch = tl.T;
+  out->n_classes = (int)e->ops[ls].cin;
+  out->tokens = r.tokens, out->lens_out = r.lens_out, out->logp = r.logp, out->frame_score = r.fs, out->ctc = r.ctc;
+  out->feats = r.feats, out->feat_lens = r.feat_lens;
+  e->forwarded = true;
+  uint64_t key[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+  if (fe) {
+    uint32_t pre_bits;
+    memcpy(&pre_bits, &fe->preemph, 4);
+    key[0] = 1, key[1] = (uint64_t)(uintptr_t)fe->fb, key[2] = (uint64_t)(uintptr_t)fe->window, key[3] = (uint64_t)(uintptr_t)fe->plan;
+    key[4] = pre_bits, key[5] = (uint64_t)fe->plan_bytes;
+  }
+  if (memcmp(key, bk->key, sizeof key)) {                    // another entry / filterbank: this bucket starts over
+    if (bk->gexec) (void)hipGraphExecDestroy(bk->gexec);
+    bk->gexec = nullptr;
+    bk->calls = 0;
+    memcpy(bk->key, key, sizeof key);
+  }
+  const uint64_t seen = bk->calls++;
+  if (bk->gexec) {
+    HIPCHK(hipGraphLaunch(bk->gexec, s));
+    r.replays++;
+    return QASR_OK;
+  }
+  if (seen >= 1 && s != nullptr) {                           // second visit: capture (the first ran every kernel's one-time setup)
+    if (g_prof) return fail(QASR_ERR_ARG, "graph capture while qasr_debug_prof / qasr_debug_timeline is set: the buffer would be baked into the graph");
+    hipGraph_t g = nullptr;
+    HIPCHK(hipStreamBeginCapture(s, hipStreamCaptureModeThreadLocal));
+    int rc = enqueue();
+    hipError_t ce = hipStreamEndCapture(s, &g);
+    if (rc) {
+      if (g) (void)hipGraphDestroy(g);
+      bk->calls = 0;
+      return rc;
+    }
+    if (ce != hipSuccess || !g) return fail(QASR_ERR_HIP, "hipStreamEndCapture failed: %s", hipGetErrorString(ce));
+    hipError_t ie = hipGraphInstantiate(&bk->gexec, g, nullptr, nullptr, 0);
+    (void)hipGraphDestroy(g);
+    if (ie != hipSuccess) {
+      bk->gexec = nullptr;
+      return fail(QASR_ERR_HIP, "hipGraphInstantiate failed: %s", hipGetErrorString(ie));
+    }
+    r.captured++;
+    HIPCHK(hipGraphLaunch(bk->gexec, s));
+    r.replays++;
+    return QASR_OK;
+  }
+  int rc = enqueue();
+  if (rc) return rc;
+  r.eager++;
+  HIPCHK(hipGetLastError());
+  return QASR_OK;
+}
+
+int qasr_engine_forward_ragged(qasr_engine* e, void* stream, const float* feats, const int32_t* lens, int B, int T,
+                               qasr_ragged_out* out) {
+  return ragged_impl(e, (hipStream_t)stream, nullptr, feats, lens, B, T, out);
+}
+
+int qasr_engine_forward_ragged_audio(qasr_engine* e, void* stream, const float* audio, const int32_t* audio_lens, int B, int S,
+                                     const float* fb, const float* window, int n_mels, float preemph, int pad_to,
+                                     const void* frontend_plan, size_t plan_bytes, qasr_ragged_out* out) {
+  if (!fb || !window || !frontend_plan) return fail(QASR_ERR_ARG, "forward_ragged_audio: bad arguments");
+  FrontArgs fe{audio, audio_lens, S, fb, window, n_mels, preemph, pad_to, frontend_plan, plan_bytes, nullptr};
+  return ragged_impl(e, (hipStream_t)stream, &fe, audio, audio_lens, B, S, out);
+}
+
+int qasr_engine_ragged_stats(const qasr_engine* e, qasr_ragged_stats* out) {
+  if (!e || !out) return fail(QASR_ERR_ARG, "ragged_stats: NULL argument");
+  if (out->struct_size != sizeof(qasr_ragged_stats)) return fail(QASR_ERR_ARG, "ragged_stats: qasr_ragged_stats.struct_size %u is not %zu", out->struct_size, sizeof(qasr_ragged_stats));
+  memset(out, 0, sizeof *out);
+  out->struct_size = (uint32_t)sizeof *out;
+  out->device_allocs = e->n_allocs;
+  out->device_frees = e->n_frees;
+  out->graphs_captured = e->rs.captured;
+  out->graph_replays = e->rs.replays;
+  out->eager_runs = e->rs.eager;
+  for (const auto& b : e->rs.buckets) {
+    if (out->n_buckets >= 64) break;
+    out->bucket_frames[out->n_buckets] = b.frames;
+    out->bucket_calls[out->n_buckets] = b.calls;
+    out->n_buckets++;
+  }
+  return QASR_OK;
 }
 
 // Replays every op `reps` times back to back between ONE pair of HIP events on `stream` and returns the
@@ -1198,7 +1561,8 @@ int qasr_sep_layer(void* stream, const qasr_sep_layer_args* a, char* label, size
   p.pw_unsigned = a->K > 0 ? 0 : a->x_unsigned;
   p.dilation = a->K > 0 ? a->dilation : 1;
   p.tile = a->tile;
-  p.gen = a->gen;
+  p.gen = a->gen == 3 ? 2 : a->gen;
+  p.mask_skip = a->gen == 3;
   p.w = a->w;
   p.bias = a->bias;
   p.cin = a->cin;

@@ -144,13 +144,17 @@ __device__ __forceinline__ int zpad(int u) { return u + (u >> 2); }
 // frequency: 4 stages, one butterfly per lane and stage — the first straight from the framing registers, the last
 // without twiddles and stored in natural order) followed by the usual even/odd split
 // X[k] = E[k] + e^{-2 pi i k/512} O[k],  k = 0..256.
+// RAGGED (reserved engines, qasr_ragged.hip): S / the frame count / the row count come from the shape block, rows are `pitch`
+// samples apart.  A separate instantiation: k_mel sits at its 128-VGPR limit and the extra branch moves the code of the
+// ordinary path (measured on the fixed-shape step), so RAGGED = false is the kernel as it was.
+template <bool RAGGED>
 __global__ void __launch_bounds__(256, 4) k_mel(const float* __restrict__ audio, int B, int S, const float* __restrict__ fb,
                                              const float* __restrict__ window, const int* __restrict__ hdr,
                                              const int* __restrict__ ranges, const int* __restrict__ goffs,
                                              const float* __restrict__ table, const double2* __restrict__ twg, int n_mels,
                                              float preemph, int n_frames, int T_pad, float* __restrict__ out,
                                              const int32_t* __restrict__ audio_lens, double* __restrict__ stats,
-                                             int32_t* __restrict__ feat_lens) {
+                                             int32_t* __restrict__ feat_lens, int pitch, const int32_t* __restrict__ shp) {
   __shared__ double2 zb[4][MEL_ZLEN];      // per wave: complex work buffer (padded, zpad)
   __shared__ float pw[4][NBIN + 3];        // per wave: power spectrum, [257..259] = 0
   __shared__ __attribute__((aligned(8))) float ys[MEL_NS];   // pre-emphasised signal under the windows, [0] <-> signal index 160 t0 - 160
@@ -163,7 +167,23 @@ __global__ void __launch_bounds__(256, 4) k_mel(const float* __restrict__ audio,
   static_assert(sizeof(float) * 64 * (MEL_FR + 1) <= sizeof(zb), "ob aliases zb");
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int b = blockIdx.y, t0 = blockIdx.x * MEL_FR;
-  const float* x = audio + (size_t)b * S;
+  // reserved engines (qasr_ragged.hip): the grid is the bucket's, the batch's own sample count - reflect padding and the
+  // frame count follow it - and its row count come from the shape block; a work-group beyond either leaves zero statistics
+  if constexpr (RAGGED) {
+    S = shp[1];
+    n_frames = shp[2];
+    if (b >= shp[0] || t0 >= n_frames) {
+      if (stats)
+        for (int m = threadIdx.x; m < n_mels; m += 256) {
+          double* st = stats + (((size_t)b * gridDim.x + blockIdx.x) * n_mels + m) * 2;
+          st[0] = 0.0;
+          st[1] = 0.0;
+        }
+      if (feat_lens && blockIdx.x == 0 && threadIdx.x == 0) feat_lens[b] = (audio_lens[b] + HOP - 1) / HOP;
+      return;
+    }
+  }
+  const float* x = audio + (size_t)b * (RAGGED ? pitch : S);
   // ---- staging: every global load of the work-group leaves before the first use ----
   const bool fb_lds = hdr[2] <= MEL_FBMAX;                   // (plan: n_mels <= MEL_MAXM and the table fits)
   float yv[MEL_NQ], ym[MEL_NQ];
@@ -324,8 +344,10 @@ __global__ void __launch_bounds__(256, 4) k_mel(const float* __restrict__ audio,
 
 #define NORM_NV 16
 __global__ void __launch_bounds__(64) k_norm(float* __restrict__ feats, const int32_t* __restrict__ audio_lens, int n_mels,
-                                             int n_frames, int T_pad, int32_t* __restrict__ feat_lens) {
+                                             int n_frames, int T_pad, int32_t* __restrict__ feat_lens,
+                                             const int32_t* __restrict__ shp) {
   const int row = blockIdx.x, lane = threadIdx.x;
+  if (shp) n_frames = shp[2];                          // reserved engines: the batch's own frame count
   const int b = row / n_mels;
   const int alen = audio_lens[b];
   const int seq = (alen + HOP - 1) / HOP;              // get_seq_len: ceil(len / hop) (features.py:327-328)
@@ -405,28 +427,43 @@ int qasr_frontend_plan(void* stream, const float* fb, int n_mels, void* workspac
   return hipGetLastError() == hipSuccess ? QASR_OK : QASR_ERR_HIP;
 }
 
-int qasr_frontend_mel_planned(void* stream, const float* audio, const int32_t* audio_lens, int B, int S, const float* fb,
-                              const float* window, int n_mels, float preemph, int pad_to, float* feats,
-                              int32_t* feat_lens, const void* workspace, size_t workspace_bytes) {
+// rg (reserved engines): rows of `audio` are rg->pitch samples apart, `feats` rows rg->T_pad frames, the grid covers
+// rg->T_pad frames and S / the frame count are read from the shape block rg->shp on the device
+static int mel_planned_impl(void* stream, const float* audio, const int32_t* audio_lens, int B, int S, const float* fb,
+                            const float* window, int n_mels, float preemph, int pad_to, float* feats, int32_t* feat_lens,
+                            const void* workspace, size_t workspace_bytes, const qasr::RaggedFront* rg) {
   if (!audio || !audio_lens || !fb || !window || !feats || !feat_lens || B <= 0 || S <= NFFT / 2 || n_mels <= 0 ||
       !workspace || workspace_bytes < qasr_frontend_workspace_bytes(B, S, n_mels) || ((size_t)workspace & 15))
     return QASR_ERR_ARG;
-  const int n_frames = 1 + S / HOP;
-  const int T_pad = qasr_frontend_frames(S, pad_to);
+  const int n_frames = rg ? rg->T_pad : 1 + S / HOP;
+  const int T_pad = rg ? rg->T_pad : qasr_frontend_frames(S, pad_to);
   hipStream_t s = (hipStream_t)stream;
   const char* ws = (const char*)workspace;
-  hipLaunchKernelGGL(qasr::k_mel, dim3((n_frames + MEL_FR - 1) / MEL_FR, B), dim3(256), 0, s, audio, B, S, fb, window,
-                     (const int*)ws, (const int*)(ws + ws_ranges(n_mels)), (const int*)(ws + ws_offs(n_mels)),
+  hipLaunchKernelGGL(rg ? qasr::k_mel<true> : qasr::k_mel<false>, dim3((n_frames + MEL_FR - 1) / MEL_FR, B), dim3(256), 0, s, audio,
+                     B, S, fb, window, (const int*)ws, (const int*)(ws + ws_ranges(n_mels)), (const int*)(ws + ws_offs(n_mels)),
                      (const float*)(ws + ws_table(n_mels)), (const double2*)(ws + ws_tw(n_mels)), n_mels, preemph, n_frames,
-                     T_pad, feats, nullptr, nullptr, nullptr);
+                     T_pad, feats, (const int32_t*)nullptr, (double*)nullptr, (int32_t*)nullptr, rg ? rg->pitch : S,
+                     rg ? rg->shp : (const int32_t*)nullptr);
   hipLaunchKernelGGL(qasr::k_norm, dim3(B * n_mels), dim3(64), 0, s, feats, audio_lens, n_mels, n_frames, T_pad,
-                     feat_lens);
+                     feat_lens, rg ? rg->shp : nullptr);
   return hipGetLastError() == hipSuccess ? QASR_OK : QASR_ERR_HIP;
+}
+int qasr_frontend_mel_planned(void* stream, const float* audio, const int32_t* audio_lens, int B, int S, const float* fb,
+                              const float* window, int n_mels, float preemph, int pad_to, float* feats,
+                              int32_t* feat_lens, const void* workspace, size_t workspace_bytes) {
+  return mel_planned_impl(stream, audio, audio_lens, B, S, fb, window, n_mels, preemph, pad_to, feats, feat_lens, workspace,
+                          workspace_bytes, nullptr);
 }
 
 }  // extern "C"
 
 namespace qasr {
+int frontend_mel_planned_ragged(hipStream_t s, const float* audio, const int32_t* audio_lens, int B, int S, const float* fb,
+                                const float* window, int n_mels, float preemph, int pad_to, float* feats, int32_t* feat_lens,
+                                const void* workspace, size_t workspace_bytes, const RaggedFront& rg) {
+  return mel_planned_impl((void*)s, audio, audio_lens, B, S, fb, window, n_mels, preemph, pad_to, feats, feat_lens, workspace,
+                          workspace_bytes, &rg);
+}
 size_t frontend_stats_bytes(int B, int S, int n_mels) {
   const int n_frames = 1 + S / HOP;
   return (size_t)B * ((n_frames + MEL_FR - 1) / MEL_FR) * n_mels * 2 * sizeof(double);
@@ -435,18 +472,19 @@ size_t frontend_stats_bytes(int B, int S, int n_mels) {
 // statistics k_stem combines into normalize_batch's mean / std (the engine's forward_audio with the fused stem)
 int frontend_mel_stats(hipStream_t s, const float* audio, const int32_t* audio_lens, int B, int S, const float* fb,
                        const float* window, int n_mels, float preemph, int pad_to, float* feats, int32_t* feat_lens,
-                       const void* workspace, size_t workspace_bytes, double* stats, int* n_tiles, int* n_frames_out) {
+                       const void* workspace, size_t workspace_bytes, double* stats, int* n_tiles, int* n_frames_out,
+                       const RaggedFront* rg) {
   if (!audio || !audio_lens || !fb || !window || !feats || !feat_lens || !stats || B <= 0 || S <= NFFT / 2 || n_mels <= 0 ||
       !workspace || workspace_bytes < qasr_frontend_workspace_bytes(B, S, n_mels) || ((size_t)workspace & 15))
     return QASR_ERR_ARG;
-  const int n_frames = 1 + S / HOP;
-  const int T_pad = qasr_frontend_frames(S, pad_to);
+  const int n_frames = rg ? rg->T_pad : 1 + S / HOP;
+  const int T_pad = rg ? rg->T_pad : qasr_frontend_frames(S, pad_to);
   const char* ws = (const char*)workspace;
   const int nt = (n_frames + MEL_FR - 1) / MEL_FR;
-  hipLaunchKernelGGL(k_mel, dim3(nt, B), dim3(256), 0, s, audio, B, S, fb, window, (const int*)ws,
+  hipLaunchKernelGGL(rg ? k_mel<true> : k_mel<false>, dim3(nt, B), dim3(256), 0, s, audio, B, S, fb, window, (const int*)ws,
                      (const int*)(ws + ws_ranges(n_mels)), (const int*)(ws + ws_offs(n_mels)),
                      (const float*)(ws + ws_table(n_mels)), (const double2*)(ws + ws_tw(n_mels)), n_mels, preemph, n_frames,
-                     T_pad, feats, audio_lens, stats, feat_lens);
+                     T_pad, feats, audio_lens, stats, feat_lens, rg ? rg->pitch : S, rg ? rg->shp : (const int32_t*)nullptr);
   *n_tiles = nt;
   *n_frames_out = n_frames;
   return hipGetLastError() == hipSuccess ? QASR_OK : QASR_ERR_HIP;

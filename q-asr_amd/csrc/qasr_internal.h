@@ -80,6 +80,7 @@ struct SepP {             // fused separable layer: depthwise stencil -> QuantAc
   int prof_mode;          // 1 (qasr_debug_timeline): every work-group writes {start, end (s_memrealtime, 100 MHz), HW_ID | XCC_ID << 32, shader cycles}
   int prof_cap;           // ... for work-groups below this count (the caller's buffer)
   int etile;              // the engine's tile_frames option (32: built for one step in flight; 64 / 128: several), before per-op adjustments
+  int mask_skip;          // k_sep2: route to the k_sep2s instantiations (mask-skip rule; reserved engines, qasr_engine_opts.mask_skip)
   PaneP panes[QASR_MAX_PANES];
   EpiP e;
 };
@@ -130,9 +131,19 @@ int launch_stem(hipStream_t s, const QuantInP& qi, const DwP& dw, const SepP& pw
 // qasr_frontend.hip: k_mel alone (un-normalised log-mel, feat_lens, per-tile statistics [B][tiles][n_mels][2] f64)
 #define QASR_MEL_TILE 16
 size_t frontend_stats_bytes(int B, int S, int n_mels);
+// front-end of a reserved engine's bucket (qasr_ragged.hip): engine-owned staging rows `pitch` samples apart, feature rows
+// of T_pad frames (the bucket edge), and the batch's own S / frame count in the device-resident shape block
+struct RaggedFront {
+  int pitch, T_pad;
+  const int32_t* shp;
+};
 int frontend_mel_stats(hipStream_t s, const float* audio, const int32_t* audio_lens, int B, int S, const float* fb,
                        const float* window, int n_mels, float preemph, int pad_to, float* feats, int32_t* feat_lens,
-                       const void* workspace, size_t workspace_bytes, double* stats, int* n_tiles, int* n_frames);
+                       const void* workspace, size_t workspace_bytes, double* stats, int* n_tiles, int* n_frames,
+                       const RaggedFront* rg = nullptr);
+int frontend_mel_planned_ragged(hipStream_t s, const float* audio, const int32_t* audio_lens, int B, int S, const float* fb,
+                                const float* window, int n_mels, float preemph, int pad_to, float* feats, int32_t* feat_lens,
+                                const void* workspace, size_t workspace_bytes, const RaggedFront& rg);
 // qasr_decoder.hip: the decoder's 1x1 conv + log_softmax + argmax (+ the encoded lengths) as one launch
 bool decoder_fusable(const SepP& p);
 int launch_decoder(hipStream_t s, const SepP& p, float* logp, int32_t* tokens, int32_t* lens_out, bool keep_logits,
@@ -145,8 +156,29 @@ size_t decoder_wide_ws_bytes(int B, int Tp);
 int launch_decoder_wide(hipStream_t s, const SepP& p, float* logp, int32_t* tokens, int32_t* lens_out, bool keep_logits,
                         void* ws, size_t ws_bytes, float* frame_score = nullptr);
 // qasr_ctc.hip: greedy CTC collapse of a token matrix (k_ctc), one work-group per utterance
+// t_act (reserved engines, device): the batch's own frame count; rows keep the pitch T
 int launch_ctc(hipStream_t s, const int32_t* tokens, const float* frame_score, const int32_t* lens, int B, int T, int blank,
-               const qasr_ctc_out& out);
+               const qasr_ctc_out& out, const int32_t* t_act = nullptr);
+// qasr_ragged.hip: the bucket policy of reserved engines and their one eager launch per call (k_ragged_stage)
+#define QASR_RAGGED_TILE 128          /* every bucket edge is a multiple of the largest frame tile */
+#define QASR_SHAPE_B 0                /* shape block, i32: rows of the batch, */
+#define QASR_SHAPE_S 1                /* its padded sample count (0: feature entry), */
+#define QASR_SHAPE_NF 2               /* STFT frames 1 + S / hop, */
+#define QASR_SHAPE_DOM 4              /* and from here its frame count per time domain */
+#define QASR_SHAPE_MAXDOM 12
+#define QASR_SHAPE_WORDS (QASR_SHAPE_DOM + QASR_SHAPE_MAXDOM)
+int ragged_bucket(int max_frames, int max_graphs, int T);
+struct RaggedStageP {
+  const float* src;         // the caller's [B][row] floats (audio: row = S; features: row = n_mels x T as n_rows rows of T)
+  float* dst;               // staging
+  const int32_t* lens_in;   // [B]
+  int32_t* lens_out;        // [max_batch]: rows >= B get 0
+  int32_t* shp;             // shape block
+  int B, max_batch;
+  int row, src_pitch, dst_pitch, n_rows;   // floats per row; n_rows rows per utterance (1 / n_mels)
+  int shape[QASR_SHAPE_WORDS];
+};
+int launch_ragged_stage(hipStream_t s, const RaggedStageP& p);
 void launch_lens(hipStream_t s, const int32_t* lens_in, int32_t* lens_all, const qasr_domain_desc* doms,
                  int n_domains, int B);
 

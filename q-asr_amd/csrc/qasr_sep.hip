@@ -19,6 +19,9 @@ extern template int launch_sep2_inst<64, false>(hipStream_t, const SepP&);
 extern template int launch_sep2_inst<64, true>(hipStream_t, const SepP&);
 extern template int launch_sep2_inst<128, false>(hipStream_t, const SepP&);
 extern template int launch_sep2_inst<128, true>(hipStream_t, const SepP&);
+extern template int launch_sep2_inst<32, false, true>(hipStream_t, const SepP&);
+extern template int launch_sep2_inst<64, false, true>(hipStream_t, const SepP&);
+extern template int launch_sep2_inst<128, false, true>(hipStream_t, const SepP&);
 
 // k_sep2 takes the stride-1 separable layers it is built for (sep2_shape_ok) unless the engine was told to stay on k_sep
 bool sep2_takes(const SepP& p) { return p.gen == 2 && sep2_shape_ok(p); }
@@ -48,6 +51,10 @@ void sep_kernel_label(const SepP& p, char* buf, size_t cap) {
     return;
   }
   if (sep2_takes(p)) {
+    if (p.mask_skip && !dbg)                                // the same kernels with the mask-skip rule
+      snprintf(buf, cap, "k_sep2s<%d, %d, %d, %d, %d, %d>", p.K, p.cin_pad >> 7, (p.e.flags & QASR_F_RESADD) ? p.panes[0].cin_pad >> 7 : 0,
+               (p.e.cout + 255) / 256, sep2_tile(p), p.K > 0 ? p.dilation : 1);
+    else
     snprintf(buf, cap, "k_sep2<%d, %d, %d, %d, %s, %d, %d>", p.K, p.cin_pad >> 7,
              (p.e.flags & QASR_F_RESADD) ? p.panes[0].cin_pad >> 7 : 0, (p.e.cout + 255) / 256, dbg ? "true" : "false", sep2_tile(p),
              p.K > 0 ? p.dilation : 1);
@@ -70,6 +77,8 @@ int launch_sep(hipStream_t s, const SepP& p) {
   if (dense2_takes(p)) return launch_dense2(s, p);           // Jasper's plain dense convs (qasr_dense2.hip)
   if (sep2_takes(p)) {
     const int tt = sep2_tile(p);
+    if (p.mask_skip && !dbg)
+      return tt == 128 ? launch_sep2_inst<128, false, true>(s, p) : tt == 64 ? launch_sep2_inst<64, false, true>(s, p) : launch_sep2_inst<32, false, true>(s, p);
     if (tt == 128) return dbg ? launch_sep2_inst<128, true>(s, p) : launch_sep2_inst<128, false>(s, p);
     if (tt == 64) return dbg ? launch_sep2_inst<64, true>(s, p) : launch_sep2_inst<64, false>(s, p);
     return dbg ? launch_sep2_inst<32, true>(s, p) : launch_sep2_inst<32, false>(s, p);

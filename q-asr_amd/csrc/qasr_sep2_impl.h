@@ -264,7 +264,10 @@ struct Sep2PassP {
 // samples with the same taps: a depthwise group is 8 real channels x 2 parities per wave (16 MFMA blocks as ever), the
 // geometry is Sep2Geo<K, TT / 2>, and the requantised values go to the [channel][frame] image byte by byte (a lane's four
 // values are frames of one parity, two apart).  Everything behind the depthwise stage is unchanged.
-template <int K, int NG, int NGP, int NP, bool DBG, int TT, int DIL = 1>
+// SKIP (k_sep2s, reserved engines / qasr_engine_opts.mask_skip): the mask-skip rule of DESIGN 5.3e.  It is a separate set of
+// instantiations because the branch alone - never taken at full length - costs k_sep2 0.14 - 0.28 us per launch (the code the
+// compiler emits for the main path moves); SKIP = false is the kernel as it was.
+template <int K, int NG, int NGP, int NP, bool DBG, int TT, int DIL = 1, bool SKIP = false>
 __device__ __forceinline__ void sep2_body(const SepP& p, const int b, const int t0, const bool stamp_wg, const int wg_id) {
   using G = Sep2Geo<K, TT / DIL>;
   constexpr bool RES = NGP > 0;
@@ -461,6 +464,16 @@ __device__ __forceinline__ void sep2_body(const SepP& p, const int b, const int 
   // shifted tap stream), B[k][j] = win[S j + D + m0 + k] (lane j's window run), so the block accumulates
   // out[S j + 4 u + i] over taps m0 - i .. m0 - i + 3 for chain u when B is taken 4 u bytes further on; m0 advances
   // by 4 per step.  Lane l: channel l >> 2, row / column l & 3; register v of chain u = frame S (l & 3) + 4 u + v.
+  // mask-skip (work-group uniform): every frame of this tile is masked - store the zero codes the epilogue would store and
+  // leave.  Taken where the full path first needs lens[b], behind the first group's requests (a skipped work-group wastes
+  // those; addresses are clamped, always in bounds); diagnostics stamp every work-group: they take the full path
+  if constexpr (SKIP && !DBG) {
+    asm volatile("" ::: "memory");                           // the requests above stay above
+    if ((flags & QASR_F_MASK_OUT) && t0 >= lim && !p.prof) {
+      store_masked_tile<SEP2_NT>(e, b, t0, TT, 0, ecout, tid);
+      return;
+    }
+  }
   const bool full_in = t0 + TT <= dlim;                      // no masked frame in this tile (uniform)
   constexpr int e0base = 8 + G::MS;                          // the lane's tap stream starts at byte e0base - jl of its row
   const int e0 = e0base - jl, tq = e0 >> 2, tsh = e0 & 3;
@@ -938,6 +951,12 @@ __global__ void __launch_bounds__(SEP2_NT, SEP2_WPE) k_sep2(SepP p) {
   sep2_body<K, NG, NGP, NP, DBG, TT, DIL>(p, blockIdx.x, blockIdx.y * TT, blockIdx.x == 0 && blockIdx.y == 1,
                                           blockIdx.y * gridDim.x + blockIdx.x);
 }
+// the same with the mask-skip rule (production instantiations only; qasr_sep2s_t{32,64,128}.hip)
+template <int K, int NG, int NGP, int NP, int TT, int DIL = 1>
+__global__ void __launch_bounds__(SEP2_NT, SEP2_WPE) k_sep2s(SepP p) {
+  sep2_body<K, NG, NGP, NP, false, TT, DIL, true>(p, blockIdx.x, blockIdx.y * TT, blockIdx.x == 0 && blockIdx.y == 1,
+                                                  blockIdx.y * gridDim.x + blockIdx.x);
+}
 
 template <int K, int TT, int DIL = 1>
 static inline size_t sep2_smem_bytes(const SepP& p) {
@@ -980,7 +999,7 @@ static inline bool sep2_shape_ok(const SepP& p) {
   return false;
 }
 
-template <int K, int NG, int NGP, int NP, bool DBG, int TT, int DIL = 1>
+template <int K, int NG, int NGP, int NP, bool DBG, int TT, int DIL = 1, bool SKIP = false>
 static int launch_sep2_v(hipStream_t s, const SepP& p) {
   const size_t smem = sep2_smem_bytes<K, TT, DIL>(p);
   if (smem > 160 * 1024 || p.e.B < 1 || p.e.Tp % TT || !p.x || !p.w || (K > 0 && !p.wdw2)) return QASR_ERR_ARG;
@@ -988,7 +1007,8 @@ static int launch_sep2_v(hipStream_t s, const SepP& p) {
   int dev = 0;
   (void)hipGetDevice(&dev);
   if (attr_dev != dev) {
-    (void)hipFuncSetAttribute((const void*)k_sep2<K, NG, NGP, NP, DBG, TT, DIL>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+    if constexpr (SKIP) (void)hipFuncSetAttribute((const void*)k_sep2s<K, NG, NGP, NP, TT, DIL>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+    else (void)hipFuncSetAttribute((const void*)k_sep2<K, NG, NGP, NP, DBG, TT, DIL>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
     attr_dev = dev;
   }
   SepP q = p;
@@ -996,23 +1016,24 @@ static int launch_sep2_v(hipStream_t s, const SepP& p) {
   static const int tune = getenv("QASR_SEP2_TUNE") ? atoi(getenv("QASR_SEP2_TUNE")) : 0;
   q.prof_mode = g_prof_mode | (tune << 8);
   q.prof_cap = g_prof_cap;
-  hipLaunchKernelGGL((k_sep2<K, NG, NGP, NP, DBG, TT, DIL>), dim3(p.e.B, p.e.Tp / TT, 1), dim3(SEP2_NT), smem, s, q);
+  if constexpr (SKIP) hipLaunchKernelGGL((k_sep2s<K, NG, NGP, NP, TT, DIL>), dim3(p.e.B, p.e.Tp / TT, 1), dim3(SEP2_NT), smem, s, q);
+  else hipLaunchKernelGGL((k_sep2<K, NG, NGP, NP, DBG, TT, DIL>), dim3(p.e.B, p.e.Tp / TT, 1), dim3(SEP2_NT), smem, s, q);
   return QASR_OK;
 }
 
 // all instantiations of one (tile, debug) pair; QASR_ERR_UNSUPPORTED for a shape without one
-template <int TT, bool DBG>
+template <int TT, bool DBG, bool SKIP = false>
 int launch_sep2_inst(hipStream_t s, const SepP& p) {
   const int ng = p.cin_pad >> 7, ngp = (p.e.flags & QASR_F_RESADD) ? (p.panes[0].cin_pad >> 7) : 0, np = (p.e.cout + 255) / 256;
   if (p.K > 0 && p.dilation == 2) {                          // block 16: the dilation-2 form (64- / 128-frame tiles)
     if constexpr (TT >= 64) {
-      if (p.K == 87 && ng == 4 && ngp == 0 && np == 2) return launch_sep2_v<87, 4, 0, 2, DBG, TT, 2>(s, p);
+      if (p.K == 87 && ng == 4 && ngp == 0 && np == 2) return launch_sep2_v<87, 4, 0, 2, DBG, TT, 2, SKIP>(s, p);
     }
     return QASR_ERR_UNSUPPORTED;
   }
 #define SEP2_LAUNCH(K_, NG_, NGP_, NP_)                                                  \
   if constexpr (TT <= 64 || K_ > 0) {   /* the bare 1x1 form spills at 128 frames */       \
-    if (p.K == K_ && ng == NG_ && ngp == NGP_ && np == NP_) return launch_sep2_v<K_, NG_, NGP_, NP_, DBG, TT>(s, p); \
+    if (p.K == K_ && ng == NG_ && ngp == NGP_ && np == NP_) return launch_sep2_v<K_, NG_, NGP_, NP_, DBG, TT, 1, SKIP>(s, p); \
   }
   SEP2_INSTANCES(SEP2_LAUNCH)
 #undef SEP2_LAUNCH

@@ -280,6 +280,14 @@ __global__ void __launch_bounds__(SEP_NT) k_sep(SepP p) {
   v4i wf[SEP_WK];
   if (!dense) sep_load_w(wf, p.w, p.cin_pad, in0 ? co_l : 0, 0);        // consumed after the depthwise stage, which hides it
   __builtin_amdgcn_sched_barrier(0);                         // keep the requests up here (the scheduler sinks them to first use)
+  // mask-skip (work-group uniform): every frame of this tile is masked - store the zero codes the epilogue
+  // would store and leave; taken behind the prefetch, so that the wait for lens[b] does not delay the full path's requests
+  if constexpr (!DBG) {
+    if ((flags & QASR_F_MASK_OUT) && !(flags & QASR_F_LOGITS) && t0 >= lim && !p.prof) {
+      store_masked_tile<SEP_NT>(e, b, t0, TT, 0, ecout, tid);
+      return;
+    }
+  }
 
   if (K > 0) {
     // ------------------------------------------------------------------ depthwise stage

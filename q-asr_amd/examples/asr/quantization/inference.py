@@ -54,6 +54,9 @@ def main():
     p.add_argument("--synthetic_model", action='store_true', help="(extension) random-init weights of --asr_model")
     p.add_argument("--dither", type=float, default=None, help="(extension) override the preprocessor's dither (0: reproducible runs)")
     p.add_argument("--dump_hyps", type=str, default=None, help="(extension) write hypotheses, references and WER as JSON")
+    p.add_argument("--reserve", type=float, default=None, metavar='SECONDS',
+                   help="(extension) reserve the engine once for batches of --batch_size utterances of at most SECONDS "
+                        "seconds: no allocation per batch, one captured graph per length bucket (EncDecCTCModel.reserve)")
     p.add_argument("--timestamps", action='store_true',
                    help="(extension) also decode every batch with EncDecCTCModel.decode: word times and confidences "
                         "(`words`, `utt_score` per utterance in the --dump_hyps JSON); hypotheses and WER are unchanged")
@@ -107,6 +110,8 @@ def main():
     print('Evaluating...')
     qm.evaluate(asr_model)
     qm.set_dynamic(asr_model, args.dynamic)
+    if args.reserve:
+        asr_model.reserve(args.batch_size, args.reserve)
     labels_map = dict(enumerate(asr_model.decoder.vocabulary))
     wer = WER(vocabulary=asr_model.decoder.vocabulary)
     hyps, refs, words, utt_scores = [], [], [], []
@@ -126,7 +131,7 @@ def main():
         audio_s += float(batch[1].sum()) / 16000.0
     torch.cuda.synchronize()
     wall = time.time() - t0
-    served = type(getattr(asr_model, '_engine', None)).__name__
+    served = type(getattr(asr_model, '_engine', None) or getattr(asr_model, '_ragged_engine', None)).__name__
     print('path:', {'Engine': 'static integer engine (HIP)', 'DynamicRunner': 'dynamic device path (HIP)'}.get(
         served, 'host modules'))
     wer_value = word_error_rate(hypotheses=hyps, references=refs)

@@ -49,6 +49,10 @@ class EncDecCTCModel(nn.Module):
         self._test_dl = None
         self._engine = None
         self._engine_key = None
+        self._reserve = None                 # (max_batch, max_seconds) after reserve()
+        self._ragged_engine = None           # the reserved engine of the current quantiser state / device
+        self._ragged_key = None
+        self._ragged_warned = False
         self._quant_version = 0
 
     # ------------------------------------------------------------------ construction / checkpoints
@@ -136,6 +140,9 @@ class EncDecCTCModel(nn.Module):
         if self._engine is not None:
             self._engine.close()
         self._engine = None
+        if getattr(self, '_ragged_engine', None) is not None:
+            self._ragged_engine.close()
+        self._ragged_engine = None
 
     # ------------------------------------------------------------------ data
     def setup_test_data(self, test_data_config):
@@ -286,6 +293,97 @@ class EncDecCTCModel(nn.Module):
             self._engine_key = key
         return self._engine
 
+    def reserve(self, max_batch, max_seconds):
+        """Ragged batches without allocation (an extension; qasr_engine_reserve): afterwards forward(), decode() and
+        transcribe() of the calibrated model run every batch of at most `max_batch` utterances of at most `max_seconds`
+        seconds through one reserved engine - buffers allocated once, one captured graph per length bucket - and return
+        what they return without it (the results are copies: they stay valid across batches).  A batch outside the
+        envelope takes the ordinary path, with one warning.  The engine is built on the first batch; reserve(None, None)
+        drops the reservation."""
+        if self._ragged_engine is not None:
+            self._ragged_engine.close()
+        self._ragged_engine = None
+        self._ragged_warned = False
+        if not max_batch or not max_seconds:
+            self._reserve = None
+            return self
+        if int(max_batch) < 1 or float(max_seconds) <= 0:
+            raise ValueError('reserve: max_batch >= 1 and max_seconds > 0')
+        self._reserve = (int(max_batch), float(max_seconds))
+        return self
+
+    def _get_ragged_engine(self, device):
+        """the reserved engine for the live weights on `device` (None: the front-end is not the HIP kernels' configuration)"""
+        if not self._frontend_hip_supported():
+            return None
+        f = self.preprocessor.featurizer
+        pad_to = int(f.pad_to) if 0 < int(f.pad_to) and 128 % int(f.pad_to) == 0 else 16
+        key = (self._quant_version, device.index or 0, self._reserve, pad_to)
+        if self._ragged_engine is None or self._ragged_key != key:
+            from qasr import engine as qengine, pack, ragged
+            qengine.load_library()
+            if self._ragged_engine is not None:
+                self._ragged_engine.close()
+            blob, self._pack_meta = pack.pack_model(*self.export_pack_inputs())
+            max_batch, max_seconds = self._reserve
+            max_samples = int(round(max_seconds * self.preprocessor._sample_rate))
+            eng = qengine.Engine(blob, device.index or 0)
+            # both entries share the envelope: audio (pad_to > 0) and features (transcribe() runs with pad_to 0)
+            eng.reserve(max_batch, max_samples=max_samples, max_frames=ragged.frontend_frames(max_samples, pad_to),
+                        want_logp=True, decode=True, n_mels=int(f.fb.shape[1]), pad_to=pad_to)
+            self._ragged_engine, self._ragged_key = eng, key
+        return self._ragged_engine
+
+    def _ragged_forward(self, has_in, input_signal, input_signal_length, processed_signal, processed_signal_length, decode):
+        """forward / decode of one batch on the reserved engine; None when the batch lies outside the envelope"""
+        import dataclasses
+        from qasr import ragged
+        ref = input_signal if has_in else processed_signal
+        eng = self._get_ragged_engine(ref.device)
+        if eng is None:
+            return None
+        f = self.preprocessor.featurizer
+        r = eng.reserved
+        M = ragged.envelope_frames(r.max_samples, r.max_frames, r.pad_to)
+        stream = torch.cuda.current_stream(ref.device)
+        if stream.cuda_stream == 0:                              # graphs cannot be captured on the legacy default stream
+            side = getattr(self, '_ragged_stream', None)
+            if side is None or side.device != ref.device:
+                side = self._ragged_stream = torch.cuda.Stream(ref.device)
+            side.wait_stream(stream)
+        else:
+            side = stream
+        out = None
+        with torch.cuda.stream(side):
+            if has_in and int(f.pad_to) == r.pad_to:
+                if input_signal.shape[0] <= r.max_batch and 256 < input_signal.shape[1] <= r.max_samples:
+                    sig = input_signal.float().contiguous()
+                    if f.dither > 0:
+                        sig = sig + f.dither * torch.randn_like(sig)
+                    fb, plan = self._frontend_plan_for(ref.device)
+                    audio_lens = input_signal_length.to(device=ref.device, dtype=torch.int32).contiguous()
+                    window = f.window.to(device=ref.device, dtype=torch.float32).contiguous()
+                    out = eng.forward_ragged_audio(sig, audio_lens, fb, window, plan, float(f.preemph), r.pad_to, stream=side)
+            else:
+                if has_in:
+                    processed_signal, processed_signal_length = self._frontend_hip(input_signal, input_signal_length)
+                if processed_signal.shape[0] <= r.max_batch and processed_signal.shape[2] <= M:
+                    out = eng.forward_ragged(processed_signal.float(), processed_signal_length, stream=side)
+            if out is not None:                                  # views of the engine's buffers: callers keep results across batches
+                if decode:
+                    res = out[3]
+                    out = dataclasses.replace(res, **{k: getattr(res, k).clone() for k in
+                                                      ('labels', 'n_labels', 'start', 'nframes', 'score', 'utt_score', 'frame_score')})
+                else:
+                    out = (out[0].clone(), out[2].long(), out[1].long())
+        if side is not stream:
+            stream.wait_stream(side)
+            if out is not None:                                  # allocated on the side stream, used on the caller's
+                for t in (out if isinstance(out, tuple) else [getattr(out, fl.name) for fl in dataclasses.fields(out)]):
+                    if torch.is_tensor(t):
+                        t.record_stream(stream)
+        return out
+
     def _frontend_hip_supported(self):
         """The HIP front-end kernels are built for the QuartzNet / Jasper preprocessor (quartznet_15x5.yaml:30-41):
         n_fft 512, hop 160, a 320-tap window, per-feature normalisation, log(x + 2^-24), power spectrum.  Any other
@@ -367,6 +465,16 @@ class EncDecCTCModel(nn.Module):
             if not ref.is_cuda:
                 raise RuntimeError('the calibrated integer model runs on the MI355X HIP engine only: move the inputs '
                                    'to cuda (there is no CPU fallback for the quantised inference path)')
+            if self._reserve is not None:                        # reserve(): ragged batches on the reserved engine
+                out = self._ragged_forward(has_in, input_signal, input_signal_length, processed_signal,
+                                           processed_signal_length, decode)
+                if out is not None:
+                    return out
+                if not self._ragged_warned:
+                    import warnings
+                    warnings.warn(f'a batch of shape {tuple(ref.shape)} lies outside the reserved envelope (max_batch, '
+                                  f'max_seconds) = {self._reserve}: such batches run on the unreserved engine')
+                    self._ragged_warned = True
             eng = self._get_engine(ref.device)
             f = self.preprocessor.featurizer
             if has_in and self._frontend_hip_supported() and f.pad_to > 0:

@@ -17,6 +17,8 @@ SYMBOLS = ['qasr_blob_check', 'qasr_engine_create', 'qasr_engine_create_ex', 'qa
            'qasr_dw_conv_acc', 'qasr_dense_conv_acc', 'qasr_requant', 'qasr_dyn_range', 'qasr_dyn_range_percentile', 'qasr_dyn_residue_codes', 'qasr_dyn_act_params', 'qasr_dyn_requant',
            'qasr_dyn_quant_in', 'qasr_dyn_conv_params', 'qasr_sep_layer', 'qasr_quantile2', 'qasr_quantile_workspace_bytes', 'qasr_debug_prof',
            'qasr_debug_timeline', 'qasr_ctc_collapse', 'qasr_engine_attach_ctc',
+           'qasr_engine_reserve', 'qasr_engine_forward_ragged', 'qasr_engine_forward_ragged_audio', 'qasr_engine_ragged_stats',
+           'qasr_ragged_bucket_frames', 'qasr_ragged_envelope_frames',
            'qasr_last_error', 'qasr_version']
 
 _lib = None
@@ -42,8 +44,9 @@ class EngineOpts(C.Structure):
     """qasr_engine_opts (include/qasr.h): the launch-plan choices of one engine."""
     _fields_ = ([('struct_size', C.c_uint32), ('debug', C.c_uint32)] +
                 [(n, C.c_int32) for n in ('tile_frames', 'sep_gen', 'fuse_dw', 'fuse_stem', 'fuse_decoder', 'graph',
-                                          'retired_whole_utterance', 'res_tile128', 'dense_tile128', 'retired_legacy_pw', 'retired_persistent', 'fuse_norm')] +
-                [('reserved', C.c_int32 * 2)])
+                                          'retired_whole_utterance', 'res_tile128', 'dense_tile128', 'retired_legacy_pw', 'retired_persistent', 'fuse_norm',
+                                          'mask_skip')] +
+                [('reserved', C.c_int32 * 1)])
 
 
 class CtcOut(C.Structure):
@@ -52,8 +55,44 @@ class CtcOut(C.Structure):
                                                                          'utt_score')]
 
 
+class ReserveOpts(C.Structure):
+    """qasr_reserve_opts (include/qasr.h): the envelope of a reserved engine."""
+    _fields_ = ([('struct_size', C.c_uint32)] +
+                [(n, C.c_int32) for n in ('max_batch', 'max_samples', 'max_frames', 'n_mels', 'pad_to', 'want_logp', 'decode',
+                                          'max_graphs')] + [('reserved', C.c_int32 * 3)])
+
+
+class RaggedOut(C.Structure):
+    """qasr_ragged_out (include/qasr.h): engine-owned buffers of the last ragged forward."""
+    _fields_ = ([('struct_size', C.c_uint32)] +
+                [(n, C.c_int32) for n in ('out_frames', 'bucket_frames', 'row_pitch', 'n_classes')] +
+                [(n, C.c_void_p) for n in ('tokens', 'lens_out', 'logp', 'frame_score')] + [('ctc', CtcOut)] +
+                [(n, C.c_void_p) for n in ('feats', 'feat_lens')])
+
+
+class RaggedStats(C.Structure):
+    """qasr_ragged_stats (include/qasr.h)"""
+    _fields_ = [('struct_size', C.c_uint32), ('n_buckets', C.c_int32), ('device_allocs', C.c_uint64),
+                ('device_frees', C.c_uint64), ('graphs_captured', C.c_uint64), ('graph_replays', C.c_uint64),
+                ('eager_runs', C.c_uint64), ('bucket_frames', C.c_int32 * 64), ('bucket_calls', C.c_uint64 * 64)]
+
+
 class QasrError(RuntimeError):
     pass
+
+
+class _DeviceView:
+    """Engine-owned device memory as a torch tensor without a copy (torch.as_tensor reads __cuda_array_interface__)."""
+
+    def __init__(self, ptr, shape, typestr):
+        self.__cuda_array_interface__ = {'shape': tuple(int(x) for x in shape), 'typestr': typestr, 'data': (int(ptr), False),
+                                         'version': 2, 'strides': None}
+
+
+def _view(ptr, shape, dtype, device):
+    if not ptr:
+        return None
+    return torch.as_tensor(_DeviceView(ptr, shape, '<f4' if dtype == torch.float32 else '<i4'), device=device)
 
 
 def load_library():
@@ -104,6 +143,14 @@ def load_library():
     if hasattr(lib, 'qasr_ctc_collapse'):       # (a QASR_LIB A/B build of an older tree lacks them: calling them raises there)
         lib.qasr_ctc_collapse.argtypes = [vp, vp, vp, vp, i32, i32, i32, C.POINTER(CtcOut)]
         lib.qasr_engine_attach_ctc.argtypes = [vp, vp, C.POINTER(CtcOut), i32]
+    if hasattr(lib, 'qasr_engine_reserve'):     # (likewise)
+        lib.qasr_engine_reserve.argtypes = [vp, C.POINTER(ReserveOpts)]
+        lib.qasr_engine_forward_ragged.argtypes = [vp, vp, vp, vp, i32, i32, C.POINTER(RaggedOut)]
+        lib.qasr_engine_forward_ragged_audio.argtypes = [vp, vp, vp, vp, i32, i32, vp, vp, i32, C.c_float, i32, vp, sz,
+                                                         C.POINTER(RaggedOut)]
+        lib.qasr_engine_ragged_stats.argtypes = [vp, C.POINTER(RaggedStats)]
+        lib.qasr_ragged_bucket_frames.argtypes = [i32, i32, i32]
+        lib.qasr_ragged_envelope_frames.argtypes = [i32, i32, i32]
     lib.qasr_debug_prof.argtypes = [vp]
     lib.qasr_debug_timeline.argtypes = [vp, sz]
     lib.qasr_sep_layer.argtypes = [vp, C.POINTER(SepLayerArgs), C.c_char_p, sz]
@@ -190,7 +237,7 @@ class Engine:
 
     def __init__(self, blob: bytes, device=0, debug=False, timing=False, wide_tiles=False,
                  graph=False, tile=None, sep_gen=None, fuse_dw=None, fuse_stem=None, fuse_decoder=None, res_tile128=None,
-                 dense_tile128=None, fuse_norm=None, legacy_create=False):
+                 dense_tile128=None, fuse_norm=None, legacy_create=False, mask_skip=None):
         """Options = qasr_engine_opts (include/qasr.h).  tile: frames per work-group (32 / 64 / 128; `wide_tiles=True` is the
         older spelling of 128); None leaves a choice at the engine's default."""
         lib = load_library()
@@ -208,7 +255,8 @@ class Engine:
         o.tile_frames = int(tile) if tile else (128 if wide_tiles else 32)
         o.sep_gen = int(sep_gen or 0)
         for name, v in (('fuse_dw', fuse_dw), ('fuse_stem', fuse_stem), ('fuse_decoder', fuse_decoder),
-                        ('res_tile128', res_tile128), ('dense_tile128', dense_tile128), ('fuse_norm', fuse_norm)):
+                        ('res_tile128', res_tile128), ('dense_tile128', dense_tile128), ('fuse_norm', fuse_norm),
+                        ('mask_skip', mask_skip)):
             if v is not None:
                 setattr(o, name, int(bool(v)))
         o.graph = int(bool(graph))
@@ -227,6 +275,7 @@ class Engine:
         self._ctc = None                    # (frame_score, CtcResult, use_lens) attached to the engine
         self._ctc_auto = False              # ... by a decode= call (dropped again by the next call without decode=)
         self._ctc_cache = {}                # decode=True: persistent buffers of the current (B, T')
+        self.reserved = None                # ReserveOpts after reserve()
 
     def close(self):
         if getattr(self, '_h', None) and self._h.value:
@@ -339,6 +388,92 @@ class Engine:
         self._keep = (audio, audio_lens, feats, feat_lens, fb, window, plan)
         return (logp, tokens, enc_len) if res is None else (logp, tokens, enc_len, res)
 
+    # ---- reserved engines: ragged batches without allocation, one captured graph per bucket (qasr_engine_reserve)
+    def reserve(self, max_batch, max_samples=None, max_frames=None, want_logp=True, decode=False, n_mels=None, pad_to=16,
+                max_graphs=None):
+        """Allocates once for the envelope max_batch x (max_samples audio samples and / or max_frames feature frames): the
+        arena, every workspace, staging for the input and the output buffers.  Afterwards forward_ragged /
+        forward_ragged_audio take any shape inside it without allocating, and replay one captured graph per bucket
+        (qasr/ragged.py has the bucket policy).  decode: False; True (collapse up to the encoded lengths, as
+        forward(decode=True)); 'padded' (walk the padded row of the batch's own T', as the reference does).
+        A reserved engine refuses forward / forward_audio."""
+        o = ReserveOpts()
+        o.struct_size = C.sizeof(ReserveOpts)
+        o.max_batch = int(max_batch)
+        o.max_samples = int(max_samples or 0)
+        o.max_frames = int(max_frames or 0)
+        o.n_mels = int(n_mels or 0)
+        o.pad_to = int(pad_to)
+        o.want_logp = int(bool(want_logp))
+        o.decode = 2 if decode == 'padded' else int(bool(decode))
+        o.max_graphs = int(max_graphs or 0)
+        with torch.cuda.device(self.device):
+            _check(self.lib.qasr_engine_reserve(self._h, C.byref(o)), 'qasr_engine_reserve')
+        self.reserved = o
+        return self
+
+    def _ragged_result(self, ro, B, decode_mode):
+        dev, To, P, Bm = self.device, ro.out_frames, ro.row_pitch, self.reserved.max_batch
+        f32, i32 = torch.float32, torch.int32
+        tokens = _view(ro.tokens, (Bm, P), i32, dev)[:B, :To]
+        enc_len = _view(ro.lens_out, (Bm,), i32, dev)[:B]
+        logp = _view(ro.logp, (Bm, P, ro.n_classes), f32, dev)
+        logp = None if logp is None else logp[:B, :To]
+        if not decode_mode:
+            return logp, tokens, enc_len
+        from .ctc import CtcResult
+        c = ro.ctc
+        res = CtcResult(labels=_view(c.labels, (Bm, P), i32, dev)[:B, :To], n_labels=_view(c.n_labels, (Bm,), i32, dev)[:B],
+                        start=_view(c.start, (Bm, P), i32, dev)[:B, :To], nframes=_view(c.nframes, (Bm, P), i32, dev)[:B, :To],
+                        score=_view(c.score, (Bm, P), f32, dev)[:B, :To], utt_score=_view(c.utt_score, (Bm,), f32, dev)[:B],
+                        blank=self.n_classes - 1, frame_score=_view(ro.frame_score, (Bm, P), f32, dev)[:B, :To])
+        return logp, tokens, enc_len, res
+
+    def forward_ragged(self, feats, lens, stream=None):
+        """qasr_engine_forward_ragged: feats f32 [B, feat_in, T] (cuda), lens [B] (each <= T), any B <= max_batch and T <=
+        max_frames of reserve() -> (log_probs or None, tokens, enc_len[, CtcResult with decode]).  The results are VIEWS
+        [:B, :T'] of the engine's own buffers - no copy - and are valid until the next call on this engine: clone what
+        must outlive it.  Bit-identical to forward() of an unreserved engine at the exact shape."""
+        assert feats.is_cuda and feats.dtype == torch.float32 and feats.dim() == 3 and feats.shape[1] == self.feat_in
+        feats = feats.contiguous()
+        lens32 = lens.to(device=feats.device, dtype=torch.int32).contiguous()
+        B, _, T = feats.shape
+        ro = RaggedOut()
+        ro.struct_size = C.sizeof(RaggedOut)
+        _check(self.lib.qasr_engine_forward_ragged(self._h, _stream_ptr(stream), _ptr(feats), _ptr(lens32), B, T, C.byref(ro)),
+               'qasr_engine_forward_ragged')
+        self._keep = (feats, lens32)
+        self.last_ragged = ro
+        return self._ragged_result(ro, B, getattr(self, 'reserved', None) is not None and self.reserved.decode)
+
+    def forward_ragged_audio(self, audio, audio_lens, fb, window, plan, preemph=0.97, pad_to=16, stream=None):
+        """qasr_engine_forward_ragged_audio: audio f32 [B, S] (cuda), audio_lens int32 [B]; any B <= max_batch, S <=
+        max_samples of reserve().  Returns what forward_ragged returns, under the same rule: views of engine-owned buffers,
+        valid until the next call on this engine."""
+        assert audio.is_cuda and audio.dtype == torch.float32 and audio.dim() == 2 and audio.is_contiguous()
+        assert audio_lens.is_cuda and audio_lens.dtype == torch.int32 and fb.is_cuda and window.is_cuda
+        B, S = audio.shape
+        ro = RaggedOut()
+        ro.struct_size = C.sizeof(RaggedOut)
+        _check(self.lib.qasr_engine_forward_ragged_audio(self._h, _stream_ptr(stream), _ptr(audio), _ptr(audio_lens), B, S,
+                                                         _ptr(fb), _ptr(window), fb.shape[0], C.c_float(preemph), pad_to,
+                                                         _ptr(plan), plan.numel(), C.byref(ro)),
+               'qasr_engine_forward_ragged_audio')
+        self._keep = (audio, audio_lens, fb, window, plan)
+        self.last_ragged = ro
+        return self._ragged_result(ro, B, self.reserved.decode)
+
+    def ragged_stats(self):
+        """qasr_engine_ragged_stats as a dict: device allocations / frees of this engine since creation, graphs captured,
+        graph replays, eager runs, and {bucket edge: calls}."""
+        st = RaggedStats()
+        st.struct_size = C.sizeof(RaggedStats)
+        _check(self.lib.qasr_engine_ragged_stats(self._h, C.byref(st)), 'qasr_engine_ragged_stats')
+        return {'device_allocs': int(st.device_allocs), 'device_frees': int(st.device_frees),
+                'graphs_captured': int(st.graphs_captured), 'graph_replays': int(st.graph_replays),
+                'eager_runs': int(st.eager_runs),
+                'buckets': {int(st.bucket_frames[i]): int(st.bucket_calls[i]) for i in range(st.n_buckets)}}
+
     # ---- parity hooks (debug engines)
     def read_acc(self, op, pane, cout, T_out):
         Tp = (T_out + 63) // 64 * 64
@@ -443,7 +578,7 @@ def requant(acc: torch.Tensor, M: torch.Tensor, lo, hi, sb=None, exact_z=False, 
 
 
 def sep_layer(x, lens, wpw, bias, outs, wdw=None, m_dw=None, dw_range=(-128, 127), x_unsigned=False, dilation=1,
-              flags=0, sb=None, res=None, tile=32, gen=2, hooks=True):
+              flags=0, sb=None, res=None, tile=32, gen=2, hooks=True, out_fill=0):
     """One fused separable layer through qasr_sep_layer (the production kernels with caller-made operands).
 
     x            int8 / uint8 [B, cin, T] (cuda)      lens  valid frames per utterance
@@ -453,7 +588,9 @@ def sep_layer(x, lens, wpw, bias, outs, wdw=None, m_dw=None, dw_range=(-128, 127
     res          None or dict(x [B, rcin, T] (uint8 / int8), w int8 [cout, rcin], bias int32 [cout], m f64 [cout],
                  sb f32 [cout], m_main f64 [cout], qlo, qhi)   -> QASR_F_RESADD
     Biases are the natural ones: the +128 sum(W) correction of u8 inputs is folded here, as pack.py does.
-    Returns dict(outs=[int8 [B, cout, T]...], dw_acc, acc, racc (int32, None without hooks), label)."""
+    out_fill     byte the output buffers hold before the call (tests of what a kernel leaves unwritten)
+    Returns dict(outs=[int8 [B, cout, T]...], outs_padded=[the same with the row padding, [B, cout, Tp]], dw_acc, acc, racc
+    (int32, None without hooks), label)."""
     from .pack import F_RESADD, fragment_order
     lib = load_library()
     dev = x.device
@@ -532,7 +669,7 @@ def sep_layer(x, lens, wpw, bias, outs, wdw=None, m_dw=None, dw_range=(-128, 127
     a.n_outs = len(outs)
     out_t = []
     for j, o in enumerate(outs):
-        t = torch.zeros(B, cout, Tp, dtype=torch.int8, device=dev)
+        t = torch.full((B, cout, Tp), int(out_fill), dtype=torch.int8, device=dev)
         out_t.append(t)
         a.outs[j].ptr = t.data_ptr()
         a.outs[j].mode, a.outs[j].lo, a.outs[j].hi = o['mode'], o['lo'], o['hi']
@@ -553,7 +690,7 @@ def sep_layer(x, lens, wpw, bias, outs, wdw=None, m_dw=None, dw_range=(-128, 127
     label = C.create_string_buffer(96)
     _check(lib.qasr_sep_layer(_stream_ptr(), C.byref(a), label, 96), 'qasr_sep_layer')
     torch.cuda.synchronize()
-    return dict(outs=[t[:, :, :T] for t in out_t], label=label.value.decode(),
+    return dict(outs=[t[:, :, :T] for t in out_t], outs_padded=out_t, label=label.value.decode(),
                 **{k: (hk[k][:, :, :T] if k in hk else None) for k in ('dw_acc', 'acc', 'racc')})
 
 
