@@ -295,6 +295,59 @@ int qasr_ctc_collapse(void* stream, const int32_t* tokens, const float* frame_sc
  * QASR_ERR_ARG: a blob without a LOGSOFTMAX op, score / utt_score without frame_score, missing labels / n_labels. */
 int qasr_engine_attach_ctc(qasr_engine* e, float* frame_score, const qasr_ctc_out* out, int use_lens);
 
+/* ---- CTC prefix beam search on the device (no language model) ---------------------------------------------------------
+ * What ctc_beam_search_decoder of ctc_decoders does without a scorer (the reference's BeamSearchDecoderWithLM with
+ * lm_path=None, cutoff_prob=1.0), in fixed point: a log-probability x becomes q = rint(x * 2^16) (clamped to +-2^30, NaN:
+ * the floor), scores are int64 sums of them, log 0 is the sentinel -2^62 (never an operand), and log-add-exp is
+ * max + table[(max - min) >> 6] (max alone from a difference of 16 * 2^16 on) with the 16384-entry u16 table
+ * table[i] = rint(log1p(exp(-(64 i) / 2^16)) * 2^16) the caller builds once and passes in device memory.  The rules, the
+ * tie order and the prefix hash are stated in qasr/beam.py, which these kernels follow bit for bit.  Prefix identity ("is p + c
+ * already in the beam", "which entry is my parent") is a 64-bit hash of the labels together with the length, not the labels
+ * themselves: two different prefixes of one length whose hashes collide would be merged.  Two launches:
+ *   k_topn: log_probs f32, utterance b / frame t / class c at log_probs[b * pitch_utt + t * pitch_frame + c]  ->
+ *           cand_id i32 [B][T][N], cand_q i32 [B][T][N]: per frame the min(N, C) classes of largest value, best first (order
+ *           of the float bit patterns, -0 < +0; ties: lower class first) and their q; the other slots, and every frame
+ *           t >= min(lens[b], T), hold -1 / INT32_MIN.  lens may be NULL (the padded row).
+ *   k_beam: candidates -> per utterance its final beam, best first: labels i32 [B][n_best][T] (tails and unused rows:
+ *           blank), n_labels i32 [B][n_best], score i64 [B][n_best] (fixed point; unused rows -2^62), n_hyps i32 [B].
+ *           workspace: qasr_ctc_beam_workspace_bytes(B, T, beam_width) bytes the call may overwrite (the prefix trie);
+ *           nothing is allocated and no length is read on the host, so both calls can be captured.
+ * QASR_ERR_ARG with nothing launched and no output written: an unknown struct_size, a NULL among the required pointers,
+ * B < 1, T < 1 or T > QASR_BEAM_MAX_FRAMES, B * T >= 2^31, C < 1, N outside 1 .. QASR_BEAM_MAX_CANDIDATES, beam_width
+ * outside 1 .. QASR_BEAM_MAX_WIDTH, n_best outside 1 .. beam_width, blank < 0, pitch_frame < C,
+ * pitch_utt < T * pitch_frame, lae_entries != QASR_BEAM_TABLE_ENTRIES, a workspace smaller than the query says. */
+#define QASR_BEAM_MAX_WIDTH 128
+#define QASR_BEAM_MAX_CANDIDATES 64
+#define QASR_BEAM_MAX_FRAMES 65536
+#define QASR_BEAM_TABLE_ENTRIES 16384
+typedef struct qasr_ctc_topn_args {
+  uint32_t struct_size;        /* sizeof of this struct in the caller's header */
+  int32_t B, T, C, N;
+  int64_t pitch_utt, pitch_frame;   /* in floats */
+  const float* log_probs;
+  const int32_t* lens;         /* optional */
+  int32_t* cand_id;
+  int32_t* cand_q;
+} qasr_ctc_topn_args;
+int qasr_ctc_topn(void* stream, const qasr_ctc_topn_args* args);
+typedef struct qasr_ctc_beam_args {
+  uint32_t struct_size;
+  int32_t B, T, N, beam_width, n_best, blank;
+  uint32_t lae_entries;        /* QASR_BEAM_TABLE_ENTRIES */
+  const int32_t* cand_id;
+  const int32_t* cand_q;
+  const int32_t* lens;         /* optional */
+  const uint16_t* lae_table;
+  void* workspace;
+  size_t workspace_bytes;
+  int32_t* labels;
+  int32_t* n_labels;
+  int64_t* score;
+  int32_t* n_hyps;
+} qasr_ctc_beam_args;
+size_t qasr_ctc_beam_workspace_bytes(int B, int T, int beam_width);
+int qasr_ctc_beam(void* stream, const qasr_ctc_beam_args* args);
+
 /* ---- reserved engines: ragged batches without allocation, with graph replay ------------------------------------------
  * A data loader pads every batch to its own longest utterance (the reference's collate function), so (B, T) changes on
  * almost every call; qasr_engine_forward[_audio] then rebuilds its plan (device-synchronising frees + allocations) and,

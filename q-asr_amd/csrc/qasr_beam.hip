@@ -1,0 +1,451 @@
+// CTC prefix beam search without a language model, in fixed point (the host statement is qasr/beam.py; this file
+// follows it bit for bit): k_topn picks each frame's N best classes out of float32 log-probabilities, k_beam runs the
+// search over those candidates.  Scores are int64 sums of q = rint(logp * 2^16); the only non-linear step is a look-up in
+// the log-add-exp table the caller passes in (16384 x u16, LDS resident), so neither kernel calls exp or log and the
+// results do not depend on thread order.
+//
+// k_topn: one wave (= one work-group) per frame.  Keys are the order-preserving integer image of the float bits (as k_ctc
+// uses it).  An MSB-first radix select (4 passes of 8 bits, LDS histogram) finds the key of the N-th largest class and how
+// many classes of exactly that key belong to the N; a compaction in class order collects them (lower id first among equal
+// keys), and one rank-by-counting sort in the wave orders the <= 64 survivors.
+//
+// k_beam: one work-group per utterance, sequential over frames.  The beam (<= 128 entries: pb, pnb, score, prefix hash,
+// parent hash, length, last label, trie node) is double-buffered in LDS.  Per frame: every entry computes its own
+// successor by gathering its (at most two) contributions; new prefixes are scored on the fly as q + base, never stored.
+// The best W of the <= W (N + 1) candidates are found by a radix select on r = max score - score (as many 8-bit passes as
+// the frame's score range needs; a tie at the cut is settled by a second select on the candidate index, the tie rule),
+// then sorted by counting.  A slot's candidates belong to a fixed group of threads that keep the slot's state in registers.
+// Prefixes are nodes (parent, label) in the caller's workspace: the node of the entry that lands in slot s at frame t is
+// t * W + s, so nothing is counted or allocated.  LDS atomics only (histogram, winner slots); global memory sees plain
+// vector stores.  Every loop is bounded by T, W, N or a constant.
+#include <climits>
+
+#include "qasr_internal.h"
+
+namespace qasr {
+
+#define BEAM_NEG (-(1ll << 62))
+#define BEAM_QFLOOR (-1073741824.f)
+#define BEAM_QCEIL (1073741824.f)
+#define BEAM_EMPTY_Q INT_MIN
+#define BEAM_DMAX (16ll << 16)
+#define BEAM_HMUL 0x9E3779B97F4A7C15ull
+
+__device__ __forceinline__ int beam_key(int bits) { return bits ^ ((bits >> 31) & 0x7fffffff); }
+
+__device__ __forceinline__ int beam_quantize(float x) {
+  float y = x * 65536.f;
+  if (!(y >= BEAM_QFLOOR)) y = BEAM_QFLOOR;      // NaN and -inf take the floor
+  if (y > BEAM_QCEIL) y = BEAM_QCEIL;
+  return (int)rintf(y);
+}
+
+// ------------------------------------------------------------------------------------------------------------ k_topn
+struct TopnP {
+  const float* logp;
+  const int32_t* lens;      // optional [B]
+  int32_t* cand_id;         // [B][T][N]
+  int32_t* cand_q;          // [B][T][N]
+  long long pitch_b, pitch_t;
+  int B, T, C, N;
+};
+
+#define TOPN_UNROLL 8
+
+__global__ void __launch_bounds__(64) k_topn(TopnP p) {
+  __shared__ unsigned sm_hist[256];
+  __shared__ unsigned sm_key[64];
+  __shared__ int sm_id[64];
+  const int lane = threadIdx.x;
+  const int frame = blockIdx.x;                  // < B * T
+  const int b = frame / p.T, t = frame - b * p.T;
+  const int lim = p.lens ? min(max(p.lens[b], 0), p.T) : p.T;
+  int32_t* const oid = p.cand_id + (size_t)frame * p.N;
+  int32_t* const oq = p.cand_q + (size_t)frame * p.N;
+  if (t >= lim) {
+    if (lane < p.N) oid[lane] = -1, oq[lane] = BEAM_EMPTY_Q;
+    return;
+  }
+  const float* const row = p.logp + (long long)b * p.pitch_b + (long long)t * p.pitch_t;
+  const int C = p.C, ne = min(p.N, C);
+  // radix select: the key of the ne-th largest class
+  unsigned prefix = 0;
+  int k = ne;                                    // still to take, counted from the top
+  for (int pass = 3; pass >= 0; --pass) {
+    const int shift = pass * 8;
+    for (int i = lane; i < 256; i += 64) sm_hist[i] = 0;      // no barrier before this: the work-group is ONE wave, whose
+    __syncthreads();                                          // LDS reads of the previous pass are behind it in program order
+    for (int c0 = lane; c0 < C; c0 += 64 * TOPN_UNROLL) {        // TOPN_UNROLL independent loads in flight per lane
+      int bits[TOPN_UNROLL];
+#pragma unroll
+      for (int j = 0; j < TOPN_UNROLL; ++j) bits[j] = c0 + j * 64 < C ? __float_as_int(row[c0 + j * 64]) : 0;
+#pragma unroll
+      for (int j = 0; j < TOPN_UNROLL; ++j) {
+        const unsigned key = (unsigned)beam_key(bits[j]) ^ 0x80000000u;
+        if (c0 + j * 64 < C && (pass == 3 || (key >> (shift + 8)) == prefix)) atomicAdd(&sm_hist[(key >> shift) & 255u], 1u);
+      }
+    }
+    __syncthreads();
+    unsigned h[4];
+    unsigned tl = 0;
+#pragma unroll
+    for (int j = 0; j < 4; ++j) h[j] = sm_hist[lane * 4 + j], tl += h[j];
+    unsigned suf = tl;                           // inclusive suffix sum over lanes: classes in this lane's bins and above
+#pragma unroll
+    for (int d = 1; d < 64; d <<= 1) {
+      const unsigned o = __shfl_down(suf, d);
+      if (lane + d < 64) suf += o;
+    }
+    const unsigned above = suf - tl;
+    const bool mine = above < (unsigned)k && (unsigned)k <= suf;
+    int bin = 0, kk = 0;
+    if (mine) {
+      unsigned acc = above;
+      bin = lane * 4;
+      kk = k - (int)acc;
+#pragma unroll
+      for (int j = 3; j >= 0; --j) {
+        if (acc + h[j] >= (unsigned)k) { bin = lane * 4 + j; kk = k - (int)acc; break; }
+        acc += h[j];
+      }
+    }
+    const unsigned long long who = __ballot(mine);
+    const int src = who ? __ffsll((long long)who) - 1 : 0;      // exactly one lane (the counts add up to >= k)
+    bin = __shfl(bin, src);
+    k = __shfl(kk, src);
+    prefix = (prefix << 8) | (unsigned)bin;
+  }
+  // prefix: the cut key; k of the classes with exactly that key belong to the ne (lowest ids first)
+  int n_out = 0, n_eq = 0;
+  for (int cb = 0; cb < C; cb += 64 * TOPN_UNROLL) {
+    int bits[TOPN_UNROLL];
+#pragma unroll
+    for (int j = 0; j < TOPN_UNROLL; ++j) bits[j] = cb + j * 64 + lane < C ? __float_as_int(row[cb + j * 64 + lane]) : 0;
+#pragma unroll
+    for (int j = 0; j < TOPN_UNROLL; ++j) {                      // class order: chunk by chunk, lane by lane
+      const int c = cb + j * 64 + lane;
+      const unsigned key = (unsigned)beam_key(bits[j]) ^ 0x80000000u;
+      const bool gt = c < C && key > prefix, eq = c < C && key == prefix;
+      const unsigned long long below = (1ull << lane) - 1ull;
+      const unsigned long long em = __ballot(eq);
+      const bool take = gt || (eq && n_eq + __popcll(em & below) < k);
+      const unsigned long long tm = __ballot(take);
+      if (take) {
+        const int pos = n_out + __popcll(tm & below);
+        if (pos < 64) sm_key[pos] = key, sm_id[pos] = c;
+      }
+      n_out += __popcll(tm);
+      n_eq += __popcll(em);
+    }
+  }
+  __syncthreads();
+  n_out = min(n_out, ne);
+  if (lane < n_out) {
+    const unsigned key = sm_key[lane];
+    const int id = sm_id[lane];
+    int rank = 0;
+    for (int j = 0; j < n_out; ++j) {
+      const unsigned kj = sm_key[j];
+      rank += (kj > key || (kj == key && sm_id[j] < id)) ? 1 : 0;
+    }
+    oid[rank] = id;
+    oq[rank] = beam_quantize(__int_as_float(beam_key((int)(key ^ 0x80000000u))));
+  } else if (lane < p.N) {
+    oid[lane] = -1, oq[lane] = BEAM_EMPTY_Q;
+  }
+}
+
+int launch_topn(hipStream_t s, const qasr_ctc_topn_args& a) {
+  TopnP p{};
+  p.logp = a.log_probs, p.lens = a.lens, p.cand_id = a.cand_id, p.cand_q = a.cand_q;
+  p.pitch_b = a.pitch_utt, p.pitch_t = a.pitch_frame;
+  p.B = a.B, p.T = a.T, p.C = a.C, p.N = a.N;
+  hipLaunchKernelGGL(k_topn, dim3((unsigned)(a.B * a.T)), dim3(64), 0, s, p);
+  return QASR_OK;
+}
+
+// ------------------------------------------------------------------------------------------------------------ k_beam
+#define BEAM_NT 256
+#define BEAM_NWAVE (BEAM_NT / 64)
+#define BEAM_W QASR_BEAM_MAX_WIDTH
+#define BEAM_N QASR_BEAM_MAX_CANDIDATES
+#define BEAM_TAB QASR_BEAM_TABLE_ENTRIES
+
+struct BeamP {
+  const int32_t* cand_id;   // [B][T][N]
+  const int32_t* cand_q;
+  const int32_t* lens;      // optional [B]
+  const uint16_t* tab;      // [BEAM_TAB]
+  int2* nodes;              // [B][T * W] (parent node, label)
+  int32_t* labels;          // [B][n_best][T]
+  int32_t* n_labels;        // [B][n_best]
+  long long* score;         // [B][n_best]
+  int32_t* n_hyps;          // [B]
+  int B, T, N, W, n_best, blank;
+};
+
+struct BeamState {          // one side of the double buffer
+  long long pb[BEAM_W], pnb[BEAM_W], sc[BEAM_W];
+  unsigned long long hash[BEAM_W], phash[BEAM_W];
+  int len[BEAM_W], last[BEAM_W], node[BEAM_W];
+};
+
+struct BeamLds {
+  uint16_t tab[BEAM_TAB];
+  BeamState st[2];
+  long long k_pb[BEAM_W], k_pnb[BEAM_W], k_sc[BEAM_W];     // the entries' own successors
+  unsigned long long sel_r[BEAM_W];
+  int sel_idx[BEAM_W];
+  unsigned long long child[BEAM_W];                        // bit n of slot i: its extension by candidate n is an entry of the beam
+  int cid[BEAM_N], cq[BEAM_N];
+  unsigned hist[256];
+  long long red_max[BEAM_NWAVE], red_min[BEAM_NWAVE];
+  int red_cnt[BEAM_NWAVE], red_a[BEAM_NWAVE], red_b[BEAM_NWAVE];
+  int bin, kk, n_at, n_sel;
+};
+
+__device__ __forceinline__ long long beam_lae(long long a, long long b, const uint16_t* tab) {
+  const long long m = a > b ? a : b, n = a > b ? b : a;
+  if (n == BEAM_NEG) return m;
+  const long long d = m - n;
+  if (d >= BEAM_DMAX) return m;
+  return m + (long long)tab[d >> 6];
+}
+
+__global__ void __launch_bounds__(BEAM_NT) k_beam(BeamP p) {
+  __shared__ BeamLds L;
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int b = blockIdx.x, T = p.T, N = p.N, W = p.W, N1 = N + 1, blank = p.blank;
+  const int lim = p.lens ? min(max(p.lens[b], 0), T) : T;
+  int2* const nodes = p.nodes + (size_t)b * T * W;
+  const int n_nodes = T * W;
+  for (int i = tid; i < BEAM_TAB; i += BEAM_NT) L.tab[i] = p.tab[i];
+  if (tid == 0) {
+    BeamState& S = L.st[0];
+    S.pb[0] = 0, S.pnb[0] = BEAM_NEG, S.sc[0] = 0, S.hash[0] = 0, S.phash[0] = 0, S.len[0] = 0, S.last[0] = -1, S.node[0] = -1;
+  }
+  const int32_t* const gid = p.cand_id + (size_t)b * T * N;
+  const int32_t* const gq = p.cand_q + (size_t)b * T * N;
+  int pf_id = -1, pf_q = 0;
+  if (tid < N && lim > 0) pf_id = gid[tid], pf_q = gq[tid];
+  int nb = 1, cur = 0;
+  __syncthreads();
+  for (int t = 0; t < lim && nb > 0; ++t) {
+    const BeamState& S = L.st[cur];
+    BeamState& D = L.st[cur ^ 1];
+    if (tid < N) {
+      L.cid[tid] = pf_id, L.cq[tid] = pf_q;
+      if (t + 1 < lim) pf_id = gid[(size_t)(t + 1) * N + tid], pf_q = gq[(size_t)(t + 1) * N + tid];
+    }
+    if (tid < nb) L.child[tid] = 0;
+    if (tid == 0) L.n_sel = 0;
+    __syncthreads();
+    // ---- the entries themselves
+    if (tid < nb) {
+      const int j = tid, c = S.last[j], lj = S.len[j];
+      int nl = -1, nbk = -1;
+      for (int n = 0; n < N; ++n) {
+        const int id = L.cid[n];
+        if (id >= 0) {
+          if (id == blank && nbk < 0) nbk = n;
+          if (id == c && nl < 0) nl = n;
+        }
+      }
+      int ps = -1;
+      if (lj > 0) {
+        const unsigned long long ph = S.phash[j];
+        for (int i = nb - 1; i >= 0; --i)            // no early exit (the loads pipeline); the first matching slot counts
+          ps = (S.hash[i] == ph && S.len[i] + 1 == lj) ? i : ps;
+      }
+      const long long pbn = nbk >= 0 ? S.sc[j] + (long long)L.cq[nbk] : BEAM_NEG;
+      long long a = BEAM_NEG, e = BEAM_NEG;
+      if (nl >= 0) {
+        const long long ql = (long long)L.cq[nl];
+        if (S.pnb[j] != BEAM_NEG) a = ql + S.pnb[j];
+        if (ps >= 0) {
+          const long long base = S.last[ps] == c ? S.pb[ps] : S.sc[ps];
+          if (base != BEAM_NEG) e = ql + base;
+          atomicOr(&L.child[ps], 1ull << nl);
+        }
+      }
+      const long long pnbn = beam_lae(a, e, L.tab);
+      L.k_pb[j] = pbn, L.k_pnb[j] = pnbn, L.k_sc[j] = beam_lae(pbn, pnbn, L.tab);
+    }
+    __syncthreads();
+    // ---- the candidates: idx = i * (N + 1) + k, k == 0 the entry in slot i itself, else its extension by candidate k - 1.
+    // A row of candidates (one slot) belongs to 256 / rows threads, rows = nb rounded up to a power of two, so a thread
+    // keeps its slot's state in registers and scores a candidate with one add.
+    const int lg = nb > 1 ? 32 - __clz(nb - 1) : 0;            // rows = 1 << lg <= 128
+    const int tpr_lg = 8 - lg, tpr = 1 << tpr_lg;               // BEAM_NT == 256
+    const int my_i = tid >> tpr_lg, my_sub = tid & (tpr - 1);
+    const bool active = my_i < nb;
+    const int r_last = active ? S.last[my_i] : -1;
+    const long long r_pb = active ? S.pb[my_i] : BEAM_NEG, r_sc = active ? S.sc[my_i] : BEAM_NEG;
+    const long long r_ksc = active ? L.k_sc[my_i] : BEAM_NEG;
+    const unsigned long long r_child = active ? L.child[my_i] : 0ull;
+    auto cand = [&](int k) -> long long {
+      if (k == 0) return r_ksc;
+      const int n = k - 1, id = L.cid[n];
+      if (id < 0 || id == blank || ((r_child >> n) & 1ull)) return BEAM_NEG;
+      const long long base = id == r_last ? r_pb : r_sc;
+      return base == BEAM_NEG ? BEAM_NEG : base + (long long)L.cq[n];
+    };
+    const int k_end = active ? N1 : 0;
+    long long mx = LLONG_MIN, mn = LLONG_MAX;
+    int cnt = 0;
+    for (int k = my_sub; k < k_end; k += tpr) {
+      const long long v = cand(k);
+      if (v != BEAM_NEG) { ++cnt; mx = v > mx ? v : mx; mn = v < mn ? v : mn; }
+    }
+#pragma unroll
+    for (int d = 32; d >= 1; d >>= 1) {
+      const long long omx = __shfl_xor(mx, d), omn = __shfl_xor(mn, d);
+      cnt += __shfl_xor(cnt, d);
+      mx = omx > mx ? omx : mx, mn = omn < mn ? omn : mn;
+    }
+    if (lane == 0) L.red_max[wave] = mx, L.red_min[wave] = mn, L.red_cnt[wave] = cnt;
+    __syncthreads();
+    mx = L.red_max[0], mn = L.red_min[0], cnt = L.red_cnt[0];
+#pragma unroll
+    for (int w = 1; w < BEAM_NWAVE; ++w) {
+      mx = L.red_max[w] > mx ? L.red_max[w] : mx, mn = L.red_min[w] < mn ? L.red_min[w] : mn;
+      cnt += L.red_cnt[w];
+    }
+    if (cnt == 0) { nb = 0; break; }               // uniform: every thread read the same totals
+    // ---- MSB-first radix select over this thread's candidates: the kk-th smallest key among those `keyfn` admits; returns
+    // the key, leaves in kk how many candidates of exactly that key belong to the kk, in n_at how many have that key
+    auto radix_select = [&](auto keyfn, int nbits, int& kk, int& n_at) -> unsigned long long {
+      const int passes = (nbits + 7) >> 3;          // <= 8
+      unsigned long long prefix = 0;
+      for (int pass = passes - 1; pass >= 0; --pass) {
+        const int shift = pass * 8;
+        __syncthreads();                            // the previous pass's bin / kk and histogram have been read
+        L.hist[tid] = 0;                            // BEAM_NT == 256 bins
+        __syncthreads();
+        for (int k = my_sub; k < k_end; k += tpr) {
+          unsigned long long key;
+          if (keyfn(k, key) && (shift + 8 >= 64 || (key >> (shift + 8)) == prefix))
+            atomicAdd(&L.hist[(unsigned)(key >> shift) & 255u], 1u);
+        }
+        __syncthreads();
+        const int mine = (int)L.hist[tid];
+        int inc = mine;                             // inclusive prefix sum over the 256 bins, smallest key first
+#pragma unroll
+        for (int d = 1; d < 64; d <<= 1) {
+          const int o = __shfl_up(inc, d);
+          if (lane >= d) inc += o;
+        }
+        if (lane == 63) L.red_a[wave] = inc;
+        __syncthreads();
+        for (int w = 0; w < wave; ++w) inc += L.red_a[w];
+        const int exc = inc - mine;
+        if (exc < kk && kk <= inc) L.bin = tid, L.kk = kk - exc, L.n_at = mine;      // exactly one thread
+        __syncthreads();
+        prefix = (prefix << 8) | (unsigned long long)L.bin;
+        kk = L.kk, n_at = L.n_at;
+      }
+      return prefix;
+    };
+    // ---- the W-th smallest r = mx - score: its value rth; of the candidates with exactly rth, those up to index ith win
+    unsigned long long rth = ~0ull;
+    int ith = INT_MAX;
+    if (cnt > W) {
+      const unsigned long long range = (unsigned long long)(mx - mn);
+      int need = W, n_at = cnt;                     // (a range of 0: every candidate has r == 0)
+      rth = radix_select([&](int k, unsigned long long& key) {
+        const long long v = cand(k);
+        key = (unsigned long long)(mx - v);
+        return v != BEAM_NEG;
+      }, range ? 64 - __clzll((long long)range) : 0, need, n_at);
+      if (n_at > need) {                            // a tie at the cut: the lower candidate indices win
+        const int M = nb * N1;
+        ith = (int)radix_select([&](int k, unsigned long long& key) {
+          const long long v = cand(k);
+          key = (unsigned long long)(my_i * N1 + k);
+          return v != BEAM_NEG && (unsigned long long)(mx - v) == rth;
+        }, 32 - __clz(M), need, n_at);
+      }
+    }
+    // ---- collect the winners (in any order: they are sorted next)
+    for (int k = my_sub; k < k_end; k += tpr) {
+      const long long v = cand(k);
+      if (v != BEAM_NEG) {
+        const unsigned long long r = (unsigned long long)(mx - v);
+        const int idx = my_i * N1 + k;
+        if (r < rth || (r == rth && idx <= ith)) {
+          const int at = atomicAdd(&L.n_sel, 1);
+          if (at < BEAM_W) L.sel_r[at] = r, L.sel_idx[at] = idx;
+        }
+      }
+    }
+    __syncthreads();
+    const int ns = min(L.n_sel, W);
+    // ---- order them (score descending = r ascending, then candidate index) and write the next beam
+    if (tid < ns) {
+      const unsigned long long r = L.sel_r[tid];
+      const int idx = L.sel_idx[tid];
+      int rank = 0;
+      for (int m = 0; m < ns; ++m) {
+        const unsigned long long rm = L.sel_r[m];
+        rank += (rm < r || (rm == r && L.sel_idx[m] < idx)) ? 1 : 0;
+      }
+      const int i = idx / N1, k = idx - i * N1;
+      if (k == 0) {
+        D.pb[rank] = L.k_pb[i], D.pnb[rank] = L.k_pnb[i], D.sc[rank] = L.k_sc[i];
+        D.hash[rank] = S.hash[i], D.phash[rank] = S.phash[i], D.len[rank] = S.len[i], D.last[rank] = S.last[i];
+        D.node[rank] = S.node[i];
+      } else {
+        const int c = L.cid[k - 1];
+        const long long v = mx - (long long)r;
+        unsigned long long x = (S.hash[i] ^ ((unsigned long long)(long long)c + 1ull)) * BEAM_HMUL;
+        x ^= x >> 32;
+        D.pb[rank] = BEAM_NEG, D.pnb[rank] = v, D.sc[rank] = v;
+        D.hash[rank] = x, D.phash[rank] = S.hash[i], D.len[rank] = S.len[i] + 1, D.last[rank] = c;
+        const int nd = t * W + rank;                // < T * W
+        D.node[rank] = nd;
+        nodes[nd] = make_int2(S.node[i], c);
+      }
+    }
+    __syncthreads();
+    nb = ns, cur ^= 1;
+  }
+  __syncthreads();
+  // ---- the final beam, best first
+  const BeamState& S = L.st[cur];
+  const int nh = min(nb, p.n_best);
+  int32_t* const lab = p.labels + (size_t)b * p.n_best * T;
+  for (int i = tid; i < p.n_best * T; i += BEAM_NT) lab[i] = blank;
+  if (tid == 0) p.n_hyps[b] = nh;
+  __syncthreads();                                  // the fill above and every node store of this work-group are visible
+  if (tid < p.n_best) {
+    const int h = tid;
+    int len = 0;
+    long long sc = BEAM_NEG;
+    if (h < nh) {
+      len = min(S.len[h], T), sc = S.sc[h];
+      int nd = S.node[h];
+      for (int k = len - 1; k >= 0; --k) {          // bounded by T; a node outside the pool ends the walk
+        if (nd < 0 || nd >= n_nodes) break;
+        const int2 e = nodes[nd];
+        lab[(size_t)h * T + k] = e.y;
+        nd = e.x;
+      }
+    }
+    p.n_labels[(size_t)b * p.n_best + h] = len;
+    p.score[(size_t)b * p.n_best + h] = sc;
+  }
+}
+
+size_t beam_workspace_bytes(int B, int T, int W) { return (size_t)B * (size_t)T * (size_t)W * sizeof(int2); }
+
+int launch_beam(hipStream_t s, const qasr_ctc_beam_args& a) {
+  BeamP p{};
+  p.cand_id = a.cand_id, p.cand_q = a.cand_q, p.lens = a.lens, p.tab = a.lae_table;
+  p.nodes = (int2*)a.workspace;
+  p.labels = a.labels, p.n_labels = a.n_labels, p.score = (long long*)a.score, p.n_hyps = a.n_hyps;
+  p.B = a.B, p.T = a.T, p.N = a.N, p.W = a.beam_width, p.n_best = a.n_best, p.blank = a.blank;
+  hipLaunchKernelGGL(k_beam, dim3((unsigned)a.B), dim3(BEAM_NT), 0, s, p);
+  return QASR_OK;
+}
+
+}  // namespace qasr

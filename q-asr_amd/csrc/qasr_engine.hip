@@ -1003,6 +1003,55 @@ int qasr_ctc_collapse(void* stream, const int32_t* tokens, const float* frame_sc
   return QASR_OK;
 }
 
+int qasr_ctc_topn(void* stream, const qasr_ctc_topn_args* a) {
+  if (!a) return fail(QASR_ERR_ARG, "ctc_topn: args is NULL");
+  if (a->struct_size != sizeof(qasr_ctc_topn_args))
+    return fail(QASR_ERR_ARG, "ctc_topn: struct_size %u is not %zu", a->struct_size, sizeof(qasr_ctc_topn_args));
+  if (!a->log_probs || !a->cand_id || !a->cand_q) return fail(QASR_ERR_ARG, "ctc_topn: log_probs, cand_id and cand_q are required");
+  if (a->B < 1 || a->T < 1 || a->T > QASR_BEAM_MAX_FRAMES || a->C < 1 || (int64_t)a->B * a->T >= (1ll << 31))
+    return fail(QASR_ERR_ARG, "ctc_topn: B %d, T %d (1 .. %d), C %d out of range", a->B, a->T, QASR_BEAM_MAX_FRAMES, a->C);
+  if (a->N < 1 || a->N > QASR_BEAM_MAX_CANDIDATES)
+    return fail(QASR_ERR_ARG, "ctc_topn: N %d is outside 1 .. %d", a->N, QASR_BEAM_MAX_CANDIDATES);
+  if (a->pitch_frame < a->C || a->pitch_utt < (int64_t)a->T * a->pitch_frame)
+    return fail(QASR_ERR_ARG, "ctc_topn: pitch_frame %lld < C or pitch_utt %lld < T * pitch_frame", (long long)a->pitch_frame,
+                (long long)a->pitch_utt);
+  int rc = launch_topn((hipStream_t)stream, *a);
+  if (rc) return fail(rc, "ctc_topn: launch");
+  HIPCHK(hipGetLastError());
+  return QASR_OK;
+}
+
+static int beam_shape_ok(int B, int T, int W) {
+  return B >= 1 && T >= 1 && T <= QASR_BEAM_MAX_FRAMES && W >= 1 && W <= QASR_BEAM_MAX_WIDTH && (int64_t)B * T < (1ll << 31);
+}
+
+size_t qasr_ctc_beam_workspace_bytes(int B, int T, int beam_width) {
+  return beam_shape_ok(B, T, beam_width) ? beam_workspace_bytes(B, T, beam_width) : 0;
+}
+
+int qasr_ctc_beam(void* stream, const qasr_ctc_beam_args* a) {
+  if (!a) return fail(QASR_ERR_ARG, "ctc_beam: args is NULL");
+  if (a->struct_size != sizeof(qasr_ctc_beam_args))
+    return fail(QASR_ERR_ARG, "ctc_beam: struct_size %u is not %zu", a->struct_size, sizeof(qasr_ctc_beam_args));
+  if (!a->cand_id || !a->cand_q || !a->lae_table || !a->workspace || !a->labels || !a->n_labels || !a->score || !a->n_hyps)
+    return fail(QASR_ERR_ARG, "ctc_beam: a required pointer is NULL (only lens is optional)");
+  if (!beam_shape_ok(a->B, a->T, a->beam_width))
+    return fail(QASR_ERR_ARG, "ctc_beam: B %d, T %d (1 .. %d) or beam_width %d (1 .. %d) out of range", a->B, a->T,
+                QASR_BEAM_MAX_FRAMES, a->beam_width, QASR_BEAM_MAX_WIDTH);
+  if (a->N < 1 || a->N > QASR_BEAM_MAX_CANDIDATES)
+    return fail(QASR_ERR_ARG, "ctc_beam: N %d is outside 1 .. %d", a->N, QASR_BEAM_MAX_CANDIDATES);
+  if (a->n_best < 1 || a->n_best > a->beam_width || a->blank < 0)
+    return fail(QASR_ERR_ARG, "ctc_beam: n_best %d is outside 1 .. beam_width, or blank %d < 0", a->n_best, a->blank);
+  if (a->lae_entries != QASR_BEAM_TABLE_ENTRIES)
+    return fail(QASR_ERR_ARG, "ctc_beam: lae_entries %u is not %d", a->lae_entries, QASR_BEAM_TABLE_ENTRIES);
+  const size_t need = beam_workspace_bytes(a->B, a->T, a->beam_width);
+  if (a->workspace_bytes < need) return fail(QASR_ERR_ARG, "ctc_beam: workspace of %zu bytes, %zu needed", a->workspace_bytes, need);
+  int rc = launch_beam((hipStream_t)stream, *a);
+  if (rc) return fail(rc, "ctc_beam: launch");
+  HIPCHK(hipGetLastError());
+  return QASR_OK;
+}
+
 int qasr_engine_attach_ctc(qasr_engine* e, float* frame_score, const qasr_ctc_out* out, int use_lens) {
   if (!e) return fail(QASR_ERR_ARG, "attach_ctc: engine is NULL");
   if (frame_score || out) {

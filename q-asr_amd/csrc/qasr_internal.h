@@ -159,6 +159,10 @@ int launch_decoder_wide(hipStream_t s, const SepP& p, float* logp, int32_t* toke
 // t_act (reserved engines, device): the batch's own frame count; rows keep the pitch T
 int launch_ctc(hipStream_t s, const int32_t* tokens, const float* frame_score, const int32_t* lens, int B, int T, int blank,
                const qasr_ctc_out& out, const int32_t* t_act = nullptr);
+// qasr_beam.hip: CTC prefix beam search (k_topn, k_beam); the arguments are checked by the callers in qasr_engine.hip
+int launch_topn(hipStream_t s, const qasr_ctc_topn_args& a);
+size_t beam_workspace_bytes(int B, int T, int W);
+int launch_beam(hipStream_t s, const qasr_ctc_beam_args& a);
 // qasr_ragged.hip: the bucket policy of reserved engines and their one eager launch per call (k_ragged_stage)
 #define QASR_RAGGED_TILE 128          /* every bucket edge is a multiple of the largest frame tile */
 #define QASR_SHAPE_B 0                /* shape block, i32: rows of the batch, */

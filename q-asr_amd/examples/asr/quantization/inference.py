@@ -60,7 +60,12 @@ def main():
     p.add_argument("--timestamps", action='store_true',
                    help="(extension) also decode every batch with EncDecCTCModel.decode: word times and confidences "
                         "(`words`, `utt_score` per utterance in the --dump_hyps JSON); hypotheses and WER are unchanged")
+    p.add_argument("--beam_width", type=int, default=None, metavar='W',
+                   help="(extension) CTC prefix beam search of width W (1 .. 128, no language model) instead of the arg-max: "
+                        "hypotheses and WER come from the beam (EncDecCTCModel.decode(beam_width=W)); --dump_hyps gains `beam_score`")
     args = p.parse_args()
+    if args.beam_width is not None and not 1 <= args.beam_width <= 128:
+        p.error(f'--beam_width must be 1 .. 128, got {args.beam_width}')
     torch.set_grad_enabled(False)
 
     if args.asr_model.endswith('.nemo'):
@@ -114,14 +119,19 @@ def main():
         asr_model.reserve(args.batch_size, args.reserve)
     labels_map = dict(enumerate(asr_model.decoder.vocabulary))
     wer = WER(vocabulary=asr_model.decoder.vocabulary)
-    hyps, refs, words, utt_scores = [], [], [], []
+    hyps, refs, words, utt_scores, beam_scores = [], [], [], [], []
     audio_s, t0 = 0.0, time.time()
     for i, batch in enumerate(asr_model.test_dataloader()):
         if i == args.eval_early_stop:
             break
         batch = [x.cuda() for x in batch]
-        log_probs, enc_len, greedy = asr_model(input_signal=batch[0].float(), input_signal_length=batch[1])
-        hyps += wer.ctc_decoder_predictions_tensor(greedy)
+        if args.beam_width is not None:                      # k_topn + k_beam behind the forward, on the same stream
+            for h in asr_model.decode(input_signal=batch[0].float(), input_signal_length=batch[1], beam_width=args.beam_width):
+                hyps.append(h.text)
+                beam_scores.append(h.utt_score)
+        else:
+            log_probs, enc_len, greedy = asr_model(input_signal=batch[0].float(), input_signal_length=batch[1])
+            hyps += wer.ctc_decoder_predictions_tensor(greedy)
         if args.timestamps:                                  # device-side collapse up to each utterance's encoded length
             for h in asr_model.decode(input_signal=batch[0].float(), input_signal_length=batch[1]):
                 words.append([list(w) for w in h.words])
@@ -140,6 +150,8 @@ def main():
         import json
         with open(args.dump_hyps, 'w') as f:
             extra = dict(words=words, utt_score=utt_scores) if args.timestamps else {}
+            if args.beam_width is not None:
+                extra.update(beam_width=args.beam_width, beam_score=beam_scores)
             json.dump(dict(hypotheses=hyps, references=refs, wer=wer_value, path=served, **extra), f)
     print(f'RTFx (incl. host data loading): {audio_s / max(wall, 1e-9):.1f}  ({audio_s:.1f} s audio in {wall:.2f} s)')
 

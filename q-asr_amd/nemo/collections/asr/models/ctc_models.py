@@ -431,16 +431,53 @@ class EncDecCTCModel(nn.Module):
         return qctc.seconds_per_frame(qconfigs.topology_from_config(self.cfg), f.hop_length / float(self.preprocessor._sample_rate))
 
     @torch.no_grad()
-    def decode(self, input_signal=None, input_signal_length=None, processed_signal=None, processed_signal_length=None):
+    def decode(self, input_signal=None, input_signal_length=None, processed_signal=None, processed_signal_length=None,
+               beam_width=None, n_best=1, cutoff_top_n=40):
         """Greedy CTC hypotheses of one batch (an extension of the reference's API): List[qasr.ctc.Hypothesis] with the
         text, every label's start / end time and confidence (best frame log-probability of its run), word groups and the
         log-probability of the greedy path.  Decoding stops at each utterance's encoded length.  On the static engine the
         collapse (k_ctc) and the per-frame scores ride inside the engine's call on persistent buffers - no log-prob tensor
         is written; on the dynamic device path and the host modules the scores are log_probs gathered at the tokens,
-        collapsed by qasr_ctc_collapse (cuda) or qasr.ctc.collapse_host (cpu)."""
+        collapsed by qasr_ctc_collapse (cuda) or qasr.ctc.collapse_host (cpu).
+
+        beam_width=W (1 .. 128) replaces the greedy collapse by a CTC prefix beam search without a language model
+        (qasr.beam): the forward runs with log-probabilities, then k_topn (the cutoff_top_n <= 64 best classes per frame)
+        and k_beam follow on the same stream - on the static engine, a reserved engine and the dynamic path alike; the host
+        modules run the NumPy twin.  The hypotheses carry text, labels and utt_score (the beam score); their time lists are
+        empty, since a prefix has no single alignment.  n_best > 1 (<= W) returns, per utterance, the list of its best
+        hypotheses, best first."""
         from qasr import ctc as qctc
+        if beam_width is not None:
+            beam_width, n_best, cutoff_top_n = self._beam_args(beam_width, n_best, cutoff_top_n)      # refused before any launch
+            return self._beam_decode(self._forward(input_signal, input_signal_length, processed_signal, processed_signal_length),
+                                     beam_width, n_best, cutoff_top_n)
         res = self._forward(input_signal, input_signal_length, processed_signal, processed_signal_length, decode=True)
         return qctc.to_hypotheses(res, self.decoder.vocabulary, self.seconds_per_frame())
+
+    @staticmethod
+    def _beam_args(beam_width, n_best, cutoff_top_n):
+        from qasr import beam as qbeam
+        beam_width, n_best, cutoff_top_n = int(beam_width), int(n_best), int(cutoff_top_n)
+        if not 1 <= beam_width <= qbeam.MAX_W:
+            raise ValueError(f'decode: beam_width must be 1 .. {qbeam.MAX_W}, got {beam_width}')
+        if not 1 <= cutoff_top_n <= qbeam.MAX_N:
+            raise ValueError(f'decode: cutoff_top_n must be 1 .. {qbeam.MAX_N}, got {cutoff_top_n}')
+        if not 1 <= n_best <= beam_width:
+            raise ValueError(f'decode: n_best must be 1 .. beam_width, got {n_best}')
+        return beam_width, n_best, cutoff_top_n
+
+    def _beam_decode(self, fwd, beam_width, n_best, cutoff_top_n):
+        """decode(beam_width=) behind any path's (log_probs, encoded lengths, tokens); the arguments passed _beam_args"""
+        from qasr import beam as qbeam
+        log_probs, enc_len = fwd[0], fwd[1]
+        blank = len(self.decoder.vocabulary)
+        if log_probs.is_cuda:
+            from qasr import engine as qengine
+            res = qengine.ctc_beam_search(log_probs.float(), enc_len, blank, beam_width, n_best, cutoff_top_n)
+        else:
+            res = qbeam.search_host(log_probs.float().numpy(), enc_len.numpy(), blank, beam_width, n_best, cutoff_top_n)
+        hyps = qbeam.to_hypotheses(res, self.decoder.vocabulary)
+        return hyps if n_best > 1 else [h[0] for h in hyps]          # a beam over real candidates never dies: h[0] exists
 
     def _collapse(self, log_probs, tokens, enc_len):
         """decode() behind a path that returned log-probabilities: frame scores = log_probs at the tokens"""

@@ -16,7 +16,7 @@ SYMBOLS = ['qasr_blob_check', 'qasr_engine_create', 'qasr_engine_create_ex', 'qa
            'qasr_frontend_workspace_bytes', 'qasr_pw_conv_acc',
            'qasr_dw_conv_acc', 'qasr_dense_conv_acc', 'qasr_requant', 'qasr_dyn_range', 'qasr_dyn_range_percentile', 'qasr_dyn_residue_codes', 'qasr_dyn_act_params', 'qasr_dyn_requant',
            'qasr_dyn_quant_in', 'qasr_dyn_conv_params', 'qasr_sep_layer', 'qasr_quantile2', 'qasr_quantile_workspace_bytes', 'qasr_debug_prof',
-           'qasr_debug_timeline', 'qasr_ctc_collapse', 'qasr_engine_attach_ctc',
+           'qasr_debug_timeline', 'qasr_ctc_collapse', 'qasr_engine_attach_ctc', 'qasr_ctc_topn', 'qasr_ctc_beam_workspace_bytes', 'qasr_ctc_beam',
            'qasr_engine_reserve', 'qasr_engine_forward_ragged', 'qasr_engine_forward_ragged_audio', 'qasr_engine_ragged_stats',
            'qasr_ragged_bucket_frames', 'qasr_ragged_envelope_frames',
            'qasr_last_error', 'qasr_version']
@@ -143,6 +143,11 @@ def load_library():
     if hasattr(lib, 'qasr_ctc_collapse'):       # (a QASR_LIB A/B build of an older tree lacks them: calling them raises there)
         lib.qasr_ctc_collapse.argtypes = [vp, vp, vp, vp, i32, i32, i32, C.POINTER(CtcOut)]
         lib.qasr_engine_attach_ctc.argtypes = [vp, vp, C.POINTER(CtcOut), i32]
+    if hasattr(lib, 'qasr_ctc_beam'):           # (likewise)
+        lib.qasr_ctc_topn.argtypes = [vp, C.POINTER(TopnArgs)]
+        lib.qasr_ctc_beam.argtypes = [vp, C.POINTER(BeamArgs)]
+        lib.qasr_ctc_beam_workspace_bytes.argtypes = [i32, i32, i32]
+        lib.qasr_ctc_beam_workspace_bytes.restype = sz
     if hasattr(lib, 'qasr_engine_reserve'):     # (likewise)
         lib.qasr_engine_reserve.argtypes = [vp, C.POINTER(ReserveOpts)]
         lib.qasr_engine_forward_ragged.argtypes = [vp, vp, vp, vp, i32, i32, C.POINTER(RaggedOut)]
@@ -230,6 +235,114 @@ def ctc_collapse(tokens, frame_score=None, lens=None, blank=None, out=None, stre
                'qasr_ctc_collapse')
     out._keep = (tok, fs, ln)               # inputs stay alive until the stream has consumed them
     return out
+
+
+class TopnArgs(C.Structure):
+    """qasr_ctc_topn_args (include/qasr.h)"""
+    _fields_ = ([('struct_size', C.c_uint32)] + [(n, C.c_int32) for n in ('B', 'T', 'C', 'N')] +
+                [('pitch_utt', C.c_int64), ('pitch_frame', C.c_int64)] +
+                [(n, C.c_void_p) for n in ('log_probs', 'lens', 'cand_id', 'cand_q')])
+
+
+class BeamArgs(C.Structure):
+    """qasr_ctc_beam_args (include/qasr.h)"""
+    _fields_ = ([('struct_size', C.c_uint32)] + [(n, C.c_int32) for n in ('B', 'T', 'N', 'beam_width', 'n_best', 'blank')] +
+                [('lae_entries', C.c_uint32)] + [(n, C.c_void_p) for n in ('cand_id', 'cand_q', 'lens', 'lae_table', 'workspace')] +
+                [('workspace_bytes', C.c_size_t)] + [(n, C.c_void_p) for n in ('labels', 'n_labels', 'score', 'n_hyps')])
+
+
+_lae_tables = {}
+
+
+def lae_table_device(device):
+    """qasr.beam.lae_table() on `device` (its 16384 u16 entries as an int16 tensor), uploaded once per device ('cuda' and
+    'cuda:N' of the current device share one copy).  The upload is a host-to-device copy on the current stream: the first
+    ctc_beam of a device must therefore run outside a stream capture (or call this first); later calls only launch."""
+    from . import beam
+    dev = torch.device(device)
+    if dev.type == 'cuda' and dev.index is None:
+        dev = torch.device('cuda', torch.cuda.current_device())
+    t = _lae_tables.get(dev)
+    if t is None:
+        t = _lae_tables[dev] = torch.from_numpy(beam.lae_table().view(np.int16).copy()).to(dev)
+    return t
+
+
+def ctc_topn(log_probs, lens=None, n=40, out=None, stream=None):
+    """qasr_ctc_topn: each frame's min(n, C) best classes of a cuda float32 tensor [B, T, C] (any utterance / frame pitch,
+    classes contiguous) as (cand_id, cand_q), int32 [B, T, n], best first: k_topn, one launch on the current stream; equal
+    to qasr.beam.topn_host byte for byte.  lens int32 [B] optional; `out`: a caller-owned (cand_id, cand_q) pair."""
+    lib = load_library()
+    assert log_probs.is_cuda and log_probs.dim() == 3 and log_probs.dtype == torch.float32, \
+        'ctc_topn: log_probs must be a cuda float32 tensor [B, T, C]'
+    dev = log_probs.device
+    lp = log_probs if log_probs.stride(2) == 1 or log_probs.shape[2] == 1 else log_probs.contiguous()
+    ln = None if lens is None else lens.to(device=dev, dtype=torch.int32).contiguous()
+    B, T, Cn = lp.shape
+    if out is None:
+        out = (torch.empty(B, T, int(n), device=dev, dtype=torch.int32), torch.empty(B, T, int(n), device=dev, dtype=torch.int32))
+    cid, cq = out
+    for t in out:
+        assert t.is_cuda and t.is_contiguous() and t.dtype == torch.int32 and tuple(t.shape) == (B, T, int(n)), 'ctc_topn: out'
+    a = TopnArgs()
+    a.struct_size = C.sizeof(TopnArgs)
+    a.B, a.T, a.C, a.N = B, T, Cn, int(n)
+    a.pitch_utt, a.pitch_frame = (lp.stride(0) if B > 1 else max(lp.stride(0), T * lp.stride(1))), lp.stride(1)
+    a.log_probs, a.lens, a.cand_id, a.cand_q = lp.data_ptr(), 0 if ln is None else ln.data_ptr(), cid.data_ptr(), cq.data_ptr()
+    with torch.cuda.device(dev):
+        _check(lib.qasr_ctc_topn(_stream_ptr(stream), C.byref(a)), 'qasr_ctc_topn')
+    cid._keep = (lp, ln)
+    return cid, cq
+
+
+def ctc_beam_workspace_bytes(B, T, beam_width):
+    return int(load_library().qasr_ctc_beam_workspace_bytes(int(B), int(T), int(beam_width)))
+
+
+def ctc_beam(cand_id, cand_q, lens=None, blank=None, beam_width=16, n_best=None, workspace=None, out=None, stream=None):
+    """qasr_ctc_beam: CTC prefix beam search over the candidates of ctc_topn (cuda int32 [B, T, N]) on the device (k_beam,
+    one launch on the current stream, no host synchronisation); equal to qasr.beam.beam_search_host byte for byte.  Returns
+    a qasr.beam.BeamResult of cuda tensors.  workspace: a caller-owned uint8 tensor of ctc_beam_workspace_bytes(B, T, W)
+    bytes (None: allocated by torch here); `out`: a caller-owned BeamResult."""
+    from .beam import BeamResult, TAB_ENTRIES
+    lib = load_library()
+    if blank is None:
+        raise ValueError('ctc_beam: blank is required (the decoder\'s last class)')
+    assert cand_id.is_cuda and cand_id.dim() == 3 and cand_id.shape == cand_q.shape, 'ctc_beam: candidates must be cuda [B, T, N]'
+    dev = cand_id.device
+    cid, cq = cand_id.to(torch.int32).contiguous(), cand_q.to(device=dev, dtype=torch.int32).contiguous()
+    ln = None if lens is None else lens.to(device=dev, dtype=torch.int32).contiguous()
+    B, T, N = cid.shape
+    W = int(beam_width)
+    nb = W if n_best is None else int(n_best)
+    if out is None:
+        shape = (B, max(nb, 0))
+        out = BeamResult(labels=torch.empty(*shape, T, device=dev, dtype=torch.int32),
+                         n_labels=torch.empty(*shape, device=dev, dtype=torch.int32),
+                         score=torch.empty(*shape, device=dev, dtype=torch.int64),
+                         n_hyps=torch.empty(B, device=dev, dtype=torch.int32), blank=int(blank))
+    if workspace is None:
+        workspace = torch.empty(max(ctc_beam_workspace_bytes(B, T, W), 8), device=dev, dtype=torch.uint8)
+    tab = lae_table_device(dev)
+    a = BeamArgs()
+    a.struct_size = C.sizeof(BeamArgs)
+    a.B, a.T, a.N, a.beam_width, a.n_best, a.blank = B, T, N, W, nb, int(blank)
+    a.lae_entries = TAB_ENTRIES
+    a.cand_id, a.cand_q, a.lens, a.lae_table = cid.data_ptr(), cq.data_ptr(), 0 if ln is None else ln.data_ptr(), tab.data_ptr()
+    a.workspace, a.workspace_bytes = workspace.data_ptr(), workspace.numel() * workspace.element_size()
+    a.labels, a.n_labels, a.score, a.n_hyps = (out.labels.data_ptr(), out.n_labels.data_ptr(), out.score.data_ptr(),
+                                               out.n_hyps.data_ptr())
+    with torch.cuda.device(dev):
+        _check(lib.qasr_ctc_beam(_stream_ptr(stream), C.byref(a)), 'qasr_ctc_beam')
+    out._keep = (cid, cq, ln, workspace, tab)
+    return out
+
+
+def ctc_beam_search(log_probs, lens=None, blank=None, beam_width=16, n_best=None, cutoff_top_n=40, stream=None):
+    """k_topn + k_beam on the same stream: the device form of qasr.beam.search_host (blank None: the last class)"""
+    blank = log_probs.shape[-1] - 1 if blank is None else blank
+    cid, cq = ctc_topn(log_probs, lens, cutoff_top_n, stream=stream)
+    return ctc_beam(cid, cq, lens, blank, beam_width, n_best, stream=stream)
 
 
 class Engine:
