@@ -160,7 +160,8 @@ void qasr_engine_destroy(qasr_engine* e);
  * the caller's header (a shorter, older struct is accepted: missing fields take their defaults; a longer one is refused).
  * Two engines in one process are configured independently of each other through this call.
  * Environment variables remain ONLY as A/B overrides for profiling runs of an unmodified caller, read once per create
- * call AFTER the options: QASR_TILE128=0|1 (128-frame tiles when tile_frames >= 64), QASR_RES_TILE128, QASR_DENSE_TILE128,
+ * call AFTER the options: QASR_TILE128=0|1 (128-frame tiles when tile_frames >= 64), QASR_RES_TILE128=0|1 (res_tile128),
+ * QASR_RES_TILE=32|64|128 (the block-end tile itself, read after QASR_RES_TILE128; 32 has no option value), QASR_DENSE_TILE128,
  * QASR_SEP_GEN=1|2, QASR_NO_FUSE, QASR_NO_FUSE_STEM, QASR_NO_FUSE_DEC, QASR_WIDE_TILES, QASR_NO_FUSE_NORM; QASR_SEP2_TUNE is a kernel-internal experiment knob (csrc/qasr_sep2_impl.h). */
 typedef struct qasr_engine_opts {
   uint32_t struct_size;
@@ -175,7 +176,11 @@ typedef struct qasr_engine_opts {
                                   classes, two (k_decw) for 33 .. 8192; 0: the generic k_sep logits + k_logsoftmax */
   int32_t graph;               /* replay the forward as one hipGraph launch (second call with the same buffers captures) */
   int32_t retired_whole_utterance; /* round 1's k_utt kernels, removed in round 4: must be <= 0 */
-  int32_t res_tile128;         /* block-end (residual) layers on 128-frame tiles too when tile_frames == 128 */
+  int32_t res_tile128;         /* block-end (residual) layers of a tile_frames == 128 engine: 1 = on 128-frame tiles too, 0 = on
+                                  64-frame tiles.  Default (-1): by the hardware queues of the process, GPU_MAX_HW_QUEUES read
+                                  with getenv per create call as a hint (unset or unparsable: 4, HIP's default): 8 or more - a
+                                  queue for each of four streams, four launch chains side by side - 128; fewer - streams share
+                                  queues, two chains at a time - 64.  The plain layers stay on tile_frames */
   int32_t dense_tile128;       /* Jasper's plain dense convs on 128-frame tiles when tile_frames >= 64 */
   int32_t retired_legacy_pw;   /* round 1's k_pw, removed in round 4: must be <= 0 */
   int32_t retired_persistent;  /* round 3's persistent per-utterance launch (built, bit-exact, measured slower: DESIGN.md closed

@@ -109,7 +109,8 @@ struct qasr_engine {
   void* decw_ws = nullptr;             // k_decw's per-(frame, class group) partials: part of the plan (no allocation in forward)
   size_t decw_ws_bytes = 0;
   bool tile128 = true;                 // tile_frames == 128 (QASR_TILE128=0: k_sep2's plain layers stay on 64-frame tiles, A/B runs)
-  bool res_tile128 = true;             // block-end layers on 128-frame tiles too (qasr_engine_opts.res_tile128)
+  int res_tile = 128;                  // frames per work-group of the block-end layers of a tile_frames == 128 engine: 128, 64 or 32
+                                       // (qasr_engine_opts.res_tile128; its default goes by res_tile_default())
   bool dense_tile128 = true;           // QASR_DENSE_TILE128=0 keeps Jasper's dense convs on 64-frame tiles (A/B runs)
   bool wide_tiles = false;             // k_sep with 64-frame tiles (throughput mode: bit 3 of `debug`, or QASR_WIDE_TILES=1)
   int mask_skip = -1;                  // k_sep2s (mask-skip rule): -1 = when reserved, 0 = never, 1 = always (qasr_engine_opts.mask_skip)
@@ -441,6 +442,24 @@ void qasr_engine_default_opts(qasr_engine_opts* o) {
   o->fuse_dw = o->fuse_stem = o->fuse_decoder = o->res_tile128 = o->dense_tile128 = o->fuse_norm = o->mask_skip = -1;
 }
 
+// Block-end tile of a tile_frames == 128 engine when the caller leaves qasr_engine_opts.res_tile128 at -1.  What decides is how
+// many launch chains run side by side, and the one thing the engine can know about that is the process's hardware queue count:
+// HIP spreads a process's streams over GPU_MAX_HW_QUEUES queues (4 when unset), and four streams on fewer than
+// QASR_SIDE_BY_SIDE_QUEUES queues run pairwise.  Two chains of 64-work-group launches leave half the CUs without a work-group
+// and the step pays each chain's own latency: the block-end layers then take the smaller tile (more, shorter work-groups).
+// With a queue per chain four chains fill the chip and the 128-frame tile is the cheaper one.
+#define QASR_SIDE_BY_SIDE_QUEUES 8      /* smallest tested count (4, 8) at which four streams' chains ran side by side */
+#define QASR_RES_TILE_FEW_CHAINS 64     /* two chains in flight, ms/step: 128 frames 0.584, 64 frames 0.543 - 0.550, 32 frames 0.551 - 0.558 */
+static int res_tile_default() {
+  long q = 4;                                               // HIP's own default
+  if (const char* g = getenv("GPU_MAX_HW_QUEUES")) {
+    char* end = nullptr;
+    const long v = strtol(g, &end, 10);
+    if (end != g && v >= 1) q = v;
+  }
+  return q >= QASR_SIDE_BY_SIDE_QUEUES ? 128 : QASR_RES_TILE_FEW_CHAINS;
+}
+
 // the `debug` bits of round 1 / 2 callers, as options
 int qasr_engine_create(const void* blob, size_t n, int device, int debug, qasr_engine** out) {
   qasr_engine_opts o;
@@ -486,7 +505,7 @@ int qasr_engine_create_ex(const void* blob, size_t n, int device, const qasr_eng
   e->fuse_norm = tri(o.fuse_norm, true);
   e->wide_tiles = o.tile_frames >= 64;
   e->tile128 = o.tile_frames == 128;
-  e->res_tile128 = tri(o.res_tile128, true);
+  e->res_tile = o.res_tile128 < 0 ? res_tile_default() : (o.res_tile128 ? 128 : 64);
   e->dense_tile128 = tri(o.dense_tile128, true);
   e->sep_gen = o.sep_gen == 1 ? 1 : 2;
   e->mask_skip = o.mask_skip < 0 ? -1 : (o.mask_skip != 0);
@@ -495,7 +514,11 @@ int qasr_engine_create_ex(const void* blob, size_t n, int device, const qasr_eng
   if (getenv("QASR_NO_FUSE")) e->fuse = false;
   if (getenv("QASR_WIDE_TILES")) { e->wide_tiles = true; e->tile128 = true; }
   if (const char* g = getenv("QASR_TILE128")) e->tile128 = atoi(g) != 0;
-  if (const char* g = getenv("QASR_RES_TILE128")) e->res_tile128 = atoi(g) != 0;
+  if (const char* g = getenv("QASR_RES_TILE128")) e->res_tile = atoi(g) != 0 ? 128 : 64;
+  if (const char* g = getenv("QASR_RES_TILE")) {
+    const int v = atoi(g);
+    if (v == 32 || v == 64 || v == 128) e->res_tile = v;
+  }
   if (const char* g = getenv("QASR_NO_FUSE_DEC")) e->fuse_dec = atoi(g) == 0;
   if (const char* g = getenv("QASR_NO_FUSE_STEM")) e->fuse_stem = atoi(g) == 0;
   if (const char* g = getenv("QASR_NO_FUSE_NORM")) e->fuse_norm = atoi(g) == 0;
@@ -610,7 +633,8 @@ static void build_sep(qasr_engine* e, uint32_t oi, SepP& p) {
   p.n_panes = (int)op.n_panes;
   p.tile = e->wide_tiles ? (e->tile128 ? 128 : 64) : 32;   // 128: k_sep2's separable layers only (sep2_tile), everything else 64
   p.etile = p.tile;
-  if (p.tile == 128 && !e->res_tile128 && (op.flags & QASR_F_RESADD)) p.tile = 64;
+  // block-end layers: the engine's own tile (32 only for the separable form: dense and bare 1x1 block ends have 64 as their smallest)
+  if (p.tile == 128 && (op.flags & QASR_F_RESADD)) p.tile = (e->res_tile == 32 && e->fused_dw[oi] < 0) ? 64 : e->res_tile;
   p.gen = e->sep_gen;
   p.mask_skip = e->mask_skip < 0 ? e->rs.on : e->mask_skip != 0;
   fill_panes(e, oi, op, p.panes);

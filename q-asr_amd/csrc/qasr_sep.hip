@@ -29,7 +29,8 @@ bool sep2_takes(const SepP& p) { return p.gen == 2 && sep2_shape_ok(p); }
 // (throughput mode: every weight fragment then feeds four frame tiles, B * Tp / 128 work-groups per launch), else the
 // engine's 32 / 64.  The block-end (residual) layers too: with the decoder and the stem fused it is 0.417 vs 0.424 ms per step
 // and steadier (four 64-work-group launches fit the chip side by side, four 128-work-group ones queue);
-// qasr_engine_opts.res_tile128 = 0 keeps them on 64 (the engine then hands those ops over with tile = 64)
+// that holds with four chains side by side; with two at a time 64 frames win (0.543 vs 0.584): the engine decides per create call
+// (res_tile_default in qasr_engine.hip, or qasr_engine_opts.res_tile128 = 0 / 1) and hands those ops over with tile = 64 / 32
 static int sep2_tile(const SepP& p) {
   if (p.tile == 128) return (p.K > 0 && p.e.Tp % 128 == 0) ? 128 : 64;
   if (p.K > 0 && p.dilation == 2) return 64;                 // the dilation-2 form has no 32-frame instantiation (16 samples per parity)
