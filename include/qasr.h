@@ -353,6 +353,48 @@ typedef struct qasr_ctc_beam_args {
 size_t qasr_ctc_beam_workspace_bytes(int B, int T, int beam_width);
 int qasr_ctc_beam(void* stream, const qasr_ctc_beam_args* args);
 
+/* ---- CTC prefix beam search with a back-off n-gram language model --------------------------------------------------------
+ * The search above with the shallow fusion of ctc_decoders' Scorer, in fixed point: every extension of a prefix by a label
+ * adds term = ((raw * alpha_q + 2^15) >> 16) + beta_q, raw = the model's log-probability of the token that the label
+ * completes (character mode: the label itself; word mode, space >= 0: the word that a space ends) in units of 2^-16 nat,
+ * walked through the packed model of qasr/ngram.py (context nodes with back-offs, an open-addressed transition table, a
+ * word-hash table).  The rules are LM_RULES of qasr/beam.py, which k_beam_lm follows bit for bit.  lm_score i64 [B][n_best]
+ * receives each hypothesis' sum of terms (unused rows 0); score includes it.
+ * qasr_lm_check validates a packed model ON THE HOST (no GPU is touched): QASR_OK, or QASR_ERR_BLOB (qasr_last_error names
+ * the field) for a bad magic, version, size, order (1 .. QASR_LM_MAX_ORDER) or mode, an n_labels other than the caller's, a
+ * capacity that is no power of two, a probe bound outside 1 .. QASR_LM_MAX_PROBE, level offsets that do not ascend, a
+ * node / word / next index out of range, a value beyond +-2^30, a suffix that does not lie exactly one level below its node,
+ * or a stored key that its probe sequence does not reach.  The kernel trusts `lm`: pass only the bytes that passed.
+ * qasr_ctc_beam_lm: QASR_ERR_ARG with nothing launched and no output written for everything qasr_ctc_beam refuses, and
+ * for a NULL or unaligned (16 bytes) lm, lm_bytes < 128, alpha_q outside 0 .. 16 * 2^16, |beta_q| > 16 * 2^16,
+ * space < -1 or space == blank, a NULL lm_score. */
+#define QASR_LM_MAX_ORDER 6
+#define QASR_LM_MAX_PROBE 1024
+#define QASR_LM_MAX_WEIGHT (16 << 16)
+int qasr_lm_check(const void* blob, size_t bytes, int n_labels);
+typedef struct qasr_ctc_beam_lm_args {
+  uint32_t struct_size;
+  int32_t B, T, N, beam_width, n_best, blank;
+  uint32_t lae_entries;        /* QASR_BEAM_TABLE_ENTRIES */
+  const int32_t* cand_id;
+  const int32_t* cand_q;
+  const int32_t* lens;         /* optional */
+  const uint16_t* lae_table;
+  void* workspace;             /* qasr_ctc_beam_workspace_bytes(B, T, beam_width) */
+  size_t workspace_bytes;
+  int32_t* labels;
+  int32_t* n_labels;
+  int64_t* score;
+  int32_t* n_hyps;
+  const void* lm;              /* device memory: a packed model that passed qasr_lm_check */
+  size_t lm_bytes;
+  int32_t alpha_q, beta_q;     /* rint(alpha * 2^16), rint(beta * 2^16) */
+  int32_t space;               /* the label that ends a word; -1: character mode (must agree with the model's mode) */
+  int32_t reserved;
+  int64_t* lm_score;
+} qasr_ctc_beam_lm_args;
+int qasr_ctc_beam_lm(void* stream, const qasr_ctc_beam_lm_args* args);
+
 /* ---- reserved engines: ragged batches without allocation, with graph replay ------------------------------------------
  * A data loader pads every batch to its own longest utterance (the reference's collate function), so (B, T) changes on
  * almost every call; qasr_engine_forward[_audio] then rebuilds its plan (device-synchronising frees + allocations) and,

@@ -1,5 +1,5 @@
-// CTC prefix beam search without a language model, in fixed point (the host statement is qasr/beam.py; this file
-// follows it bit for bit): k_topn picks each frame's N best classes out of float32 log-probabilities, k_beam runs the
+// CTC prefix beam search in fixed point, without a language model (k_beam) and with one (k_beam_lm, at the end of the file);
+// the host statement is qasr/beam.py, and this file follows it bit for bit: k_topn picks each frame's N best classes out of float32 log-probabilities, k_beam runs the
 // search over those candidates.  Scores are int64 sums of q = rint(logp * 2^16); the only non-linear step is a look-up in
 // the log-add-exp table the caller passes in (16384 x u16, LDS resident), so neither kernel calls exp or log and the
 // results do not depend on thread order.
@@ -445,6 +445,410 @@ int launch_beam(hipStream_t s, const qasr_ctc_beam_args& a) {
   p.labels = a.labels, p.n_labels = a.n_labels, p.score = (long long*)a.score, p.n_hyps = a.n_hyps;
   p.B = a.B, p.T = a.T, p.N = a.N, p.W = a.beam_width, p.n_best = a.n_best, p.blank = a.blank;
   hipLaunchKernelGGL(k_beam, dim3((unsigned)a.B), dim3(BEAM_NT), 0, s, p);
+  return QASR_OK;
+}
+
+
+// --------------------------------------------------------------------------------------------------------- k_beam_lm
+// k_beam with the shallow fusion of a back-off n-gram model (LM_RULES of qasr/beam.py; the packed model is qasr/ngram.py's).
+// A kernel of its own, so that k_beam above stays as it is.  What differs: an entry also keeps its context node, the hash
+// of its current word, the term of its own creation (the E path reuses it) and the running sum of its terms; the frame's
+// terms are evaluated ONCE, before the selection - thread (slot, sub) walks the model for the candidates it scores anyway and
+// leaves raw in L.raw[slot][n] (character mode: up to W x N walks; word mode: the space candidate of each slot, <= W) - and
+// cand() adds ((raw * alpha_q + 2^15) >> 16) + beta_q.  A winner repeats its one walk for the next context.  The model stays
+// in global memory and is read with plain vector loads (one 16-byte slot per probe); every walk is bounded by the order and
+// the header's probe bounds.  After the last frame, word mode scores the unfinished word of every entry and re-orders.
+// With the table and raw[128][64] the state is about 93 KB of static LDS: gfx950 gives one work-group up to 160 KB.
+#define BEAM_LM_MAGIC 0x314D4C51
+#define BEAM_LM_OOV (-1000 * 65536)
+#define BEAM_LM_RAWLIM 2147483647ll
+#define BEAM_LM_NOTERM INT_MIN
+
+struct LmView {
+  const int4* trans;        // [tmask + 1] node, word, prob_q, next
+  const int4* words;        // [wmask + 1] hash lo, hash hi, word id, 0
+  const int2* nodes;        // [n_nodes] backoff_q, suffix
+  const int* l2w;           // [n_labels]
+  int order, tprobe, wprobe, n_labels;
+  unsigned tmask, wmask;
+};
+
+struct BeamLmP {
+  BeamP b;
+  const int* lm;
+  long long lm_bytes, alpha_q, beta_q;
+  long long* lm_score;      // [B][n_best]
+  int space;
+};
+
+struct BeamLmState {
+  BeamState s;
+  long long own[BEAM_W], lmt[BEAM_W];
+  unsigned long long wh[BEAM_W];
+  int ctx[BEAM_W];
+};
+
+struct BeamLmLds {
+  uint16_t tab[BEAM_TAB];
+  BeamLmState st[2];
+  long long k_pb[BEAM_W], k_pnb[BEAM_W], k_sc[BEAM_W];
+  unsigned long long sel_r[BEAM_W];
+  int sel_idx[BEAM_W];
+  unsigned long long child[BEAM_W];
+  int cid[BEAM_N], cq[BEAM_N];
+  unsigned hist[256];
+  long long red_max[BEAM_NWAVE], red_min[BEAM_NWAVE];
+  int red_cnt[BEAM_NWAVE], red_a[BEAM_NWAVE], red_b[BEAM_NWAVE];
+  int bin, kk, n_at, n_sel;
+  int raw[BEAM_W * BEAM_N];
+};
+
+// raw(ctx, w) and the context it leaves
+__device__ __forceinline__ int lm_walk(const LmView& m, int ctx, int w, int& next) {
+  next = 0;
+  if (w < 0) return BEAM_LM_OOV;
+  long long acc = 0;
+  int node = ctx;
+  for (int it = 0; it < m.order; ++it) {
+    unsigned long long x = (((unsigned long long)(unsigned)node << 32) | (unsigned long long)(unsigned)w) * BEAM_HMUL;
+    x ^= x >> 32;
+    unsigned s = (unsigned)x & m.tmask;
+    bool hit = false;
+    for (int pr = 0; pr < m.tprobe; ++pr) {
+      const int4 e = m.trans[s];
+      if (e.x == node && e.y == w) { acc += e.z; next = e.w; hit = true; break; }
+      if (e.x < 0) break;
+      s = (s + 1) & m.tmask;
+    }
+    if (hit) break;
+    const int2 nd = m.nodes[node];
+    acc += nd.x, node = nd.y;
+  }
+  acc = acc > BEAM_LM_RAWLIM ? BEAM_LM_RAWLIM : acc;
+  acc = acc < -BEAM_LM_RAWLIM ? -BEAM_LM_RAWLIM : acc;
+  return (int)acc;
+}
+
+// the word id of a label hash, -1: none
+__device__ __forceinline__ int lm_word(const LmView& m, unsigned long long h) {
+  unsigned s = (unsigned)h & m.wmask;
+  for (int pr = 0; pr < m.wprobe; ++pr) {
+    const int4 e = m.words[s];
+    if (e.z < 0) return -1;
+    if ((unsigned)e.x == (unsigned)h && (unsigned)e.y == (unsigned)(h >> 32)) return e.z;
+    s = (s + 1) & m.wmask;
+  }
+  return -1;
+}
+
+__global__ void __launch_bounds__(BEAM_NT) k_beam_lm(BeamLmP q) {
+  __shared__ BeamLmLds L;
+  const BeamP& p = q.b;
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int b = blockIdx.x, T = p.T, N = p.N, W = p.W, N1 = N + 1, blank = p.blank;
+  const int lim = p.lens ? min(max(p.lens[b], 0), T) : T;
+  int2* const nodes = p.nodes + (size_t)b * T * W;
+  const int n_nodes = T * W;
+  // the model (validated on the host by qasr_lm_check); a header that does not fit the bytes given ends the search empty
+  const int* const hdr = q.lm;
+  LmView m;
+  m.order = hdr[2], m.tprobe = hdr[7], m.wprobe = hdr[10], m.n_labels = hdr[8];
+  m.tmask = (unsigned)hdr[6] - 1u, m.wmask = (unsigned)hdr[9] - 1u;
+  m.trans = reinterpret_cast<const int4*>(hdr + 32);
+  m.words = m.trans + (size_t)hdr[6];
+  m.nodes = reinterpret_cast<const int2*>(m.words + (size_t)hdr[9]);
+  m.l2w = reinterpret_cast<const int*>(m.nodes + (size_t)hdr[4]);
+  const bool word_mode = hdr[3] != 0;
+  const int space = q.space;
+  const long long alpha_q = q.alpha_q, beta_q = q.beta_q;
+  const bool model_ok = hdr[0] == BEAM_LM_MAGIC && (long long)hdr[12] == q.lm_bytes && word_mode == (space >= 0) &&
+                        hdr[5] >= 0 && hdr[5] < hdr[4] && m.order >= 1 && m.order <= 6;
+  auto lm_term = [&](int raw) -> long long {
+    return raw == BEAM_LM_NOTERM ? 0ll : ((((long long)raw * alpha_q + 32768ll) >> 16) + beta_q);
+  };
+  for (int i = tid; i < BEAM_TAB; i += BEAM_NT) L.tab[i] = p.tab[i];
+  if (tid == 0) {
+    BeamLmState& S0 = L.st[0];
+    BeamState& S = S0.s;
+    S.pb[0] = 0, S.pnb[0] = BEAM_NEG, S.sc[0] = 0, S.hash[0] = 0, S.phash[0] = 0, S.len[0] = 0, S.last[0] = -1, S.node[0] = -1;
+    S0.own[0] = 0, S0.lmt[0] = 0, S0.wh[0] = 0, S0.ctx[0] = model_ok ? hdr[5] : 0;
+  }
+  const int32_t* const gid = p.cand_id + (size_t)b * T * N;
+  const int32_t* const gq = p.cand_q + (size_t)b * T * N;
+  int pf_id = -1, pf_q = 0;
+  if (tid < N && lim > 0) pf_id = gid[tid], pf_q = gq[tid];
+  int nb = model_ok ? 1 : 0, cur = 0;
+  __syncthreads();
+  for (int t = 0; t < lim && nb > 0; ++t) {
+    const BeamLmState& SL = L.st[cur];
+    BeamLmState& DL = L.st[cur ^ 1];
+    const BeamState& S = SL.s;
+    BeamState& D = DL.s;
+    if (tid < N) {
+      L.cid[tid] = pf_id, L.cq[tid] = pf_q;
+      if (t + 1 < lim) pf_id = gid[(size_t)(t + 1) * N + tid], pf_q = gq[(size_t)(t + 1) * N + tid];
+    }
+    if (tid < nb) L.child[tid] = 0;
+    if (tid == 0) L.n_sel = 0;
+    __syncthreads();
+    // ---- the entries themselves (the E path adds the entry's own term)
+    if (tid < nb) {
+      const int j = tid, c = S.last[j], lj = S.len[j];
+      int nl = -1, nbk = -1;
+      for (int n = 0; n < N; ++n) {
+        const int id = L.cid[n];
+        if (id >= 0) {
+          if (id == blank && nbk < 0) nbk = n;
+          if (id == c && nl < 0) nl = n;
+        }
+      }
+      int ps = -1;
+      if (lj > 0) {
+        const unsigned long long ph = S.phash[j];
+        for (int i = nb - 1; i >= 0; --i)
+          ps = (S.hash[i] == ph && S.len[i] + 1 == lj) ? i : ps;
+      }
+      const long long pbn = nbk >= 0 ? S.sc[j] + (long long)L.cq[nbk] : BEAM_NEG;
+      long long a = BEAM_NEG, e = BEAM_NEG;
+      if (nl >= 0) {
+        const long long ql = (long long)L.cq[nl];
+        if (S.pnb[j] != BEAM_NEG) a = ql + S.pnb[j];
+        if (ps >= 0) {
+          const long long base = S.last[ps] == c ? S.pb[ps] : S.sc[ps];
+          if (base != BEAM_NEG) e = ql + base + SL.own[j];
+          atomicOr(&L.child[ps], 1ull << nl);
+        }
+      }
+      const long long pnbn = beam_lae(a, e, L.tab);
+      L.k_pb[j] = pbn, L.k_pnb[j] = pnbn, L.k_sc[j] = beam_lae(pbn, pnbn, L.tab);
+    }
+    __syncthreads();
+    const int lg = nb > 1 ? 32 - __clz(nb - 1) : 0;
+    const int tpr_lg = 8 - lg, tpr = 1 << tpr_lg;
+    const int my_i = tid >> tpr_lg, my_sub = tid & (tpr - 1);
+    const bool active = my_i < nb;
+    const int r_last = active ? S.last[my_i] : -1;
+    const long long r_pb = active ? S.pb[my_i] : BEAM_NEG, r_sc = active ? S.sc[my_i] : BEAM_NEG;
+    const long long r_ksc = active ? L.k_sc[my_i] : BEAM_NEG;
+    const unsigned long long r_child = active ? L.child[my_i] : 0ull;
+    const int k_end = active ? N1 : 0;
+    int* const my_raw = L.raw + my_i * N;             // my_i < 128: inside raw[BEAM_W * BEAM_N] since N <= BEAM_N
+    // ---- this frame's terms, once: the thread that scores candidate (my_i, n) below walks the model for it here
+    {
+      const int r_ctx = active ? SL.ctx[my_i] : 0;
+      const unsigned long long r_wh = active ? SL.wh[my_i] : 0ull;
+      const bool inword = r_last >= 0 && r_last != space;
+      for (int k = my_sub; k < k_end; k += tpr) {
+        if (k == 0) continue;
+        const int n = k - 1, id = L.cid[n];
+        int r = BEAM_LM_NOTERM, nx;
+        if (id >= 0 && id != blank && !((r_child >> n) & 1ull)) {
+          if (!word_mode) r = lm_walk(m, r_ctx, id < m.n_labels ? m.l2w[id] : -1, nx);
+          else if (id == space && inword) r = lm_walk(m, r_ctx, lm_word(m, r_wh), nx);
+        }
+        my_raw[n] = r;
+      }
+    }
+    auto cand = [&](int k) -> long long {
+      if (k == 0) return r_ksc;
+      const int n = k - 1, id = L.cid[n];
+      if (id < 0 || id == blank || ((r_child >> n) & 1ull)) return BEAM_NEG;
+      const long long base = id == r_last ? r_pb : r_sc;
+      return base == BEAM_NEG ? BEAM_NEG : base + (long long)L.cq[n] + lm_term(my_raw[n]);
+    };
+    long long mx = LLONG_MIN, mn = LLONG_MAX;
+    int cnt = 0;
+    for (int k = my_sub; k < k_end; k += tpr) {
+      const long long v = cand(k);
+      if (v != BEAM_NEG) { ++cnt; mx = v > mx ? v : mx; mn = v < mn ? v : mn; }
+    }
+#pragma unroll
+    for (int d = 32; d >= 1; d >>= 1) {
+      const long long omx = __shfl_xor(mx, d), omn = __shfl_xor(mn, d);
+      cnt += __shfl_xor(cnt, d);
+      mx = omx > mx ? omx : mx, mn = omn < mn ? omn : mn;
+    }
+    if (lane == 0) L.red_max[wave] = mx, L.red_min[wave] = mn, L.red_cnt[wave] = cnt;
+    __syncthreads();
+    mx = L.red_max[0], mn = L.red_min[0], cnt = L.red_cnt[0];
+#pragma unroll
+    for (int w = 1; w < BEAM_NWAVE; ++w) {
+      mx = L.red_max[w] > mx ? L.red_max[w] : mx, mn = L.red_min[w] < mn ? L.red_min[w] : mn;
+      cnt += L.red_cnt[w];
+    }
+    if (cnt == 0) { nb = 0; break; }
+    auto radix_select = [&](auto keyfn, int nbits, int& kk, int& n_at) -> unsigned long long {
+      const int passes = (nbits + 7) >> 3;
+      unsigned long long prefix = 0;
+      for (int pass = passes - 1; pass >= 0; --pass) {
+        const int shift = pass * 8;
+        __syncthreads();
+        L.hist[tid] = 0;
+        __syncthreads();
+        for (int k = my_sub; k < k_end; k += tpr) {
+          unsigned long long key;
+          if (keyfn(k, key) && (shift + 8 >= 64 || (key >> (shift + 8)) == prefix))
+            atomicAdd(&L.hist[(unsigned)(key >> shift) & 255u], 1u);
+        }
+        __syncthreads();
+        const int mine = (int)L.hist[tid];
+        int inc = mine;
+#pragma unroll
+        for (int d = 1; d < 64; d <<= 1) {
+          const int o = __shfl_up(inc, d);
+          if (lane >= d) inc += o;
+        }
+        if (lane == 63) L.red_a[wave] = inc;
+        __syncthreads();
+        for (int w = 0; w < wave; ++w) inc += L.red_a[w];
+        const int exc = inc - mine;
+        if (exc < kk && kk <= inc) L.bin = tid, L.kk = kk - exc, L.n_at = mine;
+        __syncthreads();
+        prefix = (prefix << 8) | (unsigned long long)L.bin;
+        kk = L.kk, n_at = L.n_at;
+      }
+      return prefix;
+    };
+    unsigned long long rth = ~0ull;
+    int ith = INT_MAX;
+    if (cnt > W) {
+      const unsigned long long range = (unsigned long long)(mx - mn);
+      int need = W, n_at = cnt;
+      rth = radix_select([&](int k, unsigned long long& key) {
+        const long long v = cand(k);
+        key = (unsigned long long)(mx - v);
+        return v != BEAM_NEG;
+      }, range ? 64 - __clzll((long long)range) : 0, need, n_at);
+      if (n_at > need) {
+        const int M = nb * N1;
+        ith = (int)radix_select([&](int k, unsigned long long& key) {
+          const long long v = cand(k);
+          key = (unsigned long long)(my_i * N1 + k);
+          return v != BEAM_NEG && (unsigned long long)(mx - v) == rth;
+        }, 32 - __clz(M), need, n_at);
+      }
+    }
+    for (int k = my_sub; k < k_end; k += tpr) {
+      const long long v = cand(k);
+      if (v != BEAM_NEG) {
+        const unsigned long long r = (unsigned long long)(mx - v);
+        const int idx = my_i * N1 + k;
+        if (r < rth || (r == rth && idx <= ith)) {
+          const int at = atomicAdd(&L.n_sel, 1);
+          if (at < BEAM_W) L.sel_r[at] = r, L.sel_idx[at] = idx;
+        }
+      }
+    }
+    __syncthreads();
+    const int ns = min(L.n_sel, W);
+    if (tid < ns) {
+      const unsigned long long r = L.sel_r[tid];
+      const int idx = L.sel_idx[tid];
+      int rank = 0;
+      for (int mm = 0; mm < ns; ++mm) {
+        const unsigned long long rm = L.sel_r[mm];
+        rank += (rm < r || (rm == r && L.sel_idx[mm] < idx)) ? 1 : 0;
+      }
+      const int i = idx / N1, k = idx - i * N1;
+      if (k == 0) {
+        D.pb[rank] = L.k_pb[i], D.pnb[rank] = L.k_pnb[i], D.sc[rank] = L.k_sc[i];
+        D.hash[rank] = S.hash[i], D.phash[rank] = S.phash[i], D.len[rank] = S.len[i], D.last[rank] = S.last[i];
+        D.node[rank] = S.node[i];
+        DL.own[rank] = SL.own[i], DL.lmt[rank] = SL.lmt[i], DL.wh[rank] = SL.wh[i], DL.ctx[rank] = SL.ctx[i];
+      } else {
+        const int c = L.cid[k - 1];
+        const long long v = mx - (long long)r;
+        unsigned long long x = (S.hash[i] ^ ((unsigned long long)(long long)c + 1ull)) * BEAM_HMUL;
+        x ^= x >> 32;
+        D.pb[rank] = BEAM_NEG, D.pnb[rank] = v, D.sc[rank] = v;
+        D.hash[rank] = x, D.phash[rank] = S.hash[i], D.len[rank] = S.len[i] + 1, D.last[rank] = c;
+        const int nd = t * W + rank;
+        D.node[rank] = nd;
+        nodes[nd] = make_int2(S.node[i], c);
+        const int raw = L.raw[i * N + k - 1];         // written before the barriers of the selection
+        const long long tm = lm_term(raw);
+        int ctx = SL.ctx[i];
+        unsigned long long wh = 0;
+        if (word_mode && c != space) {
+          wh = (SL.wh[i] ^ ((unsigned long long)(long long)c + 1ull)) * BEAM_HMUL;
+          wh ^= wh >> 32;
+        } else if (raw != BEAM_LM_NOTERM) {             // the token was scored: the one walk again, for its context
+          const int w = word_mode ? lm_word(m, SL.wh[i]) : (c < m.n_labels ? m.l2w[c] : -1);
+          lm_walk(m, SL.ctx[i], w, ctx);
+        }
+        DL.own[rank] = tm, DL.lmt[rank] = SL.lmt[i] + tm, DL.wh[rank] = wh, DL.ctx[rank] = ctx;
+      }
+    }
+    __syncthreads();
+    nb = ns, cur ^= 1;
+  }
+  __syncthreads();
+  // ---- word mode: the unfinished word of every entry, then the order (score descending, ties by the previous rank)
+  if (word_mode && nb > 0) {
+    const BeamLmState& SL = L.st[cur];
+    BeamLmState& DL = L.st[cur ^ 1];
+    long long sc = BEAM_NEG, lmt = 0;
+    if (tid < nb) {
+      sc = SL.s.sc[tid], lmt = SL.lmt[tid];
+      const int last = SL.s.last[tid];
+      if (last >= 0 && last != space) {
+        int nx;
+        const long long tm = lm_term(lm_walk(m, SL.ctx[tid], lm_word(m, SL.wh[tid]), nx));
+        sc += tm, lmt += tm;
+      }
+      L.k_sc[tid] = sc;
+    }
+    __syncthreads();
+    if (tid < nb) {
+      int rank = 0;
+      for (int mm = 0; mm < nb; ++mm) {
+        const long long sm = L.k_sc[mm];
+        rank += (sm > sc || (sm == sc && mm < tid)) ? 1 : 0;
+      }
+      DL.s.sc[rank] = sc, DL.lmt[rank] = lmt, DL.s.len[rank] = SL.s.len[tid], DL.s.node[rank] = SL.s.node[tid];
+    }
+    __syncthreads();
+    cur ^= 1;
+  }
+  // ---- the final beam, best first
+  const BeamLmState& SL = L.st[cur];
+  const BeamState& S = SL.s;
+  const int nh = min(nb, p.n_best);
+  int32_t* const lab = p.labels + (size_t)b * p.n_best * T;
+  for (int i = tid; i < p.n_best * T; i += BEAM_NT) lab[i] = blank;
+  if (tid == 0) p.n_hyps[b] = nh;
+  __syncthreads();
+  if (tid < p.n_best) {
+    const int h = tid;
+    int len = 0;
+    long long sc = BEAM_NEG, lmt = 0;
+    if (h < nh) {
+      len = min(S.len[h], T), sc = S.sc[h], lmt = SL.lmt[h];
+      int nd = S.node[h];
+      for (int k = len - 1; k >= 0; --k) {
+        if (nd < 0 || nd >= n_nodes) break;
+        const int2 e = nodes[nd];
+        lab[(size_t)h * T + k] = e.y;
+        nd = e.x;
+      }
+    }
+    p.n_labels[(size_t)b * p.n_best + h] = len;
+    p.score[(size_t)b * p.n_best + h] = sc;
+    q.lm_score[(size_t)b * p.n_best + h] = lmt;
+  }
+}
+
+int launch_beam_lm(hipStream_t s, const qasr_ctc_beam_lm_args& a) {
+  BeamLmP q{};
+  BeamP& p = q.b;
+  p.cand_id = a.cand_id, p.cand_q = a.cand_q, p.lens = a.lens, p.tab = a.lae_table;
+  p.nodes = (int2*)a.workspace;
+  p.labels = a.labels, p.n_labels = a.n_labels, p.score = (long long*)a.score, p.n_hyps = a.n_hyps;
+  p.B = a.B, p.T = a.T, p.N = a.N, p.W = a.beam_width, p.n_best = a.n_best, p.blank = a.blank;
+  q.lm = (const int*)a.lm, q.lm_bytes = (long long)a.lm_bytes, q.alpha_q = a.alpha_q, q.beta_q = a.beta_q;
+  q.lm_score = (long long*)a.lm_score, q.space = a.space;
+  static_assert(sizeof(BeamLmLds) <= 160 * 1024, "k_beam_lm: the LDS of one gfx950 CU");
+  hipLaunchKernelGGL(k_beam_lm, dim3((unsigned)a.B), dim3(BEAM_NT), 0, s, q);
   return QASR_OK;
 }
 

@@ -1076,6 +1076,102 @@ int qasr_ctc_beam(void* stream, const qasr_ctc_beam_args* a) {
   return QASR_OK;
 }
 
+// Host-only validation of a packed n-gram model (qasr/ngram.py states the layout); k_beam_lm trusts what passes here.
+int qasr_lm_check(const void* blob, size_t bytes, int n_labels) {
+  enum { HDR = 32 };
+  const int32_t LIM = 1 << 30;
+  if (!blob) return fail(QASR_ERR_BLOB, "lm_check: blob is NULL");
+  if (bytes < HDR * 4 || bytes > (size_t)INT32_MAX) return fail(QASR_ERR_BLOB, "lm_check: %zu bytes is no model", bytes);
+  if (((uintptr_t)blob & 3) != 0) return fail(QASR_ERR_BLOB, "lm_check: blob is not 4-byte aligned");
+  const int32_t* h = (const int32_t*)blob;
+  if (h[0] != 0x314D4C51 || h[1] != 1) return fail(QASR_ERR_BLOB, "lm_check: magic %#x / version %d", (unsigned)h[0], h[1]);
+  const int order = h[2], mode = h[3], n_nodes = h[4], start = h[5], tcap = h[6], tprobe = h[7], wcap = h[9], wprobe = h[10];
+  const int n_words = h[11];
+  const int32_t* level = h + 13;
+  if (order < 1 || order > QASR_LM_MAX_ORDER || (mode != 0 && mode != 1)) return fail(QASR_ERR_BLOB, "lm_check: order %d / mode %d", order, mode);
+  if (h[8] != n_labels || n_labels < 1) return fail(QASR_ERR_BLOB, "lm_check: packed for %d labels, asked for %d", h[8], n_labels);
+  if (n_nodes < 1 || n_words < 1 || start < 0 || start >= n_nodes)
+    return fail(QASR_ERR_BLOB, "lm_check: n_nodes %d, n_words %d or start %d out of range", n_nodes, n_words, start);
+  if (tcap < 1 || (tcap & (tcap - 1)) || wcap < 1 || (wcap & (wcap - 1)))
+    return fail(QASR_ERR_BLOB, "lm_check: capacities %d / %d are not powers of two", tcap, wcap);
+  if (tprobe < 1 || tprobe > QASR_LM_MAX_PROBE || tprobe > tcap || wprobe < 1 || wprobe > QASR_LM_MAX_PROBE || wprobe > wcap)
+    return fail(QASR_ERR_BLOB, "lm_check: probe bounds %d / %d outside 1 .. %d (or above the capacity)", tprobe, wprobe, QASR_LM_MAX_PROBE);
+  const uint64_t total = 4ull * HDR + 16ull * (uint64_t)tcap + 16ull * (uint64_t)wcap + 8ull * (uint64_t)n_nodes + 4ull * (uint64_t)n_labels;
+  if (total != (uint64_t)bytes || h[12] != (int32_t)bytes) return fail(QASR_ERR_BLOB, "lm_check: %zu bytes, the header describes %llu (total field %d)", bytes, (unsigned long long)total, h[12]);
+  for (int i = 21; i < HDR; ++i)
+    if (h[i] != 0) return fail(QASR_ERR_BLOB, "lm_check: reserved header word %d is %d", i, h[i]);
+  if (level[0] != 0 || level[1] != 1) return fail(QASR_ERR_BLOB, "lm_check: level[0 .. 1] = %d, %d", level[0], level[1]);
+  for (int k = 1; k < 8; ++k)
+    if (level[k] < level[k - 1] || level[k] > n_nodes || (k >= order && level[k] != n_nodes))
+      return fail(QASR_ERR_BLOB, "lm_check: level[%d] = %d does not ascend to n_nodes %d", k, level[k], n_nodes);
+  const int32_t* trans = h + HDR;
+  const int32_t* words = trans + 4 * (size_t)tcap;
+  const int32_t* nodes = words + 4 * (size_t)wcap;
+  const int32_t* l2w = nodes + 2 * (size_t)n_nodes;
+  int lv = 0;
+  for (int i = 0; i < n_nodes; ++i) {
+    while (lv < 7 && i >= level[lv + 1]) ++lv;                // node i has lv words
+    const int bo = nodes[2 * i], sf = nodes[2 * i + 1];
+    if (bo < -LIM || bo > LIM) return fail(QASR_ERR_BLOB, "lm_check: back-off %d of node %d beyond 2^30", bo, i);
+    const bool ok = lv == 0 ? sf == 0 : (sf >= level[lv - 1] && sf < level[lv]);
+    if (!ok) return fail(QASR_ERR_BLOB, "lm_check: suffix %d of node %d (level %d) is not one level down", sf, i, lv);
+  }
+  for (int s = 0; s < tcap; ++s) {
+    const int32_t* e = trans + 4 * (size_t)s;
+    if (e[0] == -1) continue;
+    if (e[0] < 0 || e[0] >= n_nodes || e[1] < 0 || e[1] >= n_words || e[3] < 0 || e[3] >= n_nodes || e[2] < -LIM || e[2] > LIM)
+      return fail(QASR_ERR_BLOB, "lm_check: transition slot %d (%d, %d, %d, %d) out of range", s, e[0], e[1], e[2], e[3]);
+    uint64_t x = (((uint64_t)(uint32_t)e[0] << 32) | (uint32_t)e[1]) * 0x9E3779B97F4A7C15ull;
+    x ^= x >> 32;
+    const int home = (int)((uint32_t)x & (uint32_t)(tcap - 1)), dist = (s - home) & (tcap - 1);
+    if (dist >= tprobe) return fail(QASR_ERR_BLOB, "lm_check: transition slot %d lies %d probes from its home, the bound is %d", s, dist + 1, tprobe);
+    for (int d = 0; d < dist; ++d)
+      if (trans[4 * (size_t)((home + d) & (tcap - 1))] == -1) return fail(QASR_ERR_BLOB, "lm_check: transition slot %d is cut off from its home", s);
+  }
+  for (int s = 0; s < wcap; ++s) {
+    const int32_t* e = words + 4 * (size_t)s;
+    if (e[2] == -1) continue;
+    if (e[2] < 0 || e[2] >= n_words) return fail(QASR_ERR_BLOB, "lm_check: word slot %d holds id %d", s, e[2]);
+    const int home = (int)((uint32_t)e[0] & (uint32_t)(wcap - 1)), dist = (s - home) & (wcap - 1);
+    if (dist >= wprobe) return fail(QASR_ERR_BLOB, "lm_check: word slot %d lies %d probes from its home, the bound is %d", s, dist + 1, wprobe);
+    for (int d = 0; d < dist; ++d)
+      if (words[4 * (size_t)((home + d) & (wcap - 1)) + 2] == -1) return fail(QASR_ERR_BLOB, "lm_check: word slot %d is cut off from its home", s);
+  }
+  for (int i = 0; i < n_labels; ++i)
+    if (l2w[i] < -1 || l2w[i] >= n_words) return fail(QASR_ERR_BLOB, "lm_check: label %d maps to word %d", i, l2w[i]);
+  return QASR_OK;
+}
+
+int qasr_ctc_beam_lm(void* stream, const qasr_ctc_beam_lm_args* a) {
+  if (!a) return fail(QASR_ERR_ARG, "ctc_beam_lm: args is NULL");
+  if (a->struct_size != sizeof(qasr_ctc_beam_lm_args))
+    return fail(QASR_ERR_ARG, "ctc_beam_lm: struct_size %u is not %zu", a->struct_size, sizeof(qasr_ctc_beam_lm_args));
+  if (!a->cand_id || !a->cand_q || !a->lae_table || !a->workspace || !a->labels || !a->n_labels || !a->score || !a->n_hyps ||
+      !a->lm || !a->lm_score)
+    return fail(QASR_ERR_ARG, "ctc_beam_lm: a required pointer is NULL (only lens is optional)");
+  if (!beam_shape_ok(a->B, a->T, a->beam_width))
+    return fail(QASR_ERR_ARG, "ctc_beam_lm: B %d, T %d (1 .. %d) or beam_width %d (1 .. %d) out of range", a->B, a->T,
+                QASR_BEAM_MAX_FRAMES, a->beam_width, QASR_BEAM_MAX_WIDTH);
+  if (a->N < 1 || a->N > QASR_BEAM_MAX_CANDIDATES)
+    return fail(QASR_ERR_ARG, "ctc_beam_lm: N %d is outside 1 .. %d", a->N, QASR_BEAM_MAX_CANDIDATES);
+  if (a->n_best < 1 || a->n_best > a->beam_width || a->blank < 0)
+    return fail(QASR_ERR_ARG, "ctc_beam_lm: n_best %d is outside 1 .. beam_width, or blank %d < 0", a->n_best, a->blank);
+  if (a->lae_entries != QASR_BEAM_TABLE_ENTRIES)
+    return fail(QASR_ERR_ARG, "ctc_beam_lm: lae_entries %u is not %d", a->lae_entries, QASR_BEAM_TABLE_ENTRIES);
+  const size_t need = beam_workspace_bytes(a->B, a->T, a->beam_width);
+  if (a->workspace_bytes < need) return fail(QASR_ERR_ARG, "ctc_beam_lm: workspace of %zu bytes, %zu needed", a->workspace_bytes, need);
+  if (((uintptr_t)a->lm & 15) != 0 || a->lm_bytes < 128 || a->lm_bytes > (size_t)INT32_MAX)
+    return fail(QASR_ERR_ARG, "ctc_beam_lm: lm must be 16-byte aligned and 128 .. 2^31 - 1 bytes, got %zu", a->lm_bytes);
+  if (a->alpha_q < 0 || a->alpha_q > QASR_LM_MAX_WEIGHT || a->beta_q < -QASR_LM_MAX_WEIGHT || a->beta_q > QASR_LM_MAX_WEIGHT)
+    return fail(QASR_ERR_ARG, "ctc_beam_lm: alpha_q %d outside 0 .. 16 * 2^16 or |beta_q| %d above it", a->alpha_q, a->beta_q);
+  if (a->space < -1 || a->space == a->blank)
+    return fail(QASR_ERR_ARG, "ctc_beam_lm: space %d must be a label other than blank, or -1", a->space);
+  int rc = launch_beam_lm((hipStream_t)stream, *a);
+  if (rc) return fail(rc, "ctc_beam_lm: launch");
+  HIPCHK(hipGetLastError());
+  return QASR_OK;
+}
+
 int qasr_engine_attach_ctc(qasr_engine* e, float* frame_score, const qasr_ctc_out* out, int use_lens) {
   if (!e) return fail(QASR_ERR_ARG, "attach_ctc: engine is NULL");
   if (frame_score || out) {

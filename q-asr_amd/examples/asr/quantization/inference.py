@@ -63,9 +63,21 @@ def main():
     p.add_argument("--beam_width", type=int, default=None, metavar='W',
                    help="(extension) CTC prefix beam search of width W (1 .. 128, no language model) instead of the arg-max: "
                         "hypotheses and WER come from the beam (EncDecCTCModel.decode(beam_width=W)); --dump_hyps gains `beam_score`")
+    p.add_argument("--lm_path", type=str, default=None,
+                   help="(extension, needs --beam_width) an n-gram language model as ARPA text (gzip too; KenLM binary files "
+                        "are refused: export ARPA), fused into the beam on the device; --dump_hyps gains `lm_score`")
+    p.add_argument("--alpha", type=float, default=None, help="(extension, needs --lm_path) weight of the model, 0 .. 16 (default 1.0)")
+    p.add_argument("--beta", type=float, default=None, help="(extension, needs --lm_path) bonus per scored word or character, -16 .. 16 (default 0.0)")
     args = p.parse_args()
     if args.beam_width is not None and not 1 <= args.beam_width <= 128:
         p.error(f'--beam_width must be 1 .. 128, got {args.beam_width}')
+    if args.lm_path is not None and args.beam_width is None:
+        p.error('--lm_path needs --beam_width')
+    if (args.alpha is not None or args.beta is not None) and args.lm_path is None:
+        p.error('--alpha and --beta need --lm_path')
+    alpha, beta = 1.0 if args.alpha is None else args.alpha, 0.0 if args.beta is None else args.beta
+    if not 0.0 <= alpha <= 16.0 or not abs(beta) <= 16.0:
+        p.error(f'--alpha must be 0 .. 16 and --beta -16 .. 16, got {alpha} and {beta}')
     torch.set_grad_enabled(False)
 
     if args.asr_model.endswith('.nemo'):
@@ -119,16 +131,19 @@ def main():
         asr_model.reserve(args.batch_size, args.reserve)
     labels_map = dict(enumerate(asr_model.decoder.vocabulary))
     wer = WER(vocabulary=asr_model.decoder.vocabulary)
-    hyps, refs, words, utt_scores, beam_scores = [], [], [], [], []
+    hyps, refs, words, utt_scores, beam_scores, lm_scores = [], [], [], [], [], []
+    lm_kw = dict(lm=args.lm_path, alpha=alpha, beta=beta) if args.lm_path is not None else {}
     audio_s, t0 = 0.0, time.time()
     for i, batch in enumerate(asr_model.test_dataloader()):
         if i == args.eval_early_stop:
             break
         batch = [x.cuda() for x in batch]
         if args.beam_width is not None:                      # k_topn + k_beam behind the forward, on the same stream
-            for h in asr_model.decode(input_signal=batch[0].float(), input_signal_length=batch[1], beam_width=args.beam_width):
+            for h in asr_model.decode(input_signal=batch[0].float(), input_signal_length=batch[1], beam_width=args.beam_width,
+                                      **lm_kw):
                 hyps.append(h.text)
                 beam_scores.append(h.utt_score)
+                lm_scores.append(h.lm_score)
         else:
             log_probs, enc_len, greedy = asr_model(input_signal=batch[0].float(), input_signal_length=batch[1])
             hyps += wer.ctc_decoder_predictions_tensor(greedy)
@@ -152,6 +167,8 @@ def main():
             extra = dict(words=words, utt_score=utt_scores) if args.timestamps else {}
             if args.beam_width is not None:
                 extra.update(beam_width=args.beam_width, beam_score=beam_scores)
+            if args.lm_path is not None:
+                extra.update(lm_path=args.lm_path, alpha=alpha, beta=beta, lm_score=lm_scores)
             json.dump(dict(hypotheses=hyps, references=refs, wer=wer_value, path=served, **extra), f)
     print(f'RTFx (incl. host data loading): {audio_s / max(wall, 1e-9):.1f}  ({audio_s:.1f} s audio in {wall:.2f} s)')
 

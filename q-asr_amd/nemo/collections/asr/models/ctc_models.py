@@ -432,7 +432,7 @@ class EncDecCTCModel(nn.Module):
 
     @torch.no_grad()
     def decode(self, input_signal=None, input_signal_length=None, processed_signal=None, processed_signal_length=None,
-               beam_width=None, n_best=1, cutoff_top_n=40):
+               beam_width=None, n_best=1, cutoff_top_n=40, lm=None, alpha=0.0, beta=0.0):
         """Greedy CTC hypotheses of one batch (an extension of the reference's API): List[qasr.ctc.Hypothesis] with the
         text, every label's start / end time and confidence (best frame log-probability of its run), word groups and the
         log-probability of the greedy path.  Decoding stops at each utterance's encoded length.  On the static engine the
@@ -445,12 +445,21 @@ class EncDecCTCModel(nn.Module):
         and k_beam follow on the same stream - on the static engine, a reserved engine and the dynamic path alike; the host
         modules run the NumPy twin.  The hypotheses carry text, labels and utt_score (the beam score); their time lists are
         empty, since a prefix has no single alignment.  n_best > 1 (<= W) returns, per utterance, the list of its best
-        hypotheses, best first."""
+        hypotheses, best first.
+
+        lm=<path of an ARPA file, or a qasr.ngram.NgramLM> (needs beam_width) adds the n-gram model with the weights alpha
+        (0 .. 16) and beta (|beta| <= 16) as ctc_decoders' Scorer does (qasr.beam.LM_RULES; k_beam_lm on the device): word
+        mode if the vocabulary has a space, else character mode.  utt_score then includes the model's share, which the
+        hypotheses also carry as lm_score.  A model loaded from a path is kept on the module, so a sweep of alpha / beta
+        loads and packs once.  Out of scope: KenLM binary files, cutoff_prob < 1, </s> scoring, orders above 6."""
         from qasr import ctc as qctc
+        if lm is not None and beam_width is None:
+            raise ValueError('decode: lm needs beam_width (the greedy collapse has no language model)')
         if beam_width is not None:
             beam_width, n_best, cutoff_top_n = self._beam_args(beam_width, n_best, cutoff_top_n)      # refused before any launch
+            lm = self._lm_args(lm, alpha, beta)
             return self._beam_decode(self._forward(input_signal, input_signal_length, processed_signal, processed_signal_length),
-                                     beam_width, n_best, cutoff_top_n)
+                                     beam_width, n_best, cutoff_top_n, lm, alpha, beta)
         res = self._forward(input_signal, input_signal_length, processed_signal, processed_signal_length, decode=True)
         return qctc.to_hypotheses(res, self.decoder.vocabulary, self.seconds_per_frame())
 
@@ -466,16 +475,38 @@ class EncDecCTCModel(nn.Module):
             raise ValueError(f'decode: n_best must be 1 .. beam_width, got {n_best}')
         return beam_width, n_best, cutoff_top_n
 
-    def _beam_decode(self, fwd, beam_width, n_best, cutoff_top_n):
+    def _lm_args(self, lm, alpha, beta):
+        """the NgramLM of decode(lm=): a path is loaded once per module; the weights are refused here, before any launch"""
+        if lm is None:
+            return None
+        from qasr import ngram
+        try:
+            ngram.fixed_weights(alpha, beta)
+        except ValueError as e:
+            raise ValueError(f'decode: {e}') from None
+        if not isinstance(lm, ngram.NgramLM):
+            key = os.fspath(lm)
+            cache = self.__dict__.setdefault('_lm_cache', {})
+            if key not in cache:
+                cache[key] = ngram.NgramLM.from_arpa(key, self.decoder.vocabulary)
+            lm = cache[key]
+        if lm.n_labels != len(self.decoder.vocabulary):
+            raise ValueError(f'decode: the language model was loaded for {lm.n_labels} labels, the decoder has '
+                             f'{len(self.decoder.vocabulary)}')
+        return lm
+
+    def _beam_decode(self, fwd, beam_width, n_best, cutoff_top_n, lm=None, alpha=0.0, beta=0.0):
         """decode(beam_width=) behind any path's (log_probs, encoded lengths, tokens); the arguments passed _beam_args"""
         from qasr import beam as qbeam
         log_probs, enc_len = fwd[0], fwd[1]
         blank = len(self.decoder.vocabulary)
         if log_probs.is_cuda:
             from qasr import engine as qengine
-            res = qengine.ctc_beam_search(log_probs.float(), enc_len, blank, beam_width, n_best, cutoff_top_n)
+            res = qengine.ctc_beam_search(log_probs.float(), enc_len, blank, beam_width, n_best, cutoff_top_n, lm=lm,
+                                          alpha=alpha, beta=beta)
         else:
-            res = qbeam.search_host(log_probs.float().numpy(), enc_len.numpy(), blank, beam_width, n_best, cutoff_top_n)
+            res = qbeam.search_host(log_probs.float().numpy(), enc_len.numpy(), blank, beam_width, n_best, cutoff_top_n, lm,
+                                    alpha, beta)
         hyps = qbeam.to_hypotheses(res, self.decoder.vocabulary)
         return hyps if n_best > 1 else [h[0] for h in hyps]          # a beam over real candidates never dies: h[0] exists
 

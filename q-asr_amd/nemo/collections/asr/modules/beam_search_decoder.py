@@ -1,10 +1,18 @@
-"""CTC prefix beam search behind the reference's BeamSearchDecoderWithLM interface, without a language model.
+"""CTC prefix beam search behind the reference's BeamSearchDecoderWithLM interface, with or without an n-gram model.
 
 The search is the fixed-point one of qasr.beam (csrc/qasr_beam.hip on the device): CUDA log-probabilities run k_topn +
-k_beam on the current stream, CPU tensors and the `input_tensor=False` form (a list of per-utterance probability arrays)
-run the NumPy twin; both give the same hypotheses and scores, bit for bit.  There is no n-gram scorer here: `lm_path` must
-be None (alpha and beta are kept for the signature and unused), and vocabulary pruning by cumulative probability is not
-implemented (`cutoff_prob` must be 1.0)."""
+k_beam (k_beam_lm with a model) on the current stream, CPU tensors and the `input_tensor=False` form (a list of
+per-utterance probability arrays) run the NumPy twin; both give the same hypotheses and scores, bit for bit.
+
+`lm_path`: an ARPA text file (gzip too), read by qasr.ngram - neither ctc_decoders nor kenlm is used.  Of ctc_decoders'
+Scorer this follows: the mode from the vocabulary (word-based if it has a space, else character-based), a word scored
+when a space ends it, every extension adding alpha * ln p + beta (words that the model lacks: -1000, then an empty
+history), the history starting at <s>, </s> never scored, and in word mode the unfinished last word scored after the
+last frame with the beam re-ordered.  Not followed: the arithmetic (fixed point, qasr.beam.LM_RULES, so that device and
+host agree on every bit), KenLM binary files (export ARPA), the dictionary FST that restricts prefixes to spellable
+words, vocabulary pruning by cumulative probability (`cutoff_prob` must be 1.0), timestamps for beam hypotheses, orders
+above 6.  The reported score is
+the search score including the model's share, where ctc_decoders subtracts it again."""
 import numpy as np
 import torch
 from torch import nn
@@ -23,17 +31,24 @@ class BeamSearchDecoderWithLM(nn.Module):
 
     def __init__(self, vocab, beam_width, alpha, beta, lm_path, num_cpus, cutoff_prob=1.0, cutoff_top_n=40,
                  input_tensor=False):
-        if lm_path is not None:
-            raise ModuleNotFoundError('BeamSearchDecoderWithLM with an n-gram model (lm_path) requires ctc_decoders, which '
-                                      'this build does not use: pass lm_path=None for the search without a scorer')
         if float(cutoff_prob) != 1.0:
             raise ValueError(f'BeamSearchDecoderWithLM: cutoff_prob must be 1.0 (no cumulative pruning), got {cutoff_prob}')
         if not 1 <= int(beam_width) <= qbeam.MAX_W:
             raise ValueError(f'BeamSearchDecoderWithLM: beam_width must be 1 .. {qbeam.MAX_W}, got {beam_width}')
         if not 1 <= int(cutoff_top_n) <= qbeam.MAX_N:
             raise ValueError(f'BeamSearchDecoderWithLM: cutoff_top_n must be 1 .. {qbeam.MAX_N}, got {cutoff_top_n}')
+        scorer = None
+        if lm_path is not None:                     # (a KenLM binary file raises ModuleNotFoundError: export ARPA)
+            from qasr import ngram
+            try:
+                ngram.fixed_weights(alpha, beta)
+            except ValueError as e:
+                raise ValueError(f'BeamSearchDecoderWithLM: {e}') from None
+            scorer = lm_path if isinstance(lm_path, ngram.NgramLM) else ngram.NgramLM.from_arpa(lm_path, list(vocab))
+            if scorer.n_labels != len(list(vocab)):
+                raise ValueError(f'BeamSearchDecoderWithLM: the model was loaded for {scorer.n_labels} labels, vocab has {len(list(vocab))}')
         super().__init__()
-        self.scorer = None
+        self.scorer = scorer
         self.vocab = list(vocab)
         self.beam_width = int(beam_width)
         self.alpha, self.beta = alpha, beta
@@ -50,9 +65,10 @@ class BeamSearchDecoderWithLM(nn.Module):
         if log_probs.is_cuda:
             from qasr import engine as qengine
             return qengine.ctc_beam_search(log_probs.float(), log_probs_length, blank, self.beam_width, n_best,
-                                           self.cutoff_top_n)
+                                           self.cutoff_top_n, lm=self.scorer, alpha=self.alpha, beta=self.beta)
         lens = None if log_probs_length is None else np.asarray(log_probs_length.cpu())
-        return qbeam.search_host(log_probs.float().numpy(), lens, blank, self.beam_width, n_best, self.cutoff_top_n)
+        return qbeam.search_host(log_probs.float().numpy(), lens, blank, self.beam_width, n_best, self.cutoff_top_n,
+                                 self.scorer, self.alpha, self.beta)
 
     @torch.no_grad()
     def forward(self, log_probs, log_probs_length=None):

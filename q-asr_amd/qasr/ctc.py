@@ -35,6 +35,7 @@ class Hypothesis:
     score: Optional[List[float]]            # per label: best frame log-probability inside the label's run
     utt_score: Optional[float]              # log-probability of the greedy path
     words: List[Tuple[str, float, float, Optional[float]]] = field(default_factory=list)
+    lm_score: Optional[float] = None        # beam search with a language model: the model's share of utt_score
 
 
 def _order_key(x):
