@@ -395,6 +395,51 @@ typedef struct qasr_ctc_beam_lm_args {
 } qasr_ctc_beam_lm_args;
 int qasr_ctc_beam_lm(void* stream, const qasr_ctc_beam_lm_args* args);
 
+/* ---- CTC forced alignment and transcript scoring ---------------------------------------------------------------------
+ * For a GIVEN label sequence: its best alignment against the log-probabilities (Viterbi: per label the first frame, the
+ * frame count and the best frame log-probability of its run, the outputs of k_ctc for a text instead of the arg-max) and
+ * its CTC log-likelihood over all alignments (forward), in the fixed point of the beam search above: q = rint(x * 2^16),
+ * int64 sums, log 0 = -2^62, log-add-exp through the caller's table.  The rules (states, predecessors, the tie order
+ * stay < s-1 < s-2, the order of the two log-add-exps, the end states) are RULES of qasr/align.py, which k_align follows
+ * bit for bit.  Problem p < P aligns targets[p][0 .. target_lens[p]) against utterance p / K (K problems per utterance:
+ * the n-best rows of a beam, K = 1 for one transcript each).  max_labels is the row pitch of targets and of the per-label
+ * outputs, at most QASR_ALIGN_MAX_LABELS; a longer target is not alignable.
+ *   start, nframes i32 [P][max_labels], score f32 [P][max_labels]: the label's run (tails 0); path_score i64 [P]: the best
+ *   alignment's score; total i64 [P]: the log-likelihood (both / 2^16 = nats); ok i32 [P].  Every output but ok is optional;
+ *   without total the forward pass is skipped and no table is needed.
+ * Not alignable - ok 0, the rows 0, path_score = total = -2^62: fewer frames than labels plus adjacent repeats, no frames
+ * for a non-empty target, target_lens outside 0 .. max_labels, a label outside [0, C) or equal to blank.  Targets are device
+ * data: the kernel checks them itself and reads nothing through a bad label.
+ * workspace: qasr_ctc_align_workspace_bytes(P, T, max_labels) bytes the call may overwrite (backpointers, 2 bits per frame
+ * and state); nothing is allocated and no length is read on the host, so the call can be captured.
+ * QASR_ERR_ARG with nothing launched and no output written: an unknown struct_size, a NULL among log_probs, targets,
+ * target_lens, workspace, ok; B, T, C or K < 1, P != B * K, T > QASR_BEAM_MAX_FRAMES, max_labels outside
+ * 1 .. QASR_ALIGN_MAX_LABELS, blank outside [0, C), pitch_frame < C, pitch_utt < T * pitch_frame, total without lae_table, a
+ * lae_table with lae_entries != QASR_BEAM_TABLE_ENTRIES, a workspace smaller than the query says. */
+#define QASR_ALIGN_MAX_LABELS 2048
+typedef struct qasr_ctc_align_args {
+  uint32_t struct_size;
+  int32_t B, T, C, P, K, blank, max_labels;
+  int64_t pitch_utt, pitch_frame;   /* in floats */
+  const float* log_probs;
+  const int32_t* lens;         /* optional [B] */
+  const int32_t* targets;      /* [P][max_labels] */
+  const int32_t* target_lens;  /* [P] */
+  uint32_t lae_entries;        /* QASR_BEAM_TABLE_ENTRIES (with lae_table) */
+  uint32_t reserved;
+  const uint16_t* lae_table;   /* required only with total */
+  void* workspace;
+  size_t workspace_bytes;
+  int32_t* start;              /* optional */
+  int32_t* nframes;            /* optional */
+  float* score;                /* optional */
+  int64_t* path_score;         /* optional */
+  int64_t* total;              /* optional */
+  int32_t* ok;
+} qasr_ctc_align_args;
+size_t qasr_ctc_align_workspace_bytes(int P, int T, int max_labels);   /* 0 for a shape qasr_ctc_align refuses */
+int qasr_ctc_align(void* stream, const qasr_ctc_align_args* args);
+
 /* ---- reserved engines: ragged batches without allocation, with graph replay ------------------------------------------
  * A data loader pads every batch to its own longest utterance (the reference's collate function), so (B, T) changes on
  * almost every call; qasr_engine_forward[_audio] then rebuilds its plan (device-synchronising frees + allocations) and,

@@ -1,0 +1,312 @@
+// CTC forced alignment and transcript scoring in fixed point (k_align); the host statement is qasr/align.py (RULES), and this
+// file follows it bit for bit.  Scores are int64 sums of q = rint(logp * 2^16) as in qasr_beam.hip; the forward pass adds with
+// the caller's log-add-exp table (LDS resident), so the kernel calls neither exp nor log.
+//
+// k_align<NS>: one work-group of 256 threads per problem (utterance p / K, target row p), sequential over frames.  Thread tid
+// owns the states tid, tid + 256, ... (NS of them at most; NS is chosen from the row pitch of the targets, so a short-pitch
+// call pays neither the registers nor the LDS of the 4097-state case).  A state's label and its "may skip the blank" bit
+// stay in registers; the only global reads of a frame are the gathers logp[u][t][lab(s)], and frame t + 1's are issued
+// before frame t's arithmetic, so the serial chain per frame is: 3 LDS reads, compare / add, 1 LDS write, 1 barrier (the
+// row is double-buffered).
+// Two passes over the same two int64 rows, one after the other in ONE launch: Viterbi first, then - only when `total` is
+// requested - forward.  Both at once would need four rows: 4 x 4352 x 8 B = 136 KB plus the 32 KB table is past a work-
+// group's 160 KB; one pair is 68 KB + 32 KB + 2 KB at NS = 17 and 4 KB + 32 KB + 2 KB at NS = 1.
+// Backpointers: 2 bits per (frame, state), four frames of one state to a byte (a thread collects its states' steps in
+// registers and stores one byte per state every fourth frame; consecutive threads store consecutive bytes) in the
+// caller's workspace: P x ceil(T / 4) x pitch bytes, pitch = 2 * max_labels + 1 rounded up to 4.
+// Back-walk: the path moves by at most 2 states per frame, so 64 frames (16 byte rows) need a window of 129 states.  All
+// threads copy that window into LDS (one global round trip per 64 frames), thread 0 walks it there and leaves, per label,
+// its first frame and frame count in LDS; then one thread per label takes the maximum of its frames' log-probabilities.
+// LDS atomics: none.  Global memory sees plain vector stores.  Every loop is bounded by T, the number of states, the row
+// pitch or a constant; nothing is allocated and no length is read on the host.
+#include <climits>
+#include <type_traits>
+
+#include "qasr_internal.h"
+
+namespace qasr {
+
+#define ALIGN_NT 256
+#define ALIGN_NEG (-(1ll << 62))
+#define ALIGN_QFLOOR (-1073741824.f)
+#define ALIGN_QCEIL (1073741824.f)
+#define ALIGN_DMAX (16ll << 16)
+#define ALIGN_TAB QASR_BEAM_TABLE_ENTRIES
+#define ALIGN_G 16                              /* byte rows (4 frames each) per back-walk window */
+#define ALIGN_WINW (8 * ALIGN_G + 4)            /* states per window row: the path descends <= 2 * 4 * G inside one window */
+
+struct AlignP {
+  const float* logp;
+  const int32_t* lens;          // optional [B]
+  const int32_t* targets;       // [P][ML]
+  const int32_t* target_lens;   // [P]
+  const uint16_t* tab;          // [ALIGN_TAB], with total
+  unsigned char* ws;            // [P][G4][pitch_s]
+  int32_t* start;               // [P][ML] optional
+  int32_t* nframes;             // [P][ML] optional
+  float* score;                 // [P][ML] optional
+  long long* path_score;        // [P] optional
+  long long* total;             // [P] optional
+  int32_t* ok;                  // [P]
+  long long pitch_b, pitch_t;
+  int T, C, K, blank, ML, pitch_s, G4;
+};
+
+__device__ __forceinline__ int align_key(int bits) { return bits ^ ((bits >> 31) & 0x7fffffff); }
+
+__device__ __forceinline__ long long align_quantize(float x) {
+  float y = x * 65536.f;
+  if (!(y >= ALIGN_QFLOOR)) y = ALIGN_QFLOOR;      // NaN and -inf take the floor
+  if (y > ALIGN_QCEIL) y = ALIGN_QCEIL;
+  return (long long)(int)rintf(y);
+}
+
+__device__ __forceinline__ long long align_lae(long long a, long long b, const uint16_t* tab) {
+  const long long m = a > b ? a : b, n = a > b ? b : a;
+  if (n == ALIGN_NEG) return m;
+  const long long d = m - n;
+  if (d >= ALIGN_DMAX) return m;
+  return m + (long long)tab[d >> 6];
+}
+
+static int align_pitch(int max_labels) { return (2 * max_labels + 1 + 3) & ~3; }
+
+size_t align_workspace_bytes(int P, int T, int max_labels) {
+  return (size_t)P * (size_t)((T + 3) / 4) * (size_t)align_pitch(max_labels);
+}
+
+template <int NS>
+__global__ void __launch_bounds__(ALIGN_NT) k_align(AlignP p) {
+  __shared__ long long rows[2][NS * ALIGN_NT];
+  __shared__ uint16_t tab[ALIGN_TAB];
+  __shared__ unsigned char win[ALIGN_G * ALIGN_WINW];
+  __shared__ int sh_bad, sh_s, sh_t;
+  const int tid = threadIdx.x, pr = blockIdx.x, u = pr / p.K;
+  const int T = p.T, C = p.C, blank = p.blank, ML = p.ML;
+  const int lim = p.lens ? min(max(p.lens[u], 0), T) : T;
+  const int L = p.target_lens[pr];
+  const int32_t* const y = p.targets + (size_t)pr * ML;
+  const bool want_total = p.total != nullptr;
+  int32_t* const o_start = p.start ? p.start + (size_t)pr * ML : nullptr;
+  int32_t* const o_nframes = p.nframes ? p.nframes + (size_t)pr * ML : nullptr;
+  float* const o_score = p.score ? p.score + (size_t)pr * ML : nullptr;
+
+  if (tid == 0) sh_bad = 0;
+  if (want_total)
+    for (int i = tid; i < ALIGN_TAB; i += ALIGN_NT) tab[i] = p.tab[i];
+  __syncthreads();
+  // the target is device data: its length and every label are checked here, before anything is read through them
+  const bool len_ok = L >= 0 && L <= ML && L <= QASR_ALIGN_MAX_LABELS && 2 * L + 1 <= NS * ALIGN_NT;
+  if (len_ok)
+    for (int i = tid; i < L; i += ALIGN_NT) {
+      const int c = y[i];
+      if (c < 0 || c >= C || c == blank) sh_bad = 1;
+    }
+  __syncthreads();
+  bool alignable = len_ok && !sh_bad && !(lim == 0 && L > 0);
+  const int S = alignable ? 2 * L + 1 : 0;
+
+  int lab[NS];
+  bool skp[NS];
+#pragma unroll
+  for (int k = 0; k < NS; ++k) {
+    const int s = tid + k * ALIGN_NT;
+    lab[k] = blank, skp[k] = false;
+    if (s < S && (s & 1)) {
+      lab[k] = y[s >> 1];
+      skp[k] = s >= 3 && y[s >> 1] != y[(s >> 1) - 1];
+    }
+  }
+  const float* const base = p.logp + (long long)u * p.pitch_b;
+  unsigned char* const wsp = p.ws + (size_t)pr * (size_t)p.G4 * (size_t)p.pitch_s;
+  const size_t pitch_s = (size_t)p.pitch_s;
+
+  // one pass over the frames (vit: Viterbi with backpointers, else forward); returns the row that holds frame lim - 1
+  auto run = [&](auto vit_tag) -> int {
+    constexpr bool VIT = decltype(vit_tag)::value;
+    float pf[NS];
+    unsigned acc[NS];
+#pragma unroll
+    for (int k = 0; k < NS; ++k) {
+      const int s = tid + k * ALIGN_NT;
+      acc[k] = 0;
+      pf[k] = s < S ? base[lab[k]] : 0.f;                           // frame 0 (lim >= 1 here)
+      if (s < S) rows[0][s] = s < 2 ? align_quantize(pf[k]) : ALIGN_NEG;
+      pf[k] = (s < S && lim > 1) ? base[p.pitch_t + lab[k]] : 0.f;
+    }
+    int cur = 0;
+    __syncthreads();
+    for (int t = 1; t < lim; ++t) {
+      float nx[NS];
+#pragma unroll
+      for (int k = 0; k < NS; ++k) {                                // frame t + 1's gathers, in flight across this frame
+        const int s = tid + k * ALIGN_NT;
+        nx[k] = (s < S && t + 1 < lim) ? base[(long long)(t + 1) * p.pitch_t + lab[k]] : 0.f;
+      }
+      const long long* const R = rows[cur];
+      long long* const W = rows[cur ^ 1];
+      const bool flush = (t & 3) == 3 || t == lim - 1;
+#pragma unroll
+      for (int k = 0; k < NS; ++k) {
+        const int s = tid + k * ALIGN_NT;
+        if (s < S) {
+          const long long q = align_quantize(pf[k]);
+          const long long a0 = R[s], a1 = s >= 1 ? R[s - 1] : ALIGN_NEG, a2 = skp[k] ? R[s - 2] : ALIGN_NEG;
+          if constexpr (VIT) {
+            long long best = a0;
+            unsigned step = 0;
+            if (a1 > best) best = a1, step = 1;
+            if (a2 > best) best = a2, step = 2;
+            W[s] = best == ALIGN_NEG ? ALIGN_NEG : best + q;
+            acc[k] |= step << (2 * (t & 3));
+            if (flush) {
+              wsp[(size_t)(t >> 2) * pitch_s + s] = (unsigned char)acc[k];      // t >> 2 < G4, s < S <= pitch_s
+              acc[k] = 0;
+            }
+          } else {
+            const long long x = align_lae(align_lae(a0, a1, tab), a2, tab);
+            W[s] = x == ALIGN_NEG ? ALIGN_NEG : x + q;
+          }
+        }
+      }
+#pragma unroll
+      for (int k = 0; k < NS; ++k) pf[k] = nx[k];
+      cur ^= 1;
+      __syncthreads();
+    }
+    return cur;
+  };
+
+  // ---- Viterbi
+  long long vf = ALIGN_NEG;
+  int fin = 0;
+  if (alignable) {
+    if (lim == 0) {
+      vf = 0;                                                       // L == 0: the empty path
+    } else {
+      const int cur = run(std::true_type{});
+      const long long* const R = rows[cur];
+      if (L == 0) {
+        vf = R[0];
+      } else {
+        const long long a = R[2 * L], b = R[2 * L - 1];
+        fin = a > b ? 2 * L : 2 * L - 1;
+        vf = a > b ? a : b;
+      }
+    }
+    alignable = vf != ALIGN_NEG;
+  }
+  __syncthreads();                                                  // the rows have been read: their LDS is reused below
+  if (!alignable) {                                                 // uniform
+    for (int i = tid; i < ML; i += ALIGN_NT) {
+      if (o_start) o_start[i] = 0;
+      if (o_nframes) o_nframes[i] = 0;
+      if (o_score) o_score[i] = 0.f;
+    }
+    if (tid == 0) {
+      if (p.path_score) p.path_score[pr] = ALIGN_NEG;
+      if (p.total) p.total[pr] = ALIGN_NEG;
+      p.ok[pr] = 0;
+    }
+    return;
+  }
+  // ---- back-walk: per label its first frame and frame count (L <= NS * 128 - 1: both arrays fit rows[0])
+  int* const lstart = reinterpret_cast<int*>(&rows[0][0]);
+  int* const lcnt = lstart + NS * (ALIGN_NT / 2);
+  if (L > 0) {                                                      // (then lim > 0)
+    for (int i = tid; i < L; i += ALIGN_NT) lstart[i] = 0, lcnt[i] = 0;
+    if (tid == 0) sh_s = fin, sh_t = lim - 1;
+    __syncthreads();
+    int cur_i = -1, cnt = 0, first = 0;                             // thread 0: the label run being walked
+    for (int guard = 0; guard <= p.G4; ++guard) {                   // bounded: every window consumes at least one byte row
+      const int s_hi = sh_s, t_hi = sh_t;
+      if (t_hi < 0) break;                                          // uniform
+      const int g_top = t_hi >> 2, g_lo = max(g_top - ALIGN_G + 1, 0), ng = g_top - g_lo + 1;
+      const int lo = max(s_hi - 8 * ALIGN_G, 0), width = s_hi - lo + 1;          // <= 8 G + 1 states, all < S
+      for (int i = tid; i < ng * ALIGN_WINW; i += ALIGN_NT) {
+        const int gi = i / ALIGN_WINW, si = i - gi * ALIGN_WINW;
+        if (si < width) win[i] = wsp[(size_t)(g_lo + gi) * pitch_s + lo + si];
+      }
+      __syncthreads();
+      if (tid == 0) {
+        int s = s_hi;
+        for (int t = t_hi; t >= 4 * g_lo; --t) {
+          if (s & 1) {
+            const int i = s >> 1;
+            if (i != cur_i) {
+              if (cur_i >= 0) lstart[cur_i] = first, lcnt[cur_i] = cnt;
+              cur_i = i, cnt = 0;
+            }
+            ++cnt, first = t;
+          }
+          if (t > 0) {
+            const int at = min(max(s - lo, 0), ALIGN_WINW - 1);
+            const int step = (win[((t >> 2) - g_lo) * ALIGN_WINW + at] >> (2 * (t & 3))) & 3;
+            s = max(s - step, 0);
+          }
+        }
+        sh_s = s, sh_t = 4 * g_lo - 1;
+      }
+      __syncthreads();
+    }
+    if (tid == 0 && cur_i >= 0) lstart[cur_i] = first, lcnt[cur_i] = cnt;
+    __syncthreads();
+  }
+  // ---- outputs: one thread per label; the score is the largest log-probability of the label inside its run
+  for (int i = tid; i < ML; i += ALIGN_NT) {
+    int st = 0, n = 0;
+    float sc = 0.f;
+    if (i < L) {
+      st = min(max(lstart[i], 0), lim - 1), n = min(max(lcnt[i], 0), lim - st);
+      if (o_score && n > 0) {
+        const float* const col = base + y[i];
+        int best = INT_MIN;
+        for (int f = 0; f < n; ++f) {
+          const int key = align_key(__float_as_int(col[(long long)(st + f) * p.pitch_t]));
+          best = key > best ? key : best;
+        }
+        sc = __int_as_float(align_key(best));
+      }
+    }
+    if (o_start) o_start[i] = st;
+    if (o_nframes) o_nframes[i] = n;
+    if (o_score) o_score[i] = sc;
+  }
+  if (tid == 0) {
+    if (p.path_score) p.path_score[pr] = vf;
+    p.ok[pr] = 1;
+  }
+  // ---- forward
+  if (want_total) {
+    long long tot = 0;                                              // lim == 0 (and L == 0)
+    if (lim > 0) {
+      __syncthreads();                                              // lstart / lcnt have been read
+      const int cur = run(std::false_type{});
+      const long long* const R = rows[cur];
+      tot = L == 0 ? R[0] : align_lae(R[2 * L], R[2 * L - 1], tab);
+    }
+    if (tid == 0) p.total[pr] = tot;
+  }
+}
+
+int launch_align(hipStream_t s, const qasr_ctc_align_args& a) {
+  AlignP p{};
+  p.logp = a.log_probs, p.lens = a.lens, p.targets = a.targets, p.target_lens = a.target_lens, p.tab = a.lae_table;
+  p.ws = (unsigned char*)a.workspace;
+  p.start = a.start, p.nframes = a.nframes, p.score = a.score;
+  p.path_score = (long long*)a.path_score, p.total = (long long*)a.total, p.ok = a.ok;
+  p.pitch_b = a.pitch_utt, p.pitch_t = a.pitch_frame;
+  p.T = a.T, p.C = a.C, p.K = a.K, p.blank = a.blank, p.ML = a.max_labels;
+  p.pitch_s = align_pitch(a.max_labels), p.G4 = (a.T + 3) / 4;
+  const int states = 2 * a.max_labels + 1;                          // <= 4097
+  const dim3 grid((unsigned)a.P), block(ALIGN_NT);
+  static_assert(2 * QASR_ALIGN_MAX_LABELS + 1 <= 17 * ALIGN_NT, "k_align<17> holds the longest target");
+  if (states <= 1 * ALIGN_NT) hipLaunchKernelGGL(k_align<1>, grid, block, 0, s, p);
+  else if (states <= 2 * ALIGN_NT) hipLaunchKernelGGL(k_align<2>, grid, block, 0, s, p);
+  else if (states <= 4 * ALIGN_NT) hipLaunchKernelGGL(k_align<4>, grid, block, 0, s, p);
+  else if (states <= 8 * ALIGN_NT) hipLaunchKernelGGL(k_align<8>, grid, block, 0, s, p);
+  else hipLaunchKernelGGL(k_align<17>, grid, block, 0, s, p);
+  return QASR_OK;
+}
+
+}  // namespace qasr

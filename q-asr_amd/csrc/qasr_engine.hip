@@ -1172,6 +1172,42 @@ int qasr_ctc_beam_lm(void* stream, const qasr_ctc_beam_lm_args* a) {
   return QASR_OK;
 }
 
+// ---- CTC forced alignment (k_align, qasr_align.hip): the checks of include/qasr.h, then one launch
+static int align_shape_ok(int P, int T, int max_labels) {
+  return P >= 1 && T >= 1 && T <= QASR_BEAM_MAX_FRAMES && max_labels >= 1 && max_labels <= QASR_ALIGN_MAX_LABELS;
+}
+
+size_t qasr_ctc_align_workspace_bytes(int P, int T, int max_labels) {
+  return align_shape_ok(P, T, max_labels) ? align_workspace_bytes(P, T, max_labels) : 0;
+}
+
+int qasr_ctc_align(void* stream, const qasr_ctc_align_args* a) {
+  if (!a) return fail(QASR_ERR_ARG, "ctc_align: args is NULL");
+  if (a->struct_size != sizeof(qasr_ctc_align_args))
+    return fail(QASR_ERR_ARG, "ctc_align: struct_size %u is not %zu", a->struct_size, sizeof(qasr_ctc_align_args));
+  if (!a->log_probs || !a->targets || !a->target_lens || !a->workspace || !a->ok)
+    return fail(QASR_ERR_ARG, "ctc_align: log_probs, targets, target_lens, workspace and ok are required");
+  if (a->B < 1 || a->T < 1 || a->T > QASR_BEAM_MAX_FRAMES || a->C < 1 || a->K < 1)
+    return fail(QASR_ERR_ARG, "ctc_align: B %d, T %d (1 .. %d), C %d or K %d out of range", a->B, a->T, QASR_BEAM_MAX_FRAMES, a->C,
+                a->K);
+  if ((long long)a->P != (long long)a->B * a->K) return fail(QASR_ERR_ARG, "ctc_align: P %d is not B %d * K %d", a->P, a->B, a->K);
+  if (a->max_labels < 1 || a->max_labels > QASR_ALIGN_MAX_LABELS)
+    return fail(QASR_ERR_ARG, "ctc_align: max_labels %d is outside 1 .. %d", a->max_labels, QASR_ALIGN_MAX_LABELS);
+  if (a->blank < 0 || a->blank >= a->C) return fail(QASR_ERR_ARG, "ctc_align: blank %d is outside [0, %d)", a->blank, a->C);
+  if (a->pitch_frame < a->C || a->pitch_utt < (int64_t)a->T * a->pitch_frame)
+    return fail(QASR_ERR_ARG, "ctc_align: pitch_frame %lld < C or pitch_utt %lld < T * pitch_frame", (long long)a->pitch_frame,
+                (long long)a->pitch_utt);
+  if (a->total && !a->lae_table) return fail(QASR_ERR_ARG, "ctc_align: total needs lae_table");
+  if (a->lae_table && a->lae_entries != QASR_BEAM_TABLE_ENTRIES)
+    return fail(QASR_ERR_ARG, "ctc_align: lae_entries %u is not %d", a->lae_entries, QASR_BEAM_TABLE_ENTRIES);
+  const size_t need = align_workspace_bytes(a->P, a->T, a->max_labels);
+  if (a->workspace_bytes < need) return fail(QASR_ERR_ARG, "ctc_align: workspace of %zu bytes, %zu needed", a->workspace_bytes, need);
+  int rc = launch_align((hipStream_t)stream, *a);
+  if (rc) return fail(rc, "ctc_align: launch");
+  HIPCHK(hipGetLastError());
+  return QASR_OK;
+}
+
 int qasr_engine_attach_ctc(qasr_engine* e, float* frame_score, const qasr_ctc_out* out, int use_lens) {
   if (!e) return fail(QASR_ERR_ARG, "attach_ctc: engine is NULL");
   if (frame_score || out) {

@@ -68,6 +68,11 @@ def main():
                         "are refused: export ARPA), fused into the beam on the device; --dump_hyps gains `lm_score`")
     p.add_argument("--alpha", type=float, default=None, help="(extension, needs --lm_path) weight of the model, 0 .. 16 (default 1.0)")
     p.add_argument("--beta", type=float, default=None, help="(extension, needs --lm_path) bonus per scored word or character, -16 .. 16 (default 0.0)")
+    p.add_argument("--align", type=str, default=None, metavar='OUT',
+                   help="(extension) forced alignment of every manifest line's reference text against its batch's "
+                        "log-probabilities (EncDecCTCModel.align): OUT gets one JSON line per utterance - audio_filepath, text, "
+                        "ctc_score (log-likelihood of the text), utt_score (its best alignment) and words [word, start_s, end_s, "
+                        "score]; hypotheses, WER and the other outputs are unchanged")
     args = p.parse_args()
     if args.beam_width is not None and not 1 <= args.beam_width <= 128:
         p.error(f'--beam_width must be 1 .. 128, got {args.beam_width}')
@@ -133,6 +138,7 @@ def main():
     wer = WER(vocabulary=asr_model.decoder.vocabulary)
     hyps, refs, words, utt_scores, beam_scores, lm_scores = [], [], [], [], [], []
     lm_kw = dict(lm=args.lm_path, alpha=alpha, beta=beta) if args.lm_path is not None else {}
+    aligned, items = [], getattr(asr_model.test_dataloader().dataset, 'items', [])
     audio_s, t0 = 0.0, time.time()
     for i, batch in enumerate(asr_model.test_dataloader()):
         if i == args.eval_early_stop:
@@ -151,6 +157,12 @@ def main():
             for h in asr_model.decode(input_signal=batch[0].float(), input_signal_length=batch[1]):
                 words.append([list(w) for w in h.words])
                 utt_scores.append(h.utt_score)
+        if args.align:                                       # the reference texts' own labels, one k_align launch per batch
+            ref_ids = [row[:int(n)].tolist() for row, n in zip(batch[2].cpu(), batch[3].cpu())]
+            for h in asr_model.align(input_signal=batch[0].float(), input_signal_length=batch[1], labels=ref_ids):
+                k = len(aligned)
+                aligned.append(dict(audio_filepath=items[k][0] if not args.shuffle and k < len(items) else None, text=h.text,
+                                    ctc_score=h.ctc_score, utt_score=h.utt_score, words=[list(w) for w in h.words]))
         for row in batch[2].cpu().numpy():
             refs.append(''.join(labels_map[c] for c in row))
         audio_s += float(batch[1].sum()) / 16000.0
@@ -170,6 +182,13 @@ def main():
             if args.lm_path is not None:
                 extra.update(lm_path=args.lm_path, alpha=alpha, beta=beta, lm_score=lm_scores)
             json.dump(dict(hypotheses=hyps, references=refs, wer=wer_value, path=served, **extra), f)
+    if args.align:
+        import json
+        with open(args.align, 'w', encoding='utf-8') as f:
+            for rec in aligned:                                  # a text that is not alignable has scores -inf: written as null
+                rec = {k: (None if isinstance(v, float) and v == float('-inf') else v) for k, v in rec.items()}
+                f.write(json.dumps(rec, ensure_ascii=False) + '\n')
+        print(f'aligned {len(aligned)} transcripts ({sum(1 for r in aligned if r["words"])} with word times) -> {args.align}')
     print(f'RTFx (incl. host data loading): {audio_s / max(wall, 1e-9):.1f}  ({audio_s:.1f} s audio in {wall:.2f} s)')
 
 

@@ -432,7 +432,7 @@ class EncDecCTCModel(nn.Module):
 
     @torch.no_grad()
     def decode(self, input_signal=None, input_signal_length=None, processed_signal=None, processed_signal_length=None,
-               beam_width=None, n_best=1, cutoff_top_n=40, lm=None, alpha=0.0, beta=0.0):
+               beam_width=None, n_best=1, cutoff_top_n=40, lm=None, alpha=0.0, beta=0.0, timestamps=False):
         """Greedy CTC hypotheses of one batch (an extension of the reference's API): List[qasr.ctc.Hypothesis] with the
         text, every label's start / end time and confidence (best frame log-probability of its run), word groups and the
         log-probability of the greedy path.  Decoding stops at each utterance's encoded length.  On the static engine the
@@ -443,9 +443,12 @@ class EncDecCTCModel(nn.Module):
         beam_width=W (1 .. 128) replaces the greedy collapse by a CTC prefix beam search without a language model
         (qasr.beam): the forward runs with log-probabilities, then k_topn (the cutoff_top_n <= 64 best classes per frame)
         and k_beam follow on the same stream - on the static engine, a reserved engine and the dynamic path alike; the host
-        modules run the NumPy twin.  The hypotheses carry text, labels and utt_score (the beam score); their time lists are
-        empty, since a prefix has no single alignment.  n_best > 1 (<= W) returns, per utterance, the list of its best
-        hypotheses, best first.
+        modules run the NumPy twin.  The hypotheses carry text, labels and utt_score (the beam score).  A prefix has no
+        single alignment, so their time lists are empty unless timestamps=True: then the n_best label rows of the beam are
+        aligned against the same log-probabilities (the Viterbi alignment of qasr.align; one more launch, k_align, over the
+        beam's device buffers as they lie) and start_s / end_s / score / words are filled as for greedy hypotheses;
+        utt_score stays the beam score.  n_best > 1 (<= W) returns, per utterance, the list of its best hypotheses, best
+        first.
 
         lm=<path of an ARPA file, or a qasr.ngram.NgramLM> (needs beam_width) adds the n-gram model with the weights alpha
         (0 .. 16) and beta (|beta| <= 16) as ctc_decoders' Scorer does (qasr.beam.LM_RULES; k_beam_lm on the device): word
@@ -459,7 +462,7 @@ class EncDecCTCModel(nn.Module):
             beam_width, n_best, cutoff_top_n = self._beam_args(beam_width, n_best, cutoff_top_n)      # refused before any launch
             lm = self._lm_args(lm, alpha, beta)
             return self._beam_decode(self._forward(input_signal, input_signal_length, processed_signal, processed_signal_length),
-                                     beam_width, n_best, cutoff_top_n, lm, alpha, beta)
+                                     beam_width, n_best, cutoff_top_n, lm, alpha, beta, bool(timestamps))
         res = self._forward(input_signal, input_signal_length, processed_signal, processed_signal_length, decode=True)
         return qctc.to_hypotheses(res, self.decoder.vocabulary, self.seconds_per_frame())
 
@@ -495,7 +498,7 @@ class EncDecCTCModel(nn.Module):
                              f'{len(self.decoder.vocabulary)}')
         return lm
 
-    def _beam_decode(self, fwd, beam_width, n_best, cutoff_top_n, lm=None, alpha=0.0, beta=0.0):
+    def _beam_decode(self, fwd, beam_width, n_best, cutoff_top_n, lm=None, alpha=0.0, beta=0.0, timestamps=False):
         """decode(beam_width=) behind any path's (log_probs, encoded lengths, tokens); the arguments passed _beam_args"""
         from qasr import beam as qbeam
         log_probs, enc_len = fwd[0], fwd[1]
@@ -508,7 +511,80 @@ class EncDecCTCModel(nn.Module):
             res = qbeam.search_host(log_probs.float().numpy(), enc_len.numpy(), blank, beam_width, n_best, cutoff_top_n, lm,
                                     alpha, beta)
         hyps = qbeam.to_hypotheses(res, self.decoder.vocabulary)
+        if timestamps:
+            self._beam_timestamps(hyps, res, log_probs, enc_len, blank, n_best)
         return hyps if n_best > 1 else [h[0] for h in hyps]          # a beam over real candidates never dies: h[0] exists
+
+    def _beam_timestamps(self, hyps, res, log_probs, enc_len, blank, n_best):
+        """decode(beam_width=, timestamps=True): the beam's label rows [B][n_best][T] are the targets as they lie (n_best
+        problems per utterance, row pitch T; rows past n_hyps are empty targets and are dropped with their hypotheses)"""
+        from qasr import align as qalign
+        B, nb, T = res.labels.shape
+        ml = min(T, qalign.MAX_LABELS)                           # a hypothesis beyond the cap is not alignable: no times
+        if log_probs.is_cuda:
+            from qasr import engine as qengine
+            tg = res.labels.view(B * nb, T) if ml == T else res.labels[:, :, :ml].contiguous().view(B * nb, ml)
+            ares = qengine.ctc_align(log_probs.float(), enc_len, tg, res.n_labels.view(B * nb), blank, problems_per_utt=nb,
+                                     want_total=False)
+        else:
+            ares = qalign.align_host(log_probs.float().numpy(), enc_len.numpy(), res.labels.reshape(B * nb, T)[:, :ml],
+                                     res.n_labels.reshape(B * nb), blank, problems_per_utt=nb, want_total=False)
+        timed = qalign.to_hypotheses(ares, self.decoder.vocabulary, self.seconds_per_frame())
+        for b, row in enumerate(hyps):
+            for h, hyp in enumerate(row):
+                t = timed[b * nb + h]
+                hyp.start_s, hyp.end_s, hyp.score, hyp.words = t.start_s, t.end_s, t.score, t.words
+
+    @torch.no_grad()
+    def align(self, input_signal=None, input_signal_length=None, processed_signal=None, processed_signal_length=None,
+              texts=None, labels=None):
+        """Forced alignment and CTC scoring of GIVEN transcripts (an extension of the reference's API): one
+        qasr.ctc.Hypothesis per utterance with the text's labels, every label's start / end time and confidence and the word
+        groups of its best (Viterbi) alignment against this batch's log-probabilities, utt_score = the log-probability of that
+        alignment and ctc_score = the CTC log-likelihood of the text over all alignments (qasr.align states the rules).  The
+        signal arguments are forward()'s; exactly one of `texts` (strings: they pass through the CharParser the data layer
+        uses - the model's vocabulary, the 'en' normaliser) and `labels` (one sequence of label ids per utterance).  A text the
+        parser rejects, an id outside the vocabulary or a transcript above qasr.align.MAX_LABELS labels raises ValueError naming
+        its index before anything runs.  Runs behind every path decode(beam_width=) runs behind - static engine, reserved
+        engine, dynamic path (k_align on the same stream), host modules (the NumPy twin).  A transcript with more labels (plus
+        adjacent repeats) than the utterance has frames is not alignable: empty time lists, scores -inf."""
+        from qasr import align as qalign
+        if (texts is None) == (labels is None):
+            raise ValueError('align: give exactly one of texts and labels')
+        vocab = list(self.decoder.vocabulary)
+        blank = len(vocab)
+        if texts is not None:
+            from nemo.collections.asr.parts import parsers
+            parser = parsers.make_parser(labels=vocab, name='en', unk_id=-1, blank_id=-1, do_normalize=True)
+            rows = []
+            for i, text in enumerate(texts):
+                ids = parser(text) if isinstance(text, str) else None
+                if ids is None:
+                    raise ValueError(f'align: text {i} is rejected by the parser')
+                rows.append(ids)
+        else:
+            rows = [[int(c) for c in r] for r in labels]
+        for i, ids in enumerate(rows):
+            if any(not 0 <= c < blank for c in ids):
+                raise ValueError(f'align: transcript {i} holds a label outside the vocabulary of {blank} labels')
+            if len(ids) > qalign.MAX_LABELS:
+                raise ValueError(f'align: transcript {i} has {len(ids)} labels, at most {qalign.MAX_LABELS} can be aligned')
+        ref = input_signal if input_signal is not None else processed_signal
+        if ref is not None and len(rows) != ref.shape[0]:
+            raise ValueError(f'align: {len(rows)} transcripts for a batch of {ref.shape[0]} utterances')
+        fwd = self._forward(input_signal, input_signal_length, processed_signal, processed_signal_length)
+        log_probs, enc_len = fwd[0], fwd[1]
+        tg = np.full((len(rows), max(1, max(len(r) for r in rows))), blank, dtype=np.int32)
+        for i, ids in enumerate(rows):
+            tg[i, :len(ids)] = ids
+        tl = np.array([len(r) for r in rows], dtype=np.int32)
+        if log_probs.is_cuda:
+            from qasr import engine as qengine
+            res = qengine.ctc_align(log_probs.float(), enc_len, torch.from_numpy(tg).to(log_probs.device),
+                                    torch.from_numpy(tl).to(log_probs.device), blank)
+        else:
+            res = qalign.align_host(log_probs.float().numpy(), enc_len.numpy(), tg, tl, blank)
+        return qalign.to_hypotheses(res, vocab, self.seconds_per_frame())
 
     def _collapse(self, log_probs, tokens, enc_len):
         """decode() behind a path that returned log-probabilities: frame scores = log_probs at the tokens"""

@@ -10,8 +10,8 @@ when a space ends it, every extension adding alpha * ln p + beta (words that the
 history), the history starting at <s>, </s> never scored, and in word mode the unfinished last word scored after the
 last frame with the beam re-ordered.  Not followed: the arithmetic (fixed point, qasr.beam.LM_RULES, so that device and
 host agree on every bit), KenLM binary files (export ARPA), the dictionary FST that restricts prefixes to spellable
-words, vocabulary pruning by cumulative probability (`cutoff_prob` must be 1.0), timestamps for beam hypotheses, orders
-above 6.  The reported score is
+words, vocabulary pruning by cumulative probability (`cutoff_prob` must be 1.0), orders above 6.  The reference's
+(score, string) tuples have no place for times: EncDecCTCModel.decode(beam_width=, timestamps=True) gives them.  The reported score is
 the search score including the model's share, where ctc_decoders subtracts it again."""
 import numpy as np
 import torch

@@ -1,0 +1,192 @@
+"""CTC forced alignment and transcript scoring in fixed point: the host statement of k_align (csrc/qasr_align.hip,
+include/qasr.h) and the step from its outputs to strings, label times and word times.  NumPy only: no GPU, no native library.
+
+`align_host` is the CPU path of EncDecCTCModel.align / decode(beam_width=, timestamps=True) and the yardstick the GPU tests
+compare k_align with, byte for byte.  The arithmetic (quantize, lae, its table, NEG) is that of qasr.beam and is not restated.
+
+RULES.  A problem p is a pair (utterance u = p // K, target y[0 .. L)), K = problems per utterance.  Frames run t < lim,
+lim = min(max(lens[u], 0), T) (lens None: T).  States run s = 0 .. 2L; lab(s) = blank for even s and y[(s - 1) / 2] for odd s;
+q(t, s) = quantize(logp[u][t][lab(s)]).  Two int64 rows V (Viterbi) and A (forward) are NEG except V[0] = A[0] = q(0, 0) and,
+if L > 0, V[1] = A[1] = q(0, 1).  For t >= 1 the predecessors of s are s, s - 1 (s >= 1) and s - 2 (only if s is odd, s >= 3
+and y[(s - 1) / 2] != y[(s - 3) / 2]); a missing predecessor is NEG.
+  Viterbi: best = the maximum of the three; ties keep the smaller step (stay, then s - 1, then s - 2, each replacing only on
+    strict >).  V'[s] = NEG if best == NEG, else best + q(t, s); the backpointer is the step 0, 1 or 2.
+  Forward: x = lae(lae(A[s], A[s - 1]), A[s - 2]) in exactly this order (lae is not associative); A'[s] = NEG if x == NEG, else
+    x + q(t, s).  Nothing is ever added to NEG.
+End: the final state is 2L if V[2L] > V[2L - 1], else 2L - 1 (L == 0: state 0); path_score = V[final];
+total = lae(A[2L], A[2L - 1]) (L == 0: A[0]).  The backpointers are walked from t = lim - 1 down.  For label i, start[i] is the
+first frame whose state is 2i + 1 and nframes[i] the number of such frames (one run: the path is monotone); score[i] is the
+maximum of the float32 logp[u][t][y[i]] over those frames in the `_order_key` order (exact; k_ctc's rule).
+Not alignable (ok[p] = 0; start, nframes and score rows zero; path_score = total = NEG): V[final] == NEG (fewer frames than
+labels plus adjacent repeats); lim == 0 with L > 0; L < 0, L above the row pitch or above MAX_LABELS; a label outside [0, C)
+or equal to blank.  lim == 0 with L == 0 is ok = 1 with both scores 0."""
+from dataclasses import dataclass
+from typing import List, Sequence
+
+import numpy as np
+
+from .beam import MAX_T, NEG, ONE, _order_key, lae, lae_table, quantize
+
+MAX_LABELS = 2048                       # QASR_ALIGN_MAX_LABELS
+
+
+@dataclass
+class AlignResult:
+    """Outputs of one alignment, row pitch max_labels (arrays: NumPy on the host, torch tensors from the device binding).
+    labels [P, max_labels] int32 and n_labels [P] int32 are the targets as given; start / nframes [P, max_labels] int32 and
+    score [P, max_labels] float32 (tails 0) have the meaning of qasr.ctc.CtcResult's; path_score / total [P] int64 fixed
+    point (/ 2^16 = nats: the best alignment's and the CTC log-likelihood; total None when not requested); ok [P] int32."""
+    labels: object
+    n_labels: object
+    start: object = None
+    nframes: object = None
+    score: object = None
+    path_score: object = None
+    total: object = None
+    ok: object = None
+    blank: int = -1
+    problems_per_utt: int = 1
+
+
+def _align_one(lp, lim, y, blank, tab, want_total):
+    """one problem with a valid target y (L >= 0) over lp float32 [T, C]; returns (ok, start, nframes, score, path, total)"""
+    L = len(y)
+    i64 = np.int64
+    if lim == 0:
+        return (1, None, None, None, 0, 0) if L == 0 else (0, None, None, None, NEG, NEG)
+    S = 2 * L + 1
+    lab = np.full(S, blank, dtype=np.int64)
+    lab[1::2] = y
+    skip = np.zeros(S, dtype=bool)
+    if L > 1:
+        skip[3::2] = y[1:] != y[:-1]
+    q = quantize(lp[:lim][:, lab])                                  # int32 [lim, S]
+    negs = np.full(2, NEG, i64)
+
+    def first():
+        r = np.full(S, NEG, i64)
+        r[:min(2, S)] = q[0, :min(2, S)]
+        return r
+
+    V = first()
+    bp = np.zeros((lim, S), dtype=np.uint8)
+    for t in range(1, lim):
+        ext = np.concatenate([negs, V])
+        a1, a2 = ext[1:S + 1], np.where(skip, ext[:S], NEG)
+        best, step = V, np.zeros(S, dtype=np.uint8)
+        m = a1 > best
+        best, step = np.where(m, a1, best), np.where(m, 1, step)
+        m = a2 > best
+        best, step = np.where(m, a2, best), np.where(m, 2, step)
+        live = best != NEG
+        V = np.where(live, np.where(live, best, 0) + q[t].astype(i64), NEG)
+        bp[t] = step
+    fin = 0 if L == 0 else (2 * L if V[2 * L] > V[2 * L - 1] else 2 * L - 1)
+    path_score = int(V[fin])
+    if path_score == NEG:
+        return 0, None, None, None, NEG, NEG
+    total = NEG
+    if want_total:
+        A = first()
+        for t in range(1, lim):
+            ext = np.concatenate([negs, A])
+            x = lae(lae(A, ext[1:S + 1], tab), np.where(skip, ext[:S], NEG), tab)
+            live = x != NEG
+            A = np.where(live, np.where(live, x, 0) + q[t].astype(i64), NEG)
+        total = int(A[0]) if L == 0 else int(lae(A[2 * L], A[2 * L - 1], tab))
+    states = np.empty(lim, dtype=np.int64)
+    s = fin
+    for t in range(lim - 1, -1, -1):
+        states[t] = s
+        s -= int(bp[t, s])
+    start = np.zeros(L, dtype=np.int32)
+    nframes = np.zeros(L, dtype=np.int32)
+    score = np.zeros(L, dtype=np.float32)
+    fr = np.flatnonzero(states & 1)                                 # the label frames, in time (= label) order
+    if L:
+        idx = states[fr] >> 1
+        first_of = np.flatnonzero(np.concatenate([[True], idx[1:] != idx[:-1]]))
+        start[idx[first_of]] = fr[first_of]
+        nframes[idx[first_of]] = np.diff(np.concatenate([first_of, [len(fr)]]))
+        best = np.maximum.reduceat(_order_key(lp[fr, np.asarray(y, dtype=np.int64)[idx]]), first_of)
+        score[idx[first_of]] = (best ^ ((best >> 31) & np.int32(0x7fffffff))).view(np.float32)
+    return 1, start, nframes, score, path_score, total
+
+
+def align_host(log_probs, lens, targets, target_lens, blank, problems_per_utt=1, want_total=True) -> AlignResult:
+    """log_probs float32 [B, T, C]; lens int [B] or None; targets int32 [P, max_labels] and target_lens int32 [P] with
+    P = B * problems_per_utt (problem p belongs to utterance p // problems_per_utt); blank: the blank id.  The RULES of the
+    module docstring; want_total=False skips the forward pass (total None)."""
+    lp = np.asarray(log_probs, dtype=np.float32)
+    if lp.ndim != 3 or min(lp.shape) < 1:
+        raise ValueError(f'align_host: log_probs must be [B, T, C] with B, T, C >= 1, got {lp.shape}')
+    B, T, C = lp.shape
+    K = int(problems_per_utt)
+    tg = np.asarray(targets)
+    tl = np.asarray(target_lens)
+    if K < 1 or tg.ndim != 2 or tg.shape[0] != B * K or tl.shape != (B * K,):
+        raise ValueError(f'align_host: targets must be [B * problems_per_utt, max_labels] with one length each, got '
+                         f'{tg.shape} / {tl.shape} for B {B}, problems_per_utt {K}')
+    P, ML = tg.shape
+    if not 1 <= ML <= MAX_LABELS:
+        raise ValueError(f'align_host: max_labels (the row pitch of targets) must be 1 .. {MAX_LABELS}, got {ML}')
+    if T > MAX_T:
+        raise ValueError(f'align_host: at most {MAX_T} frames, got {T}')
+    blank = int(blank)
+    if not 0 <= blank < C:
+        raise ValueError(f'align_host: blank {blank} is outside [0, {C})')
+    tg = tg.astype(np.int32)
+    tab = lae_table()
+    start = np.zeros((P, ML), dtype=np.int32)
+    nframes = np.zeros((P, ML), dtype=np.int32)
+    score = np.zeros((P, ML), dtype=np.float32)
+    path_score = np.full(P, NEG, dtype=np.int64)
+    total = np.full(P, NEG, dtype=np.int64)
+    ok = np.zeros(P, dtype=np.int32)
+    for p in range(P):
+        u = p // K
+        lim = T if lens is None else int(min(max(int(lens[u]), 0), T))
+        L = int(tl[p])
+        if L < 0 or L > ML:
+            continue
+        y = tg[p, :L]
+        if L and (y.min() < 0 or y.max() >= C or (y == blank).any()):
+            continue
+        ok[p], st, nf, sc, ps, tot = _align_one(lp[u], lim, y, blank, tab, want_total)
+        if ok[p]:
+            path_score[p], total[p] = ps, tot
+            if st is not None:
+                start[p, :L], nframes[p, :L], score[p, :L] = st, nf, sc
+    return AlignResult(tg, tl.astype(np.int32), start, nframes, score, path_score, total if want_total else None, ok, blank, K)
+
+
+def _np(x):
+    if x is None:
+        return None
+    if hasattr(x, 'detach'):
+        x = x.detach().cpu().numpy()
+    return np.asarray(x)
+
+
+def to_hypotheses(result: AlignResult, vocabulary: Sequence[str], seconds_per_frame: float) -> List:
+    """One qasr.ctc.Hypothesis per problem, through qasr.ctc.to_hypotheses (the code greedy decoding uses, so label and word
+    times mean the same): text and labels are the target's, start_s / end_s / score / words come from the best alignment,
+    utt_score = path_score / 2^16 and ctc_score = total / 2^16 (None when total was not requested).  A problem that is not
+    alignable (ok == 0) has empty time lists, score None and utt_score = ctc_score = -inf."""
+    from . import ctc as qctc
+    labels, n_labels, ok = _np(result.labels), _np(result.n_labels), _np(result.ok)
+    path, total = _np(result.path_score), _np(result.total)
+    n = np.clip(n_labels, 0, labels.shape[1]).astype(np.int32)
+    view = qctc.CtcResult(labels, np.where(ok != 0, n, 0).astype(np.int32), _np(result.start), _np(result.nframes),
+                          _np(result.score), None, result.blank)
+    vocab = list(vocabulary)
+    hyps = qctc.to_hypotheses(view, vocab, seconds_per_frame)
+    for p, h in enumerate(hyps):
+        if ok[p]:
+            h.utt_score = float(path[p]) / ONE
+            h.ctc_score = None if total is None else float(total[p]) / ONE
+        else:
+            ids = [int(i) for i in labels[p, :n[p]]]
+            text = ''.join(vocab[i] if 0 <= i < len(vocab) else '' for i in ids)
+            hyps[p] = qctc.Hypothesis(text, ids, [], [], None, float('-inf'), [], None, float('-inf'))
+    return hyps

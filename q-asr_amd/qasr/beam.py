@@ -403,7 +403,8 @@ def _np(x):
 def to_hypotheses(result: BeamResult, vocabulary: Sequence[str]) -> List[list]:
     """Per utterance the list of its hypotheses, best first, as qasr.ctc.Hypothesis: text, labels and utt_score = the beam
     score (log-probability of the prefix, summed over its alignments inside the beam).  start_s / end_s / score / words stay
-    empty: a prefix stands for many alignments, so no label has one time or one frame score."""
+    empty here: a prefix stands for many alignments, so no label has one time or one frame score (qasr.align gives the times of
+    its best alignment: decode(beam_width=, timestamps=True))."""
     from .ctc import Hypothesis
     labels, n_labels, score, n_hyps = _np(result.labels), _np(result.n_labels), _np(result.score), _np(result.n_hyps)
     lm_score = None if result.lm_score is None else _np(result.lm_score)

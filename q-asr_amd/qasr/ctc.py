@@ -36,6 +36,7 @@ class Hypothesis:
     utt_score: Optional[float]              # log-probability of the greedy path
     words: List[Tuple[str, float, float, Optional[float]]] = field(default_factory=list)
     lm_score: Optional[float] = None        # beam search with a language model: the model's share of utt_score
+    ctc_score: Optional[float] = None       # forced alignment (qasr.align): the CTC log-likelihood of the text, all alignments
 
 
 def _order_key(x):

@@ -17,7 +17,7 @@ SYMBOLS = ['qasr_blob_check', 'qasr_engine_create', 'qasr_engine_create_ex', 'qa
            'qasr_dw_conv_acc', 'qasr_dense_conv_acc', 'qasr_requant', 'qasr_dyn_range', 'qasr_dyn_range_percentile', 'qasr_dyn_residue_codes', 'qasr_dyn_act_params', 'qasr_dyn_requant',
            'qasr_dyn_quant_in', 'qasr_dyn_conv_params', 'qasr_sep_layer', 'qasr_quantile2', 'qasr_quantile_workspace_bytes', 'qasr_debug_prof',
            'qasr_debug_timeline', 'qasr_ctc_collapse', 'qasr_engine_attach_ctc', 'qasr_ctc_topn', 'qasr_ctc_beam_workspace_bytes', 'qasr_ctc_beam',
-           'qasr_lm_check', 'qasr_ctc_beam_lm',
+           'qasr_lm_check', 'qasr_ctc_beam_lm', 'qasr_ctc_align_workspace_bytes', 'qasr_ctc_align',
            'qasr_engine_reserve', 'qasr_engine_forward_ragged', 'qasr_engine_forward_ragged_audio', 'qasr_engine_ragged_stats',
            'qasr_ragged_bucket_frames', 'qasr_ragged_envelope_frames',
            'qasr_last_error', 'qasr_version']
@@ -152,6 +152,10 @@ def load_library():
     if hasattr(lib, 'qasr_ctc_beam_lm'):        # (likewise)
         lib.qasr_lm_check.argtypes = [C.c_char_p, sz, i32]
         lib.qasr_ctc_beam_lm.argtypes = [vp, C.POINTER(BeamLmArgs)]
+    if hasattr(lib, 'qasr_ctc_align'):          # (likewise)
+        lib.qasr_ctc_align.argtypes = [vp, C.POINTER(AlignArgs)]
+        lib.qasr_ctc_align_workspace_bytes.argtypes = [i32, i32, i32]
+        lib.qasr_ctc_align_workspace_bytes.restype = sz
     if hasattr(lib, 'qasr_engine_reserve'):     # (likewise)
         lib.qasr_engine_reserve.argtypes = [vp, C.POINTER(ReserveOpts)]
         lib.qasr_engine_forward_ragged.argtypes = [vp, vp, vp, vp, i32, i32, C.POINTER(RaggedOut)]
@@ -430,6 +434,78 @@ def ctc_beam_search(log_probs, lens=None, blank=None, beam_width=16, n_best=None
         fixed_weights(alpha, beta)                              # refused before the first launch
     cid, cq = ctc_topn(log_probs, lens, cutoff_top_n, stream=stream)
     return ctc_beam(cid, cq, lens, blank, beam_width, n_best, stream=stream, lm=lm, alpha=alpha, beta=beta)
+
+
+class AlignArgs(C.Structure):
+    """qasr_ctc_align_args (include/qasr.h)"""
+    _fields_ = ([('struct_size', C.c_uint32)] + [(n, C.c_int32) for n in ('B', 'T', 'C', 'P', 'K', 'blank', 'max_labels')] +
+                [('pitch_utt', C.c_int64), ('pitch_frame', C.c_int64)] +
+                [(n, C.c_void_p) for n in ('log_probs', 'lens', 'targets', 'target_lens')] +
+                [('lae_entries', C.c_uint32), ('reserved', C.c_uint32), ('lae_table', C.c_void_p), ('workspace', C.c_void_p),
+                 ('workspace_bytes', C.c_size_t)] +
+                [(n, C.c_void_p) for n in ('start', 'nframes', 'score', 'path_score', 'total', 'ok')])
+
+
+def ctc_align_workspace_bytes(P, T, max_labels):
+    return int(load_library().qasr_ctc_align_workspace_bytes(int(P), int(T), int(max_labels)))
+
+
+def ctc_align(log_probs, lens, targets, target_lens, blank, problems_per_utt=1, want_total=True, workspace=None, out=None,
+              stream=None):
+    """qasr_ctc_align: CTC forced alignment and scoring of given label sequences on the device (k_align, one launch on the
+    current stream, no host synchronisation); equal to qasr.align.align_host byte for byte.  log_probs: a cuda float32
+    tensor [B, T, C] (any utterance / frame pitch, classes contiguous); lens int32 [B] optional; targets cuda int32
+    [P, max_labels] with target_lens int32 [P], P = B * problems_per_utt (problem p belongs to utterance
+    p // problems_per_utt).  want_total=False skips the forward pass (total None).  Returns a qasr.align.AlignResult of cuda
+    tensors.  workspace: a caller-owned uint8 tensor of ctc_align_workspace_bytes(P, T, max_labels) bytes (None: allocated by
+    torch here); `out`: a caller-owned AlignResult whose start / nframes / score / path_score / total may each be None."""
+    from .align import AlignResult, MAX_LABELS
+    from .beam import TAB_ENTRIES
+    lib = load_library()
+    assert log_probs.is_cuda and log_probs.dim() == 3 and log_probs.dtype == torch.float32, \
+        'ctc_align: log_probs must be a cuda float32 tensor [B, T, C]'
+    dev = log_probs.device
+    lp = log_probs if log_probs.stride(2) == 1 or log_probs.shape[2] == 1 else log_probs.contiguous()
+    ln = None if lens is None else lens.to(device=dev, dtype=torch.int32).contiguous()
+    B, T, Cn = lp.shape
+    K = int(problems_per_utt)
+    assert targets.dim() == 2 and target_lens.dim() == 1, 'ctc_align: targets must be [P, max_labels], target_lens [P]'
+    tg = targets.to(device=dev, dtype=torch.int32).contiguous()
+    tl = target_lens.to(device=dev, dtype=torch.int32).contiguous()
+    P, ML = tg.shape
+    if ML > MAX_LABELS:                                             # refused here: the kernel holds at most this many labels
+        raise ValueError(f'ctc_align: max_labels (the row pitch of targets) must be 1 .. {MAX_LABELS}, got {ML}')
+    if tl.shape[0] != P:
+        raise ValueError(f'ctc_align: {P} target rows but {tl.shape[0]} lengths')
+    if out is None:
+        i32 = dict(device=dev, dtype=torch.int32)
+        out = AlignResult(labels=tg, n_labels=tl, start=torch.empty(P, ML, **i32), nframes=torch.empty(P, ML, **i32),
+                          score=torch.empty(P, ML, device=dev, dtype=torch.float32),
+                          path_score=torch.empty(P, device=dev, dtype=torch.int64),
+                          total=torch.empty(P, device=dev, dtype=torch.int64) if want_total else None,
+                          ok=torch.empty(P, **i32), blank=int(blank), problems_per_utt=K)
+    for n, dt, shape in (('start', torch.int32, (P, ML)), ('nframes', torch.int32, (P, ML)), ('score', torch.float32, (P, ML)),
+                         ('path_score', torch.int64, (P,)), ('total', torch.int64, (P,)), ('ok', torch.int32, (P,))):
+        t = getattr(out, n)
+        assert t is None or (t.is_cuda and t.is_contiguous() and t.dtype == dt and tuple(t.shape) == shape), f'ctc_align: out.{n}'
+    assert out.ok is not None, 'ctc_align: out.ok is required'
+    if workspace is None:
+        workspace = torch.empty(max(ctc_align_workspace_bytes(P, T, ML), 8), device=dev, dtype=torch.uint8)
+    tab = lae_table_device(dev) if out.total is not None else None
+    a = AlignArgs()
+    a.struct_size = C.sizeof(AlignArgs)
+    a.B, a.T, a.C, a.P, a.K, a.blank, a.max_labels = B, T, Cn, P, K, int(blank), ML
+    a.pitch_utt, a.pitch_frame = (lp.stride(0) if B > 1 else max(lp.stride(0), T * lp.stride(1))), lp.stride(1)
+    a.log_probs, a.lens, a.targets, a.target_lens = lp.data_ptr(), 0 if ln is None else ln.data_ptr(), tg.data_ptr(), tl.data_ptr()
+    a.lae_entries, a.lae_table = TAB_ENTRIES, 0 if tab is None else tab.data_ptr()
+    a.workspace, a.workspace_bytes = workspace.data_ptr(), workspace.numel() * workspace.element_size()
+    for n in ('start', 'nframes', 'score', 'path_score', 'total', 'ok'):
+        t = getattr(out, n)
+        setattr(a, n, 0 if t is None else t.data_ptr())
+    with torch.cuda.device(dev):
+        _check(lib.qasr_ctc_align(_stream_ptr(stream), C.byref(a)), 'qasr_ctc_align')
+    out._keep = (lp, ln, tg, tl, workspace, tab)
+    return out
 
 
 class Engine:
