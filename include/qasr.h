@@ -395,6 +395,54 @@ typedef struct qasr_ctc_beam_lm_args {
 } qasr_ctc_beam_lm_args;
 int qasr_ctc_beam_lm(void* stream, const qasr_ctc_beam_lm_args* args);
 
+/* ---- CTC prefix beam search with phrase boosting ("hot words") -----------------------------------------------------------
+ * The search above, with or without the n-gram model, biased towards a caller-supplied list of phrases: every extension of
+ * a prefix by a label moves an automaton over the compiled phrases from state s to s' = delta(s, label) and adds
+ * pot[s'] - pot[s] + bank[s'] (units of 2^-16 nat) where the model's term goes; after the last frame every entry takes a
+ * virtual space (whole words), loses the pot of its unfinished match and the beam is re-ordered once.  The rules are
+ * BOOST_RULES of qasr/boost.py, which k_beam_boost follows bit for bit; the packed set (qasr.boost.PhraseSet.pack) is a
+ * 128-byte header (magic 'QBS1', version, total bytes, n_nodes, n_labels, start state, whole_words, table capacity, probe
+ * bound, zeros), an open-addressed table of (node, label, next, 0) slots, nodes (pot_q, bank_q) and the dense root row.
+ * boost_score i64 [B][n_best] receives each hypothesis' sum of boost terms (unused rows 0); score includes it, lm_score
+ * stays the model's share alone.
+ * qasr_boost_check validates a packed set ON THE HOST (no GPU is touched): QASR_OK, or QASR_ERR_BLOB (qasr_last_error names
+ * the field) for a bad magic, version or size, an n_labels other than the caller's, a capacity that is no power of two, a
+ * probe bound outside 1 .. QASR_LM_MAX_PROBE, a start state, node, label or next out of range, a pot or bank outside
+ * 0 .. 2^30, a non-zero reserved word, or a stored key that its probe sequence does not reach.  The kernel trusts `boost`.
+ * qasr_ctc_beam_boost: lm == NULL searches without a model (alpha_q, beta_q and lm_score are then ignored; space is still
+ * needed for whole words).  QASR_ERR_ARG with nothing launched and no output written for everything qasr_ctc_beam_lm refuses
+ * (the model's own fields only with a model), and for a NULL or unaligned (16 bytes) boost, boost_bytes < 128, a NULL
+ * boost_score, whole_words != 0 with space < 0, space < -1 or space == blank.  whole_words must repeat the header's flag (the
+ * header lies in device memory, which this call does not read): a disagreement, like a header that does not fit
+ * boost_bytes, ends the search empty (n_hyps 0).  Workspace: qasr_ctc_beam_workspace_bytes, unchanged. */
+#define QASR_BOOST_MAX_PHRASE 64
+int qasr_boost_check(const void* blob, size_t bytes, int n_labels);
+typedef struct qasr_ctc_beam_boost_args {
+  uint32_t struct_size;
+  int32_t B, T, N, beam_width, n_best, blank;
+  uint32_t lae_entries;        /* QASR_BEAM_TABLE_ENTRIES */
+  const int32_t* cand_id;
+  const int32_t* cand_q;
+  const int32_t* lens;         /* optional */
+  const uint16_t* lae_table;
+  void* workspace;             /* qasr_ctc_beam_workspace_bytes(B, T, beam_width) */
+  size_t workspace_bytes;
+  int32_t* labels;
+  int32_t* n_labels;
+  int64_t* score;
+  int32_t* n_hyps;
+  const void* lm;              /* device memory: a packed model that passed qasr_lm_check, or NULL: no model */
+  size_t lm_bytes;
+  int32_t alpha_q, beta_q;
+  int32_t space;               /* the label that ends a word, -1: none (with a model: must agree with its mode) */
+  int32_t whole_words;         /* the whole_words flag of the set's header */
+  int64_t* lm_score;           /* with a model */
+  const void* boost;           /* device memory: a packed phrase set that passed qasr_boost_check */
+  size_t boost_bytes;
+  int64_t* boost_score;
+} qasr_ctc_beam_boost_args;
+int qasr_ctc_beam_boost(void* stream, const qasr_ctc_beam_boost_args* args);
+
 /* ---- CTC forced alignment and transcript scoring ---------------------------------------------------------------------
  * For a GIVEN label sequence: its best alignment against the log-probabilities (Viterbi: per label the first frame, the
  * frame count and the best frame log-probability of its run, the outputs of k_ctc for a text instead of the arg-max) and

@@ -1172,6 +1172,88 @@ int qasr_ctc_beam_lm(void* stream, const qasr_ctc_beam_lm_args* a) {
   return QASR_OK;
 }
 
+// Host-only validation of a packed phrase set (qasr/boost.py states the layout); k_beam_boost trusts what passes here.
+int qasr_boost_check(const void* blob, size_t bytes, int n_labels) {
+  enum { HDR = 32 };
+  const int32_t LIM = 1 << 30;
+  if (!blob) return fail(QASR_ERR_BLOB, "boost_check: blob is NULL");
+  if (bytes < HDR * 4 || bytes > (size_t)INT32_MAX) return fail(QASR_ERR_BLOB, "boost_check: %zu bytes is no phrase set", bytes);
+  if (((uintptr_t)blob & 3) != 0) return fail(QASR_ERR_BLOB, "boost_check: blob is not 4-byte aligned");
+  const int32_t* h = (const int32_t*)blob;
+  if (h[0] != 0x31534251 || h[1] != 1) return fail(QASR_ERR_BLOB, "boost_check: magic %#x / version %d", (unsigned)h[0], h[1]);
+  const int n_nodes = h[3], start = h[5], whole = h[6], cap = h[7], probe = h[8];
+  if (h[4] != n_labels || n_labels < 1) return fail(QASR_ERR_BLOB, "boost_check: packed for %d labels, asked for %d", h[4], n_labels);
+  if (n_nodes < 1) return fail(QASR_ERR_BLOB, "boost_check: n_nodes %d", n_nodes);
+  if (start < 0 || start >= n_nodes) return fail(QASR_ERR_BLOB, "boost_check: start state %d outside the %d nodes", start, n_nodes);
+  if (whole != 0 && whole != 1) return fail(QASR_ERR_BLOB, "boost_check: whole_words %d", whole);
+  if (cap < 1 || (cap & (cap - 1))) return fail(QASR_ERR_BLOB, "boost_check: capacity %d is no power of two", cap);
+  if (probe < 1 || probe > QASR_LM_MAX_PROBE || probe > cap)
+    return fail(QASR_ERR_BLOB, "boost_check: probe bound %d outside 1 .. %d (or above the capacity)", probe, QASR_LM_MAX_PROBE);
+  const uint64_t total = 4ull * HDR + 16ull * (uint64_t)cap + 8ull * (uint64_t)n_nodes + 4ull * (uint64_t)n_labels;
+  if (total != (uint64_t)bytes || h[2] != (int32_t)bytes)
+    return fail(QASR_ERR_BLOB, "boost_check: %zu bytes, the header describes %llu (total field %d)", bytes, (unsigned long long)total, h[2]);
+  for (int i = 9; i < HDR; ++i)
+    if (h[i] != 0) return fail(QASR_ERR_BLOB, "boost_check: reserved header word %d is %d", i, h[i]);
+  const int32_t* table = h + HDR;
+  const int32_t* nodes = table + 4 * (size_t)cap;
+  const int32_t* root_next = nodes + 2 * (size_t)n_nodes;
+  for (int i = 0; i < n_nodes; ++i) {
+    if (nodes[2 * i] < 0 || nodes[2 * i] > LIM) return fail(QASR_ERR_BLOB, "boost_check: pot %d of node %d outside 0 .. 2^30", nodes[2 * i], i);
+    if (nodes[2 * i + 1] < 0 || nodes[2 * i + 1] > LIM) return fail(QASR_ERR_BLOB, "boost_check: bank %d of node %d outside 0 .. 2^30", nodes[2 * i + 1], i);
+  }
+  for (int i = 0; i < n_labels; ++i)
+    if (root_next[i] < 0 || root_next[i] >= n_nodes) return fail(QASR_ERR_BLOB, "boost_check: root_next[%d] = %d outside the %d nodes", i, root_next[i], n_nodes);
+  for (int s = 0; s < cap; ++s) {
+    const int32_t* e = table + 4 * (size_t)s;
+    if (e[0] == -1) continue;
+    if (e[0] < 1 || e[0] >= n_nodes || e[1] < 0 || e[1] >= n_labels || e[2] < 0 || e[2] >= n_nodes || e[3] != 0)
+      return fail(QASR_ERR_BLOB, "boost_check: table slot %d (node %d, label %d, next %d, %d) out of range", s, e[0], e[1], e[2], e[3]);
+    uint64_t x = (((uint64_t)(uint32_t)e[0] << 32) | (uint32_t)e[1]) * 0x9E3779B97F4A7C15ull;
+    x ^= x >> 32;
+    const int home = (int)((uint32_t)x & (uint32_t)(cap - 1)), dist = (s - home) & (cap - 1);
+    if (dist >= probe) return fail(QASR_ERR_BLOB, "boost_check: table slot %d lies %d probes from its home, the probe bound is %d", s, dist + 1, probe);
+    for (int d = 0; d < dist; ++d)
+      if (table[4 * (size_t)((home + d) & (cap - 1))] == -1) return fail(QASR_ERR_BLOB, "boost_check: table slot %d is cut off from its home", s);
+  }
+  return QASR_OK;
+}
+
+int qasr_ctc_beam_boost(void* stream, const qasr_ctc_beam_boost_args* a) {
+  if (!a) return fail(QASR_ERR_ARG, "ctc_beam_boost: args is NULL");
+  if (a->struct_size != sizeof(qasr_ctc_beam_boost_args))
+    return fail(QASR_ERR_ARG, "ctc_beam_boost: struct_size %u is not %zu", a->struct_size, sizeof(qasr_ctc_beam_boost_args));
+  if (!a->cand_id || !a->cand_q || !a->lae_table || !a->workspace || !a->labels || !a->n_labels || !a->score || !a->n_hyps ||
+      !a->boost || !a->boost_score || (a->lm && !a->lm_score))
+    return fail(QASR_ERR_ARG, "ctc_beam_boost: a required pointer is NULL (only lens and lm are optional; lm needs lm_score)");
+  if (!beam_shape_ok(a->B, a->T, a->beam_width))
+    return fail(QASR_ERR_ARG, "ctc_beam_boost: B %d, T %d (1 .. %d) or beam_width %d (1 .. %d) out of range", a->B, a->T,
+                QASR_BEAM_MAX_FRAMES, a->beam_width, QASR_BEAM_MAX_WIDTH);
+  if (a->N < 1 || a->N > QASR_BEAM_MAX_CANDIDATES)
+    return fail(QASR_ERR_ARG, "ctc_beam_boost: N %d is outside 1 .. %d", a->N, QASR_BEAM_MAX_CANDIDATES);
+  if (a->n_best < 1 || a->n_best > a->beam_width || a->blank < 0)
+    return fail(QASR_ERR_ARG, "ctc_beam_boost: n_best %d is outside 1 .. beam_width, or blank %d < 0", a->n_best, a->blank);
+  if (a->lae_entries != QASR_BEAM_TABLE_ENTRIES)
+    return fail(QASR_ERR_ARG, "ctc_beam_boost: lae_entries %u is not %d", a->lae_entries, QASR_BEAM_TABLE_ENTRIES);
+  const size_t need = beam_workspace_bytes(a->B, a->T, a->beam_width);
+  if (a->workspace_bytes < need) return fail(QASR_ERR_ARG, "ctc_beam_boost: workspace of %zu bytes, %zu needed", a->workspace_bytes, need);
+  if (a->lm) {
+    if (((uintptr_t)a->lm & 15) != 0 || a->lm_bytes < 128 || a->lm_bytes > (size_t)INT32_MAX)
+      return fail(QASR_ERR_ARG, "ctc_beam_boost: lm must be 16-byte aligned and 128 .. 2^31 - 1 bytes, got %zu", a->lm_bytes);
+    if (a->alpha_q < 0 || a->alpha_q > QASR_LM_MAX_WEIGHT || a->beta_q < -QASR_LM_MAX_WEIGHT || a->beta_q > QASR_LM_MAX_WEIGHT)
+      return fail(QASR_ERR_ARG, "ctc_beam_boost: alpha_q %d outside 0 .. 16 * 2^16 or |beta_q| %d above it", a->alpha_q, a->beta_q);
+  }
+  if (((uintptr_t)a->boost & 15) != 0 || a->boost_bytes < 128 || a->boost_bytes > (size_t)INT32_MAX)
+    return fail(QASR_ERR_ARG, "ctc_beam_boost: boost must be 16-byte aligned and 128 .. 2^31 - 1 bytes, got %zu", a->boost_bytes);
+  if (a->space < -1 || a->space == a->blank)
+    return fail(QASR_ERR_ARG, "ctc_beam_boost: space %d must be a label other than blank, or -1", a->space);
+  if (a->whole_words != 0 && a->space < 0)
+    return fail(QASR_ERR_ARG, "ctc_beam_boost: whole words need the space label, got %d", a->space);
+  int rc = launch_beam_boost((hipStream_t)stream, *a);
+  if (rc) return fail(rc, "ctc_beam_boost: launch");
+  HIPCHK(hipGetLastError());
+  return QASR_OK;
+}
+
 // ---- CTC forced alignment (k_align, qasr_align.hip): the checks of include/qasr.h, then one launch
 static int align_shape_ok(int P, int T, int max_labels) {
   return P >= 1 && T >= 1 && T <= QASR_BEAM_MAX_FRAMES && max_labels >= 1 && max_labels <= QASR_ALIGN_MAX_LABELS;

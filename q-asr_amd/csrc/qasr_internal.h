@@ -164,6 +164,7 @@ int launch_topn(hipStream_t s, const qasr_ctc_topn_args& a);
 size_t beam_workspace_bytes(int B, int T, int W);
 int launch_beam(hipStream_t s, const qasr_ctc_beam_args& a);
 int launch_beam_lm(hipStream_t s, const qasr_ctc_beam_lm_args& a);      // k_beam_lm: the search with an n-gram model
+int launch_beam_boost(hipStream_t s, const qasr_ctc_beam_boost_args& a);      // k_beam_boost (qasr_beam_boost.hip): phrase boosting, with or without a model
 // qasr_align.hip: CTC forced alignment and transcript scoring (k_align); the arguments are checked by qasr_ctc_align
 size_t align_workspace_bytes(int P, int T, int max_labels);
 int launch_align(hipStream_t s, const qasr_ctc_align_args& a);

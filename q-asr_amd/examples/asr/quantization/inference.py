@@ -68,6 +68,11 @@ def main():
                         "are refused: export ARPA), fused into the beam on the device; --dump_hyps gains `lm_score`")
     p.add_argument("--alpha", type=float, default=None, help="(extension, needs --lm_path) weight of the model, 0 .. 16 (default 1.0)")
     p.add_argument("--beta", type=float, default=None, help="(extension, needs --lm_path) bonus per scored word or character, -16 .. 16 (default 0.0)")
+    p.add_argument("--boost_file", type=str, default=None, metavar='FILE',
+                   help="(extension, needs --beam_width) phrases to boost in the beam search (hot words): one per line with an "
+                        "optional <tab>weight in nats per label, '#' lines and blank lines are skipped; works with or without "
+                        "--lm_path; --dump_hyps gains `boost_score`")
+    p.add_argument("--boost_weight", type=float, default=None, help="(extension, needs --boost_file) weight of the phrases without one, 0 .. 16 (default 1.0)")
     p.add_argument("--align", type=str, default=None, metavar='OUT',
                    help="(extension) forced alignment of every manifest line's reference text against its batch's "
                         "log-probabilities (EncDecCTCModel.align): OUT gets one JSON line per utterance - audio_filepath, text, "
@@ -83,6 +88,13 @@ def main():
     alpha, beta = 1.0 if args.alpha is None else args.alpha, 0.0 if args.beta is None else args.beta
     if not 0.0 <= alpha <= 16.0 or not abs(beta) <= 16.0:
         p.error(f'--alpha must be 0 .. 16 and --beta -16 .. 16, got {alpha} and {beta}')
+    if args.boost_file is not None and args.beam_width is None:
+        p.error('--boost_file needs --beam_width')
+    if args.boost_weight is not None and args.boost_file is None:
+        p.error('--boost_weight needs --boost_file')
+    boost_weight = 1.0 if args.boost_weight is None else args.boost_weight
+    if not 0.0 <= boost_weight <= 16.0:
+        p.error(f'--boost_weight must be 0 .. 16, got {boost_weight}')
     torch.set_grad_enabled(False)
 
     if args.asr_model.endswith('.nemo'):
@@ -136,8 +148,11 @@ def main():
         asr_model.reserve(args.batch_size, args.reserve)
     labels_map = dict(enumerate(asr_model.decoder.vocabulary))
     wer = WER(vocabulary=asr_model.decoder.vocabulary)
-    hyps, refs, words, utt_scores, beam_scores, lm_scores = [], [], [], [], [], []
+    hyps, refs, words, utt_scores, beam_scores, lm_scores, boost_scores = [], [], [], [], [], [], []
     lm_kw = dict(lm=args.lm_path, alpha=alpha, beta=beta) if args.lm_path is not None else {}
+    if args.boost_file is not None:                          # compiled once for the run: the file does not change per batch
+        from qasr import boost as qboost
+        lm_kw['boost'] = qboost.PhraseSet(qboost.read_phrase_file(args.boost_file), asr_model.decoder.vocabulary, weight=boost_weight)
     aligned, items = [], getattr(asr_model.test_dataloader().dataset, 'items', [])
     audio_s, t0 = 0.0, time.time()
     for i, batch in enumerate(asr_model.test_dataloader()):
@@ -150,6 +165,7 @@ def main():
                 hyps.append(h.text)
                 beam_scores.append(h.utt_score)
                 lm_scores.append(h.lm_score)
+                boost_scores.append(h.boost_score)
         else:
             log_probs, enc_len, greedy = asr_model(input_signal=batch[0].float(), input_signal_length=batch[1])
             hyps += wer.ctc_decoder_predictions_tensor(greedy)
@@ -181,6 +197,8 @@ def main():
                 extra.update(beam_width=args.beam_width, beam_score=beam_scores)
             if args.lm_path is not None:
                 extra.update(lm_path=args.lm_path, alpha=alpha, beta=beta, lm_score=lm_scores)
+            if args.boost_file is not None:
+                extra.update(boost_file=args.boost_file, boost_weight=boost_weight, boost_score=boost_scores)
             json.dump(dict(hypotheses=hyps, references=refs, wer=wer_value, path=served, **extra), f)
     if args.align:
         import json

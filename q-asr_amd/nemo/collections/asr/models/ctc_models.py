@@ -432,7 +432,8 @@ class EncDecCTCModel(nn.Module):
 
     @torch.no_grad()
     def decode(self, input_signal=None, input_signal_length=None, processed_signal=None, processed_signal_length=None,
-               beam_width=None, n_best=1, cutoff_top_n=40, lm=None, alpha=0.0, beta=0.0, timestamps=False):
+               beam_width=None, n_best=1, cutoff_top_n=40, lm=None, alpha=0.0, beta=0.0, timestamps=False, boost=None,
+               boost_weight=1.0):
         """Greedy CTC hypotheses of one batch (an extension of the reference's API): List[qasr.ctc.Hypothesis] with the
         text, every label's start / end time and confidence (best frame log-probability of its run), word groups and the
         log-probability of the greedy path.  Decoding stops at each utterance's encoded length.  On the static engine the
@@ -454,15 +455,30 @@ class EncDecCTCModel(nn.Module):
         (0 .. 16) and beta (|beta| <= 16) as ctc_decoders' Scorer does (qasr.beam.LM_RULES; k_beam_lm on the device): word
         mode if the vocabulary has a space, else character mode.  utt_score then includes the model's share, which the
         hypotheses also carry as lm_score.  A model loaded from a path is kept on the module, so a sweep of alpha / beta
-        loads and packs once.  Out of scope: KenLM binary files, cutoff_prob < 1, </s> scoring, orders above 6."""
+        loads and packs once.  Out of scope: KenLM binary files, cutoff_prob < 1, </s> scoring, orders above 6.
+
+        boost=<a list of phrases (text, or (text, weight) pairs), or a qasr.boost.PhraseSet> (needs beam_width) biases the
+        search towards those phrases ("hot words"), with or without lm: every label of a matched phrase earns its weight
+        in nats (boost_weight where a phrase has none, 0 .. 16), an unfinished match earns nothing, and with a vocabulary
+        that has a space phrases match whole words only (qasr.boost.BOOST_RULES; k_beam_boost on the device, the NumPy twin
+        on the host modules).  utt_score then includes the boosting's share, which the hypotheses also carry as
+        boost_score.  The list changes per call: it is compiled and packed here, per call."""
         from qasr import ctc as qctc
         if lm is not None and beam_width is None:
             raise ValueError('decode: lm needs beam_width (the greedy collapse has no language model)')
+        if boost is not None and beam_width is None:
+            raise ValueError('decode: boost needs beam_width (the greedy collapse has no phrase boosting)')
         if beam_width is not None:
             beam_width, n_best, cutoff_top_n = self._beam_args(beam_width, n_best, cutoff_top_n)      # refused before any launch
             lm = self._lm_args(lm, alpha, beta)
+            if boost is not None:
+                from qasr import boost as qboost
+                try:
+                    boost = qboost.as_phrase_set(boost, self.decoder.vocabulary, boost_weight)
+                except ValueError as e:
+                    raise ValueError(f'decode: {e}') from None
             return self._beam_decode(self._forward(input_signal, input_signal_length, processed_signal, processed_signal_length),
-                                     beam_width, n_best, cutoff_top_n, lm, alpha, beta, bool(timestamps))
+                                     beam_width, n_best, cutoff_top_n, lm, alpha, beta, bool(timestamps), boost)
         res = self._forward(input_signal, input_signal_length, processed_signal, processed_signal_length, decode=True)
         return qctc.to_hypotheses(res, self.decoder.vocabulary, self.seconds_per_frame())
 
@@ -498,7 +514,7 @@ class EncDecCTCModel(nn.Module):
                              f'{len(self.decoder.vocabulary)}')
         return lm
 
-    def _beam_decode(self, fwd, beam_width, n_best, cutoff_top_n, lm=None, alpha=0.0, beta=0.0, timestamps=False):
+    def _beam_decode(self, fwd, beam_width, n_best, cutoff_top_n, lm=None, alpha=0.0, beta=0.0, timestamps=False, boost=None):
         """decode(beam_width=) behind any path's (log_probs, encoded lengths, tokens); the arguments passed _beam_args"""
         from qasr import beam as qbeam
         log_probs, enc_len = fwd[0], fwd[1]
@@ -506,10 +522,10 @@ class EncDecCTCModel(nn.Module):
         if log_probs.is_cuda:
             from qasr import engine as qengine
             res = qengine.ctc_beam_search(log_probs.float(), enc_len, blank, beam_width, n_best, cutoff_top_n, lm=lm,
-                                          alpha=alpha, beta=beta)
+                                          alpha=alpha, beta=beta, boost=boost)
         else:
             res = qbeam.search_host(log_probs.float().numpy(), enc_len.numpy(), blank, beam_width, n_best, cutoff_top_n, lm,
-                                    alpha, beta)
+                                    alpha, beta, boost)
         hyps = qbeam.to_hypotheses(res, self.decoder.vocabulary)
         if timestamps:
             self._beam_timestamps(hyps, res, log_probs, enc_len, blank, n_best)

@@ -27,10 +27,12 @@ class BeamSearchDecoderWithLM(nn.Module):
     vocab: the model's labels (the CTC blank is the class after the last one); beam_width: 1 .. 128; cutoff_top_n:
     1 .. 64 classes considered per frame; num_cpus is accepted and unused (the device needs none, the twin is one loop);
     input_tensor: True for a tensor [B, T, D] of log-probabilities with lengths, False for a list of [T_i, D] arrays of
-    probabilities, as the reference passes them on."""
+    probabilities, as the reference passes them on.  boost (keyword-only, an extension): a list of phrases (text or
+    (text, weight); boost_weight nats per label where a phrase has none) or a qasr.boost.PhraseSet: phrase boosting by
+    qasr.boost.BOOST_RULES (k_beam_boost on the device), with or without lm_path."""
 
     def __init__(self, vocab, beam_width, alpha, beta, lm_path, num_cpus, cutoff_prob=1.0, cutoff_top_n=40,
-                 input_tensor=False):
+                 input_tensor=False, *, boost=None, boost_weight=1.0):
         if float(cutoff_prob) != 1.0:
             raise ValueError(f'BeamSearchDecoderWithLM: cutoff_prob must be 1.0 (no cumulative pruning), got {cutoff_prob}')
         if not 1 <= int(beam_width) <= qbeam.MAX_W:
@@ -47,8 +49,16 @@ class BeamSearchDecoderWithLM(nn.Module):
             scorer = lm_path if isinstance(lm_path, ngram.NgramLM) else ngram.NgramLM.from_arpa(lm_path, list(vocab))
             if scorer.n_labels != len(list(vocab)):
                 raise ValueError(f'BeamSearchDecoderWithLM: the model was loaded for {scorer.n_labels} labels, vocab has {len(list(vocab))}')
+        phrases = None
+        if boost is not None:                       # (keyword-only: the positional signature is the reference's)
+            from qasr import boost as qboost
+            try:
+                phrases = qboost.as_phrase_set(boost, list(vocab), boost_weight)
+            except ValueError as e:
+                raise ValueError(f'BeamSearchDecoderWithLM: {e}') from None
         super().__init__()
         self.scorer = scorer
+        self.phrases = phrases
         self.vocab = list(vocab)
         self.beam_width = int(beam_width)
         self.alpha, self.beta = alpha, beta
@@ -65,10 +75,11 @@ class BeamSearchDecoderWithLM(nn.Module):
         if log_probs.is_cuda:
             from qasr import engine as qengine
             return qengine.ctc_beam_search(log_probs.float(), log_probs_length, blank, self.beam_width, n_best,
-                                           self.cutoff_top_n, lm=self.scorer, alpha=self.alpha, beta=self.beta)
+                                           self.cutoff_top_n, lm=self.scorer, alpha=self.alpha, beta=self.beta,
+                                           boost=self.phrases)
         lens = None if log_probs_length is None else np.asarray(log_probs_length.cpu())
         return qbeam.search_host(log_probs.float().numpy(), lens, blank, self.beam_width, n_best, self.cutoff_top_n,
-                                 self.scorer, self.alpha, self.beta)
+                                 self.scorer, self.alpha, self.beta, self.phrases)
 
     @torch.no_grad()
     def forward(self, log_probs, log_probs_length=None):

@@ -1,5 +1,5 @@
 """CTC prefix beam search in fixed point, without and with an n-gram language model (LM_RULES below): the host statement of k_topn / k_beam / k_beam_lm
-(csrc/qasr_beam.hip, include/qasr.h) and the step from the final beam to strings.  NumPy only: no GPU, no native library.
+(csrc/qasr_beam.hip, include/qasr.h), of k_beam_boost (phrase boosting: qasr/boost.py, csrc/qasr_beam_boost.hip) and the step from the final beam to strings.  NumPy only: no GPU, no native library.
 
 `topn_host` and `beam_search_host` are the CPU fallback of BeamSearchDecoderWithLM / EncDecCTCModel.decode(beam_width=)
 and the yardstick the GPU tests compare the kernels with, bit for bit.
@@ -126,6 +126,7 @@ class BeamResult:
     n_hyps: object
     blank: int = -1
     lm_score: object = None             # with a language model: int64 [B, n_best], the model's share of score (unused rows: 0)
+    boost_score: object = None          # with a phrase set: int64 [B, n_best], the boosting's share of score (unused rows: 0)
 
 
 def _hmix(h, c):
@@ -334,12 +335,137 @@ def _search_one_lm(cid, cq, lim, blank, W, tab, lm, alpha_q, beta_q):
     return out
 
 
+def _search_one_boost(cid, cq, lim, blank, W, tab, lm, alpha_q, beta_q, bs):
+    """one utterance under BOOST_RULES of qasr/boost.py (bs: a PhraseSet), with LM_RULES when lm is not None; returns the
+    final beam as a list of (labels, score, lm_tot, boost_tot)"""
+    N = cid.shape[1]
+    i64 = np.int64
+    has_lm = lm is not None
+    word_mode = has_lm and lm.word_mode
+    if has_lm:
+        space, nlab, l2w = lm.space, lm.n_labels, lm.label_to_word
+    half = 1 << (FRAC - 1)
+    pb, pnb, sc = np.array([0], i64), np.array([NEG], i64), np.array([0], i64)
+    hsh, phs = np.zeros(1, np.uint64), np.zeros(1, np.uint64)
+    ln, last, node = np.zeros(1, np.int32), np.full(1, -1, np.int32), np.full(1, -1, np.int64)
+    ctx, wh = np.array([lm.start if has_lm else 0], np.int32), np.zeros(1, np.uint64)
+    own, lmt = np.zeros(1, i64), np.zeros(1, i64)
+    bst, btot = np.array([bs.start], np.int64), np.zeros(1, i64)
+    nodes_parent, nodes_label = [], []
+    node_of = {}
+    for t in range(lim):
+        nb = len(sc)
+        if nb == 0:
+            break
+        c, q = cid[t].astype(np.int64), cq[t].astype(i64)
+        valid = c >= 0
+        isb = valid & (c == blank)
+        match = (last[:, None] == c[None, :]) & valid[None, :]
+        has, nl = match.any(1), match.argmax(1)
+        pm = (phs[:, None] == hsh[None, :]) & (ln[:, None] == ln[None, :] + 1)
+        hasp, ps = pm.any(1), pm.argmax(1)
+        q_l = q[nl]
+        pb_n = sc + q[isb.argmax()] if isb.any() else np.full(nb, NEG, i64)
+        ownp = has & (pnb != NEG)
+        a = np.where(ownp, q_l + np.where(ownp, pnb, 0), NEG)
+        pbase = np.where(last[ps] == last, pb[ps], sc[ps])
+        ext = has & hasp & (pbase != NEG)
+        e = np.where(ext, q_l + np.where(ext, pbase, 0) + own, NEG)
+        pnb_n = lae(a, e, tab)
+        sc_n = lae(pb_n, pnb_n, tab)
+        child = np.zeros((nb, N), dtype=bool)
+        sel = has & hasp
+        child[ps[sel], nl[sel]] = True
+        base = np.where(c[None, :] == last[:, None], pb[:, None], sc[:, None])
+        ok = (valid & ~isb)[None, :] & ~child & (base != NEG)
+        # the terms of this frame, evaluated once: the model's, then the boost's
+        scored, raws = np.zeros((nb, N), dtype=bool), np.zeros((nb, N), i64)
+        if word_mode:
+            inword = (last >= 0) & (last != space)
+            for n in np.flatnonzero(valid & (c == space)):
+                for i in np.flatnonzero(ok[:, n] & inword):
+                    raws[i, n], scored[i, n] = lm.raw(int(ctx[i]), lm.lookup_word(wh[i]))[0], True
+        elif has_lm:
+            wids = np.where(valid & (c < nlab), l2w[np.clip(c, 0, nlab - 1)], -1)
+            for i, n in zip(*np.nonzero(ok)):
+                raws[i, n] = lm.raw(int(ctx[i]), int(wids[n]))[0]
+            scored = ok
+        tm = np.where(scored, ((raws * alpha_q + half) >> FRAC) + beta_q, 0)
+        btm, bnx = np.zeros((nb, N), i64), np.zeros((nb, N), i64)
+        for i, n in zip(*np.nonzero(ok)):
+            btm[i, n], bnx[i, n] = bs.term(int(bst[i]), int(c[n]))
+        v = np.where(ok, np.where(ok, base, 0) + q[None, :] + tm + btm, NEG)
+        allc = np.concatenate([sc_n[:, None], v], axis=1).ravel()
+        n_live = int((allc != NEG).sum())
+        order = np.argsort(-allc, kind='stable')[:min(W, n_live)]
+        src, k = order // (N + 1), order % (N + 1)
+        kept = k == 0
+        kn = np.maximum(k - 1, 0)
+        cn = c[kn]
+        n_pb = np.where(kept, pb_n[src], NEG)
+        n_pnb = np.where(kept, pnb_n[src], allc[order])
+        n_sc = allc[order]
+        n_hsh = np.where(kept, hsh[src], _hmix(hsh[src], cn))
+        n_phs = np.where(kept, phs[src], hsh[src])
+        n_ln = np.where(kept, ln[src], ln[src] + 1).astype(np.int32)
+        n_last = np.where(kept, last[src], cn).astype(np.int32)
+        n_node = np.where(kept, node[src], t * W + np.arange(len(order)))
+        n_own = np.where(kept, own[src], tm[src, kn] + btm[src, kn])
+        n_lmt = np.where(kept, lmt[src], lmt[src] + tm[src, kn])
+        n_btot = np.where(kept, btot[src], btot[src] + btm[src, kn])
+        n_bst = np.where(kept, bst[src], bnx[src, kn])
+        n_ctx, n_wh = ctx[src].copy(), wh[src].copy()
+        for s in np.flatnonzero(~kept):
+            i, n = int(src[s]), int(kn[s])
+            if has_lm:
+                if word_mode and cn[s] != space:
+                    n_wh[s] = _hmix(wh[i:i + 1], cn[s:s + 1])[0]
+                else:
+                    n_wh[s] = 0
+                    if not word_mode:
+                        n_ctx[s] = lm.raw(int(ctx[i]), int(wids[n]))[1]
+                    elif scored[i, n]:
+                        n_ctx[s] = lm.raw(int(ctx[i]), lm.lookup_word(wh[i]))[1]
+            node_of[int(n_node[s])] = len(nodes_parent)
+            nodes_parent.append(int(node[i]))
+            nodes_label.append(int(cn[s]))
+        pb, pnb, sc, hsh, phs, ln, last, node = n_pb, n_pnb, n_sc, n_hsh, n_phs, n_ln, n_last, n_node
+        ctx, wh, own, lmt, bst, btot = n_ctx, n_wh, n_own, n_lmt, n_bst, n_btot
+    if len(sc):                                                 # the corrections of every entry, then ONE re-ordering
+        sc, lmt, btot = sc.copy(), lmt.copy(), btot.copy()
+        if word_mode:
+            for i in np.flatnonzero((last >= 0) & (last != space)):
+                tv = ((lm.raw(int(ctx[i]), lm.lookup_word(wh[i]))[0] * alpha_q + half) >> FRAC) + beta_q
+                sc[i] += tv
+                lmt[i] += tv
+        for i in range(len(sc)):
+            fin = bs.finish(int(bst[i]))
+            sc[i] += fin
+            btot[i] += fin
+        rank = np.argsort(-sc, kind='stable')
+    else:
+        rank = np.arange(len(sc))
+    out = []
+    for h in rank:
+        labs, nd = [], int(node[h])
+        for _ in range(int(ln[h])):
+            if nd < 0:
+                break
+            j = node_of[nd]
+            labs.append(nodes_label[j])
+            nd = nodes_parent[j]
+        out.append((labs[::-1], int(sc[h]), int(lmt[h]), int(btot[h])))
+    return out
+
+
 def beam_search_host(cand_id, cand_q, lens=None, blank=None, beam_width=16, n_best=None, lm=None, alpha=0.0,
-                     beta=0.0) -> BeamResult:
+                     beta=0.0, boost=None) -> BeamResult:
     """cand_id / cand_q int32 [B, T, N] as topn_host (or k_topn) writes them; lens int [B] or None (the padded row);
     blank: the blank id (required); beam_width W: 1 .. 128; n_best: 1 .. W hypotheses to report (None: W).  lm: a
     qasr.ngram.NgramLM (None: the search without a model, alpha and beta unused) with its weights 0 <= alpha <= 16,
-    |beta| <= 16: the rules of LM_RULES; the result then carries lm_score."""
+    |beta| <= 16: the rules of LM_RULES; the result then carries lm_score.  boost: a qasr.boost.PhraseSet (None: no
+    boosting, the searches above as they are), with or without a model: BOOST_RULES of qasr/boost.py; the result then
+    carries boost_score."""
     if blank is None:
         raise ValueError('beam_search_host: blank is required (the decoder\'s last class)')
     cid, cq = np.asarray(cand_id), np.asarray(cand_q)
@@ -361,15 +487,23 @@ def beam_search_host(cand_id, cand_q, lens=None, blank=None, beam_width=16, n_be
         alpha_q, beta_q = fixed_weights(alpha, beta)
         if lm.n_labels != int(blank):
             raise ValueError(f'beam_search_host: the model was loaded for {lm.n_labels} labels, blank is {blank}')
+    else:
+        alpha_q = beta_q = 0
+    if boost is not None and boost.n_labels != int(blank):
+        raise ValueError(f'beam_search_host: the phrase set was compiled for {boost.n_labels} labels, blank is {blank}')
     tab = lae_table()
     labels = np.full((B, nbest, T), blank, dtype=np.int32)
     n_labels = np.zeros((B, nbest), dtype=np.int32)
     score = np.full((B, nbest), NEG, dtype=np.int64)
     n_hyps = np.zeros(B, dtype=np.int32)
     lm_score = None if lm is None else np.zeros((B, nbest), dtype=np.int64)
+    boost_score = None if boost is None else np.zeros((B, nbest), dtype=np.int64)
     for b in range(B):
         lim = T if lens is None else int(min(max(int(lens[b]), 0), T))
-        if lm is None:
+        if boost is not None:
+            beam = _search_one_boost(cid[b].astype(np.int32), cq[b].astype(np.int32), lim, int(blank), W, tab, lm, alpha_q,
+                                     beta_q, boost)[:nbest]
+        elif lm is None:
             beam = _search_one(cid[b].astype(np.int32), cq[b].astype(np.int32), lim, int(blank), W, tab)[:nbest]
         else:
             beam = _search_one_lm(cid[b].astype(np.int32), cq[b].astype(np.int32), lim, int(blank), W, tab, lm, alpha_q,
@@ -382,16 +516,18 @@ def beam_search_host(cand_id, cand_q, lens=None, blank=None, beam_width=16, n_be
             score[b, h] = s
             if lm is not None:
                 lm_score[b, h] = ent[2]
-    return BeamResult(labels, n_labels, score, n_hyps, int(blank), lm_score)
+            if boost is not None:
+                boost_score[b, h] = ent[3]
+    return BeamResult(labels, n_labels, score, n_hyps, int(blank), lm_score, boost_score)
 
 
 def search_host(log_probs, lens=None, blank=None, beam_width=16, n_best=None, cutoff_top_n=40, lm=None, alpha=0.0,
-                beta=0.0) -> BeamResult:
+                beta=0.0, boost=None) -> BeamResult:
     """topn_host + beam_search_host on float32 log-probabilities [B, T, C] (blank None: the last class)"""
     lp = np.asarray(log_probs, dtype=np.float32)
     blank = lp.shape[-1] - 1 if blank is None else blank
     cid, cq = topn_host(lp, cutoff_top_n, lens)
-    return beam_search_host(cid, cq, lens, blank, beam_width, n_best, lm, alpha, beta)
+    return beam_search_host(cid, cq, lens, blank, beam_width, n_best, lm, alpha, beta, boost)
 
 
 def _np(x):
@@ -408,6 +544,7 @@ def to_hypotheses(result: BeamResult, vocabulary: Sequence[str]) -> List[list]:
     from .ctc import Hypothesis
     labels, n_labels, score, n_hyps = _np(result.labels), _np(result.n_labels), _np(result.score), _np(result.n_hyps)
     lm_score = None if result.lm_score is None else _np(result.lm_score)
+    boost_score = None if result.boost_score is None else _np(result.boost_score)
     vocab = list(vocabulary)
     out = []
     for b in range(labels.shape[0]):
@@ -417,6 +554,8 @@ def to_hypotheses(result: BeamResult, vocabulary: Sequence[str]) -> List[list]:
             hyp = Hypothesis(''.join(vocab[i] for i in ids), ids, [], [], None, float(score[b, h]) / ONE, [])
             if lm_score is not None:
                 hyp.lm_score = float(lm_score[b, h]) / ONE
+            if boost_score is not None:
+                hyp.boost_score = float(boost_score[b, h]) / ONE
             hyps.append(hyp)
         out.append(hyps)
     return out

@@ -37,6 +37,7 @@ class Hypothesis:
     words: List[Tuple[str, float, float, Optional[float]]] = field(default_factory=list)
     lm_score: Optional[float] = None        # beam search with a language model: the model's share of utt_score
     ctc_score: Optional[float] = None       # forced alignment (qasr.align): the CTC log-likelihood of the text, all alignments
+    boost_score: Optional[float] = None     # beam search with phrase boosting (qasr.boost): the boosting's share of utt_score
 
 
 def _order_key(x):

@@ -17,7 +17,7 @@ SYMBOLS = ['qasr_blob_check', 'qasr_engine_create', 'qasr_engine_create_ex', 'qa
            'qasr_dw_conv_acc', 'qasr_dense_conv_acc', 'qasr_requant', 'qasr_dyn_range', 'qasr_dyn_range_percentile', 'qasr_dyn_residue_codes', 'qasr_dyn_act_params', 'qasr_dyn_requant',
            'qasr_dyn_quant_in', 'qasr_dyn_conv_params', 'qasr_sep_layer', 'qasr_quantile2', 'qasr_quantile_workspace_bytes', 'qasr_debug_prof',
            'qasr_debug_timeline', 'qasr_ctc_collapse', 'qasr_engine_attach_ctc', 'qasr_ctc_topn', 'qasr_ctc_beam_workspace_bytes', 'qasr_ctc_beam',
-           'qasr_lm_check', 'qasr_ctc_beam_lm', 'qasr_ctc_align_workspace_bytes', 'qasr_ctc_align',
+           'qasr_lm_check', 'qasr_ctc_beam_lm', 'qasr_boost_check', 'qasr_ctc_beam_boost', 'qasr_ctc_align_workspace_bytes', 'qasr_ctc_align',
            'qasr_engine_reserve', 'qasr_engine_forward_ragged', 'qasr_engine_forward_ragged_audio', 'qasr_engine_ragged_stats',
            'qasr_ragged_bucket_frames', 'qasr_ragged_envelope_frames',
            'qasr_last_error', 'qasr_version']
@@ -152,6 +152,9 @@ def load_library():
     if hasattr(lib, 'qasr_ctc_beam_lm'):        # (likewise)
         lib.qasr_lm_check.argtypes = [C.c_char_p, sz, i32]
         lib.qasr_ctc_beam_lm.argtypes = [vp, C.POINTER(BeamLmArgs)]
+    if hasattr(lib, 'qasr_ctc_beam_boost'):     # (likewise)
+        lib.qasr_boost_check.argtypes = [C.c_char_p, sz, i32]
+        lib.qasr_ctc_beam_boost.argtypes = [vp, C.POINTER(BeamBoostArgs)]
     if hasattr(lib, 'qasr_ctc_align'):          # (likewise)
         lib.qasr_ctc_align.argtypes = [vp, C.POINTER(AlignArgs)]
         lib.qasr_ctc_align_workspace_bytes.argtypes = [i32, i32, i32]
@@ -265,7 +268,15 @@ class BeamLmArgs(C.Structure):
                 [(n, C.c_int32) for n in ('alpha_q', 'beta_q', 'space', 'reserved')] + [('lm_score', C.c_void_p)])
 
 
+class BeamBoostArgs(C.Structure):
+    """qasr_ctc_beam_boost_args (include/qasr.h): the fields of BeamLmArgs with `reserved` become whole_words, then the set"""
+    _fields_ = (BeamArgs._fields_ + [('lm', C.c_void_p), ('lm_bytes', C.c_size_t)] +
+                [(n, C.c_int32) for n in ('alpha_q', 'beta_q', 'space', 'whole_words')] + [('lm_score', C.c_void_p)] +
+                [('boost', C.c_void_p), ('boost_bytes', C.c_size_t), ('boost_score', C.c_void_p)])
+
+
 _lae_tables = {}
+_boost_blobs = {}                       # (id of the PhraseSet, device) -> (the set, its packed form on the device)
 _lm_blobs = {}                          # (id of the NgramLM, device) -> (the model, its packed form on the device)
 
 
@@ -289,6 +300,32 @@ def lm_device(lm, device):
         blob = lm.pack()
         lm_check(blob, lm.n_labels)
         hit = _lm_blobs[key] = (lm, torch.frombuffer(bytearray(blob), dtype=torch.uint8).to(dev))
+    return hit[1]
+
+
+def boost_check(blob: bytes, n_labels: int):
+    """qasr_boost_check: raises QasrError naming the first malformed field of a packed phrase set (host-only, no GPU)"""
+    lib = load_library()
+    if lib.qasr_boost_check(bytes(blob), len(blob), int(n_labels)) != 0:
+        raise QasrError('malformed phrase set: ' + lib.qasr_last_error().decode())
+
+
+def boost_device(boost, device):
+    """The packed form of a qasr.boost.PhraseSet on `device` as a uint8 tensor: packed, validated (qasr_boost_check) and
+    uploaded once per (set, device) and kept, like lm_device.  A sweep of weights builds a new PhraseSet per weight, which
+    packs and uploads again: nothing stale is reused.  The upload is a host-to-device copy: the first ctc_beam with a set
+    must run outside a stream capture (or call this first); later calls only launch."""
+    dev = torch.device(device)
+    if dev.type == 'cuda' and dev.index is None:
+        dev = torch.device('cuda', torch.cuda.current_device())
+    key = (id(boost), dev)
+    hit = _boost_blobs.get(key)
+    if hit is None or hit[0] is not boost:
+        blob = boost.pack()
+        boost_check(blob, boost.n_labels)
+        if len(_boost_blobs) >= 8:                          # per-request sets come and go: keep the cache small
+            _boost_blobs.clear()
+        hit = _boost_blobs[key] = (boost, torch.frombuffer(bytearray(blob), dtype=torch.uint8).to(dev))
     return hit[1]
 
 
@@ -338,12 +375,16 @@ def ctc_beam_workspace_bytes(B, T, beam_width):
 
 
 def ctc_beam(cand_id, cand_q, lens=None, blank=None, beam_width=16, n_best=None, workspace=None, out=None, stream=None,
-             lm=None, alpha=0.0, beta=0.0):
+             lm=None, alpha=0.0, beta=0.0, boost=None):
     """qasr_ctc_beam: CTC prefix beam search over the candidates of ctc_topn (cuda int32 [B, T, N]) on the device (k_beam,
     one launch on the current stream, no host synchronisation); equal to qasr.beam.beam_search_host byte for byte.  Returns
     a qasr.beam.BeamResult of cuda tensors.  workspace: a caller-owned uint8 tensor of ctc_beam_workspace_bytes(B, T, W)
     bytes (None: allocated by torch here); `out`: a caller-owned BeamResult.  lm: a qasr.ngram.NgramLM with its weights
-    alpha (0 .. 16) and beta (|beta| <= 16): qasr_ctc_beam_lm (k_beam_lm) instead, and the result carries lm_score."""
+    alpha (0 .. 16) and beta (|beta| <= 16): qasr_ctc_beam_lm (k_beam_lm) instead, and the result carries lm_score.
+    boost: a qasr.boost.PhraseSet, with or without lm: qasr_ctc_beam_boost (k_beam_boost) instead, and the result carries
+    boost_score; without one the calls above run exactly as they did."""
+    if boost is not None:
+        return _ctc_beam_boost(cand_id, cand_q, lens, blank, beam_width, n_best, workspace, out, stream, lm, alpha, beta, boost)
     if lm is not None:
         return _ctc_beam_lm(cand_id, cand_q, lens, blank, beam_width, n_best, workspace, out, stream, lm, alpha, beta)
     from .beam import BeamResult, TAB_ENTRIES
@@ -424,16 +465,72 @@ def _ctc_beam_lm(cand_id, cand_q, lens, blank, beam_width, n_best, workspace, ou
     return out
 
 
+def _ctc_beam_boost(cand_id, cand_q, lens, blank, beam_width, n_best, workspace, out, stream, lm, alpha, beta, boost):
+    """ctc_beam with a phrase set: qasr_ctc_beam_boost.  Weights, vocabulary sizes and the set are checked here, before any
+    launch."""
+    from .beam import BeamResult, TAB_ENTRIES
+    lib = load_library()
+    if blank is None:
+        raise ValueError('ctc_beam: blank is required (the decoder\'s last class)')
+    alpha_q = beta_q = 0
+    if lm is not None:
+        from .ngram import fixed_weights
+        alpha_q, beta_q = fixed_weights(alpha, beta)
+        if lm.n_labels != int(blank):
+            raise ValueError(f'ctc_beam: the model was loaded for {lm.n_labels} labels, blank is {blank}')
+    if boost.n_labels != int(blank):
+        raise ValueError(f'ctc_beam: the phrase set was compiled for {boost.n_labels} labels, blank is {blank}')
+    assert cand_id.is_cuda and cand_id.dim() == 3 and cand_id.shape == cand_q.shape, 'ctc_beam: candidates must be cuda [B, T, N]'
+    dev = cand_id.device
+    cid, cq = cand_id.to(torch.int32).contiguous(), cand_q.to(device=dev, dtype=torch.int32).contiguous()
+    ln = None if lens is None else lens.to(device=dev, dtype=torch.int32).contiguous()
+    B, T, N = cid.shape
+    W = int(beam_width)
+    nb = W if n_best is None else int(n_best)
+    if out is None:
+        shape = (B, max(nb, 0))
+        out = BeamResult(labels=torch.empty(*shape, T, device=dev, dtype=torch.int32),
+                         n_labels=torch.empty(*shape, device=dev, dtype=torch.int32),
+                         score=torch.empty(*shape, device=dev, dtype=torch.int64),
+                         n_hyps=torch.empty(B, device=dev, dtype=torch.int32), blank=int(blank),
+                         lm_score=None if lm is None else torch.empty(*shape, device=dev, dtype=torch.int64),
+                         boost_score=torch.empty(*shape, device=dev, dtype=torch.int64))
+    if workspace is None:
+        workspace = torch.empty(max(ctc_beam_workspace_bytes(B, T, W), 8), device=dev, dtype=torch.uint8)
+    tab = lae_table_device(dev)
+    lm_blob = None if lm is None else lm_device(lm, dev)
+    blob = boost_device(boost, dev)
+    a = BeamBoostArgs()
+    a.struct_size = C.sizeof(BeamBoostArgs)
+    a.B, a.T, a.N, a.beam_width, a.n_best, a.blank = B, T, N, W, nb, int(blank)
+    a.lae_entries = TAB_ENTRIES
+    a.cand_id, a.cand_q, a.lens, a.lae_table = cid.data_ptr(), cq.data_ptr(), 0 if ln is None else ln.data_ptr(), tab.data_ptr()
+    a.workspace, a.workspace_bytes = workspace.data_ptr(), workspace.numel() * workspace.element_size()
+    a.labels, a.n_labels, a.score, a.n_hyps = (out.labels.data_ptr(), out.n_labels.data_ptr(), out.score.data_ptr(),
+                                               out.n_hyps.data_ptr())
+    if lm is not None:
+        a.lm, a.lm_bytes, a.alpha_q, a.beta_q = lm_blob.data_ptr(), lm_blob.numel(), alpha_q, beta_q
+        a.lm_score = 0 if out.lm_score is None else out.lm_score.data_ptr()
+    a.space = int(lm.space) if lm is not None else int(boost.space)
+    a.whole_words = int(boost.whole_words)
+    a.boost, a.boost_bytes = blob.data_ptr(), blob.numel()
+    a.boost_score = 0 if out.boost_score is None else out.boost_score.data_ptr()
+    with torch.cuda.device(dev):
+        _check(lib.qasr_ctc_beam_boost(_stream_ptr(stream), C.byref(a)), 'qasr_ctc_beam_boost')
+    out._keep = (cid, cq, ln, workspace, tab, lm_blob, blob)
+    return out
+
+
 def ctc_beam_search(log_probs, lens=None, blank=None, beam_width=16, n_best=None, cutoff_top_n=40, stream=None, lm=None,
-                    alpha=0.0, beta=0.0):
-    """k_topn + k_beam (k_beam_lm with a model) on the same stream: the device form of qasr.beam.search_host (blank None:
-    the last class)"""
+                    alpha=0.0, beta=0.0, boost=None):
+    """k_topn + k_beam (k_beam_lm with a model, k_beam_boost with a phrase set) on the same stream: the device form of
+    qasr.beam.search_host (blank None: the last class)"""
     blank = log_probs.shape[-1] - 1 if blank is None else blank
     if lm is not None:
         from .ngram import fixed_weights
         fixed_weights(alpha, beta)                              # refused before the first launch
     cid, cq = ctc_topn(log_probs, lens, cutoff_top_n, stream=stream)
-    return ctc_beam(cid, cq, lens, blank, beam_width, n_best, stream=stream, lm=lm, alpha=alpha, beta=beta)
+    return ctc_beam(cid, cq, lens, blank, beam_width, n_best, stream=stream, lm=lm, alpha=alpha, beta=beta, boost=boost)
 
 
 class AlignArgs(C.Structure):
