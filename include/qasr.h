@@ -488,6 +488,57 @@ typedef struct qasr_ctc_align_args {
 size_t qasr_ctc_align_workspace_bytes(int P, int T, int max_labels);   /* 0 for a shape qasr_ctc_align refuses */
 int qasr_ctc_align(void* stream, const qasr_ctc_align_args* args);
 
+/* ---- audio at any sample rate: rational polyphase resampler and PCM ingest -----------------------------------------------
+ * What AudioSegment.__init__ does on the host with librosa.core.resample when target_sr != sample_rate (parts/segment.py:
+ * 57-59), as one kernel, k_resample, in front of the mel front-end: int16 PCM (mono or interleaved channels) or float32 at an
+ * integer rate sr_in -> float32 mono at the model's rate, with per-utterance lengths.  g = gcd(sr_in, sr_out), L = sr_out / g,
+ * M = sr_in / g; n input frames give ceil(n L / M) outputs; output i reads the 2 W frames around (i M) / L through a Kaiser-
+ * windowed sinc evaluated per phase and rounded to 2^-30 (the packed table).  int16 input accumulates exactly in int64 and
+ * is rounded twice (one float64 division by channels * 2^45, one conversion to float32); float32 input accumulates in float64,
+ * product and sum rounded separately.  Equal rates (L = M = 1) bypass the filter.  The rules are RULES of qasr/resample.py,
+ * which the kernel follows byte for byte; parity with librosa's own filter tables is not pinned.
+ * The packed table (qasr.resample.ResamplePlan.pack): 32 int32 header words (magic 'QRS1', version, total bytes, L, M, W,
+ * sr_in, sr_out, quality, entries = L * 2 W, zeros), then int32 [2 W][L], column r = the slot i mod L of an output.
+ * qasr_resample_check validates it ON THE HOST (no GPU is touched): QASR_OK, or QASR_ERR_BLOB (qasr_last_error names the field)
+ * for a bad magic, version or size, L, M or W out of range (L, M >= 1 and coprime, W 1 .. QASR_RESAMPLE_MAX_W, L * 2 W <=
+ * QASR_RESAMPLE_MAX_ENTRIES), rates that do not reduce to L / M, entries != L * 2 W, a non-zero reserved word, or a column
+ * whose sum of |c| * 32768 * QASR_RESAMPLE_MAX_CHANNELS reaches 2^53 (the int64 accumulator would not convert exactly).
+ * The kernel trusts `blob`: pass only the bytes that passed.
+ * qasr_resample: one launch on `stream`; lengths are device data and nothing is read back, so it can be captured.
+ *   in       device int16 or float32 (dtype) [B][in_pitch frames][channels], interleaved
+ *   in_lens  device i32 [B]: frames per utterance (clamped to 0 .. in_pitch); a frame at or behind it is never read
+ *   out      device f32 [B][out_pitch]: out[b][0 .. out_len) the result, zeros from there to the pitch - a row can be handed
+ *            to qasr_engine_forward_audio / qasr_engine_forward_ragged_audio as it is
+ *   out_lens device i32 [B]: out_len = min(ceil(n L / M), out_pitch)
+ *   L, M, W  repeat the header's fields (the header lies in device memory, which this call does not read): a disagreement
+ *            ends every row empty (out_lens 0, zeros)
+ * QASR_ERR_ARG with nothing launched and no output written: an unknown struct_size, a NULL blob / in / in_lens / out /
+ * out_lens, an unaligned (16 bytes) blob, blob_bytes != 128 + 4 * L * 2 W, B outside 1 .. 65535, channels outside
+ * 1 .. QASR_RESAMPLE_MAX_CHANNELS, an unknown dtype, L, M or W out of range, in_pitch or out_pitch outside
+ * 0 .. QASR_RESAMPLE_MAX_PITCH (beyond it i * M leaves 64 bits' safe range and the grid its limit).
+ * qasr_resample_out_samples: ceil(in_samples * L / M), or -1 for a negative count, L or M < 1, or a result above 2^31 - 1. */
+#define QASR_RESAMPLE_MAX_W 4096
+#define QASR_RESAMPLE_MAX_ENTRIES (1 << 20)
+#define QASR_RESAMPLE_MAX_CHANNELS 8
+#define QASR_RESAMPLE_MAX_PITCH (1ll << 38)
+enum { QASR_PCM_S16 = 0, QASR_PCM_F32 = 1 };
+int qasr_resample_check(const void* blob, size_t bytes);
+typedef struct qasr_resample_args {
+  uint32_t struct_size;        /* sizeof of this struct in the caller's header */
+  int32_t B, channels, dtype;  /* dtype: QASR_PCM_S16 / QASR_PCM_F32 */
+  int32_t L, M, W, reserved;
+  const void* blob;            /* device memory: a packed table that passed qasr_resample_check */
+  size_t blob_bytes;
+  const void* in;
+  const int32_t* in_lens;
+  int64_t in_pitch;            /* frames per input row */
+  float* out;
+  int64_t out_pitch;           /* floats per output row */
+  int32_t* out_lens;
+} qasr_resample_args;
+int qasr_resample(void* stream, const qasr_resample_args* args);
+int qasr_resample_out_samples(int in_samples, int L, int M);
+
 /* ---- reserved engines: ragged batches without allocation, with graph replay ------------------------------------------
  * A data loader pads every batch to its own longest utterance (the reference's collate function), so (B, T) changes on
  * almost every call; qasr_engine_forward[_audio] then rebuilds its plan (device-synchronising frees + allocations) and,

@@ -1290,6 +1290,86 @@ int qasr_ctc_align(void* stream, const qasr_ctc_align_args* a) {
   return QASR_OK;
 }
 
+// ---- polyphase resampler (k_resample, qasr_resample.hip): host-only validation of a packed table (qasr/resample.py states
+// the layout), then the checks of include/qasr.h and one launch
+static long long gcd_ll(long long a, long long b) {
+  while (b) {
+    const long long t = a % b;
+    a = b, b = t;
+  }
+  return a;
+}
+
+static int resample_ratio_ok(int L, int M, int W) {
+  return L >= 1 && M >= 1 && W >= 1 && W <= QASR_RESAMPLE_MAX_W && (long long)L * 2 * W <= QASR_RESAMPLE_MAX_ENTRIES &&
+         gcd_ll(L, M) == 1;
+}
+
+int qasr_resample_check(const void* blob, size_t bytes) {
+  enum { HDR = 32 };
+  if (!blob) return fail(QASR_ERR_BLOB, "resample_check: blob is NULL");
+  if (bytes < HDR * 4 || bytes > (size_t)INT32_MAX) return fail(QASR_ERR_BLOB, "resample_check: %zu bytes is no resampling table", bytes);
+  if (((uintptr_t)blob & 3) != 0) return fail(QASR_ERR_BLOB, "resample_check: blob is not 4-byte aligned");
+  const int32_t* h = (const int32_t*)blob;
+  if (h[0] != 0x31535251 || h[1] != 1) return fail(QASR_ERR_BLOB, "resample_check: magic %#x / version %d", (unsigned)h[0], h[1]);
+  const int L = h[3], M = h[4], W = h[5], sr_in = h[6], sr_out = h[7], quality = h[8], entries = h[9];
+  if (!resample_ratio_ok(L, M, W))
+    return fail(QASR_ERR_BLOB, "resample_check: L %d / M %d (coprime, >= 1), W %d (1 .. %d) or L * 2 W (<= %d) out of range", L, M, W,
+                QASR_RESAMPLE_MAX_W, QASR_RESAMPLE_MAX_ENTRIES);
+  if (sr_in < 1 || sr_out < 1 || (long long)sr_in * L != (long long)sr_out * M)
+    return fail(QASR_ERR_BLOB, "resample_check: %d Hz -> %d Hz does not reduce to L / M = %d / %d", sr_in, sr_out, L, M);
+  if (quality != 0 && quality != 1) return fail(QASR_ERR_BLOB, "resample_check: quality %d", quality);
+  if (entries != L * 2 * W) return fail(QASR_ERR_BLOB, "resample_check: table of %d entries, L * 2 W = %d", entries, L * 2 * W);
+  const uint64_t total = 4ull * HDR + 4ull * (uint64_t)entries;
+  if (total != (uint64_t)bytes || h[2] != (int32_t)bytes)
+    return fail(QASR_ERR_BLOB, "resample_check: %zu bytes, the header describes %llu (total field %d)", bytes, (unsigned long long)total, h[2]);
+  for (int i = 10; i < HDR; ++i)
+    if (h[i] != 0) return fail(QASR_ERR_BLOB, "resample_check: reserved header word %d is %d", i, h[i]);
+  const int32_t* tab = h + HDR;
+  const int64_t limit = (int64_t)1 << 53;
+  for (int r = 0; r < L; ++r) {                                       // the accumulator bound, recomputed from the table
+    int64_t sum = 0;
+    for (int j = 0; j < 2 * W; ++j) {
+      const int64_t c = tab[(size_t)j * L + r];
+      sum += c < 0 ? -c : c;
+    }
+    if (sum * 32768 * QASR_RESAMPLE_MAX_CHANNELS >= limit)
+      return fail(QASR_ERR_BLOB, "resample_check: column %d sums to %lld: %d channels of int16 would pass 2^53 in the accumulator", r,
+                  (long long)sum, QASR_RESAMPLE_MAX_CHANNELS);
+  }
+  return QASR_OK;
+}
+
+int qasr_resample_out_samples(int in_samples, int L, int M) {
+  if (in_samples < 0 || L < 1 || M < 1) return -1;
+  const long long n = ((long long)in_samples * L + M - 1) / M;
+  return n > (long long)INT32_MAX ? -1 : (int)n;
+}
+
+int qasr_resample(void* stream, const qasr_resample_args* a) {
+  if (!a) return fail(QASR_ERR_ARG, "resample: args is NULL");
+  if (a->struct_size != sizeof(qasr_resample_args))
+    return fail(QASR_ERR_ARG, "resample: struct_size %u is not %zu", a->struct_size, sizeof(qasr_resample_args));
+  if (!a->blob || !a->in || !a->in_lens || !a->out || !a->out_lens)
+    return fail(QASR_ERR_ARG, "resample: blob, in, in_lens, out and out_lens are required");
+  if (a->B < 1 || a->B > 65535) return fail(QASR_ERR_ARG, "resample: B %d is outside 1 .. 65535", a->B);
+  if (a->channels < 1 || a->channels > QASR_RESAMPLE_MAX_CHANNELS)
+    return fail(QASR_ERR_ARG, "resample: channels %d is outside 1 .. %d", a->channels, QASR_RESAMPLE_MAX_CHANNELS);
+  if (a->dtype != QASR_PCM_S16 && a->dtype != QASR_PCM_F32) return fail(QASR_ERR_ARG, "resample: dtype %d is neither int16 nor float32", a->dtype);
+  if (!resample_ratio_ok(a->L, a->M, a->W))
+    return fail(QASR_ERR_ARG, "resample: L %d / M %d, W %d (1 .. %d) or L * 2 W (<= %d) out of range", a->L, a->M, a->W, QASR_RESAMPLE_MAX_W,
+                QASR_RESAMPLE_MAX_ENTRIES);
+  if (((uintptr_t)a->blob & 15) != 0 || a->blob_bytes != 128 + 8 * (size_t)a->L * (size_t)a->W)
+    return fail(QASR_ERR_ARG, "resample: blob must be 16-byte aligned and 128 + 4 * L * 2 W = %zu bytes, got %zu",
+                128 + 8 * (size_t)a->L * (size_t)a->W, a->blob_bytes);
+  if (a->in_pitch < 0 || a->in_pitch > QASR_RESAMPLE_MAX_PITCH || a->out_pitch < 0 || a->out_pitch > QASR_RESAMPLE_MAX_PITCH)
+    return fail(QASR_ERR_ARG, "resample: in_pitch %lld or out_pitch %lld is outside 0 .. 2^38", (long long)a->in_pitch, (long long)a->out_pitch);
+  int rc = launch_resample((hipStream_t)stream, *a);
+  if (rc) return fail(rc, "resample: launch");
+  HIPCHK(hipGetLastError());
+  return QASR_OK;
+}
+
 int qasr_engine_attach_ctc(qasr_engine* e, float* frame_score, const qasr_ctc_out* out, int use_lens) {
   if (!e) return fail(QASR_ERR_ARG, "attach_ctc: engine is NULL");
   if (frame_score || out) {

@@ -168,6 +168,8 @@ int launch_beam_boost(hipStream_t s, const qasr_ctc_beam_boost_args& a);      //
 // qasr_align.hip: CTC forced alignment and transcript scoring (k_align); the arguments are checked by qasr_ctc_align
 size_t align_workspace_bytes(int P, int T, int max_labels);
 int launch_align(hipStream_t s, const qasr_ctc_align_args& a);
+// qasr_resample.hip: rational polyphase resampler (k_resample); the arguments are checked by qasr_resample
+int launch_resample(hipStream_t s, const qasr_resample_args& a);
 // qasr_ragged.hip: the bucket policy of reserved engines and their one eager launch per call (k_ragged_stage)
 #define QASR_RAGGED_TILE 128          /* every bucket edge is a multiple of the largest frame tile */
 #define QASR_SHAPE_B 0                /* shape block, i32: rows of the batch, */

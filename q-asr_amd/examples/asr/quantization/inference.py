@@ -78,7 +78,16 @@ def main():
                         "log-probabilities (EncDecCTCModel.align): OUT gets one JSON line per utterance - audio_filepath, text, "
                         "ctc_score (log-likelihood of the text), utt_score (its best alignment) and words [word, start_s, end_s, "
                         "score]; hypotheses, WER and the other outputs are unchanged")
+    p.add_argument("--input_rate", type=int, default=None, metavar='HZ',
+                   help="(extension) every file of the manifest is 16-bit mono PCM at this rate (a telephone corpus at 8000, say): "
+                        "the batches stay int16 and are resampled to the model's rate on the device (k_resample) in front of the "
+                        "mel front-end; a file of another rate is an error.  Without it files of any rate are resampled on the "
+                        "host while they are read")
+    p.add_argument("--resample_quality", type=str, default=None, choices=['best', 'fast'],
+                   help="(extension, needs --input_rate) filter preset of the device resampler (default best)")
     args = p.parse_args()
+    if args.resample_quality is not None and args.input_rate is None:
+        p.error('--resample_quality needs --input_rate')
     if args.beam_width is not None and not 1 <= args.beam_width <= 128:
         p.error(f'--beam_width must be 1 .. 128, got {args.beam_width}')
     if args.lm_path is not None and args.beam_width is None:
@@ -106,9 +115,19 @@ def main():
     asr_model = asr_model.cuda()
     if args.dither is not None:
         asr_model.preprocessor.featurizer.dither = args.dither
+    rate_kw = {}
+    if args.input_rate is not None:
+        from qasr import resample as qresample
+        asr_model.resample_quality = args.resample_quality or 'best'
+        try:                                                 # a rate without a plan is refused here, by name
+            qresample.ResamplePlan(args.input_rate, asr_model.preprocessor._sample_rate, asr_model.resample_quality)
+        except ValueError as e:
+            p.error(f'--input_rate: {e}')
+        rate_kw = dict(sample_rate=args.input_rate)
     asr_model.setup_test_data(test_data_config={
         'sample_rate': 16000, 'manifest_filepath': args.dataset, 'labels': asr_model.decoder.vocabulary,
-        'batch_size': args.batch_size, 'normalize_transcripts': args.normalize_text, 'shuffle': args.shuffle})
+        'batch_size': args.batch_size, 'normalize_transcripts': args.normalize_text, 'shuffle': args.shuffle,
+        'input_rate': args.input_rate})
 
     distilled = None
     if args.load is not None:
@@ -159,29 +178,30 @@ def main():
         if i == args.eval_early_stop:
             break
         batch = [x.cuda() for x in batch]
+        signal = batch[0] if rate_kw else batch[0].float()   # --input_rate: int16 PCM, resampled inside the model's call
         if args.beam_width is not None:                      # k_topn + k_beam behind the forward, on the same stream
-            for h in asr_model.decode(input_signal=batch[0].float(), input_signal_length=batch[1], beam_width=args.beam_width,
-                                      **lm_kw):
+            for h in asr_model.decode(input_signal=signal, input_signal_length=batch[1], beam_width=args.beam_width,
+                                      **lm_kw, **rate_kw):
                 hyps.append(h.text)
                 beam_scores.append(h.utt_score)
                 lm_scores.append(h.lm_score)
                 boost_scores.append(h.boost_score)
         else:
-            log_probs, enc_len, greedy = asr_model(input_signal=batch[0].float(), input_signal_length=batch[1])
+            log_probs, enc_len, greedy = asr_model(input_signal=signal, input_signal_length=batch[1], **rate_kw)
             hyps += wer.ctc_decoder_predictions_tensor(greedy)
         if args.timestamps:                                  # device-side collapse up to each utterance's encoded length
-            for h in asr_model.decode(input_signal=batch[0].float(), input_signal_length=batch[1]):
+            for h in asr_model.decode(input_signal=signal, input_signal_length=batch[1], **rate_kw):
                 words.append([list(w) for w in h.words])
                 utt_scores.append(h.utt_score)
         if args.align:                                       # the reference texts' own labels, one k_align launch per batch
             ref_ids = [row[:int(n)].tolist() for row, n in zip(batch[2].cpu(), batch[3].cpu())]
-            for h in asr_model.align(input_signal=batch[0].float(), input_signal_length=batch[1], labels=ref_ids):
+            for h in asr_model.align(input_signal=signal, input_signal_length=batch[1], labels=ref_ids, **rate_kw):
                 k = len(aligned)
                 aligned.append(dict(audio_filepath=items[k][0] if not args.shuffle and k < len(items) else None, text=h.text,
                                     ctc_score=h.ctc_score, utt_score=h.utt_score, words=[list(w) for w in h.words]))
         for row in batch[2].cpu().numpy():
             refs.append(''.join(labels_map[c] for c in row))
-        audio_s += float(batch[1].sum()) / 16000.0
+        audio_s += float(batch[1].sum()) / float(args.input_rate or 16000)
     torch.cuda.synchronize()
     wall = time.time() - t0
     served = type(getattr(asr_model, '_engine', None) or getattr(asr_model, '_ragged_engine', None)).__name__

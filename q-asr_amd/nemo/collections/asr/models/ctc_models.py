@@ -54,6 +54,7 @@ class EncDecCTCModel(nn.Module):
         self._ragged_key = None
         self._ragged_warned = False
         self._quant_version = 0
+        self.resample_quality = 'best'       # filter preset of forward(..., sample_rate=): 'best' or 'fast' (qasr.resample)
 
     # ------------------------------------------------------------------ construction / checkpoints
     @classmethod
@@ -420,8 +421,36 @@ class EncDecCTCModel(nn.Module):
 
     # ------------------------------------------------------------------ forward
     def forward(self, input_signal=None, input_signal_length=None, processed_signal=None,
-                processed_signal_length=None):
+                processed_signal_length=None, sample_rate=None, channels=1):
+        """sample_rate=R / channels=C (an extension): input_signal is PCM at R Hz - int16, interleaved when C > 1, or float -
+        and input_signal_length counts frames at R; see _resample_in.  The defaults leave the call as it was."""
+        input_signal, input_signal_length = self._resample_in(input_signal, input_signal_length, sample_rate, channels)
         return self._forward(input_signal, input_signal_length, processed_signal, processed_signal_length)
+
+    def _resample_in(self, signal, length, sample_rate, channels):
+        """forward / decode / align with sample_rate=R: the batch is brought to the model's rate first - on the device
+        (k_resample, one launch on the current stream, lengths converted there) for cuda tensors, by the NumPy twin
+        (qasr.resample.resample_host) otherwise - and the existing path runs on the float32 result, reserved engine and
+        dynamic path included; reserve() keeps meaning seconds.  With sample_rate=None, or the model's own rate with a mono
+        float signal, nothing here runs."""
+        if sample_rate is None:
+            if int(channels) != 1:
+                raise ValueError('channels needs sample_rate (the rate of the interleaved PCM)')
+            return signal, length
+        if signal is None or length is None:
+            raise ValueError('sample_rate describes input_signal / input_signal_length: give both')
+        target = int(self.preprocessor._sample_rate)
+        if int(sample_rate) == target and int(channels) == 1 and signal.is_floating_point():
+            return signal, length
+        from qasr import engine as qengine, resample as qresample
+        key = (int(sample_rate), target, self.resample_quality)
+        plans = self.__dict__.setdefault('_resample_plans', {})
+        if key not in plans:
+            plans[key] = qresample.ResamplePlan(sample_rate, target, self.resample_quality)      # refuses a rate by name
+        if signal.dtype != torch.int16:
+            signal = signal.float()
+        out, out_lens = qengine.resample(signal, length, plans[key], channels=int(channels))
+        return out, out_lens.to(length.dtype)
 
     def seconds_per_frame(self):
         """Seconds per encoder output frame, from the model itself: featurizer hop x the encoder's strides (0.02 s for the
@@ -433,7 +462,7 @@ class EncDecCTCModel(nn.Module):
     @torch.no_grad()
     def decode(self, input_signal=None, input_signal_length=None, processed_signal=None, processed_signal_length=None,
                beam_width=None, n_best=1, cutoff_top_n=40, lm=None, alpha=0.0, beta=0.0, timestamps=False, boost=None,
-               boost_weight=1.0):
+               boost_weight=1.0, sample_rate=None, channels=1):
         """Greedy CTC hypotheses of one batch (an extension of the reference's API): List[qasr.ctc.Hypothesis] with the
         text, every label's start / end time and confidence (best frame log-probability of its run), word groups and the
         log-probability of the greedy path.  Decoding stops at each utterance's encoded length.  On the static engine the
@@ -462,8 +491,11 @@ class EncDecCTCModel(nn.Module):
         in nats (boost_weight where a phrase has none, 0 .. 16), an unfinished match earns nothing, and with a vocabulary
         that has a space phrases match whole words only (qasr.boost.BOOST_RULES; k_beam_boost on the device, the NumPy twin
         on the host modules).  utt_score then includes the boosting's share, which the hypotheses also carry as
-        boost_score.  The list changes per call: it is compiled and packed here, per call."""
+        boost_score.  The list changes per call: it is compiled and packed here, per call.
+
+        sample_rate / channels: as for forward() - PCM at another rate is resampled first; times stay seconds."""
         from qasr import ctc as qctc
+        input_signal, input_signal_length = self._resample_in(input_signal, input_signal_length, sample_rate, channels)
         if lm is not None and beam_width is None:
             raise ValueError('decode: lm needs beam_width (the greedy collapse has no language model)')
         if boost is not None and beam_width is None:
@@ -553,7 +585,7 @@ class EncDecCTCModel(nn.Module):
 
     @torch.no_grad()
     def align(self, input_signal=None, input_signal_length=None, processed_signal=None, processed_signal_length=None,
-              texts=None, labels=None):
+              texts=None, labels=None, sample_rate=None, channels=1):
         """Forced alignment and CTC scoring of GIVEN transcripts (an extension of the reference's API): one
         qasr.ctc.Hypothesis per utterance with the text's labels, every label's start / end time and confidence and the word
         groups of its best (Viterbi) alignment against this batch's log-probabilities, utt_score = the log-probability of that
@@ -565,6 +597,7 @@ class EncDecCTCModel(nn.Module):
         engine, dynamic path (k_align on the same stream), host modules (the NumPy twin).  A transcript with more labels (plus
         adjacent repeats) than the utterance has frames is not alignable: empty time lists, scores -inf."""
         from qasr import align as qalign
+        input_signal, input_signal_length = self._resample_in(input_signal, input_signal_length, sample_rate, channels)
         if (texts is None) == (labels is None):
             raise ValueError('align: give exactly one of texts and labels')
         vocab = list(self.decoder.vocabulary)

@@ -20,6 +20,7 @@ SYMBOLS = ['qasr_blob_check', 'qasr_engine_create', 'qasr_engine_create_ex', 'qa
            'qasr_lm_check', 'qasr_ctc_beam_lm', 'qasr_boost_check', 'qasr_ctc_beam_boost', 'qasr_ctc_align_workspace_bytes', 'qasr_ctc_align',
            'qasr_engine_reserve', 'qasr_engine_forward_ragged', 'qasr_engine_forward_ragged_audio', 'qasr_engine_ragged_stats',
            'qasr_ragged_bucket_frames', 'qasr_ragged_envelope_frames',
+           'qasr_resample_check', 'qasr_resample', 'qasr_resample_out_samples',
            'qasr_last_error', 'qasr_version']
 
 _lib = None
@@ -167,6 +168,10 @@ def load_library():
         lib.qasr_engine_ragged_stats.argtypes = [vp, C.POINTER(RaggedStats)]
         lib.qasr_ragged_bucket_frames.argtypes = [i32, i32, i32]
         lib.qasr_ragged_envelope_frames.argtypes = [i32, i32, i32]
+    if hasattr(lib, 'qasr_resample'):           # (likewise)
+        lib.qasr_resample_check.argtypes = [C.c_char_p, sz]
+        lib.qasr_resample.argtypes = [vp, C.POINTER(ResampleArgs)]
+        lib.qasr_resample_out_samples.argtypes = [i32, i32, i32]
     lib.qasr_debug_prof.argtypes = [vp]
     lib.qasr_debug_timeline.argtypes = [vp, sz]
     lib.qasr_sep_layer.argtypes = [vp, C.POINTER(SepLayerArgs), C.c_char_p, sz]
@@ -603,6 +608,97 @@ def ctc_align(log_probs, lens, targets, target_lens, blank, problems_per_utt=1, 
         _check(lib.qasr_ctc_align(_stream_ptr(stream), C.byref(a)), 'qasr_ctc_align')
     out._keep = (lp, ln, tg, tl, workspace, tab)
     return out
+
+
+class ResampleArgs(C.Structure):
+    """qasr_resample_args (include/qasr.h)"""
+    _fields_ = ([('struct_size', C.c_uint32)] + [(n, C.c_int32) for n in ('B', 'channels', 'dtype', 'L', 'M', 'W', 'reserved')] +
+                [('blob', C.c_void_p), ('blob_bytes', C.c_size_t), ('in_', C.c_void_p), ('in_lens', C.c_void_p),
+                 ('in_pitch', C.c_int64), ('out', C.c_void_p), ('out_pitch', C.c_int64), ('out_lens', C.c_void_p)])
+
+
+PCM_S16, PCM_F32 = 0, 1
+_resample_blobs = {}                    # (sr_in, sr_out, quality, device) -> the packed table on the device
+
+
+def resample_check(blob: bytes):
+    """qasr_resample_check: raises QasrError naming the first malformed field of a packed resampling table (host-only, no GPU)"""
+    lib = load_library()
+    if lib.qasr_resample_check(bytes(blob), len(blob)) != 0:
+        raise QasrError('malformed resampling table: ' + lib.qasr_last_error().decode())
+
+
+def resample_out_samples(in_samples, L, M):
+    return int(load_library().qasr_resample_out_samples(int(in_samples), int(L), int(M)))
+
+
+def resample_plan(plan, device):
+    """The packed table of a qasr.resample.ResamplePlan on `device` as a uint8 tensor: packed, validated (qasr_resample_check)
+    and uploaded once per (sr_in, sr_out, quality, device) and kept.  The upload is a host-to-device copy: the first resample
+    of a rate must run outside a stream capture (or call this first); later calls only launch."""
+    dev = torch.device(device)
+    if dev.type == 'cuda' and dev.index is None:
+        dev = torch.device('cuda', torch.cuda.current_device())
+    key = (plan.sr_in, plan.sr_out, plan.quality, dev)
+    t = _resample_blobs.get(key)
+    if t is None:
+        blob = plan.pack()
+        resample_check(blob)
+        t = _resample_blobs[key] = torch.frombuffer(bytearray(blob), dtype=torch.uint8).to(dev)
+    return t
+
+
+def resample(x, lens, plan, channels=1, out=None, out_lens=None, stream=None):
+    """qasr_resample: int16 or float32 PCM [B, S * channels] (interleaved) at plan.sr_in with `lens` frames per utterance ->
+    (float32 [B, plan.out_len(S)] at plan.sr_out, zeros behind each row's length, int32 lengths [B]): k_resample, one launch
+    on the current stream, no host synchronisation; equal to qasr.resample.resample_host byte for byte.  `out` / `out_lens`:
+    caller-owned cuda tensors (float32 [B, pitch], any pitch: a row is cut at it; int32 [B]).  A CPU tensor, or a build
+    without the library, runs the NumPy twin (the results return on x's device)."""
+    from . import resample as rs
+    ch = int(channels)
+    if x.dim() != 2 or x.dtype not in (torch.int16, torch.float32):
+        raise ValueError(f'resample: samples must be an int16 or float32 tensor [B, S * channels], got {x.dtype} {tuple(x.shape)}')
+    if not 1 <= ch <= rs.MAX_CHANNELS or x.shape[1] % ch:
+        raise ValueError(f'resample: channels must be 1 .. {rs.MAX_CHANNELS} and divide the row of {x.shape[1]} samples, got {ch}')
+    B, S = x.shape[0], x.shape[1] // ch
+    if not x.is_cuda or not os.path.exists(LIB_PATH):
+        o, ol = rs.resample_host(x.cpu().numpy(), lens.cpu().numpy(), plan, ch)
+        o, ol = torch.from_numpy(o).to(x.device), torch.from_numpy(ol).to(x.device)
+        if out is not None:
+            w = min(out.shape[1], o.shape[1])
+            out.zero_()
+            out[:, :w] = o[:, :w]
+            o, ol = out, ol.clamp(max=out.shape[1])
+        if out_lens is not None:
+            out_lens.copy_(ol)
+            ol = out_lens
+        return o, ol
+    lib = load_library()
+    dev = x.device
+    blob = resample_plan(plan, dev)
+    xc = x.contiguous()
+    ln = lens.to(device=dev, dtype=torch.int32).contiguous()
+    if out is None:
+        out = torch.empty(B, plan.out_len(S), device=dev, dtype=torch.float32)
+    if out_lens is None:
+        out_lens = torch.empty(B, device=dev, dtype=torch.int32)
+    assert out.is_cuda and out.dtype == torch.float32 and out.dim() == 2 and out.shape[0] == B and out.stride(1) == 1, 'resample: out'
+    assert out_lens.is_cuda and out_lens.dtype == torch.int32 and out_lens.is_contiguous() and out_lens.numel() == B, \
+        'resample: out_lens'
+    if B == 0:
+        return out, out_lens
+    a = ResampleArgs()
+    a.struct_size = C.sizeof(ResampleArgs)
+    a.B, a.channels, a.dtype = B, ch, PCM_S16 if x.dtype == torch.int16 else PCM_F32
+    a.L, a.M, a.W = plan.L, plan.M, plan.W
+    a.blob, a.blob_bytes = blob.data_ptr(), blob.numel()
+    a.in_, a.in_lens, a.in_pitch = xc.data_ptr(), ln.data_ptr(), S
+    a.out, a.out_pitch, a.out_lens = out.data_ptr(), (out.stride(0) if B > 1 else out.shape[1]), out_lens.data_ptr()
+    if B > 1 and out.stride(0) != out.shape[1]:
+        raise ValueError('resample: out must have contiguous rows (zeros are written to the pitch)')
+    with torch.cuda.device(dev):
+        _check(lib.qasr_resample(_stream_ptr(stream), C.byref(a)), 'qasr_resample')
+    return out, out_lens
 
 
 class Engine:
