@@ -539,6 +539,60 @@ typedef struct qasr_resample_args {
 int qasr_resample(void* stream, const qasr_resample_args* args);
 int qasr_resample_out_samples(int in_samples, int L, int M);
 
+/* ---- long recordings: overlapped windows cut and stitched on the device --------------------------------------------------
+ * A recording is cut into equal windows that overlap (k_cut), the windows run through the engine as a batch, and the
+ * per-frame outputs of neighbouring windows are joined at one frame of their overlap, the seam (k_stitch).  The plan and the
+ * seam rule are qasr/longform.py (WindowPlan, SEAM_RULES), which both kernels follow byte for byte.  Normalisation is per
+ * window: the stitched result is not that of one run over the whole recording.
+ *   table    device i32 [Wn][4] = (recording, start_sample, n_samples, first_global_frame), windows of one recording adjacent
+ *            and ascending, as WindowPlan lays them out (the kernels trust it up to memory safety: a recording outside
+ *            0 .. R - 1 gives an empty window / writes nothing)
+ * qasr_longform_cut: audio f32 [R][pitch], lens i32 [R] -> windows f32 [Wn][Wl] (window k = min(n_samples, lens - start)
+ *   samples, zeros behind them) and window_lens i32 [Wn].  One launch; can be captured.
+ * qasr_longform_stitch: one launch; can be captured.
+ *   enc_lens     device i32 [Wn]: encoded frames per window (clamped to 0 .. min(Tw, 2 * hop_frames))
+ *   tokens       device i32 [Wn][Tw], frame_score f32 [Wn][Tw] or NULL: what the seam is chosen from
+ *   planes       n_planes <= QASR_LONGFORM_MAX_PLANES of (src [Wn][Tw][bytes_per_frame], dst [R][Tmax][bytes_per_frame],
+ *                bytes_per_frame a multiple of 4, fill: the 32-bit word written where no window holds a frame and behind
+ *                total_frames); tokens / frame_score are stitched only if they are listed as planes too
+ *   total_frames device i32 [R] = min(first_global_frame(last) + enc_len(last), Tmax);  seams device i32 [Wn] = the first
+ *                global frame window k contributes (0 for a recording's first window)
+ *   guard, hop_frames (H / samples_per_frame), blank, seam_mode: the plan's and SEAM_RULES'
+ * QASR_ERR_ARG with nothing launched and no output written: an unknown struct_size, a NULL among the required pointers (all
+ * but frame_score; every listed plane's src and dst), Wn < 1, R < 1, Wl / Tw / Tmax / hop_frames < 1, pitch < 0, n_planes
+ * outside 0 .. QASR_LONGFORM_MAX_PLANES, a bytes_per_frame that is < 4 or no multiple of 4, guard < 0, an unknown seam_mode. */
+#define QASR_LONGFORM_MAX_PLANES 6
+enum { QASR_SEAM_BLANK = 0, QASR_SEAM_MIDDLE = 1 };
+typedef struct qasr_longform_cut_args {
+  uint32_t struct_size;        /* sizeof of this struct in the caller's header */
+  int32_t R, Wn, Wl;
+  const float* audio;
+  int64_t pitch;               /* floats per audio row */
+  const int32_t* lens;
+  const int32_t* table;
+  float* windows;
+  int32_t* window_lens;
+} qasr_longform_cut_args;
+int qasr_longform_cut(void* stream, const qasr_longform_cut_args* args);
+typedef struct qasr_longform_plane {
+  const void* src;
+  void* dst;
+  int64_t bytes_per_frame;
+  uint32_t fill, reserved;
+} qasr_longform_plane;
+typedef struct qasr_longform_stitch_args {
+  uint32_t struct_size;        /* sizeof of this struct in the caller's header */
+  int32_t R, Wn, Tw, Tmax, guard, hop_frames, blank, seam_mode, n_planes;
+  const int32_t* table;
+  const int32_t* enc_lens;
+  const int32_t* tokens;
+  const float* frame_score;    /* optional */
+  int32_t* total_frames;
+  int32_t* seams;
+  qasr_longform_plane planes[QASR_LONGFORM_MAX_PLANES];
+} qasr_longform_stitch_args;
+int qasr_longform_stitch(void* stream, const qasr_longform_stitch_args* args);
+
 /* ---- reserved engines: ragged batches without allocation, with graph replay ------------------------------------------
  * A data loader pads every batch to its own longest utterance (the reference's collate function), so (B, T) changes on
  * almost every call; qasr_engine_forward[_audio] then rebuilds its plan (device-synchronising frees + allocations) and,

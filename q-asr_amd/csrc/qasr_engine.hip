@@ -1370,6 +1370,49 @@ int qasr_resample(void* stream, const qasr_resample_args* a) {
   return QASR_OK;
 }
 
+// ---- long recordings (k_cut, k_stitch, qasr_longform.hip): the checks of include/qasr.h and one launch each
+int qasr_longform_cut(void* stream, const qasr_longform_cut_args* a) {
+  if (!a) return fail(QASR_ERR_ARG, "longform_cut: args is NULL");
+  if (a->struct_size != sizeof(qasr_longform_cut_args))
+    return fail(QASR_ERR_ARG, "longform_cut: struct_size %u is not %zu", a->struct_size, sizeof(qasr_longform_cut_args));
+  if (!a->audio || !a->lens || !a->table || !a->windows || !a->window_lens)
+    return fail(QASR_ERR_ARG, "longform_cut: audio, lens, table, windows and window_lens are required");
+  if (a->Wn < 1 || a->Wn > 65535) return fail(QASR_ERR_ARG, "longform_cut: Wn %d is outside 1 .. 65535", a->Wn);
+  if (a->R < 1 || a->Wl < 1 || a->pitch < 0)
+    return fail(QASR_ERR_ARG, "longform_cut: R %d, Wl %d (both >= 1) or pitch %lld (>= 0) out of range", a->R, a->Wl, (long long)a->pitch);
+  int rc = launch_longform_cut((hipStream_t)stream, *a);
+  if (rc) return fail(rc, "longform_cut: launch");
+  HIPCHK(hipGetLastError());
+  return QASR_OK;
+}
+
+int qasr_longform_stitch(void* stream, const qasr_longform_stitch_args* a) {
+  if (!a) return fail(QASR_ERR_ARG, "longform_stitch: args is NULL");
+  if (a->struct_size != sizeof(qasr_longform_stitch_args))
+    return fail(QASR_ERR_ARG, "longform_stitch: struct_size %u is not %zu", a->struct_size, sizeof(qasr_longform_stitch_args));
+  if (!a->table || !a->enc_lens || !a->tokens || !a->total_frames || !a->seams)
+    return fail(QASR_ERR_ARG, "longform_stitch: table, enc_lens, tokens, total_frames and seams are required");
+  if (a->Wn < 1) return fail(QASR_ERR_ARG, "longform_stitch: Wn %d < 1", a->Wn);
+  if (a->R < 1 || a->Tw < 1 || a->Tmax < 1 || a->hop_frames < 1)
+    return fail(QASR_ERR_ARG, "longform_stitch: R %d, Tw %d, Tmax %d or hop_frames %d < 1", a->R, a->Tw, a->Tmax, a->hop_frames);
+  if (a->guard < 0) return fail(QASR_ERR_ARG, "longform_stitch: guard %d < 0", a->guard);
+  if (a->seam_mode != QASR_SEAM_BLANK && a->seam_mode != QASR_SEAM_MIDDLE)
+    return fail(QASR_ERR_ARG, "longform_stitch: seam_mode %d is neither blank nor middle", a->seam_mode);
+  if (a->n_planes < 0 || a->n_planes > QASR_LONGFORM_MAX_PLANES)
+    return fail(QASR_ERR_ARG, "longform_stitch: %d planes, at most %d", a->n_planes, QASR_LONGFORM_MAX_PLANES);
+  for (int k = 0; k < a->n_planes; ++k) {
+    const qasr_longform_plane& q = a->planes[k];
+    if (!q.src || !q.dst) return fail(QASR_ERR_ARG, "longform_stitch: plane %d has a NULL src or dst", k);
+    if (q.bytes_per_frame < 4 || q.bytes_per_frame % 4 != 0)
+      return fail(QASR_ERR_ARG, "longform_stitch: plane %d: bytes_per_frame %lld is not a positive multiple of 4", k, (long long)q.bytes_per_frame);
+    if ((((uintptr_t)q.src | (uintptr_t)q.dst) & 3) != 0) return fail(QASR_ERR_ARG, "longform_stitch: plane %d is not 4-byte aligned", k);
+  }
+  int rc = launch_longform_stitch((hipStream_t)stream, *a);
+  if (rc) return fail(rc, "longform_stitch: launch");
+  HIPCHK(hipGetLastError());
+  return QASR_OK;
+}
+
 int qasr_engine_attach_ctc(qasr_engine* e, float* frame_score, const qasr_ctc_out* out, int use_lens) {
   if (!e) return fail(QASR_ERR_ARG, "attach_ctc: engine is NULL");
   if (frame_score || out) {

@@ -170,6 +170,9 @@ size_t align_workspace_bytes(int P, int T, int max_labels);
 int launch_align(hipStream_t s, const qasr_ctc_align_args& a);
 // qasr_resample.hip: rational polyphase resampler (k_resample); the arguments are checked by qasr_resample
 int launch_resample(hipStream_t s, const qasr_resample_args& a);
+// qasr_longform.hip: windows of long recordings cut (k_cut) and stitched (k_stitch); the arguments are checked by the callers
+int launch_longform_cut(hipStream_t s, const qasr_longform_cut_args& a);
+int launch_longform_stitch(hipStream_t s, const qasr_longform_stitch_args& a);
 // qasr_ragged.hip: the bucket policy of reserved engines and their one eager launch per call (k_ragged_stage)
 #define QASR_RAGGED_TILE 128          /* every bucket edge is a multiple of the largest frame tile */
 #define QASR_SHAPE_B 0                /* shape block, i32: rows of the batch, */

@@ -85,7 +85,16 @@ def main():
                         "host while they are read")
     p.add_argument("--resample_quality", type=str, default=None, choices=['best', 'fast'],
                    help="(extension, needs --input_rate) filter preset of the device resampler (default best)")
+    p.add_argument("--window_s", type=float, default=None, metavar='SECONDS',
+                   help="(extension, for long recordings) cut every manifest entry into windows of this many seconds, run them as "
+                        "batches of --batch_size and stitch the results on the device (EncDecCTCModel.decode_long)")
+    p.add_argument("--overlap_s", type=float, default=None, metavar='SECONDS',
+                   help="(extension, needs --window_s) overlap of neighbouring windows (default 4.0)")
     args = p.parse_args()
+    if args.overlap_s is not None and args.window_s is None:
+        p.error('--overlap_s needs --window_s')
+    if args.window_s is not None and args.timestamps and args.beam_width is not None:
+        p.error('--timestamps with --window_s and --beam_width is not offered: stitched beam hypotheses carry no times')
     if args.resample_quality is not None and args.input_rate is None:
         p.error('--resample_quality needs --input_rate')
     if args.beam_width is not None and not 1 <= args.beam_width <= 128:
@@ -179,7 +188,24 @@ def main():
             break
         batch = [x.cuda() for x in batch]
         signal = batch[0] if rate_kw else batch[0].float()   # --input_rate: int16 PCM, resampled inside the model's call
-        if args.beam_width is not None:                      # k_topn + k_beam behind the forward, on the same stream
+        if args.window_s is not None:                        # k_cut, windows in batches, k_stitch, one collapse / search
+            overlap_s = 4.0 if args.overlap_s is None else args.overlap_s
+            try:
+                long_hyps = asr_model.decode_long(signal, batch[1], window_s=args.window_s, overlap_s=overlap_s,
+                                                  guard_s=min(1.0, overlap_s / 4), batch_size=args.batch_size,
+                                                  beam_width=args.beam_width, **lm_kw, **rate_kw)
+            except ValueError as e:
+                p.error(f'--window_s / --overlap_s: {e}')
+            for h in long_hyps:
+                hyps.append(h.text)
+                if args.beam_width is not None:
+                    beam_scores.append(h.utt_score)
+                    lm_scores.append(h.lm_score)
+                    boost_scores.append(h.boost_score)
+                elif args.timestamps:
+                    words.append([list(w) for w in h.words])
+                    utt_scores.append(h.utt_score)
+        elif args.beam_width is not None:                    # k_topn + k_beam behind the forward, on the same stream
             for h in asr_model.decode(input_signal=signal, input_signal_length=batch[1], beam_width=args.beam_width,
                                       **lm_kw, **rate_kw):
                 hyps.append(h.text)
@@ -189,7 +215,7 @@ def main():
         else:
             log_probs, enc_len, greedy = asr_model(input_signal=signal, input_signal_length=batch[1], **rate_kw)
             hyps += wer.ctc_decoder_predictions_tensor(greedy)
-        if args.timestamps:                                  # device-side collapse up to each utterance's encoded length
+        if args.timestamps and args.window_s is None:        # device-side collapse up to each utterance's encoded length
             for h in asr_model.decode(input_signal=signal, input_signal_length=batch[1], **rate_kw):
                 words.append([list(w) for w in h.words])
                 utt_scores.append(h.utt_score)

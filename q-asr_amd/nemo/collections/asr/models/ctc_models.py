@@ -53,6 +53,7 @@ class EncDecCTCModel(nn.Module):
         self._ragged_engine = None           # the reserved engine of the current quantiser state / device
         self._ragged_key = None
         self._ragged_warned = False
+        self._reserve_logp = True            # decode_long's own greedy reservation keeps no log-probabilities
         self._quant_version = 0
         self.resample_quality = 'best'       # filter preset of forward(..., sample_rate=): 'best' or 'fast' (qasr.resample)
 
@@ -156,15 +157,19 @@ class EncDecCTCModel(nn.Module):
         return self._test_dl
 
     @torch.no_grad()
-    def transcribe(self, paths2audio_files, batch_size=4, logprobs=False, return_hypotheses=False):
+    def transcribe(self, paths2audio_files, batch_size=4, logprobs=False, return_hypotheses=False, window_s=None,
+                   overlap_s=4.0):
         """Greedy transcripts (or per-file log-probabilities) of audio files, in input order - the reference's debugging /
         prototyping entry (ctc_models.py:148-212, 476-503): dither off and pad_to 0 for the duration of the call, evaluation
         mode, a temporary manifest with `duration` 100000 and text 'nothing', batch size min(batch_size, #files), silence
         trimmed (`trim_silence: True`), everything restored afterwards.  A calibrated model runs on the HIP engine.
         return_hypotheses=True (an extension): qasr.ctc.Hypothesis objects - text, label and word times, confidences - from
-        decode() instead of strings."""
+        decode() instead of strings.  window_s=SECONDS (an extension, for long files): every batch goes through decode_long
+        with windows of window_s that overlap by overlap_s (guard: a quarter of the overlap, at most 1 s) instead."""
         if paths2audio_files is None or len(paths2audio_files) == 0:
             return {}
+        if window_s is not None and logprobs:
+            raise ValueError('transcribe: window_s returns transcripts or hypotheses, not log-probabilities')
         import json
         import tempfile
         from nemo.collections.asr.data.audio_to_text import make_dataloader
@@ -187,6 +192,11 @@ class EncDecCTCModel(nn.Module):
                                           'shuffle': False})
                 wer = WER(vocabulary=self.decoder.vocabulary)
                 for batch in loader:
+                    if window_s is not None:
+                        hyps = self.decode_long(batch[0].to(device).float(), batch[1].to(device), window_s=window_s,
+                                                overlap_s=overlap_s, guard_s=min(1.0, float(overlap_s) / 4))
+                        hypotheses += hyps if return_hypotheses else [h.text for h in hyps]
+                        continue
                     if return_hypotheses and not logprobs:
                         hypotheses += self.decode(input_signal=batch[0].to(device).float(),
                                                   input_signal_length=batch[1].to(device))
@@ -319,7 +329,8 @@ class EncDecCTCModel(nn.Module):
             return None
         f = self.preprocessor.featurizer
         pad_to = int(f.pad_to) if 0 < int(f.pad_to) and 128 % int(f.pad_to) == 0 else 16
-        key = (self._quant_version, device.index or 0, self._reserve, pad_to)
+        want_logp = bool(getattr(self, '_reserve_logp', True))
+        key = (self._quant_version, device.index or 0, self._reserve, pad_to, want_logp)
         if self._ragged_engine is None or self._ragged_key != key:
             from qasr import engine as qengine, pack, ragged
             qengine.load_library()
@@ -331,7 +342,7 @@ class EncDecCTCModel(nn.Module):
             eng = qengine.Engine(blob, device.index or 0)
             # both entries share the envelope: audio (pad_to > 0) and features (transcribe() runs with pad_to 0)
             eng.reserve(max_batch, max_samples=max_samples, max_frames=ragged.frontend_frames(max_samples, pad_to),
-                        want_logp=True, decode=True, n_mels=int(f.fb.shape[1]), pad_to=pad_to)
+                        want_logp=want_logp, decode=True, n_mels=int(f.fb.shape[1]), pad_to=pad_to)
             self._ragged_engine, self._ragged_key = eng, key
         return self._ragged_engine
 
@@ -371,7 +382,9 @@ class EncDecCTCModel(nn.Module):
                 if processed_signal.shape[0] <= r.max_batch and processed_signal.shape[2] <= M:
                     out = eng.forward_ragged(processed_signal.float(), processed_signal_length, stream=side)
             if out is not None:                                  # views of the engine's buffers: callers keep results across batches
-                if decode:
+                if decode == 'frames':                           # decode_long: (tokens, frame scores, encoded lengths)
+                    out = (out[1].clone(), out[3].frame_score.clone(), out[2].clone())
+                elif decode:
                     res = out[3]
                     out = dataclasses.replace(res, **{k: getattr(res, k).clone() for k in
                                                       ('labels', 'n_labels', 'start', 'nframes', 'score', 'utt_score', 'frame_score')})
@@ -514,6 +527,148 @@ class EncDecCTCModel(nn.Module):
         res = self._forward(input_signal, input_signal_length, processed_signal, processed_signal_length, decode=True)
         return qctc.to_hypotheses(res, self.decoder.vocabulary, self.seconds_per_frame())
 
+    def _long_plan(self, lens_samples, window_s=30.0, overlap_s=4.0, guard_s=1.0):
+        """the qasr.longform.WindowPlan of decode_long for recordings of lens_samples samples at the model's rate; its row
+        pitch counts the frames the front-end pads a window to (pad_to), as the engine's outputs do"""
+        from qasr import longform as qlong, ragged
+        f = self.preprocessor.featurizer
+        rate = int(self.preprocessor._sample_rate)
+        spf = int(round(self.seconds_per_frame() * rate))
+        stride = max(spf // int(f.hop_length), 1)
+        pad_to = int(f.pad_to) if isinstance(f.pad_to, int) and f.pad_to > 0 else 0
+
+        def frames_of(n):
+            t = 1 + n // int(f.hop_length)
+            if pad_to and t % pad_to:
+                t += pad_to - t % pad_to
+            return -(-t // stride)
+
+        return qlong.WindowPlan(lens_samples, window_s, overlap_s, guard_s, rate, spf, frames_of)
+
+    @torch.no_grad()
+    def decode_long(self, input_signal, input_signal_length, window_s=30.0, overlap_s=4.0, guard_s=1.0, batch_size=32,
+                    seam='blank', beam_width=None, n_best=1, cutoff_top_n=40, lm=None, alpha=0.0, beta=0.0, boost=None,
+                    boost_weight=1.0, sample_rate=None, channels=1):
+        """Hypotheses of long recordings (an extension; buffered inference on the device): input_signal [R, S] with
+        input_signal_length samples each -> List[qasr.ctc.Hypothesis], one per recording, times in seconds of the recording,
+        seams_s = the times at which neighbouring windows were joined (None for a recording of one window: its hypothesis
+        is decode()'s).
+
+        Each recording is cut into windows of window_s seconds that overlap by overlap_s (k_cut); the windows of all
+        recordings run through the model in batches of batch_size - on the calibrated model through a reserved engine, so
+        every batch replays one captured graph: reserve() is honoured, and without one (batch_size, window_s) is reserved
+        for the duration of the call - then k_stitch joins the windows' frames at one seam per pair, chosen under
+        qasr.longform.SEAM_RULES (seam='blank': where both windows agree on a blank, the most confident such frame, then
+        the middle of the overlap; 'middle': the middle alone), keeping guard_s of every window edge out of the choice, and
+        the greedy collapse (k_ctc) runs once on the stitched rows.  The greedy path keeps tokens and per-frame scores only:
+        on the static engine no log-probability tensor is written.  beam_width / n_best / cutoff_top_n / lm / alpha / beta /
+        boost / boost_weight: as decode(); k_topn runs per batch, the candidates are stitched and the beam search runs once
+        per recording, which may then have at most qasr.beam.MAX_T (QASR_BEAM_MAX_FRAMES) stitched frames; beam hypotheses
+        carry no times.  sample_rate / channels: as forward().  CPU inputs run the NumPy twins.  When no recording of the
+        batch is longer than a window, nothing is cut and the batch runs as decode() runs it: the hypotheses are decode()'s.
+
+        Normalisation - the front-end's per-feature statistics, dynamic ranges - is per window: the result is NOT that of
+        decode() over the whole recording, and the defaults (30 s / 4 s / 1 s) are not tuned on speech."""
+        from qasr import beam as qbeam, ctc as qctc, engine as qengine
+        if input_signal is None or input_signal_length is None:
+            raise ValueError('decode_long: input_signal and input_signal_length are required')
+        if lm is not None and beam_width is None:
+            raise ValueError('decode_long: lm needs beam_width (the greedy collapse has no language model)')
+        if boost is not None and beam_width is None:
+            raise ValueError('decode_long: boost needs beam_width (the greedy collapse has no phrase boosting)')
+        if seam not in ('blank', 'middle'):
+            raise ValueError(f"decode_long: seam must be 'blank' or 'middle', got {seam!r}")
+        batch_size = int(batch_size)
+        if batch_size < 1:
+            raise ValueError(f'decode_long: batch_size must be at least 1, got {batch_size}')
+        if beam_width is not None:
+            beam_width, n_best, cutoff_top_n = self._beam_args(beam_width, n_best, cutoff_top_n)
+            lm = self._lm_args(lm, alpha, beta)
+            if boost is not None:
+                from qasr import boost as qboost
+                try:
+                    boost = qboost.as_phrase_set(boost, self.decoder.vocabulary, boost_weight)
+                except ValueError as e:
+                    raise ValueError(f'decode_long: {e}') from None
+        signal, length = self._resample_in(input_signal, input_signal_length, sample_rate, channels)
+        if signal.dim() != 2:
+            raise ValueError(f'decode_long: input_signal must be [R, S], got {tuple(signal.shape)}')
+        signal = signal.float()
+        lens_host = length.detach().cpu().long().clamp(max=signal.shape[1])
+        plan = self._long_plan(lens_host.numpy(), window_s, overlap_s, guard_s)      # refuses its arguments by name
+        blank = len(self.decoder.vocabulary)
+        cuda = signal.is_cuda
+        if plan.Wn == plan.R:                # nothing to cut: the batch runs as decode() runs it, padded as it came (the
+            windows, wlens = signal, lens_host.to(signal.device)      # front-end's reflect padding folds at the batch's width)
+        else:
+            windows, wlens = qengine.longform_cut(signal, lens_host.to(signal.device), plan)
+        own = cuda and self._reserve is None and self.engine_ready()
+        if own:                              # for this call: every full batch replays one graph
+            self._reserve = (batch_size, max(plan.Wl, windows.shape[1]) / float(plan.sample_rate))
+            self._reserve_logp = beam_width is not None
+        toks = fs = enc = cid = cq = None
+        try:
+            for i in range(0, plan.Wn, batch_size):
+                sig, ln = windows[i:i + batch_size], wlens[i:i + batch_size].to(length.dtype)
+                if beam_width is None:
+                    t, f, e = self._forward(sig, ln, decode='frames')
+                else:                        # the log-probabilities live for one batch: only the candidates are kept
+                    logp, e, t = self._forward(sig, ln)
+                    f = self._frame_scores(logp, t)
+                    if cuda:
+                        c = qengine.ctc_topn(logp.float(), e, cutoff_top_n)
+                    else:
+                        c = [torch.from_numpy(x) for x in qbeam.topn_host(logp.float().numpy(), cutoff_top_n, e.numpy())]
+                if toks is None:
+                    Tw, dev = t.shape[1], t.device
+                    toks = torch.empty(plan.Wn, Tw, device=dev, dtype=torch.int32)
+                    fs = torch.empty(plan.Wn, Tw, device=dev, dtype=torch.float32)
+                    enc = torch.empty(plan.Wn, device=dev, dtype=torch.int32)
+                    if beam_width is not None:
+                        cid = torch.empty(plan.Wn, Tw, c[0].shape[2], device=dev, dtype=torch.int32)
+                        cq = torch.empty_like(cid)
+                b = t.shape[0]
+                toks[i:i + b].copy_(t)
+                fs[i:i + b].copy_(f)
+                enc[i:i + b].copy_(e)
+                if beam_width is not None:
+                    cid[i:i + b].copy_(c[0])
+                    cq[i:i + b].copy_(c[1])
+        finally:
+            if own:
+                self._reserve, self._reserve_logp = None, True
+        planes = () if beam_width is None else (cid, cq)
+        out, total, seams = qengine.longform_stitch(plan, enc, toks, fs, planes, blank, seam)
+        spf_s = self.seconds_per_frame()
+        seams_h = seams.cpu().numpy()
+        seams_s = [[float(seams_h[w]) * spf_s for w in range(int(plan.first[r]) + 1, int(plan.first[r]) + int(plan.count[r]))]
+                   if plan.count[r] > 1 else None for r in range(plan.R)]      # one window: decode()'s own hypothesis
+        if beam_width is None:
+            if cuda:
+                res = qengine.ctc_collapse(out[0], out[1], total, blank=blank)
+            else:
+                res = qctc.collapse_host(out[0].numpy(), out[1].numpy(), total.numpy(), blank=blank)
+            hyps = qctc.to_hypotheses(res, self.decoder.vocabulary, spf_s)
+            for h, s in zip(hyps, seams_s):
+                h.seams_s = s
+            return hyps
+        total_h = total.cpu().numpy()
+        for r in range(plan.R):
+            if int(total_h[r]) > qbeam.MAX_T:
+                raise ValueError(f'decode_long: recording {r} has {int(total_h[r])} stitched frames; the beam search takes at most '
+                                 f'QASR_BEAM_MAX_FRAMES = {qbeam.MAX_T} frames per recording')
+        T = max(int(total_h.max()), 1)
+        scid, scq = out[2][:, :T].contiguous(), out[3][:, :T].contiguous()
+        if cuda:
+            res = qengine.ctc_beam(scid, scq, total, blank, beam_width, n_best, lm=lm, alpha=alpha, beta=beta, boost=boost)
+        else:
+            res = qbeam.beam_search_host(scid.numpy(), scq.numpy(), total_h, blank, beam_width, n_best, lm, alpha, beta, boost)
+        hyps = qbeam.to_hypotheses(res, self.decoder.vocabulary)
+        for row, s in zip(hyps, seams_s):
+            for h in row:
+                h.seams_s = s
+        return hyps if n_best > 1 else [h[0] for h in hyps]
+
     @staticmethod
     def _beam_args(beam_width, n_best, cutoff_top_n):
         from qasr import beam as qbeam
@@ -635,11 +790,15 @@ class EncDecCTCModel(nn.Module):
             res = qalign.align_host(log_probs.float().numpy(), enc_len.numpy(), tg, tl, blank)
         return qalign.to_hypotheses(res, vocab, self.seconds_per_frame())
 
+    @staticmethod
+    def _frame_scores(log_probs, tokens):
+        return log_probs.float().gather(2, tokens.long().unsqueeze(-1)).squeeze(-1)
+
     def _collapse(self, log_probs, tokens, enc_len):
         """decode() behind a path that returned log-probabilities: frame scores = log_probs at the tokens"""
         from qasr import ctc as qctc
         blank = len(self.decoder.vocabulary)
-        fs = log_probs.float().gather(2, tokens.long().unsqueeze(-1)).squeeze(-1)
+        fs = self._frame_scores(log_probs, tokens)
         if tokens.is_cuda:
             from qasr import engine as qengine
             return qengine.ctc_collapse(tokens.to(torch.int32), fs, enc_len.to(torch.int32), blank=blank)
@@ -647,7 +806,9 @@ class EncDecCTCModel(nn.Module):
 
     def _forward(self, input_signal=None, input_signal_length=None, processed_signal=None,
                  processed_signal_length=None, decode=False):
-        """forward(); decode=True returns the CTC collapse of the batch (a qasr.ctc.CtcResult) instead of the triple"""
+        """forward(); decode=True returns the CTC collapse of the batch (a qasr.ctc.CtcResult) instead of the triple;
+        decode='frames' (decode_long) returns (tokens, frame scores, encoded lengths) - on the static and the reserved
+        engine from the decoder kernel itself, without log-probabilities"""
         has_in = input_signal is not None and input_signal_length is not None
         has_pr = processed_signal is not None and processed_signal_length is not None
         if has_in == has_pr:
@@ -680,14 +841,16 @@ class EncDecCTCModel(nn.Module):
                 audio_lens = input_signal_length.to(device=ref.device, dtype=torch.int32).contiguous()
                 window = f.window.to(device=ref.device, dtype=torch.float32).contiguous()
                 if decode:                                       # tokens only: the scores come from the decoder kernel
-                    return eng.forward_audio(sig, audio_lens, fb, window, plan, float(f.preemph), int(f.pad_to),
-                                             want_logp=False, decode=True)[3]
+                    out = eng.forward_audio(sig, audio_lens, fb, window, plan, float(f.preemph), int(f.pad_to),
+                                            want_logp=False, decode=True)
+                    return (out[1], out[3].frame_score, out[2]) if decode == 'frames' else out[3]
                 log_probs, tokens, enc_len = eng.forward_audio(sig, audio_lens, fb, window, plan, float(f.preemph), int(f.pad_to))
                 return log_probs, enc_len.long(), tokens.long()
             if has_in:
                 processed_signal, processed_signal_length = self._frontend_hip(input_signal, input_signal_length)
             if decode:
-                return eng.forward(processed_signal.float(), processed_signal_length, want_logp=False, decode=True)[3]
+                out = eng.forward(processed_signal.float(), processed_signal_length, want_logp=False, decode=True)
+                return (out[1], out[3].frame_score, out[2]) if decode == 'frames' else out[3]
             log_probs, tokens, enc_len = eng.forward(processed_signal.float(), processed_signal_length)
             return log_probs, enc_len.long(), tokens.long()
         if ref.is_cuda and self.dynamic_ready():
@@ -696,6 +859,8 @@ class EncDecCTCModel(nn.Module):
                 if has_in:
                     processed_signal, processed_signal_length = self._frontend_hip(input_signal, input_signal_length)
                 out = runner.forward(processed_signal.float(), processed_signal_length)
+                if decode == 'frames':
+                    return out['tokens'], self._frame_scores(out['log_probs'], out['tokens']), out['enc_len']
                 if decode:
                     return self._collapse(out['log_probs'], out['tokens'], out['enc_len'])
                 return out['log_probs'], out['enc_len'].long(), out['tokens'].long()
@@ -704,6 +869,9 @@ class EncDecCTCModel(nn.Module):
                                                                           length=input_signal_length)
         encoded, encoded_len, encoded_sf = self.encoder(audio_signal=processed_signal, length=processed_signal_length)
         log_probs = self.decoder(encoder_output=encoded, encoder_output_scaling_factor=encoded_sf)
+        if decode == 'frames':
+            tokens = log_probs.argmax(dim=-1, keepdim=False)
+            return tokens, self._frame_scores(log_probs, tokens), encoded_len
         if decode:
             return self._collapse(log_probs, log_probs.argmax(dim=-1, keepdim=False), encoded_len)
         return log_probs, encoded_len, log_probs.argmax(dim=-1, keepdim=False)

@@ -38,6 +38,7 @@ class Hypothesis:
     lm_score: Optional[float] = None        # beam search with a language model: the model's share of utt_score
     ctc_score: Optional[float] = None       # forced alignment (qasr.align): the CTC log-likelihood of the text, all alignments
     boost_score: Optional[float] = None     # beam search with phrase boosting (qasr.boost): the boosting's share of utt_score
+    seams_s: Optional[List[float]] = None   # decode_long (qasr.longform): the times at which neighbouring windows were joined
 
 
 def _order_key(x):

@@ -20,7 +20,7 @@ SYMBOLS = ['qasr_blob_check', 'qasr_engine_create', 'qasr_engine_create_ex', 'qa
            'qasr_lm_check', 'qasr_ctc_beam_lm', 'qasr_boost_check', 'qasr_ctc_beam_boost', 'qasr_ctc_align_workspace_bytes', 'qasr_ctc_align',
            'qasr_engine_reserve', 'qasr_engine_forward_ragged', 'qasr_engine_forward_ragged_audio', 'qasr_engine_ragged_stats',
            'qasr_ragged_bucket_frames', 'qasr_ragged_envelope_frames',
-           'qasr_resample_check', 'qasr_resample', 'qasr_resample_out_samples',
+           'qasr_resample_check', 'qasr_resample', 'qasr_resample_out_samples', 'qasr_longform_cut', 'qasr_longform_stitch',
            'qasr_last_error', 'qasr_version']
 
 _lib = None
@@ -172,6 +172,9 @@ def load_library():
         lib.qasr_resample_check.argtypes = [C.c_char_p, sz]
         lib.qasr_resample.argtypes = [vp, C.POINTER(ResampleArgs)]
         lib.qasr_resample_out_samples.argtypes = [i32, i32, i32]
+    if hasattr(lib, 'qasr_longform_cut'):       # (likewise)
+        lib.qasr_longform_cut.argtypes = [vp, C.POINTER(LongformCutArgs)]
+        lib.qasr_longform_stitch.argtypes = [vp, C.POINTER(LongformStitchArgs)]
     lib.qasr_debug_prof.argtypes = [vp]
     lib.qasr_debug_timeline.argtypes = [vp, sz]
     lib.qasr_sep_layer.argtypes = [vp, C.POINTER(SepLayerArgs), C.c_char_p, sz]
@@ -699,6 +702,153 @@ def resample(x, lens, plan, channels=1, out=None, out_lens=None, stream=None):
     with torch.cuda.device(dev):
         _check(lib.qasr_resample(_stream_ptr(stream), C.byref(a)), 'qasr_resample')
     return out, out_lens
+
+
+class LongformCutArgs(C.Structure):
+    """qasr_longform_cut_args (include/qasr.h)"""
+    _fields_ = ([('struct_size', C.c_uint32)] + [(n, C.c_int32) for n in ('R', 'Wn', 'Wl')] +
+                [('audio', C.c_void_p), ('pitch', C.c_int64)] +
+                [(n, C.c_void_p) for n in ('lens', 'table', 'windows', 'window_lens')])
+
+
+class LongformPlane(C.Structure):
+    """qasr_longform_plane (include/qasr.h)"""
+    _fields_ = [('src', C.c_void_p), ('dst', C.c_void_p), ('bytes_per_frame', C.c_int64), ('fill', C.c_uint32),
+                ('reserved', C.c_uint32)]
+
+
+class LongformStitchArgs(C.Structure):
+    """qasr_longform_stitch_args (include/qasr.h)"""
+    _fields_ = ([('struct_size', C.c_uint32)] +
+                [(n, C.c_int32) for n in ('R', 'Wn', 'Tw', 'Tmax', 'guard', 'hop_frames', 'blank', 'seam_mode', 'n_planes')] +
+                [(n, C.c_void_p) for n in ('table', 'enc_lens', 'tokens', 'frame_score', 'total_frames', 'seams')] +
+                [('planes', LongformPlane * 6)])
+
+
+SEAM_MODES = {'blank': 0, 'middle': 1}
+
+
+def longform_table(plan, device):
+    """The window table of a qasr.longform.WindowPlan on `device` (int32 [Wn, 4]), uploaded once per (plan, device) and kept
+    on the plan.  The upload is a host-to-device copy: the first longform_cut / longform_stitch of a plan must run outside
+    a stream capture (or call this first); later calls only launch."""
+    dev = torch.device(device)
+    if dev.type == 'cuda' and dev.index is None:
+        dev = torch.device('cuda', torch.cuda.current_device())
+    tabs = plan.__dict__.setdefault('_device_tables', {})
+    if dev not in tabs:
+        tabs[dev] = torch.from_numpy(plan.table.copy()).to(dev)
+    return tabs[dev]
+
+
+def longform_cut(audio, lens, plan, out=None, stream=None):
+    """qasr_longform_cut: float32 audio [R, S] (rows of any pitch) with `lens` samples per recording -> (windows float32
+    [Wn, Wl], zeros behind each window's length; window_lens int32 [Wn]) under a qasr.longform.WindowPlan: k_cut, one launch
+    on the current stream, nothing read back; equal to qasr.longform.cut_host byte for byte.  `out`: a caller-owned
+    (windows, window_lens) pair.  A CPU tensor, or a build without the library, runs the NumPy twin."""
+    from . import longform as lf
+    if audio.dim() != 2 or audio.dtype != torch.float32 or audio.shape[0] != plan.R:
+        raise ValueError(f'longform_cut: audio must be a float32 tensor [{plan.R}, S], got {audio.dtype} {tuple(audio.shape)}')
+    if not audio.is_cuda or not os.path.exists(LIB_PATH):
+        w, wl = lf.cut_host(audio.cpu().numpy(), lens.cpu().numpy(), plan)
+        w, wl = torch.from_numpy(w).to(audio.device), torch.from_numpy(wl).to(audio.device)
+        if out is not None:
+            out[0].copy_(w)
+            out[1].copy_(wl)
+            return out
+        return w, wl
+    lib = load_library()
+    dev = audio.device
+    x = audio if audio.stride(1) == 1 else audio.contiguous()
+    ln = lens.to(device=dev, dtype=torch.int32).contiguous()
+    tab = longform_table(plan, dev)
+    if out is None:
+        out = (torch.empty(plan.Wn, plan.Wl, device=dev, dtype=torch.float32), torch.empty(plan.Wn, device=dev, dtype=torch.int32))
+    win, wl = out
+    assert win.is_cuda and win.dtype == torch.float32 and win.is_contiguous() and tuple(win.shape) == (plan.Wn, plan.Wl), 'longform_cut: out'
+    assert wl.is_cuda and wl.dtype == torch.int32 and wl.is_contiguous() and wl.numel() == plan.Wn, 'longform_cut: out'
+    a = LongformCutArgs()
+    a.struct_size = C.sizeof(LongformCutArgs)
+    a.R, a.Wn, a.Wl = plan.R, plan.Wn, plan.Wl
+    a.audio, a.pitch = x.data_ptr(), (x.stride(0) if plan.R > 1 else x.shape[1])
+    a.lens, a.table, a.windows, a.window_lens = ln.data_ptr(), tab.data_ptr(), win.data_ptr(), wl.data_ptr()
+    with torch.cuda.device(dev):
+        _check(lib.qasr_longform_cut(_stream_ptr(stream), C.byref(a)), 'qasr_longform_cut')
+    win._keep = (x, ln, tab)
+    return win, wl
+
+
+def longform_stitch(plan, enc_lens, tokens, frame_score=None, planes=(), blank=None, seam='blank', out=None, stream=None):
+    """qasr_longform_stitch: the per-frame outputs of a plan's windows - tokens int32 [Wn, Tw], frame_score float32 [Wn, Tw]
+    or None, planes: cuda tensors [Wn, Tw, ...] of a multiple of 4 bytes per frame - joined per recording at the seams of
+    qasr.longform.SEAM_RULES: k_stitch, one launch on the current stream, nothing read back; equal to
+    qasr.longform.stitch_host byte for byte.  Returns (out_planes, total_frames int32 [R], seams int32 [Wn]) with out_planes
+    = [tokens, frame_score (if given), *planes] stitched, each [R, plan.Tmax, ...].  `out`: the same triple, caller-owned.
+    CPU tensors, or a build without the library, run the NumPy twin."""
+    from . import longform as lf
+    if blank is None:
+        raise ValueError('longform_stitch: blank is required (the decoder\'s last class)')
+    if seam not in SEAM_MODES:
+        raise ValueError(f"longform_stitch: seam must be 'blank' or 'middle', got {seam!r}")
+    if not tokens.is_cuda or not os.path.exists(LIB_PATH):
+        o, tot, sm = lf.stitch_host(plan, enc_lens.cpu().numpy(), tokens.cpu().numpy(),
+                                    None if frame_score is None else frame_score.cpu().numpy(),
+                                    [p.cpu().numpy() for p in planes], blank, seam)
+        res = ([torch.from_numpy(x).to(tokens.device) for x in o], torch.from_numpy(tot).to(tokens.device),
+               torch.from_numpy(sm).to(tokens.device))
+        if out is not None:
+            for d, s_ in zip(out[0], res[0]):
+                d.copy_(s_)
+            out[1].copy_(res[1])
+            out[2].copy_(res[2])
+            return out
+        return res
+    lib = load_library()
+    dev = tokens.device
+    tok = tokens.to(torch.int32).contiguous()
+    if tok.dim() != 2 or tok.shape[0] != plan.Wn:
+        raise ValueError(f'longform_stitch: tokens must be [{plan.Wn}, Tw], got {tuple(tok.shape)}')
+    Tw = tok.shape[1]
+    fs = None if frame_score is None else frame_score.to(device=dev, dtype=torch.float32).contiguous()
+    if fs is not None and fs.shape != tok.shape:
+        raise ValueError('longform_stitch: frame_score must have the shape of tokens')
+    src = [tok] + ([fs] if fs is not None else []) + [p.contiguous() for p in planes]
+    if len(src) > lf.MAX_PLANES:
+        raise ValueError(f'longform_stitch: at most {lf.MAX_PLANES} planes, tokens and frame_score included, got {len(src)}')
+    bpf = []
+    for i, p in enumerate(src):
+        nbytes = p.element_size() * int(np.prod(p.shape[2:], dtype=np.int64)) if p.dim() >= 2 else 0
+        if not p.is_cuda or p.dim() < 2 or tuple(p.shape[:2]) != (plan.Wn, Tw) or nbytes < 4 or nbytes % 4:
+            raise ValueError(f'longform_stitch: plane {i} must be a cuda tensor [{plan.Wn}, {Tw}, bytes_per_frame, a multiple of 4], '
+                             f'got {tuple(p.shape)} {p.dtype}')
+        bpf.append(nbytes)
+    ln = enc_lens.to(device=dev, dtype=torch.int32).contiguous()
+    if ln.numel() != plan.Wn:
+        raise ValueError(f'longform_stitch: {plan.Wn} windows but {ln.numel()} encoded lengths')
+    tab = longform_table(plan, dev)
+    if out is None:
+        out = ([torch.empty((plan.R, plan.Tmax) + tuple(p.shape[2:]), device=dev, dtype=p.dtype) for p in src],
+               torch.empty(plan.R, device=dev, dtype=torch.int32), torch.empty(plan.Wn, device=dev, dtype=torch.int32))
+    dst, total, seams = out
+    assert len(dst) == len(src), 'longform_stitch: out'
+    for d, p in zip(dst, src):
+        assert d.is_cuda and d.is_contiguous() and d.dtype == p.dtype and tuple(d.shape) == (plan.R, plan.Tmax) + tuple(p.shape[2:]), \
+            'longform_stitch: out'
+    for t, n in ((total, plan.R), (seams, plan.Wn)):
+        assert t.is_cuda and t.dtype == torch.int32 and t.is_contiguous() and t.numel() == n, 'longform_stitch: out'
+    a = LongformStitchArgs()
+    a.struct_size = C.sizeof(LongformStitchArgs)
+    a.R, a.Wn, a.Tw, a.Tmax, a.guard, a.hop_frames = plan.R, plan.Wn, Tw, plan.Tmax, plan.guard, plan.hop_frames
+    a.blank, a.seam_mode, a.n_planes = int(blank), SEAM_MODES[seam], len(src)
+    a.table, a.enc_lens, a.tokens, a.frame_score = tab.data_ptr(), ln.data_ptr(), tok.data_ptr(), 0 if fs is None else fs.data_ptr()
+    a.total_frames, a.seams = total.data_ptr(), seams.data_ptr()
+    for i, (p, d) in enumerate(zip(src, dst)):
+        a.planes[i].src, a.planes[i].dst, a.planes[i].bytes_per_frame = p.data_ptr(), d.data_ptr(), bpf[i]
+        a.planes[i].fill = (int(blank) & 0xffffffff) if i == 0 else 0
+    with torch.cuda.device(dev):
+        _check(lib.qasr_longform_stitch(_stream_ptr(stream), C.byref(a)), 'qasr_longform_stitch')
+    total._keep = (src, ln, tab)
+    return dst, total, seams
 
 
 class Engine:
