@@ -488,6 +488,52 @@ typedef struct qasr_ctc_align_args {
 size_t qasr_ctc_align_workspace_bytes(int P, int T, int max_labels);   /* 0 for a shape qasr_ctc_align refuses */
 int qasr_ctc_align(void* stream, const qasr_ctc_align_args* args);
 
+/* ---- banded CTC alignment: one long recording against its whole transcript --------------------------------------------
+ * k_align above computes every state of every frame and holds 2048 labels and 65 536 frames.  An hour of audio is 180 000
+ * frames and some 54 000 characters; k_align_band keeps only a band of band_states = 256, 1024 or 4352 lattice states that
+ * follows the alignment (every 32 frames it is re-centred on the lowest state that holds the row's maximum, and never moves
+ * back), so the cost is T * band_states cells.  Viterbi only; the fixed point, the predecessors and the tie order are
+ * k_align's, the rest is BAND_RULES of qasr/align.py, which the kernel follows bit for bit.  One problem per recording:
+ * problem p < B aligns targets[p][0 .. target_lens[p]) against log_probs[p]; max_labels is the row pitch of targets and of the
+ * per-label outputs.  While 2 * target_lens[p] + 1 <= band_states the band never moves and every output equals qasr_ctc_align's.
+ *   start, nframes i32 [B][max_labels], score f32 [B][max_labels], path_score i64 [B], ok i32 [B]: as in qasr_ctc_align;
+ *   frame_logp f32 [B][T]: the log-probability of the path's label at each frame < lens, 0 behind;
+ *   band_base i32 [B][ceil(T / 32)]: the lowest state of the band during each 32-frame block (0 behind lens).
+ *   Every output but ok is optional.
+ * Not alignable - ok 0, the rows and frame_logp 0, path_score -2^62: the reasons of qasr_ctc_align (target_lens above
+ * QASR_BAND_MAX_LABELS in place of QASR_ALIGN_MAX_LABELS), or the band lost the path (band_base is kept then).  Targets are device
+ * data: the kernel checks them itself and reads nothing through a bad label.
+ * workspace: qasr_ctc_align_band_workspace_bytes(B, T, band_states) bytes, 4-byte aligned, that the call may overwrite:
+ * per problem ceil(T / 4) * band_states bytes of backpointers and 4 T bytes of path states (an hour at 4352: 197 MB).  Nothing is
+ * allocated and no length is read on the host, so the call can be captured.
+ * QASR_ERR_ARG with nothing launched and no output written: an unknown struct_size, a NULL among log_probs, targets,
+ * target_lens, workspace, ok; B, T or C < 1, T > QASR_BAND_MAX_FRAMES, max_labels outside 1 .. QASR_BAND_MAX_LABELS, band_states
+ * not 256, 1024 or 4352, blank outside [0, C), pitch_frame < C, pitch_utt < T * pitch_frame, a workspace that is not 4-byte
+ * aligned or smaller than the query says. */
+#define QASR_BAND_MAX_LABELS (1 << 20)
+#define QASR_BAND_MAX_FRAMES (1 << 22)
+typedef struct qasr_ctc_align_band_args {
+  uint32_t struct_size;
+  int32_t B, T, C, blank, max_labels, band_states;
+  uint32_t reserved;
+  int64_t pitch_utt, pitch_frame;   /* in floats */
+  const float* log_probs;
+  const int32_t* lens;         /* optional [B] */
+  const int32_t* targets;      /* [B][max_labels] */
+  const int32_t* target_lens;  /* [B] */
+  void* workspace;
+  size_t workspace_bytes;
+  int32_t* start;              /* optional */
+  int32_t* nframes;            /* optional */
+  float* score;                /* optional */
+  int64_t* path_score;         /* optional */
+  float* frame_logp;           /* optional */
+  int32_t* band_base;          /* optional */
+  int32_t* ok;
+} qasr_ctc_align_band_args;
+size_t qasr_ctc_align_band_workspace_bytes(int B, int T, int band_states);   /* 0 for a shape qasr_ctc_align_band refuses */
+int qasr_ctc_align_band(void* stream, const qasr_ctc_align_band_args* args);
+
 /* ---- audio at any sample rate: rational polyphase resampler and PCM ingest -----------------------------------------------
  * What AudioSegment.__init__ does on the host with librosa.core.resample when target_sr != sample_rate (parts/segment.py:
  * 57-59), as one kernel, k_resample, in front of the mel front-end: int16 PCM (mono or interleaved channels) or float32 at an

@@ -1290,6 +1290,41 @@ int qasr_ctc_align(void* stream, const qasr_ctc_align_args* a) {
   return QASR_OK;
 }
 
+// ---- banded CTC alignment (k_align_band, qasr_align_band.hip): the checks of include/qasr.h, then one launch
+static int band_shape_ok(int B, int T, int band_states) {
+  return B >= 1 && T >= 1 && T <= QASR_BAND_MAX_FRAMES && (band_states == 256 || band_states == 1024 || band_states == 4352);
+}
+
+size_t qasr_ctc_align_band_workspace_bytes(int B, int T, int band_states) {
+  return band_shape_ok(B, T, band_states) ? align_band_workspace_bytes(B, T, band_states) : 0;
+}
+
+int qasr_ctc_align_band(void* stream, const qasr_ctc_align_band_args* a) {
+  if (!a) return fail(QASR_ERR_ARG, "ctc_align_band: args is NULL");
+  if (a->struct_size != sizeof(qasr_ctc_align_band_args))
+    return fail(QASR_ERR_ARG, "ctc_align_band: struct_size %u is not %zu", a->struct_size, sizeof(qasr_ctc_align_band_args));
+  if (!a->log_probs || !a->targets || !a->target_lens || !a->workspace || !a->ok)
+    return fail(QASR_ERR_ARG, "ctc_align_band: log_probs, targets, target_lens, workspace and ok are required");
+  if (a->band_states != 256 && a->band_states != 1024 && a->band_states != 4352)
+    return fail(QASR_ERR_ARG, "ctc_align_band: band_states %d is not 256, 1024 or 4352", a->band_states);
+  if (a->B < 1 || a->T < 1 || a->T > QASR_BAND_MAX_FRAMES || a->C < 1)
+    return fail(QASR_ERR_ARG, "ctc_align_band: B %d, T %d (1 .. %d) or C %d out of range", a->B, a->T, QASR_BAND_MAX_FRAMES, a->C);
+  if (a->max_labels < 1 || a->max_labels > QASR_BAND_MAX_LABELS)
+    return fail(QASR_ERR_ARG, "ctc_align_band: max_labels %d is outside 1 .. %d", a->max_labels, QASR_BAND_MAX_LABELS);
+  if (a->blank < 0 || a->blank >= a->C) return fail(QASR_ERR_ARG, "ctc_align_band: blank %d is outside [0, %d)", a->blank, a->C);
+  if (a->pitch_frame < a->C || a->pitch_utt < (int64_t)a->T * a->pitch_frame)
+    return fail(QASR_ERR_ARG, "ctc_align_band: pitch_frame %lld < C or pitch_utt %lld < T * pitch_frame", (long long)a->pitch_frame,
+                (long long)a->pitch_utt);
+  if (((uintptr_t)a->workspace & 3) != 0) return fail(QASR_ERR_ARG, "ctc_align_band: workspace is not 4-byte aligned");
+  const size_t need = align_band_workspace_bytes(a->B, a->T, a->band_states);
+  if (a->workspace_bytes < need)
+    return fail(QASR_ERR_ARG, "ctc_align_band: workspace of %zu bytes, %zu needed", a->workspace_bytes, need);
+  int rc = launch_align_band((hipStream_t)stream, *a);
+  if (rc) return fail(rc, "ctc_align_band: launch");
+  HIPCHK(hipGetLastError());
+  return QASR_OK;
+}
+
 // ---- polyphase resampler (k_resample, qasr_resample.hip): host-only validation of a packed table (qasr/resample.py states
 // the layout), then the checks of include/qasr.h and one launch
 static long long gcd_ll(long long a, long long b) {

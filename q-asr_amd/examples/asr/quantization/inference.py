@@ -77,7 +77,9 @@ def main():
                    help="(extension) forced alignment of every manifest line's reference text against its batch's "
                         "log-probabilities (EncDecCTCModel.align): OUT gets one JSON line per utterance - audio_filepath, text, "
                         "ctc_score (log-likelihood of the text), utt_score (its best alignment) and words [word, start_s, end_s, "
-                        "score]; hypotheses, WER and the other outputs are unchanged")
+                        "score]; hypotheses, WER and the other outputs are unchanged.  With --window_s the texts are aligned "
+                        "against the stitched windows of the whole recording (EncDecCTCModel.align_long, a banded lattice: any "
+                        "length of text; ctc_score is then null)")
     p.add_argument("--input_rate", type=int, default=None, metavar='HZ',
                    help="(extension) every file of the manifest is 16-bit mono PCM at this rate (a telephone corpus at 8000, say): "
                         "the batches stay int16 and are resampled to the model's rate on the device (k_resample) in front of the "
@@ -221,7 +223,16 @@ def main():
                 utt_scores.append(h.utt_score)
         if args.align:                                       # the reference texts' own labels, one k_align launch per batch
             ref_ids = [row[:int(n)].tolist() for row, n in zip(batch[2].cpu(), batch[3].cpu())]
-            for h in asr_model.align(input_signal=signal, input_signal_length=batch[1], labels=ref_ids, **rate_kw):
+            if args.window_s is not None:                    # long recordings: windows, k_stitch, one k_align_band launch
+                overlap_s = 4.0 if args.overlap_s is None else args.overlap_s
+                try:
+                    got = asr_model.align_long(signal, batch[1], labels=ref_ids, window_s=args.window_s, overlap_s=overlap_s,
+                                               guard_s=min(1.0, overlap_s / 4), batch_size=args.batch_size, **rate_kw)
+                except ValueError as e:
+                    p.error(f'--align with --window_s / --overlap_s: {e}')
+            else:
+                got = asr_model.align(input_signal=signal, input_signal_length=batch[1], labels=ref_ids, **rate_kw)
+            for h in got:
                 k = len(aligned)
                 aligned.append(dict(audio_filepath=items[k][0] if not args.shuffle and k < len(items) else None, text=h.text,
                                     ctc_score=h.ctc_score, utt_score=h.utt_score, words=[list(w) for w in h.words]))

@@ -545,6 +545,52 @@ class EncDecCTCModel(nn.Module):
 
         return qlong.WindowPlan(lens_samples, window_s, overlap_s, guard_s, rate, spf, frames_of)
 
+    def _long_windows(self, plan, windows, wlens, len_dtype, batch_size, want, cutoff_top_n=None):
+        """The windows of a plan through the model in batches of batch_size (decode_long, align_long): tokens int32
+        [Wn, Tw], frame scores float32 [Wn, Tw], encoded lengths int32 [Wn] and the extra planes of `want` - 'frames': none
+        (on the static engine no log-probability tensor is written); 'topn': the cutoff_top_n candidates per frame (ids,
+        q), the log-probabilities living for one batch; 'logp': the log-probabilities themselves, float32 [Wn, Tw, C].  On
+        the calibrated model without a reservation, (batch_size, window) is reserved for the duration of the call."""
+        from qasr import beam as qbeam, engine as qengine
+        cuda = windows.is_cuda
+        own = cuda and self._reserve is None and self.engine_ready()
+        if own:                              # for this call: every full batch replays one graph
+            self._reserve = (batch_size, max(plan.Wl, windows.shape[1]) / float(plan.sample_rate))
+            self._reserve_logp = want != 'frames'
+        toks = fs = enc = None
+        extra = []
+        try:
+            for i in range(0, plan.Wn, batch_size):
+                sig, ln = windows[i:i + batch_size], wlens[i:i + batch_size].to(len_dtype)
+                if want == 'frames':
+                    t, f, e = self._forward(sig, ln, decode='frames')
+                    c = ()
+                else:                        # the log-probabilities live for one batch: only the candidates are kept
+                    logp, e, t = self._forward(sig, ln)
+                    f = self._frame_scores(logp, t)
+                    if want == 'logp':
+                        c = (logp.float(),)
+                    elif cuda:
+                        c = qengine.ctc_topn(logp.float(), e, cutoff_top_n)
+                    else:
+                        c = [torch.from_numpy(x) for x in qbeam.topn_host(logp.float().numpy(), cutoff_top_n, e.numpy())]
+                if toks is None:
+                    Tw, dev = t.shape[1], t.device
+                    toks = torch.empty(plan.Wn, Tw, device=dev, dtype=torch.int32)
+                    fs = torch.empty(plan.Wn, Tw, device=dev, dtype=torch.float32)
+                    enc = torch.empty(plan.Wn, device=dev, dtype=torch.int32)
+                    extra = [torch.empty((plan.Wn, Tw) + tuple(x.shape[2:]), device=dev, dtype=x.dtype) for x in c]
+                b = t.shape[0]
+                toks[i:i + b].copy_(t)
+                fs[i:i + b].copy_(f)
+                enc[i:i + b].copy_(e)
+                for dst, x in zip(extra, c):
+                    dst[i:i + b].copy_(x)
+        finally:
+            if own:
+                self._reserve, self._reserve_logp = None, True
+        return toks, fs, enc, tuple(extra)
+
     @torch.no_grad()
     def decode_long(self, input_signal, input_signal_length, window_s=30.0, overlap_s=4.0, guard_s=1.0, batch_size=32,
                     seam='blank', beam_width=None, n_best=1, cutoff_top_n=40, lm=None, alpha=0.0, beta=0.0, boost=None,
@@ -602,42 +648,8 @@ class EncDecCTCModel(nn.Module):
             windows, wlens = signal, lens_host.to(signal.device)      # front-end's reflect padding folds at the batch's width)
         else:
             windows, wlens = qengine.longform_cut(signal, lens_host.to(signal.device), plan)
-        own = cuda and self._reserve is None and self.engine_ready()
-        if own:                              # for this call: every full batch replays one graph
-            self._reserve = (batch_size, max(plan.Wl, windows.shape[1]) / float(plan.sample_rate))
-            self._reserve_logp = beam_width is not None
-        toks = fs = enc = cid = cq = None
-        try:
-            for i in range(0, plan.Wn, batch_size):
-                sig, ln = windows[i:i + batch_size], wlens[i:i + batch_size].to(length.dtype)
-                if beam_width is None:
-                    t, f, e = self._forward(sig, ln, decode='frames')
-                else:                        # the log-probabilities live for one batch: only the candidates are kept
-                    logp, e, t = self._forward(sig, ln)
-                    f = self._frame_scores(logp, t)
-                    if cuda:
-                        c = qengine.ctc_topn(logp.float(), e, cutoff_top_n)
-                    else:
-                        c = [torch.from_numpy(x) for x in qbeam.topn_host(logp.float().numpy(), cutoff_top_n, e.numpy())]
-                if toks is None:
-                    Tw, dev = t.shape[1], t.device
-                    toks = torch.empty(plan.Wn, Tw, device=dev, dtype=torch.int32)
-                    fs = torch.empty(plan.Wn, Tw, device=dev, dtype=torch.float32)
-                    enc = torch.empty(plan.Wn, device=dev, dtype=torch.int32)
-                    if beam_width is not None:
-                        cid = torch.empty(plan.Wn, Tw, c[0].shape[2], device=dev, dtype=torch.int32)
-                        cq = torch.empty_like(cid)
-                b = t.shape[0]
-                toks[i:i + b].copy_(t)
-                fs[i:i + b].copy_(f)
-                enc[i:i + b].copy_(e)
-                if beam_width is not None:
-                    cid[i:i + b].copy_(c[0])
-                    cq[i:i + b].copy_(c[1])
-        finally:
-            if own:
-                self._reserve, self._reserve_logp = None, True
-        planes = () if beam_width is None else (cid, cq)
+        toks, fs, enc, planes = self._long_windows(plan, windows, wlens, length.dtype, batch_size,
+                                                   'frames' if beam_width is None else 'topn', cutoff_top_n)
         out, total, seams = qengine.longform_stitch(plan, enc, toks, fs, planes, blank, seam)
         spf_s = self.seconds_per_frame()
         seams_h = seams.cpu().numpy()
@@ -789,6 +801,139 @@ class EncDecCTCModel(nn.Module):
         else:
             res = qalign.align_host(log_probs.float().numpy(), enc_len.numpy(), tg, tl, blank)
         return qalign.to_hypotheses(res, vocab, self.seconds_per_frame())
+
+    def _long_transcripts(self, texts, labels, n_recordings):
+        """align_long's transcripts: per recording its label ids and, where an utterance list was given, the utterances as
+        (text, first label, labels); utterances are joined by the space label when the vocabulary has one"""
+        if (texts is None) == (labels is None):
+            raise ValueError('align_long: give exactly one of texts and labels')
+        vocab = list(self.decoder.vocabulary)
+        blank = len(vocab)
+        space = vocab.index(' ') if ' ' in vocab else None
+        given = texts if texts is not None else labels
+        if len(given) != n_recordings:
+            raise ValueError(f'align_long: {len(given)} transcripts for {n_recordings} recordings')
+        if texts is not None:
+            from nemo.collections.asr.parts import parsers
+            parser = parsers.make_parser(labels=vocab, name='en', unk_id=-1, blank_id=-1, do_normalize=True)
+
+            def ids_of(x, where):
+                ids = parser(x) if isinstance(x, str) else None
+                if ids is None:
+                    raise ValueError(f'align_long: {where} is rejected by the parser')
+                return [int(c) for c in ids], x
+        else:
+            def ids_of(x, where):
+                ids = [int(c) for c in x]
+                if any(not 0 <= c < blank for c in ids):
+                    raise ValueError(f'align_long: {where} holds a label outside the vocabulary of {blank} labels')
+                return ids, ''.join(vocab[c] for c in ids)
+        rows, utts = [], []
+        for r, item in enumerate(given):
+            is_list = (not isinstance(item, str)) if texts is not None else (len(item) > 0 and np.ndim(item[0]) > 0)
+            if not is_list:
+                ids, _ = ids_of(item, f'transcript {r}')
+                rows.append(ids)
+                utts.append(None)
+                continue
+            ids, us = [], []
+            for j, u in enumerate(item):
+                uid, text = ids_of(u, f'utterance {j} of transcript {r}')
+                if not uid:
+                    raise ValueError(f'align_long: utterance {j} of transcript {r} is empty')
+                if ids and space is not None:
+                    ids.append(space)
+                us.append((text, len(ids), len(uid)))
+                ids += uid
+            rows.append(ids)
+            utts.append(us)
+        from qasr import align as qalign
+        for r, ids in enumerate(rows):
+            if any(not 0 <= c < blank for c in ids):
+                raise ValueError(f'align_long: transcript {r} holds a label outside the vocabulary of {blank} labels')
+            if len(ids) > qalign.BAND_MAX_LABELS:
+                raise ValueError(f'align_long: transcript {r} has {len(ids)} labels, at most {qalign.BAND_MAX_LABELS} can be aligned')
+        return rows, utts
+
+    @torch.no_grad()
+    def align_long(self, input_signal, input_signal_length, texts=None, labels=None, window_s=30.0, overlap_s=4.0, guard_s=1.0,
+                   batch_size=32, seam='blank', band_states=None, sample_rate=None, channels=1):
+        """CTC segmentation of long recordings (an extension; the job of the reference's tools/ctc_segmentation, on the
+        device): input_signal [R, S] with input_signal_length samples each and, per recording, its whole transcript ->
+        List[qasr.ctc.Hypothesis], one per recording, with every label's and word's times in seconds of the recording,
+        utt_score = the log-probability of the alignment, ctc_score = None (no forward pass in the band) and seams_s as
+        decode_long's.  Exactly one of `texts` and `labels`; texts[r] is a string, or a list of utterance strings (labels[r]:
+        a sequence of ids, or a list of such): utterances are joined by the space label when the vocabulary has one, by
+        nothing otherwise, an empty utterance is refused by name, and the hypothesis then carries `segments`, one
+        qasr.ctc.Segment(text, start_s, end_s, score) per utterance - from the first frame of its first label to the end of its
+        last label's run, score = the min-mean confidence of qasr.align.segment_scores over those frames.
+
+        The windows run as in decode_long (k_cut, batches of batch_size through the reserved engine, which writes
+        log-probabilities here), the log-probability rows go through k_stitch as one more plane, and one launch of
+        k_align_band aligns every recording against its transcript inside a band of band_states lattice states (256, 1024
+        or 4352; None: the smallest that holds the longest transcript whole, else 4352) that follows the alignment
+        (qasr.align.BAND_RULES).  A transcript whose path the band loses - or that has more labels than the recording has
+        frames - keeps its text; its times are empty and its scores -inf.  CPU inputs run the NumPy twins.  The stitched
+        log-probabilities take 4 * classes bytes per frame of every recording, and the windows as much again."""
+        from qasr import align as qalign, engine as qengine
+        if input_signal is None or input_signal_length is None:
+            raise ValueError('align_long: input_signal and input_signal_length are required')
+        if seam not in ('blank', 'middle'):
+            raise ValueError(f"align_long: seam must be 'blank' or 'middle', got {seam!r}")
+        batch_size = int(batch_size)
+        if batch_size < 1:
+            raise ValueError(f'align_long: batch_size must be at least 1, got {batch_size}')
+        if band_states is not None:
+            try:
+                band_states = qalign.pick_band_states(0, band_states)
+            except ValueError as e:
+                raise ValueError(f'align_long: {e}') from None
+        signal, length = self._resample_in(input_signal, input_signal_length, sample_rate, channels)
+        if signal.dim() != 2:
+            raise ValueError(f'align_long: input_signal must be [R, S], got {tuple(signal.shape)}')
+        rows, utts = self._long_transcripts(texts, labels, signal.shape[0])
+        signal = signal.float()
+        lens_host = length.detach().cpu().long().clamp(max=signal.shape[1])
+        plan = self._long_plan(lens_host.numpy(), window_s, overlap_s, guard_s)      # refuses its arguments by name
+        vocab = list(self.decoder.vocabulary)
+        blank = len(vocab)
+        if plan.Wn == plan.R:                # no recording is longer than a window: nothing is cut
+            windows, wlens = signal, lens_host.to(signal.device)
+        else:
+            windows, wlens = qengine.longform_cut(signal, lens_host.to(signal.device), plan)
+        toks, fs, enc, planes = self._long_windows(plan, windows, wlens, length.dtype, batch_size, 'logp')
+        out, total, seams = qengine.longform_stitch(plan, enc, toks, fs, planes, blank, seam)
+        logp = out[2]
+        tg = np.full((len(rows), max(1, max(len(r) for r in rows))), blank, dtype=np.int32)
+        for i, ids in enumerate(rows):
+            tg[i, :len(ids)] = ids
+        tl = np.array([len(r) for r in rows], dtype=np.int32)
+        bw = qalign.pick_band_states(tg.shape[1], band_states)
+        if logp.is_cuda:
+            res = qengine.ctc_align_band(logp, total, torch.from_numpy(tg).to(logp.device), torch.from_numpy(tl).to(logp.device),
+                                         blank, band_states=bw, want_band_base=False)
+        else:
+            res = qalign.align_band_host(logp.numpy(), total.numpy(), tg, tl, blank, band_states=bw, want_band_base=False)
+        spf_s = self.seconds_per_frame()
+        hyps = qalign.to_hypotheses(res, vocab, spf_s)
+        seams_h = seams.cpu().numpy()
+        if any(u is not None for u in utts):
+            ok, start, nframes = (qalign._np(x) for x in (res.ok, res.start, res.nframes))
+            frame_logp = qalign._np(res.frame_logp)
+        for r, h in enumerate(hyps):
+            w0, n = int(plan.first[r]), int(plan.count[r])
+            h.seams_s = [float(seams_h[w]) * spf_s for w in range(w0 + 1, w0 + n)] if n > 1 else None
+            if utts[r] is None:
+                continue
+            from qasr.ctc import Segment
+            if not ok[r]:
+                h.segments = [Segment(text, None, None, float('-inf')) for text, _, _ in utts[r]]
+                continue
+            f0 = np.array([start[r, a] for _, a, _ in utts[r]], dtype=np.int64)
+            f1 = np.array([start[r, a + k - 1] + nframes[r, a + k - 1] for _, a, k in utts[r]], dtype=np.int64)
+            sc = qalign.segment_scores(frame_logp[r], f0, f1)
+            h.segments = [Segment(text, float(a) * spf_s, float(b) * spf_s, float(c)) for (text, _, _), a, b, c in zip(utts[r], f0, f1, sc)]
+        return hyps
 
     @staticmethod
     def _frame_scores(log_probs, tokens):

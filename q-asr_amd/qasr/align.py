@@ -19,7 +19,11 @@ first frame whose state is 2i + 1 and nframes[i] the number of such frames (one 
 maximum of the float32 logp[u][t][y[i]] over those frames in the `_order_key` order (exact; k_ctc's rule).
 Not alignable (ok[p] = 0; start, nframes and score rows zero; path_score = total = NEG): V[final] == NEG (fewer frames than
 labels plus adjacent repeats); lim == 0 with L > 0; L < 0, L above the row pitch or above MAX_LABELS; a label outside [0, C)
-or equal to blank.  lim == 0 with L == 0 is ok = 1 with both scores 0."""
+or equal to blank.  lim == 0 with L == 0 is ok = 1 with both scores 0.
+
+Long recordings (a whole transcript against a whole recording, past MAX_LABELS and MAX_T) are aligned inside a band of lattice
+states that follows the path: BAND_RULES, `align_band_host` (the host statement of k_align_band, csrc/qasr_align_band.hip) and
+`segment_scores` at the end of this module; they are the CPU path of EncDecCTCModel.align_long."""
 from dataclasses import dataclass
 from typing import List, Sequence
 
@@ -46,6 +50,23 @@ class AlignResult:
     ok: object = None
     blank: int = -1
     problems_per_utt: int = 1
+
+
+def _label_runs(states, lp, y):
+    """per label of y its first frame, frame count and best frame log-probability along the path `states` [lim]"""
+    L = len(y)
+    start = np.zeros(L, dtype=np.int32)
+    nframes = np.zeros(L, dtype=np.int32)
+    score = np.zeros(L, dtype=np.float32)
+    fr = np.flatnonzero(states & 1)                                 # the label frames, in time (= label) order
+    if L:
+        idx = states[fr] >> 1
+        first_of = np.flatnonzero(np.concatenate([[True], idx[1:] != idx[:-1]]))
+        start[idx[first_of]] = fr[first_of]
+        nframes[idx[first_of]] = np.diff(np.concatenate([first_of, [len(fr)]]))
+        best = np.maximum.reduceat(_order_key(lp[fr, np.asarray(y, dtype=np.int64)[idx]]), first_of)
+        score[idx[first_of]] = (best ^ ((best >> 31) & np.int32(0x7fffffff))).view(np.float32)
+    return start, nframes, score
 
 
 def _align_one(lp, lim, y, blank, tab, want_total):
@@ -99,17 +120,7 @@ def _align_one(lp, lim, y, blank, tab, want_total):
     for t in range(lim - 1, -1, -1):
         states[t] = s
         s -= int(bp[t, s])
-    start = np.zeros(L, dtype=np.int32)
-    nframes = np.zeros(L, dtype=np.int32)
-    score = np.zeros(L, dtype=np.float32)
-    fr = np.flatnonzero(states & 1)                                 # the label frames, in time (= label) order
-    if L:
-        idx = states[fr] >> 1
-        first_of = np.flatnonzero(np.concatenate([[True], idx[1:] != idx[:-1]]))
-        start[idx[first_of]] = fr[first_of]
-        nframes[idx[first_of]] = np.diff(np.concatenate([first_of, [len(fr)]]))
-        best = np.maximum.reduceat(_order_key(lp[fr, np.asarray(y, dtype=np.int64)[idx]]), first_of)
-        score[idx[first_of]] = (best ^ ((best >> 31) & np.int32(0x7fffffff))).view(np.float32)
+    start, nframes, score = _label_runs(states, lp, y)
     return 1, start, nframes, score, path_score, total
 
 
@@ -190,3 +201,173 @@ def to_hypotheses(result: AlignResult, vocabulary: Sequence[str], seconds_per_fr
             text = ''.join(vocab[i] if 0 <= i < len(vocab) else '' for i in ids)
             hyps[p] = qctc.Hypothesis(text, ids, [], [], None, float('-inf'), [], None, float('-inf'))
     return hyps
+
+
+# ---- banded alignment of one long recording against its whole transcript (k_align_band, csrc/qasr_align_band.hip)
+BAND_MAX_LABELS = 1 << 20               # QASR_BAND_MAX_LABELS
+BAND_MAX_FRAMES = 1 << 22               # QASR_BAND_MAX_FRAMES
+BAND_STATES = (256, 1024, 4352)         # k_align's 256 threads x NS = 1, 4, 17
+BAND_BLOCK = 32                         # frames between two looks at where the band should be
+SEGMENT_WINDOW = 30                     # frames of one mean in segment_scores
+
+BAND_RULES = """Everything of RULES (the module docstring) holds - states, predecessors, tie order, q = rint(logp * 2^16), int64 sums, NEG,
+end states, per-label start / nframes / score - with these changes.
+One problem per recording: K = 1, problem p aligns targets[p] against log_probs[p]; L <= BAND_MAX_LABELS, T <= BAND_MAX_FRAMES.
+Viterbi only: no forward pass, no total, no table.
+The band: BW in BAND_STATES; S = 2L + 1, top = max(0, S - BW); the band is the states [base, min(base + BW, S)), base = 0 at
+t = 0.  At every frame t >= 1 with t % 32 == 0, before that frame's update: m = the lowest in-band state whose V (after frame
+t - 1) is the band's maximum; if that maximum is NEG the base stays, otherwise base <- max(base, min(m - BW / 2, top)).  States
+below the new base are dropped; states that enter are NEG.  The base never decreases.
+A predecessor below base is NEG; states outside the band are NEG and have no backpointer; the final state (2L or 2L - 1 as in
+RULES, an out-of-band one counting as NEG) must be in the last frame's band.
+ok = 0 for the reasons of RULES (L above BAND_MAX_LABELS in place of MAX_LABELS), or when V[final] == NEG because the band lost
+the path; start, nframes, score and frame_logp rows are then zero and path_score = NEG.
+When S <= BW the base never moves and start, nframes, score, path_score and ok equal align_host(want_total=False) on every byte.
+frame_logp float32 [P, T]: the float32 log-probability of the path's state's label at each frame < lim, 0 behind and 0 when
+ok = 0.  band_base int32 [P, ceil(T / 32)]: the base in force during each 32-frame block that has a frame < lim, 0 behind; it is
+kept when the path was lost (that is where to look), and is 0 for a problem whose lattice never ran (a bad target, lim == 0)."""
+
+
+@dataclass
+class BandResult(AlignResult):
+    """AlignResult (total None, problems_per_utt 1) plus frame_logp float32 [P, T] and band_base int32 [P, ceil(T / 32)]
+    (None when not requested) of BAND_RULES; band_states is the width used."""
+    frame_logp: object = None
+    band_base: object = None
+    band_states: int = 0
+
+
+def pick_band_states(n_labels, band_states=None) -> int:
+    """band_states as given (refused by name unless one of BAND_STATES); None: the smallest width that holds all
+    2 * n_labels + 1 states, else the widest"""
+    if band_states is None:
+        S = 2 * int(n_labels) + 1
+        return next((b for b in BAND_STATES if S <= b), BAND_STATES[-1])
+    if int(band_states) not in BAND_STATES:
+        raise ValueError(f'band_states must be one of {BAND_STATES}, got {band_states}')
+    return int(band_states)
+
+
+def _align_band_one(lp, lim, y, blank, BW):
+    """one problem with a valid target y over lp float32 [T, C]: (ok, start, nframes, score, path, frame_logp [lim], bases)"""
+    L = len(y)
+    i64 = np.int64
+    nb_blocks = (lim + BAND_BLOCK - 1) // BAND_BLOCK
+    bases = np.zeros(nb_blocks, dtype=np.int32)
+    if lim == 0:
+        return (1, None, None, None, 0, None, bases) if L == 0 else (0, None, None, None, NEG, None, bases)
+    S = 2 * L + 1
+    top = max(0, S - BW)
+    n = min(BW, S)                                                  # states in the band (constant: base <= top)
+    lab = np.full(S, blank, dtype=np.int64)
+    lab[1::2] = y
+    skip = np.zeros(S, dtype=bool)
+    if L > 1:
+        skip[3::2] = y[1:] != y[:-1]
+    negs = np.full(2, NEG, i64)
+    base = 0
+    V = np.full(n, NEG, i64)                                        # V[i]: state base + i
+    V[:min(2, S)] = quantize(lp[0, lab[:min(2, S)]])
+    bp = np.zeros((lim, n), dtype=np.uint8)                         # bp[t, i]: state bases[t // 32] + i
+    for t in range(1, lim):
+        if t % BAND_BLOCK == 0:
+            if V.max() != NEG:
+                m = base + int(np.argmax(V))                        # the first maximum: the lowest state
+                new = max(base, min(m - BW // 2, top))
+                if new > base:
+                    V = np.concatenate([V[new - base:], np.full(new - base, NEG, i64)])
+                    base = new
+            bases[t // BAND_BLOCK] = base
+        sl = slice(base, base + n)
+        q = quantize(lp[t, lab[sl]]).astype(i64)
+        ext = np.concatenate([negs, V])                             # what lies below base is NEG
+        a1, a2 = ext[1:n + 1], np.where(skip[sl], ext[:n], NEG)
+        best, step = V, np.zeros(n, dtype=np.uint8)
+        m1 = a1 > best
+        best, step = np.where(m1, a1, best), np.where(m1, 1, step)
+        m2 = a2 > best
+        best, step = np.where(m2, a2, best), np.where(m2, 2, step)
+        live = best != NEG
+        V = np.where(live, np.where(live, best, 0) + q, NEG)
+        bp[t] = step
+
+    def at(s):
+        return int(V[s - base]) if base <= s < base + n else NEG
+    fin = 0 if L == 0 else (2 * L if at(2 * L) > at(2 * L - 1) else 2 * L - 1)
+    path_score = at(fin)
+    if path_score == NEG:
+        return 0, None, None, None, NEG, None, bases
+    states = np.empty(lim, dtype=np.int64)
+    s = fin
+    for t in range(lim - 1, -1, -1):
+        states[t] = s
+        s -= int(bp[t, s - int(bases[t // BAND_BLOCK])])
+    start, nframes, score = _label_runs(states, lp, y)
+    return 1, start, nframes, score, path_score, lp[np.arange(lim), lab[states]], bases
+
+
+def align_band_host(log_probs, lens, targets, target_lens, blank, band_states=None, want_band_base=True) -> BandResult:
+    """BAND_RULES on the host.  log_probs float32 [P, T, C]; lens int [P] or None; targets int32 [P, max_labels] and
+    target_lens int32 [P]; blank: the blank id; band_states: one of BAND_STATES (None: pick_band_states of the row pitch)."""
+    lp = np.asarray(log_probs, dtype=np.float32)
+    if lp.ndim != 3 or min(lp.shape) < 1:
+        raise ValueError(f'align_band_host: log_probs must be [P, T, C] with P, T, C >= 1, got {lp.shape}')
+    P, T, C = lp.shape
+    tg = np.asarray(targets)
+    tl = np.asarray(target_lens)
+    if tg.ndim != 2 or tg.shape[0] != P or tl.shape != (P,):
+        raise ValueError(f'align_band_host: targets must be [P, max_labels] with one length each, got {tg.shape} / {tl.shape} '
+                         f'for P {P}')
+    ML = tg.shape[1]
+    if not 1 <= ML <= BAND_MAX_LABELS:
+        raise ValueError(f'align_band_host: max_labels (the row pitch of targets) must be 1 .. {BAND_MAX_LABELS}, got {ML}')
+    if T > BAND_MAX_FRAMES:
+        raise ValueError(f'align_band_host: at most {BAND_MAX_FRAMES} frames, got {T}')
+    blank = int(blank)
+    if not 0 <= blank < C:
+        raise ValueError(f'align_band_host: blank {blank} is outside [0, {C})')
+    BW = pick_band_states(ML, band_states)
+    tg = tg.astype(np.int32)
+    start = np.zeros((P, ML), dtype=np.int32)
+    nframes = np.zeros((P, ML), dtype=np.int32)
+    score = np.zeros((P, ML), dtype=np.float32)
+    path_score = np.full(P, NEG, dtype=np.int64)
+    ok = np.zeros(P, dtype=np.int32)
+    frame_logp = np.zeros((P, T), dtype=np.float32)
+    band_base = np.zeros((P, (T + BAND_BLOCK - 1) // BAND_BLOCK), dtype=np.int32)
+    for p in range(P):
+        lim = T if lens is None else int(min(max(int(lens[p]), 0), T))
+        L = int(tl[p])
+        if L < 0 or L > ML:
+            continue
+        y = tg[p, :L]
+        if L and (y.min() < 0 or y.max() >= C or (y == blank).any()):
+            continue
+        ok[p], st, nf, sc, ps, fl, bases = _align_band_one(lp[p], lim, y, blank, BW)
+        band_base[p, :len(bases)] = bases
+        if ok[p]:
+            path_score[p] = ps
+            if st is not None:
+                start[p, :L], nframes[p, :L], score[p, :L] = st, nf, sc
+                frame_logp[p, :lim] = fl
+    return BandResult(tg, tl.astype(np.int32), start, nframes, score, path_score, None, ok, blank, 1, frame_logp,
+                      band_base if want_band_base else None, BW)
+
+
+def segment_scores(frame_logp, f0, f1) -> np.ndarray:
+    """Min-mean confidence of segments (Kuerzinger et al., CTC-segmentation): for the frames [f0[i], f1[i]) of frame_logp [T],
+    in float64, the mean over all of them when there are at most SEGMENT_WINDOW, else the minimum over t of the mean of
+    frame_logp[t : t + SEGMENT_WINDOW] (whole windows inside the segment only).  An empty segment scores -inf."""
+    x = np.asarray(frame_logp, dtype=np.float64).reshape(-1)
+    f0 = np.atleast_1d(np.asarray(f0, dtype=np.int64))
+    f1 = np.atleast_1d(np.asarray(f1, dtype=np.int64))
+    out = np.full(len(f0), -np.inf, dtype=np.float64)
+    for i, (a, b) in enumerate(zip(f0, f1)):
+        a, b = max(int(a), 0), min(int(b), len(x))
+        if b - a <= 0:
+            continue
+        if b - a <= SEGMENT_WINDOW:
+            out[i] = x[a:b].mean()
+        else:
+            out[i] = np.lib.stride_tricks.sliding_window_view(x[a:b], SEGMENT_WINDOW).mean(axis=1).min()
+    return out

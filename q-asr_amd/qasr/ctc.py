@@ -27,6 +27,17 @@ class CtcResult:
 
 
 @dataclass
+class Segment:
+    """One utterance of a transcript inside a long recording (EncDecCTCModel.align_long): from the first frame of its first
+    label to the end of its last label's run, in seconds of the recording; score: qasr.align.segment_scores (-inf, with times
+    None, when the alignment was lost)."""
+    text: str
+    start_s: Optional[float]
+    end_s: Optional[float]
+    score: float
+
+
+@dataclass
 class Hypothesis:
     text: str
     labels: List[int]
@@ -38,6 +49,7 @@ class Hypothesis:
     lm_score: Optional[float] = None        # beam search with a language model: the model's share of utt_score
     ctc_score: Optional[float] = None       # forced alignment (qasr.align): the CTC log-likelihood of the text, all alignments
     boost_score: Optional[float] = None     # beam search with phrase boosting (qasr.boost): the boosting's share of utt_score
+    segments: Optional[List[Segment]] = None  # align_long with a list of utterances: one Segment per utterance
     seams_s: Optional[List[float]] = None   # decode_long (qasr.longform): the times at which neighbouring windows were joined
 
 

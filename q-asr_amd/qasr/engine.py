@@ -18,6 +18,7 @@ SYMBOLS = ['qasr_blob_check', 'qasr_engine_create', 'qasr_engine_create_ex', 'qa
            'qasr_dyn_quant_in', 'qasr_dyn_conv_params', 'qasr_sep_layer', 'qasr_quantile2', 'qasr_quantile_workspace_bytes', 'qasr_debug_prof',
            'qasr_debug_timeline', 'qasr_ctc_collapse', 'qasr_engine_attach_ctc', 'qasr_ctc_topn', 'qasr_ctc_beam_workspace_bytes', 'qasr_ctc_beam',
            'qasr_lm_check', 'qasr_ctc_beam_lm', 'qasr_boost_check', 'qasr_ctc_beam_boost', 'qasr_ctc_align_workspace_bytes', 'qasr_ctc_align',
+           'qasr_ctc_align_band_workspace_bytes', 'qasr_ctc_align_band',
            'qasr_engine_reserve', 'qasr_engine_forward_ragged', 'qasr_engine_forward_ragged_audio', 'qasr_engine_ragged_stats',
            'qasr_ragged_bucket_frames', 'qasr_ragged_envelope_frames',
            'qasr_resample_check', 'qasr_resample', 'qasr_resample_out_samples', 'qasr_longform_cut', 'qasr_longform_stitch',
@@ -160,6 +161,10 @@ def load_library():
         lib.qasr_ctc_align.argtypes = [vp, C.POINTER(AlignArgs)]
         lib.qasr_ctc_align_workspace_bytes.argtypes = [i32, i32, i32]
         lib.qasr_ctc_align_workspace_bytes.restype = sz
+    if hasattr(lib, 'qasr_ctc_align_band'):     # (likewise)
+        lib.qasr_ctc_align_band.argtypes = [vp, C.POINTER(AlignBandArgs)]
+        lib.qasr_ctc_align_band_workspace_bytes.argtypes = [i32, i32, i32]
+        lib.qasr_ctc_align_band_workspace_bytes.restype = sz
     if hasattr(lib, 'qasr_engine_reserve'):     # (likewise)
         lib.qasr_engine_reserve.argtypes = [vp, C.POINTER(ReserveOpts)]
         lib.qasr_engine_forward_ragged.argtypes = [vp, vp, vp, vp, i32, i32, C.POINTER(RaggedOut)]
@@ -610,6 +615,80 @@ def ctc_align(log_probs, lens, targets, target_lens, blank, problems_per_utt=1, 
     with torch.cuda.device(dev):
         _check(lib.qasr_ctc_align(_stream_ptr(stream), C.byref(a)), 'qasr_ctc_align')
     out._keep = (lp, ln, tg, tl, workspace, tab)
+    return out
+
+
+class AlignBandArgs(C.Structure):
+    """qasr_ctc_align_band_args (include/qasr.h)"""
+    _fields_ = ([('struct_size', C.c_uint32)] + [(n, C.c_int32) for n in ('B', 'T', 'C', 'blank', 'max_labels', 'band_states')] +
+                [('reserved', C.c_uint32), ('pitch_utt', C.c_int64), ('pitch_frame', C.c_int64)] +
+                [(n, C.c_void_p) for n in ('log_probs', 'lens', 'targets', 'target_lens', 'workspace')] +
+                [('workspace_bytes', C.c_size_t)] +
+                [(n, C.c_void_p) for n in ('start', 'nframes', 'score', 'path_score', 'frame_logp', 'band_base', 'ok')])
+
+
+def ctc_align_band_workspace_bytes(P, T, band_states):
+    return int(load_library().qasr_ctc_align_band_workspace_bytes(int(P), int(T), int(band_states)))
+
+
+def ctc_align_band(log_probs, lens, targets, target_lens, blank, band_states=None, want_band_base=True, workspace=None, out=None,
+                   stream=None):
+    """qasr_ctc_align_band: banded CTC alignment of whole recordings against whole transcripts on the device (k_align_band,
+    one launch on the current stream, no host synchronisation); equal to qasr.align.align_band_host byte for byte.
+    log_probs: a cuda float32 tensor [P, T, C] (any recording / frame pitch, classes contiguous); lens int32 [P] optional;
+    targets cuda int32 [P, max_labels] with target_lens int32 [P].  band_states: 256, 1024 or 4352 (None: the smallest that
+    holds 2 * max_labels + 1 states, else 4352).  Returns a qasr.align.BandResult of cuda tensors.  workspace: a caller-owned
+    uint8 tensor of ctc_align_band_workspace_bytes(P, T, band_states) bytes (None: allocated by torch here); `out`: a
+    caller-owned BandResult whose start / nframes / score / path_score / frame_logp / band_base may each be None."""
+    from .align import BAND_BLOCK, BAND_MAX_FRAMES, BAND_MAX_LABELS, BandResult, pick_band_states
+    lib = load_library()
+    assert log_probs.is_cuda and log_probs.dim() == 3 and log_probs.dtype == torch.float32, \
+        'ctc_align_band: log_probs must be a cuda float32 tensor [P, T, C]'
+    dev = log_probs.device
+    lp = log_probs if log_probs.stride(2) == 1 or log_probs.shape[2] == 1 else log_probs.contiguous()
+    ln = None if lens is None else lens.to(device=dev, dtype=torch.int32).contiguous()
+    P, T, Cn = lp.shape
+    assert targets.dim() == 2 and target_lens.dim() == 1, 'ctc_align_band: targets must be [P, max_labels], target_lens [P]'
+    tg = targets.to(device=dev, dtype=torch.int32).contiguous()
+    tl = target_lens.to(device=dev, dtype=torch.int32).contiguous()
+    ML = tg.shape[1]
+    if tg.shape[0] != P or tl.shape[0] != P:
+        raise ValueError(f'ctc_align_band: {P} recordings but {tg.shape[0]} target rows and {tl.shape[0]} lengths')
+    if not 1 <= ML <= BAND_MAX_LABELS:
+        raise ValueError(f'ctc_align_band: max_labels (the row pitch of targets) must be 1 .. {BAND_MAX_LABELS}, got {ML}')
+    if T > BAND_MAX_FRAMES:
+        raise ValueError(f'ctc_align_band: at most {BAND_MAX_FRAMES} frames, got {T}')
+    BW = pick_band_states(ML, band_states)
+    NB = (T + BAND_BLOCK - 1) // BAND_BLOCK
+    if out is None:
+        i32 = dict(device=dev, dtype=torch.int32)
+        out = BandResult(labels=tg, n_labels=tl, start=torch.empty(P, ML, **i32), nframes=torch.empty(P, ML, **i32),
+                         score=torch.empty(P, ML, device=dev, dtype=torch.float32),
+                         path_score=torch.empty(P, device=dev, dtype=torch.int64), total=None, ok=torch.empty(P, **i32),
+                         blank=int(blank), problems_per_utt=1, frame_logp=torch.empty(P, T, device=dev, dtype=torch.float32),
+                         band_base=torch.empty(P, NB, **i32) if want_band_base else None)
+    out.band_states = BW
+    names = ('start', 'nframes', 'score', 'path_score', 'frame_logp', 'band_base', 'ok')
+    for n, dt, shape in zip(names, (torch.int32, torch.int32, torch.float32, torch.int64, torch.float32, torch.int32, torch.int32),
+                            ((P, ML), (P, ML), (P, ML), (P,), (P, T), (P, NB), (P,))):
+        t = getattr(out, n)
+        assert t is None or (t.is_cuda and t.is_contiguous() and t.dtype == dt and tuple(t.shape) == shape), \
+            f'ctc_align_band: out.{n}'
+    assert out.ok is not None, 'ctc_align_band: out.ok is required'
+    if workspace is None:
+        workspace = torch.empty(max(ctc_align_band_workspace_bytes(P, T, BW), 8), device=dev, dtype=torch.uint8)
+    a = AlignBandArgs()
+    a.struct_size = C.sizeof(AlignBandArgs)
+    a.B, a.T, a.C, a.blank, a.max_labels, a.band_states = P, T, Cn, int(blank), ML, BW
+    a.pitch_utt, a.pitch_frame = (lp.stride(0) if P > 1 else max(lp.stride(0), T * lp.stride(1))), lp.stride(1)
+    a.log_probs, a.lens, a.targets, a.target_lens = lp.data_ptr(), 0 if ln is None else ln.data_ptr(), tg.data_ptr(), tl.data_ptr()
+    a.workspace, a.workspace_bytes = workspace.data_ptr(), workspace.numel() * workspace.element_size()
+    for n in names:
+        t = getattr(out, n)
+        setattr(a, n, 0 if t is None else t.data_ptr())
+    with torch.cuda.device(dev):
+        _check(lib.qasr_ctc_align_band(_stream_ptr(stream), C.byref(a)), 'qasr_ctc_align_band')
+    out._keep = (lp, ln, tg, tl, workspace)
     return out
 
 
