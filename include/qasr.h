@@ -639,6 +639,88 @@ typedef struct qasr_longform_stitch_args {
 } qasr_longform_stitch_args;
 int qasr_longform_stitch(void* stream, const qasr_longform_stitch_args* args);
 
+/* ---- streaming recognition, buffered: per-stream state and chunked decode on the device ---------------------------------
+ * The models are not causal and normalise per utterance, so a step re-runs a window [left context L | new chunk C |
+ * look-ahead Rr] (Wl = L + C + Rr samples, each a multiple of samples_per_frame) of a stream's latest samples through the
+ * engine, and only the chunk's frames become final, one look-ahead late.  The rule, the state layout and the NumPy twins are
+ * qasr/stream.py (StreamPlan, STREAM_RULES), which the three kernels follow byte for byte, the state included: what is
+ * pinned is that equality and the invariant that the per-step deltas of any sequence of steps over one stream, concatenated,
+ * are the outputs of qasr_ctc_collapse over the concatenated final frames on every byte (labels, start, nframes, score, count;
+ * the END step's utt_score is qasr_ctc_out.utt_score of that row).  Accuracy on speech is not pinned.
+ *   state    device memory of qasr_stream_state_bytes(S, Wl, C) bytes, 16-byte aligned, for S slots: per slot 80 32-bit
+ *            words (received i64, frames_done, the open run's token + 1 / first global frame / running maximum in k_ctc's
+ *            integer order, n_labels, 64 f32 partial sums of utt_score), then per slot a ring of Wl + C samples (rounded up
+ *            to a multiple of 4).  Zeroed memory is S fresh streams.  0 bytes: S, Wl or C < 1, or Wl + C beyond int32.
+ *   slots    device i32 [B], distinct, each < S (a slot out of range: its row is skipped / reports status 2)
+ *   flags    device i32 [B]: QASR_STREAM_BEGIN (push: forget the slot's history and state first), QASR_STREAM_END (emit:
+ *            every frame of the window becomes final, the open run closes, utt_score is summed)
+ * qasr_stream_push: chunk f32 or s16 [B][pitch] (s16 as float32(x) / 32768), n_new device i32 [B] (clamped to
+ *   0 .. min(pitch, C)) -> the slots' rings and `received`.  One launch; can be captured.
+ * qasr_stream_window: -> windows f32 [B][Wl] (the slot's samples [start, received), start = max(0, spf * ceil((received -
+ *   Wl) / spf)), zeros behind them), window_lens i32 [B], first_frame i32 [B] = start / spf: local frame j of the window is
+ *   global frame first_frame + j.  Reads the state, writes none of it.  One launch; can be captured.
+ * qasr_stream_emit: tokens i32 [B][Tw], frame_score f32 [B][Tw], enc_lens i32 [B] (clamped to 0 .. Tw) and first_frame as
+ *   the window's forward and qasr_stream_window gave them -> the step's delta, pitch P: labels (tail: blank) / start (global
+ *   frames) / nframes / score [B][P] (tails 0) of the runs that CLOSED inside the final range [frames_done, hi), hi =
+ *   first_frame + enc_len on END, else min(that, (received - Rr) / spf); the run that reaches hi - 1 stays open in the state.
+ *   n_new_labels (<= P), status (0; 1: frames_done < first_frame, frames were lost - nothing final, state untouched; 2: no such
+ *   slot), total_frames (= hi), utt_score (END rows; else 0) [B].  tail_labels i32 [B][Ptail] and tail_n i32 [B] (both or
+ *   neither): the provisional labels of the look-ahead frames, the open run's first.  One launch; can be captured.
+ * QASR_ERR_ARG with nothing launched and nothing written: an unknown struct_size, a NULL among the required pointers (all but
+ * tail_labels / tail_n), B < 1, B > S, B > 65535 (the rows are one dimension of a launch grid), Wl / C < 1, samples_per_frame < 1, Wl, C or Rr no multiple of samples_per_frame, Rr < 0
+ * or Rr + C > Wl, state_bytes below qasr_stream_state_bytes(S, Wl, C), an unknown sample format, pitch < 0, Tw / P < 1, Ptail < 1
+ * with a tail, one of tail_labels / tail_n without the other. */
+enum { QASR_STREAM_BEGIN = 1, QASR_STREAM_END = 2 };
+size_t qasr_stream_state_bytes(int S, int Wl, int C);
+typedef struct qasr_stream_push_args {
+  uint32_t struct_size;        /* sizeof of this struct in the caller's header */
+  int32_t S, B, Wl, C, samples_per_frame;
+  int32_t dtype, reserved;     /* dtype: QASR_PCM_S16 / QASR_PCM_F32 */
+  void* state;
+  size_t state_bytes;
+  const int32_t* slots;
+  const int32_t* flags;
+  const int32_t* n_new;
+  const void* chunk;
+  int64_t pitch;               /* samples per chunk row */
+} qasr_stream_push_args;
+int qasr_stream_push(void* stream, const qasr_stream_push_args* args);
+typedef struct qasr_stream_window_args {
+  uint32_t struct_size;        /* sizeof of this struct in the caller's header */
+  int32_t S, B, Wl, C, samples_per_frame;
+  int32_t reserved[2];
+  const void* state;
+  size_t state_bytes;
+  const int32_t* slots;
+  float* windows;
+  int32_t* window_lens;
+  int32_t* first_frame;
+} qasr_stream_window_args;
+int qasr_stream_window(void* stream, const qasr_stream_window_args* args);
+typedef struct qasr_stream_emit_args {
+  uint32_t struct_size;        /* sizeof of this struct in the caller's header */
+  int32_t S, B, Wl, C, Rr, samples_per_frame, Tw, P, Ptail, blank, reserved;
+  void* state;
+  size_t state_bytes;
+  const int32_t* slots;
+  const int32_t* flags;
+  const int32_t* tokens;
+  const float* frame_score;
+  const int32_t* enc_lens;
+  const int32_t* first_frame;
+  int32_t* labels;
+  int32_t* start;
+  int32_t* nframes;
+  float* score;
+  int32_t* n_new_labels;
+  int32_t* status;
+  int32_t* total_frames;
+  float* utt_score;
+  int32_t* tail_labels;        /* optional, with tail_n */
+  int32_t* tail_n;
+} qasr_stream_emit_args;
+int qasr_stream_emit(void* stream, const qasr_stream_emit_args* args);
+
 /* ---- reserved engines: ragged batches without allocation, with graph replay ------------------------------------------
  * A data loader pads every batch to its own longest utterance (the reference's collate function), so (B, T) changes on
  * almost every call; qasr_engine_forward[_audio] then rebuilds its plan (device-synchronising frees + allocations) and,

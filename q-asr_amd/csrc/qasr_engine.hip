@@ -1448,6 +1448,71 @@ int qasr_longform_stitch(void* stream, const qasr_longform_stitch_args* a) {
   return QASR_OK;
 }
 
+// ---- streaming (k_stream_push / _window / _emit, qasr_stream.hip): the checks of include/qasr.h and one launch each
+size_t qasr_stream_state_bytes(int S, int Wl, int C) { return stream_state_bytes(S, Wl, C); }
+
+static int stream_geometry(const char* who, int S, int B, int Wl, int C, int Rr, int spf, size_t state_bytes) {
+  if (S < 1 || B < 1 || B > S || B > 65535) return fail(QASR_ERR_ARG, "%s: B %d must lie in 1 .. min(S = %d, 65535)", who, B, S);
+  if (Wl < 1 || C < 1 || spf < 1) return fail(QASR_ERR_ARG, "%s: Wl %d, C %d and samples_per_frame %d must be at least 1", who, Wl, C, spf);
+  if (Wl % spf || C % spf || Rr % spf)
+    return fail(QASR_ERR_ARG, "%s: Wl %d, C %d and Rr %d must be multiples of samples_per_frame %d", who, Wl, C, Rr, spf);
+  if (Rr < 0 || (long long)Rr + C > Wl) return fail(QASR_ERR_ARG, "%s: Rr %d must lie in 0 .. Wl - C = %d", who, Rr, Wl - C);
+  const size_t need = stream_state_bytes(S, Wl, C);
+  if (!need || state_bytes < need) return fail(QASR_ERR_ARG, "%s: state_bytes %zu, qasr_stream_state_bytes gives %zu", who, state_bytes, need);
+  return QASR_OK;
+}
+
+int qasr_stream_push(void* stream, const qasr_stream_push_args* a) {
+  if (!a) return fail(QASR_ERR_ARG, "stream_push: args is NULL");
+  if (a->struct_size != sizeof(qasr_stream_push_args))
+    return fail(QASR_ERR_ARG, "stream_push: struct_size %u is not %zu", a->struct_size, sizeof(qasr_stream_push_args));
+  if (!a->state || !a->slots || !a->flags || !a->n_new || !a->chunk)
+    return fail(QASR_ERR_ARG, "stream_push: state, slots, flags, n_new and chunk are required");
+  int rc = stream_geometry("stream_push", a->S, a->B, a->Wl, a->C, 0, a->samples_per_frame, a->state_bytes);
+  if (rc) return rc;
+  if (a->dtype != QASR_PCM_S16 && a->dtype != QASR_PCM_F32) return fail(QASR_ERR_ARG, "stream_push: dtype %d is neither s16 nor f32", a->dtype);
+  if (a->pitch < 0) return fail(QASR_ERR_ARG, "stream_push: pitch %lld < 0", (long long)a->pitch);
+  if ((uintptr_t)a->state & 15) return fail(QASR_ERR_ARG, "stream_push: state is not 16-byte aligned");
+  rc = launch_stream_push((hipStream_t)stream, *a);
+  if (rc) return fail(rc, "stream_push: launch");
+  HIPCHK(hipGetLastError());
+  return QASR_OK;
+}
+
+int qasr_stream_window(void* stream, const qasr_stream_window_args* a) {
+  if (!a) return fail(QASR_ERR_ARG, "stream_window: args is NULL");
+  if (a->struct_size != sizeof(qasr_stream_window_args))
+    return fail(QASR_ERR_ARG, "stream_window: struct_size %u is not %zu", a->struct_size, sizeof(qasr_stream_window_args));
+  if (!a->state || !a->slots || !a->windows || !a->window_lens || !a->first_frame)
+    return fail(QASR_ERR_ARG, "stream_window: state, slots, windows, window_lens and first_frame are required");
+  int rc = stream_geometry("stream_window", a->S, a->B, a->Wl, a->C, 0, a->samples_per_frame, a->state_bytes);
+  if (rc) return rc;
+  if ((uintptr_t)a->state & 15) return fail(QASR_ERR_ARG, "stream_window: state is not 16-byte aligned");
+  rc = launch_stream_window((hipStream_t)stream, *a);
+  if (rc) return fail(rc, "stream_window: launch");
+  HIPCHK(hipGetLastError());
+  return QASR_OK;
+}
+
+int qasr_stream_emit(void* stream, const qasr_stream_emit_args* a) {
+  if (!a) return fail(QASR_ERR_ARG, "stream_emit: args is NULL");
+  if (a->struct_size != sizeof(qasr_stream_emit_args))
+    return fail(QASR_ERR_ARG, "stream_emit: struct_size %u is not %zu", a->struct_size, sizeof(qasr_stream_emit_args));
+  if (!a->state || !a->slots || !a->flags || !a->tokens || !a->frame_score || !a->enc_lens || !a->first_frame || !a->labels ||
+      !a->start || !a->nframes || !a->score || !a->n_new_labels || !a->status || !a->total_frames || !a->utt_score)
+    return fail(QASR_ERR_ARG, "stream_emit: every pointer but tail_labels / tail_n is required");
+  int rc = stream_geometry("stream_emit", a->S, a->B, a->Wl, a->C, a->Rr, a->samples_per_frame, a->state_bytes);
+  if (rc) return rc;
+  if (a->Tw < 1 || a->P < 1) return fail(QASR_ERR_ARG, "stream_emit: Tw %d and P %d must be at least 1", a->Tw, a->P);
+  if ((a->tail_labels == nullptr) != (a->tail_n == nullptr)) return fail(QASR_ERR_ARG, "stream_emit: tail_labels and tail_n come together");
+  if (a->tail_labels && a->Ptail < 1) return fail(QASR_ERR_ARG, "stream_emit: Ptail %d < 1", a->Ptail);
+  if ((uintptr_t)a->state & 15) return fail(QASR_ERR_ARG, "stream_emit: state is not 16-byte aligned");
+  rc = launch_stream_emit((hipStream_t)stream, *a);
+  if (rc) return fail(rc, "stream_emit: launch");
+  HIPCHK(hipGetLastError());
+  return QASR_OK;
+}
+
 int qasr_engine_attach_ctc(qasr_engine* e, float* frame_score, const qasr_ctc_out* out, int use_lens) {
   if (!e) return fail(QASR_ERR_ARG, "attach_ctc: engine is NULL");
   if (frame_score || out) {

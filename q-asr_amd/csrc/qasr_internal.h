@@ -176,6 +176,11 @@ int launch_resample(hipStream_t s, const qasr_resample_args& a);
 // qasr_longform.hip: windows of long recordings cut (k_cut) and stitched (k_stitch); the arguments are checked by the callers
 int launch_longform_cut(hipStream_t s, const qasr_longform_cut_args& a);
 int launch_longform_stitch(hipStream_t s, const qasr_longform_stitch_args& a);
+// qasr_stream.hip: streaming state, windows and the incremental collapse (k_stream_push / _window / _emit); checked by the callers
+size_t stream_state_bytes(int S, int Wl, int C);
+int launch_stream_push(hipStream_t s, const qasr_stream_push_args& a);
+int launch_stream_window(hipStream_t s, const qasr_stream_window_args& a);
+int launch_stream_emit(hipStream_t s, const qasr_stream_emit_args& a);
 // qasr_ragged.hip: the bucket policy of reserved engines and their one eager launch per call (k_ragged_stage)
 #define QASR_RAGGED_TILE 128          /* every bucket edge is a multiple of the largest frame tile */
 #define QASR_SHAPE_B 0                /* shape block, i32: rows of the batch, */

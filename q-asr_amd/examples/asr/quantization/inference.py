@@ -92,7 +92,20 @@ def main():
                         "batches of --batch_size and stitch the results on the device (EncDecCTCModel.decode_long)")
     p.add_argument("--overlap_s", type=float, default=None, metavar='SECONDS',
                    help="(extension, needs --window_s) overlap of neighbouring windows (default 4.0)")
+    p.add_argument("--stream_chunk_s", type=float, default=None, metavar='SECONDS',
+                   help="(extension) play every manifest entry through a streaming session (EncDecCTCModel.stream), --batch_size "
+                        "streams at a time in chunks of this many seconds; hypotheses and WER come from the sessions' final results")
+    p.add_argument("--stream_left_s", type=float, default=None, metavar='SECONDS',
+                   help="(extension, needs --stream_chunk_s) context in front of every chunk (default 4.0)")
+    p.add_argument("--stream_right_s", type=float, default=None, metavar='SECONDS',
+                   help="(extension, needs --stream_chunk_s) look-ahead behind every chunk (default 0.96)")
     args = p.parse_args()
+    if (args.stream_left_s is not None or args.stream_right_s is not None) and args.stream_chunk_s is None:
+        p.error('--stream_left_s and --stream_right_s need --stream_chunk_s')
+    if args.stream_chunk_s is not None:
+        for flag in ('window_s', 'beam_width', 'input_rate', 'align'):
+            if getattr(args, flag) is not None:
+                p.error(f'--stream_chunk_s does not go with --{flag}: a streaming session is greedy, at the model\'s rate')
     if args.overlap_s is not None and args.window_s is None:
         p.error('--overlap_s needs --window_s')
     if args.window_s is not None and args.timestamps and args.beam_width is not None:
@@ -185,12 +198,27 @@ def main():
         lm_kw['boost'] = qboost.PhraseSet(qboost.read_phrase_file(args.boost_file), asr_model.decoder.vocabulary, weight=boost_weight)
     aligned, items = [], getattr(asr_model.test_dataloader().dataset, 'items', [])
     audio_s, t0 = 0.0, time.time()
+    stream_sess = None
     for i, batch in enumerate(asr_model.test_dataloader()):
         if i == args.eval_early_stop:
             break
         batch = [x.cuda() for x in batch]
         signal = batch[0] if rate_kw else batch[0].float()   # --input_rate: int16 PCM, resampled inside the model's call
-        if args.window_s is not None:                        # k_cut, windows in batches, k_stitch, one collapse / search
+        if args.stream_chunk_s is not None:                  # one session per batch: k_stream_push / _window / _emit per step
+            if stream_sess is None:                          # one session for the whole manifest: one reservation, one graph
+                try:
+                    stream_sess = asr_model.stream(max_streams=args.batch_size, chunk_s=args.stream_chunk_s, tail=False,
+                                                   left_s=4.0 if args.stream_left_s is None else args.stream_left_s,
+                                                   right_s=0.96 if args.stream_right_s is None else args.stream_right_s)
+                except ValueError as e:
+                    p.error(f'--stream_chunk_s / --stream_left_s / --stream_right_s: {e}')
+            stream_hyps = asr_model.decode_stream(signal, batch[1], session=stream_sess)
+            for h in stream_hyps:
+                hyps.append(h.text)
+                if args.timestamps:
+                    words.append([list(w) for w in h.words])
+                    utt_scores.append(h.utt_score)
+        elif args.window_s is not None:                      # k_cut, windows in batches, k_stitch, one collapse / search
             overlap_s = 4.0 if args.overlap_s is None else args.overlap_s
             try:
                 long_hyps = asr_model.decode_long(signal, batch[1], window_s=args.window_s, overlap_s=overlap_s,
@@ -217,7 +245,7 @@ def main():
         else:
             log_probs, enc_len, greedy = asr_model(input_signal=signal, input_signal_length=batch[1], **rate_kw)
             hyps += wer.ctc_decoder_predictions_tensor(greedy)
-        if args.timestamps and args.window_s is None:        # device-side collapse up to each utterance's encoded length
+        if args.timestamps and args.window_s is None and args.stream_chunk_s is None:        # device-side collapse up to each utterance's encoded length
             for h in asr_model.decode(input_signal=signal, input_signal_length=batch[1], **rate_kw):
                 words.append([list(w) for w in h.words])
                 utt_scores.append(h.utt_score)
@@ -242,6 +270,9 @@ def main():
     torch.cuda.synchronize()
     wall = time.time() - t0
     served = type(getattr(asr_model, '_engine', None) or getattr(asr_model, '_ragged_engine', None)).__name__
+    if stream_sess is not None:                              # the session's engine leaves with its reservation
+        stream_sess.close_all()
+        served = stream_sess.served
     print('path:', {'Engine': 'static integer engine (HIP)', 'DynamicRunner': 'dynamic device path (HIP)'}.get(
         served, 'host modules'))
     wer_value = word_error_rate(hypotheses=hyps, references=refs)

@@ -8,6 +8,7 @@ Two execution paths share this one object:
     gfx950 kernels of libqasr_hip.so.  There is no CPU fallback for that configuration: a missing
     library or GPU raises.
 """
+import dataclasses
 import io
 import os
 import tarfile
@@ -681,6 +682,79 @@ class EncDecCTCModel(nn.Module):
                 h.seams_s = s
         return hyps if n_best > 1 else [h[0] for h in hyps]
 
+    def _stream_plan(self, chunk_s=0.96, left_s=4.0, right_s=0.96):
+        """the qasr.stream.StreamPlan of stream(): units and frames_of taken from the model as _long_plan takes them"""
+        from qasr import stream as qstream
+        lp = self._long_plan([1])
+        return qstream.StreamPlan(chunk_s, left_s, right_s, lp.sample_rate, lp.samples_per_frame, lp.frames_of)
+
+    def stream(self, max_streams=32, chunk_s=0.96, left_s=4.0, right_s=0.96, tail=True, sample_rate=None, beam_width=None):
+        """A streaming session (an extension; NeMo's buffered streaming, the FrameBatchASR idea, for many streams at once):
+
+            sess = model.stream(max_streams=32, chunk_s=0.96, left_s=4.0, right_s=0.96)
+            slot = sess.open()
+            updates = sess.push(slots, signal[B, n], lengths)      # any n; float32 or int16 at the model's rate
+            hyp = sess.close(slot)                                  # the END step; the slot is free again
+
+        The models are not causal and normalise per utterance, so nothing is cached: whenever a stream has received another
+        chunk_s seconds, a step runs the window [left_s of context | the chunk | right_s of look-ahead] of its latest
+        samples through the model - the same _forward call decode_long makes, so the static engine, a reserved engine, the
+        dynamic path and the host modules all work - and the chunk's frames become final, right_s late (qasr.stream.
+        STREAM_RULES).  The samples, the counters, the open run and the score sums of every stream stay on the device
+        (k_stream_push, k_stream_window, k_stream_emit); a step reads back its small delta only.  push() returns one
+        qasr.ctc.StreamUpdate per step and stream; close() returns the qasr.ctc.Hypothesis of the whole stream (text, label
+        and word times, confidences, utt_score), equal on every byte to the greedy collapse of the final frames.  tail=True
+        also lists the provisional text of the look-ahead frames.  CPU tensors run the NumPy twins.
+
+        On the calibrated model the session holds a reservation of (max_streams, window) for its lifetime - every step of
+        full windows replays one captured graph and the engine allocates nothing (its device_allocs counter stands still;
+        the session's small uploads of slots / flags / counts and its chunk staging go through torch's caching allocator) -
+        and close_all() / leaving the `with` block restores the caller's.  Results do not depend on how the caller slices its pushes.  On the static engine a
+        stream's result does not depend on which other streams shared its steps either; on the dynamic path the ranges
+        are derived per batch, so there it does.
+
+        Normalisation is per window; the first left_s seconds of a stream see less context; the latency is chunk_s +
+        right_s plus the step; the defaults are untried on speech.  Refused: sample_rate other than the model's (a streaming
+        resampler needs filter state), beam_width (no beam search across steps)."""
+        if sample_rate is not None and int(sample_rate) != int(self.preprocessor._sample_rate):
+            raise ValueError(f'stream: sample_rate {sample_rate} is not the model\'s {int(self.preprocessor._sample_rate)}: '
+                             'resampling a stream needs filter state across pushes, which is not built')
+        if beam_width is not None:
+            raise ValueError('stream: beam_width is not supported: the incremental collapse is greedy')
+        if int(max_streams) < 1:
+            raise ValueError(f'stream: max_streams must be at least 1, got {max_streams}')
+        try:
+            plan = self._stream_plan(chunk_s, left_s, right_s)
+        except ValueError as e:
+            raise ValueError(f'stream: {e}') from None
+        return StreamSession(self, int(max_streams), plan, bool(tail))
+
+    @torch.no_grad()
+    def decode_stream(self, input_signal, input_signal_length, chunk_s=0.96, left_s=4.0, right_s=0.96, session=None):
+        """A batch of complete recordings played through a streaming session, all rows side by side in pushes of chunk_s
+        seconds (what inference.py --stream_chunk_s does): List[qasr.ctc.Hypothesis], one per row - the hypotheses
+        stream() gives for that audio, which do not depend on the size of the pushes.
+
+        session=<a session of this model with at least B free slots> plays the batch through it and leaves it open.
+        Without one, a session is opened and closed per call - and on the calibrated model that is not free: taking and
+        restoring the reservation closes the reserved engine each time (a caller's own included), so the engine is built
+        and its graph captured again for every call.  A caller with many batches holds one session across them."""
+        if input_signal.dim() != 2:
+            raise ValueError(f'decode_stream: input_signal must be [B, S], got {tuple(input_signal.shape)}')
+        B = input_signal.shape[0]
+        lens = [min(int(n), input_signal.shape[1]) for n in input_signal_length.tolist()]
+        sess = session if session is not None else self.stream(max_streams=B, chunk_s=chunk_s, left_s=left_s, right_s=right_s, tail=False)
+        try:
+            slots = [sess.open() for _ in range(B)]
+            C = sess.plan.C
+            for off in range(0, max(lens + [0]), C):
+                live = [b for b in range(B) if off < lens[b]]
+                sess.push([slots[b] for b in live], input_signal[live, off:off + C], [min(C, lens[b] - off) for b in live])
+            return [sess.close(s) for s in slots]
+        finally:
+            if session is None:
+                sess.close_all()
+
     @staticmethod
     def _beam_args(beam_width, n_best, cutoff_top_n):
         from qasr import beam as qbeam
@@ -1020,3 +1094,174 @@ class EncDecCTCModel(nn.Module):
         if decode:
             return self._collapse(log_probs, log_probs.argmax(dim=-1, keepdim=False), encoded_len)
         return log_probs, encoded_len, log_probs.argmax(dim=-1, keepdim=False)
+
+
+class StreamSession:
+    """EncDecCTCModel.stream(): the live streams of one model.  The host keeps counts it already has (samples per stream, the
+    deltas read back so far); everything a step computes from lives on the device."""
+
+    def __init__(self, model, max_streams, plan, tail):
+        self.model, self.S, self.plan, self.tail = model, max_streams, plan, tail
+        self._open = {}                      # slot -> dict(received, begin, deltas)
+        self._dev = None                     # decided by the first push: a cuda device, or 'cpu'
+        self._state = None
+        self._own = False
+        self.steps = 0
+        self.served = None                   # after close_all(): the class that ran the steps' forwards ('Engine', 'DynamicRunner', 'NoneType': host modules)
+        if model.engine_ready():             # the calibrated model: one reservation for the session's lifetime
+            self._saved = (model._reserve, getattr(model, '_reserve_logp', True))
+            model.reserve(max_streams, plan.Wl / float(plan.sample_rate))
+            model._reserve_logp = False
+            self._own = True
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close_all()
+
+    def close_all(self):
+        """Ends the session: open streams are dropped (close() them first for their hypotheses) and the caller's
+        reservation is restored."""
+        self._open.clear()
+        if self.served is None:              # (kept for reports: the session's engine goes with its reservation)
+            m = self.model
+            self.served = type(getattr(m, '_ragged_engine', None) or getattr(m, '_engine', None)).__name__
+        if self._own:
+            res, logp = self._saved
+            self.model.reserve(*(res if res is not None else (None, None)))
+            self.model._reserve_logp = logp
+            self._own = False
+
+    def open(self, slot=None):
+        if slot is None:
+            free = [s for s in range(self.S) if s not in self._open]
+            if not free:
+                raise ValueError(f'stream: all max_streams = {self.S} streams are open')
+            slot = free[0]
+        slot = int(slot)
+        if not 0 <= slot < self.S or slot in self._open:
+            raise ValueError(f'stream: slot {slot} is already open or outside 0 .. max_streams - 1 = {self.S - 1}')
+        self._open[slot] = dict(received=0, begin=True, deltas=[])
+        return slot
+
+    # ---- the three steps, on the device or as the twins
+    def _setup(self, device):
+        from qasr import engine as qengine, stream as qstream
+        if self._dev is not None:
+            if self._dev != device:
+                raise ValueError(f'stream: the session runs on {self._dev}, got a tensor on {device}')
+            return
+        self._dev = device
+        if device.type == 'cuda':
+            self._state = qengine.stream_state(self.S, self.plan, device)
+            self._win = (torch.empty(self.S, self.plan.Wl, device=device), torch.empty(self.S, device=device, dtype=torch.int32),
+                         torch.empty(self.S, device=device, dtype=torch.int32))
+            self._out = qengine.stream_emit_buffers(self.S, self.plan, device, tail=self.tail)
+        else:
+            self._state = qstream.StreamState(self.S, self.plan)
+
+    def _i32(self, x):
+        return torch.tensor(x, dtype=torch.int32).to(self._dev)
+
+    def _push(self, slots, flags, n_new, chunk):
+        from qasr import engine as qengine, stream as qstream
+        if self._dev.type == 'cuda':
+            qengine.stream_push(self._state, self.S, self.plan, self._i32(slots), self._i32(flags), self._i32(n_new), chunk)
+        else:
+            qstream.push_host(self._state, slots, flags, n_new, chunk.numpy())
+
+    def _step(self, slots, end):
+        """one step for `slots`: window -> forward -> emit; returns the rows' deltas as qasr.stream.StepRow-like tuples"""
+        from qasr import engine as qengine, stream as qstream
+        m, plan, B = self.model, self.plan, len(slots)
+        blank = len(m.decoder.vocabulary)
+        flags = [qstream.END if end else 0] * B
+        self.steps += 1
+        if self._dev.type == 'cuda':
+            sl, fl = self._i32(slots), self._i32(flags)
+            win, wl, first = qengine.stream_window(self._state, self.S, plan, sl, out=tuple(t[:B] for t in self._win))
+            tok, fs, enc = m._forward(win, wl.long(), decode='frames')
+            tok = tok.to(torch.int32).contiguous()
+            fs = fs.float().contiguous()
+            o = self._out
+            fields = [f.name for f in dataclasses.fields(o)]
+            out = qstream.StepBatch(*[None if getattr(o, n) is None else getattr(o, n)[:B] for n in fields])
+            qengine.stream_emit(self._state, self.S, plan, sl, fl, tok, fs, enc.to(torch.int32).contiguous(), first, blank, out=out)
+            o = qstream.StepBatch(*[None if getattr(out, n) is None else getattr(out, n).cpu().numpy() for n in fields])
+        else:
+            win, wl, first = qstream.window_host(self._state, slots)
+            tok, fs, enc = m._forward(torch.from_numpy(win), torch.from_numpy(wl).long(), decode='frames')
+            o = qstream.emit_batch_host(self._state, slots, flags, tok.numpy(), fs.float().numpy(), enc.numpy(), first, blank)
+            if not self.tail:
+                o.tail_labels = o.tail_n = None
+        if int(o.status.max()) != 0:
+            raise RuntimeError(f'stream: step refused, status {o.status.tolist()} for slots {slots}')
+        rows = []
+        for b in range(B):
+            n = int(o.n_new_labels[b])
+            tl = o.tail_labels[b, :int(o.tail_n[b])].tolist() if o.tail_labels is not None else []
+            rows.append((o.labels[b, :n].copy(), o.start[b, :n].copy(), o.nframes[b, :n].copy(), o.score[b, :n].copy(),
+                         float(o.utt_score[b]), tl))
+        return rows
+
+    def push(self, slots, signal, lengths=None):
+        """signal [B, n] float32 or int16 at the model's rate, lengths [B] (default: n each), slots: B distinct open slots.
+        Returns the StreamUpdates of the steps this audio completed, in the order they ran."""
+        from qasr import ctc as qctc, stream as qstream
+        slots = [int(s) for s in (slots.tolist() if torch.is_tensor(slots) else slots)]
+        if signal.dim() != 2 or signal.shape[0] != len(slots) or signal.dtype not in (torch.float32, torch.int16):
+            raise ValueError(f'stream: signal must be float32 or int16 [{len(slots)}, n], got {signal.dtype} {tuple(signal.shape)}')
+        if len(set(slots)) != len(slots) or any(s not in self._open for s in slots):
+            raise ValueError(f'stream: slots {slots} must be distinct and open (open slots: {sorted(self._open)})')
+        lens = [signal.shape[1]] * len(slots) if lengths is None else [int(x) for x in torch.as_tensor(lengths).tolist()]
+        if len(lens) != len(slots) or any(not 0 <= n <= signal.shape[1] for n in lens):
+            raise ValueError(f'stream: lengths {lens} must be one per slot, each within 0 .. {signal.shape[1]}')
+        self._setup(signal.device)
+        C, vocab, spf_s = self.plan.C, self.model.decoder.vocabulary, self.plan.seconds_per_frame()
+        pieces = [qstream.split_pushes(self._open[s]['received'] % C, n, C) for s, n in zip(slots, lens)]
+        offs = [0] * len(slots)
+        updates = []
+        for k in range(max([len(p) for p in pieces] + [0])):
+            rows = [i for i in range(len(slots)) if k < len(pieces[i])]
+            n_new = [pieces[i][k] for i in rows]
+            w = max(n_new)
+            chunk = torch.zeros(len(rows), w, dtype=signal.dtype, device=signal.device)
+            for j, i in enumerate(rows):
+                chunk[j, :n_new[j]] = signal[i, offs[i]:offs[i] + n_new[j]]
+                offs[i] += n_new[j]
+            sl = [slots[i] for i in rows]
+            self._push(sl, [qstream.BEGIN if self._open[s]['begin'] else 0 for s in sl], n_new, chunk)
+            stepping = []
+            for s, n in zip(sl, n_new):
+                st = self._open[s]
+                st['begin'] = False
+                st['received'] += n
+                if st['received'] % C == 0:
+                    stepping.append(s)
+            if stepping:
+                for s, (lab, start, nfr, sc, _, tl) in zip(stepping, self._step(stepping, False)):
+                    self._open[s]['deltas'].append((lab, start, nfr, sc))
+                    updates.append(qctc.StreamUpdate(s, lab.tolist(), ''.join(vocab[i] for i in lab.tolist()),
+                                                     (start.astype(np.float64) * spf_s).tolist(),
+                                                     ((start + nfr).astype(np.float64) * spf_s).tolist(),
+                                                     sc.astype(np.float64).tolist(), ''.join(vocab[i] for i in tl)))
+        return updates
+
+    def close(self, slot):
+        """The END step of one stream: every frame of its last window becomes final.  Returns its qasr.ctc.Hypothesis; the
+        slot is free again."""
+        from qasr import ctc as qctc
+        slot = int(slot)
+        if slot not in self._open:
+            raise ValueError(f'stream: slot {slot} is not open (open slots: {sorted(self._open)})')
+        st = self._open.pop(slot)
+        utt = 0.0
+        if st['received'] > 0:               # (a stream that never received a sample has nothing to run)
+            lab, start, nfr, sc, utt, _ = self._step([slot], True)[0]
+            st['deltas'].append((lab, start, nfr, sc))
+        cat = lambda i, dt: np.concatenate([d[i] for d in st['deltas']] + [np.zeros(0, dtype=dt)]).astype(dt)[None]
+        lab = cat(0, np.int32)
+        res = qctc.CtcResult(lab, np.array([lab.shape[1]], dtype=np.int32), cat(1, np.int32), cat(2, np.int32), cat(3, np.float32),
+                             np.array([utt], dtype=np.float32), len(self.model.decoder.vocabulary))
+        return qctc.to_hypotheses(res, self.model.decoder.vocabulary, self.plan.seconds_per_frame())[0]

@@ -38,6 +38,20 @@ class Segment:
 
 
 @dataclass
+class StreamUpdate:
+    """What one step of a streaming session (EncDecCTCModel.stream) made final for one stream: the labels whose runs closed,
+    their text, start / end times in seconds of the stream and confidences (best frame log-probability of each run), and
+    tail_text: the provisional text of the look-ahead frames, which the next step may change."""
+    slot: int
+    labels: List[int]
+    text: str
+    start_s: List[float]
+    end_s: List[float]
+    score: List[float]
+    tail_text: str = ''
+
+
+@dataclass
 class Hypothesis:
     text: str
     labels: List[int]

@@ -22,6 +22,7 @@ SYMBOLS = ['qasr_blob_check', 'qasr_engine_create', 'qasr_engine_create_ex', 'qa
            'qasr_engine_reserve', 'qasr_engine_forward_ragged', 'qasr_engine_forward_ragged_audio', 'qasr_engine_ragged_stats',
            'qasr_ragged_bucket_frames', 'qasr_ragged_envelope_frames',
            'qasr_resample_check', 'qasr_resample', 'qasr_resample_out_samples', 'qasr_longform_cut', 'qasr_longform_stitch',
+           'qasr_stream_state_bytes', 'qasr_stream_push', 'qasr_stream_window', 'qasr_stream_emit',
            'qasr_last_error', 'qasr_version']
 
 _lib = None
@@ -180,6 +181,12 @@ def load_library():
     if hasattr(lib, 'qasr_longform_cut'):       # (likewise)
         lib.qasr_longform_cut.argtypes = [vp, C.POINTER(LongformCutArgs)]
         lib.qasr_longform_stitch.argtypes = [vp, C.POINTER(LongformStitchArgs)]
+    if hasattr(lib, 'qasr_stream_push'):        # (likewise)
+        lib.qasr_stream_state_bytes.argtypes = [i32, i32, i32]
+        lib.qasr_stream_state_bytes.restype = sz
+        lib.qasr_stream_push.argtypes = [vp, C.POINTER(StreamPushArgs)]
+        lib.qasr_stream_window.argtypes = [vp, C.POINTER(StreamWindowArgs)]
+        lib.qasr_stream_emit.argtypes = [vp, C.POINTER(StreamEmitArgs)]
     lib.qasr_debug_prof.argtypes = [vp]
     lib.qasr_debug_timeline.argtypes = [vp, sz]
     lib.qasr_sep_layer.argtypes = [vp, C.POINTER(SepLayerArgs), C.c_char_p, sz]
@@ -928,6 +935,146 @@ def longform_stitch(plan, enc_lens, tokens, frame_score=None, planes=(), blank=N
         _check(lib.qasr_longform_stitch(_stream_ptr(stream), C.byref(a)), 'qasr_longform_stitch')
     total._keep = (src, ln, tab)
     return dst, total, seams
+
+
+class StreamPushArgs(C.Structure):
+    """qasr_stream_push_args (include/qasr.h)"""
+    _fields_ = ([('struct_size', C.c_uint32)] + [(n, C.c_int32) for n in ('S', 'B', 'Wl', 'C', 'samples_per_frame', 'dtype', 'reserved')] +
+                [('state', C.c_void_p), ('state_bytes', C.c_size_t)] +
+                [(n, C.c_void_p) for n in ('slots', 'flags', 'n_new', 'chunk')] + [('pitch', C.c_int64)])
+
+
+class StreamWindowArgs(C.Structure):
+    """qasr_stream_window_args (include/qasr.h)"""
+    _fields_ = ([('struct_size', C.c_uint32)] + [(n, C.c_int32) for n in ('S', 'B', 'Wl', 'C', 'samples_per_frame')] +
+                [('reserved', C.c_int32 * 2), ('state', C.c_void_p), ('state_bytes', C.c_size_t)] +
+                [(n, C.c_void_p) for n in ('slots', 'windows', 'window_lens', 'first_frame')])
+
+
+class StreamEmitArgs(C.Structure):
+    """qasr_stream_emit_args (include/qasr.h)"""
+    _fields_ = ([('struct_size', C.c_uint32)] +
+                [(n, C.c_int32) for n in ('S', 'B', 'Wl', 'C', 'Rr', 'samples_per_frame', 'Tw', 'P', 'Ptail', 'blank', 'reserved')] +
+                [('state', C.c_void_p), ('state_bytes', C.c_size_t)] +
+                [(n, C.c_void_p) for n in ('slots', 'flags', 'tokens', 'frame_score', 'enc_lens', 'first_frame', 'labels', 'start',
+                                           'nframes', 'score', 'n_new_labels', 'status', 'total_frames', 'utt_score', 'tail_labels',
+                                           'tail_n')])
+
+
+def stream_state(S, plan, device):
+    """Zeroed device state of S fresh streams under a qasr.stream.StreamPlan: an int32 tensor of
+    qasr_stream_state_bytes(S, Wl, C) / 4 words (S blocks of 80 words, then S rings).  `stream_block(state, S)` views the
+    blocks as [S, 80]."""
+    lib = load_library()
+    n = int(lib.qasr_stream_state_bytes(int(S), plan.Wl, plan.C))
+    if n == 0:
+        raise ValueError(f'stream_state: S {S}, Wl {plan.Wl}, C {plan.C} out of range')
+    return torch.zeros(n // 4, device=device, dtype=torch.int32)
+
+
+def stream_block(state, S):
+    from . import stream as qs
+    return state[:int(S) * qs.STATE_WORDS].view(int(S), qs.STATE_WORDS)
+
+
+def _i32dev(t, B, what):
+    assert t.is_cuda and t.dtype == torch.int32 and t.is_contiguous() and t.numel() == B, what
+
+
+def stream_push(state, S, plan, slots, flags, n_new, chunk, stream=None):
+    """qasr_stream_push: chunk float32 or int16 [B, n] (rows of any pitch) appended to the slots' rings; slots / flags /
+    n_new: cuda int32 [B].  k_stream_push, one launch on the current stream, nothing read back; equal to
+    qasr.stream.push_host byte for byte."""
+    lib = load_library()
+    if chunk.dim() != 2 or chunk.dtype not in (torch.float32, torch.int16) or not chunk.is_cuda:
+        raise ValueError(f'stream_push: chunk must be a cuda float32 or int16 tensor [B, n], got {chunk.dtype} {tuple(chunk.shape)}')
+    B = chunk.shape[0]
+    x = chunk if chunk.stride(1) == 1 else chunk.contiguous()
+    for t, w in ((slots, 'slots'), (flags, 'flags'), (n_new, 'n_new')):
+        _i32dev(t, B, 'stream_push: ' + w)
+    a = StreamPushArgs()
+    a.struct_size = C.sizeof(StreamPushArgs)
+    a.S, a.B, a.Wl, a.C, a.samples_per_frame = int(S), B, plan.Wl, plan.C, plan.samples_per_frame
+    a.dtype = PCM_S16 if x.dtype == torch.int16 else PCM_F32
+    a.state, a.state_bytes = state.data_ptr(), state.numel() * state.element_size()
+    a.slots, a.flags, a.n_new = slots.data_ptr(), flags.data_ptr(), n_new.data_ptr()
+    a.chunk, a.pitch = x.data_ptr(), (x.stride(0) if B > 1 else x.shape[1])
+    with torch.cuda.device(state.device):
+        _check(lib.qasr_stream_push(_stream_ptr(stream), C.byref(a)), 'qasr_stream_push')
+
+
+def stream_window(state, S, plan, slots, out=None, stream=None):
+    """qasr_stream_window: -> (windows float32 [B, Wl], zeros behind each length; window_lens int32 [B]; first_frame int32
+    [B]).  k_stream_window, one launch, nothing read back; equal to qasr.stream.window_host byte for byte.  `out`: the same
+    triple, caller-owned."""
+    lib = load_library()
+    B, dev = slots.numel(), state.device
+    _i32dev(slots, B, 'stream_window: slots')
+    if out is None:
+        out = (torch.empty(B, plan.Wl, device=dev, dtype=torch.float32), torch.empty(B, device=dev, dtype=torch.int32),
+               torch.empty(B, device=dev, dtype=torch.int32))
+    win, wl, first = out
+    assert win.is_cuda and win.dtype == torch.float32 and win.is_contiguous() and tuple(win.shape) == (B, plan.Wl), 'stream_window: out'
+    _i32dev(wl, B, 'stream_window: out')
+    _i32dev(first, B, 'stream_window: out')
+    a = StreamWindowArgs()
+    a.struct_size = C.sizeof(StreamWindowArgs)
+    a.S, a.B, a.Wl, a.C, a.samples_per_frame = int(S), B, plan.Wl, plan.C, plan.samples_per_frame
+    a.state, a.state_bytes, a.slots = state.data_ptr(), state.numel() * state.element_size(), slots.data_ptr()
+    a.windows, a.window_lens, a.first_frame = win.data_ptr(), wl.data_ptr(), first.data_ptr()
+    with torch.cuda.device(dev):
+        _check(lib.qasr_stream_window(_stream_ptr(stream), C.byref(a)), 'qasr_stream_window')
+    return win, wl, first
+
+
+def stream_emit_buffers(B, plan, device, P=None, tail=True):
+    """k_stream_emit's outputs as a qasr.stream.StepBatch of cuda tensors"""
+    from . import stream as qs
+    P = plan.emit_pitch if P is None else int(P)
+    i = lambda *s: torch.empty(*s, device=device, dtype=torch.int32)
+    f = lambda *s: torch.empty(*s, device=device, dtype=torch.float32)
+    return qs.StepBatch(i(B, P), i(B, P), i(B, P), f(B, P), i(B), i(B), i(B), f(B),
+                        i(B, plan.tail_pitch) if tail else None, i(B) if tail else None)
+
+
+def stream_emit(state, S, plan, slots, flags, tokens, frame_score, enc_lens, first_frame, blank, out=None, stream=None):
+    """qasr_stream_emit: one step's final frames folded into the slots' state; tokens int32 [B, Tw], frame_score float32
+    [B, Tw], enc_lens / first_frame / slots / flags cuda int32 [B] -> a qasr.stream.StepBatch of cuda tensors.
+    k_stream_emit, one launch, nothing read back; equal to qasr.stream.emit_batch_host byte for byte, the state included."""
+    lib = load_library()
+    dev = state.device
+    if tokens.dim() != 2 or tokens.dtype != torch.int32 or not tokens.is_contiguous() or not tokens.is_cuda:
+        raise ValueError(f'stream_emit: tokens must be a contiguous cuda int32 tensor [B, Tw], got {tokens.dtype} {tuple(tokens.shape)}')
+    B, Tw = tokens.shape
+    if frame_score.dtype != torch.float32 or not frame_score.is_contiguous() or frame_score.shape != tokens.shape:
+        raise ValueError('stream_emit: frame_score must be a contiguous float32 tensor of the shape of tokens')
+    for t, w in ((slots, 'slots'), (flags, 'flags'), (enc_lens, 'enc_lens'), (first_frame, 'first_frame')):
+        _i32dev(t, B, 'stream_emit: ' + w)
+    if out is None:
+        out = stream_emit_buffers(B, plan, dev)
+    P = out.labels.shape[1]
+    for t in (out.labels, out.start, out.nframes):
+        assert t.is_cuda and t.dtype == torch.int32 and t.is_contiguous() and tuple(t.shape) == (B, P), 'stream_emit: out'
+    assert out.score.dtype == torch.float32 and out.score.is_contiguous() and tuple(out.score.shape) == (B, P), 'stream_emit: out'
+    for t in (out.n_new_labels, out.status, out.total_frames):
+        _i32dev(t, B, 'stream_emit: out')
+    assert out.utt_score.dtype == torch.float32 and out.utt_score.numel() == B and out.utt_score.is_contiguous(), 'stream_emit: out'
+    a = StreamEmitArgs()
+    a.struct_size = C.sizeof(StreamEmitArgs)
+    a.S, a.B, a.Wl, a.C, a.Rr, a.samples_per_frame = int(S), B, plan.Wl, plan.C, plan.Rr, plan.samples_per_frame
+    a.Tw, a.P, a.blank = Tw, P, int(blank)
+    a.state, a.state_bytes = state.data_ptr(), state.numel() * state.element_size()
+    a.slots, a.flags, a.tokens, a.frame_score = slots.data_ptr(), flags.data_ptr(), tokens.data_ptr(), frame_score.data_ptr()
+    a.enc_lens, a.first_frame = enc_lens.data_ptr(), first_frame.data_ptr()
+    for n in ('labels', 'start', 'nframes', 'score', 'n_new_labels', 'status', 'total_frames', 'utt_score'):
+        setattr(a, n, getattr(out, n).data_ptr())
+    if out.tail_labels is not None:
+        assert out.tail_labels.dtype == torch.int32 and out.tail_labels.is_contiguous() and out.tail_labels.shape[0] == B, 'stream_emit: out'
+        _i32dev(out.tail_n, B, 'stream_emit: out')
+        a.Ptail, a.tail_labels, a.tail_n = out.tail_labels.shape[1], out.tail_labels.data_ptr(), out.tail_n.data_ptr()
+    with torch.cuda.device(dev):
+        _check(lib.qasr_stream_emit(_stream_ptr(stream), C.byref(a)), 'qasr_stream_emit')
+    return out
 
 
 class Engine:
