@@ -721,6 +721,67 @@ typedef struct qasr_stream_emit_args {
 } qasr_stream_emit_args;
 int qasr_stream_emit(void* stream, const qasr_stream_emit_args* args);
 
+/* ---- streaming at any sample rate: per-stream resampler state on the device -------------------------------------------
+ * In front of the sample ring above: PCM at the source's rate (int16 or float32, 1 .. 8 interleaved channels) is appended to a
+ * per-slot history of channel sums, and the outputs of the polyphase resampler that have become FINAL are written into the
+ * slot's sample ring, where qasr_stream_window / _emit find them as if they had been pushed.  Output i reads the input frames
+ * q - W + 1 .. q + W, q = floor(i M / L); once n frames have arrived, the first ready(n) = max(0, ceil((n - W) L / M)) outputs
+ * cannot change any more, and they equal qasr_resample over the whole stream on every byte.  A FLUSH row treats the frames
+ * behind the last one as zeros (as the end of an utterance does) and produces up to out_len(n) = ceil(n L / M).  Equal rates
+ * (L = M = 1, the channel mean only) count as W = 0.  The rule and the NumPy twin: qasr/stream_rs.py (RS_STREAM_RULES).
+ *   rs_state device memory of qasr_stream_rs_state_bytes(S, hcap) bytes, 16-byte aligned: per slot 16 32-bit words
+ *            (in_received i64, the slot's sample format + 1, zeros), then per slot a history of hcap 8-byte entries; input
+ *            frame k lives at entry k % hcap as its channel sum: int64 for int16 input, float64 (channels added in ascending
+ *            order) for float32 input.  Zeroed memory is S fresh streams.  0 bytes: S < 1, hcap < 4, no multiple of 4 or
+ *            above 2^26.  hcap = StreamResamplePlan.hcap (2 W + the most frames of one append, rounded up to a multiple of 4).
+ *   work     device memory of qasr_stream_rs_work_bytes(B) bytes, 16-byte aligned: one record of 8 32-bit words per row
+ *            (first output i64, count, sample format, in_received i64, slot, zero), written by the first launch and read by
+ *            the second.  0 bytes: B < 1.
+ *   blob     the packed table of qasr_resample (it passed qasr_resample_check); L, M, W repeat its header
+ *   flags    device i32 [B]: QASR_STREAM_BEGIN (forget the slot's stream block and resampler block first), QASR_STREAM_FLUSH
+ *   chunk    device s16 or f32 (dtype) [B][pitch frames][channels]; n_in device i32 [B] frames, clamped to 0 .. min(pitch,
+ *            max(1, floor(C M / L))) and then so that no history entry is overwritten that an output at or behind the
+ *            stream's `received` still reads (frames at or above floor(received M / L) - W + 1 stay; W = 0: at or above received)
+ *   out_limit device i32 [B]: at most this many outputs are produced (and at most C)
+ *   -> n_taken, n_out, status device i32 [B]: frames appended, outputs produced, 0 / 1 (frames were dropped because the
+ *            history is full) / 2 (no such slot: nothing done) / 3 (the slot holds the other sample format: nothing appended)
+ *            / 4 (the table's header disagrees with L, M, W: nothing done)
+ * Two launches: k_stream_rs_append (one work-group per row: the history, both counters, the record, the three outputs), then
+ * k_stream_rs_fir (tiles of 256 outputs per row: reads the record, the history and the table only, writes the sample ring).
+ * Nothing is read back; can be captured.
+ * QASR_ERR_ARG with nothing launched and nothing written: an unknown struct_size, a NULL among the pointers, what
+ * qasr_stream_push refuses about S, B, Wl, C, samples_per_frame and state_bytes, rs_state_bytes / work_bytes below the two
+ * functions, state / rs_state / work / blob not 16-byte aligned, blob_bytes != 128 + 4 * L * 2 W, channels outside
+ * 1 .. QASR_RESAMPLE_MAX_CHANNELS, an unknown dtype, L, M or W out of qasr_resample's range, hcap out of range or below 2 W
+ * (W = 0 for equal rates), pitch < 0 or above QASR_RESAMPLE_MAX_PITCH. */
+enum { QASR_STREAM_FLUSH = 4 };
+size_t qasr_stream_rs_state_bytes(int S, int hcap);
+size_t qasr_stream_rs_work_bytes(int B);
+typedef struct qasr_stream_rs_push_args {
+  uint32_t struct_size;        /* sizeof of this struct in the caller's header */
+  int32_t S, B, Wl, C, samples_per_frame;
+  int32_t dtype, channels;     /* dtype: QASR_PCM_S16 / QASR_PCM_F32 */
+  int32_t L, M, W, hcap;
+  void* state;                 /* the stream state of qasr_stream_push */
+  size_t state_bytes;
+  void* rs_state;
+  size_t rs_state_bytes;
+  void* work;
+  size_t work_bytes;
+  const void* blob;
+  size_t blob_bytes;
+  const int32_t* slots;
+  const int32_t* flags;
+  const int32_t* n_in;
+  const int32_t* out_limit;
+  const void* chunk;
+  int64_t pitch;               /* frames per chunk row */
+  int32_t* n_taken;
+  int32_t* n_out;
+  int32_t* status;
+} qasr_stream_rs_push_args;
+int qasr_stream_rs_push(void* stream, const qasr_stream_rs_push_args* args);
+
 /* ---- reserved engines: ragged batches without allocation, with graph replay ------------------------------------------
  * A data loader pads every batch to its own longest utterance (the reference's collate function), so (B, T) changes on
  * almost every call; qasr_engine_forward[_audio] then rebuilds its plan (device-synchronising frees + allocations) and,

@@ -1513,6 +1513,46 @@ int qasr_stream_emit(void* stream, const qasr_stream_emit_args* a) {
   return QASR_OK;
 }
 
+// ---- streaming at any sample rate (k_stream_rs_append / _fir, qasr_stream_rs.hip): the checks of include/qasr.h, two launches
+size_t qasr_stream_rs_state_bytes(int S, int hcap) { return stream_rs_state_bytes(S, hcap); }
+size_t qasr_stream_rs_work_bytes(int B) { return stream_rs_work_bytes(B); }
+
+int qasr_stream_rs_push(void* stream, const qasr_stream_rs_push_args* a) {
+  if (!a) return fail(QASR_ERR_ARG, "stream_rs_push: args is NULL");
+  if (a->struct_size != sizeof(qasr_stream_rs_push_args))
+    return fail(QASR_ERR_ARG, "stream_rs_push: struct_size %u is not %zu", a->struct_size, sizeof(qasr_stream_rs_push_args));
+  if (!a->state || !a->rs_state || !a->work || !a->blob || !a->slots || !a->flags || !a->n_in || !a->out_limit || !a->chunk ||
+      !a->n_taken || !a->n_out || !a->status)
+    return fail(QASR_ERR_ARG, "stream_rs_push: every pointer is required");
+  int rc = stream_geometry("stream_rs_push", a->S, a->B, a->Wl, a->C, 0, a->samples_per_frame, a->state_bytes);
+  if (rc) return rc;
+  if (a->channels < 1 || a->channels > QASR_RESAMPLE_MAX_CHANNELS)
+    return fail(QASR_ERR_ARG, "stream_rs_push: channels %d is outside 1 .. %d", a->channels, QASR_RESAMPLE_MAX_CHANNELS);
+  if (a->dtype != QASR_PCM_S16 && a->dtype != QASR_PCM_F32) return fail(QASR_ERR_ARG, "stream_rs_push: dtype %d is neither s16 nor f32", a->dtype);
+  if (!resample_ratio_ok(a->L, a->M, a->W))
+    return fail(QASR_ERR_ARG, "stream_rs_push: L %d / M %d, W %d (1 .. %d) or L * 2 W (<= %d) out of range", a->L, a->M, a->W,
+                QASR_RESAMPLE_MAX_W, QASR_RESAMPLE_MAX_ENTRIES);
+  const int Wf = (a->L == 1 && a->M == 1) ? 0 : a->W;
+  const size_t need_rs = stream_rs_state_bytes(a->S, a->hcap), need_work = stream_rs_work_bytes(a->B);
+  if (!need_rs || a->hcap < 2 * Wf)
+    return fail(QASR_ERR_ARG, "stream_rs_push: hcap %d must be a multiple of 4 in max(4, 2 W = %d) .. 2^26", a->hcap, 2 * Wf);
+  if (a->rs_state_bytes < need_rs)
+    return fail(QASR_ERR_ARG, "stream_rs_push: rs_state_bytes %zu, qasr_stream_rs_state_bytes gives %zu", a->rs_state_bytes, need_rs);
+  if (a->work_bytes < need_work)
+    return fail(QASR_ERR_ARG, "stream_rs_push: work_bytes %zu, qasr_stream_rs_work_bytes gives %zu", a->work_bytes, need_work);
+  if ((((uintptr_t)a->state | (uintptr_t)a->rs_state | (uintptr_t)a->work | (uintptr_t)a->blob) & 15) != 0)
+    return fail(QASR_ERR_ARG, "stream_rs_push: state, rs_state, work and blob must be 16-byte aligned");
+  if (a->blob_bytes != 128 + 8 * (size_t)a->L * (size_t)a->W)
+    return fail(QASR_ERR_ARG, "stream_rs_push: blob must be 128 + 4 * L * 2 W = %zu bytes, got %zu", 128 + 8 * (size_t)a->L * (size_t)a->W,
+                a->blob_bytes);
+  if (a->pitch < 0 || a->pitch > QASR_RESAMPLE_MAX_PITCH)
+    return fail(QASR_ERR_ARG, "stream_rs_push: pitch %lld is outside 0 .. 2^38", (long long)a->pitch);
+  rc = launch_stream_rs_push((hipStream_t)stream, *a);
+  if (rc) return fail(rc, "stream_rs_push: launch");
+  HIPCHK(hipGetLastError());
+  return QASR_OK;
+}
+
 int qasr_engine_attach_ctc(qasr_engine* e, float* frame_score, const qasr_ctc_out* out, int use_lens) {
   if (!e) return fail(QASR_ERR_ARG, "attach_ctc: engine is NULL");
   if (frame_score || out) {

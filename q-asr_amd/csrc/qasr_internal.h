@@ -181,6 +181,10 @@ size_t stream_state_bytes(int S, int Wl, int C);
 int launch_stream_push(hipStream_t s, const qasr_stream_push_args& a);
 int launch_stream_window(hipStream_t s, const qasr_stream_window_args& a);
 int launch_stream_emit(hipStream_t s, const qasr_stream_emit_args& a);
+// qasr_stream_rs.hip: streaming at any sample rate (k_stream_rs_append, k_stream_rs_fir); checked by qasr_stream_rs_push
+size_t stream_rs_state_bytes(int S, int hcap);
+size_t stream_rs_work_bytes(int B);
+int launch_stream_rs_push(hipStream_t s, const qasr_stream_rs_push_args& a);
 // qasr_ragged.hip: the bucket policy of reserved engines and their one eager launch per call (k_ragged_stage)
 #define QASR_RAGGED_TILE 128          /* every bucket edge is a multiple of the largest frame tile */
 #define QASR_SHAPE_B 0                /* shape block, i32: rows of the batch, */

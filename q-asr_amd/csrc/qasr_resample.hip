@@ -14,69 +14,13 @@
 // A frame at or behind in_lens[b] is never read.  Every output row is written to its pitch (zeros behind out_len); work-group
 // 0 of a row writes out_lens[b].  Global memory sees plain vector stores; no atomics; nothing is read back on the host.
 #include "qasr_internal.h"
+#include "qasr_resample_dev.h"
 
 namespace qasr {
 
 #define RS_NT 256
 #define RS_TILE 256
 #define RS_STAGE 4096
-#define RS_MAGIC 0x31535251
-
-struct ResampleP {
-  const int32_t* blob;          // header (32 words) + table [2 W][L]
-  const void* in;               // int16 or float32 [B][in_pitch][ch]
-  const int32_t* in_lens;       // [B] frames
-  float* out;                   // [B][out_pitch]
-  int32_t* out_lens;            // [B]
-  long long in_pitch, out_pitch;
-  int L, M, W, ch;
-};
-
-template <typename T>
-struct RsAcc;
-template <>
-struct RsAcc<int16_t> {
-  typedef long long acc_t;
-  typedef int32_t stage_t;
-};
-template <>
-struct RsAcc<float> {
-  typedef double acc_t;
-  typedef double stage_t;
-};
-
-// frame k of a row as the sum of its channels (k inside [0, n) is the caller's business)
-__device__ __forceinline__ int32_t rs_frame(const int16_t* row, long long k, int ch) {
-  const int16_t* f = row + k * ch;
-  int32_t v = f[0];
-  for (int c = 1; c < ch; ++c) v += f[c];
-  return v;
-}
-__device__ __forceinline__ double rs_frame(const float* row, long long k, int ch) {
-  const float* f = row + k * ch;
-  double v = (double)f[0];
-  for (int c = 1; c < ch; ++c) v = v + (double)f[c];
-  return v;
-}
-
-__device__ __forceinline__ long long rs_tap(long long acc, int32_t c, int32_t x) { return acc + (long long)c * (long long)x; }
-__device__ __forceinline__ double rs_tap(double acc, int32_t c, double x) {
-#pragma clang fp contract(off)
-  const double hq = (double)c * 9.313225746154785e-10;      // 2^-30: exact
-  const double pr = hq * x;
-  return acc + pr;
-}
-
-__device__ __forceinline__ float rs_finish(long long acc, int ch) {
-  return (float)((double)acc / ((double)ch * 35184372088832.0));       // ch * 2^45
-}
-__device__ __forceinline__ float rs_finish(double acc, int ch) { return (float)(acc / (double)ch); }
-
-// the header lies in device memory; the launch repeats L, M, W: a disagreement ends the row empty
-__device__ __forceinline__ bool rs_header_ok(const ResampleP& p) {
-  const int32_t* h = p.blob;
-  return h[0] == RS_MAGIC && h[3] == p.L && h[4] == p.M && h[5] == p.W;
-}
 
 template <typename T, bool STAGED>
 __global__ void __launch_bounds__(RS_NT) k_resample(ResampleP p) {

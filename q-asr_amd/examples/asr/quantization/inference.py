@@ -94,7 +94,9 @@ def main():
                    help="(extension, needs --window_s) overlap of neighbouring windows (default 4.0)")
     p.add_argument("--stream_chunk_s", type=float, default=None, metavar='SECONDS',
                    help="(extension) play every manifest entry through a streaming session (EncDecCTCModel.stream), --batch_size "
-                        "streams at a time in chunks of this many seconds; hypotheses and WER come from the sessions' final results")
+                        "streams at a time in chunks of this many seconds; hypotheses and WER come from the sessions' final results.  "
+                        "With --input_rate (and --resample_quality) the streams carry int16 PCM at that rate and every stream is "
+                        "resampled on the device as it arrives")
     p.add_argument("--stream_left_s", type=float, default=None, metavar='SECONDS',
                    help="(extension, needs --stream_chunk_s) context in front of every chunk (default 4.0)")
     p.add_argument("--stream_right_s", type=float, default=None, metavar='SECONDS',
@@ -103,9 +105,9 @@ def main():
     if (args.stream_left_s is not None or args.stream_right_s is not None) and args.stream_chunk_s is None:
         p.error('--stream_left_s and --stream_right_s need --stream_chunk_s')
     if args.stream_chunk_s is not None:
-        for flag in ('window_s', 'beam_width', 'input_rate', 'align'):
+        for flag in ('window_s', 'beam_width', 'align'):
             if getattr(args, flag) is not None:
-                p.error(f'--stream_chunk_s does not go with --{flag}: a streaming session is greedy, at the model\'s rate')
+                p.error(f'--stream_chunk_s does not go with --{flag}: a streaming session is greedy and steps by chunks')
     if args.overlap_s is not None and args.window_s is None:
         p.error('--overlap_s needs --window_s')
     if args.window_s is not None and args.timestamps and args.beam_width is not None:
@@ -209,9 +211,10 @@ def main():
                 try:
                     stream_sess = asr_model.stream(max_streams=args.batch_size, chunk_s=args.stream_chunk_s, tail=False,
                                                    left_s=4.0 if args.stream_left_s is None else args.stream_left_s,
-                                                   right_s=0.96 if args.stream_right_s is None else args.stream_right_s)
+                                                   right_s=0.96 if args.stream_right_s is None else args.stream_right_s,
+                                                   input_rate=args.input_rate)       # int16 PCM: resampled per stream on the device
                 except ValueError as e:
-                    p.error(f'--stream_chunk_s / --stream_left_s / --stream_right_s: {e}')
+                    p.error(f'--stream_chunk_s / --stream_left_s / --stream_right_s / --input_rate: {e}')
             stream_hyps = asr_model.decode_stream(signal, batch[1], session=stream_sess)
             for h in stream_hyps:
                 hyps.append(h.text)

@@ -688,7 +688,8 @@ class EncDecCTCModel(nn.Module):
         lp = self._long_plan([1])
         return qstream.StreamPlan(chunk_s, left_s, right_s, lp.sample_rate, lp.samples_per_frame, lp.frames_of)
 
-    def stream(self, max_streams=32, chunk_s=0.96, left_s=4.0, right_s=0.96, tail=True, sample_rate=None, beam_width=None):
+    def stream(self, max_streams=32, chunk_s=0.96, left_s=4.0, right_s=0.96, tail=True, sample_rate=None, beam_width=None,
+               input_rate=None, channels=1):
         """A streaming session (an extension; NeMo's buffered streaming, the FrameBatchASR idea, for many streams at once):
 
             sess = model.stream(max_streams=32, chunk_s=0.96, left_s=4.0, right_s=0.96)
@@ -714,11 +715,25 @@ class EncDecCTCModel(nn.Module):
         are derived per batch, so there it does.
 
         Normalisation is per window; the first left_s seconds of a stream see less context; the latency is chunk_s +
-        right_s plus the step; the defaults are untried on speech.  Refused: sample_rate other than the model's (a streaming
-        resampler needs filter state), beam_width (no beam search across steps)."""
-        if sample_rate is not None and int(sample_rate) != int(self.preprocessor._sample_rate):
-            raise ValueError(f'stream: sample_rate {sample_rate} is not the model\'s {int(self.preprocessor._sample_rate)}: '
-                             'resampling a stream needs filter state across pushes, which is not built')
+        right_s plus the step; the defaults are untried on speech.
+
+        input_rate=R, channels=C: the streams carry PCM at R Hz - int16 or float32, C interleaved channels (1 .. 8) - as
+        push(slots, signal[B, n * C], lengths in frames).  Every stream keeps its own resampler state on the device next
+        to its ring (k_stream_rs_append, k_stream_rs_fir; qasr.stream_rs states the rule): the filter is
+        model.resample_quality's, a slot keeps the sample format of its first push, and however the pushes are sliced
+        the samples that reach the stream's ring are qasr.resample.resample_host of the whole stream on every byte - so
+        the session gives what a session at the model's rate gives for the offline resampler's output.  Times stay seconds
+        of the stream (frames are counted at the model's rate).  A resampled sample is final once the W input frames
+        behind it have arrived, so the filter adds W / R seconds of latency (8.5 ms at 8 kHz 'best', 4.2 ms at 48 kHz
+        'best'); close() flushes that tail, and the updates of steps it completes are kept in sess.closing_updates.
+        input_rate=None, or the model's rate with channels=1, is the plain session.
+
+        Refused: sample_rate other than the model's (here it names the model's rate: give the source's as input_rate=),
+        a rate or filter the resampler refuses, channels outside 1 .. 8, beam_width (no beam search across steps)."""
+        target = int(self.preprocessor._sample_rate)
+        if sample_rate is not None and int(sample_rate) != target:
+            raise ValueError(f'stream: sample_rate {sample_rate} is not the model\'s {target}: sample_rate names the model\'s rate '
+                             'here; give the rate of the audio as input_rate=')
         if beam_width is not None:
             raise ValueError('stream: beam_width is not supported: the incremental collapse is greedy')
         if int(max_streams) < 1:
@@ -727,10 +742,26 @@ class EncDecCTCModel(nn.Module):
             plan = self._stream_plan(chunk_s, left_s, right_s)
         except ValueError as e:
             raise ValueError(f'stream: {e}') from None
-        return StreamSession(self, int(max_streams), plan, bool(tail))
+        from qasr import resample as qresample, stream_rs as qsrs
+        if not 1 <= int(channels) <= qresample.MAX_CHANNELS:
+            raise ValueError(f'stream: channels must be 1 .. {qresample.MAX_CHANNELS}, got {channels}')
+        if input_rate is None and int(channels) != 1:
+            raise ValueError('stream: channels needs input_rate (the rate of the interleaved PCM)')
+        rs_plan = None
+        if input_rate is not None and not (int(input_rate) == input_rate and int(input_rate) == target and int(channels) == 1):
+            key = (int(input_rate) if int(input_rate) == input_rate else input_rate, target, self.resample_quality)
+            plans = self.__dict__.setdefault('_resample_plans', {})
+            try:
+                if key not in plans:
+                    plans[key] = qresample.ResamplePlan(input_rate, target, self.resample_quality)
+                rs_plan = qsrs.StreamResamplePlan(plan, plans[key], int(channels))
+            except ValueError as e:
+                raise ValueError(f'stream: input_rate {input_rate}: {e}') from None
+        return StreamSession(self, int(max_streams), plan, bool(tail), rs_plan)
 
     @torch.no_grad()
-    def decode_stream(self, input_signal, input_signal_length, chunk_s=0.96, left_s=4.0, right_s=0.96, session=None):
+    def decode_stream(self, input_signal, input_signal_length, chunk_s=0.96, left_s=4.0, right_s=0.96, session=None, input_rate=None,
+                      channels=1):
         """A batch of complete recordings played through a streaming session, all rows side by side in pushes of chunk_s
         seconds (what inference.py --stream_chunk_s does): List[qasr.ctc.Hypothesis], one per row - the hypotheses
         stream() gives for that audio, which do not depend on the size of the pushes.
@@ -738,18 +769,23 @@ class EncDecCTCModel(nn.Module):
         session=<a session of this model with at least B free slots> plays the batch through it and leaves it open.
         Without one, a session is opened and closed per call - and on the calibrated model that is not free: taking and
         restoring the reservation closes the reserved engine each time (a caller's own included), so the engine is built
-        and its graph captured again for every call.  A caller with many batches holds one session across them."""
-        if input_signal.dim() != 2:
-            raise ValueError(f'decode_stream: input_signal must be [B, S], got {tuple(input_signal.shape)}')
+        and its graph captured again for every call.  A caller with many batches holds one session across them.
+
+        input_rate=R, channels=C: the recordings are PCM at R Hz, [B, S * C] interleaved, lengths in frames, as for
+        stream(); a session passed in carries its own."""
+        ch = session.rs_plan.channels if session is not None and session.rs_plan is not None else int(channels)
+        if input_signal.dim() != 2 or ch < 1 or input_signal.shape[1] % ch:
+            raise ValueError(f'decode_stream: input_signal must be [B, S * channels], got {tuple(input_signal.shape)} for {channels} channels')
         B = input_signal.shape[0]
-        lens = [min(int(n), input_signal.shape[1]) for n in input_signal_length.tolist()]
-        sess = session if session is not None else self.stream(max_streams=B, chunk_s=chunk_s, left_s=left_s, right_s=right_s, tail=False)
+        lens = [min(int(n), input_signal.shape[1] // ch) for n in input_signal_length.tolist()]
+        sess = session if session is not None else self.stream(max_streams=B, chunk_s=chunk_s, left_s=left_s, right_s=right_s, tail=False,
+                                                               input_rate=input_rate, channels=ch)
         try:
             slots = [sess.open() for _ in range(B)]
-            C = sess.plan.C
+            C = sess.plan.C if sess.rs_plan is None else sess.rs_plan.Ain     # about chunk_s of audio per push
             for off in range(0, max(lens + [0]), C):
                 live = [b for b in range(B) if off < lens[b]]
-                sess.push([slots[b] for b in live], input_signal[live, off:off + C], [min(C, lens[b] - off) for b in live])
+                sess.push([slots[b] for b in live], input_signal[live, off * ch:(off + C) * ch], [min(C, lens[b] - off) for b in live])
             return [sess.close(s) for s in slots]
         finally:
             if session is None:
@@ -1100,8 +1136,10 @@ class StreamSession:
     """EncDecCTCModel.stream(): the live streams of one model.  The host keeps counts it already has (samples per stream, the
     deltas read back so far); everything a step computes from lives on the device."""
 
-    def __init__(self, model, max_streams, plan, tail):
+    def __init__(self, model, max_streams, plan, tail, rs_plan=None):
         self.model, self.S, self.plan, self.tail = model, max_streams, plan, tail
+        self.rs_plan = rs_plan               # qasr.stream_rs.StreamResamplePlan: the streams carry PCM at another rate
+        self.closing_updates = []            # (resampled streams) the StreamUpdates of steps the last close() completed
         self._open = {}                      # slot -> dict(received, begin, deltas)
         self._dev = None                     # decided by the first push: a cuda device, or 'cpu'
         self._state = None
@@ -1142,17 +1180,25 @@ class StreamSession:
         slot = int(slot)
         if not 0 <= slot < self.S or slot in self._open:
             raise ValueError(f'stream: slot {slot} is already open or outside 0 .. max_streams - 1 = {self.S - 1}')
-        self._open[slot] = dict(received=0, begin=True, deltas=[])
+        self._open[slot] = dict(received=0, begin=True, deltas=[], in_received=0, fmt=None)
         return slot
 
     # ---- the three steps, on the device or as the twins
     def _setup(self, device):
-        from qasr import engine as qengine, stream as qstream
+        from qasr import engine as qengine, stream as qstream, stream_rs as qsrs
         if self._dev is not None:
             if self._dev != device:
                 raise ValueError(f'stream: the session runs on {self._dev}, got a tensor on {device}')
             return
         self._dev = device
+        if self.rs_plan is not None:
+            if device.type == 'cuda':
+                self._rs_state = qengine.stream_rs_state(self.S, self.rs_plan, device)
+                self._rs_work = qengine.stream_rs_work(self.S, device)
+                self._rs_out = tuple(torch.empty(self.S, device=device, dtype=torch.int32) for _ in range(3))
+                qengine.resample_plan(self.rs_plan.resample_plan, device)        # the table's upload, outside any capture
+            else:
+                self._rs_state = qsrs.ResampleState(self.S, self.rs_plan)
         if device.type == 'cuda':
             self._state = qengine.stream_state(self.S, self.plan, device)
             self._win = (torch.empty(self.S, self.plan.Wl, device=device), torch.empty(self.S, device=device, dtype=torch.int32),
@@ -1170,6 +1216,84 @@ class StreamSession:
             qengine.stream_push(self._state, self.S, self.plan, self._i32(slots), self._i32(flags), self._i32(n_new), chunk)
         else:
             qstream.push_host(self._state, slots, flags, n_new, chunk.numpy())
+
+    def _push_rs(self, slots, flags, n_in, out_limit, chunk):
+        """one qasr_stream_rs_push (or its twin): append, then produce; nothing is read back"""
+        from qasr import engine as qengine, stream_rs as qsrs
+        if self._dev.type == 'cuda':
+            B = len(slots)
+            qengine.stream_rs_push(self._state, self._rs_state, self.S, self.rs_plan, self._i32(slots), self._i32(flags), self._i32(n_in),
+                                   self._i32(out_limit), chunk, work=self._rs_work, out=tuple(t[:B] for t in self._rs_out))
+        else:
+            qsrs.push_rs_host(self._state, self._rs_state, slots, flags, n_in, out_limit, chunk.numpy())
+
+    def _updates(self, stepping):
+        """a step for the slots that filled a chunk; its deltas are kept and returned as StreamUpdates"""
+        from qasr import ctc as qctc
+        vocab, spf_s, ups = self.model.decoder.vocabulary, self.plan.seconds_per_frame(), []
+        for s, (lab, start, nfr, sc, _, tl) in zip(stepping, self._step(stepping, False)):
+            self._open[s]['deltas'].append((lab, start, nfr, sc))
+            ups.append(qctc.StreamUpdate(s, lab.tolist(), ''.join(vocab[i] for i in lab.tolist()),
+                                         (start.astype(np.float64) * spf_s).tolist(),
+                                         ((start + nfr).astype(np.float64) * spf_s).tolist(),
+                                         sc.astype(np.float64).tolist(), ''.join(vocab[i] for i in tl)))
+        return ups
+
+    def _rounds_rs(self, slots, n_in, chunk, flush=False):
+        """The protocol of a resampled session for one piece (at most Ain frames per row): append and produce up to the
+        chunk's end, step the rows that filled a chunk, and produce and step again until no ready output is left.  The
+        host mirrors in_received and received with the plan's integer formulas."""
+        from qasr import stream as qstream, stream_rs as qsrs
+        rp, C, ch, updates = self.rs_plan, self.plan.C, self.rs_plan.channels, []
+        while slots:
+            flags, limit, stepping, more = [], [], [], []
+            for s, n in zip(slots, n_in):
+                st = self._open[s]
+                flags.append((qstream.BEGIN if st['begin'] else 0) | (qsrs.FLUSH if flush else 0))
+                limit.append(C - st['received'] % C)
+                st['begin'] = False
+                st['in_received'] += n
+                target = rp.out_len(st['in_received']) if flush else rp.ready(st['in_received'])
+                k = max(0, min(target - st['received'], limit[-1], C))
+                st['received'] += k
+                if k and st['received'] % C == 0:
+                    stepping.append(s)
+                if target > st['received']:
+                    more.append(s)
+            self._push_rs(slots, flags, n_in, limit, chunk)
+            if stepping:
+                updates += self._updates(stepping)
+            slots, n_in = more, [0] * len(more)
+            chunk = chunk[:len(more), :ch] if len(more) else chunk             # produce only: the rows' frames are not read
+        return updates
+
+    def _push_resampled(self, slots, signal, lengths):
+        rp, ch = self.rs_plan, self.rs_plan.channels
+        if signal.shape[1] % ch:
+            raise ValueError(f'stream: a signal row of {signal.shape[1]} samples is no multiple of {ch} channels')
+        S = signal.shape[1] // ch
+        lens = [S] * len(slots) if lengths is None else [int(x) for x in torch.as_tensor(lengths).tolist()]
+        if len(lens) != len(slots) or any(not 0 <= n <= S for n in lens):
+            raise ValueError(f'stream: lengths {lens} must be one per slot, each within 0 .. {S} frames')
+        for s in slots:
+            fmt = self._open[s]['fmt']
+            if fmt is not None and fmt != signal.dtype:
+                raise ValueError(f'stream: slot {s} carries the sample format {fmt} since its first push, got {signal.dtype}')
+        self._setup(signal.device)
+        for s in slots:
+            self._open[s]['fmt'] = signal.dtype
+        updates, off = [], 0
+        while off < max(lens + [0]):
+            rows = [i for i in range(len(slots)) if off < lens[i]]
+            n_in = [min(rp.Ain, lens[i] - off) for i in rows]
+            w = max(n_in)
+            if len(rows) == len(slots):
+                chunk = signal[:, off * ch:(off + w) * ch]
+            else:
+                chunk = signal[rows, off * ch:(off + w) * ch]
+            updates += self._rounds_rs([slots[i] for i in rows], n_in, chunk.contiguous())
+            off += rp.Ain
+        return updates
 
     def _step(self, slots, end):
         """one step for `slots`: window -> forward -> emit; returns the rows' deltas as qasr.stream.StepRow-like tuples"""
@@ -1207,18 +1331,22 @@ class StreamSession:
 
     def push(self, slots, signal, lengths=None):
         """signal [B, n] float32 or int16 at the model's rate, lengths [B] (default: n each), slots: B distinct open slots.
-        Returns the StreamUpdates of the steps this audio completed, in the order they ran."""
-        from qasr import ctc as qctc, stream as qstream
+        A session opened with input_rate= takes [B, n * channels] interleaved PCM at that rate, lengths in frames; a slot
+        keeps the sample format of its first push.  Returns the StreamUpdates of the steps this audio completed, in the
+        order they ran."""
+        from qasr import stream as qstream
         slots = [int(s) for s in (slots.tolist() if torch.is_tensor(slots) else slots)]
         if signal.dim() != 2 or signal.shape[0] != len(slots) or signal.dtype not in (torch.float32, torch.int16):
             raise ValueError(f'stream: signal must be float32 or int16 [{len(slots)}, n], got {signal.dtype} {tuple(signal.shape)}')
         if len(set(slots)) != len(slots) or any(s not in self._open for s in slots):
             raise ValueError(f'stream: slots {slots} must be distinct and open (open slots: {sorted(self._open)})')
+        if self.rs_plan is not None:
+            return self._push_resampled(slots, signal, lengths)
         lens = [signal.shape[1]] * len(slots) if lengths is None else [int(x) for x in torch.as_tensor(lengths).tolist()]
         if len(lens) != len(slots) or any(not 0 <= n <= signal.shape[1] for n in lens):
             raise ValueError(f'stream: lengths {lens} must be one per slot, each within 0 .. {signal.shape[1]}')
         self._setup(signal.device)
-        C, vocab, spf_s = self.plan.C, self.model.decoder.vocabulary, self.plan.seconds_per_frame()
+        C = self.plan.C
         pieces = [qstream.split_pushes(self._open[s]['received'] % C, n, C) for s, n in zip(slots, lens)]
         offs = [0] * len(slots)
         updates = []
@@ -1240,12 +1368,7 @@ class StreamSession:
                 if st['received'] % C == 0:
                     stepping.append(s)
             if stepping:
-                for s, (lab, start, nfr, sc, _, tl) in zip(stepping, self._step(stepping, False)):
-                    self._open[s]['deltas'].append((lab, start, nfr, sc))
-                    updates.append(qctc.StreamUpdate(s, lab.tolist(), ''.join(vocab[i] for i in lab.tolist()),
-                                                     (start.astype(np.float64) * spf_s).tolist(),
-                                                     ((start + nfr).astype(np.float64) * spf_s).tolist(),
-                                                     sc.astype(np.float64).tolist(), ''.join(vocab[i] for i in tl)))
+                updates += self._updates(stepping)
         return updates
 
     def close(self, slot):
@@ -1255,7 +1378,12 @@ class StreamSession:
         slot = int(slot)
         if slot not in self._open:
             raise ValueError(f'stream: slot {slot} is not open (open slots: {sorted(self._open)})')
-        st = self._open.pop(slot)
+        st = self._open[slot]
+        self.closing_updates = []
+        if self.rs_plan is not None and st['in_received'] > 0:     # the filter's tail: FLUSH rounds, stepping when a chunk fills
+            zero = torch.zeros(1, self.rs_plan.channels, dtype=st['fmt'], device=self._dev)
+            self.closing_updates = self._rounds_rs([slot], [0], zero, flush=True)
+        self._open.pop(slot)
         utt = 0.0
         if st['received'] > 0:               # (a stream that never received a sample has nothing to run)
             lab, start, nfr, sc, utt, _ = self._step([slot], True)[0]

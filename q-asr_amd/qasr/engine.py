@@ -23,6 +23,7 @@ SYMBOLS = ['qasr_blob_check', 'qasr_engine_create', 'qasr_engine_create_ex', 'qa
            'qasr_ragged_bucket_frames', 'qasr_ragged_envelope_frames',
            'qasr_resample_check', 'qasr_resample', 'qasr_resample_out_samples', 'qasr_longform_cut', 'qasr_longform_stitch',
            'qasr_stream_state_bytes', 'qasr_stream_push', 'qasr_stream_window', 'qasr_stream_emit',
+           'qasr_stream_rs_state_bytes', 'qasr_stream_rs_work_bytes', 'qasr_stream_rs_push',
            'qasr_last_error', 'qasr_version']
 
 _lib = None
@@ -187,6 +188,12 @@ def load_library():
         lib.qasr_stream_push.argtypes = [vp, C.POINTER(StreamPushArgs)]
         lib.qasr_stream_window.argtypes = [vp, C.POINTER(StreamWindowArgs)]
         lib.qasr_stream_emit.argtypes = [vp, C.POINTER(StreamEmitArgs)]
+    if hasattr(lib, 'qasr_stream_rs_push'):     # (likewise)
+        lib.qasr_stream_rs_state_bytes.argtypes = [i32, i32]
+        lib.qasr_stream_rs_state_bytes.restype = sz
+        lib.qasr_stream_rs_work_bytes.argtypes = [i32]
+        lib.qasr_stream_rs_work_bytes.restype = sz
+        lib.qasr_stream_rs_push.argtypes = [vp, C.POINTER(StreamRsPushArgs)]
     lib.qasr_debug_prof.argtypes = [vp]
     lib.qasr_debug_timeline.argtypes = [vp, sz]
     lib.qasr_sep_layer.argtypes = [vp, C.POINTER(SepLayerArgs), C.c_char_p, sz]
@@ -1001,6 +1008,77 @@ def stream_push(state, S, plan, slots, flags, n_new, chunk, stream=None):
     a.chunk, a.pitch = x.data_ptr(), (x.stride(0) if B > 1 else x.shape[1])
     with torch.cuda.device(state.device):
         _check(lib.qasr_stream_push(_stream_ptr(stream), C.byref(a)), 'qasr_stream_push')
+
+
+class StreamRsPushArgs(C.Structure):
+    """qasr_stream_rs_push_args (include/qasr.h)"""
+    _fields_ = ([('struct_size', C.c_uint32)] +
+                [(n, C.c_int32) for n in ('S', 'B', 'Wl', 'C', 'samples_per_frame', 'dtype', 'channels', 'L', 'M', 'W', 'hcap')] +
+                [('state', C.c_void_p), ('state_bytes', C.c_size_t), ('rs_state', C.c_void_p), ('rs_state_bytes', C.c_size_t),
+                 ('work', C.c_void_p), ('work_bytes', C.c_size_t), ('blob', C.c_void_p), ('blob_bytes', C.c_size_t)] +
+                [(n, C.c_void_p) for n in ('slots', 'flags', 'n_in', 'out_limit', 'chunk')] + [('pitch', C.c_int64)] +
+                [(n, C.c_void_p) for n in ('n_taken', 'n_out', 'status')])
+
+
+def stream_rs_state(S, rs_plan, device):
+    """Zeroed resampler state of S fresh streams under a qasr.stream_rs.StreamResamplePlan: an int32 tensor of
+    qasr_stream_rs_state_bytes(S, hcap) / 4 words (S blocks of 16 words, then S histories of hcap 8-byte entries)."""
+    lib = load_library()
+    n = int(lib.qasr_stream_rs_state_bytes(int(S), rs_plan.hcap))
+    if n == 0:
+        raise ValueError(f'stream_rs_state: S {S}, hcap {rs_plan.hcap} out of range')
+    return torch.zeros(n // 4, device=device, dtype=torch.int32)
+
+
+def stream_rs_work(B, device):
+    """the workspace of qasr_stream_rs_push for up to B rows (qasr_stream_rs_work_bytes)"""
+    return torch.zeros(int(load_library().qasr_stream_rs_work_bytes(int(B))) // 4, device=device, dtype=torch.int32)
+
+
+def stream_rs_args(state, rs_state, S, rs_plan, slots, flags, n_in, out_limit, chunk, work=None, out=None):
+    """the filled qasr_stream_rs_push_args of stream_rs_push (the tensors it points to are kept alive on it)"""
+    lib = load_library()
+    plan, rp, ch = rs_plan.stream_plan, rs_plan.resample_plan, rs_plan.channels
+    if chunk.dim() != 2 or chunk.dtype not in (torch.float32, torch.int16) or not chunk.is_cuda or chunk.shape[1] % ch:
+        raise ValueError(f'stream_rs_push: chunk must be a cuda float32 or int16 tensor [B, n * {ch}], got {chunk.dtype} {tuple(chunk.shape)}')
+    B, dev = chunk.shape[0], state.device
+    x = chunk if chunk.stride(1) == 1 and (B == 1 or chunk.stride(0) % ch == 0) else chunk.contiguous()
+    for t, w in ((slots, 'slots'), (flags, 'flags'), (n_in, 'n_in'), (out_limit, 'out_limit')):
+        _i32dev(t, B, 'stream_rs_push: ' + w)
+    if work is None:
+        work = stream_rs_work(B, dev)
+    if out is None:
+        out = tuple(torch.empty(B, device=dev, dtype=torch.int32) for _ in range(3))
+    for t in out:
+        _i32dev(t, B, 'stream_rs_push: out')
+    blob = resample_plan(rp, dev)
+    a = StreamRsPushArgs()
+    a.struct_size = C.sizeof(StreamRsPushArgs)
+    a.S, a.B, a.Wl, a.C, a.samples_per_frame = int(S), B, plan.Wl, plan.C, plan.samples_per_frame
+    a.dtype, a.channels = (PCM_S16 if x.dtype == torch.int16 else PCM_F32), ch
+    a.L, a.M, a.W, a.hcap = rp.L, rp.M, rp.W, rs_plan.hcap
+    a.state, a.state_bytes = state.data_ptr(), state.numel() * state.element_size()
+    a.rs_state, a.rs_state_bytes = rs_state.data_ptr(), rs_state.numel() * rs_state.element_size()
+    a.work, a.work_bytes = work.data_ptr(), work.numel() * work.element_size()
+    a.blob, a.blob_bytes = blob.data_ptr(), blob.numel()
+    a.slots, a.flags, a.n_in, a.out_limit = slots.data_ptr(), flags.data_ptr(), n_in.data_ptr(), out_limit.data_ptr()
+    a.chunk, a.pitch = x.data_ptr(), (x.stride(0) // ch if B > 1 else x.shape[1] // ch)
+    a.n_taken, a.n_out, a.status = (t.data_ptr() for t in out)
+    a._keep = (x, work, blob, out)
+    return a
+
+
+def stream_rs_push(state, rs_state, S, rs_plan, slots, flags, n_in, out_limit, chunk, work=None, out=None, stream=None):
+    """qasr_stream_rs_push: chunk int16 or float32 [B, n * channels] (interleaved, at the source's rate) appended to the slots'
+    histories, and the resampled samples that became final written to the slots' sample rings; slots / flags / n_in /
+    out_limit: cuda int32 [B].  Returns (n_taken, n_out, status), cuda int32 [B] (`out`: the same triple, caller-owned).
+    k_stream_rs_append and k_stream_rs_fir, two launches on the current stream, nothing read back; equal to
+    qasr.stream_rs.push_rs_host byte for byte, both states included.  The table is uploaded by the first call of a rate
+    (engine.resample_plan): make that call outside a capture."""
+    a = stream_rs_args(state, rs_state, S, rs_plan, slots, flags, n_in, out_limit, chunk, work, out)
+    with torch.cuda.device(state.device):
+        _check(load_library().qasr_stream_rs_push(_stream_ptr(stream), C.byref(a)), 'qasr_stream_rs_push')
+    return a._keep[3]
 
 
 def stream_window(state, S, plan, slots, out=None, stream=None):
