@@ -721,6 +721,83 @@ typedef struct qasr_stream_emit_args {
 } qasr_stream_emit_args;
 int qasr_stream_emit(void* stream, const qasr_stream_emit_args* args);
 
+/* ---- streaming beam search: per-stream beam state and fixed-lag commit on the device -------------------------------------
+ * The prefix beam search of qasr_ctc_beam / qasr_ctc_beam_lm (lm == NULL: without a model) over the frames that a streaming
+ * step makes final, with the beam of every slot kept on the device between steps.  The rule, the state layout and the NumPy
+ * twin are qasr/stream_beam.py (STREAM_BEAM_RULES), which k_stream_beam follows byte for byte, state block and ring included.
+ * Text becomes final by a fixed-lag commit that prunes: after every GLOBAL frame t with (t + 1) % K == 0 and h = t - Lg >= 0
+ * the labels of the best entry whose trie node was created at a frame <= h are committed, and every entry whose labels up to
+ * that horizon differ is dropped.  Pinned: the equality with the twin; that the steps of ANY slicing of a stream, concatenated,
+ * equal the whole-stream search (lagged_search_host) on every byte; that with Lg >= the stream's length the END rows equal
+ * qasr_ctc_beam[_lm] over the same candidates.  Accuracy on speech, and the default lag, are not pinned.
+ *   state       the stream state of qasr_stream_push / _emit, READ-ONLY here (frames_done, received): launch this call after
+ *               qasr_ctc_topn over the window's log-probabilities and BEFORE qasr_stream_emit, which advances frames_done
+ *   beam_state  device memory of qasr_stream_beam_state_bytes(S, beam_width, F) bytes, 16-byte aligned: per slot 16 header
+ *               words (live entries, commit_len, frames_done, 1 once stepped), 20 * beam_width words of entries, then a ring of
+ *               F rows x beam_width (parent node, label) pairs; node t * beam_width + r lives in row t % F.  Zeroed memory is S
+ *               fresh streams.  0 bytes: S < 1, beam_width outside 1 .. QASR_BEAM_MAX_WIDTH, F outside 1 ..
+ *               QASR_STREAM_BEAM_MAX_RING.  F >= Lg + K rows keep every live node (StreamBeamPlan derives it).
+ *   cand_id, cand_q  i32 [B][Tw][N] of the windows (qasr_ctc_topn); enc_lens, first_frame, slots as for qasr_stream_emit
+ *   flags       QASR_STREAM_BEGIN: the slot's beam is reset to the single empty entry first; QASR_STREAM_END: after the last
+ *               final frame the unfinished-word term (word-mode models) and the n-best are written
+ *   -> labels, frames i32 [B][P]: the step's newly committed labels and the creation frame of each one's node (a free
+ *      emission time, NOT an alignment; tails: blank / 0); n_new_labels (<= P), commit_len (all labels committed so far),
+ *      n_live, status i32 [B]; tail_labels i32 [B][Ptail] and tail_n i32 [B]: the best entry's uncommitted labels (the first
+ *      Ptail; tail_n is their true count; END rows: none); on END rows end_labels i32 [B][n_best][Pend], end_n_labels i32,
+ *      end_score i64, end_lm_score i64 (with lm) [B][n_best], n_hyps i32 [B]: the final beam, best first, as suffixes behind
+ *      the committed text (unused rows and other steps: blank / 0 / -2^62 / 0 / 0).
+ *   status 0; 1: frames were lost (qasr_stream_emit's status 1); 2: no such slot; 3: the beam block's frames_done (0 with
+ *      BEGIN) is not the stream block's; 4: the step's node ids would pass 2^31 - 1.  A row with a status leaves its state
+ *      alone and writes an empty step.
+ * One launch; nothing is read back; the chain qasr_ctc_topn -> qasr_stream_beam -> qasr_stream_emit can be captured.
+ * QASR_ERR_ARG with nothing launched and nothing written: an unknown struct_size, a NULL among the required pointers (all but
+ * lm, and end_lm_score without lm), what qasr_stream_emit refuses about S, B, Wl, C, Rr, samples_per_frame, state_bytes and Tw,
+ * Tw > QASR_BEAM_MAX_FRAMES, what qasr_ctc_beam refuses about N, beam_width, n_best, blank and lae_entries (and with lm what
+ * qasr_ctc_beam_lm refuses about lm, lm_bytes, alpha_q, beta_q, space), Lg < 0, K outside 1 .. QASR_STREAM_BEAM_ROUND,
+ * F < Lg + K or F > QASR_STREAM_BEAM_MAX_RING, beam_state_bytes below the query, a state not 16-byte aligned,
+ * max_final_frames outside 1 .. Tw, P < F + max_final_frames, Ptail < 1, Pend < F. */
+#define QASR_STREAM_BEAM_ROUND 32
+#define QASR_STREAM_BEAM_MAX_RING (1 << 20)
+size_t qasr_stream_beam_state_bytes(int S, int beam_width, int F);
+typedef struct qasr_stream_beam_args {
+  uint32_t struct_size;        /* sizeof of this struct in the caller's header */
+  int32_t S, B, Wl, C, Rr, samples_per_frame, Tw;
+  int32_t N, beam_width, n_best, blank;
+  int32_t Lg, K, F;            /* the lag and the round period in frames (K: QASR_STREAM_BEAM_ROUND), rows of the ring */
+  int32_t max_final_frames;    /* the most frames one step makes final (StreamPlan.max_final_frames) */
+  int32_t P, Ptail, Pend;
+  uint32_t lae_entries;        /* QASR_BEAM_TABLE_ENTRIES */
+  const void* state;
+  size_t state_bytes;
+  void* beam_state;
+  size_t beam_state_bytes;
+  const int32_t* slots;
+  const int32_t* flags;
+  const int32_t* cand_id;
+  const int32_t* cand_q;
+  const int32_t* enc_lens;
+  const int32_t* first_frame;
+  const uint16_t* lae_table;
+  int32_t* labels;
+  int32_t* frames;
+  int32_t* n_new_labels;
+  int32_t* commit_len;
+  int32_t* n_live;
+  int32_t* status;
+  int32_t* tail_labels;
+  int32_t* tail_n;
+  int32_t* end_labels;
+  int32_t* end_n_labels;
+  int64_t* end_score;
+  int32_t* n_hyps;
+  const void* lm;              /* device memory: a packed model that passed qasr_lm_check, or NULL: no model */
+  size_t lm_bytes;
+  int32_t alpha_q, beta_q;
+  int32_t space, reserved;
+  int64_t* end_lm_score;       /* with lm */
+} qasr_stream_beam_args;
+int qasr_stream_beam(void* stream, const qasr_stream_beam_args* args);
+
 /* ---- streaming at any sample rate: per-stream resampler state on the device -------------------------------------------
  * In front of the sample ring above: PCM at the source's rate (int16 or float32, 1 .. 8 interleaved channels) is appended to a
  * per-slot history of channel sums, and the outputs of the polyphase resampler that have become FINAL are written into the

@@ -181,6 +181,9 @@ size_t stream_state_bytes(int S, int Wl, int C);
 int launch_stream_push(hipStream_t s, const qasr_stream_push_args& a);
 int launch_stream_window(hipStream_t s, const qasr_stream_window_args& a);
 int launch_stream_emit(hipStream_t s, const qasr_stream_emit_args& a);
+// qasr_stream_beam.hip: the streaming beam search (k_stream_beam<LM>); checked by qasr_stream_beam
+size_t stream_beam_state_bytes(int S, int W, int F);
+int launch_stream_beam(hipStream_t s, const qasr_stream_beam_args& a);
 // qasr_stream_rs.hip: streaming at any sample rate (k_stream_rs_append, k_stream_rs_fir); checked by qasr_stream_rs_push
 size_t stream_rs_state_bytes(int S, int hcap);
 size_t stream_rs_work_bytes(int B);

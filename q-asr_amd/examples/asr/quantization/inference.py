@@ -101,13 +101,20 @@ def main():
                    help="(extension, needs --stream_chunk_s) context in front of every chunk (default 4.0)")
     p.add_argument("--stream_right_s", type=float, default=None, metavar='SECONDS',
                    help="(extension, needs --stream_chunk_s) look-ahead behind every chunk (default 0.96)")
+    p.add_argument("--stream_beam_lag_s", type=float, default=None, metavar='SECONDS',
+                   help="(extension, needs --stream_chunk_s and --beam_width) the commit lag of the streaming beam search "
+                        "(EncDecCTCModel.stream(beam=)): text older than this becomes final (default 4.0, untried on speech)")
     args = p.parse_args()
     if (args.stream_left_s is not None or args.stream_right_s is not None) and args.stream_chunk_s is None:
         p.error('--stream_left_s and --stream_right_s need --stream_chunk_s')
+    if args.stream_beam_lag_s is not None and (args.stream_chunk_s is None or args.beam_width is None):
+        p.error('--stream_beam_lag_s needs --stream_chunk_s and --beam_width')
     if args.stream_chunk_s is not None:
-        for flag in ('window_s', 'beam_width', 'align'):
+        for flag in ('window_s', 'align'):
             if getattr(args, flag) is not None:
-                p.error(f'--stream_chunk_s does not go with --{flag}: a streaming session is greedy and steps by chunks')
+                p.error(f'--stream_chunk_s does not go with --{flag}: a streaming session steps by chunks')
+        if args.boost_file is not None:
+            p.error('--stream_chunk_s does not go with --boost_file: phrase boosting does not run across steps')
     if args.overlap_s is not None and args.window_s is None:
         p.error('--overlap_s needs --window_s')
     if args.window_s is not None and args.timestamps and args.beam_width is not None:
@@ -208,17 +215,26 @@ def main():
         signal = batch[0] if rate_kw else batch[0].float()   # --input_rate: int16 PCM, resampled inside the model's call
         if args.stream_chunk_s is not None:                  # one session per batch: k_stream_push / _window / _emit per step
             if stream_sess is None:                          # one session for the whole manifest: one reservation, one graph
+                stream_beam = None
+                if args.beam_width is not None:              # k_topn + k_stream_beam in front of k_stream_emit in every step
+                    from qasr import stream_beam as qsb
+                    stream_beam = qsb.StreamBeam(width=args.beam_width, lm=args.lm_path, alpha=alpha, beta=beta,
+                                                 lag_s=4.0 if args.stream_beam_lag_s is None else args.stream_beam_lag_s)
                 try:
                     stream_sess = asr_model.stream(max_streams=args.batch_size, chunk_s=args.stream_chunk_s, tail=False,
                                                    left_s=4.0 if args.stream_left_s is None else args.stream_left_s,
                                                    right_s=0.96 if args.stream_right_s is None else args.stream_right_s,
-                                                   input_rate=args.input_rate)       # int16 PCM: resampled per stream on the device
+                                                   input_rate=args.input_rate,       # int16 PCM: resampled per stream on the device
+                                                   beam=stream_beam)
                 except ValueError as e:
-                    p.error(f'--stream_chunk_s / --stream_left_s / --stream_right_s / --input_rate: {e}')
+                    p.error(f'--stream_chunk_s / --stream_left_s / --stream_right_s / --input_rate / --stream_beam_lag_s: {e}')
             stream_hyps = asr_model.decode_stream(signal, batch[1], session=stream_sess)
             for h in stream_hyps:
                 hyps.append(h.text)
-                if args.timestamps:
+                if args.beam_width is not None:
+                    beam_scores.append(h.utt_score)
+                    lm_scores.append(h.lm_score)
+                elif args.timestamps:
                     words.append([list(w) for w in h.words])
                     utt_scores.append(h.utt_score)
         elif args.window_s is not None:                      # k_cut, windows in batches, k_stitch, one collapse / search

@@ -689,7 +689,7 @@ class EncDecCTCModel(nn.Module):
         return qstream.StreamPlan(chunk_s, left_s, right_s, lp.sample_rate, lp.samples_per_frame, lp.frames_of)
 
     def stream(self, max_streams=32, chunk_s=0.96, left_s=4.0, right_s=0.96, tail=True, sample_rate=None, beam_width=None,
-               input_rate=None, channels=1):
+               input_rate=None, channels=1, beam=None, boost=None):
         """A streaming session (an extension; NeMo's buffered streaming, the FrameBatchASR idea, for many streams at once):
 
             sess = model.stream(max_streams=32, chunk_s=0.96, left_s=4.0, right_s=0.96)
@@ -728,14 +728,32 @@ class EncDecCTCModel(nn.Module):
         'best'); close() flushes that tail, and the updates of steps it completes are kept in sess.closing_updates.
         input_rate=None, or the model's rate with channels=1, is the plain session.
 
+        beam=qasr.stream_beam.StreamBeam(width=16, n_best=1, cutoff_top_n=40, lm=None, alpha=0.0, beta=0.0, lag_s=4.0): the
+        prefix beam search of decode(beam_width=, lm=) across steps.  Every stream keeps its beam on the device next to its
+        ring (k_stream_beam; qasr.stream_beam.STREAM_BEAM_RULES states the rule); a step is window -> forward with
+        log-probabilities -> top-N -> beam -> emit.  Text becomes final by a fixed-lag commit: every 32 frames the labels of
+        the best entry created more than lag_s ago are committed and entries that disagree with them are dropped, keyed on
+        the global frame, so the result does not depend on how the pushes are sliced.  push() then returns StreamUpdates
+        whose labels / text are the newly committed labels, start_s / end_s the frame at which each label entered the beam
+        (a free emission time, not an alignment), score empty (a committed prefix has no score of its own) and tail_text
+        the best entry's uncommitted text; close() returns the Hypothesis of committed text + the best remainder with
+        utt_score = the beam score and lm_score, or with n_best > 1 the list, best first, as decode(beam_width=, n_best=)
+        returns it.  lag_s beyond the stream's length gives decode(beam_width=)'s result for the final frames.  The
+        default lag of 4.0 s is untried on speech.  It composes with input_rate= unchanged: everything here sits behind
+        the ring.
+
         Refused: sample_rate other than the model's (here it names the model's rate: give the source's as input_rate=),
-        a rate or filter the resampler refuses, channels outside 1 .. 8, beam_width (no beam search across steps)."""
+        a rate or filter the resampler refuses, channels outside 1 .. 8, beam_width (beam search across steps is beam=),
+        boost (no phrase boosting across steps), beam= arguments outside decode(beam_width=)'s ranges."""
         target = int(self.preprocessor._sample_rate)
         if sample_rate is not None and int(sample_rate) != target:
             raise ValueError(f'stream: sample_rate {sample_rate} is not the model\'s {target}: sample_rate names the model\'s rate '
                              'here; give the rate of the audio as input_rate=')
         if beam_width is not None:
-            raise ValueError('stream: beam_width is not supported: the incremental collapse is greedy')
+            raise ValueError('stream: beam_width is not an argument of stream(): give the streaming beam search as '
+                             'beam=qasr.stream_beam.StreamBeam(width=...)')
+        if boost is not None:
+            raise ValueError('stream: boost is not supported: phrase boosting does not run across steps')
         if int(max_streams) < 1:
             raise ValueError(f'stream: max_streams must be at least 1, got {max_streams}')
         try:
@@ -757,11 +775,25 @@ class EncDecCTCModel(nn.Module):
                 rs_plan = qsrs.StreamResamplePlan(plan, plans[key], int(channels))
             except ValueError as e:
                 raise ValueError(f'stream: input_rate {input_rate}: {e}') from None
-        return StreamSession(self, int(max_streams), plan, bool(tail), rs_plan)
+        bplan = None
+        if beam is not None:
+            from qasr import stream_beam as qsb
+            if not isinstance(beam, qsb.StreamBeam):
+                raise ValueError(f'stream: beam must be a qasr.stream_beam.StreamBeam, got {type(beam).__name__}')
+            if getattr(beam, 'boost', None) is not None:
+                raise ValueError('stream: boost is not supported: phrase boosting does not run across steps')
+            try:
+                w, nb, n = self._beam_args(beam.width, beam.n_best, beam.cutoff_top_n)
+                lm = self._lm_args(beam.lm, beam.alpha, beam.beta)
+                beam = qsb.StreamBeam(w, nb, n, lm, float(beam.alpha), float(beam.beta), beam.lag_s)
+                bplan = qsb.StreamBeamPlan.for_stream(plan, beam)
+            except ValueError as e:
+                raise ValueError('stream: beam: ' + str(e).replace('decode: ', '')) from None
+        return StreamSession(self, int(max_streams), plan, bool(tail), rs_plan, beam, bplan)
 
     @torch.no_grad()
     def decode_stream(self, input_signal, input_signal_length, chunk_s=0.96, left_s=4.0, right_s=0.96, session=None, input_rate=None,
-                      channels=1):
+                      channels=1, beam=None):
         """A batch of complete recordings played through a streaming session, all rows side by side in pushes of chunk_s
         seconds (what inference.py --stream_chunk_s does): List[qasr.ctc.Hypothesis], one per row - the hypotheses
         stream() gives for that audio, which do not depend on the size of the pushes.
@@ -772,14 +804,15 @@ class EncDecCTCModel(nn.Module):
         and its graph captured again for every call.  A caller with many batches holds one session across them.
 
         input_rate=R, channels=C: the recordings are PCM at R Hz, [B, S * C] interleaved, lengths in frames, as for
-        stream(); a session passed in carries its own."""
+        stream(); a session passed in carries its own.  beam=: the streaming beam search of stream(beam=); the rows are then
+        what close() returns there (a list per row with n_best > 1)."""
         ch = session.rs_plan.channels if session is not None and session.rs_plan is not None else int(channels)
         if input_signal.dim() != 2 or ch < 1 or input_signal.shape[1] % ch:
             raise ValueError(f'decode_stream: input_signal must be [B, S * channels], got {tuple(input_signal.shape)} for {channels} channels')
         B = input_signal.shape[0]
         lens = [min(int(n), input_signal.shape[1] // ch) for n in input_signal_length.tolist()]
         sess = session if session is not None else self.stream(max_streams=B, chunk_s=chunk_s, left_s=left_s, right_s=right_s, tail=False,
-                                                               input_rate=input_rate, channels=ch)
+                                                               input_rate=input_rate, channels=ch, beam=beam)
         try:
             slots = [sess.open() for _ in range(B)]
             C = sess.plan.C if sess.rs_plan is None else sess.rs_plan.Ain     # about chunk_s of audio per push
@@ -1136,8 +1169,9 @@ class StreamSession:
     """EncDecCTCModel.stream(): the live streams of one model.  The host keeps counts it already has (samples per stream, the
     deltas read back so far); everything a step computes from lives on the device."""
 
-    def __init__(self, model, max_streams, plan, tail, rs_plan=None):
+    def __init__(self, model, max_streams, plan, tail, rs_plan=None, beam=None, bplan=None):
         self.model, self.S, self.plan, self.tail = model, max_streams, plan, tail
+        self.beam, self.bplan = beam, bplan  # qasr.stream_beam.StreamBeam / StreamBeamPlan: the beam search across steps
         self.rs_plan = rs_plan               # qasr.stream_rs.StreamResamplePlan: the streams carry PCM at another rate
         self.closing_updates = []            # (resampled streams) the StreamUpdates of steps the last close() completed
         self._open = {}                      # slot -> dict(received, begin, deltas)
@@ -1149,7 +1183,7 @@ class StreamSession:
         if model.engine_ready():             # the calibrated model: one reservation for the session's lifetime
             self._saved = (model._reserve, getattr(model, '_reserve_logp', True))
             model.reserve(max_streams, plan.Wl / float(plan.sample_rate))
-            model._reserve_logp = False
+            model._reserve_logp = beam is not None       # the beam search reads log-probabilities
             self._own = True
 
     def __enter__(self):
@@ -1180,7 +1214,7 @@ class StreamSession:
         slot = int(slot)
         if not 0 <= slot < self.S or slot in self._open:
             raise ValueError(f'stream: slot {slot} is already open or outside 0 .. max_streams - 1 = {self.S - 1}')
-        self._open[slot] = dict(received=0, begin=True, deltas=[], in_received=0, fmt=None)
+        self._open[slot] = dict(received=0, begin=True, deltas=[], in_received=0, fmt=None, beam_begin=True)
         return slot
 
     # ---- the three steps, on the device or as the twins
@@ -1204,8 +1238,18 @@ class StreamSession:
             self._win = (torch.empty(self.S, self.plan.Wl, device=device), torch.empty(self.S, device=device, dtype=torch.int32),
                          torch.empty(self.S, device=device, dtype=torch.int32))
             self._out = qengine.stream_emit_buffers(self.S, self.plan, device, tail=self.tail)
+            if self.beam is not None:
+                self._bstate = qengine.stream_beam_state(self.S, self.bplan, device)
+                self._bout = qengine.stream_beam_buffers(self.S, self.bplan, device, self.beam.lm is not None)
+                self._cand = None
+                qengine.lae_table_device(device)                                 # the uploads, outside any capture
+                if self.beam.lm is not None:
+                    qengine.lm_device(self.beam.lm, device)
         else:
             self._state = qstream.StreamState(self.S, self.plan)
+            if self.beam is not None:
+                from qasr import stream_beam as qsb
+                self._bstate = qsb.StreamBeamState(self.S, self.bplan, check=False)
 
     def _i32(self, x):
         return torch.tensor(x, dtype=torch.int32).to(self._dev)
@@ -1231,6 +1275,14 @@ class StreamSession:
         """a step for the slots that filled a chunk; its deltas are kept and returned as StreamUpdates"""
         from qasr import ctc as qctc
         vocab, spf_s, ups = self.model.decoder.vocabulary, self.plan.seconds_per_frame(), []
+        if self.beam is not None:
+            for s, row in zip(stepping, self._step_beam(stepping, False)):
+                lab, fr = row['labels'], row['frames']
+                self._open[s]['deltas'].append((lab, fr))
+                ups.append(qctc.StreamUpdate(s, lab.tolist(), ''.join(vocab[i] for i in lab.tolist()),
+                                             (fr.astype(np.float64) * spf_s).tolist(), ((fr + 1).astype(np.float64) * spf_s).tolist(),
+                                             [], ''.join(vocab[i] for i in row['tail']) if self.tail else ''))
+            return ups
         for s, (lab, start, nfr, sc, _, tl) in zip(stepping, self._step(stepping, False)):
             self._open[s]['deltas'].append((lab, start, nfr, sc))
             ups.append(qctc.StreamUpdate(s, lab.tolist(), ''.join(vocab[i] for i in lab.tolist()),
@@ -1329,6 +1381,85 @@ class StreamSession:
                          float(o.utt_score[b]), tl))
         return rows
 
+    def _step_beam(self, slots, end):
+        """one step of a beam session for `slots`: window -> forward with log-probabilities -> top-N -> beam -> emit (the
+        greedy emit keeps the stream's counters); returns per row dict(labels, frames, tail, end, commit_len)"""
+        from qasr import beam as qbeam, engine as qengine, stream as qstream, stream_beam as qsb
+        m, plan, bp, bm, B = self.model, self.plan, self.bplan, self.beam, len(slots)
+        blank = len(m.decoder.vocabulary)
+        flags = [(qstream.END if end else 0) | (qstream.BEGIN if self._open[s]['beam_begin'] else 0) for s in slots]
+        for s in slots:
+            self._open[s]['beam_begin'] = False
+        self.steps += 1
+        if self._dev.type == 'cuda':
+            sl, fl = self._i32(slots), self._i32(flags)
+            win, wl, first = qengine.stream_window(self._state, self.S, plan, sl, out=tuple(t[:B] for t in self._win))
+            logp, enc, tok = m._forward(win, wl.long())
+            logp = logp.float()
+            tok = tok.to(torch.int32).contiguous()
+            fs = m._frame_scores(logp, tok).contiguous()
+            enc = enc.to(torch.int32).contiguous()
+            Tw = logp.shape[1]
+            if self._cand is None or self._cand[0].shape[1] != Tw:
+                self._cand = tuple(torch.empty(self.S, Tw, bp.N, device=self._dev, dtype=torch.int32) for _ in range(2))
+            cand = qengine.ctc_topn(logp, enc, bp.N, out=tuple(t[:B] for t in self._cand))
+            names = [f.name for f in dataclasses.fields(self._bout)]
+            bout = qsb.BeamStepBatch(*[None if getattr(self._bout, n) is None else getattr(self._bout, n)[:B] for n in names])
+            qengine.stream_beam(self._state, self._bstate, self.S, plan, bp, sl, fl, cand[0], cand[1], enc, first, blank, bm.lm,
+                                bm.alpha, bm.beta, out=bout)
+            fields = [f.name for f in dataclasses.fields(self._out)]
+            eout = qstream.StepBatch(*[None if getattr(self._out, n) is None else getattr(self._out, n)[:B] for n in fields])
+            qengine.stream_emit(self._state, self.S, plan, sl, fl, tok, fs, enc, first, blank, out=eout)
+            o = qsb.BeamStepBatch(*[None if getattr(bout, n) is None else getattr(bout, n).cpu().numpy() for n in names])
+            est = eout.status.cpu().numpy()
+        else:
+            win, wl, first = qstream.window_host(self._state, slots)
+            logp, enc, tok = m._forward(torch.from_numpy(win), torch.from_numpy(wl).long())
+            logp = logp.float()
+            fs = m._frame_scores(logp, tok)
+            cid, cq = qbeam.topn_host(logp.numpy(), bp.N, enc.numpy())
+            o = qsb.step_batch_host(self._bstate, self._state, slots, flags, cid, cq, enc.numpy(), first, blank, bm.lm, bm.alpha, bm.beta)
+            est = qstream.emit_batch_host(self._state, slots, flags, tok.numpy(), fs.numpy(), enc.numpy(), first, blank).status
+        if int(o.status.max()) != 0 or int(est.max()) != 0:
+            raise RuntimeError(f'stream: step refused, status {o.status.tolist()} / {est.tolist()} for slots {slots}')
+        rows = []
+        for b in range(B):
+            n = int(o.n_new_labels[b])
+            ends = [(o.end_labels[b, h, :int(o.end_n_labels[b, h])].tolist(), int(o.end_score[b, h]),
+                     None if o.end_lm_score is None else int(o.end_lm_score[b, h])) for h in range(int(o.n_hyps[b]))]
+            rows.append(dict(labels=o.labels[b, :n].copy(), frames=o.frames[b, :n].copy(), commit_len=int(o.commit_len[b]),
+                             tail=o.tail_labels[b, :min(int(o.tail_n[b]), o.tail_labels.shape[1])].tolist(), end=ends))
+        return rows
+
+    def _close_beam(self, st, slot):
+        """the END step of a beam session: committed text + the remainder of each of the n_best final entries"""
+        from qasr import beam as qbeam, ctc as qctc
+        vocab, spf_s = self.model.decoder.vocabulary, self.plan.seconds_per_frame()
+        ends = []
+        try:
+            if st['received'] > 0:
+                row = self._step_beam([slot], True)[0]
+                st['deltas'].append((row['labels'], row['frames']))
+                ends = row['end']
+        finally:
+            self._open.pop(slot)
+        lab = np.concatenate([d[0] for d in st['deltas']] + [np.zeros(0, dtype=np.int32)]).astype(np.int32)
+        fr = np.concatenate([d[1] for d in st['deltas']] + [np.zeros(0, dtype=np.int32)]).astype(np.int32)
+        text = lambda ids: ''.join(vocab[i] for i in ids)
+        best = qctc.Hypothesis(text(lab.tolist()), lab.tolist(), (fr.astype(np.float64) * spf_s).tolist(),
+                               ((fr + 1).astype(np.float64) * spf_s).tolist(), None, None, [])
+        head = lab.tolist()[:len(lab) - len(ends[0][0])] if ends else lab.tolist()
+        hyps = []
+        for h, (suffix, sc, lmt) in enumerate(ends):
+            hyp = best if h == 0 else qctc.Hypothesis(text(head + suffix), head + suffix, [], [], None, None, [])
+            hyp.utt_score = float(sc) / qbeam.ONE
+            if lmt is not None:
+                hyp.lm_score = float(lmt) / qbeam.ONE
+            hyps.append(hyp)
+        if not hyps:                         # nothing was received, or the beam died: the committed text alone
+            hyps = [best]
+        return hyps if self.beam.n_best > 1 else hyps[0]
+
     def push(self, slots, signal, lengths=None):
         """signal [B, n] float32 or int16 at the model's rate, lengths [B] (default: n each), slots: B distinct open slots.
         A session opened with input_rate= takes [B, n * channels] interleaved PCM at that rate, lengths in frames; a slot
@@ -1383,6 +1514,8 @@ class StreamSession:
         if self.rs_plan is not None and st['in_received'] > 0:     # the filter's tail: FLUSH rounds, stepping when a chunk fills
             zero = torch.zeros(1, self.rs_plan.channels, dtype=st['fmt'], device=self._dev)
             self.closing_updates = self._rounds_rs([slot], [0], zero, flush=True)
+        if self.beam is not None:
+            return self._close_beam(st, slot)
         self._open.pop(slot)
         utt = 0.0
         if st['received'] > 0:               # (a stream that never received a sample has nothing to run)

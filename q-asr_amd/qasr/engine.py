@@ -24,6 +24,7 @@ SYMBOLS = ['qasr_blob_check', 'qasr_engine_create', 'qasr_engine_create_ex', 'qa
            'qasr_resample_check', 'qasr_resample', 'qasr_resample_out_samples', 'qasr_longform_cut', 'qasr_longform_stitch',
            'qasr_stream_state_bytes', 'qasr_stream_push', 'qasr_stream_window', 'qasr_stream_emit',
            'qasr_stream_rs_state_bytes', 'qasr_stream_rs_work_bytes', 'qasr_stream_rs_push',
+           'qasr_stream_beam_state_bytes', 'qasr_stream_beam',
            'qasr_last_error', 'qasr_version']
 
 _lib = None
@@ -194,6 +195,10 @@ def load_library():
         lib.qasr_stream_rs_work_bytes.argtypes = [i32]
         lib.qasr_stream_rs_work_bytes.restype = sz
         lib.qasr_stream_rs_push.argtypes = [vp, C.POINTER(StreamRsPushArgs)]
+    if hasattr(lib, 'qasr_stream_beam'):        # (likewise)
+        lib.qasr_stream_beam_state_bytes.argtypes = [i32, i32, i32]
+        lib.qasr_stream_beam_state_bytes.restype = sz
+        lib.qasr_stream_beam.argtypes = [vp, C.POINTER(StreamBeamArgs)]
     lib.qasr_debug_prof.argtypes = [vp]
     lib.qasr_debug_timeline.argtypes = [vp, sz]
     lib.qasr_sep_layer.argtypes = [vp, C.POINTER(SepLayerArgs), C.c_char_p, sz]
@@ -1153,6 +1158,106 @@ def stream_emit(state, S, plan, slots, flags, tokens, frame_score, enc_lens, fir
     with torch.cuda.device(dev):
         _check(lib.qasr_stream_emit(_stream_ptr(stream), C.byref(a)), 'qasr_stream_emit')
     return out
+
+
+class StreamBeamArgs(C.Structure):
+    """qasr_stream_beam_args (include/qasr.h)"""
+    _fields_ = ([('struct_size', C.c_uint32)] +
+                [(n, C.c_int32) for n in ('S', 'B', 'Wl', 'C', 'Rr', 'samples_per_frame', 'Tw', 'N', 'beam_width', 'n_best', 'blank',
+                                          'Lg', 'K', 'F', 'max_final_frames', 'P', 'Ptail', 'Pend')] +
+                [('lae_entries', C.c_uint32), ('state', C.c_void_p), ('state_bytes', C.c_size_t), ('beam_state', C.c_void_p),
+                 ('beam_state_bytes', C.c_size_t)] +
+                [(n, C.c_void_p) for n in ('slots', 'flags', 'cand_id', 'cand_q', 'enc_lens', 'first_frame', 'lae_table', 'labels',
+                                           'frames', 'n_new_labels', 'commit_len', 'n_live', 'status', 'tail_labels', 'tail_n',
+                                           'end_labels', 'end_n_labels', 'end_score', 'n_hyps', 'lm')] +
+                [('lm_bytes', C.c_size_t)] + [(n, C.c_int32) for n in ('alpha_q', 'beta_q', 'space', 'reserved')] +
+                [('end_lm_score', C.c_void_p)])
+
+
+def stream_beam_state(S, bplan, device):
+    """Zeroed beam state of S fresh streams under a qasr.stream_beam.StreamBeamPlan: an int32 tensor of
+    qasr_stream_beam_state_bytes(S, W, F) / 4 words.  `stream_beam_block(state, S, bplan)` views it as [S, slot_words]."""
+    n = int(load_library().qasr_stream_beam_state_bytes(int(S), bplan.W, bplan.F))
+    if n == 0:
+        raise ValueError(f'stream_beam_state: S {S}, width {bplan.W}, F {bplan.F} out of range')
+    return torch.zeros(n // 4, device=device, dtype=torch.int32)
+
+
+def stream_beam_block(bstate, S, bplan):
+    """the S slots of a beam state as [S, slot_words] (header, entries, ring), as qasr.stream_beam.StreamBeamState.block"""
+    return bstate[:int(S) * bplan.slot_words].view(int(S), bplan.slot_words)
+
+
+def stream_beam_buffers(B, bplan, device, with_lm, P=None, Ptail=None, Pend=None):
+    """k_stream_beam's outputs as a qasr.stream_beam.BeamStepBatch of cuda tensors"""
+    from . import stream_beam as sb
+    P = bplan.delta_pitch if P is None else int(P)
+    Ptail = bplan.tail_pitch if Ptail is None else int(Ptail)
+    Pend = bplan.end_pitch if Pend is None else int(Pend)
+    i = lambda *s: torch.empty(*s, device=device, dtype=torch.int32)
+    l = lambda *s: torch.empty(*s, device=device, dtype=torch.int64)
+    nb = bplan.n_best
+    return sb.BeamStepBatch(i(B, P), i(B, P), i(B), i(B), i(B), i(B), i(B, Ptail), i(B), i(B, nb, Pend), i(B, nb), l(B, nb),
+                            l(B, nb) if with_lm else None, i(B))
+
+
+def stream_beam_args(state, bstate, S, plan, bplan, slots, flags, cand_id, cand_q, enc_lens, first_frame, blank, lm=None,
+                     alpha=0.0, beta=0.0, out=None):
+    """the filled qasr_stream_beam_args of stream_beam (the tensors it points to are kept alive on it)"""
+    from .beam import TAB_ENTRIES
+    dev = state.device
+    if cand_id.dim() != 3 or cand_id.dtype != torch.int32 or not cand_id.is_contiguous() or not cand_id.is_cuda:
+        raise ValueError(f'stream_beam: cand_id must be a contiguous cuda int32 tensor [B, Tw, N], got {cand_id.dtype} {tuple(cand_id.shape)}')
+    if cand_q.dtype != torch.int32 or not cand_q.is_contiguous() or cand_q.shape != cand_id.shape:
+        raise ValueError('stream_beam: cand_q must be a contiguous int32 tensor of the shape of cand_id')
+    B, Tw, N = cand_id.shape
+    for t, w in ((slots, 'slots'), (flags, 'flags'), (enc_lens, 'enc_lens'), (first_frame, 'first_frame')):
+        _i32dev(t, B, 'stream_beam: ' + w)
+    alpha_q = beta_q = 0
+    if lm is not None:
+        from .ngram import fixed_weights
+        alpha_q, beta_q = fixed_weights(alpha, beta)
+        if lm.n_labels != int(blank):
+            raise ValueError(f'stream_beam: the model was loaded for {lm.n_labels} labels, blank is {blank}')
+    if out is None:
+        out = stream_beam_buffers(B, bplan, dev, lm is not None)
+    tab = lae_table_device(dev)
+    blob = None if lm is None else lm_device(lm, dev)
+    a = StreamBeamArgs()
+    a.struct_size = C.sizeof(StreamBeamArgs)
+    a.S, a.B, a.Wl, a.C, a.Rr, a.samples_per_frame, a.Tw = int(S), B, plan.Wl, plan.C, plan.Rr, plan.samples_per_frame, Tw
+    a.N, a.beam_width, a.n_best, a.blank = N, bplan.W, bplan.n_best, int(blank)
+    a.Lg, a.K, a.F, a.max_final_frames = bplan.Lg, bplan.K, bplan.F, bplan.max_final_frames
+    a.P, a.Ptail, a.Pend = out.labels.shape[1], out.tail_labels.shape[1], out.end_labels.shape[2]
+    a.lae_entries = TAB_ENTRIES
+    a.state, a.state_bytes = state.data_ptr(), state.numel() * state.element_size()
+    a.beam_state, a.beam_state_bytes = bstate.data_ptr(), bstate.numel() * bstate.element_size()
+    a.slots, a.flags, a.cand_id, a.cand_q = slots.data_ptr(), flags.data_ptr(), cand_id.data_ptr(), cand_q.data_ptr()
+    a.enc_lens, a.first_frame, a.lae_table = enc_lens.data_ptr(), first_frame.data_ptr(), tab.data_ptr()
+    for n in ('labels', 'frames', 'n_new_labels', 'commit_len', 'n_live', 'status', 'tail_labels', 'tail_n', 'end_labels',
+              'end_n_labels', 'end_score', 'n_hyps'):
+        t = getattr(out, n)
+        assert t.is_cuda and t.is_contiguous() and t.dtype == (torch.int64 if n == 'end_score' else torch.int32), 'stream_beam: out.' + n
+        setattr(a, n, t.data_ptr())
+    if lm is not None:
+        a.lm, a.lm_bytes, a.alpha_q, a.beta_q, a.space = blob.data_ptr(), blob.numel(), alpha_q, beta_q, int(lm.space)
+        a.end_lm_score = 0 if out.end_lm_score is None else out.end_lm_score.data_ptr()
+    a._keep = (tab, blob, out)
+    return a
+
+
+def stream_beam(state, bstate, S, plan, bplan, slots, flags, cand_id, cand_q, enc_lens, first_frame, blank, lm=None, alpha=0.0,
+                beta=0.0, out=None, stream=None):
+    """qasr_stream_beam: one step's final frames searched from the slots' beams; cand_id / cand_q cuda int32 [B, Tw, N]
+    (ctc_topn over the windows' log-probabilities), enc_lens / first_frame / slots / flags cuda int32 [B]; state: the stream
+    state (read-only: call this BEFORE stream_emit), bstate: stream_beam_state.  Returns a qasr.stream_beam.BeamStepBatch of
+    cuda tensors.  k_stream_beam, one launch, nothing read back; equal to qasr.stream_beam.step_batch_host byte for byte,
+    the beam state included.  The table and the model are uploaded by the first call: make that one outside a capture."""
+    a = stream_beam_args(state, bstate, S, plan, bplan, slots, flags, cand_id, cand_q, enc_lens, first_frame, blank, lm, alpha,
+                         beta, out)
+    with torch.cuda.device(state.device):
+        _check(load_library().qasr_stream_beam(_stream_ptr(stream), C.byref(a)), 'qasr_stream_beam')
+    return a._keep[2]
 
 
 class Engine:

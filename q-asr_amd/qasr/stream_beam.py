@@ -1,0 +1,532 @@
+"""Streaming CTC prefix beam search: a per-stream beam that a step loads, advances over the frames that became final and
+stores back, with a fixed-lag commit that prunes.  The host statement of k_stream_beam (csrc/qasr_stream_beam.hip,
+include/qasr.h) and the CPU path of EncDecCTCModel.stream(beam=).  NumPy only: no GPU, no native library.
+
+The search itself is qasr.beam's (`_search_one` without a model, `_search_one_lm` under LM_RULES with one); what is new is
+where the beam lives between two steps and the rule for when text becomes final (STREAM_BEAM_RULES)."""
+from dataclasses import dataclass, field
+from typing import List, Optional
+
+import numpy as np
+
+from . import stream as qs
+from .beam import FRAC, MAX_N, MAX_W, NEG, _hmix, lae, lae_table
+
+K_ROUND = 32                            # a commit round runs after every global frame t with (t + 1) % K_ROUND == 0
+HDR_WORDS = 16
+_H_NB, _H_COMMIT, _H_DONE, _H_STARTED = 0, 1, 2, 3
+STATUS_OK, STATUS_GAP, STATUS_SLOT, STATUS_SYNC, STATUS_NODES = 0, 1, 2, 3, 4
+NODE_LIMIT = (1 << 31) - 1
+
+STREAM_BEAM_RULES = """Frames.  A step makes the frames [lo, hi) of qasr.stream's rule final (STREAM_RULES: lo = the stream block's
+frames_done, hi from the window's encoded length, `received` and END); they are GLOBAL frames t, and the candidates of
+frame t are row t - first_frame of the window's top-N (k_topn / topn_host over the window's log-probabilities).
+
+State of a slot: 16 + 20 W 32-bit words, then a ring of F rows x W entries of (parent node, label), two words each.
+Word 0: nb, the live entries; 1: commit_len; 2: frames_done; 3: 1 once the slot has been stepped (a zeroed block is a fresh
+stream: the single empty entry); 4-15: zero.  Then, W entries each, 64-bit: pb, pnb, score, prefix hash, parent hash, own
+(the term of the entry's creation), lm_tot, word hash; 32-bit: length (labels since the stream began), last label, node,
+context node.  Entries at and behind nb are zero.  Without a model own, lm_tot, word hash and context stay zero.
+
+Per frame: the step of qasr.beam._search_one (_search_one_lm with a model) on every byte - lae, tie order, hashes, dead
+candidates.  The one difference: a new prefix that lands in rank r at global frame t is node t * W + r (int32), stored in
+row t mod F of the ring, entry r.  A step whose hi * W would pass 2^31 - 1 reports status 4.
+
+Commit round.  After frame t with (t + 1) % K == 0 (K = K_ROUND), with h = t - Lg (Lg: the lag in frames); nothing happens
+while h < 0 or when the beam is dead.  old(e) of an entry e is the sequence of its labels whose node was created at a
+frame <= h; creation frames rise strictly along a chain (a prefix is created from an entry that was in the beam before that
+frame), so old(e) is a prefix of e.  The committed text becomes old(entry 0), the best entry's; an entry survives iff
+old(e) == old(entry 0) as LABEL sequences (a prefix that left the beam and came back owns a second node, so node ids are not
+compared); survivors keep their order.  commit_len = len(old(0)).  commit_len never shrinks and committed labels never
+change: entry 0 survived every earlier round, so its old() extends what was committed.  Chain walks stop at depth commit_len.
+
+END.  After the last final frame, word-mode models add the unfinished-word term and re-order (LM_RULES).  No horizon: the
+step's delta also carries everything of the best entry behind commit_len, and the first n_best entries are written as their
+suffixes behind commit_len with score, lm_score, n_labels (of the suffix) and n_hyps; all of them start with the committed
+text, which the host prepends.  The stored state is the beam after the step's frames (before the END re-ordering).
+
+Per step out: the delta (labels and, per label, the creation frame of its node: a free emission time, NOT an alignment),
+n_new_labels, commit_len (the delta included), the live entry count, status; the provisional tail = the best entry's
+uncommitted labels, the first Ptail of them, with their true count (END rows: none).
+
+Flags and status.  BEGIN resets the slot to the single empty entry first.  A beam that died (no live candidate) stays
+dead: frames_done still advances, END gives n_hyps = 0, as offline.  Status 1: the stream rule's gap (lo < first_frame); 2: a
+slot out of range; 3: the beam block's frames_done (0 on BEGIN) differs from the stream block's; 4: the node-id limit.  A
+row with a non-zero status leaves its state alone (a BEGIN included) and writes the outputs of an empty step.
+
+Consequences, the contract: `lagged_search_host`, the whole-stream statement, equals the concatenation of any sequence of
+steps on every byte; with Lg >= the stream's length no round fires and the result is beam_search_host's on every byte."""
+
+
+@dataclass
+class StreamBeam:
+    """What EncDecCTCModel.stream(beam=) takes.  width, n_best, cutoff_top_n, lm, alpha, beta: as decode(beam_width=, ...).
+    lag_s: the commit lag in seconds (rounded to frames); the default of 4.0 s is untried on speech."""
+    width: int = 16
+    n_best: int = 1
+    cutoff_top_n: int = 40
+    lm: object = None
+    alpha: float = 0.0
+    beta: float = 0.0
+    lag_s: float = 4.0
+
+
+class StreamBeamPlan:
+    """W, N, n_best, the lag Lg and the round period K in frames, and the sizes that follow from STREAM_BEAM_RULES.
+
+    Ring.  A round at frame t commits every label of the survivors created at a frame <= h = t - Lg, so afterwards every
+    live node - every node a chain walk down to commit_len can reach - was created in (t - Lg, t].  The next round runs
+    at t + K; until it has run, live nodes were created in (t - Lg, t + K]: Lg + K frames.  Before the first round (the
+    first t >= Lg with (t + 1) % K == 0, so t < Lg + K) they were created in [0, t]: at most Lg + K frames again.  Frame
+    t + K lands in the row of frame t - Lg, which died at the round before: F = Lg + K rows suffice, and no smaller ring
+    does when every frame creates a node.
+    Labels.  Creation frames rise strictly along a chain, so an entry has at most one uncommitted label per live frame:
+    at most F.  A round commits labels created in (h - K, h] (the first round: in [0, h], h < K): at most K.
+    Pitches.  end_pitch = tail_pitch = F (a suffix behind commit_len).  Every label a step commits was uncommitted before
+    the step (<= F) or created in it (<= its final frames, one per frame along one chain): delta_pitch = F +
+    max_final_frames, END steps included.
+    `walk` steps through a protocol of frames and asserts all of it on the twin."""
+
+    def __init__(self, width=16, n_best=1, cutoff_top_n=40, lag_frames=200, max_final_frames=1, K=K_ROUND):
+        W, N, nb, Lg, K = int(width), int(cutoff_top_n), int(n_best), int(lag_frames), int(K)
+        if not 1 <= W <= MAX_W:
+            raise ValueError(f'StreamBeamPlan: width must be 1 .. {MAX_W}, got {W}')
+        if not 1 <= N <= MAX_N:
+            raise ValueError(f'StreamBeamPlan: cutoff_top_n must be 1 .. {MAX_N}, got {N}')
+        if not 1 <= nb <= W:
+            raise ValueError(f'StreamBeamPlan: n_best must be 1 .. width, got {nb}')
+        if Lg < 0 or K < 1 or Lg + K > MAX_RING:
+            raise ValueError(f'StreamBeamPlan: lag {Lg} frames must lie in 0 .. {MAX_RING} - K, K {K} >= 1')
+        if int(max_final_frames) < 1:
+            raise ValueError(f'StreamBeamPlan: max_final_frames {max_final_frames} < 1')
+        self.W, self.N, self.n_best, self.Lg, self.K = W, N, nb, Lg, K
+        self.F = Lg + K
+        self.max_final_frames = int(max_final_frames)
+        self.end_pitch = self.tail_pitch = self.F
+        self.delta_pitch = self.F + self.max_final_frames
+        self.slot_words = slot_words(W, self.F)
+
+    @classmethod
+    def for_stream(cls, plan: qs.StreamPlan, beam: StreamBeam, K=K_ROUND):
+        lag = float(beam.lag_s)
+        if not np.isfinite(lag) or lag < 0:
+            raise ValueError(f'StreamBeam: lag_s {beam.lag_s} must be finite and not negative')
+        return cls(beam.width, beam.n_best, beam.cutoff_top_n, int(round(lag / plan.seconds_per_frame())),
+                   max(plan.max_final_frames, 1), K)
+
+
+MAX_RING = 1 << 20                      # rows of a ring (F); the C ABI refuses more
+
+
+def slot_words(W, F):
+    return HDR_WORDS + 20 * int(W) + 2 * int(F) * int(W)
+
+
+def state_bytes(S, W, F):
+    """qasr_stream_beam_state_bytes(S, W, F)"""
+    return 4 * int(S) * slot_words(W, F)
+
+
+class _Entries:
+    """the live entries of one slot as arrays of nb elements"""
+    names64 = ('pb', 'pnb', 'sc', 'hsh', 'phs', 'own', 'lmt', 'wh')
+    names32 = ('ln', 'last', 'node', 'ctx')
+    unsigned = ('hsh', 'phs', 'wh')
+
+    @classmethod
+    def fresh(cls, lm):
+        e = cls()
+        i64 = np.int64
+        e.pb, e.pnb, e.sc = np.array([0], i64), np.array([NEG], i64), np.array([0], i64)
+        e.hsh, e.phs, e.wh = np.zeros(1, np.uint64), np.zeros(1, np.uint64), np.zeros(1, np.uint64)
+        e.own, e.lmt = np.zeros(1, i64), np.zeros(1, i64)
+        e.ln, e.last, e.node = np.zeros(1, np.int32), np.full(1, -1, np.int32), np.full(1, -1, np.int32)
+        e.ctx = np.array([lm.start if lm is not None else 0], np.int32)
+        return e
+
+    def __len__(self):
+        return len(self.sc)
+
+    def take(self, idx):
+        o = _Entries()
+        for n in self.names64 + self.names32:
+            setattr(o, n, getattr(self, n)[idx])
+        return o
+
+
+class StreamBeamState:
+    """S slots as the device holds them: block int32 [S][slot_words].  row_frame, h_dead and trail are the twin's own
+    bookkeeping for its assertions (which frame a ring row holds, the last round's horizon, every node ever made with the
+    committed labels) and are no part of the state."""
+
+    def __init__(self, S, plan: StreamBeamPlan, check=True):
+        self.S, self.plan, self.check = int(S), plan, bool(check)
+        self.block = np.zeros((self.S, plan.slot_words), dtype=np.int32)
+        self.row_frame = np.full((self.S, plan.F), -1, dtype=np.int64)
+        self.h_dead = np.full(self.S, -1, dtype=np.int64)
+        self.trail = [dict(nodes={}, committed=[]) for _ in range(self.S)]
+
+    def ring(self, slot):
+        W, F = self.plan.W, self.plan.F
+        return self.block[slot, HDR_WORDS + 20 * W:].reshape(F, W, 2)
+
+    def header(self, slot):
+        b = self.block[slot]
+        return int(b[_H_NB]), int(b[_H_COMMIT]), int(b[_H_DONE]), int(b[_H_STARTED])
+
+    def _arrays(self, slot):
+        W = self.plan.W
+        b = self.block[slot]
+        a64 = b[HDR_WORDS:HDR_WORDS + 16 * W].view(np.int64).reshape(8, W)
+        a32 = b[HDR_WORDS + 16 * W:HDR_WORDS + 20 * W].reshape(4, W)
+        return a64, a32
+
+    def load(self, slot, lm):
+        nb, commit, done, started = self.header(slot)
+        if not started:
+            return _Entries.fresh(lm), 0, 0
+        a64, a32 = self._arrays(slot)
+        e = _Entries()
+        for k, n in enumerate(_Entries.names64):
+            v = a64[k, :nb].copy()
+            setattr(e, n, v.view(np.uint64) if n in _Entries.unsigned else v)
+        for k, n in enumerate(_Entries.names32):
+            setattr(e, n, a32[k, :nb].copy())
+        return e, commit, done
+
+    def store(self, slot, e, commit, done):
+        a64, a32 = self._arrays(slot)
+        nb = len(e)
+        a64[:], a32[:] = 0, 0
+        for k, n in enumerate(_Entries.names64):
+            a64[k, :nb] = np.asarray(getattr(e, n)).view(np.int64) if n in _Entries.unsigned else getattr(e, n)
+        for k, n in enumerate(_Entries.names32):
+            a32[k, :nb] = getattr(e, n)
+        b = self.block[slot]
+        b[:HDR_WORDS] = 0
+        b[_H_NB], b[_H_COMMIT], b[_H_DONE], b[_H_STARTED] = nb, commit, done, 1
+
+
+def _frame(e, c32, q32, t, W, blank, tab, lm, alpha_q, beta_q):
+    """one frame of qasr.beam._search_one / _search_one_lm on the entries e (nb >= 1); returns (next entries or None when
+    no candidate lives, [(slot, parent node, label)] of the new nodes)"""
+    N = len(c32)
+    i64 = np.int64
+    pb, pnb, sc, hsh, phs, ln, last, node = e.pb, e.pnb, e.sc, e.hsh, e.phs, e.ln, e.last, e.node
+    ctx, wh, own, lmt = e.ctx, e.wh, e.own, e.lmt
+    nb = len(sc)
+    has_lm = lm is not None
+    word_mode = has_lm and lm.word_mode
+    half = 1 << (FRAC - 1)
+    c, q = c32.astype(np.int64), q32.astype(i64)
+    valid = c >= 0
+    isb = valid & (c == blank)
+    match = (last[:, None] == c[None, :]) & valid[None, :]
+    has, nl = match.any(1), match.argmax(1)
+    pm = (phs[:, None] == hsh[None, :]) & (ln[:, None] == ln[None, :] + 1)
+    hasp, ps = pm.any(1), pm.argmax(1)
+    q_l = q[nl]
+    pb_n = sc + q[isb.argmax()] if isb.any() else np.full(nb, NEG, i64)
+    ownp = has & (pnb != NEG)
+    a = np.where(ownp, q_l + np.where(ownp, pnb, 0), NEG)
+    pbase = np.where(last[ps] == last, pb[ps], sc[ps])
+    ext = has & hasp & (pbase != NEG)
+    ee = np.where(ext, q_l + np.where(ext, pbase, 0) + own, NEG)
+    pnb_n = lae(a, ee, tab)
+    sc_n = lae(pb_n, pnb_n, tab)
+    child = np.zeros((nb, N), dtype=bool)
+    sel = has & hasp
+    child[ps[sel], nl[sel]] = True
+    base = np.where(c[None, :] == last[:, None], pb[:, None], sc[:, None])
+    ok = (valid & ~isb)[None, :] & ~child & (base != NEG)
+    scored, raws = np.zeros((nb, N), dtype=bool), np.zeros((nb, N), i64)
+    if word_mode:
+        space = lm.space
+        inword = (last >= 0) & (last != space)
+        for n in np.flatnonzero(valid & (c == space)):
+            for i in np.flatnonzero(ok[:, n] & inword):
+                raws[i, n], scored[i, n] = lm.raw(int(ctx[i]), lm.lookup_word(wh[i]))[0], True
+    elif has_lm:
+        nlab, l2w = lm.n_labels, lm.label_to_word
+        wids = np.where(valid & (c < nlab), l2w[np.clip(c, 0, nlab - 1)], -1)
+        for i, n in zip(*np.nonzero(ok)):
+            raws[i, n] = lm.raw(int(ctx[i]), int(wids[n]))[0]
+        scored = ok
+    tm = np.where(scored, ((raws * alpha_q + half) >> FRAC) + beta_q, 0)
+    v = np.where(ok, np.where(ok, base, 0) + q[None, :] + tm, NEG)
+    allc = np.concatenate([sc_n[:, None], v], axis=1).ravel()
+    n_live = int((allc != NEG).sum())
+    if n_live == 0:
+        return None, []
+    order = np.argsort(-allc, kind='stable')[:min(W, n_live)]
+    src, k = order // (N + 1), order % (N + 1)
+    kept = k == 0
+    kn = np.maximum(k - 1, 0)
+    cn = c[kn]
+    o = _Entries()
+    o.pb = np.where(kept, pb_n[src], NEG)
+    o.pnb = np.where(kept, pnb_n[src], allc[order])
+    o.sc = allc[order]
+    o.hsh = np.where(kept, hsh[src], _hmix(hsh[src], cn))
+    o.phs = np.where(kept, phs[src], hsh[src])
+    o.ln = np.where(kept, ln[src], ln[src] + 1).astype(np.int32)
+    o.last = np.where(kept, last[src], cn).astype(np.int32)
+    o.node = np.where(kept, node[src], t * W + np.arange(len(order))).astype(np.int32)
+    o.own = np.where(kept, own[src], tm[src, kn])
+    o.lmt = np.where(kept, lmt[src], lmt[src] + tm[src, kn])
+    o.ctx, o.wh = ctx[src].copy(), wh[src].copy()
+    new = []
+    for s in np.flatnonzero(~kept):
+        i, n = int(src[s]), int(kn[s])
+        if has_lm:
+            if word_mode and cn[s] != lm.space:
+                o.wh[s] = _hmix(wh[i:i + 1], cn[s:s + 1])[0]
+            else:
+                o.wh[s] = 0
+                if not word_mode:
+                    o.ctx[s] = lm.raw(int(ctx[i]), int(wids[n]))[1]
+                elif scored[i, n]:
+                    o.ctx[s] = lm.raw(int(ctx[i]), lm.lookup_word(wh[i]))[1]
+        new.append((int(s), int(node[i]), int(cn[s])))
+    return o, new
+
+
+@dataclass
+class BeamStepRow:
+    """What one step gives for one row.  labels / frames: the delta; tail: the best entry's uncommitted labels (all of
+    them); end: on END rows the list of (suffix labels, score, lm_tot), best first, cut to n_best."""
+    labels: List[int] = field(default_factory=list)
+    frames: List[int] = field(default_factory=list)
+    commit_len: int = 0
+    n_live: int = 0
+    status: int = 0
+    tail: List[int] = field(default_factory=list)
+    end: Optional[list] = None
+
+
+def _walk(state: StreamBeamState, slot, nd, depth):
+    """`depth` (label, creation frame) pairs of the chain that ends in node nd, newest first"""
+    W, F = state.plan.W, state.plan.F
+    ring = state.ring(slot)
+    out = []
+    assert 0 <= depth <= F, (depth, F)                       # the plan's bound on uncommitted labels
+    for _ in range(depth):
+        assert nd >= 0, 'a chain ended above commit_len'
+        f, r = divmod(int(nd), W)
+        assert state.row_frame[slot, f % F] == f, ('a live node was overwritten', f, int(state.row_frame[slot, f % F]))
+        assert not out or f < out[-1][1], 'creation frames must rise along a chain'
+        nd, lab = int(ring[f % F, r, 0]), int(ring[f % F, r, 1])
+        out.append((lab, f))
+    return out
+
+
+def _full_labels(trail, nd):
+    out = []
+    while nd >= 0:
+        nd, lab = trail['nodes'][nd]
+        out.append(lab)
+    return out[::-1]
+
+
+def advance_host(state: StreamBeamState, slot, cand_id, cand_q, first, lo, hi, begin, end, blank, lm=None, alpha_q=0,
+                 beta_q=0) -> BeamStepRow:
+    """One row of one step under STREAM_BEAM_RULES with the status checks already passed: cand_id / cand_q int32 [Tw][N]
+    of the window whose local frame 0 is global frame `first`; frames [lo, hi) become final."""
+    plan = state.plan
+    W, F, K, Lg = plan.W, plan.F, plan.K, plan.Lg
+    tab = lae_table()
+    cid, cq = np.asarray(cand_id, dtype=np.int32), np.asarray(cand_q, dtype=np.int32)
+    assert cid.ndim == 2 and cid.shape == cq.shape and cid.shape[1] == plan.N, (cid.shape, cq.shape, plan.N)
+    if begin:
+        e, commit = _Entries.fresh(lm), 0
+        state.row_frame[slot], state.h_dead[slot] = -1, -1
+        state.trail[slot] = dict(nodes={}, committed=[])
+    else:
+        e, commit, done = state.load(slot, lm)
+        assert done == lo, (done, lo)
+    trail = state.trail[slot]
+    ring = state.ring(slot)
+    out = BeamStepRow()
+    for t in range(lo, hi):
+        if len(e) == 0:
+            break
+        nxt, new = _frame(e, cid[t - first], cq[t - first], t, W, int(blank), tab, lm, alpha_q, beta_q)
+        if nxt is None:
+            e = e.take(np.zeros(0, dtype=np.int64))
+            break
+        e = nxt
+        if new:
+            prev = int(state.row_frame[slot, t % F])
+            assert prev in (-1, t) or prev <= state.h_dead[slot], ('a ring row is overwritten while it may be live', prev, t)
+            state.row_frame[slot, t % F] = t
+        for s, parent, lab in new:
+            ring[t % F, s] = (parent, lab)
+            if state.check:
+                trail['nodes'][t * W + s] = (parent, lab)
+        if (t + 1) % K == 0 and t - Lg >= 0:
+            h = t - Lg
+            olds = []
+            for i in range(len(e)):
+                ch = _walk(state, slot, int(e.node[i]), int(e.ln[i]) - commit)
+                olds.append([(lab, f) for lab, f in ch if f <= h])
+            assert len(olds[0]) <= K, (len(olds[0]), K)
+            lab0 = [x[0] for x in olds[0]]
+            keep = np.array([[x[0] for x in o] == lab0 for o in olds], dtype=bool)
+            assert keep[0]
+            out.labels += lab0[::-1]
+            out.frames += [x[1] for x in olds[0]][::-1]
+            commit += len(lab0)                                 # never shrinks: len(old(0)) >= 0 is added
+            trail['committed'] += lab0[::-1]
+            e = e.take(np.flatnonzero(keep))
+            state.h_dead[slot] = h
+            if state.check:                                     # committed labels never change: every survivor starts with them
+                for i in range(len(e)):
+                    assert _full_labels(trail, int(e.node[i]))[:commit] == trail['committed'], 'a committed label changed'
+    state.store(slot, e, commit, hi)
+    out.n_live = len(e)
+    if end:
+        sc, lmt = e.sc.copy(), e.lmt.copy()
+        if lm is not None and lm.word_mode and len(e):
+            half = 1 << (FRAC - 1)
+            for i in np.flatnonzero((e.last >= 0) & (e.last != lm.space)):
+                tv = ((lm.raw(int(e.ctx[i]), lm.lookup_word(e.wh[i]))[0] * alpha_q + half) >> FRAC) + beta_q
+                sc[i] += tv
+                lmt[i] += tv
+            rank = np.argsort(-sc, kind='stable')
+        else:
+            rank = np.arange(len(e))
+        out.end = []
+        for i in rank[:plan.n_best]:
+            ch = _walk(state, slot, int(e.node[i]), int(e.ln[i]) - commit)[::-1]
+            out.end.append(([x[0] for x in ch], int(sc[i]), int(lmt[i]), [x[1] for x in ch]))
+        if out.end:
+            out.labels += out.end[0][0]
+            out.frames += out.end[0][3]
+            commit += len(out.end[0][0])
+        out.end = [x[:3] for x in out.end]
+    elif len(e):
+        out.tail = [x[0] for x in _walk(state, slot, int(e.node[0]), int(e.ln[0]) - commit)[::-1]]
+    out.commit_len = commit
+    assert len(out.labels) <= plan.delta_pitch or hi - lo > plan.max_final_frames, (len(out.labels), plan.delta_pitch)
+    return out
+
+
+@dataclass
+class BeamStepBatch:
+    """k_stream_beam's outputs: labels / frames [B][P]; n_new_labels, commit_len, n_live, status [B]; tail_labels
+    [B][Ptail], tail_n [B] (the true count); end_labels [B][n_best][Pend], end_n_labels [B][n_best], end_score int64
+    [B][n_best], end_lm_score int64 [B][n_best] (None without a model), n_hyps [B]."""
+    labels: object
+    frames: object
+    n_new_labels: object
+    commit_len: object
+    n_live: object
+    status: object
+    tail_labels: object
+    tail_n: object
+    end_labels: object
+    end_n_labels: object
+    end_score: object
+    end_lm_score: object
+    n_hyps: object
+
+
+def batch_buffers(B, plan: StreamBeamPlan, blank, with_lm, P=None, Ptail=None, Pend=None) -> BeamStepBatch:
+    """the outputs of an empty step"""
+    P = plan.delta_pitch if P is None else int(P)
+    Ptail = plan.tail_pitch if Ptail is None else int(Ptail)
+    Pend = plan.end_pitch if Pend is None else int(Pend)
+    i = lambda *s: np.zeros(s, np.int32)
+    return BeamStepBatch(np.full((B, P), blank, np.int32), i(B, P), i(B), i(B), i(B), i(B), np.full((B, Ptail), blank, np.int32),
+                         i(B), np.full((B, plan.n_best, Pend), blank, np.int32), i(B, plan.n_best),
+                         np.full((B, plan.n_best), NEG, np.int64), np.zeros((B, plan.n_best), np.int64) if with_lm else None, i(B))
+
+
+def _weights(lm, alpha, beta, blank):
+    if lm is None:
+        return 0, 0
+    from .ngram import fixed_weights
+    if lm.n_labels != int(blank):
+        raise ValueError(f'stream_beam: the model was loaded for {lm.n_labels} labels, blank is {blank}')
+    return fixed_weights(alpha, beta)
+
+
+def step_batch_host(bstate: StreamBeamState, sstate: qs.StreamState, slots, flags, cand_id, cand_q, enc_lens, first_frame,
+                    blank, lm=None, alpha=0.0, beta=0.0, P=None, Ptail=None, Pend=None) -> BeamStepBatch:
+    """The twin of one k_stream_beam launch: cand_id / cand_q int32 [B][Tw][N]; slots / flags (BEGIN, END) / enc_lens /
+    first_frame int [B].  Reads sstate (the stream blocks, BEFORE emit_batch_host advances them), updates bstate."""
+    plan, splan = bstate.plan, sstate.plan
+    alpha_q, beta_q = _weights(lm, alpha, beta, blank)
+    cid, cq = np.asarray(cand_id), np.asarray(cand_q)
+    B, Tw = cid.shape[0], cid.shape[1]
+    o = batch_buffers(B, plan, blank, lm is not None, P, Ptail, Pend)
+    P, Ptail, Pend = o.labels.shape[1], o.tail_labels.shape[1], o.end_labels.shape[2]
+    for b in range(B):
+        slot = int(slots[b])
+        if not (0 <= slot < bstate.S and slot < sstate.S):
+            o.status[b] = STATUS_SLOT
+            continue
+        first = int(first_frame[b])
+        e = max(0, min(int(enc_lens[b]), Tw))
+        end, begin = bool(int(flags[b]) & qs.END), bool(int(flags[b]) & qs.BEGIN)
+        r = max(sstate.received(slot), 0)
+        lo, hi = splan.final_range(r, sstate.frames_done(slot), first, e, end)
+        if lo < first or first < 0:
+            o.status[b] = STATUS_GAP
+            continue
+        if (0 if begin else bstate.header(slot)[2]) != lo:
+            o.status[b] = STATUS_SYNC
+            continue
+        if hi * plan.W > NODE_LIMIT:
+            o.status[b] = STATUS_NODES
+            continue
+        row = advance_host(bstate, slot, cid[b], cq[b], first, lo, hi, begin, end, blank, lm, alpha_q, beta_q)
+        n = min(len(row.labels), P)
+        o.labels[b, :n], o.frames[b, :n], o.n_new_labels[b] = row.labels[:n], row.frames[:n], n
+        o.commit_len[b], o.n_live[b] = row.commit_len, row.n_live
+        nt = min(len(row.tail), Ptail)
+        o.tail_labels[b, :nt], o.tail_n[b] = row.tail[:nt], len(row.tail)
+        if row.end is not None:
+            o.n_hyps[b] = len(row.end)
+            for h, (labs, sc, lmt) in enumerate(row.end):
+                m = min(len(labs), Pend)
+                o.end_labels[b, h, :m], o.end_n_labels[b, h], o.end_score[b, h] = labs[:m], len(labs), sc
+                if o.end_lm_score is not None:
+                    o.end_lm_score[b, h] = lmt
+    return o
+
+
+@dataclass
+class LaggedResult:
+    """lagged_search_host's outputs: committed labels and their creation frames in commit order (the END step's
+    included), and the final hypotheses best first as (labels - the committed text prepended -, score, lm_tot)."""
+    labels: List[int]
+    frames: List[int]
+    hyps: list
+    commit_len_before_end: int = 0
+
+
+def lagged_search_host(cand_id, cand_q, lim, blank, beam_width=16, n_best=None, lm=None, alpha=0.0, beta=0.0, lag=200,
+                       K=K_ROUND, cuts=None, check=True) -> LaggedResult:
+    """The whole-stream statement: cand_id / cand_q int32 [T][N] of ONE stream, its first `lim` frames searched under
+    STREAM_BEAM_RULES with a lag of `lag` frames, ended after the last.  cuts: frame indices at which the stream is cut
+    into steps (None: one step); the result does not depend on them."""
+    cid, cq = np.asarray(cand_id, dtype=np.int32), np.asarray(cand_q, dtype=np.int32)
+    lim = int(min(max(int(lim), 0), cid.shape[0]))
+    W = int(beam_width)
+    plan = StreamBeamPlan(W, W if n_best is None else n_best, cid.shape[1], lag, max(lim, 1), K)
+    alpha_q, beta_q = _weights(lm, alpha, beta, blank)
+    if lim * W > NODE_LIMIT:
+        raise ValueError(f'lagged_search_host: {lim} frames x width {W} pass the node-id limit')
+    st = StreamBeamState(1, plan, check)
+    edges = [0] + sorted(int(c) for c in (cuts or []) if 0 < int(c) < lim) + [lim]
+    labels, frames, before, row = [], [], 0, None
+    for i in range(len(edges) - 1):
+        last = i == len(edges) - 2
+        row = advance_host(st, 0, cid, cq, 0, edges[i], edges[i + 1], i == 0, last, blank, lm, alpha_q, beta_q)
+        if last:
+            before = row.commit_len - (len(row.end[0][0]) if row.end else 0)
+        labels += row.labels
+        frames += row.frames
+    head = labels[:before]
+    return LaggedResult(labels, frames, [(head + labs, sc, lmt) for labs, sc, lmt in row.end], before)
