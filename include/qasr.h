@@ -798,6 +798,65 @@ typedef struct qasr_stream_beam_args {
 } qasr_stream_beam_args;
 int qasr_stream_beam(void* stream, const qasr_stream_beam_args* args);
 
+/* ---- streaming endpointing: utterance boundaries per stream on the device -------------------------------------------------
+ * Decoder-driven: no acoustic model, no energy threshold.  The frames that a streaming step makes final say where speech is
+ * (blank against non-blank arg-max, and the frame score); integer rules over global frames cut the stream into utterances:
+ * SILENCE (1: speech seen and Fsil frames without), TIMEOUT (2: Fstart frames and no speech), MAX (3: Fmax frames, at the next
+ * blank frame), HARD (4: Fhard frames, wherever it stands) and END (5: the END row's last utterance, written even when empty).
+ * The rule, the state layout and the NumPy twin are qasr/stream_ep.py (EP_RULES), which k_stream_endpoint follows byte for
+ * byte, the state block included.  Pinned: that equality; that the records of the steps of ANY slicing of a stream,
+ * concatenated, equal the whole-stream pass (endpoints_whole_host) on every byte; that every record's score is the utt_score
+ * of its own frames.  Accuracy on speech, and every default of the façade, are not pinned.
+ *   state       the stream state of qasr_stream_push / _emit, READ-ONLY here: launch this call AFTER qasr_stream_emit of the same
+ *               rows (hi = its frames_done, n_labels = its label count)
+ *   ep_state    device memory of qasr_stream_ep_state_bytes(S) bytes, 16-byte aligned: per slot 80 words (frames_done of this
+ *               block, utt_index, utt_first, first speech frame + 1, last speech frame + 1, speech frames, labels_done, zeros,
+ *               then float32 part[(t - utt_first) % 64]).  Zeroed memory is S fresh streams.  0 bytes: S < 1.
+ *   tokens, frame_score, enc_lens, first_frame, slots, flags   what qasr_stream_emit was given; QASR_STREAM_BEGIN zeroes the
+ *               slot's block first, QASR_STREAM_END writes the END record
+ *   emit_start, emit_nframes i32 [B][P], emit_n_new_labels, emit_status i32 [B]   qasr_stream_emit's outputs of the same step
+ *   Fsil, Fstart, Fmax, Fhard   the rules in frames, 1 .. 2^24, Fhard >= Fmax; min_logp: a non-blank frame is speech when its
+ *               score >= min_logp in float32 (-inf: every non-blank frame; NaN scores are never speech)
+ *   -> records i32 [B][E][10]: index, first, end (global frames, end exclusive), speech_first, speech_last (-1: none),
+ *      speech_frames, reason, score (float32 bits: the utt_score of frame_score[first:end]), label_end (the stream's label
+ *      count up to and including this utterance: labels whose run a final frame at or before the cut closed), 0; rows behind
+ *      n_records hold zeros; n_records (<= E; EndpointPlan.max_records is never exceeded by a session's steps), status i32 [B]
+ *   status 0; 1: emit_status of the row is not 0; 2: no such slot; 3: lo > hi, lo < first_frame, or lo < hi and hi beyond
+ *      first_frame + enc_len (lo: this block's frames_done, 0 with BEGIN).  A row with a status leaves its state alone.
+ * One launch of one wave per row; plain vector stores by the work-group that owns the slot; no atomics; nothing is read back;
+ * the chain qasr_stream_emit -> qasr_stream_endpoint can be captured.
+ * QASR_ERR_ARG with nothing launched and nothing written: an unknown struct_size, a NULL pointer (all are required), what
+ * qasr_stream_emit refuses about S, B, Wl, C, Rr, samples_per_frame, Tw, P and state_bytes, E < 1, a rule outside 1 .. 2^24
+ * frames or Fhard < Fmax, a NaN min_logp, ep_state_bytes below the query, a state not 16-byte aligned. */
+#define QASR_STREAM_EP_MAX_FRAMES (1 << 24)
+#define QASR_STREAM_EP_RECORD_WORDS 10
+size_t qasr_stream_ep_state_bytes(int S);
+typedef struct qasr_stream_endpoint_args {
+  uint32_t struct_size;        /* sizeof of this struct in the caller's header */
+  int32_t S, B, Wl, C, Rr, samples_per_frame, Tw;
+  int32_t P, E, blank;         /* the delta's row pitch, the records' row pitch (in records), the blank id */
+  int32_t Fsil, Fstart, Fmax, Fhard;
+  float min_logp;
+  const void* state;
+  size_t state_bytes;
+  void* ep_state;
+  size_t ep_state_bytes;
+  const int32_t* slots;
+  const int32_t* flags;
+  const int32_t* tokens;
+  const float* frame_score;
+  const int32_t* enc_lens;
+  const int32_t* first_frame;
+  const int32_t* emit_start;
+  const int32_t* emit_nframes;
+  const int32_t* emit_n_new_labels;
+  const int32_t* emit_status;
+  int32_t* records;
+  int32_t* n_records;
+  int32_t* status;
+} qasr_stream_endpoint_args;
+int qasr_stream_endpoint(void* stream, const qasr_stream_endpoint_args* args);
+
 /* ---- streaming at any sample rate: per-stream resampler state on the device -------------------------------------------
  * In front of the sample ring above: PCM at the source's rate (int16 or float32, 1 .. 8 interleaved channels) is appended to a
  * per-slot history of channel sums, and the outputs of the polyphase resampler that have become FINAL are written into the

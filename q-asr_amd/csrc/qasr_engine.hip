@@ -1564,6 +1564,36 @@ int qasr_stream_beam(void* stream, const qasr_stream_beam_args* a) {
   return QASR_OK;
 }
 
+// ---- streaming endpointing (k_stream_endpoint, qasr_stream_ep.hip): the checks of include/qasr.h and one launch
+size_t qasr_stream_ep_state_bytes(int S) { return stream_ep_state_bytes(S); }
+
+int qasr_stream_endpoint(void* stream, const qasr_stream_endpoint_args* a) {
+  if (!a) return fail(QASR_ERR_ARG, "stream_endpoint: args is NULL");
+  if (a->struct_size != sizeof(qasr_stream_endpoint_args))
+    return fail(QASR_ERR_ARG, "stream_endpoint: struct_size %u is not %zu", a->struct_size, sizeof(qasr_stream_endpoint_args));
+  if (!a->state || !a->ep_state || !a->slots || !a->flags || !a->tokens || !a->frame_score || !a->enc_lens || !a->first_frame ||
+      !a->emit_start || !a->emit_nframes || !a->emit_n_new_labels || !a->emit_status || !a->records || !a->n_records || !a->status)
+    return fail(QASR_ERR_ARG, "stream_endpoint: every pointer is required");
+  int rc = stream_geometry("stream_endpoint", a->S, a->B, a->Wl, a->C, a->Rr, a->samples_per_frame, a->state_bytes);
+  if (rc) return rc;
+  if (a->Tw < 1 || a->P < 1) return fail(QASR_ERR_ARG, "stream_endpoint: Tw %d and P %d must be at least 1", a->Tw, a->P);
+  if (a->E < 1 || (int64_t)a->B * a->E * QASR_STREAM_EP_RECORD_WORDS >= (1ll << 31))
+    return fail(QASR_ERR_ARG, "stream_endpoint: E %d must be at least 1 (and B * E * 10 below 2^31)", a->E);
+  if (a->Fsil < 1 || a->Fstart < 1 || a->Fmax < 1 || a->Fhard < a->Fmax || a->Fsil > QASR_STREAM_EP_MAX_FRAMES ||
+      a->Fstart > QASR_STREAM_EP_MAX_FRAMES || a->Fhard > QASR_STREAM_EP_MAX_FRAMES)
+    return fail(QASR_ERR_ARG, "stream_endpoint: Fsil %d, Fstart %d, Fmax %d must lie in 1 .. 2^24 and Fhard %d in Fmax .. 2^24", a->Fsil,
+                a->Fstart, a->Fmax, a->Fhard);
+  if (a->min_logp != a->min_logp) return fail(QASR_ERR_ARG, "stream_endpoint: min_logp is NaN");
+  const size_t need = stream_ep_state_bytes(a->S);
+  if (!need || a->ep_state_bytes < need)
+    return fail(QASR_ERR_ARG, "stream_endpoint: ep_state_bytes %zu, qasr_stream_ep_state_bytes gives %zu", a->ep_state_bytes, need);
+  if (((uintptr_t)a->state | (uintptr_t)a->ep_state) & 15) return fail(QASR_ERR_ARG, "stream_endpoint: state or ep_state is not 16-byte aligned");
+  rc = launch_stream_endpoint((hipStream_t)stream, *a);
+  if (rc) return fail(rc, "stream_endpoint: launch");
+  HIPCHK(hipGetLastError());
+  return QASR_OK;
+}
+
 // ---- streaming at any sample rate (k_stream_rs_append / _fir, qasr_stream_rs.hip): the checks of include/qasr.h, two launches
 size_t qasr_stream_rs_state_bytes(int S, int hcap) { return stream_rs_state_bytes(S, hcap); }
 size_t qasr_stream_rs_work_bytes(int B) { return stream_rs_work_bytes(B); }

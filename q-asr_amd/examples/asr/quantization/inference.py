@@ -104,7 +104,28 @@ def main():
     p.add_argument("--stream_beam_lag_s", type=float, default=None, metavar='SECONDS',
                    help="(extension, needs --stream_chunk_s and --beam_width) the commit lag of the streaming beam search "
                         "(EncDecCTCModel.stream(beam=)): text older than this becomes final (default 4.0, untried on speech)")
+    p.add_argument("--stream_endpoint_silence_s", type=float, default=None, metavar='SECONDS',
+                   help="(extension, needs --stream_chunk_s) cut every stream into utterances on the device "
+                        "(EncDecCTCModel.stream(endpoint=), decoder-driven: blank against non-blank final frames): an utterance "
+                        "ends after this many seconds without speech behind speech.  The utterance count is printed and WER is "
+                        "scored on each recording's utterance texts joined by a space (nothing for Zh).  Untried on speech")
+    p.add_argument("--stream_endpoint_timeout_s", type=float, default=None, metavar='SECONDS',
+                   help="(extension, needs --stream_endpoint_silence_s) an utterance without any speech ends after this long "
+                        "(default 5.0, untried on speech)")
+    p.add_argument("--stream_max_utt_s", type=float, default=None, metavar='SECONDS',
+                   help="(extension, needs --stream_endpoint_silence_s) an utterance this long ends at the next blank frame "
+                        "(default 30.0, untried on speech)")
+    p.add_argument("--stream_hard_max_s", type=float, default=None, metavar='SECONDS',
+                   help="(extension, needs --stream_endpoint_silence_s) an utterance this long ends wherever it stands "
+                        "(default 40.0, untried on speech)")
     args = p.parse_args()
+    if args.stream_endpoint_silence_s is not None and args.stream_chunk_s is None:
+        p.error('--stream_endpoint_silence_s needs --stream_chunk_s')
+    for flag in ('stream_endpoint_timeout_s', 'stream_max_utt_s', 'stream_hard_max_s'):
+        if getattr(args, flag) is not None and args.stream_endpoint_silence_s is None:
+            p.error(f'--{flag} needs --stream_endpoint_silence_s')
+    if args.stream_endpoint_silence_s is not None and args.beam_width is not None:
+        p.error('--stream_endpoint_silence_s does not go with --beam_width: the streaming beam is not reset at a cut')
     if (args.stream_left_s is not None or args.stream_right_s is not None) and args.stream_chunk_s is None:
         p.error('--stream_left_s and --stream_right_s need --stream_chunk_s')
     if args.stream_beam_lag_s is not None and (args.stream_chunk_s is None or args.beam_width is None):
@@ -207,7 +228,7 @@ def main():
         lm_kw['boost'] = qboost.PhraseSet(qboost.read_phrase_file(args.boost_file), asr_model.decoder.vocabulary, weight=boost_weight)
     aligned, items = [], getattr(asr_model.test_dataloader().dataset, 'items', [])
     audio_s, t0 = 0.0, time.time()
-    stream_sess = None
+    stream_sess, n_utterances = None, 0
     for i, batch in enumerate(asr_model.test_dataloader()):
         if i == args.eval_early_stop:
             break
@@ -220,16 +241,32 @@ def main():
                     from qasr import stream_beam as qsb
                     stream_beam = qsb.StreamBeam(width=args.beam_width, lm=args.lm_path, alpha=alpha, beta=beta,
                                                  lag_s=4.0 if args.stream_beam_lag_s is None else args.stream_beam_lag_s)
+                stream_ep = None
+                if args.stream_endpoint_silence_s is not None:               # k_stream_endpoint behind k_stream_emit in every step
+                    from qasr import stream_ep as qse
+                    dflt = qse.Endpointing()
+                    pick = lambda v, d: d if v is None else v
+                    stream_ep = qse.Endpointing(args.stream_endpoint_silence_s, pick(args.stream_endpoint_timeout_s, dflt.start_timeout_s),
+                                                pick(args.stream_max_utt_s, dflt.max_utt_s), pick(args.stream_hard_max_s, dflt.hard_max_s))
                 try:
                     stream_sess = asr_model.stream(max_streams=args.batch_size, chunk_s=args.stream_chunk_s, tail=False,
                                                    left_s=4.0 if args.stream_left_s is None else args.stream_left_s,
                                                    right_s=0.96 if args.stream_right_s is None else args.stream_right_s,
                                                    input_rate=args.input_rate,       # int16 PCM: resampled per stream on the device
-                                                   beam=stream_beam)
+                                                   beam=stream_beam, endpoint=stream_ep)
                 except ValueError as e:
-                    p.error(f'--stream_chunk_s / --stream_left_s / --stream_right_s / --input_rate / --stream_beam_lag_s: {e}')
+                    p.error(f'--stream_chunk_s / --stream_left_s / --stream_right_s / --input_rate / --stream_beam_lag_s / '
+                            f'--stream_endpoint_silence_s and its times: {e}')
             stream_hyps = asr_model.decode_stream(signal, batch[1], session=stream_sess)
             for h in stream_hyps:
+                if stream_sess.endpoint is not None:             # a recording's utterances: texts joined (by nothing for Zh)
+                    n_utterances += len(h)
+                    sep = ' ' if ' ' in asr_model.decoder.vocabulary else ''     # (Zh: no space label)
+                    hyps.append(sep.join(u.hypothesis.text for u in h if u.hypothesis.text))
+                    if args.timestamps:
+                        words.append([list(w) for u in h for w in u.hypothesis.words])
+                        utt_scores.append([u.hypothesis.utt_score for u in h])
+                    continue
                 hyps.append(h.text)
                 if args.beam_width is not None:
                     beam_scores.append(h.utt_score)
@@ -294,6 +331,8 @@ def main():
         served = stream_sess.served
     print('path:', {'Engine': 'static integer engine (HIP)', 'DynamicRunner': 'dynamic device path (HIP)'}.get(
         served, 'host modules'))
+    if stream_sess is not None and stream_sess.endpoint is not None:
+        print('utterances:', n_utterances)
     wer_value = word_error_rate(hypotheses=hyps, references=refs)
     print('WER:', wer_value)
     if args.dump_hyps:
@@ -306,6 +345,8 @@ def main():
                 extra.update(lm_path=args.lm_path, alpha=alpha, beta=beta, lm_score=lm_scores)
             if args.boost_file is not None:
                 extra.update(boost_file=args.boost_file, boost_weight=boost_weight, boost_score=boost_scores)
+            if stream_sess is not None and stream_sess.endpoint is not None:
+                extra.update(utterances=n_utterances)
             json.dump(dict(hypotheses=hyps, references=refs, wer=wer_value, path=served, **extra), f)
     if args.align:
         import json

@@ -689,7 +689,7 @@ class EncDecCTCModel(nn.Module):
         return qstream.StreamPlan(chunk_s, left_s, right_s, lp.sample_rate, lp.samples_per_frame, lp.frames_of)
 
     def stream(self, max_streams=32, chunk_s=0.96, left_s=4.0, right_s=0.96, tail=True, sample_rate=None, beam_width=None,
-               input_rate=None, channels=1, beam=None, boost=None):
+               input_rate=None, channels=1, beam=None, boost=None, endpoint=None):
         """A streaming session (an extension; NeMo's buffered streaming, the FrameBatchASR idea, for many streams at once):
 
             sess = model.stream(max_streams=32, chunk_s=0.96, left_s=4.0, right_s=0.96)
@@ -742,9 +742,22 @@ class EncDecCTCModel(nn.Module):
         default lag of 4.0 s is untried on speech.  It composes with input_rate= unchanged: everything here sits behind
         the ring.
 
+        endpoint=qasr.stream_ep.Endpointing(silence_s=0.8, start_timeout_s=5.0, max_utt_s=30.0, hard_max_s=40.0,
+        min_logp=None): the stream is cut into utterances on the device (k_stream_endpoint behind k_stream_emit in every
+        step; qasr.stream_ep.EP_RULES states the rule).  It is decoder-driven - a final frame is speech when its arg-max is
+        not blank (and its score is at least min_logp) - with Kaldi-style integer rules over global frames: silence_s
+        without speech after speech, start_timeout_s without any speech, max_utt_s (cut at the next blank frame),
+        hard_max_s (cut wherever it stands; a run that spans the cut goes to the next utterance).  push() returns the same
+        StreamUpdates; finished utterances queue up in sess.take_utterances() as qasr.ctc.StreamUtterance(slot, index,
+        reason, start_s, end_s, speech_start_s, speech_end_s, hypothesis) - 'timeout' utterances are delivered too, with no
+        text when min_logp is unset - and the host keeps the deltas of the open utterance only.  close() returns the
+        Hypothesis of the last ('end') utterance and queues it as well.  The results do not depend on how the pushes are
+        sliced.  All five defaults are untried on speech.  It composes with input_rate= unchanged.
+
         Refused: sample_rate other than the model's (here it names the model's rate: give the source's as input_rate=),
         a rate or filter the resampler refuses, channels outside 1 .. 8, beam_width (beam search across steps is beam=),
-        boost (no phrase boosting across steps), beam= arguments outside decode(beam_width=)'s ranges."""
+        boost (no phrase boosting across steps), beam= arguments outside decode(beam_width=)'s ranges, endpoint= times the
+        plan refuses, beam= together with endpoint= (finalising and resetting the beam at a cut is not built)."""
         target = int(self.preprocessor._sample_rate)
         if sample_rate is not None and int(sample_rate) != target:
             raise ValueError(f'stream: sample_rate {sample_rate} is not the model\'s {target}: sample_rate names the model\'s rate '
@@ -789,11 +802,22 @@ class EncDecCTCModel(nn.Module):
                 bplan = qsb.StreamBeamPlan.for_stream(plan, beam)
             except ValueError as e:
                 raise ValueError('stream: beam: ' + str(e).replace('decode: ', '')) from None
-        return StreamSession(self, int(max_streams), plan, bool(tail), rs_plan, beam, bplan)
+        eplan = None
+        if endpoint is not None:
+            from qasr import stream_ep as qse
+            if not isinstance(endpoint, qse.Endpointing):
+                raise ValueError(f'stream: endpoint must be a qasr.stream_ep.Endpointing, got {type(endpoint).__name__}')
+            if beam is not None:
+                raise ValueError('stream: beam= together with endpoint= is not supported: the beam is not finalised and reset at a cut')
+            try:
+                eplan = qse.EndpointPlan.for_stream(plan, endpoint)
+            except ValueError as e:
+                raise ValueError(f'stream: endpoint: {e}') from None
+        return StreamSession(self, int(max_streams), plan, bool(tail), rs_plan, beam, bplan, endpoint, eplan)
 
     @torch.no_grad()
     def decode_stream(self, input_signal, input_signal_length, chunk_s=0.96, left_s=4.0, right_s=0.96, session=None, input_rate=None,
-                      channels=1, beam=None):
+                      channels=1, beam=None, endpoint=None):
         """A batch of complete recordings played through a streaming session, all rows side by side in pushes of chunk_s
         seconds (what inference.py --stream_chunk_s does): List[qasr.ctc.Hypothesis], one per row - the hypotheses
         stream() gives for that audio, which do not depend on the size of the pushes.
@@ -805,21 +829,29 @@ class EncDecCTCModel(nn.Module):
 
         input_rate=R, channels=C: the recordings are PCM at R Hz, [B, S * C] interleaved, lengths in frames, as for
         stream(); a session passed in carries its own.  beam=: the streaming beam search of stream(beam=); the rows are then
-        what close() returns there (a list per row with n_best > 1)."""
+        what close() returns there (a list per row with n_best > 1).  endpoint=: the endpointing of stream(endpoint=); the
+        rows are then lists of qasr.ctc.StreamUtterance, every utterance of the recording in order (utterances that were
+        waiting in a passed session's queue before the call are left there)."""
         ch = session.rs_plan.channels if session is not None and session.rs_plan is not None else int(channels)
         if input_signal.dim() != 2 or ch < 1 or input_signal.shape[1] % ch:
             raise ValueError(f'decode_stream: input_signal must be [B, S * channels], got {tuple(input_signal.shape)} for {channels} channels')
         B = input_signal.shape[0]
         lens = [min(int(n), input_signal.shape[1] // ch) for n in input_signal_length.tolist()]
         sess = session if session is not None else self.stream(max_streams=B, chunk_s=chunk_s, left_s=left_s, right_s=right_s, tail=False,
-                                                               input_rate=input_rate, channels=ch, beam=beam)
+                                                               input_rate=input_rate, channels=ch, beam=beam, endpoint=endpoint)
         try:
+            waiting = sess.take_utterances() if sess.endpoint is not None else []
             slots = [sess.open() for _ in range(B)]
             C = sess.plan.C if sess.rs_plan is None else sess.rs_plan.Ain     # about chunk_s of audio per push
             for off in range(0, max(lens + [0]), C):
                 live = [b for b in range(B) if off < lens[b]]
                 sess.push([slots[b] for b in live], input_signal[live, off * ch:(off + C) * ch], [min(C, lens[b] - off) for b in live])
-            return [sess.close(s) for s in slots]
+            hyps = [sess.close(s) for s in slots]
+            if sess.endpoint is None:
+                return hyps
+            utts = sess.take_utterances()
+            sess._utts = waiting
+            return [[u for u in utts if u.slot == s] for s in slots]
         finally:
             if session is None:
                 sess.close_all()
@@ -1169,8 +1201,10 @@ class StreamSession:
     """EncDecCTCModel.stream(): the live streams of one model.  The host keeps counts it already has (samples per stream, the
     deltas read back so far); everything a step computes from lives on the device."""
 
-    def __init__(self, model, max_streams, plan, tail, rs_plan=None, beam=None, bplan=None):
+    def __init__(self, model, max_streams, plan, tail, rs_plan=None, beam=None, bplan=None, endpoint=None, eplan=None):
         self.model, self.S, self.plan, self.tail = model, max_streams, plan, tail
+        self.endpoint, self.eplan = endpoint, eplan      # qasr.stream_ep.Endpointing / EndpointPlan: utterance boundaries
+        self._utts = []                      # finished StreamUtterances that take_utterances() has not handed out yet
         self.beam, self.bplan = beam, bplan  # qasr.stream_beam.StreamBeam / StreamBeamPlan: the beam search across steps
         self.rs_plan = rs_plan               # qasr.stream_rs.StreamResamplePlan: the streams carry PCM at another rate
         self.closing_updates = []            # (resampled streams) the StreamUpdates of steps the last close() completed
@@ -1214,7 +1248,8 @@ class StreamSession:
         slot = int(slot)
         if not 0 <= slot < self.S or slot in self._open:
             raise ValueError(f'stream: slot {slot} is already open or outside 0 .. max_streams - 1 = {self.S - 1}')
-        self._open[slot] = dict(received=0, begin=True, deltas=[], in_received=0, fmt=None, beam_begin=True)
+        self._open[slot] = dict(received=0, begin=True, deltas=[], in_received=0, fmt=None, beam_begin=True, ep_begin=True,
+                                label_base=0)
         return slot
 
     # ---- the three steps, on the device or as the twins
@@ -1238,6 +1273,9 @@ class StreamSession:
             self._win = (torch.empty(self.S, self.plan.Wl, device=device), torch.empty(self.S, device=device, dtype=torch.int32),
                          torch.empty(self.S, device=device, dtype=torch.int32))
             self._out = qengine.stream_emit_buffers(self.S, self.plan, device, tail=self.tail)
+            if self.endpoint is not None:
+                self._ep_state = qengine.stream_ep_state(self.S, device)
+                self._ep_out = qengine.stream_endpoint_buffers(self.S, self.eplan, device)
             if self.beam is not None:
                 self._bstate = qengine.stream_beam_state(self.S, self.bplan, device)
                 self._bout = qengine.stream_beam_buffers(self.S, self.bplan, device, self.beam.lm is not None)
@@ -1247,6 +1285,9 @@ class StreamSession:
                     qengine.lm_device(self.beam.lm, device)
         else:
             self._state = qstream.StreamState(self.S, self.plan)
+            if self.endpoint is not None:
+                from qasr import stream_ep as qse
+                self._ep_state = qse.EpState(self.S)
             if self.beam is not None:
                 from qasr import stream_beam as qsb
                 self._bstate = qsb.StreamBeamState(self.S, self.bplan, check=False)
@@ -1285,6 +1326,7 @@ class StreamSession:
             return ups
         for s, (lab, start, nfr, sc, _, tl) in zip(stepping, self._step(stepping, False)):
             self._open[s]['deltas'].append((lab, start, nfr, sc))
+            self._cut(s)
             ups.append(qctc.StreamUpdate(s, lab.tolist(), ''.join(vocab[i] for i in lab.tolist()),
                                          (start.astype(np.float64) * spf_s).tolist(),
                                          ((start + nfr).astype(np.float64) * spf_s).tolist(),
@@ -1347,8 +1389,55 @@ class StreamSession:
             off += rp.Ain
         return updates
 
+    def take_utterances(self):
+        """(endpoint=) the utterances that ended since the last call, in the order they ended; the queue is cleared"""
+        if self.endpoint is None:
+            raise ValueError('stream: take_utterances needs a session opened with endpoint=')
+        out, self._utts = self._utts, []
+        return out
+
+    def _cut(self, slot, records=None):
+        """(endpoint=) the records the last step wrote for `slot`: each takes its labels off the front of the slot's deltas
+        and becomes a queued StreamUtterance.  Returns the last one's Hypothesis (None: no record)."""
+        if self.endpoint is None:
+            return None
+        from qasr import ctc as qctc, stream_ep as qse
+        st, hyp = self._open[slot], None
+        vocab, spf_s = self.model.decoder.vocabulary, self.plan.seconds_per_frame()
+        for r in (self._ep_rows.pop(slot) if records is None else records):
+            (lab, start, nfr, sc), st['deltas'] = qse.split_labels(st['deltas'], st['label_base'], r[qse.R_LABEL_END])
+            st['label_base'] = int(r[qse.R_LABEL_END])
+            res = qctc.CtcResult(lab[None], np.array([len(lab)], dtype=np.int32), start[None], nfr[None], sc[None],
+                                 qse.record_score(r).reshape(1), len(vocab))
+            hyp = qctc.to_hypotheses(res, vocab, spf_s)[0]
+            sp = int(r[qse.R_SP_FIRST]) >= 0
+            self._utts.append(qctc.StreamUtterance(slot, int(r[qse.R_INDEX]), qse.REASONS[int(r[qse.R_REASON])],
+                                                   int(r[qse.R_FIRST]) * spf_s, int(r[qse.R_END]) * spf_s,
+                                                   int(r[qse.R_SP_FIRST]) * spf_s if sp else None,
+                                                   (int(r[qse.R_SP_LAST]) + 1) * spf_s if sp else None, hyp))
+        return hyp
+
+    def _endpoint(self, slots, end, sl, tok, fs, enc, first, emit, blank):
+        """(endpoint=) the endpoint launch (or its twin) behind a step's emit; keeps the rows' records for _cut"""
+        from qasr import engine as qengine, stream as qstream, stream_ep as qse
+        B = len(slots)
+        flags = [(qstream.END if end else 0) | (qstream.BEGIN if self._open[s]['ep_begin'] else 0) for s in slots]
+        for s in slots:
+            self._open[s]['ep_begin'] = False
+        if self._dev.type == 'cuda':
+            out = qse.EpStepBatch(*[getattr(self._ep_out, n)[:B] for n in ('records', 'n_records', 'status')])
+            qengine.stream_endpoint(self._state, self._ep_state, self.S, self.plan, self.eplan, sl, self._i32(flags), tok, fs, enc, first,
+                                    emit, blank, out=out)
+            o = qse.EpStepBatch(out.records.cpu().numpy(), out.n_records.cpu().numpy(), out.status.cpu().numpy())
+        else:
+            o = qse.endpoint_batch_host(self._ep_state, self._state, slots, flags, tok, fs, enc, first, emit, blank, self.eplan)
+        if int(o.status.max()) != 0:
+            raise RuntimeError(f'stream: endpoint step refused, status {o.status.tolist()} for slots {slots}')
+        self._ep_rows = {s: o.records[b, :int(o.n_records[b])].copy() for b, s in enumerate(slots)}
+
     def _step(self, slots, end):
-        """one step for `slots`: window -> forward -> emit; returns the rows' deltas as qasr.stream.StepRow-like tuples"""
+        """one step for `slots`: window -> forward -> emit (-> endpoint); returns the rows' deltas as qasr.stream.StepRow-like
+        tuples"""
         from qasr import engine as qengine, stream as qstream
         m, plan, B = self.model, self.plan, len(slots)
         blank = len(m.decoder.vocabulary)
@@ -1363,12 +1452,17 @@ class StreamSession:
             o = self._out
             fields = [f.name for f in dataclasses.fields(o)]
             out = qstream.StepBatch(*[None if getattr(o, n) is None else getattr(o, n)[:B] for n in fields])
-            qengine.stream_emit(self._state, self.S, plan, sl, fl, tok, fs, enc.to(torch.int32).contiguous(), first, blank, out=out)
+            enc = enc.to(torch.int32).contiguous()
+            qengine.stream_emit(self._state, self.S, plan, sl, fl, tok, fs, enc, first, blank, out=out)
+            if self.endpoint is not None:
+                self._endpoint(slots, end, sl, tok, fs, enc, first, out, blank)
             o = qstream.StepBatch(*[None if getattr(out, n) is None else getattr(out, n).cpu().numpy() for n in fields])
         else:
             win, wl, first = qstream.window_host(self._state, slots)
             tok, fs, enc = m._forward(torch.from_numpy(win), torch.from_numpy(wl).long(), decode='frames')
             o = qstream.emit_batch_host(self._state, slots, flags, tok.numpy(), fs.float().numpy(), enc.numpy(), first, blank)
+            if self.endpoint is not None:
+                self._endpoint(slots, end, None, tok.numpy(), fs.float().numpy(), enc.numpy(), first, o, blank)
             if not self.tail:
                 o.tail_labels = o.tail_n = None
         if int(o.status.max()) != 0:
@@ -1516,6 +1610,17 @@ class StreamSession:
             self.closing_updates = self._rounds_rs([slot], [0], zero, flush=True)
         if self.beam is not None:
             return self._close_beam(st, slot)
+        if self.endpoint is not None:        # the END utterance: what is left of the stream behind its last cut
+            from qasr import stream_ep as qse
+            try:
+                if st['received'] > 0:
+                    lab, start, nfr, sc, utt, _ = self._step([slot], True)[0]
+                    st['deltas'].append((lab, start, nfr, sc))
+                    return self._cut(slot)
+                # a stream that never received a sample has nothing to run: the END record of a fresh block
+                return self._cut(slot, [qse._record(0, 0, 0, 0, 0, 0, qse.UTT_END, np.float32(0), 0)])
+            finally:
+                self._open.pop(slot)
         self._open.pop(slot)
         utt = 0.0
         if st['received'] > 0:               # (a stream that never received a sample has nothing to run)

@@ -67,6 +67,22 @@ class Hypothesis:
     seams_s: Optional[List[float]] = None   # decode_long (qasr.longform): the times at which neighbouring windows were joined
 
 
+@dataclass
+class StreamUtterance:
+    """One finished utterance of a stream (EncDecCTCModel.stream(endpoint=), qasr.stream_ep.EP_RULES): its number in the
+    stream, why it ended ('silence' | 'timeout' | 'max' | 'hard' | 'end'), its span and the span of its speech frames in
+    seconds of the stream (None: no speech frame), and the Hypothesis of its labels - times in seconds of the stream,
+    utt_score the greedy path's log-probability over the utterance's own frames.  A 'timeout' utterance has no text."""
+    slot: int
+    index: int
+    reason: str
+    start_s: float
+    end_s: float
+    speech_start_s: Optional[float]
+    speech_end_s: Optional[float]
+    hypothesis: Hypothesis
+
+
 def _order_key(x):
     """float32 -> int32 that orders like the float on every bit pattern (-0 < +0); the order k_ctc takes maxima in"""
     b = np.ascontiguousarray(x, dtype=np.float32).view(np.int32)

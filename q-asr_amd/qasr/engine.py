@@ -24,7 +24,7 @@ SYMBOLS = ['qasr_blob_check', 'qasr_engine_create', 'qasr_engine_create_ex', 'qa
            'qasr_resample_check', 'qasr_resample', 'qasr_resample_out_samples', 'qasr_longform_cut', 'qasr_longform_stitch',
            'qasr_stream_state_bytes', 'qasr_stream_push', 'qasr_stream_window', 'qasr_stream_emit',
            'qasr_stream_rs_state_bytes', 'qasr_stream_rs_work_bytes', 'qasr_stream_rs_push',
-           'qasr_stream_beam_state_bytes', 'qasr_stream_beam',
+           'qasr_stream_beam_state_bytes', 'qasr_stream_beam', 'qasr_stream_ep_state_bytes', 'qasr_stream_endpoint',
            'qasr_last_error', 'qasr_version']
 
 _lib = None
@@ -199,6 +199,10 @@ def load_library():
         lib.qasr_stream_beam_state_bytes.argtypes = [i32, i32, i32]
         lib.qasr_stream_beam_state_bytes.restype = sz
         lib.qasr_stream_beam.argtypes = [vp, C.POINTER(StreamBeamArgs)]
+    if hasattr(lib, 'qasr_stream_endpoint'):    # (likewise)
+        lib.qasr_stream_ep_state_bytes.argtypes = [i32]
+        lib.qasr_stream_ep_state_bytes.restype = sz
+        lib.qasr_stream_endpoint.argtypes = [vp, C.POINTER(StreamEndpointArgs)]
     lib.qasr_debug_prof.argtypes = [vp]
     lib.qasr_debug_timeline.argtypes = [vp, sz]
     lib.qasr_sep_layer.argtypes = [vp, C.POINTER(SepLayerArgs), C.c_char_p, sz]
@@ -1258,6 +1262,81 @@ def stream_beam(state, bstate, S, plan, bplan, slots, flags, cand_id, cand_q, en
     with torch.cuda.device(state.device):
         _check(load_library().qasr_stream_beam(_stream_ptr(stream), C.byref(a)), 'qasr_stream_beam')
     return a._keep[2]
+
+
+class StreamEndpointArgs(C.Structure):
+    """qasr_stream_endpoint_args (include/qasr.h)"""
+    _fields_ = ([('struct_size', C.c_uint32)] +
+                [(n, C.c_int32) for n in ('S', 'B', 'Wl', 'C', 'Rr', 'samples_per_frame', 'Tw', 'P', 'E', 'blank', 'Fsil', 'Fstart',
+                                          'Fmax', 'Fhard')] +
+                [('min_logp', C.c_float), ('state', C.c_void_p), ('state_bytes', C.c_size_t), ('ep_state', C.c_void_p),
+                 ('ep_state_bytes', C.c_size_t)] +
+                [(n, C.c_void_p) for n in ('slots', 'flags', 'tokens', 'frame_score', 'enc_lens', 'first_frame', 'emit_start',
+                                           'emit_nframes', 'emit_n_new_labels', 'emit_status', 'records', 'n_records', 'status')])
+
+
+def stream_ep_state(S, device):
+    """Zeroed endpoint state of S fresh streams: an int32 tensor of qasr_stream_ep_state_bytes(S) / 4 words, [S, 80] as
+    qasr.stream_ep.EpState.block."""
+    from . import stream_ep as qe
+    n = int(load_library().qasr_stream_ep_state_bytes(int(S)))
+    if n == 0:
+        raise ValueError(f'stream_ep_state: S {S} out of range')
+    return torch.zeros(n // 4, device=device, dtype=torch.int32).view(int(S), qe.STATE_WORDS)
+
+
+def stream_endpoint_buffers(B, eplan, device, E=None):
+    """k_stream_endpoint's outputs as a qasr.stream_ep.EpStepBatch of cuda tensors"""
+    from . import stream_ep as qe
+    E = eplan.max_records if E is None else int(E)
+    i = lambda *s: torch.empty(*s, device=device, dtype=torch.int32)
+    return qe.EpStepBatch(i(B, E, qe.REC_WORDS), i(B), i(B))
+
+
+def stream_endpoint(state, ep_state, S, plan, eplan, slots, flags, tokens, frame_score, enc_lens, first_frame, emit, blank, out=None,
+                    stream=None):
+    """qasr_stream_endpoint: the endpoint rule over one step's final frames, AFTER stream_emit of the same rows gave `emit`
+    (its StepBatch of cuda tensors); tokens int32 [B, Tw], frame_score float32 [B, Tw], enc_lens / first_frame / slots /
+    flags cuda int32 [B]; state: the stream state (read-only), ep_state: stream_ep_state -> a qasr.stream_ep.EpStepBatch of
+    cuda tensors.  k_stream_endpoint, one launch, nothing read back; equal to qasr.stream_ep.endpoint_batch_host byte for
+    byte, the endpoint state included."""
+    from . import stream_ep as qe
+    lib = load_library()
+    dev = state.device
+    if tokens.dim() != 2 or tokens.dtype != torch.int32 or not tokens.is_contiguous() or not tokens.is_cuda:
+        raise ValueError(f'stream_endpoint: tokens must be a contiguous cuda int32 tensor [B, Tw], got {tokens.dtype} {tuple(tokens.shape)}')
+    B, Tw = tokens.shape
+    if frame_score.dtype != torch.float32 or not frame_score.is_contiguous() or frame_score.shape != tokens.shape:
+        raise ValueError('stream_endpoint: frame_score must be a contiguous float32 tensor of the shape of tokens')
+    for t, w in ((slots, 'slots'), (flags, 'flags'), (enc_lens, 'enc_lens'), (first_frame, 'first_frame'),
+                 (emit.n_new_labels, 'emit.n_new_labels'), (emit.status, 'emit.status')):
+        _i32dev(t, B, 'stream_endpoint: ' + w)
+    P = emit.start.shape[1]
+    for t in (emit.start, emit.nframes):
+        assert t.is_cuda and t.dtype == torch.int32 and t.is_contiguous() and tuple(t.shape) == (B, P), 'stream_endpoint: emit'
+    assert ep_state.is_cuda and ep_state.dtype == torch.int32 and ep_state.is_contiguous(), 'stream_endpoint: ep_state'
+    if out is None:
+        out = stream_endpoint_buffers(B, eplan, dev)
+    E = out.records.shape[1]
+    assert out.records.is_cuda and out.records.dtype == torch.int32 and out.records.is_contiguous() and \
+        tuple(out.records.shape) == (B, E, qe.REC_WORDS), 'stream_endpoint: out'
+    _i32dev(out.n_records, B, 'stream_endpoint: out')
+    _i32dev(out.status, B, 'stream_endpoint: out')
+    a = StreamEndpointArgs()
+    a.struct_size = C.sizeof(StreamEndpointArgs)
+    a.S, a.B, a.Wl, a.C, a.Rr, a.samples_per_frame = int(S), B, plan.Wl, plan.C, plan.Rr, plan.samples_per_frame
+    a.Tw, a.P, a.E, a.blank = Tw, P, E, int(blank)
+    a.Fsil, a.Fstart, a.Fmax, a.Fhard, a.min_logp = eplan.Fsil, eplan.Fstart, eplan.Fmax, eplan.Fhard, float(eplan.min_logp)
+    a.state, a.state_bytes = state.data_ptr(), state.numel() * state.element_size()
+    a.ep_state, a.ep_state_bytes = ep_state.data_ptr(), ep_state.numel() * ep_state.element_size()
+    a.slots, a.flags, a.tokens, a.frame_score = slots.data_ptr(), flags.data_ptr(), tokens.data_ptr(), frame_score.data_ptr()
+    a.enc_lens, a.first_frame = enc_lens.data_ptr(), first_frame.data_ptr()
+    a.emit_start, a.emit_nframes = emit.start.data_ptr(), emit.nframes.data_ptr()
+    a.emit_n_new_labels, a.emit_status = emit.n_new_labels.data_ptr(), emit.status.data_ptr()
+    a.records, a.n_records, a.status = out.records.data_ptr(), out.n_records.data_ptr(), out.status.data_ptr()
+    with torch.cuda.device(dev):
+        _check(lib.qasr_stream_endpoint(_stream_ptr(stream), C.byref(a)), 'qasr_stream_endpoint')
+    return out
 
 
 class Engine:
