@@ -798,6 +798,50 @@ typedef struct qasr_stream_beam_args {
 } qasr_stream_beam_args;
 int qasr_stream_beam(void* stream, const qasr_stream_beam_args* args);
 
+/* ---- streaming phrase boosting: per-stream hot words in the streaming beam search ---------------------------------------
+ * qasr_stream_beam with the phrase boosting of qasr_ctc_beam_boost inside the frame step: every entry of a slot's beam also
+ * keeps its automaton state and its running bonus on the device between steps.  The rule, the state layout and the NumPy twin
+ * are qasr/stream_beam.py (STREAM_BOOST_RULES, over BOOST_RULES of qasr/boost.py), which k_stream_beam_boost follows byte for
+ * byte, state block and ring included.  Pinned: that equality; that the steps of ANY slicing of a stream equal the
+ * whole-stream search (lagged_search_host(boost=)); that with Lg >= the stream's length the END rows equal
+ * qasr_ctc_beam_boost over the same candidates (labels, score, lm_score, boost_score); that with set 0 or with every weight 0
+ * every byte shared with qasr_stream_beam's layout equals it; that end_boost_score is the brute-force sum over the phrase
+ * occurrences in the hypothesis' whole text, however much of it was committed early.  Accuracy on speech is not pinned.
+ *   beam        the arguments of qasr_stream_beam, every one as documented there (beam.struct_size =
+ *               sizeof(qasr_stream_beam_args)), with two differences: beam.beam_state holds
+ *               qasr_stream_beam_boost_state_bytes(S, beam_width, F) bytes - per slot 16 header words (word 4: the slot's set +
+ *               1, 0: not boosted), 24 * beam_width words of entries (qasr_stream_beam's eight 64-bit arrays, then boost_tot;
+ *               its four 32-bit arrays, then the automaton state, then a pad of zeros), then the ring - and beam.space is the
+ *               space label of the vocabulary (-1: none) also without lm
+ *   n_sets      1 .. QASR_STREAM_BEAM_MAX_SETS phrase sets of this session
+ *   sets, set_bytes, whole_words   per set: device memory holding a packed set that passed qasr_boost_check, 16-byte
+ *               aligned, its size, and whether it was compiled for whole words (as qasr_ctc_beam_boost's boost, boost_bytes,
+ *               whole_words); entries at and behind n_sets are ignored
+ *   boost_set   i32 [B] on the device: read on QASR_STREAM_BEGIN rows only - the set the slot uses until its next BEGIN,
+ *               -1: none (the stream is searched as qasr_stream_beam searches it)
+ *   -> qasr_stream_beam's outputs, end_score including the boosting's share, and end_boost_score i64 [B][n_best]: that share
+ *      (unused rows and other steps: 0)
+ *   status      qasr_stream_beam's, and 5: a BEGIN row whose boost_set is outside -1 .. n_sets - 1.
+ * One launch; nothing is read back; the sets are arguments, not a table on the device, so that this call validates them and
+ * the chain qasr_ctc_topn -> qasr_stream_beam_boost -> qasr_stream_emit can be captured.
+ * QASR_ERR_ARG with nothing launched and nothing written: an unknown struct_size (of either struct), everything
+ * qasr_stream_beam refuses, n_sets outside 1 .. QASR_STREAM_BEAM_MAX_SETS, a NULL or not 16-byte-aligned set or set_bytes
+ * outside 128 .. 2^31 - 1, whole_words != 0 with beam.space < 0 (and beam.space < -1 or == blank), a NULL boost_set or
+ * end_boost_score, beam_state_bytes below the boosted size. */
+#define QASR_STREAM_BEAM_MAX_SETS 8
+size_t qasr_stream_beam_boost_state_bytes(int S, int beam_width, int F);
+typedef struct qasr_stream_beam_boost_args {
+  uint32_t struct_size;        /* sizeof of this struct in the caller's header */
+  int32_t n_sets;
+  qasr_stream_beam_args beam;
+  const void* sets[QASR_STREAM_BEAM_MAX_SETS];
+  size_t set_bytes[QASR_STREAM_BEAM_MAX_SETS];
+  int32_t whole_words[QASR_STREAM_BEAM_MAX_SETS];
+  const int32_t* boost_set;
+  int64_t* end_boost_score;
+} qasr_stream_beam_boost_args;
+int qasr_stream_beam_boost(void* stream, const qasr_stream_beam_boost_args* args);
+
 /* ---- streaming endpointing: utterance boundaries per stream on the device -------------------------------------------------
  * Decoder-driven: no acoustic model, no energy threshold.  The frames that a streaming step makes final say where speech is
  * (blank against non-blank arg-max, and the frame score); integer rules over global frames cut the stream into utterances:

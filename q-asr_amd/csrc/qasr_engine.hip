@@ -1564,6 +1564,79 @@ int qasr_stream_beam(void* stream, const qasr_stream_beam_args* a) {
   return QASR_OK;
 }
 
+// ---- streaming phrase boosting (k_stream_beam_boost, qasr_stream_beam_boost.hip): qasr_stream_beam's checks under this
+// call's name (that function stays as it is), the sets' checks and one launch
+size_t qasr_stream_beam_boost_state_bytes(int S, int beam_width, int F) { return stream_beam_boost_state_bytes(S, beam_width, F); }
+
+static int stream_beam_boost_checks(const qasr_stream_beam_args* a, size_t need) {
+  if (a->struct_size != sizeof(qasr_stream_beam_args))
+    return fail(QASR_ERR_ARG, "stream_beam_boost: struct_size %u is not %zu", a->struct_size, sizeof(qasr_stream_beam_args));
+  if (!a->state || !a->beam_state || !a->slots || !a->flags || !a->cand_id || !a->cand_q || !a->enc_lens || !a->first_frame ||
+      !a->lae_table || !a->labels || !a->frames || !a->n_new_labels || !a->commit_len || !a->n_live || !a->status ||
+      !a->tail_labels || !a->tail_n || !a->end_labels || !a->end_n_labels || !a->end_score || !a->n_hyps)
+    return fail(QASR_ERR_ARG, "stream_beam_boost: every pointer but lm (and end_lm_score without lm) is required");
+  int rc = stream_geometry("stream_beam_boost", a->S, a->B, a->Wl, a->C, a->Rr, a->samples_per_frame, a->state_bytes);
+  if (rc) return rc;
+  if (a->Tw < 1 || a->Tw > QASR_BEAM_MAX_FRAMES || (int64_t)a->B * a->Tw >= (1ll << 31))
+    return fail(QASR_ERR_ARG, "stream_beam_boost: Tw %d is outside 1 .. %d (or B * Tw >= 2^31)", a->Tw, QASR_BEAM_MAX_FRAMES);
+  if (a->beam_width < 1 || a->beam_width > QASR_BEAM_MAX_WIDTH)
+    return fail(QASR_ERR_ARG, "stream_beam_boost: beam_width %d is outside 1 .. %d", a->beam_width, QASR_BEAM_MAX_WIDTH);
+  if (a->N < 1 || a->N > QASR_BEAM_MAX_CANDIDATES)
+    return fail(QASR_ERR_ARG, "stream_beam_boost: N %d is outside 1 .. %d", a->N, QASR_BEAM_MAX_CANDIDATES);
+  if (a->n_best < 1 || a->n_best > a->beam_width || a->blank < 0)
+    return fail(QASR_ERR_ARG, "stream_beam_boost: n_best %d is outside 1 .. beam_width, or blank %d < 0", a->n_best, a->blank);
+  if (a->lae_entries != QASR_BEAM_TABLE_ENTRIES)
+    return fail(QASR_ERR_ARG, "stream_beam_boost: lae_entries %u is not %d", a->lae_entries, QASR_BEAM_TABLE_ENTRIES);
+  if (a->Lg < 0 || a->K < 1 || a->K > QASR_STREAM_BEAM_ROUND)
+    return fail(QASR_ERR_ARG, "stream_beam_boost: Lg %d < 0 or K %d outside 1 .. %d", a->Lg, a->K, QASR_STREAM_BEAM_ROUND);
+  if (a->F > QASR_STREAM_BEAM_MAX_RING || (int64_t)a->F < (int64_t)a->Lg + a->K)
+    return fail(QASR_ERR_ARG, "stream_beam_boost: F %d must lie in Lg + K = %lld .. %d", a->F, (long long)a->Lg + a->K, QASR_STREAM_BEAM_MAX_RING);
+  if (!need || a->beam_state_bytes < need)
+    return fail(QASR_ERR_ARG, "stream_beam_boost: beam_state_bytes %zu, qasr_stream_beam_boost_state_bytes gives %zu", a->beam_state_bytes, need);
+  if (((uintptr_t)a->state | (uintptr_t)a->beam_state) & 15) return fail(QASR_ERR_ARG, "stream_beam_boost: state or beam_state is not 16-byte aligned");
+  if (a->max_final_frames < 1 || a->max_final_frames > a->Tw)
+    return fail(QASR_ERR_ARG, "stream_beam_boost: max_final_frames %d is outside 1 .. Tw", a->max_final_frames);
+  if ((int64_t)a->P < (int64_t)a->F + a->max_final_frames || a->Ptail < 1 || a->Pend < a->F)
+    return fail(QASR_ERR_ARG, "stream_beam_boost: P %d < F + max_final_frames = %lld, Ptail %d < 1 or Pend %d < F = %d", a->P,
+                (long long)a->F + a->max_final_frames, a->Ptail, a->Pend, a->F);
+  if (a->lm) {
+    if (!a->end_lm_score) return fail(QASR_ERR_ARG, "stream_beam_boost: end_lm_score is required with lm");
+    if (((uintptr_t)a->lm & 15) != 0 || a->lm_bytes < 128 || a->lm_bytes > (size_t)INT32_MAX)
+      return fail(QASR_ERR_ARG, "stream_beam_boost: lm must be 16-byte aligned and 128 .. 2^31 - 1 bytes, got %zu", a->lm_bytes);
+    if (a->alpha_q < 0 || a->alpha_q > QASR_LM_MAX_WEIGHT || a->beta_q < -QASR_LM_MAX_WEIGHT || a->beta_q > QASR_LM_MAX_WEIGHT)
+      return fail(QASR_ERR_ARG, "stream_beam_boost: alpha_q %d outside 0 .. 16 * 2^16 or |beta_q| %d above it", a->alpha_q, a->beta_q);
+    if (a->space < -1 || a->space == a->blank)
+      return fail(QASR_ERR_ARG, "stream_beam_boost: space %d must be a label other than blank, or -1", a->space);
+  }
+  return QASR_OK;
+}
+
+int qasr_stream_beam_boost(void* stream, const qasr_stream_beam_boost_args* q) {
+  if (!q) return fail(QASR_ERR_ARG, "stream_beam_boost: args is NULL");
+  if (q->struct_size != sizeof(qasr_stream_beam_boost_args))
+    return fail(QASR_ERR_ARG, "stream_beam_boost: struct_size %u is not %zu", q->struct_size, sizeof(qasr_stream_beam_boost_args));
+  const qasr_stream_beam_args* a = &q->beam;
+  if (a->beam_width < 1 || a->beam_width > QASR_BEAM_MAX_WIDTH)
+    return fail(QASR_ERR_ARG, "stream_beam_boost: beam_width %d is outside 1 .. %d", a->beam_width, QASR_BEAM_MAX_WIDTH);
+  int rc = stream_beam_boost_checks(a, stream_beam_boost_state_bytes(a->S, a->beam_width, a->F));
+  if (rc) return rc;
+  if (q->n_sets < 1 || q->n_sets > QASR_STREAM_BEAM_MAX_SETS)
+    return fail(QASR_ERR_ARG, "stream_beam_boost: n_sets %d is outside 1 .. %d", q->n_sets, QASR_STREAM_BEAM_MAX_SETS);
+  if (!q->boost_set || !q->end_boost_score) return fail(QASR_ERR_ARG, "stream_beam_boost: boost_set and end_boost_score are required");
+  if (a->space < -1 || a->space == a->blank)
+    return fail(QASR_ERR_ARG, "stream_beam_boost: space %d must be a label other than blank, or -1", a->space);
+  for (int g = 0; g < q->n_sets; ++g) {
+    if (!q->sets[g] || ((uintptr_t)q->sets[g] & 15) != 0 || q->set_bytes[g] < 128 || q->set_bytes[g] > (size_t)INT32_MAX)
+      return fail(QASR_ERR_ARG, "stream_beam_boost: set %d must be 16-byte aligned and 128 .. 2^31 - 1 bytes, got %zu", g, q->set_bytes[g]);
+    if (q->whole_words[g] != 0 && a->space < 0)
+      return fail(QASR_ERR_ARG, "stream_beam_boost: set %d: whole words need the space label, got %d", g, a->space);
+  }
+  rc = launch_stream_beam_boost((hipStream_t)stream, *q);
+  if (rc) return fail(rc, "stream_beam_boost: launch");
+  HIPCHK(hipGetLastError());
+  return QASR_OK;
+}
+
 // ---- streaming endpointing (k_stream_endpoint, qasr_stream_ep.hip): the checks of include/qasr.h and one launch
 size_t qasr_stream_ep_state_bytes(int S) { return stream_ep_state_bytes(S); }
 

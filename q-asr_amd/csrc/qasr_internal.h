@@ -184,6 +184,9 @@ int launch_stream_emit(hipStream_t s, const qasr_stream_emit_args& a);
 // qasr_stream_beam.hip: the streaming beam search (k_stream_beam<LM>); checked by qasr_stream_beam
 size_t stream_beam_state_bytes(int S, int W, int F);
 int launch_stream_beam(hipStream_t s, const qasr_stream_beam_args& a);
+// qasr_stream_beam_boost.hip: the streaming beam search with phrase boosting (k_stream_beam_boost<LM>); checked by qasr_stream_beam_boost
+size_t stream_beam_boost_state_bytes(int S, int W, int F);
+int launch_stream_beam_boost(hipStream_t s, const qasr_stream_beam_boost_args& a);
 // qasr_stream_ep.hip: streaming endpointing (k_stream_endpoint); checked by qasr_stream_endpoint
 size_t stream_ep_state_bytes(int S);
 int launch_stream_endpoint(hipStream_t s, const qasr_stream_endpoint_args& a);

@@ -71,7 +71,8 @@ def main():
     p.add_argument("--boost_file", type=str, default=None, metavar='FILE',
                    help="(extension, needs --beam_width) phrases to boost in the beam search (hot words): one per line with an "
                         "optional <tab>weight in nats per label, '#' lines and blank lines are skipped; works with or without "
-                        "--lm_path; --dump_hyps gains `boost_score`")
+                        "--lm_path, and with --stream_chunk_s (one set for all streams, kept per stream across steps); --dump_hyps "
+                        "gains `boost_score`")
     p.add_argument("--boost_weight", type=float, default=None, help="(extension, needs --boost_file) weight of the phrases without one, 0 .. 16 (default 1.0)")
     p.add_argument("--align", type=str, default=None, metavar='OUT',
                    help="(extension) forced alignment of every manifest line's reference text against its batch's "
@@ -134,8 +135,6 @@ def main():
         for flag in ('window_s', 'align'):
             if getattr(args, flag) is not None:
                 p.error(f'--stream_chunk_s does not go with --{flag}: a streaming session steps by chunks')
-        if args.boost_file is not None:
-            p.error('--stream_chunk_s does not go with --boost_file: phrase boosting does not run across steps')
     if args.overlap_s is not None and args.window_s is None:
         p.error('--overlap_s needs --window_s')
     if args.window_s is not None and args.timestamps and args.beam_width is not None:
@@ -158,6 +157,8 @@ def main():
     boost_weight = 1.0 if args.boost_weight is None else args.boost_weight
     if not 0.0 <= boost_weight <= 16.0:
         p.error(f'--boost_weight must be 0 .. 16, got {boost_weight}')
+    if args.boost_file is not None and not os.path.isfile(args.boost_file):      # before the model is built
+        p.error(f'--boost_file {args.boost_file}: no such file')
     torch.set_grad_enabled(False)
 
     if args.asr_model.endswith('.nemo'):
@@ -240,7 +241,9 @@ def main():
                 if args.beam_width is not None:              # k_topn + k_stream_beam in front of k_stream_emit in every step
                     from qasr import stream_beam as qsb
                     stream_beam = qsb.StreamBeam(width=args.beam_width, lm=args.lm_path, alpha=alpha, beta=beta,
-                                                 lag_s=4.0 if args.stream_beam_lag_s is None else args.stream_beam_lag_s)
+                                                 lag_s=4.0 if args.stream_beam_lag_s is None else args.stream_beam_lag_s,
+                                                 boost=lm_kw.get('boost'),   # one set for all streams: k_stream_beam_boost
+                                                 boost_weight=boost_weight)
                 stream_ep = None
                 if args.stream_endpoint_silence_s is not None:               # k_stream_endpoint behind k_stream_emit in every step
                     from qasr import stream_ep as qse
@@ -271,6 +274,7 @@ def main():
                 if args.beam_width is not None:
                     beam_scores.append(h.utt_score)
                     lm_scores.append(h.lm_score)
+                    boost_scores.append(h.boost_score)
                 elif args.timestamps:
                     words.append([list(w) for w in h.words])
                     utt_scores.append(h.utt_score)

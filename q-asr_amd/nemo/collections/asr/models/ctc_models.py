@@ -742,6 +742,14 @@ class EncDecCTCModel(nn.Module):
         default lag of 4.0 s is untried on speech.  It composes with input_rate= unchanged: everything here sits behind
         the ring.
 
+        StreamBeam(..., boost=, boost_weight=1.0): phrase boosting across steps (qasr.stream_beam.STREAM_BOOST_RULES;
+        k_stream_beam_boost keeps every beam entry's automaton state and running bonus in the slot's block).  boost is a
+        list of phrases as decode(boost=) takes it, a qasr.boost.PhraseSet, or a dict of at most 8 named sets; the sets are
+        compiled against the vocabulary, packed, checked and uploaded once, here.  With one set every stream uses it and
+        sess.open(boost=False) opts a stream out; with a dict sess.open(boost='name') picks a set and None means the
+        stream is not boosted.  close() fills boost_score as decode(boost=) does; utt_score includes it, lm_score does
+        not.  A session without boost allocates, launches and stores exactly what it did.
+
         endpoint=qasr.stream_ep.Endpointing(silence_s=0.8, start_timeout_s=5.0, max_utt_s=30.0, hard_max_s=40.0,
         min_logp=None): the stream is cut into utterances on the device (k_stream_endpoint behind k_stream_emit in every
         step; qasr.stream_ep.EP_RULES states the rule).  It is decoder-driven - a final frame is speech when its arg-max is
@@ -756,8 +764,10 @@ class EncDecCTCModel(nn.Module):
 
         Refused: sample_rate other than the model's (here it names the model's rate: give the source's as input_rate=),
         a rate or filter the resampler refuses, channels outside 1 .. 8, beam_width (beam search across steps is beam=),
-        boost (no phrase boosting across steps), beam= arguments outside decode(beam_width=)'s ranges, endpoint= times the
-        plan refuses, beam= together with endpoint= (finalising and resetting the beam at a cut is not built)."""
+        boost (phrase boosting across steps is StreamBeam(boost=)), beam= arguments outside decode(beam_width=)'s ranges,
+        more than 8 phrase sets or an empty dict of them, a set that qasr.boost.PhraseSet refuses, boost_weight outside
+        0 .. 16, endpoint= times the plan refuses, beam= together with endpoint= (finalising and resetting the beam at a
+        cut is not built)."""
         target = int(self.preprocessor._sample_rate)
         if sample_rate is not None and int(sample_rate) != target:
             raise ValueError(f'stream: sample_rate {sample_rate} is not the model\'s {target}: sample_rate names the model\'s rate '
@@ -766,7 +776,8 @@ class EncDecCTCModel(nn.Module):
             raise ValueError('stream: beam_width is not an argument of stream(): give the streaming beam search as '
                              'beam=qasr.stream_beam.StreamBeam(width=...)')
         if boost is not None:
-            raise ValueError('stream: boost is not supported: phrase boosting does not run across steps')
+            raise ValueError('stream: boost is not an argument of stream(): give the phrases of the streaming beam search as '
+                             'beam=qasr.stream_beam.StreamBeam(boost=...)')
         if int(max_streams) < 1:
             raise ValueError(f'stream: max_streams must be at least 1, got {max_streams}')
         try:
@@ -793,12 +804,11 @@ class EncDecCTCModel(nn.Module):
             from qasr import stream_beam as qsb
             if not isinstance(beam, qsb.StreamBeam):
                 raise ValueError(f'stream: beam must be a qasr.stream_beam.StreamBeam, got {type(beam).__name__}')
-            if getattr(beam, 'boost', None) is not None:
-                raise ValueError('stream: boost is not supported: phrase boosting does not run across steps')
             try:
                 w, nb, n = self._beam_args(beam.width, beam.n_best, beam.cutoff_top_n)
                 lm = self._lm_args(beam.lm, beam.alpha, beam.beta)
-                beam = qsb.StreamBeam(w, nb, n, lm, float(beam.alpha), float(beam.beta), beam.lag_s)
+                sets, bw = self._stream_boost_sets(beam.boost, beam.boost_weight)
+                beam = qsb.StreamBeam(w, nb, n, lm, float(beam.alpha), float(beam.beta), beam.lag_s, sets, bw)
                 bplan = qsb.StreamBeamPlan.for_stream(plan, beam)
             except ValueError as e:
                 raise ValueError('stream: beam: ' + str(e).replace('decode: ', '')) from None
@@ -855,6 +865,30 @@ class EncDecCTCModel(nn.Module):
         finally:
             if session is None:
                 sess.close_all()
+
+    def _stream_boost_sets(self, boost, boost_weight):
+        """StreamBeam(boost=, boost_weight=) -> (None | {name: qasr.boost.PhraseSet}, weight): a single set goes under the
+        name None; every set is compiled against the model's vocabulary here, before anything is launched"""
+        from qasr import boost as qboost, stream_beam as qsb
+        w = float(boost_weight)
+        if not 0.0 <= w <= qboost.MAX_WEIGHT:                # (NaN fails both comparisons)
+            raise ValueError(f'boost_weight must be 0 .. {qboost.MAX_WEIGHT:g}, got {boost_weight}')
+        if boost is None:
+            return None, w
+        named = boost if isinstance(boost, dict) else {None: boost}
+        if not named:
+            raise ValueError('boost: the dict of phrase sets is empty')
+        if len(named) > qsb.MAX_SETS:
+            raise ValueError(f'boost: {len(named)} phrase sets, at most MAX_SETS = {qsb.MAX_SETS} per session')
+        sets = {}
+        for name, ph in named.items():
+            if name is False or (name is not None and not isinstance(name, str)):
+                raise ValueError(f'boost: the name of a phrase set must be a string, got {name!r}')
+            try:
+                sets[name] = qboost.as_phrase_set(ph, self.decoder.vocabulary, w)
+            except ValueError as e:
+                raise ValueError(str(e) if name is None else f'{e} (set {name!r})') from None
+        return sets, w
 
     @staticmethod
     def _beam_args(beam_width, n_best, cutoff_top_n):
@@ -1206,6 +1240,10 @@ class StreamSession:
         self.endpoint, self.eplan = endpoint, eplan      # qasr.stream_ep.Endpointing / EndpointPlan: utterance boundaries
         self._utts = []                      # finished StreamUtterances that take_utterances() has not handed out yet
         self.beam, self.bplan = beam, bplan  # qasr.stream_beam.StreamBeam / StreamBeamPlan: the beam search across steps
+        # phrase boosting across steps (STREAM_BOOST_RULES): the compiled sets in the order of their indices, and their names
+        named = beam.boost if beam is not None and beam.boost is not None else None
+        self._sets = None if named is None else list(named.values())
+        self._set_index = None if named is None else {name: k for k, name in enumerate(named)}
         self.rs_plan = rs_plan               # qasr.stream_rs.StreamResamplePlan: the streams carry PCM at another rate
         self.closing_updates = []            # (resampled streams) the StreamUpdates of steps the last close() completed
         self._open = {}                      # slot -> dict(received, begin, deltas)
@@ -1239,7 +1277,23 @@ class StreamSession:
             self.model._reserve_logp = logp
             self._own = False
 
-    def open(self, slot=None):
+    def open(self, slot=None, boost=None):
+        """A free slot (or `slot`) for a new stream.  boost: with StreamBeam(boost=<one set>) every stream uses the set and
+        boost=False opts this one out; with a dict of sets boost='name' picks one and None means no boosting."""
+        bset = -1
+        if self._sets is None:
+            if boost is not None and boost is not False:
+                raise ValueError(f'stream: open(boost={boost!r}): the session has no phrase set (give StreamBeam(boost=...))')
+        elif boost is False:
+            pass
+        elif None in self._set_index:        # a single set
+            if boost is not None:
+                raise ValueError(f'stream: open(boost={boost!r}): the session has one unnamed phrase set; pass nothing, or False')
+            bset = 0
+        elif boost is not None:
+            if boost not in self._set_index:
+                raise ValueError(f'stream: open(boost={boost!r}): no such phrase set (sets: {sorted(self._set_index)})')
+            bset = self._set_index[boost]
         if slot is None:
             free = [s for s in range(self.S) if s not in self._open]
             if not free:
@@ -1249,7 +1303,7 @@ class StreamSession:
         if not 0 <= slot < self.S or slot in self._open:
             raise ValueError(f'stream: slot {slot} is already open or outside 0 .. max_streams - 1 = {self.S - 1}')
         self._open[slot] = dict(received=0, begin=True, deltas=[], in_received=0, fmt=None, beam_begin=True, ep_begin=True,
-                                label_base=0)
+                                label_base=0, boost_set=bset)
         return slot
 
     # ---- the three steps, on the device or as the twins
@@ -1277,8 +1331,13 @@ class StreamSession:
                 self._ep_state = qengine.stream_ep_state(self.S, device)
                 self._ep_out = qengine.stream_endpoint_buffers(self.S, self.eplan, device)
             if self.beam is not None:
-                self._bstate = qengine.stream_beam_state(self.S, self.bplan, device)
-                self._bout = qengine.stream_beam_buffers(self.S, self.bplan, device, self.beam.lm is not None)
+                if self._sets is None:
+                    self._bstate = qengine.stream_beam_state(self.S, self.bplan, device)
+                    self._bout = qengine.stream_beam_buffers(self.S, self.bplan, device, self.beam.lm is not None)
+                else:                        # the sets: packed, checked (qasr_boost_check) and uploaded once, held here
+                    self._bstate = qengine.stream_beam_boost_state(self.S, self.bplan, device)
+                    self._bout = qengine.stream_beam_boost_buffers(self.S, self.bplan, device, self.beam.lm is not None)
+                    self._set_blobs = [qengine.boost_device(bs, device) for bs in self._sets]
                 self._cand = None
                 qengine.lae_table_device(device)                                 # the uploads, outside any capture
                 if self.beam.lm is not None:
@@ -1482,6 +1541,7 @@ class StreamSession:
         m, plan, bp, bm, B = self.model, self.plan, self.bplan, self.beam, len(slots)
         blank = len(m.decoder.vocabulary)
         flags = [(qstream.END if end else 0) | (qstream.BEGIN if self._open[s]['beam_begin'] else 0) for s in slots]
+        bset = [self._open[s]['boost_set'] for s in slots]     # read on BEGIN rows only
         for s in slots:
             self._open[s]['beam_begin'] = False
         self.steps += 1
@@ -1499,8 +1559,12 @@ class StreamSession:
             cand = qengine.ctc_topn(logp, enc, bp.N, out=tuple(t[:B] for t in self._cand))
             names = [f.name for f in dataclasses.fields(self._bout)]
             bout = qsb.BeamStepBatch(*[None if getattr(self._bout, n) is None else getattr(self._bout, n)[:B] for n in names])
-            qengine.stream_beam(self._state, self._bstate, self.S, plan, bp, sl, fl, cand[0], cand[1], enc, first, blank, bm.lm,
-                                bm.alpha, bm.beta, out=bout)
+            if self._sets is None:
+                qengine.stream_beam(self._state, self._bstate, self.S, plan, bp, sl, fl, cand[0], cand[1], enc, first, blank, bm.lm,
+                                    bm.alpha, bm.beta, out=bout)
+            else:
+                qengine.stream_beam_boost(self._state, self._bstate, self.S, plan, bp, sl, fl, cand[0], cand[1], enc, first, blank,
+                                          self._sets, self._i32(bset), bm.lm, bm.alpha, bm.beta, out=bout, blobs=self._set_blobs)
             fields = [f.name for f in dataclasses.fields(self._out)]
             eout = qstream.StepBatch(*[None if getattr(self._out, n) is None else getattr(self._out, n)[:B] for n in fields])
             qengine.stream_emit(self._state, self.S, plan, sl, fl, tok, fs, enc, first, blank, out=eout)
@@ -1512,7 +1576,8 @@ class StreamSession:
             logp = logp.float()
             fs = m._frame_scores(logp, tok)
             cid, cq = qbeam.topn_host(logp.numpy(), bp.N, enc.numpy())
-            o = qsb.step_batch_host(self._bstate, self._state, slots, flags, cid, cq, enc.numpy(), first, blank, bm.lm, bm.alpha, bm.beta)
+            o = qsb.step_batch_host(self._bstate, self._state, slots, flags, cid, cq, enc.numpy(), first, blank, bm.lm, bm.alpha, bm.beta,
+                                    boost=self._sets, boost_set=bset if self._sets is not None else None)
             est = qstream.emit_batch_host(self._state, slots, flags, tok.numpy(), fs.numpy(), enc.numpy(), first, blank).status
         if int(o.status.max()) != 0 or int(est.max()) != 0:
             raise RuntimeError(f'stream: step refused, status {o.status.tolist()} / {est.tolist()} for slots {slots}')
@@ -1520,7 +1585,8 @@ class StreamSession:
         for b in range(B):
             n = int(o.n_new_labels[b])
             ends = [(o.end_labels[b, h, :int(o.end_n_labels[b, h])].tolist(), int(o.end_score[b, h]),
-                     None if o.end_lm_score is None else int(o.end_lm_score[b, h])) for h in range(int(o.n_hyps[b]))]
+                     None if o.end_lm_score is None else int(o.end_lm_score[b, h]),
+                     None if o.end_boost_score is None else int(o.end_boost_score[b, h])) for h in range(int(o.n_hyps[b]))]
             rows.append(dict(labels=o.labels[b, :n].copy(), frames=o.frames[b, :n].copy(), commit_len=int(o.commit_len[b]),
                              tail=o.tail_labels[b, :min(int(o.tail_n[b]), o.tail_labels.shape[1])].tolist(), end=ends))
         return rows
@@ -1544,11 +1610,13 @@ class StreamSession:
                                ((fr + 1).astype(np.float64) * spf_s).tolist(), None, None, [])
         head = lab.tolist()[:len(lab) - len(ends[0][0])] if ends else lab.tolist()
         hyps = []
-        for h, (suffix, sc, lmt) in enumerate(ends):
+        for h, (suffix, sc, lmt, bt) in enumerate(ends):
             hyp = best if h == 0 else qctc.Hypothesis(text(head + suffix), head + suffix, [], [], None, None, [])
             hyp.utt_score = float(sc) / qbeam.ONE
             if lmt is not None:
                 hyp.lm_score = float(lmt) / qbeam.ONE
+            if bt is not None:
+                hyp.boost_score = float(bt) / qbeam.ONE
             hyps.append(hyp)
         if not hyps:                         # nothing was received, or the beam died: the committed text alone
             hyps = [best]

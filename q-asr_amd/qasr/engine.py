@@ -25,6 +25,7 @@ SYMBOLS = ['qasr_blob_check', 'qasr_engine_create', 'qasr_engine_create_ex', 'qa
            'qasr_stream_state_bytes', 'qasr_stream_push', 'qasr_stream_window', 'qasr_stream_emit',
            'qasr_stream_rs_state_bytes', 'qasr_stream_rs_work_bytes', 'qasr_stream_rs_push',
            'qasr_stream_beam_state_bytes', 'qasr_stream_beam', 'qasr_stream_ep_state_bytes', 'qasr_stream_endpoint',
+           'qasr_stream_beam_boost_state_bytes', 'qasr_stream_beam_boost',
            'qasr_last_error', 'qasr_version']
 
 _lib = None
@@ -199,6 +200,10 @@ def load_library():
         lib.qasr_stream_beam_state_bytes.argtypes = [i32, i32, i32]
         lib.qasr_stream_beam_state_bytes.restype = sz
         lib.qasr_stream_beam.argtypes = [vp, C.POINTER(StreamBeamArgs)]
+    if hasattr(lib, 'qasr_stream_beam_boost'):  # (likewise)
+        lib.qasr_stream_beam_boost_state_bytes.argtypes = [i32, i32, i32]
+        lib.qasr_stream_beam_boost_state_bytes.restype = sz
+        lib.qasr_stream_beam_boost.argtypes = [vp, C.POINTER(StreamBeamBoostArgs)]
     if hasattr(lib, 'qasr_stream_endpoint'):    # (likewise)
         lib.qasr_stream_ep_state_bytes.argtypes = [i32]
         lib.qasr_stream_ep_state_bytes.restype = sz
@@ -1261,6 +1266,81 @@ def stream_beam(state, bstate, S, plan, bplan, slots, flags, cand_id, cand_q, en
                          beta, out)
     with torch.cuda.device(state.device):
         _check(load_library().qasr_stream_beam(_stream_ptr(stream), C.byref(a)), 'qasr_stream_beam')
+    return a._keep[2]
+
+
+MAX_STREAM_SETS = 8                     # QASR_STREAM_BEAM_MAX_SETS
+
+
+class StreamBeamBoostArgs(C.Structure):
+    """qasr_stream_beam_boost_args (include/qasr.h)"""
+    _fields_ = [('struct_size', C.c_uint32), ('n_sets', C.c_int32), ('beam', StreamBeamArgs),
+                ('sets', C.c_void_p * MAX_STREAM_SETS), ('set_bytes', C.c_size_t * MAX_STREAM_SETS),
+                ('whole_words', C.c_int32 * MAX_STREAM_SETS), ('boost_set', C.c_void_p), ('end_boost_score', C.c_void_p)]
+
+
+def stream_beam_boost_state(S, bplan, device):
+    """stream_beam_state for a boosted plan (StreamBeamPlan(boost=True)): qasr_stream_beam_boost_state_bytes(S, W, F) / 4
+    zeroed words; `stream_beam_block` views it."""
+    if not bplan.boost:
+        raise ValueError('stream_beam_boost_state: the plan was built without boost')
+    n = int(load_library().qasr_stream_beam_boost_state_bytes(int(S), bplan.W, bplan.F))
+    if n == 0:
+        raise ValueError(f'stream_beam_boost_state: S {S}, width {bplan.W}, F {bplan.F} out of range')
+    return torch.zeros(n // 4, device=device, dtype=torch.int32)
+
+
+def stream_beam_boost_buffers(B, bplan, device, with_lm, P=None, Ptail=None, Pend=None):
+    """k_stream_beam_boost's outputs: stream_beam_buffers with end_boost_score"""
+    out = stream_beam_buffers(B, bplan, device, with_lm, P, Ptail, Pend)
+    out.end_boost_score = torch.empty(B, bplan.n_best, device=device, dtype=torch.int64)
+    return out
+
+
+def stream_beam_boost_args(state, bstate, S, plan, bplan, slots, flags, cand_id, cand_q, enc_lens, first_frame, blank, sets,
+                           boost_set, lm=None, alpha=0.0, beta=0.0, out=None, blobs=None):
+    """the filled qasr_stream_beam_boost_args of stream_beam_boost.  sets: 1 .. 8 qasr.boost.PhraseSet of the model's
+    vocabulary; each is packed, checked (qasr_boost_check) and uploaded by boost_device, once
+    (blobs: what boost_device gave for each, for a caller that holds them itself)."""
+    from . import stream_beam as sb
+    sets = sb.as_sets(sets)
+    if sets is None or not bplan.boost:
+        raise ValueError('stream_beam_boost: needs phrase sets and a plan built with boost=True')
+    for k, bs in enumerate(sets):
+        if bs.n_labels != int(blank):
+            raise ValueError(f'stream_beam_boost: phrase set {k} was compiled for {bs.n_labels} labels, blank is {blank}')
+    B = cand_id.shape[0] if cand_id.dim() == 3 else 0
+    _i32dev(boost_set, B, 'stream_beam_boost: boost_set')
+    if out is None:
+        out = stream_beam_boost_buffers(B, bplan, state.device, lm is not None)
+    t = out.end_boost_score
+    assert t is not None and t.is_cuda and t.is_contiguous() and t.dtype == torch.int64, 'stream_beam_boost: out.end_boost_score'
+    inner = stream_beam_args(state, bstate, S, plan, bplan, slots, flags, cand_id, cand_q, enc_lens, first_frame, blank, lm, alpha,
+                             beta, out)
+    blobs = [boost_device(bs, state.device) for bs in sets] if blobs is None else list(blobs)
+    assert len(blobs) == len(sets), 'stream_beam_boost: one blob per set'
+    a = StreamBeamBoostArgs()
+    a.struct_size, a.n_sets = C.sizeof(StreamBeamBoostArgs), len(sets)
+    C.memmove(C.byref(a.beam), C.byref(inner), C.sizeof(StreamBeamArgs))
+    if lm is None:
+        a.beam.space = int(sets[0].space)
+    for k, (bs, blob) in enumerate(zip(sets, blobs)):
+        a.sets[k], a.set_bytes[k], a.whole_words[k] = blob.data_ptr(), blob.numel(), int(bs.whole_words)
+    a.boost_set, a.end_boost_score = boost_set.data_ptr(), t.data_ptr()
+    a._keep = inner._keep + (blobs, boost_set)
+    return a
+
+
+def stream_beam_boost(state, bstate, S, plan, bplan, slots, flags, cand_id, cand_q, enc_lens, first_frame, blank, sets,
+                      boost_set, lm=None, alpha=0.0, beta=0.0, out=None, stream=None, blobs=None):
+    """qasr_stream_beam_boost: stream_beam with phrase boosting across steps.  sets: the session's phrase sets, boost_set cuda
+    int32 [B]: the set of each BEGIN row (-1: none); bstate: stream_beam_boost_state.  Returns a BeamStepBatch with
+    end_boost_score.  k_stream_beam_boost, one launch, nothing read back; equal to qasr.stream_beam.step_batch_host(boost=)
+    byte for byte, the beam state included.  The sets are uploaded by the first call: make that one outside a capture."""
+    a = stream_beam_boost_args(state, bstate, S, plan, bplan, slots, flags, cand_id, cand_q, enc_lens, first_frame, blank, sets,
+                               boost_set, lm, alpha, beta, out, blobs)
+    with torch.cuda.device(state.device):
+        _check(load_library().qasr_stream_beam_boost(_stream_ptr(stream), C.byref(a)), 'qasr_stream_beam_boost')
     return a._keep[2]
 
 

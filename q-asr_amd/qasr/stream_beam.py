@@ -15,7 +15,9 @@ from .beam import FRAC, MAX_N, MAX_W, NEG, _hmix, lae, lae_table
 K_ROUND = 32                            # a commit round runs after every global frame t with (t + 1) % K_ROUND == 0
 HDR_WORDS = 16
 _H_NB, _H_COMMIT, _H_DONE, _H_STARTED = 0, 1, 2, 3
-STATUS_OK, STATUS_GAP, STATUS_SLOT, STATUS_SYNC, STATUS_NODES = 0, 1, 2, 3, 4
+STATUS_OK, STATUS_GAP, STATUS_SLOT, STATUS_SYNC, STATUS_NODES, STATUS_SET = 0, 1, 2, 3, 4, 5
+_H_SET = 4                              # boosted blocks: the slot's phrase set + 1 (0: not boosted)
+MAX_SETS = 8                            # phrase sets of one session (the kernel takes them as arguments)
 NODE_LIMIT = (1 << 31) - 1
 
 STREAM_BEAM_RULES = """Frames.  A step makes the frames [lo, hi) of qasr.stream's rule final (STREAM_RULES: lo = the stream block's
@@ -58,10 +60,50 @@ Consequences, the contract: `lagged_search_host`, the whole-stream statement, eq
 steps on every byte; with Lg >= the stream's length no round fires and the result is beam_search_host's on every byte."""
 
 
+STREAM_BOOST_RULES = """Streaming phrase boosting: STREAM_BEAM_RULES with the search clause of qasr.boost.BOOST_RULES inside the frame
+step (k_stream_beam_boost<LM> of csrc/qasr_stream_beam_boost.hip).  A session has G sets, 1 <= G <= 8 (MAX_SETS), each a
+qasr.boost.PhraseSet of the same vocabulary; a slot uses one of them or none.
+
+State of a slot: 16 + 24 W words, then the ring as in STREAM_BEAM_RULES.  The 64-bit arrays are the eight of
+STREAM_BEAM_RULES, then boost_tot; the 32-bit arrays are its four, then bst (the automaton state), then one array of zeros
+(the pad that keeps the 64-bit arrays of every slot 8-byte aligned for odd W).  Header word 4: the slot's set + 1, 0: not
+boosted; words 5-15: zero.
+
+Which set.  A BEGIN row stores boost_set[row] + 1 (boost_set -1: none) in header word 4; later rows of the stream read the
+word and ignore the input.  A word outside 0 .. G reads as 0.  0 means no boosting: bst stays 0, every term is 0, boost_tot
+stays 0.  A BEGIN row whose boost_set is outside -1 .. G - 1 gets status 5 (checked after the statuses 1 - 4) and, as every
+status, leaves its state alone.
+
+Start.  A fresh entry (BEGIN, or a zeroed block) starts in the start state of the slot's set: delta(root, space) with whole
+words on, else the root; boost_tot 0.
+
+Extending an entry (state s) by a label c != blank moves to s' = delta(s, c) with the term pot[s'] - pot[s] + bank[s'], added
+where qasr.beam._search_one_boost adds it: to the score of the new prefix, into `own` (next to the model's term) and into
+boost_tot, not into lm_tot.  Blank steps and the A path add nothing.
+
+Commit round: unchanged.  It compares label sequences only; bst and boost_tot travel with the surviving entries.  The
+provisional pot of a match that has begun inside a committed stretch is NOT settled at the commit: it stays in the entry's
+score and boost_tot and is settled where BOOST_RULES settles it, at END.
+
+END is BOOST_RULES' pass, written to the outputs only (the stored state stays the beam before it): for every live entry
+of a boosted slot the virtual space step (whole words), then - pot[state], both into score and boost_tot; with a word-mode
+model the unfinished-word term in the same pass; then ONE re-ordering by score, ties by previous rank.  END rows also
+write end_boost_score (boost_tot of each reported entry).
+
+Consequences, the contract: (1) any slicing of a stream into steps equals `lagged_search_host(..., boost=)` on every byte;
+(2) with Lg >= the stream's length the END result equals beam_search_host(..., boost=) on every byte - labels, score, lm_tot,
+boost_tot; (3) with set 0, or with every weight 0, every byte that this layout shares with STREAM_BEAM_RULES' is equal to
+it; (4) for every final hypothesis boost_tot is exactly the brute-force sum of g over the phrase occurrences in its WHOLE
+text (committed text plus remainder), however much of it was committed early."""
+
+
 @dataclass
 class StreamBeam:
     """What EncDecCTCModel.stream(beam=) takes.  width, n_best, cutoff_top_n, lm, alpha, beta: as decode(beam_width=, ...).
-    lag_s: the commit lag in seconds (rounded to frames); the default of 4.0 s is untried on speech."""
+    lag_s: the commit lag in seconds (rounded to frames); the default of 4.0 s is untried on speech.  boost: phrase
+    boosting across steps (STREAM_BOOST_RULES) - a list of phrases as decode(boost=) takes it, a qasr.boost.PhraseSet, or a
+    dict of at most MAX_SETS named sets of which sess.open(boost=name) picks one; boost_weight: the default weight of
+    phrases given without one."""
     width: int = 16
     n_best: int = 1
     cutoff_top_n: int = 40
@@ -69,6 +111,8 @@ class StreamBeam:
     alpha: float = 0.0
     beta: float = 0.0
     lag_s: float = 4.0
+    boost: object = None
+    boost_weight: float = 1.0
 
 
 class StreamBeamPlan:
@@ -85,9 +129,10 @@ class StreamBeamPlan:
     Pitches.  end_pitch = tail_pitch = F (a suffix behind commit_len).  Every label a step commits was uncommitted before
     the step (<= F) or created in it (<= its final frames, one per frame along one chain): delta_pitch = F +
     max_final_frames, END steps included.
-    `walk` steps through a protocol of frames and asserts all of it on the twin."""
+    `walk` steps through a protocol of frames and asserts all of it on the twin.
+    boost: the slots carry bst and boost_tot (STREAM_BOOST_RULES' layout)."""
 
-    def __init__(self, width=16, n_best=1, cutoff_top_n=40, lag_frames=200, max_final_frames=1, K=K_ROUND):
+    def __init__(self, width=16, n_best=1, cutoff_top_n=40, lag_frames=200, max_final_frames=1, K=K_ROUND, boost=False):
         W, N, nb, Lg, K = int(width), int(cutoff_top_n), int(n_best), int(lag_frames), int(K)
         if not 1 <= W <= MAX_W:
             raise ValueError(f'StreamBeamPlan: width must be 1 .. {MAX_W}, got {W}')
@@ -104,7 +149,9 @@ class StreamBeamPlan:
         self.max_final_frames = int(max_final_frames)
         self.end_pitch = self.tail_pitch = self.F
         self.delta_pitch = self.F + self.max_final_frames
-        self.slot_words = slot_words(W, self.F)
+        self.boost = bool(boost)
+        self.ent_words = (24 if self.boost else 20) * W
+        self.slot_words = slot_words(W, self.F, self.boost)
 
     @classmethod
     def for_stream(cls, plan: qs.StreamPlan, beam: StreamBeam, K=K_ROUND):
@@ -112,19 +159,29 @@ class StreamBeamPlan:
         if not np.isfinite(lag) or lag < 0:
             raise ValueError(f'StreamBeam: lag_s {beam.lag_s} must be finite and not negative')
         return cls(beam.width, beam.n_best, beam.cutoff_top_n, int(round(lag / plan.seconds_per_frame())),
-                   max(plan.max_final_frames, 1), K)
+                   max(plan.max_final_frames, 1), K, getattr(beam, 'boost', None) is not None)
 
 
 MAX_RING = 1 << 20                      # rows of a ring (F); the C ABI refuses more
 
 
-def slot_words(W, F):
-    return HDR_WORDS + 20 * int(W) + 2 * int(F) * int(W)
+def slot_words(W, F, boost=False):
+    return HDR_WORDS + (24 if boost else 20) * int(W) + 2 * int(F) * int(W)
 
 
-def state_bytes(S, W, F):
-    """qasr_stream_beam_state_bytes(S, W, F)"""
-    return 4 * int(S) * slot_words(W, F)
+def state_bytes(S, W, F, boost=False):
+    """qasr_stream_beam_state_bytes(S, W, F); boost: qasr_stream_beam_boost_state_bytes(S, W, F)"""
+    return 4 * int(S) * slot_words(W, F, boost)
+
+
+def as_sets(boost):
+    """boost= of the twins: None, one qasr.boost.PhraseSet, or a sequence of 1 .. MAX_SETS of them -> a list (None: none)"""
+    if boost is None:
+        return None
+    sets = list(boost) if isinstance(boost, (list, tuple)) else [boost]
+    if not 1 <= len(sets) <= MAX_SETS:
+        raise ValueError(f'stream_beam: boost must be 1 .. {MAX_SETS} phrase sets, got {len(sets)}')
+    return sets
 
 
 class _Entries:
@@ -134,8 +191,10 @@ class _Entries:
     unsigned = ('hsh', 'phs', 'wh')
 
     @classmethod
-    def fresh(cls, lm):
+    def fresh(cls, lm, boosted=False, bs=None):
         e = cls()
+        if boosted:
+            e.bst, e.btot = np.array([bs.start if bs is not None else 0], np.int32), np.zeros(1, np.int64)
         i64 = np.int64
         e.pb, e.pnb, e.sc = np.array([0], i64), np.array([NEG], i64), np.array([0], i64)
         e.hsh, e.phs, e.wh = np.zeros(1, np.uint64), np.zeros(1, np.uint64), np.zeros(1, np.uint64)
@@ -149,7 +208,7 @@ class _Entries:
 
     def take(self, idx):
         o = _Entries()
-        for n in self.names64 + self.names32:
+        for n in self.names64 + self.names32 + (('btot', 'bst') if hasattr(self, 'bst') else ()):
             setattr(o, n, getattr(self, n)[idx])
         return o
 
@@ -168,7 +227,7 @@ class StreamBeamState:
 
     def ring(self, slot):
         W, F = self.plan.W, self.plan.F
-        return self.block[slot, HDR_WORDS + 20 * W:].reshape(F, W, 2)
+        return self.block[slot, HDR_WORDS + self.plan.ent_words:].reshape(F, W, 2)
 
     def header(self, slot):
         b = self.block[slot]
@@ -177,14 +236,20 @@ class StreamBeamState:
     def _arrays(self, slot):
         W = self.plan.W
         b = self.block[slot]
-        a64 = b[HDR_WORDS:HDR_WORDS + 16 * W].view(np.int64).reshape(8, W)
-        a32 = b[HDR_WORDS + 16 * W:HDR_WORDS + 20 * W].reshape(4, W)
+        n64, n32 = (9, 6) if self.plan.boost else (8, 4)
+        a64 = b[HDR_WORDS:HDR_WORDS + 2 * n64 * W].view(np.int64).reshape(n64, W)
+        a32 = b[HDR_WORDS + 2 * n64 * W:HDR_WORDS + (2 * n64 + n32) * W].reshape(n32, W)
         return a64, a32
 
-    def load(self, slot, lm):
+    def boost_set(self, slot, n_sets):
+        """header word 4 of a boosted block: the slot's set + 1; a word outside 0 .. n_sets reads as 0"""
+        g = int(self.block[slot, _H_SET]) if self.plan.boost else 0
+        return g if 0 <= g <= int(n_sets) else 0
+
+    def load(self, slot, lm, bs=None):
         nb, commit, done, started = self.header(slot)
         if not started:
-            return _Entries.fresh(lm), 0, 0
+            return _Entries.fresh(lm, self.plan.boost, bs), 0, 0
         a64, a32 = self._arrays(slot)
         e = _Entries()
         for k, n in enumerate(_Entries.names64):
@@ -192,9 +257,11 @@ class StreamBeamState:
             setattr(e, n, v.view(np.uint64) if n in _Entries.unsigned else v)
         for k, n in enumerate(_Entries.names32):
             setattr(e, n, a32[k, :nb].copy())
+        if self.plan.boost:
+            e.btot, e.bst = a64[8, :nb].copy(), a32[4, :nb].copy()
         return e, commit, done
 
-    def store(self, slot, e, commit, done):
+    def store(self, slot, e, commit, done, gset=0):
         a64, a32 = self._arrays(slot)
         nb = len(e)
         a64[:], a32[:] = 0, 0
@@ -202,14 +269,19 @@ class StreamBeamState:
             a64[k, :nb] = np.asarray(getattr(e, n)).view(np.int64) if n in _Entries.unsigned else getattr(e, n)
         for k, n in enumerate(_Entries.names32):
             a32[k, :nb] = getattr(e, n)
+        if self.plan.boost:
+            a64[8, :nb], a32[4, :nb] = e.btot, e.bst
         b = self.block[slot]
         b[:HDR_WORDS] = 0
         b[_H_NB], b[_H_COMMIT], b[_H_DONE], b[_H_STARTED] = nb, commit, done, 1
+        if self.plan.boost:
+            b[_H_SET] = gset
 
 
-def _frame(e, c32, q32, t, W, blank, tab, lm, alpha_q, beta_q):
+def _frame(e, c32, q32, t, W, blank, tab, lm, alpha_q, beta_q, bs=None):
     """one frame of qasr.beam._search_one / _search_one_lm on the entries e (nb >= 1); returns (next entries or None when
-    no candidate lives, [(slot, parent node, label)] of the new nodes)"""
+    no candidate lives, [(slot, parent node, label)] of the new nodes).  Entries that carry bst / btot (a boosted plan)
+    keep them; bs: the slot's PhraseSet, and the frame is _search_one_boost's (None: every boost term is 0)."""
     N = len(c32)
     i64 = np.int64
     pb, pnb, sc, hsh, phs, ln, last, node = e.pb, e.pnb, e.sc, e.hsh, e.phs, e.ln, e.last, e.node
@@ -253,7 +325,16 @@ def _frame(e, c32, q32, t, W, blank, tab, lm, alpha_q, beta_q):
             raws[i, n] = lm.raw(int(ctx[i]), int(wids[n]))[0]
         scored = ok
     tm = np.where(scored, ((raws * alpha_q + half) >> FRAC) + beta_q, 0)
-    v = np.where(ok, np.where(ok, base, 0) + q[None, :] + tm, NEG)
+    boosted = hasattr(e, 'bst')
+    if boosted:
+        btm, bnx = np.zeros((nb, N), i64), np.zeros((nb, N), i64)
+        if bs is not None:
+            for i, n in zip(*np.nonzero(ok)):
+                btm[i, n], bnx[i, n] = bs.term(int(e.bst[i]), int(c[n]))
+        own_new = tm + btm
+    else:
+        btm, own_new = 0, tm
+    v = np.where(ok, np.where(ok, base, 0) + q[None, :] + tm + btm, NEG)
     allc = np.concatenate([sc_n[:, None], v], axis=1).ravel()
     n_live = int((allc != NEG).sum())
     if n_live == 0:
@@ -272,7 +353,10 @@ def _frame(e, c32, q32, t, W, blank, tab, lm, alpha_q, beta_q):
     o.ln = np.where(kept, ln[src], ln[src] + 1).astype(np.int32)
     o.last = np.where(kept, last[src], cn).astype(np.int32)
     o.node = np.where(kept, node[src], t * W + np.arange(len(order))).astype(np.int32)
-    o.own = np.where(kept, own[src], tm[src, kn])
+    o.own = np.where(kept, own[src], own_new[src, kn])
+    if boosted:
+        o.btot = np.where(kept, e.btot[src], e.btot[src] + btm[src, kn])
+        o.bst = np.where(kept, e.bst[src], bnx[src, kn]).astype(np.int32)
     o.lmt = np.where(kept, lmt[src], lmt[src] + tm[src, kn])
     o.ctx, o.wh = ctx[src].copy(), wh[src].copy()
     new = []
@@ -301,7 +385,7 @@ class BeamStepRow:
     n_live: int = 0
     status: int = 0
     tail: List[int] = field(default_factory=list)
-    end: Optional[list] = None
+    end: Optional[list] = None          # boosted plans: (suffix labels, score, lm_tot, boost_tot)
 
 
 def _walk(state: StreamBeamState, slot, nd, depth):
@@ -329,20 +413,28 @@ def _full_labels(trail, nd):
 
 
 def advance_host(state: StreamBeamState, slot, cand_id, cand_q, first, lo, hi, begin, end, blank, lm=None, alpha_q=0,
-                 beta_q=0) -> BeamStepRow:
+                 beta_q=0, boost=None, boost_set=-1) -> BeamStepRow:
     """One row of one step under STREAM_BEAM_RULES with the status checks already passed: cand_id / cand_q int32 [Tw][N]
-    of the window whose local frame 0 is global frame `first`; frames [lo, hi) become final."""
+    of the window whose local frame 0 is global frame `first`; frames [lo, hi) become final.  boost: the session's phrase
+    sets (a boosted plan: STREAM_BOOST_RULES), boost_set: the set a BEGIN row gives the slot (-1: none)."""
     plan = state.plan
     W, F, K, Lg = plan.W, plan.F, plan.K, plan.Lg
     tab = lae_table()
     cid, cq = np.asarray(cand_id, dtype=np.int32), np.asarray(cand_q, dtype=np.int32)
     assert cid.ndim == 2 and cid.shape == cq.shape and cid.shape[1] == plan.N, (cid.shape, cq.shape, plan.N)
+    sets = as_sets(boost)
+    assert (sets is not None) == plan.boost, 'advance_host: boost= goes with a plan built with boost=True'
+    gset = 0
+    if sets is not None:
+        gset = int(boost_set) + 1 if begin else state.boost_set(slot, len(sets))
+        assert 0 <= gset <= len(sets), (gset, len(sets))
+    bs = sets[gset - 1] if gset else None
     if begin:
-        e, commit = _Entries.fresh(lm), 0
+        e, commit = _Entries.fresh(lm, plan.boost, bs), 0
         state.row_frame[slot], state.h_dead[slot] = -1, -1
         state.trail[slot] = dict(nodes={}, committed=[])
     else:
-        e, commit, done = state.load(slot, lm)
+        e, commit, done = state.load(slot, lm, bs)
         assert done == lo, (done, lo)
     trail = state.trail[slot]
     ring = state.ring(slot)
@@ -350,7 +442,7 @@ def advance_host(state: StreamBeamState, slot, cand_id, cand_q, first, lo, hi, b
     for t in range(lo, hi):
         if len(e) == 0:
             break
-        nxt, new = _frame(e, cid[t - first], cq[t - first], t, W, int(blank), tab, lm, alpha_q, beta_q)
+        nxt, new = _frame(e, cid[t - first], cq[t - first], t, W, int(blank), tab, lm, alpha_q, beta_q, bs)
         if nxt is None:
             e = e.take(np.zeros(0, dtype=np.int64))
             break
@@ -382,28 +474,37 @@ def advance_host(state: StreamBeamState, slot, cand_id, cand_q, first, lo, hi, b
             if state.check:                                     # committed labels never change: every survivor starts with them
                 for i in range(len(e)):
                     assert _full_labels(trail, int(e.node[i]))[:commit] == trail['committed'], 'a committed label changed'
-    state.store(slot, e, commit, hi)
+    state.store(slot, e, commit, hi, gset)
     out.n_live = len(e)
     if end:
         sc, lmt = e.sc.copy(), e.lmt.copy()
-        if lm is not None and lm.word_mode and len(e):
+        btot = e.btot.copy() if plan.boost else None
+        word_mode = lm is not None and lm.word_mode
+        if (word_mode or bs is not None) and len(e):
             half = 1 << (FRAC - 1)
-            for i in np.flatnonzero((e.last >= 0) & (e.last != lm.space)):
-                tv = ((lm.raw(int(e.ctx[i]), lm.lookup_word(e.wh[i]))[0] * alpha_q + half) >> FRAC) + beta_q
-                sc[i] += tv
-                lmt[i] += tv
+            if word_mode:
+                for i in np.flatnonzero((e.last >= 0) & (e.last != lm.space)):
+                    tv = ((lm.raw(int(e.ctx[i]), lm.lookup_word(e.wh[i]))[0] * alpha_q + half) >> FRAC) + beta_q
+                    sc[i] += tv
+                    lmt[i] += tv
+            if bs is not None:
+                for i in range(len(e)):
+                    fin = bs.finish(int(e.bst[i]))
+                    sc[i] += fin
+                    btot[i] += fin
             rank = np.argsort(-sc, kind='stable')
         else:
             rank = np.arange(len(e))
         out.end = []
         for i in rank[:plan.n_best]:
             ch = _walk(state, slot, int(e.node[i]), int(e.ln[i]) - commit)[::-1]
-            out.end.append(([x[0] for x in ch], int(sc[i]), int(lmt[i]), [x[1] for x in ch]))
+            out.end.append(([x[0] for x in ch], int(sc[i]), int(lmt[i]), [x[1] for x in ch]) +
+                           ((int(btot[i]),) if plan.boost else ()))
         if out.end:
             out.labels += out.end[0][0]
             out.frames += out.end[0][3]
             commit += len(out.end[0][0])
-        out.end = [x[:3] for x in out.end]
+        out.end = [x[:3] + x[4:] for x in out.end]
     elif len(e):
         out.tail = [x[0] for x in _walk(state, slot, int(e.node[0]), int(e.ln[0]) - commit)[::-1]]
     out.commit_len = commit
@@ -415,7 +516,8 @@ def advance_host(state: StreamBeamState, slot, cand_id, cand_q, first, lo, hi, b
 class BeamStepBatch:
     """k_stream_beam's outputs: labels / frames [B][P]; n_new_labels, commit_len, n_live, status [B]; tail_labels
     [B][Ptail], tail_n [B] (the true count); end_labels [B][n_best][Pend], end_n_labels [B][n_best], end_score int64
-    [B][n_best], end_lm_score int64 [B][n_best] (None without a model), n_hyps [B]."""
+    [B][n_best], end_lm_score int64 [B][n_best] (None without a model), n_hyps [B]; k_stream_beam_boost's also
+    end_boost_score int64 [B][n_best] (None without boost)."""
     labels: object
     frames: object
     n_new_labels: object
@@ -429,9 +531,10 @@ class BeamStepBatch:
     end_score: object
     end_lm_score: object
     n_hyps: object
+    end_boost_score: object = None
 
 
-def batch_buffers(B, plan: StreamBeamPlan, blank, with_lm, P=None, Ptail=None, Pend=None) -> BeamStepBatch:
+def batch_buffers(B, plan: StreamBeamPlan, blank, with_lm, P=None, Ptail=None, Pend=None, with_boost=False) -> BeamStepBatch:
     """the outputs of an empty step"""
     P = plan.delta_pitch if P is None else int(P)
     Ptail = plan.tail_pitch if Ptail is None else int(Ptail)
@@ -439,7 +542,8 @@ def batch_buffers(B, plan: StreamBeamPlan, blank, with_lm, P=None, Ptail=None, P
     i = lambda *s: np.zeros(s, np.int32)
     return BeamStepBatch(np.full((B, P), blank, np.int32), i(B, P), i(B), i(B), i(B), i(B), np.full((B, Ptail), blank, np.int32),
                          i(B), np.full((B, plan.n_best, Pend), blank, np.int32), i(B, plan.n_best),
-                         np.full((B, plan.n_best), NEG, np.int64), np.zeros((B, plan.n_best), np.int64) if with_lm else None, i(B))
+                         np.full((B, plan.n_best), NEG, np.int64), np.zeros((B, plan.n_best), np.int64) if with_lm else None, i(B),
+                         np.zeros((B, plan.n_best), np.int64) if with_boost else None)
 
 
 def _weights(lm, alpha, beta, blank):
@@ -452,14 +556,23 @@ def _weights(lm, alpha, beta, blank):
 
 
 def step_batch_host(bstate: StreamBeamState, sstate: qs.StreamState, slots, flags, cand_id, cand_q, enc_lens, first_frame,
-                    blank, lm=None, alpha=0.0, beta=0.0, P=None, Ptail=None, Pend=None) -> BeamStepBatch:
+                    blank, lm=None, alpha=0.0, beta=0.0, P=None, Ptail=None, Pend=None, boost=None, boost_set=None) -> BeamStepBatch:
     """The twin of one k_stream_beam launch: cand_id / cand_q int32 [B][Tw][N]; slots / flags (BEGIN, END) / enc_lens /
-    first_frame int [B].  Reads sstate (the stream blocks, BEFORE emit_batch_host advances them), updates bstate."""
+    first_frame int [B].  Reads sstate (the stream blocks, BEFORE emit_batch_host advances them), updates bstate.
+    boost: the session's phrase sets (one PhraseSet or a sequence of at most MAX_SETS) on a boosted plan - the twin of
+    k_stream_beam_boost; boost_set int [B]: the set of each BEGIN row (-1: none; None: -1 everywhere)."""
     plan, splan = bstate.plan, sstate.plan
+    sets = as_sets(boost)
+    if (sets is not None) != plan.boost:
+        raise ValueError('stream_beam: boost= goes with a plan built with boost=True')
+    for bs in sets or []:
+        if bs.n_labels != int(blank):
+            raise ValueError(f'stream_beam: the phrase set was compiled for {bs.n_labels} labels, blank is {blank}')
     alpha_q, beta_q = _weights(lm, alpha, beta, blank)
     cid, cq = np.asarray(cand_id), np.asarray(cand_q)
     B, Tw = cid.shape[0], cid.shape[1]
-    o = batch_buffers(B, plan, blank, lm is not None, P, Ptail, Pend)
+    o = batch_buffers(B, plan, blank, lm is not None, P, Ptail, Pend, sets is not None)
+    bset = np.full(B, -1, np.int64) if boost_set is None else np.asarray(boost_set, dtype=np.int64)
     P, Ptail, Pend = o.labels.shape[1], o.tail_labels.shape[1], o.end_labels.shape[2]
     for b in range(B):
         slot = int(slots[b])
@@ -480,7 +593,11 @@ def step_batch_host(bstate: StreamBeamState, sstate: qs.StreamState, slots, flag
         if hi * plan.W > NODE_LIMIT:
             o.status[b] = STATUS_NODES
             continue
-        row = advance_host(bstate, slot, cid[b], cq[b], first, lo, hi, begin, end, blank, lm, alpha_q, beta_q)
+        if sets is not None and begin and not -1 <= int(bset[b]) < len(sets):
+            o.status[b] = STATUS_SET
+            continue
+        row = advance_host(bstate, slot, cid[b], cq[b], first, lo, hi, begin, end, blank, lm, alpha_q, beta_q, sets,
+                           int(bset[b]))
         n = min(len(row.labels), P)
         o.labels[b, :n], o.frames[b, :n], o.n_new_labels[b] = row.labels[:n], row.frames[:n], n
         o.commit_len[b], o.n_live[b] = row.commit_len, row.n_live
@@ -488,7 +605,10 @@ def step_batch_host(bstate: StreamBeamState, sstate: qs.StreamState, slots, flag
         o.tail_labels[b, :nt], o.tail_n[b] = row.tail[:nt], len(row.tail)
         if row.end is not None:
             o.n_hyps[b] = len(row.end)
-            for h, (labs, sc, lmt) in enumerate(row.end):
+            for h, ent in enumerate(row.end):
+                labs, sc, lmt = ent[:3]
+                if sets is not None:
+                    o.end_boost_score[b, h] = ent[3]
                 m = min(len(labs), Pend)
                 o.end_labels[b, h, :m], o.end_n_labels[b, h], o.end_score[b, h] = labs[:m], len(labs), sc
                 if o.end_lm_score is not None:
@@ -499,7 +619,8 @@ def step_batch_host(bstate: StreamBeamState, sstate: qs.StreamState, slots, flag
 @dataclass
 class LaggedResult:
     """lagged_search_host's outputs: committed labels and their creation frames in commit order (the END step's
-    included), and the final hypotheses best first as (labels - the committed text prepended -, score, lm_tot)."""
+    included), and the final hypotheses best first as (labels - the committed text prepended -, score, lm_tot), with
+    boost= (labels, score, lm_tot, boost_tot)."""
     labels: List[int]
     frames: List[int]
     hyps: list
@@ -507,14 +628,17 @@ class LaggedResult:
 
 
 def lagged_search_host(cand_id, cand_q, lim, blank, beam_width=16, n_best=None, lm=None, alpha=0.0, beta=0.0, lag=200,
-                       K=K_ROUND, cuts=None, check=True) -> LaggedResult:
+                       K=K_ROUND, cuts=None, check=True, boost=None) -> LaggedResult:
     """The whole-stream statement: cand_id / cand_q int32 [T][N] of ONE stream, its first `lim` frames searched under
     STREAM_BEAM_RULES with a lag of `lag` frames, ended after the last.  cuts: frame indices at which the stream is cut
-    into steps (None: one step); the result does not depend on them."""
+    into steps (None: one step); the result does not depend on them.  boost: a qasr.boost.PhraseSet, and the rule is
+    STREAM_BOOST_RULES."""
     cid, cq = np.asarray(cand_id, dtype=np.int32), np.asarray(cand_q, dtype=np.int32)
     lim = int(min(max(int(lim), 0), cid.shape[0]))
     W = int(beam_width)
-    plan = StreamBeamPlan(W, W if n_best is None else n_best, cid.shape[1], lag, max(lim, 1), K)
+    plan = StreamBeamPlan(W, W if n_best is None else n_best, cid.shape[1], lag, max(lim, 1), K, boost is not None)
+    if boost is not None and boost.n_labels != int(blank):
+        raise ValueError(f'lagged_search_host: the phrase set was compiled for {boost.n_labels} labels, blank is {blank}')
     alpha_q, beta_q = _weights(lm, alpha, beta, blank)
     if lim * W > NODE_LIMIT:
         raise ValueError(f'lagged_search_host: {lim} frames x width {W} pass the node-id limit')
@@ -523,10 +647,11 @@ def lagged_search_host(cand_id, cand_q, lim, blank, beam_width=16, n_best=None, 
     labels, frames, before, row = [], [], 0, None
     for i in range(len(edges) - 1):
         last = i == len(edges) - 2
-        row = advance_host(st, 0, cid, cq, 0, edges[i], edges[i + 1], i == 0, last, blank, lm, alpha_q, beta_q)
+        row = advance_host(st, 0, cid, cq, 0, edges[i], edges[i + 1], i == 0, last, blank, lm, alpha_q, beta_q, boost,
+                           0 if boost is not None else -1)
         if last:
             before = row.commit_len - (len(row.end[0][0]) if row.end else 0)
         labels += row.labels
         frames += row.frames
     head = labels[:before]
-    return LaggedResult(labels, frames, [(head + labs, sc, lmt) for labs, sc, lmt in row.end], before)
+    return LaggedResult(labels, frames, [(head + x[0],) + tuple(x[1:]) for x in row.end], before)
