@@ -901,6 +901,56 @@ typedef struct qasr_stream_endpoint_args {
 } qasr_stream_endpoint_args;
 int qasr_stream_endpoint(void* stream, const qasr_stream_endpoint_args* args);
 
+/* ---- streaming beam endpointing: the per-stream beam finalised and reset at the cuts of qasr_stream_endpoint ---------------
+ * qasr_stream_beam / qasr_stream_beam_boost for sessions that are cut into utterances: the same frame step and commit round,
+ * and at every record of the step's qasr_stream_endpoint the END pass of those calls, written per cut, after which the slot's
+ * beam is the single fresh entry again.  The rule and the NumPy twin are qasr/stream_beam.py (STREAM_BEAM_EP_RULES), which
+ * k_stream_beam_ep<LM, BOOST> follows byte for byte, state block and ring included.  Pinned: that equality; that the steps of
+ * ANY slicing of a stream equal the whole-stream search (lagged_search_ep_host); that with Lg at or beyond the longest
+ * utterance every cut's rows equal qasr_ctc_beam[_lm|_boost] over the utterance's own frames.  Accuracy on speech is not pinned.
+ *   boost       the arguments of qasr_stream_beam_boost (boost.struct_size and boost.beam.struct_size as there), with these
+ *               differences: this call is launched AFTER qasr_stream_emit and qasr_stream_endpoint of the same rows - lo is
+ *               the beam block's own frames_done (0 with BEGIN), hi the stream block's frames_done as emit left it;
+ *               boost.n_sets == 0 selects the layout and size of qasr_stream_beam (sets, boost_set ignored), 1 .. 8 that of
+ *               qasr_stream_beam_boost; header word 5 of a slot's block counts the cuts done; end_labels, end_n_labels,
+ *               end_score, end_lm_score, n_hyps and end_boost_score are ignored (they may be NULL); commit_len and n_live
+ *               describe the beam the step leaves behind, tail_labels / tail_n its best entry on every row
+ *   E           the records' row pitch (in records) and the most cuts of one row
+ *   records, n_records, ep_status   qasr_stream_endpoint's outputs of the same step, read-only: i32 [B][E][10], [B], [B]
+ *   -> n_cuts i32 [B] (= n_records); per cut k < n_cuts: cut_n_hyps i32 [B][E], and for the first n_best entries of the beam as
+ *      the END pass orders it cut_labels i32 [B][E][n_best][Pend] (the suffix behind commit_len), cut_n_labels i32, cut_score
+ *      i64, cut_lm_score i64 (with lm), cut_boost_score i64 (with sets) [B][E][n_best]; cut_delta_end i32 [B][E]: the length of
+ *      the step's delta (labels / frames) after cut k, whose last labels are the best entry's suffix.  Unused rows: blank / 0 /
+ *      -2^62 / 0 / 0; cut_n_hyps and cut_delta_end 0.
+ *   status      qasr_stream_beam_boost's; 3 also covers lo > hi, lo < hi with hi beyond first_frame + enc_len, n_records
+ *               outside 0 .. E, record ends that fall or lie outside (lo, hi] (end == lo only with lo == hi), a first record
+ *               whose index is not the block's cut count (0 with BEGIN), and ep_status != 0.  A row with a status leaves its
+ *               state alone and writes an empty step.
+ * One launch of one work-group of 256 threads per row; plain vector stores by the work-group that owns the slot; atomics on
+ * LDS only; nothing is read back; the chain qasr_ctc_topn -> qasr_stream_emit -> qasr_stream_endpoint -> qasr_stream_beam_ep
+ * can be captured.
+ * QASR_ERR_ARG with nothing launched and nothing written: an unknown struct_size (of any of the three structs), what
+ * qasr_stream_beam_boost refuses (but for the ignored pointers, and n_sets may be 0), E < 1 or B * E * n_best * Pend >= 2^31,
+ * a NULL among records, n_records, ep_status, n_cuts, cut_n_hyps, cut_delta_end, cut_labels, cut_n_labels, cut_score,
+ * cut_lm_score with lm, cut_boost_score with sets. */
+typedef struct qasr_stream_beam_ep_args {
+  uint32_t struct_size;        /* sizeof of this struct in the caller's header */
+  int32_t E;
+  qasr_stream_beam_boost_args boost;
+  const int32_t* records;
+  const int32_t* n_records;
+  const int32_t* ep_status;
+  int32_t* n_cuts;
+  int32_t* cut_n_hyps;
+  int32_t* cut_delta_end;
+  int32_t* cut_labels;
+  int32_t* cut_n_labels;
+  int64_t* cut_score;
+  int64_t* cut_lm_score;       /* with lm */
+  int64_t* cut_boost_score;    /* with sets */
+} qasr_stream_beam_ep_args;
+int qasr_stream_beam_ep(void* stream, const qasr_stream_beam_ep_args* args);
+
 /* ---- streaming at any sample rate: per-stream resampler state on the device -------------------------------------------
  * In front of the sample ring above: PCM at the source's rate (int16 or float32, 1 .. 8 interleaved channels) is appended to a
  * per-slot history of channel sums, and the outputs of the polyphase resampler that have become FINAL are written into the

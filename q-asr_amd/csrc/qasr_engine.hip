@@ -1637,6 +1637,78 @@ int qasr_stream_beam_boost(void* stream, const qasr_stream_beam_boost_args* q) {
   return QASR_OK;
 }
 
+// ---- streaming beam endpointing (k_stream_beam_ep, qasr_stream_beam_ep.hip): qasr_stream_beam_boost's checks under this call's
+// name without the END outputs it ignores, the records' and the cut outputs' checks, and one launch
+int qasr_stream_beam_ep(void* stream, const qasr_stream_beam_ep_args* x) {
+  if (!x) return fail(QASR_ERR_ARG, "stream_beam_ep: args is NULL");
+  if (x->struct_size != sizeof(qasr_stream_beam_ep_args))
+    return fail(QASR_ERR_ARG, "stream_beam_ep: struct_size %u is not %zu", x->struct_size, sizeof(qasr_stream_beam_ep_args));
+  const qasr_stream_beam_boost_args* q = &x->boost;
+  const qasr_stream_beam_args* a = &q->beam;
+  if (q->struct_size != sizeof(qasr_stream_beam_boost_args) || a->struct_size != sizeof(qasr_stream_beam_args))
+    return fail(QASR_ERR_ARG, "stream_beam_ep: boost.struct_size %u is not %zu or boost.beam.struct_size %u is not %zu", q->struct_size,
+                sizeof(qasr_stream_beam_boost_args), a->struct_size, sizeof(qasr_stream_beam_args));
+  if (!a->state || !a->beam_state || !a->slots || !a->flags || !a->cand_id || !a->cand_q || !a->enc_lens || !a->first_frame ||
+      !a->lae_table || !a->labels || !a->frames || !a->n_new_labels || !a->commit_len || !a->n_live || !a->status ||
+      !a->tail_labels || !a->tail_n)
+    return fail(QASR_ERR_ARG, "stream_beam_ep: every pointer of the step but lm and the END outputs is required");
+  int rc = stream_geometry("stream_beam_ep", a->S, a->B, a->Wl, a->C, a->Rr, a->samples_per_frame, a->state_bytes);
+  if (rc) return rc;
+  if (a->Tw < 1 || a->Tw > QASR_BEAM_MAX_FRAMES || (int64_t)a->B * a->Tw >= (1ll << 31))
+    return fail(QASR_ERR_ARG, "stream_beam_ep: Tw %d is outside 1 .. %d (or B * Tw >= 2^31)", a->Tw, QASR_BEAM_MAX_FRAMES);
+  if (a->beam_width < 1 || a->beam_width > QASR_BEAM_MAX_WIDTH)
+    return fail(QASR_ERR_ARG, "stream_beam_ep: beam_width %d is outside 1 .. %d", a->beam_width, QASR_BEAM_MAX_WIDTH);
+  if (a->N < 1 || a->N > QASR_BEAM_MAX_CANDIDATES)
+    return fail(QASR_ERR_ARG, "stream_beam_ep: N %d is outside 1 .. %d", a->N, QASR_BEAM_MAX_CANDIDATES);
+  if (a->n_best < 1 || a->n_best > a->beam_width || a->blank < 0)
+    return fail(QASR_ERR_ARG, "stream_beam_ep: n_best %d is outside 1 .. beam_width, or blank %d < 0", a->n_best, a->blank);
+  if (a->lae_entries != QASR_BEAM_TABLE_ENTRIES)
+    return fail(QASR_ERR_ARG, "stream_beam_ep: lae_entries %u is not %d", a->lae_entries, QASR_BEAM_TABLE_ENTRIES);
+  if (a->Lg < 0 || a->K < 1 || a->K > QASR_STREAM_BEAM_ROUND)
+    return fail(QASR_ERR_ARG, "stream_beam_ep: Lg %d < 0 or K %d outside 1 .. %d", a->Lg, a->K, QASR_STREAM_BEAM_ROUND);
+  if (a->F > QASR_STREAM_BEAM_MAX_RING || (int64_t)a->F < (int64_t)a->Lg + a->K)
+    return fail(QASR_ERR_ARG, "stream_beam_ep: F %d must lie in Lg + K = %lld .. %d", a->F, (long long)a->Lg + a->K, QASR_STREAM_BEAM_MAX_RING);
+  if (q->n_sets < 0 || q->n_sets > QASR_STREAM_BEAM_MAX_SETS)
+    return fail(QASR_ERR_ARG, "stream_beam_ep: n_sets %d is outside 0 .. %d", q->n_sets, QASR_STREAM_BEAM_MAX_SETS);
+  const size_t need = q->n_sets ? stream_beam_boost_state_bytes(a->S, a->beam_width, a->F) : stream_beam_state_bytes(a->S, a->beam_width, a->F);
+  if (!need || a->beam_state_bytes < need)
+    return fail(QASR_ERR_ARG, "stream_beam_ep: beam_state_bytes %zu, the state query for %d sets gives %zu", a->beam_state_bytes, q->n_sets, need);
+  if (((uintptr_t)a->state | (uintptr_t)a->beam_state) & 15) return fail(QASR_ERR_ARG, "stream_beam_ep: state or beam_state is not 16-byte aligned");
+  if (a->max_final_frames < 1 || a->max_final_frames > a->Tw)
+    return fail(QASR_ERR_ARG, "stream_beam_ep: max_final_frames %d is outside 1 .. Tw", a->max_final_frames);
+  if ((int64_t)a->P < (int64_t)a->F + a->max_final_frames || a->Ptail < 1 || a->Pend < a->F)
+    return fail(QASR_ERR_ARG, "stream_beam_ep: P %d < F + max_final_frames = %lld, Ptail %d < 1 or Pend %d < F = %d", a->P,
+                (long long)a->F + a->max_final_frames, a->Ptail, a->Pend, a->F);
+  if (a->lm) {
+    if (!x->cut_lm_score) return fail(QASR_ERR_ARG, "stream_beam_ep: cut_lm_score is required with lm");
+    if (((uintptr_t)a->lm & 15) != 0 || a->lm_bytes < 128 || a->lm_bytes > (size_t)INT32_MAX)
+      return fail(QASR_ERR_ARG, "stream_beam_ep: lm must be 16-byte aligned and 128 .. 2^31 - 1 bytes, got %zu", a->lm_bytes);
+    if (a->alpha_q < 0 || a->alpha_q > QASR_LM_MAX_WEIGHT || a->beta_q < -QASR_LM_MAX_WEIGHT || a->beta_q > QASR_LM_MAX_WEIGHT)
+      return fail(QASR_ERR_ARG, "stream_beam_ep: alpha_q %d outside 0 .. 16 * 2^16 or |beta_q| %d above it", a->alpha_q, a->beta_q);
+  }
+  if ((a->lm || q->n_sets) && (a->space < -1 || a->space == a->blank))
+    return fail(QASR_ERR_ARG, "stream_beam_ep: space %d must be a label other than blank, or -1", a->space);
+  if (q->n_sets) {
+    if (!q->boost_set || !x->cut_boost_score) return fail(QASR_ERR_ARG, "stream_beam_ep: boost_set and cut_boost_score are required with sets");
+    for (int g = 0; g < q->n_sets; ++g) {
+      if (!q->sets[g] || ((uintptr_t)q->sets[g] & 15) != 0 || q->set_bytes[g] < 128 || q->set_bytes[g] > (size_t)INT32_MAX)
+        return fail(QASR_ERR_ARG, "stream_beam_ep: set %d must be 16-byte aligned and 128 .. 2^31 - 1 bytes, got %zu", g, q->set_bytes[g]);
+      if (q->whole_words[g] != 0 && a->space < 0)
+        return fail(QASR_ERR_ARG, "stream_beam_ep: set %d: whole words need the space label, got %d", g, a->space);
+    }
+  }
+  const int64_t cuts = (int64_t)a->B * x->E, per_cut = (int64_t)a->n_best * a->Pend;      // each below 2^62: no overflow below
+  if (x->E < 1 || cuts >= (1ll << 31) / QASR_STREAM_EP_RECORD_WORDS || per_cut >= (1ll << 31) || cuts * per_cut >= (1ll << 31))
+    return fail(QASR_ERR_ARG, "stream_beam_ep: E %d must be at least 1 (and B * E * n_best * Pend below 2^31)", x->E);
+  if (!x->records || !x->n_records || !x->ep_status || !x->n_cuts || !x->cut_n_hyps || !x->cut_delta_end || !x->cut_labels ||
+      !x->cut_n_labels || !x->cut_score)
+    return fail(QASR_ERR_ARG, "stream_beam_ep: records, n_records, ep_status and every cut output (cut_lm_score with lm, cut_boost_score with sets) are required");
+  rc = launch_stream_beam_ep((hipStream_t)stream, *x);
+  if (rc) return fail(rc, "stream_beam_ep: launch");
+  HIPCHK(hipGetLastError());
+  return QASR_OK;
+}
+
 // ---- streaming endpointing (k_stream_endpoint, qasr_stream_ep.hip): the checks of include/qasr.h and one launch
 size_t qasr_stream_ep_state_bytes(int S) { return stream_ep_state_bytes(S); }
 

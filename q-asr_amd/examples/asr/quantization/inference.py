@@ -109,7 +109,9 @@ def main():
                    help="(extension, needs --stream_chunk_s) cut every stream into utterances on the device "
                         "(EncDecCTCModel.stream(endpoint=), decoder-driven: blank against non-blank final frames): an utterance "
                         "ends after this many seconds without speech behind speech.  The utterance count is printed and WER is "
-                        "scored on each recording's utterance texts joined by a space (nothing for Zh).  Untried on speech")
+                        "scored on each recording's utterance texts joined by a space (nothing for Zh).  With --beam_width the "
+                        "endpointing goes into the StreamBeam (StreamBeam(endpoint=)): the beam is finalised and reset at "
+                        "every cut and the utterance texts are the beam's.  Untried on speech")
     p.add_argument("--stream_endpoint_timeout_s", type=float, default=None, metavar='SECONDS',
                    help="(extension, needs --stream_endpoint_silence_s) an utterance without any speech ends after this long "
                         "(default 5.0, untried on speech)")
@@ -125,8 +127,6 @@ def main():
     for flag in ('stream_endpoint_timeout_s', 'stream_max_utt_s', 'stream_hard_max_s'):
         if getattr(args, flag) is not None and args.stream_endpoint_silence_s is None:
             p.error(f'--{flag} needs --stream_endpoint_silence_s')
-    if args.stream_endpoint_silence_s is not None and args.beam_width is not None:
-        p.error('--stream_endpoint_silence_s does not go with --beam_width: the streaming beam is not reset at a cut')
     if (args.stream_left_s is not None or args.stream_right_s is not None) and args.stream_chunk_s is None:
         p.error('--stream_left_s and --stream_right_s need --stream_chunk_s')
     if args.stream_beam_lag_s is not None and (args.stream_chunk_s is None or args.beam_width is None):
@@ -251,6 +251,8 @@ def main():
                     pick = lambda v, d: d if v is None else v
                     stream_ep = qse.Endpointing(args.stream_endpoint_silence_s, pick(args.stream_endpoint_timeout_s, dflt.start_timeout_s),
                                                 pick(args.stream_max_utt_s, dflt.max_utt_s), pick(args.stream_hard_max_s, dflt.hard_max_s))
+                if stream_beam is not None and stream_ep is not None:        # k_stream_beam_ep behind emit and endpoint in every step
+                    stream_beam.endpoint, stream_ep = stream_ep, None
                 try:
                     stream_sess = asr_model.stream(max_streams=args.batch_size, chunk_s=args.stream_chunk_s, tail=False,
                                                    left_s=4.0 if args.stream_left_s is None else args.stream_left_s,
@@ -266,7 +268,11 @@ def main():
                     n_utterances += len(h)
                     sep = ' ' if ' ' in asr_model.decoder.vocabulary else ''     # (Zh: no space label)
                     hyps.append(sep.join(u.hypothesis.text for u in h if u.hypothesis.text))
-                    if args.timestamps:
+                    if args.beam_width is not None:
+                        beam_scores.append([u.hypothesis.utt_score for u in h])
+                        lm_scores.append([u.hypothesis.lm_score for u in h])
+                        boost_scores.append([u.hypothesis.boost_score for u in h])
+                    elif args.timestamps:
                         words.append([list(w) for u in h for w in u.hypothesis.words])
                         utt_scores.append([u.hypothesis.utt_score for u in h])
                     continue

@@ -762,12 +762,23 @@ class EncDecCTCModel(nn.Module):
         Hypothesis of the last ('end') utterance and queues it as well.  The results do not depend on how the pushes are
         sliced.  All five defaults are untried on speech.  It composes with input_rate= unchanged.
 
+        StreamBeam(..., endpoint=Endpointing(...)): endpointing in a beam session (qasr.stream_beam.STREAM_BEAM_EP_RULES;
+        k_stream_beam_ep).  A step is window -> forward with log-probabilities -> top-N -> emit -> endpoint -> beam: the cuts are
+        decided by the greedy arg-max as above, and at every cut the slot's beam is finalised as at END and reset to the single
+        fresh entry (LM context and boost state at their starts; the slot's phrase set stays).  push() returns the beam
+        session's StreamUpdates (tail_text behind a cut is the fresh beam's); take_utterances() delivers StreamUtterances whose
+        span, speech span and reason come from the record and whose hypothesis is the BEAM's best for that utterance - text,
+        labels, creation-frame times in seconds of the stream, utt_score / lm_score / boost_score of that utterance alone -
+        and with n_best > 1 StreamUtterance.n_best carries the list.  close() returns the 'end' utterance's hypothesis (the
+        list with n_best > 1).  A 'hard' cut can split a label's frames, so the label can show up at the end of one utterance
+        and at the start of the next; a 'timeout' utterance reports whatever the beam holds, normally nothing.
+
         Refused: sample_rate other than the model's (here it names the model's rate: give the source's as input_rate=),
         a rate or filter the resampler refuses, channels outside 1 .. 8, beam_width (beam search across steps is beam=),
         boost (phrase boosting across steps is StreamBeam(boost=)), beam= arguments outside decode(beam_width=)'s ranges,
         more than 8 phrase sets or an empty dict of them, a set that qasr.boost.PhraseSet refuses, boost_weight outside
-        0 .. 16, endpoint= times the plan refuses, beam= together with endpoint= (finalising and resetting the beam at a
-        cut is not built)."""
+        0 .. 16, endpoint= times the plan refuses, beam= together with endpoint= (the endpointing of a beam session is
+        StreamBeam(endpoint=))."""
         target = int(self.preprocessor._sample_rate)
         if sample_rate is not None and int(sample_rate) != target:
             raise ValueError(f'stream: sample_rate {sample_rate} is not the model\'s {target}: sample_rate names the model\'s rate '
@@ -808,17 +819,30 @@ class EncDecCTCModel(nn.Module):
                 w, nb, n = self._beam_args(beam.width, beam.n_best, beam.cutoff_top_n)
                 lm = self._lm_args(beam.lm, beam.alpha, beam.beta)
                 sets, bw = self._stream_boost_sets(beam.boost, beam.boost_weight)
-                beam = qsb.StreamBeam(w, nb, n, lm, float(beam.alpha), float(beam.beta), beam.lag_s, sets, bw)
+                beam = qsb.StreamBeam(w, nb, n, lm, float(beam.alpha), float(beam.beta), beam.lag_s, sets, bw, beam.endpoint)
                 bplan = qsb.StreamBeamPlan.for_stream(plan, beam)
             except ValueError as e:
                 raise ValueError('stream: beam: ' + str(e).replace('decode: ', '')) from None
         eplan = None
+        if beam is not None and beam.endpoint is not None:
+            from qasr import stream_ep as qse
+            if endpoint is not None:
+                raise ValueError('stream: beam= together with endpoint= is not supported: the session already cuts by '
+                                 'StreamBeam(endpoint=), which finalises and resets the beam at a cut')
+            if not isinstance(beam.endpoint, qse.Endpointing):
+                raise ValueError(f'stream: beam: endpoint must be a qasr.stream_ep.Endpointing, got {type(beam.endpoint).__name__}')
+            try:
+                eplan = qse.EndpointPlan.for_stream(plan, beam.endpoint)
+            except ValueError as e:
+                raise ValueError(f'stream: beam: endpoint: {e}') from None
+            return StreamSession(self, int(max_streams), plan, bool(tail), rs_plan, beam, bplan, beam.endpoint, eplan)
         if endpoint is not None:
             from qasr import stream_ep as qse
             if not isinstance(endpoint, qse.Endpointing):
                 raise ValueError(f'stream: endpoint must be a qasr.stream_ep.Endpointing, got {type(endpoint).__name__}')
             if beam is not None:
-                raise ValueError('stream: beam= together with endpoint= is not supported: the beam is not finalised and reset at a cut')
+                raise ValueError('stream: beam= together with endpoint= is not supported: give the endpointing of a beam session as '
+                                 'beam=qasr.stream_beam.StreamBeam(endpoint=...), which finalises and resets the beam at a cut')
             try:
                 eplan = qse.EndpointPlan.for_stream(plan, endpoint)
             except ValueError as e:
@@ -839,7 +863,8 @@ class EncDecCTCModel(nn.Module):
 
         input_rate=R, channels=C: the recordings are PCM at R Hz, [B, S * C] interleaved, lengths in frames, as for
         stream(); a session passed in carries its own.  beam=: the streaming beam search of stream(beam=); the rows are then
-        what close() returns there (a list per row with n_best > 1).  endpoint=: the endpointing of stream(endpoint=); the
+        what close() returns there (a list per row with n_best > 1); with StreamBeam(endpoint=) the rows are the recordings'
+        utterances, as with endpoint=.  endpoint=: the endpointing of stream(endpoint=); the
         rows are then lists of qasr.ctc.StreamUtterance, every utterance of the recording in order (utterances that were
         waiting in a passed session's queue before the call are left there)."""
         ch = session.rs_plan.channels if session is not None and session.rs_plan is not None else int(channels)
@@ -1338,6 +1363,8 @@ class StreamSession:
                     self._bstate = qengine.stream_beam_boost_state(self.S, self.bplan, device)
                     self._bout = qengine.stream_beam_boost_buffers(self.S, self.bplan, device, self.beam.lm is not None)
                     self._set_blobs = [qengine.boost_device(bs, device) for bs in self._sets]
+                if self.endpoint is not None:                                    # cuts: k_stream_beam_ep's outputs instead
+                    self._bout = qengine.stream_beam_ep_buffers(self.S, self.bplan, self.eplan.max_records, device, self.beam.lm is not None)
                 self._cand = None
                 qengine.lae_table_device(device)                                 # the uploads, outside any capture
                 if self.beam.lm is not None:
@@ -1376,9 +1403,11 @@ class StreamSession:
         from qasr import ctc as qctc
         vocab, spf_s, ups = self.model.decoder.vocabulary, self.plan.seconds_per_frame(), []
         if self.beam is not None:
-            for s, row in zip(stepping, self._step_beam(stepping, False)):
+            step = self._step_beam_ep if self.endpoint is not None else self._step_beam
+            for s, row in zip(stepping, step(stepping, False)):
                 lab, fr = row['labels'], row['frames']
-                self._open[s]['deltas'].append((lab, fr))
+                if self.endpoint is None:
+                    self._open[s]['deltas'].append((lab, fr))
                 ups.append(qctc.StreamUpdate(s, lab.tolist(), ''.join(vocab[i] for i in lab.tolist()),
                                              (fr.astype(np.float64) * spf_s).tolist(), ((fr + 1).astype(np.float64) * spf_s).tolist(),
                                              [], ''.join(vocab[i] for i in row['tail']) if self.tail else ''))
@@ -1591,10 +1620,126 @@ class StreamSession:
                              tail=o.tail_labels[b, :min(int(o.tail_n[b]), o.tail_labels.shape[1])].tolist(), end=ends))
         return rows
 
+    def _step_beam_ep(self, slots, end):
+        """one step of a beam session with StreamBeam(endpoint=) for `slots`: window -> forward with log-probabilities ->
+        top-N -> emit -> endpoint -> beam (STREAM_BEAM_EP_RULES); the step's cuts become queued StreamUtterances; returns per
+        row dict(labels, frames, tail, last) - last: the hypothesis (or n-best list) of the row's last cut, None without one"""
+        from qasr import beam as qbeam, engine as qengine, stream as qstream, stream_beam as qsb, stream_ep as qse
+        m, plan, bp, bm, B = self.model, self.plan, self.bplan, self.beam, len(slots)
+        blank = len(m.decoder.vocabulary)
+        flags = [(qstream.END if end else 0) | (qstream.BEGIN if self._open[s]['beam_begin'] else 0) for s in slots]
+        bset = [self._open[s]['boost_set'] for s in slots]     # read on BEGIN rows only
+        for s in slots:
+            self._open[s]['beam_begin'] = self._open[s]['ep_begin'] = False
+        self.steps += 1
+        if self._dev.type == 'cuda':
+            sl, fl = self._i32(slots), self._i32(flags)
+            win, wl, first = qengine.stream_window(self._state, self.S, plan, sl, out=tuple(t[:B] for t in self._win))
+            logp, enc, tok = m._forward(win, wl.long())
+            logp = logp.float()
+            tok = tok.to(torch.int32).contiguous()
+            fs = m._frame_scores(logp, tok).contiguous()
+            enc = enc.to(torch.int32).contiguous()
+            Tw = logp.shape[1]
+            if self._cand is None or self._cand[0].shape[1] != Tw:
+                self._cand = tuple(torch.empty(self.S, Tw, bp.N, device=self._dev, dtype=torch.int32) for _ in range(2))
+            cand = qengine.ctc_topn(logp, enc, bp.N, out=tuple(t[:B] for t in self._cand))
+            fields = [f.name for f in dataclasses.fields(self._out)]
+            eout = qstream.StepBatch(*[None if getattr(self._out, n) is None else getattr(self._out, n)[:B] for n in fields])
+            qengine.stream_emit(self._state, self.S, plan, sl, fl, tok, fs, enc, first, blank, out=eout)
+            pout = qse.EpStepBatch(*[getattr(self._ep_out, n)[:B] for n in ('records', 'n_records', 'status')])
+            qengine.stream_endpoint(self._state, self._ep_state, self.S, plan, self.eplan, sl, fl, tok, fs, enc, first, eout, blank, out=pout)
+            names = [f.name for f in dataclasses.fields(self._bout)]
+            bout = qsb.BeamEpStepBatch(*[None if getattr(self._bout, n) is None else getattr(self._bout, n)[:B] for n in names])
+            qengine.stream_beam_ep(self._state, self._bstate, self.S, plan, bp, sl, fl, cand[0], cand[1], enc, first, blank, pout,
+                                   self._sets, self._i32(bset) if self._sets is not None else None, bm.lm, bm.alpha, bm.beta, out=bout,
+                                   blobs=self._set_blobs if self._sets is not None else None)
+            o = qsb.BeamEpStepBatch(*[None if getattr(bout, n) is None else getattr(bout, n).cpu().numpy() for n in names])
+            est, recs, pst = eout.status.cpu().numpy(), pout.records.cpu().numpy(), pout.status.cpu().numpy()
+        else:
+            win, wl, first = qstream.window_host(self._state, slots)
+            logp, enc, tok = m._forward(torch.from_numpy(win), torch.from_numpy(wl).long())
+            logp = logp.float()
+            fs = m._frame_scores(logp, tok)
+            cid, cq = qbeam.topn_host(logp.numpy(), bp.N, enc.numpy())
+            eo = qstream.emit_batch_host(self._state, slots, flags, tok.numpy(), fs.numpy(), enc.numpy(), first, blank)
+            po = qse.endpoint_batch_host(self._ep_state, self._state, slots, flags, tok.numpy(), fs.numpy(), enc.numpy(), first, eo, blank,
+                                         self.eplan)
+            o = qsb.step_batch_ep_host(self._bstate, self._state, slots, flags, cid, cq, enc.numpy(), first, po.records, po.n_records,
+                                       po.status, blank, bm.lm, bm.alpha, bm.beta, boost=self._sets,
+                                       boost_set=bset if self._sets is not None else None)
+            est, recs, pst = eo.status, po.records, po.status
+        if int(o.status.max()) != 0 or int(est.max()) != 0 or int(pst.max()) != 0:
+            raise RuntimeError(f'stream: step refused, status {o.status.tolist()} / {est.tolist()} / {pst.tolist()} for slots {slots}')
+        rows = []
+        for b, s in enumerate(slots):
+            n = int(o.n_new_labels[b])
+            lab, fr = o.labels[b, :n].copy(), o.frames[b, :n].copy()
+            rows.append(dict(labels=lab, frames=fr, tail=o.tail_labels[b, :min(int(o.tail_n[b]), o.tail_labels.shape[1])].tolist(),
+                             last=self._cut_beam(s, o, b, recs[b], lab, fr)))
+        return rows
+
+    def _cut_beam(self, slot, o, b, recs, lab, fr):
+        """(StreamBeam(endpoint=)) the cuts of row b of a step: each takes the utterance's labels - what the slot's open
+        utterance had committed, and the step's delta up to cut_delta_end - and becomes a queued StreamUtterance whose
+        hypothesis is the beam's best; the delta behind the last cut stays with the slot.  Returns the last cut's hypothesis
+        (the list with n_best > 1), None without a cut."""
+        from qasr import beam as qbeam, ctc as qctc, stream_ep as qse
+        st, last, at = self._open[slot], None, 0
+        vocab, spf_s = self.model.decoder.vocabulary, self.plan.seconds_per_frame()
+        text = lambda ids: ''.join(vocab[i] for i in ids)
+        for k in range(int(o.n_cuts[b])):
+            de, r = int(o.cut_delta_end[b, k]), recs[k]
+            ul = np.concatenate([d[0] for d in st['deltas']] + [lab[at:de]]).astype(np.int32).tolist()
+            uf = np.concatenate([d[1] for d in st['deltas']] + [fr[at:de]]).astype(np.float64)
+            st['deltas'], at = [], de
+            hyps = []
+            for h in range(int(o.cut_n_hyps[b, k])):
+                labs = ul[:len(ul) - int(o.cut_n_labels[b, k, 0])] + o.cut_labels[b, k, h, :int(o.cut_n_labels[b, k, h])].tolist()
+                hyp = qctc.Hypothesis(text(labs), labs, (uf * spf_s).tolist() if h == 0 else [], ((uf + 1) * spf_s).tolist() if h == 0 else [],
+                                      None, None, [])
+                hyp.utt_score = float(o.cut_score[b, k, h]) / qbeam.ONE
+                if o.cut_lm_score is not None:
+                    hyp.lm_score = float(o.cut_lm_score[b, k, h]) / qbeam.ONE
+                if o.cut_boost_score is not None:
+                    hyp.boost_score = float(o.cut_boost_score[b, k, h]) / qbeam.ONE
+                hyps.append(hyp)
+            if not hyps:                     # the beam had died: the committed text of the utterance alone
+                hyps = [qctc.Hypothesis(text(ul), ul, (uf * spf_s).tolist(), ((uf + 1) * spf_s).tolist(), None, None, [])]
+            sp = int(r[qse.R_SP_FIRST]) >= 0
+            utt = qctc.StreamUtterance(slot, int(r[qse.R_INDEX]), qse.REASONS[int(r[qse.R_REASON])], int(r[qse.R_FIRST]) * spf_s,
+                                       int(r[qse.R_END]) * spf_s, int(r[qse.R_SP_FIRST]) * spf_s if sp else None,
+                                       (int(r[qse.R_SP_LAST]) + 1) * spf_s if sp else None, hyps[0])
+            if self.beam.n_best > 1:
+                utt.n_best = hyps
+            self._utts.append(utt)
+            last = hyps if self.beam.n_best > 1 else hyps[0]
+        if len(lab) > at:
+            st['deltas'].append((lab[at:], fr[at:]))
+        return last
+
     def _close_beam(self, st, slot):
         """the END step of a beam session: committed text + the remainder of each of the n_best final entries"""
         from qasr import beam as qbeam, ctc as qctc
         vocab, spf_s = self.model.decoder.vocabulary, self.plan.seconds_per_frame()
+        if self.endpoint is not None:        # the END utterance: the END record's cut
+            try:
+                if st['received'] > 0:
+                    return self._step_beam_ep([slot], True)[0]['last']
+                # a stream that never received a sample has nothing to run: the empty END utterance
+                hyp = qctc.Hypothesis('', [], [], [], None, None, [])
+                hyp.utt_score = 0.0
+                if self.beam.lm is not None:
+                    hyp.lm_score = 0.0
+                if self._sets is not None:
+                    hyp.boost_score = 0.0
+                utt = qctc.StreamUtterance(slot, 0, 'end', 0.0, 0.0, None, None, hyp)
+                if self.beam.n_best > 1:
+                    utt.n_best = [hyp]
+                self._utts.append(utt)
+                return [hyp] if self.beam.n_best > 1 else hyp
+            finally:
+                self._open.pop(slot)
         ends = []
         try:
             if st['received'] > 0:

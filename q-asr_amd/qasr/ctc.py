@@ -72,7 +72,9 @@ class StreamUtterance:
     """One finished utterance of a stream (EncDecCTCModel.stream(endpoint=), qasr.stream_ep.EP_RULES): its number in the
     stream, why it ended ('silence' | 'timeout' | 'max' | 'hard' | 'end'), its span and the span of its speech frames in
     seconds of the stream (None: no speech frame), and the Hypothesis of its labels - times in seconds of the stream,
-    utt_score the greedy path's log-probability over the utterance's own frames.  A 'timeout' utterance has no text."""
+    utt_score the greedy path's log-probability over the utterance's own frames.  A 'timeout' utterance has no text.
+    In a beam session (StreamBeam(endpoint=)) the hypothesis is the beam's best for the utterance: label times are the
+    frames at which the labels entered the beam, utt_score / lm_score / boost_score are the utterance's alone."""
     slot: int
     index: int
     reason: str
@@ -81,6 +83,7 @@ class StreamUtterance:
     speech_start_s: Optional[float]
     speech_end_s: Optional[float]
     hypothesis: Hypothesis
+    n_best: Optional[List[Hypothesis]] = None   # beam sessions (StreamBeam(endpoint=)) with n_best > 1: the utterance's list, best first
 
 
 def _order_key(x):

@@ -25,7 +25,7 @@ SYMBOLS = ['qasr_blob_check', 'qasr_engine_create', 'qasr_engine_create_ex', 'qa
            'qasr_stream_state_bytes', 'qasr_stream_push', 'qasr_stream_window', 'qasr_stream_emit',
            'qasr_stream_rs_state_bytes', 'qasr_stream_rs_work_bytes', 'qasr_stream_rs_push',
            'qasr_stream_beam_state_bytes', 'qasr_stream_beam', 'qasr_stream_ep_state_bytes', 'qasr_stream_endpoint',
-           'qasr_stream_beam_boost_state_bytes', 'qasr_stream_beam_boost',
+           'qasr_stream_beam_boost_state_bytes', 'qasr_stream_beam_boost', 'qasr_stream_beam_ep',
            'qasr_last_error', 'qasr_version']
 
 _lib = None
@@ -208,6 +208,8 @@ def load_library():
         lib.qasr_stream_ep_state_bytes.argtypes = [i32]
         lib.qasr_stream_ep_state_bytes.restype = sz
         lib.qasr_stream_endpoint.argtypes = [vp, C.POINTER(StreamEndpointArgs)]
+    if hasattr(lib, 'qasr_stream_beam_ep'):     # (likewise)
+        lib.qasr_stream_beam_ep.argtypes = [vp, C.POINTER(StreamBeamEpArgs)]
     lib.qasr_debug_prof.argtypes = [vp]
     lib.qasr_debug_timeline.argtypes = [vp, sz]
     lib.qasr_sep_layer.argtypes = [vp, C.POINTER(SepLayerArgs), C.c_char_p, sz]
@@ -1342,6 +1344,114 @@ def stream_beam_boost(state, bstate, S, plan, bplan, slots, flags, cand_id, cand
     with torch.cuda.device(state.device):
         _check(load_library().qasr_stream_beam_boost(_stream_ptr(stream), C.byref(a)), 'qasr_stream_beam_boost')
     return a._keep[2]
+
+
+class StreamBeamEpArgs(C.Structure):
+    """qasr_stream_beam_ep_args (include/qasr.h)"""
+    _fields_ = ([('struct_size', C.c_uint32), ('E', C.c_int32), ('boost', StreamBeamBoostArgs)] +
+                [(n, C.c_void_p) for n in ('records', 'n_records', 'ep_status', 'n_cuts', 'cut_n_hyps', 'cut_delta_end', 'cut_labels',
+                                           'cut_n_labels', 'cut_score', 'cut_lm_score', 'cut_boost_score')])
+
+
+def stream_beam_ep_buffers(B, bplan, E, device, with_lm, P=None, Ptail=None, Pend=None):
+    """k_stream_beam_ep's outputs as a qasr.stream_beam.BeamEpStepBatch of cuda tensors (E: the records' row pitch,
+    EndpointPlan.max_records)"""
+    from . import stream_beam as sb
+    P = bplan.delta_pitch if P is None else int(P)
+    Ptail = bplan.tail_pitch if Ptail is None else int(Ptail)
+    Pend = bplan.end_pitch if Pend is None else int(Pend)
+    i = lambda *s: torch.empty(*s, device=device, dtype=torch.int32)
+    l = lambda *s: torch.empty(*s, device=device, dtype=torch.int64)
+    nb, E = bplan.n_best, int(E)
+    return sb.BeamEpStepBatch(i(B, P), i(B, P), i(B), i(B), i(B), i(B), i(B, Ptail), i(B), i(B), i(B, E), i(B, E), i(B, E, nb, Pend),
+                              i(B, E, nb), l(B, E, nb), l(B, E, nb) if with_lm else None, l(B, E, nb) if bplan.boost else None)
+
+
+def stream_beam_ep_args(state, bstate, S, plan, bplan, slots, flags, cand_id, cand_q, enc_lens, first_frame, blank, ep, sets=None,
+                        boost_set=None, lm=None, alpha=0.0, beta=0.0, out=None, blobs=None):
+    """the filled qasr_stream_beam_ep_args of stream_beam_ep (the tensors it points to are kept alive on it)"""
+    from . import stream_beam as sb, stream_ep as qe
+    from .beam import TAB_ENTRIES
+    dev = state.device
+    sets = sb.as_sets(sets)
+    if (sets is not None) != bplan.boost:
+        raise ValueError('stream_beam_ep: phrase sets go with a plan built with boost=True')
+    for k, bs in enumerate(sets or []):
+        if bs.n_labels != int(blank):
+            raise ValueError(f'stream_beam_ep: phrase set {k} was compiled for {bs.n_labels} labels, blank is {blank}')
+    if cand_id.dim() != 3 or cand_id.dtype != torch.int32 or not cand_id.is_contiguous() or not cand_id.is_cuda:
+        raise ValueError(f'stream_beam_ep: cand_id must be a contiguous cuda int32 tensor [B, Tw, N], got {cand_id.dtype} {tuple(cand_id.shape)}')
+    if cand_q.dtype != torch.int32 or not cand_q.is_contiguous() or cand_q.shape != cand_id.shape:
+        raise ValueError('stream_beam_ep: cand_q must be a contiguous int32 tensor of the shape of cand_id')
+    B, Tw, N = cand_id.shape
+    for t, w in ((slots, 'slots'), (flags, 'flags'), (enc_lens, 'enc_lens'), (first_frame, 'first_frame'), (ep.n_records, 'ep.n_records'),
+                 (ep.status, 'ep.status')) + (((boost_set, 'boost_set'),) if sets is not None else ()):
+        _i32dev(t, B, 'stream_beam_ep: ' + w)
+    E = ep.records.shape[1] if ep.records.dim() == 3 else 0
+    assert ep.records.is_cuda and ep.records.dtype == torch.int32 and ep.records.is_contiguous() and \
+        tuple(ep.records.shape) == (B, E, qe.REC_WORDS), 'stream_beam_ep: ep.records'
+    alpha_q = beta_q = 0
+    if lm is not None:
+        from .ngram import fixed_weights
+        alpha_q, beta_q = fixed_weights(alpha, beta)
+        if lm.n_labels != int(blank):
+            raise ValueError(f'stream_beam_ep: the model was loaded for {lm.n_labels} labels, blank is {blank}')
+    if out is None:
+        out = stream_beam_ep_buffers(B, bplan, E, dev, lm is not None)
+    tab = lae_table_device(dev)
+    blob = None if lm is None else lm_device(lm, dev)
+    x = StreamBeamEpArgs()
+    x.struct_size, x.E = C.sizeof(StreamBeamEpArgs), E
+    x.boost.struct_size, x.boost.n_sets = C.sizeof(StreamBeamBoostArgs), 0 if sets is None else len(sets)
+    a = x.boost.beam
+    a.struct_size = C.sizeof(StreamBeamArgs)
+    a.S, a.B, a.Wl, a.C, a.Rr, a.samples_per_frame, a.Tw = int(S), B, plan.Wl, plan.C, plan.Rr, plan.samples_per_frame, Tw
+    a.N, a.beam_width, a.n_best, a.blank = N, bplan.W, bplan.n_best, int(blank)
+    a.Lg, a.K, a.F, a.max_final_frames = bplan.Lg, bplan.K, bplan.F, bplan.max_final_frames
+    assert out.cut_labels.dim() == 4 and tuple(out.cut_labels.shape[:3]) == (B, E, bplan.n_best), 'stream_beam_ep: out.cut_labels'
+    a.P, a.Ptail, a.Pend = out.labels.shape[1], out.tail_labels.shape[1], out.cut_labels.shape[3]
+    a.lae_entries = TAB_ENTRIES
+    a.state, a.state_bytes = state.data_ptr(), state.numel() * state.element_size()
+    a.beam_state, a.beam_state_bytes = bstate.data_ptr(), bstate.numel() * bstate.element_size()
+    a.slots, a.flags, a.cand_id, a.cand_q = slots.data_ptr(), flags.data_ptr(), cand_id.data_ptr(), cand_q.data_ptr()
+    a.enc_lens, a.first_frame, a.lae_table = enc_lens.data_ptr(), first_frame.data_ptr(), tab.data_ptr()
+    i64 = ('cut_score', 'cut_lm_score', 'cut_boost_score')
+    for n in ('labels', 'frames', 'n_new_labels', 'commit_len', 'n_live', 'status', 'tail_labels', 'tail_n', 'n_cuts', 'cut_n_hyps',
+              'cut_delta_end', 'cut_labels', 'cut_n_labels', 'cut_score', 'cut_lm_score', 'cut_boost_score'):
+        t = getattr(out, n)
+        if t is None:
+            assert (n == 'cut_lm_score' and lm is None) or (n == 'cut_boost_score' and sets is None), 'stream_beam_ep: out.' + n
+            continue
+        assert t.is_cuda and t.is_contiguous() and t.dtype == (torch.int64 if n in i64 else torch.int32), 'stream_beam_ep: out.' + n
+        setattr(a if hasattr(a, n) else x, n, t.data_ptr())
+    x.records, x.n_records, x.ep_status = ep.records.data_ptr(), ep.n_records.data_ptr(), ep.status.data_ptr()
+    if lm is not None:
+        a.lm, a.lm_bytes, a.alpha_q, a.beta_q, a.space = blob.data_ptr(), blob.numel(), alpha_q, beta_q, int(lm.space)
+    if sets is not None:
+        blobs = [boost_device(bs, dev) for bs in sets] if blobs is None else list(blobs)
+        assert len(blobs) == len(sets), 'stream_beam_ep: one blob per set'
+        if lm is None:
+            a.space = int(sets[0].space)
+        for k, (bs, bl) in enumerate(zip(sets, blobs)):
+            x.boost.sets[k], x.boost.set_bytes[k], x.boost.whole_words[k] = bl.data_ptr(), bl.numel(), int(bs.whole_words)
+        x.boost.boost_set = boost_set.data_ptr()
+    x._keep = (tab, blob, out, blobs, boost_set, ep)
+    return x
+
+
+def stream_beam_ep(state, bstate, S, plan, bplan, slots, flags, cand_id, cand_q, enc_lens, first_frame, blank, ep, sets=None,
+                   boost_set=None, lm=None, alpha=0.0, beta=0.0, out=None, stream=None, blobs=None):
+    """qasr_stream_beam_ep: one step of a beam session that is cut into utterances, AFTER stream_emit and stream_endpoint of the
+    same rows gave `ep` (a qasr.stream_ep.EpStepBatch of cuda tensors).  The arguments of stream_beam / stream_beam_boost
+    (sets=None: bstate is stream_beam_state's, else stream_beam_boost_state's and boost_set cuda int32 [B]).  Returns a
+    qasr.stream_beam.BeamEpStepBatch of cuda tensors.  k_stream_beam_ep, one launch, nothing read back; equal to
+    qasr.stream_beam.step_batch_ep_host byte for byte, the beam state included.  The table, the model and the sets are
+    uploaded by the first call: make that one outside a capture."""
+    x = stream_beam_ep_args(state, bstate, S, plan, bplan, slots, flags, cand_id, cand_q, enc_lens, first_frame, blank, ep, sets,
+                            boost_set, lm, alpha, beta, out, blobs)
+    with torch.cuda.device(state.device):
+        _check(load_library().qasr_stream_beam_ep(_stream_ptr(stream), C.byref(x)), 'qasr_stream_beam_ep')
+    return x._keep[2]
 
 
 class StreamEndpointArgs(C.Structure):

@@ -17,6 +17,7 @@ HDR_WORDS = 16
 _H_NB, _H_COMMIT, _H_DONE, _H_STARTED = 0, 1, 2, 3
 STATUS_OK, STATUS_GAP, STATUS_SLOT, STATUS_SYNC, STATUS_NODES, STATUS_SET = 0, 1, 2, 3, 4, 5
 _H_SET = 4                              # boosted blocks: the slot's phrase set + 1 (0: not boosted)
+_H_CUTS = 5                             # sessions with cuts (STREAM_BEAM_EP_RULES): the cuts done so far
 MAX_SETS = 8                            # phrase sets of one session (the kernel takes them as arguments)
 NODE_LIMIT = (1 << 31) - 1
 
@@ -97,13 +98,65 @@ it; (4) for every final hypothesis boost_tot is exactly the brute-force sum of g
 text (committed text plus remainder), however much of it was committed early."""
 
 
+STREAM_BEAM_EP_RULES = """Streaming beam endpointing: STREAM_BEAM_RULES (STREAM_BOOST_RULES on a boosted plan) for a stream that qasr.stream_ep
+cuts into utterances - at every cut the beam is finalised as at END and reset (k_stream_beam_ep<LM, BOOST> of
+csrc/qasr_stream_beam_ep.hip).  The slot's block is the plan's: 16 + 20 W words, boosted 16 + 24 W, then the ring.
+
+Order in a step.  window -> forward with log-probabilities -> top-N -> emit (STREAM_RULES) -> endpoint (EP_RULES) -> this
+step, which therefore runs AFTER emit and endpoint of the same rows.  lo = the beam block's own frames_done (0 on BEGIN);
+hi = the stream block's frames_done as emit left it; the step reads the row's records / n_records / status of the endpoint
+step and nothing else of it: no tokens, no frame scores.  Cuts are decided by the greedy arg-max, not by the beam.
+
+Frame loop.  For t = lo .. hi - 1, in this order: (a) the frame step of the rules, skipped while the beam is dead (the
+walk goes on: it has to reach the cuts); (b) the commit round if (t + 1) % K == 0, unchanged (nothing while h < 0 or the
+beam is dead); (c) while the next unread record has end == t + 1: a CUT.  Behind the loop every unread record is a cut too
+(they have end == hi: the END record of a row without frames, a BEGIN|END row).  Records with the same end give one cut
+each, the later ones on a fresh beam.
+
+Cut k of the step (k counts the step's records from 0).  First the END pass of the rules, on the outputs only: the
+unfinished-word term (word mode), the boost END pass (a boosted slot), ONE re-ordering by score, ties by previous rank.
+cut_n_hyps[k] = min(live entries, n_best); for each of these entries its suffix behind commit_len, the suffix' length,
+score, lm_score (with a model) and boost_score (boosted plan).  Then the best entry's uncommitted labels and their creation
+frames are appended to the step's delta, and cut_delta_end[k] = the delta's length after that: the delta between two
+cut_delta_end values is one utterance's remainder, and everything the step committed before it belongs to the same
+utterance.  Then the beam is RESET to the single fresh entry: commit_len 0, length 0, hashes 0, last -1, node -1, the LM
+context at the model's start, the boost state at the start state of the slot's set (header word 4 survives the cut),
+boost_tot 0.  A beam that had died is alive again; one that is dead because the model blob is invalid (the kernel's check)
+stays dead.  A cut of a dead beam has cut_n_hyps 0 and adds nothing to the delta.
+
+Nodes stay t * W + r in ring row t % F; frames and the phase of the rounds stay GLOBAL - a cut moves neither - so the
+bytes do not depend on how the stream is sliced into steps.  A fresh entry has node -1 and length 0, and chain walks stop at
+depth length - commit_len: no walk of a later utterance reaches a node of an earlier one.
+
+Header word 5 counts the cuts done (0 on BEGIN).  Per step out: STREAM_BEAM_RULES' delta, n_new_labels, n_live, status; commit_len
+and the tail are those of the beam the step leaves behind (behind a cut at hi: 0 and none); n_cuts and the cut outputs.
+There are no END rows: the END record is a cut like any other.
+
+Status.  1, 2, 4, 5 as in the rules (1: lo < first_frame or first_frame < 0; 5 on boosted plans).  3, checked after 2 and 1
+and before 4: lo > hi; lo < hi with hi > first_frame + e (e: the row's encoded length clamped to 0 .. Tw); n_records
+outside 0 .. E; a record whose end is below the one before it (ends may repeat), outside lo .. hi, or equal to lo while
+lo < hi; a first record whose index differs from header word 5 (0 on BEGIN); a non-zero endpoint status of the row.  Every
+status leaves the state alone and writes an empty step.
+
+Consequences, the contract: (1) any slicing of a stream into steps equals `lagged_search_ep_host`, the whole-stream
+statement, on every byte - delta, cut outputs, state block and ring; (2) with Lg at or beyond the longest utterance every
+cut's rows equal beam_search_host over the utterance's own candidates cand[first:end] - labels, score, lm_tot, boost_tot;
+(3) a stream without a record equals step_batch_host on every byte the two share; (4) boost_tot of every cut hypothesis is
+the brute-force sum over the phrase occurrences in that utterance's text alone."""
+
+
 @dataclass
 class StreamBeam:
     """What EncDecCTCModel.stream(beam=) takes.  width, n_best, cutoff_top_n, lm, alpha, beta: as decode(beam_width=, ...).
     lag_s: the commit lag in seconds (rounded to frames); the default of 4.0 s is untried on speech.  boost: phrase
     boosting across steps (STREAM_BOOST_RULES) - a list of phrases as decode(boost=) takes it, a qasr.boost.PhraseSet, or a
     dict of at most MAX_SETS named sets of which sess.open(boost=name) picks one; boost_weight: the default weight of
-    phrases given without one."""
+    phrases given without one.  endpoint: a qasr.stream_ep.Endpointing - the stream is cut into utterances and the beam is
+    finalised and reset at every cut (STREAM_BEAM_EP_RULES); sess.take_utterances() then delivers per-utterance n-best.
+    `endpoint` is the last constructor argument (positional or keyword) and an attribute, but NOT a dataclass field - the
+    field list stays boost, boost_weight at its end.  repr() and == include it.  dataclasses.replace() rebuilds from the
+    fields alone: replace(beam, lag_s=...) DROPS the endpointing and gives a session that never cuts - pass it along,
+    replace(beam, lag_s=..., endpoint=beam.endpoint)."""
     width: int = 16
     n_best: int = 1
     cutoff_top_n: int = 40
@@ -113,6 +166,40 @@ class StreamBeam:
     lag_s: float = 4.0
     boost: object = None
     boost_weight: float = 1.0
+
+
+def _stream_beam_init(fields_init, n_fields):
+    """StreamBeam.__init__ with `endpoint` behind the dataclass fields, as the last positional or a keyword argument.  It is an
+    attribute and not a dataclass field: the list of fields is pinned to end in boost, boost_weight, so repr and == do not see
+    it, and dataclasses.replace keeps it only when it is passed (replace(beam, ..., endpoint=beam.endpoint))."""
+    def __init__(self, *args, endpoint=None, **kw):
+        if len(args) > n_fields + 1:
+            raise TypeError(f'StreamBeam takes at most {n_fields + 1} positional arguments, got {len(args)}')
+        if len(args) == n_fields + 1:
+            if endpoint is not None:
+                raise TypeError("StreamBeam got multiple values for argument 'endpoint'")
+            args, endpoint = args[:n_fields], args[n_fields]
+        fields_init(self, *args, **kw)
+        self.endpoint = endpoint
+    return __init__
+
+
+def _stream_beam_repr(fields_repr):
+    def __repr__(self):
+        return fields_repr(self)[:-1] + f', endpoint={self.endpoint!r})'
+    return __repr__
+
+
+def _stream_beam_eq(fields_eq):
+    def __eq__(self, other):
+        r = fields_eq(self, other)
+        return r if r is NotImplemented or not r else self.endpoint == other.endpoint
+    return __eq__
+
+
+StreamBeam.__init__ = _stream_beam_init(StreamBeam.__init__, len(StreamBeam.__dataclass_fields__))
+StreamBeam.__repr__ = _stream_beam_repr(StreamBeam.__repr__)
+StreamBeam.__eq__ = _stream_beam_eq(StreamBeam.__eq__)
 
 
 class StreamBeamPlan:
@@ -129,7 +216,15 @@ class StreamBeamPlan:
     Pitches.  end_pitch = tail_pitch = F (a suffix behind commit_len).  Every label a step commits was uncommitted before
     the step (<= F) or created in it (<= its final frames, one per frame along one chain): delta_pitch = F +
     max_final_frames, END steps included.
-    `walk` steps through a protocol of frames and asserts all of it on the twin.
+    Cuts (STREAM_BEAM_EP_RULES).  A cut at frame c resets the beam to an entry of length 0 and node -1: every chain of the
+    utterance that follows holds nodes created at frames >= c only, every chain of the one before it nodes created below c.
+    Chains of different utterances cover disjoint frames.  Ring: live nodes are still created in (t - Lg, t + K] of the
+    last round t (a cut only kills nodes), so F = Lg + K rows suffice.  Labels: an entry still has at most one uncommitted
+    label per live frame, so Pend = F holds for every cut.  Delta: a step's delta is, utterance by utterance, what rounds
+    committed and what cuts appended; each of those labels was uncommitted before the step (only in the first utterance
+    the step touches: <= F) or was created at a frame of the step, at most one per frame along one chain, and the chains
+    of the step's utterances cover disjoint frames: delta_pitch = F + max_final_frames still holds.
+    `walk_ep` steps through a protocol of frames with cuts and asserts all of it on the twin.
     boost: the slots carry bst and boost_tot (STREAM_BOOST_RULES' layout)."""
 
     def __init__(self, width=16, n_best=1, cutoff_top_n=40, lag_frames=200, max_final_frames=1, K=K_ROUND, boost=False):
@@ -655,3 +750,334 @@ def lagged_search_host(cand_id, cand_q, lim, blank, beam_width=16, n_best=None, 
         frames += row.frames
     head = labels[:before]
     return LaggedResult(labels, frames, [(head + x[0],) + tuple(x[1:]) for x in row.end], before)
+
+
+# ------------------------------------------------------------------------------------- cuts: STREAM_BEAM_EP_RULES
+@dataclass
+class BeamEpStepRow:
+    """What one step with cuts gives for one row.  labels / frames: the delta; commit_len, n_live, tail: of the beam the step
+    leaves behind; cuts: per cut the list of (suffix labels, score, lm_tot[, boost_tot]), best first, cut to n_best;
+    cut_delta_end: the delta's length after each cut."""
+    labels: List[int] = field(default_factory=list)
+    frames: List[int] = field(default_factory=list)
+    commit_len: int = 0
+    n_live: int = 0
+    tail: List[int] = field(default_factory=list)
+    cuts: list = field(default_factory=list)
+    cut_delta_end: List[int] = field(default_factory=list)
+
+
+def _end_pass(state, slot, e, commit, lm, alpha_q, beta_q, bs):
+    """the END pass of the rules on the entries e: [(suffix labels, score, lm_tot, creation frames[, boost_tot])], best first,
+    cut to n_best"""
+    plan = state.plan
+    sc, lmt = e.sc.copy(), e.lmt.copy()
+    btot = e.btot.copy() if plan.boost else None
+    word_mode = lm is not None and lm.word_mode
+    if (word_mode or bs is not None) and len(e):
+        half = 1 << (FRAC - 1)
+        if word_mode:
+            for i in np.flatnonzero((e.last >= 0) & (e.last != lm.space)):
+                tv = ((lm.raw(int(e.ctx[i]), lm.lookup_word(e.wh[i]))[0] * alpha_q + half) >> FRAC) + beta_q
+                sc[i] += tv
+                lmt[i] += tv
+        if bs is not None:
+            for i in range(len(e)):
+                fin = bs.finish(int(e.bst[i]))
+                sc[i] += fin
+                btot[i] += fin
+        rank = np.argsort(-sc, kind='stable')
+    else:
+        rank = np.arange(len(e))
+    out = []
+    for i in rank[:plan.n_best]:
+        ch = _walk(state, slot, int(e.node[i]), int(e.ln[i]) - commit)[::-1]
+        out.append(([x[0] for x in ch], int(sc[i]), int(lmt[i]), [x[1] for x in ch]) + ((int(btot[i]),) if plan.boost else ()))
+    return out
+
+
+def advance_ep_host(state: StreamBeamState, slot, cand_id, cand_q, first, lo, hi, begin, rec_ends, blank, lm=None, alpha_q=0,
+                    beta_q=0, boost=None, boost_set=-1) -> BeamEpStepRow:
+    """One row of one step under STREAM_BEAM_EP_RULES with the status checks already passed: advance_host's arguments, and
+    rec_ends: the `end` of each of the step's records, in order."""
+    plan = state.plan
+    W, F, K, Lg = plan.W, plan.F, plan.K, plan.Lg
+    tab = lae_table()
+    cid, cq = np.asarray(cand_id, dtype=np.int32), np.asarray(cand_q, dtype=np.int32)
+    assert cid.ndim == 2 and cid.shape == cq.shape and cid.shape[1] == plan.N, (cid.shape, cq.shape, plan.N)
+    sets = as_sets(boost)
+    assert (sets is not None) == plan.boost, 'advance_ep_host: boost= goes with a plan built with boost=True'
+    gset = 0
+    if sets is not None:
+        gset = int(boost_set) + 1 if begin else state.boost_set(slot, len(sets))
+        assert 0 <= gset <= len(sets), (gset, len(sets))
+    bs = sets[gset - 1] if gset else None
+    if begin:
+        e, commit, cuts0 = _Entries.fresh(lm, plan.boost, bs), 0, 0
+        state.row_frame[slot], state.h_dead[slot] = -1, -1
+        state.trail[slot] = dict(nodes={}, committed=[])
+    else:
+        e, commit, done = state.load(slot, lm, bs)
+        cuts0 = int(state.block[slot, _H_CUTS])
+        assert done == lo, (done, lo)
+    trail = state.trail[slot]
+    ring = state.ring(slot)
+    out = BeamEpStepRow()
+    ends = [int(x) for x in rec_ends]
+    rk = 0
+
+    def cut(t_end):
+        nonlocal e, commit
+        hyps = _end_pass(state, slot, e, commit, lm, alpha_q, beta_q, bs)
+        if hyps:
+            out.labels += hyps[0][0]
+            out.frames += hyps[0][3]
+        out.cuts.append([x[:3] + x[4:] for x in hyps])
+        out.cut_delta_end.append(len(out.labels))
+        e, commit = _Entries.fresh(lm, plan.boost, bs), 0
+        trail['committed'] = []
+        state.h_dead[slot] = max(int(state.h_dead[slot]), t_end - 1)      # every node made before the cut is dead
+
+    for t in range(lo, hi):
+        if len(e):
+            nxt, new = _frame(e, cid[t - first], cq[t - first], t, W, int(blank), tab, lm, alpha_q, beta_q, bs)
+            if nxt is None:
+                e = e.take(np.zeros(0, dtype=np.int64))
+                new = []
+            else:
+                e = nxt
+            if new:
+                prev = int(state.row_frame[slot, t % F])
+                assert prev in (-1, t) or prev <= state.h_dead[slot], ('a ring row is overwritten while it may be live', prev, t)
+                state.row_frame[slot, t % F] = t
+            for s, parent, lab in new:
+                ring[t % F, s] = (parent, lab)
+                if state.check:
+                    trail['nodes'][t * W + s] = (parent, lab)
+        if (t + 1) % K == 0 and t - Lg >= 0 and len(e):
+            h = t - Lg
+            olds = []
+            for i in range(len(e)):
+                ch = _walk(state, slot, int(e.node[i]), int(e.ln[i]) - commit)
+                olds.append([(lab, f) for lab, f in ch if f <= h])
+            assert len(olds[0]) <= K, (len(olds[0]), K)
+            lab0 = [x[0] for x in olds[0]]
+            keep = np.array([[x[0] for x in o] == lab0 for o in olds], dtype=bool)
+            assert keep[0]
+            out.labels += lab0[::-1]
+            out.frames += [x[1] for x in olds[0]][::-1]
+            commit += len(lab0)
+            trail['committed'] += lab0[::-1]
+            e = e.take(np.flatnonzero(keep))
+            state.h_dead[slot] = max(int(state.h_dead[slot]), h)
+            if state.check:
+                for i in range(len(e)):
+                    assert _full_labels(trail, int(e.node[i]))[:commit] == trail['committed'], 'a committed label changed'
+        while rk < len(ends) and ends[rk] == t + 1:
+            cut(t + 1)
+            rk += 1
+    while rk < len(ends):
+        assert ends[rk] == hi, (ends, lo, hi)
+        cut(hi)
+        rk += 1
+    state.store(slot, e, commit, hi, gset)
+    state.block[slot, _H_CUTS] = cuts0 + len(ends)
+    out.n_live, out.commit_len = len(e), commit
+    if len(e):
+        out.tail = [x[0] for x in _walk(state, slot, int(e.node[0]), int(e.ln[0]) - commit)[::-1]]
+    assert len(out.labels) <= plan.delta_pitch or hi - lo > plan.max_final_frames, (len(out.labels), plan.delta_pitch)
+    assert all(len(x[0]) <= plan.end_pitch for c in out.cuts for x in c)
+    return out
+
+
+@dataclass
+class BeamEpStepBatch:
+    """k_stream_beam_ep's outputs: labels / frames [B][P]; n_new_labels, commit_len, n_live, status [B]; tail_labels
+    [B][Ptail], tail_n [B]; n_cuts [B]; cut_n_hyps, cut_delta_end [B][E]; cut_labels [B][E][n_best][Pend], cut_n_labels
+    [B][E][n_best], cut_score int64 [B][E][n_best], cut_lm_score (None without a model), cut_boost_score (None without boost)."""
+    labels: object
+    frames: object
+    n_new_labels: object
+    commit_len: object
+    n_live: object
+    status: object
+    tail_labels: object
+    tail_n: object
+    n_cuts: object
+    cut_n_hyps: object
+    cut_delta_end: object
+    cut_labels: object
+    cut_n_labels: object
+    cut_score: object
+    cut_lm_score: object = None
+    cut_boost_score: object = None
+
+
+def ep_batch_buffers(B, plan: StreamBeamPlan, E, blank, with_lm, P=None, Ptail=None, Pend=None) -> BeamEpStepBatch:
+    """the outputs of an empty step"""
+    P = plan.delta_pitch if P is None else int(P)
+    Ptail = plan.tail_pitch if Ptail is None else int(Ptail)
+    Pend = plan.end_pitch if Pend is None else int(Pend)
+    E, nb = int(E), plan.n_best
+    i = lambda *s: np.zeros(s, np.int32)
+    return BeamEpStepBatch(np.full((B, P), blank, np.int32), i(B, P), i(B), i(B), i(B), i(B), np.full((B, Ptail), blank, np.int32),
+                           i(B), i(B), i(B, E), i(B, E), np.full((B, E, nb, Pend), blank, np.int32), i(B, E, nb),
+                           np.full((B, E, nb), NEG, np.int64), np.zeros((B, E, nb), np.int64) if with_lm else None,
+                           np.zeros((B, E, nb), np.int64) if plan.boost else None)
+
+
+def step_batch_ep_host(bstate: StreamBeamState, sstate: qs.StreamState, slots, flags, cand_id, cand_q, enc_lens, first_frame,
+                       records, n_records, ep_status, blank, lm=None, alpha=0.0, beta=0.0, P=None, Ptail=None, Pend=None,
+                       boost=None, boost_set=None) -> BeamEpStepBatch:
+    """The twin of one k_stream_beam_ep launch, AFTER emit_batch_host and endpoint_batch_host of the same rows: step_batch_host's
+    arguments, and records int32 [B][E][10], n_records, ep_status int [B] as qasr.stream_ep.endpoint_batch_host gave them."""
+    from .stream_ep import R_END, R_INDEX
+    plan = bstate.plan
+    sets = as_sets(boost)
+    if (sets is not None) != plan.boost:
+        raise ValueError('stream_beam: boost= goes with a plan built with boost=True')
+    for bs in sets or []:
+        if bs.n_labels != int(blank):
+            raise ValueError(f'stream_beam: the phrase set was compiled for {bs.n_labels} labels, blank is {blank}')
+    alpha_q, beta_q = _weights(lm, alpha, beta, blank)
+    cid, cq, rec = np.asarray(cand_id), np.asarray(cand_q), np.asarray(records)
+    B, Tw, E = cid.shape[0], cid.shape[1], rec.shape[1]
+    o = ep_batch_buffers(B, plan, E, blank, lm is not None, P, Ptail, Pend)
+    bset = np.full(B, -1, np.int64) if boost_set is None else np.asarray(boost_set, dtype=np.int64)
+    P, Ptail, Pend = o.labels.shape[1], o.tail_labels.shape[1], o.cut_labels.shape[3]
+    for b in range(B):
+        slot = int(slots[b])
+        if not (0 <= slot < bstate.S and slot < sstate.S):
+            o.status[b] = STATUS_SLOT
+            continue
+        first = int(first_frame[b])
+        e = max(0, min(int(enc_lens[b]), Tw))
+        begin = bool(int(flags[b]) & qs.BEGIN)
+        lo, hi = (0 if begin else bstate.header(slot)[2]), sstate.frames_done(slot)
+        if lo < first or first < 0:
+            o.status[b] = STATUS_GAP
+            continue
+        n = int(n_records[b])
+        bad = lo > hi or (lo < hi and hi > first + e) or not 0 <= n <= E or int(ep_status[b]) != 0
+        if not bad and n:
+            bad = int(rec[b, 0, R_INDEX]) != (0 if begin else int(bstate.block[slot, _H_CUTS]))
+            prev = lo
+            for k in range(n):
+                en = int(rec[b, k, R_END])
+                bad = bad or en < prev or en > hi or (en == lo and lo < hi)
+                prev = en
+        if bad:
+            o.status[b] = STATUS_SYNC
+            continue
+        if hi * plan.W > NODE_LIMIT:
+            o.status[b] = STATUS_NODES
+            continue
+        if sets is not None and begin and not -1 <= int(bset[b]) < len(sets):
+            o.status[b] = STATUS_SET
+            continue
+        row = advance_ep_host(bstate, slot, cid[b], cq[b], first, lo, hi, begin, rec[b, :n, R_END], blank, lm, alpha_q, beta_q,
+                              sets, int(bset[b]))
+        m = min(len(row.labels), P)
+        o.labels[b, :m], o.frames[b, :m], o.n_new_labels[b] = row.labels[:m], row.frames[:m], m
+        o.commit_len[b], o.n_live[b] = row.commit_len, row.n_live
+        nt = min(len(row.tail), Ptail)
+        o.tail_labels[b, :nt], o.tail_n[b] = row.tail[:nt], len(row.tail)
+        o.n_cuts[b] = n
+        for k, hyps in enumerate(row.cuts):
+            o.cut_n_hyps[b, k], o.cut_delta_end[b, k] = len(hyps), min(row.cut_delta_end[k], P)
+            for h, ent in enumerate(hyps):
+                labs, sc, lmt = ent[:3]
+                mm = min(len(labs), Pend)
+                o.cut_labels[b, k, h, :mm], o.cut_n_labels[b, k, h], o.cut_score[b, k, h] = labs[:mm], len(labs), sc
+                if o.cut_lm_score is not None:
+                    o.cut_lm_score[b, k, h] = lmt
+                if sets is not None:
+                    o.cut_boost_score[b, k, h] = ent[3]
+    return o
+
+
+def step_ep_host(bstate: StreamBeamState, sstate: qs.StreamState, slot, flag, cand_id, cand_q, enc_len, first, records, n_records,
+                 ep_status, blank, **kw) -> BeamEpStepBatch:
+    """step_batch_ep_host for one row: cand_id / cand_q [Tw][N], records [E][10]"""
+    return step_batch_ep_host(bstate, sstate, [slot], [flag], np.asarray(cand_id)[None], np.asarray(cand_q)[None], [enc_len], [first],
+                              np.asarray(records)[None], [n_records], [ep_status], blank, **kw)
+
+
+@dataclass
+class LaggedEpResult:
+    """lagged_search_ep_host's outputs: the whole delta (labels, creation frames), per cut the delta's length after it
+    (cut_delta_end), the cut's hypotheses best first as (suffix labels, score, lm_tot[, boost_tot]) (cuts), and per cut
+    the utterance's best text - what was committed since the cut before plus the best suffix - with its frames (utts);
+    block: the state block (ring included) the search leaves behind."""
+    labels: List[int]
+    frames: List[int]
+    cut_delta_end: List[int]
+    cuts: list
+    utts: list
+    block: object = None
+
+    def __eq__(self, o):
+        return (self.labels, self.frames, self.cut_delta_end, self.cuts, self.utts) == \
+            (o.labels, o.frames, o.cut_delta_end, o.cuts, o.utts) and self.block.tobytes() == o.block.tobytes()
+
+
+def lagged_search_ep_host(cand_id, cand_q, lim, cut_ends, blank, beam_width=16, n_best=None, lm=None, alpha=0.0, beta=0.0, lag=200,
+                          K=K_ROUND, steps=None, check=True, boost=None) -> LaggedEpResult:
+    """The whole-stream statement with cuts: cand_id / cand_q int32 [T][N] of ONE stream, its first `lim` frames searched
+    under STREAM_BEAM_EP_RULES with a lag of `lag` frames; cut_ends: the `end` frame of every record of the stream in
+    order (rising, repeats allowed, each in 0 .. lim; the END record's is lim).  steps: frame indices at which the stream
+    is sliced into steps (None: one step); the result does not depend on them.  boost: a qasr.boost.PhraseSet."""
+    cid, cq = np.asarray(cand_id, dtype=np.int32), np.asarray(cand_q, dtype=np.int32)
+    lim = int(min(max(int(lim), 0), cid.shape[0]))
+    W = int(beam_width)
+    ends = [int(c) for c in cut_ends]
+    if ends != sorted(ends) or any(not 0 <= c <= lim for c in ends) or (lim > 0 and 0 in ends):
+        raise ValueError(f'lagged_search_ep_host: cut ends {ends} must rise inside 1 .. {lim}')
+    plan = StreamBeamPlan(W, W if n_best is None else n_best, cid.shape[1], lag, max(lim, 1), K, boost is not None)
+    if boost is not None and boost.n_labels != int(blank):
+        raise ValueError(f'lagged_search_ep_host: the phrase set was compiled for {boost.n_labels} labels, blank is {blank}')
+    alpha_q, beta_q = _weights(lm, alpha, beta, blank)
+    if lim * W > NODE_LIMIT:
+        raise ValueError(f'lagged_search_ep_host: {lim} frames x width {W} pass the node-id limit')
+    st = StreamBeamState(1, plan, check)
+    edges = [0] + sorted(int(c) for c in (steps or []) if 0 < int(c) < lim) + [lim]
+    labels, frames, cde, cuts = [], [], [], []
+    for i in range(len(edges) - 1):
+        lo, hi = edges[i], edges[i + 1]
+        mine = [c for c in ends if (lo < c <= hi) or (lo == hi == c)]
+        row = advance_ep_host(st, 0, cid, cq, 0, lo, hi, i == 0, mine, blank, lm, alpha_q, beta_q, boost,
+                              0 if boost is not None else -1)
+        cde += [len(labels) + x for x in row.cut_delta_end]
+        cuts += row.cuts
+        labels += row.labels
+        frames += row.frames
+    utts = [(labels[a:b], frames[a:b]) for a, b in zip([0] + cde[:-1], cde)]
+    return LaggedEpResult(labels, frames, cde, cuts, utts, st.block.copy())
+
+
+def walk_ep(plan: StreamBeamPlan, cand_id, cand_q, step_edges, cut_ends, blank, lm=None, alpha=0.0, beta=0.0, boost=None):
+    """Steps the twin through a protocol of frames that contains cuts - step_edges: the frame at which each step ends, in
+    order; cut_ends: as lagged_search_ep_host takes them - and asserts the plan's sizes on every step: no live ring row is
+    overwritten and chain walks stay within F (asserted inside the twin), every delta fits delta_pitch for steps of at
+    most max_final_frames, every cut suffix and every tail fits F, creation frames rise inside every utterance and the
+    utterances' frames are disjoint and in order.  Returns the number of cuts walked."""
+    cid, cq = np.asarray(cand_id, dtype=np.int32), np.asarray(cand_q, dtype=np.int32)
+    alpha_q, beta_q = _weights(lm, alpha, beta, blank)
+    st = StreamBeamState(1, plan, check=True)
+    ends = [int(c) for c in cut_ends]
+    lo, n_cuts, last_frame = 0, 0, -1
+    for i, hi in enumerate(step_edges):
+        hi = int(hi)
+        assert lo <= hi <= cid.shape[0] and hi - lo <= plan.max_final_frames, (lo, hi, plan.max_final_frames)
+        mine = [c for c in ends if (lo < c <= hi) or (lo == hi == c and i == len(step_edges) - 1)]
+        row = advance_ep_host(st, 0, cid, cq, 0, lo, hi, i == 0, mine, blank, lm, alpha_q, beta_q, boost, 0 if boost is not None else -1)
+        assert len(row.labels) <= plan.delta_pitch and len(row.tail) <= plan.tail_pitch
+        assert all(len(x[0]) <= plan.end_pitch for c in row.cuts for x in c)
+        assert row.cut_delta_end == sorted(row.cut_delta_end) and all(x <= len(row.labels) for x in row.cut_delta_end)
+        for f in row.frames:                          # one chain per utterance, utterances over disjoint frames, in order
+            assert f > last_frame and f < hi, (f, last_frame, hi)
+            last_frame = f
+        n_cuts += len(mine)
+        assert int(st.block[0, _H_CUTS]) == n_cuts
+        lo = hi
+    return n_cuts
