@@ -162,7 +162,7 @@ void qasr_engine_destroy(qasr_engine* e);
  * Environment variables remain ONLY as A/B overrides for profiling runs of an unmodified caller, read once per create
  * call AFTER the options: QASR_TILE128=0|1 (128-frame tiles when tile_frames >= 64), QASR_RES_TILE128=0|1 (res_tile128),
  * QASR_RES_TILE=32|64|128 (the block-end tile itself, read after QASR_RES_TILE128; 32 has no option value), QASR_DENSE_TILE128,
- * QASR_SEP_GEN=1|2, QASR_NO_FUSE, QASR_NO_FUSE_STEM, QASR_NO_FUSE_DEC, QASR_WIDE_TILES, QASR_NO_FUSE_NORM; QASR_SEP2_TUNE is a kernel-internal experiment knob (csrc/qasr_sep2_impl.h). */
+ * QASR_SEP_GEN=1|2, QASR_PAIR_SPLIT=0|1 (pair_split), QASR_NO_FUSE, QASR_NO_FUSE_STEM, QASR_NO_FUSE_DEC, QASR_WIDE_TILES, QASR_NO_FUSE_NORM; QASR_SEP2_TUNE is a kernel-internal experiment knob (csrc/qasr_sep2_impl.h). */
 typedef struct qasr_engine_opts {
   uint32_t struct_size;
   uint32_t debug;              /* bit 0: keep every tensor + int32 accumulators (parity hooks); bit 1: one HIP event per op */
@@ -191,7 +191,12 @@ typedef struct qasr_engine_opts {
                                   length stores the zero codes and returns (the same bytes, no work).  Default (-1): on for a
                                   reserved engine (qasr_engine_reserve), off otherwise - the never-taken branch costs the
                                   full-length step 0.14 - 0.28 us per launch */
-  int32_t reserved[1];
+  int32_t pair_split;          /* the plain 512 -> 512 separable layers of a tile_frames == 128 engine on work-group PAIRS (k_sep2p):
+                                  each member runs half the depthwise channels and one GEMM pass, the halves meet through an
+                                  exchange buffer inside the launch (same bytes, labels and launch count).
+                                  Default (-1): by the GPU_MAX_HW_QUEUES hint res_tile128 reads - on below 8 queues (two chains
+                                  at a time), off from 8.  Never for debug / timing / reserved engines or other tiles.
+                                  QASR_PAIR_SPLIT=0|1 is the A/B override */
 } qasr_engine_opts;
 /* fills `o` with struct_size and the defaults (-1 / 0) */
 void qasr_engine_default_opts(qasr_engine_opts* o);
@@ -1220,8 +1225,18 @@ typedef struct qasr_sep_layer_args {
   int32_t* dw_acc;             /* optional hooks: i32 [B][cin][Tp], [B][cout][Tp], [B][cout][Tp] */
   int32_t* acc;
   int32_t* racc;
+  int32_t pair, pad_;          /* 1: the paired form (qasr_engine_opts.pair_split); QASR_ERR_UNSUPPORTED for a shape without one */
+  void* pair_ws;               /* ... its workspace: 256-byte aligned device memory of qasr_sep_pair_workspace_bytes(B, Tp) bytes, */
+  size_t pair_ws_bytes;        /*     one per launch in flight; the u32 at qasr_sep_pair_timeout_offset counts spins that gave up */
 } qasr_sep_layer_args;
 int qasr_sep_layer(void* stream, const qasr_sep_layer_args* a, char* label, size_t label_cap);
+size_t qasr_sep_pair_workspace_bytes(int B, int Tp);
+size_t qasr_sep_pair_timeout_offset(int B, int Tp);
+/* 1 if op `op` of the current plan runs in the paired form, 0 if not, -1 for a bad argument (after a forward) */
+int qasr_engine_op_paired(const qasr_engine* e, int op);
+/* synchronises the device, returns how many hand-off spins of paired launches gave up since the last call (their results
+ * are wrong; 0 in a healthy run) and clears the count */
+int qasr_engine_pair_timeouts(qasr_engine* e);
 
 /* Diagnostics: when set to a device buffer of 32 int64, work-group (1,0,0) of every k_sep launch writes s_memtime
  * stamps at its phase boundaries (slot 31 = number of stamps); NULL (default) disables. */

@@ -115,6 +115,14 @@ struct qasr_engine {
   bool wide_tiles = false;             // k_sep with 64-frame tiles (throughput mode: bit 3 of `debug`, or QASR_WIDE_TILES=1)
   int mask_skip = -1;                  // k_sep2s (mask-skip rule): -1 = when reserved, 0 = never, 1 = always (qasr_engine_opts.mask_skip)
   int sep_gen = 2;                     // 2: k_sep2 where it has the shape; 1 (QASR_SEP_GEN=1): k_sep everywhere (A/B runs)
+  // qasr_engine_opts.pair_split: the plain 512 -> 512 layers of a tile_frames == 128 engine as k_sep2p (two work-groups per tile)
+  bool pair_split = false;
+  std::vector<char> paired;            // per op: launched in the paired form (empty: none)
+  std::vector<size_t> pair_flag_off;   // per op: byte offset of its flag words in pair_flags
+  unsigned* pair_flags = nullptr;      // every paired op's flag words: an allocation of their own, zeroed by ONE k_pair_zero node per forward
+  size_t pair_flag_bytes = 0;
+  unsigned char* pair_x = nullptr;     // [256 B: the time-out word][exchange buffer, B x tiles x 64 KiB, shared by all paired ops]
+  bool in_forward = false;             // launch_op runs inside enqueue_forward (the forward's memset has zeroed the flags)
   // hipGraph replay (bit 4 of `debug`): the whole forward of one (shape, buffer set) is captured once and re-launched
   // with one call; key = the caller's pointers, which a serving loop keeps stable
   bool forwarded = false;              // a forward has been enqueued with the current plan
@@ -207,6 +215,13 @@ static void free_plan(qasr_engine* e) {
   dev_free(e, e->decw_ws);
   e->decw_ws = nullptr;
   e->decw_ws_bytes = 0;
+  dev_free(e, e->pair_flags);
+  e->pair_flags = nullptr;
+  e->pair_flag_bytes = 0;
+  dev_free(e, e->pair_x);
+  e->pair_x = nullptr;
+  e->paired.clear();
+  e->pair_flag_off.clear();
   for (auto& v : e->acc_dbg)
     for (auto p : v)
       dev_free(e, p);
@@ -351,6 +366,36 @@ static int plan_alloc(qasr_engine* e) {
   return QASR_OK;
 }
 
+// Which ops run in the paired form, and their exchange memory.  Never for debug / timing engines (hooks, per-op events), tiles
+// below 128, reserved engines (they do not come through build_plan); sep_pair_ok leaves only the production launches of
+// k_sep2<51 | 63 | 75, 4, 0, 2, false, 128, 1>.
+static int plan_pairs(qasr_engine* e) {
+  const auto& h = e->h;
+  if (!e->pair_split || e->debug || e->timing || !e->wide_tiles || !e->tile128 || e->rs.on) return QASR_OK;
+  std::vector<char> paired(h.n_ops, 0);
+  std::vector<size_t> off(h.n_ops, 0);
+  size_t fb = 0, xb = 0;
+  for (uint32_t oi = 0; oi < h.n_ops; ++oi) {
+    if (e->ops[oi].kind != QASR_OP_PW || e->skip[oi] || e->fused_dw[oi] < 0) continue;
+    SepP p{};
+    build_sep(e, oi, p);
+    if (!sep_pair_ok(p)) continue;
+    paired[oi] = 1;
+    off[oi] = fb;
+    fb += sep_pair_flag_bytes(p.e.B, p.e.Tp);
+    xb = std::max(xb, sep_pair_x_bytes(p.e.B, p.e.Tp));
+  }
+  if (!fb) return QASR_OK;
+  HIPCHK(dev_alloc(e, (void**)&e->pair_flags, fb));
+  HIPCHK(dev_alloc(e, (void**)&e->pair_x, 256 + xb));
+  HIPCHK(hipMemset(e->pair_flags, 0, fb));
+  HIPCHK(hipMemset(e->pair_x, 0, 256));
+  e->pair_flag_bytes = fb;
+  e->paired.swap(paired);
+  e->pair_flag_off.swap(off);
+  return QASR_OK;
+}
+
 static int build_plan(qasr_engine* e, int B, int T0) {
   free_plan(e);
   int rc = plan_shape(e, B, T0);
@@ -359,6 +404,7 @@ static int build_plan(qasr_engine* e, int B, int T0) {
     return rc;
   }
   rc = plan_alloc(e);
+  if (!rc) rc = plan_pairs(e);
   if (rc) e->B = e->T0 = 0;
   return rc;
 }
@@ -439,7 +485,7 @@ void qasr_engine_default_opts(qasr_engine_opts* o) {
   if (!o) return;
   memset(o, 0, sizeof *o);
   o->struct_size = (uint32_t)sizeof *o;
-  o->fuse_dw = o->fuse_stem = o->fuse_decoder = o->res_tile128 = o->dense_tile128 = o->fuse_norm = o->mask_skip = -1;
+  o->fuse_dw = o->fuse_stem = o->fuse_decoder = o->res_tile128 = o->dense_tile128 = o->fuse_norm = o->mask_skip = o->pair_split = -1;
 }
 
 // Block-end tile of a tile_frames == 128 engine when the caller leaves qasr_engine_opts.res_tile128 at -1.  What decides is how
@@ -450,15 +496,20 @@ void qasr_engine_default_opts(qasr_engine_opts* o) {
 // With a queue per chain four chains fill the chip and the 128-frame tile is the cheaper one.
 #define QASR_SIDE_BY_SIDE_QUEUES 8      /* smallest tested count (4, 8) at which four streams' chains ran side by side */
 #define QASR_RES_TILE_FEW_CHAINS 64     /* two chains in flight, ms/step: 128 frames 0.584, 64 frames 0.543 - 0.550, 32 frames 0.551 - 0.558 */
-static int res_tile_default() {
+static long hw_queues_hint() {
   long q = 4;                                               // HIP's own default
   if (const char* g = getenv("GPU_MAX_HW_QUEUES")) {
     char* end = nullptr;
     const long v = strtol(g, &end, 10);
     if (end != g && v >= 1) q = v;
   }
-  return q >= QASR_SIDE_BY_SIDE_QUEUES ? 128 : QASR_RES_TILE_FEW_CHAINS;
+  return q;
 }
+static int res_tile_default() { return hw_queues_hint() >= QASR_SIDE_BY_SIDE_QUEUES ? 128 : QASR_RES_TILE_FEW_CHAINS; }
+// qasr_engine_opts.pair_split at -1, by the same hint: two chains at a time leave half the CUs idle behind the 64-work-group
+// launches of the plain 512 -> 512 layers, and a tile on two work-groups halves their span; with four chains
+// side by side the chip is full and the plan stays as it is.
+static bool pair_split_default() { return hw_queues_hint() < QASR_SIDE_BY_SIDE_QUEUES; }
 
 // the `debug` bits of round 1 / 2 callers, as options
 int qasr_engine_create(const void* blob, size_t n, int device, int debug, qasr_engine** out) {
@@ -509,6 +560,7 @@ int qasr_engine_create_ex(const void* blob, size_t n, int device, const qasr_eng
   e->dense_tile128 = tri(o.dense_tile128, true);
   e->sep_gen = o.sep_gen == 1 ? 1 : 2;
   e->mask_skip = o.mask_skip < 0 ? -1 : (o.mask_skip != 0);
+  e->pair_split = o.pair_split < 0 ? pair_split_default() : o.pair_split != 0;
   e->use_graph = o.graph > 0;
   // environment: A/B overrides for profiling runs of an unmodified caller (include/qasr.h lists them), read per create call
   if (getenv("QASR_NO_FUSE")) e->fuse = false;
@@ -524,6 +576,7 @@ int qasr_engine_create_ex(const void* blob, size_t n, int device, const qasr_eng
   if (const char* g = getenv("QASR_NO_FUSE_NORM")) e->fuse_norm = atoi(g) == 0;
   if (const char* g = getenv("QASR_DENSE_TILE128")) e->dense_tile128 = atoi(g) != 0;
   if (const char* g = getenv("QASR_SEP_GEN")) e->sep_gen = atoi(g) == 1 ? 1 : 2;
+  if (const char* g = getenv("QASR_PAIR_SPLIT")) e->pair_split = atoi(g) != 0;
   e->blob.assign((const uint8_t*)blob, (const uint8_t*)blob + n);
   e->h = h;
   e->tdesc = (const qasr_tensor_desc*)(e->blob.data() + h.tensors_off);
@@ -637,6 +690,12 @@ static void build_sep(qasr_engine* e, uint32_t oi, SepP& p) {
   if (p.tile == 128 && (op.flags & QASR_F_RESADD)) p.tile = (e->res_tile == 32 && e->fused_dw[oi] < 0) ? 64 : e->res_tile;
   p.gen = e->sep_gen;
   p.mask_skip = e->mask_skip < 0 ? e->rs.on : e->mask_skip != 0;
+  if (!e->paired.empty() && e->paired[oi]) {
+    p.pair = 1;
+    p.pair_flags = (unsigned*)((unsigned char*)e->pair_flags + e->pair_flag_off[oi]);
+    p.pair_tmo = (unsigned*)e->pair_x;
+    p.pair_x = e->pair_x + 256;
+  }
   fill_panes(e, oi, op, p.panes);
   fill_epi(e, oi, op, p.e);
   const int di = e->fused_dw[oi];
@@ -784,6 +843,8 @@ static int launch_op(qasr_engine* e, hipStream_t s, uint32_t oi, float* logp, in
         e->dec_wide[oi] = 1;
         break;
       }
+      // a paired op outside a forward (run_op, time_ops): its flag words are zeroed here, as the forward's memset does for all
+      if (p.pair && !e->in_forward && launch_pair_zero(s, p.pair_flags, sep_pair_flag_bytes(p.e.B, p.e.Tp))) return fail(QASR_ERR_ARG, "op %u: k_pair_zero", oi);
       int rc = launch_sep(s, p);
       if (rc) return fail(rc, "op %u: no k_sep instantiation for K=%d dilation=%d (or bad launch shape)", oi, p.K, p.dilation);
       break;
@@ -883,6 +944,15 @@ static int enqueue_forward(qasr_engine* e, hipStream_t s, const FrontArgs* fe, b
                            float* logp, int32_t* tokens, int32_t* lens_out) {
   const auto& h = e->h;
   const int B = e->B;
+  // the flag words of every paired op, zero before the first kernel: one node per forward.  A kernel, not hipMemsetAsync: as a
+  // memset node of the captured graph the zeroing was not in place for every paired launch of back-to-back replays (a few
+  // tokens differed from the serial result, no spin timed out: flags of the previous replay were still seen set)
+  if (e->pair_flags && launch_pair_zero(s, e->pair_flags, e->pair_flag_bytes)) return fail(QASR_ERR_ARG, "forward: k_pair_zero");
+  struct InForward {
+    qasr_engine* e;
+    explicit InForward(qasr_engine* e_) : e(e_) { e->in_forward = true; }
+    ~InForward() { e->in_forward = false; }
+  } in_forward(e);
   if (fe && norm_in_stem) {
     int nt = 0, nf = 0;
     int rc = frontend_mel_stats(s, fe->audio, fe->audio_lens, B, fe->S, fe->fb, fe->window, fe->n_mels, fe->preemph, fe->pad_to,
@@ -2158,6 +2228,28 @@ int qasr_engine_op_label(qasr_engine* e, int op, char* buf, size_t cap) {
   return QASR_OK;
 }
 
+int qasr_engine_op_paired(const qasr_engine* e, int op) {
+  if (!e || op < 0 || op >= (int)e->h.n_ops) return -1;
+  return (!e->paired.empty() && e->paired[op]) ? 1 : 0;
+}
+
+int qasr_engine_pair_timeouts(qasr_engine* e) {
+  if (!e) return -1;
+  if (!e->pair_x) return 0;
+  unsigned v = 0;
+  HIPCHK(hipSetDevice(e->device));
+  HIPCHK(hipDeviceSynchronize());
+  HIPCHK(hipMemcpy(&v, e->pair_x, sizeof v, hipMemcpyDeviceToHost));
+  if (v) HIPCHK(hipMemset(e->pair_x, 0, sizeof v));
+  return (int)std::min(v, 0x7fffffffu);
+}
+
+size_t qasr_sep_pair_workspace_bytes(int B, int Tp) {
+  if (B < 1 || Tp < 128 || Tp % 128) return 0;
+  return sep_pair_flag_bytes(B, Tp) + 256 + sep_pair_x_bytes(B, Tp);
+}
+size_t qasr_sep_pair_timeout_offset(int B, int Tp) { return (B < 1 || Tp < 128 || Tp % 128) ? 0 : sep_pair_flag_bytes(B, Tp); }
+
 int qasr_engine_run_op(qasr_engine* e, void* stream, int op) {
   if (!e || !e->B || op < 0 || op >= (int)e->h.n_ops) return fail(QASR_ERR_ARG, "run_op: run a forward first");
   return launch_op(e, (hipStream_t)stream, (uint32_t)op, nullptr, e->time_tokens, nullptr);
@@ -2339,6 +2431,7 @@ int qasr_sep_layer(void* stream, const qasr_sep_layer_args* a, char* label, size
   p.tile = a->tile;
   p.gen = a->gen == 3 ? 2 : a->gen;
   p.mask_skip = a->gen == 3;
+  p.pair = a->pair != 0;
   p.w = a->w;
   p.bias = a->bias;
   p.cin = a->cin;
@@ -2380,6 +2473,17 @@ int qasr_sep_layer(void* stream, const qasr_sep_layer_args* a, char* label, size
   e.Tp = a->Tp;
   e.cout = a->cout;
   e.B = a->B;
+  if (p.pair) {
+    // hooks are debug instantiations; everything but k_sep2<51 | 63 | 75, 4, 0, 2, false, 128, 1> has no paired form
+    if (a->dw_acc || a->acc || a->racc || !sep_pair_ok(p)) return fail(QASR_ERR_UNSUPPORTED, "sep_layer: no paired form for this shape / with hooks");
+    const size_t fb = sep_pair_flag_bytes(e.B, e.Tp);
+    if (!a->pair_ws || ((uintptr_t)a->pair_ws & 255) || a->pair_ws_bytes < qasr_sep_pair_workspace_bytes(e.B, e.Tp))
+      return fail(QASR_ERR_ARG, "sep_layer: pair_ws (256-byte aligned, qasr_sep_pair_workspace_bytes)");
+    p.pair_flags = (unsigned*)a->pair_ws;
+    p.pair_tmo = (unsigned*)((unsigned char*)a->pair_ws + fb);
+    p.pair_x = (unsigned char*)a->pair_ws + fb + 256;
+    if (launch_pair_zero((hipStream_t)stream, p.pair_flags, fb)) return fail(QASR_ERR_ARG, "sep_layer: k_pair_zero");   // flag words: zero before every launch
+  }
   if (label && label_cap >= 8) sep_kernel_label(p, label, label_cap);
   int rc = launch_sep((hipStream_t)stream, p);
   if (rc) return fail(rc, "sep_layer: no kernel instantiation for K=%d dilation=%d (or bad launch shape)", p.K, p.dilation);

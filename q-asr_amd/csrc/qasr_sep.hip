@@ -73,8 +73,17 @@ int sep_tile_for(const SepP& p) {
   return (p.tile >= 64 && (p.dense_k > 1 || sep_epilogue_class(p) != EP_GENERIC)) ? 64 : 32;
 }
 
+// the paired form exists for the production k_sep2<51 | 63 | 75, 4, 0, 2, false, 128, 1> launches only
+bool sep_pair_ok(const SepP& p) {
+  const bool dbg = p.e.acc_dbg || p.dw_acc_dbg;
+  return !dbg && !p.mask_skip && !dense2_takes(p) && sep2_takes(p) && sep2_tile(p) == 128 && sep2_pair_shape(p);
+}
+size_t sep_pair_flag_bytes(int B, int Tp) { return sep2_pair_flag_bytes(B, Tp); }
+size_t sep_pair_x_bytes(int B, int Tp) { return sep2_pair_x_bytes(B, Tp); }
+
 int launch_sep(hipStream_t s, const SepP& p) {
   const bool dbg = p.e.acc_dbg || p.dw_acc_dbg;
+  if (p.pair) return sep_pair_ok(p) ? launch_sep2_pair(s, p) : QASR_ERR_UNSUPPORTED;   // (the label stays k_sep2<...>'s)
   if (dense2_takes(p)) return launch_dense2(s, p);           // Jasper's plain dense convs (qasr_dense2.hip)
   if (sep2_takes(p)) {
     const int tt = sep2_tile(p);

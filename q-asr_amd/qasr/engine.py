@@ -11,7 +11,8 @@ LIB_PATH = os.environ.get('QASR_LIB', os.path.join(HERE, 'libqasr_hip.so'))   # 
 
 SYMBOLS = ['qasr_blob_check', 'qasr_engine_create', 'qasr_engine_create_ex', 'qasr_engine_default_opts', 'qasr_engine_destroy', 'qasr_engine_forward', 'qasr_engine_forward_audio', 'qasr_engine_out_frames',
            'qasr_engine_num_ops', 'qasr_engine_num_launches', 'qasr_engine_read_acc', 'qasr_engine_read_tensor', 'qasr_engine_last_op_ms',
-           'qasr_engine_time_ops', 'qasr_engine_run_op', 'qasr_engine_op_label',
+           'qasr_engine_time_ops', 'qasr_engine_run_op', 'qasr_engine_op_label', 'qasr_engine_op_paired', 'qasr_engine_pair_timeouts',
+           'qasr_sep_pair_workspace_bytes', 'qasr_sep_pair_timeout_offset',
            'qasr_frontend_mel', 'qasr_frontend_plan', 'qasr_frontend_mel_planned', 'qasr_frontend_frames',
            'qasr_frontend_workspace_bytes', 'qasr_pw_conv_acc',
            'qasr_dw_conv_acc', 'qasr_dense_conv_acc', 'qasr_requant', 'qasr_dyn_range', 'qasr_dyn_range_percentile', 'qasr_dyn_residue_codes', 'qasr_dyn_act_params', 'qasr_dyn_requant',
@@ -44,7 +45,8 @@ class SepLayerArgs(C.Structure):
                 [(n, C.c_void_p) for n in ('wdw', 'wdw2', 'bias_dw', 'm_dw', 'w', 'bias', 'sb', 'm_main', 'lens', 'rx', 'rw',
                                            'rbias', 'rm', 'rsb')] +
                 [(n, C.c_int32) for n in ('rcin', 'r_unsigned', 'qlo', 'qhi')] +
-                [('outs', _SepOut * 3), ('dw_acc', C.c_void_p), ('acc', C.c_void_p), ('racc', C.c_void_p)])
+                [('outs', _SepOut * 3), ('dw_acc', C.c_void_p), ('acc', C.c_void_p), ('racc', C.c_void_p)] +
+                [('pair', C.c_int32), ('pad_', C.c_int32), ('pair_ws', C.c_void_p), ('pair_ws_bytes', C.c_size_t)])
 
 
 class EngineOpts(C.Structure):
@@ -52,8 +54,7 @@ class EngineOpts(C.Structure):
     _fields_ = ([('struct_size', C.c_uint32), ('debug', C.c_uint32)] +
                 [(n, C.c_int32) for n in ('tile_frames', 'sep_gen', 'fuse_dw', 'fuse_stem', 'fuse_decoder', 'graph',
                                           'retired_whole_utterance', 'res_tile128', 'dense_tile128', 'retired_legacy_pw', 'retired_persistent', 'fuse_norm',
-                                          'mask_skip')] +
-                [('reserved', C.c_int32 * 1)])
+                                          'mask_skip', 'pair_split')])
 
 
 class CtcOut(C.Structure):
@@ -129,6 +130,12 @@ def load_library():
     lib.qasr_engine_time_ops.argtypes = [vp, vp, i32, vp, i32]
     lib.qasr_engine_run_op.argtypes = [vp, vp, i32]
     lib.qasr_engine_op_label.argtypes = [vp, i32, C.c_char_p, sz]
+    lib.qasr_engine_op_paired.argtypes = [vp, i32]
+    lib.qasr_engine_pair_timeouts.argtypes = [vp]
+    lib.qasr_sep_pair_workspace_bytes.argtypes = [i32, i32]
+    lib.qasr_sep_pair_workspace_bytes.restype = sz
+    lib.qasr_sep_pair_timeout_offset.argtypes = [i32, i32]
+    lib.qasr_sep_pair_timeout_offset.restype = sz
     lib.qasr_engine_forward_audio.argtypes = [vp, vp, vp, vp, i32, i32, vp, vp, i32, C.c_float, i32, vp, sz, vp, vp, vp, vp, vp]
     lib.qasr_frontend_mel.argtypes = [vp, vp, vp, i32, i32, vp, vp, i32, C.c_float, i32, vp, vp, vp, sz]
     lib.qasr_frontend_mel_planned.argtypes = lib.qasr_frontend_mel.argtypes
@@ -1534,7 +1541,7 @@ class Engine:
 
     def __init__(self, blob: bytes, device=0, debug=False, timing=False, wide_tiles=False,
                  graph=False, tile=None, sep_gen=None, fuse_dw=None, fuse_stem=None, fuse_decoder=None, res_tile128=None,
-                 dense_tile128=None, fuse_norm=None, legacy_create=False, mask_skip=None):
+                 dense_tile128=None, fuse_norm=None, legacy_create=False, mask_skip=None, pair_split=None):
         """Options = qasr_engine_opts (include/qasr.h).  tile: frames per work-group (32 / 64 / 128; `wide_tiles=True` is the
         older spelling of 128); None leaves a choice at the engine's default."""
         lib = load_library()
@@ -1553,7 +1560,7 @@ class Engine:
         o.sep_gen = int(sep_gen or 0)
         for name, v in (('fuse_dw', fuse_dw), ('fuse_stem', fuse_stem), ('fuse_decoder', fuse_decoder),
                         ('res_tile128', res_tile128), ('dense_tile128', dense_tile128), ('fuse_norm', fuse_norm),
-                        ('mask_skip', mask_skip)):
+                        ('mask_skip', mask_skip), ('pair_split', pair_split)):
             if v is not None:
                 setattr(o, name, int(bool(v)))
         o.graph = int(bool(graph))
@@ -1803,6 +1810,17 @@ class Engine:
             out.append(buf.value.decode())
         return out
 
+    def op_paired(self):
+        """per op: does it run in the paired form (qasr_engine_opts.pair_split; after a forward)"""
+        return [self.lib.qasr_engine_op_paired(self._h, op) == 1 for op in range(self.n_ops)]
+
+    def pair_timeouts(self):
+        """hand-off spins of paired launches that gave up since the last call (synchronises; 0 in a healthy run)"""
+        n = self.lib.qasr_engine_pair_timeouts(self._h)
+        if n < 0:
+            raise QasrError('qasr_engine_pair_timeouts failed: ' + self.lib.qasr_last_error().decode())
+        return n
+
     def run_op(self, op, stream=None):
         _check(self.lib.qasr_engine_run_op(self._h, _stream_ptr(stream), int(op)), 'qasr_engine_run_op')
 
@@ -1875,7 +1893,7 @@ def requant(acc: torch.Tensor, M: torch.Tensor, lo, hi, sb=None, exact_z=False, 
 
 
 def sep_layer(x, lens, wpw, bias, outs, wdw=None, m_dw=None, dw_range=(-128, 127), x_unsigned=False, dilation=1,
-              flags=0, sb=None, res=None, tile=32, gen=2, hooks=True, out_fill=0):
+              flags=0, sb=None, res=None, tile=32, gen=2, hooks=True, out_fill=0, pair=False, pair_ws=None, sync=True, row_pad=64):
     """One fused separable layer through qasr_sep_layer (the production kernels with caller-made operands).
 
     x            int8 / uint8 [B, cin, T] (cuda)      lens  valid frames per utterance
@@ -1886,6 +1904,10 @@ def sep_layer(x, lens, wpw, bias, outs, wdw=None, m_dw=None, dw_range=(-128, 127
                  sb f32 [cout], m_main f64 [cout], qlo, qhi)   -> QASR_F_RESADD
     Biases are the natural ones: the +128 sum(W) correction of u8 inputs is folded here, as pack.py does.
     out_fill     byte the output buffers hold before the call (tests of what a kernel leaves unwritten)
+    pair         the paired form (two work-groups per tile; QasrError for a shape without one, or with hooks); pair_ws: its
+                 workspace from sep_pair_workspace (made here when None; one per launch in flight), returned as 'pair_ws'
+    sync         False: return without synchronising (the launch is in flight on the current stream)
+    row_pad      rows are padded to a multiple of this many frames (64; 128 keeps a 128-frame tile at any T)
     Returns dict(outs=[int8 [B, cout, T]...], outs_padded=[the same with the row padding, [B, cout, Tp]], dw_acc, acc, racc
     (int32, None without hooks), label)."""
     from .pack import F_RESADD, fragment_order
@@ -1893,7 +1915,7 @@ def sep_layer(x, lens, wpw, bias, outs, wdw=None, m_dw=None, dw_range=(-128, 127
     dev = x.device
     B, cin, T = x.shape
     cout = wpw.shape[0]
-    Tp, cinp, coutp = _rup(T, 64), _rup(cin, 128), _rup(cout, 128)
+    Tp, cinp, coutp = _rup(T, int(row_pad)), _rup(cin, 128), _rup(cout, 128)
     keep = []
 
     def dv(t, dtype=None):
@@ -1984,11 +2006,33 @@ def sep_layer(x, lens, wpw, bias, outs, wdw=None, m_dw=None, dw_range=(-128, 127
         if res is not None:
             hk['racc'] = torch.zeros(B, cout, Tp, dtype=torch.int32, device=dev)
             a.racc = hk['racc'].data_ptr()
+    if pair:
+        a.pair = 1
+        if pair_ws is None and Tp % 128 == 0:
+            pair_ws = sep_pair_workspace(B, Tp, dev)
+        if pair_ws is not None:
+            a.pair_ws, a.pair_ws_bytes = pair_ws.data_ptr(), pair_ws.numel()
     label = C.create_string_buffer(96)
     _check(lib.qasr_sep_layer(_stream_ptr(), C.byref(a), label, 96), 'qasr_sep_layer')
-    torch.cuda.synchronize()
-    return dict(outs=[t[:, :, :T] for t in out_t], outs_padded=out_t, label=label.value.decode(),
+    if sync:
+        torch.cuda.synchronize()
+    return dict(outs=[t[:, :, :T] for t in out_t], outs_padded=out_t, label=label.value.decode(), pair_ws=pair_ws, keep=keep,
                 **{k: (hk[k][:, :, :T] if k in hk else None) for k in ('dw_acc', 'acc', 'racc')})
+
+
+def sep_pair_workspace(B, Tp, device):
+    """zeroed workspace of a paired sep_layer launch of B utterances x Tp frames (Tp a multiple of 128)"""
+    n = load_library().qasr_sep_pair_workspace_bytes(int(B), int(Tp))
+    if n == 0:
+        raise QasrError(f'sep_pair_workspace: no paired form at Tp = {Tp}')
+    return torch.zeros(n, dtype=torch.uint8, device=device)
+
+
+def sep_pair_timeouts(pair_ws, B, Tp):
+    """spins that gave up in the paired launches that used `pair_ws` (synchronises)"""
+    torch.cuda.synchronize()
+    off = load_library().qasr_sep_pair_timeout_offset(int(B), int(Tp))
+    return int(pair_ws[off:off + 4].view(torch.int32).item())
 
 
 def frontend_plan(fb: torch.Tensor):
