@@ -18,18 +18,15 @@
 // Prefixes are nodes (parent, label) in the caller's workspace: the node of the entry that lands in slot s at frame t is
 // t * W + s, so nothing is counted or allocated.  LDS atomics only (histogram, winner slots); global memory sees plain
 // vector stores.  Every loop is bounded by T, W, N or a constant.
-#include <climits>
-
-#include "qasr_internal.h"
+// The constants, log-add-exp, the model's view and walks and the selection itself are qasr_beam_dev.h's, shared with
+// k_beam_boost and the streaming kernels.
+#include "qasr_beam_dev.h"
 
 namespace qasr {
 
-#define BEAM_NEG (-(1ll << 62))
 #define BEAM_QFLOOR (-1073741824.f)
 #define BEAM_QCEIL (1073741824.f)
 #define BEAM_EMPTY_Q INT_MIN
-#define BEAM_DMAX (16ll << 16)
-#define BEAM_HMUL 0x9E3779B97F4A7C15ull
 
 __device__ __forceinline__ int beam_key(int bits) { return bits ^ ((bits >> 31) & 0x7fffffff); }
 
@@ -165,31 +162,6 @@ int launch_topn(hipStream_t s, const qasr_ctc_topn_args& a) {
 }
 
 // ------------------------------------------------------------------------------------------------------------ k_beam
-#define BEAM_NT 256
-#define BEAM_NWAVE (BEAM_NT / 64)
-#define BEAM_W QASR_BEAM_MAX_WIDTH
-#define BEAM_N QASR_BEAM_MAX_CANDIDATES
-#define BEAM_TAB QASR_BEAM_TABLE_ENTRIES
-
-struct BeamP {
-  const int32_t* cand_id;   // [B][T][N]
-  const int32_t* cand_q;
-  const int32_t* lens;      // optional [B]
-  const uint16_t* tab;      // [BEAM_TAB]
-  int2* nodes;              // [B][T * W] (parent node, label)
-  int32_t* labels;          // [B][n_best][T]
-  int32_t* n_labels;        // [B][n_best]
-  long long* score;         // [B][n_best]
-  int32_t* n_hyps;          // [B]
-  int B, T, N, W, n_best, blank;
-};
-
-struct BeamState {          // one side of the double buffer
-  long long pb[BEAM_W], pnb[BEAM_W], sc[BEAM_W];
-  unsigned long long hash[BEAM_W], phash[BEAM_W];
-  int len[BEAM_W], last[BEAM_W], node[BEAM_W];
-};
-
 struct BeamLds {
   uint16_t tab[BEAM_TAB];
   BeamState st[2];
@@ -204,17 +176,9 @@ struct BeamLds {
   int bin, kk, n_at, n_sel;
 };
 
-__device__ __forceinline__ long long beam_lae(long long a, long long b, const uint16_t* tab) {
-  const long long m = a > b ? a : b, n = a > b ? b : a;
-  if (n == BEAM_NEG) return m;
-  const long long d = m - n;
-  if (d >= BEAM_DMAX) return m;
-  return m + (long long)tab[d >> 6];
-}
-
 __global__ void __launch_bounds__(BEAM_NT) k_beam(BeamP p) {
   __shared__ BeamLds L;
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int tid = threadIdx.x;
   const int b = blockIdx.x, T = p.T, N = p.N, W = p.W, N1 = N + 1, blank = p.blank;
   const int lim = p.lens ? min(max(p.lens[b], 0), T) : T;
   int2* const nodes = p.nodes + (size_t)b * T * W;
@@ -291,94 +255,8 @@ __global__ void __launch_bounds__(BEAM_NT) k_beam(BeamP p) {
       return base == BEAM_NEG ? BEAM_NEG : base + (long long)L.cq[n];
     };
     const int k_end = active ? N1 : 0;
-    long long mx = LLONG_MIN, mn = LLONG_MAX;
-    int cnt = 0;
-    for (int k = my_sub; k < k_end; k += tpr) {
-      const long long v = cand(k);
-      if (v != BEAM_NEG) { ++cnt; mx = v > mx ? v : mx; mn = v < mn ? v : mn; }
-    }
-#pragma unroll
-    for (int d = 32; d >= 1; d >>= 1) {
-      const long long omx = __shfl_xor(mx, d), omn = __shfl_xor(mn, d);
-      cnt += __shfl_xor(cnt, d);
-      mx = omx > mx ? omx : mx, mn = omn < mn ? omn : mn;
-    }
-    if (lane == 0) L.red_max[wave] = mx, L.red_min[wave] = mn, L.red_cnt[wave] = cnt;
-    __syncthreads();
-    mx = L.red_max[0], mn = L.red_min[0], cnt = L.red_cnt[0];
-#pragma unroll
-    for (int w = 1; w < BEAM_NWAVE; ++w) {
-      mx = L.red_max[w] > mx ? L.red_max[w] : mx, mn = L.red_min[w] < mn ? L.red_min[w] : mn;
-      cnt += L.red_cnt[w];
-    }
-    if (cnt == 0) { nb = 0; break; }               // uniform: every thread read the same totals
-    // ---- MSB-first radix select over this thread's candidates: the kk-th smallest key among those `keyfn` admits; returns
-    // the key, leaves in kk how many candidates of exactly that key belong to the kk, in n_at how many have that key
-    auto radix_select = [&](auto keyfn, int nbits, int& kk, int& n_at) -> unsigned long long {
-      const int passes = (nbits + 7) >> 3;          // <= 8
-      unsigned long long prefix = 0;
-      for (int pass = passes - 1; pass >= 0; --pass) {
-        const int shift = pass * 8;
-        __syncthreads();                            // the previous pass's bin / kk and histogram have been read
-        L.hist[tid] = 0;                            // BEAM_NT == 256 bins
-        __syncthreads();
-        for (int k = my_sub; k < k_end; k += tpr) {
-          unsigned long long key;
-          if (keyfn(k, key) && (shift + 8 >= 64 || (key >> (shift + 8)) == prefix))
-            atomicAdd(&L.hist[(unsigned)(key >> shift) & 255u], 1u);
-        }
-        __syncthreads();
-        const int mine = (int)L.hist[tid];
-        int inc = mine;                             // inclusive prefix sum over the 256 bins, smallest key first
-#pragma unroll
-        for (int d = 1; d < 64; d <<= 1) {
-          const int o = __shfl_up(inc, d);
-          if (lane >= d) inc += o;
-        }
-        if (lane == 63) L.red_a[wave] = inc;
-        __syncthreads();
-        for (int w = 0; w < wave; ++w) inc += L.red_a[w];
-        const int exc = inc - mine;
-        if (exc < kk && kk <= inc) L.bin = tid, L.kk = kk - exc, L.n_at = mine;      // exactly one thread
-        __syncthreads();
-        prefix = (prefix << 8) | (unsigned long long)L.bin;
-        kk = L.kk, n_at = L.n_at;
-      }
-      return prefix;
-    };
-    // ---- the W-th smallest r = mx - score: its value rth; of the candidates with exactly rth, those up to index ith win
-    unsigned long long rth = ~0ull;
-    int ith = INT_MAX;
-    if (cnt > W) {
-      const unsigned long long range = (unsigned long long)(mx - mn);
-      int need = W, n_at = cnt;                     // (a range of 0: every candidate has r == 0)
-      rth = radix_select([&](int k, unsigned long long& key) {
-        const long long v = cand(k);
-        key = (unsigned long long)(mx - v);
-        return v != BEAM_NEG;
-      }, range ? 64 - __clzll((long long)range) : 0, need, n_at);
-      if (n_at > need) {                            // a tie at the cut: the lower candidate indices win
-        const int M = nb * N1;
-        ith = (int)radix_select([&](int k, unsigned long long& key) {
-          const long long v = cand(k);
-          key = (unsigned long long)(my_i * N1 + k);
-          return v != BEAM_NEG && (unsigned long long)(mx - v) == rth;
-        }, 32 - __clz(M), need, n_at);
-      }
-    }
-    // ---- collect the winners (in any order: they are sorted next)
-    for (int k = my_sub; k < k_end; k += tpr) {
-      const long long v = cand(k);
-      if (v != BEAM_NEG) {
-        const unsigned long long r = (unsigned long long)(mx - v);
-        const int idx = my_i * N1 + k;
-        if (r < rth || (r == rth && idx <= ith)) {
-          const int at = atomicAdd(&L.n_sel, 1);
-          if (at < BEAM_W) L.sel_r[at] = r, L.sel_idx[at] = idx;
-        }
-      }
-    }
-    __syncthreads();
+    long long mx;
+    if (!beam_select(L, cand, my_i, my_sub, tpr, k_end, nb, N1, W, mx)) { nb = 0; break; }      // uniform
     const int ns = min(L.n_sel, W);
     // ---- order them (score descending = r ascending, then candidate index) and write the next beam
     if (tid < ns) {
@@ -451,7 +329,7 @@ int launch_beam(hipStream_t s, const qasr_ctc_beam_args& a) {
 
 // --------------------------------------------------------------------------------------------------------- k_beam_lm
 // k_beam with the shallow fusion of a back-off n-gram model (LM_RULES of qasr/beam.py; the packed model is qasr/ngram.py's).
-// A kernel of its own, so that k_beam above stays as it is.  What differs: an entry also keeps its context node, the hash
+// What differs from k_beam above: an entry also keeps its context node, the hash
 // of its current word, the term of its own creation (the E path reuses it) and the running sum of its terms; the frame's
 // terms are evaluated ONCE, before the selection - thread (slot, sub) walks the model for the candidates it scores anyway and
 // leaves raw in L.raw[slot][n] (character mode: up to W x N walks; word mode: the space candidate of each slot, <= W) - and
@@ -459,20 +337,6 @@ int launch_beam(hipStream_t s, const qasr_ctc_beam_args& a) {
 // in global memory and is read with plain vector loads (one 16-byte slot per probe); every walk is bounded by the order and
 // the header's probe bounds.  After the last frame, word mode scores the unfinished word of every entry and re-orders.
 // With the table and raw[128][64] the state is about 93 KB of static LDS: gfx950 gives one work-group up to 160 KB.
-#define BEAM_LM_MAGIC 0x314D4C51
-#define BEAM_LM_OOV (-1000 * 65536)
-#define BEAM_LM_RAWLIM 2147483647ll
-#define BEAM_LM_NOTERM INT_MIN
-
-struct LmView {
-  const int4* trans;        // [tmask + 1] node, word, prob_q, next
-  const int4* words;        // [wmask + 1] hash lo, hash hi, word id, 0
-  const int2* nodes;        // [n_nodes] backoff_q, suffix
-  const int* l2w;           // [n_labels]
-  int order, tprobe, wprobe, n_labels;
-  unsigned tmask, wmask;
-};
-
 struct BeamLmP {
   BeamP b;
   const int* lm;
@@ -503,75 +367,25 @@ struct BeamLmLds {
   int raw[BEAM_W * BEAM_N];
 };
 
-// raw(ctx, w) and the context it leaves
-__device__ __forceinline__ int lm_walk(const LmView& m, int ctx, int w, int& next) {
-  next = 0;
-  if (w < 0) return BEAM_LM_OOV;
-  long long acc = 0;
-  int node = ctx;
-  for (int it = 0; it < m.order; ++it) {
-    unsigned long long x = (((unsigned long long)(unsigned)node << 32) | (unsigned long long)(unsigned)w) * BEAM_HMUL;
-    x ^= x >> 32;
-    unsigned s = (unsigned)x & m.tmask;
-    bool hit = false;
-    for (int pr = 0; pr < m.tprobe; ++pr) {
-      const int4 e = m.trans[s];
-      if (e.x == node && e.y == w) { acc += e.z; next = e.w; hit = true; break; }
-      if (e.x < 0) break;
-      s = (s + 1) & m.tmask;
-    }
-    if (hit) break;
-    const int2 nd = m.nodes[node];
-    acc += nd.x, node = nd.y;
-  }
-  acc = acc > BEAM_LM_RAWLIM ? BEAM_LM_RAWLIM : acc;
-  acc = acc < -BEAM_LM_RAWLIM ? -BEAM_LM_RAWLIM : acc;
-  return (int)acc;
-}
-
-// the word id of a label hash, -1: none
-__device__ __forceinline__ int lm_word(const LmView& m, unsigned long long h) {
-  unsigned s = (unsigned)h & m.wmask;
-  for (int pr = 0; pr < m.wprobe; ++pr) {
-    const int4 e = m.words[s];
-    if (e.z < 0) return -1;
-    if ((unsigned)e.x == (unsigned)h && (unsigned)e.y == (unsigned)(h >> 32)) return e.z;
-    s = (s + 1) & m.wmask;
-  }
-  return -1;
-}
-
 __global__ void __launch_bounds__(BEAM_NT) k_beam_lm(BeamLmP q) {
   __shared__ BeamLmLds L;
   const BeamP& p = q.b;
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int tid = threadIdx.x;
   const int b = blockIdx.x, T = p.T, N = p.N, W = p.W, N1 = N + 1, blank = p.blank;
   const int lim = p.lens ? min(max(p.lens[b], 0), T) : T;
   int2* const nodes = p.nodes + (size_t)b * T * W;
   const int n_nodes = T * W;
   // the model (validated on the host by qasr_lm_check); a header that does not fit the bytes given ends the search empty
-  const int* const hdr = q.lm;
   LmView m;
-  m.order = hdr[2], m.tprobe = hdr[7], m.wprobe = hdr[10], m.n_labels = hdr[8];
-  m.tmask = (unsigned)hdr[6] - 1u, m.wmask = (unsigned)hdr[9] - 1u;
-  m.trans = reinterpret_cast<const int4*>(hdr + 32);
-  m.words = m.trans + (size_t)hdr[6];
-  m.nodes = reinterpret_cast<const int2*>(m.words + (size_t)hdr[9]);
-  m.l2w = reinterpret_cast<const int*>(m.nodes + (size_t)hdr[4]);
-  const bool word_mode = hdr[3] != 0;
   const int space = q.space;
-  const long long alpha_q = q.alpha_q, beta_q = q.beta_q;
-  const bool model_ok = hdr[0] == BEAM_LM_MAGIC && (long long)hdr[12] == q.lm_bytes && word_mode == (space >= 0) &&
-                        hdr[5] >= 0 && hdr[5] < hdr[4] && m.order >= 1 && m.order <= 6;
-  auto lm_term = [&](int raw) -> long long {
-    return raw == BEAM_LM_NOTERM ? 0ll : ((((long long)raw * alpha_q + 32768ll) >> 16) + beta_q);
-  };
+  const bool model_ok = lm_view(m, q.lm, q.lm_bytes, q.alpha_q, q.beta_q, space);
+  const bool word_mode = m.word_mode;
   for (int i = tid; i < BEAM_TAB; i += BEAM_NT) L.tab[i] = p.tab[i];
   if (tid == 0) {
     BeamLmState& S0 = L.st[0];
     BeamState& S = S0.s;
     S.pb[0] = 0, S.pnb[0] = BEAM_NEG, S.sc[0] = 0, S.hash[0] = 0, S.phash[0] = 0, S.len[0] = 0, S.last[0] = -1, S.node[0] = -1;
-    S0.own[0] = 0, S0.lmt[0] = 0, S0.wh[0] = 0, S0.ctx[0] = model_ok ? hdr[5] : 0;
+    S0.own[0] = 0, S0.lmt[0] = 0, S0.wh[0] = 0, S0.ctx[0] = m.start;
   }
   const int32_t* const gid = p.cand_id + (size_t)b * T * N;
   const int32_t* const gq = p.cand_q + (size_t)b * T * N;
@@ -654,92 +468,10 @@ __global__ void __launch_bounds__(BEAM_NT) k_beam_lm(BeamLmP q) {
       const int n = k - 1, id = L.cid[n];
       if (id < 0 || id == blank || ((r_child >> n) & 1ull)) return BEAM_NEG;
       const long long base = id == r_last ? r_pb : r_sc;
-      return base == BEAM_NEG ? BEAM_NEG : base + (long long)L.cq[n] + lm_term(my_raw[n]);
+      return base == BEAM_NEG ? BEAM_NEG : base + (long long)L.cq[n] + lm_term(m, my_raw[n]);
     };
-    long long mx = LLONG_MIN, mn = LLONG_MAX;
-    int cnt = 0;
-    for (int k = my_sub; k < k_end; k += tpr) {
-      const long long v = cand(k);
-      if (v != BEAM_NEG) { ++cnt; mx = v > mx ? v : mx; mn = v < mn ? v : mn; }
-    }
-#pragma unroll
-    for (int d = 32; d >= 1; d >>= 1) {
-      const long long omx = __shfl_xor(mx, d), omn = __shfl_xor(mn, d);
-      cnt += __shfl_xor(cnt, d);
-      mx = omx > mx ? omx : mx, mn = omn < mn ? omn : mn;
-    }
-    if (lane == 0) L.red_max[wave] = mx, L.red_min[wave] = mn, L.red_cnt[wave] = cnt;
-    __syncthreads();
-    mx = L.red_max[0], mn = L.red_min[0], cnt = L.red_cnt[0];
-#pragma unroll
-    for (int w = 1; w < BEAM_NWAVE; ++w) {
-      mx = L.red_max[w] > mx ? L.red_max[w] : mx, mn = L.red_min[w] < mn ? L.red_min[w] : mn;
-      cnt += L.red_cnt[w];
-    }
-    if (cnt == 0) { nb = 0; break; }
-    auto radix_select = [&](auto keyfn, int nbits, int& kk, int& n_at) -> unsigned long long {
-      const int passes = (nbits + 7) >> 3;
-      unsigned long long prefix = 0;
-      for (int pass = passes - 1; pass >= 0; --pass) {
-        const int shift = pass * 8;
-        __syncthreads();
-        L.hist[tid] = 0;
-        __syncthreads();
-        for (int k = my_sub; k < k_end; k += tpr) {
-          unsigned long long key;
-          if (keyfn(k, key) && (shift + 8 >= 64 || (key >> (shift + 8)) == prefix))
-            atomicAdd(&L.hist[(unsigned)(key >> shift) & 255u], 1u);
-        }
-        __syncthreads();
-        const int mine = (int)L.hist[tid];
-        int inc = mine;
-#pragma unroll
-        for (int d = 1; d < 64; d <<= 1) {
-          const int o = __shfl_up(inc, d);
-          if (lane >= d) inc += o;
-        }
-        if (lane == 63) L.red_a[wave] = inc;
-        __syncthreads();
-        for (int w = 0; w < wave; ++w) inc += L.red_a[w];
-        const int exc = inc - mine;
-        if (exc < kk && kk <= inc) L.bin = tid, L.kk = kk - exc, L.n_at = mine;
-        __syncthreads();
-        prefix = (prefix << 8) | (unsigned long long)L.bin;
-        kk = L.kk, n_at = L.n_at;
-      }
-      return prefix;
-    };
-    unsigned long long rth = ~0ull;
-    int ith = INT_MAX;
-    if (cnt > W) {
-      const unsigned long long range = (unsigned long long)(mx - mn);
-      int need = W, n_at = cnt;
-      rth = radix_select([&](int k, unsigned long long& key) {
-        const long long v = cand(k);
-        key = (unsigned long long)(mx - v);
-        return v != BEAM_NEG;
-      }, range ? 64 - __clzll((long long)range) : 0, need, n_at);
-      if (n_at > need) {
-        const int M = nb * N1;
-        ith = (int)radix_select([&](int k, unsigned long long& key) {
-          const long long v = cand(k);
-          key = (unsigned long long)(my_i * N1 + k);
-          return v != BEAM_NEG && (unsigned long long)(mx - v) == rth;
-        }, 32 - __clz(M), need, n_at);
-      }
-    }
-    for (int k = my_sub; k < k_end; k += tpr) {
-      const long long v = cand(k);
-      if (v != BEAM_NEG) {
-        const unsigned long long r = (unsigned long long)(mx - v);
-        const int idx = my_i * N1 + k;
-        if (r < rth || (r == rth && idx <= ith)) {
-          const int at = atomicAdd(&L.n_sel, 1);
-          if (at < BEAM_W) L.sel_r[at] = r, L.sel_idx[at] = idx;
-        }
-      }
-    }
-    __syncthreads();
+    long long mx;
+    if (!beam_select(L, cand, my_i, my_sub, tpr, k_end, nb, N1, W, mx)) { nb = 0; break; }
     const int ns = min(L.n_sel, W);
     if (tid < ns) {
       const unsigned long long r = L.sel_r[tid];
@@ -766,7 +498,7 @@ __global__ void __launch_bounds__(BEAM_NT) k_beam_lm(BeamLmP q) {
         D.node[rank] = nd;
         nodes[nd] = make_int2(S.node[i], c);
         const int raw = L.raw[i * N + k - 1];         // written before the barriers of the selection
-        const long long tm = lm_term(raw);
+        const long long tm = lm_term(m, raw);
         int ctx = SL.ctx[i];
         unsigned long long wh = 0;
         if (word_mode && c != space) {
@@ -793,7 +525,7 @@ __global__ void __launch_bounds__(BEAM_NT) k_beam_lm(BeamLmP q) {
       const int last = SL.s.last[tid];
       if (last >= 0 && last != space) {
         int nx;
-        const long long tm = lm_term(lm_walk(m, SL.ctx[tid], lm_word(m, SL.wh[tid]), nx));
+        const long long tm = lm_term(m, lm_walk(m, SL.ctx[tid], lm_word(m, SL.wh[tid]), nx));
         sc += tm, lmt += tm;
       }
       L.k_sc[tid] = sc;

@@ -1,7 +1,7 @@
 // CTC prefix beam search with phrase boosting ("hot words"): k_beam_boost, with an n-gram model (LM = true) and without
 // (LM = false: no model state is carried).  The rules are BOOST_RULES of qasr/boost.py (with LM_RULES of qasr/beam.py for
-// the model), which this kernel follows bit for bit; the packed phrase set is qasr/boost.py's.  A file of its own, so that
-// k_beam and k_beam_lm (qasr_beam.hip) stay as they are: the selection machinery below is theirs, line for line.  What
+// the model), which this kernel follows bit for bit; the packed phrase set is qasr/boost.py's.  The selection, the
+// views of the model and of the set, the walks and the look-up are qasr_beam_dev.h's, shared with qasr_beam.hip.  What
 // differs from k_beam_lm: an entry also keeps its automaton state, the pot of that state and the running sum boost_tot;
 // `own` holds the summed term (model + boost).  The frame's boost terms are evaluated ONCE, before the selection: the
 // thread that scores candidate (slot, n) looks up s' = delta(state[slot], label n) - an entry in the root state reads the
@@ -11,116 +11,10 @@
 // repeats its one look-up for its next state.  The set stays in global memory and is read with plain vector loads.  After the
 // last frame every entry takes the virtual space (whole words), loses its unfinished pot and - with a word-mode model -
 // receives its unfinished word's term, then ONE re-ordering.  No exp or log, no allocation, LDS atomics only.
-#include <climits>
-
-#include "qasr_internal.h"
+#include "qasr_beam_dev.h"
 
 namespace qasr {
-namespace {                 // the helpers of qasr_beam.hip, repeated here so that that file's code does not change
-
-#define BEAM_NEG (-(1ll << 62))
-#define BEAM_QFLOOR (-1073741824.f)
-#define BEAM_QCEIL (1073741824.f)
-#define BEAM_EMPTY_Q INT_MIN
-#define BEAM_DMAX (16ll << 16)
-#define BEAM_HMUL 0x9E3779B97F4A7C15ull
-
-#define BEAM_NT 256
-#define BEAM_NWAVE (BEAM_NT / 64)
-#define BEAM_W QASR_BEAM_MAX_WIDTH
-#define BEAM_N QASR_BEAM_MAX_CANDIDATES
-#define BEAM_TAB QASR_BEAM_TABLE_ENTRIES
-
-struct BeamP {
-  const int32_t* cand_id;   // [B][T][N]
-  const int32_t* cand_q;
-  const int32_t* lens;      // optional [B]
-  const uint16_t* tab;      // [BEAM_TAB]
-  int2* nodes;              // [B][T * W] (parent node, label)
-  int32_t* labels;          // [B][n_best][T]
-  int32_t* n_labels;        // [B][n_best]
-  long long* score;         // [B][n_best]
-  int32_t* n_hyps;          // [B]
-  int B, T, N, W, n_best, blank;
-};
-
-struct BeamState {          // one side of the double buffer
-  long long pb[BEAM_W], pnb[BEAM_W], sc[BEAM_W];
-  unsigned long long hash[BEAM_W], phash[BEAM_W];
-  int len[BEAM_W], last[BEAM_W], node[BEAM_W];
-};
-
-__device__ __forceinline__ long long beam_lae(long long a, long long b, const uint16_t* tab) {
-  const long long m = a > b ? a : b, n = a > b ? b : a;
-  if (n == BEAM_NEG) return m;
-  const long long d = m - n;
-  if (d >= BEAM_DMAX) return m;
-  return m + (long long)tab[d >> 6];
-}
-
-#define BEAM_LM_MAGIC 0x314D4C51
-#define BEAM_LM_OOV (-1000 * 65536)
-#define BEAM_LM_RAWLIM 2147483647ll
-#define BEAM_LM_NOTERM INT_MIN
-
-struct LmView {
-  const int4* trans;        // [tmask + 1] node, word, prob_q, next
-  const int4* words;        // [wmask + 1] hash lo, hash hi, word id, 0
-  const int2* nodes;        // [n_nodes] backoff_q, suffix
-  const int* l2w;           // [n_labels]
-  int order, tprobe, wprobe, n_labels;
-  unsigned tmask, wmask;
-};
-
-// raw(ctx, w) and the context it leaves
-__device__ __forceinline__ int lm_walk(const LmView& m, int ctx, int w, int& next) {
-  next = 0;
-  if (w < 0) return BEAM_LM_OOV;
-  long long acc = 0;
-  int node = ctx;
-  for (int it = 0; it < m.order; ++it) {
-    unsigned long long x = (((unsigned long long)(unsigned)node << 32) | (unsigned long long)(unsigned)w) * BEAM_HMUL;
-    x ^= x >> 32;
-    unsigned s = (unsigned)x & m.tmask;
-    bool hit = false;
-    for (int pr = 0; pr < m.tprobe; ++pr) {
-      const int4 e = m.trans[s];
-      if (e.x == node && e.y == w) { acc += e.z; next = e.w; hit = true; break; }
-      if (e.x < 0) break;
-      s = (s + 1) & m.tmask;
-    }
-    if (hit) break;
-    const int2 nd = m.nodes[node];
-    acc += nd.x, node = nd.y;
-  }
-  acc = acc > BEAM_LM_RAWLIM ? BEAM_LM_RAWLIM : acc;
-  acc = acc < -BEAM_LM_RAWLIM ? -BEAM_LM_RAWLIM : acc;
-  return (int)acc;
-}
-
-// the word id of a label hash, -1: none
-__device__ __forceinline__ int lm_word(const LmView& m, unsigned long long h) {
-  unsigned s = (unsigned)h & m.wmask;
-  for (int pr = 0; pr < m.wprobe; ++pr) {
-    const int4 e = m.words[s];
-    if (e.z < 0) return -1;
-    if ((unsigned)e.x == (unsigned)h && (unsigned)e.y == (unsigned)(h >> 32)) return e.z;
-    s = (s + 1) & m.wmask;
-  }
-  return -1;
-}
-
-// ------------------------------------------------------------------------------------------------------ k_beam_boost
-#define BOOST_MAGIC 0x31534251
-#define BOOST_BIAS (1ll << 30)
-
-struct BoostView {
-  const int4* table;        // [mask + 1] node, label, next, 0
-  const int2* nodes;        // [n_nodes] pot_q, bank_q
-  const int* root_next;     // [n_labels]
-  int probe, n_labels;
-  unsigned mask;
-};
+namespace {
 
 struct BoostP {
   BeamP b;
@@ -160,76 +54,32 @@ struct BoostLds {
   int raw[LM ? BEAM_W * BEAM_N : 1];
 };
 
-// delta(s, c): one bounded probe sequence, a miss is the root's row; the root itself reads its row only
-__device__ __forceinline__ int boost_next(const BoostView& v, int s, int c) {
-  if (c < 0 || c >= v.n_labels) return 0;
-  const int rn = v.root_next[c];
-  if (s == 0) return rn;
-  unsigned long long x = (((unsigned long long)(unsigned)s << 32) | (unsigned long long)(unsigned)c) * BEAM_HMUL;
-  x ^= x >> 32;
-  unsigned k = (unsigned)x & v.mask;
-  for (int pr = 0; pr < v.probe; ++pr) {
-    const int4 e = v.table[k];
-    if (e.x == s && e.y == c) return e.z;
-    if (e.x < 0) break;
-    k = (k + 1) & v.mask;
-  }
-  return rn;
-}
-
 template <bool LM>
 __global__ void __launch_bounds__(BEAM_NT) k_beam_boost(BoostP q) {
   __shared__ BoostLds<LM> L;
   const BeamP& p = q.b;
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int tid = threadIdx.x;
   const int b = blockIdx.x, T = p.T, N = p.N, W = p.W, N1 = N + 1, blank = p.blank;
   const int lim = p.lens ? min(max(p.lens[b], 0), T) : T;
   int2* const nodes = p.nodes + (size_t)b * T * W;
   const int n_nodes = T * W;
   const int space = q.space;
   // the phrase set (validated on the host by qasr_boost_check); a header that does not fit the bytes given ends the search empty
-  const int* const bh = q.boost;
   BoostView v;
-  const int b_nodes = bh[3], b_cap = bh[7], b_start = bh[5];
-  v.n_labels = bh[4], v.probe = bh[8], v.mask = (unsigned)b_cap - 1u;
-  v.table = reinterpret_cast<const int4*>(bh + 32);
-  v.nodes = reinterpret_cast<const int2*>(v.table + (size_t)(b_cap > 0 ? b_cap : 0));
-  v.root_next = reinterpret_cast<const int*>(v.nodes + (size_t)(b_nodes > 0 ? b_nodes : 0));
-  const bool whole = bh[6] != 0;
-  bool ok = bh[0] == BOOST_MAGIC && bh[1] == 1 && (long long)bh[2] == q.boost_bytes && b_nodes >= 1 && v.n_labels >= 1 &&
-            b_cap >= 1 && (b_cap & (b_cap - 1)) == 0 && v.probe >= 1 && v.probe <= b_cap && b_start >= 0 && b_start < b_nodes &&
-            128ll + 16ll * b_cap + 8ll * b_nodes + 4ll * v.n_labels == q.boost_bytes &&
-            whole == (q.whole_words != 0) && (!whole || (space >= 0 && space < v.n_labels));
+  bool ok = boost_view(v, q.boost, q.boost_bytes, q.whole_words, space);
+  const bool whole = v.whole;
   // the model, as k_beam_lm reads it
   LmView m{};
-  bool word_mode = false;
-  long long alpha_q = 0, beta_q = 0;
-  int lm_start = 0;
-  if constexpr (LM) {
-    const int* const hdr = q.lm;
-    m.order = hdr[2], m.tprobe = hdr[7], m.wprobe = hdr[10], m.n_labels = hdr[8];
-    m.tmask = (unsigned)hdr[6] - 1u, m.wmask = (unsigned)hdr[9] - 1u;
-    m.trans = reinterpret_cast<const int4*>(hdr + 32);
-    m.words = m.trans + (size_t)hdr[6];
-    m.nodes = reinterpret_cast<const int2*>(m.words + (size_t)hdr[9]);
-    m.l2w = reinterpret_cast<const int*>(m.nodes + (size_t)hdr[4]);
-    word_mode = hdr[3] != 0;
-    alpha_q = q.alpha_q, beta_q = q.beta_q;
-    lm_start = hdr[5];
-    ok = ok && hdr[0] == BEAM_LM_MAGIC && (long long)hdr[12] == q.lm_bytes && word_mode == (space >= 0) &&
-         hdr[5] >= 0 && hdr[5] < hdr[4] && m.order >= 1 && m.order <= 6;
-  }
-  auto lm_term = [&](int raw) -> long long {
-    return raw == BEAM_LM_NOTERM ? 0ll : ((((long long)raw * alpha_q + 32768ll) >> 16) + beta_q);
-  };
+  if constexpr (LM) ok = lm_view(m, q.lm, q.lm_bytes, q.alpha_q, q.beta_q, space) && ok;
+  const bool word_mode = m.word_mode;
   for (int i = tid; i < BEAM_TAB; i += BEAM_NT) L.tab[i] = p.tab[i];
   if (tid == 0) {
     BoostState<LM>& S0 = L.st[0];
     BeamState& S = S0.s;
     S.pb[0] = 0, S.pnb[0] = BEAM_NEG, S.sc[0] = 0, S.hash[0] = 0, S.phash[0] = 0, S.len[0] = 0, S.last[0] = -1, S.node[0] = -1;
-    const int s0 = ok ? b_start : 0;
+    const int s0 = ok ? v.start : 0;
     S0.own[0] = 0, S0.bt[0] = 0, S0.bst[0] = s0, S0.bpot[0] = ok ? v.nodes[s0].x : 0;
-    if constexpr (LM) S0.lmt[0] = 0, S0.wh[0] = 0, S0.ctx[0] = ok ? lm_start : 0;
+    if constexpr (LM) S0.lmt[0] = 0, S0.wh[0] = 0, S0.ctx[0] = ok ? m.start : 0;
   }
   const int32_t* const gid = p.cand_id + (size_t)b * T * N;
   const int32_t* const gq = p.cand_q + (size_t)b * T * N;
@@ -305,7 +155,7 @@ __global__ void __launch_bounds__(BEAM_NT) k_beam_boost(BoostP q) {
         const bool scored = id >= 0 && id != blank && !((r_child >> n) & 1ull);
         long long bt = 0;
         if (scored) {
-          const int2 nd = v.nodes[boost_next(v, r_bst, id)];
+          const int2 nd = v.nodes[boost_next<false>(v, r_bst, id)];
           bt = (long long)nd.x - (long long)r_bpot + (long long)nd.y;
         }
         my_bterm[n] = (unsigned)(bt + BOOST_BIAS);
@@ -326,93 +176,11 @@ __global__ void __launch_bounds__(BEAM_NT) k_beam_boost(BoostP q) {
       const long long base = id == r_last ? r_pb : r_sc;
       if (base == BEAM_NEG) return BEAM_NEG;
       long long v0 = base + (long long)L.cq[n] + ((long long)my_bterm[n] - BOOST_BIAS);
-      if constexpr (LM) v0 += lm_term(my_raw[n]);
+      if constexpr (LM) v0 += lm_term(m, my_raw[n]);
       return v0;
     };
-    long long mx = LLONG_MIN, mn = LLONG_MAX;
-    int cnt = 0;
-    for (int k = my_sub; k < k_end; k += tpr) {
-      const long long vv = cand(k);
-      if (vv != BEAM_NEG) { ++cnt; mx = vv > mx ? vv : mx; mn = vv < mn ? vv : mn; }
-    }
-#pragma unroll
-    for (int d = 32; d >= 1; d >>= 1) {
-      const long long omx = __shfl_xor(mx, d), omn = __shfl_xor(mn, d);
-      cnt += __shfl_xor(cnt, d);
-      mx = omx > mx ? omx : mx, mn = omn < mn ? omn : mn;
-    }
-    if (lane == 0) L.red_max[wave] = mx, L.red_min[wave] = mn, L.red_cnt[wave] = cnt;
-    __syncthreads();
-    mx = L.red_max[0], mn = L.red_min[0], cnt = L.red_cnt[0];
-#pragma unroll
-    for (int w = 1; w < BEAM_NWAVE; ++w) {
-      mx = L.red_max[w] > mx ? L.red_max[w] : mx, mn = L.red_min[w] < mn ? L.red_min[w] : mn;
-      cnt += L.red_cnt[w];
-    }
-    if (cnt == 0) { nb = 0; break; }
-    auto radix_select = [&](auto keyfn, int nbits, int& kk, int& n_at) -> unsigned long long {
-      const int passes = (nbits + 7) >> 3;
-      unsigned long long prefix = 0;
-      for (int pass = passes - 1; pass >= 0; --pass) {
-        const int shift = pass * 8;
-        __syncthreads();
-        L.hist[tid] = 0;
-        __syncthreads();
-        for (int k = my_sub; k < k_end; k += tpr) {
-          unsigned long long key;
-          if (keyfn(k, key) && (shift + 8 >= 64 || (key >> (shift + 8)) == prefix))
-            atomicAdd(&L.hist[(unsigned)(key >> shift) & 255u], 1u);
-        }
-        __syncthreads();
-        const int mine = (int)L.hist[tid];
-        int inc = mine;
-#pragma unroll
-        for (int d = 1; d < 64; d <<= 1) {
-          const int o = __shfl_up(inc, d);
-          if (lane >= d) inc += o;
-        }
-        if (lane == 63) L.red_a[wave] = inc;
-        __syncthreads();
-        for (int w = 0; w < wave; ++w) inc += L.red_a[w];
-        const int exc = inc - mine;
-        if (exc < kk && kk <= inc) L.bin = tid, L.kk = kk - exc, L.n_at = mine;
-        __syncthreads();
-        prefix = (prefix << 8) | (unsigned long long)L.bin;
-        kk = L.kk, n_at = L.n_at;
-      }
-      return prefix;
-    };
-    unsigned long long rth = ~0ull;
-    int ith = INT_MAX;
-    if (cnt > W) {
-      const unsigned long long range = (unsigned long long)(mx - mn);
-      int need = W, n_at = cnt;
-      rth = radix_select([&](int k, unsigned long long& key) {
-        const long long vv = cand(k);
-        key = (unsigned long long)(mx - vv);
-        return vv != BEAM_NEG;
-      }, range ? 64 - __clzll((long long)range) : 0, need, n_at);
-      if (n_at > need) {
-        const int M = nb * N1;
-        ith = (int)radix_select([&](int k, unsigned long long& key) {
-          const long long vv = cand(k);
-          key = (unsigned long long)(my_i * N1 + k);
-          return vv != BEAM_NEG && (unsigned long long)(mx - vv) == rth;
-        }, 32 - __clz(M), need, n_at);
-      }
-    }
-    for (int k = my_sub; k < k_end; k += tpr) {
-      const long long vv = cand(k);
-      if (vv != BEAM_NEG) {
-        const unsigned long long r = (unsigned long long)(mx - vv);
-        const int idx = my_i * N1 + k;
-        if (r < rth || (r == rth && idx <= ith)) {
-          const int at = atomicAdd(&L.n_sel, 1);
-          if (at < BEAM_W) L.sel_r[at] = r, L.sel_idx[at] = idx;
-        }
-      }
-    }
-    __syncthreads();
+    long long mx;
+    if (!beam_select(L, cand, my_i, my_sub, tpr, k_end, nb, N1, W, mx)) { nb = 0; break; }
     const int ns = min(L.n_sel, W);
     if (tid < ns) {
       const unsigned long long r = L.sel_r[tid];
@@ -440,11 +208,11 @@ __global__ void __launch_bounds__(BEAM_NT) k_beam_boost(BoostP q) {
         D.node[rank] = nd;
         nodes[nd] = make_int2(S.node[i], c);
         const long long btm = (long long)L.bterm[i * N + k - 1] - BOOST_BIAS;      // written before the barriers of the selection
-        const int s2 = boost_next(v, SL.bst[i], c);     // the one look-up again, for the next state
+        const int s2 = boost_next<false>(v, SL.bst[i], c);     // the one look-up again, for the next state
         long long own = btm;
         if constexpr (LM) {
           const int raw = L.raw[i * N + k - 1];
-          const long long tm = lm_term(raw);
+          const long long tm = lm_term(m, raw);
           int ctx = SL.ctx[i];
           unsigned long long wh = 0;
           if (word_mode && c != space) {
@@ -477,13 +245,13 @@ __global__ void __launch_bounds__(BEAM_NT) k_beam_boost(BoostP q) {
         const int last = SL.s.last[tid];
         if (word_mode && last >= 0 && last != space) {
           int nx;
-          const long long tm = lm_term(lm_walk(m, SL.ctx[tid], lm_word(m, SL.wh[tid]), nx));
+          const long long tm = lm_term(m, lm_walk(m, SL.ctx[tid], lm_word(m, SL.wh[tid]), nx));
           sc += tm, lmt += tm;
         }
       }
       long long pot = (long long)SL.bpot[tid];
       if (whole) {
-        const int2 nd = v.nodes[boost_next(v, SL.bst[tid], space)];
+        const int2 nd = v.nodes[boost_next<false>(v, SL.bst[tid], space)];
         const long long tm = (long long)nd.x - pot + (long long)nd.y;
         sc += tm, bt += tm, pot = (long long)nd.x;
       }

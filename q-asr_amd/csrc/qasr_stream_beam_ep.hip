@@ -1,8 +1,8 @@
 // Streaming beam endpointing (k_stream_beam_ep<LM, BOOST>): the streaming prefix beam search of k_stream_beam / k_stream_beam_boost
 // for sessions that k_stream_endpoint cuts into utterances.  The host statement is qasr/stream_beam.py (STREAM_BEAM_EP_RULES
 // over STREAM_BEAM_RULES / STREAM_BOOST_RULES), and this file follows it byte for byte, the state block and the ring included.
-// A kernel of its own, as the house pattern has it: qasr_stream_beam.hip and qasr_stream_beam_boost.hip stay as they are, and
-// the helpers they keep to themselves are repeated here under sbe_ names, so that no existing kernel's code object changes.
+// The one beam kernel that keeps its own copy (sbe_ names) of the helpers, the selection and the body: on qasr_beam_dev.h
+// alone, and on the body of qasr_stream_beam_dev.h, its boosted instantiations measured past the 3 % margin.
 //
 // One work-group of 256 threads per row, launched AFTER k_stream_emit and k_stream_endpoint of the same rows: lo is the beam
 // block's own frames_done (0 on BEGIN), hi the stream block's frames_done as emit left it, and the step's records are read
