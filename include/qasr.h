@@ -468,7 +468,12 @@ int qasr_ctc_beam_boost(void* stream, const qasr_ctc_beam_boost_args* args);
  * QASR_ERR_ARG with nothing launched and no output written: an unknown struct_size, a NULL among log_probs, targets,
  * target_lens, workspace, ok; B, T, C or K < 1, P != B * K, T > QASR_BEAM_MAX_FRAMES, max_labels outside
  * 1 .. QASR_ALIGN_MAX_LABELS, blank outside [0, C), pitch_frame < C, pitch_utt < T * pitch_frame, total without lae_table, a
- * lae_table with lae_entries != QASR_BEAM_TABLE_ENTRIES, a workspace smaller than the query says. */
+ * lae_table with lae_entries != QASR_BEAM_TABLE_ENTRIES, a workspace smaller than the query says, a star_logp with
+ * star_pitch < T.
+ * star_logp / star_pitch (the wildcard, see qasr_ctc_star below): f32 [B][star_pitch], one row per utterance.  With a plane
+ * the label id C is a valid target label whose log-probability at frame t is star_logp[u][t] wherever logp[u][t][c] is read
+ * (emission, score); NULL: id C is a label outside [0, C) as before.  struct_size may be the size of the struct without
+ * these two fields (QASR_CTC_ALIGN_ARGS_V1_SIZE): they then count as absent and the call is the one it was. */
 #define QASR_ALIGN_MAX_LABELS 2048
 typedef struct qasr_ctc_align_args {
   uint32_t struct_size;
@@ -489,7 +494,10 @@ typedef struct qasr_ctc_align_args {
   int64_t* path_score;         /* optional */
   int64_t* total;              /* optional */
   int32_t* ok;
+  const float* star_logp;      /* optional [B][star_pitch]: the wildcard's plane */
+  int64_t star_pitch;          /* in floats, >= T (with star_logp) */
 } qasr_ctc_align_args;
+#define QASR_CTC_ALIGN_ARGS_V1_SIZE offsetof(qasr_ctc_align_args, star_logp)
 size_t qasr_ctc_align_workspace_bytes(int P, int T, int max_labels);   /* 0 for a shape qasr_ctc_align refuses */
 int qasr_ctc_align(void* stream, const qasr_ctc_align_args* args);
 
@@ -514,7 +522,9 @@ int qasr_ctc_align(void* stream, const qasr_ctc_align_args* args);
  * QASR_ERR_ARG with nothing launched and no output written: an unknown struct_size, a NULL among log_probs, targets,
  * target_lens, workspace, ok; B, T or C < 1, T > QASR_BAND_MAX_FRAMES, max_labels outside 1 .. QASR_BAND_MAX_LABELS, band_states
  * not 256, 1024 or 4352, blank outside [0, C), pitch_frame < C, pitch_utt < T * pitch_frame, a workspace that is not 4-byte
- * aligned or smaller than the query says. */
+ * aligned or smaller than the query says, a star_logp with star_pitch < T.
+ * star_logp / star_pitch: the wildcard's plane f32 [B][star_pitch] exactly as in qasr_ctc_align (frame_logp reads it too);
+ * struct_size may be QASR_CTC_ALIGN_BAND_ARGS_V1_SIZE, the struct without the two fields. */
 #define QASR_BAND_MAX_LABELS (1 << 20)
 #define QASR_BAND_MAX_FRAMES (1 << 22)
 typedef struct qasr_ctc_align_band_args {
@@ -535,9 +545,38 @@ typedef struct qasr_ctc_align_band_args {
   float* frame_logp;           /* optional */
   int32_t* band_base;          /* optional */
   int32_t* ok;
+  const float* star_logp;      /* optional [B][star_pitch]: the wildcard's plane */
+  int64_t star_pitch;          /* in floats, >= T (with star_logp) */
 } qasr_ctc_align_band_args;
+#define QASR_CTC_ALIGN_BAND_ARGS_V1_SIZE offsetof(qasr_ctc_align_band_args, star_logp)
 size_t qasr_ctc_align_band_workspace_bytes(int B, int T, int band_states);   /* 0 for a shape qasr_ctc_align_band refuses */
 int qasr_ctc_align_band(void* stream, const qasr_ctc_align_band_args* args);
+
+/* ---- the wildcard ("star") for audio the transcript does not cover -------------------------------------------------------
+ * A transcript that omits part of the audio pushes those frames onto the neighbouring labels.  The wildcard is one more
+ * label, id C, that the caller puts into the target where text is missing; its log-probability at frame t is not a column of
+ * log_probs but star[u][t] = max over c < C of log_probs[u][t][c] - penalty (the maximum in the order k_ctc and k_align take
+ * maxima in, one IEEE float32 subtraction) for t < lens[u], 0 behind: the best class of the frame, less a price per frame that
+ * keeps the wildcard from eating its neighbours.  qasr_ctc_star (k_star: one wave per frame, log_probs read once) writes that
+ * plane; qasr_ctc_align / qasr_ctc_align_band take it as star_logp.  The rules are STAR_RULES of qasr/align.py, which the
+ * kernels follow bit for bit: every output equals the call without a plane on log_probs with star as class C of C + 1.
+ * Nothing is allocated and no length is read on the host, so the call can be captured.
+ * QASR_ERR_ARG with nothing launched and no output written: an unknown struct_size, a NULL log_probs or star, B, T or C < 1,
+ * pitch_frame < C, pitch_utt < T * pitch_frame, star_pitch < T, a penalty that is not finite or outside
+ * 0 .. QASR_STAR_MAX_PENALTY. */
+#define QASR_STAR_MAX_PENALTY 16.0f
+typedef struct qasr_ctc_star_args {
+  uint32_t struct_size;
+  int32_t B, T, C;
+  int64_t pitch_utt, pitch_frame;   /* in floats */
+  const float* log_probs;
+  const int32_t* lens;         /* optional [B] */
+  float penalty;               /* nats per frame */
+  uint32_t reserved;
+  float* star;                 /* [B][star_pitch] */
+  int64_t star_pitch;          /* in floats, >= T */
+} qasr_ctc_star_args;
+int qasr_ctc_star(void* stream, const qasr_ctc_star_args* args);
 
 /* ---- audio at any sample rate: rational polyphase resampler and PCM ingest -----------------------------------------------
  * What AudioSegment.__init__ does on the host with librosa.core.resample when target_sr != sample_rate (parts/segment.py:

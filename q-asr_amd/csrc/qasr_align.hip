@@ -17,6 +17,9 @@
 // Back-walk: the path moves by at most 2 states per frame, so 64 frames (16 byte rows) need a window of 129 states.  All
 // threads copy that window into LDS (one global round trip per 64 frames), thread 0 walks it there and leaves, per label,
 // its first frame and frame count in LDS; then one thread per label takes the maximum of its frames' log-probabilities.
+// k_align<NS, STAR>: with STAR the label id C is the wildcard of STAR_RULES (qasr/align.py): wherever a state's or a label's
+// log-probability is gathered, c == C reads star[u][t] in place of logp[u][t][c], and the target check accepts c == C.  The
+// STAR = false instantiations take the kernel argument they always took (AlignP) and are the code they were.
 // LDS atomics: none.  Global memory sees plain vector stores.  Every loop is bounded by T, the number of states, the row
 // pitch or a constant; nothing is allocated and no length is read on the host.
 #include <climits>
@@ -52,6 +55,11 @@ struct AlignP {
   int T, C, K, blank, ML, pitch_s, G4;
 };
 
+struct AlignPS : AlignP {       // k_align<NS, true>'s argument
+  const float* star;            // [B][star_pitch]
+  long long star_pitch;
+};
+
 __device__ __forceinline__ int align_key(int bits) { return bits ^ ((bits >> 31) & 0x7fffffff); }
 
 __device__ __forceinline__ long long align_quantize(float x) {
@@ -75,8 +83,8 @@ size_t align_workspace_bytes(int P, int T, int max_labels) {
   return (size_t)P * (size_t)((T + 3) / 4) * (size_t)align_pitch(max_labels);
 }
 
-template <int NS>
-__global__ void __launch_bounds__(ALIGN_NT) k_align(AlignP p) {
+template <int NS, bool STAR>
+__global__ void __launch_bounds__(ALIGN_NT) k_align(std::conditional_t<STAR, AlignPS, AlignP> p) {
   __shared__ long long rows[2][NS * ALIGN_NT];
   __shared__ uint16_t tab[ALIGN_TAB];
   __shared__ unsigned char win[ALIGN_G * ALIGN_WINW];
@@ -100,7 +108,7 @@ __global__ void __launch_bounds__(ALIGN_NT) k_align(AlignP p) {
   if (len_ok)
     for (int i = tid; i < L; i += ALIGN_NT) {
       const int c = y[i];
-      if (c < 0 || c >= C || c == blank) sh_bad = 1;
+      if (c < 0 || c >= C + (STAR ? 1 : 0) || c == blank) sh_bad = 1;
     }
   __syncthreads();
   bool alignable = len_ok && !sh_bad && !(lim == 0 && L > 0);
@@ -120,6 +128,12 @@ __global__ void __launch_bounds__(ALIGN_NT) k_align(AlignP p) {
   const float* const base = p.logp + (long long)u * p.pitch_b;
   unsigned char* const wsp = p.ws + (size_t)pr * (size_t)p.G4 * (size_t)p.pitch_s;
   const size_t pitch_s = (size_t)p.pitch_s;
+  // logp[u][t][c]; with STAR the wildcard c == C reads its plane instead (t < lim <= T <= star_pitch) and nothing at base[.. + C]
+  auto emit = [&](long long t, int c) -> float {
+    if constexpr (STAR)
+      if (c == C) return p.star[(long long)u * p.star_pitch + t];
+    return base[t * p.pitch_t + c];
+  };
 
   // one pass over the frames (vit: Viterbi with backpointers, else forward); returns the row that holds frame lim - 1
   auto run = [&](auto vit_tag) -> int {
@@ -130,9 +144,9 @@ __global__ void __launch_bounds__(ALIGN_NT) k_align(AlignP p) {
     for (int k = 0; k < NS; ++k) {
       const int s = tid + k * ALIGN_NT;
       acc[k] = 0;
-      pf[k] = s < S ? base[lab[k]] : 0.f;                           // frame 0 (lim >= 1 here)
+      pf[k] = s < S ? emit(0, lab[k]) : 0.f;                        // frame 0 (lim >= 1 here)
       if (s < S) rows[0][s] = s < 2 ? align_quantize(pf[k]) : ALIGN_NEG;
-      pf[k] = (s < S && lim > 1) ? base[p.pitch_t + lab[k]] : 0.f;
+      pf[k] = (s < S && lim > 1) ? emit(1, lab[k]) : 0.f;
     }
     int cur = 0;
     __syncthreads();
@@ -141,7 +155,7 @@ __global__ void __launch_bounds__(ALIGN_NT) k_align(AlignP p) {
 #pragma unroll
       for (int k = 0; k < NS; ++k) {                                // frame t + 1's gathers, in flight across this frame
         const int s = tid + k * ALIGN_NT;
-        nx[k] = (s < S && t + 1 < lim) ? base[(long long)(t + 1) * p.pitch_t + lab[k]] : 0.f;
+        nx[k] = (s < S && t + 1 < lim) ? emit(t + 1, lab[k]) : 0.f;
       }
       const long long* const R = rows[cur];
       long long* const W = rows[cur ^ 1];
@@ -259,10 +273,13 @@ __global__ void __launch_bounds__(ALIGN_NT) k_align(AlignP p) {
     if (i < L) {
       st = min(max(lstart[i], 0), lim - 1), n = min(max(lcnt[i], 0), lim - st);
       if (o_score && n > 0) {
-        const float* const col = base + y[i];
+        const float* col = base + y[i];
+        long long step = p.pitch_t;
+        if constexpr (STAR)
+          if (y[i] == C) col = p.star + (long long)u * p.star_pitch, step = 1;
         int best = INT_MIN;
         for (int f = 0; f < n; ++f) {
-          const int key = align_key(__float_as_int(col[(long long)(st + f) * p.pitch_t]));
+          const int key = align_key(__float_as_int(col[(long long)(st + f) * step]));
           best = key > best ? key : best;
         }
         sc = __int_as_float(align_key(best));
@@ -289,8 +306,19 @@ __global__ void __launch_bounds__(ALIGN_NT) k_align(AlignP p) {
   }
 }
 
+template <bool STAR>
+static void launch_align_ns(hipStream_t s, const std::conditional_t<STAR, AlignPS, AlignP>& p, int P, int states) {
+  const dim3 grid((unsigned)P), block(ALIGN_NT);
+  static_assert(2 * QASR_ALIGN_MAX_LABELS + 1 <= 17 * ALIGN_NT, "k_align<17> holds the longest target");
+  if (states <= 1 * ALIGN_NT) hipLaunchKernelGGL((k_align<1, STAR>), grid, block, 0, s, p);
+  else if (states <= 2 * ALIGN_NT) hipLaunchKernelGGL((k_align<2, STAR>), grid, block, 0, s, p);
+  else if (states <= 4 * ALIGN_NT) hipLaunchKernelGGL((k_align<4, STAR>), grid, block, 0, s, p);
+  else if (states <= 8 * ALIGN_NT) hipLaunchKernelGGL((k_align<8, STAR>), grid, block, 0, s, p);
+  else hipLaunchKernelGGL((k_align<17, STAR>), grid, block, 0, s, p);
+}
+
 int launch_align(hipStream_t s, const qasr_ctc_align_args& a) {
-  AlignP p{};
+  AlignPS p{};
   p.logp = a.log_probs, p.lens = a.lens, p.targets = a.targets, p.target_lens = a.target_lens, p.tab = a.lae_table;
   p.ws = (unsigned char*)a.workspace;
   p.start = a.start, p.nframes = a.nframes, p.score = a.score;
@@ -298,14 +326,10 @@ int launch_align(hipStream_t s, const qasr_ctc_align_args& a) {
   p.pitch_b = a.pitch_utt, p.pitch_t = a.pitch_frame;
   p.T = a.T, p.C = a.C, p.K = a.K, p.blank = a.blank, p.ML = a.max_labels;
   p.pitch_s = align_pitch(a.max_labels), p.G4 = (a.T + 3) / 4;
+  p.star = a.star_logp, p.star_pitch = a.star_pitch;
   const int states = 2 * a.max_labels + 1;                          // <= 4097
-  const dim3 grid((unsigned)a.P), block(ALIGN_NT);
-  static_assert(2 * QASR_ALIGN_MAX_LABELS + 1 <= 17 * ALIGN_NT, "k_align<17> holds the longest target");
-  if (states <= 1 * ALIGN_NT) hipLaunchKernelGGL(k_align<1>, grid, block, 0, s, p);
-  else if (states <= 2 * ALIGN_NT) hipLaunchKernelGGL(k_align<2>, grid, block, 0, s, p);
-  else if (states <= 4 * ALIGN_NT) hipLaunchKernelGGL(k_align<4>, grid, block, 0, s, p);
-  else if (states <= 8 * ALIGN_NT) hipLaunchKernelGGL(k_align<8>, grid, block, 0, s, p);
-  else hipLaunchKernelGGL(k_align<17>, grid, block, 0, s, p);
+  if (a.star_logp) launch_align_ns<true>(s, p, a.P, states);
+  else launch_align_ns<false>(s, static_cast<const AlignP&>(p), a.P, states);
   return QASR_OK;
 }
 

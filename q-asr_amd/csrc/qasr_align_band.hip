@@ -15,9 +15,13 @@
 // Back-walk: k_align's 64-frame LDS window with wrapped indices; thread 0 walks it and the state of every frame goes to the
 // workspace.  Then one thread per frame: frame_logp, and at the first frame of a label's run its start, count and best score.
 // Workspace per problem: ceil(T / 4) * BW bytes of backpointers, then T int32 states.
+// k_align_band<NS, STAR>: with STAR the label id C is the wildcard of STAR_RULES (qasr/align.py): wherever a state's or a label's
+// log-probability is gathered, c == C reads star[p][t] in place of logp[p][t][c], and the target check accepts c == C.  The
+// STAR = false instantiations take the kernel argument they always took (BandP) and are the code they were.
 // LDS atomics: none.  Global memory sees plain vector stores.  Every loop is bounded by T, L, the row pitch or a constant; nothing
 // is allocated and no length is read on the host.
 #include <climits>
+#include <type_traits>
 
 #include "qasr_internal.h"
 
@@ -49,6 +53,11 @@ struct BandP {
   int T, C, blank, ML, G4, NB;
 };
 
+struct BandPS : BandP {         // k_align_band<NS, true>'s argument
+  const float* star;            // [P][star_pitch]
+  long long star_pitch;
+};
+
 __device__ __forceinline__ int band_key(int bits) { return bits ^ ((bits >> 31) & 0x7fffffff); }
 
 __device__ __forceinline__ long long band_quantize(float x) {
@@ -64,8 +73,8 @@ static size_t band_problem_bytes(int T, int band_states) {
 
 size_t align_band_workspace_bytes(int P, int T, int band_states) { return (size_t)P * band_problem_bytes(T, band_states); }
 
-template <int NS>
-__global__ void __launch_bounds__(BAND_NT) k_align_band(BandP p) {
+template <int NS, bool STAR>
+__global__ void __launch_bounds__(BAND_NT) k_align_band(std::conditional_t<STAR, BandPS, BandP> p) {
   constexpr int BW = NS * BAND_NT;
   __shared__ long long rows[2][BW];
   __shared__ unsigned char win[BAND_G * BAND_WINW];
@@ -91,7 +100,7 @@ __global__ void __launch_bounds__(BAND_NT) k_align_band(BandP p) {
   if (len_ok)
     for (int i = tid; i < L; i += BAND_NT) {
       const int c = y[i];
-      if (c < 0 || c >= C || c == blank) sh_bad = 1;
+      if (c < 0 || c >= C + (STAR ? 1 : 0) || c == blank) sh_bad = 1;
     }
   __syncthreads();
   bool alignable = len_ok && !sh_bad && !(lim == 0 && L > 0);
@@ -102,6 +111,13 @@ __global__ void __launch_bounds__(BAND_NT) k_align_band(BandP p) {
   const float* const lp = p.logp + (long long)pr * p.pitch_b;
   unsigned char* const wsp = p.ws + (size_t)pr * ((size_t)p.G4 * BW + 4 * (size_t)T);
   int* const wst = reinterpret_cast<int*>(wsp + (size_t)p.G4 * BW);       // the path's state per frame (G4 * BW is a multiple of 4)
+  // lp[at], at = the place of logp[pr][t][c]; with STAR the wildcard c == C reads its plane instead (t < lim <= T <= star_pitch)
+  // and nothing at lp[.. + C]
+  auto emit = [&](long long at, int t, int c) -> float {
+    if constexpr (STAR)
+      if (c == C) return p.star[(long long)pr * p.star_pitch + t];
+    return lp[at];
+  };
 
   // ---- Viterbi inside the band
   long long vf = BAND_NEG;
@@ -119,9 +135,9 @@ __global__ void __launch_bounds__(BAND_NT) k_align_band(BandP p) {
         lab[k] = y[s >> 1];
         if (s >= 3 && y[s >> 1] != y[(s >> 1) - 1]) lab[k] |= BAND_SKIP;
       }
-      pf[k] = s < S ? lp[lab[k] & ~BAND_SKIP] : 0.f;                // frame 0
+      pf[k] = s < S ? emit(lab[k] & ~BAND_SKIP, 0, lab[k] & ~BAND_SKIP) : 0.f;           // frame 0
       rows[0][s] = (s < S && s < 2) ? band_quantize(pf[k]) : BAND_NEG;
-      pf[k] = (s < S && lim > 1) ? lp[p.pitch_t + (lab[k] & ~BAND_SKIP)] : 0.f;
+      pf[k] = (s < S && lim > 1) ? emit(p.pitch_t + (lab[k] & ~BAND_SKIP), 1, lab[k] & ~BAND_SKIP) : 0.f;
     }
     if (tid == 0 && o_base) o_base[0] = 0;
     int cur = 0, base = 0;
@@ -163,7 +179,7 @@ __global__ void __launch_bounds__(BAND_NT) k_align_band(BandP p) {
                     if (y[s >> 1] != y[(s >> 1) - 1]) lab[k] |= BAND_SKIP;      // s >= BW + 1 > 3
                   }
                   Rw[tid + k * BAND_NT] = BAND_NEG;
-                  pf[k] = lp[(long long)t * p.pitch_t + (lab[k] & ~BAND_SKIP)];   // this frame again, with the new label
+                  pf[k] = emit((long long)t * p.pitch_t + (lab[k] & ~BAND_SKIP), t, lab[k] & ~BAND_SKIP);   // this frame again, with the new label
                 }
               base = nb;
             }
@@ -175,7 +191,7 @@ __global__ void __launch_bounds__(BAND_NT) k_align_band(BandP p) {
       float nx[NS];
 #pragma unroll
       for (int k = 0; k < NS; ++k)                                  // frame t + 1's gathers, in flight across this frame
-        nx[k] = (st[k] < S && t + 1 < lim) ? lp[(long long)(t + 1) * p.pitch_t + (lab[k] & ~BAND_SKIP)] : 0.f;
+        nx[k] = (st[k] < S && t + 1 < lim) ? emit((long long)(t + 1) * p.pitch_t + (lab[k] & ~BAND_SKIP), t + 1, lab[k] & ~BAND_SKIP) : 0.f;
       const long long* const R = rows[cur];
       long long* const W = rows[cur ^ 1];
       const bool flush = (t & 3) == 3 || t == lim - 1;
@@ -278,14 +294,17 @@ __global__ void __launch_bounds__(BAND_NT) k_align_band(BandP p) {
     const int s = min(max(wst[t], 0), S - 1);
     const int i = s >> 1;                                           // (odd s: i < L)
     const int c = (s & 1) ? y[i] : blank;
-    const float* const col = lp + c;
-    if (o_flp) o_flp[t] = col[(long long)t * p.pitch_t];
+    const float* col = lp + c;
+    long long step = p.pitch_t;
+    if constexpr (STAR)
+      if (c == C) col = p.star + (long long)pr * p.star_pitch, step = 1;
+    if (o_flp) o_flp[t] = col[(long long)t * step];
     if ((s & 1) && (t == 0 || wst[t - 1] != s)) {
       int n = 0, best = INT_MIN;
       for (int f = t; f < lim && wst[f] == s; ++f) {
         ++n;
         if (o_score) {
-          const int key = band_key(__float_as_int(col[(long long)f * p.pitch_t]));
+          const int key = band_key(__float_as_int(col[(long long)f * step]));
           best = key > best ? key : best;
         }
       }
@@ -300,8 +319,18 @@ __global__ void __launch_bounds__(BAND_NT) k_align_band(BandP p) {
   }
 }
 
+template <bool STAR>
+static int launch_align_band_ns(hipStream_t s, const std::conditional_t<STAR, BandPS, BandP>& p, int B, int band_states) {
+  const dim3 grid((unsigned)B), block(BAND_NT);
+  if (band_states == 1 * BAND_NT) hipLaunchKernelGGL((k_align_band<1, STAR>), grid, block, 0, s, p);
+  else if (band_states == 4 * BAND_NT) hipLaunchKernelGGL((k_align_band<4, STAR>), grid, block, 0, s, p);
+  else if (band_states == 17 * BAND_NT) hipLaunchKernelGGL((k_align_band<17, STAR>), grid, block, 0, s, p);
+  else return QASR_ERR_ARG;
+  return QASR_OK;
+}
+
 int launch_align_band(hipStream_t s, const qasr_ctc_align_band_args& a) {
-  BandP p{};
+  BandPS p{};
   p.logp = a.log_probs, p.lens = a.lens, p.targets = a.targets, p.target_lens = a.target_lens;
   p.ws = (unsigned char*)a.workspace;
   p.start = a.start, p.nframes = a.nframes, p.score = a.score;
@@ -309,12 +338,9 @@ int launch_align_band(hipStream_t s, const qasr_ctc_align_band_args& a) {
   p.pitch_b = a.pitch_utt, p.pitch_t = a.pitch_frame;
   p.T = a.T, p.C = a.C, p.blank = a.blank, p.ML = a.max_labels;
   p.G4 = (a.T + 3) / 4, p.NB = (a.T + BAND_BLOCK - 1) / BAND_BLOCK;
-  const dim3 grid((unsigned)a.B), block(BAND_NT);
-  if (a.band_states == 1 * BAND_NT) hipLaunchKernelGGL(k_align_band<1>, grid, block, 0, s, p);
-  else if (a.band_states == 4 * BAND_NT) hipLaunchKernelGGL(k_align_band<4>, grid, block, 0, s, p);
-  else if (a.band_states == 17 * BAND_NT) hipLaunchKernelGGL(k_align_band<17>, grid, block, 0, s, p);
-  else return QASR_ERR_ARG;
-  return QASR_OK;
+  p.star = a.star_logp, p.star_pitch = a.star_pitch;
+  if (a.star_logp) return launch_align_band_ns<true>(s, p, a.B, a.band_states);
+  return launch_align_band_ns<false>(s, static_cast<const BandP&>(p), a.B, a.band_states);
 }
 
 }  // namespace qasr

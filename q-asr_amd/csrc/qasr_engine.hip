@@ -1333,10 +1333,14 @@ size_t qasr_ctc_align_workspace_bytes(int P, int T, int max_labels) {
   return align_shape_ok(P, T, max_labels) ? align_workspace_bytes(P, T, max_labels) : 0;
 }
 
-int qasr_ctc_align(void* stream, const qasr_ctc_align_args* a) {
-  if (!a) return fail(QASR_ERR_ARG, "ctc_align: args is NULL");
-  if (a->struct_size != sizeof(qasr_ctc_align_args))
-    return fail(QASR_ERR_ARG, "ctc_align: struct_size %u is not %zu", a->struct_size, sizeof(qasr_ctc_align_args));
+int qasr_ctc_align(void* stream, const qasr_ctc_align_args* given) {
+  if (!given) return fail(QASR_ERR_ARG, "ctc_align: args is NULL");
+  if (given->struct_size != sizeof(qasr_ctc_align_args) && given->struct_size != QASR_CTC_ALIGN_ARGS_V1_SIZE)
+    return fail(QASR_ERR_ARG, "ctc_align: struct_size %u is neither %zu nor %zu", given->struct_size, sizeof(qasr_ctc_align_args),
+                (size_t)QASR_CTC_ALIGN_ARGS_V1_SIZE);
+  qasr_ctc_align_args full{};                                      // the shorter struct: no wildcard plane
+  memcpy(&full, given, given->struct_size);
+  const qasr_ctc_align_args* const a = &full;
   if (!a->log_probs || !a->targets || !a->target_lens || !a->workspace || !a->ok)
     return fail(QASR_ERR_ARG, "ctc_align: log_probs, targets, target_lens, workspace and ok are required");
   if (a->B < 1 || a->T < 1 || a->T > QASR_BEAM_MAX_FRAMES || a->C < 1 || a->K < 1)
@@ -1354,6 +1358,8 @@ int qasr_ctc_align(void* stream, const qasr_ctc_align_args* a) {
     return fail(QASR_ERR_ARG, "ctc_align: lae_entries %u is not %d", a->lae_entries, QASR_BEAM_TABLE_ENTRIES);
   const size_t need = align_workspace_bytes(a->P, a->T, a->max_labels);
   if (a->workspace_bytes < need) return fail(QASR_ERR_ARG, "ctc_align: workspace of %zu bytes, %zu needed", a->workspace_bytes, need);
+  if (a->star_logp && a->star_pitch < a->T)
+    return fail(QASR_ERR_ARG, "ctc_align: star_pitch %lld < T %d", (long long)a->star_pitch, a->T);
   int rc = launch_align((hipStream_t)stream, *a);
   if (rc) return fail(rc, "ctc_align: launch");
   HIPCHK(hipGetLastError());
@@ -1369,10 +1375,14 @@ size_t qasr_ctc_align_band_workspace_bytes(int B, int T, int band_states) {
   return band_shape_ok(B, T, band_states) ? align_band_workspace_bytes(B, T, band_states) : 0;
 }
 
-int qasr_ctc_align_band(void* stream, const qasr_ctc_align_band_args* a) {
-  if (!a) return fail(QASR_ERR_ARG, "ctc_align_band: args is NULL");
-  if (a->struct_size != sizeof(qasr_ctc_align_band_args))
-    return fail(QASR_ERR_ARG, "ctc_align_band: struct_size %u is not %zu", a->struct_size, sizeof(qasr_ctc_align_band_args));
+int qasr_ctc_align_band(void* stream, const qasr_ctc_align_band_args* given) {
+  if (!given) return fail(QASR_ERR_ARG, "ctc_align_band: args is NULL");
+  if (given->struct_size != sizeof(qasr_ctc_align_band_args) && given->struct_size != QASR_CTC_ALIGN_BAND_ARGS_V1_SIZE)
+    return fail(QASR_ERR_ARG, "ctc_align_band: struct_size %u is neither %zu nor %zu", given->struct_size,
+                sizeof(qasr_ctc_align_band_args), (size_t)QASR_CTC_ALIGN_BAND_ARGS_V1_SIZE);
+  qasr_ctc_align_band_args full{};                                 // the shorter struct: no wildcard plane
+  memcpy(&full, given, given->struct_size);
+  const qasr_ctc_align_band_args* const a = &full;
   if (!a->log_probs || !a->targets || !a->target_lens || !a->workspace || !a->ok)
     return fail(QASR_ERR_ARG, "ctc_align_band: log_probs, targets, target_lens, workspace and ok are required");
   if (a->band_states != 256 && a->band_states != 1024 && a->band_states != 4352)
@@ -1389,8 +1399,29 @@ int qasr_ctc_align_band(void* stream, const qasr_ctc_align_band_args* a) {
   const size_t need = align_band_workspace_bytes(a->B, a->T, a->band_states);
   if (a->workspace_bytes < need)
     return fail(QASR_ERR_ARG, "ctc_align_band: workspace of %zu bytes, %zu needed", a->workspace_bytes, need);
+  if (a->star_logp && a->star_pitch < a->T)
+    return fail(QASR_ERR_ARG, "ctc_align_band: star_pitch %lld < T %d", (long long)a->star_pitch, a->T);
   int rc = launch_align_band((hipStream_t)stream, *a);
   if (rc) return fail(rc, "ctc_align_band: launch");
+  HIPCHK(hipGetLastError());
+  return QASR_OK;
+}
+
+// ---- the wildcard's emission plane (k_star, qasr_star.hip): the checks of include/qasr.h, then one launch
+int qasr_ctc_star(void* stream, const qasr_ctc_star_args* a) {
+  if (!a) return fail(QASR_ERR_ARG, "ctc_star: args is NULL");
+  if (a->struct_size != sizeof(qasr_ctc_star_args))
+    return fail(QASR_ERR_ARG, "ctc_star: struct_size %u is not %zu", a->struct_size, sizeof(qasr_ctc_star_args));
+  if (!a->log_probs || !a->star) return fail(QASR_ERR_ARG, "ctc_star: log_probs and star are required");
+  if (a->B < 1 || a->T < 1 || a->C < 1) return fail(QASR_ERR_ARG, "ctc_star: B %d, T %d or C %d out of range", a->B, a->T, a->C);
+  if (a->pitch_frame < a->C || a->pitch_utt < (int64_t)a->T * a->pitch_frame)
+    return fail(QASR_ERR_ARG, "ctc_star: pitch_frame %lld < C or pitch_utt %lld < T * pitch_frame", (long long)a->pitch_frame,
+                (long long)a->pitch_utt);
+  if (a->star_pitch < a->T) return fail(QASR_ERR_ARG, "ctc_star: star_pitch %lld < T %d", (long long)a->star_pitch, a->T);
+  if (!(a->penalty >= 0.f && a->penalty <= QASR_STAR_MAX_PENALTY))   // (a NaN fails both comparisons)
+    return fail(QASR_ERR_ARG, "ctc_star: penalty %g is not a finite number in 0 .. %g", (double)a->penalty, (double)QASR_STAR_MAX_PENALTY);
+  int rc = launch_star((hipStream_t)stream, *a);
+  if (rc) return fail(rc, "ctc_star: launch (B * T above 2^33)");
   HIPCHK(hipGetLastError());
   return QASR_OK;
 }

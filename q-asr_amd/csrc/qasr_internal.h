@@ -179,6 +179,8 @@ int launch_align(hipStream_t s, const qasr_ctc_align_args& a);
 // qasr_align_band.hip: banded CTC alignment of long recordings (k_align_band); the arguments are checked by qasr_ctc_align_band
 size_t align_band_workspace_bytes(int P, int T, int band_states);
 int launch_align_band(hipStream_t s, const qasr_ctc_align_band_args& a);
+// qasr_star.hip: the wildcard's emission plane (k_star); the arguments are checked by qasr_ctc_star
+int launch_star(hipStream_t s, const qasr_ctc_star_args& a);
 // qasr_resample.hip: rational polyphase resampler (k_resample); the arguments are checked by qasr_resample
 int launch_resample(hipStream_t s, const qasr_resample_args& a);
 // qasr_longform.hip: windows of long recordings cut (k_cut) and stitched (k_stitch); the arguments are checked by the callers

@@ -81,6 +81,15 @@ def main():
                         "score]; hypotheses, WER and the other outputs are unchanged.  With --window_s the texts are aligned "
                         "against the stitched windows of the whole recording (EncDecCTCModel.align_long, a banded lattice: any "
                         "length of text; ctc_score is then null)")
+    p.add_argument("--star_token", type=str, default=None, metavar='TOK',
+                   help="(extension, needs --align) a token such as '*' in the manifest's texts that marks audio the text does not "
+                        "cover: the texts are aligned as written, TOK as a wildcard label (EncDecCTCModel.align(star=)); OUT "
+                        "shows TOK as a word with its times, and ctc_score is null for a text that holds it")
+    p.add_argument("--star_penalty", type=float, default=None, metavar='X',
+                   help="(extension, needs --star_token or --star_between) nats per frame the wildcard pays below the frame's best "
+                        "class, 0 .. 16 (default 1.0: a starting point, not tuned on speech)")
+    p.add_argument("--star_between", action='store_true',
+                   help="(extension, needs --align and --window_s) a wildcard in front of and behind every recording's text")
     p.add_argument("--input_rate", type=int, default=None, metavar='HZ',
                    help="(extension) every file of the manifest is 16-bit mono PCM at this rate (a telephone corpus at 8000, say): "
                         "the batches stay int16 and are resampled to the model's rate on the device (k_resample) in front of the "
@@ -137,6 +146,14 @@ def main():
                 p.error(f'--stream_chunk_s does not go with --{flag}: a streaming session steps by chunks')
     if args.overlap_s is not None and args.window_s is None:
         p.error('--overlap_s needs --window_s')
+    if args.star_token is not None and (args.align is None or args.shuffle):
+        p.error('--star_token needs --align and does not go with --shuffle: the texts are read from the manifest in order')
+    if args.star_between and (args.align is None or args.window_s is None):
+        p.error('--star_between needs --align and --window_s')
+    if args.star_penalty is not None and args.star_token is None and not args.star_between:
+        p.error('--star_penalty needs --star_token or --star_between')
+    if args.star_penalty is not None and not 0.0 <= args.star_penalty <= 16.0:
+        p.error(f'--star_penalty must be 0 .. 16, got {args.star_penalty}')
     if args.window_s is not None and args.timestamps and args.beam_width is not None:
         p.error('--timestamps with --window_s and --beam_width is not offered: stitched beam hypotheses carry no times')
     if args.resample_quality is not None and args.input_rate is None:
@@ -317,15 +334,24 @@ def main():
                 utt_scores.append(h.utt_score)
         if args.align:                                       # the reference texts' own labels, one k_align launch per batch
             ref_ids = [row[:int(n)].tolist() for row, n in zip(batch[2].cpu(), batch[3].cpu())]
+            ref_kw = dict(labels=ref_ids)
+            if args.star_token is not None or args.star_between:     # the wildcard: k_star in front of the alignment
+                ref_kw.update(star=args.star_token, star_penalty=1.0 if args.star_penalty is None else args.star_penalty)
+            if args.star_token is not None:                          # the texts as the manifest has them: the data layer drops the token
+                raw = asr_model.test_dataloader().dataset.raw_texts[len(aligned):len(aligned) + len(ref_ids)]
+                ref_kw.update(labels=None, texts=list(raw))
             if args.window_s is not None:                    # long recordings: windows, k_stitch, one k_align_band launch
                 overlap_s = 4.0 if args.overlap_s is None else args.overlap_s
+                if args.star_between:                        # one utterance per recording: a wildcard in front of it and behind it
+                    ref_kw.update({k: [[v] for v in ref_kw[k]] for k in ('labels', 'texts') if ref_kw.get(k) is not None},
+                                  star_between=True)
                 try:
-                    got = asr_model.align_long(signal, batch[1], labels=ref_ids, window_s=args.window_s, overlap_s=overlap_s,
-                                               guard_s=min(1.0, overlap_s / 4), batch_size=args.batch_size, **rate_kw)
+                    got = asr_model.align_long(signal, batch[1], window_s=args.window_s, overlap_s=overlap_s,
+                                               guard_s=min(1.0, overlap_s / 4), batch_size=args.batch_size, **ref_kw, **rate_kw)
                 except ValueError as e:
                     p.error(f'--align with --window_s / --overlap_s: {e}')
             else:
-                got = asr_model.align(input_signal=signal, input_signal_length=batch[1], labels=ref_ids, **rate_kw)
+                got = asr_model.align(input_signal=signal, input_signal_length=batch[1], **ref_kw, **rate_kw)
             for h in got:
                 k = len(aligned)
                 aligned.append(dict(audio_filepath=items[k][0] if not args.shuffle and k < len(items) else None, text=h.text,

@@ -97,6 +97,7 @@ class AudioToCharDataset(Dataset):
         if self.input_rate is not None and self.trim:
             raise ValueError('AudioToCharDataset: trim_silence works on the resampled float signal: not available with input_rate')
         self.items = []
+        self.raw_texts = []                                  # the manifest's texts as written (an extension: align(star=) splits them)
         for path in str(manifest_filepath).split(','):
             with open(path) as f:
                 for line in f:
@@ -110,6 +111,7 @@ class AudioToCharDataset(Dataset):
                     if normalize:
                         text = normalize_text(text, self.labels)
                     self.items.append((it['audio_filepath'], text))
+                    self.raw_texts.append(it.get('text', ''))
 
     def __len__(self):
         return len(self.items)

@@ -984,9 +984,68 @@ class EncDecCTCModel(nn.Module):
                 t = timed[b * nb + h]
                 hyp.start_s, hyp.end_s, hyp.score, hyp.words = t.start_s, t.end_s, t.score, t.words
 
+    def _star_args(self, who, star, star_penalty):
+        """The wildcard's arguments (qasr.align.STAR_RULES), refused by name before anything runs: the token (None: no
+        wildcard), the wildcard's label id (len(vocabulary) + 1: one past the blank) and the penalty as float32."""
+        from qasr import align as qalign
+        vocab = list(self.decoder.vocabulary)
+        try:
+            pen = qalign.check_star_penalty(star_penalty, who)
+        except ValueError as e:
+            raise ValueError(str(e).replace('penalty', 'star_penalty', 1)) from None
+        if star is not None:
+            if not isinstance(star, str) or not star:
+                raise ValueError(f'{who}: star must be a non-empty token string, got {star!r}')
+            shared = sorted({ch for ch in star if any(ch in label for label in vocab)})
+            if shared:
+                raise ValueError(f'{who}: the star token {star!r} shares {shared!r} with the vocabulary')
+        return star, len(vocab) + 1, pen
+
+    @staticmethod
+    def _star_pieces(text, token, parser, who, where):
+        """A text split on the wildcard's token before the parser sees the pieces (its normaliser would drop the token): the
+        pieces' label ids in order, None standing for a wildcard; a piece of nothing but spaces gives no item"""
+        items = []
+        for k, part in enumerate(text.split(token)):
+            if k:
+                items.append(None)
+            if part.strip():
+                ids = parser(part)
+                if ids is None:
+                    raise ValueError(f'{who}: {where} is rejected by the parser')
+                if ids:
+                    items.append([int(c) for c in ids])
+        return items
+
+    @staticmethod
+    def _star_join(groups, space, wild):
+        """Label ids of groups of items (a list of label ids, or None for a wildcard), in order: consecutive wildcards collapse
+        to one, and when the vocabulary has a space its label stands between two neighbouring items, so a wildcard never
+        touches a word.  Also, per group, (first, count) from its first to its last label that is no wildcard (None for a group
+        without one)."""
+        ids, spans, prev_wild = [], [], False
+        for g in groups:
+            first = last = None
+            for it in g:
+                if it is None and prev_wild:
+                    continue
+                if ids and space is not None:
+                    ids.append(space)
+                if it is None:
+                    ids.append(wild)
+                else:
+                    real = [k for k, c in enumerate(it) if c != wild]
+                    if real:
+                        first = len(ids) + real[0] if first is None else first
+                        last = len(ids) + real[-1] + 1
+                    ids += it
+                prev_wild = it is None or it[-1] == wild
+            spans.append(None if first is None else (first, last - first))
+        return ids, spans
+
     @torch.no_grad()
     def align(self, input_signal=None, input_signal_length=None, processed_signal=None, processed_signal_length=None,
-              texts=None, labels=None, sample_rate=None, channels=1):
+              texts=None, labels=None, sample_rate=None, channels=1, star=None, star_penalty=1.0):
         """Forced alignment and CTC scoring of GIVEN transcripts (an extension of the reference's API): one
         qasr.ctc.Hypothesis per utterance with the text's labels, every label's start / end time and confidence and the word
         groups of its best (Viterbi) alignment against this batch's log-probabilities, utt_score = the log-probability of that
@@ -996,8 +1055,20 @@ class EncDecCTCModel(nn.Module):
         parser rejects, an id outside the vocabulary or a transcript above qasr.align.MAX_LABELS labels raises ValueError naming
         its index before anything runs.  Runs behind every path decode(beam_width=) runs behind - static engine, reserved
         engine, dynamic path (k_align on the same stream), host modules (the NumPy twin).  A transcript with more labels (plus
-        adjacent repeats) than the utterance has frames is not alignable: empty time lists, scores -inf."""
+        adjacent repeats) than the utterance has frames is not alignable: empty time lists, scores -inf.
+
+        star: a token string such as '*' that marks audio the transcript does not cover (qasr.align.STAR_RULES).  A text is
+        split on the token before the parser sees the pieces; the pieces' labels are joined by the wildcard label, a space
+        label on either side of it when the vocabulary has one, and consecutive tokens count once; in `labels` the id
+        len(vocabulary) + 1 is the wildcard.  The wildcard's log-probability at a frame is the frame's best class less
+        star_penalty nats (k_star in front of k_align on the same stream; 0 .. 16, default 1.0 - a starting point, not tuned
+        on speech).  The hypothesis shows the token in text, carries its times and, as its score, the best value of that plane
+        inside its run, lists it in words as a word of its own - where the untranscribed audio lies - and counts its emissions
+        in utt_score; ctc_score is None for a transcript that holds a wildcard.  An empty token, a token that shares a
+        character with the vocabulary, a star_penalty outside 0 .. 16 and the wildcard's id in labels without `star` are
+        refused by name; MAX_LABELS counts wildcards."""
         from qasr import align as qalign
+        star, wild, star_pen = self._star_args('align', star, star_penalty)
         input_signal, input_signal_length = self._resample_in(input_signal, input_signal_length, sample_rate, channels)
         if (texts is None) == (labels is None):
             raise ValueError('align: give exactly one of texts and labels')
@@ -1006,8 +1077,12 @@ class EncDecCTCModel(nn.Module):
         if texts is not None:
             from nemo.collections.asr.parts import parsers
             parser = parsers.make_parser(labels=vocab, name='en', unk_id=-1, blank_id=-1, do_normalize=True)
+            space = vocab.index(' ') if ' ' in vocab else None
             rows = []
             for i, text in enumerate(texts):
+                if star is not None and isinstance(text, str):
+                    rows.append(self._star_join([self._star_pieces(text, star, parser, 'align', f'text {i}')], space, wild)[0])
+                    continue
                 ids = parser(text) if isinstance(text, str) else None
                 if ids is None:
                     raise ValueError(f'align: text {i} is rejected by the parser')
@@ -1015,7 +1090,9 @@ class EncDecCTCModel(nn.Module):
         else:
             rows = [[int(c) for c in r] for r in labels]
         for i, ids in enumerate(rows):
-            if any(not 0 <= c < blank for c in ids):
+            if star is None and wild in ids:
+                raise ValueError(f'align: transcript {i} holds the wildcard label {wild}, but no star token was given')
+            if any(not 0 <= c < blank and c != wild for c in ids):
                 raise ValueError(f'align: transcript {i} holds a label outside the vocabulary of {blank} labels')
             if len(ids) > qalign.MAX_LABELS:
                 raise ValueError(f'align: transcript {i} has {len(ids)} labels, at most {qalign.MAX_LABELS} can be aligned')
@@ -1028,22 +1105,28 @@ class EncDecCTCModel(nn.Module):
         for i, ids in enumerate(rows):
             tg[i, :len(ids)] = ids
         tl = np.array([len(r) for r in rows], dtype=np.int32)
+        use_star = star is not None and any(wild in ids for ids in rows)      # no wildcard in any transcript: the call it was
         if log_probs.is_cuda:
             from qasr import engine as qengine
+            plane = qengine.ctc_star(log_probs.float(), enc_len, star_pen) if use_star else None
             res = qengine.ctc_align(log_probs.float(), enc_len, torch.from_numpy(tg).to(log_probs.device),
-                                    torch.from_numpy(tl).to(log_probs.device), blank)
+                                    torch.from_numpy(tl).to(log_probs.device), blank, star=plane)
         else:
-            res = qalign.align_host(log_probs.float().numpy(), enc_len.numpy(), tg, tl, blank)
-        return qalign.to_hypotheses(res, vocab, self.seconds_per_frame())
+            plane = qalign.star_host(log_probs.float().numpy(), enc_len.numpy(), star_pen) if use_star else None
+            res = qalign.align_host(log_probs.float().numpy(), enc_len.numpy(), tg, tl, blank, star=plane)
+        return qalign.to_hypotheses(res, vocab, self.seconds_per_frame(), star_token=star)
 
-    def _long_transcripts(self, texts, labels, n_recordings):
+    def _long_transcripts(self, texts, labels, n_recordings, star=None, wild=None, star_between=False):
         """align_long's transcripts: per recording its label ids and, where an utterance list was given, the utterances as
-        (text, first label, labels); utterances are joined by the space label when the vocabulary has one"""
+        (text, first label, labels); utterances are joined by the space label when the vocabulary has one.  star / wild: the
+        wildcard's token and label id (_star_args); star_between: a wildcard around and between the utterances of a list"""
         if (texts is None) == (labels is None):
             raise ValueError('align_long: give exactly one of texts and labels')
         vocab = list(self.decoder.vocabulary)
         blank = len(vocab)
         space = vocab.index(' ') if ' ' in vocab else None
+        if star is not None:
+            return self._long_transcripts_star(texts, labels, n_recordings, star, wild, star_between, vocab, space)
         given = texts if texts is not None else labels
         if len(given) != n_recordings:
             raise ValueError(f'align_long: {len(given)} transcripts for {n_recordings} recordings')
@@ -1059,6 +1142,8 @@ class EncDecCTCModel(nn.Module):
         else:
             def ids_of(x, where):
                 ids = [int(c) for c in x]
+                if wild is not None and wild in ids:
+                    raise ValueError(f'align_long: {where} holds the wildcard label {wild}, but no star token was given')
                 if any(not 0 <= c < blank for c in ids):
                     raise ValueError(f'align_long: {where} holds a label outside the vocabulary of {blank} labels')
                 return ids, ''.join(vocab[c] for c in ids)
@@ -1089,9 +1174,59 @@ class EncDecCTCModel(nn.Module):
                 raise ValueError(f'align_long: transcript {r} has {len(ids)} labels, at most {qalign.BAND_MAX_LABELS} can be aligned')
         return rows, utts
 
+    def _long_transcripts_star(self, texts, labels, n_recordings, star, wild, star_between, vocab, space):
+        """_long_transcripts with a wildcard token: the same rows and utterance spans, built from items (_star_pieces,
+        _star_join); an utterance's span runs from its first to its last label that is no wildcard"""
+        from qasr import align as qalign
+        blank = len(vocab)
+        given = texts if texts is not None else labels
+        if len(given) != n_recordings:
+            raise ValueError(f'align_long: {len(given)} transcripts for {n_recordings} recordings')
+        if texts is not None:
+            from nemo.collections.asr.parts import parsers
+            parser = parsers.make_parser(labels=vocab, name='en', unk_id=-1, blank_id=-1, do_normalize=True)
+
+            def items_of(x, where):
+                if not isinstance(x, str):
+                    raise ValueError(f'align_long: {where} is rejected by the parser')
+                return self._star_pieces(x, star, parser, 'align_long', where), x
+        else:
+            def items_of(x, where):
+                ids = [int(c) for c in x]
+                if any(not 0 <= c < blank and c != wild for c in ids):
+                    raise ValueError(f'align_long: {where} holds a label outside the vocabulary of {blank} labels')
+                return ([ids] if ids else []), ''.join(star if c == wild else vocab[c] for c in ids)
+        rows, utts = [], []
+        for r, item in enumerate(given):
+            is_list = (not isinstance(item, str)) if texts is not None else (len(item) > 0 and np.ndim(item[0]) > 0)
+            if not is_list:
+                ids, _ = self._star_join([items_of(item, f'transcript {r}')[0]], space, wild)
+                rows.append(ids)
+                utts.append(None)
+                continue
+            groups, shown = [[None]] if star_between else [], []
+            for j, u in enumerate(item):
+                its, text = items_of(u, f'utterance {j} of transcript {r}')
+                groups.append(its)
+                shown.append(text)
+                if star_between:
+                    groups.append([None])
+            ids, spans = self._star_join(groups, space, wild)
+            spans = spans[1::2] if star_between else spans
+            for j, sp in enumerate(spans):
+                if sp is None:
+                    raise ValueError(f'align_long: utterance {j} of transcript {r} is empty')
+            rows.append(ids)
+            utts.append([(text, a, k) for text, (a, k) in zip(shown, spans)])
+        for r, ids in enumerate(rows):
+            if len(ids) > qalign.BAND_MAX_LABELS:
+                raise ValueError(f'align_long: transcript {r} has {len(ids)} labels, at most {qalign.BAND_MAX_LABELS} can be aligned')
+        return rows, utts
+
     @torch.no_grad()
     def align_long(self, input_signal, input_signal_length, texts=None, labels=None, window_s=30.0, overlap_s=4.0, guard_s=1.0,
-                   batch_size=32, seam='blank', band_states=None, sample_rate=None, channels=1):
+                   batch_size=32, seam='blank', band_states=None, sample_rate=None, channels=1, star=None, star_penalty=1.0,
+                   star_between=False):
         """CTC segmentation of long recordings (an extension; the job of the reference's tools/ctc_segmentation, on the
         device): input_signal [R, S] with input_signal_length samples each and, per recording, its whole transcript ->
         List[qasr.ctc.Hypothesis], one per recording, with every label's and word's times in seconds of the recording,
@@ -1108,7 +1243,14 @@ class EncDecCTCModel(nn.Module):
         or 4352; None: the smallest that holds the longest transcript whole, else 4352) that follows the alignment
         (qasr.align.BAND_RULES).  A transcript whose path the band loses - or that has more labels than the recording has
         frames - keeps its text; its times are empty and its scores -inf.  CPU inputs run the NumPy twins.  The stitched
-        log-probabilities take 4 * classes bytes per frame of every recording, and the windows as much again."""
+        log-probabilities take 4 * classes bytes per frame of every recording, and the windows as much again.
+
+        star, star_penalty: the wildcard of align() - the token inside a text or an utterance, the id len(vocabulary) + 1 in
+        labels - with k_star in front of k_align_band.  star_between=True puts a wildcard before the first utterance of an
+        utterance list, between every two and behind the last (space labels around each when the vocabulary has a space; the
+        token is star, '*' when star is None), for recordings whose transcript skips what lies between the utterances.
+        `segments` stay one per utterance, from its first to its last label that is no wildcard: the frames of the wildcards
+        in between belong to no segment.  The hypothesis shows the tokens in text and in words."""
         from qasr import align as qalign, engine as qengine
         if input_signal is None or input_signal_length is None:
             raise ValueError('align_long: input_signal and input_signal_length are required')
@@ -1122,10 +1264,11 @@ class EncDecCTCModel(nn.Module):
                 band_states = qalign.pick_band_states(0, band_states)
             except ValueError as e:
                 raise ValueError(f'align_long: {e}') from None
+        star, wild, star_pen = self._star_args('align_long', '*' if star is None and star_between else star, star_penalty)
         signal, length = self._resample_in(input_signal, input_signal_length, sample_rate, channels)
         if signal.dim() != 2:
             raise ValueError(f'align_long: input_signal must be [R, S], got {tuple(signal.shape)}')
-        rows, utts = self._long_transcripts(texts, labels, signal.shape[0])
+        rows, utts = self._long_transcripts(texts, labels, signal.shape[0], star, wild, star_between)
         signal = signal.float()
         lens_host = length.detach().cpu().long().clamp(max=signal.shape[1])
         plan = self._long_plan(lens_host.numpy(), window_s, overlap_s, guard_s)      # refuses its arguments by name
@@ -1143,13 +1286,16 @@ class EncDecCTCModel(nn.Module):
             tg[i, :len(ids)] = ids
         tl = np.array([len(r) for r in rows], dtype=np.int32)
         bw = qalign.pick_band_states(tg.shape[1], band_states)
+        use_star = star is not None and any(wild in ids for ids in rows)      # no wildcard in any transcript: the call it was
         if logp.is_cuda:
+            plane = qengine.ctc_star(logp, total, star_pen) if use_star else None
             res = qengine.ctc_align_band(logp, total, torch.from_numpy(tg).to(logp.device), torch.from_numpy(tl).to(logp.device),
-                                         blank, band_states=bw, want_band_base=False)
+                                         blank, band_states=bw, want_band_base=False, star=plane)
         else:
-            res = qalign.align_band_host(logp.numpy(), total.numpy(), tg, tl, blank, band_states=bw, want_band_base=False)
+            plane = qalign.star_host(logp.numpy(), total.numpy(), star_pen) if use_star else None
+            res = qalign.align_band_host(logp.numpy(), total.numpy(), tg, tl, blank, band_states=bw, want_band_base=False, star=plane)
         spf_s = self.seconds_per_frame()
-        hyps = qalign.to_hypotheses(res, vocab, spf_s)
+        hyps = qalign.to_hypotheses(res, vocab, spf_s, star_token=star)
         seams_h = seams.cpu().numpy()
         if any(u is not None for u in utts):
             ok, start, nframes = (qalign._np(x) for x in (res.ok, res.start, res.nframes))

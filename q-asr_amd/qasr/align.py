@@ -23,7 +23,10 @@ or equal to blank.  lim == 0 with L == 0 is ok = 1 with both scores 0.
 
 Long recordings (a whole transcript against a whole recording, past MAX_LABELS and MAX_T) are aligned inside a band of lattice
 states that follows the path: BAND_RULES, `align_band_host` (the host statement of k_align_band, csrc/qasr_align_band.hip) and
-`segment_scores` at the end of this module; they are the CPU path of EncDecCTCModel.align_long."""
+`segment_scores` at the end of this module; they are the CPU path of EncDecCTCModel.align_long.
+
+Audio the transcript does not cover is given a wildcard label whose emission is a per-frame plane: STAR_RULES, `star_host` (the
+host statement of k_star, csrc/qasr_star.hip) and the `star=` argument of both twins."""
 from dataclasses import dataclass
 from typing import List, Sequence
 
@@ -32,6 +35,19 @@ import numpy as np
 from .beam import MAX_T, NEG, ONE, _order_key, lae, lae_table, quantize
 
 MAX_LABELS = 2048                       # QASR_ALIGN_MAX_LABELS
+STAR_MAX_PENALTY = 16.0                 # nats per frame; qasr_ctc_star refuses more
+
+STAR_RULES = """The wildcard ("star") is one more label, id C (one past the last class), whose emission does not come from the matrix but
+from a float32 plane star [B, T]: wherever RULES or BAND_RULES read logp[u][t][c], c == C reads star[u][t] - the quantised
+emission q, the per-label score and frame_logp alike.  Nothing else changes: the wildcard differs from every real label, so it
+may skip the blank below it; two adjacent wildcards are a repeat and need the blank between them; a wildcard takes at least
+one frame.  Without a plane, id C is a label outside [0, C) and the problem is not alignable (ok = 0).
+Hence, for any inputs, every output (start, nframes, score, path_score, total, ok, frame_logp, band_base) equals on every byte
+the output of the same function, called without a plane, on np.concatenate([log_probs, star[..., None]], axis=2) with C + 1
+classes.  total with a wildcard in the target follows the same rule; it is a score, not a likelihood.
+The plane of star_host: star[u][t] = max over c < C of logp[u][t][c] (the float32 maximum in the `_order_key` order, k_ctc's
+and k_align's) minus float32(penalty), one IEEE float32 subtraction, for t < lim; 0 for t >= lim.  penalty is finite, in
+0 .. STAR_MAX_PENALTY nats.  A row of all -inf gives -inf, which quantize takes to its floor."""
 
 
 @dataclass
@@ -52,7 +68,51 @@ class AlignResult:
     problems_per_utt: int = 1
 
 
-def _label_runs(states, lp, y):
+def star_host(log_probs, lens, penalty) -> np.ndarray:
+    """The wildcard's emission plane of STAR_RULES: log_probs float32 [B, T, C]; lens int [B] or None; penalty: nats per frame,
+    finite, 0 .. STAR_MAX_PENALTY.  Returns float32 [B, T]."""
+    lp = np.asarray(log_probs, dtype=np.float32)
+    if lp.ndim != 3 or min(lp.shape) < 1:
+        raise ValueError(f'star_host: log_probs must be [B, T, C] with B, T, C >= 1, got {lp.shape}')
+    pen = check_star_penalty(penalty, 'star_host')
+    B, T, _ = lp.shape
+    best = _order_key(lp).max(axis=2)
+    out = (best ^ ((best >> 31) & np.int32(0x7fffffff))).view(np.float32) - pen      # float32 - float32: one subtraction
+    if lens is not None:
+        lim = np.clip(np.asarray(lens, dtype=np.int64).reshape(B), 0, T)
+        out[np.arange(T)[None, :] >= lim[:, None]] = 0
+    return out
+
+
+def check_star_penalty(penalty, who) -> np.float32:
+    """penalty as float32; refused by name unless finite and in 0 .. STAR_MAX_PENALTY"""
+    try:
+        pen = float(penalty)
+    except (TypeError, ValueError):
+        pen = float('nan')
+    if not 0.0 <= pen <= STAR_MAX_PENALTY:                          # (NaN and the infinities fail the comparison too)
+        raise ValueError(f'{who}: penalty must be a finite number of nats in 0 .. {STAR_MAX_PENALTY:g}, got {penalty!r}')
+    return np.float32(pen)
+
+
+def _star_plane(star, B, T, who):
+    if star is None:
+        return None
+    st = np.asarray(star, dtype=np.float32)
+    if st.shape != (B, T):
+        raise ValueError(f'{who}: star must be a float32 plane [{B}, {T}], got {st.shape}')
+    return st
+
+
+def _emit(lp, st, t, c):
+    """lp[t, c] (index arrays that broadcast), the wildcard id lp.shape[1] reading the plane row st[t] (STAR_RULES)"""
+    if st is None:
+        return lp[t, c]
+    wild = c == lp.shape[1]
+    return np.where(wild, st[t], lp[t, np.where(wild, 0, c)])
+
+
+def _label_runs(states, lp, y, st=None):
     """per label of y its first frame, frame count and best frame log-probability along the path `states` [lim]"""
     L = len(y)
     start = np.zeros(L, dtype=np.int32)
@@ -64,13 +124,14 @@ def _label_runs(states, lp, y):
         first_of = np.flatnonzero(np.concatenate([[True], idx[1:] != idx[:-1]]))
         start[idx[first_of]] = fr[first_of]
         nframes[idx[first_of]] = np.diff(np.concatenate([first_of, [len(fr)]]))
-        best = np.maximum.reduceat(_order_key(lp[fr, np.asarray(y, dtype=np.int64)[idx]]), first_of)
+        best = np.maximum.reduceat(_order_key(_emit(lp, st, fr, np.asarray(y, dtype=np.int64)[idx])), first_of)
         score[idx[first_of]] = (best ^ ((best >> 31) & np.int32(0x7fffffff))).view(np.float32)
     return start, nframes, score
 
 
-def _align_one(lp, lim, y, blank, tab, want_total):
-    """one problem with a valid target y (L >= 0) over lp float32 [T, C]; returns (ok, start, nframes, score, path, total)"""
+def _align_one(lp, lim, y, blank, tab, want_total, st=None):
+    """one problem with a valid target y (L >= 0) over lp float32 [T, C] (st: the wildcard's plane row [T] or None); returns
+    (ok, start, nframes, score, path, total)"""
     L = len(y)
     i64 = np.int64
     if lim == 0:
@@ -81,7 +142,7 @@ def _align_one(lp, lim, y, blank, tab, want_total):
     skip = np.zeros(S, dtype=bool)
     if L > 1:
         skip[3::2] = y[1:] != y[:-1]
-    q = quantize(lp[:lim][:, lab])                                  # int32 [lim, S]
+    q = quantize(_emit(lp, st, np.arange(lim)[:, None], lab[None, :]))             # int32 [lim, S]
     negs = np.full(2, NEG, i64)
 
     def first():
@@ -120,14 +181,15 @@ def _align_one(lp, lim, y, blank, tab, want_total):
     for t in range(lim - 1, -1, -1):
         states[t] = s
         s -= int(bp[t, s])
-    start, nframes, score = _label_runs(states, lp, y)
+    start, nframes, score = _label_runs(states, lp, y, st)
     return 1, start, nframes, score, path_score, total
 
 
-def align_host(log_probs, lens, targets, target_lens, blank, problems_per_utt=1, want_total=True) -> AlignResult:
+def align_host(log_probs, lens, targets, target_lens, blank, problems_per_utt=1, want_total=True, star=None) -> AlignResult:
     """log_probs float32 [B, T, C]; lens int [B] or None; targets int32 [P, max_labels] and target_lens int32 [P] with
     P = B * problems_per_utt (problem p belongs to utterance p // problems_per_utt); blank: the blank id.  The RULES of the
-    module docstring; want_total=False skips the forward pass (total None)."""
+    module docstring; want_total=False skips the forward pass (total None).  star: a float32 plane [B, T] that makes id C the
+    wildcard label (STAR_RULES); None: id C is a label outside [0, C)."""
     lp = np.asarray(log_probs, dtype=np.float32)
     if lp.ndim != 3 or min(lp.shape) < 1:
         raise ValueError(f'align_host: log_probs must be [B, T, C] with B, T, C >= 1, got {lp.shape}')
@@ -147,6 +209,8 @@ def align_host(log_probs, lens, targets, target_lens, blank, problems_per_utt=1,
     if not 0 <= blank < C:
         raise ValueError(f'align_host: blank {blank} is outside [0, {C})')
     tg = tg.astype(np.int32)
+    star = _star_plane(star, B, T, 'align_host')
+    n_ids = C + (star is not None)
     tab = lae_table()
     start = np.zeros((P, ML), dtype=np.int32)
     nframes = np.zeros((P, ML), dtype=np.int32)
@@ -161,9 +225,9 @@ def align_host(log_probs, lens, targets, target_lens, blank, problems_per_utt=1,
         if L < 0 or L > ML:
             continue
         y = tg[p, :L]
-        if L and (y.min() < 0 or y.max() >= C or (y == blank).any()):
+        if L and (y.min() < 0 or y.max() >= n_ids or (y == blank).any()):
             continue
-        ok[p], st, nf, sc, ps, tot = _align_one(lp[u], lim, y, blank, tab, want_total)
+        ok[p], st, nf, sc, ps, tot = _align_one(lp[u], lim, y, blank, tab, want_total, None if star is None else star[u])
         if ok[p]:
             path_score[p], total[p] = ps, tot
             if st is not None:
@@ -179,11 +243,35 @@ def _np(x):
     return np.asarray(x)
 
 
-def to_hypotheses(result: AlignResult, vocabulary: Sequence[str], seconds_per_frame: float) -> List:
+def _words_with_star(h, vocab, wild):
+    """the word groups of qasr.ctc.to_hypotheses with the wildcard a word of its own, whether or not the vocabulary has ' '"""
+    chars = [vocab[c] for c in h.labels]
+    words, group = [], []
+
+    def close():
+        if group:
+            words.append((''.join(chars[k] for k in group), h.start_s[group[0]], h.end_s[group[-1]], min(h.score[k] for k in group)))
+            group.clear()
+    for k, c in enumerate(h.labels):
+        if c == wild:
+            close()
+            group.append(k)
+            close()
+        elif chars[k] == ' ':
+            close()
+        else:
+            group.append(k)
+    close()
+    return words
+
+
+def to_hypotheses(result: AlignResult, vocabulary: Sequence[str], seconds_per_frame: float, star_token=None) -> List:
     """One qasr.ctc.Hypothesis per problem, through qasr.ctc.to_hypotheses (the code greedy decoding uses, so label and word
     times mean the same): text and labels are the target's, start_s / end_s / score / words come from the best alignment,
     utt_score = path_score / 2^16 and ctc_score = total / 2^16 (None when total was not requested).  A problem that is not
-    alignable (ok == 0) has empty time lists, score None and utt_score = ctc_score = -inf."""
+    alignable (ok == 0) has empty time lists, score None and utt_score = ctc_score = -inf.
+    star_token: the string of the wildcard label len(vocabulary) + 1 (STAR_RULES); it stands in text at its positions and is a
+    word of its own, and a transcript that holds it has ctc_score None."""
     from . import ctc as qctc
     labels, n_labels, ok = _np(result.labels), _np(result.n_labels), _np(result.ok)
     path, total = _np(result.path_score), _np(result.total)
@@ -191,11 +279,17 @@ def to_hypotheses(result: AlignResult, vocabulary: Sequence[str], seconds_per_fr
     view = qctc.CtcResult(labels, np.where(ok != 0, n, 0).astype(np.int32), _np(result.start), _np(result.nframes),
                           _np(result.score), None, result.blank)
     vocab = list(vocabulary)
+    wild = len(vocab) + 1 if star_token is not None else None        # (blank = len(vocab) sits between: it never occurs in a target)
+    if wild is not None:
+        vocab += ['', star_token]
     hyps = qctc.to_hypotheses(view, vocab, seconds_per_frame)
     for p, h in enumerate(hyps):
         if ok[p]:
             h.utt_score = float(path[p]) / ONE
             h.ctc_score = None if total is None else float(total[p]) / ONE
+            if wild is not None and wild in h.labels:
+                h.ctc_score = None                                      # total is a score there, not a likelihood (STAR_RULES)
+                h.words = _words_with_star(h, vocab, wild)
         else:
             ids = [int(i) for i in labels[p, :n[p]]]
             text = ''.join(vocab[i] if 0 <= i < len(vocab) else '' for i in ids)
@@ -248,8 +342,9 @@ def pick_band_states(n_labels, band_states=None) -> int:
     return int(band_states)
 
 
-def _align_band_one(lp, lim, y, blank, BW):
-    """one problem with a valid target y over lp float32 [T, C]: (ok, start, nframes, score, path, frame_logp [lim], bases)"""
+def _align_band_one(lp, lim, y, blank, BW, st=None):
+    """one problem with a valid target y over lp float32 [T, C] (st: the wildcard's plane row [T] or None): (ok, start, nframes,
+    score, path, frame_logp [lim], bases)"""
     L = len(y)
     i64 = np.int64
     nb_blocks = (lim + BAND_BLOCK - 1) // BAND_BLOCK
@@ -267,7 +362,7 @@ def _align_band_one(lp, lim, y, blank, BW):
     negs = np.full(2, NEG, i64)
     base = 0
     V = np.full(n, NEG, i64)                                        # V[i]: state base + i
-    V[:min(2, S)] = quantize(lp[0, lab[:min(2, S)]])
+    V[:min(2, S)] = quantize(_emit(lp, st, 0, lab[:min(2, S)]))
     bp = np.zeros((lim, n), dtype=np.uint8)                         # bp[t, i]: state bases[t // 32] + i
     for t in range(1, lim):
         if t % BAND_BLOCK == 0:
@@ -279,7 +374,7 @@ def _align_band_one(lp, lim, y, blank, BW):
                     base = new
             bases[t // BAND_BLOCK] = base
         sl = slice(base, base + n)
-        q = quantize(lp[t, lab[sl]]).astype(i64)
+        q = quantize(_emit(lp, st, t, lab[sl])).astype(i64)
         ext = np.concatenate([negs, V])                             # what lies below base is NEG
         a1, a2 = ext[1:n + 1], np.where(skip[sl], ext[:n], NEG)
         best, step = V, np.zeros(n, dtype=np.uint8)
@@ -302,13 +397,14 @@ def _align_band_one(lp, lim, y, blank, BW):
     for t in range(lim - 1, -1, -1):
         states[t] = s
         s -= int(bp[t, s - int(bases[t // BAND_BLOCK])])
-    start, nframes, score = _label_runs(states, lp, y)
-    return 1, start, nframes, score, path_score, lp[np.arange(lim), lab[states]], bases
+    start, nframes, score = _label_runs(states, lp, y, st)
+    return 1, start, nframes, score, path_score, _emit(lp, st, np.arange(lim), lab[states]), bases
 
 
-def align_band_host(log_probs, lens, targets, target_lens, blank, band_states=None, want_band_base=True) -> BandResult:
+def align_band_host(log_probs, lens, targets, target_lens, blank, band_states=None, want_band_base=True, star=None) -> BandResult:
     """BAND_RULES on the host.  log_probs float32 [P, T, C]; lens int [P] or None; targets int32 [P, max_labels] and
-    target_lens int32 [P]; blank: the blank id; band_states: one of BAND_STATES (None: pick_band_states of the row pitch)."""
+    target_lens int32 [P]; blank: the blank id; band_states: one of BAND_STATES (None: pick_band_states of the row pitch);
+    star: a float32 plane [P, T] that makes id C the wildcard label (STAR_RULES)."""
     lp = np.asarray(log_probs, dtype=np.float32)
     if lp.ndim != 3 or min(lp.shape) < 1:
         raise ValueError(f'align_band_host: log_probs must be [P, T, C] with P, T, C >= 1, got {lp.shape}')
@@ -328,6 +424,8 @@ def align_band_host(log_probs, lens, targets, target_lens, blank, band_states=No
         raise ValueError(f'align_band_host: blank {blank} is outside [0, {C})')
     BW = pick_band_states(ML, band_states)
     tg = tg.astype(np.int32)
+    star = _star_plane(star, P, T, 'align_band_host')
+    n_ids = C + (star is not None)
     start = np.zeros((P, ML), dtype=np.int32)
     nframes = np.zeros((P, ML), dtype=np.int32)
     score = np.zeros((P, ML), dtype=np.float32)
@@ -341,9 +439,9 @@ def align_band_host(log_probs, lens, targets, target_lens, blank, band_states=No
         if L < 0 or L > ML:
             continue
         y = tg[p, :L]
-        if L and (y.min() < 0 or y.max() >= C or (y == blank).any()):
+        if L and (y.min() < 0 or y.max() >= n_ids or (y == blank).any()):
             continue
-        ok[p], st, nf, sc, ps, fl, bases = _align_band_one(lp[p], lim, y, blank, BW)
+        ok[p], st, nf, sc, ps, fl, bases = _align_band_one(lp[p], lim, y, blank, BW, None if star is None else star[p])
         band_base[p, :len(bases)] = bases
         if ok[p]:
             path_score[p] = ps

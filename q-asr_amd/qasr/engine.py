@@ -19,7 +19,7 @@ SYMBOLS = ['qasr_blob_check', 'qasr_engine_create', 'qasr_engine_create_ex', 'qa
            'qasr_dyn_quant_in', 'qasr_dyn_conv_params', 'qasr_sep_layer', 'qasr_quantile2', 'qasr_quantile_workspace_bytes', 'qasr_debug_prof',
            'qasr_debug_timeline', 'qasr_ctc_collapse', 'qasr_engine_attach_ctc', 'qasr_ctc_topn', 'qasr_ctc_beam_workspace_bytes', 'qasr_ctc_beam',
            'qasr_lm_check', 'qasr_ctc_beam_lm', 'qasr_boost_check', 'qasr_ctc_beam_boost', 'qasr_ctc_align_workspace_bytes', 'qasr_ctc_align',
-           'qasr_ctc_align_band_workspace_bytes', 'qasr_ctc_align_band',
+           'qasr_ctc_align_band_workspace_bytes', 'qasr_ctc_align_band', 'qasr_ctc_star',
            'qasr_engine_reserve', 'qasr_engine_forward_ragged', 'qasr_engine_forward_ragged_audio', 'qasr_engine_ragged_stats',
            'qasr_ragged_bucket_frames', 'qasr_ragged_envelope_frames',
            'qasr_resample_check', 'qasr_resample', 'qasr_resample_out_samples', 'qasr_longform_cut', 'qasr_longform_stitch',
@@ -176,6 +176,8 @@ def load_library():
         lib.qasr_ctc_align_band.argtypes = [vp, C.POINTER(AlignBandArgs)]
         lib.qasr_ctc_align_band_workspace_bytes.argtypes = [i32, i32, i32]
         lib.qasr_ctc_align_band_workspace_bytes.restype = sz
+    if hasattr(lib, 'qasr_ctc_star'):           # (likewise)
+        lib.qasr_ctc_star.argtypes = [vp, C.POINTER(StarArgs)]
     if hasattr(lib, 'qasr_engine_reserve'):     # (likewise)
         lib.qasr_engine_reserve.argtypes = [vp, C.POINTER(ReserveOpts)]
         lib.qasr_engine_forward_ragged.argtypes = [vp, vp, vp, vp, i32, i32, C.POINTER(RaggedOut)]
@@ -590,7 +592,52 @@ class AlignArgs(C.Structure):
                 [(n, C.c_void_p) for n in ('log_probs', 'lens', 'targets', 'target_lens')] +
                 [('lae_entries', C.c_uint32), ('reserved', C.c_uint32), ('lae_table', C.c_void_p), ('workspace', C.c_void_p),
                  ('workspace_bytes', C.c_size_t)] +
-                [(n, C.c_void_p) for n in ('start', 'nframes', 'score', 'path_score', 'total', 'ok')])
+                [(n, C.c_void_p) for n in ('start', 'nframes', 'score', 'path_score', 'total', 'ok')] +
+                [('star_logp', C.c_void_p), ('star_pitch', C.c_int64)])
+
+
+class StarArgs(C.Structure):
+    """qasr_ctc_star_args (include/qasr.h)"""
+    _fields_ = ([('struct_size', C.c_uint32)] + [(n, C.c_int32) for n in ('B', 'T', 'C')] +
+                [('pitch_utt', C.c_int64), ('pitch_frame', C.c_int64), ('log_probs', C.c_void_p), ('lens', C.c_void_p),
+                 ('penalty', C.c_float), ('reserved', C.c_uint32), ('star', C.c_void_p), ('star_pitch', C.c_int64)])
+
+
+def ctc_star(log_probs, lens, penalty, out=None, stream=None):
+    """qasr_ctc_star: the wildcard's emission plane on the device (k_star, one launch on the current stream, no host
+    synchronisation); equal to qasr.align.star_host byte for byte.  log_probs: a cuda float32 tensor [B, T, C] (any utterance
+    / frame pitch, classes contiguous); lens int32 [B] optional; penalty: nats per frame, finite, 0 .. 16 (refused by name
+    otherwise).  Returns a cuda float32 tensor [B, T]; `out`: a caller-owned one (rows of any pitch >= T)."""
+    from .align import check_star_penalty
+    lib = load_library()
+    assert log_probs.is_cuda and log_probs.dim() == 3 and log_probs.dtype == torch.float32, \
+        'ctc_star: log_probs must be a cuda float32 tensor [B, T, C]'
+    pen = check_star_penalty(penalty, 'ctc_star')
+    dev = log_probs.device
+    lp = log_probs if log_probs.stride(2) == 1 or log_probs.shape[2] == 1 else log_probs.contiguous()
+    ln = None if lens is None else lens.to(device=dev, dtype=torch.int32).contiguous()
+    B, T, Cn = lp.shape
+    if out is None:
+        out = torch.empty(B, T, device=dev, dtype=torch.float32)
+    assert out.is_cuda and out.dtype == torch.float32 and tuple(out.shape) == (B, T) and (T == 1 or out.stride(1) == 1), 'ctc_star: out'
+    a = StarArgs()
+    a.struct_size = C.sizeof(StarArgs)
+    a.B, a.T, a.C = B, T, Cn
+    a.pitch_utt, a.pitch_frame = (lp.stride(0) if B > 1 else max(lp.stride(0), T * lp.stride(1))), lp.stride(1)
+    a.log_probs, a.lens = lp.data_ptr(), 0 if ln is None else ln.data_ptr()
+    a.penalty = float(pen)
+    a.star, a.star_pitch = out.data_ptr(), (out.stride(0) if B > 1 else max(out.stride(0), T))
+    with torch.cuda.device(dev):
+        _check(lib.qasr_ctc_star(_stream_ptr(stream), C.byref(a)), 'qasr_ctc_star')
+    return out
+
+
+def _star_arg(star, B, T, dev, who):
+    """the wildcard's plane as (tensor, pitch): a cuda float32 [B, T] whose frames are contiguous"""
+    assert star.is_cuda and star.dtype == torch.float32 and tuple(star.shape) == (B, T), \
+        f'{who}: star must be a cuda float32 plane [{B}, {T}]'
+    st = star.to(dev) if T == 1 or star.stride(1) == 1 else star.contiguous()
+    return st, (st.stride(0) if B > 1 else max(st.stride(0), T))
 
 
 def ctc_align_workspace_bytes(P, T, max_labels):
@@ -598,14 +645,16 @@ def ctc_align_workspace_bytes(P, T, max_labels):
 
 
 def ctc_align(log_probs, lens, targets, target_lens, blank, problems_per_utt=1, want_total=True, workspace=None, out=None,
-              stream=None):
+              stream=None, star=None):
     """qasr_ctc_align: CTC forced alignment and scoring of given label sequences on the device (k_align, one launch on the
     current stream, no host synchronisation); equal to qasr.align.align_host byte for byte.  log_probs: a cuda float32
     tensor [B, T, C] (any utterance / frame pitch, classes contiguous); lens int32 [B] optional; targets cuda int32
     [P, max_labels] with target_lens int32 [P], P = B * problems_per_utt (problem p belongs to utterance
     p // problems_per_utt).  want_total=False skips the forward pass (total None).  Returns a qasr.align.AlignResult of cuda
     tensors.  workspace: a caller-owned uint8 tensor of ctc_align_workspace_bytes(P, T, max_labels) bytes (None: allocated by
-    torch here); `out`: a caller-owned AlignResult whose start / nframes / score / path_score / total may each be None."""
+    torch here); `out`: a caller-owned AlignResult whose start / nframes / score / path_score / total may each be None.
+    star: the wildcard's plane, a cuda float32 tensor [B, T] (ctc_star); with it the label id C is a valid target label
+    (qasr.align.STAR_RULES) and k_align<., true> runs."""
     from .align import AlignResult, MAX_LABELS
     from .beam import TAB_ENTRIES
     lib = load_library()
@@ -640,7 +689,7 @@ def ctc_align(log_probs, lens, targets, target_lens, blank, problems_per_utt=1, 
         workspace = torch.empty(max(ctc_align_workspace_bytes(P, T, ML), 8), device=dev, dtype=torch.uint8)
     tab = lae_table_device(dev) if out.total is not None else None
     a = AlignArgs()
-    a.struct_size = C.sizeof(AlignArgs)
+    a.struct_size = C.sizeof(AlignArgs) if star is not None else AlignArgs.star_logp.offset   # no plane: the call every build takes
     a.B, a.T, a.C, a.P, a.K, a.blank, a.max_labels = B, T, Cn, P, K, int(blank), ML
     a.pitch_utt, a.pitch_frame = (lp.stride(0) if B > 1 else max(lp.stride(0), T * lp.stride(1))), lp.stride(1)
     a.log_probs, a.lens, a.targets, a.target_lens = lp.data_ptr(), 0 if ln is None else ln.data_ptr(), tg.data_ptr(), tl.data_ptr()
@@ -649,9 +698,13 @@ def ctc_align(log_probs, lens, targets, target_lens, blank, problems_per_utt=1, 
     for n in ('start', 'nframes', 'score', 'path_score', 'total', 'ok'):
         t = getattr(out, n)
         setattr(a, n, 0 if t is None else t.data_ptr())
+    st = None
+    if star is not None:
+        st, a.star_pitch = _star_arg(star, B, T, dev, 'ctc_align')
+        a.star_logp = st.data_ptr()
     with torch.cuda.device(dev):
         _check(lib.qasr_ctc_align(_stream_ptr(stream), C.byref(a)), 'qasr_ctc_align')
-    out._keep = (lp, ln, tg, tl, workspace, tab)
+    out._keep = (lp, ln, tg, tl, workspace, tab, st)
     return out
 
 
@@ -661,7 +714,8 @@ class AlignBandArgs(C.Structure):
                 [('reserved', C.c_uint32), ('pitch_utt', C.c_int64), ('pitch_frame', C.c_int64)] +
                 [(n, C.c_void_p) for n in ('log_probs', 'lens', 'targets', 'target_lens', 'workspace')] +
                 [('workspace_bytes', C.c_size_t)] +
-                [(n, C.c_void_p) for n in ('start', 'nframes', 'score', 'path_score', 'frame_logp', 'band_base', 'ok')])
+                [(n, C.c_void_p) for n in ('start', 'nframes', 'score', 'path_score', 'frame_logp', 'band_base', 'ok')] +
+                [('star_logp', C.c_void_p), ('star_pitch', C.c_int64)])
 
 
 def ctc_align_band_workspace_bytes(P, T, band_states):
@@ -669,14 +723,15 @@ def ctc_align_band_workspace_bytes(P, T, band_states):
 
 
 def ctc_align_band(log_probs, lens, targets, target_lens, blank, band_states=None, want_band_base=True, workspace=None, out=None,
-                   stream=None):
+                   stream=None, star=None):
     """qasr_ctc_align_band: banded CTC alignment of whole recordings against whole transcripts on the device (k_align_band,
     one launch on the current stream, no host synchronisation); equal to qasr.align.align_band_host byte for byte.
     log_probs: a cuda float32 tensor [P, T, C] (any recording / frame pitch, classes contiguous); lens int32 [P] optional;
     targets cuda int32 [P, max_labels] with target_lens int32 [P].  band_states: 256, 1024 or 4352 (None: the smallest that
     holds 2 * max_labels + 1 states, else 4352).  Returns a qasr.align.BandResult of cuda tensors.  workspace: a caller-owned
     uint8 tensor of ctc_align_band_workspace_bytes(P, T, band_states) bytes (None: allocated by torch here); `out`: a
-    caller-owned BandResult whose start / nframes / score / path_score / frame_logp / band_base may each be None."""
+    caller-owned BandResult whose start / nframes / score / path_score / frame_logp / band_base may each be None.
+    star: the wildcard's plane, a cuda float32 tensor [P, T] (ctc_star), as in ctc_align."""
     from .align import BAND_BLOCK, BAND_MAX_FRAMES, BAND_MAX_LABELS, BandResult, pick_band_states
     lib = load_library()
     assert log_probs.is_cuda and log_probs.dim() == 3 and log_probs.dtype == torch.float32, \
@@ -715,7 +770,7 @@ def ctc_align_band(log_probs, lens, targets, target_lens, blank, band_states=Non
     if workspace is None:
         workspace = torch.empty(max(ctc_align_band_workspace_bytes(P, T, BW), 8), device=dev, dtype=torch.uint8)
     a = AlignBandArgs()
-    a.struct_size = C.sizeof(AlignBandArgs)
+    a.struct_size = C.sizeof(AlignBandArgs) if star is not None else AlignBandArgs.star_logp.offset   # (as ctc_align)
     a.B, a.T, a.C, a.blank, a.max_labels, a.band_states = P, T, Cn, int(blank), ML, BW
     a.pitch_utt, a.pitch_frame = (lp.stride(0) if P > 1 else max(lp.stride(0), T * lp.stride(1))), lp.stride(1)
     a.log_probs, a.lens, a.targets, a.target_lens = lp.data_ptr(), 0 if ln is None else ln.data_ptr(), tg.data_ptr(), tl.data_ptr()
@@ -723,9 +778,13 @@ def ctc_align_band(log_probs, lens, targets, target_lens, blank, band_states=Non
     for n in names:
         t = getattr(out, n)
         setattr(a, n, 0 if t is None else t.data_ptr())
+    st = None
+    if star is not None:
+        st, a.star_pitch = _star_arg(star, P, T, dev, 'ctc_align_band')
+        a.star_logp = st.data_ptr()
     with torch.cuda.device(dev):
         _check(lib.qasr_ctc_align_band(_stream_ptr(stream), C.byref(a)), 'qasr_ctc_align_band')
-    out._keep = (lp, ln, tg, tl, workspace)
+    out._keep = (lp, ln, tg, tl, workspace, st)
     return out
 
 

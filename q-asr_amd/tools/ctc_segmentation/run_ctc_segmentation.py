@@ -11,6 +11,11 @@ with times in seconds; `text_with_punct` is the matching line of `name_with_punc
 again.  The score is the min-mean confidence of qasr.align.segment_scores (natural-log probabilities); parity with the
 `ctc_segmentation` package's own numbers is not pinned.  An utterance whose alignment was lost is written with times -1 and
 score -inf.
+
+--star_between puts a wildcard label in front of the first utterance, between every two and behind the last
+(EncDecCTCModel.align_long(star_between=True)): audio the transcript does not cover - an introduction, a jingle, a skipped
+sentence - goes to the wildcards instead of being pushed onto the neighbouring utterances; the segments stay one per
+utterance.  --star_penalty is what a wildcard frame pays below the frame's best class, in nats (default 1.0, not tuned on speech).
 """
 import argparse
 import glob
@@ -89,6 +94,10 @@ def main(argv=None):
     p.add_argument('--model', type=str, default='QuartzNet15x5Base-En', help='a .nemo checkpoint or the name of a registered model')
     p.add_argument('--band_states', type=int, default=None, choices=[256, 1024, 4352],
                    help='lattice states kept per frame (default: the smallest that holds the transcript whole, else 4352)')
+    p.add_argument('--star_between', action='store_true',
+                   help='a wildcard label around and between the utterances, for audio the transcript does not cover')
+    p.add_argument('--star_penalty', type=float, default=None,
+                   help='with --star_between: nats per frame the wildcard pays below the frame\'s best class, 0 .. 16 (default 1.0)')
     p.add_argument('--window_s', type=float, default=30.0, help='seconds of audio per window of the model (overlap: 4 s, less for short windows)')
     p.add_argument('--batch_size', type=int, default=32, help='windows per batch')
     p.add_argument('--synthetic_model', action='store_true', help='seeded random weights under the model\'s name (no checkpoint needed)')
@@ -100,6 +109,9 @@ def main(argv=None):
     args = p.parse_args(argv)
     if args.device != 'cuda' and not args.no_quant:
         p.error('--device cpu needs --no_quant: the integer model runs on the HIP engine only')
+    if args.star_penalty is not None and not args.star_between:
+        p.error('--star_penalty needs --star_between')
+    star_kw = dict(star_between=True, star_penalty=1.0 if args.star_penalty is None else args.star_penalty) if args.star_between else {}
     wavs = sorted(glob.glob(os.path.join(args.data, '*.wav'))) if os.path.isdir(args.data) else [args.data]
     if not wavs or not all(w.endswith('.wav') and os.path.exists(w) for w in wavs):
         p.error(f'--data {args.data}: no wav file')
@@ -123,7 +135,7 @@ def main(argv=None):
         try:
             hyp = model.align_long(torch.from_numpy(pcm).to(args.device)[None], torch.tensor([n]).to(args.device), texts=[text],
                                    window_s=args.window_s, overlap_s=overlap_s, guard_s=overlap_s / 4, batch_size=args.batch_size,
-                                   band_states=args.band_states, sample_rate=rate, channels=ch)[0]
+                                   band_states=args.band_states, sample_rate=rate, channels=ch, **star_kw)[0]
         except ValueError as e:
             p.error(f'{path}: {e}')
         out = os.path.join(seg_dir, f'{args.window_len}_' + os.path.basename(path)[:-4] + '_segments.txt')
