@@ -501,6 +501,57 @@ typedef struct qasr_ctc_align_args {
 size_t qasr_ctc_align_workspace_bytes(int P, int T, int max_labels);   /* 0 for a shape qasr_ctc_align refuses */
 int qasr_ctc_align(void* stream, const qasr_ctc_align_args* args);
 
+/* ---- CTC posteriors along an alignment (forward-backward) -----------------------------------------------------------------
+ * How much of the transcript's probability mass agrees with the alignment qasr_ctc_align found: for every frame t < lens the
+ * log-posterior g(t) = A(t, s_t) + Bk(t, s_t) - q(t, s_t) - total of the path's state s_t, where A is the forward row of
+ * qasr_ctc_align, Bk the backward row over the same lattice and total the log-likelihood, all in the same fixed point and with
+ * the same table.  The rules (successors, the order of the two log-add-exps, the path read from start / nframes, what makes a
+ * row valid) are POST_RULES of qasr/align.py, which k_post follows bit for bit.  Problems, K, max_labels, the wildcard plane
+ * and the checks of the target are those of qasr_ctc_align.
+ *   start, nframes i32 [P][max_labels], ok_in i32 [P] (optional: NULL counts as all 1): the outputs of qasr_ctc_align for the
+ *   same inputs.  They are device data: the kernel checks that they describe a CTC alignment of the target over lens frames
+ *   (runs in order, none empty, a blank frame between equal neighbours, the last run inside lens) and only ever compares them
+ *   with frame numbers, so garbage in them reads and writes nothing out of bounds.
+ *   frame_post i32 [P][post_pitch]: g(t) clamped to [-2^30, 0] (/ 2^16 = nats) for t < lens, 0 for lens <= t < T (columns
+ *   T .. post_pitch are not written); label_post i32 [P][max_labels]: the minimum of frame_post over the label's run (tails 0);
+ *   total i64 [P] (optional): equal to qasr_ctc_align's on every byte; ok i32 [P].
+ * ok 0 - frame_post and label_post rows 0, total -2^62: ok_in 0, a target qasr_ctc_align does not align, start / nframes that
+ * are not an alignment of it.
+ * workspace: qasr_ctc_post_workspace_bytes(P, T) = P * T * 8 bytes, 8-byte aligned, that the call may overwrite (the forward
+ * score along the path); nothing is allocated and no length is read on the host, so the call can be captured, also right
+ * behind the qasr_ctc_align whose outputs it reads.
+ * QASR_ERR_ARG with nothing launched and no output written: what qasr_ctc_align refuses (an unknown struct_size, a NULL among
+ * log_probs, targets, target_lens, workspace, ok; B, T, C or K < 1, P != B * K, T > QASR_BEAM_MAX_FRAMES, max_labels outside
+ * 1 .. QASR_ALIGN_MAX_LABELS, blank outside [0, C), pitch_frame < C, pitch_utt < T * pitch_frame, lae_entries !=
+ * QASR_BEAM_TABLE_ENTRIES, a workspace smaller than the query says, a star_logp with star_pitch < T), a NULL among start,
+ * nframes, frame_post, label_post, a NULL lae_table, post_pitch < T, a workspace that is not 8-byte aligned. */
+typedef struct qasr_ctc_post_args {
+  uint32_t struct_size;
+  int32_t B, T, C, P, K, blank, max_labels;
+  int64_t pitch_utt, pitch_frame;   /* in floats */
+  const float* log_probs;
+  const int32_t* lens;         /* optional [B] */
+  const int32_t* targets;      /* [P][max_labels] */
+  const int32_t* target_lens;  /* [P] */
+  uint32_t lae_entries;        /* QASR_BEAM_TABLE_ENTRIES */
+  uint32_t reserved;
+  const uint16_t* lae_table;
+  const int32_t* start;        /* [P][max_labels]: qasr_ctc_align's */
+  const int32_t* nframes;      /* [P][max_labels]: qasr_ctc_align's */
+  const int32_t* ok_in;        /* optional [P]: qasr_ctc_align's ok */
+  void* workspace;
+  size_t workspace_bytes;
+  int32_t* frame_post;         /* [P][post_pitch] */
+  int64_t post_pitch;          /* in int32s, >= T */
+  int32_t* label_post;         /* [P][max_labels] */
+  int64_t* total;              /* optional [P] */
+  int32_t* ok;                 /* [P] */
+  const float* star_logp;      /* optional [B][star_pitch]: the wildcard's plane */
+  int64_t star_pitch;          /* in floats, >= T (with star_logp) */
+} qasr_ctc_post_args;
+size_t qasr_ctc_post_workspace_bytes(int P, int T);   /* 0 for a shape qasr_ctc_post refuses */
+int qasr_ctc_post(void* stream, const qasr_ctc_post_args* args);
+
 /* ---- banded CTC alignment: one long recording against its whole transcript --------------------------------------------
  * k_align above computes every state of every frame and holds 2048 labels and 65 536 frames.  An hour of audio is 180 000
  * frames and some 54 000 characters; k_align_band keeps only a band of band_states = 256, 1024 or 4352 lattice states that

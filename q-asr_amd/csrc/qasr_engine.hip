@@ -1366,6 +1366,43 @@ int qasr_ctc_align(void* stream, const qasr_ctc_align_args* given) {
   return QASR_OK;
 }
 
+// ---- CTC posteriors along an alignment (k_post, qasr_post.hip): the checks of include/qasr.h, then one launch
+size_t qasr_ctc_post_workspace_bytes(int P, int T) {
+  return P >= 1 && T >= 1 && T <= QASR_BEAM_MAX_FRAMES ? post_workspace_bytes(P, T) : 0;
+}
+
+int qasr_ctc_post(void* stream, const qasr_ctc_post_args* a) {
+  if (!a) return fail(QASR_ERR_ARG, "ctc_post: args is NULL");
+  if (a->struct_size != sizeof(qasr_ctc_post_args))
+    return fail(QASR_ERR_ARG, "ctc_post: struct_size %u is not %zu", a->struct_size, sizeof(qasr_ctc_post_args));
+  if (!a->log_probs || !a->targets || !a->target_lens || !a->workspace || !a->ok)
+    return fail(QASR_ERR_ARG, "ctc_post: log_probs, targets, target_lens, workspace and ok are required");
+  if (!a->start || !a->nframes || !a->frame_post || !a->label_post)
+    return fail(QASR_ERR_ARG, "ctc_post: start, nframes, frame_post and label_post are required");
+  if (a->B < 1 || a->T < 1 || a->T > QASR_BEAM_MAX_FRAMES || a->C < 1 || a->K < 1)
+    return fail(QASR_ERR_ARG, "ctc_post: B %d, T %d (1 .. %d), C %d or K %d out of range", a->B, a->T, QASR_BEAM_MAX_FRAMES, a->C,
+                a->K);
+  if ((long long)a->P != (long long)a->B * a->K) return fail(QASR_ERR_ARG, "ctc_post: P %d is not B %d * K %d", a->P, a->B, a->K);
+  if (a->max_labels < 1 || a->max_labels > QASR_ALIGN_MAX_LABELS)
+    return fail(QASR_ERR_ARG, "ctc_post: max_labels %d is outside 1 .. %d", a->max_labels, QASR_ALIGN_MAX_LABELS);
+  if (a->blank < 0 || a->blank >= a->C) return fail(QASR_ERR_ARG, "ctc_post: blank %d is outside [0, %d)", a->blank, a->C);
+  if (a->pitch_frame < a->C || a->pitch_utt < (int64_t)a->T * a->pitch_frame)
+    return fail(QASR_ERR_ARG, "ctc_post: pitch_frame %lld < C or pitch_utt %lld < T * pitch_frame", (long long)a->pitch_frame,
+                (long long)a->pitch_utt);
+  if (!a->lae_table || a->lae_entries != QASR_BEAM_TABLE_ENTRIES)
+    return fail(QASR_ERR_ARG, "ctc_post: lae_table is required and lae_entries %u must be %d", a->lae_entries, QASR_BEAM_TABLE_ENTRIES);
+  if (a->post_pitch < a->T) return fail(QASR_ERR_ARG, "ctc_post: post_pitch %lld < T %d", (long long)a->post_pitch, a->T);
+  if (((uintptr_t)a->workspace & 7) != 0) return fail(QASR_ERR_ARG, "ctc_post: workspace is not 8-byte aligned");
+  const size_t need = post_workspace_bytes(a->P, a->T);
+  if (a->workspace_bytes < need) return fail(QASR_ERR_ARG, "ctc_post: workspace of %zu bytes, %zu needed", a->workspace_bytes, need);
+  if (a->star_logp && a->star_pitch < a->T)
+    return fail(QASR_ERR_ARG, "ctc_post: star_pitch %lld < T %d", (long long)a->star_pitch, a->T);
+  int rc = launch_post((hipStream_t)stream, *a);
+  if (rc) return fail(rc, "ctc_post: launch");
+  HIPCHK(hipGetLastError());
+  return QASR_OK;
+}
+
 // ---- banded CTC alignment (k_align_band, qasr_align_band.hip): the checks of include/qasr.h, then one launch
 static int band_shape_ok(int B, int T, int band_states) {
   return B >= 1 && T >= 1 && T <= QASR_BAND_MAX_FRAMES && (band_states == 256 || band_states == 1024 || band_states == 4352);

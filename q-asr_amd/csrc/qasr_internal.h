@@ -176,6 +176,9 @@ int launch_beam_boost(hipStream_t s, const qasr_ctc_beam_boost_args& a);      //
 // qasr_align.hip: CTC forced alignment and transcript scoring (k_align); the arguments are checked by qasr_ctc_align
 size_t align_workspace_bytes(int P, int T, int max_labels);
 int launch_align(hipStream_t s, const qasr_ctc_align_args& a);
+// qasr_post.hip: CTC posteriors along an alignment (k_post); the arguments are checked by qasr_ctc_post
+size_t post_workspace_bytes(int P, int T);
+int launch_post(hipStream_t s, const qasr_ctc_post_args& a);
 // qasr_align_band.hip: banded CTC alignment of long recordings (k_align_band); the arguments are checked by qasr_ctc_align_band
 size_t align_band_workspace_bytes(int P, int T, int band_states);
 int launch_align_band(hipStream_t s, const qasr_ctc_align_band_args& a);

@@ -90,6 +90,11 @@ def main():
                         "class, 0 .. 16 (default 1.0: a starting point, not tuned on speech)")
     p.add_argument("--star_between", action='store_true',
                    help="(extension, needs --align and --window_s) a wildcard in front of and behind every recording's text")
+    p.add_argument("--posteriors", action='store_true',
+                   help="(extension, needs --align, not with --window_s) how sure the alignment is: a backward pass behind the "
+                        "alignment (EncDecCTCModel.align(posteriors=True), k_post behind k_align); every JSON line of OUT gains "
+                        "\"post\", one value in 0 .. 1 per entry of words in their order - the mean posterior of the word's label "
+                        "frames.  Goes with --star_token")
     p.add_argument("--input_rate", type=int, default=None, metavar='HZ',
                    help="(extension) every file of the manifest is 16-bit mono PCM at this rate (a telephone corpus at 8000, say): "
                         "the batches stay int16 and are resampled to the model's rate on the device (k_resample) in front of the "
@@ -150,6 +155,8 @@ def main():
         p.error('--star_token needs --align and does not go with --shuffle: the texts are read from the manifest in order')
     if args.star_between and (args.align is None or args.window_s is None):
         p.error('--star_between needs --align and --window_s')
+    if args.posteriors and (args.align is None or args.window_s is not None):
+        p.error('--posteriors needs --align and does not go with --window_s: the banded alignment has no backward pass')
     if args.star_penalty is not None and args.star_token is None and not args.star_between:
         p.error('--star_penalty needs --star_token or --star_between')
     if args.star_penalty is not None and not 0.0 <= args.star_penalty <= 16.0:
@@ -351,11 +358,15 @@ def main():
                 except ValueError as e:
                     p.error(f'--align with --window_s / --overlap_s: {e}')
             else:
+                if args.posteriors:
+                    ref_kw.update(posteriors=True)
                 got = asr_model.align(input_signal=signal, input_signal_length=batch[1], **ref_kw, **rate_kw)
             for h in got:
                 k = len(aligned)
                 aligned.append(dict(audio_filepath=items[k][0] if not args.shuffle and k < len(items) else None, text=h.text,
                                     ctc_score=h.ctc_score, utt_score=h.utt_score, words=[list(w) for w in h.words]))
+                if args.posteriors:
+                    aligned[-1]['post'] = list(h.word_post)
         for row in batch[2].cpu().numpy():
             refs.append(''.join(labels_map[c] for c in row))
         audio_s += float(batch[1].sum()) / float(args.input_rate or 16000)

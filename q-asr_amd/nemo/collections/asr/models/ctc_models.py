@@ -476,7 +476,7 @@ class EncDecCTCModel(nn.Module):
     @torch.no_grad()
     def decode(self, input_signal=None, input_signal_length=None, processed_signal=None, processed_signal_length=None,
                beam_width=None, n_best=1, cutoff_top_n=40, lm=None, alpha=0.0, beta=0.0, timestamps=False, boost=None,
-               boost_weight=1.0, sample_rate=None, channels=1):
+               boost_weight=1.0, sample_rate=None, channels=1, posteriors=False):
         """Greedy CTC hypotheses of one batch (an extension of the reference's API): List[qasr.ctc.Hypothesis] with the
         text, every label's start / end time and confidence (best frame log-probability of its run), word groups and the
         log-probability of the greedy path.  Decoding stops at each utterance's encoded length.  On the static engine the
@@ -492,7 +492,9 @@ class EncDecCTCModel(nn.Module):
         aligned against the same log-probabilities (the Viterbi alignment of qasr.align; one more launch, k_align, over the
         beam's device buffers as they lie) and start_s / end_s / score / words are filled as for greedy hypotheses;
         utt_score stays the beam score.  n_best > 1 (<= W) returns, per utterance, the list of its best hypotheses, best
-        first.
+        first.  posteriors=True (needs beam_width and timestamps=True) runs k_post behind k_align over the same rows, n_best
+        problems per utterance, and fills post / post_min / word_post / frame_post of every aligned hypothesis as
+        align(posteriors=True) does.
 
         lm=<path of an ARPA file, or a qasr.ngram.NgramLM> (needs beam_width) adds the n-gram model with the weights alpha
         (0 .. 16) and beta (|beta| <= 16) as ctc_decoders' Scorer does (qasr.beam.LM_RULES; k_beam_lm on the device): word
@@ -514,6 +516,10 @@ class EncDecCTCModel(nn.Module):
             raise ValueError('decode: lm needs beam_width (the greedy collapse has no language model)')
         if boost is not None and beam_width is None:
             raise ValueError('decode: boost needs beam_width (the greedy collapse has no phrase boosting)')
+        if posteriors and beam_width is None:
+            raise ValueError('decode: posteriors needs beam_width (greedy hypotheses are not aligned against a text)')
+        if posteriors and not timestamps:
+            raise ValueError('decode: posteriors needs timestamps=True (the posteriors are those of the alignment)')
         if beam_width is not None:
             beam_width, n_best, cutoff_top_n = self._beam_args(beam_width, n_best, cutoff_top_n)      # refused before any launch
             lm = self._lm_args(lm, alpha, beta)
@@ -524,7 +530,7 @@ class EncDecCTCModel(nn.Module):
                 except ValueError as e:
                     raise ValueError(f'decode: {e}') from None
             return self._beam_decode(self._forward(input_signal, input_signal_length, processed_signal, processed_signal_length),
-                                     beam_width, n_best, cutoff_top_n, lm, alpha, beta, bool(timestamps), boost)
+                                     beam_width, n_best, cutoff_top_n, lm, alpha, beta, bool(timestamps), boost, bool(posteriors))
         res = self._forward(input_signal, input_signal_length, processed_signal, processed_signal_length, decode=True)
         return qctc.to_hypotheses(res, self.decoder.vocabulary, self.seconds_per_frame())
 
@@ -947,7 +953,8 @@ class EncDecCTCModel(nn.Module):
                              f'{len(self.decoder.vocabulary)}')
         return lm
 
-    def _beam_decode(self, fwd, beam_width, n_best, cutoff_top_n, lm=None, alpha=0.0, beta=0.0, timestamps=False, boost=None):
+    def _beam_decode(self, fwd, beam_width, n_best, cutoff_top_n, lm=None, alpha=0.0, beta=0.0, timestamps=False, boost=None,
+                     posteriors=False):
         """decode(beam_width=) behind any path's (log_probs, encoded lengths, tokens); the arguments passed _beam_args"""
         from qasr import beam as qbeam
         log_probs, enc_len = fwd[0], fwd[1]
@@ -961,12 +968,13 @@ class EncDecCTCModel(nn.Module):
                                     alpha, beta, boost)
         hyps = qbeam.to_hypotheses(res, self.decoder.vocabulary)
         if timestamps:
-            self._beam_timestamps(hyps, res, log_probs, enc_len, blank, n_best)
+            self._beam_timestamps(hyps, res, log_probs, enc_len, blank, n_best, posteriors)
         return hyps if n_best > 1 else [h[0] for h in hyps]          # a beam over real candidates never dies: h[0] exists
 
-    def _beam_timestamps(self, hyps, res, log_probs, enc_len, blank, n_best):
+    def _beam_timestamps(self, hyps, res, log_probs, enc_len, blank, n_best, posteriors=False):
         """decode(beam_width=, timestamps=True): the beam's label rows [B][n_best][T] are the targets as they lie (n_best
-        problems per utterance, row pitch T; rows past n_hyps are empty targets and are dropped with their hypotheses)"""
+        problems per utterance, row pitch T; rows past n_hyps are empty targets and are dropped with their hypotheses).
+        posteriors: k_post (the host modules: post_host) over the same rows behind the alignment."""
         from qasr import align as qalign
         B, nb, T = res.labels.shape
         ml = min(T, qalign.MAX_LABELS)                           # a hypothesis beyond the cap is not alignable: no times
@@ -975,14 +983,23 @@ class EncDecCTCModel(nn.Module):
             tg = res.labels.view(B * nb, T) if ml == T else res.labels[:, :, :ml].contiguous().view(B * nb, ml)
             ares = qengine.ctc_align(log_probs.float(), enc_len, tg, res.n_labels.view(B * nb), blank, problems_per_utt=nb,
                                      want_total=False)
+            post = qengine.ctc_post(log_probs.float(), enc_len, tg, res.n_labels.view(B * nb), blank, ares,
+                                    problems_per_utt=nb) if posteriors else None
         else:
             ares = qalign.align_host(log_probs.float().numpy(), enc_len.numpy(), res.labels.reshape(B * nb, T)[:, :ml],
                                      res.n_labels.reshape(B * nb), blank, problems_per_utt=nb, want_total=False)
-        timed = qalign.to_hypotheses(ares, self.decoder.vocabulary, self.seconds_per_frame())
+            post = qalign.post_host(log_probs.float().numpy(), enc_len.numpy(), ares.labels, ares.n_labels, blank, ares.start,
+                                    ares.nframes, ares.ok, problems_per_utt=nb) if posteriors else None
+        if posteriors:
+            timed = qalign.post_to_hypotheses(ares, post, self.decoder.vocabulary, self.seconds_per_frame(), lens=enc_len)
+        else:
+            timed = qalign.to_hypotheses(ares, self.decoder.vocabulary, self.seconds_per_frame())
         for b, row in enumerate(hyps):
             for h, hyp in enumerate(row):
                 t = timed[b * nb + h]
                 hyp.start_s, hyp.end_s, hyp.score, hyp.words = t.start_s, t.end_s, t.score, t.words
+                if posteriors:
+                    hyp.post, hyp.post_min, hyp.word_post, hyp.frame_post = t.post, t.post_min, t.word_post, t.frame_post
 
     def _star_args(self, who, star, star_penalty):
         """The wildcard's arguments (qasr.align.STAR_RULES), refused by name before anything runs: the token (None: no
@@ -1045,7 +1062,7 @@ class EncDecCTCModel(nn.Module):
 
     @torch.no_grad()
     def align(self, input_signal=None, input_signal_length=None, processed_signal=None, processed_signal_length=None,
-              texts=None, labels=None, sample_rate=None, channels=1, star=None, star_penalty=1.0):
+              texts=None, labels=None, sample_rate=None, channels=1, star=None, star_penalty=1.0, posteriors=False):
         """Forced alignment and CTC scoring of GIVEN transcripts (an extension of the reference's API): one
         qasr.ctc.Hypothesis per utterance with the text's labels, every label's start / end time and confidence and the word
         groups of its best (Viterbi) alignment against this batch's log-probabilities, utt_score = the log-probability of that
@@ -1066,7 +1083,15 @@ class EncDecCTCModel(nn.Module):
         inside its run, lists it in words as a word of its own - where the untranscribed audio lies - and counts its emissions
         in utt_score; ctc_score is None for a transcript that holds a wildcard.  An empty token, a token that shares a
         character with the vocabulary, a star_penalty outside 0 .. 16 and the wildcard's id in labels without `star` are
-        refused by name; MAX_LABELS counts wildcards."""
+        refused by name; MAX_LABELS counts wildcards.
+
+        posteriors=True: how sure the alignment is (qasr.align.POST_RULES).  A backward pass over the same lattice (k_post
+        behind k_align on the same stream; post_host on the host modules) gives the posterior of the path's own state at every
+        frame - the share of the text's probability mass whose alignments sit in that state then.  The hypothesis carries post
+        (per label, the mean over its run, 0 .. 1), post_min (per label, its least certain frame), word_post (one per entry of
+        words: the mean over the frames of the word's labels) and frame_post (float32 log-posteriors of the frames); a transcript
+        that is not alignable gets empty lists.  With a wildcard the posteriors are taken in the lattice that holds it.  Without
+        posteriors=True the fields stay None and the call launches what it always did."""
         from qasr import align as qalign
         star, wild, star_pen = self._star_args('align', star, star_penalty)
         input_signal, input_signal_length = self._resample_in(input_signal, input_signal_length, sample_rate, channels)
@@ -1111,9 +1136,14 @@ class EncDecCTCModel(nn.Module):
             plane = qengine.ctc_star(log_probs.float(), enc_len, star_pen) if use_star else None
             res = qengine.ctc_align(log_probs.float(), enc_len, torch.from_numpy(tg).to(log_probs.device),
                                     torch.from_numpy(tl).to(log_probs.device), blank, star=plane)
+            post = qengine.ctc_post(log_probs.float(), enc_len, res.labels, res.n_labels, blank, res, star=plane) if posteriors else None
         else:
             plane = qalign.star_host(log_probs.float().numpy(), enc_len.numpy(), star_pen) if use_star else None
             res = qalign.align_host(log_probs.float().numpy(), enc_len.numpy(), tg, tl, blank, star=plane)
+            post = qalign.post_host(log_probs.float().numpy(), enc_len.numpy(), tg, tl, blank, res.start, res.nframes, res.ok,
+                                    star=plane) if posteriors else None
+        if posteriors:
+            return qalign.post_to_hypotheses(res, post, vocab, self.seconds_per_frame(), lens=enc_len, star_token=star)
         return qalign.to_hypotheses(res, vocab, self.seconds_per_frame(), star_token=star)
 
     def _long_transcripts(self, texts, labels, n_recordings, star=None, wild=None, star_between=False):
@@ -1250,7 +1280,10 @@ class EncDecCTCModel(nn.Module):
         utterance list, between every two and behind the last (space labels around each when the vocabulary has a space; the
         token is star, '*' when star is None), for recordings whose transcript skips what lies between the utterances.
         `segments` stay one per utterance, from its first to its last label that is no wildcard: the frames of the wildcards
-        in between belong to no segment.  The hypothesis shows the tokens in text and in words."""
+        in between belong to no segment.  The hypothesis shows the tokens in text and in words.
+
+        Not built: posteriors (post / post_min / word_post / frame_post stay None).  They need a forward pass in the band;
+        align(posteriors=True) has them for utterances that fit k_align."""
         from qasr import align as qalign, engine as qengine
         if input_signal is None or input_signal_length is None:
             raise ValueError('align_long: input_signal and input_signal_length are required')

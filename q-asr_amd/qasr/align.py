@@ -26,13 +26,16 @@ states that follows the path: BAND_RULES, `align_band_host` (the host statement 
 `segment_scores` at the end of this module; they are the CPU path of EncDecCTCModel.align_long.
 
 Audio the transcript does not cover is given a wildcard label whose emission is a per-frame plane: STAR_RULES, `star_host` (the
-host statement of k_star, csrc/qasr_star.hip) and the `star=` argument of both twins."""
+host statement of k_star, csrc/qasr_star.hip) and the `star=` argument of both twins.
+
+How sure an alignment is - the posterior of the path's own state at every frame, by a backward pass over the same lattice:
+POST_RULES, `post_host` (the host statement of k_post, csrc/qasr_post.hip) and `post_to_hypotheses`."""
 from dataclasses import dataclass
 from typing import List, Sequence
 
 import numpy as np
 
-from .beam import MAX_T, NEG, ONE, _order_key, lae, lae_table, quantize
+from .beam import MAX_T, NEG, ONE, Q_FLOOR, _order_key, lae, lae_table, quantize
 
 MAX_LABELS = 2048                       # QASR_ALIGN_MAX_LABELS
 STAR_MAX_PENALTY = 16.0                 # nats per frame; qasr_ctc_star refuses more
@@ -469,3 +472,200 @@ def segment_scores(frame_logp, f0, f1) -> np.ndarray:
         else:
             out[i] = np.lib.stride_tricks.sliding_window_view(x[a:b], SEGMENT_WINDOW).mean(axis=1).min()
     return out
+
+
+# ---- posteriors along an alignment: forward-backward over the lattice of RULES (k_post, csrc/qasr_post.hip)
+POST_RULES = """How much of the transcript's probability mass agrees with the alignment: the log-posterior of the path's own state at every
+frame.  The inputs are align_host's plus the alignment's start, nframes [P, max_labels] and ok [P].
+Lattice: states, lab(s), q(t, s), lim, the predecessors and the forward row A are exactly those of RULES; A(t, s) is the forward
+row after frame t.
+Backward row: Bk(lim - 1, s) = q(lim - 1, s) for s in {2L, 2L - 1} (L == 0: s = 0), NEG elsewhere.  For t < lim - 1 the successors
+of s are s, s + 1 (if s + 1 <= 2L) and s + 2 (only if s is odd, s + 2 <= 2L - 1 and y[(s + 1) / 2] != y[(s - 1) / 2]); a missing
+successor is NEG.  x = lae(lae(Bk[s], Bk[s + 1]), Bk[s + 2]) in exactly this order; Bk'[s] = NEG if x == NEG, else x + q(t, s).
+Nothing is ever added to NEG.
+The path comes from start / nframes, not from backpointers: frame t is in state 2i + 1 when start[i] <= t < start[i] + nframes[i],
+otherwise in the blank state 2j, j = the number of labels with start[i] <= t.
+Validity: start / nframes must describe a CTC alignment of the target over lim frames - runs in order, none empty, a blank frame
+between adjacent equal labels, the last run ends by lim.  ok_post[p] = 0 when they do not, when ok[p] == 0, and for a target
+align_host refuses (L < 0, L above the row pitch or MAX_LABELS, a label outside [0, C) or equal to blank, lim == 0 with L > 0);
+all outputs of such a problem are zero and total = NEG.  start / nframes are only ever compared with frame numbers, never used as
+an index.  A valid path has a finite score (q is clamped), so A and Bk along it are never NEG.
+Outputs: total int64 [P] = lae(A[2L], A[2L - 1]) at lim - 1 (L == 0: A[0]), align_host's total on every byte.
+g(t) = A(t, s_t) + Bk(t, s_t) - q(t, s_t) - total in int64.  frame_post int32 [P, T] = g(t) clamped to [Q_FLOOR, 0] for t < lim
+(lae is not exact: g can come out a little above 0), 0 behind lim.  label_post int32 [P, max_labels] = the minimum of frame_post
+over the label's run, its least certain frame; tails 0.  ok int32 [P].  lim == 0 with L == 0: ok = 1, total = 0.
+Star: id C reads the plane wherever logp[u][t][c] is read (STAR_RULES); every output equals on every byte the call without a
+plane on the matrix with the plane appended as class C of C + 1.  total with a wildcard is a score, not a likelihood."""
+
+
+@dataclass
+class PostResult:
+    """Outputs of POST_RULES (arrays: NumPy on the host, torch tensors from the device binding): frame_post int32 [P, T] and
+    label_post int32 [P, max_labels] fixed-point log-posteriors (/ 2^16 = nats, <= 0), total int64 [P] (None when not
+    requested from the device), ok int32 [P]."""
+    frame_post: object = None
+    label_post: object = None
+    total: object = None
+    ok: object = None
+
+
+def _path_ok(start, nframes, y, lim):
+    """start / nframes [L] describe a CTC alignment of y over lim frames (the validity of POST_RULES), in Python integers"""
+    end = -1
+    for i in range(len(y)):
+        s, n = int(start[i]), int(nframes[i])
+        if n < 1 or s <= end or (i and y[i] == y[i - 1] and s <= end + 1):
+            return False
+        end = s + n - 1
+    return end < lim
+
+
+def _post_one(lp, lim, y, blank, tab, start, nframes, st=None):
+    """one problem with a valid target y and a valid path over lp float32 [T, C]: (total, frame_post int32 [lim], label_post
+    int32 [L])"""
+    L = len(y)
+    i64 = np.int64
+    S = 2 * L + 1
+    lab = np.full(S, blank, dtype=np.int64)
+    lab[1::2] = y
+    skip = np.zeros(S, dtype=bool)
+    if L > 1:
+        skip[3::2] = y[1:] != y[:-1]
+    skipb = np.zeros(S, dtype=bool)                                 # s may step to s + 2: s + 2 may come from s
+    skipb[:S - 2] = skip[2:]
+    q = quantize(_emit(lp, st, np.arange(lim)[:, None], lab[None, :]))             # int32 [lim, S]
+    negs = np.full(2, NEG, i64)
+    t = np.arange(lim)
+    start, nframes = np.asarray(start, dtype=i64), np.asarray(nframes, dtype=i64)
+    j = np.searchsorted(start, t, side='right')                     # labels with start <= t (start ascends: the path is valid)
+    in_run = (j > 0) & (t < (start + nframes)[np.maximum(j, 1) - 1]) if L else np.zeros(lim, dtype=bool)
+    states = np.where(in_run, 2 * j - 1, 2 * j)
+    A = np.full(S, NEG, i64)
+    A[:min(2, S)] = q[0, :min(2, S)]
+    fa = np.empty(lim, dtype=i64)
+    fa[0] = A[states[0]]
+    for f in range(1, lim):
+        ext = np.concatenate([negs, A])
+        x = lae(lae(A, ext[1:S + 1], tab), np.where(skip, ext[:S], NEG), tab)
+        live = x != NEG
+        A = np.where(live, np.where(live, x, 0) + q[f].astype(i64), NEG)
+        fa[f] = A[states[f]]
+    total = int(A[0]) if L == 0 else int(lae(A[2 * L], A[2 * L - 1], tab))
+    Bk = np.full(S, NEG, i64)
+    Bk[max(S - 2, 0):] = q[lim - 1, max(S - 2, 0):]
+    fb = np.empty(lim, dtype=i64)
+    fb[lim - 1] = Bk[states[lim - 1]]
+    for f in range(lim - 2, -1, -1):
+        ext = np.concatenate([Bk, negs])
+        x = lae(lae(Bk, ext[1:S + 1], tab), np.where(skipb, ext[2:S + 2], NEG), tab)
+        live = x != NEG
+        Bk = np.where(live, np.where(live, x, 0) + q[f].astype(i64), NEG)
+        fb[f] = Bk[states[f]]
+    g = fa + fb - q[t, states].astype(i64) - i64(total)
+    frame_post = np.clip(g, Q_FLOOR, 0).astype(np.int32)
+    label_post = np.zeros(L, dtype=np.int32)
+    for i in range(L):
+        label_post[i] = frame_post[int(start[i]):int(start[i] + nframes[i])].min()
+    return total, frame_post, label_post
+
+
+def post_host(log_probs, lens, targets, target_lens, blank, start, nframes, ok, problems_per_utt=1, star=None) -> PostResult:
+    """POST_RULES on the host: the NumPy twin of k_post and the CPU path of align(posteriors=True).  log_probs, lens, targets,
+    target_lens, blank, problems_per_utt and star as in align_host; start, nframes int32 [P, max_labels] and ok int32 [P] (None:
+    all 1) are the alignment's own."""
+    lp = np.asarray(log_probs, dtype=np.float32)
+    if lp.ndim != 3 or min(lp.shape) < 1:
+        raise ValueError(f'post_host: log_probs must be [B, T, C] with B, T, C >= 1, got {lp.shape}')
+    B, T, C = lp.shape
+    K = int(problems_per_utt)
+    tg = np.asarray(targets)
+    tl = np.asarray(target_lens)
+    if K < 1 or tg.ndim != 2 or tg.shape[0] != B * K or tl.shape != (B * K,):
+        raise ValueError(f'post_host: targets must be [B * problems_per_utt, max_labels] with one length each, got '
+                         f'{tg.shape} / {tl.shape} for B {B}, problems_per_utt {K}')
+    P, ML = tg.shape
+    if not 1 <= ML <= MAX_LABELS:
+        raise ValueError(f'post_host: max_labels (the row pitch of targets) must be 1 .. {MAX_LABELS}, got {ML}')
+    if T > MAX_T:
+        raise ValueError(f'post_host: at most {MAX_T} frames, got {T}')
+    blank = int(blank)
+    if not 0 <= blank < C:
+        raise ValueError(f'post_host: blank {blank} is outside [0, {C})')
+    a_start, a_nframes = np.asarray(start), np.asarray(nframes)
+    a_ok = np.ones(P, dtype=np.int32) if ok is None else np.asarray(ok)
+    if a_start.shape != (P, ML) or a_nframes.shape != (P, ML) or a_ok.shape != (P,):
+        raise ValueError(f'post_host: start / nframes must be [{P}, {ML}] and ok [{P}], got {a_start.shape} / {a_nframes.shape} / '
+                         f'{a_ok.shape}')
+    tg = tg.astype(np.int32)
+    star = _star_plane(star, B, T, 'post_host')
+    n_ids = C + (star is not None)
+    tab = lae_table()
+    frame_post = np.zeros((P, T), dtype=np.int32)
+    label_post = np.zeros((P, ML), dtype=np.int32)
+    total = np.full(P, NEG, dtype=np.int64)
+    ok_post = np.zeros(P, dtype=np.int32)
+    for p in range(P):
+        u = p // K
+        lim = T if lens is None else int(min(max(int(lens[u]), 0), T))
+        L = int(tl[p])
+        if a_ok[p] == 0 or L < 0 or L > ML:
+            continue
+        y = tg[p, :L]
+        if L and (y.min() < 0 or y.max() >= n_ids or (y == blank).any()):
+            continue
+        if not _path_ok(a_start[p, :L], a_nframes[p, :L], y, lim):  # (lim == 0 with L > 0 fails here)
+            continue
+        ok_post[p] = 1
+        if lim == 0:
+            total[p] = 0
+            continue
+        total[p], frame_post[p, :lim], label_post[p, :L] = _post_one(lp[u], lim, y, blank, tab, a_start[p, :L], a_nframes[p, :L],
+                                                                     None if star is None else star[u])
+    return PostResult(frame_post, label_post, total, ok_post)
+
+
+def _word_groups(labels, vocab, wild):
+    """the label indices of every word of to_hypotheses: the labels between ' ' labels, the wildcard a word of its own"""
+    groups, group = [], []
+    for k, c in enumerate(labels):
+        if wild is not None and c == wild:
+            groups += [group, [k]]
+            group = []
+        elif vocab[c] == ' ':
+            groups.append(group)
+            group = []
+        else:
+            group.append(k)
+    return [g for g in groups + [group] if g]
+
+
+def post_to_hypotheses(result: AlignResult, post: PostResult, vocabulary: Sequence[str], seconds_per_frame: float, lens=None,
+                       star_token=None) -> List:
+    """`to_hypotheses` plus the posteriors of `post` (POST_RULES) in the optional fields of qasr.ctc.Hypothesis: post, per label
+    the mean over its run of exp(frame_post / 2^16), in 0 .. 1; post_min, per label exp(label_post / 2^16), its least certain
+    frame; word_post, one value per entry of words: the mean over the frames of the word's labels; frame_post, a float32 array
+    of the lim log-posteriors (nats) of the path's states.  lens: the frame counts [B] the alignment ran with (None: all T).  A
+    problem whose posteriors are not ok (or that is not alignable) gets empty lists."""
+    hyps = to_hypotheses(result, vocabulary, seconds_per_frame, star_token)
+    fp_all, ok, a_ok = _np(post.frame_post), _np(post.ok), _np(result.ok)
+    start, nframes = _np(result.start), _np(result.nframes)
+    T = fp_all.shape[1]
+    K = int(result.problems_per_utt)
+    ln = None if lens is None else _np(lens)
+    vocab = list(vocabulary)
+    wild = len(vocab) + 1 if star_token is not None else None
+    if wild is not None:
+        vocab += ['', star_token]
+    for p, h in enumerate(hyps):
+        if not (ok[p] and a_ok[p]):
+            h.post, h.post_min, h.word_post, h.frame_post = [], [], [], np.zeros(0, dtype=np.float32)
+            continue
+        lim = T if ln is None else int(min(max(int(ln[p // K]), 0), T))
+        pr = np.exp(fp_all[p, :lim].astype(np.float64) / ONE)
+        runs = [pr[int(start[p, i]):int(start[p, i]) + int(nframes[p, i])] for i in range(len(h.labels))]
+        h.post = [float(r.mean()) for r in runs]
+        h.post_min = [float(r.min()) for r in runs]
+        h.word_post = [float(np.concatenate([runs[k] for k in g]).mean()) for g in _word_groups(h.labels, vocab, wild)]
+        assert len(h.word_post) == len(h.words), (len(h.word_post), len(h.words))
+        h.frame_post = (fp_all[p, :lim].astype(np.float64) / ONE).astype(np.float32)
+    return hyps

@@ -64,6 +64,11 @@ class Hypothesis:
     ctc_score: Optional[float] = None       # forced alignment (qasr.align): the CTC log-likelihood of the text, all alignments
     boost_score: Optional[float] = None     # beam search with phrase boosting (qasr.boost): the boosting's share of utt_score
     segments: Optional[List[Segment]] = None  # align_long with a list of utterances: one Segment per utterance
+    # align / decode(timestamps=True) with posteriors=True (qasr.align.POST_RULES): how much of the text's probability mass agrees
+    post: Optional[List[float]] = None      # per label: the mean posterior of its state over its run, 0 .. 1
+    post_min: Optional[List[float]] = None  # per label: the posterior at its least certain frame
+    word_post: Optional[List[float]] = None  # one per entry of words: the mean over the frames of the word's labels
+    frame_post: Optional[object] = None     # float32 [frames]: the log-posterior (nats) of the path's state at every frame
     seams_s: Optional[List[float]] = None   # decode_long (qasr.longform): the times at which neighbouring windows were joined
 
 

@@ -19,7 +19,7 @@ SYMBOLS = ['qasr_blob_check', 'qasr_engine_create', 'qasr_engine_create_ex', 'qa
            'qasr_dyn_quant_in', 'qasr_dyn_conv_params', 'qasr_sep_layer', 'qasr_quantile2', 'qasr_quantile_workspace_bytes', 'qasr_debug_prof',
            'qasr_debug_timeline', 'qasr_ctc_collapse', 'qasr_engine_attach_ctc', 'qasr_ctc_topn', 'qasr_ctc_beam_workspace_bytes', 'qasr_ctc_beam',
            'qasr_lm_check', 'qasr_ctc_beam_lm', 'qasr_boost_check', 'qasr_ctc_beam_boost', 'qasr_ctc_align_workspace_bytes', 'qasr_ctc_align',
-           'qasr_ctc_align_band_workspace_bytes', 'qasr_ctc_align_band', 'qasr_ctc_star',
+           'qasr_ctc_align_band_workspace_bytes', 'qasr_ctc_align_band', 'qasr_ctc_star', 'qasr_ctc_post_workspace_bytes', 'qasr_ctc_post',
            'qasr_engine_reserve', 'qasr_engine_forward_ragged', 'qasr_engine_forward_ragged_audio', 'qasr_engine_ragged_stats',
            'qasr_ragged_bucket_frames', 'qasr_ragged_envelope_frames',
            'qasr_resample_check', 'qasr_resample', 'qasr_resample_out_samples', 'qasr_longform_cut', 'qasr_longform_stitch',
@@ -178,6 +178,10 @@ def load_library():
         lib.qasr_ctc_align_band_workspace_bytes.restype = sz
     if hasattr(lib, 'qasr_ctc_star'):           # (likewise)
         lib.qasr_ctc_star.argtypes = [vp, C.POINTER(StarArgs)]
+    if hasattr(lib, 'qasr_ctc_post'):           # (likewise)
+        lib.qasr_ctc_post.argtypes = [vp, C.POINTER(PostArgs)]
+        lib.qasr_ctc_post_workspace_bytes.argtypes = [i32, i32]
+        lib.qasr_ctc_post_workspace_bytes.restype = sz
     if hasattr(lib, 'qasr_engine_reserve'):     # (likewise)
         lib.qasr_engine_reserve.argtypes = [vp, C.POINTER(ReserveOpts)]
         lib.qasr_engine_forward_ragged.argtypes = [vp, vp, vp, vp, i32, i32, C.POINTER(RaggedOut)]
@@ -705,6 +709,88 @@ def ctc_align(log_probs, lens, targets, target_lens, blank, problems_per_utt=1, 
     with torch.cuda.device(dev):
         _check(lib.qasr_ctc_align(_stream_ptr(stream), C.byref(a)), 'qasr_ctc_align')
     out._keep = (lp, ln, tg, tl, workspace, tab, st)
+    return out
+
+
+class PostArgs(C.Structure):
+    """qasr_ctc_post_args (include/qasr.h)"""
+    _fields_ = ([('struct_size', C.c_uint32)] + [(n, C.c_int32) for n in ('B', 'T', 'C', 'P', 'K', 'blank', 'max_labels')] +
+                [('pitch_utt', C.c_int64), ('pitch_frame', C.c_int64)] +
+                [(n, C.c_void_p) for n in ('log_probs', 'lens', 'targets', 'target_lens')] +
+                [('lae_entries', C.c_uint32), ('reserved', C.c_uint32), ('lae_table', C.c_void_p)] +
+                [(n, C.c_void_p) for n in ('start', 'nframes', 'ok_in')] +
+                [('workspace', C.c_void_p), ('workspace_bytes', C.c_size_t), ('frame_post', C.c_void_p), ('post_pitch', C.c_int64)] +
+                [(n, C.c_void_p) for n in ('label_post', 'total', 'ok')] +
+                [('star_logp', C.c_void_p), ('star_pitch', C.c_int64)])
+
+
+def ctc_post_workspace_bytes(P, T):
+    return int(load_library().qasr_ctc_post_workspace_bytes(int(P), int(T)))
+
+
+def ctc_post(log_probs, lens, targets, target_lens, blank, align_result, problems_per_utt=1, star=None, workspace=None, out=None,
+             stream=None):
+    """qasr_ctc_post: the log-posteriors of an alignment's own states on the device (k_post: forward-backward, one launch on
+    the current stream, no host synchronisation); equal to qasr.align.post_host byte for byte.  The inputs are ctc_align's;
+    align_result: the AlignResult of ctc_align for them (its start, nframes and ok are read on the device, so the call may
+    follow ctc_align at once).  Returns a qasr.align.PostResult of cuda tensors: frame_post int32 [P, T], label_post int32
+    [P, max_labels], total int64 [P], ok int32 [P].  workspace: a caller-owned uint8 tensor of ctc_post_workspace_bytes(P, T)
+    bytes, 8-byte aligned (None: allocated by torch here); `out`: a caller-owned PostResult whose total may be None and whose
+    frame_post rows may have any pitch >= T."""
+    from .align import MAX_LABELS, PostResult
+    from .beam import TAB_ENTRIES
+    lib = load_library()
+    assert log_probs.is_cuda and log_probs.dim() == 3 and log_probs.dtype == torch.float32, \
+        'ctc_post: log_probs must be a cuda float32 tensor [B, T, C]'
+    dev = log_probs.device
+    lp = log_probs if log_probs.stride(2) == 1 or log_probs.shape[2] == 1 else log_probs.contiguous()
+    ln = None if lens is None else lens.to(device=dev, dtype=torch.int32).contiguous()
+    B, T, Cn = lp.shape
+    K = int(problems_per_utt)
+    assert targets.dim() == 2 and target_lens.dim() == 1, 'ctc_post: targets must be [P, max_labels], target_lens [P]'
+    tg = targets.to(device=dev, dtype=torch.int32).contiguous()
+    tl = target_lens.to(device=dev, dtype=torch.int32).contiguous()
+    P, ML = tg.shape
+    if ML > MAX_LABELS:
+        raise ValueError(f'ctc_post: max_labels (the row pitch of targets) must be 1 .. {MAX_LABELS}, got {ML}')
+    if tl.shape[0] != P:
+        raise ValueError(f'ctc_post: {P} target rows but {tl.shape[0]} lengths')
+    i32 = dict(device=dev, dtype=torch.int32)
+    ins = []
+    for n, shape in (('start', (P, ML)), ('nframes', (P, ML)), ('ok', (P,))):
+        t = getattr(align_result, n)
+        assert t is not None and tuple(t.shape) == shape, f'ctc_post: align_result.{n} must be {list(shape)}'
+        ins.append(t.to(**i32).contiguous())
+    if out is None:
+        out = PostResult(frame_post=torch.empty(P, T, **i32), label_post=torch.empty(P, ML, **i32),
+                         total=torch.empty(P, device=dev, dtype=torch.int64), ok=torch.empty(P, **i32))
+    fp = out.frame_post
+    assert fp is not None and fp.is_cuda and fp.dtype == torch.int32 and tuple(fp.shape) == (P, T) and (T == 1 or fp.stride(1) == 1), \
+        'ctc_post: out.frame_post'
+    for n, dt, shape in (('label_post', torch.int32, (P, ML)), ('total', torch.int64, (P,)), ('ok', torch.int32, (P,))):
+        t = getattr(out, n)
+        assert (t is None and n == 'total') or (t is not None and t.is_cuda and t.is_contiguous() and t.dtype == dt and
+                                                tuple(t.shape) == shape), f'ctc_post: out.{n}'
+    if workspace is None:
+        workspace = torch.empty(max(ctc_post_workspace_bytes(P, T), 8), device=dev, dtype=torch.uint8)
+    tab = lae_table_device(dev)
+    a = PostArgs()
+    a.struct_size = C.sizeof(PostArgs)
+    a.B, a.T, a.C, a.P, a.K, a.blank, a.max_labels = B, T, Cn, P, K, int(blank), ML
+    a.pitch_utt, a.pitch_frame = (lp.stride(0) if B > 1 else max(lp.stride(0), T * lp.stride(1))), lp.stride(1)
+    a.log_probs, a.lens, a.targets, a.target_lens = lp.data_ptr(), 0 if ln is None else ln.data_ptr(), tg.data_ptr(), tl.data_ptr()
+    a.lae_entries, a.lae_table = TAB_ENTRIES, tab.data_ptr()
+    a.start, a.nframes, a.ok_in = (t.data_ptr() for t in ins)
+    a.workspace, a.workspace_bytes = workspace.data_ptr(), workspace.numel() * workspace.element_size()
+    a.frame_post, a.post_pitch = fp.data_ptr(), (fp.stride(0) if P > 1 else max(fp.stride(0), T))
+    a.label_post, a.total, a.ok = out.label_post.data_ptr(), 0 if out.total is None else out.total.data_ptr(), out.ok.data_ptr()
+    st = None
+    if star is not None:
+        st, a.star_pitch = _star_arg(star, B, T, dev, 'ctc_post')
+        a.star_logp = st.data_ptr()
+    with torch.cuda.device(dev):
+        _check(lib.qasr_ctc_post(_stream_ptr(stream), C.byref(a)), 'qasr_ctc_post')
+    out._keep = (lp, ln, tg, tl, ins, workspace, tab, st)
     return out
 
 
