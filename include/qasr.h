@@ -603,6 +603,60 @@ typedef struct qasr_ctc_align_band_args {
 size_t qasr_ctc_align_band_workspace_bytes(int B, int T, int band_states);   /* 0 for a shape qasr_ctc_align_band refuses */
 int qasr_ctc_align_band(void* stream, const qasr_ctc_align_band_args* args);
 
+/* ---- CTC posteriors along a banded alignment (forward-backward inside the band) --------------------------------------------
+ * qasr_ctc_post for recordings that only fit qasr_ctc_align_band: k_post_band runs the forward and the backward pass over the
+ * cells the band kept - (t, s) with band_base[p][t / 32] <= s < band_base[p][t / 32] + band_states - and over the edges
+ * k_align_band's own step uses (a predecessor below the new base does not count), with k_align_band's circular ownership.
+ * Every quantity is the restricted lattice's: total is the log-likelihood of the alignments inside the band, a lower bound
+ * on the full lattice's; frame_post and label_post have qasr_ctc_post's meaning and fixed point.  The rules are
+ * POST_BAND_RULES of qasr/align.py, which the kernel follows bit for bit.  One problem per recording, as in
+ * qasr_ctc_align_band; band_states is the width that call ran with.
+ *   start, nframes i32 [B][max_labels], ok_in i32 [B] (optional: NULL counts as all 1), band_base i32 [B][ceil(T / 32)]: the
+ *   outputs of qasr_ctc_align_band for the same inputs.  They are device data: the kernel checks that start / nframes are a CTC
+ *   alignment of the target over lens frames, that band_base is a trajectory k_align_band can produce (starts at 0, never
+ *   decreases, moves by less than band_states / 2 per block, stays in [0, max(0, 2 * target_lens + 1 - band_states)]) and that
+ *   the path stays inside the band and on its edges, all by comparisons and before anything is read through them.
+ *   frame_post i32 [B][post_pitch], label_post i32 [B][max_labels], total i64 [B] (optional), ok i32 [B]: as in qasr_ctc_post.
+ * ok 0 - frame_post and label_post rows 0, total -2^62: ok_in 0, a target qasr_ctc_align_band does not align, start / nframes
+ * that are not an alignment of it, a band_base row that is no trajectory, a path outside the band.
+ * workspace: qasr_ctc_post_band_workspace_bytes(B, T) = B * T * 8 bytes, 8-byte aligned, that the call may overwrite (the
+ * forward score along the path); nothing is allocated and no length is read on the host, so the call can be captured, also
+ * right behind the qasr_ctc_align_band whose outputs it reads.
+ * QASR_ERR_ARG with nothing launched and no output written: what qasr_ctc_align_band refuses (an unknown struct_size, a NULL
+ * among log_probs, targets, target_lens, workspace, ok; B, T or C < 1, T > QASR_BAND_MAX_FRAMES, max_labels outside
+ * 1 .. QASR_BAND_MAX_LABELS, band_states not 256, 1024 or 4352, blank outside [0, C), pitch_frame < C, pitch_utt < T *
+ * pitch_frame, a workspace smaller than the query says, a star_logp with star_pitch < T), what qasr_ctc_post refuses (a NULL
+ * among start, nframes, frame_post, label_post, a NULL lae_table, lae_entries != QASR_BEAM_TABLE_ENTRIES, post_pitch < T, a
+ * workspace that is not 8-byte aligned), a NULL band_base. */
+typedef struct qasr_ctc_post_band_args {
+  uint32_t struct_size;
+  int32_t B, T, C, blank, max_labels, band_states;
+  uint32_t reserved;
+  int64_t pitch_utt, pitch_frame;   /* in floats */
+  const float* log_probs;
+  const int32_t* lens;         /* optional [B] */
+  const int32_t* targets;      /* [B][max_labels] */
+  const int32_t* target_lens;  /* [B] */
+  uint32_t lae_entries;        /* QASR_BEAM_TABLE_ENTRIES */
+  uint32_t reserved2;
+  const uint16_t* lae_table;
+  const int32_t* start;        /* [B][max_labels]: qasr_ctc_align_band's */
+  const int32_t* nframes;      /* [B][max_labels]: qasr_ctc_align_band's */
+  const int32_t* ok_in;        /* optional [B]: qasr_ctc_align_band's ok */
+  const int32_t* band_base;    /* [B][ceil(T / 32)]: qasr_ctc_align_band's */
+  void* workspace;
+  size_t workspace_bytes;
+  int32_t* frame_post;         /* [B][post_pitch] */
+  int64_t post_pitch;          /* in int32s, >= T */
+  int32_t* label_post;         /* [B][max_labels] */
+  int64_t* total;              /* optional [B] */
+  int32_t* ok;                 /* [B] */
+  const float* star_logp;      /* optional [B][star_pitch]: the wildcard's plane */
+  int64_t star_pitch;          /* in floats, >= T (with star_logp) */
+} qasr_ctc_post_band_args;
+size_t qasr_ctc_post_band_workspace_bytes(int B, int T);   /* 0 for a shape qasr_ctc_post_band refuses */
+int qasr_ctc_post_band(void* stream, const qasr_ctc_post_band_args* args);
+
 /* ---- the wildcard ("star") for audio the transcript does not cover -------------------------------------------------------
  * A transcript that omits part of the audio pushes those frames onto the neighbouring labels.  The wildcard is one more
  * label, id C, that the caller puts into the target where text is missing; its log-probability at frame t is not a column of

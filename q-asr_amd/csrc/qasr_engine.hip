@@ -1444,6 +1444,45 @@ int qasr_ctc_align_band(void* stream, const qasr_ctc_align_band_args* given) {
   return QASR_OK;
 }
 
+// ---- CTC posteriors inside the band (k_post_band, qasr_post_band.hip): the checks of include/qasr.h, then one launch
+size_t qasr_ctc_post_band_workspace_bytes(int B, int T) {
+  return B >= 1 && T >= 1 && T <= QASR_BAND_MAX_FRAMES ? post_band_workspace_bytes(B, T) : 0;
+}
+
+int qasr_ctc_post_band(void* stream, const qasr_ctc_post_band_args* a) {
+  if (!a) return fail(QASR_ERR_ARG, "ctc_post_band: args is NULL");
+  if (a->struct_size != sizeof(qasr_ctc_post_band_args))
+    return fail(QASR_ERR_ARG, "ctc_post_band: struct_size %u is not %zu", a->struct_size, sizeof(qasr_ctc_post_band_args));
+  if (!a->log_probs || !a->targets || !a->target_lens || !a->workspace || !a->ok)
+    return fail(QASR_ERR_ARG, "ctc_post_band: log_probs, targets, target_lens, workspace and ok are required");
+  if (!a->start || !a->nframes || !a->band_base || !a->frame_post || !a->label_post)
+    return fail(QASR_ERR_ARG, "ctc_post_band: start, nframes, band_base, frame_post and label_post are required");
+  if (a->band_states != 256 && a->band_states != 1024 && a->band_states != 4352)
+    return fail(QASR_ERR_ARG, "ctc_post_band: band_states %d is not 256, 1024 or 4352", a->band_states);
+  if (a->B < 1 || a->T < 1 || a->T > QASR_BAND_MAX_FRAMES || a->C < 1)
+    return fail(QASR_ERR_ARG, "ctc_post_band: B %d, T %d (1 .. %d) or C %d out of range", a->B, a->T, QASR_BAND_MAX_FRAMES, a->C);
+  if (a->max_labels < 1 || a->max_labels > QASR_BAND_MAX_LABELS)
+    return fail(QASR_ERR_ARG, "ctc_post_band: max_labels %d is outside 1 .. %d", a->max_labels, QASR_BAND_MAX_LABELS);
+  if (a->blank < 0 || a->blank >= a->C) return fail(QASR_ERR_ARG, "ctc_post_band: blank %d is outside [0, %d)", a->blank, a->C);
+  if (a->pitch_frame < a->C || a->pitch_utt < (int64_t)a->T * a->pitch_frame)
+    return fail(QASR_ERR_ARG, "ctc_post_band: pitch_frame %lld < C or pitch_utt %lld < T * pitch_frame", (long long)a->pitch_frame,
+                (long long)a->pitch_utt);
+  if (!a->lae_table || a->lae_entries != QASR_BEAM_TABLE_ENTRIES)
+    return fail(QASR_ERR_ARG, "ctc_post_band: lae_table is required and lae_entries %u must be %d", a->lae_entries,
+                QASR_BEAM_TABLE_ENTRIES);
+  if (a->post_pitch < a->T) return fail(QASR_ERR_ARG, "ctc_post_band: post_pitch %lld < T %d", (long long)a->post_pitch, a->T);
+  if (((uintptr_t)a->workspace & 7) != 0) return fail(QASR_ERR_ARG, "ctc_post_band: workspace is not 8-byte aligned");
+  const size_t need = post_band_workspace_bytes(a->B, a->T);
+  if (a->workspace_bytes < need)
+    return fail(QASR_ERR_ARG, "ctc_post_band: workspace of %zu bytes, %zu needed", a->workspace_bytes, need);
+  if (a->star_logp && a->star_pitch < a->T)
+    return fail(QASR_ERR_ARG, "ctc_post_band: star_pitch %lld < T %d", (long long)a->star_pitch, a->T);
+  int rc = launch_post_band((hipStream_t)stream, *a);
+  if (rc) return fail(rc, "ctc_post_band: launch");
+  HIPCHK(hipGetLastError());
+  return QASR_OK;
+}
+
 // ---- the wildcard's emission plane (k_star, qasr_star.hip): the checks of include/qasr.h, then one launch
 int qasr_ctc_star(void* stream, const qasr_ctc_star_args* a) {
   if (!a) return fail(QASR_ERR_ARG, "ctc_star: args is NULL");

@@ -182,6 +182,9 @@ int launch_post(hipStream_t s, const qasr_ctc_post_args& a);
 // qasr_align_band.hip: banded CTC alignment of long recordings (k_align_band); the arguments are checked by qasr_ctc_align_band
 size_t align_band_workspace_bytes(int P, int T, int band_states);
 int launch_align_band(hipStream_t s, const qasr_ctc_align_band_args& a);
+// qasr_post_band.hip: CTC posteriors inside the band of a banded alignment (k_post_band); checked by qasr_ctc_post_band
+size_t post_band_workspace_bytes(int P, int T);
+int launch_post_band(hipStream_t s, const qasr_ctc_post_band_args& a);
 // qasr_star.hip: the wildcard's emission plane (k_star); the arguments are checked by qasr_ctc_star
 int launch_star(hipStream_t s, const qasr_ctc_star_args& a);
 // qasr_resample.hip: rational polyphase resampler (k_resample); the arguments are checked by qasr_resample

@@ -80,7 +80,7 @@ def main():
                         "ctc_score (log-likelihood of the text), utt_score (its best alignment) and words [word, start_s, end_s, "
                         "score]; hypotheses, WER and the other outputs are unchanged.  With --window_s the texts are aligned "
                         "against the stitched windows of the whole recording (EncDecCTCModel.align_long, a banded lattice: any "
-                        "length of text; ctc_score is then null)")
+                        "length of text; ctc_score is then null unless --posteriors fills it)")
     p.add_argument("--star_token", type=str, default=None, metavar='TOK',
                    help="(extension, needs --align) a token such as '*' in the manifest's texts that marks audio the text does not "
                         "cover: the texts are aligned as written, TOK as a wildcard label (EncDecCTCModel.align(star=)); OUT "
@@ -91,10 +91,13 @@ def main():
     p.add_argument("--star_between", action='store_true',
                    help="(extension, needs --align and --window_s) a wildcard in front of and behind every recording's text")
     p.add_argument("--posteriors", action='store_true',
-                   help="(extension, needs --align, not with --window_s) how sure the alignment is: a backward pass behind the "
+                   help="(extension, needs --align) how sure the alignment is: a backward pass behind the "
                         "alignment (EncDecCTCModel.align(posteriors=True), k_post behind k_align); every JSON line of OUT gains "
                         "\"post\", one value in 0 .. 1 per entry of words in their order - the mean posterior of the word's label "
-                        "frames.  Goes with --star_token")
+                        "frames.  Goes with --star_token.  With --window_s the passes run inside the band of the banded alignment "
+                        "(EncDecCTCModel.align_long(posteriors=True), k_post_band behind k_align_band): ctc_score is then the "
+                        "log-likelihood inside the band, and with --star_between the line also gains \"segments\", [text, "
+                        "start_s, end_s, score, post] per utterance")
     p.add_argument("--input_rate", type=int, default=None, metavar='HZ',
                    help="(extension) every file of the manifest is 16-bit mono PCM at this rate (a telephone corpus at 8000, say): "
                         "the batches stay int16 and are resampled to the model's rate on the device (k_resample) in front of the "
@@ -155,8 +158,8 @@ def main():
         p.error('--star_token needs --align and does not go with --shuffle: the texts are read from the manifest in order')
     if args.star_between and (args.align is None or args.window_s is None):
         p.error('--star_between needs --align and --window_s')
-    if args.posteriors and (args.align is None or args.window_s is not None):
-        p.error('--posteriors needs --align and does not go with --window_s: the banded alignment has no backward pass')
+    if args.posteriors and args.align is None:
+        p.error('--posteriors needs --align')
     if args.star_penalty is not None and args.star_token is None and not args.star_between:
         p.error('--star_penalty needs --star_token or --star_between')
     if args.star_penalty is not None and not 0.0 <= args.star_penalty <= 16.0:
@@ -352,6 +355,8 @@ def main():
                 if args.star_between:                        # one utterance per recording: a wildcard in front of it and behind it
                     ref_kw.update({k: [[v] for v in ref_kw[k]] for k in ('labels', 'texts') if ref_kw.get(k) is not None},
                                   star_between=True)
+                if args.posteriors:                          # k_post_band behind k_align_band
+                    ref_kw.update(posteriors=True)
                 try:
                     got = asr_model.align_long(signal, batch[1], window_s=args.window_s, overlap_s=overlap_s,
                                                guard_s=min(1.0, overlap_s / 4), batch_size=args.batch_size, **ref_kw, **rate_kw)
@@ -367,6 +372,8 @@ def main():
                                     ctc_score=h.ctc_score, utt_score=h.utt_score, words=[list(w) for w in h.words]))
                 if args.posteriors:
                     aligned[-1]['post'] = list(h.word_post)
+                    if h.segments is not None:
+                        aligned[-1]['segments'] = [[sg.text, sg.start_s, sg.end_s, sg.score, sg.post] for sg in h.segments]
         for row in batch[2].cpu().numpy():
             refs.append(''.join(labels_map[c] for c in row))
         audio_s += float(batch[1].sum()) / float(args.input_rate or 16000)

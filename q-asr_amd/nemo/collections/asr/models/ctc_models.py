@@ -1256,11 +1256,11 @@ class EncDecCTCModel(nn.Module):
     @torch.no_grad()
     def align_long(self, input_signal, input_signal_length, texts=None, labels=None, window_s=30.0, overlap_s=4.0, guard_s=1.0,
                    batch_size=32, seam='blank', band_states=None, sample_rate=None, channels=1, star=None, star_penalty=1.0,
-                   star_between=False):
+                   star_between=False, posteriors=False):
         """CTC segmentation of long recordings (an extension; the job of the reference's tools/ctc_segmentation, on the
         device): input_signal [R, S] with input_signal_length samples each and, per recording, its whole transcript ->
         List[qasr.ctc.Hypothesis], one per recording, with every label's and word's times in seconds of the recording,
-        utt_score = the log-probability of the alignment, ctc_score = None (no forward pass in the band) and seams_s as
+        utt_score = the log-probability of the alignment, ctc_score = None (unless posteriors=True, below) and seams_s as
         decode_long's.  Exactly one of `texts` and `labels`; texts[r] is a string, or a list of utterance strings (labels[r]:
         a sequence of ids, or a list of such): utterances are joined by the space label when the vocabulary has one, by
         nothing otherwise, an empty utterance is refused by name, and the hypothesis then carries `segments`, one
@@ -1282,8 +1282,13 @@ class EncDecCTCModel(nn.Module):
         `segments` stay one per utterance, from its first to its last label that is no wildcard: the frames of the wildcards
         in between belong to no segment.  The hypothesis shows the tokens in text and in words.
 
-        Not built: posteriors (post / post_min / word_post / frame_post stay None).  They need a forward pass in the band;
-        align(posteriors=True) has them for utterances that fit k_align."""
+        posteriors=True: how sure the alignment is (qasr.align.POST_BAND_RULES).  The banded alignment also returns the band's
+        trajectory, and k_post_band (CPU inputs: post_band_host) follows on the same stream with a forward and a backward pass
+        inside that band.  Every hypothesis gains post, post_min, word_post and frame_post with the meaning
+        align(posteriors=True) gives them, every Segment gains post - the mean of exp(frame_post) over its frames - and ctc_score
+        is filled: total / 2^16, the log-likelihood of the alignments that stay inside the band, a lower bound on the full
+        lattice's (None when the transcript holds a wildcard, as in align).  A lost path keeps empty lists and Segment.post None.
+        Without posteriors=True the call launches, allocates and returns what it always did."""
         from qasr import align as qalign, engine as qengine
         if input_signal is None or input_signal_length is None:
             raise ValueError('align_long: input_signal and input_signal_length are required')
@@ -1323,12 +1328,24 @@ class EncDecCTCModel(nn.Module):
         if logp.is_cuda:
             plane = qengine.ctc_star(logp, total, star_pen) if use_star else None
             res = qengine.ctc_align_band(logp, total, torch.from_numpy(tg).to(logp.device), torch.from_numpy(tl).to(logp.device),
-                                         blank, band_states=bw, want_band_base=False, star=plane)
+                                         blank, band_states=bw, want_band_base=bool(posteriors), star=plane)
+            post = qengine.ctc_post_band(logp, total, res.labels, res.n_labels, blank, res, star=plane) if posteriors else None
         else:
             plane = qalign.star_host(logp.numpy(), total.numpy(), star_pen) if use_star else None
-            res = qalign.align_band_host(logp.numpy(), total.numpy(), tg, tl, blank, band_states=bw, want_band_base=False, star=plane)
+            res = qalign.align_band_host(logp.numpy(), total.numpy(), tg, tl, blank, band_states=bw, want_band_base=bool(posteriors),
+                                         star=plane)
+            post = qalign.post_band_host(logp.numpy(), total.numpy(), tg, tl, blank, res.start, res.nframes, res.ok, res.band_base, bw,
+                                         star=plane) if posteriors else None
         spf_s = self.seconds_per_frame()
-        hyps = qalign.to_hypotheses(res, vocab, spf_s, star_token=star)
+        if posteriors:
+            res.total = post.total                                  # ctc_score: the likelihood inside the band
+            hyps = qalign.post_to_hypotheses(res, post, vocab, spf_s, lens=total, star_token=star)
+            post_ok, frame_post = qalign._np(post.ok), qalign._np(post.frame_post)
+            for h, p_ok in zip(hyps, post_ok):
+                if not p_ok and h.ctc_score is not None:
+                    h.ctc_score = float('-inf')
+        else:
+            hyps = qalign.to_hypotheses(res, vocab, spf_s, star_token=star)
         seams_h = seams.cpu().numpy()
         if any(u is not None for u in utts):
             ok, start, nframes = (qalign._np(x) for x in (res.ok, res.start, res.nframes))
@@ -1346,6 +1363,10 @@ class EncDecCTCModel(nn.Module):
             f1 = np.array([start[r, a + k - 1] + nframes[r, a + k - 1] for _, a, k in utts[r]], dtype=np.int64)
             sc = qalign.segment_scores(frame_logp[r], f0, f1)
             h.segments = [Segment(text, float(a) * spf_s, float(b) * spf_s, float(c)) for (text, _, _), a, b, c in zip(utts[r], f0, f1, sc)]
+            if posteriors and post_ok[r]:
+                pr = np.exp(frame_post[r].astype(np.float64) / qalign.ONE)
+                for seg, a, b in zip(h.segments, f0, f1):
+                    seg.post = float(pr[a:b].mean())
         return hyps
 
     @staticmethod

@@ -29,7 +29,9 @@ Audio the transcript does not cover is given a wildcard label whose emission is 
 host statement of k_star, csrc/qasr_star.hip) and the `star=` argument of both twins.
 
 How sure an alignment is - the posterior of the path's own state at every frame, by a backward pass over the same lattice:
-POST_RULES, `post_host` (the host statement of k_post, csrc/qasr_post.hip) and `post_to_hypotheses`."""
+POST_RULES, `post_host` (the host statement of k_post, csrc/qasr_post.hip) and `post_to_hypotheses`; for long recordings the
+same inside the band of the banded alignment: POST_BAND_RULES and `post_band_host` (the host statement of k_post_band,
+csrc/qasr_post_band.hip), the CPU path of EncDecCTCModel.align_long(posteriors=True)."""
 from dataclasses import dataclass
 from typing import List, Sequence
 
@@ -669,3 +671,181 @@ def post_to_hypotheses(result: AlignResult, post: PostResult, vocabulary: Sequen
         assert len(h.word_post) == len(h.words), (len(h.word_post), len(h.words))
         h.frame_post = (fp_all[p, :lim].astype(np.float64) / ONE).astype(np.float32)
     return hyps
+
+
+# ---- posteriors along a banded alignment: forward-backward inside the band k_align_band chose (k_post_band, csrc/qasr_post_band.hip)
+POST_BAND_RULES = """POST_RULES for a recording that only fits k_align_band: the forward and the backward pass run over the part of the lattice that
+the band of BAND_RULES kept, so every quantity is one of the restricted lattice - total is the log-likelihood of the
+alignments that stay inside the band, a lower bound (up to lae's error) on the full lattice's.  The inputs are align_band_host's
+plus its start, nframes [P, max_labels], ok [P] and band_base [P, ceil(T / 32)], and the width BW in BAND_STATES it ran with.
+Shapes are BAND_RULES's: K = 1, L <= BAND_MAX_LABELS, T <= BAND_MAX_FRAMES.  States, lab(s), q(t, s), lim, S = 2L + 1,
+top = max(0, S - BW), the predecessors and successors, lae and its order are those of RULES and POST_RULES.
+Cells: base(t) = band_base[p][t // 32]; (t, s) exists iff base(t) <= s < min(base(t) + BW, S).
+Edges: (t - 1, s') -> (t, s) is an edge of RULES whose two cells exist and with s' >= base(t) - k_align_band's "a predecessor
+below the new base is NEG", so the Viterbi path of k_align_band runs over existing edges only.
+Forward row: A(0, s) = q(0, s) for s < 2 (s < S), NEG elsewhere; A(t, s) = x + q(t, s), x = lae(lae(A[s], A[s - 1]), A[s - 2]) over
+the existing edges into (t, s), a missing one counting as NEG; NEG if x == NEG: k_align_band's step with lae in place of max.
+Backward row: Bk(lim - 1, s) = q(lim - 1, s) for s in {2L, 2L - 1} (L == 0: s = 0) that exist at lim - 1, NEG elsewhere;
+Bk(t, s) = x + q(t, s), x = lae(lae(Bk[s], Bk[s + 1]), Bk[s + 2]) over the existing edges out of (t, s).  A state whose successors
+all lie outside is NEG at that frame; in particular a cell of a block's last frame that lies below the next block's base is a
+dead end.  Nothing is ever added to NEG.
+total = lae(A[2L], A[2L - 1]) at lim - 1 (L == 0: A[0]); an end state outside the last band counts as NEG.
+The path is read from start / nframes as in POST_RULES; g(t) = A(t, s_t) + Bk(t, s_t) - q(t, s_t) - total, frame_post = g clamped
+to [Q_FLOOR, 0] for t < lim and 0 behind, label_post = the minimum of frame_post over the label's run, tails 0.
+Validity.  ok = 0, every output row zero and total = NEG: POST_RULES's reasons (BAND_MAX_LABELS in place of MAX_LABELS); a
+band_base row that is no trajectory of k_align_band - over the blocks that have a frame < lim it must start at 0, never
+decrease, move by less than BW / 2 per block and stay in [0, top]; a path that leaves its frame's band (no cell (t, s_t)); a
+path over a missing edge (s_t < base(t + 1) for t + 1 < lim); total == NEG.  Everything is decided by comparisons: start,
+nframes and band_base are never used as an index before they are checked (a checked start or end is a frame number < lim and
+may then select a block of band_base).  lim == 0 with L == 0: ok = 1, total = 0.
+When S <= BW the base is 0 throughout and every output equals post_host's on every byte.
+Star: id C reads the plane wherever logp[p][t][c] is read (STAR_RULES); every output equals on every byte the call without a
+plane on the matrix with the plane appended as class C of C + 1."""
+
+
+def _band_base_ok(bases, nblk, top, BW):
+    """the first nblk entries of a band_base row are a trajectory k_align_band can produce (POST_BAND_RULES), in Python integers"""
+    prev = 0
+    for j in range(nblk):
+        b = int(bases[j])
+        if b < 0 or b > top or (b != 0 if j == 0 else (b < prev or b - prev >= BW // 2)):
+            return False
+        prev = b
+    return True
+
+
+def _post_band_one(lp, lim, y, blank, tab, BW, start, nframes, bases, st=None):
+    """one problem with a valid target y, a valid path and a valid band_base row `bases` over lp float32 [T, C]: (total,
+    frame_post int32 [lim], label_post int32 [L]), or None when the path is not inside the band or total == NEG"""
+    L = len(y)
+    i64 = np.int64
+    S = 2 * L + 1
+    n = min(BW, S)                                                  # states in the band (constant: base <= top)
+    lab = np.full(S, blank, dtype=np.int64)
+    lab[1::2] = y
+    skip = np.zeros(S, dtype=bool)
+    if L > 1:
+        skip[3::2] = y[1:] != y[:-1]
+    skipb = np.zeros(S, dtype=bool)                                 # s may step to s + 2
+    skipb[:S - 2] = skip[2:]
+    t = np.arange(lim)
+    start, nframes = np.asarray(start, dtype=i64), np.asarray(nframes, dtype=i64)
+    j = np.searchsorted(start, t, side='right')
+    in_run = (j > 0) & (t < (start + nframes)[np.maximum(j, 1) - 1]) if L else np.zeros(lim, dtype=bool)
+    states = np.where(in_run, 2 * j - 1, 2 * j)
+    bt = np.asarray(bases, dtype=i64)[t // BAND_BLOCK]              # base(t)
+    if ((states < bt) | (states >= bt + BW)).any() or (states[:-1] < bt[1:]).any():
+        return None                                                 # no such cell, or no such edge
+    negs = np.full(2, NEG, i64)
+
+    def q_at(f, b):
+        return quantize(_emit(lp, st, f, lab[b:b + n])).astype(i64)
+
+    def add(x, q):
+        live = x != NEG
+        return np.where(live, np.where(live, x, 0) + q, NEG)
+    b = 0
+    A = np.full(n, NEG, i64)                                        # A[i]: state b + i
+    A[:min(2, S)] = q_at(0, 0)[:min(2, S)]
+    fa = np.empty(lim, dtype=i64)
+    fa[0] = A[states[0]]
+    for f in range(1, lim):
+        nb = int(bt[f])
+        if nb > b:                                                  # (nb - b < BW / 2 <= n)
+            A = np.concatenate([A[nb - b:], np.full(nb - b, NEG, i64)])
+            b = nb
+        ext = np.concatenate([negs, A])                             # what lies below base is NEG
+        A = add(lae(lae(A, ext[1:n + 1], tab), np.where(skip[b:b + n], ext[:n], NEG), tab), q_at(f, b))
+        fa[f] = A[states[f] - b]
+
+    def at(s):
+        return int(A[s - b]) if b <= s < b + n else NEG
+    total = at(0) if L == 0 else int(lae(at(2 * L), at(2 * L - 1), tab))
+    if total == NEG:
+        return None
+    Bk = np.full(n, NEG, i64)                                       # Bk[i]: state b + i
+    q = q_at(lim - 1, b)
+    for s in range(max(S - 2, 0), S):
+        if b <= s < b + n:
+            Bk[s - b] = q[s - b]
+    fb = np.empty(lim, dtype=i64)
+    fb[lim - 1] = Bk[states[lim - 1] - b]
+    for f in range(lim - 2, -1, -1):
+        ext = np.concatenate([Bk, negs])                            # what lies above the band is NEG
+        x = lae(lae(Bk, ext[1:n + 1], tab), np.where(skipb[b:b + n], ext[2:n + 2], NEG), tab)       # x[i]: state base(f + 1) + i
+        nb = int(bt[f])
+        if nb < b:                                                  # the states below base(f + 1) are dead ends at f
+            x = np.concatenate([np.full(b - nb, NEG, i64), x[:n - (b - nb)]])
+            b = nb
+        Bk = add(x, q_at(f, b))
+        fb[f] = Bk[states[f] - b]
+    g = fa + fb - quantize(_emit(lp, st, t, lab[states])).astype(i64) - i64(total)
+    frame_post = np.clip(g, Q_FLOOR, 0).astype(np.int32)
+    label_post = np.zeros(L, dtype=np.int32)
+    for i in range(L):
+        label_post[i] = frame_post[int(start[i]):int(start[i] + nframes[i])].min()
+    return total, frame_post, label_post
+
+
+def post_band_host(log_probs, lens, targets, target_lens, blank, start, nframes, ok, band_base, band_states, star=None) -> PostResult:
+    """POST_BAND_RULES on the host: the NumPy twin of k_post_band and the CPU path of align_long(posteriors=True).  log_probs,
+    lens, targets, target_lens, blank and star as in align_band_host; start, nframes int32 [P, max_labels], ok int32 [P] (None:
+    all 1) and band_base int32 [P, ceil(T / 32)] are that alignment's own (want_band_base=True), band_states the width it used."""
+    lp = np.asarray(log_probs, dtype=np.float32)
+    if lp.ndim != 3 or min(lp.shape) < 1:
+        raise ValueError(f'post_band_host: log_probs must be [P, T, C] with P, T, C >= 1, got {lp.shape}')
+    P, T, C = lp.shape
+    tg = np.asarray(targets)
+    tl = np.asarray(target_lens)
+    if tg.ndim != 2 or tg.shape[0] != P or tl.shape != (P,):
+        raise ValueError(f'post_band_host: targets must be [P, max_labels] with one length each, got {tg.shape} / {tl.shape} '
+                         f'for P {P}')
+    ML = tg.shape[1]
+    if not 1 <= ML <= BAND_MAX_LABELS:
+        raise ValueError(f'post_band_host: max_labels (the row pitch of targets) must be 1 .. {BAND_MAX_LABELS}, got {ML}')
+    if T > BAND_MAX_FRAMES:
+        raise ValueError(f'post_band_host: at most {BAND_MAX_FRAMES} frames, got {T}')
+    blank = int(blank)
+    if not 0 <= blank < C:
+        raise ValueError(f'post_band_host: blank {blank} is outside [0, {C})')
+    if band_states is None or int(band_states) not in BAND_STATES:
+        raise ValueError(f'post_band_host: band_states must be one of {BAND_STATES}, got {band_states}')
+    BW = int(band_states)
+    NB = (T + BAND_BLOCK - 1) // BAND_BLOCK
+    a_start, a_nframes = np.asarray(start), np.asarray(nframes)
+    a_ok = np.ones(P, dtype=np.int32) if ok is None else np.asarray(ok)
+    if band_base is None:
+        raise ValueError('post_band_host: band_base is required (align_band_host(want_band_base=True))')
+    a_base = np.asarray(band_base)
+    if a_start.shape != (P, ML) or a_nframes.shape != (P, ML) or a_ok.shape != (P,) or a_base.shape != (P, NB):
+        raise ValueError(f'post_band_host: start / nframes must be [{P}, {ML}], ok [{P}] and band_base [{P}, {NB}], got '
+                         f'{a_start.shape} / {a_nframes.shape} / {a_ok.shape} / {a_base.shape}')
+    tg = tg.astype(np.int32)
+    star = _star_plane(star, P, T, 'post_band_host')
+    n_ids = C + (star is not None)
+    tab = lae_table()
+    frame_post = np.zeros((P, T), dtype=np.int32)
+    label_post = np.zeros((P, ML), dtype=np.int32)
+    total = np.full(P, NEG, dtype=np.int64)
+    ok_post = np.zeros(P, dtype=np.int32)
+    for p in range(P):
+        lim = T if lens is None else int(min(max(int(lens[p]), 0), T))
+        L = int(tl[p])
+        if a_ok[p] == 0 or L < 0 or L > ML:
+            continue
+        y = tg[p, :L]
+        if L and (y.min() < 0 or y.max() >= n_ids or (y == blank).any()):
+            continue
+        if not _path_ok(a_start[p, :L], a_nframes[p, :L], y, lim):  # (lim == 0 with L > 0 fails here)
+            continue
+        if not _band_base_ok(a_base[p], (lim + BAND_BLOCK - 1) // BAND_BLOCK, max(0, 2 * L + 1 - BW), BW):
+            continue
+        if lim == 0:
+            ok_post[p], total[p] = 1, 0
+            continue
+        got = _post_band_one(lp[p], lim, y, blank, tab, BW, a_start[p, :L], a_nframes[p, :L], a_base[p],
+                             None if star is None else star[p])
+        if got is not None:
+            ok_post[p] = 1
+            total[p], frame_post[p, :lim], label_post[p, :L] = got
+    return PostResult(frame_post, label_post, total, ok_post)

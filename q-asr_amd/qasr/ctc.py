@@ -30,11 +30,14 @@ class CtcResult:
 class Segment:
     """One utterance of a transcript inside a long recording (EncDecCTCModel.align_long): from the first frame of its first
     label to the end of its last label's run, in seconds of the recording; score: qasr.align.segment_scores (-inf, with times
-    None, when the alignment was lost)."""
+    None, when the alignment was lost); post: with align_long(posteriors=True) the mean over the segment's frames of
+    exp(frame_post), in float64, 0 .. 1 - how much of the transcript's probability mass inside the band passes through the
+    alignment there (None without posteriors and for a lost alignment)."""
     text: str
     start_s: Optional[float]
     end_s: Optional[float]
     score: float
+    post: Optional[float] = None
 
 
 @dataclass

@@ -20,6 +20,7 @@ SYMBOLS = ['qasr_blob_check', 'qasr_engine_create', 'qasr_engine_create_ex', 'qa
            'qasr_debug_timeline', 'qasr_ctc_collapse', 'qasr_engine_attach_ctc', 'qasr_ctc_topn', 'qasr_ctc_beam_workspace_bytes', 'qasr_ctc_beam',
            'qasr_lm_check', 'qasr_ctc_beam_lm', 'qasr_boost_check', 'qasr_ctc_beam_boost', 'qasr_ctc_align_workspace_bytes', 'qasr_ctc_align',
            'qasr_ctc_align_band_workspace_bytes', 'qasr_ctc_align_band', 'qasr_ctc_star', 'qasr_ctc_post_workspace_bytes', 'qasr_ctc_post',
+           'qasr_ctc_post_band_workspace_bytes', 'qasr_ctc_post_band',
            'qasr_engine_reserve', 'qasr_engine_forward_ragged', 'qasr_engine_forward_ragged_audio', 'qasr_engine_ragged_stats',
            'qasr_ragged_bucket_frames', 'qasr_ragged_envelope_frames',
            'qasr_resample_check', 'qasr_resample', 'qasr_resample_out_samples', 'qasr_longform_cut', 'qasr_longform_stitch',
@@ -182,6 +183,10 @@ def load_library():
         lib.qasr_ctc_post.argtypes = [vp, C.POINTER(PostArgs)]
         lib.qasr_ctc_post_workspace_bytes.argtypes = [i32, i32]
         lib.qasr_ctc_post_workspace_bytes.restype = sz
+    if hasattr(lib, 'qasr_ctc_post_band'):      # (likewise)
+        lib.qasr_ctc_post_band.argtypes = [vp, C.POINTER(PostBandArgs)]
+        lib.qasr_ctc_post_band_workspace_bytes.argtypes = [i32, i32]
+        lib.qasr_ctc_post_band_workspace_bytes.restype = sz
     if hasattr(lib, 'qasr_engine_reserve'):     # (likewise)
         lib.qasr_engine_reserve.argtypes = [vp, C.POINTER(ReserveOpts)]
         lib.qasr_engine_forward_ragged.argtypes = [vp, vp, vp, vp, i32, i32, C.POINTER(RaggedOut)]
@@ -871,6 +876,94 @@ def ctc_align_band(log_probs, lens, targets, target_lens, blank, band_states=Non
     with torch.cuda.device(dev):
         _check(lib.qasr_ctc_align_band(_stream_ptr(stream), C.byref(a)), 'qasr_ctc_align_band')
     out._keep = (lp, ln, tg, tl, workspace, st)
+    return out
+
+
+class PostBandArgs(C.Structure):
+    """qasr_ctc_post_band_args (include/qasr.h)"""
+    _fields_ = ([('struct_size', C.c_uint32)] + [(n, C.c_int32) for n in ('B', 'T', 'C', 'blank', 'max_labels', 'band_states')] +
+                [('reserved', C.c_uint32), ('pitch_utt', C.c_int64), ('pitch_frame', C.c_int64)] +
+                [(n, C.c_void_p) for n in ('log_probs', 'lens', 'targets', 'target_lens')] +
+                [('lae_entries', C.c_uint32), ('reserved2', C.c_uint32), ('lae_table', C.c_void_p)] +
+                [(n, C.c_void_p) for n in ('start', 'nframes', 'ok_in', 'band_base')] +
+                [('workspace', C.c_void_p), ('workspace_bytes', C.c_size_t), ('frame_post', C.c_void_p), ('post_pitch', C.c_int64)] +
+                [(n, C.c_void_p) for n in ('label_post', 'total', 'ok')] +
+                [('star_logp', C.c_void_p), ('star_pitch', C.c_int64)])
+
+
+def ctc_post_band_workspace_bytes(P, T):
+    return int(load_library().qasr_ctc_post_band_workspace_bytes(int(P), int(T)))
+
+
+def ctc_post_band(log_probs, lens, targets, target_lens, blank, band_result, star=None, workspace=None, out=None, stream=None):
+    """qasr_ctc_post_band: the log-posteriors of a banded alignment's own states, inside its band, on the device (k_post_band:
+    forward-backward, one launch on the current stream, no host synchronisation); equal to qasr.align.post_band_host byte for
+    byte.  The inputs are ctc_align_band's; band_result: the BandResult of ctc_align_band for them, made with
+    want_band_base=True (its start, nframes, ok and band_base are read on the device, so the call may follow ctc_align_band at
+    once; its band_states is the width).  Returns a qasr.align.PostResult of cuda tensors: frame_post int32 [P, T], label_post
+    int32 [P, max_labels], total int64 [P], ok int32 [P].  workspace: a caller-owned uint8 tensor of
+    ctc_post_band_workspace_bytes(P, T) bytes, 8-byte aligned (None: allocated by torch here); `out`: a caller-owned PostResult
+    whose total may be None and whose frame_post rows may have any pitch >= T."""
+    from .align import BAND_BLOCK, BAND_MAX_FRAMES, BAND_MAX_LABELS, PostResult, pick_band_states
+    from .beam import TAB_ENTRIES
+    lib = load_library()
+    assert log_probs.is_cuda and log_probs.dim() == 3 and log_probs.dtype == torch.float32, \
+        'ctc_post_band: log_probs must be a cuda float32 tensor [P, T, C]'
+    dev = log_probs.device
+    lp = log_probs if log_probs.stride(2) == 1 or log_probs.shape[2] == 1 else log_probs.contiguous()
+    ln = None if lens is None else lens.to(device=dev, dtype=torch.int32).contiguous()
+    P, T, Cn = lp.shape
+    assert targets.dim() == 2 and target_lens.dim() == 1, 'ctc_post_band: targets must be [P, max_labels], target_lens [P]'
+    tg = targets.to(device=dev, dtype=torch.int32).contiguous()
+    tl = target_lens.to(device=dev, dtype=torch.int32).contiguous()
+    ML = tg.shape[1]
+    if tg.shape[0] != P or tl.shape[0] != P:
+        raise ValueError(f'ctc_post_band: {P} recordings but {tg.shape[0]} target rows and {tl.shape[0]} lengths')
+    if not 1 <= ML <= BAND_MAX_LABELS:
+        raise ValueError(f'ctc_post_band: max_labels (the row pitch of targets) must be 1 .. {BAND_MAX_LABELS}, got {ML}')
+    if T > BAND_MAX_FRAMES:
+        raise ValueError(f'ctc_post_band: at most {BAND_MAX_FRAMES} frames, got {T}')
+    try:
+        BW = pick_band_states(ML, band_result.band_states or None)
+    except ValueError as e:
+        raise ValueError(f'ctc_post_band: band_result.{e}') from None
+    NB = (T + BAND_BLOCK - 1) // BAND_BLOCK
+    i32 = dict(device=dev, dtype=torch.int32)
+    ins = []
+    for n, shape in (('start', (P, ML)), ('nframes', (P, ML)), ('ok', (P,)), ('band_base', (P, NB))):
+        t = getattr(band_result, n)
+        assert t is not None and tuple(t.shape) == shape, f'ctc_post_band: band_result.{n} must be {list(shape)}'
+        ins.append(t.to(**i32).contiguous())
+    if out is None:
+        out = PostResult(frame_post=torch.empty(P, T, **i32), label_post=torch.empty(P, ML, **i32),
+                         total=torch.empty(P, device=dev, dtype=torch.int64), ok=torch.empty(P, **i32))
+    fp = out.frame_post
+    assert fp is not None and fp.is_cuda and fp.dtype == torch.int32 and tuple(fp.shape) == (P, T) and (T == 1 or fp.stride(1) == 1), \
+        'ctc_post_band: out.frame_post'
+    for n, dt, shape in (('label_post', torch.int32, (P, ML)), ('total', torch.int64, (P,)), ('ok', torch.int32, (P,))):
+        t = getattr(out, n)
+        assert (t is None and n == 'total') or (t is not None and t.is_cuda and t.is_contiguous() and t.dtype == dt and
+                                                tuple(t.shape) == shape), f'ctc_post_band: out.{n}'
+    if workspace is None:
+        workspace = torch.empty(max(ctc_post_band_workspace_bytes(P, T), 8), device=dev, dtype=torch.uint8)
+    tab = lae_table_device(dev)
+    a = PostBandArgs()
+    a.struct_size = C.sizeof(PostBandArgs)
+    a.B, a.T, a.C, a.blank, a.max_labels, a.band_states = P, T, Cn, int(blank), ML, BW
+    a.pitch_utt, a.pitch_frame = (lp.stride(0) if P > 1 else max(lp.stride(0), T * lp.stride(1))), lp.stride(1)
+    a.log_probs, a.lens, a.targets, a.target_lens = lp.data_ptr(), 0 if ln is None else ln.data_ptr(), tg.data_ptr(), tl.data_ptr()
+    a.lae_entries, a.lae_table = TAB_ENTRIES, tab.data_ptr()
+    a.start, a.nframes, a.ok_in, a.band_base = (t.data_ptr() for t in ins)
+    a.workspace, a.workspace_bytes = workspace.data_ptr(), workspace.numel() * workspace.element_size()
+    a.frame_post, a.post_pitch = fp.data_ptr(), (fp.stride(0) if P > 1 else max(fp.stride(0), T))
+    a.label_post, a.total, a.ok = out.label_post.data_ptr(), 0 if out.total is None else out.total.data_ptr(), out.ok.data_ptr()
+    st = None
+    if star is not None:
+        st, a.star_pitch = _star_arg(star, P, T, dev, 'ctc_post_band')
+        a.star_logp = st.data_ptr()
+    with torch.cuda.device(dev):
+        _check(lib.qasr_ctc_post_band(_stream_ptr(stream), C.byref(a)), 'qasr_ctc_post_band')
+    out._keep = (lp, ln, tg, tl, ins, workspace, tab, st)
     return out
 
 

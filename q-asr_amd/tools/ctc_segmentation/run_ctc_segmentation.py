@@ -16,6 +16,11 @@ score -inf.
 (EncDecCTCModel.align_long(star_between=True)): audio the transcript does not cover - an introduction, a jingle, a skipped
 sentence - goes to the wildcards instead of being pushed onto the neighbouring utterances; the segments stay one per
 utterance.  --star_penalty is what a wildcard frame pays below the frame's best class, in nats (default 1.0, not tuned on speech).
+
+--posteriors appends one more ` | `-separated field to every utterance line: the segment's posterior, 0 .. 1 - the mean over its
+frames of the probability that the transcript, aligned anywhere inside the band, is where this alignment put it
+(EncDecCTCModel.align_long(posteriors=True), k_post_band behind k_align_band); `nan` for a lost alignment.  No threshold is
+suggested: nothing here has been tried on speech.  Without the flag the file is what it always was.
 """
 import argparse
 import glob
@@ -98,6 +103,8 @@ def main(argv=None):
                    help='a wildcard label around and between the utterances, for audio the transcript does not cover')
     p.add_argument('--star_penalty', type=float, default=None,
                    help='with --star_between: nats per frame the wildcard pays below the frame\'s best class, 0 .. 16 (default 1.0)')
+    p.add_argument('--posteriors', action='store_true',
+                   help='one more field per utterance line: the posterior of the segment, 0 .. 1 (a forward-backward pass in the band)')
     p.add_argument('--window_s', type=float, default=30.0, help='seconds of audio per window of the model (overlap: 4 s, less for short windows)')
     p.add_argument('--batch_size', type=int, default=32, help='windows per batch')
     p.add_argument('--synthetic_model', action='store_true', help='seeded random weights under the model\'s name (no checkpoint needed)')
@@ -112,6 +119,7 @@ def main(argv=None):
     if args.star_penalty is not None and not args.star_between:
         p.error('--star_penalty needs --star_between')
     star_kw = dict(star_between=True, star_penalty=1.0 if args.star_penalty is None else args.star_penalty) if args.star_between else {}
+    post_kw = dict(posteriors=True) if args.posteriors else {}
     wavs = sorted(glob.glob(os.path.join(args.data, '*.wav'))) if os.path.isdir(args.data) else [args.data]
     if not wavs or not all(w.endswith('.wav') and os.path.exists(w) for w in wavs):
         p.error(f'--data {args.data}: no wav file')
@@ -135,7 +143,7 @@ def main(argv=None):
         try:
             hyp = model.align_long(torch.from_numpy(pcm).to(args.device)[None], torch.tensor([n]).to(args.device), texts=[text],
                                    window_s=args.window_s, overlap_s=overlap_s, guard_s=overlap_s / 4, batch_size=args.batch_size,
-                                   band_states=args.band_states, sample_rate=rate, channels=ch, **star_kw)[0]
+                                   band_states=args.band_states, sample_rate=rate, channels=ch, **star_kw, **post_kw)[0]
         except ValueError as e:
             p.error(f'{path}: {e}')
         out = os.path.join(seg_dir, f'{args.window_len}_' + os.path.basename(path)[:-4] + '_segments.txt')
@@ -143,7 +151,8 @@ def main(argv=None):
             f.write(path + '\n')
             for seg, a, b in zip(hyp.segments, text, shown):
                 start, end = (-1, -1) if seg.start_s is None else (round(seg.start_s, 4), round(seg.end_s, 4))
-                f.write(f'{start} {end} {seg.score} | {a} | {b}\n')
+                tail = f" | {'nan' if seg.post is None else seg.post}" if args.posteriors else ''
+                f.write(f'{start} {end} {seg.score} | {a} | {b}{tail}\n')
         lost = sum(1 for s in hyp.segments if s.start_s is None)
         print(f'{path}: {len(text)} utterances' + (f', alignment lost ({lost})' if lost else '') + f' -> {out}')
     return 0
