@@ -683,6 +683,55 @@ typedef struct qasr_ctc_star_args {
 } qasr_ctc_star_args;
 int qasr_ctc_star(void* stream, const qasr_ctc_star_args* args);
 
+/* ---- keyword spotting: where each of K phrases occurs, and how well it matches ----------------------------------------------
+ * K keywords (label sequences, shared by all utterances) against B utterances: problem p = u * K + k.  Each keyword's CTC
+ * lattice (the states of qasr_ctc_align, s = 1 .. 2L - 1) runs over the frames with a FREE start and a FREE end: state 0 is
+ * the constant fresh start (value 0, start = the frame being entered) and the final state is 2L - 1 only.  The emission is
+ * the likelihood ratio against the frame's best class, e(t, s) = min(q(logp[u][t][lab(s)]) - q(star_logp[u][t]), 0), q =
+ * rint(x * 2^16) clamped as in the beam search, star_logp the plane of qasr_ctc_star with penalty 0.  One Viterbi row of pairs
+ * (D i64, start i32); at frame t a live final state with n = t - start + 1 <= max_span and D >= threshold_q * n is a candidate;
+ * one greedy pass in time order keeps one open hit per problem: an overlapping candidate (start <= open.end) replaces it iff
+ * its mean is strictly higher (D * n_open > D_open * n), one that does not overlap closes and emits it.  The rules are
+ * SPOT_RULES of qasr/spot.py, which k_spot (one wave per problem, no LDS, no barrier in the frame loop) follows bit for bit.
+ *   hit_start, hit_end i32 [B * K][max_hits] (inclusive frames), hit_score i64 [B * K][max_hits] (D; / 2^16 / n = nats per
+ *   frame): the first max_hits hits in time order, rows behind them 0; n_hits i32 [B * K]: every emitted hit, stored or not;
+ *   ok i32 [B * K]: 0, with no hits, for target_lens outside 1 .. min(max_labels, QASR_SPOT_MAX_LABELS), a label outside [0, C)
+ *   or equal to blank (targets are device data: the kernel checks them itself and reads nothing through a bad label).
+ *   trace_score i64 / trace_start i32 [B * K][trace_pitch] (optional, both or neither): (D, start) of the final state at every
+ *   frame < lens (dead: -2^62 / -1), 0 behind and 0 for ok = 0.
+ * No workspace; nothing is allocated and no length is read on the host, so the call can be captured.
+ * QASR_ERR_ARG with nothing launched and no output written: an unknown struct_size, a NULL among log_probs, star_logp, targets,
+ * target_lens, hit_start, hit_end, hit_score, n_hits, ok; B, T, C or K < 1, T > QASR_BAND_MAX_FRAMES, B * K above 2^31 - 1,
+ * max_labels outside 1 .. QASR_SPOT_MAX_LABELS, blank outside [0, C), star_pitch < T, pitch_frame < C, pitch_utt < T *
+ * pitch_frame, threshold_q outside QASR_SPOT_MIN_THRESHOLD_Q .. 0, max_span outside 1 .. QASR_SPOT_MAX_SPAN, max_hits < 1, one
+ * trace pointer without the other, trace_pitch < T (with a trace). */
+#define QASR_SPOT_MAX_LABELS 127
+#define QASR_SPOT_MAX_SPAN 65536
+#define QASR_SPOT_MIN_THRESHOLD_Q (-(16 << 16))
+typedef struct qasr_ctc_spot_args {
+  uint32_t struct_size;
+  int32_t B, T, C, K, max_labels, blank;
+  int32_t threshold_q;         /* fixed point, nats per frame */
+  int32_t max_span;            /* frames */
+  int32_t max_hits;            /* row pitch of the hit outputs */
+  int64_t pitch_utt, pitch_frame;   /* in floats */
+  const float* log_probs;
+  const int32_t* lens;         /* optional [B] */
+  const float* star_logp;      /* [B][star_pitch]: qasr_ctc_star with penalty 0 */
+  int64_t star_pitch;          /* in floats, >= T */
+  const int32_t* targets;      /* [K][max_labels] */
+  const int32_t* target_lens;  /* [K] */
+  int32_t* hit_start;          /* [B * K][max_hits] */
+  int32_t* hit_end;            /* [B * K][max_hits] */
+  int64_t* hit_score;          /* [B * K][max_hits] */
+  int32_t* n_hits;             /* [B * K] */
+  int32_t* ok;                 /* [B * K] */
+  int64_t* trace_score;        /* optional [B * K][trace_pitch] */
+  int32_t* trace_start;        /* optional [B * K][trace_pitch] */
+  int64_t trace_pitch;         /* in elements, >= T (with a trace) */
+} qasr_ctc_spot_args;
+int qasr_ctc_spot(void* stream, const qasr_ctc_spot_args* args);
+
 /* ---- audio at any sample rate: rational polyphase resampler and PCM ingest -----------------------------------------------
  * What AudioSegment.__init__ does on the host with librosa.core.resample when target_sr != sample_rate (parts/segment.py:
  * 57-59), as one kernel, k_resample, in front of the mel front-end: int16 PCM (mono or interleaved channels) or float32 at an

@@ -1502,6 +1502,39 @@ int qasr_ctc_star(void* stream, const qasr_ctc_star_args* a) {
   return QASR_OK;
 }
 
+// ---- keyword spotting (k_spot, qasr_spot.hip): the checks of include/qasr.h, then one launch
+int qasr_ctc_spot(void* stream, const qasr_ctc_spot_args* a) {
+  if (!a) return fail(QASR_ERR_ARG, "ctc_spot: args is NULL");
+  if (a->struct_size != sizeof(qasr_ctc_spot_args))
+    return fail(QASR_ERR_ARG, "ctc_spot: struct_size %u is not %zu", a->struct_size, sizeof(qasr_ctc_spot_args));
+  if (!a->log_probs || !a->star_logp || !a->targets || !a->target_lens)
+    return fail(QASR_ERR_ARG, "ctc_spot: log_probs, star_logp, targets and target_lens are required");
+  if (!a->hit_start || !a->hit_end || !a->hit_score || !a->n_hits || !a->ok)
+    return fail(QASR_ERR_ARG, "ctc_spot: hit_start, hit_end, hit_score, n_hits and ok are required");
+  if (a->B < 1 || a->T < 1 || a->T > QASR_BAND_MAX_FRAMES || a->C < 1 || a->K < 1)
+    return fail(QASR_ERR_ARG, "ctc_spot: B %d, T %d (1 .. %d), C %d or K %d out of range", a->B, a->T, QASR_BAND_MAX_FRAMES, a->C, a->K);
+  if ((long long)a->B * a->K > INT_MAX) return fail(QASR_ERR_ARG, "ctc_spot: B %d * K %d is above 2^31 - 1", a->B, a->K);
+  if (a->max_labels < 1 || a->max_labels > QASR_SPOT_MAX_LABELS)
+    return fail(QASR_ERR_ARG, "ctc_spot: max_labels %d is outside 1 .. %d", a->max_labels, QASR_SPOT_MAX_LABELS);
+  if (a->blank < 0 || a->blank >= a->C) return fail(QASR_ERR_ARG, "ctc_spot: blank %d is outside [0, %d)", a->blank, a->C);
+  if (a->star_pitch < a->T) return fail(QASR_ERR_ARG, "ctc_spot: star_pitch %lld < T %d", (long long)a->star_pitch, a->T);
+  if (a->pitch_frame < a->C || a->pitch_utt < (int64_t)a->T * a->pitch_frame)
+    return fail(QASR_ERR_ARG, "ctc_spot: pitch_frame %lld < C or pitch_utt %lld < T * pitch_frame", (long long)a->pitch_frame,
+                (long long)a->pitch_utt);
+  if (a->threshold_q < QASR_SPOT_MIN_THRESHOLD_Q || a->threshold_q > 0)
+    return fail(QASR_ERR_ARG, "ctc_spot: threshold_q %d is outside %d .. 0", a->threshold_q, QASR_SPOT_MIN_THRESHOLD_Q);
+  if (a->max_span < 1 || a->max_span > QASR_SPOT_MAX_SPAN)
+    return fail(QASR_ERR_ARG, "ctc_spot: max_span %d is outside 1 .. %d", a->max_span, QASR_SPOT_MAX_SPAN);
+  if (a->max_hits < 1) return fail(QASR_ERR_ARG, "ctc_spot: max_hits %d < 1", a->max_hits);
+  if (!a->trace_score != !a->trace_start) return fail(QASR_ERR_ARG, "ctc_spot: trace_score and trace_start go together");
+  if (a->trace_score && a->trace_pitch < a->T)
+    return fail(QASR_ERR_ARG, "ctc_spot: trace_pitch %lld < T %d", (long long)a->trace_pitch, a->T);
+  int rc = launch_spot((hipStream_t)stream, *a);
+  if (rc) return fail(rc, "ctc_spot: launch");
+  HIPCHK(hipGetLastError());
+  return QASR_OK;
+}
+
 // ---- polyphase resampler (k_resample, qasr_resample.hip): host-only validation of a packed table (qasr/resample.py states
 // the layout), then the checks of include/qasr.h and one launch
 static long long gcd_ll(long long a, long long b) {

@@ -187,6 +187,8 @@ size_t post_band_workspace_bytes(int P, int T);
 int launch_post_band(hipStream_t s, const qasr_ctc_post_band_args& a);
 // qasr_star.hip: the wildcard's emission plane (k_star); the arguments are checked by qasr_ctc_star
 int launch_star(hipStream_t s, const qasr_ctc_star_args& a);
+// qasr_spot.hip: keyword spotting (k_spot); the arguments are checked by qasr_ctc_spot
+int launch_spot(hipStream_t s, const qasr_ctc_spot_args& a);
 // qasr_resample.hip: rational polyphase resampler (k_resample); the arguments are checked by qasr_resample
 int launch_resample(hipStream_t s, const qasr_resample_args& a);
 // qasr_longform.hip: windows of long recordings cut (k_cut) and stitched (k_stitch); the arguments are checked by the callers

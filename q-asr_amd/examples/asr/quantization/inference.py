@@ -98,6 +98,19 @@ def main():
                         "(EncDecCTCModel.align_long(posteriors=True), k_post_band behind k_align_band): ctc_score is then the "
                         "log-likelihood inside the band, and with --star_between the line also gains \"segments\", [text, "
                         "start_s, end_s, score, post] per utterance")
+    p.add_argument("--spot_file", type=str, default=None, metavar='FILE',
+                   help="(extension, needs --spot) keywords to look for, one phrase per line (empty lines and lines that start "
+                        "with # are skipped)")
+    p.add_argument("--spot", type=str, default=None, metavar='OUT',
+                   help="(extension, needs --spot_file) keyword spotting (EncDecCTCModel.spot, k_star and k_spot behind the forward): "
+                        "OUT gets one JSON line per manifest entry - audio_filepath and hits [{keyword, start, end, score}], times "
+                        "in seconds, score the mean likelihood ratio against the frame's best class in nats per frame (0: the "
+                        "keyword is the greedy path there); hypotheses, WER and the other outputs are unchanged.  With --window_s "
+                        "the keywords are searched in the stitched windows of the whole recording (EncDecCTCModel.spot_long)")
+    p.add_argument("--spot_threshold", type=float, default=None, metavar='X',
+                   help="(extension, needs --spot) the lowest score a hit may have, -16 .. 0 nats per frame (default -1.0, untried on speech)")
+    p.add_argument("--spot_max_span_s", type=float, default=None, metavar='S',
+                   help="(extension, needs --spot) the longest hit in seconds (default 10.0, untried on speech)")
     p.add_argument("--input_rate", type=int, default=None, metavar='HZ',
                    help="(extension) every file of the manifest is 16-bit mono PCM at this rate (a telephone corpus at 8000, say): "
                         "the batches stay int16 and are resampled to the model's rate on the device (k_resample) in front of the "
@@ -152,6 +165,14 @@ def main():
         for flag in ('window_s', 'align'):
             if getattr(args, flag) is not None:
                 p.error(f'--stream_chunk_s does not go with --{flag}: a streaming session steps by chunks')
+        if args.spot is not None:
+            p.error('--stream_chunk_s does not go with --spot: keyword spotting in a streaming session is not built')
+    if (args.spot is None) != (args.spot_file is None):
+        p.error('--spot OUT and --spot_file FILE go together')
+    if (args.spot_threshold is not None or args.spot_max_span_s is not None) and args.spot is None:
+        p.error('--spot_threshold and --spot_max_span_s need --spot')
+    if args.spot_threshold is not None and not -16.0 <= args.spot_threshold <= 0.0:
+        p.error(f'--spot_threshold must be -16 .. 0, got {args.spot_threshold}')
     if args.overlap_s is not None and args.window_s is None:
         p.error('--overlap_s needs --window_s')
     if args.star_token is not None and (args.align is None or args.shuffle):
@@ -255,6 +276,12 @@ def main():
         from qasr import boost as qboost
         lm_kw['boost'] = qboost.PhraseSet(qboost.read_phrase_file(args.boost_file), asr_model.decoder.vocabulary, weight=boost_weight)
     aligned, items = [], getattr(asr_model.test_dataloader().dataset, 'items', [])
+    spotted, spot_words = [], []
+    if args.spot is not None:                                # read once for the run: the list does not change per batch
+        with open(args.spot_file, encoding='utf-8') as f:
+            spot_words = [ln.strip() for ln in f if ln.strip() and not ln.lstrip().startswith('#')]
+        if not spot_words:
+            p.error(f'--spot_file {args.spot_file} holds no keyword')
     audio_s, t0 = 0.0, time.time()
     stream_sess, n_utterances = None, 0
     for i, batch in enumerate(asr_model.test_dataloader()):
@@ -374,6 +401,22 @@ def main():
                     aligned[-1]['post'] = list(h.word_post)
                     if h.segments is not None:
                         aligned[-1]['segments'] = [[sg.text, sg.start_s, sg.end_s, sg.score, sg.post] for sg in h.segments]
+        if args.spot is not None:                            # k_star + k_spot behind the forward (with --window_s: behind k_stitch)
+            spot_kw = dict(keywords=spot_words, threshold=-1.0 if args.spot_threshold is None else args.spot_threshold,
+                           max_span_s=10.0 if args.spot_max_span_s is None else args.spot_max_span_s)
+            try:
+                if args.window_s is not None:
+                    overlap_s = 4.0 if args.overlap_s is None else args.overlap_s
+                    found = asr_model.spot_long(signal, batch[1], window_s=args.window_s, overlap_s=overlap_s,
+                                                guard_s=min(1.0, overlap_s / 4), batch_size=args.batch_size, **spot_kw, **rate_kw)
+                else:
+                    found = asr_model.spot(input_signal=signal, input_signal_length=batch[1], **spot_kw, **rate_kw)
+            except ValueError as e:
+                p.error(f'--spot: {e}')
+            for row in found:
+                k = len(spotted)
+                spotted.append(dict(audio_filepath=items[k][0] if not args.shuffle and k < len(items) else None,
+                                    hits=[dict(keyword=h.keyword, start=h.start_s, end=h.end_s, score=h.score) for h in row]))
         for row in batch[2].cpu().numpy():
             refs.append(''.join(labels_map[c] for c in row))
         audio_s += float(batch[1].sum()) / float(args.input_rate or 16000)
@@ -409,6 +452,12 @@ def main():
                 rec = {k: (None if isinstance(v, float) and v == float('-inf') else v) for k, v in rec.items()}
                 f.write(json.dumps(rec, ensure_ascii=False) + '\n')
         print(f'aligned {len(aligned)} transcripts ({sum(1 for r in aligned if r["words"])} with word times) -> {args.align}')
+    if args.spot:
+        import json
+        with open(args.spot, 'w', encoding='utf-8') as f:
+            for rec in spotted:
+                f.write(json.dumps(rec, ensure_ascii=False) + '\n')
+        print(f'spotted {sum(len(r["hits"]) for r in spotted)} hits of {len(spot_words)} keywords in {len(spotted)} recordings -> {args.spot}')
     print(f'RTFx (incl. host data loading): {audio_s / max(wall, 1e-9):.1f}  ({audio_s:.1f} s audio in {wall:.2f} s)')
 
 

@@ -1369,6 +1369,121 @@ class EncDecCTCModel(nn.Module):
                     seg.post = float(pr[a:b].mean())
         return hyps
 
+    def _spot_args(self, who, keywords, labels, threshold, max_span_s, max_hits):
+        """The keyword list of spot / spot_long, refused by name before anything runs: (the keywords as given, targets int32
+        [K, ML], target_lens int32 [K], threshold, max_span in frames, max_hits)"""
+        from qasr import spot as qspot
+        if (keywords is None) == (labels is None):
+            raise ValueError(f'{who}: give exactly one of keywords and labels')
+        vocab = list(self.decoder.vocabulary)
+        blank = len(vocab)
+        given = list(keywords if keywords is not None else labels)
+        if not given:
+            raise ValueError(f'{who}: the keyword list is empty')
+        if keywords is not None:
+            from nemo.collections.asr.parts import parsers
+            parser = parsers.make_parser(labels=vocab, name='en', unk_id=-1, blank_id=-1, do_normalize=True)
+            rows = []
+            for i, text in enumerate(given):
+                ids = parser(text) if isinstance(text, str) else None
+                if ids is None:
+                    raise ValueError(f'{who}: keyword {i} is rejected by the parser')
+                rows.append([int(c) for c in ids])
+        else:
+            rows = [[int(c) for c in r] for r in given]
+            given = [tuple(r) for r in rows]
+        for i, ids in enumerate(rows):
+            if not ids:
+                raise ValueError(f'{who}: keyword {i} is empty')
+            if len(ids) > qspot.MAX_LABELS:
+                raise ValueError(f'{who}: keyword {i} has {len(ids)} labels, at most {qspot.MAX_LABELS} can be spotted')
+            if any(not 0 <= c < blank for c in ids):
+                raise ValueError(f'{who}: keyword {i} holds a label outside the vocabulary of {blank} labels')
+        qspot.check_threshold(threshold, who)
+        try:
+            span = int(round(float(max_span_s) / self.seconds_per_frame()))
+        except (TypeError, ValueError, OverflowError):
+            span = 0
+        if not 1 <= span <= qspot.MAX_SPAN:
+            raise ValueError(f'{who}: max_span_s {max_span_s!r} is {span} frames, outside 1 .. {qspot.MAX_SPAN}')
+        if int(max_hits) < 1:
+            raise ValueError(f'{who}: max_hits must be at least 1, got {max_hits!r}')
+        tg = np.full((len(rows), max(len(r) for r in rows)), blank, dtype=np.int32)
+        for i, ids in enumerate(rows):
+            tg[i, :len(ids)] = ids
+        return given, tg, np.array([len(r) for r in rows], dtype=np.int32), float(threshold), span, int(max_hits)
+
+    def _spot_rows(self, log_probs, lens, tg, tl, threshold, span, max_hits):
+        """k_star (penalty 0) and k_spot on the current stream for cuda rows, the NumPy twins otherwise: a qasr.spot.SpotResult"""
+        from qasr import align as qalign, spot as qspot
+        blank = len(self.decoder.vocabulary)
+        if log_probs.is_cuda:
+            from qasr import engine as qengine
+            lp = log_probs.float()
+            plane = qengine.ctc_star(lp, lens, 0.0)
+            return qengine.ctc_spot(lp, lens, plane, torch.from_numpy(tg).to(lp.device), torch.from_numpy(tl).to(lp.device), blank,
+                                    threshold, span, max_hits)
+        lp, ln = log_probs.float().numpy(), lens.numpy()
+        return qspot.spot_host(lp, ln, qalign.star_host(lp, ln, 0.0), tg, tl, blank, qspot.check_threshold(threshold, 'spot'), span,
+                               max_hits)
+
+    @torch.no_grad()
+    def spot(self, input_signal=None, input_signal_length=None, processed_signal=None, processed_signal_length=None,
+             keywords=None, labels=None, threshold=-1.0, max_span_s=10.0, max_hits=16, sample_rate=None, channels=1):
+        """Keyword spotting (an extension of the reference's API): where each of a list of phrases occurs in every utterance of
+        the batch, and how well it matches, without going through the 1-best transcript - List[List[qasr.ctc.KeywordHit]], one
+        list per utterance, sorted by start.  The signal arguments are forward()'s; exactly one of `keywords` (strings: they
+        pass through the CharParser the data layer uses, as align()'s texts do) and `labels` (one sequence of label ids per
+        keyword).  Every keyword's CTC lattice runs over the frames with a free start and a free end, scored by the likelihood
+        ratio against the frame's best class (qasr.spot.SPOT_RULES): a hit's score is the mean of that ratio over its span in
+        nats per frame, <= 0, and 0 means the keyword IS the greedy path there.  threshold: the lowest mean a hit may have,
+        -16 .. 0 nats per frame; max_span_s: the longest hit; max_hits: hits kept per keyword and utterance, the earliest first.
+        threshold = -1.0 and max_span_s = 10 are starting points, not tuned on speech.  Runs behind every path align() runs
+        behind - static engine, reserved engine, dynamic path (k_star with penalty 0, then k_spot, on the same stream), host
+        modules (the NumPy twins).  An empty list, an empty keyword, a keyword of more than 127 labels or that the parser
+        rejects, an id outside the vocabulary, a threshold outside -16 .. 0 and a max_span_s that rounds to fewer than 1 or more
+        than 65536 frames are refused by name before anything runs."""
+        from qasr import spot as qspot
+        given, tg, tl, threshold, span, max_hits = self._spot_args('spot', keywords, labels, threshold, max_span_s, max_hits)
+        input_signal, input_signal_length = self._resample_in(input_signal, input_signal_length, sample_rate, channels)
+        fwd = self._forward(input_signal, input_signal_length, processed_signal, processed_signal_length)
+        res = self._spot_rows(fwd[0], fwd[1], tg, tl, threshold, span, max_hits)
+        return qspot.to_hits(res, given, self.seconds_per_frame())
+
+    @torch.no_grad()
+    def spot_long(self, input_signal, input_signal_length, keywords=None, labels=None, window_s=30.0, overlap_s=4.0, guard_s=1.0,
+                  batch_size=32, seam='blank', threshold=-1.0, max_span_s=10.0, max_hits=16, sample_rate=None, channels=1):
+        """spot() for long recordings: input_signal [R, S] with input_signal_length samples each -> one list of
+        qasr.ctc.KeywordHit per recording, times in seconds of the recording.  The windows run as in align_long (k_cut, batches
+        of batch_size through the reserved engine with log-probabilities, k_stitch with the log-probability rows as a plane);
+        then one k_star launch and one k_spot launch cover the stitched rows of every recording, so a keyword that straddles a
+        seam is scored over the stitched frames like any other.  CPU inputs run the NumPy twins.  The keyword arguments and
+        their refusals are spot()'s, the window arguments and theirs align_long's."""
+        from qasr import engine as qengine, spot as qspot
+        if input_signal is None or input_signal_length is None:
+            raise ValueError('spot_long: input_signal and input_signal_length are required')
+        if seam not in ('blank', 'middle'):
+            raise ValueError(f"spot_long: seam must be 'blank' or 'middle', got {seam!r}")
+        batch_size = int(batch_size)
+        if batch_size < 1:
+            raise ValueError(f'spot_long: batch_size must be at least 1, got {batch_size}')
+        given, tg, tl, threshold, span, max_hits = self._spot_args('spot_long', keywords, labels, threshold, max_span_s, max_hits)
+        signal, length = self._resample_in(input_signal, input_signal_length, sample_rate, channels)
+        if signal.dim() != 2:
+            raise ValueError(f'spot_long: input_signal must be [R, S], got {tuple(signal.shape)}')
+        signal = signal.float()
+        lens_host = length.detach().cpu().long().clamp(max=signal.shape[1])
+        plan = self._long_plan(lens_host.numpy(), window_s, overlap_s, guard_s)      # refuses its arguments by name
+        blank = len(self.decoder.vocabulary)
+        if plan.Wn == plan.R:                # no recording is longer than a window: nothing is cut
+            windows, wlens = signal, lens_host.to(signal.device)
+        else:
+            windows, wlens = qengine.longform_cut(signal, lens_host.to(signal.device), plan)
+        toks, fs, enc, planes = self._long_windows(plan, windows, wlens, length.dtype, batch_size, 'logp')
+        out, total, _ = qengine.longform_stitch(plan, enc, toks, fs, planes, blank, seam)
+        res = self._spot_rows(out[2], total, tg, tl, threshold, span, max_hits)
+        return qspot.to_hits(res, given, self.seconds_per_frame())
+
     @staticmethod
     def _frame_scores(log_probs, tokens):
         return log_probs.float().gather(2, tokens.long().unsqueeze(-1)).squeeze(-1)

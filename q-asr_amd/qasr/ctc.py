@@ -41,6 +41,20 @@ class Segment:
 
 
 @dataclass
+class KeywordHit:
+    """One occurrence of a keyword (EncDecCTCModel.spot / spot_long; qasr.spot.SPOT_RULES): keyword as it was given (the string,
+    or the label ids), index: its position in the keyword list, start_s / end_s: from the start of its first frame to the end of
+    its last, in seconds, frames: the span in frames, score: the mean over the span of the likelihood ratio against the frame's
+    best class, in nats per frame, <= 0 - 0 means the keyword is the greedy path over its span."""
+    keyword: object
+    index: int
+    start_s: float
+    end_s: float
+    score: float
+    frames: int
+
+
+@dataclass
 class StreamUpdate:
     """What one step of a streaming session (EncDecCTCModel.stream) made final for one stream: the labels whose runs closed,
     their text, start / end times in seconds of the stream and confidences (best frame log-probability of each run), and

@@ -19,7 +19,7 @@ SYMBOLS = ['qasr_blob_check', 'qasr_engine_create', 'qasr_engine_create_ex', 'qa
            'qasr_dyn_quant_in', 'qasr_dyn_conv_params', 'qasr_sep_layer', 'qasr_quantile2', 'qasr_quantile_workspace_bytes', 'qasr_debug_prof',
            'qasr_debug_timeline', 'qasr_ctc_collapse', 'qasr_engine_attach_ctc', 'qasr_ctc_topn', 'qasr_ctc_beam_workspace_bytes', 'qasr_ctc_beam',
            'qasr_lm_check', 'qasr_ctc_beam_lm', 'qasr_boost_check', 'qasr_ctc_beam_boost', 'qasr_ctc_align_workspace_bytes', 'qasr_ctc_align',
-           'qasr_ctc_align_band_workspace_bytes', 'qasr_ctc_align_band', 'qasr_ctc_star', 'qasr_ctc_post_workspace_bytes', 'qasr_ctc_post',
+           'qasr_ctc_align_band_workspace_bytes', 'qasr_ctc_align_band', 'qasr_ctc_star', 'qasr_ctc_spot', 'qasr_ctc_post_workspace_bytes', 'qasr_ctc_post',
            'qasr_ctc_post_band_workspace_bytes', 'qasr_ctc_post_band',
            'qasr_engine_reserve', 'qasr_engine_forward_ragged', 'qasr_engine_forward_ragged_audio', 'qasr_engine_ragged_stats',
            'qasr_ragged_bucket_frames', 'qasr_ragged_envelope_frames',
@@ -179,6 +179,8 @@ def load_library():
         lib.qasr_ctc_align_band_workspace_bytes.restype = sz
     if hasattr(lib, 'qasr_ctc_star'):           # (likewise)
         lib.qasr_ctc_star.argtypes = [vp, C.POINTER(StarArgs)]
+    if hasattr(lib, 'qasr_ctc_spot'):           # (likewise)
+        lib.qasr_ctc_spot.argtypes = [vp, C.POINTER(SpotArgs)]
     if hasattr(lib, 'qasr_ctc_post'):           # (likewise)
         lib.qasr_ctc_post.argtypes = [vp, C.POINTER(PostArgs)]
         lib.qasr_ctc_post_workspace_bytes.argtypes = [i32, i32]
@@ -638,6 +640,85 @@ def ctc_star(log_probs, lens, penalty, out=None, stream=None):
     a.star, a.star_pitch = out.data_ptr(), (out.stride(0) if B > 1 else max(out.stride(0), T))
     with torch.cuda.device(dev):
         _check(lib.qasr_ctc_star(_stream_ptr(stream), C.byref(a)), 'qasr_ctc_star')
+    return out
+
+
+class SpotArgs(C.Structure):
+    """qasr_ctc_spot_args (include/qasr.h)"""
+    _fields_ = ([('struct_size', C.c_uint32)] +
+                [(n, C.c_int32) for n in ('B', 'T', 'C', 'K', 'max_labels', 'blank', 'threshold_q', 'max_span', 'max_hits')] +
+                [('pitch_utt', C.c_int64), ('pitch_frame', C.c_int64), ('log_probs', C.c_void_p), ('lens', C.c_void_p),
+                 ('star_logp', C.c_void_p), ('star_pitch', C.c_int64)] +
+                [(n, C.c_void_p) for n in ('targets', 'target_lens', 'hit_start', 'hit_end', 'hit_score', 'n_hits', 'ok',
+                                           'trace_score', 'trace_start')] +
+                [('trace_pitch', C.c_int64)])
+
+
+def ctc_spot(log_probs, lens, star, targets, target_lens, blank, threshold, max_span, max_hits=16, want_trace=False, out=None,
+             stream=None):
+    """qasr_ctc_spot: keyword spotting on the device (k_spot, one launch on the current stream, no host synchronisation); equal
+    to qasr.spot.spot_host byte for byte.  log_probs: a cuda float32 tensor [B, T, C] (any utterance / frame pitch, classes
+    contiguous); lens int32 [B] optional; star: the cuda float32 plane [B, T] of ctc_star(log_probs, lens, 0.0); targets int32
+    [K, max_labels] with target_lens int32 [K]: the keywords, shared by all utterances (problem p = u * K + k); threshold: nats
+    per frame, -16 .. 0; max_span: frames, 1 .. 65536; max_hits: hits stored per problem.  Returns a qasr.spot.SpotResult of
+    cuda tensors (want_trace: with trace_score / trace_start [B * K, T]); `out`: a caller-owned one."""
+    from .spot import MAX_LABELS, SpotResult, check_max_span, check_threshold
+    lib = load_library()
+    assert log_probs.is_cuda and log_probs.dim() == 3 and log_probs.dtype == torch.float32, \
+        'ctc_spot: log_probs must be a cuda float32 tensor [B, T, C]'
+    thr_q = check_threshold(threshold, 'ctc_spot')
+    span = check_max_span(max_span, 'ctc_spot')
+    MH = int(max_hits)
+    if MH < 1:
+        raise ValueError(f'ctc_spot: max_hits must be at least 1, got {max_hits!r}')
+    dev = log_probs.device
+    lp = log_probs if log_probs.stride(2) == 1 or log_probs.shape[2] == 1 else log_probs.contiguous()
+    ln = None if lens is None else lens.to(device=dev, dtype=torch.int32).contiguous()
+    B, T, Cn = lp.shape
+    assert targets.dim() == 2 and target_lens.dim() == 1, 'ctc_spot: targets must be [K, max_labels], target_lens [K]'
+    tg = targets.to(device=dev, dtype=torch.int32).contiguous()
+    tl = target_lens.to(device=dev, dtype=torch.int32).contiguous()
+    K, ML = tg.shape
+    if not 1 <= ML <= MAX_LABELS:                                   # refused here: the kernel holds at most this many labels
+        raise ValueError(f'ctc_spot: max_labels (the row pitch of targets) must be 1 .. {MAX_LABELS}, got {ML}')
+    if tl.shape[0] != K or K < 1:
+        raise ValueError(f'ctc_spot: {K} target rows but {tl.shape[0]} lengths')
+    P = B * K
+    if out is None:
+        i32 = dict(device=dev, dtype=torch.int32)
+        i64 = dict(device=dev, dtype=torch.int64)
+        out = SpotResult(torch.empty(P, MH, **i32), torch.empty(P, MH, **i32), torch.empty(P, MH, **i64), torch.empty(P, **i32),
+                         torch.empty(P, **i32), torch.empty(P, T, **i64) if want_trace else None,
+                         torch.empty(P, T, **i32) if want_trace else None, K)
+    for n, dt, shape in (('hit_start', torch.int32, (P, MH)), ('hit_end', torch.int32, (P, MH)), ('hit_score', torch.int64, (P, MH)),
+                         ('n_hits', torch.int32, (P,)), ('ok', torch.int32, (P,))):
+        t = getattr(out, n)
+        assert t is not None and t.is_cuda and t.is_contiguous() and t.dtype == dt and tuple(t.shape) == shape, f'ctc_spot: out.{n}'
+    assert (out.trace_score is None) == (out.trace_start is None), 'ctc_spot: out.trace_score and out.trace_start go together'
+    tpitch = 0
+    if out.trace_score is not None:
+        ts, tb = out.trace_score, out.trace_start
+        assert ts.is_cuda and ts.dtype == torch.int64 and tuple(ts.shape) == (P, T) and (T == 1 or ts.stride(1) == 1), 'ctc_spot: out.trace_score'
+        assert tb.is_cuda and tb.dtype == torch.int32 and tuple(tb.shape) == (P, T) and (T == 1 or tb.stride(1) == 1), 'ctc_spot: out.trace_start'
+        tpitch = ts.stride(0) if P > 1 else max(ts.stride(0), T)
+        assert P == 1 or tb.stride(0) == tpitch, 'ctc_spot: the two trace planes must share one row pitch'
+    out.n_keywords = K
+    st, spitch = _star_arg(star, B, T, dev, 'ctc_spot')
+    a = SpotArgs()
+    a.struct_size = C.sizeof(SpotArgs)
+    a.B, a.T, a.C, a.K, a.max_labels, a.blank = B, T, Cn, K, ML, int(blank)
+    a.threshold_q, a.max_span, a.max_hits = thr_q, span, MH
+    a.pitch_utt, a.pitch_frame = (lp.stride(0) if B > 1 else max(lp.stride(0), T * lp.stride(1))), lp.stride(1)
+    a.log_probs, a.lens = lp.data_ptr(), 0 if ln is None else ln.data_ptr()
+    a.star_logp, a.star_pitch = st.data_ptr(), spitch
+    a.targets, a.target_lens = tg.data_ptr(), tl.data_ptr()
+    for n in ('hit_start', 'hit_end', 'hit_score', 'n_hits', 'ok', 'trace_score', 'trace_start'):
+        t = getattr(out, n)
+        setattr(a, n, 0 if t is None else t.data_ptr())
+    a.trace_pitch = tpitch
+    with torch.cuda.device(dev):
+        _check(lib.qasr_ctc_spot(_stream_ptr(stream), C.byref(a)), 'qasr_ctc_spot')
+    out._keep = (lp, ln, st, tg, tl)
     return out
 
 
