@@ -22,28 +22,21 @@
 // STAR = false instantiations take the kernel argument they always took (AlignP) and are the code they were.
 // LDS atomics: none.  Global memory sees plain vector stores.  Every loop is bounded by T, the number of states, the row
 // pitch or a constant; nothing is allocated and no length is read on the host.
+// The arithmetic (FX_NEG, fx_quantize, fx_lae, fx_key) is qasr_fixed_dev.h's; the target check, a state's label and skip rule,
+// the emission read, the back-walk's window constants and the launch ladder are qasr_lattice_dev.h's.  The back-walk itself is
+// this file's text and k_align_band's: one function for both measured 2 to 3 % slower here at 250 frames.
 #include <climits>
-#include <type_traits>
 
-#include "qasr_internal.h"
+#include "qasr_lattice_dev.h"
 
 namespace qasr {
-
-#define ALIGN_NT 256
-#define ALIGN_NEG (-(1ll << 62))
-#define ALIGN_QFLOOR (-1073741824.f)
-#define ALIGN_QCEIL (1073741824.f)
-#define ALIGN_DMAX (16ll << 16)
-#define ALIGN_TAB QASR_BEAM_TABLE_ENTRIES
-#define ALIGN_G 16                              /* byte rows (4 frames each) per back-walk window */
-#define ALIGN_WINW (8 * ALIGN_G + 4)            /* states per window row: the path descends <= 2 * 4 * G inside one window */
 
 struct AlignP {
   const float* logp;
   const int32_t* lens;          // optional [B]
   const int32_t* targets;       // [P][ML]
   const int32_t* target_lens;   // [P]
-  const uint16_t* tab;          // [ALIGN_TAB], with total
+  const uint16_t* tab;          // [FX_TAB], with total
   unsigned char* ws;            // [P][G4][pitch_s]
   int32_t* start;               // [P][ML] optional
   int32_t* nframes;             // [P][ML] optional
@@ -60,23 +53,6 @@ struct AlignPS : AlignP {       // k_align<NS, true>'s argument
   long long star_pitch;
 };
 
-__device__ __forceinline__ int align_key(int bits) { return bits ^ ((bits >> 31) & 0x7fffffff); }
-
-__device__ __forceinline__ long long align_quantize(float x) {
-  float y = x * 65536.f;
-  if (!(y >= ALIGN_QFLOOR)) y = ALIGN_QFLOOR;      // NaN and -inf take the floor
-  if (y > ALIGN_QCEIL) y = ALIGN_QCEIL;
-  return (long long)(int)rintf(y);
-}
-
-__device__ __forceinline__ long long align_lae(long long a, long long b, const uint16_t* tab) {
-  const long long m = a > b ? a : b, n = a > b ? b : a;
-  if (n == ALIGN_NEG) return m;
-  const long long d = m - n;
-  if (d >= ALIGN_DMAX) return m;
-  return m + (long long)tab[d >> 6];
-}
-
 static int align_pitch(int max_labels) { return (2 * max_labels + 1 + 3) & ~3; }
 
 size_t align_workspace_bytes(int P, int T, int max_labels) {
@@ -84,10 +60,10 @@ size_t align_workspace_bytes(int P, int T, int max_labels) {
 }
 
 template <int NS, bool STAR>
-__global__ void __launch_bounds__(ALIGN_NT) k_align(std::conditional_t<STAR, AlignPS, AlignP> p) {
-  __shared__ long long rows[2][NS * ALIGN_NT];
-  __shared__ uint16_t tab[ALIGN_TAB];
-  __shared__ unsigned char win[ALIGN_G * ALIGN_WINW];
+__global__ void __launch_bounds__(LATTICE_NT) k_align(std::conditional_t<STAR, AlignPS, AlignP> p) {
+  __shared__ long long rows[2][NS * LATTICE_NT];
+  __shared__ uint16_t tab[FX_TAB];
+  __shared__ unsigned char win[LATTICE_G * LATTICE_WINW];
   __shared__ int sh_bad, sh_s, sh_t;
   const int tid = threadIdx.x, pr = blockIdx.x, u = pr / p.K;
   const int T = p.T, C = p.C, blank = p.blank, ML = p.ML;
@@ -101,15 +77,11 @@ __global__ void __launch_bounds__(ALIGN_NT) k_align(std::conditional_t<STAR, Ali
 
   if (tid == 0) sh_bad = 0;
   if (want_total)
-    for (int i = tid; i < ALIGN_TAB; i += ALIGN_NT) tab[i] = p.tab[i];
+    for (int i = tid; i < FX_TAB; i += LATTICE_NT) tab[i] = p.tab[i];
   __syncthreads();
   // the target is device data: its length and every label are checked here, before anything is read through them
-  const bool len_ok = L >= 0 && L <= ML && L <= QASR_ALIGN_MAX_LABELS && 2 * L + 1 <= NS * ALIGN_NT;
-  if (len_ok)
-    for (int i = tid; i < L; i += ALIGN_NT) {
-      const int c = y[i];
-      if (c < 0 || c >= C + (STAR ? 1 : 0) || c == blank) sh_bad = 1;
-    }
+  const bool len_ok = L >= 0 && L <= ML && L <= QASR_ALIGN_MAX_LABELS && 2 * L + 1 <= NS * LATTICE_NT;
+  if (len_ok && lattice_check_target<STAR>(y, L, C, blank, tid, LATTICE_NT)) sh_bad = 1;
   __syncthreads();
   bool alignable = len_ok && !sh_bad && !(lim == 0 && L > 0);
   const int S = alignable ? 2 * L + 1 : 0;
@@ -118,22 +90,16 @@ __global__ void __launch_bounds__(ALIGN_NT) k_align(std::conditional_t<STAR, Ali
   bool skp[NS];
 #pragma unroll
   for (int k = 0; k < NS; ++k) {
-    const int s = tid + k * ALIGN_NT;
+    const int s = tid + k * LATTICE_NT;
     lab[k] = blank, skp[k] = false;
     if (s < S && (s & 1)) {
-      lab[k] = y[s >> 1];
-      skp[k] = s >= 3 && y[s >> 1] != y[(s >> 1) - 1];
+      const LatticeSlot sl = lattice_slot(y, s, S);
+      lab[k] = sl.label, skp[k] = sl.skip_fwd;
     }
   }
-  const float* const base = p.logp + (long long)u * p.pitch_b;
   unsigned char* const wsp = p.ws + (size_t)pr * (size_t)p.G4 * (size_t)p.pitch_s;
   const size_t pitch_s = (size_t)p.pitch_s;
-  // logp[u][t][c]; with STAR the wildcard c == C reads its plane instead (t < lim <= T <= star_pitch) and nothing at base[.. + C]
-  auto emit = [&](long long t, int c) -> float {
-    if constexpr (STAR)
-      if (c == C) return p.star[(long long)u * p.star_pitch + t];
-    return base[t * p.pitch_t + c];
-  };
+  const LatticeEmit<STAR> emit = lattice_emit<STAR>(p, u);          // logp[u][t][c], the wildcard's plane where c == C
 
   // one pass over the frames (vit: Viterbi with backpointers, else forward); returns the row that holds frame lim - 1
   auto run = [&](auto vit_tag) -> int {
@@ -142,10 +108,10 @@ __global__ void __launch_bounds__(ALIGN_NT) k_align(std::conditional_t<STAR, Ali
     unsigned acc[NS];
 #pragma unroll
     for (int k = 0; k < NS; ++k) {
-      const int s = tid + k * ALIGN_NT;
+      const int s = tid + k * LATTICE_NT;
       acc[k] = 0;
       pf[k] = s < S ? emit(0, lab[k]) : 0.f;                        // frame 0 (lim >= 1 here)
-      if (s < S) rows[0][s] = s < 2 ? align_quantize(pf[k]) : ALIGN_NEG;
+      if (s < S) rows[0][s] = s < 2 ? fx_quantize(pf[k]) : FX_NEG;
       pf[k] = (s < S && lim > 1) ? emit(1, lab[k]) : 0.f;
     }
     int cur = 0;
@@ -154,7 +120,7 @@ __global__ void __launch_bounds__(ALIGN_NT) k_align(std::conditional_t<STAR, Ali
       float nx[NS];
 #pragma unroll
       for (int k = 0; k < NS; ++k) {                                // frame t + 1's gathers, in flight across this frame
-        const int s = tid + k * ALIGN_NT;
+        const int s = tid + k * LATTICE_NT;
         nx[k] = (s < S && t + 1 < lim) ? emit(t + 1, lab[k]) : 0.f;
       }
       const long long* const R = rows[cur];
@@ -162,24 +128,24 @@ __global__ void __launch_bounds__(ALIGN_NT) k_align(std::conditional_t<STAR, Ali
       const bool flush = (t & 3) == 3 || t == lim - 1;
 #pragma unroll
       for (int k = 0; k < NS; ++k) {
-        const int s = tid + k * ALIGN_NT;
+        const int s = tid + k * LATTICE_NT;
         if (s < S) {
-          const long long q = align_quantize(pf[k]);
-          const long long a0 = R[s], a1 = s >= 1 ? R[s - 1] : ALIGN_NEG, a2 = skp[k] ? R[s - 2] : ALIGN_NEG;
+          const long long q = fx_quantize(pf[k]);
+          const long long a0 = R[s], a1 = s >= 1 ? R[s - 1] : FX_NEG, a2 = skp[k] ? R[s - 2] : FX_NEG;
           if constexpr (VIT) {
             long long best = a0;
             unsigned step = 0;
             if (a1 > best) best = a1, step = 1;
             if (a2 > best) best = a2, step = 2;
-            W[s] = best == ALIGN_NEG ? ALIGN_NEG : best + q;
+            W[s] = best == FX_NEG ? FX_NEG : best + q;
             acc[k] |= step << (2 * (t & 3));
             if (flush) {
               wsp[(size_t)(t >> 2) * pitch_s + s] = (unsigned char)acc[k];      // t >> 2 < G4, s < S <= pitch_s
               acc[k] = 0;
             }
           } else {
-            const long long x = align_lae(align_lae(a0, a1, tab), a2, tab);
-            W[s] = x == ALIGN_NEG ? ALIGN_NEG : x + q;
+            const long long x = fx_lae(fx_lae(a0, a1, tab), a2, tab);
+            W[s] = x == FX_NEG ? FX_NEG : x + q;
           }
         }
       }
@@ -192,7 +158,7 @@ __global__ void __launch_bounds__(ALIGN_NT) k_align(std::conditional_t<STAR, Ali
   };
 
   // ---- Viterbi
-  long long vf = ALIGN_NEG;
+  long long vf = FX_NEG;
   int fin = 0;
   if (alignable) {
     if (lim == 0) {
@@ -208,37 +174,37 @@ __global__ void __launch_bounds__(ALIGN_NT) k_align(std::conditional_t<STAR, Ali
         vf = a > b ? a : b;
       }
     }
-    alignable = vf != ALIGN_NEG;
+    alignable = vf != FX_NEG;
   }
   __syncthreads();                                                  // the rows have been read: their LDS is reused below
   if (!alignable) {                                                 // uniform
-    for (int i = tid; i < ML; i += ALIGN_NT) {
+    for (int i = tid; i < ML; i += LATTICE_NT) {
       if (o_start) o_start[i] = 0;
       if (o_nframes) o_nframes[i] = 0;
       if (o_score) o_score[i] = 0.f;
     }
     if (tid == 0) {
-      if (p.path_score) p.path_score[pr] = ALIGN_NEG;
-      if (p.total) p.total[pr] = ALIGN_NEG;
+      if (p.path_score) p.path_score[pr] = FX_NEG;
+      if (p.total) p.total[pr] = FX_NEG;
       p.ok[pr] = 0;
     }
     return;
   }
   // ---- back-walk: per label its first frame and frame count (L <= NS * 128 - 1: both arrays fit rows[0])
   int* const lstart = reinterpret_cast<int*>(&rows[0][0]);
-  int* const lcnt = lstart + NS * (ALIGN_NT / 2);
+  int* const lcnt = lstart + NS * (LATTICE_NT / 2);
   if (L > 0) {                                                      // (then lim > 0)
-    for (int i = tid; i < L; i += ALIGN_NT) lstart[i] = 0, lcnt[i] = 0;
+    for (int i = tid; i < L; i += LATTICE_NT) lstart[i] = 0, lcnt[i] = 0;
     if (tid == 0) sh_s = fin, sh_t = lim - 1;
     __syncthreads();
     int cur_i = -1, cnt = 0, first = 0;                             // thread 0: the label run being walked
     for (int guard = 0; guard <= p.G4; ++guard) {                   // bounded: every window consumes at least one byte row
       const int s_hi = sh_s, t_hi = sh_t;
       if (t_hi < 0) break;                                          // uniform
-      const int g_top = t_hi >> 2, g_lo = max(g_top - ALIGN_G + 1, 0), ng = g_top - g_lo + 1;
-      const int lo = max(s_hi - 8 * ALIGN_G, 0), width = s_hi - lo + 1;          // <= 8 G + 1 states, all < S
-      for (int i = tid; i < ng * ALIGN_WINW; i += ALIGN_NT) {
-        const int gi = i / ALIGN_WINW, si = i - gi * ALIGN_WINW;
+      const int g_top = t_hi >> 2, g_lo = max(g_top - LATTICE_G + 1, 0), ng = g_top - g_lo + 1;
+      const int lo = max(s_hi - 8 * LATTICE_G, 0), width = s_hi - lo + 1;        // <= 8 G + 1 states, all < S
+      for (int i = tid; i < ng * LATTICE_WINW; i += LATTICE_NT) {
+        const int gi = i / LATTICE_WINW, si = i - gi * LATTICE_WINW;
         if (si < width) win[i] = wsp[(size_t)(g_lo + gi) * pitch_s + lo + si];
       }
       __syncthreads();
@@ -254,8 +220,8 @@ __global__ void __launch_bounds__(ALIGN_NT) k_align(std::conditional_t<STAR, Ali
             ++cnt, first = t;
           }
           if (t > 0) {
-            const int at = min(max(s - lo, 0), ALIGN_WINW - 1);
-            const int step = (win[((t >> 2) - g_lo) * ALIGN_WINW + at] >> (2 * (t & 3))) & 3;
+            const int at = min(max(s - lo, 0), LATTICE_WINW - 1);
+            const int step = (win[((t >> 2) - g_lo) * LATTICE_WINW + at] >> (2 * (t & 3))) & 3;
             s = max(s - step, 0);
           }
         }
@@ -267,22 +233,19 @@ __global__ void __launch_bounds__(ALIGN_NT) k_align(std::conditional_t<STAR, Ali
     __syncthreads();
   }
   // ---- outputs: one thread per label; the score is the largest log-probability of the label inside its run
-  for (int i = tid; i < ML; i += ALIGN_NT) {
+  for (int i = tid; i < ML; i += LATTICE_NT) {
     int st = 0, n = 0;
     float sc = 0.f;
     if (i < L) {
       st = min(max(lstart[i], 0), lim - 1), n = min(max(lcnt[i], 0), lim - st);
       if (o_score && n > 0) {
-        const float* col = base + y[i];
-        long long step = p.pitch_t;
-        if constexpr (STAR)
-          if (y[i] == C) col = p.star + (long long)u * p.star_pitch, step = 1;
+        const auto col = emit.column(y[i]);
         int best = INT_MIN;
         for (int f = 0; f < n; ++f) {
-          const int key = align_key(__float_as_int(col[(long long)(st + f) * step]));
+          const int key = fx_key(__float_as_int(col.ptr[(long long)(st + f) * col.step]));
           best = key > best ? key : best;
         }
-        sc = __int_as_float(align_key(best));
+        sc = __int_as_float(fx_key(best));
       }
     }
     if (o_start) o_start[i] = st;
@@ -300,7 +263,7 @@ __global__ void __launch_bounds__(ALIGN_NT) k_align(std::conditional_t<STAR, Ali
       __syncthreads();                                              // lstart / lcnt have been read
       const int cur = run(std::false_type{});
       const long long* const R = rows[cur];
-      tot = L == 0 ? R[0] : align_lae(R[2 * L], R[2 * L - 1], tab);
+      tot = L == 0 ? R[0] : fx_lae(R[2 * L], R[2 * L - 1], tab);
     }
     if (tid == 0) p.total[pr] = tot;
   }
@@ -308,13 +271,10 @@ __global__ void __launch_bounds__(ALIGN_NT) k_align(std::conditional_t<STAR, Ali
 
 template <bool STAR>
 static void launch_align_ns(hipStream_t s, const std::conditional_t<STAR, AlignPS, AlignP>& p, int P, int states) {
-  const dim3 grid((unsigned)P), block(ALIGN_NT);
-  static_assert(2 * QASR_ALIGN_MAX_LABELS + 1 <= 17 * ALIGN_NT, "k_align<17> holds the longest target");
-  if (states <= 1 * ALIGN_NT) hipLaunchKernelGGL((k_align<1, STAR>), grid, block, 0, s, p);
-  else if (states <= 2 * ALIGN_NT) hipLaunchKernelGGL((k_align<2, STAR>), grid, block, 0, s, p);
-  else if (states <= 4 * ALIGN_NT) hipLaunchKernelGGL((k_align<4, STAR>), grid, block, 0, s, p);
-  else if (states <= 8 * ALIGN_NT) hipLaunchKernelGGL((k_align<8, STAR>), grid, block, 0, s, p);
-  else hipLaunchKernelGGL((k_align<17, STAR>), grid, block, 0, s, p);
+  static_assert(2 * QASR_ALIGN_MAX_LABELS + 1 <= 17 * LATTICE_NT, "k_align<17> holds the longest target");
+  lattice_dispatch_ns(states, [&](auto ns) {
+    hipLaunchKernelGGL((k_align<decltype(ns)::value, STAR>), dim3((unsigned)P), dim3(LATTICE_NT), 0, s, p);
+  });
 }
 
 int launch_align(hipStream_t s, const qasr_ctc_align_args& a) {

@@ -20,21 +20,16 @@
 // STAR = false instantiations take the kernel argument they always took (BandP) and are the code they were.
 // LDS atomics: none.  Global memory sees plain vector stores.  Every loop is bounded by T, L, the row pitch or a constant; nothing
 // is allocated and no length is read on the host.
+// The arithmetic (FX_NEG, fx_quantize, fx_key) is qasr_fixed_dev.h's; LATTICE_BLOCK (the 32 frames between two moves, shared with
+// k_post_band), the target check, a state's label and skip rule, the emission read, the back-walk's window constants and the
+// launch ladder are qasr_lattice_dev.h's.
 #include <climits>
-#include <type_traits>
 
-#include "qasr_internal.h"
+#include "qasr_lattice_dev.h"
 
 namespace qasr {
 
-#define BAND_NT 256
-#define BAND_NEG (-(1ll << 62))
-#define BAND_QFLOOR (-1073741824.f)
-#define BAND_QCEIL (1073741824.f)
 #define BAND_SKIP ((int)0x80000000)             /* bit 31 of a slot's label word: the state may skip the blank below it */
-#define BAND_BLOCK 32                           /* frames between two moves of the base */
-#define BAND_G 16                               /* byte rows (4 frames each) per back-walk window */
-#define BAND_WINW (8 * BAND_G + 4)              /* states per window row: the path descends <= 2 * 4 * G inside one window */
 
 struct BandP {
   const float* logp;
@@ -58,15 +53,6 @@ struct BandPS : BandP {         // k_align_band<NS, true>'s argument
   long long star_pitch;
 };
 
-__device__ __forceinline__ int band_key(int bits) { return bits ^ ((bits >> 31) & 0x7fffffff); }
-
-__device__ __forceinline__ long long band_quantize(float x) {
-  float y = x * 65536.f;
-  if (!(y >= BAND_QFLOOR)) y = BAND_QFLOOR;        // NaN and -inf take the floor
-  if (y > BAND_QCEIL) y = BAND_QCEIL;
-  return (long long)(int)rintf(y);
-}
-
 static size_t band_problem_bytes(int T, int band_states) {
   return (size_t)((T + 3) / 4) * (size_t)band_states + 4 * (size_t)T;
 }
@@ -74,13 +60,13 @@ static size_t band_problem_bytes(int T, int band_states) {
 size_t align_band_workspace_bytes(int P, int T, int band_states) { return (size_t)P * band_problem_bytes(T, band_states); }
 
 template <int NS, bool STAR>
-__global__ void __launch_bounds__(BAND_NT) k_align_band(std::conditional_t<STAR, BandPS, BandP> p) {
-  constexpr int BW = NS * BAND_NT;
+__global__ void __launch_bounds__(LATTICE_NT) k_align_band(std::conditional_t<STAR, BandPS, BandP> p) {
+  constexpr int BW = NS * LATTICE_NT;
   __shared__ long long rows[2][BW];
-  __shared__ unsigned char win[BAND_G * BAND_WINW];
-  __shared__ int wstate[4 * BAND_G];
-  __shared__ long long red_v[BAND_NT / 64];
-  __shared__ int red_s[BAND_NT / 64];
+  __shared__ unsigned char win[LATTICE_G * LATTICE_WINW];
+  __shared__ int wstate[4 * LATTICE_G];
+  __shared__ long long red_v[LATTICE_NT / 64];
+  __shared__ int red_s[LATTICE_NT / 64];
   __shared__ int sh_bad, sh_s, sh_t;
   const int tid = threadIdx.x, pr = blockIdx.x;
   const int T = p.T, C = p.C, blank = p.blank, ML = p.ML;
@@ -97,30 +83,24 @@ __global__ void __launch_bounds__(BAND_NT) k_align_band(std::conditional_t<STAR,
   __syncthreads();
   // the target is device data: its length and every label are checked here, before anything is read through them
   const bool len_ok = L >= 0 && L <= ML && L <= QASR_BAND_MAX_LABELS;
-  if (len_ok)
-    for (int i = tid; i < L; i += BAND_NT) {
-      const int c = y[i];
-      if (c < 0 || c >= C + (STAR ? 1 : 0) || c == blank) sh_bad = 1;
-    }
+  if (len_ok && lattice_check_target<STAR>(y, L, C, blank, tid, LATTICE_NT)) sh_bad = 1;
   __syncthreads();
   bool alignable = len_ok && !sh_bad && !(lim == 0 && L > 0);
   const int S = alignable ? 2 * L + 1 : 0;
   const int top = max(0, S - BW);
-  const int nblk = alignable ? (lim + BAND_BLOCK - 1) / BAND_BLOCK : 0;  // blocks that have a frame < lim
+  const int nblk = alignable ? (lim + LATTICE_BLOCK - 1) / LATTICE_BLOCK : 0;  // blocks that have a frame < lim
 
-  const float* const lp = p.logp + (long long)pr * p.pitch_b;
   unsigned char* const wsp = p.ws + (size_t)pr * ((size_t)p.G4 * BW + 4 * (size_t)T);
   int* const wst = reinterpret_cast<int*>(wsp + (size_t)p.G4 * BW);       // the path's state per frame (G4 * BW is a multiple of 4)
-  // lp[at], at = the place of logp[pr][t][c]; with STAR the wildcard c == C reads its plane instead (t < lim <= T <= star_pitch)
-  // and nothing at lp[.. + C]
-  auto emit = [&](long long at, int t, int c) -> float {
-    if constexpr (STAR)
-      if (c == C) return p.star[(long long)pr * p.star_pitch + t];
-    return lp[at];
-  };
+  const LatticeEmit<STAR> emit = lattice_emit<STAR>(p, pr);         // logp[pr][t][c], the wildcard's plane where c == C
 
   // ---- Viterbi inside the band
-  long long vf = BAND_NEG;
+  // a slot's label word: the odd state s < S carries y[s >> 1], bit 31 says that it may skip the blank below it
+  auto label_word = [&](int s) -> int {
+    const LatticeSlot sl = lattice_slot(y, s, S);
+    return sl.skip_fwd ? sl.label | BAND_SKIP : sl.label;
+  };
+  long long vf = FX_NEG;
   int fin = 0;
   if (alignable && lim == 0) vf = 0;                                // L == 0: the empty path
   if (alignable && lim > 0) {
@@ -129,28 +109,24 @@ __global__ void __launch_bounds__(BAND_NT) k_align_band(std::conditional_t<STAR,
     unsigned acc[NS];
 #pragma unroll
     for (int k = 0; k < NS; ++k) {
-      const int s = tid + k * BAND_NT;                              // base 0
-      st[k] = s, lab[k] = blank, acc[k] = 0;
-      if (s < S && (s & 1)) {
-        lab[k] = y[s >> 1];
-        if (s >= 3 && y[s >> 1] != y[(s >> 1) - 1]) lab[k] |= BAND_SKIP;
-      }
-      pf[k] = s < S ? emit(lab[k] & ~BAND_SKIP, 0, lab[k] & ~BAND_SKIP) : 0.f;           // frame 0
-      rows[0][s] = (s < S && s < 2) ? band_quantize(pf[k]) : BAND_NEG;
-      pf[k] = (s < S && lim > 1) ? emit(p.pitch_t + (lab[k] & ~BAND_SKIP), 1, lab[k] & ~BAND_SKIP) : 0.f;
+      const int s = tid + k * LATTICE_NT;                           // base 0
+      st[k] = s, lab[k] = (s < S && (s & 1)) ? label_word(s) : blank, acc[k] = 0;
+      pf[k] = s < S ? emit(0, lab[k] & ~BAND_SKIP) : 0.f;           // frame 0
+      rows[0][s] = (s < S && s < 2) ? fx_quantize(pf[k]) : FX_NEG;
+      pf[k] = (s < S && lim > 1) ? emit(1, lab[k] & ~BAND_SKIP) : 0.f;
     }
     if (tid == 0 && o_base) o_base[0] = 0;
     int cur = 0, base = 0;
     __syncthreads();
     for (int t = 1; t < lim; ++t) {
-      if ((t & (BAND_BLOCK - 1)) == 0) {                            // uniform: where should the band be?
+      if ((t & (LATTICE_BLOCK - 1)) == 0) {                         // uniform: where should the band be?
         if (top > 0) {                                              // (S <= BW: the base never moves)
           const long long* const R = rows[cur];
-          long long bv = BAND_NEG;
+          long long bv = FX_NEG;
           int bs = INT_MAX;
 #pragma unroll
           for (int k = 0; k < NS; ++k) {                            // (top > 0: every slot holds a state < S)
-            const long long v = R[tid + k * BAND_NT];
+            const long long v = R[tid + k * LATTICE_NT];
             if (v > bv || (v == bv && st[k] < bs)) bv = v, bs = st[k];
           }
 #pragma unroll
@@ -163,9 +139,9 @@ __global__ void __launch_bounds__(BAND_NT) k_align_band(std::conditional_t<STAR,
           __syncthreads();
           bv = red_v[0], bs = red_s[0];
 #pragma unroll
-          for (int w = 1; w < BAND_NT / 64; ++w)
+          for (int w = 1; w < LATTICE_NT / 64; ++w)
             if (red_v[w] > bv || (red_v[w] == bv && red_s[w] < bs)) bv = red_v[w], bs = red_s[w];
-          if (bv != BAND_NEG) {
+          if (bv != FX_NEG) {
             const int nb = max(base, min(bs - BW / 2, top));        // nb - base < BW / 2: a slot is replaced at most once
             if (nb > base) {
               long long* const Rw = rows[cur];
@@ -173,13 +149,9 @@ __global__ void __launch_bounds__(BAND_NT) k_align_band(std::conditional_t<STAR,
               for (int k = 0; k < NS; ++k)
                 if (st[k] < nb) {                                   // dropped: state st + BW enters (nb + BW <= S)
                   const int s = st[k] + BW;
-                  st[k] = s, lab[k] = blank;
-                  if (s & 1) {
-                    lab[k] = y[s >> 1];
-                    if (y[s >> 1] != y[(s >> 1) - 1]) lab[k] |= BAND_SKIP;      // s >= BW + 1 > 3
-                  }
-                  Rw[tid + k * BAND_NT] = BAND_NEG;
-                  pf[k] = emit((long long)t * p.pitch_t + (lab[k] & ~BAND_SKIP), t, lab[k] & ~BAND_SKIP);   // this frame again, with the new label
+                  st[k] = s, lab[k] = (s & 1) ? label_word(s) : blank;
+                  Rw[tid + k * LATTICE_NT] = FX_NEG;
+                  pf[k] = emit(t, lab[k] & ~BAND_SKIP);             // this frame again, with the new label
                 }
               base = nb;
             }
@@ -191,23 +163,23 @@ __global__ void __launch_bounds__(BAND_NT) k_align_band(std::conditional_t<STAR,
       float nx[NS];
 #pragma unroll
       for (int k = 0; k < NS; ++k)                                  // frame t + 1's gathers, in flight across this frame
-        nx[k] = (st[k] < S && t + 1 < lim) ? emit((long long)(t + 1) * p.pitch_t + (lab[k] & ~BAND_SKIP), t + 1, lab[k] & ~BAND_SKIP) : 0.f;
+        nx[k] = (st[k] < S && t + 1 < lim) ? emit(t + 1, lab[k] & ~BAND_SKIP) : 0.f;
       const long long* const R = rows[cur];
       long long* const W = rows[cur ^ 1];
       const bool flush = (t & 3) == 3 || t == lim - 1;
 #pragma unroll
       for (int k = 0; k < NS; ++k) {
-        const int i0 = tid + k * BAND_NT;                           // s % BW
+        const int i0 = tid + k * LATTICE_NT;                        // s % BW
         const int s = st[k];
         if (s < S) {
           const int i1 = i0 >= 1 ? i0 - 1 : i0 - 1 + BW, i2 = i0 >= 2 ? i0 - 2 : i0 - 2 + BW;
-          const long long q = band_quantize(pf[k]);
-          const long long a0 = R[i0], a1 = s - 1 >= base ? R[i1] : BAND_NEG, a2 = (lab[k] < 0 && s - 2 >= base) ? R[i2] : BAND_NEG;
+          const long long q = fx_quantize(pf[k]);
+          const long long a0 = R[i0], a1 = s - 1 >= base ? R[i1] : FX_NEG, a2 = (lab[k] < 0 && s - 2 >= base) ? R[i2] : FX_NEG;
           long long best = a0;
           unsigned step = 0;
           if (a1 > best) best = a1, step = 1;
           if (a2 > best) best = a2, step = 2;
-          W[i0] = best == BAND_NEG ? BAND_NEG : best + q;
+          W[i0] = best == FX_NEG ? FX_NEG : best + q;
           acc[k] |= step << (2 * (t & 3));
           if (flush) {
             wsp[(size_t)(t >> 2) * BW + i0] = (unsigned char)acc[k];      // t >> 2 < G4, i0 < BW
@@ -225,26 +197,26 @@ __global__ void __launch_bounds__(BAND_NT) k_align_band(std::conditional_t<STAR,
       vf = R[0];
     } else {                                                        // an end state outside the last band is NEG
       const int s2 = 2 * L, s1 = 2 * L - 1;
-      const long long a = (s2 >= base && s2 < base + BW) ? R[s2 % BW] : BAND_NEG;
-      const long long b = (s1 >= base && s1 < base + BW) ? R[s1 % BW] : BAND_NEG;
+      const long long a = (s2 >= base && s2 < base + BW) ? R[s2 % BW] : FX_NEG;
+      const long long b = (s1 >= base && s1 < base + BW) ? R[s1 % BW] : FX_NEG;
       fin = a > b ? s2 : s1;
       vf = a > b ? a : b;
     }
   }
-  for (int i = nblk + tid; i < p.NB; i += BAND_NT)
+  for (int i = nblk + tid; i < p.NB; i += LATTICE_NT)
     if (o_base) o_base[i] = 0;
-  alignable = alignable && vf != BAND_NEG;
+  alignable = alignable && vf != FX_NEG;
   __syncthreads();
   if (!alignable) {                                                 // uniform
-    for (int i = tid; i < ML; i += BAND_NT) {
+    for (int i = tid; i < ML; i += LATTICE_NT) {
       if (o_start) o_start[i] = 0;
       if (o_nframes) o_nframes[i] = 0;
       if (o_score) o_score[i] = 0.f;
     }
     if (o_flp)
-      for (int t = tid; t < T; t += BAND_NT) o_flp[t] = 0.f;
+      for (int t = tid; t < T; t += LATTICE_NT) o_flp[t] = 0.f;
     if (tid == 0) {
-      if (p.path_score) p.path_score[pr] = BAND_NEG;
+      if (p.path_score) p.path_score[pr] = FX_NEG;
       p.ok[pr] = 0;
     }
     return;
@@ -256,10 +228,10 @@ __global__ void __launch_bounds__(BAND_NT) k_align_band(std::conditional_t<STAR,
     for (int guard = 0; guard <= p.G4; ++guard) {                   // bounded: every window consumes at least one byte row
       const int s_hi = sh_s, t_hi = sh_t;
       if (t_hi < 0) break;                                          // uniform
-      const int g_top = t_hi >> 2, g_lo = max(g_top - BAND_G + 1, 0), ng = g_top - g_lo + 1;
-      const int lo = max(s_hi - 8 * BAND_G, 0), width = s_hi - lo + 1;           // <= 8 G + 1 states
-      for (int i = tid; i < ng * BAND_WINW; i += BAND_NT) {
-        const int gi = i / BAND_WINW, si = i - gi * BAND_WINW;
+      const int g_top = t_hi >> 2, g_lo = max(g_top - LATTICE_G + 1, 0), ng = g_top - g_lo + 1;
+      const int lo = max(s_hi - 8 * LATTICE_G, 0), width = s_hi - lo + 1;        // <= 8 G + 1 states
+      for (int i = tid; i < ng * LATTICE_WINW; i += LATTICE_NT) {
+        const int gi = i / LATTICE_WINW, si = i - gi * LATTICE_WINW;
         if (si < width) win[i] = wsp[(size_t)(g_lo + gi) * BW + (lo + si) % BW];
       }
       __syncthreads();
@@ -268,8 +240,8 @@ __global__ void __launch_bounds__(BAND_NT) k_align_band(std::conditional_t<STAR,
         for (int t = t_hi; t >= 4 * g_lo; --t) {
           wstate[t - 4 * g_lo] = s;                                 // t - 4 g_lo < 4 G
           if (t > 0) {
-            const int at = min(max(s - lo, 0), BAND_WINW - 1);
-            const int step = (win[((t >> 2) - g_lo) * BAND_WINW + at] >> (2 * (t & 3))) & 3;
+            const int at = min(max(s - lo, 0), LATTICE_WINW - 1);
+            const int step = (win[((t >> 2) - g_lo) * LATTICE_WINW + at] >> (2 * (t & 3))) & 3;
             s = max(s - step, 0);
           }
         }
@@ -281,12 +253,12 @@ __global__ void __launch_bounds__(BAND_NT) k_align_band(std::conditional_t<STAR,
     }
   }
   // ---- outputs: one thread per frame; the first frame of a label's run writes the label's row entries
-  for (int i = L + tid; i < ML; i += BAND_NT) {                     // the tails (every label < L has exactly one run)
+  for (int i = L + tid; i < ML; i += LATTICE_NT) {                  // the tails (every label < L has exactly one run)
     if (o_start) o_start[i] = 0;
     if (o_nframes) o_nframes[i] = 0;
     if (o_score) o_score[i] = 0.f;
   }
-  for (int t = tid; t < T; t += BAND_NT) {
+  for (int t = tid; t < T; t += LATTICE_NT) {
     if (t >= lim) {
       if (o_flp) o_flp[t] = 0.f;
       continue;
@@ -294,23 +266,20 @@ __global__ void __launch_bounds__(BAND_NT) k_align_band(std::conditional_t<STAR,
     const int s = min(max(wst[t], 0), S - 1);
     const int i = s >> 1;                                           // (odd s: i < L)
     const int c = (s & 1) ? y[i] : blank;
-    const float* col = lp + c;
-    long long step = p.pitch_t;
-    if constexpr (STAR)
-      if (c == C) col = p.star + (long long)pr * p.star_pitch, step = 1;
-    if (o_flp) o_flp[t] = col[(long long)t * step];
+    const auto col = emit.column(c);
+    if (o_flp) o_flp[t] = col.ptr[(long long)t * col.step];
     if ((s & 1) && (t == 0 || wst[t - 1] != s)) {
       int n = 0, best = INT_MIN;
       for (int f = t; f < lim && wst[f] == s; ++f) {
         ++n;
         if (o_score) {
-          const int key = band_key(__float_as_int(col[(long long)f * step]));
+          const int key = fx_key(__float_as_int(col.ptr[(long long)f * col.step]));
           best = key > best ? key : best;
         }
       }
       if (o_start) o_start[i] = t;
       if (o_nframes) o_nframes[i] = n;
-      if (o_score) o_score[i] = __int_as_float(band_key(best));
+      if (o_score) o_score[i] = __int_as_float(fx_key(best));
     }
   }
   if (tid == 0) {
@@ -321,12 +290,9 @@ __global__ void __launch_bounds__(BAND_NT) k_align_band(std::conditional_t<STAR,
 
 template <bool STAR>
 static int launch_align_band_ns(hipStream_t s, const std::conditional_t<STAR, BandPS, BandP>& p, int B, int band_states) {
-  const dim3 grid((unsigned)B), block(BAND_NT);
-  if (band_states == 1 * BAND_NT) hipLaunchKernelGGL((k_align_band<1, STAR>), grid, block, 0, s, p);
-  else if (band_states == 4 * BAND_NT) hipLaunchKernelGGL((k_align_band<4, STAR>), grid, block, 0, s, p);
-  else if (band_states == 17 * BAND_NT) hipLaunchKernelGGL((k_align_band<17, STAR>), grid, block, 0, s, p);
-  else return QASR_ERR_ARG;
-  return QASR_OK;
+  return lattice_dispatch_band_ns(band_states, [&](auto ns) {
+    hipLaunchKernelGGL((k_align_band<decltype(ns)::value, STAR>), dim3((unsigned)B), dim3(LATTICE_NT), 0, s, p);
+  });
 }
 
 int launch_align_band(hipStream_t s, const qasr_ctc_align_band_args& a) {
@@ -337,7 +303,7 @@ int launch_align_band(hipStream_t s, const qasr_ctc_align_band_args& a) {
   p.path_score = (long long*)a.path_score, p.frame_logp = a.frame_logp, p.band_base = a.band_base, p.ok = a.ok;
   p.pitch_b = a.pitch_utt, p.pitch_t = a.pitch_frame;
   p.T = a.T, p.C = a.C, p.blank = a.blank, p.ML = a.max_labels;
-  p.G4 = (a.T + 3) / 4, p.NB = (a.T + BAND_BLOCK - 1) / BAND_BLOCK;
+  p.G4 = (a.T + 3) / 4, p.NB = (a.T + LATTICE_BLOCK - 1) / LATTICE_BLOCK;
   p.star = a.star_logp, p.star_pitch = a.star_pitch;
   if (a.star_logp) return launch_align_band_ns<true>(s, p, a.B, a.band_states);
   return launch_align_band_ns<false>(s, static_cast<const BandP&>(p), a.B, a.band_states);

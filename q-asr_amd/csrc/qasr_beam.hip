@@ -24,18 +24,7 @@
 
 namespace qasr {
 
-#define BEAM_QFLOOR (-1073741824.f)
-#define BEAM_QCEIL (1073741824.f)
 #define BEAM_EMPTY_Q INT_MIN
-
-__device__ __forceinline__ int beam_key(int bits) { return bits ^ ((bits >> 31) & 0x7fffffff); }
-
-__device__ __forceinline__ int beam_quantize(float x) {
-  float y = x * 65536.f;
-  if (!(y >= BEAM_QFLOOR)) y = BEAM_QFLOOR;      // NaN and -inf take the floor
-  if (y > BEAM_QCEIL) y = BEAM_QCEIL;
-  return (int)rintf(y);
-}
 
 // ------------------------------------------------------------------------------------------------------------ k_topn
 struct TopnP {
@@ -78,7 +67,7 @@ __global__ void __launch_bounds__(64) k_topn(TopnP p) {
       for (int j = 0; j < TOPN_UNROLL; ++j) bits[j] = c0 + j * 64 < C ? __float_as_int(row[c0 + j * 64]) : 0;
 #pragma unroll
       for (int j = 0; j < TOPN_UNROLL; ++j) {
-        const unsigned key = (unsigned)beam_key(bits[j]) ^ 0x80000000u;
+        const unsigned key = (unsigned)fx_key(bits[j]) ^ 0x80000000u;
         if (c0 + j * 64 < C && (pass == 3 || (key >> (shift + 8)) == prefix)) atomicAdd(&sm_hist[(key >> shift) & 255u], 1u);
       }
     }
@@ -121,7 +110,7 @@ __global__ void __launch_bounds__(64) k_topn(TopnP p) {
 #pragma unroll
     for (int j = 0; j < TOPN_UNROLL; ++j) {                      // class order: chunk by chunk, lane by lane
       const int c = cb + j * 64 + lane;
-      const unsigned key = (unsigned)beam_key(bits[j]) ^ 0x80000000u;
+      const unsigned key = (unsigned)fx_key(bits[j]) ^ 0x80000000u;
       const bool gt = c < C && key > prefix, eq = c < C && key == prefix;
       const unsigned long long below = (1ull << lane) - 1ull;
       const unsigned long long em = __ballot(eq);
@@ -146,7 +135,7 @@ __global__ void __launch_bounds__(64) k_topn(TopnP p) {
       rank += (kj > key || (kj == key && sm_id[j] < id)) ? 1 : 0;
     }
     oid[rank] = id;
-    oq[rank] = beam_quantize(__int_as_float(beam_key((int)(key ^ 0x80000000u))));
+    oq[rank] = fx_quantize(__int_as_float(fx_key((int)(key ^ 0x80000000u))));
   } else if (lane < p.N) {
     oid[lane] = -1, oq[lane] = BEAM_EMPTY_Q;
   }
@@ -232,8 +221,8 @@ __global__ void __launch_bounds__(BEAM_NT) k_beam(BeamP p) {
           atomicOr(&L.child[ps], 1ull << nl);
         }
       }
-      const long long pnbn = beam_lae(a, e, L.tab);
-      L.k_pb[j] = pbn, L.k_pnb[j] = pnbn, L.k_sc[j] = beam_lae(pbn, pnbn, L.tab);
+      const long long pnbn = fx_lae(a, e, L.tab);
+      L.k_pb[j] = pbn, L.k_pnb[j] = pnbn, L.k_sc[j] = fx_lae(pbn, pnbn, L.tab);
     }
     __syncthreads();
     // ---- the candidates: idx = i * (N + 1) + k, k == 0 the entry in slot i itself, else its extension by candidate k - 1.
@@ -433,8 +422,8 @@ __global__ void __launch_bounds__(BEAM_NT) k_beam_lm(BeamLmP q) {
           atomicOr(&L.child[ps], 1ull << nl);
         }
       }
-      const long long pnbn = beam_lae(a, e, L.tab);
-      L.k_pb[j] = pbn, L.k_pnb[j] = pnbn, L.k_sc[j] = beam_lae(pbn, pnbn, L.tab);
+      const long long pnbn = fx_lae(a, e, L.tab);
+      L.k_pb[j] = pbn, L.k_pnb[j] = pnbn, L.k_sc[j] = fx_lae(pbn, pnbn, L.tab);
     }
     __syncthreads();
     const int lg = nb > 1 ? 32 - __clz(nb - 1) : 0;

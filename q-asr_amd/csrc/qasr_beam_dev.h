@@ -1,7 +1,8 @@
 // What the beam kernels share, stated once for k_beam / k_beam_lm (qasr_beam.hip), k_beam_boost (qasr_beam_boost.hip) and the
 // streaming family (qasr_stream_beam_dev.h): the constants, the log-add-exp look-up, the views of the packed n-gram model and
 // of a packed phrase set with their header checks, the model walks, the automaton's transition, and the selection of a frame's
-// best W candidates.  The host statements are qasr/beam.py (RULES, LM_RULES) and qasr/boost.py (BOOST_RULES).
+// best W candidates.  The host statements are qasr/beam.py (RULES, LM_RULES) and qasr/boost.py (BOOST_RULES).  The fixed-point
+// arithmetic (NEG, fx_lae, fx_key, fx_quantize) is qasr_fixed_dev.h's, shared with the lattice kernels.
 // Bounds.  A model walk is bounded by the order (<= 6) and the header's probe bounds, its table indices are masked; a set is
 // used only if its header describes exactly the bytes the host passed (128 + 16 cap + 8 nodes + 4 labels == bytes, cap a power
 // of two), its table indices are masked by cap - 1, root-row indices are checked against n_labels, and every state that
@@ -10,18 +11,17 @@
 #pragma once
 #include <climits>
 
-#include "qasr_internal.h"
+#include "qasr_fixed_dev.h"
 
 namespace qasr {
 
-#define BEAM_NEG (-(1ll << 62))
-#define BEAM_DMAX (16ll << 16)
+#define BEAM_NEG FX_NEG
 #define BEAM_HMUL 0x9E3779B97F4A7C15ull
 #define BEAM_NT 256
 #define BEAM_NWAVE (BEAM_NT / 64)
 #define BEAM_W QASR_BEAM_MAX_WIDTH
 #define BEAM_N QASR_BEAM_MAX_CANDIDATES
-#define BEAM_TAB QASR_BEAM_TABLE_ENTRIES
+#define BEAM_TAB FX_TAB
 #define BEAM_LM_MAGIC 0x314D4C51
 #define BEAM_LM_OOV (-1000 * 65536)
 #define BEAM_LM_RAWLIM 2147483647ll
@@ -47,14 +47,6 @@ struct BeamState {          // one side of the offline kernels' double buffer
   unsigned long long hash[BEAM_W], phash[BEAM_W];
   int len[BEAM_W], last[BEAM_W], node[BEAM_W];
 };
-
-__device__ __forceinline__ long long beam_lae(long long a, long long b, const uint16_t* tab) {
-  const long long m = a > b ? a : b, n = a > b ? b : a;
-  if (n == BEAM_NEG) return m;
-  const long long d = m - n;
-  if (d >= BEAM_DMAX) return m;
-  return m + (long long)tab[d >> 6];
-}
 
 // ---------------------------------------------------------------------------------------------------- the n-gram model
 struct LmView {

@@ -1324,6 +1324,27 @@ int qasr_ctc_beam_boost(void* stream, const qasr_ctc_beam_boost_args* a) {
   return QASR_OK;
 }
 
+// ---- the checks the CTC lattice entry points below share, with the entry's name in the message; 0 or the error's code
+static int ctc_blank_check(const char* who, int blank, int C) {
+  return blank < 0 || blank >= C ? fail(QASR_ERR_ARG, "%s: blank %d is outside [0, %d)", who, blank, C) : 0;
+}
+static int ctc_pitch_check(const char* who, int T, int C, int64_t pitch_frame, int64_t pitch_utt) {
+  if (pitch_frame < C || pitch_utt < (int64_t)T * pitch_frame)
+    return fail(QASR_ERR_ARG, "%s: pitch_frame %lld < C or pitch_utt %lld < T * pitch_frame", who, (long long)pitch_frame, (long long)pitch_utt);
+  return 0;
+}
+static int ctc_star_pitch_check(const char* who, int64_t star_pitch, int T) {
+  return star_pitch < T ? fail(QASR_ERR_ARG, "%s: star_pitch %lld < T %d", who, (long long)star_pitch, T) : 0;
+}
+static int ctc_lae_check(const char* who, const void* lae_table, uint32_t lae_entries) {     // the posterior kernels: required
+  if (!lae_table || lae_entries != QASR_BEAM_TABLE_ENTRIES)
+    return fail(QASR_ERR_ARG, "%s: lae_table is required and lae_entries %u must be %d", who, lae_entries, QASR_BEAM_TABLE_ENTRIES);
+  return 0;
+}
+static int ctc_workspace_check(const char* who, size_t have, size_t need) {
+  return have < need ? fail(QASR_ERR_ARG, "%s: workspace of %zu bytes, %zu needed", who, have, need) : 0;
+}
+
 // ---- CTC forced alignment (k_align, qasr_align.hip): the checks of include/qasr.h, then one launch
 static int align_shape_ok(int P, int T, int max_labels) {
   return P >= 1 && T >= 1 && T <= QASR_BEAM_MAX_FRAMES && max_labels >= 1 && max_labels <= QASR_ALIGN_MAX_LABELS;
@@ -1349,17 +1370,14 @@ int qasr_ctc_align(void* stream, const qasr_ctc_align_args* given) {
   if ((long long)a->P != (long long)a->B * a->K) return fail(QASR_ERR_ARG, "ctc_align: P %d is not B %d * K %d", a->P, a->B, a->K);
   if (a->max_labels < 1 || a->max_labels > QASR_ALIGN_MAX_LABELS)
     return fail(QASR_ERR_ARG, "ctc_align: max_labels %d is outside 1 .. %d", a->max_labels, QASR_ALIGN_MAX_LABELS);
-  if (a->blank < 0 || a->blank >= a->C) return fail(QASR_ERR_ARG, "ctc_align: blank %d is outside [0, %d)", a->blank, a->C);
-  if (a->pitch_frame < a->C || a->pitch_utt < (int64_t)a->T * a->pitch_frame)
-    return fail(QASR_ERR_ARG, "ctc_align: pitch_frame %lld < C or pitch_utt %lld < T * pitch_frame", (long long)a->pitch_frame,
-                (long long)a->pitch_utt);
+  if (int rc = ctc_blank_check("ctc_align", a->blank, a->C)) return rc;
+  if (int rc = ctc_pitch_check("ctc_align", a->T, a->C, a->pitch_frame, a->pitch_utt)) return rc;
   if (a->total && !a->lae_table) return fail(QASR_ERR_ARG, "ctc_align: total needs lae_table");
   if (a->lae_table && a->lae_entries != QASR_BEAM_TABLE_ENTRIES)
     return fail(QASR_ERR_ARG, "ctc_align: lae_entries %u is not %d", a->lae_entries, QASR_BEAM_TABLE_ENTRIES);
-  const size_t need = align_workspace_bytes(a->P, a->T, a->max_labels);
-  if (a->workspace_bytes < need) return fail(QASR_ERR_ARG, "ctc_align: workspace of %zu bytes, %zu needed", a->workspace_bytes, need);
-  if (a->star_logp && a->star_pitch < a->T)
-    return fail(QASR_ERR_ARG, "ctc_align: star_pitch %lld < T %d", (long long)a->star_pitch, a->T);
+  if (int rc = ctc_workspace_check("ctc_align", a->workspace_bytes, align_workspace_bytes(a->P, a->T, a->max_labels))) return rc;
+  if (a->star_logp)
+    if (int rc = ctc_star_pitch_check("ctc_align", a->star_pitch, a->T)) return rc;
   int rc = launch_align((hipStream_t)stream, *a);
   if (rc) return fail(rc, "ctc_align: launch");
   HIPCHK(hipGetLastError());
@@ -1385,18 +1403,14 @@ int qasr_ctc_post(void* stream, const qasr_ctc_post_args* a) {
   if ((long long)a->P != (long long)a->B * a->K) return fail(QASR_ERR_ARG, "ctc_post: P %d is not B %d * K %d", a->P, a->B, a->K);
   if (a->max_labels < 1 || a->max_labels > QASR_ALIGN_MAX_LABELS)
     return fail(QASR_ERR_ARG, "ctc_post: max_labels %d is outside 1 .. %d", a->max_labels, QASR_ALIGN_MAX_LABELS);
-  if (a->blank < 0 || a->blank >= a->C) return fail(QASR_ERR_ARG, "ctc_post: blank %d is outside [0, %d)", a->blank, a->C);
-  if (a->pitch_frame < a->C || a->pitch_utt < (int64_t)a->T * a->pitch_frame)
-    return fail(QASR_ERR_ARG, "ctc_post: pitch_frame %lld < C or pitch_utt %lld < T * pitch_frame", (long long)a->pitch_frame,
-                (long long)a->pitch_utt);
-  if (!a->lae_table || a->lae_entries != QASR_BEAM_TABLE_ENTRIES)
-    return fail(QASR_ERR_ARG, "ctc_post: lae_table is required and lae_entries %u must be %d", a->lae_entries, QASR_BEAM_TABLE_ENTRIES);
+  if (int rc = ctc_blank_check("ctc_post", a->blank, a->C)) return rc;
+  if (int rc = ctc_pitch_check("ctc_post", a->T, a->C, a->pitch_frame, a->pitch_utt)) return rc;
+  if (int rc = ctc_lae_check("ctc_post", a->lae_table, a->lae_entries)) return rc;
   if (a->post_pitch < a->T) return fail(QASR_ERR_ARG, "ctc_post: post_pitch %lld < T %d", (long long)a->post_pitch, a->T);
   if (((uintptr_t)a->workspace & 7) != 0) return fail(QASR_ERR_ARG, "ctc_post: workspace is not 8-byte aligned");
-  const size_t need = post_workspace_bytes(a->P, a->T);
-  if (a->workspace_bytes < need) return fail(QASR_ERR_ARG, "ctc_post: workspace of %zu bytes, %zu needed", a->workspace_bytes, need);
-  if (a->star_logp && a->star_pitch < a->T)
-    return fail(QASR_ERR_ARG, "ctc_post: star_pitch %lld < T %d", (long long)a->star_pitch, a->T);
+  if (int rc = ctc_workspace_check("ctc_post", a->workspace_bytes, post_workspace_bytes(a->P, a->T))) return rc;
+  if (a->star_logp)
+    if (int rc = ctc_star_pitch_check("ctc_post", a->star_pitch, a->T)) return rc;
   int rc = launch_post((hipStream_t)stream, *a);
   if (rc) return fail(rc, "ctc_post: launch");
   HIPCHK(hipGetLastError());
@@ -1428,16 +1442,12 @@ int qasr_ctc_align_band(void* stream, const qasr_ctc_align_band_args* given) {
     return fail(QASR_ERR_ARG, "ctc_align_band: B %d, T %d (1 .. %d) or C %d out of range", a->B, a->T, QASR_BAND_MAX_FRAMES, a->C);
   if (a->max_labels < 1 || a->max_labels > QASR_BAND_MAX_LABELS)
     return fail(QASR_ERR_ARG, "ctc_align_band: max_labels %d is outside 1 .. %d", a->max_labels, QASR_BAND_MAX_LABELS);
-  if (a->blank < 0 || a->blank >= a->C) return fail(QASR_ERR_ARG, "ctc_align_band: blank %d is outside [0, %d)", a->blank, a->C);
-  if (a->pitch_frame < a->C || a->pitch_utt < (int64_t)a->T * a->pitch_frame)
-    return fail(QASR_ERR_ARG, "ctc_align_band: pitch_frame %lld < C or pitch_utt %lld < T * pitch_frame", (long long)a->pitch_frame,
-                (long long)a->pitch_utt);
+  if (int rc = ctc_blank_check("ctc_align_band", a->blank, a->C)) return rc;
+  if (int rc = ctc_pitch_check("ctc_align_band", a->T, a->C, a->pitch_frame, a->pitch_utt)) return rc;
   if (((uintptr_t)a->workspace & 3) != 0) return fail(QASR_ERR_ARG, "ctc_align_band: workspace is not 4-byte aligned");
-  const size_t need = align_band_workspace_bytes(a->B, a->T, a->band_states);
-  if (a->workspace_bytes < need)
-    return fail(QASR_ERR_ARG, "ctc_align_band: workspace of %zu bytes, %zu needed", a->workspace_bytes, need);
-  if (a->star_logp && a->star_pitch < a->T)
-    return fail(QASR_ERR_ARG, "ctc_align_band: star_pitch %lld < T %d", (long long)a->star_pitch, a->T);
+  if (int rc = ctc_workspace_check("ctc_align_band", a->workspace_bytes, align_band_workspace_bytes(a->B, a->T, a->band_states))) return rc;
+  if (a->star_logp)
+    if (int rc = ctc_star_pitch_check("ctc_align_band", a->star_pitch, a->T)) return rc;
   int rc = launch_align_band((hipStream_t)stream, *a);
   if (rc) return fail(rc, "ctc_align_band: launch");
   HIPCHK(hipGetLastError());
@@ -1463,20 +1473,14 @@ int qasr_ctc_post_band(void* stream, const qasr_ctc_post_band_args* a) {
     return fail(QASR_ERR_ARG, "ctc_post_band: B %d, T %d (1 .. %d) or C %d out of range", a->B, a->T, QASR_BAND_MAX_FRAMES, a->C);
   if (a->max_labels < 1 || a->max_labels > QASR_BAND_MAX_LABELS)
     return fail(QASR_ERR_ARG, "ctc_post_band: max_labels %d is outside 1 .. %d", a->max_labels, QASR_BAND_MAX_LABELS);
-  if (a->blank < 0 || a->blank >= a->C) return fail(QASR_ERR_ARG, "ctc_post_band: blank %d is outside [0, %d)", a->blank, a->C);
-  if (a->pitch_frame < a->C || a->pitch_utt < (int64_t)a->T * a->pitch_frame)
-    return fail(QASR_ERR_ARG, "ctc_post_band: pitch_frame %lld < C or pitch_utt %lld < T * pitch_frame", (long long)a->pitch_frame,
-                (long long)a->pitch_utt);
-  if (!a->lae_table || a->lae_entries != QASR_BEAM_TABLE_ENTRIES)
-    return fail(QASR_ERR_ARG, "ctc_post_band: lae_table is required and lae_entries %u must be %d", a->lae_entries,
-                QASR_BEAM_TABLE_ENTRIES);
+  if (int rc = ctc_blank_check("ctc_post_band", a->blank, a->C)) return rc;
+  if (int rc = ctc_pitch_check("ctc_post_band", a->T, a->C, a->pitch_frame, a->pitch_utt)) return rc;
+  if (int rc = ctc_lae_check("ctc_post_band", a->lae_table, a->lae_entries)) return rc;
   if (a->post_pitch < a->T) return fail(QASR_ERR_ARG, "ctc_post_band: post_pitch %lld < T %d", (long long)a->post_pitch, a->T);
   if (((uintptr_t)a->workspace & 7) != 0) return fail(QASR_ERR_ARG, "ctc_post_band: workspace is not 8-byte aligned");
-  const size_t need = post_band_workspace_bytes(a->B, a->T);
-  if (a->workspace_bytes < need)
-    return fail(QASR_ERR_ARG, "ctc_post_band: workspace of %zu bytes, %zu needed", a->workspace_bytes, need);
-  if (a->star_logp && a->star_pitch < a->T)
-    return fail(QASR_ERR_ARG, "ctc_post_band: star_pitch %lld < T %d", (long long)a->star_pitch, a->T);
+  if (int rc = ctc_workspace_check("ctc_post_band", a->workspace_bytes, post_band_workspace_bytes(a->B, a->T))) return rc;
+  if (a->star_logp)
+    if (int rc = ctc_star_pitch_check("ctc_post_band", a->star_pitch, a->T)) return rc;
   int rc = launch_post_band((hipStream_t)stream, *a);
   if (rc) return fail(rc, "ctc_post_band: launch");
   HIPCHK(hipGetLastError());
@@ -1490,10 +1494,8 @@ int qasr_ctc_star(void* stream, const qasr_ctc_star_args* a) {
     return fail(QASR_ERR_ARG, "ctc_star: struct_size %u is not %zu", a->struct_size, sizeof(qasr_ctc_star_args));
   if (!a->log_probs || !a->star) return fail(QASR_ERR_ARG, "ctc_star: log_probs and star are required");
   if (a->B < 1 || a->T < 1 || a->C < 1) return fail(QASR_ERR_ARG, "ctc_star: B %d, T %d or C %d out of range", a->B, a->T, a->C);
-  if (a->pitch_frame < a->C || a->pitch_utt < (int64_t)a->T * a->pitch_frame)
-    return fail(QASR_ERR_ARG, "ctc_star: pitch_frame %lld < C or pitch_utt %lld < T * pitch_frame", (long long)a->pitch_frame,
-                (long long)a->pitch_utt);
-  if (a->star_pitch < a->T) return fail(QASR_ERR_ARG, "ctc_star: star_pitch %lld < T %d", (long long)a->star_pitch, a->T);
+  if (int rc = ctc_pitch_check("ctc_star", a->T, a->C, a->pitch_frame, a->pitch_utt)) return rc;
+  if (int rc = ctc_star_pitch_check("ctc_star", a->star_pitch, a->T)) return rc;
   if (!(a->penalty >= 0.f && a->penalty <= QASR_STAR_MAX_PENALTY))   // (a NaN fails both comparisons)
     return fail(QASR_ERR_ARG, "ctc_star: penalty %g is not a finite number in 0 .. %g", (double)a->penalty, (double)QASR_STAR_MAX_PENALTY);
   int rc = launch_star((hipStream_t)stream, *a);
@@ -1516,11 +1518,9 @@ int qasr_ctc_spot(void* stream, const qasr_ctc_spot_args* a) {
   if ((long long)a->B * a->K > INT_MAX) return fail(QASR_ERR_ARG, "ctc_spot: B %d * K %d is above 2^31 - 1", a->B, a->K);
   if (a->max_labels < 1 || a->max_labels > QASR_SPOT_MAX_LABELS)
     return fail(QASR_ERR_ARG, "ctc_spot: max_labels %d is outside 1 .. %d", a->max_labels, QASR_SPOT_MAX_LABELS);
-  if (a->blank < 0 || a->blank >= a->C) return fail(QASR_ERR_ARG, "ctc_spot: blank %d is outside [0, %d)", a->blank, a->C);
-  if (a->star_pitch < a->T) return fail(QASR_ERR_ARG, "ctc_spot: star_pitch %lld < T %d", (long long)a->star_pitch, a->T);
-  if (a->pitch_frame < a->C || a->pitch_utt < (int64_t)a->T * a->pitch_frame)
-    return fail(QASR_ERR_ARG, "ctc_spot: pitch_frame %lld < C or pitch_utt %lld < T * pitch_frame", (long long)a->pitch_frame,
-                (long long)a->pitch_utt);
+  if (int rc = ctc_blank_check("ctc_spot", a->blank, a->C)) return rc;
+  if (int rc = ctc_star_pitch_check("ctc_spot", a->star_pitch, a->T)) return rc;
+  if (int rc = ctc_pitch_check("ctc_spot", a->T, a->C, a->pitch_frame, a->pitch_utt)) return rc;
   if (a->threshold_q < QASR_SPOT_MIN_THRESHOLD_Q || a->threshold_q > 0)
     return fail(QASR_ERR_ARG, "ctc_spot: threshold_q %d is outside %d .. 0", a->threshold_q, QASR_SPOT_MIN_THRESHOLD_Q);
   if (a->max_span < 1 || a->max_span > QASR_SPOT_MAX_SPAN)

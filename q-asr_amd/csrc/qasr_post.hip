@@ -23,26 +23,18 @@
 // LDS: 2 x NS x 256 x 8 B of rows + 32 KB of table + a few words: 100 KB at NS = 17, 36 KB at NS = 1.  LDS atomics: none.
 // Global memory sees plain vector stores.  Every loop is bounded by T, the number of states, the row pitch or a constant;
 // nothing is allocated and no length is read on the host.
-#include <type_traits>
-
-#include "qasr_internal.h"
+// The arithmetic (FX_NEG, fx_quantize, fx_lae) is qasr_fixed_dev.h's; the checks of the target and of start / nframes, a state's
+// label and skip rules, the emission read, the clamp of g and the launch ladder are qasr_lattice_dev.h's, with their bounds.
+#include "qasr_lattice_dev.h"
 
 namespace qasr {
-
-#define POST_NT 256
-#define POST_NEG (-(1ll << 62))
-#define POST_QFLOOR (-1073741824.f)
-#define POST_QCEIL (1073741824.f)
-#define POST_GFLOOR (-(1ll << 30))
-#define POST_DMAX (16ll << 16)
-#define POST_TAB QASR_BEAM_TABLE_ENTRIES
 
 struct PostP {
   const float* logp;
   const int32_t* lens;          // optional [B]
   const int32_t* targets;       // [P][ML]
   const int32_t* target_lens;   // [P]
-  const uint16_t* tab;          // [POST_TAB]
+  const uint16_t* tab;          // [FX_TAB]
   const int32_t* start;         // [P][ML]
   const int32_t* nframes;       // [P][ML]
   const int32_t* ok_in;         // [P] optional
@@ -56,28 +48,12 @@ struct PostP {
   int T, C, K, blank, ML;
 };
 
-// the arithmetic of qasr_align.hip (align_quantize, align_lae), which lives in no header
-__device__ __forceinline__ long long post_quantize(float x) {
-  float y = x * 65536.f;
-  if (!(y >= POST_QFLOOR)) y = POST_QFLOOR;        // NaN and -inf take the floor
-  if (y > POST_QCEIL) y = POST_QCEIL;
-  return (long long)(int)rintf(y);
-}
-
-__device__ __forceinline__ long long post_lae(long long a, long long b, const uint16_t* tab) {
-  const long long m = a > b ? a : b, n = a > b ? b : a;
-  if (n == POST_NEG) return m;
-  const long long d = m - n;
-  if (d >= POST_DMAX) return m;
-  return m + (long long)tab[d >> 6];
-}
-
 size_t post_workspace_bytes(int P, int T) { return (size_t)P * (size_t)T * sizeof(long long); }
 
 template <int NS, bool STAR>
-__global__ void __launch_bounds__(POST_NT) k_post(PostP p) {
-  __shared__ long long rows[2][NS * POST_NT];
-  __shared__ uint16_t tab[POST_TAB];
+__global__ void __launch_bounds__(LATTICE_NT) k_post(PostP p) {
+  __shared__ long long rows[2][NS * LATTICE_NT];
+  __shared__ uint16_t tab[FX_TAB];
   __shared__ int sh_bad;
   const int tid = threadIdx.x, pr = blockIdx.x, u = pr / p.K;
   const int T = p.T, C = p.C, blank = p.blank, ML = p.ML;
@@ -92,35 +68,28 @@ __global__ void __launch_bounds__(POST_NT) k_post(PostP p) {
 
   // a state that may not skip the blank reads this slot instead: 2L + 1 is odd and <= NS * 256, so no state lives here, nothing
   // but the next line writes it, and the frame step needs no mask per state for the third term
-  constexpr int SENT = NS * POST_NT - 1;
-  if (tid == 0) sh_bad = 0, rows[0][SENT] = rows[1][SENT] = POST_NEG;
-  for (int i = tid; i < POST_TAB; i += POST_NT) tab[i] = p.tab[i];
+  constexpr int SENT = NS * LATTICE_NT - 1;
+  if (tid == 0) sh_bad = 0, rows[0][SENT] = rows[1][SENT] = FX_NEG;
+  for (int i = tid; i < FX_TAB; i += LATTICE_NT) tab[i] = p.tab[i];
   __syncthreads();
   // the target and the alignment are device data: lengths, labels and runs are checked here, before anything is read through them
-  const bool len_ok = L >= 0 && L <= ML && L <= QASR_ALIGN_MAX_LABELS && 2 * L + 1 <= NS * POST_NT;
-  if (len_ok)
-    for (int i = tid; i < L; i += POST_NT) {
-      const int c = y[i];
-      bool bad = c < 0 || c >= C + (STAR ? 1 : 0) || c == blank;
-      const long long st = a_start[i], n = a_nframes[i];
-      const long long end_before = i ? (long long)a_start[i - 1] + (long long)a_nframes[i - 1] : 0;   // one past run i - 1
-      bad |= n < 1 || st < end_before || (i && c == y[i - 1] && st < end_before + 1);
-      bad |= i == L - 1 && st + n > (long long)lim;
-      if (bad) sh_bad = 1;
-    }
+  const bool len_ok = L >= 0 && L <= ML && L <= QASR_ALIGN_MAX_LABELS && 2 * L + 1 <= NS * LATTICE_NT;
+  if (len_ok && (lattice_check_target<STAR>(y, L, C, blank, tid, LATTICE_NT) |
+                 lattice_check_runs(y, a_start, a_nframes, L, lim, tid, LATTICE_NT)))
+    sh_bad = 1;
   __syncthreads();
   const bool valid = len_ok && !sh_bad && !(p.ok_in && p.ok_in[pr] == 0) && !(lim == 0 && L > 0);
   if (!valid) {                                                     // uniform: sh_bad was read behind the barrier
-    for (int i = tid; i < T; i += POST_NT) o_frame[i] = 0;
-    for (int i = tid; i < ML; i += POST_NT) o_label[i] = 0;
+    for (int i = tid; i < T; i += LATTICE_NT) o_frame[i] = 0;
+    for (int i = tid; i < ML; i += LATTICE_NT) o_label[i] = 0;
     if (tid == 0) {
-      if (p.total) p.total[pr] = POST_NEG;
+      if (p.total) p.total[pr] = FX_NEG;
       p.ok[pr] = 0;
     }
     return;
   }
-  for (int i = lim + tid; i < T; i += POST_NT) o_frame[i] = 0;       // behind lim
-  for (int i = L + tid; i < ML; i += POST_NT) o_label[i] = 0;        // the tails
+  for (int i = lim + tid; i < T; i += LATTICE_NT) o_frame[i] = 0;   // behind lim
+  for (int i = L + tid; i < ML; i += LATTICE_NT) o_label[i] = 0;    // the tails
   if (lim == 0) {                                                   // L == 0: the empty path
     if (tid == 0) {
       if (p.total) p.total[pr] = 0;
@@ -135,13 +104,14 @@ __global__ void __launch_bounds__(POST_NT) k_post(PostP p) {
   int i2f[NS], i2b[NS];                                             // where the third term lives: s - 2 / s + 2, or SENT
 #pragma unroll
   for (int k = 0; k < NS; ++k) {
-    const int s = tid + k * POST_NT, i = s >> 1;
+    const int s = tid + k * LATTICE_NT, i = s >> 1;
     lab[k] = blank, i2f[k] = i2b[k] = SENT, lo[k] = hi[k] = 0, lmin[k] = 0;
     if (s < S) {
       if (s & 1) {
-        lab[k] = y[i];
-        if (s >= 3 && y[i] != y[i - 1]) i2f[k] = s - 2;
-        if (s + 2 < S && y[i + 1] != y[i]) i2b[k] = s + 2;
+        const LatticeSlot sl = lattice_slot(y, s, S);
+        lab[k] = sl.label;
+        if (sl.skip_fwd) i2f[k] = s - 2;
+        if (sl.skip_bwd) i2b[k] = s + 2;
         lo[k] = a_start[i], hi[k] = a_start[i] + a_nframes[i];
       } else {
         lo[k] = i ? a_start[i - 1] + a_nframes[i - 1] : 0;
@@ -149,22 +119,16 @@ __global__ void __launch_bounds__(POST_NT) k_post(PostP p) {
       }
     }
   }
-  const float* const base = p.logp + (long long)u * p.pitch_b;
-  // logp[u][t][c]; with STAR the wildcard c == C reads its plane instead (t < lim <= T <= star_pitch) and nothing at base[.. + C]
-  auto emit = [&](long long t, int c) -> float {
-    if constexpr (STAR)
-      if (c == C) return p.star[(long long)u * p.star_pitch + t];
-    return base[t * p.pitch_t + c];
-  };
+  const LatticeEmit<STAR> emit = lattice_emit<STAR>(p, u);          // logp[u][t][c], the wildcard's plane where c == C
 
   float pf[NS];
   // ---- forward: k_align's step; the on-path thread leaves A(t, s_t) in fa[t]
 #pragma unroll
   for (int k = 0; k < NS; ++k) {
-    const int s = tid + k * POST_NT;
+    const int s = tid + k * LATTICE_NT;
     pf[k] = s < S ? emit(0, lab[k]) : 0.f;
     if (s < S) {
-      const long long a = s < 2 ? post_quantize(pf[k]) : POST_NEG;
+      const long long a = s < 2 ? fx_quantize(pf[k]) : FX_NEG;
       rows[0][s] = a;
       if (0 >= lo[k] && 0 < hi[k]) fa[0] = a;
     }
@@ -176,19 +140,19 @@ __global__ void __launch_bounds__(POST_NT) k_post(PostP p) {
     float nx[NS];
 #pragma unroll
     for (int k = 0; k < NS; ++k) {                                  // frame t + 1's gathers, in flight across this frame
-      const int s = tid + k * POST_NT;
+      const int s = tid + k * LATTICE_NT;
       nx[k] = (s < S && t + 1 < lim) ? emit(t + 1, lab[k]) : 0.f;
     }
     const long long* const R = rows[cur];
     long long* const W = rows[cur ^ 1];
 #pragma unroll
     for (int k = 0; k < NS; ++k) {
-      const int s = tid + k * POST_NT;
+      const int s = tid + k * LATTICE_NT;
       if (s < S) {
-        const long long q = post_quantize(pf[k]);
-        const long long a0 = R[s], a1 = s >= 1 ? R[s - 1] : POST_NEG, a2 = R[i2f[k]];
-        const long long x = post_lae(post_lae(a0, a1, tab), a2, tab);
-        const long long a = x == POST_NEG ? POST_NEG : x + q;
+        const long long q = fx_quantize(pf[k]);
+        const long long a0 = R[s], a1 = s >= 1 ? R[s - 1] : FX_NEG, a2 = R[i2f[k]];
+        const long long x = fx_lae(fx_lae(a0, a1, tab), a2, tab);
+        const long long a = x == FX_NEG ? FX_NEG : x + q;
         W[s] = a;
         if (t >= lo[k] && t < hi[k]) fa[t] = a;                     // t < lim <= T
       }
@@ -198,24 +162,23 @@ __global__ void __launch_bounds__(POST_NT) k_post(PostP p) {
     cur ^= 1;
     __syncthreads();
   }
-  const long long tot = L == 0 ? rows[cur][0] : post_lae(rows[cur][2 * L], rows[cur][2 * L - 1], tab);
+  const long long tot = L == 0 ? rows[cur][0] : fx_lae(rows[cur][2 * L], rows[cur][2 * L - 1], tab);
   __syncthreads();                                                  // the rows have been read: the backward pass starts over in them
 
   // ---- backward: frame lim - 1 first, then the mirrored step; fa[t] was stored by this work-group in front of a barrier
   auto post = [&](int t, int k, long long a, long long b, long long q) {
-    long long g = a + b - q - tot;
-    g = g < POST_GFLOOR ? POST_GFLOOR : (g > 0 ? 0 : g);
-    o_frame[t] = (int)g;                                            // t < lim <= T <= post_pitch
-    lmin[k] = min(lmin[k], (int)g);
+    const int g = lattice_post_clamp(a, b, q, tot);
+    o_frame[t] = g;                                                 // t < lim <= T <= post_pitch
+    lmin[k] = min(lmin[k], g);
   };
   long long fa_cur = 0, fa_nx = 0;
 #pragma unroll
   for (int k = 0; k < NS; ++k) {
-    const int s = tid + k * POST_NT;
+    const int s = tid + k * LATTICE_NT;
     pf[k] = s < S ? emit(lim - 1, lab[k]) : 0.f;
     if (s < S) {
-      const long long q = post_quantize(pf[k]);
-      const long long b = (s == S - 1 || s == S - 2) ? q : POST_NEG;
+      const long long q = fx_quantize(pf[k]);
+      const long long b = (s == S - 1 || s == S - 2) ? q : FX_NEG;
       rows[0][s] = b;
       if (lim - 1 >= lo[k] && lim - 1 < hi[k]) post(lim - 1, k, fa[lim - 1], b, q);
       if (lim - 2 >= lo[k] && lim - 2 < hi[k]) fa_cur = fa[lim - 2];    // (lo >= 0: never with lim == 1)
@@ -228,7 +191,7 @@ __global__ void __launch_bounds__(POST_NT) k_post(PostP p) {
     float nx[NS];
 #pragma unroll
     for (int k = 0; k < NS; ++k) {                                  // frame t - 1's gathers, in flight across this frame
-      const int s = tid + k * POST_NT;
+      const int s = tid + k * LATTICE_NT;
       nx[k] = (s < S && t >= 1) ? emit(t - 1, lab[k]) : 0.f;
       if (s < S && t - 1 >= lo[k] && t - 1 < hi[k]) fa_nx = fa[t - 1];
     }
@@ -236,12 +199,12 @@ __global__ void __launch_bounds__(POST_NT) k_post(PostP p) {
     long long* const W = rows[cur ^ 1];
 #pragma unroll
     for (int k = 0; k < NS; ++k) {
-      const int s = tid + k * POST_NT;
+      const int s = tid + k * LATTICE_NT;
       if (s < S) {
-        const long long q = post_quantize(pf[k]);
-        const long long b0 = R[s], b1 = s + 1 < S ? R[s + 1] : POST_NEG, b2 = R[i2b[k]];
-        const long long x = post_lae(post_lae(b0, b1, tab), b2, tab);
-        const long long b = x == POST_NEG ? POST_NEG : x + q;
+        const long long q = fx_quantize(pf[k]);
+        const long long b0 = R[s], b1 = s + 1 < S ? R[s + 1] : FX_NEG, b2 = R[i2b[k]];
+        const long long x = fx_lae(fx_lae(b0, b1, tab), b2, tab);
+        const long long b = x == FX_NEG ? FX_NEG : x + q;
         W[s] = b;
         if (t >= lo[k] && t < hi[k]) post(t, k, fa_cur, b, q);
       }
@@ -255,7 +218,7 @@ __global__ void __launch_bounds__(POST_NT) k_post(PostP p) {
   // ---- per label the least certain frame of its run: the owner of state 2i + 1 has seen them all
 #pragma unroll
   for (int k = 0; k < NS; ++k) {
-    const int s = tid + k * POST_NT;
+    const int s = tid + k * LATTICE_NT;
     if (s < S && (s & 1)) o_label[s >> 1] = lmin[k];                // s >> 1 < L <= ML
   }
   if (tid == 0) {
@@ -266,13 +229,10 @@ __global__ void __launch_bounds__(POST_NT) k_post(PostP p) {
 
 template <bool STAR>
 static void launch_post_ns(hipStream_t s, const PostP& p, int P, int states) {
-  const dim3 grid((unsigned)P), block(POST_NT);
-  static_assert(2 * QASR_ALIGN_MAX_LABELS + 1 <= 17 * POST_NT, "k_post<17> holds the longest target");
-  if (states <= 1 * POST_NT) hipLaunchKernelGGL((k_post<1, STAR>), grid, block, 0, s, p);
-  else if (states <= 2 * POST_NT) hipLaunchKernelGGL((k_post<2, STAR>), grid, block, 0, s, p);
-  else if (states <= 4 * POST_NT) hipLaunchKernelGGL((k_post<4, STAR>), grid, block, 0, s, p);
-  else if (states <= 8 * POST_NT) hipLaunchKernelGGL((k_post<8, STAR>), grid, block, 0, s, p);
-  else hipLaunchKernelGGL((k_post<17, STAR>), grid, block, 0, s, p);
+  static_assert(2 * QASR_ALIGN_MAX_LABELS + 1 <= 17 * LATTICE_NT, "k_post<17> holds the longest target");
+  lattice_dispatch_ns(states, [&](auto ns) {
+    hipLaunchKernelGGL((k_post<decltype(ns)::value, STAR>), dim3((unsigned)P), dim3(LATTICE_NT), 0, s, p);
+  });
 }
 
 int launch_post(hipStream_t s, const qasr_ctc_post_args& a) {

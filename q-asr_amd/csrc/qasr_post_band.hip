@@ -30,27 +30,19 @@
 // LDS: 2 x (BW + 1) x 8 B of rows + 32 KB of table + two words: 102 424 B at NS = 17, 36 888 B at NS = 1.  LDS atomics: none.
 // Global memory sees plain vector stores.  Every loop is bounded by T, L, the row pitch or a constant; nothing is allocated and
 // no length is read on the host.  The STAR = false instantiations take no plane argument.
-#include <type_traits>
-
-#include "qasr_internal.h"
+// The arithmetic (FX_NEG, fx_quantize, fx_lae) is qasr_fixed_dev.h's; LATTICE_BLOCK (the frames per entry of band_base, the one
+// k_align_band moves by), the checks of the target and of start / nframes, a state's label and skip rules, the emission read,
+// the clamp of g and the launch ladder are qasr_lattice_dev.h's, with their bounds.
+#include "qasr_lattice_dev.h"
 
 namespace qasr {
-
-#define PB_NT 256
-#define PB_NEG (-(1ll << 62))
-#define PB_QFLOOR (-1073741824.f)
-#define PB_QCEIL (1073741824.f)
-#define PB_GFLOOR (-(1ll << 30))
-#define PB_DMAX (16ll << 16)
-#define PB_TAB QASR_BEAM_TABLE_ENTRIES
-#define PB_BLOCK 32                             /* frames per entry of band_base: k_align_band's BAND_BLOCK */
 
 struct PostBandP {
   const float* logp;
   const int32_t* lens;          // optional [P]
   const int32_t* targets;       // [P][ML]
   const int32_t* target_lens;   // [P]
-  const uint16_t* tab;          // [PB_TAB]
+  const uint16_t* tab;          // [FX_TAB]
   const int32_t* start;         // [P][ML]
   const int32_t* nframes;       // [P][ML]
   const int32_t* ok_in;         // [P] optional
@@ -69,30 +61,14 @@ struct PostBandPS : PostBandP {  // k_post_band<NS, true>'s argument
   long long star_pitch;
 };
 
-// the arithmetic of qasr_post.hip (post_quantize, post_lae), which lives in no header
-__device__ __forceinline__ long long pb_quantize(float x) {
-  float y = x * 65536.f;
-  if (!(y >= PB_QFLOOR)) y = PB_QFLOOR;            // NaN and -inf take the floor
-  if (y > PB_QCEIL) y = PB_QCEIL;
-  return (long long)(int)rintf(y);
-}
-
-__device__ __forceinline__ long long pb_lae(long long a, long long b, const uint16_t* tab) {
-  const long long m = a > b ? a : b, n = a > b ? b : a;
-  if (n == PB_NEG) return m;
-  const long long d = m - n;
-  if (d >= PB_DMAX) return m;
-  return m + (long long)tab[d >> 6];
-}
-
 size_t post_band_workspace_bytes(int P, int T) { return (size_t)P * (size_t)T * sizeof(long long); }
 
 template <int NS, bool STAR>
-__global__ void __launch_bounds__(PB_NT) k_post_band(std::conditional_t<STAR, PostBandPS, PostBandP> p) {
-  constexpr int BW = NS * PB_NT;
+__global__ void __launch_bounds__(LATTICE_NT) k_post_band(std::conditional_t<STAR, PostBandPS, PostBandP> p) {
+  constexpr int BW = NS * LATTICE_NT;
   constexpr int SENT = BW;                                          // one entry past the circular row: always NEG
   __shared__ long long rows[2][BW + 1];
-  __shared__ uint16_t tab[PB_TAB];
+  __shared__ uint16_t tab[FX_TAB];
   __shared__ int sh_bad, sh_out;
   const int tid = threadIdx.x, pr = blockIdx.x;
   const int T = p.T, C = p.C, blank = p.blank, ML = p.ML;
@@ -106,25 +82,18 @@ __global__ void __launch_bounds__(PB_NT) k_post_band(std::conditional_t<STAR, Po
   int32_t* const o_label = p.label_post + (size_t)pr * ML;
   long long* const fa = p.fa + (size_t)pr * (size_t)T;
 
-  if (tid == 0) sh_bad = 0, sh_out = 0, rows[0][SENT] = rows[1][SENT] = PB_NEG;
-  for (int i = tid; i < PB_TAB; i += PB_NT) tab[i] = p.tab[i];
+  if (tid == 0) sh_bad = 0, sh_out = 0, rows[0][SENT] = rows[1][SENT] = FX_NEG;
+  for (int i = tid; i < FX_TAB; i += LATTICE_NT) tab[i] = p.tab[i];
   __syncthreads();
   // the target, the alignment and the trajectory are device data: checked here, before anything is read through them
   const bool len_ok = L >= 0 && L <= ML && L <= QASR_BAND_MAX_LABELS;
   const int S = len_ok ? 2 * L + 1 : 1;
   const int top = max(0, S - BW);
-  const int nblk = (lim + PB_BLOCK - 1) / PB_BLOCK;                 // blocks that have a frame < lim (<= NB: lim <= T)
+  const int nblk = (lim + LATTICE_BLOCK - 1) / LATTICE_BLOCK;       // blocks that have a frame < lim (<= NB: lim <= T)
   if (len_ok) {
-    for (int i = tid; i < L; i += PB_NT) {
-      const int c = y[i];
-      bool bad = c < 0 || c >= C + (STAR ? 1 : 0) || c == blank;
-      const long long st = a_start[i], n = a_nframes[i];
-      const long long end_before = i ? (long long)a_start[i - 1] + (long long)a_nframes[i - 1] : 0;   // one past run i - 1
-      bad |= n < 1 || st < end_before || (i && c == y[i - 1] && st < end_before + 1);
-      bad |= i == L - 1 && st + n > (long long)lim;
-      if (bad) sh_bad = 1;
-    }
-    for (int j = tid; j < nblk; j += PB_NT) {
+    if (lattice_check_target<STAR>(y, L, C, blank, tid, LATTICE_NT) | lattice_check_runs(y, a_start, a_nframes, L, lim, tid, LATTICE_NT))
+      sh_bad = 1;
+    for (int j = tid; j < nblk; j += LATTICE_NT) {
       const long long b = bb[j], before = j ? (long long)bb[j - 1] : 0;
       if (b < 0 || b > top || (j ? (b < before || b - before >= BW / 2) : b != 0)) sh_bad = 1;
     }
@@ -135,7 +104,7 @@ __global__ void __launch_bounds__(PB_NT) k_post_band(std::conditional_t<STAR, Po
     // every run is a frame interval inside [0, lim] now and every base of a block < nblk lies in [0, top]: a frame may select
     // a block.  The state s of the frames [lo, hi), lo < hi, needs a cell at each and an edge out of each but the last of all
     auto outside = [&](int s, int lo, int hi) -> bool { return s < bb[min(hi, lim - 1) >> 5] || s >= bb[lo >> 5] + BW; };
-    for (int i = tid; i < L; i += PB_NT) {
+    for (int i = tid; i < L; i += LATTICE_NT) {
       const int st = a_start[i], en = st + a_nframes[i];
       const int end_before = i ? a_start[i - 1] + a_nframes[i - 1] : 0;
       bool bad = outside(2 * i + 1, st, en);
@@ -150,10 +119,10 @@ __global__ void __launch_bounds__(PB_NT) k_post_band(std::conditional_t<STAR, Po
   __syncthreads();
   valid = valid && !sh_out;
   auto refuse = [&]() {
-    for (int i = tid; i < T; i += PB_NT) o_frame[i] = 0;
-    for (int i = tid; i < ML; i += PB_NT) o_label[i] = 0;
+    for (int i = tid; i < T; i += LATTICE_NT) o_frame[i] = 0;
+    for (int i = tid; i < ML; i += LATTICE_NT) o_label[i] = 0;
     if (tid == 0) {
-      if (p.total) p.total[pr] = PB_NEG;
+      if (p.total) p.total[pr] = FX_NEG;
       p.ok[pr] = 0;
     }
   };
@@ -161,8 +130,8 @@ __global__ void __launch_bounds__(PB_NT) k_post_band(std::conditional_t<STAR, Po
     refuse();
     return;
   }
-  for (int i = lim + tid; i < T; i += PB_NT) o_frame[i] = 0;         // behind lim
-  for (int i = L + tid; i < ML; i += PB_NT) o_label[i] = 0;          // the tails
+  for (int i = lim + tid; i < T; i += LATTICE_NT) o_frame[i] = 0;   // behind lim
+  for (int i = L + tid; i < ML; i += LATTICE_NT) o_label[i] = 0;    // the tails
   if (lim == 0) {                                                   // L == 0: the empty path
     if (tid == 0) {
       if (p.total) p.total[pr] = 0;
@@ -171,25 +140,20 @@ __global__ void __launch_bounds__(PB_NT) k_post_band(std::conditional_t<STAR, Po
     return;
   }
 
-  const float* const lp = p.logp + (long long)pr * p.pitch_b;
-  // logp[pr][t][c]; with STAR the wildcard c == C reads its plane instead (t < lim <= T <= star_pitch) and nothing at lp[.. + C]
-  auto emit = [&](long long t, int c) -> float {
-    if constexpr (STAR)
-      if (c == C) return p.star[(long long)pr * p.star_pitch + t];
-    return lp[t * p.pitch_t + c];
-  };
+  const LatticeEmit<STAR> emit = lattice_emit<STAR>(p, pr);         // logp[pr][t][c], the wildcard's plane where c == C
 
   int st[NS], lab[NS], lo[NS], hi[NS], lmin[NS];
   int i2f[NS], i2b[NS];                                             // where the third term lives: (s - 2) % BW / (s + 2) % BW, or SENT
   float pf[NS];
   // slot k takes the state s < S, s % BW == tid + k * 256 (a valid alignment: lo and hi are frame numbers in 0 .. lim)
   auto load_slot = [&](int k, int s) {
-    const int i = s >> 1, i0 = tid + k * PB_NT;
+    const int i = s >> 1, i0 = tid + k * LATTICE_NT;
     st[k] = s, lab[k] = blank, i2f[k] = i2b[k] = SENT, lmin[k] = 0;
     if (s & 1) {
-      lab[k] = y[i];
-      if (s >= 3 && y[i] != y[i - 1]) i2f[k] = i0 >= 2 ? i0 - 2 : i0 - 2 + BW;
-      if (s + 2 < S && y[i + 1] != y[i]) i2b[k] = i0 + 2 < BW ? i0 + 2 : i0 + 2 - BW;
+      const LatticeSlot sl = lattice_slot(y, s, S);
+      lab[k] = sl.label;
+      if (sl.skip_fwd) i2f[k] = i0 >= 2 ? i0 - 2 : i0 - 2 + BW;
+      if (sl.skip_bwd) i2b[k] = i0 + 2 < BW ? i0 + 2 : i0 + 2 - BW;
       lo[k] = a_start[i], hi[k] = a_start[i] + a_nframes[i];
     } else {
       lo[k] = i ? a_start[i - 1] + a_nframes[i - 1] : 0;
@@ -200,12 +164,12 @@ __global__ void __launch_bounds__(PB_NT) k_post_band(std::conditional_t<STAR, Po
   // ---- forward: k_align_band's step with lae for max; the on-path thread leaves A(t, s_t) in fa[t]
 #pragma unroll
   for (int k = 0; k < NS; ++k) {
-    const int s = tid + k * PB_NT;                                  // base 0
+    const int s = tid + k * LATTICE_NT;                             // base 0
     st[k] = s, lab[k] = blank, i2f[k] = i2b[k] = SENT, lo[k] = hi[k] = 0, lmin[k] = 0;
     if (s < S) load_slot(k, s);
     pf[k] = s < S ? emit(0, lab[k]) : 0.f;
     if (s < S) {
-      const long long a = s < 2 ? pb_quantize(pf[k]) : PB_NEG;
+      const long long a = s < 2 ? fx_quantize(pf[k]) : FX_NEG;
       rows[0][s] = a;
       if (0 >= lo[k] && 0 < hi[k]) fa[0] = a;
     }
@@ -214,7 +178,7 @@ __global__ void __launch_bounds__(PB_NT) k_post_band(std::conditional_t<STAR, Po
   int cur = 0, base = 0;
   __syncthreads();
   for (int t = 1; t < lim; ++t) {
-    if ((t & (PB_BLOCK - 1)) == 0) {                                // uniform: a block begins
+    if ((t & (LATTICE_BLOCK - 1)) == 0) {                           // uniform: a block begins
       const int nb = bb[t >> 5];                                    // t < lim: a checked entry, base <= nb < base + BW / 2
       if (nb > base) {                                              // (then top > 0: every slot holds a state < S)
         long long* const Rw = rows[cur];
@@ -222,7 +186,7 @@ __global__ void __launch_bounds__(PB_NT) k_post_band(std::conditional_t<STAR, Po
         for (int k = 0; k < NS; ++k)
           if (st[k] < nb) {                                         // dropped: state st + BW enters (nb + BW <= S)
             load_slot(k, st[k] + BW);
-            Rw[tid + k * PB_NT] = PB_NEG;
+            Rw[tid + k * LATTICE_NT] = FX_NEG;
             pf[k] = emit(t, lab[k]);                                // this frame again, with the new label
           }
         base = nb;
@@ -237,14 +201,14 @@ __global__ void __launch_bounds__(PB_NT) k_post_band(std::conditional_t<STAR, Po
     long long* const W = rows[cur ^ 1];
 #pragma unroll
     for (int k = 0; k < NS; ++k) {
-      const int i0 = tid + k * PB_NT;                               // s % BW
+      const int i0 = tid + k * LATTICE_NT;                          // s % BW
       const int s = st[k];
       if (s < S) {
         const int i1 = i0 >= 1 ? i0 - 1 : i0 - 1 + BW;
-        const long long q = pb_quantize(pf[k]);
-        const long long a0 = R[i0], a1 = s - 1 >= base ? R[i1] : PB_NEG, a2 = R[s - 2 >= base ? i2f[k] : SENT];
-        const long long x = pb_lae(pb_lae(a0, a1, tab), a2, tab);
-        const long long a = x == PB_NEG ? PB_NEG : x + q;
+        const long long q = fx_quantize(pf[k]);
+        const long long a0 = R[i0], a1 = s - 1 >= base ? R[i1] : FX_NEG, a2 = R[s - 2 >= base ? i2f[k] : SENT];
+        const long long x = fx_lae(fx_lae(a0, a1, tab), a2, tab);
+        const long long a = x == FX_NEG ? FX_NEG : x + q;
         W[i0] = a;
         if (t >= lo[k] && t < hi[k]) fa[t] = a;                     // t < lim <= T
       }
@@ -261,33 +225,32 @@ __global__ void __launch_bounds__(PB_NT) k_post_band(std::conditional_t<STAR, Po
       tot = R[0];
     } else {                                                        // an end state outside the last band is NEG
       const int s2 = 2 * L, s1 = 2 * L - 1;
-      const long long a = (s2 >= base && s2 < base + BW) ? R[s2 % BW] : PB_NEG;
-      const long long b = (s1 >= base && s1 < base + BW) ? R[s1 % BW] : PB_NEG;
-      tot = pb_lae(a, b, tab);
+      const long long a = (s2 >= base && s2 < base + BW) ? R[s2 % BW] : FX_NEG;
+      const long long b = (s1 >= base && s1 < base + BW) ? R[s1 % BW] : FX_NEG;
+      tot = fx_lae(a, b, tab);
     }
   }
   __syncthreads();                                                  // the rows have been read: the backward pass starts over in them
-  if (tot == PB_NEG) {                                              // uniform (a checked path has a finite score: not expected)
+  if (tot == FX_NEG) {                                              // uniform (a checked path has a finite score: not expected)
     refuse();
     return;
   }
 
   // ---- backward: frame lim - 1 first (the slots are the last band's), then the mirrored step
   auto post = [&](int t, int k, long long a, long long b, long long q) {
-    long long g = a + b - q - tot;
-    g = g < PB_GFLOOR ? PB_GFLOOR : (g > 0 ? 0 : g);
-    o_frame[t] = (int)g;                                            // t < lim <= T <= post_pitch
-    lmin[k] = min(lmin[k], (int)g);
+    const int g = lattice_post_clamp(a, b, q, tot);
+    o_frame[t] = g;                                                 // t < lim <= T <= post_pitch
+    lmin[k] = min(lmin[k], g);
   };
   long long fa_cur = 0, fa_nx = 0;
 #pragma unroll
   for (int k = 0; k < NS; ++k) {
-    const int i0 = tid + k * PB_NT;
+    const int i0 = tid + k * LATTICE_NT;
     const int s = st[k];
     pf[k] = s < S ? emit(lim - 1, lab[k]) : 0.f;
     if (s < S) {
-      const long long q = pb_quantize(pf[k]);
-      const long long b = (s == S - 1 || s == S - 2) ? q : PB_NEG;
+      const long long q = fx_quantize(pf[k]);
+      const long long b = (s == S - 1 || s == S - 2) ? q : FX_NEG;
       rows[0][i0] = b;
       if (lim - 1 >= lo[k] && lim - 1 < hi[k]) post(lim - 1, k, fa[lim - 1], b, q);
       if (lim - 2 >= lo[k] && lim - 2 < hi[k]) fa_cur = fa[lim - 2];    // (lo >= 0: never with lim == 1)
@@ -298,7 +261,7 @@ __global__ void __launch_bounds__(PB_NT) k_post_band(std::conditional_t<STAR, Po
   __syncthreads();
   for (int t = lim - 2; t >= 0; --t) {
     const int bnext = base;                                         // base(t + 1)
-    if (((t + 1) & (PB_BLOCK - 1)) == 0) {                          // uniform: frame t + 1 began a block
+    if (((t + 1) & (LATTICE_BLOCK - 1)) == 0) {                     // uniform: frame t + 1 began a block
       const int nb = bb[t >> 5];
       if (nb < base) {
 #pragma unroll
@@ -321,14 +284,14 @@ __global__ void __launch_bounds__(PB_NT) k_post_band(std::conditional_t<STAR, Po
     long long* const W = rows[cur ^ 1];
 #pragma unroll
     for (int k = 0; k < NS; ++k) {
-      const int i0 = tid + k * PB_NT;
+      const int i0 = tid + k * LATTICE_NT;
       const int s = st[k];
       if (s < S) {
         const int i1 = i0 + 1 < BW ? i0 + 1 : i0 + 1 - BW;
-        const long long q = pb_quantize(pf[k]);
-        const long long b0 = R[i0], b1 = s + 1 < hi_b ? R[i1] : PB_NEG, b2 = R[s + 2 < hi_b ? i2b[k] : SENT];
-        const long long x = pb_lae(pb_lae(b0, b1, tab), b2, tab);
-        const long long b = (s < bnext || x == PB_NEG) ? PB_NEG : x + q;      // below base(t + 1): no edge out
+        const long long q = fx_quantize(pf[k]);
+        const long long b0 = R[i0], b1 = s + 1 < hi_b ? R[i1] : FX_NEG, b2 = R[s + 2 < hi_b ? i2b[k] : SENT];
+        const long long x = fx_lae(fx_lae(b0, b1, tab), b2, tab);
+        const long long b = (s < bnext || x == FX_NEG) ? FX_NEG : x + q;      // below base(t + 1): no edge out
         W[i0] = b;
         if (t >= lo[k] && t < hi[k]) post(t, k, fa_cur, b, q);
       }
@@ -353,12 +316,9 @@ __global__ void __launch_bounds__(PB_NT) k_post_band(std::conditional_t<STAR, Po
 
 template <bool STAR>
 static int launch_post_band_ns(hipStream_t s, const std::conditional_t<STAR, PostBandPS, PostBandP>& p, int B, int band_states) {
-  const dim3 grid((unsigned)B), block(PB_NT);
-  if (band_states == 1 * PB_NT) hipLaunchKernelGGL((k_post_band<1, STAR>), grid, block, 0, s, p);
-  else if (band_states == 4 * PB_NT) hipLaunchKernelGGL((k_post_band<4, STAR>), grid, block, 0, s, p);
-  else if (band_states == 17 * PB_NT) hipLaunchKernelGGL((k_post_band<17, STAR>), grid, block, 0, s, p);
-  else return QASR_ERR_ARG;
-  return QASR_OK;
+  return lattice_dispatch_band_ns(band_states, [&](auto ns) {
+    hipLaunchKernelGGL((k_post_band<decltype(ns)::value, STAR>), dim3((unsigned)B), dim3(LATTICE_NT), 0, s, p);
+  });
 }
 
 int launch_post_band(hipStream_t s, const qasr_ctc_post_band_args& a) {
@@ -368,7 +328,7 @@ int launch_post_band(hipStream_t s, const qasr_ctc_post_band_args& a) {
   p.fa = (long long*)a.workspace;
   p.frame_post = a.frame_post, p.label_post = a.label_post, p.total = (long long*)a.total, p.ok = a.ok;
   p.pitch_b = a.pitch_utt, p.pitch_t = a.pitch_frame, p.post_pitch = a.post_pitch;
-  p.T = a.T, p.C = a.C, p.blank = a.blank, p.ML = a.max_labels, p.NB = (a.T + PB_BLOCK - 1) / PB_BLOCK;
+  p.T = a.T, p.C = a.C, p.blank = a.blank, p.ML = a.max_labels, p.NB = (a.T + LATTICE_BLOCK - 1) / LATTICE_BLOCK;
   p.star = a.star_logp, p.star_pitch = a.star_pitch;
   if (a.star_logp) return launch_post_band_ns<true>(s, p, a.B, a.band_states);
   return launch_post_band_ns<false>(s, static_cast<const PostBandP&>(p), a.B, a.band_states);

@@ -1,7 +1,7 @@
 // Keyword spotting over CTC log-probabilities (k_spot); the host statement is SPOT_RULES and spot_host of qasr/spot.py, and this
 // file follows it bit for bit.  Every keyword's lattice (k_align's states s = 1 .. 2L - 1) runs over the frames with a free start
 // - state 0 is the constant fresh start (0, t) - and a free end at F = 2L - 1; a state carries the pair (D int64, start int32);
-// the emission is e(t, s) = min(q(logp[u][t][lab(s)]) - q(star[u][t]), 0), q = rint(x * 2^16) clamped as in qasr_align.hip.
+// the emission is e(t, s) = min(q(logp[u][t][lab(s)]) - q(star[u][t]), 0), q = rint(x * 2^16) clamped (fx_quantize).
 //
 // k_spot<NS>: one WAVE per problem p = u * K + k, four problems to a work-group of 256 threads.  Lane l owns the NS contiguous
 // states l * NS .. l * NS + NS - 1 (NS = 1, 2, 4 from the row pitch of the targets: 2 ML + 1 <= 64 / 128 / 256).  A state's
@@ -14,18 +14,16 @@
 // optional trace, with plain vector stores.  The tails (hit rows behind the stored hits, trace frames behind lim) are zeroed by
 // all lanes.  LDS: none.  Atomics: none.  Nothing is read back.  Every loop is bounded by T, ML, max_hits or a constant; nothing
 // is allocated and no length is read on the host.
+// FX_NEG and fx_quantize are qasr_fixed_dev.h's; the target check and a state's label and skip rule are qasr_lattice_dev.h's.
 #include <climits>
 
-#include "qasr_internal.h"
+#include "qasr_lattice_dev.h"
 
 namespace qasr {
 
 #define SPOT_NT 256
 #define SPOT_WAVE 64
 #define SPOT_WAVES (SPOT_NT / SPOT_WAVE)
-#define SPOT_NEG (-(1ll << 62))
-#define SPOT_QFLOOR (-1073741824.f)
-#define SPOT_QCEIL (1073741824.f)
 
 struct SpotP {
   const float* logp;
@@ -43,13 +41,6 @@ struct SpotP {
   long long pitch_b, pitch_t, star_pitch, trace_pitch;
   int P, T, C, K, ML, blank, threshold_q, max_span, max_hits;
 };
-
-__device__ __forceinline__ long long spot_quantize(float x) {       // align_quantize
-  float y = x * 65536.f;
-  if (!(y >= SPOT_QFLOOR)) y = SPOT_QFLOOR;         // NaN and -inf take the floor
-  if (y > SPOT_QCEIL) y = SPOT_QCEIL;
-  return (long long)(int)rintf(y);
-}
 
 template <int NS>
 __global__ void __launch_bounds__(SPOT_NT) k_spot(SpotP p) {
@@ -69,12 +60,7 @@ __global__ void __launch_bounds__(SPOT_NT) k_spot(SpotP p) {
 
   // the target is device data: its length and every label are checked here, before anything is read through them
   const bool len_ok = L >= 1 && L <= ML && L <= QASR_SPOT_MAX_LABELS && 2 * L <= NS * SPOT_WAVE;
-  int bad = 0;
-  if (len_ok)
-    for (int i = lane; i < L; i += SPOT_WAVE) {
-      const int c = y[i];
-      if (c < 0 || c >= C || c == blank) bad = 1;
-    }
+  const bool bad = len_ok && lattice_check_target<false>(y, L, C, blank, lane, SPOT_WAVE);
   const bool valid = len_ok && __ballot(bad) == 0;                  // wave-uniform
   if (!valid) {
     for (int i = lane; i < MH; i += SPOT_WAVE) o_start[i] = 0, o_end[i] = 0, o_score[i] = 0;
@@ -95,10 +81,10 @@ __global__ void __launch_bounds__(SPOT_NT) k_spot(SpotP p) {
     const int s = lane * NS + k;
     lab[k] = blank, skp[k] = false;
     if (s < S && (s & 1)) {                                         // s >> 1 < L
-      lab[k] = y[s >> 1];
-      skp[k] = s >= 3 && y[s >> 1] != y[(s >> 1) - 1];
+      const LatticeSlot sl = lattice_slot(y, s, S);
+      lab[k] = sl.label, skp[k] = sl.skip_fwd;
     }
-    D[k] = SPOT_NEG, st[k] = -1;                                    // the row before frame 0: every state dead
+    D[k] = FX_NEG, st[k] = -1;                                      // the row before frame 0: every state dead
   }
   const float* const base = p.logp + (long long)u * p.pitch_b;      // [t * pitch_t + c], c < C <= pitch_t
   const float* const srow = p.star + (long long)u * p.star_pitch;   // [t], t < T <= star_pitch
@@ -123,31 +109,31 @@ __global__ void __launch_bounds__(SPOT_NT) k_spot(SpotP p) {
     // the two pairs below this lane's states: b1 = state lane * NS - 1, b2 = state lane * NS - 2 (NEG below state 0)
     long long b1d = __shfl_up(D[NS - 1], 1), b2d = NS >= 2 ? __shfl_up(D[NS >= 2 ? NS - 2 : 0], 1) : __shfl_up(D[0], 2);
     int b1s = __shfl_up(st[NS - 1], 1), b2s = NS >= 2 ? __shfl_up(st[NS >= 2 ? NS - 2 : 0], 1) : __shfl_up(st[0], 2);
-    if (lane < 1) b1d = SPOT_NEG, b1s = -1;
-    if (lane < (NS >= 2 ? 1 : 2)) b2d = SPOT_NEG, b2s = -1;
-    const long long qs = spot_quantize(ps);
+    if (lane < 1) b1d = FX_NEG, b1s = -1;
+    if (lane < (NS >= 2 ? 1 : 2)) b2d = FX_NEG, b2s = -1;
+    const long long qs = fx_quantize(ps);
     long long nd[NS];
     int nst[NS];
 #pragma unroll
     for (int k = 0; k < NS; ++k) {
       const int s = lane * NS + k;
-      long long e = spot_quantize(pf[k]) - qs;
+      long long e = fx_quantize(pf[k]) - qs;
       e = e < 0 ? e : 0;
       long long a1 = k >= 1 ? D[k >= 1 ? k - 1 : 0] : b1d;
       int s1 = k >= 1 ? st[k >= 1 ? k - 1 : 0] : b1s;
       if (s == 1) a1 = 0, s1 = t;                                   // the fresh start
       long long a2 = k >= 2 ? D[k >= 2 ? k - 2 : 0] : (k == 1 ? b1d : b2d);
       int s2 = k >= 2 ? st[k >= 2 ? k - 2 : 0] : (k == 1 ? b1s : b2s);
-      if (!skp[k]) a2 = SPOT_NEG;
+      if (!skp[k]) a2 = FX_NEG;
       long long best = D[k];
       int bs = st[k];
       if (a1 > best) best = a1, bs = s1;
       if (a2 > best) best = a2, bs = s2;
-      const bool live = best != SPOT_NEG && s >= 1;                 // (state 0 is not computed: it stays dead)
-      nd[k] = live ? best + e : SPOT_NEG;
+      const bool live = best != FX_NEG && s >= 1;                   // (state 0 is not computed: it stays dead)
+      nd[k] = live ? best + e : FX_NEG;
       nst[k] = live ? bs : -1;
     }
-    long long fd = SPOT_NEG;
+    long long fd = FX_NEG;
     int fs = -1;
 #pragma unroll
     for (int k = 0; k < NS; ++k) {
@@ -157,7 +143,7 @@ __global__ void __launch_bounds__(SPOT_NT) k_spot(SpotP p) {
     ps = ns;
     if (lane == f_lane) {
       if (tr_d) tr_d[t] = fd, tr_s[t] = fs;                         // t < lim <= T <= trace_pitch
-      if (fd != SPOT_NEG) {
+      if (fd != FX_NEG) {
         const long long n = (long long)t - fs + 1;                  // 0 <= fs <= t
         if (n <= max_span && fd >= thr * n) {                       // a candidate
           if (open && fs <= h_end) {                                // overlaps the open hit: the higher mean stays

@@ -6,10 +6,10 @@
 // tail (at most 3).  Each lane keeps the largest key it saw, six __shfl_xor steps spread the wave's maximum, lane 0 subtracts
 // the penalty with one __fsub_rn and stores one float.  Every byte of logp is read once, so the kernel is memory-bound:
 // 4 B T C bytes in, 4 B T out.  LDS: none.  Global memory sees plain vector stores.  Nothing is allocated and no length is read
-// on the host.
+// on the host.  The key (align_key of the host statement) is qasr_fixed_dev.h's fx_key.
 #include <climits>
 
-#include "qasr_internal.h"
+#include "qasr_fixed_dev.h"
 
 namespace qasr {
 
@@ -25,8 +25,6 @@ struct StarP {
   int T, C;
   float penalty;
 };
-
-__device__ __forceinline__ int star_key(int bits) { return bits ^ ((bits >> 31) & 0x7fffffff); }   // align_key
 
 __global__ void __launch_bounds__(STAR_NT) k_star(StarP p) {
   const int lane = threadIdx.x & (STAR_WAVE - 1);
@@ -44,18 +42,18 @@ __global__ void __launch_bounds__(STAR_NT) k_star(StarP p) {
   const int head = min((int)((4 - (((uintptr_t)row >> 2) & 3)) & 3), C);       // floats before the first 16-byte boundary
   const int nvec = (C - head) >> 2, tail0 = head + 4 * nvec;        // float4s; the first float behind them
   int best = INT_MIN;
-  if (lane < head) best = star_key(__float_as_int(row[lane]));      // head <= 3
+  if (lane < head) best = fx_key(__float_as_int(row[lane]));        // head <= 3
   const float4* const v = reinterpret_cast<const float4*>(row + head);
   for (int i = lane; i < nvec; i += STAR_WAVE) {                    // head + 4 i + 3 < head + 4 nvec <= C
     const float4 x = v[i];
-    const int k0 = star_key(__float_as_int(x.x)), k1 = star_key(__float_as_int(x.y));
-    const int k2 = star_key(__float_as_int(x.z)), k3 = star_key(__float_as_int(x.w));
+    const int k0 = fx_key(__float_as_int(x.x)), k1 = fx_key(__float_as_int(x.y));
+    const int k2 = fx_key(__float_as_int(x.z)), k3 = fx_key(__float_as_int(x.w));
     best = max(best, max(max(k0, k1), max(k2, k3)));
   }
-  if (tail0 + lane < C) best = max(best, star_key(__float_as_int(row[tail0 + lane])));     // C - tail0 <= 3
+  if (tail0 + lane < C) best = max(best, fx_key(__float_as_int(row[tail0 + lane])));       // C - tail0 <= 3
 #pragma unroll
   for (int o = STAR_WAVE / 2; o >= 1; o >>= 1) best = max(best, __shfl_xor(best, o));
-  if (lane == 0) *out = __fsub_rn(__int_as_float(star_key(best)), p.penalty);
+  if (lane == 0) *out = __fsub_rn(__int_as_float(fx_key(best)), p.penalty);
 }
 
 int launch_star(hipStream_t s, const qasr_ctc_star_args& a) {

@@ -329,8 +329,8 @@ struct StreamBeamRun {
           atomicOr(&L.child[ps], 1ull << nl);
         }
       }
-      const long long pnbn = beam_lae(a, e, L.tab);
-      L.k_pb[j] = pbn, L.k_pnb[j] = pnbn, L.k_sc[j] = beam_lae(pbn, pnbn, L.tab);
+      const long long pnbn = fx_lae(a, e, L.tab);
+      L.k_pb[j] = pbn, L.k_pnb[j] = pnbn, L.k_sc[j] = fx_lae(pbn, pnbn, L.tab);
     }
     __syncthreads();
     const int lg = nb > 1 ? 32 - __clz(nb - 1) : 0;
