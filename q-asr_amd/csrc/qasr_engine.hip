@@ -57,6 +57,21 @@ static int fail(int code, const char* fmt, ...) {
     if (_e != hipSuccess) return fail(QASR_ERR_HIP, "%s: %s", #x, hipGetErrorString(_e)); \
   } while (0)
 
+// How an entry point that takes an args struct opens and closes: the struct is there and of this library's size; the launch
+// function's code, then HIP's.  `who` is the entry's name in the message.  (Entries that accept an older, shorter struct and
+// those whose text differs keep their own lines.)
+template <class A>
+static int args_check(const char* who, const A* a) {
+  if (!a) return fail(QASR_ERR_ARG, "%s: args is NULL", who);
+  if (a->struct_size != sizeof(A)) return fail(QASR_ERR_ARG, "%s: struct_size %u is not %zu", who, a->struct_size, sizeof(A));
+  return QASR_OK;
+}
+static int launched(const char* who, int rc) {
+  if (rc) return fail(rc, "%s: launch", who);
+  HIPCHK(hipGetLastError());
+  return QASR_OK;
+}
+
 static inline int rup(int x, int m) { return (x + m - 1) / m * m; }
 static inline size_t dt_size(uint32_t dt) { return (dt == QASR_DT_F32 || dt == QASR_DT_I32) ? 4 : 1; }
 
@@ -1091,16 +1106,11 @@ int qasr_ctc_collapse(void* stream, const int32_t* tokens, const float* frame_sc
   if (!tokens || !out || B < 1 || T < 1) return fail(QASR_ERR_ARG, "ctc_collapse: tokens / out NULL or B, T < 1");
   int rc = ctc_out_check(out, frame_score != nullptr, "ctc_collapse");
   if (rc) return rc;
-  rc = launch_ctc((hipStream_t)stream, tokens, frame_score, lens, B, T, blank, *out);
-  if (rc) return fail(rc, "ctc_collapse: launch");
-  HIPCHK(hipGetLastError());
-  return QASR_OK;
+  return launched("ctc_collapse", launch_ctc((hipStream_t)stream, tokens, frame_score, lens, B, T, blank, *out));
 }
 
 int qasr_ctc_topn(void* stream, const qasr_ctc_topn_args* a) {
-  if (!a) return fail(QASR_ERR_ARG, "ctc_topn: args is NULL");
-  if (a->struct_size != sizeof(qasr_ctc_topn_args))
-    return fail(QASR_ERR_ARG, "ctc_topn: struct_size %u is not %zu", a->struct_size, sizeof(qasr_ctc_topn_args));
+  if (int rc = args_check("ctc_topn", a)) return rc;
   if (!a->log_probs || !a->cand_id || !a->cand_q) return fail(QASR_ERR_ARG, "ctc_topn: log_probs, cand_id and cand_q are required");
   if (a->B < 1 || a->T < 1 || a->T > QASR_BEAM_MAX_FRAMES || a->C < 1 || (int64_t)a->B * a->T >= (1ll << 31))
     return fail(QASR_ERR_ARG, "ctc_topn: B %d, T %d (1 .. %d), C %d out of range", a->B, a->T, QASR_BEAM_MAX_FRAMES, a->C);
@@ -1109,10 +1119,7 @@ int qasr_ctc_topn(void* stream, const qasr_ctc_topn_args* a) {
   if (a->pitch_frame < a->C || a->pitch_utt < (int64_t)a->T * a->pitch_frame)
     return fail(QASR_ERR_ARG, "ctc_topn: pitch_frame %lld < C or pitch_utt %lld < T * pitch_frame", (long long)a->pitch_frame,
                 (long long)a->pitch_utt);
-  int rc = launch_topn((hipStream_t)stream, *a);
-  if (rc) return fail(rc, "ctc_topn: launch");
-  HIPCHK(hipGetLastError());
-  return QASR_OK;
+  return launched("ctc_topn", launch_topn((hipStream_t)stream, *a));
 }
 
 static int beam_shape_ok(int B, int T, int W) {
@@ -1123,27 +1130,52 @@ size_t qasr_ctc_beam_workspace_bytes(int B, int T, int beam_width) {
   return beam_shape_ok(B, T, beam_width) ? beam_workspace_bytes(B, T, beam_width) : 0;
 }
 
-int qasr_ctc_beam(void* stream, const qasr_ctc_beam_args* a) {
-  if (!a) return fail(QASR_ERR_ARG, "ctc_beam: args is NULL");
-  if (a->struct_size != sizeof(qasr_ctc_beam_args))
-    return fail(QASR_ERR_ARG, "ctc_beam: struct_size %u is not %zu", a->struct_size, sizeof(qasr_ctc_beam_args));
-  if (!a->cand_id || !a->cand_q || !a->lae_table || !a->workspace || !a->labels || !a->n_labels || !a->score || !a->n_hyps)
-    return fail(QASR_ERR_ARG, "ctc_beam: a required pointer is NULL (only lens is optional)");
+// ---- the checks the beam entry points share, offline and streaming, with the entry's name in the message; 0 or the error's code.
+// qasr_ctc_beam, _lm and _boost: their structs open with the same fields but are three types, hence the templates.  Each entry
+// words its own pointer refusal (what is optional differs).
+static int beam_cand_check(const char* who, int N, int n_best, int beam_width, int blank, uint32_t lae_entries) {
+  if (N < 1 || N > QASR_BEAM_MAX_CANDIDATES) return fail(QASR_ERR_ARG, "%s: N %d is outside 1 .. %d", who, N, QASR_BEAM_MAX_CANDIDATES);
+  if (n_best < 1 || n_best > beam_width || blank < 0)
+    return fail(QASR_ERR_ARG, "%s: n_best %d is outside 1 .. beam_width, or blank %d < 0", who, n_best, blank);
+  if (lae_entries != QASR_BEAM_TABLE_ENTRIES) return fail(QASR_ERR_ARG, "%s: lae_entries %u is not %d", who, lae_entries, QASR_BEAM_TABLE_ENTRIES);
+  return 0;
+}
+extern "C++" {                                                               // (templates: not inside the extern "C" block around them)
+template <class A>
+static bool beam_ptrs_ok(const A* a) {
+  return a->cand_id && a->cand_q && a->lae_table && a->workspace && a->labels && a->n_labels && a->score && a->n_hyps;
+}
+template <class A>
+static int beam_shape_check(const char* who, const A* a) {                 // shape, N, n_best / blank, table, workspace
   if (!beam_shape_ok(a->B, a->T, a->beam_width))
-    return fail(QASR_ERR_ARG, "ctc_beam: B %d, T %d (1 .. %d) or beam_width %d (1 .. %d) out of range", a->B, a->T,
-                QASR_BEAM_MAX_FRAMES, a->beam_width, QASR_BEAM_MAX_WIDTH);
-  if (a->N < 1 || a->N > QASR_BEAM_MAX_CANDIDATES)
-    return fail(QASR_ERR_ARG, "ctc_beam: N %d is outside 1 .. %d", a->N, QASR_BEAM_MAX_CANDIDATES);
-  if (a->n_best < 1 || a->n_best > a->beam_width || a->blank < 0)
-    return fail(QASR_ERR_ARG, "ctc_beam: n_best %d is outside 1 .. beam_width, or blank %d < 0", a->n_best, a->blank);
-  if (a->lae_entries != QASR_BEAM_TABLE_ENTRIES)
-    return fail(QASR_ERR_ARG, "ctc_beam: lae_entries %u is not %d", a->lae_entries, QASR_BEAM_TABLE_ENTRIES);
+    return fail(QASR_ERR_ARG, "%s: B %d, T %d (1 .. %d) or beam_width %d (1 .. %d) out of range", who, a->B, a->T, QASR_BEAM_MAX_FRAMES,
+                a->beam_width, QASR_BEAM_MAX_WIDTH);
+  if (int rc = beam_cand_check(who, a->N, a->n_best, a->beam_width, a->blank, a->lae_entries)) return rc;
   const size_t need = beam_workspace_bytes(a->B, a->T, a->beam_width);
-  if (a->workspace_bytes < need) return fail(QASR_ERR_ARG, "ctc_beam: workspace of %zu bytes, %zu needed", a->workspace_bytes, need);
-  int rc = launch_beam((hipStream_t)stream, *a);
-  if (rc) return fail(rc, "ctc_beam: launch");
-  HIPCHK(hipGetLastError());
-  return QASR_OK;
+  if (a->workspace_bytes < need) return fail(QASR_ERR_ARG, "%s: workspace of %zu bytes, %zu needed", who, a->workspace_bytes, need);
+  return 0;
+}
+}
+static int beam_blob_check(const char* who, const char* what, const void* blob, size_t bytes) {     // a packed model (`lm`) or phrase set (`boost`)
+  if (((uintptr_t)blob & 15) != 0 || bytes < 128 || bytes > (size_t)INT32_MAX)
+    return fail(QASR_ERR_ARG, "%s: %s must be 16-byte aligned and 128 .. 2^31 - 1 bytes, got %zu", who, what, bytes);
+  return 0;
+}
+static int beam_lm_check(const char* who, const void* lm, size_t lm_bytes, int alpha_q, int beta_q) {
+  if (int rc = beam_blob_check(who, "lm", lm, lm_bytes)) return rc;
+  if (alpha_q < 0 || alpha_q > QASR_LM_MAX_WEIGHT || beta_q < -QASR_LM_MAX_WEIGHT || beta_q > QASR_LM_MAX_WEIGHT)
+    return fail(QASR_ERR_ARG, "%s: alpha_q %d outside 0 .. 16 * 2^16 or |beta_q| %d above it", who, alpha_q, beta_q);
+  return 0;
+}
+static int beam_space_check(const char* who, int space, int blank) {
+  return space < -1 || space == blank ? fail(QASR_ERR_ARG, "%s: space %d must be a label other than blank, or -1", who, space) : 0;
+}
+
+int qasr_ctc_beam(void* stream, const qasr_ctc_beam_args* a) {
+  if (int rc = args_check("ctc_beam", a)) return rc;
+  if (!beam_ptrs_ok(a)) return fail(QASR_ERR_ARG, "ctc_beam: a required pointer is NULL (only lens is optional)");
+  if (int rc = beam_shape_check("ctc_beam", a)) return rc;
+  return launched("ctc_beam", launch_beam((hipStream_t)stream, *a));
 }
 
 // Host-only validation of a packed n-gram model (qasr/ngram.py states the layout); k_beam_lm trusts what passes here.
@@ -1213,33 +1245,12 @@ int qasr_lm_check(const void* blob, size_t bytes, int n_labels) {
 }
 
 int qasr_ctc_beam_lm(void* stream, const qasr_ctc_beam_lm_args* a) {
-  if (!a) return fail(QASR_ERR_ARG, "ctc_beam_lm: args is NULL");
-  if (a->struct_size != sizeof(qasr_ctc_beam_lm_args))
-    return fail(QASR_ERR_ARG, "ctc_beam_lm: struct_size %u is not %zu", a->struct_size, sizeof(qasr_ctc_beam_lm_args));
-  if (!a->cand_id || !a->cand_q || !a->lae_table || !a->workspace || !a->labels || !a->n_labels || !a->score || !a->n_hyps ||
-      !a->lm || !a->lm_score)
-    return fail(QASR_ERR_ARG, "ctc_beam_lm: a required pointer is NULL (only lens is optional)");
-  if (!beam_shape_ok(a->B, a->T, a->beam_width))
-    return fail(QASR_ERR_ARG, "ctc_beam_lm: B %d, T %d (1 .. %d) or beam_width %d (1 .. %d) out of range", a->B, a->T,
-                QASR_BEAM_MAX_FRAMES, a->beam_width, QASR_BEAM_MAX_WIDTH);
-  if (a->N < 1 || a->N > QASR_BEAM_MAX_CANDIDATES)
-    return fail(QASR_ERR_ARG, "ctc_beam_lm: N %d is outside 1 .. %d", a->N, QASR_BEAM_MAX_CANDIDATES);
-  if (a->n_best < 1 || a->n_best > a->beam_width || a->blank < 0)
-    return fail(QASR_ERR_ARG, "ctc_beam_lm: n_best %d is outside 1 .. beam_width, or blank %d < 0", a->n_best, a->blank);
-  if (a->lae_entries != QASR_BEAM_TABLE_ENTRIES)
-    return fail(QASR_ERR_ARG, "ctc_beam_lm: lae_entries %u is not %d", a->lae_entries, QASR_BEAM_TABLE_ENTRIES);
-  const size_t need = beam_workspace_bytes(a->B, a->T, a->beam_width);
-  if (a->workspace_bytes < need) return fail(QASR_ERR_ARG, "ctc_beam_lm: workspace of %zu bytes, %zu needed", a->workspace_bytes, need);
-  if (((uintptr_t)a->lm & 15) != 0 || a->lm_bytes < 128 || a->lm_bytes > (size_t)INT32_MAX)
-    return fail(QASR_ERR_ARG, "ctc_beam_lm: lm must be 16-byte aligned and 128 .. 2^31 - 1 bytes, got %zu", a->lm_bytes);
-  if (a->alpha_q < 0 || a->alpha_q > QASR_LM_MAX_WEIGHT || a->beta_q < -QASR_LM_MAX_WEIGHT || a->beta_q > QASR_LM_MAX_WEIGHT)
-    return fail(QASR_ERR_ARG, "ctc_beam_lm: alpha_q %d outside 0 .. 16 * 2^16 or |beta_q| %d above it", a->alpha_q, a->beta_q);
-  if (a->space < -1 || a->space == a->blank)
-    return fail(QASR_ERR_ARG, "ctc_beam_lm: space %d must be a label other than blank, or -1", a->space);
-  int rc = launch_beam_lm((hipStream_t)stream, *a);
-  if (rc) return fail(rc, "ctc_beam_lm: launch");
-  HIPCHK(hipGetLastError());
-  return QASR_OK;
+  if (int rc = args_check("ctc_beam_lm", a)) return rc;
+  if (!beam_ptrs_ok(a) || !a->lm || !a->lm_score) return fail(QASR_ERR_ARG, "ctc_beam_lm: a required pointer is NULL (only lens is optional)");
+  if (int rc = beam_shape_check("ctc_beam_lm", a)) return rc;
+  if (int rc = beam_lm_check("ctc_beam_lm", a->lm, a->lm_bytes, a->alpha_q, a->beta_q)) return rc;
+  if (int rc = beam_space_check("ctc_beam_lm", a->space, a->blank)) return rc;
+  return launched("ctc_beam_lm", launch_beam_lm((hipStream_t)stream, *a));
 }
 
 // Host-only validation of a packed phrase set (qasr/boost.py states the layout); k_beam_boost trusts what passes here.
@@ -1289,39 +1300,17 @@ int qasr_boost_check(const void* blob, size_t bytes, int n_labels) {
 }
 
 int qasr_ctc_beam_boost(void* stream, const qasr_ctc_beam_boost_args* a) {
-  if (!a) return fail(QASR_ERR_ARG, "ctc_beam_boost: args is NULL");
-  if (a->struct_size != sizeof(qasr_ctc_beam_boost_args))
-    return fail(QASR_ERR_ARG, "ctc_beam_boost: struct_size %u is not %zu", a->struct_size, sizeof(qasr_ctc_beam_boost_args));
-  if (!a->cand_id || !a->cand_q || !a->lae_table || !a->workspace || !a->labels || !a->n_labels || !a->score || !a->n_hyps ||
-      !a->boost || !a->boost_score || (a->lm && !a->lm_score))
+  if (int rc = args_check("ctc_beam_boost", a)) return rc;
+  if (!beam_ptrs_ok(a) || !a->boost || !a->boost_score || (a->lm && !a->lm_score))
     return fail(QASR_ERR_ARG, "ctc_beam_boost: a required pointer is NULL (only lens and lm are optional; lm needs lm_score)");
-  if (!beam_shape_ok(a->B, a->T, a->beam_width))
-    return fail(QASR_ERR_ARG, "ctc_beam_boost: B %d, T %d (1 .. %d) or beam_width %d (1 .. %d) out of range", a->B, a->T,
-                QASR_BEAM_MAX_FRAMES, a->beam_width, QASR_BEAM_MAX_WIDTH);
-  if (a->N < 1 || a->N > QASR_BEAM_MAX_CANDIDATES)
-    return fail(QASR_ERR_ARG, "ctc_beam_boost: N %d is outside 1 .. %d", a->N, QASR_BEAM_MAX_CANDIDATES);
-  if (a->n_best < 1 || a->n_best > a->beam_width || a->blank < 0)
-    return fail(QASR_ERR_ARG, "ctc_beam_boost: n_best %d is outside 1 .. beam_width, or blank %d < 0", a->n_best, a->blank);
-  if (a->lae_entries != QASR_BEAM_TABLE_ENTRIES)
-    return fail(QASR_ERR_ARG, "ctc_beam_boost: lae_entries %u is not %d", a->lae_entries, QASR_BEAM_TABLE_ENTRIES);
-  const size_t need = beam_workspace_bytes(a->B, a->T, a->beam_width);
-  if (a->workspace_bytes < need) return fail(QASR_ERR_ARG, "ctc_beam_boost: workspace of %zu bytes, %zu needed", a->workspace_bytes, need);
-  if (a->lm) {
-    if (((uintptr_t)a->lm & 15) != 0 || a->lm_bytes < 128 || a->lm_bytes > (size_t)INT32_MAX)
-      return fail(QASR_ERR_ARG, "ctc_beam_boost: lm must be 16-byte aligned and 128 .. 2^31 - 1 bytes, got %zu", a->lm_bytes);
-    if (a->alpha_q < 0 || a->alpha_q > QASR_LM_MAX_WEIGHT || a->beta_q < -QASR_LM_MAX_WEIGHT || a->beta_q > QASR_LM_MAX_WEIGHT)
-      return fail(QASR_ERR_ARG, "ctc_beam_boost: alpha_q %d outside 0 .. 16 * 2^16 or |beta_q| %d above it", a->alpha_q, a->beta_q);
-  }
-  if (((uintptr_t)a->boost & 15) != 0 || a->boost_bytes < 128 || a->boost_bytes > (size_t)INT32_MAX)
-    return fail(QASR_ERR_ARG, "ctc_beam_boost: boost must be 16-byte aligned and 128 .. 2^31 - 1 bytes, got %zu", a->boost_bytes);
-  if (a->space < -1 || a->space == a->blank)
-    return fail(QASR_ERR_ARG, "ctc_beam_boost: space %d must be a label other than blank, or -1", a->space);
+  if (int rc = beam_shape_check("ctc_beam_boost", a)) return rc;
+  if (a->lm)
+    if (int rc = beam_lm_check("ctc_beam_boost", a->lm, a->lm_bytes, a->alpha_q, a->beta_q)) return rc;
+  if (int rc = beam_blob_check("ctc_beam_boost", "boost", a->boost, a->boost_bytes)) return rc;
+  if (int rc = beam_space_check("ctc_beam_boost", a->space, a->blank)) return rc;
   if (a->whole_words != 0 && a->space < 0)
     return fail(QASR_ERR_ARG, "ctc_beam_boost: whole words need the space label, got %d", a->space);
-  int rc = launch_beam_boost((hipStream_t)stream, *a);
-  if (rc) return fail(rc, "ctc_beam_boost: launch");
-  HIPCHK(hipGetLastError());
-  return QASR_OK;
+  return launched("ctc_beam_boost", launch_beam_boost((hipStream_t)stream, *a));
 }
 
 // ---- the checks the CTC lattice entry points below share, with the entry's name in the message; 0 or the error's code
@@ -1378,10 +1367,7 @@ int qasr_ctc_align(void* stream, const qasr_ctc_align_args* given) {
   if (int rc = ctc_workspace_check("ctc_align", a->workspace_bytes, align_workspace_bytes(a->P, a->T, a->max_labels))) return rc;
   if (a->star_logp)
     if (int rc = ctc_star_pitch_check("ctc_align", a->star_pitch, a->T)) return rc;
-  int rc = launch_align((hipStream_t)stream, *a);
-  if (rc) return fail(rc, "ctc_align: launch");
-  HIPCHK(hipGetLastError());
-  return QASR_OK;
+  return launched("ctc_align", launch_align((hipStream_t)stream, *a));
 }
 
 // ---- CTC posteriors along an alignment (k_post, qasr_post.hip): the checks of include/qasr.h, then one launch
@@ -1390,9 +1376,7 @@ size_t qasr_ctc_post_workspace_bytes(int P, int T) {
 }
 
 int qasr_ctc_post(void* stream, const qasr_ctc_post_args* a) {
-  if (!a) return fail(QASR_ERR_ARG, "ctc_post: args is NULL");
-  if (a->struct_size != sizeof(qasr_ctc_post_args))
-    return fail(QASR_ERR_ARG, "ctc_post: struct_size %u is not %zu", a->struct_size, sizeof(qasr_ctc_post_args));
+  if (int rc = args_check("ctc_post", a)) return rc;
   if (!a->log_probs || !a->targets || !a->target_lens || !a->workspace || !a->ok)
     return fail(QASR_ERR_ARG, "ctc_post: log_probs, targets, target_lens, workspace and ok are required");
   if (!a->start || !a->nframes || !a->frame_post || !a->label_post)
@@ -1411,10 +1395,7 @@ int qasr_ctc_post(void* stream, const qasr_ctc_post_args* a) {
   if (int rc = ctc_workspace_check("ctc_post", a->workspace_bytes, post_workspace_bytes(a->P, a->T))) return rc;
   if (a->star_logp)
     if (int rc = ctc_star_pitch_check("ctc_post", a->star_pitch, a->T)) return rc;
-  int rc = launch_post((hipStream_t)stream, *a);
-  if (rc) return fail(rc, "ctc_post: launch");
-  HIPCHK(hipGetLastError());
-  return QASR_OK;
+  return launched("ctc_post", launch_post((hipStream_t)stream, *a));
 }
 
 // ---- banded CTC alignment (k_align_band, qasr_align_band.hip): the checks of include/qasr.h, then one launch
@@ -1448,10 +1429,7 @@ int qasr_ctc_align_band(void* stream, const qasr_ctc_align_band_args* given) {
   if (int rc = ctc_workspace_check("ctc_align_band", a->workspace_bytes, align_band_workspace_bytes(a->B, a->T, a->band_states))) return rc;
   if (a->star_logp)
     if (int rc = ctc_star_pitch_check("ctc_align_band", a->star_pitch, a->T)) return rc;
-  int rc = launch_align_band((hipStream_t)stream, *a);
-  if (rc) return fail(rc, "ctc_align_band: launch");
-  HIPCHK(hipGetLastError());
-  return QASR_OK;
+  return launched("ctc_align_band", launch_align_band((hipStream_t)stream, *a));
 }
 
 // ---- CTC posteriors inside the band (k_post_band, qasr_post_band.hip): the checks of include/qasr.h, then one launch
@@ -1460,9 +1438,7 @@ size_t qasr_ctc_post_band_workspace_bytes(int B, int T) {
 }
 
 int qasr_ctc_post_band(void* stream, const qasr_ctc_post_band_args* a) {
-  if (!a) return fail(QASR_ERR_ARG, "ctc_post_band: args is NULL");
-  if (a->struct_size != sizeof(qasr_ctc_post_band_args))
-    return fail(QASR_ERR_ARG, "ctc_post_band: struct_size %u is not %zu", a->struct_size, sizeof(qasr_ctc_post_band_args));
+  if (int rc = args_check("ctc_post_band", a)) return rc;
   if (!a->log_probs || !a->targets || !a->target_lens || !a->workspace || !a->ok)
     return fail(QASR_ERR_ARG, "ctc_post_band: log_probs, targets, target_lens, workspace and ok are required");
   if (!a->start || !a->nframes || !a->band_base || !a->frame_post || !a->label_post)
@@ -1481,17 +1457,12 @@ int qasr_ctc_post_band(void* stream, const qasr_ctc_post_band_args* a) {
   if (int rc = ctc_workspace_check("ctc_post_band", a->workspace_bytes, post_band_workspace_bytes(a->B, a->T))) return rc;
   if (a->star_logp)
     if (int rc = ctc_star_pitch_check("ctc_post_band", a->star_pitch, a->T)) return rc;
-  int rc = launch_post_band((hipStream_t)stream, *a);
-  if (rc) return fail(rc, "ctc_post_band: launch");
-  HIPCHK(hipGetLastError());
-  return QASR_OK;
+  return launched("ctc_post_band", launch_post_band((hipStream_t)stream, *a));
 }
 
 // ---- the wildcard's emission plane (k_star, qasr_star.hip): the checks of include/qasr.h, then one launch
 int qasr_ctc_star(void* stream, const qasr_ctc_star_args* a) {
-  if (!a) return fail(QASR_ERR_ARG, "ctc_star: args is NULL");
-  if (a->struct_size != sizeof(qasr_ctc_star_args))
-    return fail(QASR_ERR_ARG, "ctc_star: struct_size %u is not %zu", a->struct_size, sizeof(qasr_ctc_star_args));
+  if (int rc = args_check("ctc_star", a)) return rc;
   if (!a->log_probs || !a->star) return fail(QASR_ERR_ARG, "ctc_star: log_probs and star are required");
   if (a->B < 1 || a->T < 1 || a->C < 1) return fail(QASR_ERR_ARG, "ctc_star: B %d, T %d or C %d out of range", a->B, a->T, a->C);
   if (int rc = ctc_pitch_check("ctc_star", a->T, a->C, a->pitch_frame, a->pitch_utt)) return rc;
@@ -1506,9 +1477,7 @@ int qasr_ctc_star(void* stream, const qasr_ctc_star_args* a) {
 
 // ---- keyword spotting (k_spot, qasr_spot.hip): the checks of include/qasr.h, then one launch
 int qasr_ctc_spot(void* stream, const qasr_ctc_spot_args* a) {
-  if (!a) return fail(QASR_ERR_ARG, "ctc_spot: args is NULL");
-  if (a->struct_size != sizeof(qasr_ctc_spot_args))
-    return fail(QASR_ERR_ARG, "ctc_spot: struct_size %u is not %zu", a->struct_size, sizeof(qasr_ctc_spot_args));
+  if (int rc = args_check("ctc_spot", a)) return rc;
   if (!a->log_probs || !a->star_logp || !a->targets || !a->target_lens)
     return fail(QASR_ERR_ARG, "ctc_spot: log_probs, star_logp, targets and target_lens are required");
   if (!a->hit_start || !a->hit_end || !a->hit_score || !a->n_hits || !a->ok)
@@ -1529,10 +1498,7 @@ int qasr_ctc_spot(void* stream, const qasr_ctc_spot_args* a) {
   if (!a->trace_score != !a->trace_start) return fail(QASR_ERR_ARG, "ctc_spot: trace_score and trace_start go together");
   if (a->trace_score && a->trace_pitch < a->T)
     return fail(QASR_ERR_ARG, "ctc_spot: trace_pitch %lld < T %d", (long long)a->trace_pitch, a->T);
-  int rc = launch_spot((hipStream_t)stream, *a);
-  if (rc) return fail(rc, "ctc_spot: launch");
-  HIPCHK(hipGetLastError());
-  return QASR_OK;
+  return launched("ctc_spot", launch_spot((hipStream_t)stream, *a));
 }
 
 // ---- polyphase resampler (k_resample, qasr_resample.hip): host-only validation of a packed table (qasr/resample.py states
@@ -1592,9 +1558,7 @@ int qasr_resample_out_samples(int in_samples, int L, int M) {
 }
 
 int qasr_resample(void* stream, const qasr_resample_args* a) {
-  if (!a) return fail(QASR_ERR_ARG, "resample: args is NULL");
-  if (a->struct_size != sizeof(qasr_resample_args))
-    return fail(QASR_ERR_ARG, "resample: struct_size %u is not %zu", a->struct_size, sizeof(qasr_resample_args));
+  if (int rc = args_check("resample", a)) return rc;
   if (!a->blob || !a->in || !a->in_lens || !a->out || !a->out_lens)
     return fail(QASR_ERR_ARG, "resample: blob, in, in_lens, out and out_lens are required");
   if (a->B < 1 || a->B > 65535) return fail(QASR_ERR_ARG, "resample: B %d is outside 1 .. 65535", a->B);
@@ -1609,32 +1573,22 @@ int qasr_resample(void* stream, const qasr_resample_args* a) {
                 128 + 8 * (size_t)a->L * (size_t)a->W, a->blob_bytes);
   if (a->in_pitch < 0 || a->in_pitch > QASR_RESAMPLE_MAX_PITCH || a->out_pitch < 0 || a->out_pitch > QASR_RESAMPLE_MAX_PITCH)
     return fail(QASR_ERR_ARG, "resample: in_pitch %lld or out_pitch %lld is outside 0 .. 2^38", (long long)a->in_pitch, (long long)a->out_pitch);
-  int rc = launch_resample((hipStream_t)stream, *a);
-  if (rc) return fail(rc, "resample: launch");
-  HIPCHK(hipGetLastError());
-  return QASR_OK;
+  return launched("resample", launch_resample((hipStream_t)stream, *a));
 }
 
 // ---- long recordings (k_cut, k_stitch, qasr_longform.hip): the checks of include/qasr.h and one launch each
 int qasr_longform_cut(void* stream, const qasr_longform_cut_args* a) {
-  if (!a) return fail(QASR_ERR_ARG, "longform_cut: args is NULL");
-  if (a->struct_size != sizeof(qasr_longform_cut_args))
-    return fail(QASR_ERR_ARG, "longform_cut: struct_size %u is not %zu", a->struct_size, sizeof(qasr_longform_cut_args));
+  if (int rc = args_check("longform_cut", a)) return rc;
   if (!a->audio || !a->lens || !a->table || !a->windows || !a->window_lens)
     return fail(QASR_ERR_ARG, "longform_cut: audio, lens, table, windows and window_lens are required");
   if (a->Wn < 1 || a->Wn > 65535) return fail(QASR_ERR_ARG, "longform_cut: Wn %d is outside 1 .. 65535", a->Wn);
   if (a->R < 1 || a->Wl < 1 || a->pitch < 0)
     return fail(QASR_ERR_ARG, "longform_cut: R %d, Wl %d (both >= 1) or pitch %lld (>= 0) out of range", a->R, a->Wl, (long long)a->pitch);
-  int rc = launch_longform_cut((hipStream_t)stream, *a);
-  if (rc) return fail(rc, "longform_cut: launch");
-  HIPCHK(hipGetLastError());
-  return QASR_OK;
+  return launched("longform_cut", launch_longform_cut((hipStream_t)stream, *a));
 }
 
 int qasr_longform_stitch(void* stream, const qasr_longform_stitch_args* a) {
-  if (!a) return fail(QASR_ERR_ARG, "longform_stitch: args is NULL");
-  if (a->struct_size != sizeof(qasr_longform_stitch_args))
-    return fail(QASR_ERR_ARG, "longform_stitch: struct_size %u is not %zu", a->struct_size, sizeof(qasr_longform_stitch_args));
+  if (int rc = args_check("longform_stitch", a)) return rc;
   if (!a->table || !a->enc_lens || !a->tokens || !a->total_frames || !a->seams)
     return fail(QASR_ERR_ARG, "longform_stitch: table, enc_lens, tokens, total_frames and seams are required");
   if (a->Wn < 1) return fail(QASR_ERR_ARG, "longform_stitch: Wn %d < 1", a->Wn);
@@ -1652,10 +1606,7 @@ int qasr_longform_stitch(void* stream, const qasr_longform_stitch_args* a) {
       return fail(QASR_ERR_ARG, "longform_stitch: plane %d: bytes_per_frame %lld is not a positive multiple of 4", k, (long long)q.bytes_per_frame);
     if ((((uintptr_t)q.src | (uintptr_t)q.dst) & 3) != 0) return fail(QASR_ERR_ARG, "longform_stitch: plane %d is not 4-byte aligned", k);
   }
-  int rc = launch_longform_stitch((hipStream_t)stream, *a);
-  if (rc) return fail(rc, "longform_stitch: launch");
-  HIPCHK(hipGetLastError());
-  return QASR_OK;
+  return launched("longform_stitch", launch_longform_stitch((hipStream_t)stream, *a));
 }
 
 // ---- streaming (k_stream_push / _window / _emit, qasr_stream.hip): the checks of include/qasr.h and one launch each
@@ -1673,9 +1624,7 @@ static int stream_geometry(const char* who, int S, int B, int Wl, int C, int Rr,
 }
 
 int qasr_stream_push(void* stream, const qasr_stream_push_args* a) {
-  if (!a) return fail(QASR_ERR_ARG, "stream_push: args is NULL");
-  if (a->struct_size != sizeof(qasr_stream_push_args))
-    return fail(QASR_ERR_ARG, "stream_push: struct_size %u is not %zu", a->struct_size, sizeof(qasr_stream_push_args));
+  if (int rc = args_check("stream_push", a)) return rc;
   if (!a->state || !a->slots || !a->flags || !a->n_new || !a->chunk)
     return fail(QASR_ERR_ARG, "stream_push: state, slots, flags, n_new and chunk are required");
   int rc = stream_geometry("stream_push", a->S, a->B, a->Wl, a->C, 0, a->samples_per_frame, a->state_bytes);
@@ -1683,31 +1632,21 @@ int qasr_stream_push(void* stream, const qasr_stream_push_args* a) {
   if (a->dtype != QASR_PCM_S16 && a->dtype != QASR_PCM_F32) return fail(QASR_ERR_ARG, "stream_push: dtype %d is neither s16 nor f32", a->dtype);
   if (a->pitch < 0) return fail(QASR_ERR_ARG, "stream_push: pitch %lld < 0", (long long)a->pitch);
   if ((uintptr_t)a->state & 15) return fail(QASR_ERR_ARG, "stream_push: state is not 16-byte aligned");
-  rc = launch_stream_push((hipStream_t)stream, *a);
-  if (rc) return fail(rc, "stream_push: launch");
-  HIPCHK(hipGetLastError());
-  return QASR_OK;
+  return launched("stream_push", launch_stream_push((hipStream_t)stream, *a));
 }
 
 int qasr_stream_window(void* stream, const qasr_stream_window_args* a) {
-  if (!a) return fail(QASR_ERR_ARG, "stream_window: args is NULL");
-  if (a->struct_size != sizeof(qasr_stream_window_args))
-    return fail(QASR_ERR_ARG, "stream_window: struct_size %u is not %zu", a->struct_size, sizeof(qasr_stream_window_args));
+  if (int rc = args_check("stream_window", a)) return rc;
   if (!a->state || !a->slots || !a->windows || !a->window_lens || !a->first_frame)
     return fail(QASR_ERR_ARG, "stream_window: state, slots, windows, window_lens and first_frame are required");
   int rc = stream_geometry("stream_window", a->S, a->B, a->Wl, a->C, 0, a->samples_per_frame, a->state_bytes);
   if (rc) return rc;
   if ((uintptr_t)a->state & 15) return fail(QASR_ERR_ARG, "stream_window: state is not 16-byte aligned");
-  rc = launch_stream_window((hipStream_t)stream, *a);
-  if (rc) return fail(rc, "stream_window: launch");
-  HIPCHK(hipGetLastError());
-  return QASR_OK;
+  return launched("stream_window", launch_stream_window((hipStream_t)stream, *a));
 }
 
 int qasr_stream_emit(void* stream, const qasr_stream_emit_args* a) {
-  if (!a) return fail(QASR_ERR_ARG, "stream_emit: args is NULL");
-  if (a->struct_size != sizeof(qasr_stream_emit_args))
-    return fail(QASR_ERR_ARG, "stream_emit: struct_size %u is not %zu", a->struct_size, sizeof(qasr_stream_emit_args));
+  if (int rc = args_check("stream_emit", a)) return rc;
   if (!a->state || !a->slots || !a->flags || !a->tokens || !a->frame_score || !a->enc_lens || !a->first_frame || !a->labels ||
       !a->start || !a->nframes || !a->score || !a->n_new_labels || !a->status || !a->total_frames || !a->utt_score)
     return fail(QASR_ERR_ARG, "stream_emit: every pointer but tail_labels / tail_n is required");
@@ -1717,195 +1656,124 @@ int qasr_stream_emit(void* stream, const qasr_stream_emit_args* a) {
   if ((a->tail_labels == nullptr) != (a->tail_n == nullptr)) return fail(QASR_ERR_ARG, "stream_emit: tail_labels and tail_n come together");
   if (a->tail_labels && a->Ptail < 1) return fail(QASR_ERR_ARG, "stream_emit: Ptail %d < 1", a->Ptail);
   if ((uintptr_t)a->state & 15) return fail(QASR_ERR_ARG, "stream_emit: state is not 16-byte aligned");
-  rc = launch_stream_emit((hipStream_t)stream, *a);
-  if (rc) return fail(rc, "stream_emit: launch");
-  HIPCHK(hipGetLastError());
-  return QASR_OK;
+  return launched("stream_emit", launch_stream_emit((hipStream_t)stream, *a));
 }
 
 // ---- streaming beam search (k_stream_beam, qasr_stream_beam.hip): the checks of include/qasr.h and one launch
 size_t qasr_stream_beam_state_bytes(int S, int beam_width, int F) { return stream_beam_state_bytes(S, beam_width, F); }
 
-int qasr_stream_beam(void* stream, const qasr_stream_beam_args* a) {
-  if (!a) return fail(QASR_ERR_ARG, "stream_beam: args is NULL");
-  if (a->struct_size != sizeof(qasr_stream_beam_args))
-    return fail(QASR_ERR_ARG, "stream_beam: struct_size %u is not %zu", a->struct_size, sizeof(qasr_stream_beam_args));
-  if (!a->state || !a->beam_state || !a->slots || !a->flags || !a->cand_id || !a->cand_q || !a->enc_lens || !a->first_frame ||
-      !a->lae_table || !a->labels || !a->frames || !a->n_new_labels || !a->commit_len || !a->n_live || !a->status ||
-      !a->tail_labels || !a->tail_n || !a->end_labels || !a->end_n_labels || !a->end_score || !a->n_hyps)
-    return fail(QASR_ERR_ARG, "stream_beam: every pointer but lm (and end_lm_score without lm) is required");
-  int rc = stream_geometry("stream_beam", a->S, a->B, a->Wl, a->C, a->Rr, a->samples_per_frame, a->state_bytes);
-  if (rc) return rc;
-  if (a->Tw < 1 || a->Tw > QASR_BEAM_MAX_FRAMES || (int64_t)a->B * a->Tw >= (1ll << 31))
-    return fail(QASR_ERR_ARG, "stream_beam: Tw %d is outside 1 .. %d (or B * Tw >= 2^31)", a->Tw, QASR_BEAM_MAX_FRAMES);
-  if (a->beam_width < 1 || a->beam_width > QASR_BEAM_MAX_WIDTH)
-    return fail(QASR_ERR_ARG, "stream_beam: beam_width %d is outside 1 .. %d", a->beam_width, QASR_BEAM_MAX_WIDTH);
-  if (a->N < 1 || a->N > QASR_BEAM_MAX_CANDIDATES)
-    return fail(QASR_ERR_ARG, "stream_beam: N %d is outside 1 .. %d", a->N, QASR_BEAM_MAX_CANDIDATES);
-  if (a->n_best < 1 || a->n_best > a->beam_width || a->blank < 0)
-    return fail(QASR_ERR_ARG, "stream_beam: n_best %d is outside 1 .. beam_width, or blank %d < 0", a->n_best, a->blank);
-  if (a->lae_entries != QASR_BEAM_TABLE_ENTRIES)
-    return fail(QASR_ERR_ARG, "stream_beam: lae_entries %u is not %d", a->lae_entries, QASR_BEAM_TABLE_ENTRIES);
-  if (a->Lg < 0 || a->K < 1 || a->K > QASR_STREAM_BEAM_ROUND)
-    return fail(QASR_ERR_ARG, "stream_beam: Lg %d < 0 or K %d outside 1 .. %d", a->Lg, a->K, QASR_STREAM_BEAM_ROUND);
-  if (a->F > QASR_STREAM_BEAM_MAX_RING || (int64_t)a->F < (int64_t)a->Lg + a->K)
-    return fail(QASR_ERR_ARG, "stream_beam: F %d must lie in Lg + K = %lld .. %d", a->F, (long long)a->Lg + a->K, QASR_STREAM_BEAM_MAX_RING);
-  const size_t need = stream_beam_state_bytes(a->S, a->beam_width, a->F);
-  if (!need || a->beam_state_bytes < need)
-    return fail(QASR_ERR_ARG, "stream_beam: beam_state_bytes %zu, qasr_stream_beam_state_bytes gives %zu", a->beam_state_bytes, need);
-  if (((uintptr_t)a->state | (uintptr_t)a->beam_state) & 15) return fail(QASR_ERR_ARG, "stream_beam: state or beam_state is not 16-byte aligned");
-  if (a->max_final_frames < 1 || a->max_final_frames > a->Tw)
-    return fail(QASR_ERR_ARG, "stream_beam: max_final_frames %d is outside 1 .. Tw", a->max_final_frames);
-  if ((int64_t)a->P < (int64_t)a->F + a->max_final_frames || a->Ptail < 1 || a->Pend < a->F)
-    return fail(QASR_ERR_ARG, "stream_beam: P %d < F + max_final_frames = %lld, Ptail %d < 1 or Pend %d < F = %d", a->P,
-                (long long)a->F + a->max_final_frames, a->Ptail, a->Pend, a->F);
-  if (a->lm) {
-    if (!a->end_lm_score) return fail(QASR_ERR_ARG, "stream_beam: end_lm_score is required with lm");
-    if (((uintptr_t)a->lm & 15) != 0 || a->lm_bytes < 128 || a->lm_bytes > (size_t)INT32_MAX)
-      return fail(QASR_ERR_ARG, "stream_beam: lm must be 16-byte aligned and 128 .. 2^31 - 1 bytes, got %zu", a->lm_bytes);
-    if (a->alpha_q < 0 || a->alpha_q > QASR_LM_MAX_WEIGHT || a->beta_q < -QASR_LM_MAX_WEIGHT || a->beta_q > QASR_LM_MAX_WEIGHT)
-      return fail(QASR_ERR_ARG, "stream_beam: alpha_q %d outside 0 .. 16 * 2^16 or |beta_q| %d above it", a->alpha_q, a->beta_q);
-    if (a->space < -1 || a->space == a->blank)
-      return fail(QASR_ERR_ARG, "stream_beam: space %d must be a label other than blank, or -1", a->space);
-  }
-  rc = launch_stream_beam((hipStream_t)stream, *a);
-  if (rc) return fail(rc, "stream_beam: launch");
-  HIPCHK(hipGetLastError());
-  return QASR_OK;
+// What qasr_stream_beam, _boost and _ep ask of the embedded qasr_stream_beam_args, in the order they ask it: the pointers (the
+// entry words that refusal: _ep does not want the END outputs), stream_geometry, the ranges Tw .. F, then the tail from the beam
+// state's size (`need` bytes, by the query that `query` names) to the pitches, then the model.
+static bool stream_beam_step_ptrs(const qasr_stream_beam_args* a) {
+  return a->state && a->beam_state && a->slots && a->flags && a->cand_id && a->cand_q && a->enc_lens && a->first_frame && a->lae_table &&
+         a->labels && a->frames && a->n_new_labels && a->commit_len && a->n_live && a->status && a->tail_labels && a->tail_n;
 }
-
-// ---- streaming phrase boosting (k_stream_beam_boost, qasr_stream_beam_boost.hip): qasr_stream_beam's checks under this
-// call's name (that function stays as it is), the sets' checks and one launch
-size_t qasr_stream_beam_boost_state_bytes(int S, int beam_width, int F) { return stream_beam_boost_state_bytes(S, beam_width, F); }
-
-static int stream_beam_boost_checks(const qasr_stream_beam_args* a, size_t need) {
-  if (a->struct_size != sizeof(qasr_stream_beam_args))
-    return fail(QASR_ERR_ARG, "stream_beam_boost: struct_size %u is not %zu", a->struct_size, sizeof(qasr_stream_beam_args));
-  if (!a->state || !a->beam_state || !a->slots || !a->flags || !a->cand_id || !a->cand_q || !a->enc_lens || !a->first_frame ||
-      !a->lae_table || !a->labels || !a->frames || !a->n_new_labels || !a->commit_len || !a->n_live || !a->status ||
-      !a->tail_labels || !a->tail_n || !a->end_labels || !a->end_n_labels || !a->end_score || !a->n_hyps)
-    return fail(QASR_ERR_ARG, "stream_beam_boost: every pointer but lm (and end_lm_score without lm) is required");
-  int rc = stream_geometry("stream_beam_boost", a->S, a->B, a->Wl, a->C, a->Rr, a->samples_per_frame, a->state_bytes);
-  if (rc) return rc;
-  if (a->Tw < 1 || a->Tw > QASR_BEAM_MAX_FRAMES || (int64_t)a->B * a->Tw >= (1ll << 31))
-    return fail(QASR_ERR_ARG, "stream_beam_boost: Tw %d is outside 1 .. %d (or B * Tw >= 2^31)", a->Tw, QASR_BEAM_MAX_FRAMES);
-  if (a->beam_width < 1 || a->beam_width > QASR_BEAM_MAX_WIDTH)
-    return fail(QASR_ERR_ARG, "stream_beam_boost: beam_width %d is outside 1 .. %d", a->beam_width, QASR_BEAM_MAX_WIDTH);
-  if (a->N < 1 || a->N > QASR_BEAM_MAX_CANDIDATES)
-    return fail(QASR_ERR_ARG, "stream_beam_boost: N %d is outside 1 .. %d", a->N, QASR_BEAM_MAX_CANDIDATES);
-  if (a->n_best < 1 || a->n_best > a->beam_width || a->blank < 0)
-    return fail(QASR_ERR_ARG, "stream_beam_boost: n_best %d is outside 1 .. beam_width, or blank %d < 0", a->n_best, a->blank);
-  if (a->lae_entries != QASR_BEAM_TABLE_ENTRIES)
-    return fail(QASR_ERR_ARG, "stream_beam_boost: lae_entries %u is not %d", a->lae_entries, QASR_BEAM_TABLE_ENTRIES);
-  if (a->Lg < 0 || a->K < 1 || a->K > QASR_STREAM_BEAM_ROUND)
-    return fail(QASR_ERR_ARG, "stream_beam_boost: Lg %d < 0 or K %d outside 1 .. %d", a->Lg, a->K, QASR_STREAM_BEAM_ROUND);
-  if (a->F > QASR_STREAM_BEAM_MAX_RING || (int64_t)a->F < (int64_t)a->Lg + a->K)
-    return fail(QASR_ERR_ARG, "stream_beam_boost: F %d must lie in Lg + K = %lld .. %d", a->F, (long long)a->Lg + a->K, QASR_STREAM_BEAM_MAX_RING);
-  if (!need || a->beam_state_bytes < need)
-    return fail(QASR_ERR_ARG, "stream_beam_boost: beam_state_bytes %zu, qasr_stream_beam_boost_state_bytes gives %zu", a->beam_state_bytes, need);
-  if (((uintptr_t)a->state | (uintptr_t)a->beam_state) & 15) return fail(QASR_ERR_ARG, "stream_beam_boost: state or beam_state is not 16-byte aligned");
-  if (a->max_final_frames < 1 || a->max_final_frames > a->Tw)
-    return fail(QASR_ERR_ARG, "stream_beam_boost: max_final_frames %d is outside 1 .. Tw", a->max_final_frames);
-  if ((int64_t)a->P < (int64_t)a->F + a->max_final_frames || a->Ptail < 1 || a->Pend < a->F)
-    return fail(QASR_ERR_ARG, "stream_beam_boost: P %d < F + max_final_frames = %lld, Ptail %d < 1 or Pend %d < F = %d", a->P,
-                (long long)a->F + a->max_final_frames, a->Ptail, a->Pend, a->F);
-  if (a->lm) {
-    if (!a->end_lm_score) return fail(QASR_ERR_ARG, "stream_beam_boost: end_lm_score is required with lm");
-    if (((uintptr_t)a->lm & 15) != 0 || a->lm_bytes < 128 || a->lm_bytes > (size_t)INT32_MAX)
-      return fail(QASR_ERR_ARG, "stream_beam_boost: lm must be 16-byte aligned and 128 .. 2^31 - 1 bytes, got %zu", a->lm_bytes);
-    if (a->alpha_q < 0 || a->alpha_q > QASR_LM_MAX_WEIGHT || a->beta_q < -QASR_LM_MAX_WEIGHT || a->beta_q > QASR_LM_MAX_WEIGHT)
-      return fail(QASR_ERR_ARG, "stream_beam_boost: alpha_q %d outside 0 .. 16 * 2^16 or |beta_q| %d above it", a->alpha_q, a->beta_q);
-    if (a->space < -1 || a->space == a->blank)
-      return fail(QASR_ERR_ARG, "stream_beam_boost: space %d must be a label other than blank, or -1", a->space);
-  }
-  return QASR_OK;
+static int stream_beam_width_check(const char* who, int W) {
+  return W < 1 || W > QASR_BEAM_MAX_WIDTH ? fail(QASR_ERR_ARG, "%s: beam_width %d is outside 1 .. %d", who, W, QASR_BEAM_MAX_WIDTH) : 0;
 }
-
-int qasr_stream_beam_boost(void* stream, const qasr_stream_beam_boost_args* q) {
-  if (!q) return fail(QASR_ERR_ARG, "stream_beam_boost: args is NULL");
-  if (q->struct_size != sizeof(qasr_stream_beam_boost_args))
-    return fail(QASR_ERR_ARG, "stream_beam_boost: struct_size %u is not %zu", q->struct_size, sizeof(qasr_stream_beam_boost_args));
-  const qasr_stream_beam_args* a = &q->beam;
-  if (a->beam_width < 1 || a->beam_width > QASR_BEAM_MAX_WIDTH)
-    return fail(QASR_ERR_ARG, "stream_beam_boost: beam_width %d is outside 1 .. %d", a->beam_width, QASR_BEAM_MAX_WIDTH);
-  int rc = stream_beam_boost_checks(a, stream_beam_boost_state_bytes(a->S, a->beam_width, a->F));
-  if (rc) return rc;
-  if (q->n_sets < 1 || q->n_sets > QASR_STREAM_BEAM_MAX_SETS)
-    return fail(QASR_ERR_ARG, "stream_beam_boost: n_sets %d is outside 1 .. %d", q->n_sets, QASR_STREAM_BEAM_MAX_SETS);
-  if (!q->boost_set || !q->end_boost_score) return fail(QASR_ERR_ARG, "stream_beam_boost: boost_set and end_boost_score are required");
-  if (a->space < -1 || a->space == a->blank)
-    return fail(QASR_ERR_ARG, "stream_beam_boost: space %d must be a label other than blank, or -1", a->space);
+static int stream_beam_range_check(const char* who, const qasr_stream_beam_args* a) {
+  if (a->Tw < 1 || a->Tw > QASR_BEAM_MAX_FRAMES || (int64_t)a->B * a->Tw >= (1ll << 31))
+    return fail(QASR_ERR_ARG, "%s: Tw %d is outside 1 .. %d (or B * Tw >= 2^31)", who, a->Tw, QASR_BEAM_MAX_FRAMES);
+  if (int rc = stream_beam_width_check(who, a->beam_width)) return rc;
+  if (int rc = beam_cand_check(who, a->N, a->n_best, a->beam_width, a->blank, a->lae_entries)) return rc;
+  if (a->Lg < 0 || a->K < 1 || a->K > QASR_STREAM_BEAM_ROUND)
+    return fail(QASR_ERR_ARG, "%s: Lg %d < 0 or K %d outside 1 .. %d", who, a->Lg, a->K, QASR_STREAM_BEAM_ROUND);
+  if (a->F > QASR_STREAM_BEAM_MAX_RING || (int64_t)a->F < (int64_t)a->Lg + a->K)
+    return fail(QASR_ERR_ARG, "%s: F %d must lie in Lg + K = %lld .. %d", who, a->F, (long long)a->Lg + a->K, QASR_STREAM_BEAM_MAX_RING);
+  return 0;
+}
+static int stream_beam_tail_check(const char* who, const qasr_stream_beam_args* a, size_t need, const char* query) {
+  if (!need || a->beam_state_bytes < need)
+    return fail(QASR_ERR_ARG, "%s: beam_state_bytes %zu, %s gives %zu", who, a->beam_state_bytes, query, need);
+  if (((uintptr_t)a->state | (uintptr_t)a->beam_state) & 15) return fail(QASR_ERR_ARG, "%s: state or beam_state is not 16-byte aligned", who);
+  if (a->max_final_frames < 1 || a->max_final_frames > a->Tw)
+    return fail(QASR_ERR_ARG, "%s: max_final_frames %d is outside 1 .. Tw", who, a->max_final_frames);
+  if ((int64_t)a->P < (int64_t)a->F + a->max_final_frames || a->Ptail < 1 || a->Pend < a->F)
+    return fail(QASR_ERR_ARG, "%s: P %d < F + max_final_frames = %lld, Ptail %d < 1 or Pend %d < F = %d", who, a->P,
+                (long long)a->F + a->max_final_frames, a->Ptail, a->Pend, a->F);
+  return 0;
+}
+static int stream_beam_lm_check(const char* who, const qasr_stream_beam_args* a, const void* lm_score, const char* lm_score_name) {
+  if (!a->lm) return 0;
+  if (!lm_score) return fail(QASR_ERR_ARG, "%s: %s is required with lm", who, lm_score_name);
+  return beam_lm_check(who, a->lm, a->lm_bytes, a->alpha_q, a->beta_q);
+}
+static size_t stream_beam_need(const qasr_stream_beam_args* a, bool boosted) {
+  return boosted ? stream_beam_boost_state_bytes(a->S, a->beam_width, a->F) : stream_beam_state_bytes(a->S, a->beam_width, a->F);
+}
+// all of it for the two calls that write the END outputs
+static int stream_beam_checks(const char* who, const qasr_stream_beam_args* a, bool boosted) {
+  if (int rc = args_check(who, a)) return rc;
+  if (!stream_beam_step_ptrs(a) || !a->end_labels || !a->end_n_labels || !a->end_score || !a->n_hyps)
+    return fail(QASR_ERR_ARG, "%s: every pointer but lm (and end_lm_score without lm) is required", who);
+  if (int rc = stream_geometry(who, a->S, a->B, a->Wl, a->C, a->Rr, a->samples_per_frame, a->state_bytes)) return rc;
+  if (int rc = stream_beam_range_check(who, a)) return rc;
+  if (int rc = stream_beam_tail_check(who, a, stream_beam_need(a, boosted), boosted ? "qasr_stream_beam_boost_state_bytes" : "qasr_stream_beam_state_bytes"))
+    return rc;
+  if (int rc = stream_beam_lm_check(who, a, a->end_lm_score, "end_lm_score")) return rc;
+  return a->lm ? beam_space_check(who, a->space, a->blank) : 0;
+}
+// the phrase sets of qasr_stream_beam_boost and _ep
+static int stream_beam_sets_check(const char* who, const qasr_stream_beam_boost_args* q) {
   for (int g = 0; g < q->n_sets; ++g) {
     if (!q->sets[g] || ((uintptr_t)q->sets[g] & 15) != 0 || q->set_bytes[g] < 128 || q->set_bytes[g] > (size_t)INT32_MAX)
-      return fail(QASR_ERR_ARG, "stream_beam_boost: set %d must be 16-byte aligned and 128 .. 2^31 - 1 bytes, got %zu", g, q->set_bytes[g]);
-    if (q->whole_words[g] != 0 && a->space < 0)
-      return fail(QASR_ERR_ARG, "stream_beam_boost: set %d: whole words need the space label, got %d", g, a->space);
+      return fail(QASR_ERR_ARG, "%s: set %d must be 16-byte aligned and 128 .. 2^31 - 1 bytes, got %zu", who, g, q->set_bytes[g]);
+    if (q->whole_words[g] != 0 && q->beam.space < 0)
+      return fail(QASR_ERR_ARG, "%s: set %d: whole words need the space label, got %d", who, g, q->beam.space);
   }
-  rc = launch_stream_beam_boost((hipStream_t)stream, *q);
-  if (rc) return fail(rc, "stream_beam_boost: launch");
-  HIPCHK(hipGetLastError());
-  return QASR_OK;
+  return 0;
 }
 
-// ---- streaming beam endpointing (k_stream_beam_ep, qasr_stream_beam_ep.hip): qasr_stream_beam_boost's checks under this call's
-// name without the END outputs it ignores, the records' and the cut outputs' checks, and one launch
+int qasr_stream_beam(void* stream, const qasr_stream_beam_args* a) {
+  if (int rc = stream_beam_checks("stream_beam", a, false)) return rc;
+  return launched("stream_beam", launch_stream_beam((hipStream_t)stream, *a));
+}
+
+// ---- streaming phrase boosting (k_stream_beam_boost, qasr_stream_beam_boost.hip): qasr_stream_beam's checks under this call's
+// name and against its own state query, the sets' checks and one launch.  beam_width is asked about first here, as it always
+// was, and space a second time for the sets' sake (a call without lm has not been asked yet).
+size_t qasr_stream_beam_boost_state_bytes(int S, int beam_width, int F) { return stream_beam_boost_state_bytes(S, beam_width, F); }
+
+int qasr_stream_beam_boost(void* stream, const qasr_stream_beam_boost_args* q) {
+  const char* const who = "stream_beam_boost";
+  if (int rc = args_check(who, q)) return rc;
+  const qasr_stream_beam_args* a = &q->beam;
+  if (int rc = stream_beam_width_check(who, a->beam_width)) return rc;
+  if (int rc = stream_beam_checks(who, a, true)) return rc;
+  if (q->n_sets < 1 || q->n_sets > QASR_STREAM_BEAM_MAX_SETS)
+    return fail(QASR_ERR_ARG, "%s: n_sets %d is outside 1 .. %d", who, q->n_sets, QASR_STREAM_BEAM_MAX_SETS);
+  if (!q->boost_set || !q->end_boost_score) return fail(QASR_ERR_ARG, "%s: boost_set and end_boost_score are required", who);
+  if (int rc = beam_space_check(who, a->space, a->blank)) return rc;
+  if (int rc = stream_beam_sets_check(who, q)) return rc;
+  return launched(who, launch_stream_beam_boost((hipStream_t)stream, *q));
+}
+
+// ---- streaming beam endpointing (k_stream_beam_ep, qasr_stream_beam_ep.hip): the same blocks under this call's name, without
+// the END outputs it ignores; n_sets (0 allowed) is asked between F and the state's size because it picks the query; space once,
+// for the model or the sets; then the records' and the cut outputs' checks, and one launch
 int qasr_stream_beam_ep(void* stream, const qasr_stream_beam_ep_args* x) {
-  if (!x) return fail(QASR_ERR_ARG, "stream_beam_ep: args is NULL");
-  if (x->struct_size != sizeof(qasr_stream_beam_ep_args))
-    return fail(QASR_ERR_ARG, "stream_beam_ep: struct_size %u is not %zu", x->struct_size, sizeof(qasr_stream_beam_ep_args));
+  const char* const who = "stream_beam_ep";
+  if (int rc = args_check(who, x)) return rc;
   const qasr_stream_beam_boost_args* q = &x->boost;
   const qasr_stream_beam_args* a = &q->beam;
   if (q->struct_size != sizeof(qasr_stream_beam_boost_args) || a->struct_size != sizeof(qasr_stream_beam_args))
     return fail(QASR_ERR_ARG, "stream_beam_ep: boost.struct_size %u is not %zu or boost.beam.struct_size %u is not %zu", q->struct_size,
                 sizeof(qasr_stream_beam_boost_args), a->struct_size, sizeof(qasr_stream_beam_args));
-  if (!a->state || !a->beam_state || !a->slots || !a->flags || !a->cand_id || !a->cand_q || !a->enc_lens || !a->first_frame ||
-      !a->lae_table || !a->labels || !a->frames || !a->n_new_labels || !a->commit_len || !a->n_live || !a->status ||
-      !a->tail_labels || !a->tail_n)
-    return fail(QASR_ERR_ARG, "stream_beam_ep: every pointer of the step but lm and the END outputs is required");
-  int rc = stream_geometry("stream_beam_ep", a->S, a->B, a->Wl, a->C, a->Rr, a->samples_per_frame, a->state_bytes);
-  if (rc) return rc;
-  if (a->Tw < 1 || a->Tw > QASR_BEAM_MAX_FRAMES || (int64_t)a->B * a->Tw >= (1ll << 31))
-    return fail(QASR_ERR_ARG, "stream_beam_ep: Tw %d is outside 1 .. %d (or B * Tw >= 2^31)", a->Tw, QASR_BEAM_MAX_FRAMES);
-  if (a->beam_width < 1 || a->beam_width > QASR_BEAM_MAX_WIDTH)
-    return fail(QASR_ERR_ARG, "stream_beam_ep: beam_width %d is outside 1 .. %d", a->beam_width, QASR_BEAM_MAX_WIDTH);
-  if (a->N < 1 || a->N > QASR_BEAM_MAX_CANDIDATES)
-    return fail(QASR_ERR_ARG, "stream_beam_ep: N %d is outside 1 .. %d", a->N, QASR_BEAM_MAX_CANDIDATES);
-  if (a->n_best < 1 || a->n_best > a->beam_width || a->blank < 0)
-    return fail(QASR_ERR_ARG, "stream_beam_ep: n_best %d is outside 1 .. beam_width, or blank %d < 0", a->n_best, a->blank);
-  if (a->lae_entries != QASR_BEAM_TABLE_ENTRIES)
-    return fail(QASR_ERR_ARG, "stream_beam_ep: lae_entries %u is not %d", a->lae_entries, QASR_BEAM_TABLE_ENTRIES);
-  if (a->Lg < 0 || a->K < 1 || a->K > QASR_STREAM_BEAM_ROUND)
-    return fail(QASR_ERR_ARG, "stream_beam_ep: Lg %d < 0 or K %d outside 1 .. %d", a->Lg, a->K, QASR_STREAM_BEAM_ROUND);
-  if (a->F > QASR_STREAM_BEAM_MAX_RING || (int64_t)a->F < (int64_t)a->Lg + a->K)
-    return fail(QASR_ERR_ARG, "stream_beam_ep: F %d must lie in Lg + K = %lld .. %d", a->F, (long long)a->Lg + a->K, QASR_STREAM_BEAM_MAX_RING);
+  if (!stream_beam_step_ptrs(a)) return fail(QASR_ERR_ARG, "stream_beam_ep: every pointer of the step but lm and the END outputs is required");
+  if (int rc = stream_geometry(who, a->S, a->B, a->Wl, a->C, a->Rr, a->samples_per_frame, a->state_bytes)) return rc;
+  if (int rc = stream_beam_range_check(who, a)) return rc;
   if (q->n_sets < 0 || q->n_sets > QASR_STREAM_BEAM_MAX_SETS)
     return fail(QASR_ERR_ARG, "stream_beam_ep: n_sets %d is outside 0 .. %d", q->n_sets, QASR_STREAM_BEAM_MAX_SETS);
-  const size_t need = q->n_sets ? stream_beam_boost_state_bytes(a->S, a->beam_width, a->F) : stream_beam_state_bytes(a->S, a->beam_width, a->F);
-  if (!need || a->beam_state_bytes < need)
-    return fail(QASR_ERR_ARG, "stream_beam_ep: beam_state_bytes %zu, the state query for %d sets gives %zu", a->beam_state_bytes, q->n_sets, need);
-  if (((uintptr_t)a->state | (uintptr_t)a->beam_state) & 15) return fail(QASR_ERR_ARG, "stream_beam_ep: state or beam_state is not 16-byte aligned");
-  if (a->max_final_frames < 1 || a->max_final_frames > a->Tw)
-    return fail(QASR_ERR_ARG, "stream_beam_ep: max_final_frames %d is outside 1 .. Tw", a->max_final_frames);
-  if ((int64_t)a->P < (int64_t)a->F + a->max_final_frames || a->Ptail < 1 || a->Pend < a->F)
-    return fail(QASR_ERR_ARG, "stream_beam_ep: P %d < F + max_final_frames = %lld, Ptail %d < 1 or Pend %d < F = %d", a->P,
-                (long long)a->F + a->max_final_frames, a->Ptail, a->Pend, a->F);
-  if (a->lm) {
-    if (!x->cut_lm_score) return fail(QASR_ERR_ARG, "stream_beam_ep: cut_lm_score is required with lm");
-    if (((uintptr_t)a->lm & 15) != 0 || a->lm_bytes < 128 || a->lm_bytes > (size_t)INT32_MAX)
-      return fail(QASR_ERR_ARG, "stream_beam_ep: lm must be 16-byte aligned and 128 .. 2^31 - 1 bytes, got %zu", a->lm_bytes);
-    if (a->alpha_q < 0 || a->alpha_q > QASR_LM_MAX_WEIGHT || a->beta_q < -QASR_LM_MAX_WEIGHT || a->beta_q > QASR_LM_MAX_WEIGHT)
-      return fail(QASR_ERR_ARG, "stream_beam_ep: alpha_q %d outside 0 .. 16 * 2^16 or |beta_q| %d above it", a->alpha_q, a->beta_q);
-  }
-  if ((a->lm || q->n_sets) && (a->space < -1 || a->space == a->blank))
-    return fail(QASR_ERR_ARG, "stream_beam_ep: space %d must be a label other than blank, or -1", a->space);
+  char query[48];
+  snprintf(query, sizeof query, "the state query for %d sets", q->n_sets);
+  if (int rc = stream_beam_tail_check(who, a, stream_beam_need(a, q->n_sets != 0), query)) return rc;
+  if (int rc = stream_beam_lm_check(who, a, x->cut_lm_score, "cut_lm_score")) return rc;
+  if (a->lm || q->n_sets)
+    if (int rc = beam_space_check(who, a->space, a->blank)) return rc;
   if (q->n_sets) {
     if (!q->boost_set || !x->cut_boost_score) return fail(QASR_ERR_ARG, "stream_beam_ep: boost_set and cut_boost_score are required with sets");
-    for (int g = 0; g < q->n_sets; ++g) {
-      if (!q->sets[g] || ((uintptr_t)q->sets[g] & 15) != 0 || q->set_bytes[g] < 128 || q->set_bytes[g] > (size_t)INT32_MAX)
-        return fail(QASR_ERR_ARG, "stream_beam_ep: set %d must be 16-byte aligned and 128 .. 2^31 - 1 bytes, got %zu", g, q->set_bytes[g]);
-      if (q->whole_words[g] != 0 && a->space < 0)
-        return fail(QASR_ERR_ARG, "stream_beam_ep: set %d: whole words need the space label, got %d", g, a->space);
-    }
+    if (int rc = stream_beam_sets_check(who, q)) return rc;
   }
   const int64_t cuts = (int64_t)a->B * x->E, per_cut = (int64_t)a->n_best * a->Pend;      // each below 2^62: no overflow below
   if (x->E < 1 || cuts >= (1ll << 31) / QASR_STREAM_EP_RECORD_WORDS || per_cut >= (1ll << 31) || cuts * per_cut >= (1ll << 31))
@@ -1913,19 +1781,14 @@ int qasr_stream_beam_ep(void* stream, const qasr_stream_beam_ep_args* x) {
   if (!x->records || !x->n_records || !x->ep_status || !x->n_cuts || !x->cut_n_hyps || !x->cut_delta_end || !x->cut_labels ||
       !x->cut_n_labels || !x->cut_score)
     return fail(QASR_ERR_ARG, "stream_beam_ep: records, n_records, ep_status and every cut output (cut_lm_score with lm, cut_boost_score with sets) are required");
-  rc = launch_stream_beam_ep((hipStream_t)stream, *x);
-  if (rc) return fail(rc, "stream_beam_ep: launch");
-  HIPCHK(hipGetLastError());
-  return QASR_OK;
+  return launched(who, launch_stream_beam_ep((hipStream_t)stream, *x));
 }
 
 // ---- streaming endpointing (k_stream_endpoint, qasr_stream_ep.hip): the checks of include/qasr.h and one launch
 size_t qasr_stream_ep_state_bytes(int S) { return stream_ep_state_bytes(S); }
 
 int qasr_stream_endpoint(void* stream, const qasr_stream_endpoint_args* a) {
-  if (!a) return fail(QASR_ERR_ARG, "stream_endpoint: args is NULL");
-  if (a->struct_size != sizeof(qasr_stream_endpoint_args))
-    return fail(QASR_ERR_ARG, "stream_endpoint: struct_size %u is not %zu", a->struct_size, sizeof(qasr_stream_endpoint_args));
+  if (int rc = args_check("stream_endpoint", a)) return rc;
   if (!a->state || !a->ep_state || !a->slots || !a->flags || !a->tokens || !a->frame_score || !a->enc_lens || !a->first_frame ||
       !a->emit_start || !a->emit_nframes || !a->emit_n_new_labels || !a->emit_status || !a->records || !a->n_records || !a->status)
     return fail(QASR_ERR_ARG, "stream_endpoint: every pointer is required");
@@ -1943,10 +1806,7 @@ int qasr_stream_endpoint(void* stream, const qasr_stream_endpoint_args* a) {
   if (!need || a->ep_state_bytes < need)
     return fail(QASR_ERR_ARG, "stream_endpoint: ep_state_bytes %zu, qasr_stream_ep_state_bytes gives %zu", a->ep_state_bytes, need);
   if (((uintptr_t)a->state | (uintptr_t)a->ep_state) & 15) return fail(QASR_ERR_ARG, "stream_endpoint: state or ep_state is not 16-byte aligned");
-  rc = launch_stream_endpoint((hipStream_t)stream, *a);
-  if (rc) return fail(rc, "stream_endpoint: launch");
-  HIPCHK(hipGetLastError());
-  return QASR_OK;
+  return launched("stream_endpoint", launch_stream_endpoint((hipStream_t)stream, *a));
 }
 
 // ---- streaming at any sample rate (k_stream_rs_append / _fir, qasr_stream_rs.hip): the checks of include/qasr.h, two launches
@@ -1954,9 +1814,7 @@ size_t qasr_stream_rs_state_bytes(int S, int hcap) { return stream_rs_state_byte
 size_t qasr_stream_rs_work_bytes(int B) { return stream_rs_work_bytes(B); }
 
 int qasr_stream_rs_push(void* stream, const qasr_stream_rs_push_args* a) {
-  if (!a) return fail(QASR_ERR_ARG, "stream_rs_push: args is NULL");
-  if (a->struct_size != sizeof(qasr_stream_rs_push_args))
-    return fail(QASR_ERR_ARG, "stream_rs_push: struct_size %u is not %zu", a->struct_size, sizeof(qasr_stream_rs_push_args));
+  if (int rc = args_check("stream_rs_push", a)) return rc;
   if (!a->state || !a->rs_state || !a->work || !a->blob || !a->slots || !a->flags || !a->n_in || !a->out_limit || !a->chunk ||
       !a->n_taken || !a->n_out || !a->status)
     return fail(QASR_ERR_ARG, "stream_rs_push: every pointer is required");
@@ -1983,10 +1841,7 @@ int qasr_stream_rs_push(void* stream, const qasr_stream_rs_push_args* a) {
                 a->blob_bytes);
   if (a->pitch < 0 || a->pitch > QASR_RESAMPLE_MAX_PITCH)
     return fail(QASR_ERR_ARG, "stream_rs_push: pitch %lld is outside 0 .. 2^38", (long long)a->pitch);
-  rc = launch_stream_rs_push((hipStream_t)stream, *a);
-  if (rc) return fail(rc, "stream_rs_push: launch");
-  HIPCHK(hipGetLastError());
-  return QASR_OK;
+  return launched("stream_rs_push", launch_stream_rs_push((hipStream_t)stream, *a));
 }
 
 int qasr_engine_attach_ctc(qasr_engine* e, float* frame_score, const qasr_ctc_out* out, int use_lens) {

@@ -437,6 +437,58 @@ def ctc_beam_workspace_bytes(B, T, beam_width):
     return int(load_library().qasr_ctc_beam_workspace_bytes(int(B), int(T), int(beam_width)))
 
 
+def _lm_weights(who, lm, alpha, beta, blank):
+    """The weights of a model in fixed point ((0, 0) without one); they and the model's vocabulary are checked here, under the
+    call's name, before any launch."""
+    if lm is None:
+        return 0, 0
+    from .ngram import fixed_weights
+    alpha_q, beta_q = fixed_weights(alpha, beta)
+    if lm.n_labels != int(blank):
+        raise ValueError(f'{who}: the model was loaded for {lm.n_labels} labels, blank is {blank}')
+    return alpha_q, beta_q
+
+
+def _beam_args(cls, cand_id, cand_q, lens, blank, beam_width, n_best, workspace, out, lm_score=False, boost_score=False):
+    """What qasr_ctc_beam, _lm and _boost share: the candidates coerced, the BeamResult (with lm_score / boost_score where the
+    call writes them) and the workspace unless the caller owns them, the table, and the fields every one of the three structs
+    opens with.  Returns (the struct of type cls, out, what must stay alive)."""
+    from .beam import BeamResult, TAB_ENTRIES
+    assert cand_id.is_cuda and cand_id.dim() == 3 and cand_id.shape == cand_q.shape, 'ctc_beam: candidates must be cuda [B, T, N]'
+    dev = cand_id.device
+    cid, cq = cand_id.to(torch.int32).contiguous(), cand_q.to(device=dev, dtype=torch.int32).contiguous()
+    ln = None if lens is None else lens.to(device=dev, dtype=torch.int32).contiguous()
+    B, T, N = cid.shape
+    W = int(beam_width)
+    nb = W if n_best is None else int(n_best)
+    if out is None:
+        shape = (B, max(nb, 0))
+        i64 = lambda on: torch.empty(*shape, device=dev, dtype=torch.int64) if on else None
+        out = BeamResult(labels=torch.empty(*shape, T, device=dev, dtype=torch.int32),
+                         n_labels=torch.empty(*shape, device=dev, dtype=torch.int32), score=i64(True),
+                         n_hyps=torch.empty(B, device=dev, dtype=torch.int32), blank=int(blank), lm_score=i64(lm_score),
+                         boost_score=i64(boost_score))
+    if workspace is None:
+        workspace = torch.empty(max(ctc_beam_workspace_bytes(B, T, W), 8), device=dev, dtype=torch.uint8)
+    tab = lae_table_device(dev)
+    a = cls()
+    a.struct_size = C.sizeof(cls)
+    a.B, a.T, a.N, a.beam_width, a.n_best, a.blank = B, T, N, W, nb, int(blank)
+    a.lae_entries = TAB_ENTRIES
+    a.cand_id, a.cand_q, a.lens, a.lae_table = cid.data_ptr(), cq.data_ptr(), 0 if ln is None else ln.data_ptr(), tab.data_ptr()
+    a.workspace, a.workspace_bytes = workspace.data_ptr(), workspace.numel() * workspace.element_size()
+    a.labels, a.n_labels, a.score, a.n_hyps = (out.labels.data_ptr(), out.n_labels.data_ptr(), out.score.data_ptr(),
+                                               out.n_hyps.data_ptr())
+    return a, out, (cid, cq, ln, workspace, tab)
+
+
+def _beam_launch(symbol, a, out, keep, stream):
+    with torch.cuda.device(keep[0].device):
+        _check(getattr(load_library(), symbol)(_stream_ptr(stream), C.byref(a)), symbol)
+    out._keep = keep
+    return out
+
+
 def ctc_beam(cand_id, cand_q, lens=None, blank=None, beam_width=16, n_best=None, workspace=None, out=None, stream=None,
              lm=None, alpha=0.0, beta=0.0, boost=None):
     """qasr_ctc_beam: CTC prefix beam search over the candidates of ctc_topn (cuda int32 [B, T, N]) on the device (k_beam,
@@ -450,127 +502,36 @@ def ctc_beam(cand_id, cand_q, lens=None, blank=None, beam_width=16, n_best=None,
         return _ctc_beam_boost(cand_id, cand_q, lens, blank, beam_width, n_best, workspace, out, stream, lm, alpha, beta, boost)
     if lm is not None:
         return _ctc_beam_lm(cand_id, cand_q, lens, blank, beam_width, n_best, workspace, out, stream, lm, alpha, beta)
-    from .beam import BeamResult, TAB_ENTRIES
-    lib = load_library()
     if blank is None:
         raise ValueError('ctc_beam: blank is required (the decoder\'s last class)')
-    assert cand_id.is_cuda and cand_id.dim() == 3 and cand_id.shape == cand_q.shape, 'ctc_beam: candidates must be cuda [B, T, N]'
-    dev = cand_id.device
-    cid, cq = cand_id.to(torch.int32).contiguous(), cand_q.to(device=dev, dtype=torch.int32).contiguous()
-    ln = None if lens is None else lens.to(device=dev, dtype=torch.int32).contiguous()
-    B, T, N = cid.shape
-    W = int(beam_width)
-    nb = W if n_best is None else int(n_best)
-    if out is None:
-        shape = (B, max(nb, 0))
-        out = BeamResult(labels=torch.empty(*shape, T, device=dev, dtype=torch.int32),
-                         n_labels=torch.empty(*shape, device=dev, dtype=torch.int32),
-                         score=torch.empty(*shape, device=dev, dtype=torch.int64),
-                         n_hyps=torch.empty(B, device=dev, dtype=torch.int32), blank=int(blank))
-    if workspace is None:
-        workspace = torch.empty(max(ctc_beam_workspace_bytes(B, T, W), 8), device=dev, dtype=torch.uint8)
-    tab = lae_table_device(dev)
-    a = BeamArgs()
-    a.struct_size = C.sizeof(BeamArgs)
-    a.B, a.T, a.N, a.beam_width, a.n_best, a.blank = B, T, N, W, nb, int(blank)
-    a.lae_entries = TAB_ENTRIES
-    a.cand_id, a.cand_q, a.lens, a.lae_table = cid.data_ptr(), cq.data_ptr(), 0 if ln is None else ln.data_ptr(), tab.data_ptr()
-    a.workspace, a.workspace_bytes = workspace.data_ptr(), workspace.numel() * workspace.element_size()
-    a.labels, a.n_labels, a.score, a.n_hyps = (out.labels.data_ptr(), out.n_labels.data_ptr(), out.score.data_ptr(),
-                                               out.n_hyps.data_ptr())
-    with torch.cuda.device(dev):
-        _check(lib.qasr_ctc_beam(_stream_ptr(stream), C.byref(a)), 'qasr_ctc_beam')
-    out._keep = (cid, cq, ln, workspace, tab)
-    return out
+    a, out, keep = _beam_args(BeamArgs, cand_id, cand_q, lens, blank, beam_width, n_best, workspace, out)
+    return _beam_launch('qasr_ctc_beam', a, out, keep, stream)
 
 
 def _ctc_beam_lm(cand_id, cand_q, lens, blank, beam_width, n_best, workspace, out, stream, lm, alpha, beta):
     """ctc_beam with a model: qasr_ctc_beam_lm.  The weights and the vocabulary are checked here, before any launch."""
-    from .beam import BeamResult, TAB_ENTRIES
-    from .ngram import fixed_weights
-    lib = load_library()
     if blank is None:
         raise ValueError('ctc_beam: blank is required (the decoder\'s last class)')
-    alpha_q, beta_q = fixed_weights(alpha, beta)
-    if lm.n_labels != int(blank):
-        raise ValueError(f'ctc_beam: the model was loaded for {lm.n_labels} labels, blank is {blank}')
-    assert cand_id.is_cuda and cand_id.dim() == 3 and cand_id.shape == cand_q.shape, 'ctc_beam: candidates must be cuda [B, T, N]'
-    dev = cand_id.device
-    cid, cq = cand_id.to(torch.int32).contiguous(), cand_q.to(device=dev, dtype=torch.int32).contiguous()
-    ln = None if lens is None else lens.to(device=dev, dtype=torch.int32).contiguous()
-    B, T, N = cid.shape
-    W = int(beam_width)
-    nb = W if n_best is None else int(n_best)
-    if out is None:
-        shape = (B, max(nb, 0))
-        out = BeamResult(labels=torch.empty(*shape, T, device=dev, dtype=torch.int32),
-                         n_labels=torch.empty(*shape, device=dev, dtype=torch.int32),
-                         score=torch.empty(*shape, device=dev, dtype=torch.int64),
-                         n_hyps=torch.empty(B, device=dev, dtype=torch.int32), blank=int(blank),
-                         lm_score=torch.empty(*shape, device=dev, dtype=torch.int64))
-    if workspace is None:
-        workspace = torch.empty(max(ctc_beam_workspace_bytes(B, T, W), 8), device=dev, dtype=torch.uint8)
-    tab = lae_table_device(dev)
-    blob = lm_device(lm, dev)
-    a = BeamLmArgs()
-    a.struct_size = C.sizeof(BeamLmArgs)
-    a.B, a.T, a.N, a.beam_width, a.n_best, a.blank = B, T, N, W, nb, int(blank)
-    a.lae_entries = TAB_ENTRIES
-    a.cand_id, a.cand_q, a.lens, a.lae_table = cid.data_ptr(), cq.data_ptr(), 0 if ln is None else ln.data_ptr(), tab.data_ptr()
-    a.workspace, a.workspace_bytes = workspace.data_ptr(), workspace.numel() * workspace.element_size()
-    a.labels, a.n_labels, a.score, a.n_hyps = (out.labels.data_ptr(), out.n_labels.data_ptr(), out.score.data_ptr(),
-                                               out.n_hyps.data_ptr())
+    alpha_q, beta_q = _lm_weights('ctc_beam', lm, alpha, beta, blank)
+    a, out, keep = _beam_args(BeamLmArgs, cand_id, cand_q, lens, blank, beam_width, n_best, workspace, out, lm_score=True)
+    blob = lm_device(lm, keep[0].device)
     a.lm, a.lm_bytes, a.alpha_q, a.beta_q, a.space = blob.data_ptr(), blob.numel(), alpha_q, beta_q, int(lm.space)
     a.lm_score = 0 if out.lm_score is None else out.lm_score.data_ptr()
-    with torch.cuda.device(dev):
-        _check(lib.qasr_ctc_beam_lm(_stream_ptr(stream), C.byref(a)), 'qasr_ctc_beam_lm')
-    out._keep = (cid, cq, ln, workspace, tab, blob)
-    return out
+    return _beam_launch('qasr_ctc_beam_lm', a, out, keep + (blob,), stream)
 
 
 def _ctc_beam_boost(cand_id, cand_q, lens, blank, beam_width, n_best, workspace, out, stream, lm, alpha, beta, boost):
     """ctc_beam with a phrase set: qasr_ctc_beam_boost.  Weights, vocabulary sizes and the set are checked here, before any
     launch."""
-    from .beam import BeamResult, TAB_ENTRIES
-    lib = load_library()
     if blank is None:
         raise ValueError('ctc_beam: blank is required (the decoder\'s last class)')
-    alpha_q = beta_q = 0
-    if lm is not None:
-        from .ngram import fixed_weights
-        alpha_q, beta_q = fixed_weights(alpha, beta)
-        if lm.n_labels != int(blank):
-            raise ValueError(f'ctc_beam: the model was loaded for {lm.n_labels} labels, blank is {blank}')
+    alpha_q, beta_q = _lm_weights('ctc_beam', lm, alpha, beta, blank)
     if boost.n_labels != int(blank):
         raise ValueError(f'ctc_beam: the phrase set was compiled for {boost.n_labels} labels, blank is {blank}')
-    assert cand_id.is_cuda and cand_id.dim() == 3 and cand_id.shape == cand_q.shape, 'ctc_beam: candidates must be cuda [B, T, N]'
-    dev = cand_id.device
-    cid, cq = cand_id.to(torch.int32).contiguous(), cand_q.to(device=dev, dtype=torch.int32).contiguous()
-    ln = None if lens is None else lens.to(device=dev, dtype=torch.int32).contiguous()
-    B, T, N = cid.shape
-    W = int(beam_width)
-    nb = W if n_best is None else int(n_best)
-    if out is None:
-        shape = (B, max(nb, 0))
-        out = BeamResult(labels=torch.empty(*shape, T, device=dev, dtype=torch.int32),
-                         n_labels=torch.empty(*shape, device=dev, dtype=torch.int32),
-                         score=torch.empty(*shape, device=dev, dtype=torch.int64),
-                         n_hyps=torch.empty(B, device=dev, dtype=torch.int32), blank=int(blank),
-                         lm_score=None if lm is None else torch.empty(*shape, device=dev, dtype=torch.int64),
-                         boost_score=torch.empty(*shape, device=dev, dtype=torch.int64))
-    if workspace is None:
-        workspace = torch.empty(max(ctc_beam_workspace_bytes(B, T, W), 8), device=dev, dtype=torch.uint8)
-    tab = lae_table_device(dev)
-    lm_blob = None if lm is None else lm_device(lm, dev)
-    blob = boost_device(boost, dev)
-    a = BeamBoostArgs()
-    a.struct_size = C.sizeof(BeamBoostArgs)
-    a.B, a.T, a.N, a.beam_width, a.n_best, a.blank = B, T, N, W, nb, int(blank)
-    a.lae_entries = TAB_ENTRIES
-    a.cand_id, a.cand_q, a.lens, a.lae_table = cid.data_ptr(), cq.data_ptr(), 0 if ln is None else ln.data_ptr(), tab.data_ptr()
-    a.workspace, a.workspace_bytes = workspace.data_ptr(), workspace.numel() * workspace.element_size()
-    a.labels, a.n_labels, a.score, a.n_hyps = (out.labels.data_ptr(), out.n_labels.data_ptr(), out.score.data_ptr(),
-                                               out.n_hyps.data_ptr())
+    a, out, keep = _beam_args(BeamBoostArgs, cand_id, cand_q, lens, blank, beam_width, n_best, workspace, out, lm_score=lm is not None,
+                              boost_score=True)
+    lm_blob = None if lm is None else lm_device(lm, keep[0].device)
+    blob = boost_device(boost, keep[0].device)
     if lm is not None:
         a.lm, a.lm_bytes, a.alpha_q, a.beta_q = lm_blob.data_ptr(), lm_blob.numel(), alpha_q, beta_q
         a.lm_score = 0 if out.lm_score is None else out.lm_score.data_ptr()
@@ -578,10 +539,7 @@ def _ctc_beam_boost(cand_id, cand_q, lens, blank, beam_width, n_best, workspace,
     a.whole_words = int(boost.whole_words)
     a.boost, a.boost_bytes = blob.data_ptr(), blob.numel()
     a.boost_score = 0 if out.boost_score is None else out.boost_score.data_ptr()
-    with torch.cuda.device(dev):
-        _check(lib.qasr_ctc_beam_boost(_stream_ptr(stream), C.byref(a)), 'qasr_ctc_beam_boost')
-    out._keep = (cid, cq, ln, workspace, tab, lm_blob, blob)
-    return out
+    return _beam_launch('qasr_ctc_beam_boost', a, out, keep + (lm_blob, blob), stream)
 
 
 def ctc_beam_search(log_probs, lens=None, blank=None, beam_width=16, n_best=None, cutoff_top_n=40, stream=None, lm=None,
@@ -1525,12 +1483,16 @@ def stream_beam_block(bstate, S, bplan):
     return bstate[:int(S) * bplan.slot_words].view(int(S), bplan.slot_words)
 
 
+def _stream_beam_pitches(bplan, P, Ptail, Pend):
+    """the row pitches of a step's outputs: the plan's own unless given"""
+    return (bplan.delta_pitch if P is None else int(P), bplan.tail_pitch if Ptail is None else int(Ptail),
+            bplan.end_pitch if Pend is None else int(Pend))
+
+
 def stream_beam_buffers(B, bplan, device, with_lm, P=None, Ptail=None, Pend=None):
     """k_stream_beam's outputs as a qasr.stream_beam.BeamStepBatch of cuda tensors"""
     from . import stream_beam as sb
-    P = bplan.delta_pitch if P is None else int(P)
-    Ptail = bplan.tail_pitch if Ptail is None else int(Ptail)
-    Pend = bplan.end_pitch if Pend is None else int(Pend)
+    P, Ptail, Pend = _stream_beam_pitches(bplan, P, Ptail, Pend)
     i = lambda *s: torch.empty(*s, device=device, dtype=torch.int32)
     l = lambda *s: torch.empty(*s, device=device, dtype=torch.int64)
     nb = bplan.n_best
@@ -1538,46 +1500,82 @@ def stream_beam_buffers(B, bplan, device, with_lm, P=None, Ptail=None, Pend=None
                             l(B, nb) if with_lm else None, i(B))
 
 
-def stream_beam_args(state, bstate, S, plan, bplan, slots, flags, cand_id, cand_q, enc_lens, first_frame, blank, lm=None,
-                     alpha=0.0, beta=0.0, out=None):
-    """the filled qasr_stream_beam_args of stream_beam (the tensors it points to are kept alive on it)"""
-    from .beam import TAB_ENTRIES
-    dev = state.device
+def _stream_beam_rows(who, cand_id, cand_q, rows):
+    """(B, Tw, N) of a step's candidates; they and `rows`, the step's int32 [B] tensors as (tensor, name), are checked under
+    the call's name"""
     if cand_id.dim() != 3 or cand_id.dtype != torch.int32 or not cand_id.is_contiguous() or not cand_id.is_cuda:
-        raise ValueError(f'stream_beam: cand_id must be a contiguous cuda int32 tensor [B, Tw, N], got {cand_id.dtype} {tuple(cand_id.shape)}')
+        raise ValueError(f'{who}: cand_id must be a contiguous cuda int32 tensor [B, Tw, N], got {cand_id.dtype} {tuple(cand_id.shape)}')
     if cand_q.dtype != torch.int32 or not cand_q.is_contiguous() or cand_q.shape != cand_id.shape:
-        raise ValueError('stream_beam: cand_q must be a contiguous int32 tensor of the shape of cand_id')
+        raise ValueError(f'{who}: cand_q must be a contiguous int32 tensor of the shape of cand_id')
+    for t, w in rows:
+        _i32dev(t, cand_id.shape[0], f'{who}: {w}')
+    return cand_id.shape
+
+
+def _stream_beam_fill(a, who, state, bstate, S, plan, bplan, slots, flags, cand_id, cand_q, enc_lens, first_frame, blank, lm, alpha_q,
+                      beta_q, out, outs, Pend):
+    """Fills a qasr_stream_beam_args, stream_beam's own or the one embedded in stream_beam_ep's: the plans' numbers, the states,
+    the step's inputs, the outputs `outs` of `out` (checked under the call's name) and the model.  Returns (the table, the
+    model's blob): they must stay alive."""
+    from .beam import TAB_ENTRIES
     B, Tw, N = cand_id.shape
-    for t, w in ((slots, 'slots'), (flags, 'flags'), (enc_lens, 'enc_lens'), (first_frame, 'first_frame')):
-        _i32dev(t, B, 'stream_beam: ' + w)
-    alpha_q = beta_q = 0
-    if lm is not None:
-        from .ngram import fixed_weights
-        alpha_q, beta_q = fixed_weights(alpha, beta)
-        if lm.n_labels != int(blank):
-            raise ValueError(f'stream_beam: the model was loaded for {lm.n_labels} labels, blank is {blank}')
-    if out is None:
-        out = stream_beam_buffers(B, bplan, dev, lm is not None)
-    tab = lae_table_device(dev)
-    blob = None if lm is None else lm_device(lm, dev)
-    a = StreamBeamArgs()
+    tab = lae_table_device(state.device)
+    blob = None if lm is None else lm_device(lm, state.device)
     a.struct_size = C.sizeof(StreamBeamArgs)
     a.S, a.B, a.Wl, a.C, a.Rr, a.samples_per_frame, a.Tw = int(S), B, plan.Wl, plan.C, plan.Rr, plan.samples_per_frame, Tw
     a.N, a.beam_width, a.n_best, a.blank = N, bplan.W, bplan.n_best, int(blank)
     a.Lg, a.K, a.F, a.max_final_frames = bplan.Lg, bplan.K, bplan.F, bplan.max_final_frames
-    a.P, a.Ptail, a.Pend = out.labels.shape[1], out.tail_labels.shape[1], out.end_labels.shape[2]
+    a.P, a.Ptail, a.Pend = out.labels.shape[1], out.tail_labels.shape[1], Pend
     a.lae_entries = TAB_ENTRIES
     a.state, a.state_bytes = state.data_ptr(), state.numel() * state.element_size()
     a.beam_state, a.beam_state_bytes = bstate.data_ptr(), bstate.numel() * bstate.element_size()
     a.slots, a.flags, a.cand_id, a.cand_q = slots.data_ptr(), flags.data_ptr(), cand_id.data_ptr(), cand_q.data_ptr()
     a.enc_lens, a.first_frame, a.lae_table = enc_lens.data_ptr(), first_frame.data_ptr(), tab.data_ptr()
-    for n in ('labels', 'frames', 'n_new_labels', 'commit_len', 'n_live', 'status', 'tail_labels', 'tail_n', 'end_labels',
-              'end_n_labels', 'end_score', 'n_hyps'):
+    for n in outs:
         t = getattr(out, n)
-        assert t.is_cuda and t.is_contiguous() and t.dtype == (torch.int64 if n == 'end_score' else torch.int32), 'stream_beam: out.' + n
+        assert t.is_cuda and t.is_contiguous() and t.dtype == (torch.int64 if n == 'end_score' else torch.int32), f'{who}: out.{n}'
         setattr(a, n, t.data_ptr())
     if lm is not None:
         a.lm, a.lm_bytes, a.alpha_q, a.beta_q, a.space = blob.data_ptr(), blob.numel(), alpha_q, beta_q, int(lm.space)
+    return tab, blob
+
+
+def _stream_beam_set_labels(who, sets, blank):
+    for k, bs in enumerate(sets or []):
+        if bs.n_labels != int(blank):
+            raise ValueError(f'{who}: phrase set {k} was compiled for {bs.n_labels} labels, blank is {blank}')
+
+
+def _stream_beam_sets(q, who, sets, blobs, boost_set, device, lm):
+    """Fills the sets of a qasr_stream_beam_boost_args whose `beam` is filled (without a model the sets name the space label);
+    returns the sets' blobs: boost_device's unless the caller holds them"""
+    blobs = [boost_device(bs, device) for bs in sets] if blobs is None else list(blobs)
+    assert len(blobs) == len(sets), f'{who}: one blob per set'
+    q.struct_size, q.n_sets = C.sizeof(StreamBeamBoostArgs), len(sets)
+    if lm is None:
+        q.beam.space = int(sets[0].space)
+    for k, (bs, blob) in enumerate(zip(sets, blobs)):
+        q.sets[k], q.set_bytes[k], q.whole_words[k] = blob.data_ptr(), blob.numel(), int(bs.whole_words)
+    q.boost_set = boost_set.data_ptr()
+    return blobs
+
+
+_STREAM_BEAM_STEP_OUTS = ('labels', 'frames', 'n_new_labels', 'commit_len', 'n_live', 'status', 'tail_labels', 'tail_n')
+
+
+def stream_beam_args(state, bstate, S, plan, bplan, slots, flags, cand_id, cand_q, enc_lens, first_frame, blank, lm=None,
+                     alpha=0.0, beta=0.0, out=None):
+    """the filled qasr_stream_beam_args of stream_beam (the tensors it points to are kept alive on it)"""
+    B, _, _ = _stream_beam_rows('stream_beam', cand_id, cand_q,
+                                ((slots, 'slots'), (flags, 'flags'), (enc_lens, 'enc_lens'), (first_frame, 'first_frame')))
+    alpha_q, beta_q = _lm_weights('stream_beam', lm, alpha, beta, blank)
+    if out is None:
+        out = stream_beam_buffers(B, bplan, state.device, lm is not None)
+    a = StreamBeamArgs()
+    tab, blob = _stream_beam_fill(a, 'stream_beam', state, bstate, S, plan, bplan, slots, flags, cand_id, cand_q, enc_lens, first_frame,
+                                  blank, lm, alpha_q, beta_q, out,
+                                  _STREAM_BEAM_STEP_OUTS + ('end_labels', 'end_n_labels', 'end_score', 'n_hyps'), out.end_labels.shape[2])
+    if lm is not None:
         a.end_lm_score = 0 if out.end_lm_score is None else out.end_lm_score.data_ptr()
     a._keep = (tab, blob, out)
     return a
@@ -1634,9 +1632,7 @@ def stream_beam_boost_args(state, bstate, S, plan, bplan, slots, flags, cand_id,
     sets = sb.as_sets(sets)
     if sets is None or not bplan.boost:
         raise ValueError('stream_beam_boost: needs phrase sets and a plan built with boost=True')
-    for k, bs in enumerate(sets):
-        if bs.n_labels != int(blank):
-            raise ValueError(f'stream_beam_boost: phrase set {k} was compiled for {bs.n_labels} labels, blank is {blank}')
+    _stream_beam_set_labels('stream_beam_boost', sets, blank)
     B = cand_id.shape[0] if cand_id.dim() == 3 else 0
     _i32dev(boost_set, B, 'stream_beam_boost: boost_set')
     if out is None:
@@ -1645,16 +1641,10 @@ def stream_beam_boost_args(state, bstate, S, plan, bplan, slots, flags, cand_id,
     assert t is not None and t.is_cuda and t.is_contiguous() and t.dtype == torch.int64, 'stream_beam_boost: out.end_boost_score'
     inner = stream_beam_args(state, bstate, S, plan, bplan, slots, flags, cand_id, cand_q, enc_lens, first_frame, blank, lm, alpha,
                              beta, out)
-    blobs = [boost_device(bs, state.device) for bs in sets] if blobs is None else list(blobs)
-    assert len(blobs) == len(sets), 'stream_beam_boost: one blob per set'
     a = StreamBeamBoostArgs()
-    a.struct_size, a.n_sets = C.sizeof(StreamBeamBoostArgs), len(sets)
     C.memmove(C.byref(a.beam), C.byref(inner), C.sizeof(StreamBeamArgs))
-    if lm is None:
-        a.beam.space = int(sets[0].space)
-    for k, (bs, blob) in enumerate(zip(sets, blobs)):
-        a.sets[k], a.set_bytes[k], a.whole_words[k] = blob.data_ptr(), blob.numel(), int(bs.whole_words)
-    a.boost_set, a.end_boost_score = boost_set.data_ptr(), t.data_ptr()
+    blobs = _stream_beam_sets(a, 'stream_beam_boost', sets, blobs, boost_set, state.device, lm)
+    a.end_boost_score = t.data_ptr()
     a._keep = inner._keep + (blobs, boost_set)
     return a
 
@@ -1683,9 +1673,7 @@ def stream_beam_ep_buffers(B, bplan, E, device, with_lm, P=None, Ptail=None, Pen
     """k_stream_beam_ep's outputs as a qasr.stream_beam.BeamEpStepBatch of cuda tensors (E: the records' row pitch,
     EndpointPlan.max_records)"""
     from . import stream_beam as sb
-    P = bplan.delta_pitch if P is None else int(P)
-    Ptail = bplan.tail_pitch if Ptail is None else int(Ptail)
-    Pend = bplan.end_pitch if Pend is None else int(Pend)
+    P, Ptail, Pend = _stream_beam_pitches(bplan, P, Ptail, Pend)
     i = lambda *s: torch.empty(*s, device=device, dtype=torch.int32)
     l = lambda *s: torch.empty(*s, device=device, dtype=torch.int64)
     nb, E = bplan.n_best, int(E)
@@ -1697,70 +1685,36 @@ def stream_beam_ep_args(state, bstate, S, plan, bplan, slots, flags, cand_id, ca
                         boost_set=None, lm=None, alpha=0.0, beta=0.0, out=None, blobs=None):
     """the filled qasr_stream_beam_ep_args of stream_beam_ep (the tensors it points to are kept alive on it)"""
     from . import stream_beam as sb, stream_ep as qe
-    from .beam import TAB_ENTRIES
-    dev = state.device
+    who, dev = 'stream_beam_ep', state.device
     sets = sb.as_sets(sets)
     if (sets is not None) != bplan.boost:
         raise ValueError('stream_beam_ep: phrase sets go with a plan built with boost=True')
-    for k, bs in enumerate(sets or []):
-        if bs.n_labels != int(blank):
-            raise ValueError(f'stream_beam_ep: phrase set {k} was compiled for {bs.n_labels} labels, blank is {blank}')
-    if cand_id.dim() != 3 or cand_id.dtype != torch.int32 or not cand_id.is_contiguous() or not cand_id.is_cuda:
-        raise ValueError(f'stream_beam_ep: cand_id must be a contiguous cuda int32 tensor [B, Tw, N], got {cand_id.dtype} {tuple(cand_id.shape)}')
-    if cand_q.dtype != torch.int32 or not cand_q.is_contiguous() or cand_q.shape != cand_id.shape:
-        raise ValueError('stream_beam_ep: cand_q must be a contiguous int32 tensor of the shape of cand_id')
-    B, Tw, N = cand_id.shape
-    for t, w in ((slots, 'slots'), (flags, 'flags'), (enc_lens, 'enc_lens'), (first_frame, 'first_frame'), (ep.n_records, 'ep.n_records'),
-                 (ep.status, 'ep.status')) + (((boost_set, 'boost_set'),) if sets is not None else ()):
-        _i32dev(t, B, 'stream_beam_ep: ' + w)
+    _stream_beam_set_labels(who, sets, blank)
+    B, _, _ = _stream_beam_rows(who, cand_id, cand_q,
+                                ((slots, 'slots'), (flags, 'flags'), (enc_lens, 'enc_lens'), (first_frame, 'first_frame'),
+                                 (ep.n_records, 'ep.n_records'), (ep.status, 'ep.status')) + (((boost_set, 'boost_set'),) if sets is not None else ()))
     E = ep.records.shape[1] if ep.records.dim() == 3 else 0
     assert ep.records.is_cuda and ep.records.dtype == torch.int32 and ep.records.is_contiguous() and \
         tuple(ep.records.shape) == (B, E, qe.REC_WORDS), 'stream_beam_ep: ep.records'
-    alpha_q = beta_q = 0
-    if lm is not None:
-        from .ngram import fixed_weights
-        alpha_q, beta_q = fixed_weights(alpha, beta)
-        if lm.n_labels != int(blank):
-            raise ValueError(f'stream_beam_ep: the model was loaded for {lm.n_labels} labels, blank is {blank}')
+    alpha_q, beta_q = _lm_weights(who, lm, alpha, beta, blank)
     if out is None:
         out = stream_beam_ep_buffers(B, bplan, E, dev, lm is not None)
-    tab = lae_table_device(dev)
-    blob = None if lm is None else lm_device(lm, dev)
+    assert out.cut_labels.dim() == 4 and tuple(out.cut_labels.shape[:3]) == (B, E, bplan.n_best), 'stream_beam_ep: out.cut_labels'
     x = StreamBeamEpArgs()
     x.struct_size, x.E = C.sizeof(StreamBeamEpArgs), E
-    x.boost.struct_size, x.boost.n_sets = C.sizeof(StreamBeamBoostArgs), 0 if sets is None else len(sets)
-    a = x.boost.beam
-    a.struct_size = C.sizeof(StreamBeamArgs)
-    a.S, a.B, a.Wl, a.C, a.Rr, a.samples_per_frame, a.Tw = int(S), B, plan.Wl, plan.C, plan.Rr, plan.samples_per_frame, Tw
-    a.N, a.beam_width, a.n_best, a.blank = N, bplan.W, bplan.n_best, int(blank)
-    a.Lg, a.K, a.F, a.max_final_frames = bplan.Lg, bplan.K, bplan.F, bplan.max_final_frames
-    assert out.cut_labels.dim() == 4 and tuple(out.cut_labels.shape[:3]) == (B, E, bplan.n_best), 'stream_beam_ep: out.cut_labels'
-    a.P, a.Ptail, a.Pend = out.labels.shape[1], out.tail_labels.shape[1], out.cut_labels.shape[3]
-    a.lae_entries = TAB_ENTRIES
-    a.state, a.state_bytes = state.data_ptr(), state.numel() * state.element_size()
-    a.beam_state, a.beam_state_bytes = bstate.data_ptr(), bstate.numel() * bstate.element_size()
-    a.slots, a.flags, a.cand_id, a.cand_q = slots.data_ptr(), flags.data_ptr(), cand_id.data_ptr(), cand_q.data_ptr()
-    a.enc_lens, a.first_frame, a.lae_table = enc_lens.data_ptr(), first_frame.data_ptr(), tab.data_ptr()
-    i64 = ('cut_score', 'cut_lm_score', 'cut_boost_score')
-    for n in ('labels', 'frames', 'n_new_labels', 'commit_len', 'n_live', 'status', 'tail_labels', 'tail_n', 'n_cuts', 'cut_n_hyps',
-              'cut_delta_end', 'cut_labels', 'cut_n_labels', 'cut_score', 'cut_lm_score', 'cut_boost_score'):
+    x.boost.struct_size = C.sizeof(StreamBeamBoostArgs)
+    tab, blob = _stream_beam_fill(x.boost.beam, who, state, bstate, S, plan, bplan, slots, flags, cand_id, cand_q, enc_lens, first_frame,
+                                  blank, lm, alpha_q, beta_q, out, _STREAM_BEAM_STEP_OUTS, out.cut_labels.shape[3])
+    for n in ('n_cuts', 'cut_n_hyps', 'cut_delta_end', 'cut_labels', 'cut_n_labels', 'cut_score', 'cut_lm_score', 'cut_boost_score'):
         t = getattr(out, n)
         if t is None:
             assert (n == 'cut_lm_score' and lm is None) or (n == 'cut_boost_score' and sets is None), 'stream_beam_ep: out.' + n
             continue
-        assert t.is_cuda and t.is_contiguous() and t.dtype == (torch.int64 if n in i64 else torch.int32), 'stream_beam_ep: out.' + n
-        setattr(a if hasattr(a, n) else x, n, t.data_ptr())
+        assert t.is_cuda and t.is_contiguous() and t.dtype == (torch.int64 if n.endswith('score') else torch.int32), 'stream_beam_ep: out.' + n
+        setattr(x, n, t.data_ptr())
     x.records, x.n_records, x.ep_status = ep.records.data_ptr(), ep.n_records.data_ptr(), ep.status.data_ptr()
-    if lm is not None:
-        a.lm, a.lm_bytes, a.alpha_q, a.beta_q, a.space = blob.data_ptr(), blob.numel(), alpha_q, beta_q, int(lm.space)
     if sets is not None:
-        blobs = [boost_device(bs, dev) for bs in sets] if blobs is None else list(blobs)
-        assert len(blobs) == len(sets), 'stream_beam_ep: one blob per set'
-        if lm is None:
-            a.space = int(sets[0].space)
-        for k, (bs, bl) in enumerate(zip(sets, blobs)):
-            x.boost.sets[k], x.boost.set_bytes[k], x.boost.whole_words[k] = bl.data_ptr(), bl.numel(), int(bs.whole_words)
-        x.boost.boost_set = boost_set.data_ptr()
+        blobs = _stream_beam_sets(x.boost, who, sets, blobs, boost_set, dev, lm)
     x._keep = (tab, blob, out, blobs, boost_set, ep)
     return x
 

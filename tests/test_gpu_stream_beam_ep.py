@@ -16,6 +16,7 @@ pytestmark = pytest.mark.gpu
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 
 import stream_beam_ep_cases as cases  # noqa: E402
+import stream_beam_refusal_cases as refusals  # noqa: E402
 import stream_cases as sc  # noqa: E402
 from qasr import beam as qb  # noqa: E402
 from qasr import stream as st  # noqa: E402
@@ -414,17 +415,8 @@ def test_abi_refusals_leave_the_outputs_alone():
                 setattr(a, k, v)
             return a
 
-        nb, nbb = state.numel() * 4, bstate.numel() * 4
-        inner = [dict(struct_size=8), dict(B=0), dict(B=S + 1), dict(Wl=0), dict(C=0), dict(samples_per_frame=0), dict(Wl=splan.Wl + 1),
-                 dict(C=splan.C - 1), dict(Rr=splan.Rr + 1), dict(Rr=splan.Wl), dict(state_bytes=nb - 4), dict(Tw=0), dict(Tw=65537),
-                 dict(N=0), dict(N=65), dict(beam_width=0), dict(beam_width=129), dict(n_best=0), dict(n_best=W + 1), dict(blank=-1),
-                 dict(lae_entries=16383), dict(Lg=-1), dict(K=0), dict(K=33), dict(F=bplan.F - 1), dict(F=(1 << 20) + 1),
-                 dict(beam_state_bytes=nbb - 4), dict(F=bplan.F + 1), dict(state=state.data_ptr() + 4), dict(beam_state=bstate.data_ptr() + 8),
-                 dict(max_final_frames=0), dict(max_final_frames=splan.Tw + 1), dict(P=bplan.delta_pitch - 1), dict(Ptail=0),
-                 dict(Pend=bplan.F - 1), dict(lm_bytes=64), dict(lm=engine.lm_device(lm, 'cuda').data_ptr() + 4),
-                 dict(alpha_q=-1), dict(alpha_q=(16 << 16) + 1), dict(beta_q=-(16 << 16) - 1), dict(space=-2), dict(space=blank)] + \
-            [{n: None} for n in ('state', 'beam_state', 'slots', 'flags', 'cand_id', 'cand_q', 'enc_lens', 'first_frame', 'lae_table',
-                                 'labels', 'frames', 'n_new_labels', 'commit_len', 'n_live', 'status', 'tail_labels', 'tail_n')]
+        inner = refusals.step_mutations(splan, bplan, S, state, bstate, engine.lm_device(lm, 'cuda').data_ptr(), blank, ends=False)
+        assert len(inner) == 42 + 17
         mid = [dict(struct_size=8), dict(n_sets=9), dict(n_sets=-1)]
         if boosted:
             blob1 = engine.boost_device(sets[1], 'cuda')

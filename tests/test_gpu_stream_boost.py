@@ -17,6 +17,7 @@ sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 
 import boost_cases  # noqa: E402
 import stream_beam_cases as sbc  # noqa: E402
+import stream_beam_refusal_cases as refusals  # noqa: E402
 import stream_boost_cases as cases  # noqa: E402
 import stream_cases as sc  # noqa: E402
 from qasr import beam as qb  # noqa: E402
@@ -384,23 +385,13 @@ def test_abi_refusals_leave_the_outputs_alone():
                 setattr(a, k, v)
         return a
 
-    nb, nbb = state.numel() * 4, bstate.numel() * 4
+    nbb = bstate.numel() * 4
     assert nbb == sb.state_bytes(S, W, bplan.F, True) == lib.qasr_stream_beam_boost_state_bytes(S, W, bplan.F)
     assert nbb > lib.qasr_stream_beam_state_bytes(S, W, bplan.F)
     blob1 = engine.boost_device(sets[1], 'cuda')
-    inner = [dict(struct_size=8), dict(B=0), dict(B=S + 1), dict(Wl=0), dict(C=0), dict(samples_per_frame=0), dict(Wl=splan.Wl + 1),
-             dict(C=splan.C - 1), dict(Rr=splan.Rr + 1), dict(Rr=splan.Wl), dict(state_bytes=nb - 4), dict(Tw=0), dict(Tw=65537),
-             dict(N=0), dict(N=65), dict(beam_width=0), dict(beam_width=129), dict(n_best=0), dict(n_best=W + 1), dict(blank=-1),
-             dict(lae_entries=16383), dict(Lg=-1), dict(K=0), dict(K=33), dict(F=bplan.F - 1), dict(F=(1 << 20) + 1),
-             dict(beam_state_bytes=nbb - 4), dict(beam_state_bytes=lib.qasr_stream_beam_state_bytes(S, W, bplan.F)), dict(F=bplan.F + 1),
-             dict(state=state.data_ptr() + 4), dict(beam_state=bstate.data_ptr() + 8),
-             dict(max_final_frames=0), dict(max_final_frames=splan.Tw + 1), dict(P=bplan.delta_pitch - 1), dict(Ptail=0),
-             dict(Pend=bplan.F - 1), dict(end_lm_score=None), dict(lm_bytes=64), dict(lm=engine.lm_device(lm, 'cuda').data_ptr() + 4),
-             dict(alpha_q=-1), dict(alpha_q=(16 << 16) + 1), dict(beta_q=-(16 << 16) - 1), dict(space=-2), dict(space=blank),
-             dict(space=-1, lm=None, end_lm_score=None)] + \
-        [{n: None} for n in ('state', 'beam_state', 'slots', 'flags', 'cand_id', 'cand_q', 'enc_lens', 'first_frame', 'lae_table',
-                             'labels', 'frames', 'n_new_labels', 'commit_len', 'n_live', 'status', 'tail_labels', 'tail_n',
-                             'end_labels', 'end_n_labels', 'end_score', 'n_hyps')]
+    inner = refusals.step_mutations(splan, bplan, S, state, bstate, engine.lm_device(lm, 'cuda').data_ptr(), blank, ends=True) + \
+        [dict(beam_state_bytes=lib.qasr_stream_beam_state_bytes(S, W, bplan.F)), dict(space=-1, lm=None, end_lm_score=None)]
+    assert len(inner) == 43 + 21 + 2
     outer = [dict(struct_size=8), dict(n_sets=0), dict(n_sets=9), dict(n_sets=-1), dict(boost_set=None), dict(end_boost_score=None),
              dict(sets=(1, None)), dict(sets=(0, blob1.data_ptr() + 8)), dict(set_bytes=(1, 64)), dict(set_bytes=(0, 1 << 31))]
     s = engine._stream_ptr()
