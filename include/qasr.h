@@ -261,7 +261,8 @@ int qasr_engine_run_op(qasr_engine* e, void* stream, int op);
  * (nemo/quantization/utils/quant_modules.py:121-125: x_min = quantile(x_act, 1 - p/100), x_max = quantile(x_act, p/100))
  * over a flattened float32 device tensor of n elements (16-byte aligned, finite values): exact order statistics by a
  * 4-pass radix select + torch's float32 linear interpolation.  out2[0] = quantile(q_lo), out2[1] = quantile(q_hi);
- * bit-identical to torch.quantile on the CPU.  Enqueued on `stream`; `workspace` (device, qasr_quantile_workspace_bytes()
+ * bit-identical to torch.quantile on the CPU; ranks clamp to n - 1 (n > 2^24, where fl32(n - 1) can round up to n:
+ * q = 1 is the maximum).  Enqueued on `stream`; `workspace` (device, qasr_quantile_workspace_bytes()
  * bytes) must stay untouched until the stream has finished. */
 size_t qasr_quantile_workspace_bytes(void);
 int qasr_quantile2(void* stream, const float* x, size_t n, float q_lo, float q_hi, float* out2, void* workspace,
@@ -1375,8 +1376,9 @@ int qasr_dyn_quant_in(void* stream, const float* x, int Tx, const uint32_t* minm
 int qasr_dyn_residue_codes(void* stream, const int8_t* codes, int x_unsigned, const float* s_x, size_t n, int8_t* lo,
                            int8_t* hi);
 /* the conv that consumes those codes (quant_modules.py:293-299,307): sf_out[c] = s_w[c] s_x, bias[c] =
- * clamp(round(fl32(1/sf_out[c]) bprime[c])) evaluated in float32 (+ wsum128[c] = 128 sum(W[c]) when the codes are
- * stored as u8); rows C..C_pad-1: scale 1, bias 0. */
+ * clamp(round(fl32(1/sf_out[c]) bprime[c])) evaluated in float32, saturated to [INT32_MIN, INT32_MAX] (the reference's
+ * float32 clamp gives +-2^31: (float)INT32_MAX is its +2^31) (+ wsum128[c] = 128 sum(W[c]) modulo 2^32 when the codes
+ * are stored as u8); rows C..C_pad-1: scale 1, bias 0. */
 int qasr_dyn_conv_params(void* stream, const float* s_x, const float* s_w, const float* bprime, const int32_t* wsum128,
                          int C, int C_pad, float* sf_out, int32_t* bias);
 

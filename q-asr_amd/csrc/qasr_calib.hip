@@ -41,8 +41,10 @@ __global__ void __launch_bounds__(64) k_qs_init(QSelState* st, unsigned long lon
     const float q = t ? q_hi : q_lo;
     const float rank = mul_f32_unfused(q, (float)(n - 1)); // torch: ranks = q * (size - 1) in the input dtype
     const float below = floorf(rank), above = ceilf(rank);
-    st->rank[2 * t] = (unsigned long long)below;
-    st->rank[2 * t + 1] = (unsigned long long)above;
+    // n > 2^24: fl32(n - 1) may round up to n, and q = 1 then asks for rank n, which no element has (torch.quantile
+    // refuses inputs this large).  Both ranks clamp to the last element: q = 1 is the maximum
+    st->rank[2 * t] = min((unsigned long long)below, n - 1);
+    st->rank[2 * t + 1] = min((unsigned long long)above, n - 1);
     st->weight[t] = __fsub_rn(rank, below);
     st->prefix[2 * t] = st->prefix[2 * t + 1] = 0;
   }

@@ -272,7 +272,10 @@ __global__ void __launch_bounds__(256) k_dyn_conv_params(DynConvP p) {
   long long bi = 0;
   if (p.bprime) {           // SymmetricQuantFunction at 32 bits, evaluated in float32 (quant_modules.py:293-299)
     const float q = rintf(mul_f32_unfused(__fdiv_rn(1.0f, sb), p.bprime[c]));
-    bi = (long long)fminf(fmaxf(q, -2147483648.0f), 2147483520.0f);
+    // the reference clamps in float32 to [-n, n - 1] with n = 2^31 - 1: both bounds round to +-2^31, and its double conv
+    // carries +2^31 on.  Saturate that side to INT32_MAX: (float)INT32_MAX is 2^31 again, so every float view of an
+    // accumulator that holds just this bias (a silent batch: s_x at its floor, all codes 0) equals the reference's
+    bi = q >= 2147483648.0f ? 2147483647ll : (long long)fmaxf(q, -2147483648.0f);
   }
   if (p.wsum128) bi += p.wsum128[c];
   p.bias[c] = (int32_t)bi;
@@ -322,6 +325,10 @@ int qasr_dyn_range_percentile(void* stream, const qasr_dyn_view* a, const qasr_d
                               void* workspace, size_t workspace_bytes, uint32_t* minmax) {
   if (!minmax || !x_act || B < 1 || C < 1 || T < 1 || (!xf && (!view_ok(a) || T > Tp)) || (xf && T > Tx) || (b && !view_ok(b)))
     return QASR_ERR_ARG;
+  // what qasr_quantile2 would refuse, before x_act is written
+  if (!workspace || workspace_bytes < qasr_quantile_workspace_bytes() || !(q_lo >= 0.f && q_lo <= 1.f) ||
+      !(q_hi >= 0.f && q_hi <= 1.f) || ((uintptr_t)x_act & 15) || ((uintptr_t)workspace & 7))
+    return QASR_ERR_ARG;
   hipStream_t s = (hipStream_t)stream;
   DynRangeP p{};
   if (!xf) p.a = make_view(a);
@@ -355,7 +362,7 @@ int qasr_dyn_act_params(void* stream, const uint32_t* minmax, int bits, int C, c
 
 int qasr_dyn_requant(void* stream, const qasr_dyn_view* a, const double* Ma, const qasr_dyn_view* b, const double* Mb,
                      const int32_t* lens, int relu, int B, int C, int T, int Tp, int lo, int hi, int8_t* out) {
-  if (!view_ok(a) || !Ma || !out || (b && (!view_ok(b) || !Mb)) || B < 1 || C < 1 || T > Tp ||
+  if (!view_ok(a) || !Ma || !out || (b && (!view_ok(b) || !Mb)) || B < 1 || C < 1 || T < 0 || T > Tp ||
       lo > hi || lo < -256 || hi > 255 || hi - lo > 255)
     return QASR_ERR_ARG;
   DynRequantP p{};
@@ -372,7 +379,8 @@ int qasr_dyn_requant(void* stream, const qasr_dyn_view* a, const double* Ma, con
 
 int qasr_dyn_quant_in(void* stream, const float* x, int Tx, const uint32_t* minmax, const int32_t* lens, int bits, int B,
                       int C, int T, int Tp, float* s_out, int8_t* out) {
-  if (!x || !minmax || !lens || !s_out || !out || bits < 2 || bits > 8 || T > Tx || T > Tp) return QASR_ERR_ARG;
+  if (!x || !minmax || !lens || !s_out || !out || bits < 2 || bits > 8 || B < 1 || C < 1 || T < 0 || T > Tx || T > Tp)
+    return QASR_ERR_ARG;
   DynQuantInP p{};
   p.x = x, p.mm = minmax, p.lens = lens;
   p.bits = bits, p.B = B, p.C = C, p.T = T, p.Tx = Tx, p.Tp = Tp;
