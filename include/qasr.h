@@ -1100,6 +1100,84 @@ typedef struct qasr_stream_endpoint_args {
 } qasr_stream_endpoint_args;
 int qasr_stream_endpoint(void* stream, const qasr_stream_endpoint_args* args);
 
+/* ---- streaming keyword spotting: per-stream lattice state on the device ------------------------------------------------------
+ * qasr_ctc_spot over the frames that a streaming step makes final.  K keywords are shared by all streams of a session; problem
+ * p = row * K + k of a step, its state at (slot, k).  A keyword's whole lattice is one Viterbi row of pairs (D i64, start i32),
+ * so a stream's state between two steps is that row plus one open hit: a step loads it, walks the frames that became final -
+ * the frame step, the candidate rule and the overlap rule are qasr_ctc_spot's on every point, the fresh start (0, t) with t the
+ * GLOBAL frame - and stores it back.  An open hit closes when a candidate that does not overlap arrives, at END, and EARLY:
+ * after frame t unless some state 1 .. 2L - 1 is live with start <= open.end and (t + 1) - start + 1 <= max_span; no later
+ * candidate can overlap a hit closed this way, so the emitted list is qasr_ctc_spot's of the whole stream.  The rule, the state
+ * layout and the NumPy twin are qasr/stream_spot.py (STREAM_SPOT_RULES), which k_stream_spot follows byte for byte, the state
+ * block included.  Pinned: that equality; that the hits of the steps of ANY slicing of a stream, concatenated, equal spot_host
+ * over the concatenated final frames on every byte of start / end / score and in count.  Accuracy on speech, the façade's
+ * defaults and how long a final hit trails its end (up to max_span frames on blank-dominated audio) are not pinned.
+ *   state       the stream state of qasr_stream_push / _emit, READ-ONLY here: launch this call AFTER qasr_stream_emit of the same
+ *               rows (hi = its frames_done)
+ *   spot_state  device memory of qasr_stream_spot_state_bytes(S, K, max_labels) bytes, 16-byte aligned: per (slot, keyword) a
+ *               block of 8 + 3 SP 32-bit words, SP = 64 NS, NS = 1 / 2 / 4 by 2 max_labels + 1 <= 64 / 128 / 256: frames_done of
+ *               this block, stepped (0: fresh), open flag, the open hit's start, end, count (hits emitted since BEGIN), its
+ *               score (i64); then D i64 [SP] and start i32 [SP].  A block with stepped == 0 is a fresh stream whatever else it
+ *               holds: zeroed memory is S fresh streams.  0 bytes: S or K < 1, max_labels outside 1 .. QASR_SPOT_MAX_LABELS.
+ *   log_probs f32 [B][Tw][n_classes] with pitches, star_logp f32 [B][star_pitch] (qasr_ctc_star, penalty 0, lens = enc_lens,
+ *               over the same window), enc_lens, first_frame, slots, flags   what the step's forward and qasr_stream_emit were
+ *               given; QASR_STREAM_BEGIN makes the slot's blocks fresh first, QASR_STREAM_END closes the open hit
+ *   emit_status i32 [B]   qasr_stream_emit's status of the same step
+ *   targets i32 [K][max_labels], target_lens i32 [K]   device data: the kernel checks them itself (ok) and reads nothing through
+ *               a bad label;  threshold_q, max_span   as for qasr_ctc_spot
+ *   max_final_frames   the most frames one step walks (StreamPlan.max_final_frames); PH: the row pitch of the hit outputs (a
+ *               frame closes at most two hits and END one more: 2 * max_final_frames + 1 holds every hit of a step)
+ *   -> hit_start, hit_end, hit_detect i32 [B * K][PH] (global frames, inclusive; detect: the frame after which the hit closed,
+ *      hi - 1 on END), hit_score i64 [B * K][PH]: the hits that closed in this step, in order, tails 0; n_new_hits: every hit
+ *      closed, stored or not; n_hits_total: the block's count; open_start, open_end i32, open_score i64 [B * K]: the open hit
+ *      after the step (-1 / -1 / 0: none), the provisional detection; ok (the keyword's validity, as qasr_ctc_spot's), status
+ *   status 0; 1: emit_status of the row is not 0; 2: no such slot; 3: lo > hi, lo < first_frame, lo < hi and hi beyond
+ *      first_frame + enc_len, or hi - lo > max_final_frames (lo: this block's frames_done, 0 when fresh or with BEGIN).  A problem
+ *      with a status, or with ok = 0, leaves its block alone and writes an empty step (no hits, counts 0, open -1 / -1 / 0).
+ * One launch, one wave per problem; plain vector stores by the wave that owns the block; no LDS, no barrier, no atomics; nothing
+ * is read back; the chain qasr_ctc_star -> qasr_stream_spot behind qasr_stream_emit can be captured.
+ * QASR_ERR_ARG with nothing launched and nothing written: an unknown struct_size, a NULL pointer (all are required), what
+ * qasr_stream_emit refuses about S, B, Wl, C, Rr, samples_per_frame, state_bytes and Tw, what qasr_ctc_spot refuses about
+ * n_classes (its C), K, max_labels, blank, pitch_frame, pitch_utt, star_pitch (with T = Tw), threshold_q and max_span, B * K above
+ * 2^31 - 1, PH < 1, max_final_frames outside 1 .. Tw, spot_state_bytes below the query, a state not 16-byte aligned. */
+size_t qasr_stream_spot_state_bytes(int S, int K, int max_labels);
+typedef struct qasr_stream_spot_args {
+  uint32_t struct_size;        /* sizeof of this struct in the caller's header */
+  int32_t S, B, Wl, C, Rr, samples_per_frame, Tw;    /* C: the chunk in samples, as in qasr_stream_emit_args */
+  int32_t n_classes, K, max_labels, blank;
+  int32_t threshold_q;         /* fixed point, nats per frame */
+  int32_t max_span;            /* frames */
+  int32_t PH;                  /* row pitch of the hit outputs */
+  int32_t max_final_frames;
+  int64_t pitch_utt, pitch_frame;   /* of log_probs, in floats */
+  const float* log_probs;
+  const float* star_logp;      /* [B][star_pitch] */
+  int64_t star_pitch;          /* in floats, >= Tw */
+  const void* state;
+  size_t state_bytes;
+  void* spot_state;
+  size_t spot_state_bytes;
+  const int32_t* slots;
+  const int32_t* flags;
+  const int32_t* enc_lens;
+  const int32_t* first_frame;
+  const int32_t* emit_status;
+  const int32_t* targets;      /* [K][max_labels] */
+  const int32_t* target_lens;  /* [K] */
+  int32_t* hit_start;          /* [B * K][PH] */
+  int32_t* hit_end;
+  int32_t* hit_detect;
+  int64_t* hit_score;
+  int32_t* n_new_hits;         /* [B * K] */
+  int32_t* n_hits_total;
+  int32_t* open_start;
+  int32_t* open_end;
+  int64_t* open_score;
+  int32_t* ok;
+  int32_t* status;
+} qasr_stream_spot_args;
+int qasr_stream_spot(void* stream, const qasr_stream_spot_args* args);
+
 /* ---- streaming beam endpointing: the per-stream beam finalised and reset at the cuts of qasr_stream_endpoint ---------------
  * qasr_stream_beam / qasr_stream_beam_boost for sessions that are cut into utterances: the same frame step and commit round,
  * and at every record of the step's qasr_stream_endpoint the END pass of those calls, written per cut, after which the slot's

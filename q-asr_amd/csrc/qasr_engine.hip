@@ -1809,6 +1809,42 @@ int qasr_stream_endpoint(void* stream, const qasr_stream_endpoint_args* a) {
   return launched("stream_endpoint", launch_stream_endpoint((hipStream_t)stream, *a));
 }
 
+// ---- streaming keyword spotting (k_stream_spot, qasr_stream_spot.hip): qasr_ctc_spot's checks of the keywords and the window's
+// planes (T = Tw), qasr_stream_emit's of the session's geometry, the spot state's, and one launch
+size_t qasr_stream_spot_state_bytes(int S, int K, int max_labels) { return stream_spot_state_bytes(S, K, max_labels); }
+
+int qasr_stream_spot(void* stream, const qasr_stream_spot_args* a) {
+  const char* const who = "stream_spot";
+  if (int rc = args_check(who, a)) return rc;
+  if (!a->state || !a->spot_state || !a->slots || !a->flags || !a->log_probs || !a->star_logp || !a->enc_lens || !a->first_frame ||
+      !a->emit_status || !a->targets || !a->target_lens)
+    return fail(QASR_ERR_ARG, "stream_spot: state, spot_state, slots, flags, log_probs, star_logp, enc_lens, first_frame, emit_status, targets and target_lens are required");
+  if (!a->hit_start || !a->hit_end || !a->hit_detect || !a->hit_score || !a->n_new_hits || !a->n_hits_total || !a->open_start ||
+      !a->open_end || !a->open_score || !a->ok || !a->status)
+    return fail(QASR_ERR_ARG, "stream_spot: every output pointer is required");
+  if (int rc = stream_geometry(who, a->S, a->B, a->Wl, a->C, a->Rr, a->samples_per_frame, a->state_bytes)) return rc;
+  if (a->Tw < 1 || a->n_classes < 1 || a->K < 1)
+    return fail(QASR_ERR_ARG, "stream_spot: Tw %d, n_classes %d and K %d must be at least 1", a->Tw, a->n_classes, a->K);
+  if ((long long)a->B * a->K > INT_MAX) return fail(QASR_ERR_ARG, "stream_spot: B %d * K %d is above 2^31 - 1", a->B, a->K);
+  if (a->max_labels < 1 || a->max_labels > QASR_SPOT_MAX_LABELS)
+    return fail(QASR_ERR_ARG, "stream_spot: max_labels %d is outside 1 .. %d", a->max_labels, QASR_SPOT_MAX_LABELS);
+  if (int rc = ctc_blank_check(who, a->blank, a->n_classes)) return rc;
+  if (int rc = ctc_star_pitch_check(who, a->star_pitch, a->Tw)) return rc;
+  if (int rc = ctc_pitch_check(who, a->Tw, a->n_classes, a->pitch_frame, a->pitch_utt)) return rc;
+  if (a->threshold_q < QASR_SPOT_MIN_THRESHOLD_Q || a->threshold_q > 0)
+    return fail(QASR_ERR_ARG, "stream_spot: threshold_q %d is outside %d .. 0", a->threshold_q, QASR_SPOT_MIN_THRESHOLD_Q);
+  if (a->max_span < 1 || a->max_span > QASR_SPOT_MAX_SPAN)
+    return fail(QASR_ERR_ARG, "stream_spot: max_span %d is outside 1 .. %d", a->max_span, QASR_SPOT_MAX_SPAN);
+  if (a->PH < 1) return fail(QASR_ERR_ARG, "stream_spot: PH %d < 1", a->PH);
+  if (a->max_final_frames < 1 || a->max_final_frames > a->Tw)
+    return fail(QASR_ERR_ARG, "stream_spot: max_final_frames %d is outside 1 .. Tw = %d", a->max_final_frames, a->Tw);
+  const size_t need = stream_spot_state_bytes(a->S, a->K, a->max_labels);
+  if (!need || a->spot_state_bytes < need)
+    return fail(QASR_ERR_ARG, "stream_spot: spot_state_bytes %zu, qasr_stream_spot_state_bytes gives %zu", a->spot_state_bytes, need);
+  if (((uintptr_t)a->state | (uintptr_t)a->spot_state) & 15) return fail(QASR_ERR_ARG, "stream_spot: state or spot_state is not 16-byte aligned");
+  return launched(who, launch_stream_spot((hipStream_t)stream, *a));
+}
+
 // ---- streaming at any sample rate (k_stream_rs_append / _fir, qasr_stream_rs.hip): the checks of include/qasr.h, two launches
 size_t qasr_stream_rs_state_bytes(int S, int hcap) { return stream_rs_state_bytes(S, hcap); }
 size_t qasr_stream_rs_work_bytes(int B) { return stream_rs_work_bytes(B); }

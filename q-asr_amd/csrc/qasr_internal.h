@@ -208,6 +208,9 @@ int launch_stream_beam_boost(hipStream_t s, const qasr_stream_beam_boost_args& a
 // qasr_stream_ep.hip: streaming endpointing (k_stream_endpoint); checked by qasr_stream_endpoint
 size_t stream_ep_state_bytes(int S);
 int launch_stream_endpoint(hipStream_t s, const qasr_stream_endpoint_args& a);
+// qasr_stream_spot.hip: streaming keyword spotting (k_stream_spot<NS>); checked by qasr_stream_spot
+size_t stream_spot_state_bytes(int S, int K, int max_labels);
+int launch_stream_spot(hipStream_t s, const qasr_stream_spot_args& a);
 // qasr_stream_beam_ep.hip: the streaming beam search finalised and reset at cuts (k_stream_beam_ep<LM, BOOST>); checked by qasr_stream_beam_ep
 int launch_stream_beam_ep(hipStream_t s, const qasr_stream_beam_ep_args& a);
 // qasr_stream_rs.hip: streaming at any sample rate (k_stream_rs_append, k_stream_rs_fir); checked by qasr_stream_rs_push

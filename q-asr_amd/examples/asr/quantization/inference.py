@@ -106,7 +106,10 @@ def main():
                         "OUT gets one JSON line per manifest entry - audio_filepath and hits [{keyword, start, end, score}], times "
                         "in seconds, score the mean likelihood ratio against the frame's best class in nats per frame (0: the "
                         "keyword is the greedy path there); hypotheses, WER and the other outputs are unchanged.  With --window_s "
-                        "the keywords are searched in the stitched windows of the whole recording (EncDecCTCModel.spot_long)")
+                        "the keywords are searched in the stitched windows of the whole recording (EncDecCTCModel.spot_long).  With "
+                        "--stream_chunk_s the manifest plays through streaming sessions that spot on the live stream "
+                        "(EncDecCTCModel.stream(spot=), k_star and k_stream_spot behind k_stream_emit in every step): the same lines, "
+                        "every hit with \"detected_s\", the stream time at which it became final; not with --beam_width")
     p.add_argument("--spot_threshold", type=float, default=None, metavar='X',
                    help="(extension, needs --spot) the lowest score a hit may have, -16 .. 0 nats per frame (default -1.0, untried on speech)")
     p.add_argument("--spot_max_span_s", type=float, default=None, metavar='S',
@@ -165,8 +168,9 @@ def main():
         for flag in ('window_s', 'align'):
             if getattr(args, flag) is not None:
                 p.error(f'--stream_chunk_s does not go with --{flag}: a streaming session steps by chunks')
-        if args.spot is not None:
-            p.error('--stream_chunk_s does not go with --spot: keyword spotting in a streaming session is not built')
+        if args.spot is not None and args.beam_width is not None:
+            p.error('--stream_chunk_s with --spot does not go with --beam_width: keyword spotting in a streaming beam session '
+                    '(stream(spot=) together with beam=) is not built')
     if (args.spot is None) != (args.spot_file is None):
         p.error('--spot OUT and --spot_file FILE go together')
     if (args.spot_threshold is not None or args.spot_max_span_s is not None) and args.spot is None:
@@ -307,16 +311,28 @@ def main():
                                                 pick(args.stream_max_utt_s, dflt.max_utt_s), pick(args.stream_hard_max_s, dflt.hard_max_s))
                 if stream_beam is not None and stream_ep is not None:        # k_stream_beam_ep behind emit and endpoint in every step
                     stream_beam.endpoint, stream_ep = stream_ep, None
+                stream_spot = None
+                if args.spot is not None:                                    # k_star + k_stream_spot behind k_stream_emit in every step
+                    from qasr import stream_spot as qss
+                    stream_spot = qss.StreamSpot(keywords=spot_words, threshold=-1.0 if args.spot_threshold is None else args.spot_threshold,
+                                                 max_span_s=10.0 if args.spot_max_span_s is None else args.spot_max_span_s)
                 try:
                     stream_sess = asr_model.stream(max_streams=args.batch_size, chunk_s=args.stream_chunk_s, tail=False,
                                                    left_s=4.0 if args.stream_left_s is None else args.stream_left_s,
                                                    right_s=0.96 if args.stream_right_s is None else args.stream_right_s,
                                                    input_rate=args.input_rate,       # int16 PCM: resampled per stream on the device
-                                                   beam=stream_beam, endpoint=stream_ep)
+                                                   beam=stream_beam, endpoint=stream_ep, spot=stream_spot)
                 except ValueError as e:
                     p.error(f'--stream_chunk_s / --stream_left_s / --stream_right_s / --input_rate / --stream_beam_lag_s / '
-                            f'--stream_endpoint_silence_s and its times: {e}')
+                            f'--stream_endpoint_silence_s and its times / --spot and its arguments: {e}')
             stream_hyps = asr_model.decode_stream(signal, batch[1], session=stream_sess)
+            if stream_sess.spot is not None:                     # the hits that closed while the recordings played, END included
+                stream_hyps = stream_hyps[0]
+                for row in stream_sess.decoded_hits:
+                    k = len(spotted)
+                    spotted.append(dict(audio_filepath=items[k][0] if not args.shuffle and k < len(items) else None,
+                                        hits=[dict(keyword=h.hit.keyword, start=h.hit.start_s, end=h.hit.end_s, score=h.hit.score,
+                                                   detected_s=h.detected_s) for h in row]))
             for h in stream_hyps:
                 if stream_sess.endpoint is not None:             # a recording's utterances: texts joined (by nothing for Zh)
                     n_utterances += len(h)
@@ -401,7 +417,7 @@ def main():
                     aligned[-1]['post'] = list(h.word_post)
                     if h.segments is not None:
                         aligned[-1]['segments'] = [[sg.text, sg.start_s, sg.end_s, sg.score, sg.post] for sg in h.segments]
-        if args.spot is not None:                            # k_star + k_spot behind the forward (with --window_s: behind k_stitch)
+        if args.spot is not None and args.stream_chunk_s is None:       # k_star + k_spot behind the forward (with --window_s: behind k_stitch)
             spot_kw = dict(keywords=spot_words, threshold=-1.0 if args.spot_threshold is None else args.spot_threshold,
                            max_span_s=10.0 if args.spot_max_span_s is None else args.spot_max_span_s)
             try:

@@ -695,7 +695,7 @@ class EncDecCTCModel(nn.Module):
         return qstream.StreamPlan(chunk_s, left_s, right_s, lp.sample_rate, lp.samples_per_frame, lp.frames_of)
 
     def stream(self, max_streams=32, chunk_s=0.96, left_s=4.0, right_s=0.96, tail=True, sample_rate=None, beam_width=None,
-               input_rate=None, channels=1, beam=None, boost=None, endpoint=None):
+               input_rate=None, channels=1, beam=None, boost=None, endpoint=None, spot=None):
         """A streaming session (an extension; NeMo's buffered streaming, the FrameBatchASR idea, for many streams at once):
 
             sess = model.stream(max_streams=32, chunk_s=0.96, left_s=4.0, right_s=0.96)
@@ -779,12 +779,27 @@ class EncDecCTCModel(nn.Module):
         list with n_best > 1).  A 'hard' cut can split a label's frames, so the label can show up at the end of one utterance
         and at the start of the next; a 'timeout' utterance reports whatever the beam holds, normally nothing.
 
+        spot=qasr.stream_spot.StreamSpot(keywords=[...], labels=None, threshold=-1.0, max_span_s=10.0): keyword spotting on the
+        live stream (qasr.stream_spot.STREAM_SPOT_RULES; k_star with penalty 0 and k_stream_spot behind k_stream_emit in every
+        step).  The keywords are spot()'s - the same parser, the same refusals - and are shared by all streams of the session;
+        every (stream, keyword) keeps its lattice row and one open hit on the device next to the stream state, and the session
+        forwards with log-probabilities.  push() returns the same StreamUpdates and close() what it returned; the hits that
+        closed - the END step's included - queue up in sess.take_hits() as qasr.ctc.StreamHit(slot, hit, detected_s), hit a
+        qasr.ctc.KeywordHit in seconds of the stream, sorted by (detected_s, slot, start_s, index); sess.pending_hits(slot)
+        lists the hits that are open after the last step: the provisional, immediate detection, which a later frame may still
+        replace by an overlapping hit with a higher mean.  The final hits of a stream are spot()'s hits over its final frames
+        on every byte, however the pushes are sliced.  A hit becomes final only when nothing can overlap it any more: on
+        blank-dominated audio that is up to max_span_s after its end, so a wake-word caller sets max_span_s near the keyword's
+        longest plausible duration and acts on pending_hits.  Both defaults are untried on speech.  It composes with
+        input_rate= and endpoint= unchanged; spot= together with beam= is not built.
+
         Refused: sample_rate other than the model's (here it names the model's rate: give the source's as input_rate=),
         a rate or filter the resampler refuses, channels outside 1 .. 8, beam_width (beam search across steps is beam=),
         boost (phrase boosting across steps is StreamBeam(boost=)), beam= arguments outside decode(beam_width=)'s ranges,
         more than 8 phrase sets or an empty dict of them, a set that qasr.boost.PhraseSet refuses, boost_weight outside
         0 .. 16, endpoint= times the plan refuses, beam= together with endpoint= (the endpointing of a beam session is
-        StreamBeam(endpoint=))."""
+        StreamBeam(endpoint=)), spot= that is no StreamSpot, whatever spot() refuses about its keywords, threshold and
+        max_span_s, spot= together with beam=."""
         target = int(self.preprocessor._sample_rate)
         if sample_rate is not None and int(sample_rate) != target:
             raise ValueError(f'stream: sample_rate {sample_rate} is not the model\'s {target}: sample_rate names the model\'s rate '
@@ -816,6 +831,16 @@ class EncDecCTCModel(nn.Module):
                 rs_plan = qsrs.StreamResamplePlan(plan, plans[key], int(channels))
             except ValueError as e:
                 raise ValueError(f'stream: input_rate {input_rate}: {e}') from None
+        sspot = None
+        if spot is not None:
+            from qasr import spot as qspot, stream_spot as qss
+            if not isinstance(spot, qss.StreamSpot):
+                raise ValueError(f'stream: spot must be a qasr.stream_spot.StreamSpot, got {type(spot).__name__}')
+            if beam is not None:
+                raise ValueError('stream: spot= together with beam= is not built: keyword spotting runs in sessions of the greedy '
+                                 'decoder (with or without endpoint=)')
+            given, tg, tl, thr, span, _ = self._spot_args('stream: spot', spot.keywords, spot.labels, spot.threshold, spot.max_span_s, 1)
+            sspot = (spot, given, qss.StreamSpotPlan(plan, tg, tl, qspot.check_threshold(thr, 'stream: spot'), span))
         bplan = None
         if beam is not None:
             from qasr import stream_beam as qsb
@@ -853,11 +878,11 @@ class EncDecCTCModel(nn.Module):
                 eplan = qse.EndpointPlan.for_stream(plan, endpoint)
             except ValueError as e:
                 raise ValueError(f'stream: endpoint: {e}') from None
-        return StreamSession(self, int(max_streams), plan, bool(tail), rs_plan, beam, bplan, endpoint, eplan)
+        return StreamSession(self, int(max_streams), plan, bool(tail), rs_plan, beam, bplan, endpoint, eplan, sspot)
 
     @torch.no_grad()
     def decode_stream(self, input_signal, input_signal_length, chunk_s=0.96, left_s=4.0, right_s=0.96, session=None, input_rate=None,
-                      channels=1, beam=None, endpoint=None):
+                      channels=1, beam=None, endpoint=None, spot=None):
         """A batch of complete recordings played through a streaming session, all rows side by side in pushes of chunk_s
         seconds (what inference.py --stream_chunk_s does): List[qasr.ctc.Hypothesis], one per row - the hypotheses
         stream() gives for that audio, which do not depend on the size of the pushes.
@@ -872,27 +897,36 @@ class EncDecCTCModel(nn.Module):
         what close() returns there (a list per row with n_best > 1); with StreamBeam(endpoint=) the rows are the recordings'
         utterances, as with endpoint=.  endpoint=: the endpointing of stream(endpoint=); the
         rows are then lists of qasr.ctc.StreamUtterance, every utterance of the recording in order (utterances that were
-        waiting in a passed session's queue before the call are left there)."""
+        waiting in a passed session's queue before the call are left there).  spot=: the keyword spotting of stream(spot=); the
+        call then returns the pair (the rows as above, one list of qasr.ctc.KeywordHit per recording: its final hits in the
+        order of take_hits - sess.decoded_hits keeps them as StreamHits, with detected_s, until the next call); hits that were
+        waiting in a passed session's queue are left there."""
         ch = session.rs_plan.channels if session is not None and session.rs_plan is not None else int(channels)
         if input_signal.dim() != 2 or ch < 1 or input_signal.shape[1] % ch:
             raise ValueError(f'decode_stream: input_signal must be [B, S * channels], got {tuple(input_signal.shape)} for {channels} channels')
         B = input_signal.shape[0]
         lens = [min(int(n), input_signal.shape[1] // ch) for n in input_signal_length.tolist()]
         sess = session if session is not None else self.stream(max_streams=B, chunk_s=chunk_s, left_s=left_s, right_s=right_s, tail=False,
-                                                               input_rate=input_rate, channels=ch, beam=beam, endpoint=endpoint)
+                                                               input_rate=input_rate, channels=ch, beam=beam, endpoint=endpoint, spot=spot)
         try:
             waiting = sess.take_utterances() if sess.endpoint is not None else []
+            waiting_hits = sess.take_hits() if sess.spot is not None else []
             slots = [sess.open() for _ in range(B)]
             C = sess.plan.C if sess.rs_plan is None else sess.rs_plan.Ain     # about chunk_s of audio per push
             for off in range(0, max(lens + [0]), C):
                 live = [b for b in range(B) if off < lens[b]]
                 sess.push([slots[b] for b in live], input_signal[live, off * ch:(off + C) * ch], [min(C, lens[b] - off) for b in live])
             hyps = [sess.close(s) for s in slots]
-            if sess.endpoint is None:
+            if sess.endpoint is not None:
+                utts = sess.take_utterances()
+                sess._utts = waiting
+                hyps = [[u for u in utts if u.slot == s] for s in slots]
+            if sess.spot is None:
                 return hyps
-            utts = sess.take_utterances()
-            sess._utts = waiting
-            return [[u for u in utts if u.slot == s] for s in slots]
+            hits = sess.take_hits()
+            sess._hits = waiting_hits
+            sess.decoded_hits = [[h for h in hits if h.slot == s] for s in slots]      # the same with their detection times
+            return hyps, [[h.hit for h in row] for row in sess.decoded_hits]
         finally:
             if session is None:
                 sess.close_all()
@@ -1575,8 +1609,13 @@ class StreamSession:
     """EncDecCTCModel.stream(): the live streams of one model.  The host keeps counts it already has (samples per stream, the
     deltas read back so far); everything a step computes from lives on the device."""
 
-    def __init__(self, model, max_streams, plan, tail, rs_plan=None, beam=None, bplan=None, endpoint=None, eplan=None):
+    def __init__(self, model, max_streams, plan, tail, rs_plan=None, beam=None, bplan=None, endpoint=None, eplan=None, spot=None):
         self.model, self.S, self.plan, self.tail = model, max_streams, plan, tail
+        # keyword spotting across steps (STREAM_SPOT_RULES): the StreamSpot, the keywords as given and the StreamSpotPlan
+        self.spot, self._sp_given, self.splan = spot if spot is not None else (None, None, None)
+        self._hits = []                      # final StreamHits that take_hits() has not handed out yet
+        self._pending = {}                   # slot -> the KeywordHits that were open after the slot's last step
+        self.decoded_hits = []               # decode_stream(spot=): the last call's StreamHits per recording
         self.endpoint, self.eplan = endpoint, eplan      # qasr.stream_ep.Endpointing / EndpointPlan: utterance boundaries
         self._utts = []                      # finished StreamUtterances that take_utterances() has not handed out yet
         self.beam, self.bplan = beam, bplan  # qasr.stream_beam.StreamBeam / StreamBeamPlan: the beam search across steps
@@ -1595,7 +1634,7 @@ class StreamSession:
         if model.engine_ready():             # the calibrated model: one reservation for the session's lifetime
             self._saved = (model._reserve, getattr(model, '_reserve_logp', True))
             model.reserve(max_streams, plan.Wl / float(plan.sample_rate))
-            model._reserve_logp = beam is not None       # the beam search reads log-probabilities
+            model._reserve_logp = beam is not None or spot is not None       # the beam search and the spotter read log-probabilities
             self._own = True
 
     def __enter__(self):
@@ -1643,7 +1682,8 @@ class StreamSession:
         if not 0 <= slot < self.S or slot in self._open:
             raise ValueError(f'stream: slot {slot} is already open or outside 0 .. max_streams - 1 = {self.S - 1}')
         self._open[slot] = dict(received=0, begin=True, deltas=[], in_received=0, fmt=None, beam_begin=True, ep_begin=True,
-                                label_base=0, boost_set=bset)
+                                label_base=0, boost_set=bset, spot_begin=True)
+        self._pending.pop(slot, None)
         return slot
 
     # ---- the three steps, on the device or as the twins
@@ -1670,6 +1710,11 @@ class StreamSession:
             if self.endpoint is not None:
                 self._ep_state = qengine.stream_ep_state(self.S, device)
                 self._ep_out = qengine.stream_endpoint_buffers(self.S, self.eplan, device)
+            if self.spot is not None:        # the keywords: uploaded once, held here
+                self._sp_state = qengine.stream_spot_state(self.S, self.splan, device)
+                self._sp_out = qengine.stream_spot_buffers(self.S, self.splan, device)
+                self._sp_kw = qengine.stream_spot_keywords(self.splan, device)
+                self._sp_plane = None
             if self.beam is not None:
                 if self._sets is None:
                     self._bstate = qengine.stream_beam_state(self.S, self.bplan, device)
@@ -1689,6 +1734,9 @@ class StreamSession:
             if self.endpoint is not None:
                 from qasr import stream_ep as qse
                 self._ep_state = qse.EpState(self.S)
+            if self.spot is not None:
+                from qasr import stream_spot as qss
+                self._sp_state = qss.SpotState(self.S, self.splan)
             if self.beam is not None:
                 from qasr import stream_beam as qsb
                 self._bstate = qsb.StreamBeamState(self.S, self.bplan, check=False)
@@ -1838,9 +1886,51 @@ class StreamSession:
             raise RuntimeError(f'stream: endpoint step refused, status {o.status.tolist()} for slots {slots}')
         self._ep_rows = {s: o.records[b, :int(o.n_records[b])].copy() for b, s in enumerate(slots)}
 
+    def take_hits(self):
+        """(spot=) the keyword hits that closed since the last call as qasr.ctc.StreamHit, sorted by (detected_s, slot, start_s,
+        index); the queue is cleared"""
+        if self.spot is None:
+            raise ValueError('stream: take_hits needs a session opened with spot=')
+        from qasr import stream_spot as qss
+        out, self._hits = qss.sort_hits(self._hits), []
+        return out
+
+    def pending_hits(self, slot):
+        """(spot=) the hits that are open after the last step of `slot`, one qasr.ctc.KeywordHit per keyword at most: what the
+        stream shows now, before it is certain that nothing replaces it"""
+        if self.spot is None:
+            raise ValueError('stream: pending_hits needs a session opened with spot=')
+        return list(self._pending.get(int(slot), []))
+
+    def _spot(self, slots, end, sl, logp, enc, first, status, blank):
+        """(spot=) k_star (penalty 0) and the spot launch (or their twins) behind a step's emit; queues the hits that closed and
+        keeps the rows' open hits"""
+        from qasr import align as qalign, engine as qengine, stream as qstream, stream_spot as qss
+        B, K = len(slots), self.splan.K
+        flags = [(qstream.END if end else 0) | (qstream.BEGIN if self._open[s]['spot_begin'] else 0) for s in slots]
+        for s in slots:
+            self._open[s]['spot_begin'] = False
+        if self._dev.type == 'cuda':
+            Tw = logp.shape[1]
+            if self._sp_plane is None or self._sp_plane.shape[1] != Tw:
+                self._sp_plane = torch.empty(self.S, Tw, device=self._dev, dtype=torch.float32)
+            plane = qengine.ctc_star(logp, enc, 0.0, out=self._sp_plane[:B])
+            out = qss.SpotStepBatch(*[getattr(self._sp_out, n)[:B * K] for n in qss.FIELDS])
+            qengine.stream_spot(self._state, self._sp_state, self.S, self.plan, self.splan, sl, self._i32(flags), logp, plane, enc, first,
+                                status, blank, keywords=self._sp_kw, out=out)
+            o = qss.SpotStepBatch(*[getattr(out, n).cpu().numpy() for n in qss.FIELDS])
+        else:
+            o = qss.spot_batch_host(self._sp_state, self._state, slots, flags, logp, qalign.star_host(logp, enc, 0.0), enc, first, status,
+                                    blank)
+        if int(o.status.max()) != 0 or int(o.n_new_hits.max()) > o.hit_start.shape[1]:
+            raise RuntimeError(f'stream: spot step refused, status {o.status.tolist()} / hits {o.n_new_hits.tolist()} for slots {slots}')
+        final, pending = qss.to_stream_hits(o, slots, self._sp_given, self.plan.seconds_per_frame())
+        self._hits += final
+        self._pending.update(pending)
+
     def _step(self, slots, end):
-        """one step for `slots`: window -> forward -> emit (-> endpoint); returns the rows' deltas as qasr.stream.StepRow-like
-        tuples"""
+        """one step for `slots`: window -> forward -> emit (-> endpoint) (-> star -> spot); returns the rows' deltas as
+        qasr.stream.StepRow-like tuples"""
         from qasr import engine as qengine, stream as qstream
         m, plan, B = self.model, self.plan, len(slots)
         blank = len(m.decoder.vocabulary)
@@ -1849,9 +1939,15 @@ class StreamSession:
         if self._dev.type == 'cuda':
             sl, fl = self._i32(slots), self._i32(flags)
             win, wl, first = qengine.stream_window(self._state, self.S, plan, sl, out=tuple(t[:B] for t in self._win))
-            tok, fs, enc = m._forward(win, wl.long(), decode='frames')
-            tok = tok.to(torch.int32).contiguous()
-            fs = fs.float().contiguous()
+            if self.spot is not None:        # the spotter reads log-probabilities: the frame scores are gathered from them
+                logp, enc, tok = m._forward(win, wl.long())
+                logp = logp.float()
+                tok = tok.to(torch.int32).contiguous()
+                fs = m._frame_scores(logp, tok).contiguous()
+            else:
+                tok, fs, enc = m._forward(win, wl.long(), decode='frames')
+                tok = tok.to(torch.int32).contiguous()
+                fs = fs.float().contiguous()
             o = self._out
             fields = [f.name for f in dataclasses.fields(o)]
             out = qstream.StepBatch(*[None if getattr(o, n) is None else getattr(o, n)[:B] for n in fields])
@@ -1859,13 +1955,22 @@ class StreamSession:
             qengine.stream_emit(self._state, self.S, plan, sl, fl, tok, fs, enc, first, blank, out=out)
             if self.endpoint is not None:
                 self._endpoint(slots, end, sl, tok, fs, enc, first, out, blank)
+            if self.spot is not None:
+                self._spot(slots, end, sl, logp, enc, first, out.status, blank)
             o = qstream.StepBatch(*[None if getattr(out, n) is None else getattr(out, n).cpu().numpy() for n in fields])
         else:
             win, wl, first = qstream.window_host(self._state, slots)
-            tok, fs, enc = m._forward(torch.from_numpy(win), torch.from_numpy(wl).long(), decode='frames')
+            if self.spot is not None:
+                logp, enc, tok = m._forward(torch.from_numpy(win), torch.from_numpy(wl).long())
+                logp = logp.float()
+                fs = m._frame_scores(logp, tok)
+            else:
+                tok, fs, enc = m._forward(torch.from_numpy(win), torch.from_numpy(wl).long(), decode='frames')
             o = qstream.emit_batch_host(self._state, slots, flags, tok.numpy(), fs.float().numpy(), enc.numpy(), first, blank)
             if self.endpoint is not None:
                 self._endpoint(slots, end, None, tok.numpy(), fs.float().numpy(), enc.numpy(), first, o, blank)
+            if self.spot is not None:
+                self._spot(slots, end, None, logp.numpy(), enc.numpy(), first, o.status, blank)
             if not self.tail:
                 o.tail_labels = o.tail_n = None
         if int(o.status.max()) != 0:
@@ -2149,11 +2254,13 @@ class StreamSession:
                 return self._cut(slot, [qse._record(0, 0, 0, 0, 0, 0, qse.UTT_END, np.float32(0), 0)])
             finally:
                 self._open.pop(slot)
-        self._open.pop(slot)
         utt = 0.0
-        if st['received'] > 0:               # (a stream that never received a sample has nothing to run)
-            lab, start, nfr, sc, utt, _ = self._step([slot], True)[0]
-            st['deltas'].append((lab, start, nfr, sc))
+        try:
+            if st['received'] > 0:           # (a stream that never received a sample has nothing to run)
+                lab, start, nfr, sc, utt, _ = self._step([slot], True)[0]
+                st['deltas'].append((lab, start, nfr, sc))
+        finally:
+            self._open.pop(slot)
         cat = lambda i, dt: np.concatenate([d[i] for d in st['deltas']] + [np.zeros(0, dtype=dt)]).astype(dt)[None]
         lab = cat(0, np.int32)
         res = qctc.CtcResult(lab, np.array([lab.shape[1]], dtype=np.int32), cat(1, np.int32), cat(2, np.int32), cat(3, np.float32),

@@ -55,6 +55,16 @@ class KeywordHit:
 
 
 @dataclass
+class StreamHit:
+    """One final keyword hit of a streaming session (EncDecCTCModel.stream(spot=), qasr.stream_spot.STREAM_SPOT_RULES): the
+    stream's slot, the KeywordHit in seconds of the stream, and detected_s: the end of the final frame after which the hit
+    closed - the stream time at which it became certain that nothing can replace it."""
+    slot: int
+    hit: KeywordHit
+    detected_s: float
+
+
+@dataclass
 class StreamUpdate:
     """What one step of a streaming session (EncDecCTCModel.stream) made final for one stream: the labels whose runs closed,
     their text, start / end times in seconds of the stream and confidences (best frame log-probability of each run), and

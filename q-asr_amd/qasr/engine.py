@@ -28,6 +28,7 @@ SYMBOLS = ['qasr_blob_check', 'qasr_engine_create', 'qasr_engine_create_ex', 'qa
            'qasr_stream_rs_state_bytes', 'qasr_stream_rs_work_bytes', 'qasr_stream_rs_push',
            'qasr_stream_beam_state_bytes', 'qasr_stream_beam', 'qasr_stream_ep_state_bytes', 'qasr_stream_endpoint',
            'qasr_stream_beam_boost_state_bytes', 'qasr_stream_beam_boost', 'qasr_stream_beam_ep',
+           'qasr_stream_spot_state_bytes', 'qasr_stream_spot',
            'qasr_last_error', 'qasr_version']
 
 _lib = None
@@ -230,6 +231,10 @@ def load_library():
         lib.qasr_stream_endpoint.argtypes = [vp, C.POINTER(StreamEndpointArgs)]
     if hasattr(lib, 'qasr_stream_beam_ep'):     # (likewise)
         lib.qasr_stream_beam_ep.argtypes = [vp, C.POINTER(StreamBeamEpArgs)]
+    if hasattr(lib, 'qasr_stream_spot'):        # (likewise)
+        lib.qasr_stream_spot_state_bytes.argtypes = [i32, i32, i32]
+        lib.qasr_stream_spot_state_bytes.restype = sz
+        lib.qasr_stream_spot.argtypes = [vp, C.POINTER(StreamSpotArgs)]
     lib.qasr_debug_prof.argtypes = [vp]
     lib.qasr_debug_timeline.argtypes = [vp, sz]
     lib.qasr_sep_layer.argtypes = [vp, C.POINTER(SepLayerArgs), C.c_char_p, sz]
@@ -1806,6 +1811,93 @@ def stream_endpoint(state, ep_state, S, plan, eplan, slots, flags, tokens, frame
     a.records, a.n_records, a.status = out.records.data_ptr(), out.n_records.data_ptr(), out.status.data_ptr()
     with torch.cuda.device(dev):
         _check(lib.qasr_stream_endpoint(_stream_ptr(stream), C.byref(a)), 'qasr_stream_endpoint')
+    return out
+
+
+class StreamSpotArgs(C.Structure):
+    """qasr_stream_spot_args (include/qasr.h)"""
+    _fields_ = ([('struct_size', C.c_uint32)] +
+                [(n, C.c_int32) for n in ('S', 'B', 'Wl', 'C', 'Rr', 'samples_per_frame', 'Tw', 'n_classes', 'K', 'max_labels', 'blank',
+                                          'threshold_q', 'max_span', 'PH', 'max_final_frames')] +
+                [('pitch_utt', C.c_int64), ('pitch_frame', C.c_int64), ('log_probs', C.c_void_p), ('star_logp', C.c_void_p),
+                 ('star_pitch', C.c_int64), ('state', C.c_void_p), ('state_bytes', C.c_size_t), ('spot_state', C.c_void_p),
+                 ('spot_state_bytes', C.c_size_t)] +
+                [(n, C.c_void_p) for n in ('slots', 'flags', 'enc_lens', 'first_frame', 'emit_status', 'targets', 'target_lens',
+                                           'hit_start', 'hit_end', 'hit_detect', 'hit_score', 'n_new_hits', 'n_hits_total',
+                                           'open_start', 'open_end', 'open_score', 'ok', 'status')])
+
+
+def stream_spot_state(S, splan, device):
+    """Zeroed spot state of S fresh streams: an int32 tensor [S, K, 8 + 3 SP] as qasr.stream_spot.SpotState.block, of
+    qasr_stream_spot_state_bytes(S, K, max_labels) bytes."""
+    n = int(load_library().qasr_stream_spot_state_bytes(int(S), splan.K, splan.ML))
+    if n == 0 or n != int(S) * splan.K * splan.block_words * 4:
+        raise ValueError(f'stream_spot_state: S {S}, K {splan.K} or max_labels {splan.ML} out of range')
+    return torch.zeros(n // 4, device=device, dtype=torch.int32).view(int(S), splan.K, splan.block_words)
+
+
+def stream_spot_keywords(splan, device):
+    """the keyword arrays of a session on the device, uploaded once: (targets int32 [K, ML], target_lens int32 [K])"""
+    return (torch.from_numpy(splan.targets).to(device).contiguous(), torch.from_numpy(splan.target_lens).to(device).contiguous())
+
+
+def stream_spot_buffers(B, splan, device, PH=None):
+    """k_stream_spot's outputs as a qasr.stream_spot.SpotStepBatch of cuda tensors"""
+    from . import stream_spot as qs
+    PH = splan.hit_pitch if PH is None else int(PH)
+    P = int(B) * splan.K
+    t = lambda dt, *s: torch.empty(*s, device=device, dtype=dt)
+    i32, i64 = torch.int32, torch.int64
+    return qs.SpotStepBatch(t(i32, P, PH), t(i32, P, PH), t(i32, P, PH), t(i64, P, PH), t(i32, P), t(i32, P), t(i32, P), t(i32, P),
+                            t(i64, P), t(i32, P), t(i32, P))
+
+
+def stream_spot(state, spot_state, S, plan, splan, slots, flags, log_probs, star, enc_lens, first_frame, emit_status, blank,
+                keywords=None, out=None, stream=None):
+    """qasr_stream_spot: streaming keyword spotting over one step's final frames, AFTER stream_emit of the same rows gave
+    emit_status; log_probs: a cuda float32 tensor [B, Tw, C] (any row / frame pitch, classes contiguous), star: the cuda float32
+    plane [B, Tw] of ctc_star(log_probs, enc_lens, 0.0); enc_lens / first_frame / slots / flags / emit_status cuda int32 [B];
+    state: the stream state (read-only), spot_state: stream_spot_state; keywords: stream_spot_keywords (uploaded here when
+    None) -> a qasr.stream_spot.SpotStepBatch of cuda tensors.  k_stream_spot, one launch, nothing read back; equal to
+    qasr.stream_spot.spot_batch_host byte for byte, the spot state included."""
+    from . import stream_spot as qs
+    lib = load_library()
+    dev = state.device
+    assert log_probs.is_cuda and log_probs.dim() == 3 and log_probs.dtype == torch.float32, \
+        'stream_spot: log_probs must be a cuda float32 tensor [B, Tw, C]'
+    lp = log_probs if log_probs.stride(2) == 1 or log_probs.shape[2] == 1 else log_probs.contiguous()
+    B, Tw, Cn = lp.shape
+    for t, w in ((slots, 'slots'), (flags, 'flags'), (enc_lens, 'enc_lens'), (first_frame, 'first_frame'), (emit_status, 'emit_status')):
+        _i32dev(t, B, 'stream_spot: ' + w)
+    assert spot_state.is_cuda and spot_state.dtype == torch.int32 and spot_state.is_contiguous(), 'stream_spot: spot_state'
+    tg, tl = stream_spot_keywords(splan, dev) if keywords is None else keywords
+    assert tg.is_cuda and tg.dtype == torch.int32 and tg.is_contiguous() and tuple(tg.shape) == (splan.K, splan.ML), 'stream_spot: targets'
+    _i32dev(tl, splan.K, 'stream_spot: target_lens')
+    if out is None:
+        out = stream_spot_buffers(B, splan, dev)
+    P, PH = B * splan.K, out.hit_start.shape[1]
+    for n in qs.FIELDS:
+        t = getattr(out, n)
+        dt = torch.int64 if n in qs.FIELD_DTYPES else torch.int32
+        shape = (P, PH) if n.startswith('hit_') else (P,)
+        assert t.is_cuda and t.is_contiguous() and t.dtype == dt and tuple(t.shape) == shape, f'stream_spot: out.{n}'
+    st, spitch = _star_arg(star, B, Tw, dev, 'stream_spot')
+    a = StreamSpotArgs()
+    a.struct_size = C.sizeof(StreamSpotArgs)
+    a.S, a.B, a.Wl, a.C, a.Rr, a.samples_per_frame, a.Tw = int(S), B, plan.Wl, plan.C, plan.Rr, plan.samples_per_frame, Tw
+    a.n_classes, a.K, a.max_labels, a.blank = Cn, splan.K, splan.ML, int(blank)
+    a.threshold_q, a.max_span, a.PH, a.max_final_frames = splan.threshold_q, splan.max_span, PH, splan.max_final_frames
+    a.pitch_utt, a.pitch_frame = (lp.stride(0) if B > 1 else max(lp.stride(0), Tw * lp.stride(1))), lp.stride(1)
+    a.log_probs, a.star_logp, a.star_pitch = lp.data_ptr(), st.data_ptr(), spitch
+    a.state, a.state_bytes = state.data_ptr(), state.numel() * state.element_size()
+    a.spot_state, a.spot_state_bytes = spot_state.data_ptr(), spot_state.numel() * spot_state.element_size()
+    a.slots, a.flags, a.enc_lens, a.first_frame = slots.data_ptr(), flags.data_ptr(), enc_lens.data_ptr(), first_frame.data_ptr()
+    a.emit_status, a.targets, a.target_lens = emit_status.data_ptr(), tg.data_ptr(), tl.data_ptr()
+    for n in qs.FIELDS:
+        setattr(a, n, getattr(out, n).data_ptr())
+    with torch.cuda.device(dev):
+        _check(lib.qasr_stream_spot(_stream_ptr(stream), C.byref(a)), 'qasr_stream_spot')
+    out._keep = (lp, st, tg, tl)
     return out
 
 
