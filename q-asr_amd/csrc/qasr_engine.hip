@@ -1313,7 +1313,9 @@ int qasr_ctc_beam_boost(void* stream, const qasr_ctc_beam_boost_args* a) {
   return launched("ctc_beam_boost", launch_beam_boost((hipStream_t)stream, *a));
 }
 
-// ---- the checks the CTC lattice entry points below share, with the entry's name in the message; 0 or the error's code
+// ---- the checks the CTC lattice entry points below share, with the entry's name in the message; 0 or the error's code.  The
+// templates run over structs that hold the same fields but are distinct types (no casts); what one entry asks differently stays in it.
+extern "C++" {                                                               // (templates, as above)
 static int ctc_blank_check(const char* who, int blank, int C) {
   return blank < 0 || blank >= C ? fail(QASR_ERR_ARG, "%s: blank %d is outside [0, %d)", who, blank, C) : 0;
 }
@@ -1325,13 +1327,73 @@ static int ctc_pitch_check(const char* who, int T, int C, int64_t pitch_frame, i
 static int ctc_star_pitch_check(const char* who, int64_t star_pitch, int T) {
   return star_pitch < T ? fail(QASR_ERR_ARG, "%s: star_pitch %lld < T %d", who, (long long)star_pitch, T) : 0;
 }
-static int ctc_lae_check(const char* who, const void* lae_table, uint32_t lae_entries) {     // the posterior kernels: required
-  if (!lae_table || lae_entries != QASR_BEAM_TABLE_ENTRIES)
-    return fail(QASR_ERR_ARG, "%s: lae_table is required and lae_entries %u must be %d", who, lae_entries, QASR_BEAM_TABLE_ENTRIES);
+template <class A>
+static int ctc_workspace_plane_check(const char* who, const A* a, size_t need) {   // how the four alignment entries' checks end
+  if (a->workspace_bytes < need) return fail(QASR_ERR_ARG, "%s: workspace of %zu bytes, %zu needed", who, a->workspace_bytes, need);
+  return a->star_logp ? ctc_star_pitch_check(who, a->star_pitch, a->T) : 0;                // the plane is optional
+}
+static int ctc_max_labels_check(const char* who, int max_labels, int cap) {
+  return max_labels < 1 || max_labels > cap ? fail(QASR_ERR_ARG, "%s: max_labels %d is outside 1 .. %d", who, max_labels, cap) : 0;
+}
+template <class A>
+static int ctc_targets_check(const char* who, const A* a, int max_labels_cap) {   // of the four alignment entries
+  if (int rc = ctc_max_labels_check(who, a->max_labels, max_labels_cap)) return rc;
+  if (int rc = ctc_blank_check(who, a->blank, a->C)) return rc;
+  return ctc_pitch_check(who, a->T, a->C, a->pitch_frame, a->pitch_utt);
+}
+// ctc_align and ctc_align_band take their struct in two sizes: `full`, zeroed by the caller, receives what was given (the
+// shorter struct: no wildcard plane)
+template <class A>
+static int ctc_two_size_args(const char* who, const A* given, size_t v1_size, A* full) {
+  if (!given) return fail(QASR_ERR_ARG, "%s: args is NULL", who);
+  if (given->struct_size != sizeof(A) && given->struct_size != v1_size)
+    return fail(QASR_ERR_ARG, "%s: struct_size %u is neither %zu nor %zu", who, given->struct_size, sizeof(A), v1_size);
+  memcpy(full, given, given->struct_size);
   return 0;
 }
-static int ctc_workspace_check(const char* who, size_t have, size_t need) {
-  return have < need ? fail(QASR_ERR_ARG, "%s: workspace of %zu bytes, %zu needed", who, have, need) : 0;
+template <class A>
+static int ctc_five_ptrs_check(const char* who, const A* a) {
+  if (!a->log_probs || !a->targets || !a->target_lens || !a->workspace || !a->ok)
+    return fail(QASR_ERR_ARG, "%s: log_probs, targets, target_lens, workspace and ok are required", who);
+  return 0;
+}
+template <class A>
+static int ctc_problems_check(const char* who, const A* a) {         // ctc_align and ctc_post: K problems per utterance, their rows
+  if (a->B < 1 || a->T < 1 || a->T > QASR_BEAM_MAX_FRAMES || a->C < 1 || a->K < 1)
+    return fail(QASR_ERR_ARG, "%s: B %d, T %d (1 .. %d), C %d or K %d out of range", who, a->B, a->T, QASR_BEAM_MAX_FRAMES, a->C, a->K);
+  if ((long long)a->P != (long long)a->B * a->K) return fail(QASR_ERR_ARG, "%s: P %d is not B %d * K %d", who, a->P, a->B, a->K);
+  return ctc_targets_check(who, a, QASR_ALIGN_MAX_LABELS);
+}
+static bool band_states_ok(int band_states) { return band_states == 256 || band_states == 1024 || band_states == 4352; }
+template <class A>
+static int ctc_band_check(const char* who, const A* a) {             // the banded entries: one problem per recording, its rows
+  if (!band_states_ok(a->band_states)) return fail(QASR_ERR_ARG, "%s: band_states %d is not 256, 1024 or 4352", who, a->band_states);
+  if (a->B < 1 || a->T < 1 || a->T > QASR_BAND_MAX_FRAMES || a->C < 1)
+    return fail(QASR_ERR_ARG, "%s: B %d, T %d (1 .. %d) or C %d out of range", who, a->B, a->T, QASR_BAND_MAX_FRAMES, a->C);
+  return ctc_targets_check(who, a, QASR_BAND_MAX_LABELS);
+}
+template <class A>
+static int ctc_post_tail_check(const char* who, const A* a, size_t need) {   // the posterior entries: table (required) .. plane
+  if (!a->lae_table || a->lae_entries != QASR_BEAM_TABLE_ENTRIES)
+    return fail(QASR_ERR_ARG, "%s: lae_table is required and lae_entries %u must be %d", who, a->lae_entries, QASR_BEAM_TABLE_ENTRIES);
+  if (a->post_pitch < a->T) return fail(QASR_ERR_ARG, "%s: post_pitch %lld < T %d", who, (long long)a->post_pitch, a->T);
+  if (((uintptr_t)a->workspace & 7) != 0) return fail(QASR_ERR_ARG, "%s: workspace is not 8-byte aligned", who);
+  return ctc_workspace_plane_check(who, a, need);
+}
+// what ctc_spot and stream_spot ask of the keywords and of the planes they run over: T frames (the window's Tw) of C classes
+template <class A>
+static int spot_keywords_check(const char* who, const A* a, int T, int C) {
+  if ((long long)a->B * a->K > INT_MAX) return fail(QASR_ERR_ARG, "%s: B %d * K %d is above 2^31 - 1", who, a->B, a->K);
+  if (int rc = ctc_max_labels_check(who, a->max_labels, QASR_SPOT_MAX_LABELS)) return rc;
+  if (int rc = ctc_blank_check(who, a->blank, C)) return rc;
+  if (int rc = ctc_star_pitch_check(who, a->star_pitch, T)) return rc;
+  if (int rc = ctc_pitch_check(who, T, C, a->pitch_frame, a->pitch_utt)) return rc;
+  if (a->threshold_q < QASR_SPOT_MIN_THRESHOLD_Q || a->threshold_q > 0)
+    return fail(QASR_ERR_ARG, "%s: threshold_q %d is outside %d .. 0", who, a->threshold_q, QASR_SPOT_MIN_THRESHOLD_Q);
+  if (a->max_span < 1 || a->max_span > QASR_SPOT_MAX_SPAN)
+    return fail(QASR_ERR_ARG, "%s: max_span %d is outside 1 .. %d", who, a->max_span, QASR_SPOT_MAX_SPAN);
+  return 0;
+}
 }
 
 // ---- CTC forced alignment (k_align, qasr_align.hip): the checks of include/qasr.h, then one launch
@@ -1344,30 +1406,17 @@ size_t qasr_ctc_align_workspace_bytes(int P, int T, int max_labels) {
 }
 
 int qasr_ctc_align(void* stream, const qasr_ctc_align_args* given) {
-  if (!given) return fail(QASR_ERR_ARG, "ctc_align: args is NULL");
-  if (given->struct_size != sizeof(qasr_ctc_align_args) && given->struct_size != QASR_CTC_ALIGN_ARGS_V1_SIZE)
-    return fail(QASR_ERR_ARG, "ctc_align: struct_size %u is neither %zu nor %zu", given->struct_size, sizeof(qasr_ctc_align_args),
-                (size_t)QASR_CTC_ALIGN_ARGS_V1_SIZE);
-  qasr_ctc_align_args full{};                                      // the shorter struct: no wildcard plane
-  memcpy(&full, given, given->struct_size);
+  const char* const who = "ctc_align";
+  qasr_ctc_align_args full{};
   const qasr_ctc_align_args* const a = &full;
-  if (!a->log_probs || !a->targets || !a->target_lens || !a->workspace || !a->ok)
-    return fail(QASR_ERR_ARG, "ctc_align: log_probs, targets, target_lens, workspace and ok are required");
-  if (a->B < 1 || a->T < 1 || a->T > QASR_BEAM_MAX_FRAMES || a->C < 1 || a->K < 1)
-    return fail(QASR_ERR_ARG, "ctc_align: B %d, T %d (1 .. %d), C %d or K %d out of range", a->B, a->T, QASR_BEAM_MAX_FRAMES, a->C,
-                a->K);
-  if ((long long)a->P != (long long)a->B * a->K) return fail(QASR_ERR_ARG, "ctc_align: P %d is not B %d * K %d", a->P, a->B, a->K);
-  if (a->max_labels < 1 || a->max_labels > QASR_ALIGN_MAX_LABELS)
-    return fail(QASR_ERR_ARG, "ctc_align: max_labels %d is outside 1 .. %d", a->max_labels, QASR_ALIGN_MAX_LABELS);
-  if (int rc = ctc_blank_check("ctc_align", a->blank, a->C)) return rc;
-  if (int rc = ctc_pitch_check("ctc_align", a->T, a->C, a->pitch_frame, a->pitch_utt)) return rc;
-  if (a->total && !a->lae_table) return fail(QASR_ERR_ARG, "ctc_align: total needs lae_table");
+  if (int rc = ctc_two_size_args(who, given, QASR_CTC_ALIGN_ARGS_V1_SIZE, &full)) return rc;
+  if (int rc = ctc_five_ptrs_check(who, a)) return rc;
+  if (int rc = ctc_problems_check(who, a)) return rc;
+  if (a->total && !a->lae_table) return fail(QASR_ERR_ARG, "ctc_align: total needs lae_table");     // the table is optional here
   if (a->lae_table && a->lae_entries != QASR_BEAM_TABLE_ENTRIES)
     return fail(QASR_ERR_ARG, "ctc_align: lae_entries %u is not %d", a->lae_entries, QASR_BEAM_TABLE_ENTRIES);
-  if (int rc = ctc_workspace_check("ctc_align", a->workspace_bytes, align_workspace_bytes(a->P, a->T, a->max_labels))) return rc;
-  if (a->star_logp)
-    if (int rc = ctc_star_pitch_check("ctc_align", a->star_pitch, a->T)) return rc;
-  return launched("ctc_align", launch_align((hipStream_t)stream, *a));
+  if (int rc = ctc_workspace_plane_check(who, a, align_workspace_bytes(a->P, a->T, a->max_labels))) return rc;
+  return launched(who, launch_align((hipStream_t)stream, *a));
 }
 
 // ---- CTC posteriors along an alignment (k_post, qasr_post.hip): the checks of include/qasr.h, then one launch
@@ -1376,31 +1425,19 @@ size_t qasr_ctc_post_workspace_bytes(int P, int T) {
 }
 
 int qasr_ctc_post(void* stream, const qasr_ctc_post_args* a) {
-  if (int rc = args_check("ctc_post", a)) return rc;
-  if (!a->log_probs || !a->targets || !a->target_lens || !a->workspace || !a->ok)
-    return fail(QASR_ERR_ARG, "ctc_post: log_probs, targets, target_lens, workspace and ok are required");
+  const char* const who = "ctc_post";
+  if (int rc = args_check(who, a)) return rc;
+  if (int rc = ctc_five_ptrs_check(who, a)) return rc;
   if (!a->start || !a->nframes || !a->frame_post || !a->label_post)
     return fail(QASR_ERR_ARG, "ctc_post: start, nframes, frame_post and label_post are required");
-  if (a->B < 1 || a->T < 1 || a->T > QASR_BEAM_MAX_FRAMES || a->C < 1 || a->K < 1)
-    return fail(QASR_ERR_ARG, "ctc_post: B %d, T %d (1 .. %d), C %d or K %d out of range", a->B, a->T, QASR_BEAM_MAX_FRAMES, a->C,
-                a->K);
-  if ((long long)a->P != (long long)a->B * a->K) return fail(QASR_ERR_ARG, "ctc_post: P %d is not B %d * K %d", a->P, a->B, a->K);
-  if (a->max_labels < 1 || a->max_labels > QASR_ALIGN_MAX_LABELS)
-    return fail(QASR_ERR_ARG, "ctc_post: max_labels %d is outside 1 .. %d", a->max_labels, QASR_ALIGN_MAX_LABELS);
-  if (int rc = ctc_blank_check("ctc_post", a->blank, a->C)) return rc;
-  if (int rc = ctc_pitch_check("ctc_post", a->T, a->C, a->pitch_frame, a->pitch_utt)) return rc;
-  if (int rc = ctc_lae_check("ctc_post", a->lae_table, a->lae_entries)) return rc;
-  if (a->post_pitch < a->T) return fail(QASR_ERR_ARG, "ctc_post: post_pitch %lld < T %d", (long long)a->post_pitch, a->T);
-  if (((uintptr_t)a->workspace & 7) != 0) return fail(QASR_ERR_ARG, "ctc_post: workspace is not 8-byte aligned");
-  if (int rc = ctc_workspace_check("ctc_post", a->workspace_bytes, post_workspace_bytes(a->P, a->T))) return rc;
-  if (a->star_logp)
-    if (int rc = ctc_star_pitch_check("ctc_post", a->star_pitch, a->T)) return rc;
-  return launched("ctc_post", launch_post((hipStream_t)stream, *a));
+  if (int rc = ctc_problems_check(who, a)) return rc;
+  if (int rc = ctc_post_tail_check(who, a, post_workspace_bytes(a->P, a->T))) return rc;
+  return launched(who, launch_post((hipStream_t)stream, *a));
 }
 
 // ---- banded CTC alignment (k_align_band, qasr_align_band.hip): the checks of include/qasr.h, then one launch
 static int band_shape_ok(int B, int T, int band_states) {
-  return B >= 1 && T >= 1 && T <= QASR_BAND_MAX_FRAMES && (band_states == 256 || band_states == 1024 || band_states == 4352);
+  return B >= 1 && T >= 1 && T <= QASR_BAND_MAX_FRAMES && band_states_ok(band_states);
 }
 
 size_t qasr_ctc_align_band_workspace_bytes(int B, int T, int band_states) {
@@ -1408,28 +1445,15 @@ size_t qasr_ctc_align_band_workspace_bytes(int B, int T, int band_states) {
 }
 
 int qasr_ctc_align_band(void* stream, const qasr_ctc_align_band_args* given) {
-  if (!given) return fail(QASR_ERR_ARG, "ctc_align_band: args is NULL");
-  if (given->struct_size != sizeof(qasr_ctc_align_band_args) && given->struct_size != QASR_CTC_ALIGN_BAND_ARGS_V1_SIZE)
-    return fail(QASR_ERR_ARG, "ctc_align_band: struct_size %u is neither %zu nor %zu", given->struct_size,
-                sizeof(qasr_ctc_align_band_args), (size_t)QASR_CTC_ALIGN_BAND_ARGS_V1_SIZE);
-  qasr_ctc_align_band_args full{};                                 // the shorter struct: no wildcard plane
-  memcpy(&full, given, given->struct_size);
+  const char* const who = "ctc_align_band";
+  qasr_ctc_align_band_args full{};
   const qasr_ctc_align_band_args* const a = &full;
-  if (!a->log_probs || !a->targets || !a->target_lens || !a->workspace || !a->ok)
-    return fail(QASR_ERR_ARG, "ctc_align_band: log_probs, targets, target_lens, workspace and ok are required");
-  if (a->band_states != 256 && a->band_states != 1024 && a->band_states != 4352)
-    return fail(QASR_ERR_ARG, "ctc_align_band: band_states %d is not 256, 1024 or 4352", a->band_states);
-  if (a->B < 1 || a->T < 1 || a->T > QASR_BAND_MAX_FRAMES || a->C < 1)
-    return fail(QASR_ERR_ARG, "ctc_align_band: B %d, T %d (1 .. %d) or C %d out of range", a->B, a->T, QASR_BAND_MAX_FRAMES, a->C);
-  if (a->max_labels < 1 || a->max_labels > QASR_BAND_MAX_LABELS)
-    return fail(QASR_ERR_ARG, "ctc_align_band: max_labels %d is outside 1 .. %d", a->max_labels, QASR_BAND_MAX_LABELS);
-  if (int rc = ctc_blank_check("ctc_align_band", a->blank, a->C)) return rc;
-  if (int rc = ctc_pitch_check("ctc_align_band", a->T, a->C, a->pitch_frame, a->pitch_utt)) return rc;
+  if (int rc = ctc_two_size_args(who, given, QASR_CTC_ALIGN_BAND_ARGS_V1_SIZE, &full)) return rc;
+  if (int rc = ctc_five_ptrs_check(who, a)) return rc;
+  if (int rc = ctc_band_check(who, a)) return rc;
   if (((uintptr_t)a->workspace & 3) != 0) return fail(QASR_ERR_ARG, "ctc_align_band: workspace is not 4-byte aligned");
-  if (int rc = ctc_workspace_check("ctc_align_band", a->workspace_bytes, align_band_workspace_bytes(a->B, a->T, a->band_states))) return rc;
-  if (a->star_logp)
-    if (int rc = ctc_star_pitch_check("ctc_align_band", a->star_pitch, a->T)) return rc;
-  return launched("ctc_align_band", launch_align_band((hipStream_t)stream, *a));
+  if (int rc = ctc_workspace_plane_check(who, a, align_band_workspace_bytes(a->B, a->T, a->band_states))) return rc;
+  return launched(who, launch_align_band((hipStream_t)stream, *a));
 }
 
 // ---- CTC posteriors inside the band (k_post_band, qasr_post_band.hip): the checks of include/qasr.h, then one launch
@@ -1438,26 +1462,14 @@ size_t qasr_ctc_post_band_workspace_bytes(int B, int T) {
 }
 
 int qasr_ctc_post_band(void* stream, const qasr_ctc_post_band_args* a) {
-  if (int rc = args_check("ctc_post_band", a)) return rc;
-  if (!a->log_probs || !a->targets || !a->target_lens || !a->workspace || !a->ok)
-    return fail(QASR_ERR_ARG, "ctc_post_band: log_probs, targets, target_lens, workspace and ok are required");
+  const char* const who = "ctc_post_band";
+  if (int rc = args_check(who, a)) return rc;
+  if (int rc = ctc_five_ptrs_check(who, a)) return rc;
   if (!a->start || !a->nframes || !a->band_base || !a->frame_post || !a->label_post)
     return fail(QASR_ERR_ARG, "ctc_post_band: start, nframes, band_base, frame_post and label_post are required");
-  if (a->band_states != 256 && a->band_states != 1024 && a->band_states != 4352)
-    return fail(QASR_ERR_ARG, "ctc_post_band: band_states %d is not 256, 1024 or 4352", a->band_states);
-  if (a->B < 1 || a->T < 1 || a->T > QASR_BAND_MAX_FRAMES || a->C < 1)
-    return fail(QASR_ERR_ARG, "ctc_post_band: B %d, T %d (1 .. %d) or C %d out of range", a->B, a->T, QASR_BAND_MAX_FRAMES, a->C);
-  if (a->max_labels < 1 || a->max_labels > QASR_BAND_MAX_LABELS)
-    return fail(QASR_ERR_ARG, "ctc_post_band: max_labels %d is outside 1 .. %d", a->max_labels, QASR_BAND_MAX_LABELS);
-  if (int rc = ctc_blank_check("ctc_post_band", a->blank, a->C)) return rc;
-  if (int rc = ctc_pitch_check("ctc_post_band", a->T, a->C, a->pitch_frame, a->pitch_utt)) return rc;
-  if (int rc = ctc_lae_check("ctc_post_band", a->lae_table, a->lae_entries)) return rc;
-  if (a->post_pitch < a->T) return fail(QASR_ERR_ARG, "ctc_post_band: post_pitch %lld < T %d", (long long)a->post_pitch, a->T);
-  if (((uintptr_t)a->workspace & 7) != 0) return fail(QASR_ERR_ARG, "ctc_post_band: workspace is not 8-byte aligned");
-  if (int rc = ctc_workspace_check("ctc_post_band", a->workspace_bytes, post_band_workspace_bytes(a->B, a->T))) return rc;
-  if (a->star_logp)
-    if (int rc = ctc_star_pitch_check("ctc_post_band", a->star_pitch, a->T)) return rc;
-  return launched("ctc_post_band", launch_post_band((hipStream_t)stream, *a));
+  if (int rc = ctc_band_check(who, a)) return rc;
+  if (int rc = ctc_post_tail_check(who, a, post_band_workspace_bytes(a->B, a->T))) return rc;
+  return launched(who, launch_post_band((hipStream_t)stream, *a));
 }
 
 // ---- the wildcard's emission plane (k_star, qasr_star.hip): the checks of include/qasr.h, then one launch
@@ -1484,16 +1496,7 @@ int qasr_ctc_spot(void* stream, const qasr_ctc_spot_args* a) {
     return fail(QASR_ERR_ARG, "ctc_spot: hit_start, hit_end, hit_score, n_hits and ok are required");
   if (a->B < 1 || a->T < 1 || a->T > QASR_BAND_MAX_FRAMES || a->C < 1 || a->K < 1)
     return fail(QASR_ERR_ARG, "ctc_spot: B %d, T %d (1 .. %d), C %d or K %d out of range", a->B, a->T, QASR_BAND_MAX_FRAMES, a->C, a->K);
-  if ((long long)a->B * a->K > INT_MAX) return fail(QASR_ERR_ARG, "ctc_spot: B %d * K %d is above 2^31 - 1", a->B, a->K);
-  if (a->max_labels < 1 || a->max_labels > QASR_SPOT_MAX_LABELS)
-    return fail(QASR_ERR_ARG, "ctc_spot: max_labels %d is outside 1 .. %d", a->max_labels, QASR_SPOT_MAX_LABELS);
-  if (int rc = ctc_blank_check("ctc_spot", a->blank, a->C)) return rc;
-  if (int rc = ctc_star_pitch_check("ctc_spot", a->star_pitch, a->T)) return rc;
-  if (int rc = ctc_pitch_check("ctc_spot", a->T, a->C, a->pitch_frame, a->pitch_utt)) return rc;
-  if (a->threshold_q < QASR_SPOT_MIN_THRESHOLD_Q || a->threshold_q > 0)
-    return fail(QASR_ERR_ARG, "ctc_spot: threshold_q %d is outside %d .. 0", a->threshold_q, QASR_SPOT_MIN_THRESHOLD_Q);
-  if (a->max_span < 1 || a->max_span > QASR_SPOT_MAX_SPAN)
-    return fail(QASR_ERR_ARG, "ctc_spot: max_span %d is outside 1 .. %d", a->max_span, QASR_SPOT_MAX_SPAN);
+  if (int rc = spot_keywords_check("ctc_spot", a, a->T, a->C)) return rc;
   if (a->max_hits < 1) return fail(QASR_ERR_ARG, "ctc_spot: max_hits %d < 1", a->max_hits);
   if (!a->trace_score != !a->trace_start) return fail(QASR_ERR_ARG, "ctc_spot: trace_score and trace_start go together");
   if (a->trace_score && a->trace_pitch < a->T)
@@ -1809,8 +1812,8 @@ int qasr_stream_endpoint(void* stream, const qasr_stream_endpoint_args* a) {
   return launched("stream_endpoint", launch_stream_endpoint((hipStream_t)stream, *a));
 }
 
-// ---- streaming keyword spotting (k_stream_spot, qasr_stream_spot.hip): qasr_ctc_spot's checks of the keywords and the window's
-// planes (T = Tw), qasr_stream_emit's of the session's geometry, the spot state's, and one launch
+// ---- streaming keyword spotting (k_stream_spot, qasr_stream_spot.hip): qasr_stream_emit's checks of the session's geometry,
+// qasr_ctc_spot's of the keywords and the window's planes (spot_keywords_check with T = Tw), the spot state's, and one launch
 size_t qasr_stream_spot_state_bytes(int S, int K, int max_labels) { return stream_spot_state_bytes(S, K, max_labels); }
 
 int qasr_stream_spot(void* stream, const qasr_stream_spot_args* a) {
@@ -1825,16 +1828,7 @@ int qasr_stream_spot(void* stream, const qasr_stream_spot_args* a) {
   if (int rc = stream_geometry(who, a->S, a->B, a->Wl, a->C, a->Rr, a->samples_per_frame, a->state_bytes)) return rc;
   if (a->Tw < 1 || a->n_classes < 1 || a->K < 1)
     return fail(QASR_ERR_ARG, "stream_spot: Tw %d, n_classes %d and K %d must be at least 1", a->Tw, a->n_classes, a->K);
-  if ((long long)a->B * a->K > INT_MAX) return fail(QASR_ERR_ARG, "stream_spot: B %d * K %d is above 2^31 - 1", a->B, a->K);
-  if (a->max_labels < 1 || a->max_labels > QASR_SPOT_MAX_LABELS)
-    return fail(QASR_ERR_ARG, "stream_spot: max_labels %d is outside 1 .. %d", a->max_labels, QASR_SPOT_MAX_LABELS);
-  if (int rc = ctc_blank_check(who, a->blank, a->n_classes)) return rc;
-  if (int rc = ctc_star_pitch_check(who, a->star_pitch, a->Tw)) return rc;
-  if (int rc = ctc_pitch_check(who, a->Tw, a->n_classes, a->pitch_frame, a->pitch_utt)) return rc;
-  if (a->threshold_q < QASR_SPOT_MIN_THRESHOLD_Q || a->threshold_q > 0)
-    return fail(QASR_ERR_ARG, "stream_spot: threshold_q %d is outside %d .. 0", a->threshold_q, QASR_SPOT_MIN_THRESHOLD_Q);
-  if (a->max_span < 1 || a->max_span > QASR_SPOT_MAX_SPAN)
-    return fail(QASR_ERR_ARG, "stream_spot: max_span %d is outside 1 .. %d", a->max_span, QASR_SPOT_MAX_SPAN);
+  if (int rc = spot_keywords_check(who, a, a->Tw, a->n_classes)) return rc;
   if (a->PH < 1) return fail(QASR_ERR_ARG, "stream_spot: PH %d < 1", a->PH);
   if (a->max_final_frames < 1 || a->max_final_frames > a->Tw)
     return fail(QASR_ERR_ARG, "stream_spot: max_final_frames %d is outside 1 .. Tw = %d", a->max_final_frames, a->Tw);

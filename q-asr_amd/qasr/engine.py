@@ -577,32 +577,140 @@ class StarArgs(C.Structure):
                  ('penalty', C.c_float), ('reserved', C.c_uint32), ('star', C.c_void_p), ('star_pitch', C.c_int64)])
 
 
+def _row_pitch(t, T):
+    """the row pitch of a plane [rows, T] whose frames are contiguous (a single row: at least T)"""
+    return t.stride(0) if t.shape[0] > 1 else max(t.stride(0), T)
+
+
+def _lattice_logp(who, cls, log_probs, lens, dims='[B, T, C]', struct_size=None):
+    """What every CTC lattice binding opens with, under the call's name `who`: the library loaded, log_probs checked, it and lens
+    coerced and written with the two pitches into a fresh struct of type cls.  Returns (the struct, lp, ln, (B, T, C))."""
+    load_library()
+    assert log_probs.is_cuda and log_probs.dim() == 3 and log_probs.dtype == torch.float32, \
+        f'{who}: log_probs must be a cuda float32 tensor {dims}'
+    lp = log_probs if log_probs.stride(2) == 1 or log_probs.shape[2] == 1 else log_probs.contiguous()
+    B, T, _ = lp.shape
+    a = cls()
+    a.struct_size = C.sizeof(cls) if struct_size is None else struct_size
+    a.log_probs, a.pitch_utt, a.pitch_frame = lp.data_ptr(), (lp.stride(0) if B > 1 else max(lp.stride(0), T * lp.stride(1))), lp.stride(1)
+    ln = None
+    if lens is not None:
+        ln = lens.to(device=lp.device, dtype=torch.int32).contiguous()
+        a.lens = ln.data_ptr()
+    return a, lp, ln, tuple(lp.shape)
+
+
+def _lattice_targets(who, a, targets, target_lens, dev, rows='P'):
+    """targets / target_lens checked for their ranks, coerced and written into the struct; returns (tg, tl)"""
+    assert targets.dim() == 2 and target_lens.dim() == 1, f'{who}: targets must be [{rows}, max_labels], target_lens [{rows}]'
+    tg, tl = (t.to(device=dev, dtype=torch.int32).contiguous() for t in (targets, target_lens))
+    a.targets, a.target_lens = tg.data_ptr(), tl.data_ptr()
+    return tg, tl
+
+
+def _max_labels_error(who, cap, ML):
+    return ValueError(f'{who}: max_labels (the row pitch of targets) must be 1 .. {cap}, got {ML}')
+
+
+def _align_targets(who, a, targets, target_lens, dev):
+    """the targets of ctc_align and ctc_post: P rows of at most MAX_LABELS labels, P lengths"""
+    from .align import MAX_LABELS
+    tg, tl = _lattice_targets(who, a, targets, target_lens, dev)
+    P, ML = tg.shape
+    if ML > MAX_LABELS:                                             # refused here: the kernel holds at most this many labels
+        raise _max_labels_error(who, MAX_LABELS, ML)
+    if tl.shape[0] != P:
+        raise ValueError(f'{who}: {P} target rows but {tl.shape[0]} lengths')
+    return tg, tl
+
+
+def _band_targets(who, a, targets, target_lens, dev, P, T):
+    """the targets of ctc_align_band and ctc_post_band: one row and one length per recording, and the two limits of the band"""
+    from .align import BAND_MAX_FRAMES, BAND_MAX_LABELS
+    tg, tl = _lattice_targets(who, a, targets, target_lens, dev)
+    ML = tg.shape[1]
+    if tg.shape[0] != P or tl.shape[0] != P:
+        raise ValueError(f'{who}: {P} recordings but {tg.shape[0]} target rows and {tl.shape[0]} lengths')
+    if not 1 <= ML <= BAND_MAX_LABELS:
+        raise _max_labels_error(who, BAND_MAX_LABELS, ML)
+    if T > BAND_MAX_FRAMES:
+        raise ValueError(f'{who}: at most {BAND_MAX_FRAMES} frames, got {T}')
+    return tg, tl
+
+
+def _set_outputs(who, a, out, table):
+    """Each (name, dtype, shape, optional) of the table: out.<name> is a contiguous cuda tensor of that dtype and shape, or None
+    where optional; its pointer goes into the struct's field of the same name."""
+    for n, dt, shape, optional in table:
+        t = getattr(out, n)
+        assert optional if t is None else (t.is_cuda and t.is_contiguous() and t.dtype == dt and tuple(t.shape) == shape), f'{who}: out.{n}'
+        setattr(a, n, 0 if t is None else t.data_ptr())
+
+
+def _set_workspace(a, workspace, dev, query, *shape):
+    """the caller's workspace, or query(*shape) bytes allocated by torch here, into the struct; returns the tensor"""
+    if workspace is None:
+        workspace = torch.empty(max(query(*shape), 8), device=dev, dtype=torch.uint8)
+    a.workspace, a.workspace_bytes = workspace.data_ptr(), workspace.numel() * workspace.element_size()
+    return workspace
+
+
+def _set_star(who, a, star, B, T, dev):
+    """the wildcard's plane, a cuda float32 [B, T] whose frames are contiguous, into the struct; returns the tensor to keep alive"""
+    assert star.is_cuda and star.dtype == torch.float32 and tuple(star.shape) == (B, T), \
+        f'{who}: star must be a cuda float32 plane [{B}, {T}]'
+    st = star.to(dev) if T == 1 or star.stride(1) == 1 else star.contiguous()
+    a.star_logp, a.star_pitch = st.data_ptr(), _row_pitch(st, T)
+    return st
+
+
+def _set_post(who, a, result, result_name, ins, out, P, T, ML, dev):
+    """What ctc_post and ctc_post_band share behind their targets.  `ins`, (field, shape) rows: the alignment's outputs that the
+    kernel reads, checked, coerced and written (result.ok is the struct's ok_in); the PostResult, allocated here unless the caller
+    owns it, checked and written, frame_post with its row pitch; the table.  Returns (out, the coerced inputs, the table)."""
+    from .align import PostResult
+    from .beam import TAB_ENTRIES
+    i32 = dict(device=dev, dtype=torch.int32)
+    kept = []
+    for n, shape in ins:
+        t = getattr(result, n)
+        assert t is not None and tuple(t.shape) == shape, f'{who}: {result_name}.{n} must be {list(shape)}'
+        kept.append(t.to(**i32).contiguous())
+        setattr(a, 'ok_in' if n == 'ok' else n, kept[-1].data_ptr())
+    if out is None:
+        out = PostResult(frame_post=torch.empty(P, T, **i32), label_post=torch.empty(P, ML, **i32),
+                         total=torch.empty(P, device=dev, dtype=torch.int64), ok=torch.empty(P, **i32))
+    fp = out.frame_post
+    assert fp is not None and fp.is_cuda and fp.dtype == torch.int32 and tuple(fp.shape) == (P, T) and (T == 1 or fp.stride(1) == 1), \
+        f'{who}: out.frame_post'
+    _set_outputs(who, a, out, (('label_post', torch.int32, (P, ML), False), ('total', torch.int64, (P,), True), ('ok', torch.int32, (P,), False)))
+    a.frame_post, a.post_pitch = fp.data_ptr(), _row_pitch(fp, T)
+    tab = lae_table_device(dev)
+    a.lae_entries, a.lae_table = TAB_ENTRIES, tab.data_ptr()
+    return out, kept, tab
+
+
+def _lattice_launch(symbol, a, dev, stream, out, keep):
+    with torch.cuda.device(dev):
+        _check(getattr(load_library(), symbol)(_stream_ptr(stream), C.byref(a)), symbol)
+    out._keep = keep                                                # device memory the asynchronous launch reads
+    return out
+
+
 def ctc_star(log_probs, lens, penalty, out=None, stream=None):
     """qasr_ctc_star: the wildcard's emission plane on the device (k_star, one launch on the current stream, no host
     synchronisation); equal to qasr.align.star_host byte for byte.  log_probs: a cuda float32 tensor [B, T, C] (any utterance
     / frame pitch, classes contiguous); lens int32 [B] optional; penalty: nats per frame, finite, 0 .. 16 (refused by name
     otherwise).  Returns a cuda float32 tensor [B, T]; `out`: a caller-owned one (rows of any pitch >= T)."""
     from .align import check_star_penalty
-    lib = load_library()
-    assert log_probs.is_cuda and log_probs.dim() == 3 and log_probs.dtype == torch.float32, \
-        'ctc_star: log_probs must be a cuda float32 tensor [B, T, C]'
-    pen = check_star_penalty(penalty, 'ctc_star')
-    dev = log_probs.device
-    lp = log_probs if log_probs.stride(2) == 1 or log_probs.shape[2] == 1 else log_probs.contiguous()
-    ln = None if lens is None else lens.to(device=dev, dtype=torch.int32).contiguous()
-    B, T, Cn = lp.shape
+    a, lp, ln, (B, T, Cn) = _lattice_logp('ctc_star', StarArgs, log_probs, lens)
+    a.B, a.T, a.C, a.penalty = B, T, Cn, float(check_star_penalty(penalty, 'ctc_star'))
     if out is None:
-        out = torch.empty(B, T, device=dev, dtype=torch.float32)
+        out = torch.empty(B, T, device=lp.device, dtype=torch.float32)
     assert out.is_cuda and out.dtype == torch.float32 and tuple(out.shape) == (B, T) and (T == 1 or out.stride(1) == 1), 'ctc_star: out'
-    a = StarArgs()
-    a.struct_size = C.sizeof(StarArgs)
-    a.B, a.T, a.C = B, T, Cn
-    a.pitch_utt, a.pitch_frame = (lp.stride(0) if B > 1 else max(lp.stride(0), T * lp.stride(1))), lp.stride(1)
-    a.log_probs, a.lens = lp.data_ptr(), 0 if ln is None else ln.data_ptr()
-    a.penalty = float(pen)
-    a.star, a.star_pitch = out.data_ptr(), (out.stride(0) if B > 1 else max(out.stride(0), T))
-    with torch.cuda.device(dev):
-        _check(lib.qasr_ctc_star(_stream_ptr(stream), C.byref(a)), 'qasr_ctc_star')
+    a.star, a.star_pitch = out.data_ptr(), _row_pitch(out, T)
+    with torch.cuda.device(lp.device):
+        _check(load_library().qasr_ctc_star(_stream_ptr(stream), C.byref(a)), 'qasr_ctc_star')
     return out
 
 
@@ -626,71 +734,36 @@ def ctc_spot(log_probs, lens, star, targets, target_lens, blank, threshold, max_
     per frame, -16 .. 0; max_span: frames, 1 .. 65536; max_hits: hits stored per problem.  Returns a qasr.spot.SpotResult of
     cuda tensors (want_trace: with trace_score / trace_start [B * K, T]); `out`: a caller-owned one."""
     from .spot import MAX_LABELS, SpotResult, check_max_span, check_threshold
-    lib = load_library()
-    assert log_probs.is_cuda and log_probs.dim() == 3 and log_probs.dtype == torch.float32, \
-        'ctc_spot: log_probs must be a cuda float32 tensor [B, T, C]'
-    thr_q = check_threshold(threshold, 'ctc_spot')
-    span = check_max_span(max_span, 'ctc_spot')
-    MH = int(max_hits)
+    who, i32, i64 = 'ctc_spot', torch.int32, torch.int64
+    a, lp, ln, (B, T, Cn) = _lattice_logp(who, SpotArgs, log_probs, lens)
+    a.threshold_q, a.max_span, MH = check_threshold(threshold, who), check_max_span(max_span, who), int(max_hits)
     if MH < 1:
         raise ValueError(f'ctc_spot: max_hits must be at least 1, got {max_hits!r}')
-    dev = log_probs.device
-    lp = log_probs if log_probs.stride(2) == 1 or log_probs.shape[2] == 1 else log_probs.contiguous()
-    ln = None if lens is None else lens.to(device=dev, dtype=torch.int32).contiguous()
-    B, T, Cn = lp.shape
-    assert targets.dim() == 2 and target_lens.dim() == 1, 'ctc_spot: targets must be [K, max_labels], target_lens [K]'
-    tg = targets.to(device=dev, dtype=torch.int32).contiguous()
-    tl = target_lens.to(device=dev, dtype=torch.int32).contiguous()
+    dev = lp.device
+    tg, tl = _lattice_targets(who, a, targets, target_lens, dev, 'K')
     K, ML = tg.shape
     if not 1 <= ML <= MAX_LABELS:                                   # refused here: the kernel holds at most this many labels
-        raise ValueError(f'ctc_spot: max_labels (the row pitch of targets) must be 1 .. {MAX_LABELS}, got {ML}')
+        raise _max_labels_error(who, MAX_LABELS, ML)
     if tl.shape[0] != K or K < 1:
         raise ValueError(f'ctc_spot: {K} target rows but {tl.shape[0]} lengths')
     P = B * K
     if out is None:
-        i32 = dict(device=dev, dtype=torch.int32)
-        i64 = dict(device=dev, dtype=torch.int64)
-        out = SpotResult(torch.empty(P, MH, **i32), torch.empty(P, MH, **i32), torch.empty(P, MH, **i64), torch.empty(P, **i32),
-                         torch.empty(P, **i32), torch.empty(P, T, **i64) if want_trace else None,
-                         torch.empty(P, T, **i32) if want_trace else None, K)
-    for n, dt, shape in (('hit_start', torch.int32, (P, MH)), ('hit_end', torch.int32, (P, MH)), ('hit_score', torch.int64, (P, MH)),
-                         ('n_hits', torch.int32, (P,)), ('ok', torch.int32, (P,))):
-        t = getattr(out, n)
-        assert t is not None and t.is_cuda and t.is_contiguous() and t.dtype == dt and tuple(t.shape) == shape, f'ctc_spot: out.{n}'
+        new = lambda dt, *shape: torch.empty(*shape, device=dev, dtype=dt)
+        out = SpotResult(new(i32, P, MH), new(i32, P, MH), new(i64, P, MH), new(i32, P), new(i32, P),
+                         new(i64, P, T) if want_trace else None, new(i32, P, T) if want_trace else None, K)
+    _set_outputs(who, a, out, (('hit_start', i32, (P, MH), False), ('hit_end', i32, (P, MH), False), ('hit_score', i64, (P, MH), False),
+                               ('n_hits', i32, (P,), False), ('ok', i32, (P,), False)))
     assert (out.trace_score is None) == (out.trace_start is None), 'ctc_spot: out.trace_score and out.trace_start go together'
-    tpitch = 0
-    if out.trace_score is not None:
+    if out.trace_score is not None:                                 # the two planes: rows of any one pitch >= T
         ts, tb = out.trace_score, out.trace_start
-        assert ts.is_cuda and ts.dtype == torch.int64 and tuple(ts.shape) == (P, T) and (T == 1 or ts.stride(1) == 1), 'ctc_spot: out.trace_score'
-        assert tb.is_cuda and tb.dtype == torch.int32 and tuple(tb.shape) == (P, T) and (T == 1 or tb.stride(1) == 1), 'ctc_spot: out.trace_start'
-        tpitch = ts.stride(0) if P > 1 else max(ts.stride(0), T)
-        assert P == 1 or tb.stride(0) == tpitch, 'ctc_spot: the two trace planes must share one row pitch'
+        assert ts.is_cuda and ts.dtype == i64 and tuple(ts.shape) == (P, T) and (T == 1 or ts.stride(1) == 1), 'ctc_spot: out.trace_score'
+        assert tb.is_cuda and tb.dtype == i32 and tuple(tb.shape) == (P, T) and (T == 1 or tb.stride(1) == 1), 'ctc_spot: out.trace_start'
+        a.trace_score, a.trace_start, a.trace_pitch = ts.data_ptr(), tb.data_ptr(), _row_pitch(ts, T)
+        assert P == 1 or tb.stride(0) == a.trace_pitch, 'ctc_spot: the two trace planes must share one row pitch'
     out.n_keywords = K
-    st, spitch = _star_arg(star, B, T, dev, 'ctc_spot')
-    a = SpotArgs()
-    a.struct_size = C.sizeof(SpotArgs)
-    a.B, a.T, a.C, a.K, a.max_labels, a.blank = B, T, Cn, K, ML, int(blank)
-    a.threshold_q, a.max_span, a.max_hits = thr_q, span, MH
-    a.pitch_utt, a.pitch_frame = (lp.stride(0) if B > 1 else max(lp.stride(0), T * lp.stride(1))), lp.stride(1)
-    a.log_probs, a.lens = lp.data_ptr(), 0 if ln is None else ln.data_ptr()
-    a.star_logp, a.star_pitch = st.data_ptr(), spitch
-    a.targets, a.target_lens = tg.data_ptr(), tl.data_ptr()
-    for n in ('hit_start', 'hit_end', 'hit_score', 'n_hits', 'ok', 'trace_score', 'trace_start'):
-        t = getattr(out, n)
-        setattr(a, n, 0 if t is None else t.data_ptr())
-    a.trace_pitch = tpitch
-    with torch.cuda.device(dev):
-        _check(lib.qasr_ctc_spot(_stream_ptr(stream), C.byref(a)), 'qasr_ctc_spot')
-    out._keep = (lp, ln, st, tg, tl)
-    return out
-
-
-def _star_arg(star, B, T, dev, who):
-    """the wildcard's plane as (tensor, pitch): a cuda float32 [B, T] whose frames are contiguous"""
-    assert star.is_cuda and star.dtype == torch.float32 and tuple(star.shape) == (B, T), \
-        f'{who}: star must be a cuda float32 plane [{B}, {T}]'
-    st = star.to(dev) if T == 1 or star.stride(1) == 1 else star.contiguous()
-    return st, (st.stride(0) if B > 1 else max(st.stride(0), T))
+    st = _set_star(who, a, star, B, T, dev)
+    a.B, a.T, a.C, a.K, a.max_labels, a.blank, a.max_hits = B, T, Cn, K, ML, int(blank), MH
+    return _lattice_launch('qasr_ctc_spot', a, dev, stream, out, (lp, ln, st, tg, tl))
 
 
 def ctc_align_workspace_bytes(P, T, max_labels):
@@ -708,57 +781,28 @@ def ctc_align(log_probs, lens, targets, target_lens, blank, problems_per_utt=1, 
     torch here); `out`: a caller-owned AlignResult whose start / nframes / score / path_score / total may each be None.
     star: the wildcard's plane, a cuda float32 tensor [B, T] (ctc_star); with it the label id C is a valid target label
     (qasr.align.STAR_RULES) and k_align<., true> runs."""
-    from .align import AlignResult, MAX_LABELS
+    from .align import AlignResult
     from .beam import TAB_ENTRIES
-    lib = load_library()
-    assert log_probs.is_cuda and log_probs.dim() == 3 and log_probs.dtype == torch.float32, \
-        'ctc_align: log_probs must be a cuda float32 tensor [B, T, C]'
-    dev = log_probs.device
-    lp = log_probs if log_probs.stride(2) == 1 or log_probs.shape[2] == 1 else log_probs.contiguous()
-    ln = None if lens is None else lens.to(device=dev, dtype=torch.int32).contiguous()
-    B, T, Cn = lp.shape
-    K = int(problems_per_utt)
-    assert targets.dim() == 2 and target_lens.dim() == 1, 'ctc_align: targets must be [P, max_labels], target_lens [P]'
-    tg = targets.to(device=dev, dtype=torch.int32).contiguous()
-    tl = target_lens.to(device=dev, dtype=torch.int32).contiguous()
+    who, i32, i64 = 'ctc_align', torch.int32, torch.int64
+    v1 = None if star is not None else AlignArgs.star_logp.offset   # no plane: the shorter struct, the call every build takes
+    a, lp, ln, (B, T, Cn) = _lattice_logp(who, AlignArgs, log_probs, lens, struct_size=v1)
+    dev, K = lp.device, int(problems_per_utt)
+    tg, tl = _align_targets(who, a, targets, target_lens, dev)
     P, ML = tg.shape
-    if ML > MAX_LABELS:                                             # refused here: the kernel holds at most this many labels
-        raise ValueError(f'ctc_align: max_labels (the row pitch of targets) must be 1 .. {MAX_LABELS}, got {ML}')
-    if tl.shape[0] != P:
-        raise ValueError(f'ctc_align: {P} target rows but {tl.shape[0]} lengths')
     if out is None:
-        i32 = dict(device=dev, dtype=torch.int32)
-        out = AlignResult(labels=tg, n_labels=tl, start=torch.empty(P, ML, **i32), nframes=torch.empty(P, ML, **i32),
-                          score=torch.empty(P, ML, device=dev, dtype=torch.float32),
-                          path_score=torch.empty(P, device=dev, dtype=torch.int64),
-                          total=torch.empty(P, device=dev, dtype=torch.int64) if want_total else None,
-                          ok=torch.empty(P, **i32), blank=int(blank), problems_per_utt=K)
-    for n, dt, shape in (('start', torch.int32, (P, ML)), ('nframes', torch.int32, (P, ML)), ('score', torch.float32, (P, ML)),
-                         ('path_score', torch.int64, (P,)), ('total', torch.int64, (P,)), ('ok', torch.int32, (P,))):
-        t = getattr(out, n)
-        assert t is None or (t.is_cuda and t.is_contiguous() and t.dtype == dt and tuple(t.shape) == shape), f'ctc_align: out.{n}'
+        new = lambda dt, *shape: torch.empty(*shape, device=dev, dtype=dt)
+        out = AlignResult(labels=tg, n_labels=tl, start=new(i32, P, ML), nframes=new(i32, P, ML), score=new(torch.float32, P, ML),
+                          path_score=new(i64, P), total=new(i64, P) if want_total else None, ok=new(i32, P), blank=int(blank),
+                          problems_per_utt=K)
+    _set_outputs(who, a, out, (('start', i32, (P, ML), True), ('nframes', i32, (P, ML), True), ('score', torch.float32, (P, ML), True),
+                               ('path_score', i64, (P,), True), ('total', i64, (P,), True), ('ok', i32, (P,), True)))
     assert out.ok is not None, 'ctc_align: out.ok is required'
-    if workspace is None:
-        workspace = torch.empty(max(ctc_align_workspace_bytes(P, T, ML), 8), device=dev, dtype=torch.uint8)
-    tab = lae_table_device(dev) if out.total is not None else None
-    a = AlignArgs()
-    a.struct_size = C.sizeof(AlignArgs) if star is not None else AlignArgs.star_logp.offset   # no plane: the call every build takes
-    a.B, a.T, a.C, a.P, a.K, a.blank, a.max_labels = B, T, Cn, P, K, int(blank), ML
-    a.pitch_utt, a.pitch_frame = (lp.stride(0) if B > 1 else max(lp.stride(0), T * lp.stride(1))), lp.stride(1)
-    a.log_probs, a.lens, a.targets, a.target_lens = lp.data_ptr(), 0 if ln is None else ln.data_ptr(), tg.data_ptr(), tl.data_ptr()
+    workspace = _set_workspace(a, workspace, dev, ctc_align_workspace_bytes, P, T, ML)
+    tab = lae_table_device(dev) if out.total is not None else None  # the table is needed for total only
     a.lae_entries, a.lae_table = TAB_ENTRIES, 0 if tab is None else tab.data_ptr()
-    a.workspace, a.workspace_bytes = workspace.data_ptr(), workspace.numel() * workspace.element_size()
-    for n in ('start', 'nframes', 'score', 'path_score', 'total', 'ok'):
-        t = getattr(out, n)
-        setattr(a, n, 0 if t is None else t.data_ptr())
-    st = None
-    if star is not None:
-        st, a.star_pitch = _star_arg(star, B, T, dev, 'ctc_align')
-        a.star_logp = st.data_ptr()
-    with torch.cuda.device(dev):
-        _check(lib.qasr_ctc_align(_stream_ptr(stream), C.byref(a)), 'qasr_ctc_align')
-    out._keep = (lp, ln, tg, tl, workspace, tab, st)
-    return out
+    a.B, a.T, a.C, a.P, a.K, a.blank, a.max_labels = B, T, Cn, P, K, int(blank), ML
+    st = None if star is None else _set_star(who, a, star, B, T, dev)
+    return _lattice_launch('qasr_ctc_align', a, dev, stream, out, (lp, ln, tg, tl, workspace, tab, st))
 
 
 class PostArgs(C.Structure):
@@ -786,61 +830,17 @@ def ctc_post(log_probs, lens, targets, target_lens, blank, align_result, problem
     [P, max_labels], total int64 [P], ok int32 [P].  workspace: a caller-owned uint8 tensor of ctc_post_workspace_bytes(P, T)
     bytes, 8-byte aligned (None: allocated by torch here); `out`: a caller-owned PostResult whose total may be None and whose
     frame_post rows may have any pitch >= T."""
-    from .align import MAX_LABELS, PostResult
-    from .beam import TAB_ENTRIES
-    lib = load_library()
-    assert log_probs.is_cuda and log_probs.dim() == 3 and log_probs.dtype == torch.float32, \
-        'ctc_post: log_probs must be a cuda float32 tensor [B, T, C]'
-    dev = log_probs.device
-    lp = log_probs if log_probs.stride(2) == 1 or log_probs.shape[2] == 1 else log_probs.contiguous()
-    ln = None if lens is None else lens.to(device=dev, dtype=torch.int32).contiguous()
-    B, T, Cn = lp.shape
-    K = int(problems_per_utt)
-    assert targets.dim() == 2 and target_lens.dim() == 1, 'ctc_post: targets must be [P, max_labels], target_lens [P]'
-    tg = targets.to(device=dev, dtype=torch.int32).contiguous()
-    tl = target_lens.to(device=dev, dtype=torch.int32).contiguous()
+    who = 'ctc_post'
+    a, lp, ln, (B, T, Cn) = _lattice_logp(who, PostArgs, log_probs, lens)
+    dev = lp.device
+    tg, tl = _align_targets(who, a, targets, target_lens, dev)
     P, ML = tg.shape
-    if ML > MAX_LABELS:
-        raise ValueError(f'ctc_post: max_labels (the row pitch of targets) must be 1 .. {MAX_LABELS}, got {ML}')
-    if tl.shape[0] != P:
-        raise ValueError(f'ctc_post: {P} target rows but {tl.shape[0]} lengths')
-    i32 = dict(device=dev, dtype=torch.int32)
-    ins = []
-    for n, shape in (('start', (P, ML)), ('nframes', (P, ML)), ('ok', (P,))):
-        t = getattr(align_result, n)
-        assert t is not None and tuple(t.shape) == shape, f'ctc_post: align_result.{n} must be {list(shape)}'
-        ins.append(t.to(**i32).contiguous())
-    if out is None:
-        out = PostResult(frame_post=torch.empty(P, T, **i32), label_post=torch.empty(P, ML, **i32),
-                         total=torch.empty(P, device=dev, dtype=torch.int64), ok=torch.empty(P, **i32))
-    fp = out.frame_post
-    assert fp is not None and fp.is_cuda and fp.dtype == torch.int32 and tuple(fp.shape) == (P, T) and (T == 1 or fp.stride(1) == 1), \
-        'ctc_post: out.frame_post'
-    for n, dt, shape in (('label_post', torch.int32, (P, ML)), ('total', torch.int64, (P,)), ('ok', torch.int32, (P,))):
-        t = getattr(out, n)
-        assert (t is None and n == 'total') or (t is not None and t.is_cuda and t.is_contiguous() and t.dtype == dt and
-                                                tuple(t.shape) == shape), f'ctc_post: out.{n}'
-    if workspace is None:
-        workspace = torch.empty(max(ctc_post_workspace_bytes(P, T), 8), device=dev, dtype=torch.uint8)
-    tab = lae_table_device(dev)
-    a = PostArgs()
-    a.struct_size = C.sizeof(PostArgs)
-    a.B, a.T, a.C, a.P, a.K, a.blank, a.max_labels = B, T, Cn, P, K, int(blank), ML
-    a.pitch_utt, a.pitch_frame = (lp.stride(0) if B > 1 else max(lp.stride(0), T * lp.stride(1))), lp.stride(1)
-    a.log_probs, a.lens, a.targets, a.target_lens = lp.data_ptr(), 0 if ln is None else ln.data_ptr(), tg.data_ptr(), tl.data_ptr()
-    a.lae_entries, a.lae_table = TAB_ENTRIES, tab.data_ptr()
-    a.start, a.nframes, a.ok_in = (t.data_ptr() for t in ins)
-    a.workspace, a.workspace_bytes = workspace.data_ptr(), workspace.numel() * workspace.element_size()
-    a.frame_post, a.post_pitch = fp.data_ptr(), (fp.stride(0) if P > 1 else max(fp.stride(0), T))
-    a.label_post, a.total, a.ok = out.label_post.data_ptr(), 0 if out.total is None else out.total.data_ptr(), out.ok.data_ptr()
-    st = None
-    if star is not None:
-        st, a.star_pitch = _star_arg(star, B, T, dev, 'ctc_post')
-        a.star_logp = st.data_ptr()
-    with torch.cuda.device(dev):
-        _check(lib.qasr_ctc_post(_stream_ptr(stream), C.byref(a)), 'qasr_ctc_post')
-    out._keep = (lp, ln, tg, tl, ins, workspace, tab, st)
-    return out
+    out, ins, tab = _set_post(who, a, align_result, 'align_result', (('start', (P, ML)), ('nframes', (P, ML)), ('ok', (P,))), out, P, T,
+                              ML, dev)
+    workspace = _set_workspace(a, workspace, dev, ctc_post_workspace_bytes, P, T)
+    a.B, a.T, a.C, a.P, a.K, a.blank, a.max_labels = B, T, Cn, P, int(problems_per_utt), int(blank), ML
+    st = None if star is None else _set_star(who, a, star, B, T, dev)
+    return _lattice_launch('qasr_ctc_post', a, dev, stream, out, (lp, ln, tg, tl, ins, workspace, tab, st))
 
 
 class AlignBandArgs(C.Structure):
@@ -867,60 +867,29 @@ def ctc_align_band(log_probs, lens, targets, target_lens, blank, band_states=Non
     uint8 tensor of ctc_align_band_workspace_bytes(P, T, band_states) bytes (None: allocated by torch here); `out`: a
     caller-owned BandResult whose start / nframes / score / path_score / frame_logp / band_base may each be None.
     star: the wildcard's plane, a cuda float32 tensor [P, T] (ctc_star), as in ctc_align."""
-    from .align import BAND_BLOCK, BAND_MAX_FRAMES, BAND_MAX_LABELS, BandResult, pick_band_states
-    lib = load_library()
-    assert log_probs.is_cuda and log_probs.dim() == 3 and log_probs.dtype == torch.float32, \
-        'ctc_align_band: log_probs must be a cuda float32 tensor [P, T, C]'
-    dev = log_probs.device
-    lp = log_probs if log_probs.stride(2) == 1 or log_probs.shape[2] == 1 else log_probs.contiguous()
-    ln = None if lens is None else lens.to(device=dev, dtype=torch.int32).contiguous()
-    P, T, Cn = lp.shape
-    assert targets.dim() == 2 and target_lens.dim() == 1, 'ctc_align_band: targets must be [P, max_labels], target_lens [P]'
-    tg = targets.to(device=dev, dtype=torch.int32).contiguous()
-    tl = target_lens.to(device=dev, dtype=torch.int32).contiguous()
+    from .align import BAND_BLOCK, BandResult, pick_band_states
+    who, i32, f32 = 'ctc_align_band', torch.int32, torch.float32
+    v1 = None if star is not None else AlignBandArgs.star_logp.offset   # (as ctc_align)
+    a, lp, ln, (P, T, Cn) = _lattice_logp(who, AlignBandArgs, log_probs, lens, '[P, T, C]', struct_size=v1)
+    dev = lp.device
+    tg, tl = _band_targets(who, a, targets, target_lens, dev, P, T)
     ML = tg.shape[1]
-    if tg.shape[0] != P or tl.shape[0] != P:
-        raise ValueError(f'ctc_align_band: {P} recordings but {tg.shape[0]} target rows and {tl.shape[0]} lengths')
-    if not 1 <= ML <= BAND_MAX_LABELS:
-        raise ValueError(f'ctc_align_band: max_labels (the row pitch of targets) must be 1 .. {BAND_MAX_LABELS}, got {ML}')
-    if T > BAND_MAX_FRAMES:
-        raise ValueError(f'ctc_align_band: at most {BAND_MAX_FRAMES} frames, got {T}')
     BW = pick_band_states(ML, band_states)
     NB = (T + BAND_BLOCK - 1) // BAND_BLOCK
     if out is None:
-        i32 = dict(device=dev, dtype=torch.int32)
-        out = BandResult(labels=tg, n_labels=tl, start=torch.empty(P, ML, **i32), nframes=torch.empty(P, ML, **i32),
-                         score=torch.empty(P, ML, device=dev, dtype=torch.float32),
-                         path_score=torch.empty(P, device=dev, dtype=torch.int64), total=None, ok=torch.empty(P, **i32),
-                         blank=int(blank), problems_per_utt=1, frame_logp=torch.empty(P, T, device=dev, dtype=torch.float32),
-                         band_base=torch.empty(P, NB, **i32) if want_band_base else None)
+        new = lambda dt, *shape: torch.empty(*shape, device=dev, dtype=dt)
+        out = BandResult(labels=tg, n_labels=tl, start=new(i32, P, ML), nframes=new(i32, P, ML), score=new(f32, P, ML),
+                         path_score=new(torch.int64, P), total=None, ok=new(i32, P), blank=int(blank), problems_per_utt=1,
+                         frame_logp=new(f32, P, T), band_base=new(i32, P, NB) if want_band_base else None)
     out.band_states = BW
-    names = ('start', 'nframes', 'score', 'path_score', 'frame_logp', 'band_base', 'ok')
-    for n, dt, shape in zip(names, (torch.int32, torch.int32, torch.float32, torch.int64, torch.float32, torch.int32, torch.int32),
-                            ((P, ML), (P, ML), (P, ML), (P,), (P, T), (P, NB), (P,))):
-        t = getattr(out, n)
-        assert t is None or (t.is_cuda and t.is_contiguous() and t.dtype == dt and tuple(t.shape) == shape), \
-            f'ctc_align_band: out.{n}'
+    _set_outputs(who, a, out, (('start', i32, (P, ML), True), ('nframes', i32, (P, ML), True), ('score', f32, (P, ML), True),
+                               ('path_score', torch.int64, (P,), True), ('frame_logp', f32, (P, T), True),
+                               ('band_base', i32, (P, NB), True), ('ok', i32, (P,), True)))
     assert out.ok is not None, 'ctc_align_band: out.ok is required'
-    if workspace is None:
-        workspace = torch.empty(max(ctc_align_band_workspace_bytes(P, T, BW), 8), device=dev, dtype=torch.uint8)
-    a = AlignBandArgs()
-    a.struct_size = C.sizeof(AlignBandArgs) if star is not None else AlignBandArgs.star_logp.offset   # (as ctc_align)
+    workspace = _set_workspace(a, workspace, dev, ctc_align_band_workspace_bytes, P, T, BW)
     a.B, a.T, a.C, a.blank, a.max_labels, a.band_states = P, T, Cn, int(blank), ML, BW
-    a.pitch_utt, a.pitch_frame = (lp.stride(0) if P > 1 else max(lp.stride(0), T * lp.stride(1))), lp.stride(1)
-    a.log_probs, a.lens, a.targets, a.target_lens = lp.data_ptr(), 0 if ln is None else ln.data_ptr(), tg.data_ptr(), tl.data_ptr()
-    a.workspace, a.workspace_bytes = workspace.data_ptr(), workspace.numel() * workspace.element_size()
-    for n in names:
-        t = getattr(out, n)
-        setattr(a, n, 0 if t is None else t.data_ptr())
-    st = None
-    if star is not None:
-        st, a.star_pitch = _star_arg(star, P, T, dev, 'ctc_align_band')
-        a.star_logp = st.data_ptr()
-    with torch.cuda.device(dev):
-        _check(lib.qasr_ctc_align_band(_stream_ptr(stream), C.byref(a)), 'qasr_ctc_align_band')
-    out._keep = (lp, ln, tg, tl, workspace, st)
-    return out
+    st = None if star is None else _set_star(who, a, star, P, T, dev)
+    return _lattice_launch('qasr_ctc_align_band', a, dev, stream, out, (lp, ln, tg, tl, workspace, st))
 
 
 class PostBandArgs(C.Structure):
@@ -948,67 +917,23 @@ def ctc_post_band(log_probs, lens, targets, target_lens, blank, band_result, sta
     int32 [P, max_labels], total int64 [P], ok int32 [P].  workspace: a caller-owned uint8 tensor of
     ctc_post_band_workspace_bytes(P, T) bytes, 8-byte aligned (None: allocated by torch here); `out`: a caller-owned PostResult
     whose total may be None and whose frame_post rows may have any pitch >= T."""
-    from .align import BAND_BLOCK, BAND_MAX_FRAMES, BAND_MAX_LABELS, PostResult, pick_band_states
-    from .beam import TAB_ENTRIES
-    lib = load_library()
-    assert log_probs.is_cuda and log_probs.dim() == 3 and log_probs.dtype == torch.float32, \
-        'ctc_post_band: log_probs must be a cuda float32 tensor [P, T, C]'
-    dev = log_probs.device
-    lp = log_probs if log_probs.stride(2) == 1 or log_probs.shape[2] == 1 else log_probs.contiguous()
-    ln = None if lens is None else lens.to(device=dev, dtype=torch.int32).contiguous()
-    P, T, Cn = lp.shape
-    assert targets.dim() == 2 and target_lens.dim() == 1, 'ctc_post_band: targets must be [P, max_labels], target_lens [P]'
-    tg = targets.to(device=dev, dtype=torch.int32).contiguous()
-    tl = target_lens.to(device=dev, dtype=torch.int32).contiguous()
+    from .align import BAND_BLOCK, pick_band_states
+    who = 'ctc_post_band'
+    a, lp, ln, (P, T, Cn) = _lattice_logp(who, PostBandArgs, log_probs, lens, '[P, T, C]')
+    dev = lp.device
+    tg, tl = _band_targets(who, a, targets, target_lens, dev, P, T)
     ML = tg.shape[1]
-    if tg.shape[0] != P or tl.shape[0] != P:
-        raise ValueError(f'ctc_post_band: {P} recordings but {tg.shape[0]} target rows and {tl.shape[0]} lengths')
-    if not 1 <= ML <= BAND_MAX_LABELS:
-        raise ValueError(f'ctc_post_band: max_labels (the row pitch of targets) must be 1 .. {BAND_MAX_LABELS}, got {ML}')
-    if T > BAND_MAX_FRAMES:
-        raise ValueError(f'ctc_post_band: at most {BAND_MAX_FRAMES} frames, got {T}')
     try:
         BW = pick_band_states(ML, band_result.band_states or None)
     except ValueError as e:
         raise ValueError(f'ctc_post_band: band_result.{e}') from None
     NB = (T + BAND_BLOCK - 1) // BAND_BLOCK
-    i32 = dict(device=dev, dtype=torch.int32)
-    ins = []
-    for n, shape in (('start', (P, ML)), ('nframes', (P, ML)), ('ok', (P,)), ('band_base', (P, NB))):
-        t = getattr(band_result, n)
-        assert t is not None and tuple(t.shape) == shape, f'ctc_post_band: band_result.{n} must be {list(shape)}'
-        ins.append(t.to(**i32).contiguous())
-    if out is None:
-        out = PostResult(frame_post=torch.empty(P, T, **i32), label_post=torch.empty(P, ML, **i32),
-                         total=torch.empty(P, device=dev, dtype=torch.int64), ok=torch.empty(P, **i32))
-    fp = out.frame_post
-    assert fp is not None and fp.is_cuda and fp.dtype == torch.int32 and tuple(fp.shape) == (P, T) and (T == 1 or fp.stride(1) == 1), \
-        'ctc_post_band: out.frame_post'
-    for n, dt, shape in (('label_post', torch.int32, (P, ML)), ('total', torch.int64, (P,)), ('ok', torch.int32, (P,))):
-        t = getattr(out, n)
-        assert (t is None and n == 'total') or (t is not None and t.is_cuda and t.is_contiguous() and t.dtype == dt and
-                                                tuple(t.shape) == shape), f'ctc_post_band: out.{n}'
-    if workspace is None:
-        workspace = torch.empty(max(ctc_post_band_workspace_bytes(P, T), 8), device=dev, dtype=torch.uint8)
-    tab = lae_table_device(dev)
-    a = PostBandArgs()
-    a.struct_size = C.sizeof(PostBandArgs)
+    out, ins, tab = _set_post(who, a, band_result, 'band_result',
+                              (('start', (P, ML)), ('nframes', (P, ML)), ('ok', (P,)), ('band_base', (P, NB))), out, P, T, ML, dev)
+    workspace = _set_workspace(a, workspace, dev, ctc_post_band_workspace_bytes, P, T)
     a.B, a.T, a.C, a.blank, a.max_labels, a.band_states = P, T, Cn, int(blank), ML, BW
-    a.pitch_utt, a.pitch_frame = (lp.stride(0) if P > 1 else max(lp.stride(0), T * lp.stride(1))), lp.stride(1)
-    a.log_probs, a.lens, a.targets, a.target_lens = lp.data_ptr(), 0 if ln is None else ln.data_ptr(), tg.data_ptr(), tl.data_ptr()
-    a.lae_entries, a.lae_table = TAB_ENTRIES, tab.data_ptr()
-    a.start, a.nframes, a.ok_in, a.band_base = (t.data_ptr() for t in ins)
-    a.workspace, a.workspace_bytes = workspace.data_ptr(), workspace.numel() * workspace.element_size()
-    a.frame_post, a.post_pitch = fp.data_ptr(), (fp.stride(0) if P > 1 else max(fp.stride(0), T))
-    a.label_post, a.total, a.ok = out.label_post.data_ptr(), 0 if out.total is None else out.total.data_ptr(), out.ok.data_ptr()
-    st = None
-    if star is not None:
-        st, a.star_pitch = _star_arg(star, P, T, dev, 'ctc_post_band')
-        a.star_logp = st.data_ptr()
-    with torch.cuda.device(dev):
-        _check(lib.qasr_ctc_post_band(_stream_ptr(stream), C.byref(a)), 'qasr_ctc_post_band')
-    out._keep = (lp, ln, tg, tl, ins, workspace, tab, st)
-    return out
+    st = None if star is None else _set_star(who, a, star, P, T, dev)
+    return _lattice_launch('qasr_ctc_post_band', a, dev, stream, out, (lp, ln, tg, tl, ins, workspace, tab, st))
 
 
 class ResampleArgs(C.Structure):
@@ -1861,12 +1786,8 @@ def stream_spot(state, spot_state, S, plan, splan, slots, flags, log_probs, star
     None) -> a qasr.stream_spot.SpotStepBatch of cuda tensors.  k_stream_spot, one launch, nothing read back; equal to
     qasr.stream_spot.spot_batch_host byte for byte, the spot state included."""
     from . import stream_spot as qs
-    lib = load_library()
-    dev = state.device
-    assert log_probs.is_cuda and log_probs.dim() == 3 and log_probs.dtype == torch.float32, \
-        'stream_spot: log_probs must be a cuda float32 tensor [B, Tw, C]'
-    lp = log_probs if log_probs.stride(2) == 1 or log_probs.shape[2] == 1 else log_probs.contiguous()
-    B, Tw, Cn = lp.shape
+    who, dev = 'stream_spot', state.device
+    a, lp, _, (B, Tw, Cn) = _lattice_logp(who, StreamSpotArgs, log_probs, None, '[B, Tw, C]')
     for t, w in ((slots, 'slots'), (flags, 'flags'), (enc_lens, 'enc_lens'), (first_frame, 'first_frame'), (emit_status, 'emit_status')):
         _i32dev(t, B, 'stream_spot: ' + w)
     assert spot_state.is_cuda and spot_state.dtype == torch.int32 and spot_state.is_contiguous(), 'stream_spot: spot_state'
@@ -1876,29 +1797,17 @@ def stream_spot(state, spot_state, S, plan, splan, slots, flags, log_probs, star
     if out is None:
         out = stream_spot_buffers(B, splan, dev)
     P, PH = B * splan.K, out.hit_start.shape[1]
-    for n in qs.FIELDS:
-        t = getattr(out, n)
-        dt = torch.int64 if n in qs.FIELD_DTYPES else torch.int32
-        shape = (P, PH) if n.startswith('hit_') else (P,)
-        assert t.is_cuda and t.is_contiguous() and t.dtype == dt and tuple(t.shape) == shape, f'stream_spot: out.{n}'
-    st, spitch = _star_arg(star, B, Tw, dev, 'stream_spot')
-    a = StreamSpotArgs()
-    a.struct_size = C.sizeof(StreamSpotArgs)
+    _set_outputs(who, a, out, [(n, torch.int64 if n in qs.FIELD_DTYPES else torch.int32, (P, PH) if n.startswith('hit_') else (P,), False)
+                               for n in qs.FIELDS])
+    st = _set_star(who, a, star, B, Tw, dev)
     a.S, a.B, a.Wl, a.C, a.Rr, a.samples_per_frame, a.Tw = int(S), B, plan.Wl, plan.C, plan.Rr, plan.samples_per_frame, Tw
     a.n_classes, a.K, a.max_labels, a.blank = Cn, splan.K, splan.ML, int(blank)
     a.threshold_q, a.max_span, a.PH, a.max_final_frames = splan.threshold_q, splan.max_span, PH, splan.max_final_frames
-    a.pitch_utt, a.pitch_frame = (lp.stride(0) if B > 1 else max(lp.stride(0), Tw * lp.stride(1))), lp.stride(1)
-    a.log_probs, a.star_logp, a.star_pitch = lp.data_ptr(), st.data_ptr(), spitch
     a.state, a.state_bytes = state.data_ptr(), state.numel() * state.element_size()
     a.spot_state, a.spot_state_bytes = spot_state.data_ptr(), spot_state.numel() * spot_state.element_size()
     a.slots, a.flags, a.enc_lens, a.first_frame = slots.data_ptr(), flags.data_ptr(), enc_lens.data_ptr(), first_frame.data_ptr()
     a.emit_status, a.targets, a.target_lens = emit_status.data_ptr(), tg.data_ptr(), tl.data_ptr()
-    for n in qs.FIELDS:
-        setattr(a, n, getattr(out, n).data_ptr())
-    with torch.cuda.device(dev):
-        _check(lib.qasr_stream_spot(_stream_ptr(stream), C.byref(a)), 'qasr_stream_spot')
-    out._keep = (lp, st, tg, tl)
-    return out
+    return _lattice_launch('qasr_stream_spot', a, dev, stream, out, (lp, st, tg, tl))
 
 
 class Engine:

@@ -3,15 +3,15 @@ check fires and what qasr_last_error says.  Host code only: ctypes structs of qa
 host buffer standing for every pointer, stream NULL.  Every argument block is a base that passes all checks with mutations
 on top; the base alone is never passed, so nothing is ever launched.
 
-An entry is a list of checks in the order of the source; a check is a list of mutations that reach its `fail(` line.  The
-cases of an entry are (a) every mutation on its own, named `check/mutation`, and (b) for each two checks that follow one
-another the first mutation of both at once, named `check+next`: the message must be the earlier check's.  A field that both
-mutations set takes the earlier one's value.
+An entry is a list of checks in the order of the source; a check is a list of mutations that reach its `fail(` line.  How the
+entries become cases - (a) every mutation on its own, (b) each two neighbouring checks broken at once - and the runner are
+abi_refusal_driver's, shared with abi_lattice_refusal_cases.
 
 tests/golden/gen_golden_abi_beam_refusals.py records (entry, case, rc, text); test_abi_beam_refusals_cpu.py compares."""
 import ctypes as C
 
-import numpy as np
+import abi_refusal_driver as driver
+from abi_refusal_driver import PTR, null as _null
 
 S, B, W, N, NB, BLANK, SPACE = 3, 2, 16, 20, 2, 28, 27
 T = 5                                                   # frames of the offline calls
@@ -19,25 +19,6 @@ SPF, WL, CH, RR, TW, MFF = 160, 4800, 1600, 1600, 30, 10  # samples per frame, w
 LG, K, F, P, PTAIL, PEND, E = 2, 7, 9, 24, 4, 12, 3     # P and Pend with room for F + 1
 LAE = 16384
 MAXW = 16 << 16                                         # QASR_LM_MAX_WEIGHT
-
-_buf = np.zeros(64 + 4, dtype=np.int32)
-PTR = (_buf.ctypes.data + 15) & ~15                     # stands for every pointer: a refused call reads none of them
-
-
-def put(a, path, v):
-    """a.path = v; path: dotted fields, the last one possibly indexed ('boost.sets[1]')"""
-    *head, last = path.split('.')
-    for h in head:
-        a = getattr(a, h)
-    if last.endswith(']'):
-        name, i = last[:-1].split('[')
-        getattr(a, name)[int(i)] = v
-    else:
-        setattr(a, last, v)
-
-
-def _null(names):
-    return [(n, {n: None}) for n in names]
 
 
 # ---- the offline calls
@@ -240,31 +221,8 @@ def entries(lib, engine):
 
 
 def cases(lib, engine):
-    """[(entry, case, function, base, mutation)], NULL args first"""
-    out = []
-    for entry, fn, base, checks in entries(lib, engine):
-        out.append((entry, 'args NULL', fn, None, {}))
-        for name, muts in checks:
-            out += [(entry, f'{name}/{m}', fn, base, kw) for m, kw in muts]
-        for (n0, m0), (n1, m1) in zip(checks, checks[1:]):
-            out.append((entry, f'{n0}+{n1}', fn, base, {**m1[0][1], **m0[0][1]}))
-    return out
+    return driver.cases(entries(lib, engine))
 
 
 def run(lib, engine):
-    """Every case's (entry, case, rc, text).  Stops at the first rc that is not 1 (QASR_ERR_ARG): a call that is not refused
-    would go on to launch."""
-    got = []
-    for entry, case, fn, base, kw in cases(lib, engine):
-        assert kw or base is None, (entry, case)                   # the base alone is never passed
-        if base is None:
-            rc = fn(None, None)
-        else:
-            a = base()
-            for path, v in kw.items():
-                put(a, path, v)
-            rc = fn(None, C.byref(a))
-        text = lib.qasr_last_error().decode()
-        assert rc == 1, f'{entry}: {case}: rc {rc} ({text!r} is the last error)'
-        got.append([entry, case, rc, text])
-    return got
+    return driver.run(lib, entries(lib, engine))

@@ -19,11 +19,12 @@ import abi_beam_refusal_cases as cases  # noqa: E402
 from qasr import engine  # noqa: E402
 
 
-def main():
+def main(cases=cases, name='abi_beam_refusals'):
+    """(gen_golden_abi_lattice_refusals.py calls this with its own list of cases)"""
     lib = engine.load_library()
     got = cases.run(lib, engine)
     assert got == cases.run(lib, engine), 'the texts differ between two runs'
-    with open(os.path.join(HERE, 'abi_beam_refusals.json'), 'w') as f:
+    with open(os.path.join(HERE, name + '.json'), 'w') as f:
         f.write('{"library": %s, "cases": [\n%s\n]}\n' % (json.dumps(lib.qasr_version().decode()), ',\n'.join(json.dumps(c) for c in got)))
     print(len(got), 'cases,', len({(e.split(' (')[0], t) for e, _, _, t in got}), 'distinct (entry, message) pairs')
 
