@@ -55,6 +55,12 @@ typedef v4i __attribute__((address_space(3))) lds_v4i;
 #define SEP2_WPE 2                      /* waves per SIMD the register budget is sized for: 2 = one work-group per CU, 256 VGPRs */
 #endif
 #define SEP2_CH 128                     /* channels per depthwise group: 16 per wave */
+#ifndef SEP2_EARLY
+#define SEP2_EARLY 1                    /* the work-group prologue: 1 = group 0's requests leave on the shortest path, */
+#endif                                  /* lens[b] and the later phases' kernel arguments travel behind them; 0 = the order before (A/B) */
+#ifndef SEP2_PSTAMP
+#define SEP2_PSTAMP 0                   /* 1 (profiling builds, profiles/phase_stamps.py --prologue): phase stamps inside the prologue */
+#endif
 
 template <int K, int TT>
 struct Sep2Geo {
@@ -310,6 +316,23 @@ struct Sep2PassP {
   float sbm, sbp;                                            // EXACT_Z: conv output scales
 };
 
+// (SEP2_EARLY) ONE round of scalar loads, waited for once, for every kernel argument of the prologue.  A first touch of the
+// argument segment costs 0.7 - 1 k cycles (phase stamps), and left to the compiler the arguments came in rounds of their own,
+// each in front of its first use: the pointer to lens[], what group 0's addresses need, then on the way to the first MFMA
+// x_unsigned (commit) and n_outs, bias, the consumers' tables, sb (load_pps), one behind the other.  (k_sep2p calls it in
+// front of its own look at B and Tp, which was one more round.)
+template <bool RES>
+__device__ __forceinline__ void sep2_args_round(const SepP& p) {
+  const EpiP& e = p.e;
+  asm volatile("" :: "s"(e.lens), "s"(e.Tp), "s"(e.B), "s"(p.x), "s"(p.wdw2), "s"(p.bias_dw), "s"(p.m_dw), "s"(p.prof), "s"(p.prof_mode),
+               "s"(p.dw_lo), "s"(p.dw_hi), "s"(e.flags), "s"(e.n_outs), "s"(p.x_unsigned), "s"(p.bias), "s"(e.sb), "s"(p.w));
+  if constexpr (RES) asm volatile("" :: "s"(p.panes[0].bias), "s"(e.m_main), "s"(p.panes[0].m), "s"(p.panes[0].sb),
+                                  "s"(p.panes[0].x_unsigned), "s"(p.panes[0].w), "s"(p.panes[0].x));
+  else asm volatile("" :: "s"(p.pw_unsigned), "s"(e.outs[0].mtab), "s"(e.outs[1].mtab), "s"(e.outs[2].mtab), "s"(e.outs[0].ptr),
+                    "s"(e.outs[0].lo), "s"(e.outs[0].hi));
+  __builtin_amdgcn_sched_barrier(0);                         // (a first use hoisted above this point splits the round in two)
+}
+
 // K taps, NG groups of 128 input channels (cin_pad = 128 NG), NGP groups of the residual 1x1 conv (0: no res_act),
 // NP passes of 256 output channels - all compile-time: the whole kernel is straight-line code, which is what lets the
 // compiler count its s_waitcnt vmcnt(N) exactly instead of draining every prefetch at each join
@@ -364,17 +387,34 @@ __device__ __forceinline__ void sep2_body(const SepP& p, const int b, const int 
   lds_u8* const Wsw = Un + wave * G::WREG;
   lds_u8* const Tlw = Wsw + 16 * G::WP;
 
+  long long t_entry = 0;                                     // (SEP2_PSTAMP) the wave's first instruction: in front of lens[b]
+  if constexpr (SEP2_PSTAMP != 0) {
+    t_entry = (long long)__builtin_amdgcn_s_memtime();
+    asm volatile("" : "+s"(t_entry) :: "memory");
+  }
   const unsigned flags = e.flags;
   const int eT = e.T, eTp = e.Tp, ecout = e.cout, n_outs = e.n_outs;
-  const int len_b = e.lens[b];
-  const int lim = (flags & QASR_F_MASK_OUT) ? min(len_b, eT) : eT;
-  const int dlim = min(len_b, eT);                           // the 1x1 conv's MaskedConv1d masks its input
+  // the prologue order of DESIGN.md 5.8.  The mask-skip instantiations keep the order before: reordered, two of them took one
+  // and two registers more, and no phase stamp of a reserved engine's launch says what they would gain
+  constexpr bool EARLY = SEP2_EARLY && !SKIP;
+  if constexpr (EARLY && !DBG && !PAIR) sep2_args_round<(NGP > 0)>(p);   // (k_sep2p has called it in front of its look at B and Tp)
+  // lens[b] is a global load behind a pointer from the kernel arguments, and only the masks need it.  Requested here and
+  // consumed here, the wave waited for it (s_waitcnt vmcnt(0)) before it computed the first address of group 0; SEP2_EARLY
+  // consumes it behind every request of the prologue (len_use)
+  int len_b = e.lens[b], lim = 0, dlim = 0;
+  auto len_use = [&]() {
+    lim = (flags & QASR_F_MASK_OUT) ? min(len_b, eT) : eT;
+    dlim = min(len_b, eT);                                   // the 1x1 conv's MaskedConv1d masks its input
+  };
+  if constexpr (!EARLY) len_use();
   const bool f_relu = flags & QASR_F_RELU;
   const bool f_exact = flags & QASR_F_EXACT_Z;
   int dw_lo = p.dw_lo, dw_hi = p.dw_hi;
   // fetched NOW: left to the compiler the scalar load sits in front of the first requantisation, and its
   // s_waitcnt lgkmcnt(0) (scalar loads return out of order) also waits for the next group's LDS reads issued just before
-  asm volatile("" : "+v"(dw_lo), "+v"(dw_hi));               // (as VGPRs: v_med3_i32's operands; "+s" breaks the debug build)
+  // (as VGPRs: v_med3_i32's operands; "+s" breaks the debug build.  SEP2_EARLY: behind group 0's requests - here the copies
+  //  to VGPRs, hoisted to the front of the arguments' round, split it in two)
+  if constexpr (!EARLY) asm volatile("" : "+v"(dw_lo), "+v"(dw_hi));
   const bool stamp = p.prof && (p.prof_mode & 255) == 0 && stamp_wg && tid == 0;
   const bool tline = p.prof && (p.prof_mode & 255) == 1 && tid == 0;
   const int tune = p.prof_mode >> 8;                          // QASR_SEP2_TUNE (experiments)
@@ -384,8 +424,17 @@ __device__ __forceinline__ void sep2_body(const SepP& p, const int b, const int 
     tl_clk = (long long)__builtin_amdgcn_s_memtime();
   }
   int nst = 0;
-#define STAMP2() do { if (stamp && nst < 31) p.prof[nst++] = (long long)__builtin_amdgcn_s_memtime(); } while (0)
+#define STAMP2() do { if (stamp && nst < (SEP2_PSTAMP ? 24 : 31)) p.prof[nst++] = (long long)__builtin_amdgcn_s_memtime(); } while (0)
+  // SEP2_PSTAMP builds: the prologue's own points, in slots of their own (24 + I; the order of the points differs between
+  // the two prologue orders, the slots do not).  WAIT: first wait for everything requested so far
+#define PSTAMP2(I, WAIT) do { if constexpr (SEP2_PSTAMP != 0) { if (stamp) {                                   \
+      if (WAIT) asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");                                   \
+      p.prof[24 + (I)] = (long long)__builtin_amdgcn_s_memtime(); } } } while (0)
   STAMP2();
+  PSTAMP2(0, !EARLY);                                   // kernel arguments (and, in the old order, lens[b]) are here
+  if constexpr (SEP2_PSTAMP != 0) {
+    if (stamp) p.prof[24 + 5] = t_entry;
+  }
 
   // Shapes are exact (sep2_shape_ok): cin == CIN_PAD, cout == 256 NP, residual cin == PCIN_PAD - no row / channel guards.
   // ------------------------------------------------------------------------------------------ global requests
@@ -408,21 +457,27 @@ __device__ __forceinline__ void sep2_body(const SepP& p, const int b, const int 
   int woff[NPT], toff[NTT];
   unsigned wkeep[NPT];
   lds_u8* wlds[NPT];
-#pragma unroll
-  for (int i = 0; i < NPT; ++i) {
-    const int pi = lane + 64 * i;
-    const int row = pi / NPGR, col = pi - row * NPGR;
-    const int t = t0 - DIL * G::HALO + 16 * col;             // a granule lies entirely inside or outside [0, Tp)
-    // unconditional loads from clamped addresses (the keep mask zeroes what lies outside): a load under a branch with a
-    // zero-initialised destination is waited for on the spot
-    woff[i] = min(row, RCH - 1) * eTp + min(max(t, 0), eTp - 16);
-    wkeep[i] = (t >= 0 && t < eTp) ? 0xffffffffu : 0u;       // conv zero padding beyond the tensor
-    // DIL 2: the granule's even bytes go to row 2 r (8 bytes at 8 col), its odd bytes to row 2 r + 1
-    wlds[i] = DIL == 1 ? Wsw + min(row, 15) * G::WP + 16 * col : Wsw + 2 * min(row, RCH - 1) * G::WP + 8 * col;
-    asm volatile("" : "+v"(wkeep[i]));                       // a mask, not a predicate: (v & keep) ^ flip is ONE v_bitop3_b32
+  // (EARLY: only the offsets stand between the kernel arguments and group 0's requests; masks and LDS addresses are computed
+  //  while those travel.  A macro, not a lambda: through a closure the same loops cost the dilation-2 form two registers)
+#define SEP2_LANE_CONSTS(OFFS, REST)                                                                                     \
+  _Pragma("unroll") for (int i = 0; i < NPT; ++i) {                                                                      \
+    const int pi = lane + 64 * i;                                                                                        \
+    const int row = pi / NPGR, col = pi - row * NPGR;                                                                    \
+    const int t = t0 - DIL * G::HALO + 16 * col;             /* a granule lies entirely inside or outside [0, Tp) */     \
+    /* unconditional loads from clamped addresses (the keep mask zeroes what lies outside): a load under a branch with   \
+       a zero-initialised destination is waited for on the spot */                                                       \
+    if constexpr (OFFS) woff[i] = min(row, RCH - 1) * eTp + min(max(t, 0), eTp - 16);                                    \
+    if constexpr (REST) {                                                                                                \
+      wkeep[i] = (t >= 0 && t < eTp) ? 0xffffffffu : 0u;     /* conv zero padding beyond the tensor */                   \
+      /* DIL 2: the granule's even bytes go to row 2 r (8 bytes at 8 col), its odd bytes to row 2 r + 1 */               \
+      wlds[i] = DIL == 1 ? Wsw + min(row, 15) * G::WP + 16 * col : Wsw + 2 * min(row, RCH - 1) * G::WP + 8 * col;        \
+      asm volatile("" : "+v"(wkeep[i]));                     /* a mask, not a predicate: (v & keep) ^ flip is ONE v_bitop3_b32 */ \
+    }                                                                                                                    \
+  }                                                                                                                      \
+  if constexpr (OFFS) {                                                                                                  \
+    _Pragma("unroll") for (int i = 0; i < NTT; ++i) toff[i] = 16 * min(lane + 64 * i, NTG - 1);                          \
   }
-#pragma unroll
-  for (int i = 0; i < NTT; ++i) toff[i] = 16 * min(lane + 64 * i, NTG - 1);
+  SEP2_LANE_CONSTS(true, !EARLY)
   auto ld_grp = [&](int g) {
     const int cw = cbase + GCH * g + RCH * wave;             // (wave-uniform: the bases below are scalar)
     const int8_t* const xg = p.x + ((size_t)b * CIN_PAD + cw) * eTp;
@@ -490,9 +545,16 @@ __device__ __forceinline__ void sep2_body(const SepP& p, const int b, const int 
 #pragma unroll
     for (int j = 0; j < 4 * NG; ++j) wf[j] = w0[64 * j];       // the whole first slab right behind the tile
   } else {
+    if constexpr (!EARLY) PSTAMP2(1, false);            // per-lane constants
     ld_grp(0);
   }
   STAMP2();                                                  // requests of group 0 issued
+  if constexpr (EARLY) {
+    // what the requests did not need, while they travel: the rest of the per-lane constants
+    SEP2_LANE_CONSTS(false, true)
+    asm volatile("" : "+v"(dw_lo), "+v"(dw_hi));
+    PSTAMP2(1, false);                                       // per-lane constants (and the arguments above)
+  }
 
   // per-group depthwise parameters of this lane's channels and the per-lane parameters of every GEMM pass: a handful
   // of registers, requested right behind chunk 0
@@ -507,6 +569,14 @@ __device__ __forceinline__ void sep2_body(const SepP& p, const int b, const int 
       dM[gi] = p.m_dw[c];
     }
   }
+  if constexpr (EARLY) {
+    // behind every request of the prologue: the length (the "+v" keeps every use of lens[b], and with them its s_waitcnt,
+    // below this point)
+    asm volatile("" : "+v"(len_b));
+    len_b = __builtin_amdgcn_readfirstlane(len_b);
+    len_use();
+  }
+  PSTAMP2(2, false);                                         // depthwise parameters requested
   Sep2PassP pps[NPL];
   auto load_pps = [&]() {                                    // (issued behind the first group's operands: not on the way
 #pragma unroll                                               //  to the first MFMA)
@@ -683,7 +753,11 @@ __device__ __forceinline__ void sep2_body(const SepP& p, const int b, const int 
   auto stage = [&](auto chc) {                               // rows of group CH: registers -> LDS -> lane streams
     constexpr int CH = decltype(chc)::value;
     commit();
-    if constexpr (CH + 1 < NCHUNK) ld_grp(CH + 1);
+    if constexpr (CH == 0) PSTAMP2(3, false);                // group 0's rows are on their way to LDS
+    // (group 0, SEP2_EARLY: nothing runs beside this wave's LDS round trip yet, so the lane streams are read back first and
+    //  the next group is requested while they travel)
+    constexpr bool RD1ST = EARLY && CH == 0;
+    if constexpr (CH + 1 < NCHUNK && !RD1ST) ld_grp(CH + 1);
     // the wave's own LDS writes -> its own reads: LDS executes a wave's instructions in order; the fences keep the
     // compiler from moving the reads above the writes of other lanes
     __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
@@ -691,6 +765,7 @@ __device__ __forceinline__ void sep2_body(const SepP& p, const int b, const int 
     __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
     dw_read(in);
     __builtin_amdgcn_sched_barrier(0);                       // the reads are issued here; their first use is the next group
+    if constexpr (CH + 1 < NCHUNK && RD1ST) ld_grp(CH + 1);
   };
   // The SIMD issues one VALU or MFMA instruction per ~4.6 cycles whichever wave it comes from, a 4x4x4 MFMA occupies the
   // matrix pipe for 8.3, and the older wave of a SIMD pair wins every issue slot it can use (profiles/microbench/
@@ -706,13 +781,18 @@ __device__ __forceinline__ void sep2_body(const SepP& p, const int b, const int 
 #endif
   constexpr bool ILV = SEP2_ILV && (!RES || TT <= 64) && DIL == 1;   // (register budget of the block-end forms at 128 frames)
   v4i accs[ILV ? 2 : 1][NU];
+  // (EARLY) the GEMM passes' per-lane parameters are requested from inside group 0's MFMAs, where the wave has issue
+  // slots to spare, not in front of them
+  auto pps_late = [&]() {
+    if constexpr (EARLY && !DBG) load_pps();               // (the debug instantiations have no registers to spare there)
+  };
   auto chunk = [&](auto chc) {
     constexpr int CH = decltype(chc)::value;
     constexpr int c0 = GCH * CH;
     constexpr int NPF = (CH + 1 == NCHUNK ? NRT : 0) + (CH < SLC ? 4 * NG * (CH + 1) / SLC - 4 * NG * CH / SLC : 0);
     constexpr int Q = (NPF + 2) / 3;                         // three issue points per group
     if constexpr (ILV) {
-      if constexpr (CH == 0) dw_mfma(in, accs[0], dbias[0], [&](int k) { pf(chc, Q * k, Q * (k + 1)); });
+      if constexpr (CH == 0) dw_mfma(in, accs[0], dbias[0], [&](int k) { pf(chc, Q * k, Q * (k + 1)); if (k == 1) pps_late(); });
       else {
         if (DBG && p.dw_acc_dbg) {                           // (debug builds: the plain order, accumulators dumped)
           dw_out(accs[(CH - 1) & 1], c0 - GCH, dM[CH - 1]);
@@ -728,7 +808,7 @@ __device__ __forceinline__ void sep2_body(const SepP& p, const int b, const int 
       else dw_out(accs[CH & 1], c0, dM[CH]);
       STAMP2();
     } else {
-      dw_mfma(in, accs[0], dbias[CH], [&](int k) { pf(chc, Q * k, Q * (k + 1)); });
+      dw_mfma(in, accs[0], dbias[CH], [&](int k) { pf(chc, Q * k, Q * (k + 1)); if (CH == 0 && k == 1) pps_late(); });
       STAMP2();
       if constexpr (CH + 1 < NCHUNK) stage(std::integral_constant<int, CH + 1>{});
       dw_out(accs[0], c0, dM[CH]);
@@ -745,7 +825,7 @@ __device__ __forceinline__ void sep2_body(const SepP& p, const int b, const int 
       if (wave < 4) __builtin_amdgcn_s_setprio(3);
     }
     stage(std::integral_constant<int, 0>{});
-    load_pps();
+    if constexpr (!EARLY || DBG) load_pps();
     if (tune & 2) {                                          // stagger the SIMD partners by (tune >> 4) x 64 cycles
       if (wave >= 4)
         for (int i = 0; i < ((tune >> 4) & 127); ++i) __builtin_amdgcn_s_sleep(1);
@@ -1068,6 +1148,8 @@ __device__ __forceinline__ void sep2_body(const SepP& p, const int b, const int 
     r[2] = (long long)__builtin_amdgcn_s_getreg(63492) | ((long long)__builtin_amdgcn_s_getreg(6164) << 32);   // HW_ID, XCC_ID
   }
 #undef STAMP2
+#undef PSTAMP2
+#undef SEP2_LANE_CONSTS
 }
 
 template <int K, int NG, int NGP, int NP, bool DBG, int TT, int DIL = 1>
@@ -1088,6 +1170,7 @@ __global__ void __launch_bounds__(SEP2_NT, SEP2_WPE) k_sep2s(SepP p) {
 // depend on where or when a member runs; ids beyond the last pair leave at once.
 template <int K>
 __global__ void __launch_bounds__(SEP2_NT, SEP2_WPE) k_sep2p(SepP p) {
+  if constexpr (SEP2_EARLY) sep2_args_round<false>(p);
   const int id = blockIdx.x, P = 8 * (id >> 4) + (id & 7), hm = (id >> 3) & 1;
   const int B = p.e.B;
   if (P >= B * (p.e.Tp / 128)) return;
