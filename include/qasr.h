@@ -1510,6 +1510,10 @@ int qasr_engine_op_paired(const qasr_engine* e, int op);
 /* synchronises the device, returns how many hand-off spins of paired launches gave up since the last call (their results
  * are wrong; 0 in a healthy run) and clears the count */
 int qasr_engine_pair_timeouts(qasr_engine* e);
+/* Diagnostics, read-only: the flag words of the plan's paired ops (2 per work-group pair and op, each op's padded to 256
+ * bytes).  Returns how many words the engine has (0: no paired op, -1: error); with `out`, synchronises the device and copies
+ * the first min(n, that many) words.  Behind a forward every word of a pair that ran holds 1: each forward zeroes them first. */
+int qasr_engine_pair_flag_words(const qasr_engine* e, uint32_t* out, size_t n);
 
 /* Diagnostics: when set to a device buffer of 32 int64, work-group (1,0,0) of every k_sep launch writes s_memtime
  * stamps at its phase boundaries (slot 31 = number of stamps); NULL (default) disables. */

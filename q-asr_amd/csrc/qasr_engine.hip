@@ -134,10 +134,10 @@ struct qasr_engine {
   bool pair_split = false;
   std::vector<char> paired;            // per op: launched in the paired form (empty: none)
   std::vector<size_t> pair_flag_off;   // per op: byte offset of its flag words in pair_flags
-  unsigned* pair_flags = nullptr;      // every paired op's flag words: an allocation of their own, zeroed by ONE k_pair_zero node per forward
+  unsigned* pair_flags = nullptr;      // every paired op's flag words: an allocation of their own, zeroed once per forward (by k_stem, or by ONE k_pair_zero node without the fused stem)
   size_t pair_flag_bytes = 0;
   unsigned char* pair_x = nullptr;     // [256 B: the time-out word][exchange buffer, B x tiles x 64 KiB, shared by all paired ops]
-  bool in_forward = false;             // launch_op runs inside enqueue_forward (the forward's memset has zeroed the flags)
+  bool in_forward = false;             // launch_op runs inside enqueue_forward (which zeroes the flags: k_pair_zero in front, or k_stem)
   // hipGraph replay (bit 4 of `debug`): the whole forward of one (shape, buffer set) is captured once and re-launched
   // with one call; key = the caller's pointers, which a serving loop keeps stable
   bool forwarded = false;              // a forward has been enqueued with the current plan
@@ -816,8 +816,12 @@ static int stem_launch(qasr_engine* e, hipStream_t s) {
   build_quant_in(e, 0, qi);
   build_dw(e, 1, dw);
   build_sep(e, 2, pw);
+  // inside a forward the stem zeroes the flag words of every paired op (enqueue_forward enqueues no k_pair_zero then); run_op
+  // and time_ops reach here outside one, and their paired ops zero their own words
+  const bool zero = e->in_forward && e->pair_flags;
   int rc = launch_stem(s, qi, dw, pw, (const qasr_domain_desc*)(e->dblob + e->h.domains_off), (int)e->h.n_domains, e->cur_lens,
-                       e->lens_all, e->norm_tiles ? e->norm_stats : nullptr, e->norm_tiles, e->norm_frames);
+                       e->lens_all, e->norm_tiles ? e->norm_stats : nullptr, e->norm_tiles, e->norm_frames,
+                       zero ? e->pair_flags : nullptr, zero ? e->pair_flag_bytes : 0);
   return rc ? fail(rc, "k_stem launch") : QASR_OK;
 }
 
@@ -962,7 +966,8 @@ static int enqueue_forward(qasr_engine* e, hipStream_t s, const FrontArgs* fe, b
   // the flag words of every paired op, zero before the first kernel: one node per forward.  A kernel, not hipMemsetAsync: as a
   // memset node of the captured graph the zeroing was not in place for every paired launch of back-to-back replays (a few
   // tokens differed from the serial result, no spin timed out: flags of the previous replay were still seen set)
-  if (e->pair_flags && launch_pair_zero(s, e->pair_flags, e->pair_flag_bytes)) return fail(QASR_ERR_ARG, "forward: k_pair_zero");
+  // With the fused stem there is no node of its own: k_stem, the first kernel of the ops, zeroes them (stem_launch)
+  if (e->pair_flags && !e->stem && launch_pair_zero(s, e->pair_flags, e->pair_flag_bytes)) return fail(QASR_ERR_ARG, "forward: k_pair_zero");
   struct InForward {
     qasr_engine* e;
     explicit InForward(qasr_engine* e_) : e(e_) { e->in_forward = true; }
@@ -2267,6 +2272,16 @@ int qasr_engine_pair_timeouts(qasr_engine* e) {
   HIPCHK(hipMemcpy(&v, e->pair_x, sizeof v, hipMemcpyDeviceToHost));
   if (v) HIPCHK(hipMemset(e->pair_x, 0, sizeof v));
   return (int)std::min(v, 0x7fffffffu);
+}
+
+int qasr_engine_pair_flag_words(const qasr_engine* e, uint32_t* out, size_t n) {
+  if (!e) return -1;
+  const size_t have = e->pair_flags ? e->pair_flag_bytes / sizeof(uint32_t) : 0;
+  if (!out || n == 0 || have == 0) return (int)std::min(have, (size_t)0x7fffffff);
+  HIPCHK(hipSetDevice(e->device));
+  HIPCHK(hipDeviceSynchronize());
+  HIPCHK(hipMemcpy(out, e->pair_flags, std::min(n, have) * sizeof(uint32_t), hipMemcpyDeviceToHost));
+  return (int)std::min(have, (size_t)0x7fffffff);
 }
 
 size_t qasr_sep_pair_workspace_bytes(int B, int Tp) {

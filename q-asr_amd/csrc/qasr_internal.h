@@ -134,8 +134,11 @@ void launch_logsoftmax(hipStream_t s, const float* logits, float* logp, int32_t*
 // qasr_stem.hip: lengths + first-layer QuantAct + strided depthwise conv + 1x1 conv of block 0 as one launch
 bool stem_supported(const QuantInP& qi, const DwP& dw, const SepP& pw);
 // stats != nullptr: x holds un-normalised log-mel and normalize_batch runs inside (per-tile sums from frontend_mel_stats)
+// pair_flags != nullptr: the launch also zeroes these flag words of the forward's paired ops (16-byte granules), in place of a
+// k_pair_zero node
 int launch_stem(hipStream_t s, const QuantInP& qi, const DwP& dw, const SepP& pw, const qasr_domain_desc* doms, int n_domains,
-                const int32_t* lens_in, int32_t* lens_all, const double* stats = nullptr, int n_stat_tiles = 0, int n_frames = 0);
+                const int32_t* lens_in, int32_t* lens_all, const double* stats = nullptr, int n_stat_tiles = 0, int n_frames = 0,
+                unsigned* pair_flags = nullptr, size_t pair_flag_bytes = 0);
 // qasr_frontend.hip: k_mel alone (un-normalised log-mel, feat_lens, per-tile statistics [B][tiles][n_mels][2] f64)
 #define QASR_MEL_TILE 16
 size_t frontend_stats_bytes(int B, int S, int n_mels);

@@ -61,6 +61,9 @@ typedef v4i __attribute__((address_space(3))) lds_v4i;
 #ifndef SEP2_PSTAMP
 #define SEP2_PSTAMP 0                   /* 1 (profiling builds, profiles/phase_stamps.py --prologue): phase stamps inside the prologue */
 #endif
+#ifndef SEP2_PAIR_LDS
+#define SEP2_PAIR_LDS 1                 /* k_sep2p: the partner's half image is loaded straight into LDS; 0 = through registers (A/B) */
+#endif
 
 template <int K, int TT>
 struct Sep2Geo {
@@ -279,9 +282,9 @@ __device__ __forceinline__ void sep2_gemm_ks(v16i* __restrict__ acc, v4i (&wf)[1
 // Producer: every byte of the half image leaves as a write-through 16-byte store, each 128-byte line written whole by one
 // store instruction; every wave waits for its stores, the work-group meets at a barrier, one lane adds to the pair's flag
 // word (agent scope).  Consumer: one wave polls that word with write-through loads, a work-group barrier, then every load of
-// the partner's bytes is a write-through 16-byte load to registers - no cache holds a line of the exchange buffer on
-// either side, so neither a release nor an acquire fence is needed.  Flag words are zero before every launch (the
-// caller's k_pair_zero node); a spin gives up after SEP2_PAIR_SPIN ticks of the 100 MHz clock, sets the time-out word and carries
+// the partner's bytes is a write-through 16-byte load (SEP2_PAIR_LDS: straight into LDS; 0: to registers) - no cache holds a
+// line of the exchange buffer on either side, so neither a release nor an acquire fence is needed.  Flag words are zero before
+// every launch (the caller's k_pair_zero node, or k_stem in a forward with the fused stem); a spin gives up after SEP2_PAIR_SPIN ticks of the 100 MHz clock, sets the time-out word and carries
 // on with whatever the buffer holds (wrong and reported, never a hang).
 #define SEP2_PAIR_HALF 32768            /* bytes of a member's half image: 256 channels x 128 frames */
 #define SEP2_PAIR_SPIN 400000           /* 4 ms */
@@ -901,7 +904,7 @@ __device__ __forceinline__ void sep2_body(const SepP& p, const int b, const int 
       // more into two single-tile units - the only requantise + pack + store nothing hides is then one 32-frame tile (16 values
       // per lane, one 16-byte store) instead of two, and half as many bytes are outstanding when the wave ends.
       constexpr int MH = MT >= 2 ? MT / 2 : 1, NH = MT / MH;
-      constexpr bool SPLIT = SEP2_TAIL1 && MH == 2;
+      constexpr bool SPLIT = SEP2_TAIL1 && MH == 2 && !PAIR;   // (the paired form has its own unit order and no split: a SEP2_TAIL1 build leaves it as it is)
       constexpr int NUN0 = NP * NH, NUN = NUN0 + (SPLIT ? 1 : 0);
       const OutP& o0 = e.outs[0];
       const int olo = o0.lo, ohi = o0.hi;
@@ -977,7 +980,24 @@ __device__ __forceinline__ void sep2_body(const SepP& p, const int b, const int 
         STAMP2();                                            // published
         sep2_gemm_ks<2, 0, 8>(accs[0], wf, xd_lane, CIN_PAD * 32, none);
         sep2_pair_wait(p.pair_flags + 2 * pair_id + (1 - hm), p.pair_tmo, wave, lane);
-        v4u pv[MT];                                          // the partner's half: channels 256..511 of the image
+        // the partner's half: channels 256..511 of the image.  SEP2_PAIR_LDS: 16-byte buffer loads straight into LDS (a wave's
+        // 64 granules of one instruction are contiguous there: base + 16 lane, which is what that form writes) - no trip
+        // through four register quads, no ds_write; the loads are waited for (vmcnt) in front of the barrier below
+#if SEP2_PAIR_LDS
+        {
+          const auto rs = __builtin_amdgcn_make_buffer_rsrc(p.pair_x + ((size_t)pair_id * 2 + (1 - hm)) * SEP2_PAIR_HALF, 0, SEP2_PAIR_HALF, 0x00020000);
+#pragma unroll
+          for (int i = 0; i < MT; ++i)
+            __builtin_amdgcn_raw_ptr_buffer_load_lds(rs, (lds_v4u*)(Xd + i * (CIN_PAD * 32) + SEP2_PAIR_HALF / MT + wave * 1024), 16,
+                                                     i * (SEP2_PAIR_HALF / MT) + tid * 16, 0, 0, 16);   // sc1
+        }
+        __builtin_amdgcn_sched_barrier(0);
+        sep2_gemm_ks<2, 0, 8>(accs[1], wf, xd_lane + 2 * (CIN_PAD * 32), CIN_PAD * 32, none);
+        STAMP2();                                            // own-half GEMM (and the wait for the flag) done
+        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");     // this wave's share of the partner's half is in LDS
+        __syncthreads();
+#else
+        v4u pv[MT];
         {
           const auto rs = __builtin_amdgcn_make_buffer_rsrc(p.pair_x + ((size_t)pair_id * 2 + (1 - hm)) * SEP2_PAIR_HALF, 0, SEP2_PAIR_HALF, 0x00020000);
 #pragma unroll
@@ -989,6 +1009,7 @@ __device__ __forceinline__ void sep2_body(const SepP& p, const int b, const int 
 #pragma unroll
         for (int i = 0; i < MT; ++i) *(lds_v4u*)(Xd + i * (CIN_PAD * 32) + SEP2_PAIR_HALF / MT + tid * 16) = pv[i];
         __syncthreads();
+#endif
         STAMP2();                                            // fill done
         sep2_gemm_ks<2, 8, 8>(accs[0], wf, xd_lane, CIN_PAD * 32, none);
         unit_finish(accs[0], 0, 0, mh2{});

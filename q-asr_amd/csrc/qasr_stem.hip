@@ -50,6 +50,10 @@ struct StemP {
   // normalised already
   const double* stats;
   int n_stat_tiles, n_frames;
+  // flag words of the forward's paired ops (k_sep2p): zeroed here instead of by a k_pair_zero node of their
+  // own; nullptr: the caller zeroes them (or the plan has no paired op)
+  v4u* pair_zero;
+  int pair_zero_n;          // 16-byte granules
 };
 
 __device__ __forceinline__ int stem_out_len(int l, int kernel, int stride, int dilation, int padding) {
@@ -75,6 +79,13 @@ __global__ void __launch_bounds__(STEM_NT) k_stem(StemP p) {
                                                 (int)dd.padding);
       }
     }
+  }
+  // ---- flag words of the paired ops back to zero: one granule per thread over the first work-groups (a stride loop, so that a
+  // grid of any size covers them).  This launch lies behind the last paired kernel of the previous forward on the stream and
+  // ahead of the first one of this forward, as the k_pair_zero node did
+  if (p.pair_zero) {
+    const int wg = blockIdx.y * gridDim.x + blockIdx.x, nth = gridDim.x * gridDim.y * STEM_NT;
+    for (int g = wg * STEM_NT + tid; g < p.pair_zero_n; g += nth) p.pair_zero[g] = (v4u){0u, 0u, 0u, 0u};
   }
   const int len_in = p.lens_in[b];
   const int len_mid = stem_out_len(len_in, p.K, 2, 1, p.padding);
@@ -255,9 +266,11 @@ bool stem_supported(const QuantInP& qi, const DwP& dw, const SepP& pw) {
 }
 
 int launch_stem(hipStream_t s, const QuantInP& qi, const DwP& dw, const SepP& pw, const qasr_domain_desc* doms, int n_domains,
-                const int32_t* lens_in, int32_t* lens_all, const double* stats, int n_stat_tiles, int n_frames) {
+                const int32_t* lens_in, int32_t* lens_all, const double* stats, int n_stat_tiles, int n_frames,
+                unsigned* pair_flags, size_t pair_flag_bytes) {
   const EpiP& e = pw.e;
   if (!stem_supported(qi, dw, pw) || !qi.x || !lens_in || !lens_all || !doms) return QASR_ERR_UNSUPPORTED;
+  if (pair_flags && (!pair_flag_bytes || pair_flag_bytes % 16 || pair_flag_bytes / 16 > 0x7fffffffu)) return QASR_ERR_ARG;
   StemP p{};
   p.x = qi.x, p.lens_in = lens_in, p.inv_scale = qi.inv_scale, p.qlo = qi.lo, p.qhi = qi.hi, p.C = qi.C, p.Tx = qi.T;
   p.wdw = dw.w, p.bias_dw = dw.bias, p.m_dw = dw.e.outs[0].mtab, p.sb_dw = dw.e.sb, p.flags_dw = dw.e.flags;
@@ -267,6 +280,7 @@ int launch_stem(hipStream_t s, const QuantInP& qi, const DwP& dw, const SepP& pw
   p.e = e;
   p.doms = doms, p.n_domains = n_domains, p.lens_all = lens_all;
   p.stats = stats, p.n_stat_tiles = n_stat_tiles, p.n_frames = n_frames;
+  p.pair_zero = (v4u*)pair_flags, p.pair_zero_n = pair_flags ? (int)(pair_flag_bytes / 16) : 0;
   if (stats && (n_stat_tiles < 1 || n_frames < 1 || n_frames > qi.T)) return QASR_ERR_ARG;
   hipLaunchKernelGGL(k_stem, dim3(e.B, e.Tp / STEM_TT), dim3(STEM_NT), 0, s, p);
   return QASR_OK;

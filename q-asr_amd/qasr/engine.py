@@ -11,7 +11,7 @@ LIB_PATH = os.environ.get('QASR_LIB', os.path.join(HERE, 'libqasr_hip.so'))   # 
 
 SYMBOLS = ['qasr_blob_check', 'qasr_engine_create', 'qasr_engine_create_ex', 'qasr_engine_default_opts', 'qasr_engine_destroy', 'qasr_engine_forward', 'qasr_engine_forward_audio', 'qasr_engine_out_frames',
            'qasr_engine_num_ops', 'qasr_engine_num_launches', 'qasr_engine_read_acc', 'qasr_engine_read_tensor', 'qasr_engine_last_op_ms',
-           'qasr_engine_time_ops', 'qasr_engine_run_op', 'qasr_engine_op_label', 'qasr_engine_op_paired', 'qasr_engine_pair_timeouts',
+           'qasr_engine_time_ops', 'qasr_engine_run_op', 'qasr_engine_op_label', 'qasr_engine_op_paired', 'qasr_engine_pair_timeouts', 'qasr_engine_pair_flag_words',
            'qasr_sep_pair_workspace_bytes', 'qasr_sep_pair_timeout_offset',
            'qasr_frontend_mel', 'qasr_frontend_plan', 'qasr_frontend_mel_planned', 'qasr_frontend_frames',
            'qasr_frontend_workspace_bytes', 'qasr_pw_conv_acc',
@@ -134,6 +134,8 @@ def load_library():
     lib.qasr_engine_op_label.argtypes = [vp, i32, C.c_char_p, sz]
     lib.qasr_engine_op_paired.argtypes = [vp, i32]
     lib.qasr_engine_pair_timeouts.argtypes = [vp]
+    if hasattr(lib, 'qasr_engine_pair_flag_words'):   # (a QASR_LIB A/B build of an older tree lacks it)
+        lib.qasr_engine_pair_flag_words.argtypes = [vp, vp, sz]
     lib.qasr_sep_pair_workspace_bytes.argtypes = [i32, i32]
     lib.qasr_sep_pair_workspace_bytes.restype = sz
     lib.qasr_sep_pair_timeout_offset.argtypes = [i32, i32]
@@ -2094,6 +2096,17 @@ class Engine:
         if n < 0:
             raise QasrError('qasr_engine_pair_timeouts failed: ' + self.lib.qasr_last_error().decode())
         return n
+
+    def pair_flag_words(self):
+        """the flag words of the plan's paired ops as a numpy uint32 array (synchronises; empty without paired ops).  Read-only:
+        behind a forward every word of a pair that ran holds 1, because each forward zeroes them first"""
+        n = self.lib.qasr_engine_pair_flag_words(self._h, None, 0)
+        if n < 0:
+            raise QasrError('qasr_engine_pair_flag_words failed: ' + self.lib.qasr_last_error().decode())
+        out = np.zeros(n, dtype=np.uint32)
+        if n and self.lib.qasr_engine_pair_flag_words(self._h, out.ctypes.data_as(C.c_void_p), n) != n:
+            raise QasrError('qasr_engine_pair_flag_words failed: ' + self.lib.qasr_last_error().decode())
+        return out
 
     def run_op(self, op, stream=None):
         _check(self.lib.qasr_engine_run_op(self._h, _stream_ptr(stream), int(op)), 'qasr_engine_run_op')
