@@ -192,8 +192,8 @@ typedef struct qasr_engine_opts {
                                   reserved engine (qasr_engine_reserve), off otherwise - the never-taken branch costs the
                                   full-length step 0.14 - 0.28 us per launch */
   int32_t pair_split;          /* the plain 512 -> 512 separable layers of a tile_frames == 128 engine on work-group PAIRS (k_sep2p):
-                                  each member runs half the depthwise channels and one GEMM pass, the halves meet through an
-                                  exchange buffer inside the launch (same bytes, labels and launch count).
+                                  each member serves 64 of the tile's 128 frames over all channels with the 64-frame body, the
+                                  members exchange nothing (same bytes, labels and launch count).
                                   Default (-1): by the GPU_MAX_HW_QUEUES hint res_tile128 reads - on below 8 queues (two chains
                                   at a time), off from 8.  Never for debug / timing / reserved engines or other tiles.
                                   QASR_PAIR_SPLIT=0|1 is the A/B override */
@@ -1500,19 +1500,23 @@ typedef struct qasr_sep_layer_args {
   int32_t* racc;
   int32_t pair, pad_;          /* 1: the paired form (qasr_engine_opts.pair_split); QASR_ERR_UNSUPPORTED for a shape without one */
   void* pair_ws;               /* ... its workspace: 256-byte aligned device memory of qasr_sep_pair_workspace_bytes(B, Tp) bytes, */
-  size_t pair_ws_bytes;        /*     one per launch in flight; the u32 at qasr_sep_pair_timeout_offset counts spins that gave up */
+  size_t pair_ws_bytes;        /*     one per launch in flight.  Its head holds the members' completion counters (2 u32 per pair, zeroed
+                                      by the call; each member adds 1 at its end, nothing waits for them); the u32 at
+                                      qasr_sep_pair_timeout_offset, the time-out word of the former hand-off, is no longer written, and
+                                      nothing behind it is touched (the size is kept for callers that sized their buffers by it) */
 } qasr_sep_layer_args;
 int qasr_sep_layer(void* stream, const qasr_sep_layer_args* a, char* label, size_t label_cap);
 size_t qasr_sep_pair_workspace_bytes(int B, int Tp);
 size_t qasr_sep_pair_timeout_offset(int B, int Tp);
 /* 1 if op `op` of the current plan runs in the paired form, 0 if not, -1 for a bad argument (after a forward) */
 int qasr_engine_op_paired(const qasr_engine* e, int op);
-/* synchronises the device, returns how many hand-off spins of paired launches gave up since the last call (their results
- * are wrong; 0 in a healthy run) and clears the count */
+/* synchronises the device and reads the time-out word of paired launches.  Kept from the form whose members handed their
+ * halves over inside the launch: the members of a pair exchange nothing now, no kernel writes the word, the result is always 0 */
 int qasr_engine_pair_timeouts(qasr_engine* e);
 /* Diagnostics, read-only: the flag words of the plan's paired ops (2 per work-group pair and op, each op's padded to 256
- * bytes).  Returns how many words the engine has (0: no paired op, -1: error); with `out`, synchronises the device and copies
- * the first min(n, that many) words.  Behind a forward every word of a pair that ran holds 1: each forward zeroes them first. */
+ * bytes) - completion counters: each member of a pair adds 1 to its own word at its end, nothing waits for them.  Returns how
+ * many words the engine has (0: no paired op, -1: error); with `out`, synchronises the device and copies the first
+ * min(n, that many) words.  Behind a forward every word of a pair that ran holds 1: each forward zeroes them first. */
 int qasr_engine_pair_flag_words(const qasr_engine* e, uint32_t* out, size_t n);
 
 /* Diagnostics: when set to a device buffer of 32 int64, work-group (1,0,0) of every k_sep launch writes s_memtime

@@ -136,7 +136,7 @@ struct qasr_engine {
   std::vector<size_t> pair_flag_off;   // per op: byte offset of its flag words in pair_flags
   unsigned* pair_flags = nullptr;      // every paired op's flag words: an allocation of their own, zeroed once per forward (by k_stem, or by ONE k_pair_zero node without the fused stem)
   size_t pair_flag_bytes = 0;
-  unsigned char* pair_x = nullptr;     // [256 B: the time-out word][exchange buffer, B x tiles x 64 KiB, shared by all paired ops]
+  unsigned* pair_tmo = nullptr;        // 256 B: the time-out word of the former hand-off; no kernel writes it, qasr_engine_pair_timeouts reads 0
   bool in_forward = false;             // launch_op runs inside enqueue_forward (which zeroes the flags: k_pair_zero in front, or k_stem)
   // hipGraph replay (bit 4 of `debug`): the whole forward of one (shape, buffer set) is captured once and re-launched
   // with one call; key = the caller's pointers, which a serving loop keeps stable
@@ -233,8 +233,8 @@ static void free_plan(qasr_engine* e) {
   dev_free(e, e->pair_flags);
   e->pair_flags = nullptr;
   e->pair_flag_bytes = 0;
-  dev_free(e, e->pair_x);
-  e->pair_x = nullptr;
+  dev_free(e, e->pair_tmo);
+  e->pair_tmo = nullptr;
   e->paired.clear();
   e->pair_flag_off.clear();
   for (auto& v : e->acc_dbg)
@@ -381,7 +381,7 @@ static int plan_alloc(qasr_engine* e) {
   return QASR_OK;
 }
 
-// Which ops run in the paired form, and their exchange memory.  Never for debug / timing engines (hooks, per-op events), tiles
+// Which ops run in the paired form, and their completion words.  Never for debug / timing engines (hooks, per-op events), tiles
 // below 128, reserved engines (they do not come through build_plan); sep_pair_ok leaves only the production launches of
 // k_sep2<51 | 63 | 75, 4, 0, 2, false, 128, 1>.
 static int plan_pairs(qasr_engine* e) {
@@ -389,7 +389,7 @@ static int plan_pairs(qasr_engine* e) {
   if (!e->pair_split || e->debug || e->timing || !e->wide_tiles || !e->tile128 || e->rs.on) return QASR_OK;
   std::vector<char> paired(h.n_ops, 0);
   std::vector<size_t> off(h.n_ops, 0);
-  size_t fb = 0, xb = 0;
+  size_t fb = 0;
   for (uint32_t oi = 0; oi < h.n_ops; ++oi) {
     if (e->ops[oi].kind != QASR_OP_PW || e->skip[oi] || e->fused_dw[oi] < 0) continue;
     SepP p{};
@@ -398,13 +398,12 @@ static int plan_pairs(qasr_engine* e) {
     paired[oi] = 1;
     off[oi] = fb;
     fb += sep_pair_flag_bytes(p.e.B, p.e.Tp);
-    xb = std::max(xb, sep_pair_x_bytes(p.e.B, p.e.Tp));
   }
   if (!fb) return QASR_OK;
   HIPCHK(dev_alloc(e, (void**)&e->pair_flags, fb));
-  HIPCHK(dev_alloc(e, (void**)&e->pair_x, 256 + xb));
+  HIPCHK(dev_alloc(e, (void**)&e->pair_tmo, 256));
   HIPCHK(hipMemset(e->pair_flags, 0, fb));
-  HIPCHK(hipMemset(e->pair_x, 0, 256));
+  HIPCHK(hipMemset(e->pair_tmo, 0, 256));
   e->pair_flag_bytes = fb;
   e->paired.swap(paired);
   e->pair_flag_off.swap(off);
@@ -708,8 +707,6 @@ static void build_sep(qasr_engine* e, uint32_t oi, SepP& p) {
   if (!e->paired.empty() && e->paired[oi]) {
     p.pair = 1;
     p.pair_flags = (unsigned*)((unsigned char*)e->pair_flags + e->pair_flag_off[oi]);
-    p.pair_tmo = (unsigned*)e->pair_x;
-    p.pair_x = e->pair_x + 256;
   }
   fill_panes(e, oi, op, p.panes);
   fill_epi(e, oi, op, p.e);
@@ -2265,12 +2262,12 @@ int qasr_engine_op_paired(const qasr_engine* e, int op) {
 
 int qasr_engine_pair_timeouts(qasr_engine* e) {
   if (!e) return -1;
-  if (!e->pair_x) return 0;
+  if (!e->pair_tmo) return 0;
   unsigned v = 0;
   HIPCHK(hipSetDevice(e->device));
   HIPCHK(hipDeviceSynchronize());
-  HIPCHK(hipMemcpy(&v, e->pair_x, sizeof v, hipMemcpyDeviceToHost));
-  if (v) HIPCHK(hipMemset(e->pair_x, 0, sizeof v));
+  HIPCHK(hipMemcpy(&v, e->pair_tmo, sizeof v, hipMemcpyDeviceToHost));
+  if (v) HIPCHK(hipMemset(e->pair_tmo, 0, sizeof v));
   return (int)std::min(v, 0x7fffffffu);
 }
 
@@ -2520,8 +2517,6 @@ int qasr_sep_layer(void* stream, const qasr_sep_layer_args* a, char* label, size
     if (!a->pair_ws || ((uintptr_t)a->pair_ws & 255) || a->pair_ws_bytes < qasr_sep_pair_workspace_bytes(e.B, e.Tp))
       return fail(QASR_ERR_ARG, "sep_layer: pair_ws (256-byte aligned, qasr_sep_pair_workspace_bytes)");
     p.pair_flags = (unsigned*)a->pair_ws;
-    p.pair_tmo = (unsigned*)((unsigned char*)a->pair_ws + fb);
-    p.pair_x = (unsigned char*)a->pair_ws + fb + 256;
     if (launch_pair_zero((hipStream_t)stream, p.pair_flags, fb)) return fail(QASR_ERR_ARG, "sep_layer: k_pair_zero");   // flag words: zero before every launch
   }
   if (label && label_cap >= 8) sep_kernel_label(p, label, label_cap);

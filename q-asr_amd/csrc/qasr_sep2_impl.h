@@ -61,9 +61,6 @@ typedef v4i __attribute__((address_space(3))) lds_v4i;
 #ifndef SEP2_PSTAMP
 #define SEP2_PSTAMP 0                   /* 1 (profiling builds, profiles/phase_stamps.py --prologue): phase stamps inside the prologue */
 #endif
-#ifndef SEP2_PAIR_LDS
-#define SEP2_PAIR_LDS 1                 /* k_sep2p: the partner's half image is loaded straight into LDS; 0 = through registers (A/B) */
-#endif
 
 template <int K, int TT>
 struct Sep2Geo {
@@ -254,61 +251,15 @@ __device__ __forceinline__ void sep2_gemm_cb(v16i* __restrict__ acc, v4i (&wf)[1
   });
 }
 
-// K steps [J0, J0 + NJ) of a GEMM unit on the register-resident slab, one slice of other work behind every MFMA
-// (sep2_gemm_cb with a K range and no slab re-request: the paired form multiplies each half of the image on its own)
-template <int MT, int J0, int NJ, class CB>
-__device__ __forceinline__ void sep2_gemm_ks(v16i* __restrict__ acc, v4i (&wf)[16], const lds_u8* img_lane, int mt_stride, CB&& cb) {
-  v4i a[2][MT];
-#pragma unroll
-  for (int mt = 0; mt < MT; ++mt) a[0][mt] = sep2_a_frag(img_lane + mt * mt_stride, J0);
-  sep2_for<0, NJ>([&](auto qc) {
-    constexpr int q = decltype(qc)::value;
-    if constexpr (q + 1 < NJ) {
-#pragma unroll
-      for (int mt = 0; mt < MT; ++mt) a[(q + 1) & 1][mt] = sep2_a_frag(img_lane + mt * mt_stride, J0 + q + 1);
-    }
-    sep2_for<0, MT>([&](auto mc) {
-      constexpr int mt = decltype(mc)::value;
-      acc[mt] = __builtin_amdgcn_mfma_i32_32x32x32_i8(a[q & 1][mt], wf[J0 + q], acc[mt], 0, 0, 0);
-      __builtin_amdgcn_sched_barrier(0);
-      cb(std::integral_constant<int, q * MT + mt>{});
-      __builtin_amdgcn_sched_barrier(0);
-    });
-    __builtin_amdgcn_sched_barrier(0);
-  });
-}
-
-// ---- hand-off between the two work-groups of a pair (k_sep2p) -----------------------------------------------------
-// Producer: every byte of the half image leaves as a write-through 16-byte store, each 128-byte line written whole by one
-// store instruction; every wave waits for its stores, the work-group meets at a barrier, one lane adds to the pair's flag
-// word (agent scope).  Consumer: one wave polls that word with write-through loads, a work-group barrier, then every load of
-// the partner's bytes is a write-through 16-byte load (SEP2_PAIR_LDS: straight into LDS; 0: to registers) - no cache holds a
-// line of the exchange buffer on either side, so neither a release nor an acquire fence is needed.  Flag words are zero before
-// every launch (the caller's k_pair_zero node, or k_stem in a forward with the fused stem); a spin gives up after SEP2_PAIR_SPIN ticks of the 100 MHz clock, sets the time-out word and carries
-// on with whatever the buffer holds (wrong and reported, never a hang).
-#define SEP2_PAIR_HALF 32768            /* bytes of a member's half image: 256 channels x 128 frames */
-#define SEP2_PAIR_SPIN 400000           /* 4 ms */
+// ---- completion counters of a pair (k_sep2p) --------------------------------------------------------------------
+// The two members of a pair serve disjoint halves of the tile's frames and exchange nothing.  What is left of
+// the former in-launch hand-off is one word per member: zero before every launch (the caller's k_pair_zero node, or k_stem
+// in a forward with the fused stem), and the member adds 1 to it once, at its end.  Nothing waits for these words: they are
+// completion counters now, read back by the host (qasr_engine_pair_flag_words) - after a forward every word holds exactly 1.
 typedef unsigned v4u __attribute__((ext_vector_type(4)));
-typedef v4u __attribute__((address_space(3))) lds_v4u;
 typedef unsigned __attribute__((address_space(1))) glb_u32;
 __device__ __forceinline__ void sep2_pair_signal(unsigned* flag, int tid) {
-  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");           // every storing wave
-  __syncthreads();
   if (tid == 0) (void)__hip_atomic_fetch_add((glb_u32*)flag, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-}
-__device__ __forceinline__ void sep2_pair_wait(unsigned* flag, unsigned* tmo, int wave, int lane) {
-  if (wave == 0) {
-    const unsigned long long t_end = __builtin_amdgcn_s_memrealtime() + SEP2_PAIR_SPIN;
-    while (__hip_atomic_load((glb_u32*)flag, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == 0u) {
-      __builtin_amdgcn_s_sleep(2);
-      if (__builtin_amdgcn_s_memrealtime() > t_end) {
-        if (lane == 0) (void)__hip_atomic_fetch_add((glb_u32*)tmo, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        break;
-      }
-    }
-  }
-  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");     // (no instruction: the loads below stay below the poll)
-  __syncthreads();
 }
 
 // per-lane (= per output channel, MFMA C layout: channel = lane & 31) parameters of one 256-channel pass
@@ -350,25 +301,18 @@ __device__ __forceinline__ void sep2_args_round(const SepP& p) {
 // SKIP (k_sep2s, reserved engines / qasr_engine_opts.mask_skip): the mask-skip rule of DESIGN 5.3e.  It is a separate set of
 // instantiations because the branch alone - never taken at full length - costs k_sep2 0.14 - 0.28 us per launch (the code the
 // compiler emits for the main path moves); SKIP = false is the kernel as it was.
-// PAIR (k_sep2p): the tile is served by two work-groups.  Member hm runs the depthwise stage of input channels
-// [256 hm, 256 hm + 256) only - its codes are channels 0..255 of ITS A image - and GEMM pass hm only, over all 512 input
-// channels: the partner's codes arrive through the exchange buffer (sep2_pair_*) as channels 256..511 of the image.  The
-// weight slab is loaded in the same rotated K order, so register j of the slab always meets K step j of the image.
-template <int K, int NG, int NGP, int NP, bool DBG, int TT, int DIL = 1, bool SKIP = false, bool PAIR = false>
-__device__ __forceinline__ void sep2_body(const SepP& p, const int b, const int t0, const bool stamp_wg, const int wg_id,
-                                          const int hm = 0, const int pair_id = 0) {
+// ROUND = false (k_sep2p): the caller has issued the kernel arguments' round (sep2_args_round) itself, in front of
+// its own look at B and Tp; the body does not issue a second one.
+template <int K, int NG, int NGP, int NP, bool DBG, int TT, int DIL = 1, bool SKIP = false, bool ROUND = true>
+__device__ __forceinline__ void sep2_body(const SepP& p, const int b, const int t0, const bool stamp_wg, const int wg_id) {
   using G = Sep2Geo<K, TT / DIL>;
   constexpr bool RES = NGP > 0;
-  static_assert(!PAIR || (K > 0 && NG == 4 && NGP == 0 && NP == 2 && !DBG && TT == 128 && DIL == 1 && !SKIP),
-                "paired form: the plain 512 -> 512 layers at 128 frames");
-  constexpr int NPL = PAIR ? 1 : NP;                         // GEMM passes of this work-group
-  const int cbase = PAIR ? 256 * hm : 0;                     // first input channel of its depthwise stage = first output channel
   static_assert(DIL == 1 || (DIL == 2 && !RES && TT >= 64), "dilation 2: plain layers, 64- / 128-frame tiles");
   constexpr int MT = TT / 32;
   constexpr int NU = G::NU, S = G::S, NS = G::NS;
   constexpr int CIN_PAD = 128 * NG, PCIN_PAD = 128 * NGP;
   constexpr int RCH = 16 / DIL, GCH = SEP2_CH / DIL;         // real channels per wave / per work-group in one depthwise group
-  constexpr int NCHUNK = PAIR ? 2 : (CIN_PAD + GCH - 1) / GCH;
+  constexpr int NCHUNK = (CIN_PAD + GCH - 1) / GCH;
   // staging granules of a wave and group: DIL 1: 16 rows x NPG granules of the row itself; DIL 2: RCH real channels x the
   // granules of the REAL window [t0 - 2 HALO, t0 + TT + 2 HALO) (each splits into 8 even + 8 odd bytes); tap rows: RCH x KS bytes
   constexpr int NPGR = DIL == 1 ? G::NPG : (TT + 2 * DIL * G::HALO) / 16;
@@ -400,7 +344,7 @@ __device__ __forceinline__ void sep2_body(const SepP& p, const int b, const int 
   // the prologue order of DESIGN.md 5.8.  The mask-skip instantiations keep the order before: reordered, two of them took one
   // and two registers more, and no phase stamp of a reserved engine's launch says what they would gain
   constexpr bool EARLY = SEP2_EARLY && !SKIP;
-  if constexpr (EARLY && !DBG && !PAIR) sep2_args_round<(NGP > 0)>(p);   // (k_sep2p has called it in front of its look at B and Tp)
+  if constexpr (EARLY && !DBG && ROUND) sep2_args_round<(NGP > 0)>(p);   // (k_sep2p has called it in front of its look at B and Tp)
   // lens[b] is a global load behind a pointer from the kernel arguments, and only the masks need it.  Requested here and
   // consumed here, the wave waited for it (s_waitcnt vmcnt(0)) before it computed the first address of group 0; SEP2_EARLY
   // consumes it behind every request of the prologue (len_use)
@@ -450,10 +394,7 @@ __device__ __forceinline__ void sep2_body(const SepP& p, const int b, const int 
   constexpr int NRT = RES ? (TT * PCIN_PAD / 16) / SEP2_NT : 0;
   v4i pc[NPT], pt[NTT], rr[NRT > 0 ? NRT : 1], wf[16];
   const int co_l = 32 * wave + (lane & 31);                  // row inside a 256-channel pass
-  const v4i* const w0 = w_frag(p.w, CIN_PAD, cbase + co_l, 0);
-  // (PAIR) slab register j holds K step (j + 8 hm) & 15: the member's own 8 steps first
-  const v4i* const w0a = PAIR ? w0 + 64 * 8 * hm : w0;
-  const v4i* const w0b = PAIR ? w0 + 64 * 8 * (1 - hm) - 64 * 8 : w0;
+  const v4i* const w0 = w_frag(p.w, CIN_PAD, co_l, 0);
   // window + tap rows of this wave's 16 channels of group g (channels 128 g + 16 wave ..): 16-B granules, lane-contiguous.
   // Everything per lane is the same for every group and computed once - byte offsets of its granules from the group's
   // (wave-uniform) row 0, zero-padding masks, LDS addresses: a group's staging is loads, one bit-op per dword, stores
@@ -482,7 +423,7 @@ __device__ __forceinline__ void sep2_body(const SepP& p, const int b, const int 
   }
   SEP2_LANE_CONSTS(true, !EARLY)
   auto ld_grp = [&](int g) {
-    const int cw = cbase + GCH * g + RCH * wave;             // (wave-uniform: the bases below are scalar)
+    const int cw = GCH * g + RCH * wave;                     // (wave-uniform: the bases below are scalar)
     const int8_t* const xg = p.x + ((size_t)b * CIN_PAD + cw) * eTp;
     const unsigned char* const tg = (const unsigned char*)p.wdw2 + (size_t)cw * G::KS;   // zero-margined tap rows [C][KS]
 #pragma unroll
@@ -499,7 +440,7 @@ __device__ __forceinline__ void sep2_body(const SepP& p, const int b, const int 
   };
   // request list of depthwise group CH besides the next group's operands: [residual operand, last group] [this group's
   // share of the weight slab of GEMM pass 0]
-  constexpr int SLC = NCHUNK >= 4 ? 3 : PAIR ? 2 : 1;        // groups the slab's requests are spread over
+  constexpr int SLC = NCHUNK >= 4 ? 3 : 1;                   // groups the slab's requests are spread over
   auto pf = [&](auto chc, int lo, int hi) {
     constexpr int CH = decltype(chc)::value;
     constexpr int n_res = CH + 1 == NCHUNK ? NRT : 0;
@@ -507,7 +448,7 @@ __device__ __forceinline__ void sep2_body(const SepP& p, const int b, const int 
 #pragma unroll
     for (int i = lo; i < hi; ++i) {
       if (i < n_res) ld_res(i);
-      else if (i < n_res + n_slab) wf[s0 + i - n_res] = (s0 + i - n_res < 8 ? w0a : w0b)[64 * (s0 + i - n_res)];
+      else if (i < n_res + n_slab) wf[s0 + i - n_res] = w0[64 * (s0 + i - n_res)];
     }
   };
   auto commit = [&]() {                                      // registers -> this wave's LDS rows
@@ -567,7 +508,7 @@ __device__ __forceinline__ void sep2_body(const SepP& p, const int b, const int 
   if constexpr (K > 0) {
 #pragma unroll
     for (int gi = 0; gi < NCHUNK; ++gi) {
-      const int c = cbase + GCH * gi + RCH * wave + cb / DIL;   // a wave owns 16 / DIL channels of every chunk
+      const int c = GCH * gi + RCH * wave + cb / DIL;   // a wave owns 16 / DIL channels of every chunk
       dbias[gi] = p.bias_dw[c];
       dM[gi] = p.m_dw[c];
     }
@@ -580,11 +521,11 @@ __device__ __forceinline__ void sep2_body(const SepP& p, const int b, const int 
     len_use();
   }
   PSTAMP2(2, false);                                         // depthwise parameters requested
-  Sep2PassP pps[NPL];
+  Sep2PassP pps[NP];
   auto load_pps = [&]() {                                    // (issued behind the first group's operands: not on the way
 #pragma unroll                                               //  to the first MFMA)
-  for (int ps = 0; ps < NPL; ++ps) {
-    const int cor = cbase + 256 * ps + co_l;
+  for (int ps = 0; ps < NP; ++ps) {
+    const int cor = 256 * ps + co_l;
     Sep2PassP& q = pps[ps];
     q.bias = p.bias[cor];
     if constexpr (RES) {
@@ -850,17 +791,6 @@ __device__ __forceinline__ void sep2_body(const SepP& p, const int b, const int 
   static_assert(NCHUNK <= 4 * DIL, "more than 512 input channels");
   if ((tune & 5) == 1) __builtin_amdgcn_s_setprio(0);        // (tune & 4: the priority stays through the GEMM passes)
   __syncthreads();                                           // Xd complete, windows dead
-  if constexpr (PAIR) {
-    // publish this member's half of the image (channels 0..255 of the four frame tiles, 4 x 8 KiB) in the image's own layout:
-    // write-through 16-byte stores, a wave instruction writes 1 KiB = eight whole 128-byte lines.  They drain behind the
-    // own-half GEMM; the flag follows there (sep2_pair_signal)
-    const auto rs = __builtin_amdgcn_make_buffer_rsrc(p.pair_x + ((size_t)pair_id * 2 + hm) * SEP2_PAIR_HALF, 0, SEP2_PAIR_HALF, 0x00020000);
-#pragma unroll
-    for (int i = 0; i < MT; ++i) {
-      const v4u v = *(const lds_v4u*)(Xd + i * (CIN_PAD * 32) + tid * 16);
-      __builtin_amdgcn_raw_buffer_store_b128(v, rs, i * (SEP2_PAIR_HALF / MT) + tid * 16, 0, 16);   // aux 16 = sc1
-    }
-  }
   if constexpr (DIL == 2) {
     if (t0 + TT > dlim) {                                    // (uniform) MaskedConv1d of the 1x1 conv: frames >= len are code 0
       for (int r = tid; r < MT * CIN_PAD; r += SEP2_NT) {
@@ -897,14 +827,13 @@ __device__ __forceinline__ void sep2_body(const SepP& p, const int b, const int 
   // the epilogue is VALU work (fp64 fma + med3 per value), the GEMM matrix-pipe work, and a work-group's phases are
   // otherwise serial.  Only the first GEMM unit and the last unit's epilogue stay exposed.
   constexpr bool PIPED = !RES && (NP * (MT >= 2 ? 2 : 1) > 1);
-  static_assert(!PAIR || PIPED, "paired form: the pipelined epilogue");   // (sep2_shape_ok: plain layers have exactly one consumer)
   if constexpr (PIPED) {
     {
       // Units: a pass is split into NH units of MH frame tiles each.  SEP2_TAIL1: the LAST unit of the last pass is split once
       // more into two single-tile units - the only requantise + pack + store nothing hides is then one 32-frame tile (16 values
       // per lane, one 16-byte store) instead of two, and half as many bytes are outstanding when the wave ends.
       constexpr int MH = MT >= 2 ? MT / 2 : 1, NH = MT / MH;
-      constexpr bool SPLIT = SEP2_TAIL1 && MH == 2 && !PAIR;   // (the paired form has its own unit order and no split: a SEP2_TAIL1 build leaves it as it is)
+      constexpr bool SPLIT = SEP2_TAIL1 && MH == 2;
       constexpr int NUN0 = NP * NH, NUN = NUN0 + (SPLIT ? 1 : 0);
       const OutP& o0 = e.outs[0];
       const int olo = o0.lo, ohi = o0.hi;
@@ -915,7 +844,7 @@ __device__ __forceinline__ void sep2_body(const SepP& p, const int b, const int 
       // accumulator hooks and EXACT_Z of a finished unit (tiles mt0 .. mt0 + mh - 1 of pass ps)
       auto unit_finish = [&](v16i* a, int ps, int mt0, auto mhc) __attribute__((always_inline)) {
         constexpr int mh = decltype(mhc)::value;
-        const int co = cbase + 256 * ps + co_l;
+        const int co = 256 * ps + co_l;
         if (DBG && e.acc_dbg) {
 #pragma unroll
           for (int mt = 0; mt < mh; ++mt)
@@ -954,7 +883,7 @@ __device__ __forceinline__ void sep2_body(const SepP& p, const int b, const int 
             const auto s13 = __builtin_amdgcn_permlane32_swap(P[1], P[3], false, false);
             v4i pk = {(int)s02[0], (int)s02[1], (int)s13[0], (int)s13[1]};
             if (t0 + 32 * (mt0 + mt + 1) > lim) pk = sep2_mask16(pk, lim - (t0 + 32 * (mt0 + mt) + 16 * h));   // (uniform)
-            *(v4i*)(optr + ((size_t)b * ecout + cbase + 256 * ps + co_l) * eTp + t0 + 32 * (mt0 + mt) + 16 * h) = pk;
+            *(v4i*)(optr + ((size_t)b * ecout + 256 * ps + co_l) * eTp + t0 + 32 * (mt0 + mt) + 16 * h) = pk;
           }
         });
       };
@@ -962,66 +891,6 @@ __device__ __forceinline__ void sep2_body(const SepP& p, const int b, const int 
       auto u_ps = [](int u) constexpr { return u < NUN0 ? u / NH : NP - 1; };
       auto u_mh = [](int u) constexpr { return (SPLIT && u >= NUN0 - 1) ? 1 : MH; };
       auto u_mt0 = [](int u) constexpr { return u < NUN0 ? (u % NH) * MH : (NH - 1) * MH + 1; };
-      if constexpr (PAIR) {
-        // one pass, two units of two frame tiles, both accumulator sets live: the K steps of the member's own channels for
-        // both units, the hand-off, then the partner's K steps - unit 0's requantisation behind unit 1's second half
-        static_assert(MH == 2 && NH == 2 && !SPLIT, "paired form: two units of two tiles");
-        using mh2 = std::integral_constant<int, 2>;
-#pragma unroll
-        for (int un = 0; un < 2; ++un)
-#pragma unroll
-          for (int mt = 0; mt < 2; ++mt)
-#pragma unroll
-            for (int r = 0; r < 16; ++r) accs[un][mt][r] = pps[0].bias;
-        auto none = [](auto) {};
-        // the flag goes out first (the stores were issued at the barrier above): its way to the partner hides behind unit 0's
-        // own K steps, the way of the partner's bytes into registers behind unit 1's
-        sep2_pair_signal(p.pair_flags + 2 * pair_id + hm, tid);
-        STAMP2();                                            // published
-        sep2_gemm_ks<2, 0, 8>(accs[0], wf, xd_lane, CIN_PAD * 32, none);
-        sep2_pair_wait(p.pair_flags + 2 * pair_id + (1 - hm), p.pair_tmo, wave, lane);
-        // the partner's half: channels 256..511 of the image.  SEP2_PAIR_LDS: 16-byte buffer loads straight into LDS (a wave's
-        // 64 granules of one instruction are contiguous there: base + 16 lane, which is what that form writes) - no trip
-        // through four register quads, no ds_write; the loads are waited for (vmcnt) in front of the barrier below
-#if SEP2_PAIR_LDS
-        {
-          const auto rs = __builtin_amdgcn_make_buffer_rsrc(p.pair_x + ((size_t)pair_id * 2 + (1 - hm)) * SEP2_PAIR_HALF, 0, SEP2_PAIR_HALF, 0x00020000);
-#pragma unroll
-          for (int i = 0; i < MT; ++i)
-            __builtin_amdgcn_raw_ptr_buffer_load_lds(rs, (lds_v4u*)(Xd + i * (CIN_PAD * 32) + SEP2_PAIR_HALF / MT + wave * 1024), 16,
-                                                     i * (SEP2_PAIR_HALF / MT) + tid * 16, 0, 0, 16);   // sc1
-        }
-        __builtin_amdgcn_sched_barrier(0);
-        sep2_gemm_ks<2, 0, 8>(accs[1], wf, xd_lane + 2 * (CIN_PAD * 32), CIN_PAD * 32, none);
-        STAMP2();                                            // own-half GEMM (and the wait for the flag) done
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");     // this wave's share of the partner's half is in LDS
-        __syncthreads();
-#else
-        v4u pv[MT];
-        {
-          const auto rs = __builtin_amdgcn_make_buffer_rsrc(p.pair_x + ((size_t)pair_id * 2 + (1 - hm)) * SEP2_PAIR_HALF, 0, SEP2_PAIR_HALF, 0x00020000);
-#pragma unroll
-          for (int i = 0; i < MT; ++i) pv[i] = __builtin_amdgcn_raw_buffer_load_b128(rs, i * (SEP2_PAIR_HALF / MT) + tid * 16, 0, 16);   // sc1
-        }
-        __builtin_amdgcn_sched_barrier(0);
-        sep2_gemm_ks<2, 0, 8>(accs[1], wf, xd_lane + 2 * (CIN_PAD * 32), CIN_PAD * 32, none);
-        STAMP2();                                            // own-half GEMM (and the wait for the flag) done
-#pragma unroll
-        for (int i = 0; i < MT; ++i) *(lds_v4u*)(Xd + i * (CIN_PAD * 32) + SEP2_PAIR_HALF / MT + tid * 16) = pv[i];
-        __syncthreads();
-#endif
-        STAMP2();                                            // fill done
-        sep2_gemm_ks<2, 8, 8>(accs[0], wf, xd_lane, CIN_PAD * 32, none);
-        unit_finish(accs[0], 0, 0, mh2{});
-        sep2_gemm_ks<2, 8, 8>(accs[1], wf, xd_lane + 2 * (CIN_PAD * 32), CIN_PAD * 32, [&](auto qc) {
-          constexpr int q = decltype(qc)::value;             // 16 MFMA slots, 32 values
-          unit_values(accs[0], 0, 0, std::integral_constant<int, 2 * q>{}, std::integral_constant<int, 2 * q + 2>{});
-        });
-        STAMP2();                                            // second-half GEMM done
-        unit_finish(accs[1], 0, 2, mh2{});
-        unit_values(accs[1], 0, 2, std::integral_constant<int, 0>{}, std::integral_constant<int, 32>{});
-        STAMP2();
-      } else {
       sep2_for<0, NUN>([&](auto uc) {
         constexpr int u = decltype(uc)::value, ps = u_ps(u), mh = u_mh(u), mt0 = u_mt0(u);
         constexpr int AB = mh >= 2 ? 1 : 2, NSL = 4 * NG * mh;   // (AB: register budget at two tiles per unit)
@@ -1045,7 +914,6 @@ __device__ __forceinline__ void sep2_body(const SepP& p, const int b, const int 
       unit_finish(accs[(NUN - 1) & 1], NP - 1, u_mt0(NUN - 1), std::integral_constant<int, u_mh(NUN - 1)>{});
       unit_values(accs[(NUN - 1) & 1], NP - 1, u_mt0(NUN - 1), std::integral_constant<int, 0>{}, std::integral_constant<int, 16 * u_mh(NUN - 1)>{});
       STAMP2();
-      }
     }
   }
   if constexpr (!PIPED) {
@@ -1185,10 +1053,13 @@ __global__ void __launch_bounds__(SEP2_NT, SEP2_WPE) k_sep2s(SepP p) {
                                                   blockIdx.y * gridDim.x + blockIdx.x);
 }
 
-// the paired form of k_sep2<K, 4, 0, 2, false, 128, 1>.  Linear work-group id = 16 (P / 8) + 8 hm + P % 8 for member hm of pair
-// P = b + B t: the two members are 8 ids apart (the dispatcher deals ids round-robin over the 8 XCDs: same XCD, one right
-// behind the other) and utterance b stays on the XCD of the layer that produced it.  Speed only - the hand-off does not
-// depend on where or when a member runs; ids beyond the last pair leave at once.
+// the paired form of k_sep2<K, 4, 0, 2, false, 128, 1>: a 128-frame tile on two work-groups that split it by
+// FRAMES.  Member hm of pair P = b + B t serves frames [128 t + 64 hm, 128 t + 64 hm + 64) of utterance b over all 512 input and
+// output channels with the 64-frame body - four depthwise groups, both GEMM passes, that body's own length masks - and the
+// members exchange nothing.  Linear work-group id = 16 (P / 8) + 8 hm + P % 8: the two members are 8 ids apart (the dispatcher
+// deals ids round-robin over the 8 XCDs: same XCD, one right behind the other, so they share the weights and the halo between
+// them in its L2) and utterance b stays on the XCD of the layer that produced it.  Speed only; ids beyond the last pair leave
+// at once.  At its end a member counts itself in its completion word (sep2_pair_signal).
 template <int K>
 __global__ void __launch_bounds__(SEP2_NT, SEP2_WPE) k_sep2p(SepP p) {
   if constexpr (SEP2_EARLY) sep2_args_round<false>(p);
@@ -1196,7 +1067,8 @@ __global__ void __launch_bounds__(SEP2_NT, SEP2_WPE) k_sep2p(SepP p) {
   const int B = p.e.B;
   if (P >= B * (p.e.Tp / 128)) return;
   const int t = P / B, b = P - t * B;
-  sep2_body<K, 4, 0, 2, false, 128, 1, false, true>(p, b, t * 128, b == 0 && t == 1 && hm == 0, 2 * P + hm, hm, P);
+  sep2_body<K, 4, 0, 2, false, 64, 1, false, false>(p, b, t * 128 + 64 * hm, b == 0 && t == 1 && hm == 0, 2 * P + hm);
+  sep2_pair_signal(p.pair_flags + 2 * P + hm, threadIdx.x);
 }
 
 template <int K, int TT, int DIL = 1>
@@ -1267,19 +1139,21 @@ static inline bool sep2_pair_shape(const SepP& p) {
   return (p.K == 51 || p.K == 63 || p.K == 75) && p.dilation == 1 && p.cin_pad == 512 && p.e.cout == 512 && p.n_panes == 0 &&
          !(p.e.flags & QASR_F_RESADD) && p.e.Tp % 128 == 0;
 }
-// exchange workspace of one paired launch: flag words (2 per pair), then the half images
+// workspace of one paired launch: the members' completion words (2 per pair).  sep2_pair_x_bytes is the size of the exchange
+// buffer the hand-off form kept behind them (two 32 KiB half images per pair): no kernel touches it any more, the size only
+// keeps qasr_sep_pair_workspace_bytes what callers have sized their workspaces by
 static inline size_t sep2_pair_flag_bytes(int B, int Tp) { return ((size_t)B * (Tp / 128) * 2 * sizeof(unsigned) + 255) / 256 * 256; }
-static inline size_t sep2_pair_x_bytes(int B, int Tp) { return (size_t)B * (Tp / 128) * 2 * SEP2_PAIR_HALF; }
+static inline size_t sep2_pair_x_bytes(int B, int Tp) { return (size_t)B * (Tp / 128) * 2 * 32768; }
 
 template <int K>
 static int launch_sep2_pair_v(hipStream_t s, const SepP& p) {
-  const size_t smem = sep2_smem_bytes<K, 128, 1>(p);
-  if (smem > 160 * 1024 || p.e.B < 1 || p.e.Tp % 128 || !p.x || !p.w || !p.wdw2 || !p.pair_flags || !p.pair_tmo || !p.pair_x) return QASR_ERR_ARG;
+  const size_t smem = sep2_smem_bytes<K, 64, 1>(p);          // a member runs the 64-frame body
+  if (smem > 160 * 1024 || p.e.B < 1 || p.e.Tp % 128 || !p.x || !p.w || !p.wdw2 || !p.pair_flags) return QASR_ERR_ARG;
   static int attr_dev = -1;
   int dev = 0;
   (void)hipGetDevice(&dev);
   if (attr_dev != dev) {
-    (void)hipFuncSetAttribute((const void*)k_sep2p<K>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+    (void)hipFuncSetAttribute((const void*)k_sep2p<K>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem);   // (cin_pad == 512: one size)
     attr_dev = dev;
   }
   SepP q = p;

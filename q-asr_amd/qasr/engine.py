@@ -2091,7 +2091,7 @@ class Engine:
         return [self.lib.qasr_engine_op_paired(self._h, op) == 1 for op in range(self.n_ops)]
 
     def pair_timeouts(self):
-        """hand-off spins of paired launches that gave up since the last call (synchronises; 0 in a healthy run)"""
+        """the time-out word of paired launches (synchronises).  Always 0: the members of a pair exchange nothing any more"""
         n = self.lib.qasr_engine_pair_timeouts(self._h)
         if n < 0:
             raise QasrError('qasr_engine_pair_timeouts failed: ' + self.lib.qasr_last_error().decode())
@@ -2316,7 +2316,7 @@ def sep_pair_workspace(B, Tp, device):
 
 
 def sep_pair_timeouts(pair_ws, B, Tp):
-    """spins that gave up in the paired launches that used `pair_ws` (synchronises)"""
+    """the time-out word of the paired launches that used `pair_ws` (synchronises; no kernel writes it any more: 0)"""
     torch.cuda.synchronize()
     off = load_library().qasr_sep_pair_timeout_offset(int(B), int(Tp))
     return int(pair_ws[off:off + 4].view(torch.int32).item())
