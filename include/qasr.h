@@ -733,6 +733,60 @@ typedef struct qasr_ctc_spot_args {
 } qasr_ctc_spot_args;
 int qasr_ctc_spot(void* stream, const qasr_ctc_spot_args* args);
 
+/* ---- word and character error counts: edit distance over label ids -----------------------------------------------------------
+ * What word_error_rate (nemo/collections/asr/metrics/wer.py) computes on the host from strings, over the label rows where they
+ * lie on the device: hypothesis rows hyp i32 [B * K][hyp_pitch] (max_hyp ids each; hyp_lens i32 [B * K] or NULL) against
+ * reference rows ref i32 [B][ref_pitch] (max_ref ids each; ref_lens i32 [B] or NULL); a NULL length vector means the padded
+ * row, every id of it.  Problem p = b * K + k scores hypothesis row p against reference row b (K rows per reference: the beam's
+ * n-best layout); n_hyps i32 [B] (optional): rows k >= n_hyps[b] are absent.  mode QASR_EDIT_CHAR: a unit is one id;
+ * QASR_EDIT_WORD: a unit is a maximal run of ids c with is_space[c] == 0 (is_space u8 [C], the caller's
+ * vocabulary[c].isspace()); two words are equal when their id sequences are equal - length and a 64-bit hash are compared first
+ * and the ids are verified on a match.  Unit costs; D[0][j] = j deletions, D[i][0] = i insertions; among predecessors of equal
+ * cost the diagonal first, then the deletion (i, j - 1), then the insertion (i - 1, j); every cell carries (cost, S, D) of the
+ * path this picks.  The rules are EDIT_RULES of qasr/edit.py, which the kernels follow byte for byte.
+ *   rows i32 [B * K][8]: errors, S, D, I, ref_units, hyp_units, ok, 0.  ok = 1 scored; 2 an absent row; 0 a length outside
+ *   0 .. max_hyp (max_ref) or an id inside the length outside [0, C), in either row (rows are device data: the kernels check
+ *   them before any use).  Rows with ok != 1 hold 0 in every count.
+ *   totals i64 [16], which the call ADDS to (the caller zeroes it): [0] errors [1] ref_units [2] S [3] D [4] I [5] hyp_units
+ *   [6] rows, each over the rows with ok == 1 and k == 0; [7] the n-best oracle: over b, the smallest errors of b's rows with
+ *   ok == 1; [8] the number of rows with ok == 0; [9 .. 15] reserved, left as they are.
+ * Three launches on `stream`: k_edit_cut (one wave per row: checks, and in word mode the words as (start, len, hash) in the
+ * workspace), k_edit<MODE, NC> (one wave per problem, NC = 1 / 4 / 16 reference units per lane from max_ref, references wider
+ * than 64 * 16 units in consecutive strips) and k_edit_totals (one work-group; thread w writes totals[w]).  No atomics, plain
+ * vector stores, nothing allocated and nothing read on the host, so the call can be captured behind qasr_ctc_collapse or the
+ * beam kernels and replayed.  workspace: 16-byte aligned device memory of qasr_edit_workspace_bytes(B * K, max_hyp, max_ref,
+ * mode) bytes (0: a shape the call refuses), one per call in flight.
+ * QASR_ERR_ARG with nothing launched and nothing written: an unknown struct_size, a NULL among hyp, ref, rows, totals and
+ * workspace, a mode other than the two, is_space NULL in word mode, B, K or C < 1, B * K above QASR_EDIT_MAX_PROBLEMS, max_hyp or
+ * max_ref outside 1 .. QASR_EDIT_MAX_IDS, hyp_pitch < max_hyp, ref_pitch < max_ref, workspace_bytes below the query, a
+ * workspace or rows not 16-byte aligned, totals not 8-byte aligned. */
+#define QASR_EDIT_CHAR 0
+#define QASR_EDIT_WORD 1
+#define QASR_EDIT_MAX_IDS (1 << 20)
+#define QASR_EDIT_MAX_PROBLEMS (1 << 24)
+#define QASR_EDIT_ROW_WORDS 8
+#define QASR_EDIT_TOTAL_WORDS 16
+typedef struct qasr_edit_args {
+  uint32_t struct_size;        /* sizeof of this struct in the caller's header */
+  int32_t mode;                /* QASR_EDIT_CHAR / QASR_EDIT_WORD */
+  int32_t B, K, C;             /* references, hypothesis rows per reference, classes */
+  int32_t max_hyp, max_ref;    /* ids per row */
+  int32_t pad_;
+  int64_t hyp_pitch, ref_pitch;   /* in int32 */
+  const int32_t* hyp;          /* [B * K][hyp_pitch] */
+  const int32_t* hyp_lens;     /* optional [B * K] */
+  const int32_t* ref;          /* [B][ref_pitch] */
+  const int32_t* ref_lens;     /* optional [B] */
+  const int32_t* n_hyps;       /* optional [B] */
+  const uint8_t* is_space;     /* [C]; word mode */
+  int32_t* rows;               /* [B * K][8] */
+  int64_t* totals;             /* [16] */
+  void* workspace;
+  size_t workspace_bytes;
+} qasr_edit_args;
+size_t qasr_edit_workspace_bytes(int P, int max_hyp, int max_ref, int mode);
+int qasr_edit_distance(void* stream, const qasr_edit_args* args);
+
 /* ---- audio at any sample rate: rational polyphase resampler and PCM ingest -----------------------------------------------
  * What AudioSegment.__init__ does on the host with librosa.core.resample when target_sr != sample_rate (parts/segment.py:
  * 57-59), as one kernel, k_resample, in front of the mel front-end: int16 PCM (mono or interleaved channels) or float32 at an

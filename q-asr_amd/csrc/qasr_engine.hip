@@ -1506,6 +1506,37 @@ int qasr_ctc_spot(void* stream, const qasr_ctc_spot_args* a) {
   return launched("ctc_spot", launch_spot((hipStream_t)stream, *a));
 }
 
+// ---- word and character error counts (k_edit_cut, k_edit, k_edit_totals, qasr_edit.hip): the checks of include/qasr.h, then
+// three launches
+static bool edit_shape_ok(long long P, int max_hyp, int max_ref, int mode) {
+  return P >= 1 && P <= QASR_EDIT_MAX_PROBLEMS && max_hyp >= 1 && max_hyp <= QASR_EDIT_MAX_IDS && max_ref >= 1 &&
+         max_ref <= QASR_EDIT_MAX_IDS && (mode == QASR_EDIT_CHAR || mode == QASR_EDIT_WORD);
+}
+size_t qasr_edit_workspace_bytes(int P, int max_hyp, int max_ref, int mode) {
+  return edit_shape_ok(P, max_hyp, max_ref, mode) ? edit_workspace_bytes(P, max_hyp, max_ref, mode) : 0;
+}
+int qasr_edit_distance(void* stream, const qasr_edit_args* a) {
+  if (int rc = args_check("edit_distance", a)) return rc;
+  if (!a->hyp || !a->ref || !a->rows || !a->totals || !a->workspace)
+    return fail(QASR_ERR_ARG, "edit_distance: hyp, ref, rows, totals and workspace are required");
+  if (a->mode != QASR_EDIT_CHAR && a->mode != QASR_EDIT_WORD)
+    return fail(QASR_ERR_ARG, "edit_distance: mode %d is neither QASR_EDIT_CHAR nor QASR_EDIT_WORD", a->mode);
+  if (a->mode == QASR_EDIT_WORD && !a->is_space) return fail(QASR_ERR_ARG, "edit_distance: word mode needs is_space");
+  const long long P = (long long)a->B * a->K;
+  if (a->B < 1 || a->K < 1 || a->C < 1 || P > QASR_EDIT_MAX_PROBLEMS)
+    return fail(QASR_ERR_ARG, "edit_distance: B %d, K %d or C %d < 1, or B * K above %d", a->B, a->K, a->C, QASR_EDIT_MAX_PROBLEMS);
+  if (!edit_shape_ok(P, a->max_hyp, a->max_ref, a->mode))
+    return fail(QASR_ERR_ARG, "edit_distance: max_hyp %d or max_ref %d is outside 1 .. %d", a->max_hyp, a->max_ref, QASR_EDIT_MAX_IDS);
+  if (a->hyp_pitch < a->max_hyp || a->ref_pitch < a->max_ref)
+    return fail(QASR_ERR_ARG, "edit_distance: hyp_pitch %lld < max_hyp %d or ref_pitch %lld < max_ref %d", (long long)a->hyp_pitch,
+                a->max_hyp, (long long)a->ref_pitch, a->max_ref);
+  const size_t need = edit_workspace_bytes(P, a->max_hyp, a->max_ref, a->mode);
+  if (a->workspace_bytes < need) return fail(QASR_ERR_ARG, "edit_distance: workspace_bytes %zu < %zu", a->workspace_bytes, need);
+  if (((uintptr_t)a->workspace | (uintptr_t)a->rows) & 15 || (uintptr_t)a->totals & 7)
+    return fail(QASR_ERR_ARG, "edit_distance: workspace and rows must be 16-byte aligned, totals 8-byte aligned");
+  return launched("edit_distance", launch_edit((hipStream_t)stream, *a));
+}
+
 // ---- polyphase resampler (k_resample, qasr_resample.hip): host-only validation of a packed table (qasr/resample.py states
 // the layout), then the checks of include/qasr.h and one launch
 static long long gcd_ll(long long a, long long b) {

@@ -190,6 +190,9 @@ int launch_post_band(hipStream_t s, const qasr_ctc_post_band_args& a);
 int launch_star(hipStream_t s, const qasr_ctc_star_args& a);
 // qasr_spot.hip: keyword spotting (k_spot); the arguments are checked by qasr_ctc_spot
 int launch_spot(hipStream_t s, const qasr_ctc_spot_args& a);
+// qasr_edit.hip: word and character error counts (k_edit_cut, k_edit, k_edit_totals); checked by qasr_edit_distance
+size_t edit_workspace_bytes(long long P, int max_hyp, int max_ref, int mode);
+int launch_edit(hipStream_t s, const qasr_edit_args& a);
 // qasr_resample.hip: rational polyphase resampler (k_resample); the arguments are checked by qasr_resample
 int launch_resample(hipStream_t s, const qasr_resample_args& a);
 // qasr_longform.hip: windows of long recordings cut (k_cut) and stitched (k_stitch); the arguments are checked by the callers

@@ -34,6 +34,15 @@ if not torch.cuda.is_available():
 from qasr.calib_io import load_synthetic  # noqa: E402  (restricted loader for --load)
 
 
+def _add_report(counts, rep):
+    """--device_wer: an ErrorReport's total and oracle into the run's counts (errors, S, D, I, ref, hyp, oracle)"""
+    t = rep.total
+    if rep.invalid:
+        raise SystemExit(f'--device_wer: {rep.invalid} rows held an id outside the vocabulary')
+    for k, v in enumerate((t.errors, t.substitutions, t.deletions, t.insertions, t.ref_units, t.hyp_units, rep.oracle_errors)):
+        counts[k] += v
+
+
 def main():
     p = ArgumentParser()
     p.add_argument("--asr_model", type=str, default="QuartzNet15x5Base-En", required=True)
@@ -74,6 +83,15 @@ def main():
                         "--lm_path, and with --stream_chunk_s (one set for all streams, kept per stream across steps); --dump_hyps "
                         "gains `boost_score`")
     p.add_argument("--boost_weight", type=float, default=None, help="(extension, needs --boost_file) weight of the phrases without one, 0 .. 16 (default 1.0)")
+    p.add_argument("--device_wer", action='store_true',
+                   help="(extension) score on the device: the label rows go through the edit-distance kernel (k_edit) where they "
+                        "lie and only counts are read back per batch; WER is the number printed without the flag, a line "
+                        "`S / D / I:` is added and, with --beam_width W --n_best K, a line `oracle WER:` (the best of the K rows of "
+                        "every utterance).  With --stream_chunk_s or --window_s the hypotheses exist as strings and are scored "
+                        "through qasr.edit.error_counts.  --dump_hyps still reads the strings")
+    p.add_argument("--n_best", type=int, default=None, metavar='K',
+                   help="(extension, needs --device_wer and --beam_width) rows of the beam scored per utterance for `oracle WER:`")
+    p.add_argument("--cer", action='store_true', help="(extension) character error rate: WER is computed over characters")
     p.add_argument("--align", type=str, default=None, metavar='OUT',
                    help="(extension) forced alignment of every manifest line's reference text against its batch's "
                         "log-probabilities (EncDecCTCModel.align): OUT gets one JSON line per utterance - audio_filepath, text, "
@@ -179,6 +197,8 @@ def main():
         p.error(f'--spot_threshold must be -16 .. 0, got {args.spot_threshold}')
     if args.overlap_s is not None and args.window_s is None:
         p.error('--overlap_s needs --window_s')
+    if args.n_best is not None and (not args.device_wer or args.beam_width is None or not 1 <= args.n_best <= args.beam_width):
+        p.error('--n_best K needs --device_wer and --beam_width W, 1 <= K <= W')
     if args.star_token is not None and (args.align is None or args.shuffle):
         p.error('--star_token needs --align and does not go with --shuffle: the texts are read from the manifest in order')
     if args.star_between and (args.align is None or args.window_s is None):
@@ -274,6 +294,9 @@ def main():
         asr_model.reserve(args.batch_size, args.reserve)
     labels_map = dict(enumerate(asr_model.decoder.vocabulary))
     wer = WER(vocabulary=asr_model.decoder.vocabulary)
+    dev_wer = WER(vocabulary=asr_model.decoder.vocabulary, use_cer=args.cer, device=True) if args.device_wer else None
+    dev_counts = [0] * 7                                     # --device_wer beyond the greedy path: errors, S, D, I, ref, hyp, oracle
+    need_text = not args.device_wer or bool(args.dump_hyps)  # the strings are read only where something needs them
     hyps, refs, words, utt_scores, beam_scores, lm_scores, boost_scores = [], [], [], [], [], [], []
     lm_kw = dict(lm=args.lm_path, alpha=alpha, beta=beta) if args.lm_path is not None else {}
     if args.boost_file is not None:                          # compiled once for the run: the file does not change per batch
@@ -372,15 +395,22 @@ def main():
                     words.append([list(w) for w in h.words])
                     utt_scores.append(h.utt_score)
         elif args.beam_width is not None:                    # k_topn + k_beam behind the forward, on the same stream
-            for h in asr_model.decode(input_signal=signal, input_signal_length=batch[1], beam_width=args.beam_width,
-                                      **lm_kw, **rate_kw):
+            if args.device_wer:                              # ... and k_edit behind them: only the counts are read back
+                _add_report(dev_counts, asr_model.error_rate(input_signal=signal, input_signal_length=batch[1], targets=batch[2],
+                                                             use_cer=args.cer, beam_width=args.beam_width,
+                                                             n_best=args.n_best or 1, **lm_kw, **rate_kw))
+            for h in (asr_model.decode(input_signal=signal, input_signal_length=batch[1], beam_width=args.beam_width,
+                                       **lm_kw, **rate_kw) if need_text else ()):
                 hyps.append(h.text)
                 beam_scores.append(h.utt_score)
                 lm_scores.append(h.lm_score)
                 boost_scores.append(h.boost_score)
         else:
             log_probs, enc_len, greedy = asr_model(input_signal=signal, input_signal_length=batch[1], **rate_kw)
-            hyps += wer.ctc_decoder_predictions_tensor(greedy)
+            if dev_wer is not None:                          # k_ctc over the padded rows, then k_edit against the padded targets
+                dev_wer.update(greedy, batch[2], None)
+            if need_text:
+                hyps += wer.ctc_decoder_predictions_tensor(greedy)
         if args.timestamps and args.window_s is None and args.stream_chunk_s is None:        # device-side collapse up to each utterance's encoded length
             for h in asr_model.decode(input_signal=signal, input_signal_length=batch[1], **rate_kw):
                 words.append([list(w) for w in h.words])
@@ -433,8 +463,16 @@ def main():
                 k = len(spotted)
                 spotted.append(dict(audio_filepath=items[k][0] if not args.shuffle and k < len(items) else None,
                                     hits=[dict(keyword=h.keyword, start=h.start_s, end=h.end_s, score=h.score) for h in row]))
-        for row in batch[2].cpu().numpy():
-            refs.append(''.join(labels_map[c] for c in row))
+        strings_scored = args.device_wer and (args.stream_chunk_s is not None or args.window_s is not None)
+        if need_text or strings_scored:
+            for row in batch[2].cpu().numpy():
+                refs.append(''.join(labels_map[c] for c in row))
+        if strings_scored:                                   # hypotheses that exist only as strings
+            from qasr.edit import error_counts
+            n = batch[2].shape[0]
+            c = error_counts(hyps[-n:], refs[-n:], use_cer=args.cer, device='cuda')
+            for k, v in enumerate((c.errors, c.substitutions, c.deletions, c.insertions, c.ref_units, c.hyp_units, c.errors)):
+                dev_counts[k] += v
         audio_s += float(batch[1].sum()) / float(args.input_rate or 16000)
     torch.cuda.synchronize()
     wall = time.time() - t0
@@ -446,8 +484,18 @@ def main():
         served, 'host modules'))
     if stream_sess is not None and stream_sess.endpoint is not None:
         print('utterances:', n_utterances)
-    wer_value = word_error_rate(hypotheses=hyps, references=refs)
+    if args.device_wer:
+        if dev_wer is not None and args.beam_width is None and args.stream_chunk_s is None and args.window_s is None:
+            c = dev_wer.counts()                             # the one read of the metric's totals block
+            dev_counts = [c.errors, c.substitutions, c.deletions, c.insertions, c.ref_units, c.hyp_units, c.errors]
+        wer_value = 1.0 * dev_counts[0] / dev_counts[4] if dev_counts[4] != 0 else float('inf')
+    else:
+        wer_value = word_error_rate(hypotheses=hyps, references=refs, use_cer=args.cer)
     print('WER:', wer_value)
+    if args.device_wer:
+        print('S / D / I:', dev_counts[1], '/', dev_counts[2], '/', dev_counts[3])
+        if args.beam_width is not None and args.n_best and args.stream_chunk_s is None and args.window_s is None:
+            print('oracle WER:', 1.0 * dev_counts[6] / dev_counts[4] if dev_counts[4] != 0 else float('inf'))
     if args.dump_hyps:
         import json
         with open(args.dump_hyps, 'w') as f:

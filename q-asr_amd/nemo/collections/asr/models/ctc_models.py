@@ -476,7 +476,7 @@ class EncDecCTCModel(nn.Module):
     @torch.no_grad()
     def decode(self, input_signal=None, input_signal_length=None, processed_signal=None, processed_signal_length=None,
                beam_width=None, n_best=1, cutoff_top_n=40, lm=None, alpha=0.0, beta=0.0, timestamps=False, boost=None,
-               boost_weight=1.0, sample_rate=None, channels=1, posteriors=False):
+               boost_weight=1.0, sample_rate=None, channels=1, posteriors=False, _rows=False):
         """Greedy CTC hypotheses of one batch (an extension of the reference's API): List[qasr.ctc.Hypothesis] with the
         text, every label's start / end time and confidence (best frame log-probability of its run), word groups and the
         log-probability of the greedy path.  Decoding stops at each utterance's encoded length.  On the static engine the
@@ -530,8 +530,11 @@ class EncDecCTCModel(nn.Module):
                 except ValueError as e:
                     raise ValueError(f'decode: {e}') from None
             return self._beam_decode(self._forward(input_signal, input_signal_length, processed_signal, processed_signal_length),
-                                     beam_width, n_best, cutoff_top_n, lm, alpha, beta, bool(timestamps), boost, bool(posteriors))
+                                     beam_width, n_best, cutoff_top_n, lm, alpha, beta, bool(timestamps), boost, bool(posteriors),
+                                     rows=_rows)
         res = self._forward(input_signal, input_signal_length, processed_signal, processed_signal_length, decode=True)
+        if _rows:                            # error_rate: the CtcResult as it lies, nothing turned into strings
+            return res
         return qctc.to_hypotheses(res, self.decoder.vocabulary, self.seconds_per_frame())
 
     def _long_plan(self, lens_samples, window_s=30.0, overlap_s=4.0, guard_s=1.0):
@@ -601,7 +604,7 @@ class EncDecCTCModel(nn.Module):
     @torch.no_grad()
     def decode_long(self, input_signal, input_signal_length, window_s=30.0, overlap_s=4.0, guard_s=1.0, batch_size=32,
                     seam='blank', beam_width=None, n_best=1, cutoff_top_n=40, lm=None, alpha=0.0, beta=0.0, boost=None,
-                    boost_weight=1.0, sample_rate=None, channels=1):
+                    boost_weight=1.0, sample_rate=None, channels=1, _rows=False):
         """Hypotheses of long recordings (an extension; buffered inference on the device): input_signal [R, S] with
         input_signal_length samples each -> List[qasr.ctc.Hypothesis], one per recording, times in seconds of the recording,
         seams_s = the times at which neighbouring windows were joined (None for a recording of one window: its hypothesis
@@ -667,6 +670,8 @@ class EncDecCTCModel(nn.Module):
                 res = qengine.ctc_collapse(out[0], out[1], total, blank=blank)
             else:
                 res = qctc.collapse_host(out[0].numpy(), out[1].numpy(), total.numpy(), blank=blank)
+            if _rows:                        # error_rate_long: the stitched rows' CtcResult as it lies
+                return res
             hyps = qctc.to_hypotheses(res, self.decoder.vocabulary, spf_s)
             for h, s in zip(hyps, seams_s):
                 h.seams_s = s
@@ -682,11 +687,93 @@ class EncDecCTCModel(nn.Module):
             res = qengine.ctc_beam(scid, scq, total, blank, beam_width, n_best, lm=lm, alpha=alpha, beta=beta, boost=boost)
         else:
             res = qbeam.beam_search_host(scid.numpy(), scq.numpy(), total_h, blank, beam_width, n_best, lm, alpha, beta, boost)
+        if _rows:
+            return res
         hyps = qbeam.to_hypotheses(res, self.decoder.vocabulary)
         for row, s in zip(hyps, seams_s):
             for h in row:
                 h.seams_s = s
         return hyps if n_best > 1 else [h[0] for h in hyps]
+
+    def _reference_rows(self, who, targets, target_lengths, texts, n, device):
+        """the references of error_rate as (ids [n, L], lengths [n] or None) on `device`: targets / target_lengths as the data
+        loader gives them (no lengths: the padded rows), or texts over the decoder's vocabulary of single characters"""
+        if (targets is None) == (texts is None):
+            raise ValueError(f'{who}: give the references as targets (with target_lengths) or as texts, not both')
+        if texts is not None:
+            at = {ch: i for i, ch in enumerate(self.decoder.vocabulary)}
+            if len(texts) != n:
+                raise ValueError(f'{who}: {len(texts)} texts for {n} utterances')
+            ids = []
+            for r, t in enumerate(texts):
+                for ch in t:
+                    if ch not in at:
+                        raise ValueError(f'{who}: text {r} has {ch!r}, which is not in the vocabulary')
+                ids.append([at[ch] for ch in t])
+            targets = torch.zeros(n, max(1, max(len(x) for x in ids)), dtype=torch.int32)
+            for r, x in enumerate(ids):
+                targets[r, :len(x)] = torch.tensor(x, dtype=torch.int32)
+            target_lengths = torch.tensor([len(x) for x in ids], dtype=torch.int32)
+        if targets.dim() != 2 or targets.shape[0] != n:
+            raise ValueError(f'{who}: targets must be [{n}, ids], got {tuple(targets.shape)}')
+        if targets.shape[1] == 0:
+            targets, target_lengths = torch.zeros(n, 1, dtype=torch.int32), torch.zeros(n, dtype=torch.int32)
+        return targets.to(device), None if target_lengths is None else target_lengths.to(device)
+
+    def _score_rows(self, who, res, targets, target_lengths, texts, use_cer):
+        """error_rate behind any decode chain: the CtcResult's or BeamResult's label rows against the references through k_edit
+        (cuda) or its twin; only the counts are read back"""
+        from qasr import edit as qedit
+        vocab = self.decoder.vocabulary
+        labels, n_labels = res.labels, res.n_labels
+        n_hyps = getattr(res, 'n_hyps', None)
+        K = labels.shape[1] if n_hyps is not None else 1
+        cuda = torch.is_tensor(labels) and labels.is_cuda
+        n = labels.shape[0]
+        hyp, hl = labels.reshape(n * K, labels.shape[-1]), n_labels.reshape(n * K)
+        tg, tl = self._reference_rows(who, targets, target_lengths, texts, n, labels.device if cuda else 'cpu')
+        mode = 'char' if use_cer else 'word'
+        mask = None if use_cer else qedit.space_mask(list(vocab), who)
+        if cuda:
+            sp = None if mask is None else torch.from_numpy(mask).to(labels.device)
+            out = qedit.edit_device(hyp, hl, tg, tl, len(vocab), mode=mode, is_space=sp, rows_per_ref=K, n_hyps=n_hyps)
+            rows, totals = out.rows.cpu().numpy(), out.totals.cpu().numpy()
+        else:
+            host = lambda t: None if t is None else (t.numpy() if torch.is_tensor(t) else t)
+            out = qedit.edit_host(host(hyp), host(hl), host(tg), host(tl), len(vocab), mode=mode, is_space=mask, rows_per_ref=K,
+                                  n_hyps=host(n_hyps))
+            rows, totals = out.rows, out.totals
+        return qedit.report_of(rows, totals, K)
+
+    @torch.no_grad()
+    def error_rate(self, input_signal=None, input_signal_length=None, targets=None, target_lengths=None, texts=None, use_cer=False,
+                   beam_width=None, n_best=1, processed_signal=None, processed_signal_length=None, **decode_args):
+        """Word (use_cer: character) error counts of one batch against its references (an extension): decode()'s device
+        chain - greedy, or the beam search with beam_width / n_best and decode()'s cutoff_top_n, lm, alpha, beta, boost,
+        boost_weight, sample_rate, channels - then the edit distance over the label rows where they lie (k_edit;
+        qasr.edit.EDIT_RULES).  Only the counts are read back: a qasr.ctc.ErrorReport with the total over the best
+        hypotheses, the per-utterance counts and, with n_best = K > 1, oracle_errors = the sum over the utterances of the
+        fewest errors among their K rows.  References: targets int [B, L] with target_lengths (None: the padded rows), or
+        texts.  The numbers are word_error_rate's over decode()'s texts.  Works on the static engine, a reserved engine, the
+        dynamic path, and through the NumPy twin with the host modules or CPU tensors.  Word mode needs a vocabulary of
+        single characters."""
+        for k in ('timestamps', 'posteriors', '_rows'):
+            if k in decode_args:
+                raise ValueError(f'error_rate: {k} is not an argument of the error rate')
+        res = self.decode(input_signal, input_signal_length, processed_signal, processed_signal_length, beam_width=beam_width,
+                          n_best=n_best, _rows=True, **decode_args)
+        return self._score_rows('error_rate', res, targets, target_lengths, texts, use_cer)
+
+    @torch.no_grad()
+    def error_rate_long(self, input_signal, input_signal_length, targets=None, target_lengths=None, texts=None, use_cer=False,
+                        beam_width=None, n_best=1, **decode_long_args):
+        """error_rate behind decode_long's stitched rows: window_s / overlap_s / guard_s / batch_size / seam and the beam
+        arguments as decode_long takes them, one reference per recording."""
+        if '_rows' in decode_long_args:
+            raise ValueError('error_rate_long: _rows is not an argument of the error rate')
+        res = self.decode_long(input_signal, input_signal_length, beam_width=beam_width, n_best=n_best, _rows=True,
+                               **decode_long_args)
+        return self._score_rows('error_rate_long', res, targets, target_lengths, texts, use_cer)
 
     def _stream_plan(self, chunk_s=0.96, left_s=4.0, right_s=0.96):
         """the qasr.stream.StreamPlan of stream(): units and frames_of taken from the model as _long_plan takes them"""
@@ -988,7 +1075,7 @@ class EncDecCTCModel(nn.Module):
         return lm
 
     def _beam_decode(self, fwd, beam_width, n_best, cutoff_top_n, lm=None, alpha=0.0, beta=0.0, timestamps=False, boost=None,
-                     posteriors=False):
+                     posteriors=False, rows=False):
         """decode(beam_width=) behind any path's (log_probs, encoded lengths, tokens); the arguments passed _beam_args"""
         from qasr import beam as qbeam
         log_probs, enc_len = fwd[0], fwd[1]
@@ -1000,6 +1087,8 @@ class EncDecCTCModel(nn.Module):
         else:
             res = qbeam.search_host(log_probs.float().numpy(), enc_len.numpy(), blank, beam_width, n_best, cutoff_top_n, lm,
                                     alpha, beta, boost)
+        if rows:                             # error_rate: the BeamResult as it lies
+            return res
         hyps = qbeam.to_hypotheses(res, self.decoder.vocabulary)
         if timestamps:
             self._beam_timestamps(hyps, res, log_probs, enc_len, blank, n_best, posteriors)

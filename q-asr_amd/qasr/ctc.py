@@ -118,6 +118,31 @@ class StreamUtterance:
     n_best: Optional[List[Hypothesis]] = None   # beam sessions (StreamBeam(endpoint=)) with n_best > 1: the utterance's list, best first
 
 
+@dataclass
+class ErrorCounts:
+    """Edit-distance counts of one utterance, or their sum over a set (qasr.edit.EDIT_RULES): errors = substitutions +
+    deletions + insertions against ref_units reference words (characters with use_cer), hyp_units units in the hypotheses;
+    rate = errors / ref_units, inf for ref_units == 0 as word_error_rate gives it."""
+    errors: int
+    substitutions: int
+    deletions: int
+    insertions: int
+    ref_units: int
+    hyp_units: int
+    rate: float
+
+
+@dataclass
+class ErrorReport:
+    """EncDecCTCModel.error_rate / error_rate_long: total over the best hypothesis of every utterance, oracle_errors: the sum
+    over the utterances of the fewest errors of any of their n-best rows (n_best = 1: total.errors), per_utterance: the best
+    hypothesis's counts, invalid: rows left out because an id or a length was out of range."""
+    total: ErrorCounts
+    oracle_errors: int
+    per_utterance: List[ErrorCounts]
+    invalid: int
+
+
 def _order_key(x):
     """float32 -> int32 that orders like the float on every bit pattern (-0 < +0); the order k_ctc takes maxima in"""
     b = np.ascontiguousarray(x, dtype=np.float32).view(np.int32)

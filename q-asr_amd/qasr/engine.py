@@ -28,7 +28,7 @@ SYMBOLS = ['qasr_blob_check', 'qasr_engine_create', 'qasr_engine_create_ex', 'qa
            'qasr_stream_rs_state_bytes', 'qasr_stream_rs_work_bytes', 'qasr_stream_rs_push',
            'qasr_stream_beam_state_bytes', 'qasr_stream_beam', 'qasr_stream_ep_state_bytes', 'qasr_stream_endpoint',
            'qasr_stream_beam_boost_state_bytes', 'qasr_stream_beam_boost', 'qasr_stream_beam_ep',
-           'qasr_stream_spot_state_bytes', 'qasr_stream_spot',
+           'qasr_stream_spot_state_bytes', 'qasr_stream_spot', 'qasr_edit_workspace_bytes', 'qasr_edit_distance',
            'qasr_last_error', 'qasr_version']
 
 _lib = None
@@ -237,6 +237,10 @@ def load_library():
         lib.qasr_stream_spot_state_bytes.argtypes = [i32, i32, i32]
         lib.qasr_stream_spot_state_bytes.restype = sz
         lib.qasr_stream_spot.argtypes = [vp, C.POINTER(StreamSpotArgs)]
+    if hasattr(lib, 'qasr_edit_distance'):      # (likewise)
+        lib.qasr_edit_workspace_bytes.argtypes = [i32, i32, i32, i32]
+        lib.qasr_edit_workspace_bytes.restype = sz
+        lib.qasr_edit_distance.argtypes = [vp, C.POINTER(EditArgs)]
     lib.qasr_debug_prof.argtypes = [vp]
     lib.qasr_debug_timeline.argtypes = [vp, sz]
     lib.qasr_sep_layer.argtypes = [vp, C.POINTER(SepLayerArgs), C.c_char_p, sz]
@@ -766,6 +770,81 @@ def ctc_spot(log_probs, lens, star, targets, target_lens, blank, threshold, max_
     st = _set_star(who, a, star, B, T, dev)
     a.B, a.T, a.C, a.K, a.max_labels, a.blank, a.max_hits = B, T, Cn, K, ML, int(blank), MH
     return _lattice_launch('qasr_ctc_spot', a, dev, stream, out, (lp, ln, st, tg, tl))
+
+
+class EditArgs(C.Structure):
+    """qasr_edit_args (include/qasr.h)"""
+    _fields_ = ([('struct_size', C.c_uint32)] +
+                [(n, C.c_int32) for n in ('mode', 'B', 'K', 'C', 'max_hyp', 'max_ref', 'pad_')] +
+                [('hyp_pitch', C.c_int64), ('ref_pitch', C.c_int64)] +
+                [(n, C.c_void_p) for n in ('hyp', 'hyp_lens', 'ref', 'ref_lens', 'n_hyps', 'is_space', 'rows', 'totals',
+                                           'workspace')] +
+                [('workspace_bytes', C.c_size_t)])
+
+
+def edit_workspace_bytes(P, max_hyp, max_ref, mode):
+    """qasr_edit_workspace_bytes; mode: 'char' / 'word'"""
+    from .edit import check_mode
+    return int(load_library().qasr_edit_workspace_bytes(int(P), int(max_hyp), int(max_ref), check_mode(mode, 'edit_workspace_bytes')))
+
+
+def _edit_rows(who, t, name):
+    """an id matrix for k_edit: cuda int32 [rows, ids] with contiguous ids (rows of any pitch)"""
+    assert t.is_cuda and t.dim() == 2, f'{who}: {name} must be a cuda matrix [rows, ids]'
+    t = t if t.dtype == torch.int32 else t.to(torch.int32)
+    return t if t.shape[1] == 1 or t.stride(1) == 1 else t.contiguous()
+
+
+def edit_distance(hyp, hyp_lens, ref, ref_lens, n_classes, mode='char', is_space=None, rows_per_ref=1, n_hyps=None, totals=None,
+                  workspace=None, out=None, stream=None):
+    """qasr_edit_distance: word / character error counts on the device (k_edit_cut, k_edit, k_edit_totals: three launches on the
+    current stream, no host synchronisation); equal to qasr.edit.edit_host byte for byte.  hyp: a cuda int32 matrix
+    [B * rows_per_ref, max_hyp], ref [B, max_ref] (rows of any pitch), hyp_lens / ref_lens / n_hyps int32 vectors or None (None
+    lengths: the padded rows); is_space: uint8 [n_classes] (word mode); totals: a cuda int64 [16] block the call adds to (None: a
+    zeroed one); `out`: a caller-owned cuda int32 [B * rows_per_ref, 8].  Returns a qasr.edit.EditResult of cuda tensors."""
+    from .edit import ROW_WORDS, TOTAL_WORDS, EditResult, check_mode, check_widths
+    who = 'edit_distance'
+    lib = load_library()
+    a = EditArgs()
+    a.struct_size, a.mode = C.sizeof(EditArgs), check_mode(mode, who)
+    h, r = _edit_rows(who, hyp, 'hyp'), _edit_rows(who, ref, 'ref')
+    dev = h.device
+    (P, MH), (B, MR), K = h.shape, r.shape, int(rows_per_ref)
+    if K < 1 or B < 1 or P != B * K:
+        raise ValueError(f'{who}: {P} hypothesis rows are not {B} references * {K} rows per reference')
+    if int(n_classes) < 1:
+        raise ValueError(f'{who}: n_classes must be at least 1, got {n_classes}')
+    check_widths(MH, MR, who)
+    keep = [h, r]
+    for name, v, n in (('hyp_lens', hyp_lens, P), ('ref_lens', ref_lens, B), ('n_hyps', n_hyps, B)):
+        if v is not None:
+            if tuple(v.shape) != (n,):
+                raise ValueError(f'{who}: {name} must have {n} entries')
+            v = v.to(device=dev, dtype=torch.int32).contiguous()
+            keep.append(v)
+            setattr(a, name, v.data_ptr())
+    if a.mode == 1:
+        if is_space is None:
+            raise ValueError(f'{who}: word mode needs is_space')
+        if tuple(is_space.shape) != (int(n_classes),):
+            raise ValueError(f'{who}: is_space must have one entry per class ({int(n_classes)}), got shape {tuple(is_space.shape)}')
+        sp = is_space.to(device=dev, dtype=torch.uint8).contiguous()
+        keep.append(sp)
+        a.is_space = sp.data_ptr()
+    if totals is None:
+        totals = torch.zeros(TOTAL_WORDS, device=dev, dtype=torch.int64)
+    assert totals.is_cuda and totals.dtype == torch.int64 and tuple(totals.shape) == (TOTAL_WORDS,) and totals.is_contiguous(), \
+        f'{who}: totals must be a cuda int64 [{TOTAL_WORDS}]'
+    if out is None:
+        out = torch.empty(P, ROW_WORDS, device=dev, dtype=torch.int32)
+    assert out.is_cuda and out.dtype == torch.int32 and tuple(out.shape) == (P, ROW_WORDS) and out.is_contiguous(), \
+        f'{who}: out must be a cuda int32 [{P}, {ROW_WORDS}]'
+    a.B, a.K, a.C, a.max_hyp, a.max_ref = B, K, int(n_classes), MH, MR
+    a.hyp, a.hyp_pitch, a.ref, a.ref_pitch = h.data_ptr(), _row_pitch(h, MH), r.data_ptr(), _row_pitch(r, MR)
+    a.rows, a.totals = out.data_ptr(), totals.data_ptr()
+    keep.append(_set_workspace(a, workspace, dev, lib.qasr_edit_workspace_bytes, P, MH, MR, a.mode))
+    res = EditResult(out, totals, K)
+    return _lattice_launch('qasr_edit_distance', a, dev, stream, res, tuple(keep))
 
 
 def ctc_align_workspace_bytes(P, T, max_labels):
