@@ -162,7 +162,9 @@ void qasr_engine_destroy(qasr_engine* e);
  * Environment variables remain ONLY as A/B overrides for profiling runs of an unmodified caller, read once per create
  * call AFTER the options: QASR_TILE128=0|1 (128-frame tiles when tile_frames >= 64), QASR_RES_TILE128=0|1 (res_tile128),
  * QASR_RES_TILE=32|64|128 (the block-end tile itself, read after QASR_RES_TILE128; 32 has no option value), QASR_DENSE_TILE128,
- * QASR_SEP_GEN=1|2, QASR_PAIR_SPLIT=0|1 (pair_split), QASR_NO_FUSE, QASR_NO_FUSE_STEM, QASR_NO_FUSE_DEC, QASR_WIDE_TILES, QASR_NO_FUSE_NORM; QASR_SEP2_TUNE is a kernel-internal experiment knob (csrc/qasr_sep2_impl.h). */
+ * QASR_SEP_GEN=1|2, QASR_PAIR_SPLIT=0|1 (pair_split), QASR_HALF_TILES=0|1 (the unpaired plain layers of a
+ * tile_frames == 128 engine as 64-frame launches, qasr_engine_op_halved; no option field: on below 8 hardware queues by the hint
+ * res_tile128 reads), QASR_NO_FUSE, QASR_NO_FUSE_STEM, QASR_NO_FUSE_DEC, QASR_WIDE_TILES, QASR_NO_FUSE_NORM; QASR_SEP2_TUNE is a kernel-internal experiment knob (csrc/qasr_sep2_impl.h). */
 typedef struct qasr_engine_opts {
   uint32_t struct_size;
   uint32_t debug;              /* bit 0: keep every tensor + int32 accumulators (parity hooks); bit 1: one HIP event per op */
@@ -1564,6 +1566,12 @@ size_t qasr_sep_pair_workspace_bytes(int B, int Tp);
 size_t qasr_sep_pair_timeout_offset(int B, int Tp);
 /* 1 if op `op` of the current plan runs in the paired form, 0 if not, -1 for a bad argument (after a forward) */
 int qasr_engine_op_paired(const qasr_engine* e, int op);
+/* 1 if op `op` of the current plan runs in the halved form, 0 if not, -1 for a bad argument (after a forward).  Halved: an
+ * unpaired plain k_sep2 layer of a 128-frame tile launched as the 64-frame instantiation of the same kernel on grid
+ * (B, Tp / 64) - the same bytes, label and launch count.  For a tile_frames == 128 engine below 8 hardware queues (the
+ * GPU_MAX_HW_QUEUES hint of res_tile128; QASR_HALF_TILES=0|1 overrides), never for debug / timing / reserved engines, paired
+ * ops, block-end layers or rows that 128 does not divide */
+int qasr_engine_op_halved(const qasr_engine* e, int op);
 /* synchronises the device and reads the time-out word of paired launches.  Kept from the form whose members handed their
  * halves over inside the launch: the members of a pair exchange nothing now, no kernel writes the word, the result is always 0 */
 int qasr_engine_pair_timeouts(qasr_engine* e);

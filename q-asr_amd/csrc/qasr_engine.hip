@@ -137,6 +137,9 @@ struct qasr_engine {
   unsigned* pair_flags = nullptr;      // every paired op's flag words: an allocation of their own, zeroed once per forward (by k_stem, or by ONE k_pair_zero node without the fused stem)
   size_t pair_flag_bytes = 0;
   unsigned* pair_tmo = nullptr;        // 256 B: the time-out word of the former hand-off; no kernel writes it, qasr_engine_pair_timeouts reads 0
+  // the unpaired plain layers of a tile_frames == 128 engine on 64-frame halves: by half_tiles_default(), QASR_HALF_TILES
+  bool half_tiles = false;
+  std::vector<char> halved;            // per op: launched in the halved form (empty: none)
   bool in_forward = false;             // launch_op runs inside enqueue_forward (which zeroes the flags: k_pair_zero in front, or k_stem)
   // hipGraph replay (bit 4 of `debug`): the whole forward of one (shape, buffer set) is captured once and re-launched
   // with one call; key = the caller's pointers, which a serving loop keeps stable
@@ -237,6 +240,7 @@ static void free_plan(qasr_engine* e) {
   e->pair_tmo = nullptr;
   e->paired.clear();
   e->pair_flag_off.clear();
+  e->halved.clear();
   for (auto& v : e->acc_dbg)
     for (auto p : v)
       dev_free(e, p);
@@ -410,6 +414,22 @@ static int plan_pairs(qasr_engine* e) {
   return QASR_OK;
 }
 
+// Which ops run in the halved form (after plan_pairs: a paired op is never halved).  The same engines as plan_pairs; sep_half_ok
+// leaves the unpaired plain production launches of 128-frame tiles whose shape class is in sep2_half_shape.
+static void plan_halves(qasr_engine* e) {
+  const auto& h = e->h;
+  if (!e->half_tiles || e->debug || e->timing || !e->wide_tiles || !e->tile128 || e->rs.on) return;
+  std::vector<char> halved(h.n_ops, 0);
+  bool any = false;
+  for (uint32_t oi = 0; oi < h.n_ops; ++oi) {
+    if (e->ops[oi].kind != QASR_OP_PW || e->skip[oi] || e->fused_dw[oi] < 0) continue;
+    SepP p{};
+    build_sep(e, oi, p);
+    if (sep_half_ok(p)) halved[oi] = 1, any = true;
+  }
+  if (any) e->halved.swap(halved);
+}
+
 static int build_plan(qasr_engine* e, int B, int T0) {
   free_plan(e);
   int rc = plan_shape(e, B, T0);
@@ -419,6 +439,7 @@ static int build_plan(qasr_engine* e, int B, int T0) {
   }
   rc = plan_alloc(e);
   if (!rc) rc = plan_pairs(e);
+  if (!rc) plan_halves(e);
   if (rc) e->B = e->T0 = 0;
   return rc;
 }
@@ -524,6 +545,10 @@ static int res_tile_default() { return hw_queues_hint() >= QASR_SIDE_BY_SIDE_QUE
 // launches of the plain 512 -> 512 layers, and a tile on two work-groups halves their span; with four chains
 // side by side the chip is full and the plan stays as it is.
 static bool pair_split_default() { return hw_queues_hint() < QASR_SIDE_BY_SIDE_QUEUES; }
+// The unpaired plain layers' 128-frame tiles as two 64-frame work-groups, by the same hint: with two chains at a time their 64
+// work-groups become 128, one chain's plus the other's fill the 256 CUs, and a shorter work-group shortens the chain
+// (DESIGN.md 5.10); from QASR_SIDE_BY_SIDE_QUEUES queues the plan stays as it is.  No option field: QASR_HALF_TILES=0|1 overrides.
+static bool half_tiles_default() { return hw_queues_hint() < QASR_SIDE_BY_SIDE_QUEUES; }
 
 // the `debug` bits of round 1 / 2 callers, as options
 int qasr_engine_create(const void* blob, size_t n, int device, int debug, qasr_engine** out) {
@@ -575,6 +600,7 @@ int qasr_engine_create_ex(const void* blob, size_t n, int device, const qasr_eng
   e->sep_gen = o.sep_gen == 1 ? 1 : 2;
   e->mask_skip = o.mask_skip < 0 ? -1 : (o.mask_skip != 0);
   e->pair_split = o.pair_split < 0 ? pair_split_default() : o.pair_split != 0;
+  e->half_tiles = half_tiles_default();
   e->use_graph = o.graph > 0;
   // environment: A/B overrides for profiling runs of an unmodified caller (include/qasr.h lists them), read per create call
   if (getenv("QASR_NO_FUSE")) e->fuse = false;
@@ -591,6 +617,7 @@ int qasr_engine_create_ex(const void* blob, size_t n, int device, const qasr_eng
   if (const char* g = getenv("QASR_DENSE_TILE128")) e->dense_tile128 = atoi(g) != 0;
   if (const char* g = getenv("QASR_SEP_GEN")) e->sep_gen = atoi(g) == 1 ? 1 : 2;
   if (const char* g = getenv("QASR_PAIR_SPLIT")) e->pair_split = atoi(g) != 0;
+  if (const char* g = getenv("QASR_HALF_TILES")) e->half_tiles = atoi(g) != 0;
   e->blob.assign((const uint8_t*)blob, (const uint8_t*)blob + n);
   e->h = h;
   e->tdesc = (const qasr_tensor_desc*)(e->blob.data() + h.tensors_off);
@@ -708,6 +735,7 @@ static void build_sep(qasr_engine* e, uint32_t oi, SepP& p) {
     p.pair = 1;
     p.pair_flags = (unsigned*)((unsigned char*)e->pair_flags + e->pair_flag_off[oi]);
   }
+  if (!e->halved.empty() && e->halved[oi]) p.half = 1;
   fill_panes(e, oi, op, p.panes);
   fill_epi(e, oi, op, p.e);
   const int di = e->fused_dw[oi];
@@ -2289,6 +2317,11 @@ int qasr_engine_op_label(qasr_engine* e, int op, char* buf, size_t cap) {
 int qasr_engine_op_paired(const qasr_engine* e, int op) {
   if (!e || op < 0 || op >= (int)e->h.n_ops) return -1;
   return (!e->paired.empty() && e->paired[op]) ? 1 : 0;
+}
+
+int qasr_engine_op_halved(const qasr_engine* e, int op) {
+  if (!e || op < 0 || op >= (int)e->h.n_ops) return -1;
+  return (!e->halved.empty() && e->halved[op]) ? 1 : 0;
 }
 
 int qasr_engine_pair_timeouts(qasr_engine* e) {

@@ -81,7 +81,8 @@ struct SepP {             // fused separable layer: depthwise stencil -> QuantAc
   int prof_cap;           // ... for work-groups below this count (the caller's buffer)
   int etile;              // the engine's tile_frames option (32: built for one step in flight; 64 / 128: several), before per-op adjustments
   int mask_skip;          // k_sep2: route to the k_sep2s instantiations (mask-skip rule; reserved engines, qasr_engine_opts.mask_skip)
-  int pair, pad_;         // k_sep2: the paired form k_sep2p (two work-groups per tile, 64 frames each; plain 512 -> 512 layers at 128 frames)
+  int pair;               // k_sep2: the paired form k_sep2p (two work-groups per tile, 64 frames each; plain 512 -> 512 layers at 128 frames)
+  int half;               // k_sep2: a 128-frame op launched as its 64-frame instantiation on grid (B, Tp / 64) (sep_half_ok; never with pair)
   unsigned* pair_flags;   // ... its completion words, 2 per (utterance, tile), zero before the launch: each member adds 1 at its end
   PaneP panes[QASR_MAX_PANES];
   EpiP e;
@@ -123,6 +124,7 @@ int launch_sep(hipStream_t s, const SepP& p);      // QASR_OK, or QASR_ERR_UNSUP
 void sep_kernel_label(const SepP& p, char* buf, size_t cap);
 int sep_tile_for(const SepP& p);
 bool sep_pair_ok(const SepP& p);                   // does launch_sep have the paired form (p.pair) for this op?
+bool sep_half_ok(const SepP& p);                   // does launch_sep have the halved form (p.half) for this op?
 size_t sep_pair_flag_bytes(int B, int Tp);         // completion words of one paired launch
 size_t sep_pair_x_bytes(int B, int Tp);            // the former exchange buffer's bytes (qasr_sep_pair_workspace_bytes keeps its values)
 int launch_pair_zero(hipStream_t s, unsigned* flags, size_t bytes);   // k_pair_zero: flag words (16-byte granules) back to zero

@@ -81,9 +81,27 @@ bool sep_pair_ok(const SepP& p) {
 size_t sep_pair_flag_bytes(int B, int Tp) { return sep2_pair_flag_bytes(B, Tp); }
 size_t sep_pair_x_bytes(int B, int Tp) { return sep2_pair_x_bytes(B, Tp); }
 
+// Shape classes of the halved form (the counterpart of sep2_pair_shape; the caller has checked sep2_shape_ok and the tile): the
+// plain layers whose 64-frame launch measured shorter than their 128-frame one with two chains at a time.
+// {taps, dilation, cin, cout}; the three 512 -> 512 classes are the paired ones and get here only with pairing off
+static inline bool sep2_half_shape(const SepP& p) {
+  static const int classes[][4] = {{33, 1, 256, 256}, {39, 1, 256, 256}, {51, 1, 256, 512}, {87, 2, 512, 512},
+                                   {51, 1, 512, 512}, {63, 1, 512, 512}, {75, 1, 512, 512}};
+  for (const auto& c : classes)
+    if (p.K == c[0] && p.dilation == c[1] && p.cin_pad == c[2] && p.e.cout == c[3]) return true;
+  return false;
+}
+// the halved form: an unpaired plain production launch of a 128-frame tile as the 64-frame instantiation of the same kernel
+bool sep_half_ok(const SepP& p) {
+  const bool dbg = p.e.acc_dbg || p.dw_acc_dbg;
+  return !dbg && !p.mask_skip && !p.pair && !dense2_takes(p) && sep2_takes(p) && sep2_tile(p) == 128 && p.K > 0 &&
+         !(p.e.flags & QASR_F_RESADD) && p.n_panes == 0 && sep2_half_shape(p);
+}
+
 int launch_sep(hipStream_t s, const SepP& p) {
   const bool dbg = p.e.acc_dbg || p.dw_acc_dbg;
   if (p.pair) return sep_pair_ok(p) ? launch_sep2_pair(s, p) : QASR_ERR_UNSUPPORTED;   // (the label stays k_sep2<...>'s)
+  if (p.half) return sep_half_ok(p) ? launch_sep2_inst<64, false>(s, p) : QASR_ERR_UNSUPPORTED;   // (and here: <..., 128, ...>)
   if (dense2_takes(p)) return launch_dense2(s, p);           // Jasper's plain dense convs (qasr_dense2.hip)
   if (sep2_takes(p)) {
     const int tt = sep2_tile(p);

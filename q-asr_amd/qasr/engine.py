@@ -11,7 +11,7 @@ LIB_PATH = os.environ.get('QASR_LIB', os.path.join(HERE, 'libqasr_hip.so'))   # 
 
 SYMBOLS = ['qasr_blob_check', 'qasr_engine_create', 'qasr_engine_create_ex', 'qasr_engine_default_opts', 'qasr_engine_destroy', 'qasr_engine_forward', 'qasr_engine_forward_audio', 'qasr_engine_out_frames',
            'qasr_engine_num_ops', 'qasr_engine_num_launches', 'qasr_engine_read_acc', 'qasr_engine_read_tensor', 'qasr_engine_last_op_ms',
-           'qasr_engine_time_ops', 'qasr_engine_run_op', 'qasr_engine_op_label', 'qasr_engine_op_paired', 'qasr_engine_pair_timeouts', 'qasr_engine_pair_flag_words',
+           'qasr_engine_time_ops', 'qasr_engine_run_op', 'qasr_engine_op_label', 'qasr_engine_op_paired', 'qasr_engine_op_halved', 'qasr_engine_pair_timeouts', 'qasr_engine_pair_flag_words',
            'qasr_sep_pair_workspace_bytes', 'qasr_sep_pair_timeout_offset',
            'qasr_frontend_mel', 'qasr_frontend_plan', 'qasr_frontend_mel_planned', 'qasr_frontend_frames',
            'qasr_frontend_workspace_bytes', 'qasr_pw_conv_acc',
@@ -133,6 +133,8 @@ def load_library():
     lib.qasr_engine_run_op.argtypes = [vp, vp, i32]
     lib.qasr_engine_op_label.argtypes = [vp, i32, C.c_char_p, sz]
     lib.qasr_engine_op_paired.argtypes = [vp, i32]
+    if hasattr(lib, 'qasr_engine_op_halved'):   # (a QASR_LIB A/B build of an older tree lacks it)
+        lib.qasr_engine_op_halved.argtypes = [vp, i32]
     lib.qasr_engine_pair_timeouts.argtypes = [vp]
     if hasattr(lib, 'qasr_engine_pair_flag_words'):   # (a QASR_LIB A/B build of an older tree lacks it)
         lib.qasr_engine_pair_flag_words.argtypes = [vp, vp, sz]
@@ -2168,6 +2170,10 @@ class Engine:
     def op_paired(self):
         """per op: does it run in the paired form (qasr_engine_opts.pair_split; after a forward)"""
         return [self.lib.qasr_engine_op_paired(self._h, op) == 1 for op in range(self.n_ops)]
+
+    def op_halved(self):
+        """per op: does it run in the halved form, a 128-frame tile as two 64-frame work-groups (QASR_HALF_TILES; after a forward)"""
+        return [self.lib.qasr_engine_op_halved(self._h, op) == 1 for op in range(self.n_ops)]
 
     def pair_timeouts(self):
         """the time-out word of paired launches (synchronises).  Always 0: the members of a pair exchange nothing any more"""
