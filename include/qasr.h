@@ -789,6 +789,47 @@ typedef struct qasr_edit_args {
 size_t qasr_edit_workspace_bytes(int P, int max_hyp, int max_ref, int mode);
 int qasr_edit_distance(void* stream, const qasr_edit_args* args);
 
+/* ---- the edit path: which unit became which ----------------------------------------------------------------------------------
+ * qasr_edit_distance's rows, units, validity and recurrence, with the path the recurrence picks written out (TRACE_RULES of
+ * qasr/edit.py, which k_edit_trace follows byte for byte).  The path runs from cell (hyp_units, ref_units) back to (0, 0): at
+ * i == 0 a deletion, at j == 0 an insertion, otherwise the predecessor the cell took - the diagonal first, the deletion
+ * (i, j - 1) only when strictly cheaper, the insertion (i - 1, j) only when strictly cheaper than that.
+ *   ops u8 [B * K][ops_pitch], in FORWARD order: 0 hit and 1 substitution (one unit of each row), 2 deletion (a reference
+ *   unit), 3 insertion (a hypothesis unit).  n_ops i32 [B * K]; bytes at and behind n_ops[p] are left as they are; rows with
+ *   ok != 1 have n_ops = 0 and nothing written.  The numbers of codes 1 / 2 / 3 are rows[p][1 / 2 / 3], that of code 0 is
+ *   ref_units - S - D, n_ops = ref_units + I <= hyp_units + ref_units.
+ *   rows i32 [B * K][8]: qasr_edit_distance's, byte for byte.  There is no totals block: sum with qasr_edit_distance.
+ * Two launches on `stream`: k_edit_cut, as above, and k_edit_trace<MODE, NC> (one wave per problem: k_edit's frame step with
+ * the choice of every cell, 2 bits, stored step-major to a plane in the workspace, then the walk by the same wave, which
+ * reads the plane in blocks and writes the ops to their forward places).  No atomics, plain vector stores, nothing allocated
+ * and nothing read on the host: capturable.  ops_pitch >= HU + RU, the unit bounds of the two widths: max_hyp (max_ref) in
+ * char mode, (max_hyp + 1) / 2 in word mode.  workspace: 16-byte aligned device memory of
+ * qasr_edit_trace_workspace_bytes(B * K, max_hyp, max_ref, mode) bytes (0: a shape the call refuses) - about HU * RU / 4 bytes
+ * per problem (64 HU when RU <= 64) -, one per call in flight.
+ * QASR_ERR_ARG with nothing launched and nothing written: what qasr_edit_distance refuses (totals aside), ops or n_ops NULL,
+ * ops_pitch < HU + RU. */
+typedef struct qasr_edit_trace_args {
+  uint32_t struct_size;        /* sizeof of this struct in the caller's header */
+  int32_t mode;                /* QASR_EDIT_CHAR / QASR_EDIT_WORD */
+  int32_t B, K, C;             /* references, hypothesis rows per reference, classes */
+  int32_t max_hyp, max_ref;    /* ids per row */
+  int32_t pad_;
+  int64_t hyp_pitch, ref_pitch, ops_pitch;   /* in int32, int32, bytes */
+  const int32_t* hyp;          /* [B * K][hyp_pitch] */
+  const int32_t* hyp_lens;     /* optional [B * K] */
+  const int32_t* ref;          /* [B][ref_pitch] */
+  const int32_t* ref_lens;     /* optional [B] */
+  const int32_t* n_hyps;       /* optional [B] */
+  const uint8_t* is_space;     /* [C]; word mode */
+  int32_t* rows;               /* [B * K][8], = qasr_edit_distance's */
+  uint8_t* ops;                /* [B * K][ops_pitch] */
+  int32_t* n_ops;              /* [B * K] */
+  void* workspace;
+  size_t workspace_bytes;
+} qasr_edit_trace_args;
+size_t qasr_edit_trace_workspace_bytes(int P, int max_hyp, int max_ref, int mode);
+int qasr_edit_trace(void* stream, const qasr_edit_trace_args* args);
+
 /* ---- audio at any sample rate: rational polyphase resampler and PCM ingest -----------------------------------------------
  * What AudioSegment.__init__ does on the host with librosa.core.resample when target_sr != sample_rate (parts/segment.py:
  * 57-59), as one kernel, k_resample, in front of the mel front-end: int16 PCM (mono or interleaved channels) or float32 at an

@@ -1534,8 +1534,8 @@ int qasr_ctc_spot(void* stream, const qasr_ctc_spot_args* a) {
   return launched("ctc_spot", launch_spot((hipStream_t)stream, *a));
 }
 
-// ---- word and character error counts (k_edit_cut, k_edit, k_edit_totals, qasr_edit.hip): the checks of include/qasr.h, then
-// three launches
+// ---- word and character error counts (k_edit_cut, k_edit, k_edit_totals, qasr_edit.hip) and the edit path (k_edit_cut,
+// k_edit_trace): the checks of include/qasr.h, stated once for the two entry points, then the launches
 static bool edit_shape_ok(long long P, int max_hyp, int max_ref, int mode) {
   return P >= 1 && P <= QASR_EDIT_MAX_PROBLEMS && max_hyp >= 1 && max_hyp <= QASR_EDIT_MAX_IDS && max_ref >= 1 &&
          max_ref <= QASR_EDIT_MAX_IDS && (mode == QASR_EDIT_CHAR || mode == QASR_EDIT_WORD);
@@ -1543,26 +1543,45 @@ static bool edit_shape_ok(long long P, int max_hyp, int max_ref, int mode) {
 size_t qasr_edit_workspace_bytes(int P, int max_hyp, int max_ref, int mode) {
   return edit_shape_ok(P, max_hyp, max_ref, mode) ? edit_workspace_bytes(P, max_hyp, max_ref, mode) : 0;
 }
-int qasr_edit_distance(void* stream, const qasr_edit_args* a) {
-  if (int rc = args_check("edit_distance", a)) return rc;
-  if (!a->hyp || !a->ref || !a->rows || !a->totals || !a->workspace)
-    return fail(QASR_ERR_ARG, "edit_distance: hyp, ref, rows, totals and workspace are required");
+size_t qasr_edit_trace_workspace_bytes(int P, int max_hyp, int max_ref, int mode) {
+  return edit_shape_ok(P, max_hyp, max_ref, mode) ? edit_trace_workspace_bytes(P, max_hyp, max_ref, mode) : 0;
+}
+// what the two args structs share: the struct itself, the rows, the mode, the shape, the pitches, the workspace (`need`: the
+// entry's own query) and the alignment of workspace and rows; `extra`: the entry's further required pointers, named in `names`
+extern "C++" {
+template <class A>
+static int edit_check(const char* who, const A* a, bool extra, const char* names, size_t (*need_of)(long long, int, int, int)) {
+  if (int rc = args_check(who, a)) return rc;
+  if (!a->hyp || !a->ref || !a->rows || !extra || !a->workspace) return fail(QASR_ERR_ARG, "%s: %s and workspace are required", who, names);
   if (a->mode != QASR_EDIT_CHAR && a->mode != QASR_EDIT_WORD)
-    return fail(QASR_ERR_ARG, "edit_distance: mode %d is neither QASR_EDIT_CHAR nor QASR_EDIT_WORD", a->mode);
-  if (a->mode == QASR_EDIT_WORD && !a->is_space) return fail(QASR_ERR_ARG, "edit_distance: word mode needs is_space");
+    return fail(QASR_ERR_ARG, "%s: mode %d is neither QASR_EDIT_CHAR nor QASR_EDIT_WORD", who, a->mode);
+  if (a->mode == QASR_EDIT_WORD && !a->is_space) return fail(QASR_ERR_ARG, "%s: word mode needs is_space", who);
   const long long P = (long long)a->B * a->K;
   if (a->B < 1 || a->K < 1 || a->C < 1 || P > QASR_EDIT_MAX_PROBLEMS)
-    return fail(QASR_ERR_ARG, "edit_distance: B %d, K %d or C %d < 1, or B * K above %d", a->B, a->K, a->C, QASR_EDIT_MAX_PROBLEMS);
+    return fail(QASR_ERR_ARG, "%s: B %d, K %d or C %d < 1, or B * K above %d", who, a->B, a->K, a->C, QASR_EDIT_MAX_PROBLEMS);
   if (!edit_shape_ok(P, a->max_hyp, a->max_ref, a->mode))
-    return fail(QASR_ERR_ARG, "edit_distance: max_hyp %d or max_ref %d is outside 1 .. %d", a->max_hyp, a->max_ref, QASR_EDIT_MAX_IDS);
+    return fail(QASR_ERR_ARG, "%s: max_hyp %d or max_ref %d is outside 1 .. %d", who, a->max_hyp, a->max_ref, QASR_EDIT_MAX_IDS);
   if (a->hyp_pitch < a->max_hyp || a->ref_pitch < a->max_ref)
-    return fail(QASR_ERR_ARG, "edit_distance: hyp_pitch %lld < max_hyp %d or ref_pitch %lld < max_ref %d", (long long)a->hyp_pitch,
+    return fail(QASR_ERR_ARG, "%s: hyp_pitch %lld < max_hyp %d or ref_pitch %lld < max_ref %d", who, (long long)a->hyp_pitch,
                 a->max_hyp, (long long)a->ref_pitch, a->max_ref);
-  const size_t need = edit_workspace_bytes(P, a->max_hyp, a->max_ref, a->mode);
-  if (a->workspace_bytes < need) return fail(QASR_ERR_ARG, "edit_distance: workspace_bytes %zu < %zu", a->workspace_bytes, need);
-  if (((uintptr_t)a->workspace | (uintptr_t)a->rows) & 15 || (uintptr_t)a->totals & 7)
-    return fail(QASR_ERR_ARG, "edit_distance: workspace and rows must be 16-byte aligned, totals 8-byte aligned");
+  const size_t need = need_of(P, a->max_hyp, a->max_ref, a->mode);
+  if (a->workspace_bytes < need) return fail(QASR_ERR_ARG, "%s: workspace_bytes %zu < %zu", who, a->workspace_bytes, need);
+  if (((uintptr_t)a->workspace | (uintptr_t)a->rows) & 15) return fail(QASR_ERR_ARG, "%s: workspace and rows must be 16-byte aligned", who);
+  return QASR_OK;
+}
+}  // extern "C++"
+int qasr_edit_distance(void* stream, const qasr_edit_args* a) {
+  if (int rc = edit_check("edit_distance", a, a && a->totals, "hyp, ref, rows, totals", edit_workspace_bytes)) return rc;
+  if ((uintptr_t)a->totals & 7) return fail(QASR_ERR_ARG, "edit_distance: totals must be 8-byte aligned");
   return launched("edit_distance", launch_edit((hipStream_t)stream, *a));
+}
+int qasr_edit_trace(void* stream, const qasr_edit_trace_args* a) {
+  if (int rc = edit_check("edit_trace", a, a && a->ops && a->n_ops, "hyp, ref, rows, ops, n_ops", edit_trace_workspace_bytes)) return rc;
+  const long long units = (a->mode == QASR_EDIT_WORD ? ((long long)a->max_hyp + 1) / 2 + ((long long)a->max_ref + 1) / 2
+                                                     : (long long)a->max_hyp + a->max_ref);
+  if (a->ops_pitch < units) return fail(QASR_ERR_ARG, "edit_trace: ops_pitch %lld < %lld units of the two rows", (long long)a->ops_pitch, units);
+  if ((uintptr_t)a->n_ops & 3) return fail(QASR_ERR_ARG, "edit_trace: n_ops must be 4-byte aligned");
+  return launched("edit_trace", launch_edit_trace((hipStream_t)stream, *a));
 }
 
 // ---- polyphase resampler (k_resample, qasr_resample.hip): host-only validation of a packed table (qasr/resample.py states

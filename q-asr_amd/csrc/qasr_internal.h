@@ -195,6 +195,9 @@ int launch_spot(hipStream_t s, const qasr_ctc_spot_args& a);
 // qasr_edit.hip: word and character error counts (k_edit_cut, k_edit, k_edit_totals); checked by qasr_edit_distance
 size_t edit_workspace_bytes(long long P, int max_hyp, int max_ref, int mode);
 int launch_edit(hipStream_t s, const qasr_edit_args& a);
+// the edit path (k_edit_cut, k_edit_trace); checked by qasr_edit_trace
+size_t edit_trace_workspace_bytes(long long P, int max_hyp, int max_ref, int mode);
+int launch_edit_trace(hipStream_t s, const qasr_edit_trace_args& a);
 // qasr_resample.hip: rational polyphase resampler (k_resample); the arguments are checked by qasr_resample
 int launch_resample(hipStream_t s, const qasr_resample_args& a);
 // qasr_longform.hip: windows of long recordings cut (k_cut) and stitched (k_stitch); the arguments are checked by the callers

@@ -92,6 +92,12 @@ def main():
     p.add_argument("--n_best", type=int, default=None, metavar='K',
                    help="(extension, needs --device_wer and --beam_width) rows of the beam scored per utterance for `oracle WER:`")
     p.add_argument("--cer", action='store_true', help="(extension) character error rate: WER is computed over characters")
+    p.add_argument("--alignments", type=str, default=None, metavar='OUT',
+                   help="(extension, needs --device_wer) which words were wrong: the edit path of every utterance's best "
+                        "hypothesis from the device (k_edit_trace behind k_edit; with --stream_chunk_s or --window_s through "
+                        "qasr.edit.align_texts on the device).  OUT gets per manifest entry the audio path, the counts and the "
+                        "two-line REF: / HYP: listing (characters with --cer), then the 20 most frequent substitution pairs, "
+                        "deletions and insertions of the run; WER and the other outputs are unchanged")
     p.add_argument("--align", type=str, default=None, metavar='OUT',
                    help="(extension) forced alignment of every manifest line's reference text against its batch's "
                         "log-probabilities (EncDecCTCModel.align): OUT gets one JSON line per utterance - audio_filepath, text, "
@@ -197,6 +203,8 @@ def main():
         p.error(f'--spot_threshold must be -16 .. 0, got {args.spot_threshold}')
     if args.overlap_s is not None and args.window_s is None:
         p.error('--overlap_s needs --window_s')
+    if args.alignments is not None and not args.device_wer:
+        p.error('--alignments OUT needs --device_wer')
     if args.n_best is not None and (not args.device_wer or args.beam_width is None or not 1 <= args.n_best <= args.beam_width):
         p.error('--n_best K needs --device_wer and --beam_width W, 1 <= K <= W')
     if args.star_token is not None and (args.align is None or args.shuffle):
@@ -303,6 +311,7 @@ def main():
         from qasr import boost as qboost
         lm_kw['boost'] = qboost.PhraseSet(qboost.read_phrase_file(args.boost_file), asr_model.decoder.vocabulary, weight=boost_weight)
     aligned, items = [], getattr(asr_model.test_dataloader().dataset, 'items', [])
+    listed = []                                              # --alignments: one qasr.ctc.Alignment (or None) per utterance
     spotted, spot_words = [], []
     if args.spot is not None:                                # read once for the run: the list does not change per batch
         with open(args.spot_file, encoding='utf-8') as f:
@@ -396,9 +405,11 @@ def main():
                     utt_scores.append(h.utt_score)
         elif args.beam_width is not None:                    # k_topn + k_beam behind the forward, on the same stream
             if args.device_wer:                              # ... and k_edit behind them: only the counts are read back
-                _add_report(dev_counts, asr_model.error_rate(input_signal=signal, input_signal_length=batch[1], targets=batch[2],
-                                                             use_cer=args.cer, beam_width=args.beam_width,
-                                                             n_best=args.n_best or 1, **lm_kw, **rate_kw))
+                rep = asr_model.error_rate(input_signal=signal, input_signal_length=batch[1], targets=batch[2], use_cer=args.cer,
+                                           beam_width=args.beam_width, n_best=args.n_best or 1,
+                                           alignments=args.alignments is not None, **lm_kw, **rate_kw)
+                _add_report(dev_counts, rep)
+                listed += rep.alignments or []               # --alignments: k_edit_trace over the best rows
             for h in (asr_model.decode(input_signal=signal, input_signal_length=batch[1], beam_width=args.beam_width,
                                        **lm_kw, **rate_kw) if need_text else ()):
                 hyps.append(h.text)
@@ -411,6 +422,17 @@ def main():
                 dev_wer.update(greedy, batch[2], None)
             if need_text:
                 hyps += wer.ctc_decoder_predictions_tensor(greedy)
+            if args.alignments is not None:                  # the rows dev_wer scored (k_ctc over the padded rows), through k_edit_trace
+                from qasr import edit as qedit, engine as qengine
+                vocab, mode = list(asr_model.decoder.vocabulary), 'char' if args.cer else 'word'
+                mask = None if args.cer else qedit.space_mask(vocab, '--alignments')
+                col = qengine.ctc_collapse(greedy, lens=None, blank=dev_wer.blank_id)
+                tg = batch[2] if batch[2].shape[1] else torch.zeros(batch[2].shape[0], 1, device=greedy.device, dtype=torch.int32)
+                tr = qedit.trace_device(col.labels, col.n_labels, tg, None, len(vocab), mode=mode,
+                                        is_space=None if mask is None else torch.from_numpy(mask).cuda())
+                cpu = lambda t: t.cpu().numpy()
+                listed += qedit.alignments_of(qedit.TraceResult(cpu(tr.rows), cpu(tr.ops), cpu(tr.n_ops), 1), cpu(col.labels),
+                                              cpu(col.n_labels), cpu(tg), None, vocab, mode=mode, is_space=mask)
         if args.timestamps and args.window_s is None and args.stream_chunk_s is None:        # device-side collapse up to each utterance's encoded length
             for h in asr_model.decode(input_signal=signal, input_signal_length=batch[1], **rate_kw):
                 words.append([list(w) for w in h.words])
@@ -473,6 +495,9 @@ def main():
             c = error_counts(hyps[-n:], refs[-n:], use_cer=args.cer, device='cuda')
             for k, v in enumerate((c.errors, c.substitutions, c.deletions, c.insertions, c.ref_units, c.hyp_units, c.errors)):
                 dev_counts[k] += v
+            if args.alignments is not None:
+                from qasr.edit import align_texts
+                listed += align_texts(hyps[-n:], refs[-n:], use_cer=args.cer, device='cuda')
         audio_s += float(batch[1].sum()) / float(args.input_rate or 16000)
     torch.cuda.synchronize()
     wall = time.time() - t0
@@ -509,6 +534,22 @@ def main():
             if stream_sess is not None and stream_sess.endpoint is not None:
                 extra.update(utterances=n_utterances)
             json.dump(dict(hypotheses=hyps, references=refs, wer=wer_value, path=served, **extra), f)
+    if args.alignments:
+        from qasr.edit import confusions, listing
+        with open(args.alignments, 'w', encoding='utf-8') as f:
+            for k, a in enumerate(listed):
+                f.write(f'{items[k][0] if not args.shuffle and k < len(items) else None}\n')
+                if a is None:                                    # a row the kernel refused: an id outside the vocabulary
+                    f.write('not scored\n\n')
+                    continue
+                c = a.counts
+                f.write(f'errors {c.errors}  S {c.substitutions}  D {c.deletions}  I {c.insertions}  ref {c.ref_units}  hyp {c.hyp_units}\n')
+                f.write(listing(a) + '\n\n')
+            sub, dele, ins = confusions(listed, top=20)
+            f.write('substitutions (ref -> hyp):\n' + ''.join(f'{n:6d}  {r!r} -> {h!r}\n' for (r, h), n in sub))
+            f.write('deletions:\n' + ''.join(f'{n:6d}  {u!r}\n' for u, n in dele))
+            f.write('insertions:\n' + ''.join(f'{n:6d}  {u!r}\n' for u, n in ins))
+        print(f'listed {len(listed)} alignments -> {args.alignments}')
     if args.align:
         import json
         with open(args.align, 'w', encoding='utf-8') as f:

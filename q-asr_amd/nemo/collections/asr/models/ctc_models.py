@@ -720,9 +720,10 @@ class EncDecCTCModel(nn.Module):
             targets, target_lengths = torch.zeros(n, 1, dtype=torch.int32), torch.zeros(n, dtype=torch.int32)
         return targets.to(device), None if target_lengths is None else target_lengths.to(device)
 
-    def _score_rows(self, who, res, targets, target_lengths, texts, use_cer):
+    def _score_rows(self, who, res, targets, target_lengths, texts, use_cer, alignments=False, max_workspace_bytes=1 << 30):
         """error_rate behind any decode chain: the CtcResult's or BeamResult's label rows against the references through k_edit
-        (cuda) or its twin; only the counts are read back"""
+        (cuda) or its twin; only the counts are read back.  alignments: the best rows (k = 0) also go through k_edit_trace or
+        its twin, and ops, n_ops and the label rows are read back for the report's Alignments"""
         from qasr import edit as qedit
         vocab = self.decoder.vocabulary
         labels, n_labels = res.labels, res.n_labels
@@ -743,11 +744,26 @@ class EncDecCTCModel(nn.Module):
             out = qedit.edit_host(host(hyp), host(hl), host(tg), host(tl), len(vocab), mode=mode, is_space=mask, rows_per_ref=K,
                                   n_hyps=host(n_hyps))
             rows, totals = out.rows, out.totals
-        return qedit.report_of(rows, totals, K)
+        rep = qedit.report_of(rows, totals, K)
+        if alignments:
+            hyp0, hl0 = (hyp, hl) if K == 1 else (labels[:, 0], n_labels[:, 0])          # the k = 0 rows, where they lie
+            n0 = None if n_hyps is None else (n_hyps.clamp(max=1) if torch.is_tensor(n_hyps) else np.minimum(n_hyps, 1))
+            if cuda:
+                tr = qedit.trace_device(hyp0, hl0, tg, tl, len(vocab), mode=mode, is_space=sp, n_hyps=n0,
+                                        max_workspace_bytes=max_workspace_bytes)
+                cpu = lambda t: None if t is None else t.cpu().numpy()
+                tr = qedit.TraceResult(rows.reshape(n, K, -1)[:, 0], cpu(tr.ops), cpu(tr.n_ops), 1)    # the rows are k_edit's
+            else:
+                cpu = host
+                tr = qedit.trace_host(cpu(hyp0), cpu(hl0), cpu(tg), cpu(tl), len(vocab), mode=mode, is_space=mask, n_hyps=cpu(n0),
+                                      max_workspace_bytes=max_workspace_bytes)
+            rep.alignments = qedit.alignments_of(tr, cpu(hyp0), cpu(hl0), cpu(tg), cpu(tl), list(vocab), mode=mode, is_space=mask)
+        return rep
 
     @torch.no_grad()
     def error_rate(self, input_signal=None, input_signal_length=None, targets=None, target_lengths=None, texts=None, use_cer=False,
-                   beam_width=None, n_best=1, processed_signal=None, processed_signal_length=None, **decode_args):
+                   beam_width=None, n_best=1, processed_signal=None, processed_signal_length=None, alignments=False,
+                   max_workspace_bytes=1 << 30, **decode_args):
         """Word (use_cer: character) error counts of one batch against its references (an extension): decode()'s device
         chain - greedy, or the beam search with beam_width / n_best and decode()'s cutoff_top_n, lm, alpha, beta, boost,
         boost_weight, sample_rate, channels - then the edit distance over the label rows where they lie (k_edit;
@@ -756,24 +772,27 @@ class EncDecCTCModel(nn.Module):
         fewest errors among their K rows.  References: targets int [B, L] with target_lengths (None: the padded rows), or
         texts.  The numbers are word_error_rate's over decode()'s texts.  Works on the static engine, a reserved engine, the
         dynamic path, and through the NumPy twin with the host modules or CPU tensors.  Word mode needs a vocabulary of
-        single characters."""
+        single characters.  alignments=True: the report also carries one qasr.ctc.Alignment per utterance for its best row
+        (k_edit_trace, qasr.edit.TRACE_RULES; ops, n_ops and the label rows are read back); a batch whose back-pointer plane
+        would exceed max_workspace_bytes is refused by name."""
         for k in ('timestamps', 'posteriors', '_rows'):
             if k in decode_args:
                 raise ValueError(f'error_rate: {k} is not an argument of the error rate')
         res = self.decode(input_signal, input_signal_length, processed_signal, processed_signal_length, beam_width=beam_width,
                           n_best=n_best, _rows=True, **decode_args)
-        return self._score_rows('error_rate', res, targets, target_lengths, texts, use_cer)
+        return self._score_rows('error_rate', res, targets, target_lengths, texts, use_cer, bool(alignments), max_workspace_bytes)
 
     @torch.no_grad()
     def error_rate_long(self, input_signal, input_signal_length, targets=None, target_lengths=None, texts=None, use_cer=False,
-                        beam_width=None, n_best=1, **decode_long_args):
+                        beam_width=None, n_best=1, alignments=False, max_workspace_bytes=1 << 30, **decode_long_args):
         """error_rate behind decode_long's stitched rows: window_s / overlap_s / guard_s / batch_size / seam and the beam
-        arguments as decode_long takes them, one reference per recording."""
+        arguments as decode_long takes them, one reference per recording; alignments / max_workspace_bytes as error_rate's."""
         if '_rows' in decode_long_args:
             raise ValueError('error_rate_long: _rows is not an argument of the error rate')
         res = self.decode_long(input_signal, input_signal_length, beam_width=beam_width, n_best=n_best, _rows=True,
                                **decode_long_args)
-        return self._score_rows('error_rate_long', res, targets, target_lengths, texts, use_cer)
+        return self._score_rows('error_rate_long', res, targets, target_lengths, texts, use_cer, bool(alignments),
+                                max_workspace_bytes)
 
     def _stream_plan(self, chunk_s=0.96, left_s=4.0, right_s=0.96):
         """the qasr.stream.StreamPlan of stream(): units and frames_of taken from the model as _long_plan takes them"""

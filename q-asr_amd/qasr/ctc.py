@@ -141,6 +141,21 @@ class ErrorReport:
     oracle_errors: int
     per_utterance: List[ErrorCounts]
     invalid: int
+    alignments: Optional[List[Optional['Alignment']]] = None   # alignments=True: one per utterance for its best row (None: not scored)
+
+
+@dataclass
+class Alignment:
+    """The edit path of one hypothesis against its reference (qasr.edit.TRACE_RULES): ops over 'CSDI' - correct, substitution,
+    deletion, insertion - in forward order; ref_units / hyp_units: the words (characters with use_cer) of the two rows;
+    ref_index / hyp_index: per op the unit it consumes of each row, None opposite an insertion / a deletion -
+    Hypothesis.words[hyp_index[t]] is where an error lies in time; counts: the row's ErrorCounts."""
+    ops: str
+    ref_units: List[str]
+    hyp_units: List[str]
+    ref_index: List[Optional[int]]
+    hyp_index: List[Optional[int]]
+    counts: ErrorCounts
 
 
 def _order_key(x):

@@ -56,6 +56,25 @@ class EditResult:
     ok = property(lambda s: s.rows[:, 6])
 
 
+TRACE_RULES = """The edit path behind EDIT_RULES: which hypothesis unit met which reference unit.  Rows, units, validity, recurrence and the
+per-problem int32 [P, 8] are EDIT_RULES', byte for byte; there is no totals block.
+The path runs from cell (n, m) - n hypothesis units, m reference units - back to (0, 0).  At i == 0 the step is a deletion, at
+j == 0 an insertion; otherwise it goes to the predecessor the recurrence picked for the cell: the diagonal first, then the deletion
+(i, j - 1) only when strictly cheaper, then the insertion (i - 1, j) only when strictly cheaper than that - the order in which
+EDIT_RULES' cells took their (cost, S, D).
+ops uint8 [P, ops_pitch], ops_pitch >= HU + RU (the unit bounds of the two widths: width in char mode, (width + 1) // 2 in word
+mode), in FORWARD order, first unit first.  Codes: 0 a hit and 1 a substitution, each consuming one unit of each row; 2 a
+deletion, consuming a reference unit; 3 an insertion, consuming a hypothesis unit.  n_ops int32 [P]: the path's length.  Bytes at
+and behind n_ops[p] are left as they are; a caller's ops array is written into.  Rows with ok != 1 have n_ops = 0 and nothing
+written.
+Invariants: the numbers of codes 1 / 2 / 3 in ops[p, :n_ops[p]] are rows[p, 1 / 2 / 3] (S / D / I), the number of code 0 is
+ref_units - S - D, and n_ops = ref_units + I <= hyp_units + ref_units.
+Workspace of the device call (trace_workspace_bytes): the choices of all cells, 2 bits each, about HU * RU / 4 bytes per problem
+(64 HU when RU <= 64); entry points refuse a shape that needs more than max_workspace_bytes, naming the bytes."""
+OP_CODES = 'CSDI'                       # ops code -> the letter of Alignment.ops: correct, substitution, deletion, insertion
+MAX_WORKSPACE = 1 << 30                 # max_workspace_bytes of the Python entry points
+
+
 def check_mode(mode, who) -> int:
     if mode not in MODES:
         raise ValueError(f"{who}: mode must be 'char' or 'word', got {mode!r}")
@@ -190,6 +209,194 @@ def edit_host(hyp, hyp_lens, ref, ref_lens, n_classes, mode='char', is_space=Non
     return EditResult(rows, tot, K)
 
 
+@dataclass
+class TraceResult:
+    """Outputs of TRACE_RULES (NumPy on the host, torch tensors from the device binding): rows int32 [P, 8], ops uint8
+    [P, ops_pitch], n_ops int32 [P]; rows_per_ref = K."""
+    rows: object
+    ops: object
+    n_ops: object
+    rows_per_ref: int = 1
+
+
+def unit_bound(width, mode) -> int:
+    """the most units a row of `width` ids holds (edit_units of qasr_edit.hip); mode: 0 char / 1 word"""
+    return (int(width) + 1) // 2 if mode == 1 else int(width)
+
+
+def trace_workspace_bytes(P, max_hyp, max_ref, mode) -> int:
+    """qasr_edit_trace_workspace_bytes, stated on the host (mode: 'char' / 'word'): qasr_edit_distance's workspace, then per
+    problem a plane of one word per lane and step - strips of 64 NC reference units, HU + 63 steps each, NC = 1 / 4 / 16 from RU"""
+    md = check_mode(mode, 'trace_workspace_bytes')
+    up16 = lambda x: (x + 15) & ~15
+    P, HU, RU = int(P), unit_bound(max_hyp, md), unit_bound(max_ref, md)
+    at = up16(P * 16)
+    if md == 1:
+        at += P * HU * 16 + P * RU * 16
+    if RU > 64 * 16:
+        at += up16(P * 3 * (HU + 1) * 4)
+    nc = 1 if RU <= 64 else (4 if RU <= 256 else 16)
+    strips = (RU + 64 * nc - 1) // (64 * nc)
+    return up16(at) + P * up16(strips * (HU + 63) * 64 * (4 if nc == 16 else 1))
+
+
+def check_trace_workspace(P, max_hyp, max_ref, mode, max_workspace_bytes, who):
+    need = trace_workspace_bytes(P, max_hyp, max_ref, mode)
+    if need > int(max_workspace_bytes):
+        raise ValueError(f'{who}: the edit path of {int(P)} problems of {int(max_hyp)} x {int(max_ref)} ids needs a workspace of '
+                         f'{need} bytes, above max_workspace_bytes = {int(max_workspace_bytes)}')
+    return need
+
+
+def _path(hu, ru):
+    """the forward op list (uint8) of TRACE_RULES for unit arrays hu [n], ru [m] (int64) and the last cell's cost: _triple's
+    anti-diagonals with the pick of every cell kept in a plane [n + 1, m + 1], then the walk back"""
+    n, m = len(hu), len(ru)
+    if n == 0 or m == 0:
+        return np.full(n + m, 2 if n == 0 else 3, dtype=np.uint8), n + m
+    pick = np.zeros((n + 1, m + 1), dtype=np.uint8)
+    c2 = np.zeros(n + 1, dtype=np.int64)                            # diagonal 0: the cell (0, 0)
+    c1 = np.zeros(n + 1, dtype=np.int64)                            # diagonal 1
+    c1[0], c1[1] = 1, 1
+    for d in range(2, n + m + 1):
+        c0 = np.zeros(n + 1, dtype=np.int64)
+        i = np.arange(max(1, d - m), min(n, d - 1) + 1)             # the cells with i >= 1 and j = d - i >= 1
+        if len(i):
+            neq = (hu[i - 1] != ru[d - i - 1]).astype(np.int64)
+            cost, op = c2[i - 1] + neq, neq.astype(np.uint8)
+            t = c1[i] + 1 < cost                                    # the deletion, from (i, j - 1): only when strictly cheaper
+            cost[t], op[t] = c1[i][t] + 1, 2
+            t = c1[i - 1] + 1 < cost                                # the insertion, from (i - 1, j)
+            cost[t], op[t] = c1[i - 1][t] + 1, 3
+            c0[i], pick[i, d - i] = cost, op
+        if d <= m:
+            c0[0] = d
+        if d <= n:
+            c0[d] = d
+        c2, c1 = c1, c0
+    back, i, j = [], n, m
+    while i > 0 or j > 0:
+        op = 2 if i == 0 else (3 if j == 0 else int(pick[i, j]))
+        back.append(op)
+        i, j = i - (op != 2), j - (op != 3)
+    return np.array(back[::-1], dtype=np.uint8), int(c1[n])
+
+
+def trace_host(hyp, hyp_lens, ref, ref_lens, n_classes, mode='char', is_space=None, rows_per_ref=1, n_hyps=None, ops=None,
+               max_workspace_bytes=MAX_WORKSPACE) -> TraceResult:
+    """TRACE_RULES on the host: edit_host's arguments and rows; ops: a uint8 [P, >= HU + RU] array to write into (None: a
+    zeroed one of the least pitch)."""
+    who = 'trace_host'
+    md = check_mode(mode, who)
+    hyp, ref = np.asarray(hyp), np.asarray(ref)
+    if hyp.ndim == 2 and ref.ndim == 2:                             # the cap before any work; edit_host refuses the other shapes
+        check_trace_workspace(hyp.shape[0], hyp.shape[1], ref.shape[1], mode, max_workspace_bytes, who)
+    res = edit_host(hyp, hyp_lens, ref, ref_lens, n_classes, mode=mode, is_space=is_space, rows_per_ref=rows_per_ref, n_hyps=n_hyps)
+    P, K = hyp.shape[0], int(rows_per_ref)
+    units = unit_bound(hyp.shape[1], md) + unit_bound(ref.shape[1], md)
+    if ops is None:
+        ops = np.zeros((P, units), dtype=np.uint8)
+    if not isinstance(ops, np.ndarray) or ops.dtype != np.uint8 or ops.ndim != 2 or ops.shape[0] != P or ops.shape[1] < units:
+        raise ValueError(f'{who}: ops must be a uint8 array [{P}, >= {units}] (the unit bounds of the two widths)')
+    n_ops = np.zeros(P, dtype=np.int32)
+    ids = {}
+    number = lambda us: np.array([ids.setdefault(u, len(ids)) for u in us], dtype=np.int64)
+    sp = None if is_space is None else np.asarray(is_space)
+    for p in range(P):
+        if res.rows[p, 6] != 1:
+            continue
+        b = p // K
+        nh = hyp.shape[1] if hyp_lens is None else int(hyp_lens[p])
+        nr = ref.shape[1] if ref_lens is None else int(ref_lens[b])
+        path, cost = _path(number(_row_units(hyp[p], nh, md, sp)), number(_row_units(ref[b], nr, md, sp)))
+        assert cost == res.rows[p, 0] and len(path) == res.rows[p, 4] + res.rows[p, 3], (p, cost, len(path))
+        ops[p, :len(path)], n_ops[p] = path, len(path)
+    return TraceResult(res.rows, ops, n_ops, K)
+
+
+def trace_device(hyp, hyp_lens, ref, ref_lens, n_classes, mode='char', is_space=None, rows_per_ref=1, n_hyps=None, ops=None,
+                 workspace=None, out=None, stream=None, max_workspace_bytes=MAX_WORKSPACE) -> TraceResult:
+    """TRACE_RULES on the device (qasr_edit_trace: two launches on the current stream, nothing read back): cuda matrices as for
+    edit_device; ops: a cuda uint8 [P, >= HU + RU] to write into.  Returns a TraceResult of cuda tensors."""
+    from . import engine
+    return engine.edit_trace(hyp, hyp_lens, ref, ref_lens, n_classes, mode=mode, is_space=is_space, rows_per_ref=rows_per_ref,
+                             n_hyps=n_hyps, ops=ops, workspace=workspace, out=out, stream=stream,
+                             max_workspace_bytes=max_workspace_bytes)
+
+
+def alignments_of(trace, hyp, hyp_lens, ref, ref_lens, vocabulary, mode='char', is_space=None):
+    """One qasr.ctc.Alignment per problem of a TraceResult from host copies (NumPy) of its arrays and of the label rows it was
+    made from; None for a problem with ok != 1.  A unit's text is the vocabulary entries of its ids, joined."""
+    from .ctc import Alignment
+    md = check_mode(mode, 'alignments_of')
+    rows, ops, n_ops = np.asarray(trace.rows), np.asarray(trace.ops), np.asarray(trace.n_ops)
+    hyp, ref, K = np.asarray(hyp), np.asarray(ref), int(trace.rows_per_ref)
+    sp = None if is_space is None else np.asarray(is_space)
+    text = (lambda u: vocabulary[u]) if md == 0 else (lambda u: ''.join(vocabulary[c] for c in u))
+    out = []
+    for p in range(rows.shape[0]):
+        if rows[p, 6] != 1:
+            out.append(None)
+            continue
+        b = p // K
+        nh = hyp.shape[1] if hyp_lens is None else int(hyp_lens[p])
+        nr = ref.shape[1] if ref_lens is None else int(ref_lens[b])
+        hu = [text(u) for u in _row_units(hyp[p], nh, md, sp)]
+        ru = [text(u) for u in _row_units(ref[b], nr, md, sp)]
+        codes = ops[p, :int(n_ops[p])].tolist()
+        ri, hi, i, j = [], [], 0, 0
+        for c in codes:
+            ri.append(j if c != 3 else None)
+            hi.append(i if c != 2 else None)
+            i, j = i + (c != 2), j + (c != 3)
+        if i != len(hu) or j != len(ru):
+            raise RuntimeError(f'alignments_of: the ops of problem {p} consume {i} x {j} units, its rows hold {len(hu)} x {len(ru)}')
+        r = rows[p]
+        out.append(Alignment(''.join(OP_CODES[c] for c in codes), ru, hu, ri, hi, counts_of(r[0], r[1], r[2], r[3], r[4], r[5])))
+    return out
+
+
+def listing(alignment) -> str:
+    """The two-line listing of an Alignment as sclite prints it: one column per op, padded to equal width and joined by one
+    blank; substituted, deleted and inserted units in upper case, correct ones as they are; `*` fillers of the unit's length
+    opposite an insertion or a deletion; a whitespace unit (character mode) shows as `_`."""
+    show = lambda u: ''.join('_' if ch.isspace() else ch for ch in u)
+    top, bot = [], []
+    for op, ri, hi in zip(alignment.ops, alignment.ref_index, alignment.hyp_index):
+        r = show(alignment.ref_units[ri]) if ri is not None else None
+        h = show(alignment.hyp_units[hi]) if hi is not None else None
+        if op == 'C':
+            a, b = r, h
+        elif op == 'S':
+            a, b = r.upper(), h.upper()
+        elif op == 'D':
+            a, b = r.upper(), '*' * len(r)
+        else:
+            a, b = '*' * len(h), h.upper()
+        w = max(len(a), len(b))
+        top.append(a.ljust(w)), bot.append(b.ljust(w))
+    return ('REF: ' + ' '.join(top)).rstrip() + '\n' + ('HYP: ' + ' '.join(bot)).rstrip()
+
+
+def confusions(alignments, top=None):
+    """(substitutions, deletions, insertions) over Alignments (None entries skipped): lists of ((ref, hyp), count), (unit, count)
+    and (unit, count), the most frequent first and equal counts in the order of the units; top: at most that many of each."""
+    sub, dele, ins = {}, {}, {}
+    for a in alignments:
+        if a is None:
+            continue
+        for op, ri, hi in zip(a.ops, a.ref_index, a.hyp_index):
+            if op == 'S':
+                k = (a.ref_units[ri], a.hyp_units[hi])
+                sub[k] = sub.get(k, 0) + 1
+            elif op == 'D':
+                dele[a.ref_units[ri]] = dele.get(a.ref_units[ri], 0) + 1
+            elif op == 'I':
+                ins[a.hyp_units[hi]] = ins.get(a.hyp_units[hi], 0) + 1
+    order = lambda d: sorted(d.items(), key=lambda kv: (-kv[1], kv[0]))[:top]
+    return order(sub), order(dele), order(ins)
+
+
 def counts_of(errors, S, D, I, ref_units, hyp_units):
     """an ErrorCounts with word_error_rate's rate: errors / ref_units, inf for no reference unit"""
     from .ctc import ErrorCounts
@@ -229,6 +436,33 @@ def _pack(texts: Sequence[str], table):
         mat[r, :len(t)] = [table.setdefault(ch, len(table)) for ch in t]
         lens[r] = len(t)
     return mat, lens
+
+
+def align_texts(hyps: List[str], refs: List[str], use_cer=False, device: Optional[str] = None,
+                max_workspace_bytes=MAX_WORKSPACE):
+    """One Alignment per (hypothesis, reference) pair of strings, packed as error_counts packs them: through k_edit_trace on
+    device='cuda' (or a cuda device), where only ops and n_ops are read back beside the rows, and through the twin otherwise."""
+    if len(hyps) != len(refs):
+        raise ValueError("In word error rate calculation, hypotheses and reference lists must have the same "
+                         "number of elements. But I got:{0} and {1} correspondingly".format(len(hyps), len(refs)))
+    if not hyps:
+        return []
+    table = {}
+    h, hl = _pack(hyps, table)
+    r, rl = _pack(refs, table)
+    chars = sorted(table, key=table.get) or [' ']
+    mask = np.array([ch.isspace() for ch in chars], dtype=np.uint8)
+    mode = 'char' if use_cer else 'word'
+    if device is not None and str(device).startswith('cuda'):
+        import torch
+        t = lambda a: torch.from_numpy(a).to(device)
+        res = trace_device(t(h), t(hl), t(r), t(rl), len(chars), mode=mode, is_space=t(mask), max_workspace_bytes=max_workspace_bytes)
+        res = TraceResult(res.rows.cpu().numpy(), res.ops.cpu().numpy(), res.n_ops.cpu().numpy(), 1)
+    else:
+        res = trace_host(h, hl, r, rl, len(chars), mode=mode, is_space=mask, max_workspace_bytes=max_workspace_bytes)
+    if (res.rows[:, 6] != 1).any():
+        raise RuntimeError('align_texts: the edit distance refused a row it packed itself')
+    return alignments_of(res, h, hl, r, rl, chars, mode=mode, is_space=mask)
 
 
 def error_counts(hyps: List[str], refs: List[str], use_cer=False, device: Optional[str] = None):

@@ -29,6 +29,7 @@ SYMBOLS = ['qasr_blob_check', 'qasr_engine_create', 'qasr_engine_create_ex', 'qa
            'qasr_stream_beam_state_bytes', 'qasr_stream_beam', 'qasr_stream_ep_state_bytes', 'qasr_stream_endpoint',
            'qasr_stream_beam_boost_state_bytes', 'qasr_stream_beam_boost', 'qasr_stream_beam_ep',
            'qasr_stream_spot_state_bytes', 'qasr_stream_spot', 'qasr_edit_workspace_bytes', 'qasr_edit_distance',
+           'qasr_edit_trace_workspace_bytes', 'qasr_edit_trace',
            'qasr_last_error', 'qasr_version']
 
 _lib = None
@@ -243,6 +244,10 @@ def load_library():
         lib.qasr_edit_workspace_bytes.argtypes = [i32, i32, i32, i32]
         lib.qasr_edit_workspace_bytes.restype = sz
         lib.qasr_edit_distance.argtypes = [vp, C.POINTER(EditArgs)]
+    if hasattr(lib, 'qasr_edit_trace'):         # (likewise)
+        lib.qasr_edit_trace_workspace_bytes.argtypes = [i32, i32, i32, i32]
+        lib.qasr_edit_trace_workspace_bytes.restype = sz
+        lib.qasr_edit_trace.argtypes = [vp, C.POINTER(EditTraceArgs)]
     lib.qasr_debug_prof.argtypes = [vp]
     lib.qasr_debug_timeline.argtypes = [vp, sz]
     lib.qasr_sep_layer.argtypes = [vp, C.POINTER(SepLayerArgs), C.c_char_p, sz]
@@ -797,18 +802,11 @@ def _edit_rows(who, t, name):
     return t if t.shape[1] == 1 or t.stride(1) == 1 else t.contiguous()
 
 
-def edit_distance(hyp, hyp_lens, ref, ref_lens, n_classes, mode='char', is_space=None, rows_per_ref=1, n_hyps=None, totals=None,
-                  workspace=None, out=None, stream=None):
-    """qasr_edit_distance: word / character error counts on the device (k_edit_cut, k_edit, k_edit_totals: three launches on the
-    current stream, no host synchronisation); equal to qasr.edit.edit_host byte for byte.  hyp: a cuda int32 matrix
-    [B * rows_per_ref, max_hyp], ref [B, max_ref] (rows of any pitch), hyp_lens / ref_lens / n_hyps int32 vectors or None (None
-    lengths: the padded rows); is_space: uint8 [n_classes] (word mode); totals: a cuda int64 [16] block the call adds to (None: a
-    zeroed one); `out`: a caller-owned cuda int32 [B * rows_per_ref, 8].  Returns a qasr.edit.EditResult of cuda tensors."""
-    from .edit import ROW_WORDS, TOTAL_WORDS, EditResult, check_mode, check_widths
-    who = 'edit_distance'
-    lib = load_library()
-    a = EditArgs()
-    a.struct_size, a.mode = C.sizeof(EditArgs), check_mode(mode, who)
+def _edit_fill(who, a, hyp, hyp_lens, ref, ref_lens, n_classes, mode, is_space, rows_per_ref, n_hyps):
+    """What the two edit bindings share, under the call's name `who`: the rows, lengths and mask checked, coerced and written
+    into the struct `a` with the shape and the pitches.  Returns (tensors to keep alive, device, P, max_hyp, max_ref, K)."""
+    from .edit import check_mode, check_widths
+    a.struct_size, a.mode = C.sizeof(type(a)), check_mode(mode, who)
     h, r = _edit_rows(who, hyp, 'hyp'), _edit_rows(who, ref, 'ref')
     dev = h.device
     (P, MH), (B, MR), K = h.shape, r.shape, int(rows_per_ref)
@@ -833,6 +831,23 @@ def edit_distance(hyp, hyp_lens, ref, ref_lens, n_classes, mode='char', is_space
         sp = is_space.to(device=dev, dtype=torch.uint8).contiguous()
         keep.append(sp)
         a.is_space = sp.data_ptr()
+    a.B, a.K, a.C, a.max_hyp, a.max_ref = B, K, int(n_classes), MH, MR
+    a.hyp, a.hyp_pitch, a.ref, a.ref_pitch = h.data_ptr(), _row_pitch(h, MH), r.data_ptr(), _row_pitch(r, MR)
+    return keep, dev, P, MH, MR, K
+
+
+def edit_distance(hyp, hyp_lens, ref, ref_lens, n_classes, mode='char', is_space=None, rows_per_ref=1, n_hyps=None, totals=None,
+                  workspace=None, out=None, stream=None):
+    """qasr_edit_distance: word / character error counts on the device (k_edit_cut, k_edit, k_edit_totals: three launches on the
+    current stream, no host synchronisation); equal to qasr.edit.edit_host byte for byte.  hyp: a cuda int32 matrix
+    [B * rows_per_ref, max_hyp], ref [B, max_ref] (rows of any pitch), hyp_lens / ref_lens / n_hyps int32 vectors or None (None
+    lengths: the padded rows); is_space: uint8 [n_classes] (word mode); totals: a cuda int64 [16] block the call adds to (None: a
+    zeroed one); `out`: a caller-owned cuda int32 [B * rows_per_ref, 8].  Returns a qasr.edit.EditResult of cuda tensors."""
+    from .edit import ROW_WORDS, TOTAL_WORDS, EditResult
+    who = 'edit_distance'
+    lib = load_library()
+    a = EditArgs()
+    keep, dev, P, MH, MR, K = _edit_fill(who, a, hyp, hyp_lens, ref, ref_lens, n_classes, mode, is_space, rows_per_ref, n_hyps)
     if totals is None:
         totals = torch.zeros(TOTAL_WORDS, device=dev, dtype=torch.int64)
     assert totals.is_cuda and totals.dtype == torch.int64 and tuple(totals.shape) == (TOTAL_WORDS,) and totals.is_contiguous(), \
@@ -841,12 +856,60 @@ def edit_distance(hyp, hyp_lens, ref, ref_lens, n_classes, mode='char', is_space
         out = torch.empty(P, ROW_WORDS, device=dev, dtype=torch.int32)
     assert out.is_cuda and out.dtype == torch.int32 and tuple(out.shape) == (P, ROW_WORDS) and out.is_contiguous(), \
         f'{who}: out must be a cuda int32 [{P}, {ROW_WORDS}]'
-    a.B, a.K, a.C, a.max_hyp, a.max_ref = B, K, int(n_classes), MH, MR
-    a.hyp, a.hyp_pitch, a.ref, a.ref_pitch = h.data_ptr(), _row_pitch(h, MH), r.data_ptr(), _row_pitch(r, MR)
     a.rows, a.totals = out.data_ptr(), totals.data_ptr()
     keep.append(_set_workspace(a, workspace, dev, lib.qasr_edit_workspace_bytes, P, MH, MR, a.mode))
     res = EditResult(out, totals, K)
     return _lattice_launch('qasr_edit_distance', a, dev, stream, res, tuple(keep))
+
+
+class EditTraceArgs(C.Structure):
+    """qasr_edit_trace_args (include/qasr.h)"""
+    _fields_ = ([('struct_size', C.c_uint32)] +
+                [(n, C.c_int32) for n in ('mode', 'B', 'K', 'C', 'max_hyp', 'max_ref', 'pad_')] +
+                [('hyp_pitch', C.c_int64), ('ref_pitch', C.c_int64), ('ops_pitch', C.c_int64)] +
+                [(n, C.c_void_p) for n in ('hyp', 'hyp_lens', 'ref', 'ref_lens', 'n_hyps', 'is_space', 'rows', 'ops', 'n_ops',
+                                           'workspace')] +
+                [('workspace_bytes', C.c_size_t)])
+
+
+def edit_trace_workspace_bytes(P, max_hyp, max_ref, mode):
+    """qasr_edit_trace_workspace_bytes; mode: 'char' / 'word'"""
+    from .edit import check_mode
+    return int(load_library().qasr_edit_trace_workspace_bytes(int(P), int(max_hyp), int(max_ref),
+                                                              check_mode(mode, 'edit_trace_workspace_bytes')))
+
+
+def edit_trace(hyp, hyp_lens, ref, ref_lens, n_classes, mode='char', is_space=None, rows_per_ref=1, n_hyps=None, ops=None,
+               n_ops=None, workspace=None, out=None, stream=None, max_workspace_bytes=1 << 30):
+    """qasr_edit_trace: the edit path on the device (k_edit_cut, k_edit_trace: two launches on the current stream, no host
+    synchronisation); equal to qasr.edit.trace_host byte for byte.  The rows as for edit_distance; ops: a caller-owned cuda uint8
+    [B * rows_per_ref, >= HU + RU] whose ids are contiguous (rows of any pitch), n_ops: a cuda int32 [B * rows_per_ref], `out`: a
+    cuda int32 [B * rows_per_ref, 8].  A shape whose workspace exceeds max_workspace_bytes is refused by name before anything
+    is allocated.  Returns a qasr.edit.TraceResult of cuda tensors."""
+    from .edit import ROW_WORDS, TraceResult, check_trace_workspace, unit_bound
+    who = 'edit_trace'
+    lib = load_library()
+    a = EditTraceArgs()
+    keep, dev, P, MH, MR, K = _edit_fill(who, a, hyp, hyp_lens, ref, ref_lens, n_classes, mode, is_space, rows_per_ref, n_hyps)
+    check_trace_workspace(P, MH, MR, mode, max_workspace_bytes, who)
+    units = unit_bound(MH, a.mode) + unit_bound(MR, a.mode)
+    if ops is None:
+        ops = torch.zeros(P, units, device=dev, dtype=torch.uint8)
+    if not (ops.is_cuda and ops.dtype == torch.uint8 and ops.dim() == 2 and ops.shape[0] == P and ops.shape[1] >= units
+            and ops.stride(1) == 1):
+        raise ValueError(f'{who}: ops must be a cuda uint8 [{P}, >= {units}] (the unit bounds of the two widths)')
+    if n_ops is None:
+        n_ops = torch.empty(P, device=dev, dtype=torch.int32)
+    assert n_ops.is_cuda and n_ops.dtype == torch.int32 and tuple(n_ops.shape) == (P,) and n_ops.is_contiguous(), \
+        f'{who}: n_ops must be a cuda int32 [{P}]'
+    if out is None:
+        out = torch.empty(P, ROW_WORDS, device=dev, dtype=torch.int32)
+    assert out.is_cuda and out.dtype == torch.int32 and tuple(out.shape) == (P, ROW_WORDS) and out.is_contiguous(), \
+        f'{who}: out must be a cuda int32 [{P}, {ROW_WORDS}]'
+    a.rows, a.ops, a.n_ops, a.ops_pitch = out.data_ptr(), ops.data_ptr(), n_ops.data_ptr(), _row_pitch(ops, ops.shape[1])
+    keep.append(_set_workspace(a, workspace, dev, lib.qasr_edit_trace_workspace_bytes, P, MH, MR, a.mode))
+    res = TraceResult(out, ops, n_ops, K)
+    return _lattice_launch('qasr_edit_trace', a, dev, stream, res, tuple(keep))
 
 
 def ctc_align_workspace_bytes(P, T, max_labels):
