@@ -830,6 +830,61 @@ typedef struct qasr_edit_trace_args {
 size_t qasr_edit_trace_workspace_bytes(int P, int max_hyp, int max_ref, int mode);
 int qasr_edit_trace(void* stream, const qasr_edit_trace_args* args);
 
+/* ---- minimum Bayes risk re-ranking of n-best rows -----------------------------------------------------------------------------
+ * Among the K rows the beam kernels leave per utterance - labels i32 [B * K][label_pitch] (max_ids ids each), n_labels i32
+ * [B * K], score i64 [B * K] in 2^-16 nat, n_hyps i32 [B] (optional) - the order by expected edit distance to the other rows,
+ * those weighted by their posterior (MBR_RULES of qasr/mbr.py, which the kernels follow byte for byte).  mode, is_space, units
+ * and the equality of words are qasr_edit_distance's.
+ *   ok i32 [B * K]: 2 an absent row (k >= n_hyps[b]); 1 a present row: length in 0 .. max_ids, every id inside it in [0, C)
+ *   and score > -2^61; 0 otherwise.  Rows with ok != 1 take no part.
+ *   weight i32 [B * K]: with smax the largest score of b's present rows, d = min(smax - score, 2^40),
+ *   x = (d * scale_q + 2^15) >> 16: 0 when x >= 16 << 16, else wtab[x >> 6]; wtab u32 [QASR_MBR_TABLE_ENTRIES],
+ *   wtab[i] = rint(exp(-(64 i) / 2^16) * 2^24) (qasr.mbr.weight_table), in device memory.  0 for rows with ok != 1.
+ *   wsum i64 [B]: the sum of b's weights (0: no present row).
+ *   dist i32 [B][K][K] (optional; NULL: the matrix lives in the workspace): the unit-cost edit distance between rows i and j,
+ *   0 on the diagonal, -1 wherever either row has ok != 1.
+ *   risk i64 [B * K]: sum over present j of weight[j] * dist[i][j]; -1 for rows with ok != 1.
+ *   order i32 [B * K]: b's present rows by (risk ascending, score descending, k ascending), then -1.
+ * Three launches on `stream`: k_edit_cut over the B * K rows, k_mbr_pair<MODE, NC> (one wave per unordered pair of rows of an
+ * utterance, NC = 1 / 4 / 16 units per lane from max_ids, longer rows in strips; none for K = 1) and k_mbr_pick (one work-group
+ * per utterance).  No atomics, plain vector stores, nothing allocated and nothing read on the host, so the call can be
+ * captured behind qasr_ctc_beam[_lm|_boost] and replayed; every output element is written exactly once per call.
+ * workspace: 16-byte aligned device memory of qasr_mbr_workspace_bytes(B, K, max_ids, mode) bytes (0: a shape the call
+ * refuses), one per call in flight.
+ * QASR_ERR_ARG with nothing launched and nothing written: an unknown struct_size, a NULL among labels, n_labels, score, wtab,
+ * weight, wsum, risk, order, ok and workspace, a mode other than the two, is_space NULL in word mode, B or C < 1, K outside
+ * 1 .. QASR_BEAM_MAX_WIDTH, max_ids outside 1 .. QASR_BEAM_MAX_FRAMES, B * K or B * K * (K - 1) / 2 above
+ * QASR_EDIT_MAX_PROBLEMS, scale_q outside 0 .. 16 << 16, wtab_entries != QASR_MBR_TABLE_ENTRIES, label_pitch < max_ids,
+ * workspace_bytes below the query, a workspace not 16-byte aligned, wsum or risk not 8-byte aligned, dist, weight, order or ok
+ * not 4-byte aligned. */
+#define QASR_MBR_TABLE_ENTRIES 16384
+#define QASR_MBR_MAX_SCALE_Q (16 << 16)
+typedef struct qasr_mbr_args {
+  uint32_t struct_size;        /* sizeof of this struct in the caller's header */
+  int32_t mode;                /* QASR_EDIT_CHAR / QASR_EDIT_WORD */
+  int32_t B, K, C;             /* utterances, rows per utterance, classes */
+  int32_t max_ids;             /* ids per row */
+  int32_t scale_q;             /* rint(scale * 2^16), 0 .. QASR_MBR_MAX_SCALE_Q */
+  uint32_t wtab_entries;       /* QASR_MBR_TABLE_ENTRIES */
+  int64_t label_pitch;         /* in int32 */
+  const int32_t* labels;       /* [B * K][label_pitch] */
+  const int32_t* n_labels;     /* [B * K] */
+  const int64_t* score;        /* [B * K] */
+  const int32_t* n_hyps;       /* optional [B] */
+  const uint8_t* is_space;     /* [C]; word mode */
+  const uint32_t* wtab;        /* [wtab_entries] */
+  int32_t* dist;               /* optional [B][K][K] */
+  int32_t* weight;             /* [B * K] */
+  int64_t* wsum;               /* [B] */
+  int64_t* risk;               /* [B * K] */
+  int32_t* order;              /* [B * K] */
+  int32_t* ok;                 /* [B * K] */
+  void* workspace;
+  size_t workspace_bytes;
+} qasr_mbr_args;
+size_t qasr_mbr_workspace_bytes(int B, int K, int max_ids, int mode);
+int qasr_ctc_mbr(void* stream, const qasr_mbr_args* args);
+
 /* ---- audio at any sample rate: rational polyphase resampler and PCM ingest -----------------------------------------------
  * What AudioSegment.__init__ does on the host with librosa.core.resample when target_sr != sample_rate (parts/segment.py:
  * 57-59), as one kernel, k_resample, in front of the mel front-end: int16 PCM (mono or interleaved channels) or float32 at an

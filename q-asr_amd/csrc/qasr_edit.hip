@@ -547,4 +547,16 @@ int launch_edit_trace(hipStream_t s, const qasr_edit_trace_args& a) {
   return QASR_OK;
 }
 
+// k_edit_cut over P hypothesis rows alone (no reference rows: the guard P + B holds with B = 0), for qasr_mbr.hip
+void launch_edit_cut_rows(hipStream_t s, int mode, const int32_t* rows, const int32_t* lens, const int32_t* n_hyps,
+                          const uint8_t* is_space, int2* info, int4* rec, long long pitch, long long HU, int P, int K, int C,
+                          int width) {
+  EditP p{};
+  p.hyp = rows, p.hyp_lens = lens, p.n_hyps = n_hyps, p.is_space = is_space, p.info = info, p.hrec = rec;
+  p.hyp_pitch = pitch, p.HU = HU, p.P = P, p.B = 0, p.K = K, p.C = C, p.max_hyp = width;
+  const dim3 block(EDIT_NT), grid((unsigned)(((long long)P + EDIT_WAVES - 1) / EDIT_WAVES));
+  if (mode == QASR_EDIT_WORD) hipLaunchKernelGGL(k_edit_cut<QASR_EDIT_WORD>, grid, block, 0, s, p);
+  else hipLaunchKernelGGL(k_edit_cut<QASR_EDIT_CHAR>, grid, block, 0, s, p);
+}
+
 }  // namespace qasr

@@ -1584,6 +1584,41 @@ int qasr_edit_trace(void* stream, const qasr_edit_trace_args* a) {
   return launched("edit_trace", launch_edit_trace((hipStream_t)stream, *a));
 }
 
+// ---- minimum Bayes risk re-ranking of n-best rows (k_edit_cut, k_mbr_pair, k_mbr_pick, qasr_mbr.hip): the checks of
+// include/qasr.h, then the launches
+static bool mbr_shape_ok(int B, int K, int max_ids, int mode) {
+  return B >= 1 && K >= 1 && K <= QASR_BEAM_MAX_WIDTH && max_ids >= 1 && max_ids <= QASR_BEAM_MAX_FRAMES &&
+         (long long)B * K <= QASR_EDIT_MAX_PROBLEMS && (long long)B * K * (K - 1) / 2 <= QASR_EDIT_MAX_PROBLEMS &&
+         (mode == QASR_EDIT_CHAR || mode == QASR_EDIT_WORD);
+}
+size_t qasr_mbr_workspace_bytes(int B, int K, int max_ids, int mode) {
+  return mbr_shape_ok(B, K, max_ids, mode) ? mbr_workspace_bytes(B, K, max_ids, mode) : 0;
+}
+int qasr_ctc_mbr(void* stream, const qasr_mbr_args* a) {
+  const char* const who = "ctc_mbr";
+  if (int rc = args_check(who, a)) return rc;
+  if (!a->labels || !a->n_labels || !a->score || !a->wtab || !a->weight || !a->wsum || !a->risk || !a->order || !a->ok || !a->workspace)
+    return fail(QASR_ERR_ARG, "%s: labels, n_labels, score, wtab, weight, wsum, risk, order, ok and workspace are required", who);
+  if (a->mode != QASR_EDIT_CHAR && a->mode != QASR_EDIT_WORD)
+    return fail(QASR_ERR_ARG, "%s: mode %d is neither QASR_EDIT_CHAR nor QASR_EDIT_WORD", who, a->mode);
+  if (a->mode == QASR_EDIT_WORD && !a->is_space) return fail(QASR_ERR_ARG, "%s: word mode needs is_space", who);
+  if (a->C < 1 || !mbr_shape_ok(a->B, a->K, a->max_ids, a->mode))
+    return fail(QASR_ERR_ARG, "%s: B %d or C %d < 1, K %d outside 1 .. %d, max_ids %d outside 1 .. %d, or more than %d rows or pairs",
+                who, a->B, a->C, a->K, QASR_BEAM_MAX_WIDTH, a->max_ids, QASR_BEAM_MAX_FRAMES, QASR_EDIT_MAX_PROBLEMS);
+  if (a->scale_q < 0 || a->scale_q > QASR_MBR_MAX_SCALE_Q)
+    return fail(QASR_ERR_ARG, "%s: scale_q %d is outside 0 .. %d", who, a->scale_q, QASR_MBR_MAX_SCALE_Q);
+  if (a->wtab_entries != QASR_MBR_TABLE_ENTRIES)
+    return fail(QASR_ERR_ARG, "%s: wtab_entries %u is not %d", who, a->wtab_entries, QASR_MBR_TABLE_ENTRIES);
+  if (a->label_pitch < a->max_ids) return fail(QASR_ERR_ARG, "%s: label_pitch %lld < max_ids %d", who, (long long)a->label_pitch, a->max_ids);
+  const size_t need = mbr_workspace_bytes(a->B, a->K, a->max_ids, a->mode);
+  if (a->workspace_bytes < need) return fail(QASR_ERR_ARG, "%s: workspace_bytes %zu < %zu", who, a->workspace_bytes, need);
+  if ((uintptr_t)a->workspace & 15) return fail(QASR_ERR_ARG, "%s: workspace must be 16-byte aligned", who);
+  if (((uintptr_t)a->wsum | (uintptr_t)a->risk) & 7) return fail(QASR_ERR_ARG, "%s: wsum and risk must be 8-byte aligned", who);
+  if (((uintptr_t)a->dist | (uintptr_t)a->weight | (uintptr_t)a->order | (uintptr_t)a->ok) & 3)
+    return fail(QASR_ERR_ARG, "%s: dist, weight, order and ok must be 4-byte aligned", who);
+  return launched(who, launch_mbr((hipStream_t)stream, *a));
+}
+
 // ---- polyphase resampler (k_resample, qasr_resample.hip): host-only validation of a packed table (qasr/resample.py states
 // the layout), then the checks of include/qasr.h and one launch
 static long long gcd_ll(long long a, long long b) {

@@ -198,6 +198,13 @@ int launch_edit(hipStream_t s, const qasr_edit_args& a);
 // the edit path (k_edit_cut, k_edit_trace); checked by qasr_edit_trace
 size_t edit_trace_workspace_bytes(long long P, int max_hyp, int max_ref, int mode);
 int launch_edit_trace(hipStream_t s, const qasr_edit_trace_args& a);
+// k_edit_cut over P n-best rows without reference rows: (units, state) per row into info, in word mode the words into rec [P][HU]
+void launch_edit_cut_rows(hipStream_t s, int mode, const int32_t* rows, const int32_t* lens, const int32_t* n_hyps,
+                          const uint8_t* is_space, int2* info, int4* rec, long long pitch, long long HU, int P, int K, int C,
+                          int width);
+// qasr_mbr.hip: minimum Bayes risk re-ranking of n-best rows (k_edit_cut, k_mbr_pair, k_mbr_pick); checked by qasr_ctc_mbr
+size_t mbr_workspace_bytes(int B, int K, int max_ids, int mode);
+int launch_mbr(hipStream_t s, const qasr_mbr_args& a);
 // qasr_resample.hip: rational polyphase resampler (k_resample); the arguments are checked by qasr_resample
 int launch_resample(hipStream_t s, const qasr_resample_args& a);
 // qasr_longform.hip: windows of long recordings cut (k_cut) and stitched (k_stitch); the arguments are checked by the callers

@@ -90,7 +90,16 @@ def main():
                         "every utterance).  With --stream_chunk_s or --window_s the hypotheses exist as strings and are scored "
                         "through qasr.edit.error_counts.  --dump_hyps still reads the strings")
     p.add_argument("--n_best", type=int, default=None, metavar='K',
-                   help="(extension, needs --device_wer and --beam_width) rows of the beam scored per utterance for `oracle WER:`")
+                   help="(extension, needs --beam_width and --device_wer or --mbr) rows of the beam scored per utterance for "
+                        "`oracle WER:`, and the list --mbr re-ranks")
+    p.add_argument("--mbr", type=str, default=None, choices=['word', 'char'],
+                   help="(extension, needs --beam_width W --n_best K, K >= 2) minimum Bayes risk re-ranking of every utterance's "
+                        "K rows on the device (qasr.mbr.MBR_RULES; EncDecCTCModel.decode(mbr=)): the transcripts are the picks, the "
+                        "rows with the fewest expected word (character) errors against the rest of the list.  With --device_wer "
+                        "`WER:` stays the beam's first row and a line `MBR WER:` is printed between `WER:` and `oracle WER:`; "
+                        "--dump_hyps gains `posterior` and `mbr_risk`.  Not with --stream_chunk_s or --window_s")
+    p.add_argument("--mbr_scale", type=float, default=None, help="(extension, needs --mbr) the weight of the scores in the rows' "
+                        "posteriors, 0 .. 16 (default 1.0, untuned)")
     p.add_argument("--cer", action='store_true', help="(extension) character error rate: WER is computed over characters")
     p.add_argument("--alignments", type=str, default=None, metavar='OUT',
                    help="(extension, needs --device_wer) which words were wrong: the edit path of every utterance's best "
@@ -205,8 +214,17 @@ def main():
         p.error('--overlap_s needs --window_s')
     if args.alignments is not None and not args.device_wer:
         p.error('--alignments OUT needs --device_wer')
-    if args.n_best is not None and (not args.device_wer or args.beam_width is None or not 1 <= args.n_best <= args.beam_width):
-        p.error('--n_best K needs --device_wer and --beam_width W, 1 <= K <= W')
+    if args.mbr is not None and args.beam_width is None:
+        p.error('--mbr needs --beam_width W --n_best K (the greedy path has one hypothesis, nothing to re-rank)')
+    if args.mbr is not None and (args.n_best is None or args.n_best < 2):
+        p.error('--mbr needs --n_best K with K >= 2 (a list of one row has nothing to re-rank)')
+    if args.mbr is not None and (args.stream_chunk_s is not None or args.window_s is not None):
+        p.error('--mbr does not go with --stream_chunk_s or --window_s: MBR re-ranking is built for decode() alone')
+    if args.mbr_scale is not None and (args.mbr is None or not 0.0 <= args.mbr_scale <= 16.0):
+        p.error('--mbr_scale needs --mbr and a value in 0 .. 16')
+    if args.n_best is not None and ((not args.device_wer and args.mbr is None) or args.beam_width is None
+                                    or not 1 <= args.n_best <= args.beam_width):
+        p.error('--n_best K needs --beam_width W, 1 <= K <= W, and --device_wer or --mbr')
     if args.star_token is not None and (args.align is None or args.shuffle):
         p.error('--star_token needs --align and does not go with --shuffle: the texts are read from the manifest in order')
     if args.star_between and (args.align is None or args.window_s is None):
@@ -306,6 +324,8 @@ def main():
     dev_counts = [0] * 7                                     # --device_wer beyond the greedy path: errors, S, D, I, ref, hyp, oracle
     need_text = not args.device_wer or bool(args.dump_hyps)  # the strings are read only where something needs them
     hyps, refs, words, utt_scores, beam_scores, lm_scores, boost_scores = [], [], [], [], [], [], []
+    mbr_kw = dict(mbr=args.mbr, mbr_scale=1.0 if args.mbr_scale is None else args.mbr_scale) if args.mbr is not None else {}
+    mbr_errors, posteriors, mbr_risks = 0, [], []            # --mbr: the picks' errors (--device_wer), their posterior and expected errors
     lm_kw = dict(lm=args.lm_path, alpha=alpha, beta=beta) if args.lm_path is not None else {}
     if args.boost_file is not None:                          # compiled once for the run: the file does not change per batch
         from qasr import boost as qboost
@@ -407,11 +427,16 @@ def main():
             if args.device_wer:                              # ... and k_edit behind them: only the counts are read back
                 rep = asr_model.error_rate(input_signal=signal, input_signal_length=batch[1], targets=batch[2], use_cer=args.cer,
                                            beam_width=args.beam_width, n_best=args.n_best or 1,
-                                           alignments=args.alignments is not None, **lm_kw, **rate_kw)
+                                           alignments=args.alignments is not None, **lm_kw, **rate_kw, **mbr_kw)
                 _add_report(dev_counts, rep)
+                mbr_errors += rep.mbr_total.errors if mbr_kw else 0
                 listed += rep.alignments or []               # --alignments: k_edit_trace over the best rows
             for h in (asr_model.decode(input_signal=signal, input_signal_length=batch[1], beam_width=args.beam_width,
-                                       **lm_kw, **rate_kw) if need_text else ()):
+                                       **lm_kw, **rate_kw, **(dict(mbr_kw, n_best=args.n_best) if mbr_kw else {})) if need_text else ()):
+                if mbr_kw:                                   # the list in MBR order: the transcript is the pick
+                    h = h[0]
+                    posteriors.append(h.posterior)
+                    mbr_risks.append(h.mbr_risk)
                 hyps.append(h.text)
                 beam_scores.append(h.utt_score)
                 lm_scores.append(h.lm_score)
@@ -519,6 +544,8 @@ def main():
     print('WER:', wer_value)
     if args.device_wer:
         print('S / D / I:', dev_counts[1], '/', dev_counts[2], '/', dev_counts[3])
+        if args.mbr is not None:
+            print('MBR WER:', 1.0 * mbr_errors / dev_counts[4] if dev_counts[4] != 0 else float('inf'))
         if args.beam_width is not None and args.n_best and args.stream_chunk_s is None and args.window_s is None:
             print('oracle WER:', 1.0 * dev_counts[6] / dev_counts[4] if dev_counts[4] != 0 else float('inf'))
     if args.dump_hyps:
@@ -527,6 +554,10 @@ def main():
             extra = dict(words=words, utt_score=utt_scores) if args.timestamps else {}
             if args.beam_width is not None:
                 extra.update(beam_width=args.beam_width, beam_score=beam_scores)
+            if args.mbr is not None:
+                extra.update(mbr=args.mbr, mbr_scale=mbr_kw['mbr_scale'], n_best=args.n_best, posterior=posteriors, mbr_risk=mbr_risks)
+                if args.device_wer:                          # `wer` is the beam's first row there; the hypotheses are the picks
+                    extra.update(mbr_wer=1.0 * mbr_errors / dev_counts[4] if dev_counts[4] != 0 else float('inf'))
             if args.lm_path is not None:
                 extra.update(lm_path=args.lm_path, alpha=alpha, beta=beta, lm_score=lm_scores)
             if args.boost_file is not None:

@@ -476,7 +476,7 @@ class EncDecCTCModel(nn.Module):
     @torch.no_grad()
     def decode(self, input_signal=None, input_signal_length=None, processed_signal=None, processed_signal_length=None,
                beam_width=None, n_best=1, cutoff_top_n=40, lm=None, alpha=0.0, beta=0.0, timestamps=False, boost=None,
-               boost_weight=1.0, sample_rate=None, channels=1, posteriors=False, _rows=False):
+               boost_weight=1.0, sample_rate=None, channels=1, posteriors=False, _rows=False, mbr=None, mbr_scale=1.0):
         """Greedy CTC hypotheses of one batch (an extension of the reference's API): List[qasr.ctc.Hypothesis] with the
         text, every label's start / end time and confidence (best frame log-probability of its run), word groups and the
         log-probability of the greedy path.  Decoding stops at each utterance's encoded length.  On the static engine the
@@ -509,8 +509,17 @@ class EncDecCTCModel(nn.Module):
         on the host modules).  utt_score then includes the boosting's share, which the hypotheses also carry as
         boost_score.  The list changes per call: it is compiled and packed here, per call.
 
+        mbr='word' | 'char' (needs beam_width and n_best >= 2) re-ranks every utterance's n-best list by minimum Bayes risk
+        (qasr.mbr.MBR_RULES): the row with the fewest expected word (character) errors against the other rows, those weighted
+        by exp(mbr_scale * score), comes first.  qasr_ctc_mbr runs behind the beam chain on the same stream over the beam's
+        buffers as they lie (the NumPy twin for CPU tensors and the host modules); the lists come back in MBR order and
+        every hypothesis carries posterior, mbr_risk (its expected errors) and beam_rank (its place in the beam's list).
+        mbr_scale: 0 .. 16; 1.0 is a starting point, not a tuned value.  timestamps / posteriors align the rows as they lie;
+        the lists are re-ordered afterwards.  lm, boost and sample_rate compose unchanged.
+
         sample_rate / channels: as for forward() - PCM at another rate is resampled first; times stay seconds."""
         from qasr import ctc as qctc
+        mbr = self._mbr_args('decode', mbr, mbr_scale, beam_width, n_best)                            # refused before anything runs
         input_signal, input_signal_length = self._resample_in(input_signal, input_signal_length, sample_rate, channels)
         if lm is not None and beam_width is None:
             raise ValueError('decode: lm needs beam_width (the greedy collapse has no language model)')
@@ -531,7 +540,7 @@ class EncDecCTCModel(nn.Module):
                     raise ValueError(f'decode: {e}') from None
             return self._beam_decode(self._forward(input_signal, input_signal_length, processed_signal, processed_signal_length),
                                      beam_width, n_best, cutoff_top_n, lm, alpha, beta, bool(timestamps), boost, bool(posteriors),
-                                     rows=_rows)
+                                     rows=_rows, mbr=mbr)
         res = self._forward(input_signal, input_signal_length, processed_signal, processed_signal_length, decode=True)
         if _rows:                            # error_rate: the CtcResult as it lies, nothing turned into strings
             return res
@@ -604,7 +613,7 @@ class EncDecCTCModel(nn.Module):
     @torch.no_grad()
     def decode_long(self, input_signal, input_signal_length, window_s=30.0, overlap_s=4.0, guard_s=1.0, batch_size=32,
                     seam='blank', beam_width=None, n_best=1, cutoff_top_n=40, lm=None, alpha=0.0, beta=0.0, boost=None,
-                    boost_weight=1.0, sample_rate=None, channels=1, _rows=False):
+                    boost_weight=1.0, sample_rate=None, channels=1, _rows=False, mbr=None):
         """Hypotheses of long recordings (an extension; buffered inference on the device): input_signal [R, S] with
         input_signal_length samples each -> List[qasr.ctc.Hypothesis], one per recording, times in seconds of the recording,
         seams_s = the times at which neighbouring windows were joined (None for a recording of one window: its hypothesis
@@ -628,6 +637,10 @@ class EncDecCTCModel(nn.Module):
         from qasr import beam as qbeam, ctc as qctc, engine as qengine
         if input_signal is None or input_signal_length is None:
             raise ValueError('decode_long: input_signal and input_signal_length are required')
+        if mbr is not None:
+            raise ValueError('decode_long: mbr is not built for long recordings (stitched rows make the pair workspace a separate '
+                             'question; see "Minimum Bayes risk re-ranking" in the README): re-rank decode()\'s lists, or '
+                             'qasr.mbr.rerank_texts over the texts')
         if lm is not None and beam_width is None:
             raise ValueError('decode_long: lm needs beam_width (the greedy collapse has no language model)')
         if boost is not None and beam_width is None:
@@ -745,6 +758,14 @@ class EncDecCTCModel(nn.Module):
                                   n_hyps=host(n_hyps))
             rows, totals = out.rows, out.totals
         rep = qedit.report_of(rows, totals, K)
+        mres = getattr(res, 'mbr', None)
+        if mres is not None:                 # the counts of the MBR picks: the rows read back above, and order[:, 0]
+            pick = mres.order[:, 0]
+            pick = (pick.cpu().numpy() if torch.is_tensor(pick) else np.asarray(pick)).astype(np.int64)
+            r = np.asarray(rows).reshape(n, K, -1)[np.arange(n), np.maximum(pick, 0)].astype(np.int64)
+            r = r[(pick >= 0) & (r[:, 6] == 1)]
+            rep.mbr_total = qedit.counts_of(*(int(r[:, c].sum()) for c in (0, 1, 2, 3, 4, 5)))
+            rep.mbr_pick = pick.tolist()
         if alignments:
             hyp0, hl0 = (hyp, hl) if K == 1 else (labels[:, 0], n_labels[:, 0])          # the k = 0 rows, where they lie
             n0 = None if n_hyps is None else (n_hyps.clamp(max=1) if torch.is_tensor(n_hyps) else np.minimum(n_hyps, 1))
@@ -774,7 +795,10 @@ class EncDecCTCModel(nn.Module):
         dynamic path, and through the NumPy twin with the host modules or CPU tensors.  Word mode needs a vocabulary of
         single characters.  alignments=True: the report also carries one qasr.ctc.Alignment per utterance for its best row
         (k_edit_trace, qasr.edit.TRACE_RULES; ops, n_ops and the label rows are read back); a batch whose back-pointer plane
-        would exceed max_workspace_bytes is refused by name."""
+        would exceed max_workspace_bytes is refused by name.  mbr='word' | 'char' with mbr_scale, as decode() takes them: the
+        report also carries mbr_total, the counts of every utterance's MBR pick (qasr.mbr.MBR_RULES), and mbr_pick - so one call
+        tells how wrong the first row is (total), the reference-free pick (mbr_total) and the best row of the list
+        (oracle_errors)."""
         for k in ('timestamps', 'posteriors', '_rows'):
             if k in decode_args:
                 raise ValueError(f'error_rate: {k} is not an argument of the error rate')
@@ -1093,8 +1117,58 @@ class EncDecCTCModel(nn.Module):
                              f'{len(self.decoder.vocabulary)}')
         return lm
 
+    def _mbr_args(self, who, mbr, mbr_scale, beam_width, n_best):
+        """decode(mbr=)'s arguments, refused by name before anything runs: None without mbr, else (mode, scale)"""
+        if mbr is None:
+            return None
+        from qasr import mbr as qmbr
+        if mbr not in ('word', 'char'):
+            raise ValueError(f"{who}: mbr must be None, 'word' or 'char', got {mbr!r}")
+        if beam_width is None:
+            raise ValueError(f'{who}: mbr needs beam_width (the greedy collapse has one hypothesis, nothing to re-rank)')
+        if int(n_best) < 2:
+            raise ValueError(f'{who}: mbr needs n_best >= 2 (a list of one row has nothing to re-rank), got {n_best}')
+        try:
+            qmbr.check_scale(mbr_scale, who)
+        except ValueError as e:
+            raise ValueError(str(e)) from None
+        if mbr == 'word':
+            from qasr import edit as qedit
+            qedit.space_mask(list(self.decoder.vocabulary), who)
+        return mbr, float(mbr_scale)
+
+    def _mbr_rows(self, res, mbr):
+        """qasr_ctc_mbr (the twin for host arrays) behind a BeamResult, over its buffers as they lie; nothing is read back"""
+        from qasr import edit as qedit, mbr as qmbr
+        mode, scale = mbr
+        vocab = list(self.decoder.vocabulary)
+        mask = qedit.space_mask(vocab, 'decode') if mode == 'word' else None
+        if torch.is_tensor(res.labels) and res.labels.is_cuda:
+            sp = None if mask is None else torch.from_numpy(mask).to(res.labels.device)
+            return qmbr.mbr_device(res.labels, res.n_labels, res.score, res.n_hyps, len(vocab), mode=mode, is_space=sp, scale=scale)
+        host = lambda t: t.numpy() if torch.is_tensor(t) else t
+        return qmbr.mbr_host(host(res.labels), host(res.n_labels), host(res.score), host(res.n_hyps), len(vocab), mode=mode,
+                             is_space=mask, scale=scale)
+
+    @staticmethod
+    def _mbr_order(hyps, mres):
+        """the lists in MBR order, every hypothesis with posterior, mbr_risk and beam_rank; weight, wsum, risk and order are read"""
+        from qasr import mbr as qmbr
+        cpu = lambda t: t.cpu().numpy() if torch.is_tensor(t) else t
+        mres = qmbr.MbrResult(None, cpu(mres.weight), cpu(mres.wsum), cpu(mres.risk), cpu(mres.order), cpu(mres.ok))
+        ee, post = qmbr.expected_errors(mres)
+        out = []
+        for b, row in enumerate(hyps):
+            order = [int(k) for k in mres.order[b] if 0 <= k < len(row)]
+            if len(order) != len(row):
+                raise RuntimeError(f'decode: the re-ranking refused a row of utterance {b} that the beam wrote')
+            for k in order:
+                row[k].posterior, row[k].mbr_risk, row[k].beam_rank = float(post[b, k]), float(ee[b, k]), k
+            out.append([row[k] for k in order])
+        return out
+
     def _beam_decode(self, fwd, beam_width, n_best, cutoff_top_n, lm=None, alpha=0.0, beta=0.0, timestamps=False, boost=None,
-                     posteriors=False, rows=False):
+                     posteriors=False, rows=False, mbr=None):
         """decode(beam_width=) behind any path's (log_probs, encoded lengths, tokens); the arguments passed _beam_args"""
         from qasr import beam as qbeam
         log_probs, enc_len = fwd[0], fwd[1]
@@ -1106,11 +1180,16 @@ class EncDecCTCModel(nn.Module):
         else:
             res = qbeam.search_host(log_probs.float().numpy(), enc_len.numpy(), blank, beam_width, n_best, cutoff_top_n, lm,
                                     alpha, beta, boost)
-        if rows:                             # error_rate: the BeamResult as it lies
+        mres = None if mbr is None else self._mbr_rows(res, mbr)     # behind the beam chain, on the same stream
+        if rows:                             # error_rate: the BeamResult as it lies (with mbr: its MbrResult beside it)
+            if mres is not None:
+                res.mbr = mres
             return res
         hyps = qbeam.to_hypotheses(res, self.decoder.vocabulary)
         if timestamps:
             self._beam_timestamps(hyps, res, log_probs, enc_len, blank, n_best, posteriors)
+        if mres is not None:
+            hyps = self._mbr_order(hyps, mres)
         return hyps if n_best > 1 else [h[0] for h in hyps]          # a beam over real candidates never dies: h[0] exists
 
     def _beam_timestamps(self, hyps, res, log_probs, enc_len, blank, n_best, posteriors=False):

@@ -29,10 +29,13 @@ class BeamSearchDecoderWithLM(nn.Module):
     input_tensor: True for a tensor [B, T, D] of log-probabilities with lengths, False for a list of [T_i, D] arrays of
     probabilities, as the reference passes them on.  boost (keyword-only, an extension): a list of phrases (text or
     (text, weight); boost_weight nats per label where a phrase has none) or a qasr.boost.PhraseSet: phrase boosting by
-    qasr.boost.BOOST_RULES (k_beam_boost on the device), with or without lm_path."""
+    qasr.boost.BOOST_RULES (k_beam_boost on the device), with or without lm_path.  mbr (keyword-only, an extension): 'word' |
+    'char' returns every list in minimum Bayes risk order (qasr.mbr.MBR_RULES; qasr_ctc_mbr behind the beam on the device,
+    the twin otherwise) - the row with the fewest expected word (character) errors against the rest of its list first, the rows
+    weighted by exp(mbr_scale * score), mbr_scale 0 .. 16; the tuples stay (log-probability, string).  Needs beam_width >= 2."""
 
     def __init__(self, vocab, beam_width, alpha, beta, lm_path, num_cpus, cutoff_prob=1.0, cutoff_top_n=40,
-                 input_tensor=False, *, boost=None, boost_weight=1.0):
+                 input_tensor=False, *, boost=None, boost_weight=1.0, mbr=None, mbr_scale=1.0):
         if float(cutoff_prob) != 1.0:
             raise ValueError(f'BeamSearchDecoderWithLM: cutoff_prob must be 1.0 (no cumulative pruning), got {cutoff_prob}')
         if not 1 <= int(beam_width) <= qbeam.MAX_W:
@@ -56,7 +59,17 @@ class BeamSearchDecoderWithLM(nn.Module):
                 phrases = qboost.as_phrase_set(boost, list(vocab), boost_weight)
             except ValueError as e:
                 raise ValueError(f'BeamSearchDecoderWithLM: {e}') from None
+        mask = None
+        if mbr is not None:                         # (keyword-only, likewise)
+            from qasr import edit as qedit, mbr as qmbr
+            if mbr not in ('word', 'char'):
+                raise ValueError(f"BeamSearchDecoderWithLM: mbr must be None, 'word' or 'char', got {mbr!r}")
+            if int(beam_width) < 2:
+                raise ValueError('BeamSearchDecoderWithLM: mbr needs beam_width >= 2 (a list of one row has nothing to re-rank)')
+            qmbr.check_scale(mbr_scale, 'BeamSearchDecoderWithLM')
+            mask = qedit.space_mask(list(vocab), 'BeamSearchDecoderWithLM') if mbr == 'word' else None
         super().__init__()
+        self.mbr, self.mbr_scale, self.mbr_mask = mbr, float(mbr_scale), mask
         self.scorer = scorer
         self.phrases = phrases
         self.vocab = list(vocab)
@@ -93,4 +106,17 @@ class BeamSearchDecoderWithLM(nn.Module):
                 for i, r in enumerate(rows):
                     lp[i, :r.shape[0]] = np.log(r)              # a probability of 0 becomes the fixed-point floor
             res = self.search(torch.from_numpy(lp), torch.tensor([r.shape[0] for r in rows], dtype=torch.int64))
-        return [[(h.utt_score, h.text) for h in hyps] for hyps in qbeam.to_hypotheses(res, self.vocab)]
+        lists = qbeam.to_hypotheses(res, self.vocab)
+        if self.mbr is not None:
+            lists = [[row[k] for k in order if 0 <= k < len(row)] for row, order in zip(lists, self._mbr_order(res))]
+        return [[(h.utt_score, h.text) for h in hyps] for hyps in lists]
+
+    def _mbr_order(self, res):
+        """order [B][n_best] of MBR_RULES over a BeamResult where it lies (cuda: qasr_ctc_mbr, cpu: the twin)"""
+        from qasr import mbr as qmbr
+        if torch.is_tensor(res.labels) and res.labels.is_cuda:
+            sp = None if self.mbr_mask is None else torch.from_numpy(self.mbr_mask).to(res.labels.device)
+            return qmbr.mbr_device(res.labels, res.n_labels, res.score, res.n_hyps, len(self.vocab), mode=self.mbr, is_space=sp,
+                                   scale=self.mbr_scale).order.cpu().tolist()
+        return qmbr.mbr_host(res.labels, res.n_labels, res.score, res.n_hyps, len(self.vocab), mode=self.mbr, is_space=self.mbr_mask,
+                             scale=self.mbr_scale).order.tolist()

@@ -13,7 +13,7 @@ SOURCES = ['qasr_kernels.hip', 'qasr_sep.hip', 'qasr_sep_t32.hip', 'qasr_sep_t32
            'qasr_sep_t64_dbg.hip', 'qasr_sep_t128.hip', 'qasr_sep2_t32.hip', 'qasr_sep2_t32_dbg.hip', 'qasr_sep2_t64.hip', 'qasr_sep2_t64_dbg.hip', 'qasr_sep2_t128.hip', 'qasr_sep2_t128_dbg.hip', 'qasr_sep2s_t32.hip', 'qasr_sep2s_t64.hip', 'qasr_sep2s_t128.hip', 'qasr_sep2p_t128.hip', 'qasr_dense2.hip',
            'qasr_engine.hip', 'qasr_blob_check.cpp', 'qasr_frontend.hip', 'qasr_calib.hip', 'qasr_dynamic.hip', 'qasr_decoder.hip', 'qasr_decoder_wide.hip', 'qasr_stem.hip', 'qasr_ctc.hip', 'qasr_ragged.hip', 'qasr_beam.hip', 'qasr_align.hip', 'qasr_align_band.hip', 'qasr_star.hip', 'qasr_spot.hip', 'qasr_post.hip', 'qasr_post_band.hip',
            'qasr_beam_boost.hip', 'qasr_resample.hip', 'qasr_longform.hip', 'qasr_stream.hip', 'qasr_stream_rs.hip', 'qasr_stream_beam.hip',
-           'qasr_stream_ep.hip', 'qasr_stream_beam_boost.hip', 'qasr_stream_beam_ep.hip', 'qasr_stream_spot.hip', 'qasr_edit.hip']
+           'qasr_stream_ep.hip', 'qasr_stream_beam_boost.hip', 'qasr_stream_beam_ep.hip', 'qasr_stream_spot.hip', 'qasr_edit.hip', 'qasr_mbr.hip']
 
 
 def _headers():

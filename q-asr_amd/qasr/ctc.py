@@ -96,6 +96,10 @@ class Hypothesis:
     post_min: Optional[List[float]] = None  # per label: the posterior at its least certain frame
     word_post: Optional[List[float]] = None  # one per entry of words: the mean over the frames of the word's labels
     frame_post: Optional[object] = None     # float32 [frames]: the log-posterior (nats) of the path's state at every frame
+    # decode(mbr=) (qasr.mbr.MBR_RULES): the n-best list in minimum Bayes risk order
+    posterior: Optional[float] = None       # the row's normalised weight among the rows of its list, 0 .. 1
+    mbr_risk: Optional[float] = None        # its expected number of errors against the list, in the mode's units (words / characters)
+    beam_rank: Optional[int] = None         # its place in the beam's list (0: the row with the best path score)
     seams_s: Optional[List[float]] = None   # decode_long (qasr.longform): the times at which neighbouring windows were joined
 
 
@@ -142,6 +146,8 @@ class ErrorReport:
     per_utterance: List[ErrorCounts]
     invalid: int
     alignments: Optional[List[Optional['Alignment']]] = None   # alignments=True: one per utterance for its best row (None: not scored)
+    mbr_total: Optional[ErrorCounts] = None                    # error_rate(mbr=): the counts of every utterance's MBR pick, summed
+    mbr_pick: Optional[List[int]] = None                       # error_rate(mbr=): the row picked per utterance (-1: no present row)
 
 
 @dataclass

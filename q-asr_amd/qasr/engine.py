@@ -29,7 +29,7 @@ SYMBOLS = ['qasr_blob_check', 'qasr_engine_create', 'qasr_engine_create_ex', 'qa
            'qasr_stream_beam_state_bytes', 'qasr_stream_beam', 'qasr_stream_ep_state_bytes', 'qasr_stream_endpoint',
            'qasr_stream_beam_boost_state_bytes', 'qasr_stream_beam_boost', 'qasr_stream_beam_ep',
            'qasr_stream_spot_state_bytes', 'qasr_stream_spot', 'qasr_edit_workspace_bytes', 'qasr_edit_distance',
-           'qasr_edit_trace_workspace_bytes', 'qasr_edit_trace',
+           'qasr_edit_trace_workspace_bytes', 'qasr_edit_trace', 'qasr_mbr_workspace_bytes', 'qasr_ctc_mbr',
            'qasr_last_error', 'qasr_version']
 
 _lib = None
@@ -248,6 +248,10 @@ def load_library():
         lib.qasr_edit_trace_workspace_bytes.argtypes = [i32, i32, i32, i32]
         lib.qasr_edit_trace_workspace_bytes.restype = sz
         lib.qasr_edit_trace.argtypes = [vp, C.POINTER(EditTraceArgs)]
+    if hasattr(lib, 'qasr_ctc_mbr'):            # (likewise)
+        lib.qasr_mbr_workspace_bytes.argtypes = [i32, i32, i32, i32]
+        lib.qasr_mbr_workspace_bytes.restype = sz
+        lib.qasr_ctc_mbr.argtypes = [vp, C.POINTER(MbrArgs)]
     lib.qasr_debug_prof.argtypes = [vp]
     lib.qasr_debug_timeline.argtypes = [vp, sz]
     lib.qasr_sep_layer.argtypes = [vp, C.POINTER(SepLayerArgs), C.c_char_p, sz]
@@ -860,6 +864,95 @@ def edit_distance(hyp, hyp_lens, ref, ref_lens, n_classes, mode='char', is_space
     keep.append(_set_workspace(a, workspace, dev, lib.qasr_edit_workspace_bytes, P, MH, MR, a.mode))
     res = EditResult(out, totals, K)
     return _lattice_launch('qasr_edit_distance', a, dev, stream, res, tuple(keep))
+
+
+class MbrArgs(C.Structure):
+    """qasr_mbr_args (include/qasr.h)"""
+    _fields_ = ([('struct_size', C.c_uint32)] +
+                [(n, C.c_int32) for n in ('mode', 'B', 'K', 'C', 'max_ids', 'scale_q')] +
+                [('wtab_entries', C.c_uint32), ('label_pitch', C.c_int64)] +
+                [(n, C.c_void_p) for n in ('labels', 'n_labels', 'score', 'n_hyps', 'is_space', 'wtab', 'dist', 'weight', 'wsum',
+                                           'risk', 'order', 'ok', 'workspace')] +
+                [('workspace_bytes', C.c_size_t)])
+
+
+_mbr_tables = {}
+
+
+def mbr_table_device(device):
+    """qasr.mbr.weight_table() on `device` (its 16384 u32 entries as an int32 tensor), uploaded once per device, as
+    lae_table_device: the first mbr_rerank of a device must run outside a stream capture (or call this first)."""
+    from . import mbr
+    dev = torch.device(device)
+    if dev.type == 'cuda' and dev.index is None:
+        dev = torch.device('cuda', torch.cuda.current_device())
+    t = _mbr_tables.get(dev)
+    if t is None:
+        t = _mbr_tables[dev] = torch.from_numpy(mbr.weight_table().view(np.int32).copy()).to(dev)
+    return t
+
+
+def mbr_workspace_bytes(B, K, max_ids, mode):
+    """qasr_mbr_workspace_bytes; mode: 'char' / 'word'"""
+    from .edit import check_mode
+    return int(load_library().qasr_mbr_workspace_bytes(int(B), int(K), int(max_ids), check_mode(mode, 'mbr_workspace_bytes')))
+
+
+def mbr_rerank(labels, n_labels, score, n_hyps, n_classes, mode='word', is_space=None, scale=1.0, wtab=None, dist=None,
+               workspace=None, out=None, stream=None):
+    """qasr_ctc_mbr: minimum Bayes risk order of n-best rows on the device (k_edit_cut, k_mbr_pair, k_mbr_pick: three launches on
+    the current stream, no host synchronisation); equal to qasr.mbr.mbr_host byte for byte.  The beam's tensors as they lie, no
+    copy: labels cuda int32 [B, K, L] (ids contiguous, rows of one pitch >= L, utterances K rows apart), n_labels int32 [B, K],
+    score int64 [B, K], n_hyps int32 [B] or None; is_space uint8 [n_classes] (word mode); wtab: the weight table on the device
+    (None: mbr_table_device); dist: True for the matrix [B, K, K] in the result (None: it stays in the workspace); `out`: a
+    caller-owned qasr.mbr.MbrResult of cuda tensors.  Returns an MbrResult of cuda tensors."""
+    from .edit import check_mode
+    from .mbr import WTAB_ENTRIES, MbrResult, check_scale, check_shape
+    who, i32, i64 = 'mbr_rerank', torch.int32, torch.int64
+    lib = load_library()
+    a = MbrArgs()
+    a.struct_size, a.mode = C.sizeof(MbrArgs), check_mode(mode, who)
+    assert labels.is_cuda and labels.dim() == 3 and labels.dtype == i32, f'{who}: labels must be a cuda int32 tensor [B, K, L]'
+    B, K, L = labels.shape
+    check_shape(B, K, L, who)
+    if int(n_classes) < 1:
+        raise ValueError(f'{who}: n_classes must be at least 1, got {n_classes}')
+    pitch = labels.stride(1) if K > 1 else max(labels.stride(1), L)
+    if not ((L == 1 or labels.stride(2) == 1) and pitch >= L and (B == 1 or labels.stride(0) == K * pitch)):
+        labels = labels.contiguous()
+        pitch = L
+    dev = labels.device
+    a.scale_q = check_scale(scale, who)
+    keep = [labels]
+    for name, v, shape, dt in (('n_labels', n_labels, (B, K), i32), ('score', score, (B, K), i64), ('n_hyps', n_hyps, (B,), i32)):
+        if v is None and name == 'n_hyps':
+            continue
+        if v is None or tuple(v.shape) != shape:
+            raise ValueError(f'{who}: {name} must be {list(shape)}')
+        v = v.to(device=dev, dtype=dt).contiguous()
+        keep.append(v)
+        setattr(a, name, v.data_ptr())
+    if a.mode == 1:
+        if is_space is None:
+            raise ValueError(f'{who}: word mode needs is_space')
+        if tuple(is_space.shape) != (int(n_classes),):
+            raise ValueError(f'{who}: is_space must have one entry per class ({int(n_classes)}), got shape {tuple(is_space.shape)}')
+        sp = is_space.to(device=dev, dtype=torch.uint8).contiguous()
+        keep.append(sp)
+        a.is_space = sp.data_ptr()
+    tab = mbr_table_device(dev) if wtab is None else wtab
+    assert tab.is_cuda and tab.is_contiguous() and tab.numel() == WTAB_ENTRIES and tab.element_size() == 4, \
+        f'{who}: wtab must be a cuda tensor of {WTAB_ENTRIES} 32-bit entries'
+    keep.append(tab)
+    if out is None:
+        new = lambda dt, *shape: torch.empty(*shape, device=dev, dtype=dt)
+        out = MbrResult(new(i32, B, K, K) if dist else None, new(i32, B, K), new(i64, B), new(i64, B, K), new(i32, B, K), new(i32, B, K))
+    _set_outputs(who, a, out, (('dist', i32, (B, K, K), True), ('weight', i32, (B, K), False), ('wsum', i64, (B,), False),
+                               ('risk', i64, (B, K), False), ('order', i32, (B, K), False), ('ok', i32, (B, K), False)))
+    a.B, a.K, a.C, a.max_ids, a.label_pitch = B, K, int(n_classes), L, pitch
+    a.labels, a.wtab, a.wtab_entries = labels.data_ptr(), tab.data_ptr(), WTAB_ENTRIES
+    keep.append(_set_workspace(a, workspace, dev, lib.qasr_mbr_workspace_bytes, B, K, L, a.mode))
+    return _lattice_launch('qasr_ctc_mbr', a, dev, stream, out, tuple(keep))
 
 
 class EditTraceArgs(C.Structure):
